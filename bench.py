@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json's metric on its configuration, measured on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]     (N>1: launched by torch.distributed.run, one rank per GPU)
 
 A "step" is one ConvVAE SGD step (forward, ELBO, backward, gradient all-reduce when N>1, fused TF-Adam) on one minibatch
 of 512 synthetic 160x80x3 frames PER GPU in bf16 (BASELINE configs[1]; global batch 512*N -> configs[3] at N=8), frames
 already resident in HBM (a pool of synthetic uint8 camera frames -- the reference's own frame format, normalised to k/255
 inside the kernels that read them; minibatches are gathered inside the conv1 / loss kernels; the reparameterisation noise is
 drawn inside the reparameterisation kernel).  Nothing runs on the timed path but the library's own kernels.
-`value` = frames/s of the whole job = N*512*K / max-over-ranks(time of exactly K steps).
+`value` = frames/s of the whole job = N*512*K / max-over-ranks(time of exactly K steps); `ms_per_step` = that time / K.
+A plain run sets up, conditions the clocks (--condition-ms), restores the freshly initialised model, warms up W steps, times the K steps and prints the line;
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs): equal arguments give equal inputs and outputs from run to run.
 
-Extra objects on the same JSON line:
+Extra objects on the same JSON line, measured with --full only:
   box           in-run calibration of THIS GPU (mi_device_probe, csrc/probe.hip): sustained bf16 MFMA TFLOP/s and the shader clock under it, HBM streaming read /
                 copy TB/s, sysfs clocks / power where readable -- measured after --condition-ms of untimed steps (the DVFS ramp) and before the counted
                 warm-up; `roofline.frac_of_box` prices the dominant kernel against these instead of the datasheet.
@@ -451,6 +453,15 @@ def step_traffic(B):
     return out
 
 
+def dump_outputs(out_dir, losses, params):
+    """--dump-outputs: what the last timed step computed, as a caller of the step receives it -- its two losses (reconstruction, KL) as losses.npy and every
+    updated parameter under its TensorFlow name ("/" -> "."), float32: 10.3 MB at the benchmark's shapes."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "losses.npy"), np.asarray(losses, np.float32))
+    for name, value in params.items():
+        np.save(os.path.join(out_dir, name.replace("/", ".") + ".npy"), np.asarray(value, np.float32))
+
+
 def _watchdog(seconds, last_words):
     """A timer that ends THIS process (exit code 0) after `seconds` unless cancelled; rank 0 passes `last_words` (prints the result line it already has)."""
     import threading
@@ -614,7 +625,12 @@ def main():
     ap.add_argument("--no-box", action="store_true", help="skip the in-run box calibration (mi_device_probe)")
     ap.add_argument("--long-steps", type=int, default=200, help="a second, longer timed leg of the same step behind the counted one (`value_200`): shows whether the driver's "
                                                                 "20-step sample (16 ms) is representative; 0 = off")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: box calibration, per-op profile and roofline, the longer leg, the data-parallel "
+                                                        "legs, CPU baseline, parity, the other precisions and workloads (the --no-* options and --long-steps apply here only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (its two losses, every parameter) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from mi355 import dist as midist
     # (test hook: MI355_BENCH_BACKEND=gloo MI355_BENCH_ONE_DEVICE=1 runs the N > 1 code path with all ranks on cuda:0 -- RCCL wants one device per rank)
@@ -656,35 +672,46 @@ def main():
     def step(i):
         model._train_minibatch(pool, pool, idx[i % n_idx], B, inv_b, None)     # eps=None: drawn inside the reparameterisation kernel
 
+    # the state the counted warm-up starts from: the conditioning below runs for wall time, so its number of SGD steps differs from run to run and from build to
+    # build; it is undone before the warm-up, so that equal arguments give equal outputs (--dump-outputs)
+    fresh = (model.state_dict(), dev._seed)
+
     # ---- clock conditioning (untimed, in front of the counted warm-up): the driver's command is 5 + 20 steps = 25 ms of GPU work from an idle
     # box, i.e. measured on the DVFS ramp; >= --condition-ms of the very same steps first, then the box calibration, then the counted warm-up ----
     conditioned = condition_clocks(step, args.condition_ms, world, device) if args.condition_ms > 0 else 0
     box = None
-    if not args.no_box:
+    if args.full and not args.no_box:
         try:
             box = box_probe(dev, local)
         except Exception as e:
             box = {"error": repr(e)}
         for _ in range(20 if args.condition_ms > 0 else 0):      # (the probes ran at their own power point: back to the step's before the warm-up)
             step(conditioned); conditioned += 1
-    # ---- warm-up (untimed); two of the warm-up steps run with every op bracketed by HIP events to find the dominant kernel ----
-    for i in range(max(args.warmup - 2, 0)):
-        step(i)
-    torch.cuda.synchronize()
-    dev.L.mi_vae_timing_begin(dev.handle, 1, -1, 2 * n_ops + 8)
-    for i in range(max(args.warmup - 2, 0), args.warmup):
-        step(i)
-    if args.warmup == 0:                                  # --warmup 0: the dominant kernel is still found on one extra, untimed step
-        step(total + 1)
-    torch.cuda.synchronize()
-    ms_all, cnt_all = collect_timing(dev, n_ops)
-    per_op = {names[i]: float(ms_all[i] / cnt_all[i]) for i in range(n_ops) if cnt_all[i] > 0}
-    dominant = max(per_op, key=per_op.get) if per_op else None
+    model.load_state_dict(fresh[0])                       # parameters, Adam slots and powers ...
+    dev.set_seed(fresh[1])                                # ... the noise stream (synchronises) ...
+    dev.grads.zero_(); dev.metrics.zero_()                # ... and the buffers a fresh engine starts with zeroed
+    per_op, per_op_in_step, dominant = {}, {}, None
+    if not args.full:
+        for i in range(args.warmup):
+            step(i)
+    else:
+        # ---- warm-up (untimed); two of the warm-up steps run with every op bracketed by HIP events to find the dominant kernel ----
+        for i in range(max(args.warmup - 2, 0)):
+            step(i)
+        torch.cuda.synchronize()
+        dev.L.mi_vae_timing_begin(dev.handle, 1, -1, 2 * n_ops + 8)
+        for i in range(max(args.warmup - 2, 0), args.warmup):
+            step(i)
+        if args.warmup == 0:                              # --warmup 0: the dominant kernel is still found on one extra, untimed step
+            step(total + 1)
+        torch.cuda.synchronize()
+        ms_all, cnt_all = collect_timing(dev, n_ops)
+        per_op = {names[i]: float(ms_all[i] / cnt_all[i]) for i in range(n_ops) if cnt_all[i] > 0}
+        dominant = max(per_op, key=per_op.get) if per_op else None
     # The profile above runs one op at a time (isolated launch times; the two front-runners -- the decoder tail and deconv3's filter gradient -- are within a microsecond
     # of each other there, so the crown used to change from run to run and `roofline.frac` with it: 0.35 one run, 0.20 the next).  The dominant kernel of the STEP is the
     # one that takes longest IN the step, next to its neighbour on the other backward queue: the four front-runners are timed again inside whole two-queue steps (events
     # around that op only, 6 untimed steps each) and the longest in-step average wins.
-    per_op_in_step = {}
     if per_op and args.precision == "bf16" and args.warmup > 0:
         for cand in sorted(per_op, key=per_op.get, reverse=True)[:4]:
             dev.L.mi_vae_timing_begin(dev.handle, 2, names.index(cand), 16)
@@ -716,6 +743,8 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(t[0].item())
     losses = dev.losses.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, dev.export_params())
     roofline = None
     if dominant is not None:
         how = "HIP events on the launch stream around every launch of this op inside the timed region"
@@ -758,7 +787,7 @@ def main():
 
     # ---- a longer leg of the very same step, same run (the driver's --steps 20 is a 16 ms sample): barrier + synchronize on both sides, MAX over ranks ----
     long_leg = None
-    if args.long_steps > args.steps:
+    if args.full and args.long_steps > args.steps:
         midist.barrier()
         torch.cuda.synchronize()
         tl0 = time.perf_counter()
@@ -776,7 +805,7 @@ def main():
     # backward parts in bucket order, every bucket handed to the communicator, the join, Adam) on a RECORDING communicator -- the driver computes scaling efficiency from the N = 1
     # line, and the part that is schedule, not transport, can be read here
     dp_form = None
-    if world == 1 and args.precision == "bf16" and not args.no_dp_form and hasattr(dev, "train_step_dp"):
+    if args.full and world == 1 and args.precision == "bf16" and not args.no_dp_form and hasattr(dev, "train_step_dp"):
         try:
             import ctypes
             from vae.models import adam_alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON
@@ -805,7 +834,7 @@ def main():
 
     # data parallel: what one rank spends per step, and how much of it is gradient all-reduce that nothing overlaps
     dp = None
-    if world > 1:
+    if args.full and world > 1:
         per_rank = [torch.zeros(2, device=device, dtype=torch.float64) for _ in range(world)]
         torch.distributed.all_gather(per_rank, torch.tensor([t_local / args.steps * 1e3, 0.0], device=device, dtype=torch.float64))
         # exposed all-reduce: the same steps with the collectives skipped (gradients then differ per rank: parameters are re-broadcast afterwards)
@@ -837,21 +866,24 @@ def main():
                        "launch": "eager launches: one C call per step (mi_vae_train_step)",
                        "storage": "bf16 activations/weights, fp32 accumulate, fp32 master weights+Adam" if args.precision == "bf16" else "fp32",
                        "library": _library_stamp()},
-            "roofline": roofline,
-            "box": box,
             "conditioning": {"untimed_steps_before_warmup": conditioned, "target_ms": args.condition_ms},
             "step_model_flops_utilisation": {"algorithmic_tflops_per_step": step_flops / 1e12,
                                              "achieved_tflops": step_flops * args.steps / elapsed / 1e12,
                                              "frac_of_mfma_peak": step_flops * args.steps / elapsed / PEAK[{"bf16": "mfma_bf16", "bf16x3": "mfma_bf16x3"}.get(args.precision, "mfma_f32")]},
+            "final_losses": {"reconstruction": float(losses[0]), "kl": float(losses[1])},
+        }
+    if rank == 0 and args.full:
+        out.update({
+            "roofline": roofline,
+            "box": box,
             "per_op_ms_note": "every op bracketed by HIP events, one at a time (two warm-up steps): isolated launch times, not in-step times",
             "per_op_in_step_ms": {k: round(v, 4) for k, v in sorted(per_op_in_step.items(), key=lambda kv: -kv[1])},
             "per_op_in_step_note": "the four longest ops timed again INSIDE whole two-queue steps (events around that op only): the dominant kernel of `roofline` is the longest of these",
             "per_op_ms": {k: round(v, 4) for k, v in sorted(per_op.items(), key=lambda kv: -kv[1])},
-            "final_losses": {"reconstruction": float(losses[0]), "kl": float(losses[1])},
             "data_parallel": dp,
             "data_parallel_form_at_one_rank": dp_form,
             "value_200": long_leg,
-        }
+        })
         if roofline is not None and args.precision == "bf16":
             roofline["step_traffic"] = step_traffic(B)
         out["cpu_baseline"] = None
@@ -888,7 +920,7 @@ def main():
                 out["replay"] = {"error": repr(e)}
         if box and "error" not in box and box.get("mfma_bf16_tflops", 0) > 0 and args.precision == "bf16":
             out["step_model_flops_utilisation"]["frac_of_box_mfma_rate"] = out["step_model_flops_utilisation"]["achieved_tflops"] / box["mfma_bf16_tflops"]
-    if world > 1:
+    if args.full and world > 1:
         # both bucket schedules, timed in this run -- behind a watchdog: the headline line exists by now and must get out even if a collective schedule that has never run
         # on this many devices does not come back (rank 0 prints it without the schedule object; every rank leaves)
         wd = _watchdog(180.0, (lambda: print(json.dumps(dict(out, data_parallel=dict(out["data_parallel"] or {}, schedules_note="watchdog: the schedule leg did not return"))), flush=True))

@@ -1,16 +1,17 @@
 #!/usr/bin/env python3
-"""Assemble profiles/<name>.md + profiles/rNN_pmc_traffic.json from the files one GPU call leaves in gpurun_out/:
+"""Assemble profiles/<name>.md + profiles/rNN_pmc_traffic.json from the files one GPU call leaves in $OUT (default out/ of the repository):
     prof_<tag>.md (rocprofv3 --kernel-trace --stats via tools/rocpd_summary.py), pmc_<tag>_sq.md / _fetch.md / _write.md (tools/pmc_pass.sh),
     bench_<tag>_full.json (bench.py), timeline_<tag>.md (tools/timeline.sh; optional).  tools/profile_round.sh produces all of them.   usage: python tools/make_profile.py <tag> <out-name> "<title>" """
 import json, os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))) + "/"
+OUT = os.path.join(R, os.environ.get("OUT", "out")) + "/"
 tag, outname, title = sys.argv[1], sys.argv[2], sys.argv[3]
-stats = open(R + "gpurun_out/prof_%s.md" % tag).read()
-sq = open(R + "gpurun_out/pmc_%s_sq.md" % tag).read()
-fe = open(R + "gpurun_out/pmc_%s_fetch.md" % tag).read()
-wr = open(R + "gpurun_out/pmc_%s_write.md" % tag).read()
-bench = json.load(open(R + "gpurun_out/bench_%s_full.json" % tag))
-tl_path = R + "gpurun_out/timeline_%s.md" % tag
+stats = open(OUT + "prof_%s.md" % tag).read()
+sq = open(OUT + "pmc_%s_sq.md" % tag).read()
+fe = open(OUT + "pmc_%s_fetch.md" % tag).read()
+wr = open(OUT + "pmc_%s_write.md" % tag).read()
+bench = json.load(open(OUT + "bench_%s_full.json" % tag))
+tl_path = OUT + "timeline_%s.md" % tag
 timeline = open(tl_path).read() if os.path.exists(tl_path) else "(not collected)"
 
 def rows(md):
