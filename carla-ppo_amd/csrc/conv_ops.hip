@@ -649,11 +649,12 @@ int try_narrow_conv(hipStream_t st, int dtype, const void* src, int src_f32, con
 }
 
 // conv-form (A_CONV x B_NK).  Returns 1 if launched, 0 if not eligible, <0 on error.
-int try_conv_form_gemm2(hipStream_t st, int dtype, const GemmParams& p, int gz = 1) {
+// wfrag: fragment-ordered weights for the register-weight kernel (mi_rwconv_take_wfrag) or NULL
+int try_conv_form_gemm2(hipStream_t st, int dtype, const GemmParams& p, int gz, const void* wfrag) {
     if (p.a_frame_idx) return 0;
     if (p.ksplit_len > 0 && (!g_gemm2_splitk || p.stride != 1 || p.KH != 1 || p.KW != 1 || (p.ksplit_len * esz_of(dtype)) % 128 != 0)) return 0;   // split-K: dense layers, whole 128-byte stages per split
     if (p.stride == 2 && !p.out_f32) {
-        const int r5 = mi_try_rwconv_conv(st, dtype, p.a, p.b, p.nbatch, p.IH, p.IW, p.C, p.OH, p.OW, p.N, p.KH, p.KW, p.ldb, p.out, p.bias, p.mask, p.relu);
+        const int r5 = mi_try_rwconv_conv(st, dtype, p.a, p.b, p.nbatch, p.IH, p.IW, p.C, p.OH, p.OW, p.N, p.KH, p.KW, p.ldb, p.out, p.bias, p.mask, p.relu, wfrag);
         if (r5 != 0) return r5;
         const int r3 = try_tapconv(st, dtype, TC_CONV, p.a, p.b, p.nbatch, p.IH, p.IW, p.C, p.OH, p.OW, p.N, p.KH, p.KW, p.ldb, p.out, p.bias, p.mask, p.relu);
         if (r3 != 0) return r3;
@@ -707,10 +708,10 @@ int try_deconv_form_gemm2(hipStream_t st, int dtype, const GemmParams& p, int ma
 
 // A_CONV GEMM with dtype/vector dispatch. in_f32: the A tensor is fp32 in HBM even when T = bf16 (input frames).
 template <int BMODE>
-int conv_form_gemm(hipStream_t st, int dtype, int in_f32, GemmParams& p, int gz) {
+int conv_form_gemm(hipStream_t st, int dtype, int in_f32, GemmParams& p, int gz, const void* wfrag = nullptr) {
     const int C = p.C;
     if (BMODE == B_NK && !(in_f32 && dtype != MI_F32)) {
-        const int r2 = try_conv_form_gemm2(st, dtype, p, gz);
+        const int r2 = try_conv_form_gemm2(st, dtype, p, gz, wfrag);
         if (r2 != 0) return r2 > 0 ? MI_OK : r2;
     }
     const bool a16 = (((uintptr_t)p.a) & 15) == 0;
@@ -749,7 +750,7 @@ bool vec_ok(const void* ptr, long long ld, int dtype) {
     return ((((uintptr_t)ptr) & 15) == 0) && (ld % vb == 0);
 }
 
-int deconv_form_gemm(hipStream_t st, int dtype, GemmParams& p, int B, int IH, int IW, int C, int OH, int OW, int N, int KH, int KW) {
+int deconv_form_gemm(hipStream_t st, int dtype, GemmParams& p, int B, int IH, int IW, int C, int OH, int OW, int N, int KH, int KW, const void* wfrag = nullptr) {
     // gather-form stride-2 transposed conv; output may be larger than the natural (IH-1)*2+KH (extra rows/cols get bias only)
     p.IH = IH; p.IW = IW; p.C = C; p.OH = OH; p.OW = OW; p.KH = KH; p.KW = KW; p.stride = 2;
     p.nbatch = B; p.N = N; p.M = 0; p.K = 0;
@@ -778,7 +779,7 @@ int deconv_form_gemm(hipStream_t st, int dtype, GemmParams& p, int B, int IH, in
         if (r4 != 0) return r4 > 0 ? MI_OK : r4;
     }
     if (!p.out_f32) {
-        const int r5 = mi_try_rwconv_gather(st, dtype, p.a, p.b, B, IH, IW, C, OH, OW, N, KH, KW, p.out, p.bias, p.mask, p.relu, nullptr, nullptr);
+        const int r5 = mi_try_rwconv_gather(st, dtype, p.a, p.b, B, IH, IW, C, OH, OW, N, KH, KW, p.out, p.bias, p.mask, p.relu, nullptr, nullptr, wfrag);
         if (r5 != 0) return r5 > 0 ? MI_OK : r5;
     }
     if (!p.out_f32) {
@@ -891,8 +892,8 @@ inline bool needs_merge(int C, int dtype, int in_f32) {
 static thread_local SmallReduceParams t_sr;
 static thread_local int t_sr_defer = 0;
 // The recorded list belongs to ONE stream (round 5): the stream of its first job, or the one the engine named with mi_small_reduce_bind.  A job that
-// arrives from another stream while the pass defers (a layer the engine issues on its filter-gradient stream, e.g. conv1's narrow filter gradient with
-// MI355_WGRAD_MAIN_MASK bit 0 clear) is launched at once on ITS stream instead of being flushed later on a stream that never waited for its slabs.
+// arrives from another stream while the pass defers (e.g. conv1's narrow filter gradient on the caller's stream in a backward part whose list is bound to the
+// filter-gradient stream) is launched at once on ITS stream instead of being flushed later on a stream that never waited for its slabs.
 static thread_local hipStream_t t_sr_stream = nullptr;
 static thread_local bool t_sr_bound = false;
 static int sr_launch_params(hipStream_t st, SmallReduceParams& f) {
@@ -999,6 +1000,7 @@ int mi_conv2d_nhwc_fwd(void* stream, int dtype, const void* x, const int* frame_
 int mi_conv2d_nhwc_fwd_bits(void* stream, int dtype, const void* x, const int* frame_idx, int x_is_f32,
                             int B, int IH, int IW, int Cin, const void* w, int w_transposed, const float* bias, int KH, int KW, int Cout,
                             int relu, void* out, void* relu_bits, int* wrote_bits) {
+    const void* const wfrag = mi_rwconv_take_wfrag();
     const int OH = (IH - KH) / 2 + 1, OW = (IW - KW) / 2 + 1;
     if (wrote_bits) *wrote_bits = 0;
     if (w_transposed) {
@@ -1013,7 +1015,7 @@ int mi_conv2d_nhwc_fwd_bits(void* stream, int dtype, const void* x, const int* f
     fill_conv_geom(p, B, IH, IW, Cin, OH, OW, KH, KW, 2, needs_merge(Cin, dtype, x_is_f32));
     p.N = Cout; p.b = w; p.ldb = w_transposed ? p.K : Cout; p.b_vec = vec_ok(w, p.ldb, dtype);
     p.out = out; p.bias = bias; p.mask = nullptr; p.relu = relu; p.out_f32 = 0; p.ksplit_len = 0;
-    if (w_transposed) return conv_form_gemm<B_NK>((hipStream_t)stream, dtype, x_is_f32, p, 1);
+    if (w_transposed) return conv_form_gemm<B_NK>((hipStream_t)stream, dtype, x_is_f32, p, 1, wfrag);
     return conv_form_gemm<B_KN>((hipStream_t)stream, dtype, x_is_f32, p, 1);
 }
 
@@ -1029,7 +1031,7 @@ int mi_conv2d_nhwc_dgrad(void* stream, int dtype, const void* dy, int B, int OH,
 int mi_conv2d_nhwc_dgrad_bits(void* stream, int dtype, const void* dy, int B, int OH, int OW, int Cout,
                               const void* w, int KH, int KW, int Cin, int IH, int IW, const void* mask, const void* mask_bits, void* dx) {
     if (mask_bits) {
-        const int r5 = mi_try_rwconv_gather((hipStream_t)stream, dtype, dy, w, B, OH, OW, Cout, IH, IW, Cin, KH, KW, dx, nullptr, mask, 0, mask_bits, nullptr);
+        const int r5 = mi_try_rwconv_gather((hipStream_t)stream, dtype, dy, w, B, OH, OW, Cout, IH, IW, Cin, KH, KW, dx, nullptr, mask, 0, mask_bits, nullptr, nullptr);
         if (r5 != 0) return r5 > 0 ? MI_OK : r5;
     }
     GemmParams p = {};
@@ -1082,9 +1084,10 @@ int mi_deconv2d_nhwc_fwd(void* stream, int dtype, const void* x, int B, int IH, 
 // same; relu_bits != NULL: also writes the ReLU bit words of the output where the kernel can (*wrote_bits tells)
 int mi_deconv2d_nhwc_fwd_bits(void* stream, int dtype, const void* x, int B, int IH, int IW, int Cin,
                               const void* w, const float* bias, int KH, int KW, int Cout, int relu, void* out, void* relu_bits, int* wrote_bits) {
+    const void* const wfrag = mi_rwconv_take_wfrag();
     if (wrote_bits) *wrote_bits = 0;
     if (relu_bits && relu) {
-        const int r5 = mi_try_rwconv_gather((hipStream_t)stream, dtype, x, w, B, IH, IW, Cin, (IH - 1) * 2 + KH, (IW - 1) * 2 + KW, Cout, KH, KW, out, bias, nullptr, relu, nullptr, relu_bits);
+        const int r5 = mi_try_rwconv_gather((hipStream_t)stream, dtype, x, w, B, IH, IW, Cin, (IH - 1) * 2 + KH, (IW - 1) * 2 + KW, Cout, KH, KW, out, bias, nullptr, relu, nullptr, relu_bits, wfrag);
         if (r5 > 0 && wrote_bits) *wrote_bits = 1;
         if (r5 != 0) return r5 > 0 ? MI_OK : r5;
     }
@@ -1092,7 +1095,7 @@ int mi_deconv2d_nhwc_fwd_bits(void* stream, int dtype, const void* x, int B, int
     GemmParams p = {};
     p.a = x; p.b = w; p.ldb = 0; p.b_vec = 1;
     p.out = out; p.bias = bias; p.mask = nullptr; p.relu = relu; p.out_f32 = 0;
-    return deconv_form_gemm((hipStream_t)stream, dtype, p, B, IH, IW, Cin, OH, OW, Cout, KH, KW);
+    return deconv_form_gemm((hipStream_t)stream, dtype, p, B, IH, IW, Cin, OH, OW, Cout, KH, KW, wfrag);
 }
 
 // conv2d_transpose into narrow logits + fused reconstruction loss (see the header); *n_partial = 0: not eligible, nothing launched
@@ -1200,6 +1203,7 @@ int mi_deconv2d_nhwc_dgrad(void* stream, int dtype, const void* dy, int B, int O
 
 int mi_deconv2d_nhwc_dgrad_bits(void* stream, int dtype, const void* dy, int B, int OH, int OW, int Cout,
                                 const void* w, int w_transposed, int KH, int KW, int Cin, const void* mask, const void* mask_bits, void* dx) {
+    const void* const wfrag = mi_rwconv_take_wfrag();
     const int IH = (OH - KH) / 2 + 1, IW = (OW - KW) / 2 + 1;
     if (w_transposed) {
         const int r4 = try_narrow_conv((hipStream_t)stream, dtype, dy, dtype == MI_F32 ? 1 : (dtype == MI_BF16X3 ? 3 : 0), nullptr, w, B, OH, OW, Cout, KH, KW, Cin, nullptr, 0, mask, dx, nullptr, mask_bits);
@@ -1210,7 +1214,7 @@ int mi_deconv2d_nhwc_dgrad_bits(void* stream, int dtype, const void* dy, int B, 
     fill_conv_geom(p, B, OH, OW, Cout, IH, IW, KH, KW, 2, needs_merge(Cout, dtype, 0));
     p.N = Cin; p.b = w; p.ldb = w_transposed ? p.K : Cin; p.b_vec = vec_ok(w, p.ldb, dtype);
     p.out = dx; p.bias = nullptr; p.mask = mask; p.relu = 0; p.out_f32 = 0; p.ksplit_len = 0;
-    if (w_transposed) return conv_form_gemm<B_NK>((hipStream_t)stream, dtype, 0, p, 1);
+    if (w_transposed) return conv_form_gemm<B_NK>((hipStream_t)stream, dtype, 0, p, 1, wfrag);
     return conv_form_gemm<B_KN>((hipStream_t)stream, dtype, 0, p, 1);
 }
 
@@ -1368,11 +1372,9 @@ int mi_gemm_wgrad_bias_set(void* stream, int dtype, const void* a, const void* d
 // shapes: the two single calls.  Round 6: the two ~190-block grids sat back to back at the very end of the backward pass.
 int mi_gemm_wgrad_bias_pair_ws(void* stream, int dtype, const void* a0, const void* dy0, int M0, int K0, int N0, float* dw0, float* db0, void* scratch0, long long scratch_bytes0,
                                const void* a1, const void* dy1, int M1, int K1, int N1, float* dw1, float* db1, void* scratch1, long long scratch_bytes1) {
-    static int pair_on = -1;
-    if (pair_on < 0) { const char* e = getenv("MI355_DENSE_PAIR"); pair_on = (e && e[0] == '0') ? 0 : 1; }
     const void* A[2] = {a0, a1}; const void* DY[2] = {dy0, dy1}; const int M[2] = {M0, M1}, K[2] = {K0, K1}, N[2] = {N0, N1};
     float* DW[2] = {dw0, dw1}; float* DB[2] = {db0, db1}; void* WS[2] = {scratch0, scratch1}; const long long NB[2] = {scratch_bytes0, scratch_bytes1};
-    bool ok = pair_on && dtype == MI_BF16;
+    bool ok = dtype == MI_BF16;
     WgradPair q = {};
     dim3 g[2];
     for (int i = 0; i < 2 && ok; ++i) {

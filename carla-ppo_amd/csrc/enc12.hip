@@ -28,6 +28,7 @@ static int enc12_grid(int u8) {
 // (another summation order than the unfused kernel).  *launched = 0: not eligible -- bf16 storage and this geometry only; nothing was launched: call the two layer ops.
 extern "C" int mi_conv2d_enc12_fwd(void* stream, int dtype, const void* frames, int frames_fmt, const int* frame_idx, int B, int FH, int FW, const void* w1_t, const float* b1,
                                    const void* w2_t, const float* b2, void* act1, void* relu_bits1, void* act2, int* launched) {
+    const void* const w2f = mi_rwconv_take_wfrag();         // conv2's kernel in fragment order (mi_rwconv_next_weights_fragment_ordered, form 5), or NULL
     if (!launched || !frames || !w1_t || !b1 || !w2_t || !b2 || !act1 || !act2) return mi_fail(MI_ERR_ARG, "mi_conv2d_enc12_fwd: missing buffers");
     *launched = 0;
     static int on = -1;
@@ -40,7 +41,7 @@ extern "C" int mi_conv2d_enc12_fwd(void* stream, int dtype, const void* frames, 
     q.frames = frames; q.frame_idx = frame_idx; q.frame_stride = (long long)FH * FW * 3;
     q.w1 = (const bf16_t*)w1_t; q.b1 = b1; q.w2 = (const bf16_t*)w2_t; q.b2 = b2;
     q.act1 = (bf16_t*)act1; q.bits1 = (uint32_t*)relu_bits1; q.act2 = (bf16_t*)act2;
-    q.w2f = (const bf16_t*)mi_tl_rc_wfrag; mi_tl_rc_wfrag = nullptr;      // (announced by mi_rwconv_next_weights_fragment_ordered; consumed by this launch)
+    q.w2f = (const bf16_t*)w2f;
     q.B = B; q.ntiles = 3 * B;
     int nblocks = enc12_grid(frames_fmt == 2 ? 1 : 0);
     if (nblocks > q.ntiles) nblocks = q.ntiles;

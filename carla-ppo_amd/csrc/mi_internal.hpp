@@ -16,7 +16,7 @@ extern thread_local hipEvent_t mi_tl_stop_event;
             hipExtLaunchKernelGGL(kernel, grid, block, shmem, stream, nullptr, ev__, 0, __VA_ARGS__); } \
         else hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__); } while (0)
 
-extern thread_local const void* mi_tl_rc_wfrag;  // rwconv.hip: fragment-ordered weights for the next conv-form register-weight launch of this thread (mi_rwconv_next_weights_fragment_ordered)
+const void* mi_rwconv_take_wfrag();             // rwconv.hip: returns and clears this thread's mi_rwconv_next_weights_fragment_ordered announcement (called first thing by the entries it applies to)
 int mi_enc12_debug(int mask);                    // enc12.hip: ablation mask of the fused encoder-head forward kernel (tools/enc12_ablate.py); returns the previous one
 int mi_fail(int code, const char* msg);          // records msg (thread-local) and returns code
 int mi_check_launch(const char* what);           // hipGetLastError() -> MI_OK / MI_ERR_LAUNCH
@@ -28,10 +28,11 @@ extern "C" int mi_tapwgrad_defer_pause(int pause);   // != 0: reduce right behin
 extern "C" int mi_tapwgrad_slab_bf16(int on);    // partial-sum slabs rounded to bf16 (the engine's bf16 backward); returns the previous setting
 
 // register-weight kernel of the thin gather-form layers (rwconv.hip): 1 launched, 0 not eligible, < 0 error
+// wfrag: the layer's weights in fragment order (mi_rwconv_take_wfrag), or NULL
 int mi_try_rwconv_gather(hipStream_t st, int dtype, const void* a, const void* w, int B, int IH, int IW, int C, int OH, int OW, int N,
-                         int KH, int KW, void* out, const float* bias, const void* mask, int relu, const void* mask_bits, void* bits_out);
+                         int KH, int KW, void* out, const float* bias, const void* mask, int relu, const void* mask_bits, void* bits_out, const void* wfrag);
 int mi_try_rwconv_conv(hipStream_t st, int dtype, const void* a, const void* w, int B, int IH, int IW, int C, int OH, int OW, int N,
-                       int KH, int KW, int ldb, void* out, const float* bias, const void* mask, int relu);   // rwconv.hip, conv form (32 -> 64 channels)
+                       int KH, int KW, int ldb, void* out, const float* bias, const void* mask, int relu, const void* wfrag);   // rwconv.hip, conv form (32 -> 64 channels)
 int mi_rwconv_conv_mode(int set);                // mi_set_tuning key 15: 0 off, 1 k = 5 layers, 2 also k = 4; set < 0 queries
 int mi_rwconv_blocks(int set);                   // mi_set_tuning key 16: persistent blocks per XCD (0 = resident maximum); set < 0 queries
 int mi_rwconv_mode(int set);                     // mi_set_tuning key 13: 0 off, 1 auto, 2 whenever eligible; set < 0 queries

@@ -650,9 +650,7 @@ int mi_rwconv_mode(int set) {                            // set < 0: query
 // gather-form transposed conv / conv input gradient on the register-weight kernel.  Same contract as try_tapconv (conv_ops.hip):
 // returns 1 launched, 0 not eligible, < 0 error.  x [B,IH,IW,64] bf16, w [KH][KW][32][64] bf16, out / mask [B,OH,OW,32] bf16.
 int mi_try_rwconv_gather(hipStream_t st, int dtype, const void* a, const void* w, int B, int IH, int IW, int C, int OH, int OW, int N,
-                         int KH, int KW, void* out, const float* bias, const void* mask, int relu, const void* mask_bits, void* bits_out) {
-    const void* const wfrag = mi_tl_rc_wfrag;              // fragment-ordered weights announced for this launch (mi_rwconv_next_weights_fragment_ordered; pack form 4: k = 5, 64 -> 32 channels)
-    mi_tl_rc_wfrag = nullptr;
+                         int KH, int KW, void* out, const float* bias, const void* mask, int relu, const void* mask_bits, void* bits_out, const void* wfrag) {
     mi_rwconv_mode(-1);
     static int wide = -1;                                 // MI355_RWCONV_WIDE=0: the 128 -> 64 channel layers stay on tapconv (A/B runs)
     if (wide < 0) { const char* ev = getenv("MI355_RWCONV_WIDE"); wide = (ev && ev[0] == '0') ? 0 : 1; }
@@ -722,15 +720,19 @@ int mi_rwconv_blocks(int set) {                          // mi_set_tuning key 16
     if (set >= 0) g_rwconv_blocks = set;
     return prev;
 }
-// The NEXT register-weight launch issued by this thread reads its weights from `wf`, the same kernel in the fragment order its prologue loads registers in (mi_ares_pack_weights forms
-// 3 / 4 / 5): conv form 64 -> 128 channels k = 4 (mi_conv2d_nhwc_fwd[_bits] = conv3 forward, mi_deconv2d_nhwc_dgrad[_bits] = deconv2's input gradient; form 3), gather form
-// 64 -> 32 channels k = 5 (mi_deconv2d_nhwc_fwd[_bits] = deconv3 forward; form 4), the fused encoder head (mi_conv2d_enc12_fwd: conv2's kernel, form 5).  Consumed by that call
-// whether or not such a kernel takes the layer; NULL clears.  The VAE engine sets it in front of those four launches (round 6).
-thread_local const void* mi_tl_rc_wfrag = nullptr;
+// Fragment-ordered weights announced for the next call of mi_conv2d_nhwc_fwd[_bits], mi_deconv2d_nhwc_fwd[_bits], mi_deconv2d_nhwc_dgrad[_bits] or mi_conv2d_enc12_fwd on
+// this thread: the same kernel in the order the register-weight prologue loads it (mi_ares_pack_weights forms 3 - 6).  Each of those entries takes it first thing, so the
+// announcement never outlives that call, and passes it down explicitly to the launch that can use it.
+static thread_local const void* mi_tl_rc_wfrag = nullptr;
 extern "C" int mi_rwconv_next_weights_fragment_ordered(const void* wf) {
     if (((uintptr_t)wf) & 15) return mi_fail(MI_ERR_ARG, "mi_rwconv_next_weights_fragment_ordered: the copy must be 16-byte aligned");
     mi_tl_rc_wfrag = wf;
     return MI_OK;
+}
+const void* mi_rwconv_take_wfrag() {
+    const void* const wf = mi_tl_rc_wfrag;
+    mi_tl_rc_wfrag = nullptr;
+    return wf;
 }
 int g_rwconv_conv = -1;                                  // mi_set_tuning key 15 / MI355_RWCONV_CONV: 0 off, 1 k = 5 only, 2 also k = 4, 3 also the 64 -> 128 channel shape (default)
 int mi_rwconv_conv_mode(int set) {                       // set < 0: query
@@ -744,9 +746,7 @@ int mi_rwconv_conv_mode(int set) {                       // set < 0: query
 // bf16, (C, N) = (32, 64) with k = 4 | 5 or (64, 128) with k = 4.  Same contract as try_tapconv: 1 launched, 0 not eligible, < 0 error.
 // mi_set_tuning key 15 / MI355_RWCONV_CONV: 0 off, 1 the k = 5 layer, 2 also 32 -> 64 channels k = 4, 3 also 64 -> 128 channels (default).
 int mi_try_rwconv_conv(hipStream_t st, int dtype, const void* a, const void* w, int B, int IH, int IW, int C, int OH, int OW, int N,
-                       int KH, int KW, int ldb, void* out, const float* bias, const void* mask, int relu) {
-    const void* const wfrag = mi_tl_rc_wfrag;              // (consumed by THIS call whatever it dispatches to)
-    mi_tl_rc_wfrag = nullptr;
+                       int KH, int KW, int ldb, void* out, const float* bias, const void* mask, int relu, const void* wfrag) {
     const int on = mi_rwconv_conv_mode(-1);
     mi_rwconv_mode(-1);
     const int ck = (C == 64 && N == 128) ? 2 : 1;

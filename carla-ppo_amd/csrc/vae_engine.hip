@@ -70,7 +70,6 @@ struct Workspace {
     long long enc_slabs, enc_slab_bytes;     // per-block partial sums of the fused encoder-head backward kernel (enchead_tile.hpp)
     long long scratch, scratch_bytes;  // split-reduction slabs of the filter-gradient kernels on the filter-gradient stream (SCRATCH_REGIONS rotating regions)
     long long scratch_main, scratch_main_bytes;    // ... of the filter / bias gradients issued on the caller's stream (one region, reused in stream order)
-    long long scratch_third, scratch_third_bytes;  // ... of the latent layers' gradients on the optional third stream
     long long scratch_tail, scratch_tail_bytes;    // ... of the small reductions at the end of a full backward pass that run as ONE deferred launch (bump-allocated: every job keeps its slabs until the flush)
     long long scratch_side, scratch_side_bytes;    // ... of the latent layers' gradients when they run on the filter-gradient stream (outside the rotating regions: those may hold deferred slabs)
     long long bits_act1, bits_dec3;    // ReLU bit words of conv1's / deconv3's output (bf16 engine: 8 bytes per pixel; read by conv2's / deconv4's input gradient)
@@ -139,13 +138,7 @@ struct VaeEngine {
                                         // all-reduce is then chained to the filter-gradient stream and the caller's stream goes straight on with the next part's input-gradient chain
     int ares_mid;                       // ... and the mid-layer copies (conv3's input gradient, deconv2 forward)
     int ares_ok;                        // the fragment-ordered weight copies exist (bf16 engine, the model's geometry): the four small-grid layers run on the activation-resident kernels
-    int fwd_produced;                   // the last forward's final kernel (the fused decoder tail) carries ev_ready on its own dispatch packet (MI355_KEVENT; consumed by the backward pass's first hand-over)
-    hipStream_t main2;                  // MI355_CU_SPLIT=N (measurement aid, round 6): the caller-side half of the backward pass on an engine stream bound to compute units [0, N), the filter-gradient stream to [N, 256)
-    hipEvent_t ev_in, ev_out;
-    int main2_ok;
-    hipStream_t third;                  // latent-layer gradients + loss finalisation of a full two-stream backward (small launches with early operands)
-    hipEvent_t ev_lat, ev_third;
-    int third_ok;
+    int fwd_produced;                   // the last forward's final kernel (the fused decoder tail) carries ev_ready on its own dispatch packet (consumed by the backward pass's first hand-over)
     int bits1_ok, bits3_ok;             // the last forward pass wrote the ReLU bit words of act1 / dec3
     int rng_ready;                      // generator state in the workspace has been initialised (mi_vae_set_seed)
     const float* last_eps;              // the noise the last sampling forward used (caller's buffer or the engine's own draw)
@@ -212,7 +205,6 @@ void make_workspace(VaeEngine& e) {
     W.scratch_bytes = train ? SCRATCH_REGIONS * (64ll << 20) : 0;
     W.scratch = add(train ? W.scratch_bytes : 256);
     W.scratch_main_bytes = train ? 64ll << 20 : 0; W.scratch_main = add(train ? W.scratch_main_bytes : 256);
-    W.scratch_third_bytes = train ? 16ll << 20 : 0; W.scratch_third = add(train ? W.scratch_third_bytes : 256);
     W.scratch_side_bytes = train ? 16ll << 20 : 0; W.scratch_side = add(train ? W.scratch_side_bytes : 256);
     W.scratch_tail_bytes = train ? 32ll << 20 : 0; W.scratch_tail = add(train ? W.scratch_tail_bytes : 256);
     W.tail_slab_bytes = (train && d.dtype == MI_BF16) ? 2048ll * 6144 : 0;      // up to 8 resident blocks per CU x 6 KB
@@ -263,33 +255,6 @@ int check_batch(const VaeEngine* e, int B) {
     return MI_OK;
 }
 
-static int cu_split_env() {                            // MI355_CU_SPLIT=N, 8 <= N <= 248: compute units of the caller-side backward queue (0 / unset: no masks)
-    static int n = -1;
-    if (n < 0) { const char* ev = getenv("MI355_CU_SPLIT"); n = ev ? atoi(ev) : 0; if (n < 8 || n > 248) n = 0; }
-    return n;
-}
-
-unsigned ready_event_flags() {                         // MI355_KEVENT=2: the hand-over event with timing enabled (A/B: what hipExtLaunchKernelGGL's stop event wants)
-    const char* ev = getenv("MI355_KEVENT");
-    unsigned f = (ev && atoi(ev) == 2) ? hipEventDefault : hipEventDisableTiming;
-    // the hand-over events are consumed on this device only: MI355_EVENT_SCOPE=1 device-scope release, =2 no system-scope fence (A/B; default 0 = the runtime's default)
-    const char* sc = getenv("MI355_EVENT_SCOPE");
-    if (sc && atoi(sc) == 1) f |= hipEventReleaseToDevice;
-    if (sc && atoi(sc) == 2) f |= hipEventDisableSystemFence;
-    return f;
-}
-
-bool rc_wfrag_enabled() {                              // MI355_RC_WFRAG=0: the conv-form register-weight kernels of the mid layers read the K-contiguous weight copy (A/B runs)
-    static int on = -1;
-    if (on < 0) { const char* ev = getenv("MI355_RC_WFRAG"); on = (ev && ev[0] == '0') ? 0 : 1; }
-    return on != 0;
-}
-
-bool rc_wfrag6_enabled() {                             // MI355_RC_WFRAG6=0: deconv3's input gradient alone back on the K-contiguous copy (A/B runs)
-    static int on = -1;
-    if (on < 0) { const char* ev = getenv("MI355_RC_WFRAG6"); on = (ev && ev[0] == '0') ? 0 : 1; }
-    return on != 0;
-}
 // conv2 is 32 -> 64 channels k = 4 and deconv3 64 -> 32 channels k = 5 (the reference's geometry): their fragment-ordered copies (pack forms 5 / 4, 6) exist next to the activation-resident ones
 bool rc_small_frag_ok(const VaeEngine* e) {
     const Geom& g = e->g;
@@ -314,8 +279,7 @@ int run_encoder(VaeEngine* e, void* st, const void* frames, int frames_u8, const
             // (per-op timing keeps the two layer launches: they are what the profile names)
             const bool bits12 = want_bits && relu_bits_enabled();
             int launched = 0;
-            if (e->ares_ok && rc_small_frag_ok(e) && rc_wfrag_enabled()) mi_tl_rc_wfrag = e->at(e->W.wfrag[9]);      // conv2's kernel in fragment order (consumed by the launch below)
-            struct WfragGuard0 { ~WfragGuard0() { mi_tl_rc_wfrag = nullptr; } } wfrag_guard0;
+            if (e->ares_ok && rc_small_frag_ok(e)) CK(mi_rwconv_next_weights_fragment_ordered(e->at(e->W.wfrag[9])));      // conv2's kernel in fragment order
             TOP(e, st, OP_CONV_FWD + 1, mi_conv2d_enc12_fwd(st, d.dtype, frames, frames_u8 ? 2 : 1, idx, B, g.ih[0], g.iw[0], e->wtptr(0), e->bptr(1), e->wtptr(2), e->bptr(3),
                                                          e->at(e->W.act[1]), bits12 ? e->at(e->W.bits_act1) : nullptr, e->at(e->W.act[2]), &launched));
             if (launched) { if (bits12) e->bits1_ok = 1; i = 1; continue; }
@@ -327,9 +291,8 @@ int run_encoder(VaeEngine* e, void* st, const void* frames, int frames_u8, const
             TOP(e, st, OP_CONV_FWD + i, mi_ares_conv(st, d.dtype, 0, x, B, e->at(e->W.wfrag[0]), e->bptr(7), 1, nullptr, e->at(e->W.act[4]), &launched));
             if (launched) continue;
         }
-        // conv3 (64 -> 128 channels, k = 4): the register-weight kernel loads its weights from their fragment-ordered copy (round 6; MI355_RC_WFRAG=0: from the K-contiguous one)
-        if (i == 2 && e->ares_ok && e->ares_mid && rc_wfrag_enabled()) mi_tl_rc_wfrag = e->at(e->W.wfrag[6]);
-        struct WfragGuard { ~WfragGuard() { mi_tl_rc_wfrag = nullptr; } } wfrag_guard;
+        // conv3 (64 -> 128 channels, k = 4): the register-weight kernel loads its weights from their fragment-ordered copy (round 6)
+        if (i == 2 && e->ares_ok && e->ares_mid) CK(mi_rwconv_next_weights_fragment_ordered(e->at(e->W.wfrag[6])));
         TOP(e, st, OP_CONV_FWD + i, mi_conv2d_nhwc_fwd_bits(st, d.dtype, x, i == 0 ? idx : nullptr, i == 0 ? (frames_u8 ? 2 : 1) : 0, B, g.ih[i], g.iw[i], g.c[i],
                               e->wtptr(2 * i), 1, e->bptr(2 * i + 1), 4, 4, g.c[i + 1], 1, e->at(e->W.act[i + 1]), bits ? e->at(e->W.bits_act1) : nullptr, bits ? &e->bits1_ok : nullptr));
     }
@@ -362,8 +325,7 @@ int run_decoder(VaeEngine* e, void* st, int B, int last = 4, int want_bits = 0) 
             TOP(e, st, OP_DECONV_FWD + i, mi_ares_conv(st, d.dtype, 2, e->at(e->W.dec[1]), B, e->at(e->W.wfrag[5]), e->bptr(15), 1, nullptr, e->at(e->W.dec[2]), &launched));
             if (launched) continue;
         }
-        if (i == 2 && e->ares_ok && rc_small_frag_ok(e) && rc_wfrag_enabled()) mi_tl_rc_wfrag = e->at(e->W.wfrag[8]);      // deconv3: its kernel in the gather form's fragment order (round 6)
-        struct WfragGuard3 { ~WfragGuard3() { mi_tl_rc_wfrag = nullptr; } } wfrag_guard3;
+        if (i == 2 && e->ares_ok && rc_small_frag_ok(e)) CK(mi_rwconv_next_weights_fragment_ordered(e->at(e->W.wfrag[8])));      // deconv3: its kernel in the gather form's fragment order (round 6)
         TOP(e, st, OP_DECONV_FWD + i, mi_deconv2d_nhwc_fwd_bits(st, d.dtype, e->at(e->W.dec[i]), B, g.dh[i], g.dw[i], g.dc[i], e->wptr(12 + 2 * i), e->bptr(13 + 2 * i),
                                 DEC_K[i], DEC_K[i], g.dc[i + 1], i < 3 ? 1 : 0, e->at(e->W.dec[i + 1]), bits ? e->at(e->W.bits_dec3) : nullptr, bits ? &e->bits3_ok : nullptr));
     }
@@ -497,8 +459,6 @@ int mi_vae_debug_check_guards(void* h, int* n_regions, int* n_bad, int guard_ind
 void mi_vae_destroy(void* h) {
     VaeEngine* e = (VaeEngine*)h;
     if (e && e->side_ok == 1) { hipStreamDestroy(e->side); hipEventDestroy(e->ev_ready); hipEventDestroy(e->ev_done); }
-    if (e && e->third_ok == 1) { hipStreamDestroy(e->third); hipEventDestroy(e->ev_lat); hipEventDestroy(e->ev_third); }
-    if (e && e->main2_ok == 1) { hipStreamDestroy(e->main2); hipEventDestroy(e->ev_in); hipEventDestroy(e->ev_out); }
     free(h);
 }
 
@@ -558,20 +518,13 @@ int mi_vae_forward(void* h, void* stream, const void* src, const void* tgt, int 
     int nblk = 0;
     e->fwd_produced = 0;
     if (tail_try) {
-        static int kev = -1;
-        if (kev < 0) { const char* ev = getenv("MI355_KEVENT"); kev = ev ? atoi(ev) : 1; }
-        const bool carry = kev && kev != 3 && e->side_ok == 1 && e->defer_fin && e->tm.mode != 1;      // (MI355_KEVENT=3: in the backward pass only)      // (mi_vae_train_step: nothing else is issued between this kernel and the backward pass)
+        const bool carry = e->side_ok == 1 && e->defer_fin && e->tm.mode != 1;      // (mi_vae_train_step: nothing else is issued between this kernel and the backward pass)
         if (carry) mi_tl_stop_event = e->ev_ready;
         TOP(e, stream, OP_DECONV_FWD + 3, mi_deconv2d_tail_fused(stream, d.dtype, e->at(e->W.dec[3]), B, g.dh[3], g.dw[3], g.dc[3], e->wptr(18), e->wtptr(18), e->bptr(19), DEC_K[3], DEC_K[3], g.dc[4],
                                            tgt, frames_u8, idx, (long long)P, d.loss_kind, inv_batch, e->at(e->W.gdec[3]), e->gptr(18),
                                            (float*)e->at(e->W.partial), (float*)e->at(e->W.bpart), e->partial_cap, &nblk, e->at(e->W.tail_slabs), e->W.tail_slab_bytes, 0));
         if (carry) { e->fwd_produced = (nblk > 0 && mi_tl_stop_event == nullptr) ? 1 : 0; mi_tl_stop_event = nullptr; }
         if (nblk > 0) { e->tail_fused = 1; e->tail_nblk = nblk; }      // (its slab reduce runs inside mi_vae_backward)
-        {
-            static int defer_on = -1;
-            if (defer_on < 0) { const char* ev = getenv("MI355_DEFER"); defer_on = (ev && ev[0] == '0') ? 0 : 1; }
-            if (nblk > 0 && !defer_on) { CK(mi_deconv2d_tail_reduce(stream, e->at(e->W.tail_slabs), nblk, e->gptr(18))); e->tail_nblk = 0; }
-        }
     }
     // (the fused forms never store the logits: only the loss partial sums and dlogits / the gradients leave the kernel)
     if (nblk == 0) TOP(e, stream, OP_DECONV_FWD + 3, mi_deconv2d_nhwc_fwd_bce_u8(stream, d.dtype, e->at(e->W.dec[3]), B, g.dh[3], g.dw[3], g.dc[3], e->wptr(18), e->bptr(19), DEC_K[3], DEC_K[3], g.dc[4],
@@ -619,59 +572,26 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
     static int two_streams = -1;
     if (two_streams < 0) { const char* ev = getenv("MI355_BWD_STREAMS"); two_streams = (ev && ev[0] == '0') ? 0 : 1; }
     if (two_streams && !e->side_ok) {
-        // MI355_SIDE_PRIO=-1 / 1: the filter-gradient queue above / below the caller's queue in the hardware scheduler's priority order (default 0: equal; A/B knob)
-        static int side_prio = -99;
-        if (side_prio == -99) { const char* ev = getenv("MI355_SIDE_PRIO"); side_prio = ev ? atoi(ev) : 0; }
-        int prio_lo = 0, prio_hi = 0;
-        if (side_prio != 0) hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);        // (numerically: lowest priority = largest value)
-        const int prio = side_prio < 0 ? prio_hi : prio_lo;
-        // MI355_CU_SPLIT=N (measurement aid): the two queues of the backward pass on DISJOINT compute units -- mask bits [0, N) for the caller-side queue (an
-        // engine stream the pass forks to and joins from), [N, 256) for the filter-gradient queue; KFD deals the mask bits round-robin over the eight XCDs, so both halves
-        // span all of them.  Tells time-slicing of whole CUs (147 KB-LDS blocks) from HBM / L2 interference: DESIGN 3.16.
-        const int cu_split = cu_split_env();
-        uint32_t mask_side[8], mask_main[8];
-        for (int w = 0; w < 8; ++w) { mask_side[w] = 0; mask_main[w] = 0; }
-        for (int b = 0; b < 256; ++b) { if (b < cu_split) mask_main[b >> 5] |= 1u << (b & 31); else mask_side[b >> 5] |= 1u << (b & 31); }
-        if (cu_split > 0 && !e->main2_ok) {
-            if (hipExtStreamCreateWithCUMask(&e->main2, 8, mask_main) == hipSuccess && hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&e->ev_out, hipEventDisableTiming) == hipSuccess) e->main2_ok = 1;
-            else e->main2_ok = -1;
-        }
-        if ((cu_split > 0 ? hipExtStreamCreateWithCUMask(&e->side, 8, mask_side) : side_prio == 0 ? hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) : hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, prio)) == hipSuccess &&
-            hipEventCreateWithFlags(&e->ev_ready, ready_event_flags()) == hipSuccess &&
-            hipEventCreateWithFlags(&e->ev_done, ready_event_flags()) == hipSuccess) e->side_ok = 1;
+        if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) == hipSuccess &&
+            hipEventCreateWithFlags(&e->ev_ready, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&e->ev_done, hipEventDisableTiming) == hipSuccess) e->side_ok = 1;
         else e->side_ok = -1;
     }
-    static int third_on = -1;                             // MI355_THIRD=1: the latent layers' filter / bias gradients, the tail's slab sum and the loss finalisation on a third stream
-    if (third_on < 0) { const char* ev = getenv("MI355_THIRD"); third_on = (ev && ev[0] == '1') ? 1 : 0; }
-    if (third_on && two_streams && !e->third_ok) {
-        if (hipStreamCreateWithFlags(&e->third, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e->ev_lat, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&e->ev_third, hipEventDisableTiming) == hipSuccess) e->third_ok = 1;
-        else e->third_ok = -1;
-    }
     const bool fork = two_streams && e->side_ok == 1 && e->tm.mode != 1;      // per-op timing (mode 1) wants one op at a time
-    const bool split_cus = fork && cu_split_env() > 0 && e->main2_ok == 1 && part == 0;
-    if (split_cus) { hipEventRecord(e->ev_in, (hipStream_t)stream); hipStreamWaitEvent(e->main2, e->ev_in, 0); st = (void*)e->main2; }
-    struct SplitGuard { bool on; VaeEngine* e; void* caller; ~SplitGuard() { if (on) { hipEventRecord(e->ev_out, e->main2); hipStreamWaitEvent((hipStream_t)caller, e->ev_out, 0); } } } split_guard{split_cus, e, stream};
     struct StopEventGuard { ~StopEventGuard() { mi_tl_stop_event = nullptr; } } stop_guard;      // (see mi_vae_forward)
     void* sw = fork ? (void*)e->side : st;                                     // stream of the filter gradients
-    // Hand-over of a gradient tensor from the caller's stream to the filter-gradient stream.  Round 3 form: hipEventRecord behind the producing kernel -- a marker
-    // packet of its own that costs the PRODUCING queue a 6-8 us bubble each time (six per step on the critical queue, profiles/r03_d).  Round 4 (MI355_KEVENT=0: the record form; measured 0.913 -> 0.896 ms per step, two interleaved pairs on one box):
-    // the producing kernel itself carries the event as the completion signal of its dispatch packet (hipExtLaunchKernelGGL's stop event, mi_internal.hpp MI_LAUNCH):
-    // no marker on the caller's queue, and the other queue's wait resolves the moment that kernel retires.
-    static int kev_env = -1;
-    if (kev_env < 0) { const char* ev = getenv("MI355_KEVENT"); kev_env = ev ? atoi(ev) : 1; }
-    const int kev = kev_env;
-    bool produced = fork && kev && e->fwd_produced && (part == 0 || part == 1);      // ev_ready already rides on the last kernel issued on st
+    // Hand-over of a gradient tensor from the caller's stream to the filter-gradient stream: the producing kernel itself carries the event as the completion signal of its
+    // dispatch packet (hipExtLaunchKernelGGL's stop event, mi_internal.hpp MI_LAUNCH), so the other queue's wait resolves the moment that kernel retires.  Round 4: a
+    // hipEventRecord marker behind the kernel cost the producing queue a 6-8 us bubble each time (profiles/r03_d); 0.913 -> 0.896 ms per step.
+    bool produced = fork && e->fwd_produced && (part == 0 || part == 1);      // ev_ready already rides on the last kernel issued on st
     e->fwd_produced = 0;
-    bool mid_flush_pending = false;
     auto release = [&]() {                                                     // "everything issued on st so far is an input of the next sw op"
         if (fork) { if (!produced) hipEventRecord(e->ev_ready, (hipStream_t)st); hipStreamWaitEvent(e->side, e->ev_ready, 0); }
         produced = false;
     };
     // call(): a layer op whose single kernel produces the tensor the NEXT release() hands over
-    auto arm = [&]() { produced = false; if (fork && kev) mi_tl_stop_event = e->ev_ready; };
-    auto armed_ok = [&]() { if (fork && kev) { produced = mi_tl_stop_event == nullptr; mi_tl_stop_event = nullptr; } };
+    auto arm = [&]() { produced = false; if (fork) mi_tl_stop_event = e->ev_ready; };
+    auto armed_ok = [&]() { if (fork) { produced = mi_tl_stop_event == nullptr; mi_tl_stop_event = nullptr; } };
     // In two-stream mode the split reductions of the filter gradients are deferred to the end of the side stream's work (they are tiny, but
     // next to a big input-gradient kernel each takes 15-30 us instead of ~7): every layer writes its slabs into its own scratch region.
     const bool defer = fork && W.scratch_bytes > 0;
@@ -685,20 +605,16 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
     const long long scratch_sz = defer ? region : W.scratch_bytes;
     // latent-layer filter / bias gradients (dense1, heads): slabs of their row splits in the region that belongs to the stream they are issued on
     // (reused in stream order: each call's ordered reduce is issued right behind its kernel)
-    // End of a full two-stream pass (round 4, MI355_TAIL_FUSE=0 switches it off): the slab sums of the encoder head, the decoder tail and the latent layers' filter /
-    // bias gradients -- seven to eleven latency-bound launches in a row on the caller's stream -- are recorded and issued as ONE launch (mi_small_reduce_flush);
-    // every job then keeps its own piece of the tail scratch until that launch.
-    static int tail_fuse_on = -1;
-    if (tail_fuse_on < 0) { const char* ev = getenv("MI355_TAIL_FUSE"); tail_fuse_on = (ev && ev[0] == '0') ? 0 : 1; }
+    // End of a full two-stream pass (round 4): the slab sums of the encoder head, the decoder tail and the latent layers' filter / bias gradients -- seven to eleven
+    // latency-bound launches in a row on the caller's stream -- are recorded and issued as ONE launch (mi_small_reduce_flush); every job then keeps its own piece of the
+    // tail scratch until that launch.
     bool tail_defer = false;
     long long tail_bump = 0;
     // A backward PART on two streams (the data-parallel step; round 6): the small slab sums of the part's filter-gradient stream -- the latent layer's filter + bias gradient, the bias
     // rows of a lone raw-staged filter gradient -- are recorded the same way and issued as ONE launch in front of the part's join (they were two or three ~5 us launches per part on the
-    // stream that ends the data-parallel step); MI355_PART_FUSE=0: a launch each.  (tail_defer belongs to the full pass, part 0: the two never meet.)
-    static int part_fuse_on = -1;
-    if (part_fuse_on < 0) { const char* ev = getenv("MI355_PART_FUSE"); part_fuse_on = (ev && ev[0] == '0') ? 0 : 1; }
+    // stream that ends the data-parallel step).  (tail_defer belongs to the full pass, part 0: the two never meet.)
     bool side_defer = false;
-    if (part_fuse_on && fork && part != 0 && W.scratch_tail_bytes > 0 && e->tm.mode != 1) { mi_small_reduce_defer(1); mi_small_reduce_bind(sw); side_defer = true; }
+    if (fork && part != 0 && W.scratch_tail_bytes > 0 && e->tm.mode != 1) { mi_small_reduce_defer(1); mi_small_reduce_bind(sw); side_defer = true; }
     struct SrGuard { bool* on; bool* on2; ~SrGuard() { if (*on || *on2) mi_small_reduce_defer(0); } } sr_guard{&tail_defer, &side_defer};
     auto small_ws = [&](void* s_, long long need, long long* bytes) -> void* {
         if ((tail_defer && s_ == st) || (side_defer && s_ == sw)) {
@@ -712,20 +628,13 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
             mi_small_reduce_flush(s_);
         }
         if (fork && s_ == (void*)e->side) { *bytes = W.scratch_side_bytes; return e->at(W.scratch_side); }
-        if (e->third_ok == 1 && s_ == (void*)e->third) { *bytes = W.scratch_third_bytes; return e->at(W.scratch_third); }
         *bytes = W.scratch_main_bytes; return e->at(W.scratch_main);
     };
-    auto bias_grad = [&](void* s_, const void* x, long long M, int N, float* out) -> int {
-        long long nb = 0; void* ws_ = small_ws(s_, mi_colsum_scratch_bytes(d.dtype, M, N), &nb);
-        return mi_colsum_ws(s_, d.dtype, x, M, N, out, ws_, nb);
-    };
     // round 4: the latent layers' BiasAddGrad rides on their filter gradient as one more row of the same product (mi_gemm_wgrad_bias_ws: a column of ones in the
-    // loader) -- two launches less at the end of the pass; MI355_DENSE_BIAS_FUSED=0: the separate column sums
-    static int bias_fused = -1;
-    if (bias_fused < 0) { const char* ev = getenv("MI355_DENSE_BIAS_FUSED"); bias_fused = (ev && ev[0] == '0') ? 0 : 1; }
+    // loader) -- two launches less at the end of the pass
     auto dense_wgrad = [&](void* s_, const void* a, const void* dy, int M, int K, int N, float* dw, float* db) -> int {
         long long nb = 0; void* ws_ = small_ws(s_, mi_gemm_wgrad_scratch_bytes(d.dtype, M, K, N), &nb);
-        return mi_gemm_wgrad_bias_ws(s_, d.dtype, a, dy, M, K, N, dw, bias_fused ? db : nullptr, ws_, nb);
+        return mi_gemm_wgrad_bias_ws(s_, d.dtype, a, dy, M, K, N, dw, db, ws_, nb);
     };
     if (defer) mi_tapwgrad_defer(1);
     auto join = [&]() {
@@ -750,12 +659,10 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
     if (slab16 < 0) { const char* ev = getenv("MI355_SLAB_BF16"); slab16 = (ev && ev[0] == '0') ? 0 : 1; }
     struct SlabGuard { int prev; bool on; ~SlabGuard() { if (on) mi_tapwgrad_slab_bf16(prev); } } slab_guard{-1, false};
     if (slab16 && d.dtype == MI_BF16) { slab_guard.prev = mi_tapwgrad_slab_bf16(1); slab_guard.on = true; }
-    static int late_on = -1;                              // MI355_LATE_DENSE=0: dense1 / heads filter gradients on the filter-gradient stream as in round 2
-    if (late_on < 0) { const char* ev = getenv("MI355_LATE_DENSE"); late_on = (ev && ev[0] == '0') ? 0 : 1; }
-    const bool late_dense = late_on && fork && part == 0;
-    const bool use_third = late_dense && third_on && e->third_ok == 1;
-    static int heads_main = -1;                           // MI355_HEADS_MAIN=0: the heads' filter / bias gradient stay on the filter-gradient stream behind a fused encoder head
-    if (heads_main < 0) { const char* ev = getenv("MI355_HEADS_MAIN"); heads_main = (ev && ev[0] == '0') ? 0 : 1; }
+    // Full two-stream backward (round 3): the latent-side filter / bias gradients (dense1, heads: ~60 us of the filter-gradient stream, which is the longer one) are
+    // issued on the caller's stream at the very END of the pass, where that stream would otherwise wait ~100 us for the other one; their operands (gdec0, z, dheads,
+    // act4) stay intact until then and no event is needed for them.  The parts and the one-stream pass issue them in place on the filter-gradient stream.
+    const bool late_dense = fork && part == 0;
     if (part == 0 || part == 1) {
         for (int i = 3; i >= 0; --i) {                       // deconv(i+1): input dec[i] -> output dec[i+1]
             if (i == 3 && e->tail_fused) continue;           // deconv4's two gradients were computed by the forward pass's decoder-tail kernel
@@ -769,38 +676,25 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
                 if (launched) continue;
             }
             if (i > 0) arm();                                // its output is the next layer's filter-gradient operand
-            if (i == 1 && e->ares_ok && e->ares_mid && rc_wfrag_enabled()) mi_tl_rc_wfrag = e->at(W.wfrag[7]);      // deconv2's input gradient: conv form, fragment-ordered weights
-            if (i == 2 && e->ares_ok && rc_small_frag_ok(e) && rc_wfrag_enabled() && rc_wfrag6_enabled()) mi_tl_rc_wfrag = e->at(W.wfrag[10]);   // deconv3's: conv form, k = 5 (pack form 6)
-            struct WfragGuard2 { ~WfragGuard2() { mi_tl_rc_wfrag = nullptr; } } wfrag_guard2;
+            if (i == 1 && e->ares_ok && e->ares_mid) CK(mi_rwconv_next_weights_fragment_ordered(e->at(W.wfrag[7])));      // deconv2's input gradient: conv form, fragment-ordered weights
+            if (i == 2 && e->ares_ok && rc_small_frag_ok(e)) CK(mi_rwconv_next_weights_fragment_ordered(e->at(W.wfrag[10])));   // deconv3's: conv form, k = 5 (pack form 6)
             TOP(e, st, OP_DECONV_DGRAD + i, mi_deconv2d_nhwc_dgrad_bits(st, d.dtype, gy, B, g.dh[i + 1], g.dw[i + 1], g.dc[i + 1], e->wtptr(12 + 2 * i), 1, DEC_K[i], DEC_K[i], g.dc[i],
                                       i > 0 ? e->at(W.dec[i]) : nullptr, (i == 3 && e->bits3_ok) ? e->at(W.bits_dec3) : nullptr, e->at(W.gdec[i])));
             if (i > 0) armed_ok();
         }
         e->b4_fused = 0; e->tail_fused = 0;
-        {
-            // Round 5: the slab sums of the three DECODER filter gradients are issued here, behind deconv1's filter gradient, instead of with the encoder's at the very end:
-            // the filter-gradient stream idles ~20 us at this point (conv4's filter gradient waits for the latent chain dense1.dgrad -> reparam.bwd -> heads.dgrad on the
-            // caller's stream, six small launches that leave the chip nearly empty), and the reduce at the end of the pass -- which ends the longer of the two queues --
-            // shrinks from six layers to three.  MI355_MID_FLUSH=0: one reduce at the end (A/B runs).
-            static int mid_flush = -1;
-            if (mid_flush < 0) { const char* ev = getenv("MI355_MID_FLUSH"); mid_flush = (ev && ev[0] == '0') ? 0 : 1; }
-            // MI355_MID_FLUSH_LATE=1 (round 6 A/B): the same launch on the same queue behind the same kernel, but SUBMITTED behind the latent chain's launches (dense1.dgrad,
-            // reparam.bwd, heads.dgrad) -- on boxes whose dispatcher serves the older submission first the chain's 128-block kernels otherwise queue behind the reduce's 1,864 blocks
-            static int mid_late = -1;
-            if (mid_late < 0) { const char* ev = getenv("MI355_MID_FLUSH_LATE"); mid_late = (ev && ev[0] == '1') ? 1 : 0; }
-            mid_flush_pending = defer && part == 0 && mid_flush && mid_late;
-            if (defer && part == 0 && mid_flush && !mid_late) CK(mi_tapwgrad_flush(sw));
-        }
+        // Round 5: the slab sums of the three DECODER filter gradients are issued here, behind deconv1's filter gradient, instead of with the encoder's at the very end:
+        // the filter-gradient stream idles ~20 us at this point (conv4's filter gradient waits for the latent chain dense1.dgrad -> reparam.bwd -> heads.dgrad on the
+        // caller's stream, six small launches that leave the chip nearly empty), and the reduce at the end of the pass -- which ends the longer of the two queues --
+        // shrinks from six layers to three.
+        if (defer && part == 0) CK(mi_tapwgrad_flush(sw));
         if (e->tail_nblk > 0 && !late_dense) {               // deconv4's filter gradient: the fused tail's per-block sums -> the gradient buffer
             CK(mi_deconv2d_tail_reduce(st, e->at(W.tail_slabs), e->tail_nblk, e->gptr(18)));      // (full two-stream backward: at the tail of the caller's stream, below)
             e->tail_nblk = 0;
         }
-        // dense1: h = z W1 + b1.  Full two-stream backward (round 3): the four latent-side filter / bias gradients (dense1, heads: ~60 us of the
-        // filter-gradient stream, which is the longer one) are issued on the caller's stream at the very END of the pass, where that stream would
-        // otherwise wait ~100 us for the other one; their operands (gdec0, z, dheads, act4) stay intact until then and no event is needed for them.
+        // dense1: h = z W1 + b1
         if (!late_dense) {
             release();
-            if (!bias_fused) TOP(e, sw, OP_DENSE1_BIAS, bias_grad(sw, e->at(W.gdec[0]), B, g.flat, e->gptr(11)));
             TOP(e, sw, OP_DENSE1_WGRAD, dense_wgrad(sw, e->at(W.z), e->at(W.gdec[0]), B, d.z_dim, g.flat, e->gptr(10), e->gptr(11)));
         }
         TOP(e, st, OP_DENSE1_DGRAD, mi_gemm_bias_act(st, d.dtype, e->at(W.gdec[0]), B, g.flat, e->wptr(10), 1, d.z_dim, nullptr, 0, nullptr, e->at(W.dz_slab), 1, e->ns_dz));
@@ -814,47 +708,24 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
                                  eps, (const float*)e->at(W.kl_row), d.beta, kl_floor, inv_batch, B, d.z_dim, e->at(W.dheads)));
         if (!late_dense) {
             release();
-            if (!bias_fused) TOP(e, sw, OP_HEADS_BIAS, bias_grad(sw, e->at(W.dheads), B, 2 * d.z_dim, e->gptr(9)));
             TOP(e, sw, OP_HEADS_WGRAD, dense_wgrad(sw, e->at(W.act[4]), e->at(W.dheads), B, g.flat, 2 * d.z_dim, e->gptr(8), e->gptr(9)));
         }
-        if (!use_third) arm();                               // gact4: conv4's filter-gradient operand
+        arm();                                               // gact4: conv4's filter-gradient operand
         TOP(e, st, OP_HEADS_DGRAD, mi_gemm_bias_act(st, d.dtype, e->at(W.dheads), B, 2 * d.z_dim, e->wptr(8), 1, g.flat, nullptr, 0, e->at(W.act[4]), e->at(W.gact[4]), 0, 1));
-        if (!use_third) armed_ok();
-        if (mid_flush_pending) { mid_flush_pending = false; CK(mi_tapwgrad_flush(sw)); }
-        if (use_third) {
-            // everything the latent layers' gradients read exists from here on (gdec0, z, dheads, act4; the tail's slabs and loss partials since the forward pass): they run on
-            // their own stream under the encoder half instead of serialising ~70 us of small launches at the end of the caller's stream
-            hipStream_t s3 = e->third;
-            hipEventRecord(e->ev_lat, (hipStream_t)st); hipStreamWaitEvent(s3, e->ev_lat, 0);
-            if (!bias_fused) TOP(e, s3, OP_DENSE1_BIAS, bias_grad(s3, e->at(W.gdec[0]), B, g.flat, e->gptr(11)));
-            TOP(e, s3, OP_DENSE1_WGRAD, dense_wgrad(s3, e->at(W.z), e->at(W.gdec[0]), B, d.z_dim, g.flat, e->gptr(10), e->gptr(11)));
-            if (!bias_fused) TOP(e, s3, OP_HEADS_BIAS, bias_grad(s3, e->at(W.dheads), B, 2 * d.z_dim, e->gptr(9)));
-            TOP(e, s3, OP_HEADS_WGRAD, dense_wgrad(s3, e->at(W.act[4]), e->at(W.dheads), B, g.flat, 2 * d.z_dim, e->gptr(8), e->gptr(9)));
-            if (e->tail_nblk > 0) { CK(mi_deconv2d_tail_reduce(s3, e->at(W.tail_slabs), e->tail_nblk, e->gptr(18))); e->tail_nblk = 0; }
-            if (e->fin.pending) {
-                e->fin.pending = 0;
-                TOP(e, s3, OP_FINALIZE, mi_vae_finalize_losses_flat(s3, (const float*)e->at(W.partial), e->fin.nblk, (const float*)e->at(W.kl_row), e->fin.kl_floor, e->fin.B, e->fin.inv_batch,
-                                               (float*)e->at(W.out2), e->fin.metrics3, e->fin.metric_weight, (const float*)e->at(W.bpart), e->fin.nblk, d.ct, e->fin.dbias));
-            }
-            hipEventRecord(e->ev_third, s3);
-        }
+        armed_ok();
     }
     if (upper || lower) {
-        bool enc_fused = false, dense_done = false, pair_used = false;
+        bool enc_fused = false, pair_used = false;
         for (int i = NCONV - 1; i >= 0; --i) {               // conv(i+1): input act[i] -> output act[i+1]
             if (i == NCONV - 1 ? !upper : !lower) continue;
             const void* gy = e->at(W.gact[i + 1]);
             const void* x = i == 0 ? (const void*)src : e->at(W.act[i]);
-            // The filter-gradient stream is the longer one of the two: conv1 has no input gradient, and since the register-weight kernels shortened
-            // conv2's / conv3's input gradients the caller's stream has room for one more -- the filter gradients of conv1 AND conv3 run there (mask 5,
-            // measured against 1 / 3 / 9 / 13 interleaved on one box: 1.068 vs 1.090 / 1.111 / 1.078 / 1.079 ms per step; moving a decoder layer's
-            // filter gradient instead: no gain), without the shared split scratch, which the other stream may still be using (fp32 atomics into dW).
-            // MI355_WGRAD_MAIN_MASK: bit i = conv(i+1).
-            // Round 3: with the decoder tail fused into the forward pass (its two gradient launches were the head of both streams) the filter-gradient
-            // stream is the shorter one again and takes conv3's filter gradient back: mask 1 (0.969 vs 0.984 / 0.988 / 0.992 / 1.014 ms for 5 / 3 / 0 / 4).
-            static int main_mask = -2;
-            if (main_mask == -2) { const char* ev = getenv("MI355_WGRAD_MAIN_MASK"); main_mask = ev ? atoi(ev) : -1; }
-            const int mm = main_mask >= 0 ? main_mask : (tail_was_fused ? 1 : 5);
+            // Filter gradients issued on the caller's stream (mask bit i = conv(i+1)) without the shared split scratch, which the other stream may still be using.
+            // The filter-gradient stream is the longer one of the two: conv1 has no input gradient, and since the register-weight kernels shortened conv2's / conv3's
+            // input gradients the caller's stream has room for one more -- conv1 AND conv3 (mask 5: 1.068 vs 1.090 / 1.111 / 1.078 / 1.079 ms per step for
+            // 1 / 3 / 9 / 13).  Round 3: with the decoder tail fused into the forward pass the filter-gradient stream is the shorter one again and takes conv3's
+            // filter gradient back: mask 1 (0.969 vs 0.984 / 0.988 / 0.992 / 1.014 ms for 5 / 3 / 0 / 4).
+            const int mm = tail_was_fused ? 1 : 5;
             const bool on_main = ((mm >> i) & 1) != 0;
             void* sg = on_main ? st : sw;
             if (i == 0 && enc_fused) continue;               // conv1's filter / bias gradient came out of the fused encoder-head kernel below
@@ -870,18 +741,7 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
             }();
             if (own) mi_tapwgrad_defer_pause(0);
             CK(rcw);
-            if (i == 1 && late_dense && !use_third && tail_fuse_on && !tail_defer) { mi_small_reduce_defer(1); mi_small_reduce_bind(st); tail_defer = true; }      // from here to the end of the pass every small slab sum on st is one job of the fused launch
-            // MI355_DENSE_EARLY=1 (round 4 A/B): the latent layers' filter gradients in FRONT of the encoder-head kernel instead of behind it: behind it they only
-            // start when conv2's filter gradient on the other stream releases its compute units (64 KB of LDS next to 147 KB: no co-residence) and end the pass late
-            static int dense_early = -1;
-            if (dense_early < 0) { const char* ev = getenv("MI355_DENSE_EARLY"); dense_early = (ev && ev[0] == '1') ? 1 : 0; }
-            if (i == 1 && dense_early && late_dense && !use_third && tail_defer && !dense_done) {
-                TOP(e, st, OP_DENSE1_WGRAD, dense_wgrad(st, e->at(W.z), e->at(W.gdec[0]), B, d.z_dim, g.flat, e->gptr(10), bias_fused ? e->gptr(11) : nullptr));
-                if (!bias_fused) TOP(e, st, OP_DENSE1_BIAS, bias_grad(st, e->at(W.gdec[0]), B, g.flat, e->gptr(11)));
-                TOP(e, st, OP_HEADS_WGRAD, dense_wgrad(st, e->at(W.act[4]), e->at(W.dheads), B, g.flat, 2 * d.z_dim, e->gptr(8), bias_fused ? e->gptr(9) : nullptr));
-                if (!bias_fused) TOP(e, st, OP_HEADS_BIAS, bias_grad(st, e->at(W.dheads), B, 2 * d.z_dim, e->gptr(9)));
-                dense_done = true;
-            }
+            if (i == 1 && late_dense) { mi_small_reduce_defer(1); mi_small_reduce_bind(st); tail_defer = true; }      // from here to the end of the pass every small slab sum on st is one job of the fused launch
             if (i == 1 && d.dtype == MI_BF16 && e->bits1_ok && e->W.enc_slab_bytes > 0 && g.c[0] == 3 && g.c[1] == 32 && g.c[2] == 64) {
                 // conv2's input gradient feeds nothing but conv1's filter gradient: both in one launch, the 99 MB tensor between them never exists (enchead_tile.hpp)
                 int nblk = 0;
@@ -905,28 +765,13 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
                                         e->at(W.act[i]), (i == 1 && e->bits1_ok) ? e->at(W.bits_act1) : nullptr, e->at(W.gact[i])));
             if (i > 1) armed_ok();
         }
-        static int dbg_skip_tail = -1;                       // MI355_DBG_SKIP_TAIL=1 (wrong results): how much of the step the small launches at the end of the caller's stream are
-        if (dbg_skip_tail < 0) { const char* ev = getenv("MI355_DBG_SKIP_TAIL"); dbg_skip_tail = (ev && ev[0] == '1') ? 1 : 0; }
-        if (late_dense && dbg_skip_tail) { if (defer) mi_tapwgrad_flush(sw); e->tail_nblk = 0; e->fin.pending = 0; }
-        else
-        if (late_dense && !use_third) {                      // the tails of both streams: dense1 + the decoder tail's slab sums here, the heads on the other one
-            if (tail_fuse_on && !tail_defer) { mi_small_reduce_defer(1); mi_small_reduce_bind(st); tail_defer = true; }
+        if (late_dense) {                                    // the tails of both streams: dense1 + the decoder tail's slab sums here, the heads on the one that ends first
             // round 6: dense1's and the heads' filter + bias gradients as ONE launch when both are issued here on the caller's stream (a fused encoder head in front): the two
-            // ~190-block grids of a latency-bound kernel ran back to back on the step's critical tail (MI355_DENSE_PAIR=0: two launches; per-op timing keeps them apart)
-            const bool pair = !dense_done && bias_fused && enc_fused && heads_main && e->tm.mode != 1;
-            // ... and the one-block loss finalisation IN FRONT of that launch (MI355_FIN_EARLY=0: behind the slab sums): the pair's blocks wait for conv2's filter gradient to release
-            // the CUs anyway, so the 4 us kernel and its boundary leave the serial tail (slab sums -> Adam)
-            static int fin_early = -1;
-            if (fin_early < 0) { const char* ev = getenv("MI355_FIN_EARLY"); fin_early = (ev && ev[0] == '0') ? 0 : 1; }
-            // ... and the small slab sums that are READY (the fused encoder head's, the decoder tail's) as their own launch in front of both (MI355_TAIL_EARLY_FLUSH=1; default: one launch with the
-            // pair's at the very end -- measured 0.7360 against 0.7380 ms): it runs while the pair waits for compute units, and the launch between the pair and Adam sums the pair's slabs only
-            static int early_flush = -1;
-            if (early_flush < 0) { const char* ev = getenv("MI355_TAIL_EARLY_FLUSH"); early_flush = (ev && ev[0] == '1') ? 1 : 0; }
-            if (pair && early_flush && tail_defer) {
-                if (e->tail_nblk > 0) { CK(mi_deconv2d_tail_reduce(st, e->at(W.tail_slabs), e->tail_nblk, e->gptr(18))); e->tail_nblk = 0; }
-                CK(mi_small_reduce_flush(st));
-            }
-            if (pair && fin_early && e->fin.pending && part == 0) {
+            // ~190-block grids of a latency-bound kernel ran back to back on the step's critical tail (per-op timing keeps them apart)
+            const bool pair = enc_fused && e->tm.mode != 1;
+            // ... and the one-block loss finalisation IN FRONT of that launch: the pair's blocks wait for conv2's filter gradient to release the CUs anyway, so the 4 us kernel
+            // and its boundary leave the serial tail (slab sums -> Adam)
+            if (pair && e->fin.pending) {
                 e->fin.pending = 0;
                 TOP(e, st, OP_FINALIZE, mi_vae_finalize_losses_flat(st, (const float*)e->at(W.partial), e->fin.nblk, (const float*)e->at(W.kl_row), e->fin.kl_floor, e->fin.B, e->fin.inv_batch,
                                                (float*)e->at(W.out2), e->fin.metrics3, e->fin.metric_weight, (const float*)e->at(W.bpart), e->fin.nblk, d.ct, e->fin.dbias));
@@ -938,33 +783,27 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
             if (pair && ws0 && ws1 && ((char*)ws0 + nb0 <= (char*)ws1 || (char*)ws1 + nb1 <= (char*)ws0)) {
                 TOP(e, st, OP_DENSE1_WGRAD, mi_gemm_wgrad_bias_pair_ws(st, d.dtype, e->at(W.z), e->at(W.gdec[0]), B, d.z_dim, g.flat, e->gptr(10), e->gptr(11), ws0, nb0,
                                                                        e->at(W.act[4]), e->at(W.dheads), B, g.flat, 2 * d.z_dim, e->gptr(8), e->gptr(9), ws1, nb1));
-                dense_done = true; pair_used = true;
-            }
-            if (!dense_done) {
-                if (!bias_fused) TOP(e, st, OP_DENSE1_BIAS, bias_grad(st, e->at(W.gdec[0]), B, g.flat, e->gptr(11)));
+                pair_used = true;
+            } else {
                 TOP(e, st, OP_DENSE1_WGRAD, dense_wgrad(st, e->at(W.z), e->at(W.gdec[0]), B, d.z_dim, g.flat, e->gptr(10), e->gptr(11)));
             }
             if (e->tail_nblk > 0) { CK(mi_deconv2d_tail_reduce(st, e->at(W.tail_slabs), e->tail_nblk, e->gptr(18))); e->tail_nblk = 0; }
             if (defer) { mi_tapwgrad_flush(sw); }            // (the deferred slab reductions first: they end the other stream's real work; join() then finds the list empty)
-            // the heads' gradients: behind a fused encoder head the caller's stream is the one that ends early (conv1's filter gradient is no longer a launch of its own)
-            void* sh = (enc_fused && heads_main) ? st : sw;
-            if (tail_defer && sh != st && !dense_done) { CK(mi_small_reduce_flush(st)); mi_small_reduce_defer(0); tail_defer = false; }      // (what follows is issued on the other stream: nothing of it may land in st's list)
-            if (!dense_done) {
-                if (!bias_fused) TOP(e, sh, OP_HEADS_BIAS, bias_grad(sh, e->at(W.dheads), B, 2 * d.z_dim, e->gptr(9)));
+            if (!pair_used) {
+                // the heads' gradients: behind a fused encoder head the caller's stream is the one that ends early (conv1's filter gradient is no longer a launch of its own)
+                void* sh = enc_fused ? st : sw;
+                if (tail_defer && sh != st) { CK(mi_small_reduce_flush(st)); mi_small_reduce_defer(0); tail_defer = false; }      // (what follows is issued on the other stream: nothing of it may land in st's list)
                 TOP(e, sh, OP_HEADS_WGRAD, dense_wgrad(sh, e->at(W.act[4]), e->at(W.dheads), B, g.flat, 2 * d.z_dim, e->gptr(8), e->gptr(9)));
             }
             if (tail_defer) { CK(mi_small_reduce_flush(st)); mi_small_reduce_defer(0); tail_defer = false; }
         }
-        if (use_third) { if (defer) mi_tapwgrad_flush(sw); hipStreamWaitEvent((hipStream_t)st, e->ev_third, 0); }
-        if (e->fin.pending && (part == 0 || part == 2 || part == 4)) {      // the deferred loss scalars: on the caller's stream, in front of its wait for the other one
+        if (e->fin.pending && (part == 0 || part == 2 || part == 4)) {      // the deferred loss scalars, where the pair launch did not take them
             e->fin.pending = 0;
-            // Round 5: behind the filter-gradient queue's last reduce instead (it ends ~20 us before the caller's queue does: the one-block kernel and its boundary leave
-            // the critical tail; everything it reads exists since the forward pass, what it writes -- the loss scalars, deconv4's bias gradient -- is read behind the join).
-            // MI355_FIN_SIDE=0: on the caller's stream as before.  Round 6: with dense1's and the heads' filter gradients in ONE launch the caller's queue ends first again
-            // (its last slab sum ~10 us before the other queue's): the kernel is back on the caller's stream unless MI355_FIN_SIDE=1 (0.7468 -> 0.7446, 0.7818 -> 0.7792 ms on two boxes).
-            static int fin_side = -1;
-            if (fin_side < 0) { const char* ev = getenv("MI355_FIN_SIDE"); fin_side = !ev ? 2 : ev[0] == '0' ? 0 : 1; }      // 2: by the tail's shape
-            void* sf = (fork && (fin_side == 1 || (fin_side == 2 && !pair_used)) && part == 0) ? sw : st;
+            // Round 5: behind the filter-gradient queue's last reduce (it ends ~20 us before the caller's queue does: the one-block kernel and its boundary leave the critical
+            // tail; everything it reads exists since the forward pass, what it writes -- the loss scalars, deconv4's bias gradient -- is read behind the join).  Round 6: with
+            // dense1's and the heads' filter gradients in ONE launch the caller's queue ends first again: the kernel goes in front of that launch instead (above;
+            // 0.7468 -> 0.7446, 0.7818 -> 0.7792 ms on two boxes).
+            void* sf = (fork && !pair_used && part == 0) ? sw : st;
             TOP(e, sf, OP_FINALIZE, mi_vae_finalize_losses_flat(sf, (const float*)e->at(W.partial), e->fin.nblk, (const float*)e->at(W.kl_row), e->fin.kl_floor, e->fin.B, e->fin.inv_batch,
                                            (float*)e->at(W.out2), e->fin.metrics3, e->fin.metric_weight, (const float*)e->at(W.bpart), e->fin.nblk, d.ct, e->fin.dbias));
         }
@@ -977,20 +816,16 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
 static int apply_adam(VaeEngine* e, void* stream, float alpha, const float* alpha_dev, float beta1, float beta2, float epsilon) {
     if (!e->grads || !e->m || !e->v) return mi_fail(MI_ERR_STATE, "mi_vae_apply_adam: engine created without optimiser buffers");
     // fp32 / bf16 storage: the optimiser launch writes the K-contiguous kernel copies as well (mi_adam_tf_layouts, round 4: one launch and one pass over the master
-    // weights less per step; same arithmetic, bit-identical parameters).  MI355_ADAM_LAYOUTS=0: Adam, then the transpose launch (split storage always).
-    static int layouts_on = -1;
-    if (layouts_on < 0) { const char* ev = getenv("MI355_ADAM_LAYOUTS"); layouts_on = (ev && ev[0] == '0') ? 0 : 1; }
-    if (layouts_on && e->d.dtype != MI_BF16X3) {
+    // weights less per step; same arithmetic, bit-identical parameters).  Split storage: Adam, then the transpose launch.
+    if (e->d.dtype != MI_BF16X3) {
         long long off[10]; int K[10], N[10];
         const int n = kernel_table(e, off, K, N);
-        // round 5: the fragment-ordered copies of conv4 / deconv1 (/ conv3 / deconv2) for the activation-resident kernels come out of the same launch (MI355_ADAM_FRAG=0: the
-        // separate ares_pack launch behind it, 5.6 us + a boundary at the head of the next step)
-        static int frag_on = -1;
-        if (frag_on < 0) { const char* ev = getenv("MI355_ADAM_FRAG"); frag_on = (ev && ev[0] == '0') ? 0 : 1; }
+        // round 5: the fragment-ordered copies of conv4 / deconv1 (/ conv3 / deconv2) for the activation-resident kernels come out of the same launch (the separate
+        // ares_pack launch cost 5.6 us + a boundary at the head of the next step)
         void* fp[20]; int ff[20];
         for (int i = 0; i < 20; ++i) { fp[i] = nullptr; ff[i] = -1; }
         bool mid = false;
-        const bool frag = frag_on && ares_eligible(e, &mid) && n == 10;
+        const bool frag = ares_eligible(e, &mid) && n == 10;
         if (frag) {      // kernel table: 0-3 conv1-4, 4 heads, 5 dense1, 6-9 deconv1-4
             fp[2 * 3] = e->at(e->W.wfrag[0]); ff[2 * 3] = 0; fp[2 * 3 + 1] = e->at(e->W.wfrag[1]); ff[2 * 3 + 1] = 1;      // conv4: forward (conv form), input gradient (gather form)
             fp[2 * 6] = e->at(e->W.wfrag[2]); ff[2 * 6] = 1; fp[2 * 6 + 1] = e->at(e->W.wfrag[3]); ff[2 * 6 + 1] = 0;      // deconv1: forward (gather form), input gradient (conv form)
@@ -1034,9 +869,7 @@ int mi_vae_train_step(void* h, void* stream, const void* src, const void* tgt, i
     VaeEngine* e = (VaeEngine*)h;
     CK(check_batch(e, B));
     struct FinGuard { VaeEngine* e; ~FinGuard() { e->defer_fin = 0; } } fin_guard{e};
-    static int defer_on = -1;                           // MI355_DEFER=0: loss finalisation and the tail's slab reduce right behind the forward pass (A/B runs)
-    if (defer_on < 0) { const char* ev = getenv("MI355_DEFER"); defer_on = (ev && ev[0] == '0') ? 0 : 1; }
-    e->defer_fin = defer_on;                            // forward + backward are issued together here: the loss scalars are finalised inside the backward pass
+    e->defer_fin = 1;                                   // forward + backward are issued together here: the loss scalars are finalised inside the backward pass
     CK(mi_vae_forward(h, stream, src, tgt, frames_u8, idx, B, inv_batch, eps, 1, 1, metrics3, metric_weight));
     CK(mi_vae_backward(h, stream, src, idx, eps, inv_batch, 0));
     return apply_adam(e, stream, alpha, nullptr, beta1, beta2, epsilon);

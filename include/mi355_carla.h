@@ -188,15 +188,17 @@ int mi_ares_pack_weights6(void* stream, const float* conv4_w, const float* decon
 /* round 6: ... plus the conv-form copies of the same two mid-layer kernels for the register-weight kernel (form 3: the order rwconv_conv_kernel<4, 2> loads its 64 weight fragments in, 256 KB
  * each): conv3_w -> wf6 (conv3 forward, vae/models.py:252), deconv2_w -> wf7 (deconv2's input gradient, Conv2D of dy behind :262).  NULL pairs are skipped. */
 int mi_ares_pack_weights8(void* stream, const float* conv4_w, const float* deconv1_w, const float* conv3_w, const float* deconv2_w, void* wf0, void* wf1, void* wf2, void* wf3, void* wf4, void* wf5, void* wf6, void* wf7);
-/* The NEXT register-weight launch of the calling thread reads its weights from `wf` instead of the K-contiguous copy: 1 KB contiguous per wave load in the kernel's prologue
- * (the K-contiguous copy gives 16 B per lane at a 1-2 KB lane stride).  Which form `wf` must hold follows from the call:
+/* Announces `wf` for the calling thread's NEXT call of mi_conv2d_nhwc_fwd[_bits], mi_deconv2d_nhwc_fwd[_bits], mi_deconv2d_nhwc_dgrad[_bits] or mi_conv2d_enc12_fwd.  That call
+ * always clears the announcement, whether it launches anything or not; if it runs the register-weight kernel below, that kernel reads its weights from `wf` instead of the
+ * K-contiguous copy: 1 KB contiguous per wave load in the kernel's prologue (the K-contiguous copy gives 16 B per lane at a 1-2 KB lane stride).  Which form `wf` must hold
+ * follows from the call:
  *   form 3 (above)  mi_conv2d_nhwc_fwd[_bits] of a 64 -> 128 channel k = 4 layer (conv3), mi_deconv2d_nhwc_dgrad[_bits] of a 128 -> 64 channel one (deconv2)
  *   form 4          mi_deconv2d_nhwc_fwd of the k = 5, 64 -> 32 channel layer (deconv3, vae/models.py:263): mi_ares_pack_weights(form 4) of its [5][5][32][64] kernel,
  *                   144 fragments of 1 KB ordered (output-parity class, tap of the 3 x 3 class window, 16-channel K step); fragments of taps outside the 5 x 5 kernel are never read
  *   form 6          mi_deconv2d_nhwc_dgrad[_bits] of the k = 5, 32 -> 64 channel layer (deconv3's input gradient): mi_ares_pack_weights(form 6) of deconv3's kernel read as [800][64],
  *                   2 x 50 fragments (32-wide output tile, the 50 live (tap, k-step) pairs of the 3 x 3 slot taps in the prologue's order)
  *   form 5          mi_conv2d_enc12_fwd: conv2's [4][4][32][64] HWIO kernel (vae/models.py:251), mi_ares_pack_weights(form 5), 64 fragments (32-wide output half, K step)
- * Consumed by that call whether or not the kernel it picks uses it; NULL clears.  Same values in the same registers: results are bit-identical either way. */
+ * NULL clears.  Same values in the same registers: results are bit-identical either way. */
 int mi_rwconv_next_weights_fragment_ordered(const void* wf);
 int mi_ares_conv(void* stream, int dtype, int form, const void* x, int B, const void* wf, const float* bias, int relu, const void* mask, void* out, int* launched);
 /* backward of conv2d_transpose wrt its input (= a plain s2 conv of dy) with fused ReluGrad mask */

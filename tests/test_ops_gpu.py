@@ -1425,6 +1425,52 @@ def test_register_weight_conv_reads_fragment_ordered_weights(which, B):
             L.mi_set_tuning(k_, v)
 
 
+def test_fragment_ordered_announcement_is_cleared_by_a_call_that_launches_nothing():
+    """mi_rwconv_next_weights_fragment_ordered applies to the NEXT call of the entries that take it, and that call clears it even when it launches nothing: mi_conv2d_enc12_fwd
+    on a geometry it declines (FH != 80) must not leave the announced copy for the thread's next register-weight launch.  The announced buffer is live memory holding zeros:
+    a stale read would give a wrong, not a faulting, conv3 forward."""
+    import ctypes
+    L = milib.get()
+    code, td = DT["bf16"]
+    rng = np.random.RandomState(11)
+    B, IH, IW, Ci, Co, k = 3, 18, 38, 64, 128, 4
+    OH, OW = 8, 18
+    xd = dev(np.maximum(rng.randn(B, IH, IW, Ci), 0).astype(np.float32), td)
+    wmaster = dev((rng.randn(k, k, Ci, Co) / np.sqrt(k * k * Ci)).astype(np.float32))
+    bd = dev((0.1 * rng.randn(Co)).astype(np.float32))
+    wt = alloc(td, k * k * Ci * Co, fill=0.0)
+    offs, Ks, Ns = np.array([0], np.int64), np.array([k * k * Ci], np.int32), np.array([Co], np.int32)
+    L.mi_transpose_weights(stream(), code, wmaster.data_ptr(), wt.data_ptr(), offs.ctypes.data, Ks.ctypes.data, Ns.ctypes.data, 1)
+
+    def conv3_forward():
+        out = alloc(td, B, OH, OW, Co, fill=3.0)
+        L.mi_conv2d_nhwc_fwd(stream(), code, xd.data_ptr(), None, 0, B, IH, IW, Ci, wt.data_ptr(), 1, bd.data_ptr(), k, k, Co, 1, out.data_ptr())
+        torch.cuda.synchronize()
+        return out.view(torch.int16).clone()
+
+    prev = {k_: L.mi_set_tuning(k_, v) for k_, v in ((13, 2), (15, 3))}          # the register-weight kernels whenever eligible
+    try:
+        fresh = conv3_forward()
+        stale = torch.zeros(1 << 20, device="cuda", dtype=torch.uint8)
+        L.mi_rwconv_next_weights_fragment_ordered(stale.data_ptr())
+        FH, FW = 64, 160                                                             # enc12 takes FH = 80 only
+        frames = torch.zeros(FH * FW * 3, device="cuda", dtype=torch.uint8)
+        w1t, w2t = alloc(td, 32 * 48, fill=0.0), alloc(td, 64 * 512, fill=0.0)
+        b1d, b2d = dev(np.zeros(32, np.float32)), dev(np.zeros(64, np.float32))
+        act1, act2 = alloc(td, 1, 31, 79, 32, fill=0.0), alloc(td, 1, 14, 38, 64, fill=0.0)
+        launched = ctypes.c_int(-1)
+        L.mi_conv2d_enc12_fwd(stream(), code, frames.data_ptr(), 2, None, 1, FH, FW, w1t.data_ptr(), b1d.data_ptr(), w2t.data_ptr(), b2d.data_ptr(),
+                              act1.data_ptr(), None, act2.data_ptr(), ctypes.addressof(launched))
+        assert launched.value == 0
+        after = conv3_forward()
+        assert torch.equal(fresh, after)
+        assert float(fresh.float().abs().max()) > 0 and not bool((fresh == fresh.flatten()[0]).all())      # (something was computed)
+    finally:
+        L.mi_rwconv_next_weights_fragment_ordered(None)
+        for k_, v in prev.items():
+            L.mi_set_tuning(k_, v)
+
+
 @pytest.mark.parametrize("B", [2, 24])
 def test_deconv3_forward_and_fused_encoder_head_read_fragment_ordered_weights(B):
     """Round 6: the gather-form register-weight kernel of deconv3's forward pass (k = 5, 64 -> 32 channels; pack form 4) and the fused encoder head's conv2 stage (pack form 5) load their
