@@ -29,6 +29,7 @@ struct PpoEngine {
     long long f_gslab;                            // per-chunk gradient slabs of the large-minibatch step (max_batch > 256): [ceil(max_batch / 256)][total]
     long long f_h1, f_h2, f_dh1, f_dh2, f_part;   // fused step (ppo_fused.hip): [3][M][H1], [3][M][H2], [2][M][H1], [2][M][H2], loss-block partials
     int last_M;
+    int precision;                                // MI_F32 (calloc: the default) or MI_BF16X3 (mi_ppo_set_precision): which instantiation of the fused GEMM stages runs
     hipStream_t side; hipEvent_t ev_fork, ev_join; int side_ok;     // second stream of the forked minibatch step (0 = not tried, 1 = ok, -1 = unavailable)
     float* P(int t) const { return params + off[t]; }
     float* PO(int t) const { return params_old + off[t]; }
@@ -99,6 +100,8 @@ bool fused_switch() {                                    // MI355_PPO_FUSED=0: t
 bool fused_enabled(const PpoEngine* e);
 
 bool fused_enabled(const PpoEngine* e) { return fused_switch() && mi_ppo_fused_shape_in_range(e->d.num_actions, e->d.h2, e->kin); }
+
+bool x3(const PpoEngine* e) { return e->precision == MI_BF16X3; }
 
 void fill_fused(const PpoEngine* e, PpoFusedParams& q, const float* states, int M) {
     const MiPpoDesc& d = e->d;
@@ -239,8 +242,9 @@ int mi_ppo_forward_backward(void* h, void* stream, const float* states, const fl
         PpoFusedParams q; fill_fused(e, q, states, M);
         q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
         e->last_M = M;
-        return mi_ppo_fused_step((hipStream_t)stream, q, 0);
+        return mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e));
     }
+    if (x3(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_forward_backward: the split-bf16 mode needs the fused kernels (no per-layer form of it)");
     const MiPpoDesc& d = e->d;
     void* st = stream;
     const int A = d.num_actions;
@@ -316,7 +320,7 @@ int mi_ppo_train_step(void* h, void* stream, const float* states, const float* a
             q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
             q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
             e->last_M = M;
-            CK(mi_ppo_fused_step((hipStream_t)stream, q, 0));
+            CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));
         }
         return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
     }
@@ -325,7 +329,7 @@ int mi_ppo_train_step(void* h, void* stream, const float* states, const float* a
     q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
     q.alpha = alpha; q.omb1 = 1.0f - beta1; q.omb2 = 1.0f - beta2; q.epsilon = epsilon;
     e->last_M = M;
-    return mi_ppo_fused_step((hipStream_t)stream, q, 1);
+    return mi_ppo_fused_step((hipStream_t)stream, q, 1, x3(e));
 }
 
 // 1: this engine's shape (num_actions, hidden sizes, input width) is inside the range of the fused kernels (csrc/ppo_fused.hip) and they are switched on, i.e.
@@ -353,11 +357,11 @@ int mi_ppo_train_step_idx(void* h, void* stream, const float* states, const floa
     q.row_idx = row_idx; q.n_rows = n_rows; q.s_gath = (float*)e->at(e->s_pad);
     e->last_M = M;
     if (M > 256) {
-        CK(mi_ppo_fused_step((hipStream_t)stream, q, 0));
+        CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));
         return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
     }
     q.alpha = alpha; q.omb1 = 1.0f - beta1; q.omb2 = 1.0f - beta2; q.epsilon = epsilon;
-    return mi_ppo_fused_step((hipStream_t)stream, q, 1);
+    return mi_ppo_fused_step((hipStream_t)stream, q, 1, x3(e));
 }
 
 // One DATA-PARALLEL SGD step of PPO.train (ppo.py:218-229 behind train.py:193-207) in ONE call (round 6): the fused five-launch chain of
@@ -379,7 +383,7 @@ int mi_ppo_train_step_dp(void* h, void* comm, void* stream, const float* states,
         q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
         if (row_idx) { q.row_idx = row_idx; q.n_rows = n_rows; q.s_gath = (float*)e->at(e->s_pad); }
         e->last_M = M;
-        CK(mi_ppo_fused_step((hipStream_t)stream, q, 0));      // gradients written into the flat buffer (M > 256: ordered row chunks)
+        CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));      // gradients written into the flat buffer (M > 256: ordered row chunks)
     } else {
         if (row_idx) return mi_fail(MI_ERR_SHAPE, "mi_ppo_train_step_dp: the in-kernel gather needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0): gather on the host side and pass row_idx = NULL");
         CK(mi_ppo_forward_backward(h, stream, states, actions, returns, advantage, M, inv_m, grad_scale));
@@ -395,7 +399,26 @@ int mi_ppo_logp_old(void* h, void* stream, const float* states, const float* act
     if (M < 1 || M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_logp_old: batch outside [1, max_batch]");
     PpoFusedParams q; fill_fused(e, q, states, M);
     q.actions = actions;
-    return mi_ppo_fused_logp_old((hipStream_t)stream, q, out);
+    return mi_ppo_fused_logp_old((hipStream_t)stream, q, out, x3(e));
+}
+
+// precision of the engine's training forms (mi_ppo_train_step[_idx|_dp], the fused mi_ppo_forward_backward, mi_ppo_logp_old): MI_F32 (exact fp32, the default) or
+// MI_BF16X3 (split-bf16 GEMM stages, ppo_fused.hip).  MI_BF16 has no PPO form; the split form exists only as fused kernels, so an engine that runs the per-layer
+// path refuses it instead of training in fp32.  mi_ppo_predict and the rollout step stay exact fp32 in both modes.
+int mi_ppo_set_precision(void* h, int dtype) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "ppo engine: null handle");
+    if (dtype != MI_F32 && dtype != MI_BF16X3) return mi_fail(MI_ERR_ARG, "mi_ppo_set_precision: MI_F32 or MI_BF16X3 (PPO has no bf16-storage mode)");
+    if (dtype == MI_BF16X3 && !fused_enabled(e))
+        return mi_fail(MI_ERR_SHAPE, "mi_ppo_set_precision: the split-bf16 mode needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0)");
+    e->precision = dtype;
+    return MI_OK;
+}
+
+int mi_ppo_precision(void* h) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "ppo engine: null handle");
+    return e->precision;
 }
 
 // tf.train.AdamOptimizer over the 13 policy/ variables (ppo.py:143-144); alpha folds lr*lr_decay^episode and the bias correction

@@ -9,7 +9,8 @@
 //                         head kernels, biases as all-ones MFMA rows) and -- single GPU -- its TF-Adam update straight from the accumulators;
 //                         one spare wave finalises the loss scalars and logstd
 //
-// All arithmetic is exact fp32 (v_mfma_f32_32x32x2_f32 = fmaf chains; 1e-4 parity with the oracle).  The step is latency bound (78 MFLOP,
+// All arithmetic is exact fp32 (v_mfma_f32_32x32x2_f32 = fmaf chains; 1e-4 parity with the oracle).  The split-bf16 mode (X3 = true: MI_BF16X3 through
+// mi_ppo_set_precision) instantiates the four GEMM kernels with three v_mfma_f32_32x32x16_bf16 per k-block of 16 instead; everything else is shared.  The step is latency bound (78 MFLOP,
 // 1.5 MB of weights): what matters is the number of dependent launches and that none of them serialises on one CU.  With FUSE_ADAM the
 // gradient never goes through HBM as a separate buffer: the block that finishes a weight tile's gradient (it sums over ALL minibatch rows)
 // applies tf.train.AdamOptimizer to that tile at once.  Data parallel (more than one rank) uses the same kernels with FUSE_ADAM = false: they
@@ -52,6 +53,50 @@ __device__ __forceinline__ void pf_mma_chunked(int sb, int se, FA load_a, FB loa
     }
 }
 
+// ---- split-bf16 ("bf16x3") form of the GEMM stages (MI_BF16X3, mi_ppo_set_precision): the operands stay fp32 in HBM and are split in registers by the rule of
+// split_from_f32 (common.hpp): hi = RNE-bf16(x), lo = bf16(x - hi).  A k-block of 16 is THREE v_mfma_f32_32x32x16_bf16 -- hi hi, hi lo, lo hi, fp32 accumulation
+// (3 x 32 cycles where exact fp32 takes 8 x v_mfma_f32_32x32x2_f32, 8 x 64).  The dropped lo lo term and the halves' own truncation leave ~2^-16 of each
+// product.  Operand form of the 32x32x16 MFMA: lane (row r = lane & 31, h = lane >> 5) holds k = 16 s + 8 h + j, j = 0..7, of k-block s.
+typedef float f32x8_t __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void pf_split8(const f32x8_t& v, bf16x8& hi, bf16x8& lo) {
+    hi = __builtin_convertvector(v, bf16x8);
+    lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x8_t), bf16x8);      // x - hi is exact in fp32
+}
+__device__ __forceinline__ void pf_mma_x3(const f32x8_t& a, const f32x8_t& b, f32x16_t& c) {
+    bf16x8 ah, al, bh, bl;
+    pf_split8(a, ah, al);
+    pf_split8(b, bh, bl);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
+}
+// column sums of B (the bias rows: all-ones A) kept exact in the split form: three bf16 pieces hold all 24 significand bits of an fp32 value
+// (x = hi + mid + lo exactly) and 1.0 times a piece is exact, so only the fp32 accumulation rounds -- as in the exact-fp32 MFMA
+__device__ __forceinline__ void pf_colsum_x3(const f32x8_t& b, f32x16_t& c) {
+    bf16x8 h, m;
+    pf_split8(b, h, m);
+    const bf16x8 l = __builtin_convertvector((b - __builtin_convertvector(h, f32x8_t)) - __builtin_convertvector(m, f32x8_t), bf16x8);
+    const bf16x8 ones = __builtin_bit_cast(bf16x8, u16x8{0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80});
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, l, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, m, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, h, c, 0, 0, 0);
+}
+// pf_mma_chunked for k-blocks of 16: U blocks' operands requested before their first MFMA
+template <int U, class FA, class FB>
+__device__ __forceinline__ void pf_mma_x3_chunked(int sb, int se, FA load_a, FB load_b, f32x16_t& acc) {
+    for (int s0 = sb; s0 < se; s0 += U) {
+        f32x8_t a[U], b[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (s0 + u < se) { a[u] = load_a(s0 + u); b[u] = load_b(s0 + u); }
+            else { a[u] = f32x8_t{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; b[u] = a[u]; }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) pf_mma_x3(a[u], b[u], acc);
+    }
+}
+__device__ __forceinline__ f32x8_t pf_cat(const f32x4& x, const f32x4& y) { return f32x8_t{x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]}; }
+
 // operands through buffer descriptors: rows are clamped, reads past a tensor return 0.0 from the hardware range check, stores past it are dropped --
 // no per-lane guard branches (at one wave per SIMD the instruction count is the kernel time: rollout.hip)
 #define PF_RSRC(ptr, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(ptr), 0, (int)(bytes), 0x00020000)
@@ -78,8 +123,9 @@ __device__ __forceinline__ const float* pf_theta(const PpoFusedParams& q, int ne
 __device__ __forceinline__ long long pf_off(const PpoFusedParams& q, int net, int which) { return q.off[(net == 1 ? 7 : 0) + which]; }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// layer 1: grid (ceil(H1 / 128), n_nets, ceil(M / 32)); wave w of a block owns the 32-column tile 4 blockIdx.x + w.  K = kin (72): 9 steps.
+// layer 1: grid (ceil(H1 / 128), n_nets, ceil(M / 32)); wave w of a block owns the 32-column tile 4 blockIdx.x + w.  K = kin (72): 9 steps (X3: 5 k-blocks).
 // ---------------------------------------------------------------------------------------------------------------------
+template <bool X3>
 __global__ __launch_bounds__(256) void ppo_l1_kernel(const PpoFusedParams q) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lrow = lane & 31, lgrp = lane >> 5;
     const int net = blockIdx.y, m0 = blockIdx.z * 32, n0 = (blockIdx.x * 4 + wave) * 32;
@@ -108,6 +154,17 @@ __global__ __launch_bounds__(256) void ppo_l1_kernel(const PpoFusedParams q) {
     f32x16_t acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    if constexpr (X3) {
+        pf_mma_x3_chunked<5>(0, (q.kin + 15) / 16,
+            [&](int s_) { const unsigned k = (unsigned)(s_ * 16 + lgrp * 8); f32x8_t a;
+#pragma unroll
+                          for (int e = 0; e < 8; ++e) a[e] = pf_ld(rsS, (arow + k + e) * 4u);
+                          return a; },
+            [&](int s_) { const unsigned k = (unsigned)(s_ * 16 + lgrp * 8); f32x8_t b;
+#pragma unroll
+                          for (int e = 0; e < 8; ++e) b[e] = pf_ld(rsW, ((k + e) * H1u + (unsigned)n) * 4u);
+                          return b; }, acc);
+    } else {
     pf_mma_chunked<9>(0, (q.kin + 7) / 8,
         [&](int s_) { const unsigned k = (unsigned)(s_ * 8 + lgrp * 4); f32x4 a;
 #pragma unroll
@@ -117,6 +174,7 @@ __global__ __launch_bounds__(256) void ppo_l1_kernel(const PpoFusedParams q) {
 #pragma unroll
                       for (int e = 0; e < 4; ++e) b[e] = pf_ld(rsW, ((k + e) * H1u + (unsigned)n) * 4u);
                       return b; }, acc);
+    }
     {
         const float bn = pf_ld(PF_RSRC(bias, (long long)q.H1 * 4), (unsigned)n * 4u);
         const __amdgpu_buffer_rsrc_t rsO = PF_RSRC(q.h1 + (long long)net * q.M * q.H1, (long long)q.M * q.H1 * 4);
@@ -129,6 +187,7 @@ __global__ __launch_bounds__(256) void ppo_l1_kernel(const PpoFusedParams q) {
 // ---------------------------------------------------------------------------------------------------------------------
 // layer 2: grid (ceil(H2 / 32), n_nets, ceil(M / 32)); the four waves split K = H1, partial tiles meet in LDS.
 // ---------------------------------------------------------------------------------------------------------------------
+template <bool X3>
 __global__ __launch_bounds__(256) void ppo_l2_kernel(const PpoFusedParams q) {
     __shared__ float red[3][16][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lrow = lane & 31, lgrp = lane >> 5;
@@ -138,7 +197,7 @@ __global__ __launch_bounds__(256) void ppo_l2_kernel(const PpoFusedParams q) {
     const float* bias = th + pf_off(q, net, 3);
     const float* x = q.h1 + (long long)net * q.M * q.H1;
     const int K = q.H1;
-    const int ksteps = (K + 7) / 8, per = (ksteps + 3) / 4;
+    const int ksteps = X3 ? (K + 15) / 16 : (K + 7) / 8, per = (ksteps + 3) / 4;
     const int sb = wave * per, se = min(ksteps, sb + per);
     const int n = n0 + lrow;
     const __amdgpu_buffer_rsrc_t rsX = PF_RSRC(x, (long long)q.M * K * 4), rsW = PF_RSRC(W, (long long)K * q.H2 * 4);
@@ -146,12 +205,21 @@ __global__ __launch_bounds__(256) void ppo_l2_kernel(const PpoFusedParams q) {
     f32x16_t acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    if constexpr (X3) {
+        pf_mma_x3_chunked<8>(sb, se,
+            [&](int s_) { const unsigned k = arow + (unsigned)(s_ * 16 + lgrp * 8); return pf_cat(pf_ld4(rsX, k * 4u), pf_ld4(rsX, (k + 4u) * 4u)); },
+            [&](int s_) { const unsigned k = (unsigned)(s_ * 16 + lgrp * 8); f32x8_t b;
+#pragma unroll
+                          for (int e = 0; e < 8; ++e) b[e] = pf_ld(rsW, ((k + e) * H2u + (unsigned)n) * 4u);
+                          return b; }, acc);
+    } else {
     pf_mma_chunked<16>(sb, se,                            // K % 4 == 0; a k past K reads the next row of x against weights past the tensor (0.0)
         [&](int s_) { return pf_ld4(rsX, (arow + (unsigned)(s_ * 8 + lgrp * 4)) * 4u); },
         [&](int s_) { const unsigned k = (unsigned)(s_ * 8 + lgrp * 4); f32x4 b;
 #pragma unroll
                       for (int e = 0; e < 4; ++e) b[e] = pf_ld(rsW, ((k + e) * H2u + (unsigned)n) * 4u);
                       return b; }, acc);
+    }
     if (wave > 0) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) red[wave - 1][r][lane] = acc[r];
@@ -368,6 +436,7 @@ __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams
 //   dh1[m, k] = (sum_n dh2[m, n] W2[k, n]) * relu'(h1[m, k])      the four waves split the 300 columns, partial tiles meet in LDS
 // (its own launch: the weight-gradient kernel below updates W2 in place, this one still reads it)
 // ---------------------------------------------------------------------------------------------------------------------
+template <bool X3>
 __global__ __launch_bounds__(256) void ppo_dh1_kernel(const PpoFusedParams q) {
     __shared__ float red[3][16][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lrow = lane & 31, lgrp = lane >> 5;
@@ -376,7 +445,7 @@ __global__ __launch_bounds__(256) void ppo_dh1_kernel(const PpoFusedParams q) {
     const float* __restrict__ W2 = q.theta + pf_off(q, net, 2);
     const float* __restrict__ h1 = q.h1 + (long long)net * M * H1;
     float* dh1 = q.dh1 + (long long)net * M * H1;
-    const int nsteps = (H2 + 7) / 8, per = (nsteps + 3) / 4;
+    const int nsteps = X3 ? (H2 + 15) / 16 : (H2 + 7) / 8, per = (nsteps + 3) / 4;
     const int sb = wave * per, se = min(nsteps, sb + per);
     const int kk = k0 + lrow;
     const __amdgpu_buffer_rsrc_t rsG = PF_RSRC(dh2, (long long)M * H2 * 4), rsW = PF_RSRC(W2, (long long)H1 * H2 * 4), rsH = PF_RSRC(h1, (long long)M * H1 * 4);
@@ -390,9 +459,16 @@ __global__ __launch_bounds__(256) void ppo_dh1_kernel(const PpoFusedParams q) {
     f32x16_t acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    if constexpr (X3) {
+        pf_mma_x3_chunked<5>(sb, se,                      // (the same cut-off, per group of 4)
+            [&](int s_) { const unsigned n = grow + (unsigned)(s_ * 16 + lgrp * 8); return pf_cat(pf_ld4(rsG, n * 4u), pf_ld4(rsG, (n + 4u) * 4u)); },
+            [&](int s_) { const int n = s_ * 16 + lgrp * 8;
+                          return pf_cat(pf_ld4(rsW, n < H2 ? (wrow + (unsigned)n) * 4u : PF_OOB), pf_ld4(rsW, n + 4 < H2 ? (wrow + (unsigned)n + 4u) * 4u : PF_OOB)); }, acc);
+    } else {
     pf_mma_chunked<10>(sb, se,                            // H2 % 4 == 0; the reduction index past H2 must read zeros on one side: the W2 row is cut off there
         [&](int s_) { return pf_ld4(rsG, (grow + (unsigned)(s_ * 8 + lgrp * 4)) * 4u); },
         [&](int s_) { const int n = s_ * 8 + lgrp * 4; return pf_ld4(rsW, n < H2 ? (wrow + (unsigned)n) * 4u : PF_OOB); }, acc);
+    }
     if (wave > 0) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) red[wave - 1][r][lane] = acc[r];
@@ -415,7 +491,7 @@ __global__ __launch_bounds__(256) void ppo_dh1_kernel(const PpoFusedParams q) {
 // grid ceil(tiles / 4) blocks of 4 waves; the last block's spare wave finalises the loss scalars and logstd.  All rows of the minibatch are
 // summed inside the wave (M <= 256 on this path), so the update is applied to the tile straight from the accumulators.
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool FUSE>
+template <bool FUSE, bool X3>
 __global__ __launch_bounds__(256) void ppo_wgrad_kernel(const PpoFusedParams q) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lrow = lane & 31, lgrp = lane >> 5;
     const int H1 = q.H1, H2 = q.H2, M = q.M;
@@ -491,6 +567,25 @@ __global__ __launch_bounds__(256) void ppo_wgrad_kernel(const PpoFusedParams q) 
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[r] = 0.f; accb[r] = 0.f; }
     const int m_beg = split ? (int)blockIdx.y * q.m_chunk : 0, m_end = split ? min(M, m_beg + q.m_chunk) : M;
+    if constexpr (X3) {                                   // 32 rows per round as below: two k-blocks of 16, rows 16 s + 8 h + j on lane half h
+        const int mblocks = (m_end + 15) / 16;
+        for (int s0 = m_beg / 16; s0 < mblocks; s0 += 2) {
+            f32x8_t a[2], b[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const unsigned mm = (unsigned)((s0 + u) * 16 + lgrp * 8 + e);
+                    a[u][e] = pf_ld(rsX, mm * ldxb + xcol);
+                    b[u][e] = pf_ld(rsG, mm * ldgb + gcol);
+                }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                pf_mma_x3(a[u], b[u], acc);
+                if (kt == 0) pf_colsum_x3(b[u], accb);
+            }
+        }
+    } else {
     const int msteps = (m_end + 7) / 8;
     for (int s0 = m_beg / 8; s0 < msteps; s0 += 4) {
         f32x4 a[4], b[4];
@@ -507,6 +602,7 @@ __global__ __launch_bounds__(256) void ppo_wgrad_kernel(const PpoFusedParams q) 
             pf_mma4(a[u], b[u], acc);
             if (kt == 0) pf_mma4(f32x4{1.f, 1.f, 1.f, 1.f}, b[u], accb);          // all-ones rows: every output row = column sums of G
         }
+    }
     }
     if (!nok) return;
     if constexpr (FUSE) {
@@ -598,7 +694,7 @@ static int pf_check_shape(const PpoFusedParams& q, const char* who) {
 int mi_ppo_fused_predict(hipStream_t st, PpoFusedParams& q, const float* noise, int greedy, float* action, float* value) {
     { const int rc0 = pf_check_shape(q, "ppo fused predict"); if (rc0 != MI_OK) return rc0; }
     q.n_nets = 2;
-    int rc = mi_ppo_fused_trunks(st, q);
+    int rc = mi_ppo_fused_trunks(st, q, false);            // (PPO.predict stays exact fp32 in every precision mode)
     if (rc != MI_OK) return rc;
     if (q.M <= 8) {                                       // a wave per sample
         if (q.A <= 2) hipLaunchKernelGGL((ppo_predict_head_kernel<2, 6>), dim3((q.M + 3) / 4), dim3(256), 0, st, q, noise, greedy, action, value, (float*)nullptr, 0);
@@ -608,13 +704,13 @@ int mi_ppo_fused_predict(hipStream_t st, PpoFusedParams& q, const float* noise, 
     return mi_check_launch("ppo_predict_head");
 }
 
-// log pi_old(a | s) of M samples (theta_old's trunk in net slot 2)
-int mi_ppo_fused_logp_old(hipStream_t st, PpoFusedParams& q, float* out) {
+// log pi_old(a | s) of M samples (theta_old's trunk in net slot 2); x3: the trunks in the split-bf16 form, as in the step of that mode
+int mi_ppo_fused_logp_old(hipStream_t st, PpoFusedParams& q, float* out, bool x3) {
     // only net 2 is needed: run the trunk kernels over the grid's net range [2, 3) by offsetting nothing -- the kernels index nets by blockIdx.y,
     // so all three are computed (M x 1.2 MFLOP, once per horizon batch)
     { const int rc0 = pf_check_shape(q, "ppo fused logp_old"); if (rc0 != MI_OK) return rc0; }
     q.n_nets = 3;
-    int rc = mi_ppo_fused_trunks(st, q);
+    int rc = mi_ppo_fused_trunks(st, q, x3);
     if (rc != MI_OK) return rc;
     if (q.A <= 2) hipLaunchKernelGGL((ppo_predict_head_kernel<2, 3>), dim3((q.M + 31) / 32), dim3(256), 0, st, q, (const float*)nullptr, 1, (float*)nullptr, (float*)nullptr, out, 2);
     else hipLaunchKernelGGL((ppo_predict_head_kernel<PF_MAX_ACT, 3>), dim3((q.M + 31) / 32), dim3(256), 0, st, q, (const float*)nullptr, 1, (float*)nullptr, (float*)nullptr, out, 2);
@@ -623,11 +719,16 @@ int mi_ppo_fused_logp_old(hipStream_t st, PpoFusedParams& q, float* out) {
 
 int mi_ppo_fused_partial_floats(int M) { return ((M + 31) / 32) * PF_NPART; }
 
-// forward only (PPO.predict, the cache of log pi_old): layers 1-2 of `n_nets` nets, then the caller's head kernel
-int mi_ppo_fused_trunks(hipStream_t st, const PpoFusedParams& q) {
+// forward only (PPO.predict, the cache of log pi_old): layers 1-2 of `n_nets` nets, then the caller's head kernel; x3: split-bf16 instantiations
+int mi_ppo_fused_trunks(hipStream_t st, const PpoFusedParams& q, bool x3) {
     const dim3 g1((q.H1 + 127) / 128, q.n_nets, (q.M + 31) / 32), g2((q.H2 + 31) / 32, q.n_nets, (q.M + 31) / 32);
-    hipLaunchKernelGGL(ppo_l1_kernel, g1, dim3(256), 0, st, q);
-    hipLaunchKernelGGL(ppo_l2_kernel, g2, dim3(256), 0, st, q);
+    if (x3) {
+        hipLaunchKernelGGL(ppo_l1_kernel<true>, g1, dim3(256), 0, st, q);
+        hipLaunchKernelGGL(ppo_l2_kernel<true>, g2, dim3(256), 0, st, q);
+    } else {
+        hipLaunchKernelGGL(ppo_l1_kernel<false>, g1, dim3(256), 0, st, q);
+        hipLaunchKernelGGL(ppo_l2_kernel<false>, g2, dim3(256), 0, st, q);
+    }
     return mi_check_launch("ppo_fused_trunks");
 }
 
@@ -647,35 +748,40 @@ static int ppo_pad(hipStream_t st, float* sink) {
 static inline int ppo_pad(hipStream_t, float*) { return MI_OK; }
 #endif
 
-// the whole minibatch step; fuse_adam = 0: gradients to q.grads instead of the in-place optimiser update
-int mi_ppo_fused_step(hipStream_t st, PpoFusedParams& q, int fuse_adam) {
+// the whole minibatch step; fuse_adam = 0: gradients to q.grads instead of the in-place optimiser update.  x3: the GEMM stages (layers 1-2, the layer-1 input
+// gradient, the weight gradients) in their split-bf16 instantiations; the head / loss kernel, the flat Adam and the slab sums are the same launches in both modes
+int mi_ppo_fused_step(hipStream_t st, PpoFusedParams& q, int fuse_adam, bool x3) {
     { const int rc0 = pf_check_shape(q, "ppo fused step"); if (rc0 != MI_OK) return rc0; }         // before the first launch
     if (fuse_adam && q.M > 256) return mi_fail(MI_ERR_ARG, "ppo fused step: the in-kernel Adam update needs the whole minibatch in one wave (M <= 256)");
     q.n_loss_blocks = (q.M + 31) / 32;
-    int rc = mi_ppo_fused_trunks(st, q);
+    int rc = mi_ppo_fused_trunks(st, q, x3);
     if (rc != MI_OK) return rc;
     rc = ppo_pad(st, q.losses);
     if (rc != MI_OK) return rc;
     if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_kernel<2>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);     // (action loops are compile-time unrolled)
     else hipLaunchKernelGGL(ppo_head_loss_kernel<PF_MAX_ACT>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);
-    hipLaunchKernelGGL(ppo_dh1_kernel, dim3((q.H1 + 31) / 32, 2, (q.M + 31) / 32), dim3(256), 0, st, q);
+    if (x3) hipLaunchKernelGGL(ppo_dh1_kernel<true>, dim3((q.H1 + 31) / 32, 2, (q.M + 31) / 32), dim3(256), 0, st, q);
+    else hipLaunchKernelGGL(ppo_dh1_kernel<false>, dim3((q.H1 + 31) / 32, 2, (q.M + 31) / 32), dim3(256), 0, st, q);
     rc = ppo_pad(st, q.losses);
     if (rc != MI_OK) return rc;
     const int nt1 = (q.H1 + 31) / 32, nt2 = (q.H2 + 31) / 32, kt1 = (q.kin + 31) / 32;
     const int tiles = 2 * (nt1 * nt2 + kt1 * nt1 + nt2) + 1;         // + the wave that finalises the loss scalars
     q.m_chunk = 0;
     if (fuse_adam) {
-        hipLaunchKernelGGL(ppo_wgrad_kernel<true>, dim3((tiles + 3) / 4), dim3(256), 0, st, q);
+        if (x3) hipLaunchKernelGGL((ppo_wgrad_kernel<true, true>), dim3((tiles + 3) / 4), dim3(256), 0, st, q);
+        else hipLaunchKernelGGL((ppo_wgrad_kernel<true, false>), dim3((tiles + 3) / 4), dim3(256), 0, st, q);
     } else if (q.M > 256) {                               // row chunks of 256: every chunk stores its own gradient slab, one ordered pass adds them (no atomics: round 4)
         const int chunks = (q.M + 255) / 256;
         if (!q.gslab) return mi_fail(MI_ERR_STATE, "ppo fused step: the engine's workspace has no gradient slabs for minibatches above 256 rows");
         q.m_chunk = 256;
         // (the alignment gaps between the tensors are written by nobody: zeroed, so that the sum leaves zeros there like the memset of the gradient buffer did)
         if (hipMemsetAsync(q.gslab, 0, (size_t)chunks * q.gslab_stride * 4, st) != hipSuccess) return mi_fail(MI_ERR_LAUNCH, "ppo fused step: memset failed");
-        hipLaunchKernelGGL(ppo_wgrad_kernel<false>, dim3((tiles + 3) / 4, chunks), dim3(256), 0, st, q);
+        if (x3) hipLaunchKernelGGL((ppo_wgrad_kernel<false, true>), dim3((tiles + 3) / 4, chunks), dim3(256), 0, st, q);
+        else hipLaunchKernelGGL((ppo_wgrad_kernel<false, false>), dim3((tiles + 3) / 4, chunks), dim3(256), 0, st, q);
         const int rc2 = mi_check_launch("ppo_fused_step");
         if (rc2 != MI_OK) return rc2;
         return mi_reduce_slabs(st, q.gslab, q.gslab_stride, chunks, q.n_params, q.grads, 1);
-    } else hipLaunchKernelGGL(ppo_wgrad_kernel<false>, dim3((tiles + 3) / 4), dim3(256), 0, st, q);
+    } else if (x3) hipLaunchKernelGGL((ppo_wgrad_kernel<false, true>), dim3((tiles + 3) / 4), dim3(256), 0, st, q);
+    else hipLaunchKernelGGL((ppo_wgrad_kernel<false, false>), dim3((tiles + 3) / 4), dim3(256), 0, st, q);
     return mi_check_launch("ppo_fused_step");
 }

@@ -13,6 +13,17 @@ HEADER = os.path.join(ROOT, "include", "mi355_carla.h")
 LIB_PATH = os.environ.get("MI355_LIB") or os.path.join(HERE, "libmi355_carla.so")     # MI355_LIB: another build of the same library (tools/asan_host_check.sh)
 
 MI_F32, MI_BF16, MI_BF16X3 = 0, 1, 2              # MI_BF16X3: split storage (two bf16 halves hi | lo per 4-byte element), include/mi355_carla.h
+# precision modes of the PPO step (mi_ppo_set_precision): exact fp32, or its GEMM stages on the bf16 matrix pipe as split (hi + lo) fp32 operands
+PPO_PRECISIONS = {"fp32": MI_F32, "f32": MI_F32, "bf16x3": MI_BF16X3}
+
+
+def ppo_precision_name(precision):
+    """'fp32' / 'f32' / 'bf16x3' -> the canonical name ('fp32' or 'bf16x3'); anything else raises ValueError."""
+    p = str(precision).strip().lower()
+    if p not in PPO_PRECISIONS:
+        raise ValueError("PPO precision %r: expected one of %s" % (precision, ", ".join(sorted(PPO_PRECISIONS))))
+    return "fp32" if p == "f32" else p
+
 
 _CTYPES = {
     "void*": ctypes.c_void_p, "const void*": ctypes.c_void_p,

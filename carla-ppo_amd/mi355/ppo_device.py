@@ -13,7 +13,8 @@ from .vae_device import require_gpu
 
 class PpoDevice:
     def __init__(self, input_dim, num_actions, action_low, action_high, clip_eps, value_scale, entropy_scale,
-                 hidden=(500, 300), max_batch=256, device=None):
+                 hidden=(500, 300), max_batch=256, device=None, precision="fp32"):
+        self.precision = milib.ppo_precision_name(precision)
         require_gpu()
         self.L = milib.get()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -54,6 +55,13 @@ class PpoDevice:
                                            p(self.workspace), nbytes, self.low.ctypes.data, self.high.ctypes.data)
         if not self.handle:
             raise milib.MiError("mi_ppo_create: " + self.L.cdll.mi_last_error().decode())
+        # a new engine starts in fp32: the mode is applied to every engine this object creates (ensure_batch recreates it for larger batches)
+        try:
+            self.L.mi_ppo_set_precision(self.handle, milib.PPO_PRECISIONS[self.precision])      # raises MiError (no fp32 fallback) where the mode has no kernels
+        except milib.MiError:
+            self.L.mi_ppo_destroy(self.handle)
+            self.handle = None
+            raise
         self.max_batch = int(max_batch)
         addr = self.L.mi_ppo_buffer(self.handle, 0)
         o = addr - self.workspace.data_ptr()
@@ -164,6 +172,10 @@ class PpoDevice:
         p = milib.ptr
         self.L.mi_ppo_train_step_dp(self.handle, comm_handle, self.stream(), p(states), p(actions), p(returns), p(advantage), p(logp_old), p(row_idx),
                                     int(states.shape[0]), int(M), float(inv_m), float(grad_scale), float(alpha), float(beta1), float(beta2), float(epsilon))
+
+    def engine_precision(self):
+        """The engine's own record of its mode (mi_ppo_precision): MI_F32 or MI_BF16X3."""
+        return int(self.L.cdll.mi_ppo_precision(self.handle))      # (the raw call: a mode is a non-zero return, not an error)
 
     def fused_ok(self):
         """True when the fused kernels (in-kernel minibatch gather, cached log pi_old) take this engine's shape; else only the per-layer path runs."""

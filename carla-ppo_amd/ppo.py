@@ -32,7 +32,11 @@ class PPO():
     def __init__(self, input_shape, action_space,
                  learning_rate=3e-4, lr_decay=0.998, epsilon=0.2,
                  value_scale=0.5, entropy_scale=0.01, initial_std=0.4,
-                 model_dir="./", seed=None):
+                 model_dir="./", seed=None, precision=None):
+        # precision of the training step: "fp32" (exact, the default) or "bf16x3" (the GEMM stages on the bf16 matrix pipe as split hi + lo operands,
+        # include/mi355_carla.h mi_ppo_set_precision).  MI355_PPO_PRECISION supplies it when the argument is not given; MI355_PRECISION is the VAE's knob
+        # and does not apply here.  Not part of a checkpoint: weights and optimiser state are fp32 in both modes.
+        self.precision = milib.ppo_precision_name(precision or os.environ.get("MI355_PPO_PRECISION", "fp32"))
         self.input_dim = int(np.asarray(input_shape).reshape(-1)[0])
         self.num_actions = int(action_space.shape[0])
         self.action_low = np.asarray(action_space.low, np.float32).reshape(-1)
@@ -71,7 +75,7 @@ class PPO():
             from mi355.init import seed_from_numpy_state
             self.seed = seed_from_numpy_state()
         self.dev = PpoDevice(self.input_dim, self.num_actions, self.action_low, self.action_high,
-                             self.epsilon, self.value_scale, self.entropy_scale)
+                             self.epsilon, self.value_scale, self.entropy_scale, precision=self.precision)
         values = self._init_values or init_ppo(self.seed, self.input_dim, self.num_actions, self.initial_std)
         # policy_old is a separately initialised copy in the reference; the trainer overwrites it with
         # update_old_policy() before the first train() (train.py:192), so it starts as a copy of policy.

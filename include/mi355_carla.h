@@ -455,6 +455,17 @@ int mi_ppo_train_step_dp(void* h, void* comm, void* stream, const float* states,
  * back by themselves; gather the minibatch on the host side instead of calling the _idx form).  Row indices are clamped into [0, n_rows) by the kernels. */
 int mi_ppo_fused_shape_ok(void* h);
 int mi_ppo_logp_old(void* h, void* stream, const float* states, const float* actions, int M, float* out);
+/* precision of the PPO step (the GEMMs of the forward, the losses' gradients and PPO.train) — ppo.py:42-66,112-147,218-229.  dtype MI_F32 (exact fp32, the
+ * default of a new engine) or MI_BF16X3: the GEMM stages of the fused kernels (layers 1-2 of the policy / value / old-policy nets, the layer-1 input gradient, the
+ * weight gradients) take their fp32 operands from HBM as they are, split them in registers (hi = bf16(x), lo = bf16(x - hi)) and form hi.hi + hi.lo + lo.hi with
+ * v_mfma_f32_32x32x16_bf16, fp32 accumulate; heads, losses, bias gradients, Adam and the order of every sum stay as in fp32 (bitwise reproducible run to run).
+ * The mode governs mi_ppo_train_step, mi_ppo_train_step_idx, mi_ppo_train_step_dp, the fused path of mi_ppo_forward_backward and mi_ppo_logp_old (so the cached
+ * log pi_old and the in-step old-policy forward come from the same kernels).  mi_ppo_predict and mi_rollout_step stay EXACT FP32 in both modes.
+ * Returns MI_ERR_ARG for MI_BF16 (no bf16-storage PPO) or any other value, MI_ERR_SHAPE when mi_ppo_fused_shape_ok(h) is 0 (the split form exists only as fused
+ * kernels: never a silent fp32 run).  Weights, gradients and optimiser state are fp32 in both modes; a new engine (mi_ppo_create) starts in MI_F32. */
+int mi_ppo_set_precision(void* h, int dtype);
+/* the engine's current precision (MI_F32 or MI_BF16X3) — ppo.py:42-66,112-147,218-229 */
+int mi_ppo_precision(void* h);
 
 #ifdef __cplusplus
 }
