@@ -5,8 +5,9 @@
 // (rwconv_conv_kernel) reads those 111 MB back.  Here a block owns a BAND of a frame -- 6 of the 18 output rows of conv2 = 14 rows of conv1's activation -- computes the
 // band's conv1 pixels with the loader / MFMA / epilogue of narrow_conv48_kernel (bit for bit the same activation and bit words), keeps them in LDS, and runs conv2 on
 // them with its 64 KB of weights in REGISTERS (a wave = one 32-output tile over all of K = 16 taps x 32 channels: 32 fragments = 128 VGPRs, the form of rwconv.hip).
-// conv1's activation is still WRITTEN (conv2's filter gradient reads it in the backward pass) -- every pixel by the band that owns it -- but never read back in the
-// forward pass: one launch and 100 MB of reads less on the serial forward chain.
+// The training form (INFER = 0) still WRITES conv1's activation and its ReLU bit words (the backward pass reads them) -- every pixel by the band that owns it -- but never
+// reads them back in the forward pass: one launch and 100 MB of reads less on the serial forward chain.  The inference form (INFER = 1: a forward pass with no backward
+// pass behind it -- encode, reconstruct, evaluate) keeps conv1's band in LDS only and stores act2 alone; same arithmetic, same summation order: act2 bit for bit.
 //
 // LDS: the band's activation as two PLANES (even / odd columns), [plane][row 0 .. 14][column / 2][32 channels] bf16 = 64 bytes per pixel, the 16-byte chunk c of pixel
 // index i stored at c ^ ((i >> 2) & 3): conv2's fragment reads (lane = output pixel, consecutive lanes = consecutive output columns = consecutive entries of ONE plane)
@@ -30,7 +31,7 @@ struct Enc12Params {
     const bf16_t* w1; const float* b1;                    // conv1: K-contiguous [32][48]
     const bf16_t* w2; const float* b2;                    // conv2: K-contiguous [64][512], k = (kh * 4 + kw) * 32 + c
     const bf16_t* w2f;                                    // optional: conv2's kernel in fragment order (mi_ares_pack_weights form 5): the prologue's 32 loads per wave are then 1 KB contiguous each
-    bf16_t* act1; uint32_t* bits1;                        // [B, 39, 79, 32]; ReLU bit words [B * 39 * 79][2] (may be NULL)
+    bf16_t* act1; uint32_t* bits1;                        // [B, 39, 79, 32]; ReLU bit words [B * 39 * 79][2] (may be NULL); the inference form (INFER = 1) writes neither
     bf16_t* act2;                                         // [B, 18, 38, 64]
     int B, ntiles;                                        // ntiles = 3 B
     int dbg;                                              // ablation mask of the DBG instantiation (tools/enc12_ablate.py; results are WRONG with any bit set): 1 no act1 / bit-word stores, 2 no bit words,
@@ -63,9 +64,10 @@ template <int F, int NF> struct E12Conv2Prologue {
     }
 };
 
-template <typename TS, int DBG = 0, int RING = 0, int C2 = 0>
+template <typename TS, int DBG = 0, int RING = 0, int C2 = 0, int INFER = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void enc12_fwd_kernel(const Enc12Params p) {
     const int dbg = DBG ? p.dbg : 0;                      // (DBG = 0, the product: every `dbg &` test below folds away)
+    constexpr bool STORE1 = !INFER;                       // conv1's activation (+ bit words) leaves the kernel: the training form only
     constexpr int SSZ = (int)sizeof(TS), GSZ = 4 * SSZ, GDW = GSZ / 4;
     constexpr int FW = 160, A1H = 39, A1W = 79, A2H = 18, A2W = 38;
     __shared__ __attribute__((aligned(1024))) unsigned char lds[E12_LDS];
@@ -239,7 +241,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         *(e12_u32x4*)(q + (((2 * lgrp) ^ sw) << 4)) = e12_u32x4{o[0], o[1], o[2], o[3]};
                         *(e12_u32x4*)(q + (((2 * lgrp + 1) ^ sw) << 4)) = e12_u32x4{o[4], o[5], o[6], o[7]};
                     }
-                    if (row < own_rows && !(dbg & 1)) {                      // this band owns the pixel: the activation tensor and its ReLU bit words
+                    if (STORE1 && row < own_rows && !(dbg & 1)) {            // this band owns the pixel: the activation tensor and its ReLU bit words
                         const long long m = ((long long)b * A1H + y0 + row) * A1W + col;
                         unsigned char* g = (unsigned char*)p.act1 + m * 64 + lgrp * 32;
                         *(e12_u32x4*)g = e12_u32x4{o[0], o[1], o[2], o[3]};
@@ -308,7 +310,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         *(e12_u32x4*)(q + (((2 * lgrp) ^ sw) << 4)) = e12_u32x4{o[0], o[1], o[2], o[3]};
                         *(e12_u32x4*)(q + (((2 * lgrp + 1) ^ sw) << 4)) = e12_u32x4{o[4], o[5], o[6], o[7]};
                     }
-                    if (row < own_rows && !(dbg & 1)) {                      // this band owns the pixel: the activation tensor and its ReLU bit words
+                    if (STORE1 && row < own_rows && !(dbg & 1)) {            // this band owns the pixel: the activation tensor and its ReLU bit words
                         const long long m = ((long long)b * A1H + y0 + row) * A1W + col;
                         unsigned char* g = (unsigned char*)p.act1 + m * 64 + lgrp * 32;
                         *(e12_u32x4*)g = e12_u32x4{o[0], o[1], o[2], o[3]};

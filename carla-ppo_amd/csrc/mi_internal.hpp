@@ -18,6 +18,7 @@ extern thread_local hipEvent_t mi_tl_stop_event;
 
 const void* mi_rwconv_take_wfrag();             // rwconv.hip: returns and clears this thread's mi_rwconv_next_weights_fragment_ordered announcement (called first thing by the entries it applies to)
 int mi_enc12_debug(int mask);                    // enc12.hip: ablation mask of the fused encoder-head forward kernel (tools/enc12_ablate.py); returns the previous one
+bool mi_enc12_eligible(int dtype, int B, int FH, int FW);   // enc12.hip: mi_conv2d_enc12_fwd takes calls of this storage type / batch / frame size (before its alignment checks)
 int mi_fail(int code, const char* msg);          // records msg (thread-local) and returns code
 int mi_check_launch(const char* what);           // hipGetLastError() -> MI_OK / MI_ERR_LAUNCH
 

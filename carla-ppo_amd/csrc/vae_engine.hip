@@ -59,7 +59,7 @@ void make_layout(const MiVaeDesc& d, const Geom& g, Layout& L) {
 }
 
 struct Workspace {
-    // byte offsets into the caller's workspace
+    // byte offsets into the caller's workspace; -1: not carved (an inference-only engine has no regions of the backward pass, and no act[1] behind a fused encoder head)
     long long act[NCONV + 1];          // act[i] = output of conv i (T)         (act[0] unused: frames stay in the dataset)
     long long gact[NCONV + 1];         // gradient wrt pre-activation of conv i output (T)
     long long dec[5];                  // dec[0] = dense1 output, dec[i] = output of deconv i (T); dec[4] = logits
@@ -141,6 +141,7 @@ struct VaeEngine {
     int fwd_produced;                   // the last forward's final kernel (the fused decoder tail) carries ev_ready on its own dispatch packet (consumed by the backward pass's first hand-over)
     int bits1_ok, bits3_ok;             // the last forward pass wrote the ReLU bit words of act1 / dec3
     int rng_ready;                      // generator state in the workspace has been initialised (mi_vae_set_seed)
+    int has_act1;                       // the workspace holds conv1's activation: a training engine, or conv1 and conv2 run as two launches (init_engine)
     const float* last_eps;              // the noise the last sampling forward used (caller's buffer or the engine's own draw)
     int last_u8;                        // frame-table format of the last forward (backward reads the same source table)
     // weights as the MFMA kernels read them: the fp32 masters (MI_F32) or the shadow copy Adam keeps in the engine's storage type (bf16 / split)
@@ -168,6 +169,11 @@ int pick_split(int M, int N, int K, int bk) {
     return ns;
 }
 
+// conv1 + conv2 of this model fit the fused encoder-head kernel (enc12_tile.hpp: 3-channel frames, 32 -> 64 channels, bf16 storage)
+bool enc12_model(const VaeEngine& e) {
+    return e.d.dtype == MI_BF16 && e.g.c[0] == 3 && e.g.c[1] == 32 && e.g.c[2] == 64;
+}
+
 void make_workspace(VaeEngine& e) {
     const MiVaeDesc& d = e.d; const Geom& g = e.g;
     const long long B = d.max_batch;
@@ -181,27 +187,31 @@ void make_workspace(VaeEngine& e) {
         if (guards && W.n_guards < 96) { W.guard_off[W.n_guards++] = o; o += 256; }
         return r;
     };
+    // An inference-only engine (MiVaeDesc::inference_only: VAE(training=False) -- rollout, evaluation, encode) never runs a backward pass: it carves the regions of the
+    // forward passes only -- no gradient tensors, ReLU bit words, split-K slabs of the latent gradients or slab scratch (at batch 512 in bf16: ~300 MB instead of ~810) --
+    // and conv1's activation only where conv1 and conv2 run as two launches (has_act1: behind the fused encoder head it never leaves LDS)
+    const bool train = d.inference_only == 0;
+    auto add_if = [&](bool keep, long long bytes) { return keep ? add(bytes) : -1ll; };
     W.act[0] = W.gact[0] = 0;
     for (int i = 1; i <= NCONV; ++i) {
         const long long n = B * g.ih[i] * g.iw[i] * g.c[i];
-        W.act[i] = add(n * e.esz); W.gact[i] = add(n * e.esz);
+        W.act[i] = add_if(i > 1 || e.has_act1, n * e.esz); W.gact[i] = add_if(train, n * e.esz);
     }
     for (int i = 0; i <= 4; ++i) {
         const long long n = B * g.dh[i] * g.dw[i] * g.dc[i];
-        W.dec[i] = add(n * e.esz); W.gdec[i] = add(n * e.esz);
+        W.dec[i] = add(n * e.esz); W.gdec[i] = add_if(train, n * e.esz);
     }
-    W.z = add(B * d.z_dim * e.esz); W.dheads = add(B * 2 * d.z_dim * e.esz);
+    W.z = add(B * d.z_dim * e.esz); W.dheads = add_if(train, B * 2 * d.z_dim * e.esz);
     W.heads_slab = add((long long)e.ns_heads * B * 2 * d.z_dim * 4);
-    W.dz_slab = add((long long)e.ns_dz * B * d.z_dim * 4);
+    W.dz_slab = add_if(train, (long long)e.ns_dz * B * d.z_dim * 4);
     W.mean = add(B * d.z_dim * 4); W.logvar = add(B * d.z_dim * 4); W.kl_row = add(B * 4);
     e.partial_cap = (int)(B * 64 > B * e.nchunks ? B * 64 : B * e.nchunks);   // loss partial sums: per (frame, chunk) or per block of the fused decoder tail
     W.partial = add((long long)e.partial_cap * 4); W.bpart = add((long long)e.partial_cap * 16); W.out2 = add(256); W.zf32 = add(B * d.z_dim * 4);
     // 256 position splits x the largest per-split slab (deconv3: 25 taps x 64 x 32 floats), rounded up
     // one region per raw-staged filter gradient of a backward pass (split storage: + the unfolded dW').  Round 4: the fp32 engine has them too -- every
     // filter / bias gradient of every engine reduces its position splits through slabs in a fixed order (two runs of a step are bitwise equal)
-    // An inference-only engine (MiVaeDesc::inference_only: VAE(training=False) -- rollout, evaluation, encode) never runs a backward pass: no slab scratch at all
-    // (every B = 1 rollout engine paid ~0.5 GB of HBM for it).  The slab sizes do not depend on the batch: 256 position splits x the largest per-split slab.
-    const bool train = d.inference_only == 0;
+    // No slab scratch for an inference-only engine (every B = 1 rollout engine paid ~0.5 GB of HBM for it).  The slab sizes do not depend on the batch:
+    // 256 position splits x the largest per-split slab.
     W.scratch_bytes = train ? SCRATCH_REGIONS * (64ll << 20) : 0;
     W.scratch = add(train ? W.scratch_bytes : 256);
     W.scratch_main_bytes = train ? 64ll << 20 : 0; W.scratch_main = add(train ? W.scratch_main_bytes : 256);
@@ -211,7 +221,7 @@ void make_workspace(VaeEngine& e) {
     W.tail_slabs = add(W.tail_slab_bytes > 0 ? W.tail_slab_bytes : 256);
     W.enc_slab_bytes = (train && d.dtype == MI_BF16) ? 2048ll * 8320 : 0;       // up to 8 resident blocks per CU x (64 x 32 + 32) floats
     W.enc_slabs = add(W.enc_slab_bytes > 0 ? W.enc_slab_bytes : 256);
-    W.bits_act1 = add(B * g.ih[1] * g.iw[1] * (g.c[1] / 16) * 4); W.bits_dec3 = add(B * g.dh[3] * g.dw[3] * (g.dc[3] / 16) * 4);
+    W.bits_act1 = add_if(train, B * g.ih[1] * g.iw[1] * (g.c[1] / 16) * 4); W.bits_dec3 = add_if(train, B * g.dh[3] * g.dw[3] * (g.dc[3] / 16) * 4);
     {
         long long n = 0;
         for (int i = 1; i <= NCONV; ++i) n += (long long)g.ih[i] * g.iw[i] * g.c[i];
@@ -232,6 +242,9 @@ bool init_engine(VaeEngine& e, const MiVaeDesc* desc) {
     e.ns_heads = pick_split(e.d.max_batch, 2 * e.d.z_dim, e.g.flat, bk);
     e.ns_dz = pick_split(e.d.max_batch, e.d.z_dim, e.g.flat, bk);
     e.nchunks = mi_recon_loss_chunks(e.g.dh[4] * e.g.dw[4] * e.g.dc[4]);
+    // conv1's activation exists for the backward pass (training engines) and as conv2's input where the fused encoder head does not take the model -- decided HERE, once, so
+    // the workspace and run_encoder agree (an inference engine without it fails a forward pass the fused kernel refuses instead of writing a region that does not exist)
+    e.has_act1 = !e.d.inference_only || !enc12_model(e) || !mi_enc12_eligible(e.d.dtype, e.d.max_batch, e.g.ih[0], e.g.iw[0]);
     make_workspace(e);
     return true;
 }
@@ -267,25 +280,29 @@ bool relu_bits_enabled() {                             // MI355_RELU_BITS=0: the
     return on != 0;
 }
 
-// encoder: frames (fp32, optional gather) -> act[1..4] -> heads slabs -> mean/logvar/z/kl
-int run_encoder(VaeEngine* e, void* st, const void* frames, int frames_u8, const int* idx, int B, const float* eps, int sample, int want_bits = 0) {
+// encoder: frames (fp32, optional gather) -> act[1..4] -> heads slabs -> mean/logvar/z/kl.  bwd: a backward pass follows (a training forward on an engine with gradients)
+int run_encoder(VaeEngine* e, void* st, const void* frames, int frames_u8, const int* idx, int B, const float* eps, int sample, int bwd = 0) {
     const MiVaeDesc& d = e->d; const Geom& g = e->g;
     if (frames_u8 && d.dtype != MI_BF16) return mi_fail(MI_ERR_ARG, "vae engine: uint8 frame tables are read by the bf16 engine only (fp32 mode takes float frames)");
     e->bits1_ok = 0;
     for (int i = 0; i < NCONV; ++i) {
         const void* x = i == 0 ? frames : e->at(e->W.act[i]);
-        if (i == 0 && d.dtype == MI_BF16 && g.c[0] == 3 && g.c[1] == 32 && g.c[2] == 64 && e->tm.mode != 1) {      // (the fused kernel reads 3-channel frames: frame stride FH FW 3, w1 as [32][48])
-            // round 5: conv1 + conv2 as ONE launch (enc12_tile.hpp): conv1's activation stays in LDS for conv2 (it is still written for the backward pass, never read back here).
-            // (per-op timing keeps the two layer launches: they are what the profile names)
-            const bool bits12 = want_bits && relu_bits_enabled();
+        if (i == 0 && enc12_model(*e) && (e->tm.mode != 1 || !e->has_act1)) {      // (the fused kernel reads 3-channel frames: frame stride FH FW 3, w1 as [32][48])
+            // round 5: conv1 + conv2 as ONE launch (enc12_tile.hpp): conv1's activation stays in LDS for conv2.  In front of a backward pass it is also written (with its ReLU
+            // bit words), never read back here; any other forward pass runs the kernel's inference form, which stores conv2's output alone.
+            // (per-op timing keeps the two layer launches -- they are what the profile names -- where the workspace has conv1's activation; otherwise it times the one launch)
+            const bool bits12 = bwd && relu_bits_enabled();
             int launched = 0;
             if (e->ares_ok && rc_small_frag_ok(e)) CK(mi_rwconv_next_weights_fragment_ordered(e->at(e->W.wfrag[9])));      // conv2's kernel in fragment order
             TOP(e, st, OP_CONV_FWD + 1, mi_conv2d_enc12_fwd(st, d.dtype, frames, frames_u8 ? 2 : 1, idx, B, g.ih[0], g.iw[0], e->wtptr(0), e->bptr(1), e->wtptr(2), e->bptr(3),
-                                                         e->at(e->W.act[1]), bits12 ? e->at(e->W.bits_act1) : nullptr, e->at(e->W.act[2]), &launched));
+                                                         bwd ? e->at(e->W.act[1]) : nullptr, bits12 ? e->at(e->W.bits_act1) : nullptr, e->at(e->W.act[2]), &launched));
             if (launched) { if (bits12) e->bits1_ok = 1; i = 1; continue; }
+            if (!e->has_act1)
+                return mi_fail(MI_ERR_ARG, "vae engine: the fused encoder head refused this call (frames not 2- / 8-byte aligned, weight copies not 16-byte aligned, or the narrow kernels "
+                                           "switched off after mi_vae_create) and this inference engine's workspace has no conv1 activation for the two-launch form");
         }
         // conv1 (training pass, bf16): also writes the ReLU bit words conv2's input gradient reads instead of the 101 MB activation tensor
-        const bool bits = i == 0 && want_bits && relu_bits_enabled() && d.dtype == MI_BF16 && g.c[1] == 32;
+        const bool bits = i == 0 && bwd && relu_bits_enabled() && d.dtype == MI_BF16 && g.c[1] == 32;
         if (i == 3 && e->ares_ok) {                           // conv4: activation-resident kernel (frames of the group in LDS, fragment-ordered weights streamed)
             int launched = 0;
             TOP(e, st, OP_CONV_FWD + i, mi_ares_conv(st, d.dtype, 0, x, B, e->at(e->W.wfrag[0]), e->bptr(7), 1, nullptr, e->at(e->W.act[4]), &launched));
@@ -497,7 +514,8 @@ int mi_vae_forward(void* h, void* stream, const void* src, const void* tgt, int 
     CK(check_batch(e, B));
     const MiVaeDesc& d = e->d; const Geom& g = e->g;
     struct StopEventGuard { ~StopEventGuard() { mi_tl_stop_event = nullptr; } } stop_guard;      // an error return between arming and the launch must not leave the event armed for this thread's next, unrelated launch
-    CK(run_encoder(e, stream, src, frames_u8, idx, B, eps, sample, want_grad));
+    if (d.inference_only) want_grad = 0;                  // (an inference engine has no gradient regions: every forward pass is one without gradient)
+    CK(run_encoder(e, stream, src, frames_u8, idx, B, eps, sample, want_grad && e->grads));
     e->last_u8 = frames_u8 ? 1 : 0;
     const int P = g.dh[4] * g.dw[4] * g.dc[4];
     const float kl_floor = d.kl_tolerance > 0.f ? d.kl_tolerance * d.z_dim : 0.f;

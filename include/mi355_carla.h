@@ -49,8 +49,10 @@ typedef struct MiVaeDesc {
     int loss_kind;      /* 0 bce_loss, 1 bce_loss_v2, 2 mse_loss (vae/models.py:11-22) */
     float beta;
     float kl_tolerance;
-    int inference_only; /* != 0: no backward pass will ever run on this engine (VAE(training=False): rollout / evaluation / encode): the workspace carries no
-                         * filter-gradient scratch (~0.5 GB less); mi_vae_create then wants grads == NULL.  0 (the zero-initialised default): a training engine */
+    int inference_only; /* != 0: no backward pass will ever run on this engine (VAE(training=False): rollout / evaluation / encode): the workspace carries the regions of
+                         * forward passes only -- no gradient tensors, ReLU bit words or filter-gradient scratch, and no conv1 activation where conv1 + conv2 run as the fused
+                         * encoder head (bf16, B = 512: 298 MB instead of 808); mi_vae_create then wants grads == NULL, and mi_vae_forward(want_grad = 1) is a forward without
+                         * gradient.  0 (the zero-initialised default): a training engine */
 } MiVaeDesc;
 
 /* MlpVAE (vae/models.py:271-299): dense encoder / decoder around the same latent block; up to MI_MLP_MAX_HIDDEN hidden layers per side */
@@ -167,8 +169,9 @@ int mi_conv2d_head_bwd_fused(void* stream, int dtype, const void* frames, int fr
 /* The encoder head of a FORWARD pass in ONE launch (round 5, csrc/enc12_tile.hpp; replaces the two tf.layers.conv2d of vae/models.py:250-251): frames
  * [*, 80, 160, 3] as uint8 camera bytes (frames_fmt 2) or float32 (1), optionally gathered through frame_idx, -conv1 k4 s2 + bias + ReLU-> act1 [B, 39, 79, 32] kept in LDS -conv2 k4 s2 + bias + ReLU-> act2
  * [B, 18, 38, 64].  w1_t / w2_t: the K-contiguous kernel copies [32][48] / [64][512] (mi_transpose_weights).  act1 and (relu_bits1 != NULL) its ReLU bit words are still
- * written, bit for bit as mi_conv2d_nhwc_fwd_bits writes them (the backward pass reads them); act2 = conv2 of that activation.  *launched = 0: not eligible (bf16 storage,
- * this geometry only; nothing was launched: call mi_conv2d_nhwc_fwd_bits and mi_conv2d_nhwc_fwd). */
+ * written, bit for bit as mi_conv2d_nhwc_fwd_bits writes them (the backward pass reads them); act2 = conv2 of that activation.  act1 == NULL: the INFERENCE form (a forward
+ * pass with no backward pass behind it) -- conv1's activation never leaves LDS, act2 is bit for bit what the training form writes; relu_bits1 must then be NULL too
+ * (MI_ERR_ARG otherwise).  *launched = 0: not eligible (bf16 storage, this geometry only; nothing was launched: call mi_conv2d_nhwc_fwd_bits and mi_conv2d_nhwc_fwd). */
 int mi_conv2d_enc12_fwd(void* stream, int dtype, const void* frames, int frames_fmt, const int* frame_idx, int B, int FH, int FW, const void* w1_t, const float* b1, const void* w2_t, const float* b2, void* act1, void* relu_bits1, void* act2, int* launched);
 /* The four SMALL-GRID layers of the ConvVAE on the activation-resident kernels (round 4, csrc/ares_tile.hpp): a block keeps the whole inputs of a group of frames
  * in LDS and streams fragment-ordered weights through registers.  form 0 (conv form, k4 s2, [B,8,18,128] -> [B,3,8,256]): conv4 forward (vae/models.py:253) and

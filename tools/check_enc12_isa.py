@@ -4,12 +4,16 @@ their s_waitcnt is written by hand, so nothing protects a register between `glob
 enc12.hip (compiled here if no path is given), walks the kernel in layout order -- once from the top, then the band loop a second time for the loop-carried
 requests -- with the hardware's rule (loads retire in order; a wait vmcnt(N) leaves at most N of them outstanding; stores only ever make a wait stricter) and fails if any
 instruction READS a register whose load may still be outstanding, or if the kernel spills.
-    python tools/check_enc12_isa.py [listing.s]
+    python tools/check_enc12_isa.py [--all] [listing.s]
     python tools/check_enc12_isa.py --generic carla-ppo_amd/csrc/ares.hip "ares_(conv|gather|gather2)_kernel"      (any file / kernels: the replay alone)"""
 import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ["_ZN2mi16enc12_fwd_kernelIhLi0ELi1ELi0E", "_ZN2mi16enc12_fwd_kernelIhLi0ELi1ELi1E"]      # ring form; ring form + pipelined conv2 reads
+# enc12_fwd_kernel<unsigned char, DBG = 0, RING = 1, C2, INFER>, each name up to the end of its template arguments (a prefix of one must not match another).
+# The product: ring form + pipelined conv2 reads, training form (act1 + bit words stored) and inference form (act2 stored alone).  --all: also the ring form with
+# compiler-scheduled conv2 reads (MI355_ENC12_C2=0, A/B runs).
+KERNELS = ["_ZN2mi16enc12_fwd_kernelIhLi0ELi1ELi1ELi0EE", "_ZN2mi16enc12_fwd_kernelIhLi0ELi1ELi1ELi1EE"]
+KERNELS_AB = ["_ZN2mi16enc12_fwd_kernelIhLi0ELi1ELi0ELi0EE"]
 
 
 def listing(kernel, path=None):
@@ -141,8 +145,9 @@ def check_generic(hip_path, pattern, listing_path=None):
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--generic":          # --generic file.hip name-regex [listing.s]
         raise SystemExit(1 if check_generic(sys.argv[2], sys.argv[3], sys.argv[4] if len(sys.argv) > 4 else None) else 0)
-    path, bad = sys.argv[1] if len(sys.argv) > 1 else None, False
-    for k in KERNELS:
+    args = [a for a in sys.argv[1:] if a != "--all"]
+    path, bad = args[0] if args else None, False
+    for k in KERNELS + (KERNELS_AB if "--all" in sys.argv[1:] else []):
         path, b = check(k, path)
         bad = bad or b
     if bad:
