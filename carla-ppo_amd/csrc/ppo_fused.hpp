@@ -43,3 +43,7 @@ struct MiZeroList { float* p[3]; long long n[3]; };     // raw-sum buffers conv1
 int mi_rollout_conv(hipStream_t st, const float* x, const float* x_bias, int IH, int IW, int C, const float* w, int ldw, int N, int KH, int KW, float* out_raw, int flat_k);
 int mi_rollout_conv1(hipStream_t st, const unsigned char* frame, const float* w, const float* bias, float* out, int IH, int IW, int Cs, int KH, int KW, int N, const MiZeroList* zero);
 int mi_rollout_policy(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, float* out);
+// batched forms (n environments per launch; mi_rollout_step_batch)
+int mi_rollout_conv1_batch(hipStream_t st, const unsigned char* frames, const float* w, const float* bias, float* out, int IH, int IW, int Cs, int KH, int KW, int N, int n, const MiZeroList* zero);
+int mi_rollout_conv_batch(hipStream_t st, const float* x, const float* x_bias, int IH, int IW, int C, const float* w, int ldw, int N, int KH, int KW, float* out_raw, int flat_k, int n);
+int mi_rollout_policy_batch(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n, float* out);

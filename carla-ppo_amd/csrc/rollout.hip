@@ -1,4 +1,4 @@
-// rollout.hip — the B = 1 inference path of the rollout loop as ONE C-ABI call: raw uint8 camera frame + measurements ->
+// rollout.hip — the inference path of the rollout loop (B = 1, and n environments per call: the *_batch kernels) as ONE C-ABI call: raw uint8 camera frame + measurements ->
 // ConvVAE encoder mean z (vae/models.py:199-202, 249-256) -> state = [z, measurements] (vae_common.py:45-59) -> policy / value heads
 // (ppo.py:231-251) -> (action, value, z) in one buffer (device memory or pinned host memory).  Exact fp32 (v_mfma_f32_32x32x2_f32).
 //
@@ -9,6 +9,7 @@
 // eight launches whose cost is their latency, not their work:
 //     conv1 (also clears the raw buffers) -> conv2 -> conv3 -> conv4 -> mean -> trunk layer 1 (both nets) -> trunk layer 2 (both nets) -> heads
 #include <stdlib.h>
+#include <type_traits>
 #include "common.hpp"
 #include "mi_internal.hpp"
 #include "mi355_carla.h"
@@ -32,6 +33,14 @@ struct RollConvParams {
     int IW, C, OW, M, N, K, KW, flat, relu, c_shift, vec; // flat = 1: x is a vector of K values, M = 1; c_shift = log2(C) or -1
 };
 
+// The batched step (n environments in one call) carries the same fields plus the row geometry: rows run over n * OH * OW output pixels (conv) or
+// over the n environments (flat layers); the image / environment index is taken from the row.  A type of its own, so the B = 1 instantiations
+// see the parameter block (and compile to the code) they always had.
+struct RollConvBatchParams : RollConvParams {
+    int OHW; unsigned img_stride;                         // conv: output pixels per image; floats between two images of x
+    int row_tiles; unsigned x_row, t_row;                 // flat: blockIdx.y = net * row_tiles + row tile; floats between two rows of x / of x_tail
+};
+
 #define ROLL_RSRC(ptr, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(ptr), 0, (int)(bytes), 0x00020000)
 #define ROLL_OOB 0x40000000u                              // a byte offset past every descriptor of this file
 
@@ -41,19 +50,27 @@ __device__ __forceinline__ f32x4 roll_ld4(const __amdgpu_buffer_rsrc_t r, unsign
 // one block unit (bx, by, bz) of the grid (ceil(N / 32), ceil(M / 32) | nets, ceil(K / 256)); wave w of the block: k in [256 bz + 64 w, + 64)
 // MODE: 0 = conv, power-of-two C and KW = 4 (shifts); 1 = flattened input, power-of-two C (the mean head); 2 = flattened, bias indexed by k
 // (trunk layer 2); 3 = the assembled state vector (trunk layer 1); 4 = conv, any C / KW
-template <int MODE>
-__device__ __forceinline__ void roll_conv_unit(const RollConvParams& p, int bx, int by, int bz, f32x4 (*red)[4][64]) {
+// P = RollConvBatchParams: the batched form.  conv: M = n OH OW rows, the lane's row m lies in image m / OHW.  flat: M = n rows, one per environment, so the
+// MFMA's 32 rows carry 32 environments instead of one; grid.y = nets x row tiles; row m of x / x_tail starts at m x_row / m t_row.  A load of k >= K is sent
+// past the descriptor explicitly (behind the last k of a row lies the next row); rows past M stay clamped on load and dropped by the output descriptor.
+template <int MODE, class P>
+__device__ __forceinline__ void roll_conv_unit(const P& p, int bx, int by, int bz, f32x4 (*red)[4][64]) {
     constexpr bool FLAT = MODE == 1 || MODE == 2 || MODE == 3;
+    constexpr bool NB = std::is_same<P, RollConvBatchParams>::value;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lrow = lane & 31, lgrp = lane >> 5;
-    const int net = FLAT ? by : 0;
-    const int n0 = bx * 32, m0 = FLAT ? 0 : by * 32, kb = bz * 256 + wave * 64;
+    int net = FLAT ? by : 0, m0 = FLAT ? 0 : by * 32;
+    if constexpr (NB && FLAT) { net = by / p.row_tiles; m0 = (by - net * p.row_tiles) * 32; }
+    const int n0 = bx * 32, kb = bz * 256 + wave * 64;
     const int n = n0 + lrow, m = min(m0 + lrow, p.M - 1);
     const __amdgpu_buffer_rsrc_t rsX = ROLL_RSRC(p.x + net * p.x_net, p.x_bytes);
     const __amdgpu_buffer_rsrc_t rsB = ROLL_RSRC(p.x_bias ? p.x_bias + net * p.xb_net : p.x, p.xb_bytes);
     const __amdgpu_buffer_rsrc_t rsT = ROLL_RSRC(p.x_tail ? p.x_tail : p.x, p.tail_bytes);
     const __amdgpu_buffer_rsrc_t rsW = ROLL_RSRC(p.w + net * p.w_net, p.w_bytes);
-    const int oy = FLAT ? 0 : m / p.OW, ox = m - oy * p.OW;
-    const unsigned pix = FLAT ? 0u : (unsigned)((2 * oy * p.IW + 2 * ox) * p.C);
+    int mi = m; unsigned xrow = 0u, trow = 0u;            // batched: where this lane's image / row starts in x and in x_tail (floats)
+    if constexpr (NB && !FLAT) { const int img = m / p.OHW; mi = m - img * p.OHW; xrow = (unsigned)img * p.img_stride; }
+    if constexpr (NB && FLAT) { xrow = (unsigned)m * p.x_row; trow = (unsigned)m * p.t_row; }
+    const int oy = FLAT ? 0 : mi / p.OW, ox = mi - oy * p.OW;
+    const unsigned pix = FLAT ? 0u : xrow + (unsigned)((2 * oy * p.IW + 2 * ox) * p.C);
     const unsigned ldw = (unsigned)p.ldw;
     f32x4 a[8], b[8], bi[8];
 #pragma unroll
@@ -61,7 +78,10 @@ __device__ __forceinline__ void roll_conv_unit(const RollConvParams& p, int bx, 
         const int k = kb + u * 8 + lgrp * 4;               // 4 consecutive k: one (kh, kw), 4 consecutive input channels (C % 4 == 0)
         if (MODE != 3) {
             unsigned off, ci;
-            if (FLAT) { off = (unsigned)k; ci = MODE == 1 ? (unsigned)(k & (p.C - 1)) : (unsigned)k; }
+            if (FLAT) {
+                off = (unsigned)k; ci = MODE == 1 ? (unsigned)(k & (p.C - 1)) : (unsigned)k;
+                if constexpr (NB) off = k < p.K ? xrow + (unsigned)k : (ROLL_OOB >> 2);
+            }
             else {
                 int tap, kh, kw;
                 if (MODE == 0) { tap = k >> p.c_shift; ci = (unsigned)(k & (p.C - 1)); kh = tap >> 2; kw = tap & 3; }
@@ -74,7 +94,13 @@ __device__ __forceinline__ void roll_conv_unit(const RollConvParams& p, int bx, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const unsigned ke = (unsigned)(k + e);
-                a[u][e] = roll_ld(rsX, ke * 4u) + roll_ld(rsT, (ke - (unsigned)p.split) * 4u);
+                if constexpr (NB) {
+                    const unsigned xo = ke < (unsigned)p.split ? (xrow + ke) * 4u : ROLL_OOB;
+                    const unsigned to = (ke >= (unsigned)p.split && ke < (unsigned)p.K) ? (trow + ke - (unsigned)p.split) * 4u : ROLL_OOB;
+                    a[u][e] = roll_ld(rsX, xo) + roll_ld(rsT, to);
+                } else {
+                    a[u][e] = roll_ld(rsX, ke * 4u) + roll_ld(rsT, (ke - (unsigned)p.split) * 4u);
+                }
                 bi[u][e] = roll_ld(rsB, ke * 4u);
             }
         }
@@ -121,8 +147,26 @@ __global__ __launch_bounds__(256) void rollout_conv_kernel(const RollConvParams 
     roll_conv_unit<MODE>(p, blockIdx.x, blockIdx.y, blockIdx.z, red);
 }
 
+template <int MODE>
+__global__ __launch_bounds__(256) void rollout_conv_batch_kernel(const RollConvBatchParams p) {
+    __shared__ f32x4 red[3][4][64];
+    roll_conv_unit<MODE>(p, blockIdx.x, blockIdx.y, blockIdx.z, red);
+}
+
+static int conv_mode(const RollConvParams& p) { return !p.flat ? ((p.c_shift >= 0 && p.KW == 4) ? 0 : 4) : (!p.vec ? 3 : (p.c_shift >= 0 ? 1 : 2)); }
+
+static void launch_conv_batch(hipStream_t st, const dim3& g, const RollConvBatchParams& p) {
+    switch (conv_mode(p)) {
+        case 0: hipLaunchKernelGGL(rollout_conv_batch_kernel<0>, g, dim3(256), 0, st, p); break;
+        case 1: hipLaunchKernelGGL(rollout_conv_batch_kernel<1>, g, dim3(256), 0, st, p); break;
+        case 2: hipLaunchKernelGGL(rollout_conv_batch_kernel<2>, g, dim3(256), 0, st, p); break;
+        case 3: hipLaunchKernelGGL(rollout_conv_batch_kernel<3>, g, dim3(256), 0, st, p); break;
+        default: hipLaunchKernelGGL(rollout_conv_batch_kernel<4>, g, dim3(256), 0, st, p); break;
+    }
+}
+
 static void launch_conv(hipStream_t st, const dim3& g, const RollConvParams& p) {
-    const int mode = !p.flat ? ((p.c_shift >= 0 && p.KW == 4) ? 0 : 4) : (!p.vec ? 3 : (p.c_shift >= 0 ? 1 : 2));
+    const int mode = conv_mode(p);
     switch (mode) {
         case 0: hipLaunchKernelGGL(rollout_conv_kernel<0>, g, dim3(256), 0, st, p); break;
         case 1: hipLaunchKernelGGL(rollout_conv_kernel<1>, g, dim3(256), 0, st, p); break;
@@ -143,6 +187,8 @@ struct RollConv1Params {
     MiZeroList z;
 };
 
+struct RollConv1BatchParams : RollConv1Params { int OHW; unsigned frame_stride; };     // batched: M = n OHW pixels, frame e starts frame_stride bytes behind frame e - 1
+
 __device__ __forceinline__ void roll_zero(const MiZeroList& z, long long t, long long nt) {
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -159,22 +205,25 @@ __device__ __forceinline__ void roll_zero(const MiZeroList& z, long long t, long
 }
 
 // 32 pixels x 32 channels of conv1 by one wave; wunit = index of the 32-pixel group.  Same descriptor discipline as roll_conv_unit.
-template <int ROW>
-__device__ __forceinline__ void roll_conv1_unit(const RollConv1Params& c, int wunit) {
+template <int ROW, class P>
+__device__ __forceinline__ void roll_conv1_unit(const P& c, int wunit) {
+    constexpr bool NB = std::is_same<P, RollConv1BatchParams>::value;
     const int IW = c.IW, Cs = c.Cs, OW = c.OW, M = c.M, N = c.N, KW = c.KW, K = c.K;
     const int lane = threadIdx.x & 63, lrow = lane & 31, lgrp = lane >> 5;
     const int m0 = wunit * 32;
     if (m0 >= M) return;
     const int m = min(m0 + lrow, M - 1), n = lrow;
-    const __amdgpu_buffer_rsrc_t rsF = ROLL_RSRC(c.frame, c.IH * IW * Cs);
+    unsigned f_bytes = (unsigned)(c.IH * IW * Cs), f_off = 0u; int mi = m;
+    if constexpr (NB) { const int img = m / c.OHW; mi = m - img * c.OHW; f_off = (unsigned)img * c.frame_stride; f_bytes = (unsigned)(M / c.OHW) * c.frame_stride; }
+    const __amdgpu_buffer_rsrc_t rsF = ROLL_RSRC(c.frame, f_bytes);
     const __amdgpu_buffer_rsrc_t rsW = ROLL_RSRC(c.w, K * N * 4);
     const __amdgpu_buffer_rsrc_t rsO = ROLL_RSRC(c.out, M * N * 4);
-    const int oy = m / OW, ox = m - oy * OW;
+    const int oy = mi / OW, ox = mi - oy * OW;
     f32x16_r acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     f32x4 a[6], b[6];
-    const unsigned base = (unsigned)((2 * oy * IW + 2 * ox) * Cs), rowbytes = (unsigned)(IW * Cs);
+    const unsigned base = f_off + (unsigned)((2 * oy * IW + 2 * ox) * Cs), rowbytes = (unsigned)(IW * Cs);
 #pragma unroll
     for (int u = 0; u < 6; ++u) {
         const int k0 = u * 8 + lgrp * 4;
@@ -214,6 +263,12 @@ __global__ __launch_bounds__(256) void rollout_conv1_kernel(const RollConv1Param
     roll_conv1_unit<ROW>(c, blockIdx.x * 4 + (threadIdx.x >> 6));
 }
 
+template <int ROW>
+__global__ __launch_bounds__(256) void rollout_conv1_batch_kernel(const RollConv1BatchParams c) {
+    roll_zero(c.z, (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256);
+    roll_conv1_unit<ROW>(c, blockIdx.x * 4 + (threadIdx.x >> 6));
+}
+
 // heads of the rollout step: h2 = relu(raw layer-2 sums + bias) of both trunks -> action mean (tanh, scaled to the action range, ppo.py:56-67),
 // the sampled / greedy action (ppo.py:81-88, clipped), the value (ppo.py:70-71), and the encoder mean z beside them: out = [action | value | z].
 // One block; the arithmetic of the finishing thread is that of ppo_predict_head_kernel.
@@ -225,13 +280,13 @@ struct RollHeadParams {
 };
 
 template <int NA>
-__device__ __forceinline__ void roll_head(const RollHeadParams& q, float (*red)[NA + 1]) {
+__device__ __forceinline__ void roll_head(const RollHeadParams& q, float (*red)[NA + 1], const int vnet) {     // vnet: floats from the policy trunk's h2 row to the value trunk's
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, A = q.A, H2 = q.H2;
     float au[NA], av = 0.f;
 #pragma unroll
     for (int a = 0; a < NA; ++a) au[a] = 0.f;
     for (int j = tid; j < H2; j += 256) {
-        const float hp = fmaxf(q.h2raw[j] + q.b2p[j], 0.f), hv = fmaxf(q.h2raw[H2 + j] + q.b2v[j], 0.f);
+        const float hp = fmaxf(q.h2raw[j] + q.b2p[j], 0.f), hv = fmaxf(q.h2raw[vnet + j] + q.b2v[j], 0.f);
         av += hv * q.Wv[j];
 #pragma unroll
         for (int a = 0; a < NA; ++a) if (a < A) au[a] += hp * q.Wm[(long long)j * A + a];
@@ -266,7 +321,19 @@ __device__ __forceinline__ void roll_head(const RollHeadParams& q, float (*red)[
 template <int NA>
 __global__ __launch_bounds__(256) void rollout_head_kernel(const RollHeadParams q) {
     __shared__ float red[4][NA + 1];
-    roll_head<NA>(q, red);
+    roll_head<NA>(q, red, q.H2);
+}
+
+// the batched heads: block e finishes environment e -- row e of both trunks' raw sums ([net][n][H2]), of the raw means and of the noise; output row e
+template <int NA>
+__global__ __launch_bounds__(256) void rollout_head_batch_kernel(const RollHeadParams q0, const int n) {
+    __shared__ float red[4][NA + 1];
+    RollHeadParams q = q0;
+    const long long e = blockIdx.x;
+    q.h2raw += e * q.H2; q.mean_raw += e * q.z_dim; q.out += e * (q.A + 1 + q.z_dim);
+    if (q.noise) q.noise += e * q.A;
+    if (q.mean_out) q.mean_out += e * q.A;
+    roll_head<NA>(q, red, n * q.H2);
 }
 
 }  // namespace mi
@@ -360,3 +427,60 @@ int mi_rollout_policy(hipStream_t st, const PpoFusedParams& q, const float* mean
     return mi_check_launch("rollout_policy");
 }
 
+
+// ---- the batched step: n environments per launch (mi_rollout_step_batch) ----
+
+int mi_rollout_conv1_batch(hipStream_t st, const unsigned char* frames, const float* w, const float* bias, float* out, int IH, int IW, int Cs, int KH, int KW, int N, int n,
+                           const MiZeroList* zero) {
+    RollConv1BatchParams c;
+    int rc = fill_conv1(c, frames, w, bias, out, IH, IW, Cs, KH, KW, N, zero);
+    if (rc != MI_OK) return rc;
+    c.OHW = c.M; c.frame_stride = (unsigned)(IH * IW * Cs);
+    const long long fb = (long long)n * c.frame_stride, ob = (long long)n * c.OHW * N * 4;
+    if (fb >= 0x40000000ll || ob >= 0x40000000ll) return mi_fail(MI_ERR_SHAPE, "rollout conv1: operand beyond 1 GiB");
+    c.M = n * c.OHW;
+    const dim3 g((c.M + 127) / 128);
+    // the two-byte loads of the 12-byte patch row need every frame to start on an even byte
+    if (KW * Cs == 12 && (c.frame_stride & 1u) == 0 && (((uintptr_t)frames) & 1) == 0) hipLaunchKernelGGL(rollout_conv1_batch_kernel<12>, g, dim3(256), 0, st, c);
+    else hipLaunchKernelGGL(rollout_conv1_batch_kernel<0>, g, dim3(256), 0, st, c);
+    return mi_check_launch("rollout_conv1_batch_kernel");
+}
+
+// conv (flat_k = 0): x [n][IH,IW,C] -> raw sums [n OH OW][N].  flat (flat_k > 0): x [n][flat_k] -> raw sums [n][N]
+int mi_rollout_conv_batch(hipStream_t st, const float* x, const float* x_bias, int IH, int IW, int C, const float* w, int ldw, int N, int KH, int KW, float* out_raw, int flat_k, int n) {
+    RollConvBatchParams p; dim3 g;
+    int rc = fill_conv(p, g, x, x_bias, IH, IW, C, w, ldw, N, KH, KW, out_raw, flat_k);
+    if (rc != MI_OK) return rc;
+    p.OHW = p.M; p.img_stride = (unsigned)(IH * IW * C); p.row_tiles = (n + 31) / 32; p.x_row = (unsigned)flat_k; p.t_row = 0;
+    const long long xb = (long long)n * p.x_bytes, ob = (long long)n * p.out_bytes;
+    if (xb >= 0x40000000ll || ob >= 0x40000000ll) return mi_fail(MI_ERR_SHAPE, "rollout conv: operand beyond 1 GiB");
+    p.x_bytes = (unsigned)xb; p.out_bytes = (unsigned)ob; p.M = n * p.OHW;
+    g.y = p.flat ? p.row_tiles : (p.M + 31) / 32;
+    if (g.y > 65535u) return mi_fail(MI_ERR_SHAPE, "rollout conv: too many row tiles");
+    launch_conv_batch(st, g, p);
+    return mi_check_launch("rollout_conv_batch_kernel");
+}
+
+// trunks and heads of n environments: mean_raw [n][z_dim], measurements [n][din - z_dim], noise [n][A], out [n][A + 1 + z_dim]; raw sums in q.h1 / q.h2 as [net][n][H]
+int mi_rollout_policy_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
+                            const float* noise, int greedy, int n, float* out) {
+    if (q.A < 1 || q.A > 8) return mi_fail(MI_ERR_ARG, "rollout step: 1 <= num_actions <= 8");
+    if (q.H1 % 4 != 0) return mi_fail(MI_ERR_SHAPE, "rollout step: hidden sizes must be multiples of 4");
+    if ((long long)n * (q.H1 > q.H2 ? q.H1 : q.H2) * 4 >= 0x40000000ll || (long long)n * q.din * 4 >= 0x40000000ll) return mi_fail(MI_ERR_SHAPE, "rollout step: operand beyond 1 GiB");
+    RollConvParams b1, b2; dim3 g1, g2; RollHeadParams h;
+    fill_trunks(b1, g1, b2, g2, q, mean_raw, mean_bias, z_dim, measurements);
+    fill_head(h, q, mean_raw, mean_bias, z_dim, noise, greedy, out);
+    RollConvBatchParams l1, l2;
+    const unsigned un = (unsigned)n;
+    static_cast<RollConvParams&>(l1) = b1; static_cast<RollConvParams&>(l2) = b2;
+    l1.OHW = l2.OHW = 1; l1.img_stride = l2.img_stride = 0; l1.row_tiles = l2.row_tiles = (n + 31) / 32;
+    l1.M = l2.M = n;
+    l1.x_row = (unsigned)z_dim; l1.t_row = (unsigned)(q.din - z_dim); l1.x_bytes *= un; l1.tail_bytes *= un; l1.out_bytes *= un; l1.out_net = (long long)n * q.H1;
+    l2.x_row = (unsigned)q.H1; l2.t_row = 0; l2.x_bytes *= un; l2.out_bytes *= un; l2.x_net = (long long)n * q.H1; l2.out_net = (long long)n * q.H2;
+    g1.y = g2.y = 2 * l1.row_tiles;
+    launch_conv_batch(st, g1, l1);
+    launch_conv_batch(st, g2, l2);
+    if (q.A <= 2) hipLaunchKernelGGL(rollout_head_batch_kernel<2>, dim3(n), dim3(256), 0, st, h, n);
+    else hipLaunchKernelGGL(rollout_head_batch_kernel<8>, dim3(n), dim3(256), 0, st, h, n);
+    return mi_check_launch("rollout_policy_batch");
+}

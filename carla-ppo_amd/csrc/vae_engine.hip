@@ -976,6 +976,53 @@ int mi_rollout_step(void* vae_h, void* ppo_h, void* stream, const unsigned char*
     return mi_rollout_policy(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, out);
 }
 
+// The rollout step for n environments in ONE call (vae_common.py:45-61 + ppo.py:231-251 per environment): the same eight launches as mi_rollout_step with the rows
+// of every layer running over the environments.  The activations live in the caller's scratch, one layer after the other with all n environments each:
+//   act1 [n][OH1,OW1,32] | raw conv2 [n][..] | raw conv3 | raw conv4 | raw mean [n][z]      (everything behind act1 is cleared by the first launch)
+// the trunks' raw sums in the PPO engine's f_h1 / f_h2 regions as [net][n][H], which hold max_batch rows per net: n above that is refused.
+static long long roll_env_floats(const VaeEngine* e) {
+    long long o = e->d.z_dim;
+    for (int i = 1; i <= NCONV; ++i) o += (long long)e->g.ih[i] * e->g.iw[i] * e->g.c[i];
+    return o;
+}
+
+long long mi_rollout_batch_workspace_bytes(void* vae_h, void* ppo_h, int n_envs) {
+    const VaeEngine* e = (const VaeEngine*)vae_h;
+    if (!e || !ppo_h) return mi_fail(MI_ERR_STATE, "mi_rollout_batch_workspace_bytes: null handle");
+    if (n_envs < 1 || n_envs > MI_ROLLOUT_MAX_ENVS) return mi_fail(MI_ERR_ARG, "mi_rollout_batch_workspace_bytes: 1 <= n_envs <= MI_ROLLOUT_MAX_ENVS");
+    return roll_env_floats(e) * 4 * n_envs;
+}
+
+int mi_rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
+                          void* scratch, long long scratch_bytes, float* out) {
+    VaeEngine* e = (VaeEngine*)vae_h;
+    if (!e || !ppo_h) return mi_fail(MI_ERR_STATE, "mi_rollout_step_batch: null handle");
+    if (!frames_u8 || !out || !scratch || (n_meas > 0 && !measurements) || (!greedy && !noise)) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: missing buffers");
+    if (n < 1 || n > MI_ROLLOUT_MAX_ENVS) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: 1 <= n <= MI_ROLLOUT_MAX_ENVS");
+    if (((uintptr_t)scratch) & 15) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: the scratch must be 16-byte aligned");
+    if (scratch_bytes < roll_env_floats(e) * 4 * n) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: scratch too small (mi_rollout_batch_workspace_bytes)");
+    const MiVaeDesc& d = e->d; const Geom& g = e->g;
+    hipStream_t st = (hipStream_t)stream;
+    float* act[NCONV + 1]; act[0] = nullptr;
+    long long o = 0;
+    for (int i = 1; i <= NCONV; ++i) { act[i] = (float*)scratch + o; o += (long long)n * g.ih[i] * g.iw[i] * g.c[i]; }
+    float* mean_raw = (float*)scratch + o;
+    mi::PpoFusedParams q;
+    CK(mi_ppo_internal_fill(ppo_h, &q, mean_raw, 1));
+    if (q.din != d.z_dim + n_meas) return mi_fail(MI_ERR_SHAPE, "mi_rollout_step_batch: z_dim + measurements must equal the policy's input size");
+    if (q.A > 8) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: at most 8 actions");
+    if (mi_ppo_internal_fill(ppo_h, &q, mean_raw, n) != MI_OK) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: n exceeds the PPO engine's max_batch");
+    MiZeroList zl = {};
+    zl.p[0] = act[2]; zl.n[0] = (mean_raw + (long long)n * d.z_dim) - act[2];
+    zl.p[1] = q.h1; zl.n[1] = 2LL * n * q.H1;
+    zl.p[2] = q.h2; zl.n[2] = 2LL * n * q.H2;
+    CK(mi_rollout_conv1_batch(st, frames_u8, e->params + e->L.off[0], e->bptr(1), act[1], g.ih[0], g.iw[0], g.c[0], 4, 4, g.c[1], n, &zl));
+    for (int i = 1; i < NCONV; ++i)                      // conv(i+1): conv2 reads conv1's finished output, the others raw sums + bias + ReLU on load
+        CK(mi_rollout_conv_batch(st, act[i], i == 1 ? nullptr : e->bptr(2 * (i - 1) + 1), g.ih[i], g.iw[i], g.c[i], e->params + e->L.off[2 * i], g.c[i + 1], g.c[i + 1], 4, 4, act[i + 1], 0, n));
+    CK(mi_rollout_conv_batch(st, act[NCONV], e->bptr(2 * (NCONV - 1) + 1), 1, 1, g.c[NCONV], e->params + e->L.off[8], 2 * d.z_dim, d.z_dim, 1, 1, mean_raw, g.flat, n));
+    return mi_rollout_policy_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out);
+}
+
 // VAE.encode (vae/models.py:199-202): frames -> mean [B,Z] fp32
 int mi_vae_encode(void* h, void* stream, const void* src, int frames_u8, const int* idx, int B, float* mean_out) {
     VaeEngine* e = (VaeEngine*)h;

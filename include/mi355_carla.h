@@ -382,6 +382,14 @@ int mi_mlpvae_reconstruct(void* h, void* stream, const void* src, int frames_u8,
  * measurements -> out [num_actions + 1 + z_dim] = action | value | z; noise [num_actions] for sampling or NULL with greedy.  Exact fp32.
  * Every buffer may be HBM or pinned (device-mapped) host memory: with pinned buffers the step needs no copy in either direction. */
 int mi_rollout_step(void* vae_h, void* ppo_h, void* stream, const unsigned char* frame_u8, const float* measurements, int n_meas, const float* noise, int greedy, float* out);
+/* the same step for n environments in one call (same eight launches, rows of every layer running over the environments) — vae_common.py:45-61 + ppo.py:231-251 per
+ * environment: frames_u8 [n][IH*IW*3], measurements [n][n_meas], noise [n][num_actions] or NULL with greedy -> out [n][num_actions + 1 + z_dim], row e = action | value | z of
+ * environment e; rows >= n are not written.  Exact fp32 on the master weights.  1 <= n <= MI_ROLLOUT_MAX_ENVS and n <= the PPO engine's max_batch (the trunks' raw sums live in
+ * that engine's workspace); anything else is an error and launches nothing.  Input and output buffers may be HBM or pinned host memory; `scratch` is HBM, 16-byte aligned, at
+ * least mi_rollout_batch_workspace_bytes(vae_h, ppo_h, n) bytes (fp32 act1 | raw sums of conv2..conv4 | raw means: 0.67 MB per environment at the reference geometry; < 0 = error). */
+#define MI_ROLLOUT_MAX_ENVS 1024
+long long mi_rollout_batch_workspace_bytes(void* vae_h, void* ppo_h, int n_envs);
+int mi_rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n, void* scratch, long long scratch_bytes, float* out);
 
 /* ---- collectives of the data-parallel path (no reference counterpart: the reference is single-process) ----
  * RCCL over xGMI, one communicator per process = per GPU; librccl.so.1 is bound at mi_comm_init (a single-GPU process never loads it).

@@ -1,6 +1,12 @@
 """Latency of the rollout-loop inference path at batch 1 (SURVEY 8f.3 callers: vae_common.py:45-61, train.py:142, run_eval.py:54):
-VAE.encode([frame]) (host frame -> device, conv stack, mean to host) followed by PPO.predict(state) (host -> device, two MLP trunks, action to host)."""
-import os, sys, tempfile, time
+VAE.encode([frame]) (host frame -> device, conv stack, mean to host) followed by PPO.predict(state) (host -> device, two MLP trunks, action to host).
+
+    python tools/rollout_latency.py --envs [1,2,4,8,16,32,64] [--rounds 3] [--calls 200] [--batched-only] [--no-box]
+
+times, for each number of environments E, one BatchedRolloutStep call against a loop of E RolloutStep calls and against the two-call path (VAE.encode of E float
+frames + PPO.predict of E states) on the same engines: the three are interleaved in every round, the line gives the median of the rounds' medians, the spread of
+those medians (min - max) and the p90 over all calls.  --batched-only runs the batched calls alone (the form a kernel trace is taken of)."""
+import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
     sys.path.insert(0, p)
@@ -14,7 +20,64 @@ vae = ConvVAE(np.array([80, 160, 3]), z_dim=64, model_dir=tempfile.mkdtemp(), pr
 vae.init_session(init_logging=False)
 agent = PPO(np.array([67]), Box(), model_dir=tempfile.mkdtemp())
 agent.init_session(init_logging=False)
+ap = argparse.ArgumentParser()
+ap.add_argument("--envs", nargs="?", const="1,2,4,8,16,32,64", default=None)
+ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--calls", type=int, default=200, help="timed calls per path, E and round")
+ap.add_argument("--batched-only", action="store_true")
+ap.add_argument("--no-box", action="store_true")
+args = ap.parse_args()
 rng = np.random.RandomState(0)
+
+
+def timed(fn, calls):
+    for i in range(10): fn(i)
+    ts = []
+    for i in range(calls):
+        t0 = time.perf_counter(); fn(i); ts.append(time.perf_counter() - t0)
+    return np.array(ts) * 1e6
+
+
+def envs_table():
+    from rollout import BatchedRolloutStep, RolloutStep
+    if args.rounds < 3:
+        ap.error("--rounds must be at least 3")
+    if not args.no_box:
+        from bench import box_probe
+        b = box_probe(agent.dev, 0)
+        print("box: %.0f TFLOP/s bf16 MFMA at %.0f MHz, %.2f TB/s read" % (b["mfma_bf16_tflops"], b["sclk_mhz"], b["hbm_read_tbps"]))
+    u8 = rng.randint(0, 256, (128, 80, 160, 3), dtype=np.uint8)
+    f32 = u8.astype(np.float32) / 255.0
+    ms = rng.rand(128, 3).astype(np.float32)
+    one = RolloutStep(vae, agent)
+    for E in [int(x) for x in args.envs.split(",") if x]:
+        many = BatchedRolloutStep(vae, agent, E)
+        sl = lambda i: slice((i * E) % 64, (i * E) % 64 + E)       # noqa: E731
+
+        def batched(i): many(u8[sl(i)], ms[sl(i)])
+        def loop(i):
+            for e in range(E): one(u8[(i * E) % 64 + e], ms[(i * E) % 64 + e])
+        def two_call(i):
+            z = vae.encode(f32[sl(i)])
+            agent.predict(np.concatenate([z, ms[sl(i)]], axis=1))
+        paths = [("batched", batched)] if args.batched_only else [("batched", batched), ("loop of B=1", loop), ("two-call", two_call)]
+        ts = {name: [] for name, _ in paths}
+        for _ in range(args.rounds):
+            for name, fn in paths:
+                ts[name].append(timed(fn, args.calls if name != "loop of B=1" else max(20, args.calls // E)))
+        line, med = "E = %3d (io=%s):" % (E, many.io), {}
+        for name, _ in paths:
+            meds = [np.median(t) for t in ts[name]]
+            med[name] = np.median(meds)
+            line += "  %s %.1f us (rounds %.1f - %.1f, p90 %.1f)" % (name, med[name], min(meds), max(meds), np.percentile(np.concatenate(ts[name]), 90))
+        if not args.batched_only:
+            line += "  | loop / batched %.2f x, two-call / batched %.2f x" % (med["loop of B=1"] / med["batched"], med["two-call"] / med["batched"])
+        print(line, flush=True)
+
+
+if args.envs is not None:
+    envs_table()
+    sys.exit(0)
 frames = rng.randint(0, 256, (64, 80, 160, 3)).astype(np.float32) / 255.0
 meas = rng.rand(64, 3).astype(np.float32)
 def one(i):
