@@ -47,3 +47,7 @@ int mi_rollout_policy(hipStream_t st, const mi::PpoFusedParams& q, const float* 
 int mi_rollout_conv1_batch(hipStream_t st, const unsigned char* frames, const float* w, const float* bias, float* out, int IH, int IW, int Cs, int KH, int KW, int N, int n, const MiZeroList* zero);
 int mi_rollout_conv_batch(hipStream_t st, const float* x, const float* x_bias, int IH, int IW, int C, const float* w, int ldw, int N, int KH, int KW, float* out_raw, int flat_k, int n);
 int mi_rollout_policy_batch(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n, float* out);
+// the recording form (mi_rollout_step_batch_rec): call row e is also stored as row table_rows[e] of the horizon-batch tables (rows outside [0, n_table_rows) are skipped)
+struct MiRolloutRec { const int* table_rows; long long n_table_rows; float* states; float* actions; float* values; };
+int mi_rollout_policy_batch_rec(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n, float* out,
+                                const MiRolloutRec& rec);

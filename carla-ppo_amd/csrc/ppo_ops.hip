@@ -157,6 +157,61 @@ __global__ void adv_normalize_f64_kernel(double* __restrict__ adv, const double*
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------
+// mi_rollout_finish: GAE + returns + per-row normalisation of a RAGGED rollout buffer in one launch (utils.py:45-50, train.py:175-177 per row).  One wave (= one
+// block) per row; row e has len[e] = L recorded steps in slots 0 .. L-1 of its T + 1 table slots and its bootstrap value in slot L.  The operation sequences are
+// those of gae_scan_f64_kernel and adv_normalize_f64_kernel above (no FMA contraction; the fp32 values widen to fp64 exactly), so a row comes out bit for bit as
+// those two kernels give it on that row alone.  The deltas do not depend on each other: all lanes form them into LDS; the recurrence is serial and lane 0 walks
+// it in the dense kernel's order.  Slots >= L and rows with L < 1 are not written.
+// ---------------------------------------------------------------------------------------------------
+namespace mi {
+__global__ __launch_bounds__(64) void rollout_finish_kernel(const float* __restrict__ values, const double* __restrict__ rewards, const double* __restrict__ terminals,
+                                                            const int* __restrict__ len, int T, double gamma, double gl, float* __restrict__ tab_returns,
+                                                            float* __restrict__ tab_adv, double* __restrict__ adv_raw, double* __restrict__ returns, double* __restrict__ adv_norm) {
+    __shared__ double a[MI_ROLLOUT_MAX_HORIZON];
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const int L = min(len[row], T);                       // a length beyond the horizon cannot index past the row
+    if (L < 1) return;
+    const long long tab = (long long)row * (T + 1), flat = (long long)row * T;
+    const float* v = values + tab;
+    const double* r = rewards + flat;
+    const double* d = terminals + flat;
+    for (int t = lane; t < L; t += WAVE) {
+        const double nonterm = __dsub_rn(1.0, d[t]);
+        a[t] = __dsub_rn(__dadd_rn(r[t], __dmul_rn(__dmul_rn(nonterm, gamma), (double)v[t + 1])), (double)v[t]);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        double carry = 0.0;
+        for (int t = L - 1; t >= 0; --t) {
+            const double y = __dadd_rn(carry, a[t]);
+            carry = __dmul_rn(gl, y);
+            a[t] = y;
+        }
+    }
+    __syncthreads();
+    double s = 0.0;
+    for (int t = lane; t < L; t += WAVE) {
+        s += a[t];
+        const double ret = a[t] + (double)v[t];
+        tab_returns[tab + t] = (float)ret;                 // f64 -> f32 at the feed (ppo.py:108-109), round to nearest even
+        if (returns) returns[flat + t] = ret;
+        if (adv_raw) adv_raw[flat + t] = a[t];
+    }
+    s = wave_sum_f64(s);
+    const double mean = s / (double)L;
+    double ss = 0.0;
+    for (int t = lane; t < L; t += WAVE) { const double dd = a[t] - mean; ss += dd * dd; }
+    ss = wave_sum_f64(ss);
+    const double sd = sqrt(ss / (double)L);
+    for (int t = lane; t < L; t += WAVE) {
+        const double an = (a[t] - mean) / (sd + 1e-8);
+        tab_adv[tab + t] = (float)an;
+        if (adv_norm) adv_norm[flat + t] = an;
+    }
+}
+}  // namespace mi
+
 namespace {
 __global__ __launch_bounds__(256) void relu_grad_kernel(const float* __restrict__ g, const float* __restrict__ h, long long n, float* __restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -233,6 +288,17 @@ int mi_adv_normalize(void* stream, double* adv, const double* values, int R, int
     if (R < 1 || T < 1) return mi_fail(MI_ERR_ARG, "mi_adv_normalize: empty input");
     hipLaunchKernelGGL(adv_normalize_f64_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, adv, values, R, T, returns);
     return mi_check_launch("adv_normalize");
+}
+
+// rewards / terminals [num_envs, T] fp64, values: the fp32 table [num_envs (T + 1)], len [num_envs] int32 (all device) -> fp32 tables and optional fp64 [num_envs, T] outputs
+int mi_rollout_finish(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* len, int num_envs, int T, double gamma, double lam,
+                      float* tab_returns, float* tab_advantages, double* adv_raw, double* returns, double* adv_norm) {
+    if (!tab_values || !rewards || !terminals || !len || !tab_returns || !tab_advantages) return mi_fail(MI_ERR_ARG, "mi_rollout_finish: missing buffers");
+    if (num_envs < 1 || T < 1) return mi_fail(MI_ERR_ARG, "mi_rollout_finish: empty input (num_envs >= 1, T >= 1)");
+    if (T > MI_ROLLOUT_MAX_HORIZON) return mi_fail(MI_ERR_ARG, "mi_rollout_finish: the horizon exceeds MI_ROLLOUT_MAX_HORIZON");
+    hipLaunchKernelGGL(rollout_finish_kernel, dim3(num_envs), dim3(64), 0, (hipStream_t)stream, tab_values, rewards, terminals, len, T, gamma, gamma * lam,
+                       tab_returns, tab_advantages, adv_raw, returns, adv_norm);
+    return mi_check_launch("rollout_finish");
 }
 
 }  // extern "C"

@@ -279,8 +279,11 @@ struct RollHeadParams {
     int A, H2, z_dim, greedy;
 };
 
-template <int NA>
-__device__ __forceinline__ void roll_head(const RollHeadParams& q, float (*red)[NA + 1], const int vnet) {     // vnet: floats from the policy trunk's h2 row to the value trunk's
+// where the recording heads store a call row besides `out`: row r of the tables (all NULL: this block records nothing)
+struct RollRecRow { float *state, *action, *value; };
+
+template <int NA, bool REC = false>
+__device__ __forceinline__ void roll_head(const RollHeadParams& q, float (*red)[NA + 1], const int vnet, const RollRecRow rec = RollRecRow{}) {     // vnet: floats from the policy trunk's h2 row to the value trunk's
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, A = q.A, H2 = q.H2;
     float au[NA], av = 0.f;
 #pragma unroll
@@ -303,10 +306,19 @@ __device__ __forceinline__ void roll_head(const RollHeadParams& q, float (*red)[
         red[wave][NA] = av;
     }
     float* out = q.out;
-    for (int i = tid; i < q.z_dim; i += 256) out[A + 1 + i] = q.mean_raw[i] + q.mean_bias[i];
+    for (int i = tid; i < q.z_dim; i += 256) {
+        const float zv = q.mean_raw[i] + q.mean_bias[i];
+        out[A + 1 + i] = zv;
+        if constexpr (REC) { if (rec.state) rec.state[i] = zv; }
+    }
     __syncthreads();
     if (tid > A) return;
-    if (tid == A) { out[A] = ((red[0][NA] + red[1][NA]) + (red[2][NA] + red[3][NA])) + q.bv[0]; return; }
+    if (tid == A) {
+        const float v = ((red[0][NA] + red[1][NA]) + (red[2][NA] + red[3][NA])) + q.bv[0];
+        out[A] = v;
+        if constexpr (REC) { if (rec.value) rec.value[0] = v; }
+        return;
+    }
     float u = 0.f;
 #pragma unroll
     for (int a = 0; a < NA; ++a) if (a == tid) u = (red[0][a] + red[1][a]) + (red[2][a] + red[3][a]);
@@ -316,6 +328,7 @@ __device__ __forceinline__ void roll_head(const RollHeadParams& q, float (*red)[
     float act = mean;
     if (!q.greedy) act = fminf(fmaxf(mean + expf(q.logstd[tid]) * q.noise[tid], lo), hi);
     out[tid] = act;
+    if constexpr (REC) { if (rec.action) rec.action[tid] = act; }
 }
 
 template <int NA>
@@ -334,6 +347,32 @@ __global__ __launch_bounds__(256) void rollout_head_batch_kernel(const RollHeadP
     if (q.noise) q.noise += e * q.A;
     if (q.mean_out) q.mean_out += e * q.A;
     roll_head<NA>(q, red, n * q.H2);
+}
+
+// the recording heads (mi_rollout_step_batch_rec): rollout_head_batch_kernel's arithmetic, and block e also stores what it computed as row r = table_rows[e] of the
+// horizon-batch tables an update trains from: states[r] = [z | measurements[e]], actions[r], values[r] -- the same registers that go to `out`, plain vector stores.
+// r outside [0, n_table_rows) (-1 = "do not record this environment") stores nothing into the tables, whatever its value.
+struct RollRecParams {
+    const int* table_rows; long long n_table_rows;       // [n] (the step's input buffer: HBM or pinned host memory); rows the tables hold
+    const float* meas; int n_meas, din;                   // measurements [n][n_meas]; din = z_dim + n_meas floats per states row
+    float *states, *actions, *values;
+};
+
+template <int NA>
+__global__ __launch_bounds__(256) void rollout_head_rec_kernel(const RollHeadParams q0, const int n, const RollRecParams t) {
+    __shared__ float red[4][NA + 1];
+    RollHeadParams q = q0;
+    const long long e = blockIdx.x;
+    q.h2raw += e * q.H2; q.mean_raw += e * q.z_dim; q.out += e * (q.A + 1 + q.z_dim);
+    if (q.noise) q.noise += e * q.A;
+    if (q.mean_out) q.mean_out += e * q.A;
+    const long long r = t.table_rows[e];
+    RollRecRow rec = {};
+    if (r >= 0 && r < t.n_table_rows) {
+        rec.state = t.states + r * t.din; rec.action = t.actions + r * q.A; rec.value = t.values + r;
+        for (int j = threadIdx.x; j < t.n_meas; j += 256) rec.state[q.z_dim + j] = t.meas[e * t.n_meas + j];
+    }
+    roll_head<NA, true>(q, red, n * q.H2, rec);
 }
 
 }  // namespace mi
@@ -462,8 +501,8 @@ int mi_rollout_conv_batch(hipStream_t st, const float* x, const float* x_bias, i
 }
 
 // trunks and heads of n environments: mean_raw [n][z_dim], measurements [n][din - z_dim], noise [n][A], out [n][A + 1 + z_dim]; raw sums in q.h1 / q.h2 as [net][n][H]
-int mi_rollout_policy_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
-                            const float* noise, int greedy, int n, float* out) {
+static int policy_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
+                        const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec) {
     if (q.A < 1 || q.A > 8) return mi_fail(MI_ERR_ARG, "rollout step: 1 <= num_actions <= 8");
     if (q.H1 % 4 != 0) return mi_fail(MI_ERR_SHAPE, "rollout step: hidden sizes must be multiples of 4");
     if ((long long)n * (q.H1 > q.H2 ? q.H1 : q.H2) * 4 >= 0x40000000ll || (long long)n * q.din * 4 >= 0x40000000ll) return mi_fail(MI_ERR_SHAPE, "rollout step: operand beyond 1 GiB");
@@ -480,7 +519,23 @@ int mi_rollout_policy_batch(hipStream_t st, const PpoFusedParams& q, const float
     g1.y = g2.y = 2 * l1.row_tiles;
     launch_conv_batch(st, g1, l1);
     launch_conv_batch(st, g2, l2);
+    if (rec) {
+        const RollRecParams t = {rec->table_rows, rec->n_table_rows, measurements, q.din - z_dim, q.din, rec->states, rec->actions, rec->values};
+        if (q.A <= 2) hipLaunchKernelGGL(rollout_head_rec_kernel<2>, dim3(n), dim3(256), 0, st, h, n, t);
+        else hipLaunchKernelGGL(rollout_head_rec_kernel<8>, dim3(n), dim3(256), 0, st, h, n, t);
+        return mi_check_launch("rollout_policy_batch_rec");
+    }
     if (q.A <= 2) hipLaunchKernelGGL(rollout_head_batch_kernel<2>, dim3(n), dim3(256), 0, st, h, n);
     else hipLaunchKernelGGL(rollout_head_batch_kernel<8>, dim3(n), dim3(256), 0, st, h, n);
     return mi_check_launch("rollout_policy_batch");
+}
+
+int mi_rollout_policy_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
+                            const float* noise, int greedy, int n, float* out) {
+    return policy_batch(st, q, mean_raw, mean_bias, z_dim, measurements, noise, greedy, n, out, nullptr);
+}
+
+int mi_rollout_policy_batch_rec(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
+                                const float* noise, int greedy, int n, float* out, const MiRolloutRec& rec) {
+    return policy_batch(st, q, mean_raw, mean_bias, z_dim, measurements, noise, greedy, n, out, &rec);
 }

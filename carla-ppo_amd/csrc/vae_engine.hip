@@ -993,11 +993,13 @@ long long mi_rollout_batch_workspace_bytes(void* vae_h, void* ppo_h, int n_envs)
     return roll_env_floats(e) * 4 * n_envs;
 }
 
-int mi_rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
-                          void* scratch, long long scratch_bytes, float* out) {
+// one body for the plain and the recording call (rec != NULL: mi_rollout_step_batch_rec, whose last launch is the recording heads)
+static int rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
+                              void* scratch, long long scratch_bytes, float* out, const MiRolloutRec* rec) {
     VaeEngine* e = (VaeEngine*)vae_h;
-    if (!e || !ppo_h) return mi_fail(MI_ERR_STATE, "mi_rollout_step_batch: null handle");
+    if (!e || !ppo_h) return mi_fail(MI_ERR_STATE, rec ? "mi_rollout_step_batch_rec: null handle" : "mi_rollout_step_batch: null handle");
     if (!frames_u8 || !out || !scratch || (n_meas > 0 && !measurements) || (!greedy && !noise)) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: missing buffers");
+    if (rec && (!rec->table_rows || !rec->states || !rec->actions || !rec->values || rec->n_table_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch_rec: missing tables");
     if (n < 1 || n > MI_ROLLOUT_MAX_ENVS) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: 1 <= n <= MI_ROLLOUT_MAX_ENVS");
     if (((uintptr_t)scratch) & 15) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: the scratch must be 16-byte aligned");
     if (scratch_bytes < roll_env_floats(e) * 4 * n) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: scratch too small (mi_rollout_batch_workspace_bytes)");
@@ -1020,7 +1022,19 @@ int mi_rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned
     for (int i = 1; i < NCONV; ++i)                      // conv(i+1): conv2 reads conv1's finished output, the others raw sums + bias + ReLU on load
         CK(mi_rollout_conv_batch(st, act[i], i == 1 ? nullptr : e->bptr(2 * (i - 1) + 1), g.ih[i], g.iw[i], g.c[i], e->params + e->L.off[2 * i], g.c[i + 1], g.c[i + 1], 4, 4, act[i + 1], 0, n));
     CK(mi_rollout_conv_batch(st, act[NCONV], e->bptr(2 * (NCONV - 1) + 1), 1, 1, g.c[NCONV], e->params + e->L.off[8], 2 * d.z_dim, d.z_dim, 1, 1, mean_raw, g.flat, n));
+    if (rec) return mi_rollout_policy_batch_rec(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out, *rec);
     return mi_rollout_policy_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out);
+}
+
+int mi_rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
+                          void* scratch, long long scratch_bytes, float* out) {
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, nullptr);
+}
+
+int mi_rollout_step_batch_rec(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
+                              void* scratch, long long scratch_bytes, float* out, const int* table_rows, long long n_table_rows, float* tab_states, float* tab_actions, float* tab_values) {
+    const MiRolloutRec rec = {table_rows, n_table_rows, tab_states, tab_actions, tab_values};
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, &rec);
 }
 
 // VAE.encode (vae/models.py:199-202): frames -> mean [B,Z] fp32

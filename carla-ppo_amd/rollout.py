@@ -26,6 +26,25 @@ environments; the flat layers' MFMA rows, 31 of 32 empty at one frame, carry the
 On the measured box one call takes 70 / 96 / 310 us for 2 / 8 / 64 environments against 127 / 504 / 3840 us for a loop of RolloutStep calls; at one environment it
 is 3 us slower than RolloutStep (66 against 63 us).  The two-call path (vae.encode + ppo.predict of the batch) was not faster at any measured E up to 64 (3.0 x
 slower at E = 1, 1.3 x at E = 64; profiles/r08_rollout_batch.md).
+
+RolloutBuffer joins that step to the PPO update without a trip through the host: its step is the batched step with RECORDING heads (mi_rollout_step_batch_rec), which leave
+the state [z | measurements], the action and the value of every environment in device tables of num_envs x (horizon + 1) rows -- the tables mi_ppo_train_step_idx gathers
+from.  A row is one episode segment, as the reference's loop collects it (train.py:139-207): it ends when its environment reports done or reaches the horizon, and the slot
+behind its last step holds the bootstrap state and value (train.py:172).  update() finishes the ragged rows in one launch (mi_rollout_finish: GAE, returns, per-row
+normalisation, fp64, bit for bit the dense kernels on each row alone) and runs the epochs of shuffled minibatches from the tables:
+
+    buf = RolloutBuffer(vae, ppo, num_envs=8, horizon=128)
+    buf.reset()
+    live = np.arange(8)
+    while len(live):
+        actions, values, states = buf.step(frames[live], measurements[live], env_ids=live)
+        rewards, dones = simulator(actions)                                     # host arrays, 16 bytes per step
+        buf.outcome(rewards, dones, env_ids=live)
+        live = live[(~dones) & (buf.lengths[live] < buf.horizon)]
+    buf.bootstrap(last_frames, last_measurements)                               # every environment that was stepped: closes the rows
+    out = buf.update(gamma=0.99, lam=0.95, num_epochs=3, batch_size=32)
+
+Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import os
 
@@ -167,3 +186,290 @@ class BatchedRolloutStep:
         actions, values = o[:, :self.A].copy(), o[:, self.A].copy()
         states = np.concatenate([o[:, self.A + 1:].astype(np.float64), meas], axis=1)
         return actions, values, states
+
+
+MAX_HORIZON = 4096                                                                   # MI_ROLLOUT_MAX_HORIZON of include/mi355_carla.h
+
+
+class RolloutRows:
+    """The row book-keeping of a RolloutBuffer; numpy only (no torch, no GPU).  Environment e owns the table rows e (horizon + 1) .. e (horizon + 1) + horizon.  A row is
+    open (it takes steps), awaiting the outcome of its last recorded step, ended (its environment reported done or it is full: it takes the bootstrap only) or closed
+    (bootstrapped).  Every method checks its whole call before it changes anything and raises ValueError."""
+
+    def __init__(self, num_envs, horizon):
+        self.num_envs, self.horizon = int(num_envs), int(horizon)
+        if not 1 <= self.num_envs <= MAX_ENVS:
+            raise ValueError("RolloutBuffer: 1 <= num_envs <= %d" % MAX_ENVS)
+        if not 1 <= self.horizon <= MAX_HORIZON:
+            raise ValueError("RolloutBuffer: 1 <= horizon <= %d" % MAX_HORIZON)
+        self._all = np.arange(self.num_envs, dtype=np.int64)
+        self._base = (self._all * (self.horizon + 1)).astype(np.int32)               # table row of slot 0 of every environment
+        self.reset()
+
+    OPEN, AWAITING, ENDED, CLOSED = 0, 1, 2, 3                                        # per row, one small array: a call is a handful of numpy operations
+
+    def reset(self):
+        E, T = self.num_envs, self.horizon
+        self.lengths = np.zeros(E, np.int32)
+        self.state = np.zeros(E, np.int8)
+        self.rewards, self.dones = np.zeros((E, T), np.float64), np.zeros((E, T), np.float64)
+
+    @property
+    def awaiting(self):
+        """A step is recorded at slot lengths[e]; its reward / done are not in yet."""
+        return self.state == self.AWAITING
+
+    @property
+    def ended(self):
+        """done was reported or the horizon is reached: no further step, the bootstrap only."""
+        return self.state == self.ENDED
+
+    @property
+    def closed(self):
+        return self.state == self.CLOSED
+
+    def env_ids(self, env_ids, n):
+        """env_ids (None = 0 .. n-1) of a call with n rows -> int64 [n], distinct, inside [0, num_envs)."""
+        if env_ids is None:                                                          # 0 .. n-1: distinct and in range once n is
+            if n < 1 or n > self.num_envs:
+                raise ValueError("RolloutBuffer: 1 <= n <= num_envs = %d, got %d" % (self.num_envs, n))
+            return self._all[:n]
+        ids = np.asarray(env_ids)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu":
+            raise ValueError("RolloutBuffer: env_ids must be a vector of integers")
+        ids = ids.astype(np.int64)
+        if ids.shape[0] != n:
+            raise ValueError("RolloutBuffer: %d env_ids for %d rows" % (ids.shape[0], n))
+        if n < 1 or n > self.num_envs:
+            raise ValueError("RolloutBuffer: 1 <= n <= num_envs = %d, got %d" % (self.num_envs, n))
+        if ids.min() < 0 or ids.max() >= self.num_envs:
+            raise ValueError("RolloutBuffer: env_ids outside [0, %d)" % self.num_envs)
+        if np.unique(ids).shape[0] != n:
+            raise ValueError("RolloutBuffer: duplicate env_ids")
+        return ids
+
+    def _rows(self, ids):
+        return self._base[ids] + self.lengths[ids]                                   # int32
+
+    def _refuse(self, what, ids, st, codes):
+        for code, why in codes:
+            if (st == code).any():
+                raise ValueError("RolloutBuffer: %s %s (environments %s)" % (what, why, ids[st == code].tolist()))
+
+    def step_rows(self, env_ids, n):
+        """The table rows a step of these environments records into; marks them as awaiting their outcome."""
+        ids = self.env_ids(env_ids, n)
+        st = self.state[ids]
+        if st.any():
+            self._refuse("step on", ids, st, ((self.CLOSED, "a closed row"), (self.AWAITING, "a row whose last step has no outcome yet"),
+                                              (self.ENDED, "a full row -- done was reported or the horizon is reached")))
+        rows = self._rows(ids)
+        self.state[ids] = self.AWAITING
+        return rows
+
+    def outcome(self, rewards, dones, env_ids=None):
+        """Reward and done of the step just recorded for these environments: the step now counts."""
+        r = np.asarray(rewards, np.float64)
+        d = np.asarray(dones)
+        if r.ndim != 1 or d.shape != r.shape:
+            raise ValueError("RolloutBuffer: rewards and dones must be vectors of one length")
+        ids = self.env_ids(env_ids, r.shape[0])
+        st = self.state[ids]
+        if (st != self.AWAITING).any():
+            raise ValueError("RolloutBuffer: outcome without a recorded step (environments %s)" % ids[st != self.AWAITING].tolist())
+        slot = self.lengths[ids]
+        self.rewards[ids, slot], self.dones[ids, slot] = r, d
+        self.lengths[ids] = slot + 1
+        self.state[ids] = np.where(d.astype(bool) | (slot + 1 >= self.horizon), self.ENDED, self.OPEN)
+
+    def bootstrap_rows(self, env_ids, n):
+        """The table rows (slot lengths[e]) that take the state after the last step and its value; closes the rows."""
+        ids = self.env_ids(env_ids, n)
+        st = self.state[ids]
+        self._refuse("bootstrap of", ids, st, ((self.CLOSED, "a closed row"), (self.AWAITING, "a row whose last step has no outcome yet")))
+        if (self.lengths[ids] < 1).any():
+            raise ValueError("RolloutBuffer: bootstrap of an empty row (environments %s)" % ids[self.lengths[ids] < 1].tolist())
+        rows = self._rows(ids)
+        self.state[ids] = self.CLOSED
+        return rows
+
+    def stepped(self):
+        """Environments with a non-empty row that is not closed yet (the default of RolloutBuffer.bootstrap)."""
+        return np.nonzero((self.lengths > 0) & (self.state != self.CLOSED))[0]
+
+    def check_update(self):
+        open_rows = np.nonzero(((self.lengths > 0) | (self.state == self.AWAITING)) & (self.state != self.CLOSED))[0]
+        if open_rows.size:
+            raise ValueError("RolloutBuffer: update with open rows (environments %s): bootstrap them first" % open_rows.tolist())
+        if int(self.lengths.sum()) < 1:
+            raise ValueError("RolloutBuffer: update with no samples")
+
+    def valid_rows(self):
+        """Table rows of all recorded steps: rows in environment order, slots ascending (int32)."""
+        T1 = self.horizon + 1
+        parts = [e * T1 + np.arange(self.lengths[e]) for e in range(self.num_envs)]
+        return np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+
+
+class _RecordingStep(BatchedRolloutStep):
+    """BatchedRolloutStep whose input buffer also carries the int32 table rows (behind the noise) and whose call is mi_rollout_step_batch_rec."""
+
+    def __init__(self, vae, ppo, num_envs, seed=None, io=None):
+        import torch
+        super().__init__(vae, ppo, num_envs, seed=seed, io=io)
+        nbytes = self._f_off + 4 * self.num_envs * (self.n_meas + self.A + 1)
+        self.h_in = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        self.d_in = torch.empty(nbytes, dtype=torch.uint8, device=self.device) if self.io == "device" else None
+        self._in_np = self.h_in.numpy()
+        self._f_np = self._in_np[self._f_off:].view(np.float32)
+        self._i_np = self._in_np[self._f_off:].view(np.int32)
+
+    def check(self, frames_u8, measurements, greedy, noise):
+        """The host-side checks of BatchedRolloutStep.__call__ -> (frames, n, measurements float64 [n, k], noise float32 [n, A] or None)."""
+        f = np.asarray(frames_u8)
+        if f.dtype != np.uint8 or f.ndim < 1 or f.size != f.shape[0] * self.frame_bytes:
+            raise ValueError("RolloutBuffer: expected uint8 frames [n, ...] of %d bytes each" % self.frame_bytes)
+        n = int(f.shape[0])
+        if not 1 <= n <= self.num_envs:
+            raise ValueError("RolloutBuffer: 1 <= n <= num_envs = %d, got %d" % (self.num_envs, n))
+        meas = np.asarray(measurements, np.float64)
+        if meas.shape != (n, self.n_meas):
+            raise ValueError("RolloutBuffer: expected measurements [%d, %d]" % (n, self.n_meas))
+        nz = None
+        if not greedy and noise is not None:
+            nz = np.asarray(noise, np.float32)
+            if nz.shape != (n, self.A):
+                raise ValueError("RolloutBuffer: expected noise [%d, %d]" % (n, self.A))
+        return f, n, meas, nz
+
+    def record(self, f, n, meas, nz, greedy, table_rows, states, actions, values):
+        import torch
+        nm, na = n * self.n_meas, n * self.A
+        if not greedy:
+            self._f_np[nm:nm + na] = (self._rng.standard_normal((n, self.A)) if nz is None else nz).reshape(-1)
+        self._in_np[:n * self.frame_bytes] = f.reshape(-1)
+        self._f_np[:nm] = meas.reshape(-1)                                           # f64 -> f32 at the feed, as ppo.py:108-109
+        self._i_np[nm + na:nm + na + n] = table_rows
+        st = torch.cuda.current_stream(self.device)
+        used = self._f_off + 4 * (nm + na + n)
+        if self.d_in is not None:
+            self.d_in[:used].copy_(self.h_in[:used], non_blocking=True)
+        base = (self.h_in if self.d_in is None else self.d_in).data_ptr()
+        fptr = base + self._f_off
+        self.L.mi_rollout_step_batch_rec(self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, None if greedy else fptr + 4 * nm,
+                                         1 if greedy else 0, n, self.scratch.data_ptr(), self.scratch_bytes, (self.h_out if self.d_out is None else self.d_out).data_ptr(),
+                                         fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), actions.data_ptr(), values.data_ptr())
+        if self.d_out is not None:
+            self.h_out[:n * self.row].copy_(self.d_out[:n * self.row], non_blocking=True)
+        st.synchronize()
+        o = self._out_np[:n]
+        return o[:, :self.A].copy(), o[:, self.A].copy(), np.concatenate([o[:, self.A + 1:].astype(np.float64), meas], axis=1)
+
+
+class RolloutBuffer:
+    """Device-resident rollout buffer for `num_envs` environments and a horizon of T steps that PPO updates train from (see the module docstring).  Device tables of
+    num_envs (T + 1) rows, row e (T + 1) + t = slot t of environment e: states fp32 [input_dim], actions fp32 [A], values, returns, advantages, logp_old fp32 scalars.
+    Rewards and dones stay host arrays [num_envs, T] (self.rows) and are uploaded once per update."""
+
+    def __init__(self, vae, ppo, num_envs, horizon, seed=None, io=None):
+        import torch
+        self.rows = RolloutRows(num_envs, horizon)                                   # (raises before anything touches a device)
+        self.vae, self.ppo = vae, ppo
+        self.num_envs, self.horizon = self.rows.num_envs, self.rows.horizon
+        self._step = _RecordingStep(vae, ppo, self.num_envs, seed=seed, io=io)
+        self.io, self.device, self.L = self._step.io, self._step.device, self._step.L
+        n = self.n_table_rows = self.num_envs * (self.horizon + 1)
+        self.states = torch.zeros(n, int(ppo.input_dim), device=self.device)
+        self.actions = torch.zeros(n, int(ppo.num_actions), device=self.device)
+        self.values, self.returns, self.advantages, self.logp_old = (torch.zeros(n, device=self.device) for _ in range(4))
+
+    @property
+    def lengths(self):
+        return self.rows.lengths
+
+    def reset(self):
+        """All rows empty and open."""
+        self.rows.reset()
+
+    def step(self, frames_u8, measurements, env_ids=None, greedy=False, noise=None):
+        """BatchedRolloutStep.__call__ of these frames, and row i of the call is recorded at slot lengths[env_ids[i]] of environment env_ids[i] (None: 0 .. n-1)."""
+        f, n, meas, nz = self._step.check(frames_u8, measurements, greedy, noise)
+        rows = self.rows.step_rows(env_ids, n)
+        return self._step.record(f, n, meas, nz, greedy, rows, self.states, self.actions, self.values)
+
+    def outcome(self, rewards, dones, env_ids=None):
+        """Reward and done of the step just recorded for these environments (the simulator's answer to the action); the row's length grows by one."""
+        self.rows.outcome(rewards, dones, env_ids)
+
+    def bootstrap(self, frames_u8, measurements, env_ids=None):
+        """The state after the last step of these environments (None: every stepped row still open) and its value into slot lengths[e] (train.py:172; computed after a
+        terminal too, the terminal flag masks it); closes the rows.  A greedy recording call: the action slot it writes is never read."""
+        if env_ids is None:
+            env_ids = self.rows.stepped()
+        f, n, meas, _ = self._step.check(frames_u8, measurements, True, None)
+        rows = self.rows.bootstrap_rows(env_ids, n)
+        return self._step.record(f, n, meas, None, True, rows, self.states, self.actions, self.values)
+
+    def update(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, stage_times=None):
+        """One PPO update from the tables (train.py:175-207 over the recorded rows): mi_rollout_finish, update_old_policy, log pi_old once, num_epochs x shuffled
+        minibatches of batch_size (the last one partial) with the gather inside the step's kernels.  Returns the per-minibatch loss records (replay_update's keys),
+        `lengths`, and fp64 `returns` / `advantages` / `raw_advantages` and fp32 `values` as [num_envs, T] arrays, NaN beyond a row's length."""
+        import time
+        import torch
+        from mi355 import dist as midist
+        if midist.world_size() > 1:
+            raise ValueError("RolloutBuffer.update: single rank only (ragged rows give ranks different numbers of gradient all-reduces)")
+        if int(batch_size) < 1 or int(num_epochs) < 0:
+            raise ValueError("RolloutBuffer.update: batch_size >= 1, num_epochs >= 0")
+        self.rows.check_update()
+        batch_size = int(batch_size)
+        E, T, ppo, device = self.num_envs, self.horizon, self.ppo, self.device
+        pdev = ppo._need_dev()
+        valid = self.rows.valid_rows()
+        n_valid = int(valid.shape[0])
+        lengths = self.rows.lengths.copy()
+
+        def mark(name, t0):
+            if stage_times is not None:
+                torch.cuda.synchronize(device)
+                stage_times[name] = stage_times.get(name, 0.0) + time.perf_counter() - t0
+            return time.perf_counter()
+        t_stage = time.perf_counter()
+        st = torch.cuda.current_stream(device).cuda_stream
+        r = torch.from_numpy(self.rows.rewards).to(device)
+        d = torch.from_numpy(self.rows.dones).to(device)
+        ln = torch.from_numpy(lengths).to(device)
+        f64 = torch.full((3, E, T), float("nan"), dtype=torch.float64, device=device)      # raw advantages, returns, normalised advantages (inspection)
+        self.L.mi_rollout_finish(st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), ln.data_ptr(), E, T, float(gamma), float(lam), self.returns.data_ptr(),
+                                 self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
+        t_stage = mark("finish", t_stage)
+        ppo.update_old_policy()
+        # theta_old is fixed for the whole update: log pi_old(a | s) once per table row, in chunks of 4096 rows that hold a recorded step (slots that hold none are
+        # computed along and never read: the tables start as zeros)
+        fused = pdev.fused_ok()
+        logp_old = self.logp_old if fused else None
+        if fused:
+            for lo in range(0, self.n_table_rows, 4096):
+                hi = min(lo + 4096, self.n_table_rows)
+                if np.any((valid >= lo) & (valid < hi)):
+                    pdev.logp_old(self.states[lo:hi], self.actions[lo:hi], hi - lo, self.logp_old[lo:hi])
+        t_stage = mark("logp_old", t_stage)
+        records = []
+        for _ in range(int(num_epochs)):
+            indices = np.arange(n_valid)
+            np.random.shuffle(indices)                                               # legacy numpy RNG, as train.py:194-195
+            perm = torch.from_numpy(valid[indices]).to(device)                       # shuffled positions -> table rows
+            for i in range(0, n_valid, batch_size):
+                mb = perm[i:i + batch_size]                                          # the last one may be partial (train.py:199-201)
+                m = int(mb.numel())
+                ppo._step_rows(self.states, self.actions, self.returns, self.advantages, logp_old, mb, m, m)
+                ppo.train_step_counter += 1
+                records.append(pdev.losses.clone())
+        losses = torch.stack(records).cpu().numpy() if records else np.zeros((0, 5), np.float32)
+        mark("sgd", t_stage)
+        keys = ("policy_loss", "value_loss", "entropy_loss", "loss", "prob_ratio")
+        f64 = f64.cpu().numpy()
+        v_all = self.values.view(E, T + 1).cpu().numpy()
+        values = np.where(np.arange(T)[None, :] < lengths[:, None], v_all[:, :T], np.float32(np.nan)).astype(np.float32)
+        return {"losses": [dict(zip(keys, (float(x) for x in row))) for row in losses], "lengths": lengths, "raw_advantages": f64[0], "returns": f64[1],
+                "advantages": f64[2], "values": values, "bootstrap_values": np.where(lengths > 0, v_all[np.arange(E), lengths], np.float32(np.nan)).astype(np.float32), "samples": n_valid}

@@ -390,6 +390,20 @@ int mi_rollout_step(void* vae_h, void* ppo_h, void* stream, const unsigned char*
 #define MI_ROLLOUT_MAX_ENVS 1024
 long long mi_rollout_batch_workspace_bytes(void* vae_h, void* ppo_h, int n_envs);
 int mi_rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n, void* scratch, long long scratch_bytes, float* out);
+/* the batched step that also RECORDS what it computed (same eight launches, the last one being the recording heads) — vae_common.py:45-61 + ppo.py:231-251 per environment, and the
+ * state / value the trainer keeps per step and for the bootstrap (train.py:172): the arguments of mi_rollout_step_batch, and call row e is stored as row r = table_rows[e] of
+ * the horizon-batch tables mi_ppo_train_step_idx gathers from: tab_states[r] = [z | measurements[e]] (z_dim + n_meas floats), tab_actions[r] (num_actions floats),
+ * tab_values[r] -- the registers that go to `out`, bit for bit.  table_rows: int32 [n], HBM or pinned host memory like the other inputs; a row outside [0, n_table_rows)
+ * (-1 = "do not record this environment") is skipped: no value of it stores outside the tables.  The tables are HBM with n_table_rows rows each.  Same checks as
+ * mi_rollout_step_batch, plus missing tables. */
+int mi_rollout_step_batch_rec(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n, void* scratch, long long scratch_bytes, float* out, const int* table_rows, long long n_table_rows, float* tab_states, float* tab_actions, float* tab_values);
+/* finishes a RAGGED rollout buffer in one launch — compute_gae (utils.py:45-50) + returns and advantage normalisation (train.py:175-177) per row: row e of num_envs has
+ * len[e] = L <= T recorded steps in slots 0 .. L-1 of its T + 1 table slots (table row e (T + 1) + t) and the bootstrap value in slot L.  tab_values: the fp32 values table;
+ * rewards / terminals: fp64 [num_envs, T]; len: int32 [num_envs] (all device).  fp64 with the rounding sequence of mi_gae_scan + mi_adv_normalize on that row alone (divisor L,
+ * population std, + 1e-8), bit for bit.  Writes fp32 returns / normalised advantages into tab_returns / tab_advantages (round to nearest even) and, where non-NULL, fp64
+ * raw advantages / returns / normalised advantages [num_envs, T].  Slots >= L and rows with L = 0 are not written.  1 <= T <= MI_ROLLOUT_MAX_HORIZON. */
+#define MI_ROLLOUT_MAX_HORIZON 4096
+int mi_rollout_finish(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* len, int num_envs, int T, double gamma, double lam, float* tab_returns, float* tab_advantages, double* adv_raw, double* returns, double* adv_norm);
 
 /* ---- collectives of the data-parallel path (no reference counterpart: the reference is single-process) ----
  * RCCL over xGMI, one communicator per process = per GPU; librccl.so.1 is bound at mi_comm_init (a single-GPU process never loads it).

@@ -1,0 +1,99 @@
+"""Seconds per PPO update from a device-resident rollout buffer (rollout.RolloutBuffer.update) against replay.replay_update on the same collection, from host
+uint8 frames and from a device-resident frame table, with both functions' stage times.
+
+    python tools/rollout_buffer_bench.py [--envs 64] [--steps 128] [--batch 32,2048] [--epochs 1] [--rounds 3] [--no-host-frames] [--no-box]
+
+The collection: E environments x T steps (full rows, no terminal), frames drawn from a pool of random camera frames; the buffer records it through its own step
+(mi_rollout_step_batch_rec), replay_update is handed the frames, the measurements and the actions the buffer's steps returned.  The three paths are interleaved in
+every round; a line gives the median over the rounds and the stage times of the median round's neighbours (all rounds are printed).  The SGD stage is the same code
+on every path; what differs is everything in front of it: upload + encode + values + GAE + casts against finish + log pi_old."""
+import argparse, os, sys, tempfile, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
+    sys.path.insert(0, p)
+import numpy as np, torch
+from vae.models import ConvVAE
+from ppo import PPO
+import replay
+from rollout import RolloutBuffer
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--envs", type=int, default=64)
+ap.add_argument("--steps", type=int, default=128)
+ap.add_argument("--batch", default="32,2048")
+ap.add_argument("--epochs", type=int, default=1)
+ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--pool", type=int, default=512, help="distinct random frames the collection draws from")
+ap.add_argument("--no-host-frames", action="store_true", help="skip replay_update from host frames (E x (T + 1) x 38400 bytes of host memory)")
+ap.add_argument("--no-box", action="store_true")
+args = ap.parse_args()
+
+
+class Box:
+    low, high, shape = np.array([-1.0, 0.0], np.float32), np.array([1.0, 1.0], np.float32), (2,)
+
+
+vae = ConvVAE(np.array([80, 160, 3]), z_dim=64, model_dir=tempfile.mkdtemp(), precision="bf16", training=False, seed=0)
+vae.init_session(init_logging=False)
+agent = PPO(np.array([67]), Box(), learning_rate=1e-4, lr_decay=1.0, epsilon=0.2, value_scale=1.0, entropy_scale=0.01, initial_std=1.0, model_dir=tempfile.mkdtemp())
+agent.init_session(init_logging=False)
+if not args.no_box:
+    from bench import box_probe
+    b = box_probe(agent.dev, 0)
+    print("box: %.0f TFLOP/s bf16 MFMA at %.0f MHz, %.2f TB/s read" % (b["mfma_bf16_tflops"], b["sclk_mhz"], b["hbm_read_tbps"]), flush=True)
+
+E, T = args.envs, args.steps
+rng = np.random.RandomState(0)
+pool = rng.randint(0, 256, (args.pool, 80, 160, 3), dtype=np.uint8)
+idx = rng.randint(0, args.pool, (E, T + 1))
+meas = np.stack([rng.uniform(-1, 1, (E, T + 1)), rng.uniform(0, 1, (E, T + 1)), rng.uniform(0, 30, (E, T + 1))], axis=-1).astype(np.float32)
+rewards, dones = rng.uniform(0, 1, (E, T)), np.zeros((E, T))
+frames_d = torch.from_numpy(pool).to("cuda")[torch.from_numpy(idx).to("cuda")]           # [E, T + 1, 80, 160, 3] uint8 in HBM
+frames_h = None if args.no_host_frames else pool[idx]
+
+buf = RolloutBuffer(vae, agent, E, T)
+
+
+def collect():
+    buf.reset()
+    acts = np.zeros((E, T, 2), np.float32)
+    t0 = time.perf_counter()
+    for t in range(T):
+        a, _, _ = buf.step(pool[idx[:, t]], meas[:, t])
+        acts[:, t] = a
+        buf.outcome(rewards[:, t], dones[:, t])
+    buf.bootstrap(pool[idx[:, T]], meas[:, T])
+    return acts, time.perf_counter() - t0
+
+
+actions, t_collect = collect()
+print("collection of %d x %d steps through the recording step: %.3f s (%.1f us per call incl. the host's frame gather)" % (E, T, t_collect, 1e6 * t_collect / (T + 1)), flush=True)
+
+
+def run(path, batch):
+    st = {}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    if path == "buffer":
+        buf.update(num_epochs=args.epochs, batch_size=batch, stage_times=st)
+    else:
+        replay.replay_update(vae, agent, frames_h if path == "replay, host frames" else frames_d, meas, actions, rewards, dones, num_epochs=args.epochs, batch_size=batch, stage_times=st)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, st
+
+
+paths = ["buffer", "replay, device frames"] + ([] if frames_h is None else ["replay, host frames"])
+for batch in [int(x) for x in args.batch.split(",") if x]:
+    for p in paths:
+        run(p, batch)                                                                     # warm-up (engine growth, allocator)
+    res = {p: [] for p in paths}
+    for _ in range(args.rounds):
+        for p in paths:
+            res[p].append(run(p, batch))
+    print("E x T = %d x %d, batch_size %d, %d epoch(s), %d SGD steps:" % (E, T, batch, args.epochs, args.epochs * -(-E * T // batch)), flush=True)
+    for p in paths:
+        tot = sorted(r[0] for r in res[p])
+        med = tot[len(tot) // 2]
+        stages = next(r[1] for r in res[p] if r[0] == med)
+        front = sum(v for k, v in stages.items() if k != "sgd")
+        print("  %-22s %.4f s (rounds %.4f - %.4f)  in front of the SGD loop %.4f s  | %s" % (p, med, tot[0], tot[-1], front, "  ".join("%s %.4f" % kv for kv in stages.items())), flush=True)

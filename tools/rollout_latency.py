@@ -1,11 +1,13 @@
 """Latency of the rollout-loop inference path at batch 1 (SURVEY 8f.3 callers: vae_common.py:45-61, train.py:142, run_eval.py:54):
 VAE.encode([frame]) (host frame -> device, conv stack, mean to host) followed by PPO.predict(state) (host -> device, two MLP trunks, action to host).
 
-    python tools/rollout_latency.py --envs [1,2,4,8,16,32,64] [--rounds 3] [--calls 200] [--batched-only] [--no-box]
+    python tools/rollout_latency.py --envs [1,2,4,8,16,32,64] [--rounds 3] [--calls 200] [--batched-only | --record] [--no-box]
 
 times, for each number of environments E, one BatchedRolloutStep call against a loop of E RolloutStep calls and against the two-call path (VAE.encode of E float
 frames + PPO.predict of E states) on the same engines: the three are interleaved in every round, the line gives the median of the rounds' medians, the spread of
-those medians (min - max) and the p90 over all calls.  --batched-only runs the batched calls alone (the form a kernel trace is taken of)."""
+those medians (min - max) and the p90 over all calls.  --batched-only runs the batched calls alone (the form a kernel trace is taken of).  --record times
+RolloutBuffer.step (the recording step, mi_rollout_step_batch_rec: the same eight launches, the heads also store state / action / value into the device tables)
+against BatchedRolloutStep, interleaved; the buffer's outcome() / reset() book-keeping runs between the timed calls."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
@@ -25,16 +27,20 @@ ap.add_argument("--envs", nargs="?", const="1,2,4,8,16,32,64", default=None)
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--calls", type=int, default=200, help="timed calls per path, E and round")
 ap.add_argument("--batched-only", action="store_true")
+ap.add_argument("--record", action="store_true", help="RolloutBuffer.step against BatchedRolloutStep")
 ap.add_argument("--no-box", action="store_true")
 args = ap.parse_args()
 rng = np.random.RandomState(0)
 
 
-def timed(fn, calls):
-    for i in range(10): fn(i)
+def timed(fn, calls, after=None):
+    for i in range(10):
+        fn(i)
+        if after: after()
     ts = []
     for i in range(calls):
         t0 = time.perf_counter(); fn(i); ts.append(time.perf_counter() - t0)
+        if after: after()
     return np.array(ts) * 1e6
 
 
@@ -61,16 +67,33 @@ def envs_table():
             z = vae.encode(f32[sl(i)])
             agent.predict(np.concatenate([z, ms[sl(i)]], axis=1))
         paths = [("batched", batched)] if args.batched_only else [("batched", batched), ("loop of B=1", loop), ("two-call", two_call)]
+        after = {}
+        if args.record:
+            from rollout import RolloutBuffer
+            buf = RolloutBuffer(vae, agent, E, horizon=64, io=many.io)
+            zeros, no = np.zeros(E), np.zeros(E, bool)
+
+            def recording(i): buf.step(u8[sl(i)], ms[sl(i)])
+            def book():                                              # untimed: the step's outcome, and a fresh buffer when the rows are full
+                buf.outcome(zeros, no)
+                if buf.lengths[0] >= buf.horizon: buf.reset()
+            fixed = (np.arange(E) * (buf.horizon + 1)).astype(np.int32)
+
+            def device_only(i):                                      # the recording call without the row book-keeping: always slot 0
+                buf._step.record(*buf._step.check(u8[sl(i)], ms[sl(i)], False, None), False, fixed, buf.states, buf.actions, buf.values)
+            paths, after = [("batched", batched), ("recording", recording), ("recording w/o book-keeping", device_only)], {"recording": book}
         ts = {name: [] for name, _ in paths}
         for _ in range(args.rounds):
             for name, fn in paths:
-                ts[name].append(timed(fn, args.calls if name != "loop of B=1" else max(20, args.calls // E)))
+                ts[name].append(timed(fn, args.calls if name != "loop of B=1" else max(20, args.calls // E), after.get(name)))
         line, med = "E = %3d (io=%s):" % (E, many.io), {}
         for name, _ in paths:
             meds = [np.median(t) for t in ts[name]]
             med[name] = np.median(meds)
             line += "  %s %.1f us (rounds %.1f - %.1f, p90 %.1f)" % (name, med[name], min(meds), max(meds), np.percentile(np.concatenate(ts[name]), 90))
-        if not args.batched_only:
+        if args.record:
+            line += "  | recording - batched %+.2f us, w/o book-keeping %+.2f us" % (med["recording"] - med["batched"], med["recording w/o book-keeping"] - med["batched"])
+        elif not args.batched_only:
             line += "  | loop / batched %.2f x, two-call / batched %.2f x" % (med["loop of B=1"] / med["batched"], med["two-call"] / med["batched"])
         print(line, flush=True)
 
