@@ -210,6 +210,130 @@ __global__ __launch_bounds__(64) void rollout_finish_kernel(const float* __restr
         if (adv_norm) adv_norm[flat + t] = an;
     }
 }
+
+// ---------------------------------------------------------------------------------------------------
+// mi_rollout_finish_segments: the same finish for lanes that hold SEVERAL episodes (utils.py:45-50, train.py:175-177 per segment).  A segment is a run of n recorded
+// steps inside one lane's step slots, given by the table row of its first slot; one wave (= one block) per segment runs rollout_finish_kernel's body relative to that
+// slot, so a segment comes out bit for bit as the dense kernels give it on that segment alone.  A segment whose last step is terminal bootstraps from 0.0 and does not
+// read the slot behind it (the next episode's first value, or a stale one).  The deltas need n <= T doubles of LDS: the launch sizes the dynamic LDS by T, not by
+// MI_ROLLOUT_MAX_HORIZON, so that short horizons keep many segments resident per CU.  A descriptor that does not lie inside one lane's step slots is not executed.
+// NORM = 1 (normalisation over the batch): this kernel leaves the raw advantages in adv_raw and the segment's sum in part[seg]; the kernels below do the rest in a
+// fixed order: partials in lane-strided segment order by one wave, no floating-point atomics.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool rollout_seg_decode(int r, int n, int num_envs, int T, long long& flat) {
+    if (n < 1 || r < 0) return false;
+    const int env = r / (T + 1), slot = r - env * (T + 1);
+    if (env >= num_envs || (long long)slot + n > T) return false;      // (a first slot of T, the lane's bootstrap slot, fails here for every n >= 1)
+    flat = (long long)env * T + slot;
+    return true;
+}
+
+template <int NORM>
+__global__ __launch_bounds__(64) void rollout_finish_seg_kernel(const float* __restrict__ values, const double* __restrict__ rewards, const double* __restrict__ terminals,
+                                                                const int* __restrict__ seg_row, const int* __restrict__ seg_len, int num_envs, int T, double gamma, double gl,
+                                                                float* __restrict__ tab_returns, float* __restrict__ tab_adv, double* __restrict__ adv_raw,
+                                                                double* __restrict__ returns, double* __restrict__ adv_norm, double* __restrict__ part) {
+    extern __shared__ double seg_a[];                      // T doubles
+    double* a = seg_a;
+    const int seg = blockIdx.x, lane = threadIdx.x;
+    const int L = seg_len[seg];
+    const long long tab = seg_row[seg];
+    long long flat;
+    if (!rollout_seg_decode((int)tab, L, num_envs, T, flat)) {
+        if (NORM && lane == 0) part[seg] = 0.0;            // adds nothing to the batch sum
+        return;
+    }
+    const float* v = values + tab;
+    const double* r = rewards + flat;
+    const double* d = terminals + flat;
+    for (int t = lane; t < L; t += WAVE) {
+        const double nonterm = __dsub_rn(1.0, d[t]);
+        double vnext = 0.0;                                // behind a terminal last step: the bootstrap value is 0.0 and the slot is not read
+        if (t < L - 1 || d[t] == 0.0) vnext = (double)v[t + 1];
+        a[t] = __dsub_rn(__dadd_rn(r[t], __dmul_rn(__dmul_rn(nonterm, gamma), vnext)), (double)v[t]);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        double carry = 0.0;
+        for (int t = L - 1; t >= 0; --t) {
+            const double y = __dadd_rn(carry, a[t]);
+            carry = __dmul_rn(gl, y);
+            a[t] = y;
+        }
+    }
+    __syncthreads();
+    double s = 0.0;
+    for (int t = lane; t < L; t += WAVE) {
+        s += a[t];
+        const double ret = a[t] + (double)v[t];
+        tab_returns[tab + t] = (float)ret;
+        if (returns) returns[flat + t] = ret;
+        if (NORM || adv_raw) adv_raw[flat + t] = a[t];
+    }
+    s = wave_sum_f64(s);
+    if (NORM) {
+        if (lane == 0) part[seg] = s;
+        return;
+    }
+    const double mean = s / (double)L;
+    double ss = 0.0;
+    for (int t = lane; t < L; t += WAVE) { const double dd = a[t] - mean; ss += dd * dd; }
+    ss = wave_sum_f64(ss);
+    const double sd = sqrt(ss / (double)L);
+    for (int t = lane; t < L; t += WAVE) {
+        const double an = (a[t] - mean) / (sd + 1e-8);
+        tab_adv[tab + t] = (float)an;
+        if (adv_norm) adv_norm[flat + t] = an;
+    }
+}
+
+// One wave: the n_seg partials in lane-strided segment order + the wave reduction.  STAGE 0: stat[0] = mean of all steps of all executed segments (their count from the
+// descriptors, by the same test); STAGE 1: stat[1] = population std from the partial sums of squared deviations.
+template <int STAGE>
+__global__ __launch_bounds__(64) void rollout_seg_reduce_kernel(const double* __restrict__ part, const int* __restrict__ seg_row, const int* __restrict__ seg_len, int n_seg,
+                                                                int num_envs, int T, double* __restrict__ stat) {
+    const int lane = threadIdx.x;
+    double s = 0.0, cnt = 0.0;                             // the count is exact in fp64 (at most 2^22 steps)
+    for (int i = lane; i < n_seg; i += WAVE) {
+        long long flat;
+        s += part[i];
+        if (rollout_seg_decode(seg_row[i], seg_len[i], num_envs, T, flat)) cnt += (double)seg_len[i];
+    }
+    s = wave_sum_f64(s);
+    cnt = wave_sum_f64(cnt);
+    if (lane == 0) stat[STAGE] = cnt < 1.0 ? 0.0 : (STAGE == 0 ? s / cnt : sqrt(s / cnt));
+}
+
+// PASS 0: part[seg] = sum over the segment of (A - mean)^2 (lane-strided from the segment's first slot + the wave reduction); PASS 1: (A - mean) / (std + 1e-8) into the
+// fp32 table and adv_norm.  Both read the raw advantages rollout_finish_seg_kernel<1> left in adv_raw.
+template <int PASS>
+__global__ __launch_bounds__(64) void rollout_seg_norm_kernel(const double* __restrict__ adv_raw, const int* __restrict__ seg_row, const int* __restrict__ seg_len, int num_envs,
+                                                              int T, const double* __restrict__ stat, double* __restrict__ part, float* __restrict__ tab_adv,
+                                                              double* __restrict__ adv_norm) {
+    const int seg = blockIdx.x, lane = threadIdx.x;
+    const int L = seg_len[seg];
+    const long long tab = seg_row[seg];
+    long long flat;
+    if (!rollout_seg_decode((int)tab, L, num_envs, T, flat)) {
+        if (PASS == 0 && lane == 0) part[seg] = 0.0;
+        return;
+    }
+    const double* a = adv_raw + flat;
+    const double mean = stat[0];
+    if (PASS == 0) {
+        double ss = 0.0;
+        for (int t = lane; t < L; t += WAVE) { const double dd = a[t] - mean; ss += dd * dd; }
+        ss = wave_sum_f64(ss);
+        if (lane == 0) part[seg] = ss;
+    } else {
+        const double sd = stat[1];
+        for (int t = lane; t < L; t += WAVE) {
+            const double an = (a[t] - mean) / (sd + 1e-8);
+            tab_adv[tab + t] = (float)an;
+            if (adv_norm) adv_norm[flat + t] = an;
+        }
+    }
+}
 }  // namespace mi
 
 namespace {
@@ -299,6 +423,39 @@ int mi_rollout_finish(void* stream, const float* tab_values, const double* rewar
     hipLaunchKernelGGL(rollout_finish_kernel, dim3(num_envs), dim3(64), 0, (hipStream_t)stream, tab_values, rewards, terminals, len, T, gamma, gamma * lam,
                        tab_returns, tab_advantages, adv_raw, returns, adv_norm);
     return mi_check_launch("rollout_finish");
+}
+
+// scratch of normalize = 1: per-segment sums | per-segment sums of squared deviations | mean, std
+long long mi_rollout_finish_segments_scratch_doubles(int n_seg) { return n_seg < 1 ? -1 : 2LL * n_seg + 2; }
+
+// mi_rollout_finish with segment descriptors in place of len: seg_row / seg_len int32 [n_seg] (device)
+int mi_rollout_finish_segments(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* seg_row, const int* seg_len, int n_seg,
+                               int num_envs, int T, double gamma, double lam, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw,
+                               double* returns, double* adv_norm) {
+    if (!tab_values || !rewards || !terminals || !seg_row || !seg_len || !tab_returns || !tab_advantages)
+        return mi_fail(MI_ERR_ARG, "mi_rollout_finish_segments: missing buffers");
+    if (n_seg < 1 || num_envs < 1 || T < 1) return mi_fail(MI_ERR_ARG, "mi_rollout_finish_segments: empty input (n_seg >= 1, num_envs >= 1, T >= 1)");
+    if (T > MI_ROLLOUT_MAX_HORIZON) return mi_fail(MI_ERR_ARG, "mi_rollout_finish_segments: the horizon exceeds MI_ROLLOUT_MAX_HORIZON");
+    if (normalize != 0 && normalize != 1) return mi_fail(MI_ERR_ARG, "mi_rollout_finish_segments: normalize is 0 (per segment) or 1 (per batch)");
+    if (normalize == 1 && (!scratch || !adv_raw)) return mi_fail(MI_ERR_ARG, "mi_rollout_finish_segments: normalize = 1 needs scratch and adv_raw (missing buffers)");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = (size_t)T * sizeof(double);
+    const double gl = gamma * lam;
+    if (normalize == 0) {
+        hipLaunchKernelGGL(rollout_finish_seg_kernel<0>, dim3(n_seg), dim3(64), lds, st, tab_values, rewards, terminals, seg_row, seg_len, num_envs, T, gamma, gl, tab_returns,
+                           tab_advantages, adv_raw, returns, adv_norm, (double*)nullptr);
+        return mi_check_launch("rollout_finish_seg");
+    }
+    double* part = scratch;
+    double* part2 = scratch + n_seg;
+    double* stat = scratch + 2LL * n_seg;
+    hipLaunchKernelGGL(rollout_finish_seg_kernel<1>, dim3(n_seg), dim3(64), lds, st, tab_values, rewards, terminals, seg_row, seg_len, num_envs, T, gamma, gl, tab_returns,
+                       tab_advantages, adv_raw, returns, adv_norm, part);
+    hipLaunchKernelGGL(rollout_seg_reduce_kernel<0>, dim3(1), dim3(64), 0, st, part, seg_row, seg_len, n_seg, num_envs, T, stat);
+    hipLaunchKernelGGL(rollout_seg_norm_kernel<0>, dim3(n_seg), dim3(64), 0, st, adv_raw, seg_row, seg_len, num_envs, T, stat, part2, tab_advantages, adv_norm);
+    hipLaunchKernelGGL(rollout_seg_reduce_kernel<1>, dim3(1), dim3(64), 0, st, part2, seg_row, seg_len, n_seg, num_envs, T, stat);
+    hipLaunchKernelGGL(rollout_seg_norm_kernel<1>, dim3(n_seg), dim3(64), 0, st, adv_raw, seg_row, seg_len, num_envs, T, stat, part2, tab_advantages, adv_norm);
+    return mi_check_launch("rollout_finish_seg (batch normalisation)");
 }
 
 }  // extern "C"

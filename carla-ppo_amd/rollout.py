@@ -44,6 +44,22 @@ normalisation, fp64, bit for bit the dense kernels on each row alone) and runs t
     buf.bootstrap(last_frames, last_measurements)                               # every environment that was stepped: closes the rows
     out = buf.update(gamma=0.99, lam=0.95, num_epochs=3, batch_size=32)
 
+ContinuousRolloutBuffer is that buffer for vectorised collection: every environment steps `horizon` times per update, and a simulator that reports done hands back its
+reset observation and goes on.  A lane (the horizon + 1 table rows of an environment) then holds several episode SEGMENTS; update() finishes them in one call
+(mi_rollout_finish_segments: GAE, returns and normalisation per segment, each bit for bit the dense kernels on that segment alone; a segment that ends in a done bootstraps
+from 0.0 and never reads the slot behind it, which holds the next episode's first value) and otherwise does what RolloutBuffer.update does.  normalize="batch" normalises the
+advantages over all samples of the update instead (tail segments of one or two steps otherwise come out as 0 or +-1):
+
+    buf = ContinuousRolloutBuffer(vae, ppo, num_envs=8, horizon=128)
+    buf.reset()
+    for _ in range(buf.horizon):                                   # every call carries all 8 environments
+        actions, values, states = buf.step(frames, measurements)
+        rewards, dones, frames, measurements = simulators_step(actions)   # a simulator that reports done returns its reset observation
+        buf.outcome(rewards, dones)
+    need = buf.rows.needs_bootstrap()
+    buf.bootstrap(frames[need], measurements[need], env_ids=need)
+    out = buf.update(num_epochs=3, batch_size=32)                  # exactly 8 x 128 samples
+
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import os
@@ -311,6 +327,50 @@ class RolloutRows:
         return np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
 
 
+class SegmentedRows(RolloutRows):
+    """RolloutRows for lanes that hold SEVERAL episodes (ContinuousRolloutBuffer): a done does not end a lane, the next step of that environment records at slot
+    lengths[e] and starts a new segment; a lane is ended only when it is full.  A segment is a maximal run of recorded steps of a lane that ends at a step with
+    done != 0 or at the lane's last recorded step; only a lane's last segment can end without a done, and slot lengths[e] behind it is the lane's bootstrap slot."""
+
+    def outcome(self, rewards, dones, env_ids=None):
+        super().outcome(rewards, dones, env_ids)                                     # (checks the whole call first)
+        ids = self.env_ids(env_ids, np.asarray(rewards).shape[0])
+        self.state[ids] = np.where(self.lengths[ids] >= self.horizon, self.ENDED, self.OPEN)
+
+    def _last_done(self):
+        """Per lane: its last counted step reported done (False for an empty lane)."""
+        last = np.maximum(self.lengths, 1) - 1
+        return (self.lengths > 0) & (self.dones[self._all, last] != 0)
+
+    def needs_bootstrap(self):
+        """Lanes that are non-empty, not closed, not awaiting an outcome, and whose last counted step has done == 0: their last segment bootstraps from slot lengths[e]."""
+        return np.nonzero((self.lengths > 0) & (self.state != self.CLOSED) & (self.state != self.AWAITING) & ~self._last_done())[0]
+
+    def check_update(self):
+        waiting = np.nonzero(self.state == self.AWAITING)[0]
+        if waiting.size:
+            raise ValueError("RolloutBuffer: update with open rows (environments %s): their last step has no outcome yet" % waiting.tolist())
+        need = self.needs_bootstrap()
+        if need.size:
+            raise ValueError("RolloutBuffer: update with open rows (environments %s): bootstrap them first" % need.tolist())
+        if int(self.lengths.sum()) < 1:
+            raise ValueError("RolloutBuffer: update with no samples")
+
+    def segments(self):
+        """int32 [n_seg, 3] of (environment, first slot, length): lanes in environment order, segments in slot order; every recorded step is in exactly one."""
+        out = []
+        for e in range(self.num_envs):
+            n = int(self.lengths[e])
+            ends = (np.nonzero(self.dones[e, :n] != 0)[0] + 1).tolist()
+            if n and (not ends or ends[-1] != n):
+                ends.append(n)
+            first = 0
+            for end in ends:
+                out.append((e, first, end - first))
+                first = end
+        return np.asarray(out, np.int32).reshape(-1, 3)
+
+
 class _RecordingStep(BatchedRolloutStep):
     """BatchedRolloutStep whose input buffer also carries the int32 table rows (behind the noise) and whose call is mi_rollout_step_batch_rec."""
 
@@ -371,9 +431,11 @@ class RolloutBuffer:
     num_envs (T + 1) rows, row e (T + 1) + t = slot t of environment e: states fp32 [input_dim], actions fp32 [A], values, returns, advantages, logp_old fp32 scalars.
     Rewards and dones stay host arrays [num_envs, T] (self.rows) and are uploaded once per update."""
 
+    _rows_class = RolloutRows
+
     def __init__(self, vae, ppo, num_envs, horizon, seed=None, io=None):
         import torch
-        self.rows = RolloutRows(num_envs, horizon)                                   # (raises before anything touches a device)
+        self.rows = self._rows_class(num_envs, horizon)                              # (raises before anything touches a device)
         self.vae, self.ppo = vae, ppo
         self.num_envs, self.horizon = self.rows.num_envs, self.rows.horizon
         self._step = _RecordingStep(vae, ppo, self.num_envs, seed=seed, io=io)
@@ -414,13 +476,23 @@ class RolloutBuffer:
         """One PPO update from the tables (train.py:175-207 over the recorded rows): mi_rollout_finish, update_old_policy, log pi_old once, num_epochs x shuffled
         minibatches of batch_size (the last one partial) with the gather inside the step's kernels.  Returns the per-minibatch loss records (replay_update's keys),
         `lengths`, and fp64 `returns` / `advantages` / `raw_advantages` and fp32 `values` as [num_envs, T] arrays, NaN beyond a row's length."""
+        def finish(st, r, d, lengths, f64):
+            import torch
+            ln = torch.from_numpy(lengths).to(self.device)
+            self.L.mi_rollout_finish(st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), ln.data_ptr(), self.num_envs, self.horizon, float(gamma), float(lam),
+                                     self.returns.data_ptr(), self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
+        return self._update("RolloutBuffer", finish, num_epochs, batch_size, stage_times)
+
+    def _update(self, who, finish, num_epochs, batch_size, stage_times):
+        """What every buffer's update does around its finish call `finish(stream, rewards, dones, lengths, f64)` (device rewards / dones, fp64 [3, E, T] of NaN for the raw
+        advantages, returns and normalised advantages)."""
         import time
         import torch
         from mi355 import dist as midist
         if midist.world_size() > 1:
-            raise ValueError("RolloutBuffer.update: single rank only (ragged rows give ranks different numbers of gradient all-reduces)")
+            raise ValueError(who + ".update: single rank only (ragged rows give ranks different numbers of gradient all-reduces)")
         if int(batch_size) < 1 or int(num_epochs) < 0:
-            raise ValueError("RolloutBuffer.update: batch_size >= 1, num_epochs >= 0")
+            raise ValueError(who + ".update: batch_size >= 1, num_epochs >= 0")
         self.rows.check_update()
         batch_size = int(batch_size)
         E, T, ppo, device = self.num_envs, self.horizon, self.ppo, self.device
@@ -438,10 +510,8 @@ class RolloutBuffer:
         st = torch.cuda.current_stream(device).cuda_stream
         r = torch.from_numpy(self.rows.rewards).to(device)
         d = torch.from_numpy(self.rows.dones).to(device)
-        ln = torch.from_numpy(lengths).to(device)
         f64 = torch.full((3, E, T), float("nan"), dtype=torch.float64, device=device)      # raw advantages, returns, normalised advantages (inspection)
-        self.L.mi_rollout_finish(st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), ln.data_ptr(), E, T, float(gamma), float(lam), self.returns.data_ptr(),
-                                 self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
+        finish(st, r, d, lengths, f64)
         t_stage = mark("finish", t_stage)
         ppo.update_old_policy()
         # theta_old is fixed for the whole update: log pi_old(a | s) once per table row, in chunks of 4096 rows that hold a recorded step (slots that hold none are
@@ -473,3 +543,41 @@ class RolloutBuffer:
         values = np.where(np.arange(T)[None, :] < lengths[:, None], v_all[:, :T], np.float32(np.nan)).astype(np.float32)
         return {"losses": [dict(zip(keys, (float(x) for x in row))) for row in losses], "lengths": lengths, "raw_advantages": f64[0], "returns": f64[1],
                 "advantages": f64[2], "values": values, "bootstrap_values": np.where(lengths > 0, v_all[np.arange(E), lengths], np.float32(np.nan)).astype(np.float32), "samples": n_valid}
+
+
+class ContinuousRolloutBuffer(RolloutBuffer):
+    """RolloutBuffer whose lanes go on after a done (see the module docstring): every environment steps `horizon` times per update, a simulator that reports done is
+    stepped again with its reset observation, and update() finishes the lanes segment by segment (mi_rollout_finish_segments).  Same tables and recording step."""
+
+    _rows_class = SegmentedRows
+
+    def bootstrap(self, frames_u8, measurements, env_ids=None):
+        """RolloutBuffer.bootstrap; env_ids None: rows.needs_bootstrap() -- a lane whose last step reported done needs none (given one, it is recorded and never read).
+        With no such lane and no frames the call does nothing."""
+        if env_ids is None:
+            env_ids = self.rows.needs_bootstrap()
+        if len(env_ids) == 0 and (frames_u8 is None or len(frames_u8) == 0):         # (the loop's frames[need] with every lane ending in a done)
+            return None
+        return super().bootstrap(frames_u8, measurements, env_ids)
+
+    def update(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, normalize="segment", stage_times=None):
+        """RolloutBuffer.update with one mi_rollout_finish_segments call for the finish.  normalize: "segment" (train.py:176-177 on every segment alone, the reference's
+        semantics) or "batch" (mean and population std over all samples of the update: a 1-step tail segment's advantage is not forced to 0).  Returns RolloutBuffer.update's
+        keys and `segments` (SegmentedRows.segments()); `bootstrap_values` is NaN for lanes whose last step reported done."""
+        if normalize not in ("segment", "batch"):
+            raise ValueError("ContinuousRolloutBuffer.update: normalize is 'segment' or 'batch'")
+        segs = self.rows.segments()
+
+        def finish(st, r, d, lengths, f64):
+            import torch
+            n_seg, T = int(segs.shape[0]), self.horizon
+            desc = torch.from_numpy(np.stack([segs[:, 0] * (T + 1) + segs[:, 1], segs[:, 2]]).astype(np.int32)).to(self.device)     # table row of the first slot | length
+            batch = normalize == "batch"
+            scratch = torch.empty(int(self.L.mi_rollout_finish_segments_scratch_doubles(n_seg)), dtype=torch.float64, device=self.device) if batch else None
+            self.L.mi_rollout_finish_segments(st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), n_seg, self.num_envs, T,
+                                              float(gamma), float(lam), 1 if batch else 0, milib.ptr(scratch), self.returns.data_ptr(), self.advantages.data_ptr(),
+                                              f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
+        out = self._update("ContinuousRolloutBuffer", finish, num_epochs, batch_size, stage_times)
+        out["segments"] = segs
+        out["bootstrap_values"] = np.where(self.rows._last_done(), np.float32(np.nan), out["bootstrap_values"]).astype(np.float32)
+        return out

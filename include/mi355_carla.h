@@ -404,6 +404,18 @@ int mi_rollout_step_batch_rec(void* vae_h, void* ppo_h, void* stream, const unsi
  * raw advantages / returns / normalised advantages [num_envs, T].  Slots >= L and rows with L = 0 are not written.  1 <= T <= MI_ROLLOUT_MAX_HORIZON. */
 #define MI_ROLLOUT_MAX_HORIZON 4096
 int mi_rollout_finish(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* len, int num_envs, int T, double gamma, double lam, float* tab_returns, float* tab_advantages, double* adv_raw, double* returns, double* adv_norm);
+/* the same finish for lanes that hold SEVERAL episodes (continuous collection) — compute_gae (utils.py:45-50) + returns and advantage normalisation (train.py:175-177) per
+ * SEGMENT: segment i is seg_len[i] = n recorded steps that start at table row seg_row[i] = e (T + 1) + s of lane e and lie inside its step slots (s + n <= T); seg_row /
+ * seg_len: int32 [n_seg] on the device; the other buffers as in mi_rollout_finish.  If the segment's last step has terminals != 0 its bootstrap value is 0.0 and the slot
+ * behind it is NOT read (it may hold the next episode's first value, or a stale one); otherwise it is the table value in the slot behind it.  normalize = 0: every segment
+ * comes out bit for bit as mi_gae_scan + mi_adv_normalize give it on that segment alone (divisor n, population std, + 1e-8; fp32 tables round to nearest even).
+ * normalize = 1: returns and raw advantages as before; the normalised advantages use the mean and population std (+ 1e-8) over ALL steps of all segments of the call,
+ * summed in a fixed order (per-segment partials, then the partials in segment order; no floating-point atomics: two calls are bitwise equal); it NEEDS adv_raw (the raw
+ * advantages are read back from it) and `scratch`, device doubles, at least mi_rollout_finish_segments_scratch_doubles(n_seg) = 2 n_seg + 2 of them; scratch may be
+ * NULL with normalize = 0.  A descriptor that does not lie inside one lane's step slots (n < 1, s + n > T, lane >= num_envs, negative row) is not executed; slots that
+ * belong to no executed segment are not written.  n_seg, num_envs, T >= 1, T <= MI_ROLLOUT_MAX_HORIZON. */
+long long mi_rollout_finish_segments_scratch_doubles(int n_seg);
+int mi_rollout_finish_segments(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* seg_row, const int* seg_len, int n_seg, int num_envs, int T, double gamma, double lam, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw, double* returns, double* adv_norm);
 
 /* ---- collectives of the data-parallel path (no reference counterpart: the reference is single-process) ----
  * RCCL over xGMI, one communicator per process = per GPU; librccl.so.1 is bound at mi_comm_init (a single-GPU process never loads it).

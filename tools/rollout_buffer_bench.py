@@ -6,7 +6,13 @@ uint8 frames and from a device-resident frame table, with both functions' stage 
 The collection: E environments x T steps (full rows, no terminal), frames drawn from a pool of random camera frames; the buffer records it through its own step
 (mi_rollout_step_batch_rec), replay_update is handed the frames, the measurements and the actions the buffer's steps returned.  The three paths are interleaved in
 every round; a line gives the median over the rounds and the stage times of the median round's neighbours (all rounds are printed).  The SGD stage is the same code
-on every path; what differs is everything in front of it: upload + encode + values + GAE + casts against finish + log pi_old."""
+on every path; what differs is everything in front of it: upload + encode + values + GAE + casts against finish + log pi_old.
+
+    python tools/rollout_buffer_bench.py --continuous [--mean-episode N] [--envs 8] [--steps 128] [--batch 32] ...
+
+drives ONE scripted set of simulators (episode lengths from a seeded geometric draw with mean N, default a third of the horizon) through rollout.RolloutBuffer (a lane is
+one episode segment: a simulator that reported done waits for the update) and through rollout.ContinuousRolloutBuffer (the simulator goes on from its reset observation),
+and prints for both: step calls per update, samples per update, samples per step call, seconds per collection and seconds per update with the stage times."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
@@ -15,7 +21,7 @@ import numpy as np, torch
 from vae.models import ConvVAE
 from ppo import PPO
 import replay
-from rollout import RolloutBuffer
+from rollout import ContinuousRolloutBuffer, RolloutBuffer
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=64)
@@ -26,6 +32,8 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--pool", type=int, default=512, help="distinct random frames the collection draws from")
 ap.add_argument("--no-host-frames", action="store_true", help="skip replay_update from host frames (E x (T + 1) x 38400 bytes of host memory)")
 ap.add_argument("--no-box", action="store_true")
+ap.add_argument("--continuous", action="store_true", help="RolloutBuffer against ContinuousRolloutBuffer on one scripted set of simulators (no replay paths)")
+ap.add_argument("--mean-episode", type=float, default=None, help="mean of the geometric episode lengths of --continuous (default: steps / 3)")
 args = ap.parse_args()
 
 
@@ -45,6 +53,68 @@ if not args.no_box:
 E, T = args.envs, args.steps
 rng = np.random.RandomState(0)
 pool = rng.randint(0, 256, (args.pool, 80, 160, 3), dtype=np.uint8)
+
+
+def continuous_bench():
+    """Both buffer classes on the same scripted simulators: simulator e's k-th episode lasts episodes[e][k] steps (its last step reports done)."""
+    mean = args.mean_episode or T / 3.0
+    erng = np.random.RandomState(1)
+    episodes = erng.geometric(1.0 / mean, (E, T))                                     # at most T episodes fit into a lane
+    frame_of = erng.randint(0, args.pool, (E, T + 1))
+    ms = np.stack([erng.uniform(-1, 1, (E, T + 1)), erng.uniform(0, 1, (E, T + 1)), erng.uniform(0, 30, (E, T + 1))], axis=-1)
+    rew = erng.uniform(0, 1, (E, T))
+    bufs = {"RolloutBuffer": RolloutBuffer(vae, agent, E, T), "ContinuousRolloutBuffer": ContinuousRolloutBuffer(vae, agent, E, T)}
+
+    def collect(name):
+        b = bufs[name]
+        b.reset()
+        episode, left = np.zeros(E, np.int64), episodes[:, 0].copy()                  # current episode of every simulator, steps left in it
+        live, calls = np.arange(E), 0
+        t0 = time.perf_counter()
+        while len(live):
+            slot = b.lengths[live]
+            b.step(pool[frame_of[live, slot]], ms[live, slot], env_ids=live)
+            left[live] -= 1
+            dones = left[live] == 0
+            b.outcome(rew[live, slot], dones, env_ids=live)
+            calls += 1
+            over = live[dones]
+            episode[over] += 1
+            left[over] = episodes[over, np.minimum(episode[over], T - 1)]
+            keep = b.lengths[live] < T
+            live = live[keep] if name == "ContinuousRolloutBuffer" else live[keep & ~dones]
+        need = b.rows.needs_bootstrap() if name == "ContinuousRolloutBuffer" else b.rows.stepped()
+        if len(need):
+            b.bootstrap(pool[frame_of[need, b.lengths[need]]], ms[need, b.lengths[need]], env_ids=need)
+            calls += 1
+        return calls, time.perf_counter() - t0
+
+    print("mean episode length %.1f steps (drawn: %.1f), E x T = %d x %d" % (mean, episodes.mean(), E, T), flush=True)
+    for batch in [int(x) for x in args.batch.split(",") if x]:
+        res = {name: [] for name in bufs}
+        for rnd in range(args.rounds + 1):                                            # round 0 warms up (engine growth, allocator)
+            for name in bufs:
+                calls, t_collect = collect(name)
+                st = {}
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = bufs[name].update(num_epochs=args.epochs, batch_size=batch, stage_times=st)
+                torch.cuda.synchronize()
+                if rnd:
+                    res[name].append((time.perf_counter() - t0, st, calls, out["samples"], t_collect, len(out["segments"]) if "segments" in out else int((out["lengths"] > 0).sum())))
+        print("batch_size %d, %d epoch(s):" % (batch, args.epochs), flush=True)
+        for name in bufs:
+            tot = sorted(r[0] for r in res[name])
+            med = next(r for r in res[name] if r[0] == tot[len(tot) // 2])
+            _, stages, calls, samples, t_collect, n_seg = med
+            print("  %-24s %4d step calls per update (incl. the bootstrap call), %6d samples per update in %d segments, %6.1f samples per step call, %d SGD steps; "
+                  "collection %.4f s; update %.4f s (rounds %.4f - %.4f) | %s" % (name, calls, samples, n_seg, samples / calls, args.epochs * -(-samples // batch), t_collect, med[0],
+                                                                                  tot[0], tot[-1], "  ".join("%s %.4f" % kv for kv in stages.items())), flush=True)
+
+
+if args.continuous:
+    continuous_bench()
+    sys.exit(0)
 idx = rng.randint(0, args.pool, (E, T + 1))
 meas = np.stack([rng.uniform(-1, 1, (E, T + 1)), rng.uniform(0, 1, (E, T + 1)), rng.uniform(0, 30, (E, T + 1))], axis=-1).astype(np.float32)
 rewards, dones = rng.uniform(0, 1, (E, T)), np.zeros((E, T))
