@@ -117,8 +117,82 @@ __global__ void policy_head_kernel(const float* __restrict__ u, const float* __r
 // ---------------------------------------------------------------------------------------------------
 // GAE (reference utils.py:45-50) in fp64 with the exact rounding sequence of numpy + scipy.signal.lfilter:
 //   delta_t = r_t + ((1-done_t)*gamma)*V_{t+1} - V_t ;  A_t = delta_t + (gamma*lam)*A_{t+1}   (no FMA contraction)
-// One thread per trajectory row; rows are independent (config C5 shards them across GPUs with no exchange).
+// and returns = A + V ; A = (A - mean(A)) / (std(A) + 1e-8), population std (reference train.py:176-177).
+// Every rounding sequence is spelled ONCE, in the helpers below; the dense kernels (one row = one trajectory) and the rollout finish kernels (one row or one
+// episode segment of a ragged buffer) are shells around them, which is what makes a finished row or segment come out bit for bit as the dense kernels give it.
+// Explicit __d*_rn calls or plain operators under -ffp-contract=off; no fma() here.
 // ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double gae_delta(double r, double d, double vnext, double v, double gamma) {      // utils.py:45-48
+    const double nonterm = __dsub_rn(1.0, d);
+    return __dsub_rn(__dadd_rn(r, __dmul_rn(__dmul_rn(nonterm, gamma), vnext)), v);
+}
+
+// one step of lfilter's recurrence, walked from the last step to the first (utils.py:49-50): y = carry + delta ; carry = (gamma*lam) * y
+__device__ __forceinline__ double gae_step(double& carry, double delta, double gl) {
+    const double y = __dadd_rn(carry, delta);
+    carry = __dmul_rn(gl, y);
+    return y;
+}
+
+// One wave, L steps: v = the fp32 value slots (they widen to fp64 exactly), r / d = fp64 rewards / terminals of the first step, a = L doubles of LDS that hold the raw
+// advantages on return.  The deltas do not depend on each other: all lanes form them; the recurrence is serial and lane 0 walks it in the dense kernel's order.
+// SKIP_BEHIND_DONE: behind a terminal LAST step the bootstrap value is 0.0 and slot L is not read; without it slot L is read and the terminal flag masks it (the two
+// differ in the sign of a zero and in what a NaN in slot L does).
+template <bool SKIP_BEHIND_DONE>
+__device__ __forceinline__ void finish_gae(double* a, const float* v, const double* r, const double* d, int L, double gamma, double gl, int lane) {
+    for (int t = lane; t < L; t += WAVE) {
+        double vnext = 0.0;
+        if (!SKIP_BEHIND_DONE || t < L - 1 || d[t] == 0.0) vnext = (double)v[t + 1];
+        a[t] = gae_delta(r[t], d[t], vnext, (double)v[t], gamma);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        double carry = 0.0;
+        for (int t = L - 1; t >= 0; --t) a[t] = gae_step(carry, a[t], gl);
+    }
+    __syncthreads();
+}
+
+// returns = A + V into the fp32 table (f64 -> f32 at the feed, ppo.py:108-109, round to nearest even) and the optional fp64 outputs; -> the wave's sum of A.
+// tab / flat: the first step's position in the [num_envs (T + 1)] tables and in the [num_envs, T] arrays.  RAW_ALWAYS: adv_raw is not optional.
+template <bool RAW_ALWAYS>
+__device__ __forceinline__ double finish_returns(const double* a, const float* v, int L, int lane, long long tab, long long flat, float* tab_returns, double* returns,
+                                                 double* adv_raw) {
+    double s = 0.0;
+    for (int t = lane; t < L; t += WAVE) {
+        s += a[t];
+        const double ret = a[t] + (double)v[t];
+        tab_returns[tab + t] = (float)ret;
+        if (returns) returns[flat + t] = ret;
+        if (RAW_ALWAYS || adv_raw) adv_raw[flat + t] = a[t];
+    }
+    return wave_sum_f64(s);
+}
+
+// sum over the wave's L values of (A - mean)^2, lane-strided from the first + the wave reduction (train.py:176-177's std, before the division)
+__device__ __forceinline__ double sum_sq_dev(const double* a, double mean, int L, int lane) {
+    double ss = 0.0;
+    for (int t = lane; t < L; t += WAVE) { const double dd = a[t] - mean; ss += dd * dd; }
+    return wave_sum_f64(ss);
+}
+
+// (A - mean) / (std + 1e-8) (train.py:177) into the fp32 table and the optional fp64 output
+__device__ __forceinline__ void store_normalized(const double* a, double mean, double sd, int L, int lane, long long tab, long long flat, float* tab_adv, double* adv_norm) {
+    for (int t = lane; t < L; t += WAVE) {
+        const double an = (a[t] - mean) / (sd + 1e-8);
+        tab_adv[tab + t] = (float)an;
+        if (adv_norm) adv_norm[flat + t] = an;
+    }
+}
+
+// the normalisation of one row or segment alone from its raw advantages and their sum s
+__device__ __forceinline__ void finish_normalize(const double* a, double s, int L, int lane, long long tab, long long flat, float* tab_adv, double* adv_norm) {
+    const double mean = s / (double)L;
+    const double sd = sqrt(sum_sq_dev(a, mean, L, lane) / (double)L);
+    store_normalized(a, mean, sd, L, lane, tab, flat, tab_adv, adv_norm);
+}
+
+// One thread per trajectory row; rows are independent (config C5 shards them across GPUs with no exchange).
 __global__ void gae_scan_f64_kernel(const double* __restrict__ rewards, const double* __restrict__ values, const double* __restrict__ terminals,
                                     int R, int T, double gamma, double gl, double* __restrict__ adv) {
     const int row = blockIdx.x * blockDim.x + threadIdx.x;
@@ -128,16 +202,10 @@ __global__ void gae_scan_f64_kernel(const double* __restrict__ rewards, const do
     const double* d = terminals + (long long)row * T;
     double* o = adv + (long long)row * T;
     double carry = 0.0;
-    for (int t = T - 1; t >= 0; --t) {
-        const double nonterm = __dsub_rn(1.0, d[t]);
-        const double delta = __dsub_rn(__dadd_rn(r[t], __dmul_rn(__dmul_rn(nonterm, gamma), v[t + 1])), v[t]);
-        const double y = __dadd_rn(carry, delta);
-        carry = __dmul_rn(gl, y);
-        o[t] = y;
-    }
+    for (int t = T - 1; t >= 0; --t) o[t] = gae_step(carry, gae_delta(r[t], d[t], v[t + 1], v[t], gamma), gl);
 }
 
-// returns = A + V ; A = (A - mean(A)) / (std(A) + 1e-8), population std, per row (reference train.py:176-177). One wave per row.
+// returns = A + V, then the normalisation in place, per row.  One wave per row.  (It adds the values as it sums and normalises where it reads: its own loops.)
 __global__ void adv_normalize_f64_kernel(double* __restrict__ adv, const double* __restrict__ values, int R, int T, double* __restrict__ returns) {
     const int row = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
     const int lane = threadIdx.x & 63;
@@ -148,10 +216,7 @@ __global__ void adv_normalize_f64_kernel(double* __restrict__ adv, const double*
     for (int t = lane; t < T; t += WAVE) { s += a[t]; if (returns) returns[(long long)row * T + t] = a[t] + v[t]; }
     s = wave_sum_f64(s);
     const double mean = s / (double)T;
-    double ss = 0.0;
-    for (int t = lane; t < T; t += WAVE) { const double dd = a[t] - mean; ss += dd * dd; }
-    ss = wave_sum_f64(ss);
-    const double sd = sqrt(ss / (double)T);
+    const double sd = sqrt(sum_sq_dev(a, mean, T, lane) / (double)T);
     for (int t = lane; t < T; t += WAVE) a[t] = (a[t] - mean) / (sd + 1e-8);
 }
 
@@ -159,10 +224,8 @@ __global__ void adv_normalize_f64_kernel(double* __restrict__ adv, const double*
 
 // ---------------------------------------------------------------------------------------------------
 // mi_rollout_finish: GAE + returns + per-row normalisation of a RAGGED rollout buffer in one launch (utils.py:45-50, train.py:175-177 per row).  One wave (= one
-// block) per row; row e has len[e] = L recorded steps in slots 0 .. L-1 of its T + 1 table slots and its bootstrap value in slot L.  The operation sequences are
-// those of gae_scan_f64_kernel and adv_normalize_f64_kernel above (no FMA contraction; the fp32 values widen to fp64 exactly), so a row comes out bit for bit as
-// those two kernels give it on that row alone.  The deltas do not depend on each other: all lanes form them into LDS; the recurrence is serial and lane 0 walks
-// it in the dense kernel's order.  Slots >= L and rows with L < 1 are not written.
+// block) per row; row e has len[e] = L recorded steps in slots 0 .. L-1 of its T + 1 table slots and its bootstrap value in slot L.  The body is the helpers above,
+// so a row comes out bit for bit as gae_scan_f64_kernel and adv_normalize_f64_kernel give it on that row alone.  Slots >= L and rows with L < 1 are not written.
 // ---------------------------------------------------------------------------------------------------
 namespace mi {
 __global__ __launch_bounds__(64) void rollout_finish_kernel(const float* __restrict__ values, const double* __restrict__ rewards, const double* __restrict__ terminals,
@@ -174,47 +237,15 @@ __global__ __launch_bounds__(64) void rollout_finish_kernel(const float* __restr
     if (L < 1) return;
     const long long tab = (long long)row * (T + 1), flat = (long long)row * T;
     const float* v = values + tab;
-    const double* r = rewards + flat;
-    const double* d = terminals + flat;
-    for (int t = lane; t < L; t += WAVE) {
-        const double nonterm = __dsub_rn(1.0, d[t]);
-        a[t] = __dsub_rn(__dadd_rn(r[t], __dmul_rn(__dmul_rn(nonterm, gamma), (double)v[t + 1])), (double)v[t]);
-    }
-    __syncthreads();
-    if (lane == 0) {
-        double carry = 0.0;
-        for (int t = L - 1; t >= 0; --t) {
-            const double y = __dadd_rn(carry, a[t]);
-            carry = __dmul_rn(gl, y);
-            a[t] = y;
-        }
-    }
-    __syncthreads();
-    double s = 0.0;
-    for (int t = lane; t < L; t += WAVE) {
-        s += a[t];
-        const double ret = a[t] + (double)v[t];
-        tab_returns[tab + t] = (float)ret;                 // f64 -> f32 at the feed (ppo.py:108-109), round to nearest even
-        if (returns) returns[flat + t] = ret;
-        if (adv_raw) adv_raw[flat + t] = a[t];
-    }
-    s = wave_sum_f64(s);
-    const double mean = s / (double)L;
-    double ss = 0.0;
-    for (int t = lane; t < L; t += WAVE) { const double dd = a[t] - mean; ss += dd * dd; }
-    ss = wave_sum_f64(ss);
-    const double sd = sqrt(ss / (double)L);
-    for (int t = lane; t < L; t += WAVE) {
-        const double an = (a[t] - mean) / (sd + 1e-8);
-        tab_adv[tab + t] = (float)an;
-        if (adv_norm) adv_norm[flat + t] = an;
-    }
+    finish_gae<false>(a, v, rewards + flat, terminals + flat, L, gamma, gl, lane);
+    const double s = finish_returns<false>(a, v, L, lane, tab, flat, tab_returns, returns, adv_raw);
+    finish_normalize(a, s, L, lane, tab, flat, tab_adv, adv_norm);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // mi_rollout_finish_segments: the same finish for lanes that hold SEVERAL episodes (utils.py:45-50, train.py:175-177 per segment).  A segment is a run of n recorded
-// steps inside one lane's step slots, given by the table row of its first slot; one wave (= one block) per segment runs rollout_finish_kernel's body relative to that
-// slot, so a segment comes out bit for bit as the dense kernels give it on that segment alone.  A segment whose last step is terminal bootstraps from 0.0 and does not
+// steps inside one lane's step slots, given by the table row of its first slot; one wave (= one block) per segment runs the same helpers relative to that slot, so a
+// segment comes out bit for bit as the dense kernels give it on that segment alone.  A segment whose last step is terminal bootstraps from 0.0 and does not
 // read the slot behind it (the next episode's first value, or a stale one).  The deltas need n <= T doubles of LDS: the launch sizes the dynamic LDS by T, not by
 // MI_ROLLOUT_MAX_HORIZON, so that short horizons keep many segments resident per CU.  A descriptor that does not lie inside one lane's step slots is not executed.
 // NORM = 1 (normalisation over the batch): this kernel leaves the raw advantages in adv_raw and the segment's sum in part[seg]; the kernels below do the rest in a
@@ -244,47 +275,13 @@ __global__ __launch_bounds__(64) void rollout_finish_seg_kernel(const float* __r
         return;
     }
     const float* v = values + tab;
-    const double* r = rewards + flat;
-    const double* d = terminals + flat;
-    for (int t = lane; t < L; t += WAVE) {
-        const double nonterm = __dsub_rn(1.0, d[t]);
-        double vnext = 0.0;                                // behind a terminal last step: the bootstrap value is 0.0 and the slot is not read
-        if (t < L - 1 || d[t] == 0.0) vnext = (double)v[t + 1];
-        a[t] = __dsub_rn(__dadd_rn(r[t], __dmul_rn(__dmul_rn(nonterm, gamma), vnext)), (double)v[t]);
-    }
-    __syncthreads();
-    if (lane == 0) {
-        double carry = 0.0;
-        for (int t = L - 1; t >= 0; --t) {
-            const double y = __dadd_rn(carry, a[t]);
-            carry = __dmul_rn(gl, y);
-            a[t] = y;
-        }
-    }
-    __syncthreads();
-    double s = 0.0;
-    for (int t = lane; t < L; t += WAVE) {
-        s += a[t];
-        const double ret = a[t] + (double)v[t];
-        tab_returns[tab + t] = (float)ret;
-        if (returns) returns[flat + t] = ret;
-        if (NORM || adv_raw) adv_raw[flat + t] = a[t];
-    }
-    s = wave_sum_f64(s);
+    finish_gae<true>(a, v, rewards + flat, terminals + flat, L, gamma, gl, lane);
+    const double s = finish_returns<NORM != 0>(a, v, L, lane, tab, flat, tab_returns, returns, adv_raw);
     if (NORM) {
         if (lane == 0) part[seg] = s;
         return;
     }
-    const double mean = s / (double)L;
-    double ss = 0.0;
-    for (int t = lane; t < L; t += WAVE) { const double dd = a[t] - mean; ss += dd * dd; }
-    ss = wave_sum_f64(ss);
-    const double sd = sqrt(ss / (double)L);
-    for (int t = lane; t < L; t += WAVE) {
-        const double an = (a[t] - mean) / (sd + 1e-8);
-        tab_adv[tab + t] = (float)an;
-        if (adv_norm) adv_norm[flat + t] = an;
-    }
+    finish_normalize(a, s, L, lane, tab, flat, tab_adv, adv_norm);
 }
 
 // One wave: the n_seg partials in lane-strided segment order + the wave reduction.  STAGE 0: stat[0] = mean of all steps of all executed segments (their count from the
@@ -304,8 +301,8 @@ __global__ __launch_bounds__(64) void rollout_seg_reduce_kernel(const double* __
     if (lane == 0) stat[STAGE] = cnt < 1.0 ? 0.0 : (STAGE == 0 ? s / cnt : sqrt(s / cnt));
 }
 
-// PASS 0: part[seg] = sum over the segment of (A - mean)^2 (lane-strided from the segment's first slot + the wave reduction); PASS 1: (A - mean) / (std + 1e-8) into the
-// fp32 table and adv_norm.  Both read the raw advantages rollout_finish_seg_kernel<1> left in adv_raw.
+// PASS 0: part[seg] = sum over the segment of (A - mean)^2; PASS 1: (A - mean) / (std + 1e-8) into the fp32 table and adv_norm.  Both read the raw advantages
+// rollout_finish_seg_kernel<1> left in adv_raw.
 template <int PASS>
 __global__ __launch_bounds__(64) void rollout_seg_norm_kernel(const double* __restrict__ adv_raw, const int* __restrict__ seg_row, const int* __restrict__ seg_len, int num_envs,
                                                               int T, const double* __restrict__ stat, double* __restrict__ part, float* __restrict__ tab_adv,
@@ -321,17 +318,10 @@ __global__ __launch_bounds__(64) void rollout_seg_norm_kernel(const double* __re
     const double* a = adv_raw + flat;
     const double mean = stat[0];
     if (PASS == 0) {
-        double ss = 0.0;
-        for (int t = lane; t < L; t += WAVE) { const double dd = a[t] - mean; ss += dd * dd; }
-        ss = wave_sum_f64(ss);
+        const double ss = sum_sq_dev(a, mean, L, lane);
         if (lane == 0) part[seg] = ss;
     } else {
-        const double sd = stat[1];
-        for (int t = lane; t < L; t += WAVE) {
-            const double an = (a[t] - mean) / (sd + 1e-8);
-            tab_adv[tab + t] = (float)an;
-            if (adv_norm) adv_norm[flat + t] = an;
-        }
+        store_normalized(a, mean, stat[1], L, lane, tab, flat, tab_adv, adv_norm);
     }
 }
 }  // namespace mi

@@ -69,9 +69,14 @@ import numpy as np
 from mi355 import lib as milib
 
 
-class RolloutStep:
-    def __init__(self, vae, ppo, seed=None, io=None):
-        import torch
+MAX_ENVS = 1024                                                                      # MI_ROLLOUT_MAX_ENVS of include/mi355_carla.h
+
+
+class _StepBase:
+    """What every step class starts from: the engines' handles, the sizes, the io mode and the Philox noise stream."""
+
+    def _setup(self, who, vae, ppo, seed, io):
+        """-> (the VAE's device engine, the policy's)."""
         self.vae, self.ppo = vae, ppo
         vdev, pdev = vae._need_dev(), ppo._need_dev()
         self.L = vdev.L
@@ -80,21 +85,31 @@ class RolloutStep:
         self.n_meas = int(ppo.input_dim) - self.z_dim
         if self.n_meas < 0:
             raise ValueError("the policy takes fewer inputs than the VAE's latent size")
-        self.frame_bytes = int(np.prod(vdev.source_shape))
-        self._noise_off = (self.frame_bytes + 15) // 16 * 16                         # float region: measurements, then noise
-        nbytes = self._noise_off + 4 * (self.n_meas + self.A)
-        self.h_in = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-        self.d_in = None                                                             # (allocated below for io="device")
-        self.h_out = torch.empty(self.A + 1 + self.z_dim, dtype=torch.float32).pin_memory()
         self.io = io or os.environ.get("MI355_ROLLOUT_IO", "pinned")
         if self.io not in ("pinned", "device"):
-            raise ValueError("RolloutStep: io must be 'pinned' or 'device'")
-        self.d_out = torch.empty(self.A + 1 + self.z_dim, dtype=torch.float32, device=self.device) if self.io == "device" else None
-        self.d_in = torch.empty(nbytes, dtype=torch.uint8, device=self.device) if self.io == "device" else None
+            raise ValueError(who + ": io must be 'pinned' or 'device'")
+        self.frame_bytes = int(np.prod(vdev.source_shape))
+        self._rng = np.random.Generator(np.random.Philox(int(seed if seed is not None else (ppo.seed or 0)) + 0xAC7))
+        return vdev, pdev
+
+    def _io_buffers(self, in_bytes, out_floats):
+        """Pinned host buffers, and their device twins for io="device" (one copy each way per call)."""
+        import torch
+        self.h_in = torch.empty(in_bytes, dtype=torch.uint8).pin_memory()
+        self.h_out = torch.empty(out_floats, dtype=torch.float32).pin_memory()
+        dev_io = self.io == "device"
+        self.d_in = torch.empty(in_bytes, dtype=torch.uint8, device=self.device) if dev_io else None
+        self.d_out = torch.empty(out_floats, dtype=torch.float32, device=self.device) if dev_io else None
         self._in_np = self.h_in.numpy()
+
+
+class RolloutStep(_StepBase):
+    def __init__(self, vae, ppo, seed=None, io=None):
+        self._setup("RolloutStep", vae, ppo, seed, io)
+        self._noise_off = (self.frame_bytes + 15) // 16 * 16                         # float region: measurements, then noise
+        self._io_buffers(self._noise_off + 4 * (self.n_meas + self.A), self.A + 1 + self.z_dim)
         self._f_np = self._in_np[self._noise_off:].view(np.float32)
         self._out_np = self.h_out.numpy()
-        self._rng = np.random.Generator(np.random.Philox(int(seed if seed is not None else (ppo.seed or 0)) + 0xAC7))
 
     def __call__(self, frame_u8, measurements, greedy=False, noise=None):
         """frame_u8: uint8 [H, W, 3] camera frame; measurements: the k values appended to the latent.  Returns (action [A], value, state [z + k])."""
@@ -125,83 +140,82 @@ class RolloutStep:
         return action, value, state
 
 
-MAX_ENVS = 1024                                                                      # MI_ROLLOUT_MAX_ENVS of include/mi355_carla.h
-
-
-class BatchedRolloutStep:
+class BatchedRolloutStep(_StepBase):
     """RolloutStep for up to `num_envs` environments per call (mi_rollout_step_batch): frames_u8 [n, H, W, 3] uint8 and measurements [n, k] in,
     (actions float32 [n, A], values float32 [n], states float64 [n, z_dim + k]) out, 1 <= n <= num_envs -- environments finish their episodes at
     different times.  Row e is what RolloutStep gives for frame e: np.append(vae.encode([frame_e])[0], meas_e) and model.predict of it."""
 
+    _who = "BatchedRolloutStep"                                                      # the prefix of check()'s messages
+    _row_ints = 0                                                                    # int32 per environment behind the noise (the recording step's table rows)
+
     def __init__(self, vae, ppo, num_envs, seed=None, io=None):
         import torch
-        self.vae, self.ppo = vae, ppo
         self.num_envs = int(num_envs)
         if not 1 <= self.num_envs <= MAX_ENVS:
             raise ValueError("BatchedRolloutStep: 1 <= num_envs <= %d" % MAX_ENVS)
-        vdev, pdev = vae._need_dev(), ppo._need_dev()
-        self.L = vdev.L
-        self.device = vdev.device
-        self.z_dim, self.A = int(vae.z_dim), int(ppo.num_actions)
-        self.n_meas = int(ppo.input_dim) - self.z_dim
-        if self.n_meas < 0:
-            raise ValueError("the policy takes fewer inputs than the VAE's latent size")
-        self.io = io or os.environ.get("MI355_ROLLOUT_IO", "pinned")
-        if self.io not in ("pinned", "device"):
-            raise ValueError("BatchedRolloutStep: io must be 'pinned' or 'device'")
+        vdev, pdev = self._setup("BatchedRolloutStep", vae, ppo, seed, io)
         pdev.ensure_batch(self.num_envs)                                             # recreates the engine when it grows: ppo.dev.handle is read per call
         E, self.row = self.num_envs, self.A + 1 + self.z_dim
-        self.frame_bytes = int(np.prod(vdev.source_shape))
-        self._f_off = (E * self.frame_bytes + 15) // 16 * 16                         # float region: measurements [E, k], then noise [E, A]
-        nbytes = self._f_off + 4 * E * (self.n_meas + self.A)
-        self.h_in = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-        self.h_out = torch.empty(E * self.row, dtype=torch.float32).pin_memory()
-        dev_io = self.io == "device"
-        self.d_in = torch.empty(nbytes, dtype=torch.uint8, device=self.device) if dev_io else None
-        self.d_out = torch.empty(E * self.row, dtype=torch.float32, device=self.device) if dev_io else None
+        self._f_off = (E * self.frame_bytes + 15) // 16 * 16                         # float region: measurements [E, k], then noise [E, A], then _row_ints [E]
+        self._io_buffers(self._f_off + 4 * E * (self.n_meas + self.A + self._row_ints), E * self.row)
         self.scratch_bytes = int(self.L.mi_rollout_batch_workspace_bytes(vae.dev.handle, ppo.dev.handle, E))
         if self.scratch_bytes <= 0:
             raise milib.MiError("mi_rollout_batch_workspace_bytes: " + self.L.cdll.mi_last_error().decode())
         self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=self.device)
-        self._in_np = self.h_in.numpy()
         self._f_np = self._in_np[self._f_off:].view(np.float32)
+        self._i_np = self._in_np[self._f_off:].view(np.int32)
         self._out_np = self.h_out.numpy().reshape(E, self.row)
-        self._rng = np.random.Generator(np.random.Philox(int(seed if seed is not None else (ppo.seed or 0)) + 0xAC7))
 
     def __call__(self, frames_u8, measurements, greedy=False, noise=None):
+        return self.record(*self.check(frames_u8, measurements, greedy, noise), greedy)
+
+    def check(self, frames_u8, measurements, greedy, noise):
+        """The host-side checks of a call -> (frames, n, measurements float64 [n, k], noise float32 [n, A] or None)."""
         f = np.asarray(frames_u8)
         if f.dtype != np.uint8 or f.ndim < 1 or f.size != f.shape[0] * self.frame_bytes:
-            raise ValueError("BatchedRolloutStep: expected uint8 frames [n, ...] of %d bytes each" % self.frame_bytes)
+            raise ValueError("%s: expected uint8 frames [n, ...] of %d bytes each" % (self._who, self.frame_bytes))
         n = int(f.shape[0])
         if not 1 <= n <= self.num_envs:
-            raise ValueError("BatchedRolloutStep: 1 <= n <= num_envs = %d, got %d" % (self.num_envs, n))
+            raise ValueError("%s: 1 <= n <= num_envs = %d, got %d" % (self._who, self.num_envs, n))
         meas = np.asarray(measurements, np.float64)
         if meas.shape != (n, self.n_meas):
-            raise ValueError("BatchedRolloutStep: expected measurements [%d, %d]" % (n, self.n_meas))
-        nm, na = n * self.n_meas, n * self.A
-        if not greedy:
-            nz = self._rng.standard_normal((n, self.A)) if noise is None else np.asarray(noise, np.float32)
+            raise ValueError("%s: expected measurements [%d, %d]" % (self._who, n, self.n_meas))
+        nz = None
+        if not greedy and noise is not None:
+            nz = np.asarray(noise, np.float32)
             if nz.shape != (n, self.A):
-                raise ValueError("BatchedRolloutStep: expected noise [%d, %d]" % (n, self.A))
-            self._f_np[nm:nm + na] = nz.reshape(-1)
+                raise ValueError("%s: expected noise [%d, %d]" % (self._who, n, self.A))
+        return f, n, meas, nz
+
+    def record(self, f, n, meas, nz, greedy, table_rows=None, states=None, actions=None, values=None):
+        """One device call on checked inputs.  table_rows None: mi_rollout_step_batch; else the int32 table rows go behind the noise and mi_rollout_step_batch_rec also
+        leaves state / action / value of row i in row table_rows[i] of the device tables `states`, `actions`, `values`."""
+        import torch
+        nm, na = n * self.n_meas, n * self.A
+        nr = 0 if table_rows is None else n
+        if not greedy:
+            self._f_np[nm:nm + na] = (self._rng.standard_normal((n, self.A)) if nz is None else nz).reshape(-1)
         self._in_np[:n * self.frame_bytes] = f.reshape(-1)
         self._f_np[:nm] = meas.reshape(-1)                                           # f64 -> f32 at the feed, as ppo.py:108-109
-        import torch
+        if nr:
+            self._i_np[nm + na:nm + na + nr] = table_rows
         st = torch.cuda.current_stream(self.device)
-        used = self._f_off + 4 * (nm + na)
+        used = self._f_off + 4 * (nm + na + nr)
         if self.d_in is not None:
             self.d_in[:used].copy_(self.h_in[:used], non_blocking=True)
         base = (self.h_in if self.d_in is None else self.d_in).data_ptr()
         fptr = base + self._f_off
-        self.L.mi_rollout_step_batch(self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, None if greedy else fptr + 4 * nm,
-                                     1 if greedy else 0, n, self.scratch.data_ptr(), self.scratch_bytes, (self.h_out if self.d_out is None else self.d_out).data_ptr())
+        args = (self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, None if greedy else fptr + 4 * nm, 1 if greedy else 0, n,
+                self.scratch.data_ptr(), self.scratch_bytes, (self.h_out if self.d_out is None else self.d_out).data_ptr())
+        if table_rows is None:
+            self.L.mi_rollout_step_batch(*args)
+        else:
+            self.L.mi_rollout_step_batch_rec(*args, fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), actions.data_ptr(), values.data_ptr())
         if self.d_out is not None:
             self.h_out[:n * self.row].copy_(self.d_out[:n * self.row], non_blocking=True)
         st.synchronize()
         o = self._out_np[:n]
-        actions, values = o[:, :self.A].copy(), o[:, self.A].copy()
-        states = np.concatenate([o[:, self.A + 1:].astype(np.float64), meas], axis=1)
-        return actions, values, states
+        return o[:, :self.A].copy(), o[:, self.A].copy(), np.concatenate([o[:, self.A + 1:].astype(np.float64), meas], axis=1)
 
 
 MAX_HORIZON = 4096                                                                   # MI_ROLLOUT_MAX_HORIZON of include/mi355_carla.h
@@ -296,7 +310,11 @@ class RolloutRows:
         slot = self.lengths[ids]
         self.rewards[ids, slot], self.dones[ids, slot] = r, d
         self.lengths[ids] = slot + 1
-        self.state[ids] = np.where(d.astype(bool) | (slot + 1 >= self.horizon), self.ENDED, self.OPEN)
+        self.state[ids] = np.where(self._ends(d.astype(bool), slot + 1), self.ENDED, self.OPEN)
+
+    def _ends(self, done, length):
+        """Does a row whose step just counted take no further step?  done was reported, or the horizon is reached."""
+        return done | (length >= self.horizon)
 
     def bootstrap_rows(self, env_ids, n):
         """The table rows (slot lengths[e]) that take the state after the last step and its value; closes the rows."""
@@ -332,10 +350,8 @@ class SegmentedRows(RolloutRows):
     lengths[e] and starts a new segment; a lane is ended only when it is full.  A segment is a maximal run of recorded steps of a lane that ends at a step with
     done != 0 or at the lane's last recorded step; only a lane's last segment can end without a done, and slot lengths[e] behind it is the lane's bootstrap slot."""
 
-    def outcome(self, rewards, dones, env_ids=None):
-        super().outcome(rewards, dones, env_ids)                                     # (checks the whole call first)
-        ids = self.env_ids(env_ids, np.asarray(rewards).shape[0])
-        self.state[ids] = np.where(self.lengths[ids] >= self.horizon, self.ENDED, self.OPEN)
+    def _ends(self, done, length):
+        return length >= self.horizon
 
     def _last_done(self):
         """Per lane: its last counted step reported done (False for an empty lane)."""
@@ -372,58 +388,10 @@ class SegmentedRows(RolloutRows):
 
 
 class _RecordingStep(BatchedRolloutStep):
-    """BatchedRolloutStep whose input buffer also carries the int32 table rows (behind the noise) and whose call is mi_rollout_step_batch_rec."""
+    """The step of a RolloutBuffer: BatchedRolloutStep with room for the int32 table rows in its input buffer, called through check() and record(.., table_rows, tables)."""
 
-    def __init__(self, vae, ppo, num_envs, seed=None, io=None):
-        import torch
-        super().__init__(vae, ppo, num_envs, seed=seed, io=io)
-        nbytes = self._f_off + 4 * self.num_envs * (self.n_meas + self.A + 1)
-        self.h_in = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-        self.d_in = torch.empty(nbytes, dtype=torch.uint8, device=self.device) if self.io == "device" else None
-        self._in_np = self.h_in.numpy()
-        self._f_np = self._in_np[self._f_off:].view(np.float32)
-        self._i_np = self._in_np[self._f_off:].view(np.int32)
-
-    def check(self, frames_u8, measurements, greedy, noise):
-        """The host-side checks of BatchedRolloutStep.__call__ -> (frames, n, measurements float64 [n, k], noise float32 [n, A] or None)."""
-        f = np.asarray(frames_u8)
-        if f.dtype != np.uint8 or f.ndim < 1 or f.size != f.shape[0] * self.frame_bytes:
-            raise ValueError("RolloutBuffer: expected uint8 frames [n, ...] of %d bytes each" % self.frame_bytes)
-        n = int(f.shape[0])
-        if not 1 <= n <= self.num_envs:
-            raise ValueError("RolloutBuffer: 1 <= n <= num_envs = %d, got %d" % (self.num_envs, n))
-        meas = np.asarray(measurements, np.float64)
-        if meas.shape != (n, self.n_meas):
-            raise ValueError("RolloutBuffer: expected measurements [%d, %d]" % (n, self.n_meas))
-        nz = None
-        if not greedy and noise is not None:
-            nz = np.asarray(noise, np.float32)
-            if nz.shape != (n, self.A):
-                raise ValueError("RolloutBuffer: expected noise [%d, %d]" % (n, self.A))
-        return f, n, meas, nz
-
-    def record(self, f, n, meas, nz, greedy, table_rows, states, actions, values):
-        import torch
-        nm, na = n * self.n_meas, n * self.A
-        if not greedy:
-            self._f_np[nm:nm + na] = (self._rng.standard_normal((n, self.A)) if nz is None else nz).reshape(-1)
-        self._in_np[:n * self.frame_bytes] = f.reshape(-1)
-        self._f_np[:nm] = meas.reshape(-1)                                           # f64 -> f32 at the feed, as ppo.py:108-109
-        self._i_np[nm + na:nm + na + n] = table_rows
-        st = torch.cuda.current_stream(self.device)
-        used = self._f_off + 4 * (nm + na + n)
-        if self.d_in is not None:
-            self.d_in[:used].copy_(self.h_in[:used], non_blocking=True)
-        base = (self.h_in if self.d_in is None else self.d_in).data_ptr()
-        fptr = base + self._f_off
-        self.L.mi_rollout_step_batch_rec(self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, None if greedy else fptr + 4 * nm,
-                                         1 if greedy else 0, n, self.scratch.data_ptr(), self.scratch_bytes, (self.h_out if self.d_out is None else self.d_out).data_ptr(),
-                                         fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), actions.data_ptr(), values.data_ptr())
-        if self.d_out is not None:
-            self.h_out[:n * self.row].copy_(self.d_out[:n * self.row], non_blocking=True)
-        st.synchronize()
-        o = self._out_np[:n]
-        return o[:, :self.A].copy(), o[:, self.A].copy(), np.concatenate([o[:, self.A + 1:].astype(np.float64), meas], axis=1)
+    _who = "RolloutBuffer"
+    _row_ints = 1
 
 
 class RolloutBuffer:
@@ -481,14 +449,15 @@ class RolloutBuffer:
             ln = torch.from_numpy(lengths).to(self.device)
             self.L.mi_rollout_finish(st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), ln.data_ptr(), self.num_envs, self.horizon, float(gamma), float(lam),
                                      self.returns.data_ptr(), self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
-        return self._update("RolloutBuffer", finish, num_epochs, batch_size, stage_times)
+        return self._update(finish, num_epochs, batch_size, stage_times)
 
-    def _update(self, who, finish, num_epochs, batch_size, stage_times):
+    def _update(self, finish, num_epochs, batch_size, stage_times):
         """What every buffer's update does around its finish call `finish(stream, rewards, dones, lengths, f64)` (device rewards / dones, fp64 [3, E, T] of NaN for the raw
         advantages, returns and normalised advantages)."""
         import time
         import torch
         from mi355 import dist as midist
+        who = type(self).__name__
         if midist.world_size() > 1:
             raise ValueError(who + ".update: single rank only (ragged rows give ranks different numbers of gradient all-reduces)")
         if int(batch_size) < 1 or int(num_epochs) < 0:
@@ -577,7 +546,7 @@ class ContinuousRolloutBuffer(RolloutBuffer):
             self.L.mi_rollout_finish_segments(st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), n_seg, self.num_envs, T,
                                               float(gamma), float(lam), 1 if batch else 0, milib.ptr(scratch), self.returns.data_ptr(), self.advantages.data_ptr(),
                                               f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
-        out = self._update("ContinuousRolloutBuffer", finish, num_epochs, batch_size, stage_times)
+        out = self._update(finish, num_epochs, batch_size, stage_times)
         out["segments"] = segs
         out["bootstrap_values"] = np.where(self.rows._last_done(), np.float32(np.nan), out["bootstrap_values"]).astype(np.float32)
         return out

@@ -8,91 +8,12 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from oracle import ppo_oracle as po  # noqa: E402
-from oracle import vae_oracle as vo  # noqa: E402
-from ppo import PPO  # noqa: E402
-
-Z, K, A = 64, 3, 2
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def make_pair(tmp_path, seed=2, input_dim=67, **kw):
-    space = po.ActionSpace()
-    hp = dict(learning_rate=1e-4, lr_decay=1.0, epsilon=0.2, value_scale=1.0, entropy_scale=0.01, initial_std=1.0)
-    hp.update(kw)
-    o = po.OraclePPO([input_dim], space, seed=seed, **hp)
-    m = PPO(np.array([input_dim]), space, model_dir=str(tmp_path), seed=seed, **hp)
-    m.set_weights(o.params)
-    m.init_session(init_logging=False)
-    return o, m
-
-
-def vae_params():
-    rng = np.random.RandomState(21)
-    vparams = vo.init_vae_params(3)
-    for k in vparams:
-        if k.endswith("bias"):
-            vparams[k] = (0.05 * rng.standard_normal(vparams[k].shape)).astype(np.float32)
-    return vparams
-
-
-def make_vae(tmp_path, vparams, precision="fp32"):
-    from vae.models import ConvVAE
-    vae = ConvVAE(np.array([80, 160, 3]), z_dim=Z, model_dir=str(tmp_path), precision=precision, training=False)
-    vae.set_weights(vparams)
-    vae.init_session(init_logging=False)
-    return vae
-
-
-def inputs(rng, n):
-    frames = rng.randint(0, 256, (n, 80, 160, 3), dtype=np.uint8)
-    meas = np.stack([rng.uniform(-1, 1, n), rng.uniform(0, 1, n), rng.uniform(0, 30, n)], axis=1)
-    noise = rng.standard_normal((n, A)).astype(np.float32)
-    return frames, meas, noise
-
-
-class Oracle:
-    """encode -> np.append -> predict of every row; the latents of a frame set are computed once."""
-
-    def __init__(self, vparams, o):
-        self.ovae, self.o = vo.OracleVAE(params=vparams, training=False), o
-
-    def latents(self, frames):
-        return np.concatenate([self.ovae.encode(frames[i:i + 16].astype(np.float32) / 255.0) for i in range(0, len(frames), 16)])
-
-    def predict(self, z, meas, noise, greedy):
-        states = np.stack([np.append(z[e], meas[e]) for e in range(len(z))])
-        a, v = self.o.predict(states, greedy=greedy, noise=None if greedy else noise)
-        return np.asarray(a).reshape(len(z), A), np.asarray(v).reshape(len(z)), states
-
-
-def check_against_oracle(got, z_o, a_o, v_o, meas, tag):
-    a, v, states = got
-    n = len(z_o)
-    assert a.shape == (n, A) and a.dtype == np.float32 and v.shape == (n,) and v.dtype == np.float32, tag
-    assert states.shape == (n, Z + K) and states.dtype == np.float64, tag
-    assert np.array_equal(states[:, Z:], np.asarray(meas, np.float64)), tag
-    for e in range(n):
-        err = rel_err(states[e, :Z], z_o[e])
-        assert err < 1e-4, (tag, e, err)
-        assert np.allclose(a[e], a_o[e], rtol=1e-4, atol=1e-5), (tag, e, a[e], a_o[e])
-        assert float(v[e]) == pytest.approx(float(v_o[e]), rel=1e-4, abs=1e-5), (tag, e)
-
-
-def close(x, y, tol=1e-5):
-    return all(np.allclose(p, q, rtol=tol, atol=tol) for p, q in zip(x, y))
+from rollout_gpu_common import A, K, Z, Oracle, check_against_oracle, close, inputs, make_pair, make_vae, make_world  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def world(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("rollout_batch")
-    vparams = vae_params()
-    o, m = make_pair(tmp / "ppo")
-    return dict(tmp=tmp, vparams=vparams, o=o, m=m, vae=make_vae(tmp / "vae_fp32", vparams), orc=Oracle(vparams, o))
+    return make_world(tmp_path_factory, "rollout_batch")
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])

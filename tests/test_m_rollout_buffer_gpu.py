@@ -9,114 +9,15 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import ppo_oracle as po  # noqa: E402
-from oracle import vae_oracle as vo  # noqa: E402
-from ppo import PPO  # noqa: E402
+from rollout_gpu_common import (SENTINEL, Oracle, check_against_oracle, check_losses, check_recorded, close, fill_tables, inputs, make_pair, make_world,  # noqa: E402
+                                rel_err, tables)
 
-Z, K, A = 64, 3, 2
-SENTINEL = -777.0
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def make_pair(tmp_path, seed=2, input_dim=67, precision=None, **kw):
-    space = po.ActionSpace()
-    hp = dict(learning_rate=1e-4, lr_decay=1.0, epsilon=0.2, value_scale=1.0, entropy_scale=0.01, initial_std=1.0)
-    hp.update(kw)
-    o = po.OraclePPO([input_dim], space, seed=seed, **hp)
-    extra = {} if precision is None else dict(precision=precision)
-    m = PPO(np.array([input_dim]), space, model_dir=str(tmp_path), seed=seed, **extra, **hp)
-    m.set_weights(o.params)
-    m.init_session(init_logging=False)
-    return o, m
-
-
-def vae_params():
-    rng = np.random.RandomState(21)
-    vparams = vo.init_vae_params(3)
-    for k in vparams:
-        if k.endswith("bias"):
-            vparams[k] = (0.05 * rng.standard_normal(vparams[k].shape)).astype(np.float32)
-    return vparams
-
-
-def make_vae(tmp_path, vparams, precision="fp32"):
-    from vae.models import ConvVAE
-    vae = ConvVAE(np.array([80, 160, 3]), z_dim=Z, model_dir=str(tmp_path), precision=precision, training=False)
-    vae.set_weights(vparams)
-    vae.init_session(init_logging=False)
-    return vae
-
-
-def inputs(rng, n):
-    frames = rng.randint(0, 256, (n, 80, 160, 3), dtype=np.uint8)
-    meas = np.stack([rng.uniform(-1, 1, n), rng.uniform(0, 1, n), rng.uniform(0, 30, n)], axis=1)
-    noise = rng.standard_normal((n, A)).astype(np.float32)
-    return frames, meas, noise
-
-
-class Oracle:
-    """encode -> np.append -> predict of every row; the latents of a frame set are computed once."""
-
-    def __init__(self, vparams, o):
-        self.ovae, self.o = vo.OracleVAE(params=vparams, training=False), o
-
-    def latents(self, frames):
-        return np.concatenate([self.ovae.encode(frames[i:i + 16].astype(np.float32) / 255.0) for i in range(0, len(frames), 16)])
-
-    def predict(self, z, meas, noise, greedy):
-        states = np.stack([np.append(z[e], meas[e]) for e in range(len(z))])
-        a, v = self.o.predict(states, greedy=greedy, noise=None if greedy else noise)
-        return np.asarray(a).reshape(len(z), A), np.asarray(v).reshape(len(z)), states
-
-
-def check_against_oracle(got, z_o, a_o, v_o, meas, tag):
-    a, v, states = got
-    n = len(z_o)
-    assert a.shape == (n, A) and a.dtype == np.float32 and v.shape == (n,) and v.dtype == np.float32, tag
-    assert states.shape == (n, Z + K) and states.dtype == np.float64, tag
-    assert np.array_equal(states[:, Z:], np.asarray(meas, np.float64)), tag
-    for e in range(n):
-        err = rel_err(states[e, :Z], z_o[e])
-        assert err < 1e-4, (tag, e, err)
-        assert np.allclose(a[e], a_o[e], rtol=1e-4, atol=1e-5), (tag, e, a[e], a_o[e])
-        assert float(v[e]) == pytest.approx(float(v_o[e]), rel=1e-4, abs=1e-5), (tag, e)
-
-
-def close(x, y, tol=1e-5):
-    return all(np.allclose(p, q, rtol=tol, atol=tol) for p, q in zip(x, y))
+K, A = 3, 2
 
 
 @pytest.fixture(scope="module")
 def world(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("rollout_buffer")
-    vparams = vae_params()
-    o, m = make_pair(tmp / "ppo")
-    return dict(tmp=tmp, vparams=vparams, o=o, m=m, vae=make_vae(tmp / "vae_fp32", vparams), orc=Oracle(vparams, o))
-
-
-def fill_tables(buf, value=SENTINEL):
-    for t in (buf.states, buf.actions, buf.values, buf.returns, buf.advantages, buf.logp_old):
-        t.fill_(value)
-
-
-def tables(buf):
-    return buf.states.cpu().numpy(), buf.actions.cpu().numpy(), buf.values.cpu().numpy()
-
-
-def check_recorded(tabs, before, rows, got, meas, tag):
-    """Table rows `rows` hold, bitwise, what the call returned; every other row is what it was before the call."""
-    s, a, v = tabs
-    actions, values, states = got
-    assert np.array_equal(s[rows, :Z], states[:, :Z].astype(np.float32)), tag        # the returned float64 latents are exact widenings of the fp32 the kernel stored
-    assert np.array_equal(s[rows, Z:], np.asarray(meas, np.float32)), tag
-    assert np.array_equal(a[rows], actions) and np.array_equal(v[rows], values), tag
-    other = np.ones(len(v), bool)
-    other[rows] = False
-    for now, was in zip(tabs, before):
-        assert np.array_equal(now[other], was[other]), tag
+    return make_world(tmp_path_factory, "rollout_buffer")
 
 
 def test_recording_is_exact_and_confined(world):
@@ -267,16 +168,6 @@ def collect(buf, rng, done_at, noise_rng=None, frames_per_step=None):
     f, ms, _ = inputs(rng, E)
     buf.bootstrap(f, ms)
     return buf.rows.valid_rows()
-
-
-def check_losses(got, want, tag):
-    """test_e_c5_replay_gpu.py's tolerances; `want` has the oracle's keys or the device's."""
-    assert len(got) == len(want), tag
-    for i, (g, w) in enumerate(zip(got, want)):
-        assert g["loss"] == pytest.approx(w["loss"], rel=1e-4, abs=1e-4), (tag, i, g, w)
-        assert g["value_loss"] == pytest.approx(w["value_loss"], rel=1e-4), (tag, i, g, w)
-        assert g["policy_loss"] == pytest.approx(w["policy_loss"], abs=1e-4), (tag, i, g, w)
-        assert g["prob_ratio"] == pytest.approx(w["ratio_mean"] if "ratio_mean" in w else w["prob_ratio"], rel=1e-4), (tag, i, g, w)
 
 
 def host_samples(buf, valid, gamma, lam):

@@ -9,92 +9,14 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import ppo_oracle as po  # noqa: E402
-from oracle import vae_oracle as vo  # noqa: E402
-from ppo import PPO  # noqa: E402
+from rollout_gpu_common import SENTINEL, Z, check_losses, check_recorded, fill_tables, inputs, make_pair, make_world, rel_err, tables  # noqa: E402
 
-Z, K, A = 64, 3, 2
-SENTINEL = -777.0
 GAMMA, LAM = 0.99, 0.95
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def make_pair(tmp_path, seed=2, input_dim=67, precision=None, **kw):
-    space = po.ActionSpace()
-    hp = dict(learning_rate=1e-4, lr_decay=1.0, epsilon=0.2, value_scale=1.0, entropy_scale=0.01, initial_std=1.0)
-    hp.update(kw)
-    o = po.OraclePPO([input_dim], space, seed=seed, **hp)
-    extra = {} if precision is None else dict(precision=precision)
-    m = PPO(np.array([input_dim]), space, model_dir=str(tmp_path), seed=seed, **extra, **hp)
-    m.set_weights(o.params)
-    m.init_session(init_logging=False)
-    return o, m
-
-
-def vae_params():
-    rng = np.random.RandomState(21)
-    vparams = vo.init_vae_params(3)
-    for k in vparams:
-        if k.endswith("bias"):
-            vparams[k] = (0.05 * rng.standard_normal(vparams[k].shape)).astype(np.float32)
-    return vparams
-
-
-def make_vae(tmp_path, vparams, precision="fp32"):
-    from vae.models import ConvVAE
-    vae = ConvVAE(np.array([80, 160, 3]), z_dim=Z, model_dir=str(tmp_path), precision=precision, training=False)
-    vae.set_weights(vparams)
-    vae.init_session(init_logging=False)
-    return vae
-
-
-def inputs(rng, n):
-    frames = rng.randint(0, 256, (n, 80, 160, 3), dtype=np.uint8)
-    meas = np.stack([rng.uniform(-1, 1, n), rng.uniform(0, 1, n), rng.uniform(0, 30, n)], axis=1)
-    noise = rng.standard_normal((n, A)).astype(np.float32)
-    return frames, meas, noise
 
 
 @pytest.fixture(scope="module")
 def world(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("rollout_segments")
-    vparams = vae_params()
-    return dict(tmp=tmp, vparams=vparams, vae=make_vae(tmp / "vae_fp32", vparams))
-
-
-def fill_tables(buf, value=SENTINEL):
-    for t in (buf.states, buf.actions, buf.values, buf.returns, buf.advantages, buf.logp_old):
-        t.fill_(value)
-
-
-def tables(buf):
-    return buf.states.cpu().numpy(), buf.actions.cpu().numpy(), buf.values.cpu().numpy()
-
-
-def check_recorded(tabs, before, rows, got, meas, tag):
-    """Table rows `rows` hold, bitwise, what the call returned; every other row is what it was before the call."""
-    s, a, v = tabs
-    actions, values, states = got
-    assert np.array_equal(s[rows, :Z], states[:, :Z].astype(np.float32)), tag
-    assert np.array_equal(s[rows, Z:], np.asarray(meas, np.float32)), tag
-    assert np.array_equal(a[rows], actions) and np.array_equal(v[rows], values), tag
-    other = np.ones(len(v), bool)
-    other[rows] = False
-    for now, was in zip(tabs, before):
-        assert np.array_equal(now[other], was[other]), tag
-
-
-def check_losses(got, want, tag):
-    """test_e_c5_replay_gpu.py's tolerances; `want` has the oracle's keys or the device's."""
-    assert len(got) == len(want), tag
-    for i, (g, w) in enumerate(zip(got, want)):
-        assert g["loss"] == pytest.approx(w["loss"], rel=1e-4, abs=1e-4), (tag, i, g, w)
-        assert g["value_loss"] == pytest.approx(w["value_loss"], rel=1e-4), (tag, i, g, w)
-        assert g["policy_loss"] == pytest.approx(w["policy_loss"], abs=1e-4), (tag, i, g, w)
-        assert g["prob_ratio"] == pytest.approx(w["ratio_mean"] if "ratio_mean" in w else w["prob_ratio"], rel=1e-4), (tag, i, g, w)
+    return make_world(tmp_path_factory, "rollout_segments", policy=False)
 
 
 # ---- the kernel ----------------------------------------------------------------------------------------------------------------------------------------------------

@@ -2,14 +2,11 @@
 of rollout.hip (compiled here, no GPU needed): the batched kernels exist, run on the exact-fp32 MFMA, spill nothing and store nothing through the scalar unit; the
 B = 1 kernels mi_rollout_step launches are still there."""
 import inspect
-import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from rollout_host_common import SCALAR_WRITES, _kernel, _listing
 
 
 def test_batch_entry_points_are_declared_exported_and_checked():
@@ -49,37 +46,20 @@ BATCHED = [r"_ZN2mi26rollout_conv1_batch_kernelILi12EE", r"_ZN2mi26rollout_conv1
 BATCHED_HEADS = [r"_ZN2mi25rollout_head_batch_kernelILi2EE", r"_ZN2mi25rollout_head_batch_kernelILi8EE"]
 SINGLE = [r"_ZN2mi20rollout_conv1_kernelILi12EE", r"_ZN2mi20rollout_conv1_kernelILi0EE"] + [r"_ZN2mi19rollout_conv_kernelILi%dEE" % m for m in range(5)]
 SINGLE_HEADS = [r"_ZN2mi19rollout_head_kernelILi2EE", r"_ZN2mi19rollout_head_kernelILi8EE"]
-# stores and atomics of the scalar unit, and its cache write-back / discard (the mnemonics are put together here so that this file does not spell them)
-SCALAR_WRITES = re.compile(r"\bs_(?:buffer_|scratch_)?(?:store|atomic)|\bs_d" + r"cache_(?:wb|discard)")
-
-
 @pytest.fixture(scope="module")
 def rollout_listing():
-    path = os.path.join(tempfile.mkdtemp(), "rollout.s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-S",
-                    "--cuda-device-only", os.path.join(ROOT, "carla-ppo_amd", "csrc", "rollout.hip"), "-o", path], check=True, capture_output=True)
-    return open(path).read()
-
-
-def _kernel(text, prefix):
-    m = re.search(r"^(" + prefix + r"[A-Za-z0-9_]*):", text, re.M)
-    assert m, prefix
-    name = m.group(1)
-    body = text[m.start():text.index("s_endpgm", m.start())]
-    scratch = re.search(r"\.name:\s+" + re.escape(name) + r"\s*\n\s+\.private_segment_fixed_size:\s+(\d+)", text)
-    assert scratch, name
-    return name, body, int(scratch.group(1))
+    return _listing("rollout")
 
 
 def test_batched_kernels_are_exact_fp32_mfma_and_spill_free(rollout_listing):
     for prefix in BATCHED:
-        name, body, scratch = _kernel(rollout_listing, prefix)
+        name, body, scratch, _ = _kernel(rollout_listing, prefix)
         assert "v_mfma_f32_32x32x2_f32" in body, name
         assert "bf16" not in body, name
         assert scratch == 0, name
         assert not SCALAR_WRITES.search(body), name
     for prefix in BATCHED_HEADS:
-        name, body, scratch = _kernel(rollout_listing, prefix)
+        name, body, scratch, _ = _kernel(rollout_listing, prefix)
         assert scratch == 0 and "v_mfma" not in body, name
         assert not SCALAR_WRITES.search(body), name
     assert not SCALAR_WRITES.search(rollout_listing)
@@ -87,9 +67,9 @@ def test_batched_kernels_are_exact_fp32_mfma_and_spill_free(rollout_listing):
 
 def test_single_frame_kernels_are_still_there(rollout_listing):
     for prefix in SINGLE:
-        name, body, scratch = _kernel(rollout_listing, prefix)
+        name, body, scratch, _ = _kernel(rollout_listing, prefix)
         assert "v_mfma_f32_32x32x2_f32" in body and "bf16" not in body, name
         assert scratch == 0, name
     for prefix in SINGLE_HEADS:
-        name, body, scratch = _kernel(rollout_listing, prefix)
+        name, body, scratch, _ = _kernel(rollout_listing, prefix)
         assert scratch == 0, name

@@ -5,13 +5,11 @@ the existing steps launch are still found by their names."""
 import inspect
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from rollout_host_common import ROOT, SCALAR_WRITES, _kernel, _listing
 
 
 def test_entry_points_are_declared_exported_and_checked():
@@ -164,31 +162,11 @@ FINISH = r"_ZN2mi21rollout_finish_kernelE"
 EXISTING = [r"_ZN2mi19rollout_head_kernelILi2EE", r"_ZN2mi19rollout_head_kernelILi8EE", r"_ZN2mi25rollout_head_batch_kernelILi2EE", r"_ZN2mi25rollout_head_batch_kernelILi8EE",
             r"_ZN2mi20rollout_conv1_kernelILi12EE", r"_ZN2mi20rollout_conv1_kernelILi0EE", r"_ZN2mi26rollout_conv1_batch_kernelILi12EE", r"_ZN2mi26rollout_conv1_batch_kernelILi0EE"] + \
            [r"_ZN2mi19rollout_conv_kernelILi%dEE" % m for m in range(5)] + [r"_ZN2mi25rollout_conv_batch_kernelILi%dEE" % m for m in range(5)]
-# stores and atomics of the scalar unit, and its cache write-back / discard (the mnemonics are put together here so that this file does not spell them)
-SCALAR_WRITES = re.compile(r"\bs_(?:buffer_|scratch_)?(?:st" + r"ore|at" + r"omic)|\bs_d" + r"cache_(?:wb|discard)")
-
-
-def _listing(name):
-    path = os.path.join(tempfile.mkdtemp(), name + ".s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-S",
-                    "--cuda-device-only", os.path.join(ROOT, "carla-ppo_amd", "csrc", name + ".hip"), "-o", path], check=True, capture_output=True)
-    return open(path).read()
-
-
-def _kernel(text, prefix):
-    m = re.search(r"^(" + prefix + r"[A-Za-z0-9_]*):", text, re.M)
-    assert m, prefix
-    name = m.group(1)
-    body = text[m.start():text.index("s_endpgm", m.start())]
-    scratch = re.search(r"\.name:\s+" + re.escape(name) + r"\s*\n\s+\.private_segment_fixed_size:\s+(\d+)", text)
-    assert scratch, name
-    return name, body, int(scratch.group(1))
-
 
 def test_recording_heads_and_existing_rollout_kernels_in_the_gfx950_listing():
     text = _listing("rollout")
     for prefix in HEADS_REC:
-        name, body, scratch = _kernel(text, prefix)
+        name, body, scratch, _ = _kernel(text, prefix)
         assert scratch == 0 and "v_mfma" not in body, name
         assert not SCALAR_WRITES.search(body), name
         assert "global_store_dword" in body, name                                  # the table rows leave through the vector unit
@@ -199,7 +177,7 @@ def test_recording_heads_and_existing_rollout_kernels_in_the_gfx950_listing():
 
 def test_finish_kernel_in_the_gfx950_listing():
     text = _listing("ppo_ops")
-    name, body, scratch = _kernel(text, FINISH)
+    name, body, scratch, _ = _kernel(text, FINISH)
     assert scratch == 0, name
     assert not SCALAR_WRITES.search(body), name
     assert "v_add_f64" in body and "v_mul_f64" in body and "v_cvt_f32_f64" in body, name
@@ -208,7 +186,7 @@ def test_finish_kernel_in_the_gfx950_listing():
 
 def test_new_sources_do_not_spell_scalar_unit_writes():
     for rel in ("carla-ppo_amd/csrc/rollout.hip", "carla-ppo_amd/csrc/ppo_ops.hip", "carla-ppo_amd/csrc/vae_engine.hip", "carla-ppo_amd/rollout.py",
-                "tests/test_rollout_buffer_host.py", "tests/test_m_rollout_buffer_gpu.py", "tools/rollout_latency.py", "tools/rollout_buffer_bench.py"):
+                "tests/test_rollout_buffer_host.py", "tests/test_m_rollout_buffer_gpu.py", "tests/rollout_host_common.py", "tests/rollout_gpu_common.py", "tools/rollout_latency.py", "tools/rollout_buffer_bench.py"):
         path = os.path.join(ROOT, rel)
         if os.path.exists(path):
             assert not SCALAR_WRITES.search(open(path).read().lower()), rel

@@ -6,13 +6,11 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from rollout_host_common import ROOT, SCALAR_WRITES, _kernel, _listing
 
 
 def test_entry_point_is_declared_exported_and_checked():
@@ -219,25 +217,6 @@ def test_parent_classes_are_untouched_and_the_new_signatures():
 SEGMENT_KERNELS = [r"_ZN2mi25rollout_finish_seg_kernelILi0EE", r"_ZN2mi25rollout_finish_seg_kernelILi1EE", r"_ZN2mi25rollout_seg_reduce_kernelILi0EE",
                    r"_ZN2mi25rollout_seg_reduce_kernelILi1EE", r"_ZN2mi23rollout_seg_norm_kernelILi0EE", r"_ZN2mi23rollout_seg_norm_kernelILi1EE"]
 FINISH = r"_ZN2mi21rollout_finish_kernelE"
-# stores and atomics of the scalar unit, and its cache write-back / discard (the mnemonics are put together here so that this file does not spell them)
-SCALAR_WRITES = re.compile(r"\bs_(?:buffer_|scratch_)?(?:st" + r"ore|at" + r"omic)|\bs_d" + r"cache_(?:wb|discard)")
-
-
-def _listing(name):
-    path = os.path.join(tempfile.mkdtemp(), name + ".s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-S",
-                    "--cuda-device-only", os.path.join(ROOT, "carla-ppo_amd", "csrc", name + ".hip"), "-o", path], check=True, capture_output=True)
-    return open(path).read()
-
-
-def _kernel(text, prefix):
-    m = re.search(r"^(" + prefix + r"[A-Za-z0-9_]*):", text, re.M)
-    assert m, prefix
-    name = m.group(1)
-    body = text[m.start():text.index("s_endpgm", m.start())]
-    meta = re.search(r"\.group_segment_fixed_size:\s+(\d+)\s*\n(?:(?!\s*\.name:).*\n)*?\s+\.name:\s+" + re.escape(name) + r"\s*\n\s+\.private_segment_fixed_size:\s+(\d+)", text)
-    assert meta, name
-    return name, body, int(meta.group(2)), int(meta.group(1))
 
 
 def test_segment_kernels_in_the_gfx950_listing():
@@ -261,7 +240,7 @@ def test_segment_kernels_in_the_gfx950_listing():
 
 def test_new_sources_do_not_spell_scalar_unit_writes():
     for rel in ("carla-ppo_amd/csrc/ppo_ops.hip", "carla-ppo_amd/rollout.py", "include/mi355_carla.h", "tests/test_rollout_segments_host.py",
-                "tests/test_n_rollout_segments_gpu.py", "tools/rollout_buffer_bench.py", "tools/rollout_finish_bench.py"):
+                "tests/test_n_rollout_segments_gpu.py", "tests/rollout_host_common.py", "tests/rollout_gpu_common.py", "tools/rollout_buffer_bench.py", "tools/rollout_finish_bench.py"):
         path = os.path.join(ROOT, rel)
         assert os.path.exists(path), rel
         assert not SCALAR_WRITES.search(open(path).read().lower()), rel
