@@ -8,18 +8,6 @@
 
 using namespace mi;
 
-static bool ares_on() {                                     // MI355_ARES=0: the general tile kernels (A/B runs)
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("MI355_ARES"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on != 0;
-}
-
-static int ares_cfg() {                                    // MI355_ARES_CFG (A/B runs): bit 0 conv form with 2 frames per block (two blocks per CU), bit 1 gather form with 8 (one block per CU)
-    static int c = -1;
-    if (c < 0) { const char* e = getenv("MI355_ARES_CFG"); c = e ? atoi(e) : 0; }
-    return c;
-}
-
 extern "C" {
 
 // bytes of one fragment-ordered weight copy (either form: 16 x 128 x 256 bf16)
@@ -80,18 +68,18 @@ int mi_ares_pack_weights8(void* stream, const float* conv4_w, const float* decon
 int mi_ares_conv(void* stream, int dtype, int form, const void* x, int B, const void* wf, const float* bias, int relu, const void* mask, void* out, int* launched) {
     if (!launched) return mi_fail(MI_ERR_ARG, "mi_ares_conv: missing arguments");
     *launched = 0;
-    if (!ares_on() || dtype != MI_BF16 || form < 0 || form > 2 || !x || !wf || !out || B < 1) return MI_OK;
+    if (!knob(K_ARES) || dtype != MI_BF16 || form < 0 || form > 2 || !x || !wf || !out || B < 1) return MI_OK;
     if ((((uintptr_t)x) | ((uintptr_t)wf) | ((uintptr_t)out) | ((uintptr_t)mask) | ((uintptr_t)bias)) & 15) return MI_OK;
     const long long xb = (long long)B * (form == 1 ? 3 * 8 * 256 : 8 * 18 * 128) * 2;      // the descriptor's range check supplies the zeros of a ragged last frame group
     if (xb >= (long long)G2_OOB) return MI_OK;
     AresParams p = {};
     p.x = x; p.x_bytes = (uint32_t)xb; p.wf = wf; p.B = B;
     p.out = out; p.bias = bias; p.mask = mask; p.relu = relu; p.out_f32 = 0;
-    { static int dbg = -1; if (dbg < 0) { const char* e = getenv("MI355_ARES_DBG"); dbg = e ? atoi(e) : 0; } p.dbg = dbg; }
+    p.dbg = knob(K_ARES_DBG);
     hipStream_t st = (hipStream_t)stream;
     if (form == 0) {
         p.M = B * 24; p.N = AC_N; p.OH = AC_OH; p.OW = AC_OW;
-        const int F = ares_cfg() & 1 ? 2 : 4;               // frames per block (MI355_ARES_CFG bit 0: the two-blocks-per-CU form, measured slower)
+        const int F = knob(K_ARES_CFG) & 1 ? 2 : 4;               // frames per block (MI355_ARES_CFG bit 0: the two-blocks-per-CU form, measured slower)
         const int groups = (B + F - 1) / F;
         const int nb = (groups + 7) / 8 * 16;                // block b: frame group (b & 7) + 8 (b >> 4), column half (b >> 3) & 1
         if (F == 4) MI_LAUNCH((ares_conv_kernel<4, 1>), dim3(nb), dim3(256), 0, st, p);
@@ -99,9 +87,7 @@ int mi_ares_conv(void* stream, int dtype, int form, const void* x, int B, const 
         const int rc = mi_check_launch("ares_conv_kernel");
         if (rc != MI_OK) return rc;
     } else if (form == 2) {
-        static int mid_on = -1;                             // MI355_ARES_MID=0: the mid layers stay on the register-weight kernels (A/B runs)
-        if (mid_on < 0) { const char* e = getenv("MI355_ARES_MID"); mid_on = (e && e[0] == '0') ? 0 : 1; }
-        if (!mid_on) return MI_OK;
+        if (!knob(K_ARES_MID)) return MI_OK;                // MI355_ARES_MID=0: the mid layers stay on the register-weight kernels (A/B runs)
         p.M = B * G2_RPF; p.N = G2_N; p.OH = G2_OH; p.OW = G2_OW;
         for (int c = 0; c < 4; ++c) { p.dc_ohw[c] = make_fastdiv(G2_RPF); p.dc_ow[c] = make_fastdiv(19); }
         MI_LAUNCH(ares_gather2_kernel, dim3(B), dim3(256), 0, st, p);
@@ -110,7 +96,7 @@ int mi_ares_conv(void* stream, int dtype, int form, const void* x, int B, const 
     } else {
         p.M = B * AG_RPF; p.N = AG_N; p.OH = AG_OH; p.OW = AG_OW;
         for (int c = 0; c < 4; ++c) { p.dc_ohw[c] = make_fastdiv(AG_RPF); p.dc_ow[c] = make_fastdiv(9); }
-        const int F = ares_cfg() & 2 ? 8 : 4;               // (bit 1: the one-block-per-CU form of the gather kernel)
+        const int F = knob(K_ARES_CFG) & 2 ? 8 : 4;               // (bit 1: the one-block-per-CU form of the gather kernel)
         const int groups = (B + F - 1) / F;
         const int nb = (groups + 7) / 8 * 32;                // block b: parity class (b >> 3) & 3, frame group (b & 7) + 8 (b >> 5)
         if (F == 8) MI_LAUNCH((ares_gather_kernel<8, 1>), dim3(nb), dim3(256), 0, st, p);

@@ -50,25 +50,11 @@ void fill_conv_geom(GemmParams& p, int B, int IH, int IW, int C, int OH, int OW,
 // register-staged kernel (A/B comparisons, bisecting).
 // ---------------------------------------------------------------------------------------------------------------
 long long* g_trace = nullptr; int g_trace_cap = 0;
-int g_wgrad_skip = 0;
-int g_tap_mask_prefetch = 1;                                // tapconv: touch the ReluGrad-mask lines in the last main-loop step; mi_set_tuning key 12
-int g_gemm2_on = -1;
-static int gemm2_stages_env() { const char* e = getenv("MI355_GEMM2_STAGES"); return e ? atoi(e) : 2; }
-int g_gemm2_stages = gemm2_stages_env();                    // gemm2 128 x 64 tiles: LDS stages of the K pipeline (2 | 3 | 4); mi_set_tuning key 20
-static int gemm2_tile_env() { const char* e = getenv("MI355_GEMM2_TILE"); return e ? atoi(e) : 2; }
-static int gemm2_splitk_env() { const char* e = getenv("MI355_GEMM2_SPLITK"); return (e && e[0] == '0') ? 0 : 1; }
-int g_gemm2_splitk = gemm2_splitk_env();                                   // split-K dense layers (raw fp32 slabs) on the LDS-DMA tiles instead of the first-generation kernel (round 4: the 38400-long reductions of the MlpVAE)
-int g_gemm2_tile = gemm2_tile_env();                                       // wide-output gemm2 layers: 0 auto (64 x 64 tiles on small grids), 1 always 64 x 64, 2 never, 3 always 128 x 128 (64 x 64 wave tiles: 1 KB of LDS reads per MFMA instead of 1.5); mi_set_tuning key 17
-int g_tap_min = -2;
-bool gemm2_enabled() {
-    if (g_gemm2_on < 0) { const char* e = getenv("MI355_GEMM2"); g_gemm2_on = (e && e[0] == '0') ? 0 : 1; }
-    return g_gemm2_on != 0;
-}
 
 template <typename T, int AMODE, int BMODE, bool UTAP>
 void launch_gemm2_128x64(hipStream_t st, dim3 g, const Gemm2Params& p) {
     const int nk = (p.K * (int)sizeof(T) + 127) / 128;    // (upper bound for the gather form: its K depends on the parity class)
-    const int ns = nk >= 6 ? g_gemm2_stages : 2;           // a deeper ring needs steps to fill
+    const int ns = nk >= 6 ? knob(K_GEMM2_STAGES) : 2;           // a deeper ring needs steps to fill
     if (ns >= 4) MI_LAUNCH((gemm2_kernel<T, AMODE, BMODE, 128, 64, UTAP, 4>), g, dim3(GEMM_NT), 0, st, p);
     else if (ns == 3) MI_LAUNCH((gemm2_kernel<T, AMODE, BMODE, 128, 64, UTAP, 3>), g, dim3(GEMM_NT), 0, st, p);
     else MI_LAUNCH((gemm2_kernel<T, AMODE, BMODE, 128, 64, UTAP, 2>), g, dim3(GEMM_NT), 0, st, p);
@@ -84,7 +70,7 @@ int launch_gemm2_tiles(hipStream_t st, const Gemm2Params& p, int M_for_grid, int
         dim3 g((M_for_grid + 127) / 128, 1, gz);
         launch_gemm2_128x64<T, AMODE, BMODE, UTAP>(st, g, p);
     } else {
-        if (g_gemm2_tile == 1 || (g_gemm2_tile == 0 && (long long)((M_for_grid + 127) / 128) * ((p.N + 63) / 64) * gz < 512)) {
+        if (knob(K_GEMM2_TILE) == 1 || (knob(K_GEMM2_TILE) == 0 && (long long)((M_for_grid + 127) / 128) * ((p.N + 63) / 64) * gz < 512)) {
             // small grids (conv4 forward / deconv1 input gradient at batch 512: 96 x 4 tiles of 128 x 64 = 1.5 blocks per CU, each a serial chain of
             // 32 latency-bound k-steps): 64 x 64 tiles double the blocks in flight (32 KB of LDS each: four resident per CU cover each other's waits)
             dim3 g((M_for_grid + 63) / 64, (p.N + 63) / 64, gz);
@@ -92,10 +78,10 @@ int launch_gemm2_tiles(hipStream_t st, const Gemm2Params& p, int M_for_grid, int
             return mi_check_launch("gemm2_kernel");
         }
         const int gx = (M_for_grid + 127) / 128;
-        if (g_gemm2_tile == 3 || (long long)gx * ((p.N + 127) / 128) * gz >= 384) {
+        if (knob(K_GEMM2_TILE) == 3 || (long long)gx * ((p.N + 127) / 128) * gz >= 384) {
             dim3 g(gx, (p.N + 127) / 128, gz);
             const int nk = (p.K * (int)sizeof(T) + 127) / 128;
-            if (g_gemm2_tile == 3 && g_gemm2_stages >= 3 && nk >= 6) MI_LAUNCH((gemm2_kernel<T, AMODE, BMODE, 128, 128, UTAP, 3>), g, dim3(GEMM_NT), 0, st, p);
+            if (knob(K_GEMM2_TILE) == 3 && knob(K_GEMM2_STAGES) >= 3 && nk >= 6) MI_LAUNCH((gemm2_kernel<T, AMODE, BMODE, 128, 128, UTAP, 3>), g, dim3(GEMM_NT), 0, st, p);
             else MI_LAUNCH((gemm2_kernel<T, AMODE, BMODE, 128, 128, UTAP>), g, dim3(GEMM_NT), 0, st, p);
         } else {                                          // few tiles: narrower blocks fill the 256 CUs
             dim3 g(gx, (p.N + 63) / 64, gz);
@@ -115,18 +101,6 @@ void copy_epilogue(Gemm2Params& q, const GemmParams& p) {
 // tapconv (raw-staged slot tiles, tapconv_tile.hpp): stride-2 k=4/5 layers with whole 16-byte chunks per pixel and enough
 // positions to fill the chip.  MI355_TAPCONV=0 disables it; MI355_TAPCONV_MINBLOCKS overrides the occupancy threshold.
 // ---------------------------------------------------------------------------------------------------------------
-int tapconv_minblocks() {
-    if (g_tap_min == -2) {
-        const char* e = getenv("MI355_TAPCONV");
-        if (e && e[0] == '0') g_tap_min = -1;
-        else { const char* m = getenv("MI355_TAPCONV_MINBLOCKS"); g_tap_min = m ? atoi(m) : 300; }
-    }
-    return g_tap_min;
-}
-
-int g_tap_direct = 1;                                      // tapconv epilogue: 1 registers -> 16-byte stores, 0 LDS-staged; mi_set_tuning key 6
-int g_tap_variant = 0;                                    // 0 auto, 1 big tile (256 x 96), 2 small tile (128 x 48); mi_set_tuning key 5
-
 template <typename T, int MODE, int TAPS, int BMT, int MAXHALO>
 int launch_tapconv_v(hipStream_t st, const TapParams& q) {
     const int gx = (q.MP + BMT - 1) / BMT;
@@ -152,7 +126,7 @@ int launch_tapconv(hipStream_t st, const TapParams& q, bool small_tile) {
 // weights [KH][KW][N][C].  Returns 1 launched, 0 not eligible, <0 error.
 int try_tapconv(hipStream_t st, int dtype, int mode, const void* a, const void* w, int B, int IH, int IW, int C, int OH, int OW, int N,
                 int KH, int KW, int ldb, void* out, const float* bias, const void* mask, int relu) {
-    const int minblocks = tapconv_minblocks();
+    const int minblocks = knob(K_TAPCONV_MINBLOCKS);
     if (minblocks < 0) return 0;
     const int esz = esz_of(dtype);
     if (KH != KW || KH < 3 || KH > 6) return 0;
@@ -185,14 +159,14 @@ int try_tapconv(hipStream_t st, int dtype, int mode, const void* a, const void* 
     q.div_g = make_fastdiv(q.GH); q.div_gw = make_fastdiv(q.GW); q.div_n = make_fastdiv(N);
     q.div_2c = make_fastdiv(2 * C); q.div_c = make_fastdiv(C);
     q.out = out; q.bias = bias; q.mask = mask; q.relu = relu;
-    q.direct_epilogue = (g_tap_direct && N % 32 == 0) ? 1 : 0;       // a 32-output tile is all valid or all out of range
-    q.trace = g_trace; q.trace_cap = g_trace_cap; q.dbg = g_wgrad_skip; q.mask_prefetch = g_tap_mask_prefetch;
+    q.direct_epilogue = (knob(K_TAP_DIRECT) && N % 32 == 0) ? 1 : 0;       // a 32-output tile is all valid or all out of range
+    q.trace = g_trace; q.trace_cap = g_trace_cap; q.dbg = knob(K_WGRAD_DBG); q.mask_prefetch = knob(K_TAP_MASK_PREFETCH);
     const int halo = (q.TH - 1) * q.GW + q.TW - 1;
     // measured (tools/trace_tapconv.py variants): the 128-position tile wins 5-12 % where the 256-position grid is only 1.3-3 rounds
     // of blocks (tile quantisation), loses a little on the 4-column grids and ties on the big grids
     const int gy_t = (q.NE + (q.NE >= 128 ? 127 : 63)) / (q.NE >= 128 ? 128 : 64);
     const bool auto_small = blocks >= 300 && blocks <= 1000 && gy_t <= 2;
-    const bool small_tile = halo <= 48 && dtype == MI_BF16 && (g_tap_variant == 2 || (g_tap_variant == 0 && auto_small));
+    const bool small_tile = halo <= 48 && dtype == MI_BF16 && (knob(K_TAP_VARIANT) == 2 || (knob(K_TAP_VARIANT) == 0 && auto_small));
     int rc;
     if (dtype == MI_F32) rc = mode == TC_CONV ? launch_tapconv<float, TC_CONV>(st, q, false) : launch_tapconv<float, TC_GATHER>(st, q, false);
     else if (dtype == MI_BF16X3) rc = mode == TC_CONV ? launch_tapconv<split_t, TC_CONV>(st, q, false) : launch_tapconv<split_t, TC_GATHER>(st, q, false);
@@ -249,10 +223,9 @@ static int launch_fold(hipStream_t st, const PendingFold& f) {
 }
 static thread_local PendingReduce g_pending[16];
 static thread_local int g_npending = 0, g_defer_reduces = 0, g_defer_pause = 0;
-static unsigned reduce_ry_cap() { static int c = -1; if (c < 0) { const char* e = getenv("MI355_REDUCE_RY_CAP"); c = e ? atoi(e) : 16; if (c < 1 || c > 64) c = 16; } return (unsigned)c; }      // (16: 0.7900 / 0.7923 against 0.7929 / 0.7949 ms per step at 64, two interleaved A/B runs of four rounds)
 static unsigned reduce_ry(const PendingReduce& r) {       // slab chains per element (a power of two <= 64, from the shape only): about 512 blocks in flight, at most ~16 slabs per thread
     unsigned ry = 1;                                        // (MI355_REDUCE_RY_CAP: A/B knob -- fewer chains = longer contiguous pieces per slab and block, fewer blocks)
-    while (((unsigned)(r.ngroups / 512 + 1) * ry < 512 || r.splits / (int)ry > 16) && (int)(ry * 2) <= r.splits / 4 && ry < reduce_ry_cap()) ry *= 2;
+    while (((unsigned)(r.ngroups / 512 + 1) * ry < 512 || r.splits / (int)ry > 16) && (int)(ry * 2) <= r.splits / 4 && ry < (unsigned)knob(K_REDUCE_RY_CAP)) ry *= 2;
     return ry;
 }
 static unsigned reduce_blocks(const PendingReduce& r, unsigned ry) { const unsigned upb = 256 / ry, nunits = (unsigned)r.ngroups / 2; return (nunits + upb - 1) / upb; }      // units = pairs of 16-byte groups
@@ -273,10 +246,8 @@ extern "C" int mi_tapwgrad_defer(int on) {               // switching the mode d
 // pause != 0: the next filter gradients reduce their slabs right behind their own launch although the pass defers (a layer issued on ANOTHER stream than the
 // one the deferred list will be flushed on); returns the previous setting
 extern "C" int mi_tapwgrad_defer_pause(int pause) { const int prev = g_defer_pause; g_defer_pause = pause ? 1 : 0; return prev; }
-int g_slab_bf16 = 0;                                       // tapwgrad partial-sum slabs rounded to bf16 (half the slab traffic): off for the layer-op entry points (exact fp32
-                                                           // partial sums), switched on by the VAE engine around its backward pass (mi_tapwgrad_slab_bf16); mi_set_tuning key 18
-static thread_local int t_slab_bf16 = -1;                  // this thread's override for the pass it is issuing (-1: the process default above)
-static inline int slab_bf16_now() { return t_slab_bf16 >= 0 ? t_slab_bf16 : g_slab_bf16; }
+static thread_local int t_slab_bf16 = -1;                  // this thread's override for the pass it is issuing (-1: the process default, K_SLAB_BF16_DEFAULT)
+static inline int slab_bf16_now() { return t_slab_bf16 >= 0 ? t_slab_bf16 : knob(K_SLAB_BF16_DEFAULT); }
 extern "C" int mi_tapwgrad_slab_bf16(int on) { const int prev = t_slab_bf16; t_slab_bf16 = on < 0 ? -1 : (on ? 1 : 0); return prev; }
 static int tapwgrad_flush_reduces(void* stream);
 extern "C" int mi_tapwgrad_flush(void* stream) {
@@ -311,33 +282,10 @@ static int tapwgrad_flush_reduces(void* stream) {
 // tapwgrad (tapwgrad_tile.hpp): bf16 weight gradients of the wide stride-2 layers on raw-staged slot tiles.
 // mi_set_tuning key 3 / MI355_TAPWGRAD=0 disables it.
 // ---------------------------------------------------------------------------------------------------------------
-static int x3_tapwgrad_env() { const char* e = getenv("MI355_X3_TAPWGRAD"); return e ? atoi(e) : 1; }
-int g_x3_tapwgrad = x3_tapwgrad_env();                   // split-storage filter gradients on the doubled-channel bf16 kernel: 0 off, 1 conv2 / conv3 (default since round 5: 2.637 -> 2.595 ms per bf16x3 step, two interleaved pairs on one box, gpurun_out/ab_x3_r05e.txt; round 4 measured no difference), 2 every eligible layer (2.870: the wide layers lose); mi_set_tuning key 21
-int g_tapwgrad_on = -1;
-int g_tapwgrad_split = 1;
-static int dwgs_env() { const char* e = getenv("MI355_DWGS"); return (e && e[0] == '0') ? 0 : 1; }
-int g_dwgs_on = dwgs_env();                              // LDS-free one-wave-per-tile dense filter gradient (dwgs_tile.hpp, round 5) for bf16 layers of up to 2048 tiles of 64 x 64; mi_set_tuning key 22
-static int dense_wgrad_blocks_env() { const char* e = getenv("MI355_DENSE_WGRAD_BLOCKS"); return e ? atoi(e) : 256; }
-int g_dense_wgrad_blocks = dense_wgrad_blocks_env();       // dense filter gradients: target block count (row splits); mi_set_tuning key 11
-static int nw_depth_env() { const char* e = getenv("MI355_NW_DEPTH"); return e ? atoi(e) : 3; }
-int g_nw_depth = nw_depth_env();                          // narrow_wgrad (uint8 conv1 shape): steps in flight per wave (3 | 5 | 6); mi_set_tuning key 19
-int g_nw_waves = 12;                                       // narrow_wgrad: waves per block (4 | 8 | 12); mi_set_tuning key 10
-int g_tapwgrad_cw = 1;                                     // k = 5 filter gradient: class-wave layout (tapwgrad_cw_kernel); mi_set_tuning key 14
-static int dectail_split5_env() { const char* e = getenv("MI355_DECTAIL_SPLIT5"); return (e && e[0] == '1') ? 1 : 0; }      // measured neutral (74.4-77.4 vs 76.2-77.6 us alone, 0.8440 = 0.8440 ms per step): off
-int g_dectail_split5 = dectail_split5_env();               // decoder tail: the fifth slot group's loss shared by three waves (dectail_tile.hpp, round 6); mi_set_tuning key 26
-int g_dectail_dbg = 0;                                     // ablation mask of the decoder tail's timing instantiation (wrong results); mi_set_tuning key 25
-static int tw_ldec_env() { const char* e = getenv("MI355_TW_LDEC"); const int v = e ? atoi(e) : 0; return v < 0 || v > 3 ? 0 : v; }      // bit 0: the 2 x 2-tap kernels, bit 1: the k = 5 class-wave kernel.  Default 0: once the product kernels lost their run-time debug branch (below) the two forms are equal (0.7929 / 0.7932 / 0.7942 ms for 0 / 1 / 3)
-int g_tw_ldec = tw_ldec_env();                             // raw-staged filter gradients: a step's DMA rows decoded once per wave, one row per lane (tapwgrad_tile.hpp, round 6); mi_set_tuning key 24
-int g_tapwgrad_blocks = 256;                               // tapwgrad: target number of blocks (position splits x block columns); mi_set_tuning key 9
-bool tapwgrad_enabled() {
-    if (g_tapwgrad_on < 0) { const char* e = getenv("MI355_TAPWGRAD"); g_tapwgrad_on = (e && e[0] == '0') ? 0 : 1; }
-    return g_tapwgrad_on != 0;
-}
-
 // a: slot-side tensor [B,IH,IW,C]; d: gradient tensor [B,OH,OW,N]; out: dW (conv form HWIO [kh,kw,C,N]; gather form [kh,kw,N,C])
 int try_tapwgrad(hipStream_t st, int dtype, int mode, const void* a, const void* d, int B, int IH, int IW, int C, int OH, int OW, int N,
                  int KH, int KW, float* out, void* scratch, long long scratch_bytes, float* dbias) {
-    if (!tapwgrad_enabled() || dtype != MI_BF16) return 0;
+    if (!knob(K_TAPWGRAD) || dtype != MI_BF16) return 0;
     if (KH != KW || KH < 3 || KH > 6) return 0;
     if ((((uintptr_t)a) & 15) || (((uintptr_t)d) & 15) || C % 8 != 0 || N % 8 != 0) return 0;
     TapWgradParams q = {};
@@ -387,20 +335,20 @@ int try_tapwgrad(hipStream_t st, int dtype, int mode, const void* a, const void*
         for (int i = 0; i < q.npairs; ++i) { q.pair_tap[i] = t2[i]; q.pair_nt[i] = n2[i]; q.pair_first[i] = f2[i]; }
     }
     q.dbias = dbias;
-    int splits = g_tapwgrad_blocks / gy; if (splits < 1) splits = 1;
+    int splits = knob(K_TAPWGRAD_BLOCKS) / gy; if (splits < 1) splits = 1;
     long long pps = (MP + splits - 1) / splits; pps = (pps + TW_BP - 1) / TW_BP * TW_BP;
     splits = (int)((MP + pps - 1) / pps);
     q.pos_per_split = (int)pps;
     q.div_g = make_fastdiv(q.GH); q.div_gw = make_fastdiv(q.GW); q.div_n = make_fastdiv(N);
     q.div_2c = make_fastdiv(2 * C); q.div_c = make_fastdiv(C);
     q.out = out;
-    q.trace = g_trace; q.trace_cap = g_trace_cap; q.dbg_cheap_addr = (g_wgrad_skip >= 2 && g_wgrad_skip <= 5) ? g_wgrad_skip : 0;
+    q.trace = g_trace; q.trace_cap = g_trace_cap; q.dbg_cheap_addr = (knob(K_WGRAD_DBG) >= 2 && knob(K_WGRAD_DBG) <= 5) ? knob(K_WGRAD_DBG) : 0;
     // partial sums per split in the caller's scratch (accumulator-order 16-byte stores + one reduce that does the dW index decode)
     // when it is large enough; otherwise fp32 atomics straight into dW (~1 element per clock per CU: 35-45 % of the kernel at 256 splits)
     const int kt_tiles = taps == 2 ? 4 : 2;
     const long long slab_floats = (long long)gy * q.npairs * kt_tiles * 1024;
     q.slabs = nullptr; q.slab_stride = slab_floats; q.slab_bf16 = slab_bf16_now() ? 1 : 0;
-    const bool split = g_tapwgrad_split && taps == 2 && q.npairs == 8;   // wave = (tap, position half): fewer LDS reads per MFMA
+    const bool split = knob(K_TAPWGRAD_SPLIT) && taps == 2 && q.npairs == 8;   // wave = (tap, position half): fewer LDS reads per MFMA
     // behind the slabs: the bias-gradient partial sums of every position split (x 2 position halves in the split layout), summed in a fixed order with the slabs
     const long long slab_bytes = ((long long)splits * slab_floats * (q.slab_bf16 ? 2 : 4) + 255) / 256 * 256;
     q.bias_part = nullptr; q.bias_nh = split ? 2 : 1;
@@ -411,7 +359,7 @@ int try_tapwgrad(hipStream_t st, int dtype, int mode, const void* a, const void*
     }
     q.gx = splits; q.gy = gy;
     dim3 g((unsigned)((splits + 7) / 8 * 8 * gy), 1, 1);   // 1-D: the column blocks of a position split share an XCD (tapwgrad_tile.hpp)
-    const bool ldec = (g_tw_ldec & 1) && !q.dbg_cheap_addr && !q.trace, ldec_cw = (g_tw_ldec & 2) && !q.dbg_cheap_addr && !q.trace;
+    const bool ldec = (knob(K_TW_LDEC) & 1) && !q.dbg_cheap_addr && !q.trace, ldec_cw = (knob(K_TW_LDEC) & 2) && !q.dbg_cheap_addr && !q.trace;
     const bool dbg = q.dbg_cheap_addr != 0;                // timing instantiations (tools/wgrad_ablate.py): their own kernels, the split layouts and the k = 5 kernel only
     if (mode == TC_CONV) {
         if (split && dbg) MI_LAUNCH((tapwgrad_kernel<TC_CONV, 2, 4, 2, 2, true, false, true>), g, dim3(TW_NT), 0, st, q);
@@ -427,7 +375,7 @@ int try_tapwgrad(hipStream_t st, int dtype, int mode, const void* a, const void*
     else {
         if (q.npairs > 32) return 0;
         // k = 5 with caller scratch: a wave per (parity class, tap row), the shifted slot fragments formed in registers (mi_set_tuning key 14 = 0: the pair layout)
-        if (g_tapwgrad_cw && KH == 5 && C == 64 && q.NE == 128 && q.KC == 64 && q.slabs) {
+        if (knob(K_TAPWGRAD_CW) && KH == 5 && C == 64 && q.NE == 128 && q.KC == 64 && q.slabs) {
             if (dbg) MI_LAUNCH((tapwgrad_cw_kernel<false, true>), g, dim3(TWC_NT), 0, st, q);
             else if (ldec_cw) MI_LAUNCH(tapwgrad_cw_kernel<true>, g, dim3(TWC_NT), 0, st, q); else MI_LAUNCH(tapwgrad_cw_kernel<false>, g, dim3(TWC_NT), 0, st, q);
         }
@@ -447,7 +395,7 @@ int try_tapwgrad(hipStream_t st, int dtype, int mode, const void* a, const void*
 // MI_BF16X3 filter gradients on the bf16 kernel (see PendingFold): scratch = [dW' (4 x the filter, fp32) | bias' (2 N) | slabs ...]
 int try_tapwgrad_split(hipStream_t st, int mode, const void* a, const void* d, int B, int IH, int IW, int C, int OH, int OW, int N,
                        int KH, int KW, float* out, void* scratch, long long scratch_bytes, float* dbias) {
-    const int on = g_x3_tapwgrad;
+    const int on = knob(K_X3_TAPWGRAD);
     if (!on || !scratch || (((uintptr_t)scratch) & 255)) return 0;
     const long long nw = (long long)KH * KW * C * N;
     const long long tmp_bytes = ((4 * nw + 2 * N) * 4 + 255) / 256 * 256;
@@ -456,8 +404,7 @@ int try_tapwgrad_split(hipStream_t st, int mode, const void* a, const void* d, i
     const int taps = (KH + 1) / 2;
     if (KH != KW || taps != 2) return 0;                    // (the k = 5 gather kernels are built for 32 output channels per parity class: 2 N = 64 does not fit)
     if (mode == TC_CONV ? ((8 * C) % 128 != 0 || (2 * N) % 64 != 0) : ((2 * C) % 128 != 0 || (2 * N) % 64 != 0)) return 0;
-    // measured per layer at batch 512 (us, doubled-channel bf16 kernel vs the first-generation split kernel): conv2 125 / 164, conv3 122 / 136, deconv2 150 / 150, conv4 187 / 86,
-    // deconv1 227 / 91 -- the wide layers end up with 64 column blocks and four position splits.  MI355_X3_TAPWGRAD=2 takes every eligible layer (A/B).
+    // 1: the layers the doubled-channel kernel wins (per-layer times: K_X3_TAPWGRAD, tuning.hip); MI355_X3_TAPWGRAD=2 takes every eligible layer (A/B)
     if (on != 2 && (mode != TC_CONV || (long long)C * N > 64 * 128)) return 0;
     float* tmp = (float*)scratch; float* tb = tmp + 4 * nw;
     if (hipMemsetAsync(tmp, 0, (size_t)((4 * nw + 2 * N) * 4), st) != hipSuccess) return mi_fail(MI_ERR_LAUNCH, "try_tapwgrad_split: memset failed");
@@ -469,27 +416,15 @@ int try_tapwgrad_split(hipStream_t st, int mode, const void* a, const void* d, i
     return rc == MI_OK ? 1 : rc;
 }
 
-static bool narrow_lean_enabled() {                       // MI355_NARROW_LEAN=0: the first-generation narrow-layer kernels (A/B runs)
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("MI355_NARROW_LEAN"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on != 0;
-}
-
 // gather-form transposed conv into a narrow output (narrow_tile.hpp): 4N <= 32 output columns, 64- or 128-byte input pixels
 template <typename T, int TAPS, int CPR>
 int launch_gather_narrow(hipStream_t st, const TapParams& q) {
     dim3 g((q.MP + GN_BMT - 1) / GN_BMT);
-    if (q.N == 3 && sizeof(T) == 2 && q.labels && q.loss_kind == 0 && narrow_lean_enabled()) MI_LAUNCH((gather_narrow_kernel<T, TAPS, CPR, 3, true>), g, dim3(GN_NT), 0, st, q);
+    if (q.N == 3 && sizeof(T) == 2 && q.labels && q.loss_kind == 0 && knob(K_NARROW_LEAN)) MI_LAUNCH((gather_narrow_kernel<T, TAPS, CPR, 3, true>), g, dim3(GN_NT), 0, st, q);
     else if (q.N == 3) MI_LAUNCH((gather_narrow_kernel<T, TAPS, CPR, 3>), g, dim3(GN_NT), 0, st, q);
     else if (q.N == 1) MI_LAUNCH((gather_narrow_kernel<T, TAPS, CPR, 1>), g, dim3(GN_NT), 0, st, q);
     else MI_LAUNCH((gather_narrow_kernel<T, TAPS, CPR, 0>), g, dim3(GN_NT), 0, st, q);
     return mi_check_launch("gather_narrow_kernel");
-}
-
-int g_narrow_on = -1;
-bool narrow_enabled() {
-    if (g_narrow_on < 0) { const char* e = getenv("MI355_NARROW"); g_narrow_on = (e && e[0] == '0') ? 0 : 1; }
-    return g_narrow_on != 0;
 }
 
 struct NarrowLoss {                                       // optional fused reconstruction loss of gather_narrow_kernel
@@ -499,7 +434,7 @@ struct NarrowLoss {                                       // optional fused reco
 
 int try_gather_narrow(hipStream_t st, int dtype, const void* a, const void* w, int B, int IH, int IW, int C, int OH, int OW, int N,
                       int KH, int KW, void* out, const float* bias, const void* mask, int relu, NarrowLoss* loss = nullptr) {
-    if (!narrow_enabled() || mask || 4 * N > 32 || KH != KW || KH < 3 || KH > 6) return 0;
+    if (!knob(K_NARROW) || mask || 4 * N > 32 || KH != KW || KH < 3 || KH > 6) return 0;
     const int esz = esz_of(dtype);
     const int pa = C * esz;
     if ((pa != 64 && pa != 128) || (((uintptr_t)a) & 15) || (((uintptr_t)w) & 15) || (((uintptr_t)out) & 3) || (2 * N * esz) % 4 != 0) return 0;
@@ -541,7 +476,7 @@ int try_gather_narrow(hipStream_t st, int dtype, const void* a, const void* w, i
 int try_narrow_wgrad(hipStream_t st, int dtype, const void* narrow, int narrow_f32, const int* frame_idx, const void* wide,
                      int B, int IH, int IW, int Cs, int OH, int OW, int Nwide, int KH, int KW, float* out, float* dbias,
                      void* scratch, long long scratch_bytes) {
-    if (!narrow_enabled() || dtype != MI_BF16) return 0;
+    if (!knob(K_NARROW) || dtype != MI_BF16) return 0;
     const int run = KW * Cs;
     if (Nwide != 32 || KH > 4 || run > 12 || run % 4 != 0 || KH * run > 64 || (((uintptr_t)wide) & 15)) return 0;
     const int nsz = narrow_f32 == 2 ? 1 : (narrow_f32 ? 4 : 2);       // narrow_f32: 0 = bf16, 1 = fp32, 2 = uint8 camera bytes (value k / 255)
@@ -553,18 +488,16 @@ int try_narrow_wgrad(hipStream_t st, int dtype, const void* narrow, int narrow_f
     q.src = narrow; q.frame_idx = frame_idx; q.frame_stride = (long long)IH * IW * Cs;
     q.s = wide; q.s_bytes = (uint32_t)s_bytes;
     q.B = B; q.IH = IH; q.IW = IW; q.Cs = Cs; q.OH = OH; q.OW = OW; q.KH = KH; q.KW = KW; q.M = (int)M;
-    static int wpc = -1;                                   // resident waves per CU the grid is sized for (131 registers -> 3 per SIMD)
-    if (wpc < 0) { const char* e = getenv("MI355_NW_WAVES"); wpc = e ? atoi(e) : 12; }
-    long long nwave = 256ll * wpc;                         // one wave-range per resident wave: a single round, no tail
+    long long nwave = 256ll * knob(K_NW_WAVES);                        // one wave-range per resident wave: a single round, no tail
     long long ppw = (M + nwave - 1) / nwave; ppw = (ppw + NW_BP - 1) / NW_BP * NW_BP;
     if ((long long)OH * OW < NW_BP) return 0;
     if (ppw > 2ll * OH * OW) ppw = 2ll * OH * OW / NW_BP * NW_BP;   // a wave's range touches at most 3 frames (their indices are looked up once)
     nwave = (M + ppw - 1) / ppw;
-    const int nwv = (narrow_f32 == 2 || g_nw_waves >= 12) ? 12 : g_nw_waves >= 8 ? 8 : 4;
+    const int nwv = (narrow_f32 == 2 || knob(K_NW_BLOCK_WAVES) >= 12) ? 12 : knob(K_NW_BLOCK_WAVES) >= 8 ? 8 : 4;
     const int blocks = (int)((nwave + nwv - 1) / nwv);
     q.pix_per_block = (int)ppw;
     q.div_ohw = make_fastdiv(OH * OW); q.div_ow = make_fastdiv(OW);
-    q.out = out; q.dbias = dbias; q.dbg_skip_out = g_wgrad_skip == 1;
+    q.out = out; q.dbias = dbias; q.dbg_skip_out = knob(K_WGRAD_DBG) == 1;
     q.slabs = (scratch && (((uintptr_t)scratch) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (!dbias || (((uintptr_t)dbias) & 15) == 0) &&
                scratch_bytes >= (long long)blocks * NW_SLAB * 4) ? (float*)scratch : nullptr;
     const bool g3 = KW * q.Cs == 12;                     // the 4 x 4 x 3-channel layers: fixed-shape loop body (one basic block)
@@ -573,13 +506,13 @@ int try_narrow_wgrad(hipStream_t st, int dtype, const void* narrow, int narrow_f
         if (g3 && q.dbias) MI_LAUNCH((narrow_wgrad_kernel<TS_, 3, 1, NWV_>), g, t, 0, st, q); \
         else if (g3) MI_LAUNCH((narrow_wgrad_kernel<TS_, 3, 0, NWV_>), g, t, 0, st, q); \
         else MI_LAUNCH((narrow_wgrad_kernel<TS_, 0, -1, NWV_>), g, t, 0, st, q); } while (0)
-    if (narrow_f32 == 2 && g3 && q.dbias && g_nw_depth == 6) {
+    if (narrow_f32 == 2 && g3 && q.dbias && knob(K_NW_DEPTH) == 6) {
         MI_LAUNCH((narrow_wgrad_kernel<unsigned char, 3, 1, 12, 6>), dim3((unsigned)((nwave + 11) / 12)), dim3(768), 0, st, q);
-    } else if (narrow_f32 == 2 && g3 && q.dbias && g_nw_depth == 5) {
+    } else if (narrow_f32 == 2 && g3 && q.dbias && knob(K_NW_DEPTH) == 5) {
         MI_LAUNCH((narrow_wgrad_kernel<unsigned char, 3, 1, 12, 5>), dim3((unsigned)((nwave + 11) / 12)), dim3(768), 0, st, q);
     } else if (narrow_f32 == 2) NW_LAUNCH(unsigned char, 12);
-    else if (narrow_f32) { if (g_nw_waves >= 12) NW_LAUNCH(float, 12); else if (g_nw_waves >= 8) NW_LAUNCH(float, 8); else NW_LAUNCH(float, 4); }
-    else { if (g_nw_waves >= 12) NW_LAUNCH(bf16_t, 12); else if (g_nw_waves >= 8) NW_LAUNCH(bf16_t, 8); else NW_LAUNCH(bf16_t, 4); }
+    else if (narrow_f32) { if (knob(K_NW_BLOCK_WAVES) >= 12) NW_LAUNCH(float, 12); else if (knob(K_NW_BLOCK_WAVES) >= 8) NW_LAUNCH(float, 8); else NW_LAUNCH(float, 4); }
+    else { if (knob(K_NW_BLOCK_WAVES) >= 12) NW_LAUNCH(bf16_t, 12); else if (knob(K_NW_BLOCK_WAVES) >= 8) NW_LAUNCH(bf16_t, 8); else NW_LAUNCH(bf16_t, 4); }
 #undef NW_LAUNCH
     int rc = mi_check_launch("narrow_wgrad_kernel");
     if (rc == MI_OK && q.slabs) {
@@ -593,7 +526,7 @@ int try_narrow_wgrad(hipStream_t st, int dtype, const void* narrow, int narrow_f
 // conv k x k, s2 from a 1..3-channel tensor into exactly 32 channels (narrow_tile.hpp): conv1 fwd, deconv4 dgrad
 int try_narrow_conv(hipStream_t st, int dtype, const void* src, int src_f32, const int* frame_idx, const void* wt, int B, int IH, int IW, int Cs,
                     int KH, int KW, int Cout, const float* bias, int relu, const void* mask, void* out, void* bits_out = nullptr, const void* mask_bits = nullptr) {
-    if (!narrow_enabled() || Cout != 32 || KH != KW || KH > 4) return 0;
+    if (!knob(K_NARROW) || Cout != 32 || KH != KW || KH > 4) return 0;
     const int run = KW * Cs, K = KH * run;
     if (run % 4 != 0 || K > 48) return 0;
     const int ssz = src_f32 == 2 ? 1 : (src_f32 ? 4 : 2), esz = esz_of(dtype);   // src_f32: 0 = bf16, 1 = fp32, 2 = uint8 camera bytes, 3 = split storage
@@ -615,7 +548,7 @@ int try_narrow_conv(hipStream_t st, int dtype, const void* src, int src_f32, con
     if (bits_out && !q.bits_out) return 0;                // the caller asked for ReLU bits this kernel cannot write
     dim3 g((unsigned)((M + 127) / 128));
     // the model's geometry (K = 48 as 4 rows of 12) in bf16: the instruction-lean form; mode 0 = bias + ReLU (+ bit words), mode 1 = masked by bit words
-    const int lean = (dtype == MI_BF16 && KH == 4 && run == 12 && M * 64 < (1ll << 31) && narrow_lean_enabled())
+    const int lean = (dtype == MI_BF16 && KH == 4 && run == 12 && M * 64 < (1ll << 31) && knob(K_NARROW_LEAN))
                          ? ((bias && relu && !mask && !mask_bits) ? 1 : ((!bias && !relu && mask_bits && !bits_out) ? 2 : 0)) : 0;
     if (lean) {
         // persistent: as many four-wave blocks as stay resident (5-8 per compute unit by register count), each wave walks tiles with a one-tile prefetch
@@ -652,14 +585,14 @@ int try_narrow_conv(hipStream_t st, int dtype, const void* src, int src_f32, con
 // wfrag: fragment-ordered weights for the register-weight kernel (mi_rwconv_take_wfrag) or NULL
 int try_conv_form_gemm2(hipStream_t st, int dtype, const GemmParams& p, int gz, const void* wfrag) {
     if (p.a_frame_idx) return 0;
-    if (p.ksplit_len > 0 && (!g_gemm2_splitk || p.stride != 1 || p.KH != 1 || p.KW != 1 || (p.ksplit_len * esz_of(dtype)) % 128 != 0)) return 0;   // split-K: dense layers, whole 128-byte stages per split
+    if (p.ksplit_len > 0 && (!knob(K_GEMM2_SPLITK) || p.stride != 1 || p.KH != 1 || p.KW != 1 || (p.ksplit_len * esz_of(dtype)) % 128 != 0)) return 0;   // split-K: dense layers, whole 128-byte stages per split
     if (p.stride == 2 && !p.out_f32) {
         const int r5 = mi_try_rwconv_conv(st, dtype, p.a, p.b, p.nbatch, p.IH, p.IW, p.C, p.OH, p.OW, p.N, p.KH, p.KW, p.ldb, p.out, p.bias, p.mask, p.relu, wfrag);
         if (r5 != 0) return r5;
         const int r3 = try_tapconv(st, dtype, TC_CONV, p.a, p.b, p.nbatch, p.IH, p.IW, p.C, p.OH, p.OW, p.N, p.KH, p.KW, p.ldb, p.out, p.bias, p.mask, p.relu);
         if (r3 != 0) return r3;
     }
-    if (!gemm2_enabled()) return 0;
+    if (!knob(K_GEMM2)) return 0;
     const int esz = esz_of(dtype);
     const long long a_bytes = (long long)p.nbatch * p.a_frame_stride * esz, b_bytes = (long long)p.N * p.ldb * esz;
     if ((p.C * esz) % 16 != 0 || (((uintptr_t)p.a) & 15) || (((uintptr_t)p.b) & 15) || (p.ldb * esz) % 16 != 0 || p.ldb < p.K) return 0;
@@ -671,11 +604,8 @@ int try_conv_form_gemm2(hipStream_t st, int dtype, const GemmParams& p, int gz, 
     q.run = p.KW * p.C; q.div_run = make_fastdiv(q.run); q.div_ohw = p.div_ohw; q.div_ow = p.div_ow;
     q.ldb = p.ldb;
     q.ksplit_len = p.ksplit_len > 0 ? p.ksplit_len : 0;
-    {   // dense layers (1 x 1 "convolutions" of one position per row): XCD-contiguous numbering of the whole grid (MI355_GEMM2_REMAP3=0: x only, as for the convolutions)
-        static int remap3_on = -1;
-        if (remap3_on < 0) { const char* e = getenv("MI355_GEMM2_REMAP3"); remap3_on = (e && e[0] == '0') ? 0 : 1; }
-        q.remap3 = (remap3_on && p.stride == 1 && p.KH == 1 && p.KW == 1) ? 1 : 0;
-    }
+    // dense layers (1 x 1 "convolutions" of one position per row): XCD-contiguous numbering of the whole grid (MI355_GEMM2_REMAP3=0: x only, as for the convolutions)
+    q.remap3 = (knob(K_GEMM2_REMAP3) && p.stride == 1 && p.KH == 1 && p.KW == 1) ? 1 : 0;
     copy_epilogue(q, p);
     int rc = dtype == MI_F32 ? launch_gemm2_tiles<float, A_CONV, B_NK, false>(st, q, q.M, gz)
            : dtype == MI_BF16X3 ? launch_gemm2_tiles<split_t, A_CONV, B_NK, false>(st, q, q.M, gz)
@@ -685,7 +615,7 @@ int try_conv_form_gemm2(hipStream_t st, int dtype, const GemmParams& p, int gz, 
 
 // gather-form transposed conv (A_DECONV x B_DECONV); p already carries the class geometry from deconv_form_gemm
 int try_deconv_form_gemm2(hipStream_t st, int dtype, const GemmParams& p, int maxM) {
-    if (!gemm2_enabled()) return 0;
+    if (!knob(K_GEMM2)) return 0;
     if (p.N <= 32) return 0;      // measured: narrow gather-form layers (deconv3/4 fwd, conv2 dgrad) are not faster on the DMA tiles
     const int esz = esz_of(dtype);
     const long long a_bytes = (long long)p.nbatch * p.a_frame_stride * esz, b_bytes = (long long)p.KH * p.KW * p.N * p.C * esz;
@@ -818,7 +748,7 @@ static int prepare_wgrad(int dtype, WgradParams& p, int target_blocks, void* scr
     int mps = 0;
     const int splits = wgrad_splits(dtype, p.M, Kce, p.N, target_blocks, &mps);
     p.m_per_split = mps;
-    p.debug_skip_out = g_wgrad_skip;
+    p.debug_skip_out = knob(K_WGRAD_DBG);
     p.slabs = nullptr; p.slab_stride = ((long long)Kce * p.N + 3) / 4 * 4;
     if (splits > 1 && scratch && (((uintptr_t)scratch) & 15) == 0 && scratch_bytes >= (long long)splits * p.slab_stride * 4) p.slabs = (float*)scratch;
     // overwrite: out = result (no zeroed buffer, no atomics): plain stores from the single split, or the ordered slab sum storing instead of adding
@@ -938,53 +868,12 @@ extern "C" int mi_small_reduce_flush(void* stream) {
 }
 extern "C" int mi_small_reduce_deferring(void) { return t_sr_defer; }
 
-bool mi_narrow_enabled() { return narrow_enabled(); }
-
 void mi_get_trace(long long** buf, int* cap) { *buf = g_trace; *cap = g_trace_cap; }
-
-static bool tallk_enabled() {                              // MI355_TALLK=0: the general split-K kernel for the latent-side layers (A/B runs)
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("MI355_TALLK"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on != 0;
-}
 
 extern "C" {
 
 // debug: device buffer of int64 stamps, 32 per wave of every tapconv block (see tools/trace_tapconv.py); nullptr switches it off
 int mi_debug_set_trace(void* dev_ptr, int capacity_entries) { g_trace = (long long*)dev_ptr; g_trace_cap = dev_ptr ? capacity_entries : 0; return MI_OK; }
-
-int mi_set_tuning(int key, int value) {
-    int prev;
-    if (key == 0) { prev = gemm2_enabled() ? 1 : 0; g_gemm2_on = value ? 1 : 0; }
-    else if (key == 1) { prev = tapconv_minblocks(); g_tap_min = value < 0 ? -1 : value; }
-    else if (key == 2) { prev = g_wgrad_skip; g_wgrad_skip = value; }
-    else if (key == 5) { prev = g_tap_variant; g_tap_variant = value; }
-    else if (key == 6) { prev = g_tap_direct; g_tap_direct = value ? 1 : 0; }
-    else if (key == 8) { prev = 0; }                     // (was: persistent tapconv blocks, removed -- rwconv.hip is the persistent form that won)
-    else if (key == 4) { prev = narrow_enabled() ? 1 : 0; g_narrow_on = value ? 1 : 0; }
-    else if (key == 3) { prev = tapwgrad_enabled() ? 1 : 0; g_tapwgrad_on = value ? 1 : 0; }
-    else if (key == 7) { prev = g_tapwgrad_split; g_tapwgrad_split = value ? 1 : 0; }
-    else if (key == 9) { prev = g_tapwgrad_blocks; g_tapwgrad_blocks = value < 16 ? 16 : value; }
-    else if (key == 10) { prev = g_nw_waves; g_nw_waves = value; }
-    else if (key == 12) { prev = g_tap_mask_prefetch; g_tap_mask_prefetch = value ? 1 : 0; }
-    else if (key == 11) { prev = g_dense_wgrad_blocks; g_dense_wgrad_blocks = value < 1 ? 1 : value; }
-    else if (key == 13) { prev = mi_rwconv_mode(value < 0 ? 0 : value); }
-    else if (key == 14) { prev = g_tapwgrad_cw; g_tapwgrad_cw = value ? 1 : 0; }
-    else if (key == 15) { prev = mi_rwconv_conv_mode(value < 0 ? 0 : value); }
-    else if (key == 16) { prev = mi_rwconv_blocks(value < 0 ? 0 : value); }
-    else if (key == 17) { prev = g_gemm2_tile; g_gemm2_tile = value; }
-    else if (key == 18) { prev = g_slab_bf16; g_slab_bf16 = value ? 1 : 0; }
-    else if (key == 19) { prev = g_nw_depth; g_nw_depth = value; }
-    else if (key == 20) { prev = g_gemm2_stages; g_gemm2_stages = value; }
-    else if (key == 21) { prev = g_x3_tapwgrad; g_x3_tapwgrad = value; }
-    else if (key == 22) { prev = g_dwgs_on; g_dwgs_on = value ? 1 : 0; }
-    else if (key == 24) { prev = g_tw_ldec; g_tw_ldec = value < 0 || value > 3 ? 0 : value; }
-    else if (key == 25) { prev = g_dectail_dbg; g_dectail_dbg = value; }
-    else if (key == 26) { prev = g_dectail_split5; g_dectail_split5 = value ? 1 : 0; }
-    else if (key == 23) { prev = mi_enc12_debug(value); }  // (debug: ablation mask of the fused encoder head's timing instantiation -- results are wrong with any bit set)
-    else return mi_fail(MI_ERR_ARG, "mi_set_tuning: unknown key");
-    return prev;
-}
 
 // conv2d NHWC stride-2 VALID forward: out[B,OH,OW,Cout] = relu?(im2col(x) * W[kh,kw,ci,co] + bias)
 // replaces tf.layers.conv2d in ConvVAE.build_encoder (reference vae/models.py:250-253)
@@ -1146,9 +1035,7 @@ int mi_deconv2d_tail_fused(void* stream, int dtype, const void* x, int B, int IH
     if (!n_partial || !labels || !loss_partial || !bias_partial || !x || !w || !w_t || !dx || !dw) return mi_fail(MI_ERR_ARG, "mi_deconv2d_tail_fused: missing buffers");
     *n_partial = 0;
     if (loss_kind < 0 || loss_kind > 2) return mi_fail(MI_ERR_ARG, "mi_deconv2d_tail_fused: loss_kind must be 0 (bce), 1 (bce_v2) or 2 (mse)");
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("MI355_DECTAIL"); on = (e && e[0] == '0') ? 0 : 1; }
-    if (!on || !narrow_enabled() || dtype != MI_BF16 || Cin != 32 || Cout != 3 || KH != 4 || KW != 4 || B < 1 || IH < 1 || IW < 1) return MI_OK;
+    if (!knob(K_DECTAIL) || !knob(K_NARROW) || dtype != MI_BF16 || Cin != 32 || Cout != 3 || KH != 4 || KW != 4 || B < 1 || IH < 1 || IW < 1) return MI_OK;
     if (((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)w_t) | ((uintptr_t)dx) | ((uintptr_t)scratch) | ((uintptr_t)dw)) & 15) || !scratch) return MI_OK;
     // the label tile is staged in 4-value items: rows of 3 OW values must be a whole number of items, frames 4-byte (uint8) / 16-byte (fp32) aligned
     if ((3 * (2 * IW + 2)) % 4 != 0 || label_stride % 4 != 0 || (((uintptr_t)labels) & (labels_u8 ? 3 : 15))) return MI_OK;
@@ -1157,8 +1044,7 @@ int mi_deconv2d_tail_fused(void* stream, int dtype, const void* x, int B, int IH
     q.labels = labels; q.lab_u8 = labels_u8 ? 1 : 0; q.lab_idx = frame_idx; q.lab_stride = label_stride; q.loss_kind = loss_kind; q.inv_b = inv_batch;
     q.dx = (bf16_t*)dx; q.lpart = loss_partial; q.bpart = bias_partial;
     q.OH = 2 * IH + 2; q.OW = 2 * IW + 2; q.GH = IH + 1; q.GW = IW + 1;
-    static int edge = -1;                                 // A/B knob: tiles over the pixel grid, last slot row / column owned by the last tiles
-    if (edge < 0) { const char* e = getenv("MI355_DECTAIL_EDGE"); edge = (e && e[0] == '0') ? 0 : 1; }
+    const int edge = knob(K_DECTAIL_EDGE);                // A/B knob: tiles over the pixel grid, last slot row / column owned by the last tiles
     q.edge_own = edge;
     if ((long long)B * IH * IW * 64 >= 0x7fffff00ll || (long long)q.OH * q.OW * 12 >= 0x7fffff00ll) return MI_OK;      // 32-bit buffer offsets
     q.x_bytes = (unsigned)((long long)B * IH * IW * 64);
@@ -1173,9 +1059,9 @@ int mi_deconv2d_tail_fused(void* stream, int dtype, const void* x, int B, int IH
     if (nblocks >= 16) nblocks &= ~7;                       // whole rounds of the eight XCDs (the kernel's tile order)
     if (nblocks > partial_capacity || scratch_bytes < (long long)nblocks * DT_SLAB * 4) return MI_OK;
     q.slabs = (float*)scratch;
-    q.dbg = g_dectail_dbg;
+    q.dbg = knob(K_DECTAIL_DBG);
     if (fast && q.dbg) MI_LAUNCH((dectail_kernel<true, true>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, q);      // (timing instantiation: tools/dectail_ablate.py)
-    else if (fast && g_dectail_split5) MI_LAUNCH((dectail_kernel<true, false, true>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, q);
+    else if (fast && knob(K_DECTAIL_SPLIT5)) MI_LAUNCH((dectail_kernel<true, false, true>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, q);
     else if (fast) MI_LAUNCH(dectail_kernel<true>, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, q);
     else MI_LAUNCH(dectail_kernel<false>, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, q);
     int rc = mi_check_launch("dectail_kernel");
@@ -1254,14 +1140,14 @@ int mi_deconv2d_nhwc_wgrad_ws(void* stream, int dtype, const void* dy, int B, in
 // nsplit > 1: split-K, raw fp32 partial slabs out[nsplit][M][N] (bias/act/mask must be unset; consumer reduces).
 int mi_gemm_bias_act(void* stream, int dtype, const void* a, int M, int K, const void* w, int w_layout, int N,
                      const float* bias, int relu, const void* mask, void* out, int out_f32, int nsplit) {
-    if (dtype == MI_F32 && w_layout == 0 && nsplit <= 1 && !mask && M <= 256 && K % 4 == 0 && gemm2_enabled() &&
+    if (dtype == MI_F32 && w_layout == 0 && nsplit <= 1 && !mask && M <= 256 && K % 4 == 0 && knob(K_GEMM2) &&
         ((((uintptr_t)a) | ((uintptr_t)out)) & 15) == 0) {                 // small-M fp32 dense layer (PPO): K split across the waves of a block
         DenseSmallParams q = {(const float*)a, (const float*)w, bias, (float*)out, M, N, K, relu};
         MI_LAUNCH(dense_smallm_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0, (hipStream_t)stream, q);
         return mi_check_launch("dense_smallm_kernel");
     }
     // long reduction into a narrow output, K-contiguous weights, raw split-K slabs wanted (the latent-side layers): tallk_tile.hpp
-    if (dtype == MI_BF16 && w_layout == 1 && nsplit > 1 && out_f32 && !bias && !relu && !mask && tallk_enabled() && (N == 32 || N == 64 || N == 128) &&
+    if (dtype == MI_BF16 && w_layout == 1 && nsplit > 1 && out_f32 && !bias && !relu && !mask && knob(K_TALLK) && (N == 32 || N == 64 || N == 128) &&
         K % (nsplit * 16) == 0 && ((((uintptr_t)a) | ((uintptr_t)w)) & 15) == 0 && (long long)M * K * 2 < (1ll << 30) && (long long)N * K * 2 < (1ll << 30)) {
         const int nt = N / 32, kp = 4 / nt;
         if (nsplit % kp == 0) {
@@ -1305,7 +1191,7 @@ static bool dwgs_eligible(int dtype, int M, int K, int N) {
     // three forms of this kernel -- one wave per tile, row splits through slabs, row splits inside the block -- at 0.8573 / 0.8168 / 0.8163 ms per step against 0.8449 / 0.8153 /
     // 0.8032 on the first-generation kernel (same box within a pair): at the end of the backward pass their time is set by the 147 KB-LDS filter gradient that holds the
     // CUs and by the slab reduce that saturates HBM, and the 64 KB-LDS row-split kernel rides that out better
-    return g_dwgs_on && dtype == MI_BF16 && M >= 16 && M % 16 == 0 && K % 64 == 0 && N % 64 == 0 && (long long)K * N <= 262144 &&
+    return knob(K_DWGS) && dtype == MI_BF16 && M >= 16 && M % 16 == 0 && K % 64 == 0 && N % 64 == 0 && (long long)K * N <= 262144 &&
            (long long)M * K < (1ll << 31) && (long long)M * N < (1ll << 31);
 }
 // ... with this many waves per tile (row splits inside the block; a function of the row count only): at least two load rounds per wave
@@ -1318,7 +1204,7 @@ static int dwgs_wsplit(int M) {
 
 long long mi_gemm_wgrad_scratch_bytes(int dtype, int M, int K, int N) {
     if (M < 1 || K < 1 || N < 1) return 0;
-    const int splits = wgrad_splits(dtype, M, K + 1, N, g_dense_wgrad_blocks, nullptr);      // (+ 1: room for the bias row of mi_gemm_wgrad_bias_ws)
+    const int splits = wgrad_splits(dtype, M, K + 1, N, knob(K_DENSE_WGRAD_BLOCKS), nullptr);      // (+ 1: room for the bias row of mi_gemm_wgrad_bias_ws)
     return splits > 1 ? (long long)splits * (((long long)(K + 1) * N + 3) / 4 * 4) * 4 : 0;  // (one row split: a single block per element adds straight into dw)
 }
 
@@ -1336,15 +1222,11 @@ int mi_gemm_wgrad_bias_ws(void* stream, int dtype, const void* a, const void* dy
 // need not be zeroed between steps and no element is touched by an atomic (the MlpVAE engine: 39.5 M weights, the zeroing alone was 158 MB per step)
 int mi_gemm_wgrad_bias_set(void* stream, int dtype, const void* a, const void* dy, int M, int K, int N, float* dw, float* dbias, void* scratch, long long scratch_bytes, int overwrite) {
     // large result, short reduction, storing form: whole 128 x 128 tiles of dW per block over all rows (dwg_tile.hpp)
-    static int dwg_on = -1;
-    if (dwg_on < 0) { const char* e = getenv("MI355_DWG"); dwg_on = (e && e[0] == '0') ? 0 : 1; }
-    if (overwrite && dwg_on && dtype == MI_BF16 && M >= 1 && K % 128 == 0 && N % 128 == 0 && (long long)(K / 128) * (N / 128) >= 256 &&
+    if (overwrite && knob(K_DWG) && dtype == MI_BF16 && M >= 1 && K % 128 == 0 && N % 128 == 0 && (long long)(K / 128) * (N / 128) >= 256 &&
         ((((uintptr_t)a) | ((uintptr_t)dy) | ((uintptr_t)dw)) & 15) == 0 && fits_desc((long long)M * K * 2) && fits_desc((long long)M * N * 2)) {
         DwgParams q = {a, (uint32_t)((long long)M * K * 2), dy, (uint32_t)((long long)M * N * 2), dw, dbias, M, K, N, K / 128, N / 128};
         const int per = (q.KT * q.NT + 7) / 8;
-        static int nst = -1;
-        if (nst < 0) { const char* e = getenv("MI355_DWG_NST"); nst = (e && atoi(e) == 4) ? 4 : 3; }
-        if (nst == 3) MI_LAUNCH(dwg_kernel<3>, dim3((unsigned)(per * 8)), dim3(256), 0, (hipStream_t)stream, q);
+        if (knob(K_DWG_NST) == 3) MI_LAUNCH(dwg_kernel<3>, dim3((unsigned)(per * 8)), dim3(256), 0, (hipStream_t)stream, q);
         else MI_LAUNCH(dwg_kernel<4>, dim3((unsigned)(per * 8)), dim3(256), 0, (hipStream_t)stream, q);
         return mi_check_launch("dwg_kernel");
     }
@@ -1364,7 +1246,7 @@ int mi_gemm_wgrad_bias_set(void* stream, int dtype, const void* a, const void* d
     const int vb = dtype == MI_BF16 ? 8 : 4;
     if (K % vb != 0) return mi_fail(MI_ERR_SHAPE, "mi_gemm_wgrad: K must be a multiple of the 16-byte vector (pad K)");
     p.N = N; p.small = dy; p.s_vec = vec_ok(dy, N, dtype); p.out = dw;
-    return launch_wgrad((hipStream_t)stream, dtype, 0, p, g_dense_wgrad_blocks, scratch, scratch_bytes, overwrite);
+    return launch_wgrad((hipStream_t)stream, dtype, 0, p, knob(K_DENSE_WGRAD_BLOCKS), scratch, scratch_bytes, overwrite);
 }
 
 // TWO dense filter gradients (+ bias rows) as ONE launch: what mi_gemm_wgrad_bias_ws(problem 0) followed by mi_gemm_wgrad_bias_ws(problem 1) computes, bit for bit, when both take the
@@ -1385,7 +1267,7 @@ int mi_gemm_wgrad_bias_pair_ws(void* stream, int dtype, const void* a0, const vo
         fill_wgrad_geom(p, M[i], 1, 1, K[i], 1, 1, 1, 1, 1, false);
         p.N = N[i]; p.small = DY[i]; p.s_vec = vec_ok(DY[i], N[i], dtype); p.out = DW[i];
         bool wide = false;
-        if (prepare_wgrad(dtype, p, g_dense_wgrad_blocks, WS[i], NB[i], 0, &g[i], &wide) != MI_OK || !wide || p.C % 8 != 0) ok = false;
+        if (prepare_wgrad(dtype, p, knob(K_DENSE_WGRAD_BLOCKS), WS[i], NB[i], 0, &g[i], &wide) != MI_OK || !wide || p.C % 8 != 0) ok = false;
     }
     if (!ok) {
         const int rc = mi_gemm_wgrad_bias_ws(stream, dtype, a0, dy0, M0, K0, N0, dw0, db0, scratch0, scratch_bytes0);

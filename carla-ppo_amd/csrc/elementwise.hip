@@ -766,12 +766,6 @@ int mi_vae_reparam_kl_fwd(void* stream, int dtype, const float* heads, int nspli
     return mi_vae_reparam_kl_fwd_rng(stream, dtype, heads, nsplit, bias_mean, bias_lv, eps, sample, B, Z, mean, logvar, z, kl_row, nullptr, nullptr);
 }
 
-static bool reparam_wide() {                             // MI355_REPARAM_WIDE=1 (A/B knob, default off): the reparameterisation kernels request up to 32 slabs per element at once
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("MI355_REPARAM_WIDE"); on = (e && e[0] == '1') ? 1 : 0; }
-    return on != 0;
-}
-
 // same; eps == NULL with sample != 0: the kernel draws the noise from the Philox stream in rng_state (4 x uint64 on the device: seed, next
 // element offset, 2 words of kernel bookkeeping -- zero them once) and stores what it drew in eps_out [B,Z] for the backward pass
 int mi_vae_reparam_kl_fwd_rng(void* stream, int dtype, const float* heads, int nsplit, const float* bias_mean, const float* bias_lv,
@@ -779,7 +773,7 @@ int mi_vae_reparam_kl_fwd_rng(void* stream, int dtype, const float* heads, int n
                               unsigned long long* rng_state, float* eps_out) {
     if (sample && !eps && !(rng_state && eps_out)) return mi_fail(MI_ERR_ARG, "mi_vae_reparam_kl_fwd: sampling needs eps or a generator state + eps_out");
     dim3 g((B + 3) / 4), b(256);
-    if (reparam_wide() && nsplit > 8) {                   // MI355_REPARAM_WIDE=1: all (up to 32) slabs of an element requested before the first add -- same order, same sums
+    if (knob(K_REPARAM_WIDE) && nsplit > 8) {                   // MI355_REPARAM_WIDE=1: all (up to 32) slabs of an element requested before the first add -- same order, same sums
         BY_DTYPE(dtype, hipLaunchKernelGGL((reparam_kl_fwd_kernel<TT, 32>), g, b, 0, (hipStream_t)stream, heads, nsplit, bias_mean, bias_lv, eps, sample, B, Z, mean, logvar, (TT*)z, kl_row, rng_state, eps_out));
         return mi_check_launch("reparam_kl_fwd");
     }
@@ -797,7 +791,7 @@ int mi_normal_philox(void* stream, unsigned long long seed, unsigned long long o
 int mi_vae_reparam_kl_bwd(void* stream, int dtype, const float* dz_slabs, int nsplit, const float* mean, const float* logvar,
                           const float* eps, const float* kl_row, float beta, float kl_floor, float inv_batch, int B, int Z, void* dheads) {
     dim3 g((B + 3) / 4), b(256);
-    if (reparam_wide() && nsplit > 8) {
+    if (knob(K_REPARAM_WIDE) && nsplit > 8) {
         BY_DTYPE(dtype, hipLaunchKernelGGL((reparam_kl_bwd_kernel<TT, 32>), g, b, 0, (hipStream_t)stream, dz_slabs, nsplit, mean, logvar, eps, kl_row, beta, kl_floor, inv_batch, B, Z, (TT*)dheads));
         return mi_check_launch("reparam_kl_bwd");
     }

@@ -6,9 +6,6 @@
 
 using namespace mi;
 
-static int g_enc12_dbg = 0;
-int mi_enc12_debug(int mask) { const int prev = g_enc12_dbg; g_enc12_dbg = mask < 0 ? 0 : mask; return prev; }
-
 // resident blocks of one instantiation (slot: 0 / 1 training form on fp32 frames / camera bytes, 2 / 3 the inference form)
 static int enc12_grid(const void* fn, int slot) {
     static int resident[4];
@@ -24,9 +21,7 @@ static int enc12_grid(const void* fn, int slot) {
 
 // the fused kernel takes calls of this storage type, batch and frame size (switched on: MI355_ENC12, the narrow kernels); the VAE engine sizes its workspace by it
 bool mi_enc12_eligible(int dtype, int B, int FH, int FW) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("MI355_ENC12"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on && mi_narrow_enabled() && dtype == MI_BF16 && B >= 1 && FH == 80 && FW == 160 && (long long)B * 3 < (1ll << 30);
+    return knob(K_ENC12) && knob(K_NARROW) && dtype == MI_BF16 && B >= 1 && FH == 80 && FW == 160 && (long long)B * 3 < (1ll << 30);
 }
 
 // The encoder head of a forward pass in ONE launch (round 5): frames [*, 80, 160, 3] as raw uint8 camera bytes (frames_fmt 2) or float32 in [0, 1] (1), optionally gathered through frame_idx, -conv1 k4 s2 + bias +
@@ -62,12 +57,8 @@ extern "C" int mi_conv2d_enc12_fwd(void* stream, int dtype, const void* frames, 
     // 55.5 -> 53.0 -> 51.1 us for the op alone at batch 512, interleaved medians; step -0.5 ... -0.8 %).  MI355_ENC12_RING=0 / MI355_ENC12_C2=0: the compiler-scheduled forms (A/B).
     // Both forms issue loads by inline assembly and wait by hand: tools/check_enc12_isa.py (run by tests/test_host_logic.py) proves on the generated code that no
     // register is read while its load can be outstanding.
-    static int ring = -1;
-    if (ring < 0) { const char* e = getenv("MI355_ENC12_RING"); ring = (e && e[0] == '0') ? 0 : 1; }
-    static int c2 = -1;
-    if (c2 < 0) { const char* e = getenv("MI355_ENC12_C2"); c2 = (e && e[0] == '0') ? 0 : 1; }
-    int use_ring = ring, use_c2 = c2;
-    int dbg = g_enc12_dbg;
+    int use_ring = knob(K_ENC12_RING), use_c2 = knob(K_ENC12_C2);
+    int dbg = knob(K_ENC12_DBG);
     if (dbg & 4096) { use_ring = (dbg >> 13) & 1; use_c2 = (dbg >> 14) & 1; dbg = 0; }      // (bit 4096: pick a PRODUCT form by mask -- bit 8192 ring, 16384 pipelined conv2 -- for interleaved timing in one process)
     if (dbg && frames_fmt == 2) {                           // ablation timing (mi_set_tuning key 23; tools/enc12_ablate.py): WRONG results by construction
         q.dbg = dbg;

@@ -57,9 +57,7 @@ extern "C" int mi_conv2d_head_bwd_fused(void* stream, int dtype, const void* fra
                                         const void* dy2, const void* w2, const void* bits_act1, float* dw1, float* db1, void* scratch, long long scratch_bytes, int* n_blocks) {
     if (!n_blocks || !frames || !dy2 || !w2 || !dw1 || !db1) return mi_fail(MI_ERR_ARG, "mi_conv2d_head_bwd_fused: missing buffers");
     *n_blocks = 0;
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("MI355_ENCHEAD"); on = (e && e[0] == '0') ? 0 : 1; }
-    if (!on || !mi_narrow_enabled() || dtype != MI_BF16 || !bits_act1 || !scratch || B < 1) return MI_OK;
+    if (!knob(K_ENCHEAD) || !knob(K_NARROW) || dtype != MI_BF16 || !bits_act1 || !scratch || B < 1) return MI_OK;
     if (frames_fmt != 1 && frames_fmt != 2) return MI_OK;                     // fp32 or uint8 camera frames
     if (FH < 10 || FW < 10) return MI_OK;
     const int IH = (FH - 4) / 2 + 1, IW = (FW - 4) / 2 + 1;

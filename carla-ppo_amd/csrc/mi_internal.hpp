@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include "tuning.hpp"                              // mi::knob(K_...): every launcher reads its knobs from the one table
 
 enum { MI_F32 = 0, MI_BF16 = 1, MI_BF16X3 = 2 };   // MI_BF16X3: split storage (hi | lo bf16 halves per 4-byte element), common.hpp
 enum { MI_OK = 0, MI_ERR_ARG = -1, MI_ERR_SHAPE = -2, MI_ERR_LAUNCH = -3, MI_ERR_STATE = -4 };
@@ -17,7 +18,6 @@ extern thread_local hipEvent_t mi_tl_stop_event;
         else hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__); } while (0)
 
 const void* mi_rwconv_take_wfrag();             // rwconv.hip: returns and clears this thread's mi_rwconv_next_weights_fragment_ordered announcement (called first thing by the entries it applies to)
-int mi_enc12_debug(int mask);                    // enc12.hip: ablation mask of the fused encoder-head forward kernel (tools/enc12_ablate.py); returns the previous one
 bool mi_enc12_eligible(int dtype, int B, int FH, int FW);   // enc12.hip: mi_conv2d_enc12_fwd takes calls of this storage type / batch / frame size (before its alignment checks)
 int mi_fail(int code, const char* msg);          // records msg (thread-local) and returns code
 int mi_check_launch(const char* what);           // hipGetLastError() -> MI_OK / MI_ERR_LAUNCH
@@ -34,9 +34,6 @@ int mi_try_rwconv_gather(hipStream_t st, int dtype, const void* a, const void* w
                          int KH, int KW, void* out, const float* bias, const void* mask, int relu, const void* mask_bits, void* bits_out, const void* wfrag);
 int mi_try_rwconv_conv(hipStream_t st, int dtype, const void* a, const void* w, int B, int IH, int IW, int C, int OH, int OW, int N,
                        int KH, int KW, int ldb, void* out, const float* bias, const void* mask, int relu, const void* wfrag);   // rwconv.hip, conv form (32 -> 64 channels)
-int mi_rwconv_conv_mode(int set);                // mi_set_tuning key 15: 0 off, 1 k = 5 layers, 2 also k = 4; set < 0 queries
-int mi_rwconv_blocks(int set);                   // mi_set_tuning key 16: persistent blocks per XCD (0 = resident maximum); set < 0 queries
-int mi_rwconv_mode(int set);                     // mi_set_tuning key 13: 0 off, 1 auto, 2 whenever eligible; set < 0 queries
 void mi_get_trace(long long** buf, int* cap);     // the debug stamp buffer of mi_debug_set_trace
 
 // out[0 .. n) += sum over nslab slabs of slabs[k * stride + i] (reduce_small_fused_kernel, tapwgrad_tile.hpp; fixed summation order, no atomics) -- conv_ops.hip
@@ -46,4 +43,3 @@ extern "C" int mi_small_reduce_defer(int on);
 extern "C" int mi_small_reduce_flush(void* stream);
 extern "C" int mi_small_reduce_bind(void* stream);      // the list of the deferring pass belongs to `stream`; mi_reduce_slabs calls from other streams launch immediately (round 5)
 extern "C" int mi_small_reduce_deferring(void);
-bool mi_narrow_enabled();                        // the narrow-layer kernels are switched on (mi_set_tuning key 4 / MI355_NARROW) -- conv_ops.hip

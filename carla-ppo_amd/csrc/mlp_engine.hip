@@ -300,8 +300,7 @@ int mi_mlpvae_backward(void* h, void* stream, const float* eps, float inv_batch,
     // A full pass (part 0) runs on two streams: the input-gradient chain is a row of dependent kernels, eight of them a few microseconds of work on an empty GPU, and no
     // filter gradient is on it.  The output layer's filter gradient (needs only the loss gradient) runs UNDER the chain on the second stream; behind the chain the small
     // layers' filter gradients run there next to the first layer's on the caller's stream.  Two events on the caller's stream, one join.  MI355_MLP_STREAMS=0: one stream.
-    static int streams_on = -1;
-    if (streams_on < 0) { const char* ev = getenv("MI355_MLP_STREAMS"); streams_on = (ev && ev[0] == '0') ? 0 : 1; }
+    const int streams_on = mi::knob(mi::K_MLP_STREAMS);
     if (part == 0 && streams_on && e->side_ok == 0) {
         if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&e->ev_chain, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&e->ev_done, hipEventDisableTiming) == hipSuccess) e->side_ok = 1;

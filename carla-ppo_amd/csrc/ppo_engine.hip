@@ -91,15 +91,10 @@ __global__ void head_dgrad_kernel(const float* __restrict__ du, const float* __r
 
 #define CK(call) do { int rc__ = (call); if (rc__ != MI_OK) return rc__; } while (0)
 
-bool fused_switch() {                                    // MI355_PPO_FUSED=0: the first-generation step (one launch per layer op), for A/B runs
-    static int on = -1;
-    if (on < 0) { const char* ev = getenv("MI355_PPO_FUSED"); on = (ev && ev[0] == '0') ? 0 : 1; }
-    return on != 0;
-}
 // the fused kernels serve the shapes they were built for (the reference's 500 / 300 trunk, <= 8 actions); anything else takes the per-layer path
 bool fused_enabled(const PpoEngine* e);
 
-bool fused_enabled(const PpoEngine* e) { return fused_switch() && mi_ppo_fused_shape_in_range(e->d.num_actions, e->d.h2, e->kin); }
+bool fused_enabled(const PpoEngine* e) { return knob(K_PPO_FUSED) && mi_ppo_fused_shape_in_range(e->d.num_actions, e->d.h2, e->kin); }
 
 bool x3(const PpoEngine* e) { return e->precision == MI_BF16X3; }
 
@@ -253,8 +248,7 @@ int mi_ppo_forward_backward(void* h, void* stream, const float* states, const fl
     // backward: policy head + trunk | value head + trunk.  OFF by default (MI355_PPO_STREAMS=1 enables it): with device-resident minibatches
     // the step drops from 181 to 172 us, but the four event operations raise the host cost per step from 90 to 135 us, and the reference's
     // calling pattern (one host minibatch per train() call) is host-bound: 3.25 -> 3.6 ms per update of 16 steps.
-    static int two_streams = -1;
-    if (two_streams < 0) { const char* ev = getenv("MI355_PPO_STREAMS"); two_streams = (ev && ev[0] == '1') ? 1 : 0; }
+    const int two_streams = knob(K_PPO_STREAMS);
     if (two_streams && !e->side_ok) {
         if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) == hipSuccess) e->side_ok = 1;

@@ -738,9 +738,8 @@ int mi_ppo_fused_trunks(hipStream_t st, const PpoFusedParams& q, bool x3) {
 // Compiled only with -DMI355_PPO_PAD_PROBE (HIPCC_EXTRA=-DMI355_PPO_PAD_PROBE python -m mi355.build --force): the production step carries no measurement code.
 #ifdef MI355_PPO_PAD_PROBE
 __global__ void ppo_boundary_probe_kernel(float* sink) { if (threadIdx.x == 1024) sink[0] = 0.f; }
-static int ppo_pad_launches() { static int n = -1; if (n < 0) { const char* e = getenv("MI355_PPO_PAD"); n = e ? atoi(e) : 0; if (n < 0 || n > 64) n = 0; } return n; }
 static int ppo_pad(hipStream_t st, float* sink) {
-    const int pad = ppo_pad_launches();
+    const int pad = knob(K_PPO_PAD);
     for (int i = 0; i < pad; ++i) hipLaunchKernelGGL(ppo_boundary_probe_kernel, dim3(1), dim3(64), 0, st, sink);
     return pad ? mi_check_launch("ppo_boundary_probe") : MI_OK;
 }

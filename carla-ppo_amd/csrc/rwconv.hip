@@ -636,25 +636,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 using namespace mi;
 
-int g_rwconv_dbg = 0;
-int g_rwconv_blocks = 0;                                 // debug (MI355_RWCONV_BLOCKS): persistent blocks per XCD, 0 = as many as stay resident
-int g_rwconv_mode = -1;                                  // mi_set_tuning key 13 / MI355_RWCONV: 0 off, 1 auto, 2 whenever the layer is eligible
-int mi_rwconv_mode(int set) {                            // set < 0: query
-    if (g_rwconv_mode < 0) { const char* b = getenv("MI355_RWCONV_BLOCKS"); g_rwconv_blocks = b ? atoi(b) : 0; const char* d = getenv("MI355_RWCONV_DBG"); g_rwconv_dbg = d ? atoi(d) : 0; }
-    if (g_rwconv_mode < 0) { const char* e = getenv("MI355_RWCONV"); g_rwconv_mode = e ? atoi(e) : 1; if (g_rwconv_mode < 0 || g_rwconv_mode > 2) g_rwconv_mode = 1; }
-    const int prev = g_rwconv_mode;
-    if (set >= 0) g_rwconv_mode = set > 2 ? 2 : set;
-    return prev;
-}
-
 // gather-form transposed conv / conv input gradient on the register-weight kernel.  Same contract as try_tapconv (conv_ops.hip):
 // returns 1 launched, 0 not eligible, < 0 error.  x [B,IH,IW,64] bf16, w [KH][KW][32][64] bf16, out / mask [B,OH,OW,32] bf16.
 int mi_try_rwconv_gather(hipStream_t st, int dtype, const void* a, const void* w, int B, int IH, int IW, int C, int OH, int OW, int N,
                          int KH, int KW, void* out, const float* bias, const void* mask, int relu, const void* mask_bits, void* bits_out, const void* wfrag) {
-    mi_rwconv_mode(-1);
-    static int wide = -1;                                 // MI355_RWCONV_WIDE=0: the 128 -> 64 channel layers stay on tapconv (A/B runs)
-    if (wide < 0) { const char* ev = getenv("MI355_RWCONV_WIDE"); wide = (ev && ev[0] == '0') ? 0 : 1; }
-    const int ck = (C == 128 && N == 64 && KH == 4 && wide) ? 2 : 1;                      // 128 -> 64 channels: k = 4 only
+    const int rw_mode = knob(K_RWCONV), rw_blocks = knob(K_RWCONV_BLOCKS), rw_dbg = knob(K_RWCONV_DBG);
+    const int ck = (C == 128 && N == 64 && KH == 4 && knob(K_RWCONV_WIDE)) ? 2 : 1;       // 128 -> 64 channels: k = 4 only (MI355_RWCONV_WIDE=0: they stay on tapconv, A/B runs)
     if (dtype != MI_BF16 || C != 64 * ck || N != 32 * ck || KH != KW || (KH != 4 && KH != 5)) return 0;
     if ((((uintptr_t)a) | ((uintptr_t)w) | ((uintptr_t)out) | ((uintptr_t)mask)) & 15) return 0;
     if ((long long)B * OH * OW * N >= (1ll << 31)) return 0;
@@ -678,12 +665,12 @@ int mi_try_rwconv_gather(hipStream_t st, int dtype, const void* a, const void* w
     mi_get_trace(&q.trace, &q.trace_cap);
     const int bmt = KH == 4 ? (ck == 2 ? RwCfg<2, 2>::BMT : RwCfg<2>::BMT) : RwCfg<3>::BMT;
     const int nchunks = (int)((MP + bmt - 1) / bmt);
-    if (g_rwconv_mode == 0 || (g_rwconv_mode == 1 && MP < 75000)) return 0;      // auto: only where the grid fills the chip (as tapconv)
+    if (rw_mode == 0 || (rw_mode == 1 && MP < 75000)) return 0;      // auto: only where the grid fills the chip (as tapconv)
     // persistent grid: as many blocks as stay resident (3 per CU for k = 4, 2 for k = 5), a multiple of 8 (one share per XCD)
     static int n_cu = 0;
     if (!n_cu) { int dev = 0; hipDeviceProp_t pr; n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256; }
     int per_xcd = (n_cu / 8) * ((KH == 4 && ck == 1) ? 3 : 1);
-    if (g_rwconv_blocks > 0) per_xcd = g_rwconv_blocks;
+    if (rw_blocks > 0) per_xcd = rw_blocks;
     if (per_xcd > (nchunks + 7) / 8) per_xcd = (nchunks + 7) / 8;
     const dim3 g((unsigned)(8 * per_xcd));
 #define RW_LAUNCH(TAPS_, KH_) do { \
@@ -695,9 +682,9 @@ int mi_try_rwconv_gather(hipStream_t st, int dtype, const void* a, const void* w
         else if (q.mask_bits) MI_LAUNCH((rwconv_gather_kernel<TAPS_, KH_, false, 2, false>), g, t_, 0, st, q, nchunks); \
         else if (mask) MI_LAUNCH((rwconv_gather_kernel<TAPS_, KH_, false, 1, false>), g, t_, 0, st, q, nchunks); \
         else MI_LAUNCH((rwconv_gather_kernel<TAPS_, KH_, false, 0, false>), g, t_, 0, st, q, nchunks); } while (0)
-    if (KH == 5 && relu && !mask && !bits_out && g_rwconv_dbg > 0) {  // debug variants of the deconv3-forward instantiation (MI355_RWCONV_DBG: 1 no stores, 2 no LDS reads, 3 no MFMAs)
-        if (g_rwconv_dbg == 1) MI_LAUNCH((rwconv_gather_kernel<3, 5, true, 0, false, 1>), g, dim3(512), 0, st, q, nchunks);
-        else if (g_rwconv_dbg == 2) MI_LAUNCH((rwconv_gather_kernel<3, 5, true, 0, false, 2>), g, dim3(512), 0, st, q, nchunks);
+    if (KH == 5 && relu && !mask && !bits_out && rw_dbg > 0) {  // debug variants of the deconv3-forward instantiation (MI355_RWCONV_DBG: 1 no stores, 2 no LDS reads, 3 no MFMAs)
+        if (rw_dbg == 1) MI_LAUNCH((rwconv_gather_kernel<3, 5, true, 0, false, 1>), g, dim3(512), 0, st, q, nchunks);
+        else if (rw_dbg == 2) MI_LAUNCH((rwconv_gather_kernel<3, 5, true, 0, false, 2>), g, dim3(512), 0, st, q, nchunks);
         else MI_LAUNCH((rwconv_gather_kernel<3, 5, true, 0, false, 3>), g, dim3(512), 0, st, q, nchunks);
     } else if (KH == 4 && ck == 2) {
         const dim3 t_(512);
@@ -714,12 +701,6 @@ int mi_try_rwconv_gather(hipStream_t st, int dtype, const void* a, const void* w
     return rc == MI_OK ? 1 : rc;
 }
 
-int mi_rwconv_blocks(int set) {                          // mi_set_tuning key 16: persistent blocks per XCD of the register-weight kernels, 0 = one (k = 4 gather: three) per CU
-    mi_rwconv_mode(-1);
-    const int prev = g_rwconv_blocks;
-    if (set >= 0) g_rwconv_blocks = set;
-    return prev;
-}
 // Fragment-ordered weights announced for the next call of mi_conv2d_nhwc_fwd[_bits], mi_deconv2d_nhwc_fwd[_bits], mi_deconv2d_nhwc_dgrad[_bits] or mi_conv2d_enc12_fwd on
 // this thread: the same kernel in the order the register-weight prologue loads it (mi_ares_pack_weights forms 3 - 6).  Each of those entries takes it first thing, so the
 // announcement never outlives that call, and passes it down explicitly to the launch that can use it.
@@ -734,23 +715,15 @@ const void* mi_rwconv_take_wfrag() {
     mi_tl_rc_wfrag = nullptr;
     return wf;
 }
-int g_rwconv_conv = -1;                                  // mi_set_tuning key 15 / MI355_RWCONV_CONV: 0 off, 1 k = 5 only, 2 also k = 4, 3 also the 64 -> 128 channel shape (default)
-int mi_rwconv_conv_mode(int set) {                       // set < 0: query
-    if (g_rwconv_conv < 0) { const char* e = getenv("MI355_RWCONV_CONV"); g_rwconv_conv = e ? atoi(e) : 3; if (g_rwconv_conv < 0 || g_rwconv_conv > 3) g_rwconv_conv = 3; }
-    const int prev = g_rwconv_conv;
-    if (set >= 0) g_rwconv_conv = set > 3 ? 3 : set;
-    return prev;
-}
 
 // conv-form layer on the register-weight kernel: x [B,IH,IW,C] bf16, w [N][ldb] bf16 (K-contiguous, k = (kh KW + kw) C + c), out / mask [B,OH,OW,N]
 // bf16, (C, N) = (32, 64) with k = 4 | 5 or (64, 128) with k = 4.  Same contract as try_tapconv: 1 launched, 0 not eligible, < 0 error.
 // mi_set_tuning key 15 / MI355_RWCONV_CONV: 0 off, 1 the k = 5 layer, 2 also 32 -> 64 channels k = 4, 3 also 64 -> 128 channels (default).
 int mi_try_rwconv_conv(hipStream_t st, int dtype, const void* a, const void* w, int B, int IH, int IW, int C, int OH, int OW, int N,
                        int KH, int KW, int ldb, void* out, const float* bias, const void* mask, int relu, const void* wfrag) {
-    const int on = mi_rwconv_conv_mode(-1);
-    mi_rwconv_mode(-1);
+    const int on = knob(K_RWCONV_CONV), rw_mode = knob(K_RWCONV), rw_blocks = knob(K_RWCONV_BLOCKS);
     const int ck = (C == 64 && N == 128) ? 2 : 1;
-    if (!on || g_rwconv_mode == 0 || dtype != MI_BF16 || C != 32 * ck || N != 64 * ck || KH != KW) return 0;
+    if (!on || rw_mode == 0 || dtype != MI_BF16 || C != 32 * ck || N != 64 * ck || KH != KW) return 0;
     if (!((KH == 5 && ck == 1) || (KH == 4 && ck == 1 && on >= 2) || (KH == 4 && ck == 2 && on >= 3))) return 0;
     if (OH != (IH - KH) / 2 + 1 || OW != (IW - KW) / 2 + 1 || (ldb % 8) != 0 || ldb < KH * KW * C) return 0;
     if ((((uintptr_t)a) | ((uintptr_t)w) | ((uintptr_t)out) | ((uintptr_t)mask)) & 15) return 0;
@@ -761,7 +734,7 @@ int mi_try_rwconv_conv(hipStream_t st, int dtype, const void* a, const void* w, 
     if (halo > (ck == 2 ? RcCfg<4, 2>::MAXHALO : KH == 4 ? RcCfg<4>::MAXHALO : RcCfg<5>::MAXHALO) || q.GW <= 16) return 0;     // (GW > 16: the incremental slot walk of the staging)
     const long long MP = (long long)B * q.GH * q.GW, a_bytes = (long long)B * IH * IW * C * 2, o_bytes = (long long)B * OH * OW * N * 2;
     if (MP >= (1ll << 30) || a_bytes <= 0 || a_bytes >= (long long)G2_OOB || o_bytes >= (long long)G2_OOB) return 0;
-    if (g_rwconv_mode == 1 && MP < 75000) return 0;
+    if (rw_mode == 1 && MP < 75000) return 0;
     q.a = a; q.a_bytes = (uint32_t)a_bytes; q.b = w; q.b_bytes = (uint32_t)o_bytes; q.ldb = ldb;
     q.B = B; q.IH = IH; q.IW = IW; q.C = C; q.OH = OH; q.OW = OW; q.N = N; q.KH = KH; q.KW = KW; q.MP = (int)MP;
     q.KC = 4 * C; q.NE = N;
@@ -772,7 +745,7 @@ int mi_try_rwconv_conv(hipStream_t st, int dtype, const void* a, const void* w, 
     const int nchunks = (int)((MP + bmt - 1) / bmt);
     static int n_cu = 0;
     if (!n_cu) { int dev = 0; hipDeviceProp_t pr; n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256; }
-    int nblk = g_rwconv_blocks > 0 ? 8 * g_rwconv_blocks : n_cu;       // one persistent block per CU; each walks a contiguous range of chunks
+    int nblk = rw_blocks > 0 ? 8 * rw_blocks : n_cu;       // one persistent block per CU; each walks a contiguous range of chunks
     if (nblk > nchunks) nblk = nchunks;
     const dim3 g((unsigned)nblk), t(256);
 #define RC_LAUNCH(KH_, CK_) do { \

@@ -12,6 +12,7 @@
 #include "mi355_carla.h"
 #include "ppo_fused.hpp"
 
+using namespace mi;
 namespace {
 
 constexpr int NCONV = 4;
@@ -156,11 +157,8 @@ int pick_split(int M, int N, int K, int bk) {
     const int tiles = ((M + 127) / 128) * (N <= 64 ? 1 : (N + 127) / 128);
     int ns = 256 / (tiles > 0 ? tiles : 1);
     if (ns < 1) ns = 1;
-    // MI355_LATENT_SPLIT=<n>: at most n K slices in the latent layers' split-K sums.  16 since late round 5 (32 before): half the slab traffic between the tall-K kernels and the
-    // reparameterisation kernels that sum them, one block per CU instead of two; step 0.8225 -> 0.8179 / 0.8153 -> 0.8125 ms on two boxes (12: the same, 8 and 24: slower)
-    static int ns_cap = -1;
-    if (ns_cap < 0) { const char* ev = getenv("MI355_LATENT_SPLIT"); ns_cap = ev ? atoi(ev) : 16; if (ns_cap < 1 || ns_cap > 32) ns_cap = 16; }
-    if (ns > ns_cap) ns = ns_cap;
+    // MI355_LATENT_SPLIT=<n>: at most n K slices in the latent layers' split-K sums (16; the measurements: K_LATENT_SPLIT, tuning.hip)
+    if (ns > knob(K_LATENT_SPLIT)) ns = knob(K_LATENT_SPLIT);
     while (ns > 1) {                    // every slab must own at least one K block
         int len = (K + ns - 1) / ns; len = (len + bk - 1) / bk * bk;
         if ((long long)len * (ns - 1) < K) break;
@@ -179,8 +177,7 @@ void make_workspace(VaeEngine& e) {
     const long long B = d.max_batch;
     long long o = 0;
     Workspace& W = e.W;
-    const char* ge = getenv("MI355_DEBUG_GUARDS");
-    const bool guards = ge && ge[0] == '1';
+    const bool guards = knob_env_now(K_DEBUG_GUARDS) != 0;
     W.n_guards = 0;
     auto add = [&](long long bytes) {
         long long r = o; o += (bytes + 255) / 256 * 256;
@@ -274,12 +271,6 @@ bool rc_small_frag_ok(const VaeEngine* e) {
     return g.c[1] == 32 && g.c[2] == 64 && g.dc[2] == 64 && g.dc[3] == 32 && DEC_K[2] == 5;
 }
 
-bool relu_bits_enabled() {                             // MI355_RELU_BITS=0: the input gradients read the activation tensors as ReluGrad masks (A/B runs)
-    static int on = -1;
-    if (on < 0) { const char* ev = getenv("MI355_RELU_BITS"); on = (ev && ev[0] == '0') ? 0 : 1; }
-    return on != 0;
-}
-
 // encoder: frames (fp32, optional gather) -> act[1..4] -> heads slabs -> mean/logvar/z/kl.  bwd: a backward pass follows (a training forward on an engine with gradients)
 int run_encoder(VaeEngine* e, void* st, const void* frames, int frames_u8, const int* idx, int B, const float* eps, int sample, int bwd = 0) {
     const MiVaeDesc& d = e->d; const Geom& g = e->g;
@@ -291,7 +282,7 @@ int run_encoder(VaeEngine* e, void* st, const void* frames, int frames_u8, const
             // round 5: conv1 + conv2 as ONE launch (enc12_tile.hpp): conv1's activation stays in LDS for conv2.  In front of a backward pass it is also written (with its ReLU
             // bit words), never read back here; any other forward pass runs the kernel's inference form, which stores conv2's output alone.
             // (per-op timing keeps the two layer launches -- they are what the profile names -- where the workspace has conv1's activation; otherwise it times the one launch)
-            const bool bits12 = bwd && relu_bits_enabled();
+            const bool bits12 = bwd && knob(K_RELU_BITS);
             int launched = 0;
             if (e->ares_ok && rc_small_frag_ok(e)) CK(mi_rwconv_next_weights_fragment_ordered(e->at(e->W.wfrag[9])));      // conv2's kernel in fragment order
             TOP(e, st, OP_CONV_FWD + 1, mi_conv2d_enc12_fwd(st, d.dtype, frames, frames_u8 ? 2 : 1, idx, B, g.ih[0], g.iw[0], e->wtptr(0), e->bptr(1), e->wtptr(2), e->bptr(3),
@@ -302,7 +293,7 @@ int run_encoder(VaeEngine* e, void* st, const void* frames, int frames_u8, const
                                            "switched off after mi_vae_create) and this inference engine's workspace has no conv1 activation for the two-launch form");
         }
         // conv1 (training pass, bf16): also writes the ReLU bit words conv2's input gradient reads instead of the 101 MB activation tensor
-        const bool bits = i == 0 && bwd && relu_bits_enabled() && d.dtype == MI_BF16 && g.c[1] == 32;
+        const bool bits = i == 0 && bwd && knob(K_RELU_BITS) && d.dtype == MI_BF16 && g.c[1] == 32;
         if (i == 3 && e->ares_ok) {                           // conv4: activation-resident kernel (frames of the group in LDS, fragment-ordered weights streamed)
             int launched = 0;
             TOP(e, st, OP_CONV_FWD + i, mi_ares_conv(st, d.dtype, 0, x, B, e->at(e->W.wfrag[0]), e->bptr(7), 1, nullptr, e->at(e->W.act[4]), &launched));
@@ -331,7 +322,7 @@ int run_decoder(VaeEngine* e, void* st, int B, int last = 4, int want_bits = 0) 
     e->bits3_ok = 0;
     TOP(e, st, OP_DENSE1_FWD, mi_gemm_bias_act(st, d.dtype, e->at(e->W.z), B, d.z_dim, e->wtptr(10), 1, g.flat, e->bptr(11), 0, nullptr, e->at(e->W.dec[0]), 0, 1));
     for (int i = 0; i < last; ++i) {
-        const bool bits = i == 2 && want_bits && relu_bits_enabled() && d.dtype == MI_BF16 && g.dc[3] == 32;   // deconv3: ReLU bit words for deconv4's input gradient
+        const bool bits = i == 2 && want_bits && knob(K_RELU_BITS) && d.dtype == MI_BF16 && g.dc[3] == 32;   // deconv3: ReLU bit words for deconv4's input gradient
         if (i == 0 && e->ares_ok) {
             int launched = 0;
             TOP(e, st, OP_DECONV_FWD + i, mi_ares_conv(st, d.dtype, 1, e->at(e->W.dec[0]), B, e->at(e->W.wfrag[2]), e->bptr(13), 1, nullptr, e->at(e->W.dec[1]), &launched));
@@ -364,9 +355,7 @@ int kernel_table(const VaeEngine* e, long long* off, int* K, int* N) {
 // the activation-resident kernels take this model (bf16 storage, the reference's geometry); *mid: also the mid-layer gather form (conv3's input gradient, deconv2 forward)
 bool ares_eligible(const VaeEngine* e, bool* mid) {
     const Geom& g = e->g; const MiVaeDesc& d = e->d;
-    static int ares_on = -1;
-    if (ares_on < 0) { const char* ev = getenv("MI355_ARES"); ares_on = (ev && ev[0] == '0') ? 0 : 1; }
-    const bool ok = ares_on && d.dtype == MI_BF16 && g.ih[3] == 8 && g.iw[3] == 18 && g.c[3] == 128 && g.c[4] == 256 && g.dh[0] == 3 && g.dw[0] == 8 && g.dc[0] == 256 && g.dc[1] == 128 && DEC_K[0] == 4;
+    const bool ok = knob(K_ARES) && d.dtype == MI_BF16 && g.ih[3] == 8 && g.iw[3] == 18 && g.c[3] == 128 && g.c[4] == 256 && g.dh[0] == 3 && g.dw[0] == 8 && g.dc[0] == 256 && g.dc[1] == 128 && DEC_K[0] == 4;
     if (mid) *mid = ok && g.c[2] == 64 && g.c[3] == 128 && g.dc[1] == 128 && g.dc[2] == 64 && DEC_K[1] == 4;
     return ok;
 }
@@ -528,9 +517,7 @@ int mi_vae_forward(void* h, void* stream, const void* src, const void* tgt, int 
     // decoder tail.  Training pass, bf16, rgb target: ONE launch computes deconv4, the loss, deconv4's filter gradient (straight into the gradient
     // buffer) and the gradient of deconv3's output (dectail_tile.hpp): dlogits never exist in HBM, deconv3's output is read once instead of three
     // times, and the backward pass starts at deconv3.  Otherwise: deconv4 with the loss fused into its epilogue (dlogits written), or the plain ops.
-    static int tail_on = -1;
-    if (tail_on < 0) { const char* ev = getenv("MI355_DECTAIL"); tail_on = (ev && ev[0] == '0') ? 0 : 1; }
-    const bool tail_try = tail_on && want_grad && e->grads && d.dtype == MI_BF16 && d.ct == 3 && g.dc[3] == 32 && DEC_K[3] == 4 && e->W.scratch_bytes > 0;
+    const bool tail_try = knob(K_DECTAIL) && want_grad && e->grads && d.dtype == MI_BF16 && d.ct == 3 && g.dc[3] == 32 && DEC_K[3] == 4 && e->W.scratch_bytes > 0;
     e->tail_fused = 0;
     CK(run_decoder(e, stream, B, 3, want_grad && !tail_try));
     int nblk = 0;
@@ -587,8 +574,7 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
     // filter gradients run on a second stream, each one released by an event recorded on the caller's stream when its operand is ready.
     // Every kernel on this path fills a whole CU (150 KB of LDS), so the gain is in the tails: a 342-block launch leaves 2/3 of the
     // chip idle in its second round, which the neighbouring launch now fills.  MI355_BWD_STREAMS=0 serialises everything again.
-    static int two_streams = -1;
-    if (two_streams < 0) { const char* ev = getenv("MI355_BWD_STREAMS"); two_streams = (ev && ev[0] == '0') ? 0 : 1; }
+    const int two_streams = knob(K_BWD_STREAMS);
     if (two_streams && !e->side_ok) {
         if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&e->ev_ready, hipEventDisableTiming) == hipSuccess &&
@@ -673,10 +659,8 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
     // and inside the 1.25 e_emul + 2e-3 gradient criterion of the bf16 engine with bench.py's parity.bf16.grad_worst = 0.79 (the operands were bf16 to begin
     // with: their own rounding contributes 3e-3 ... 6e-2 of the tensor max).  The layer-op entry points keep exact fp32 slabs.
     // Measured, three interleaved pairs on one box: 0.966 -> 0.943 ms per step.  MI355_SLAB_BF16=0: fp32 slabs.
-    static int slab16 = -1;
-    if (slab16 < 0) { const char* ev = getenv("MI355_SLAB_BF16"); slab16 = (ev && ev[0] == '0') ? 0 : 1; }
     struct SlabGuard { int prev; bool on; ~SlabGuard() { if (on) mi_tapwgrad_slab_bf16(prev); } } slab_guard{-1, false};
-    if (slab16 && d.dtype == MI_BF16) { slab_guard.prev = mi_tapwgrad_slab_bf16(1); slab_guard.on = true; }
+    if (knob(K_SLAB_BF16) && d.dtype == MI_BF16) { slab_guard.prev = mi_tapwgrad_slab_bf16(1); slab_guard.on = true; }
     // Full two-stream backward (round 3): the latent-side filter / bias gradients (dense1, heads: ~60 us of the filter-gradient stream, which is the longer one) are
     // issued on the caller's stream at the very END of the pass, where that stream would otherwise wait ~100 us for the other one; their operands (gdec0, z, dheads,
     // act4) stay intact until then and no event is needed for them.  The parts and the one-stream pass issue them in place on the filter-gradient stream.
@@ -925,8 +909,7 @@ int mi_vae_train_step_dp(void* h, void* comm, void* stream, const void* src, con
     // data-parallel step without its collectives ran 0.863 ms against the single-rank step's 0.744).  Nothing the later parts issue on the caller's stream reads what the
     // filter-gradient stream produces; the part's bucket is complete when THAT stream has also seen the caller's work of the part, so the all-reduce is chained to it.
     // MI355_DP_OPEN_JOIN=0: the joins of round 5.
-    static int open_join = -1;
-    if (open_join < 0) { const char* ev = getenv("MI355_DP_OPEN_JOIN"); open_join = (ev && ev[0] == '0') ? 0 : 1; }
+    const int open_join = knob(K_DP_OPEN_JOIN);
     int rc = MI_OK;
     for (int i = 0; i < 3 && rc == MI_OK; ++i) {
         e->dp_open_join = (open_join && i < 2) ? 1 : 0; e->dp_side_ready = 0;
