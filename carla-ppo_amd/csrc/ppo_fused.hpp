@@ -51,3 +51,7 @@ int mi_rollout_policy_batch(hipStream_t st, const mi::PpoFusedParams& q, const f
 struct MiRolloutRec { const int* table_rows; long long n_table_rows; float* states; float* actions; float* values; };
 int mi_rollout_policy_batch_rec(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n, float* out,
                                 const MiRolloutRec& rec);
+// the value-only form (mi_rollout_value_batch_rec): the value trunk and the value head alone; out [n], and the value of call row e is also stored as final_values[table_rows[e]]
+struct MiRolloutValueRec { const int* table_rows; long long n_table_rows; float* final_values; };
+int mi_rollout_value_batch(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, int n, float* out,
+                           const MiRolloutValueRec& rec);

@@ -137,12 +137,14 @@ __device__ __forceinline__ double gae_step(double& carry, double delta, double g
 // One wave, L steps: v = the fp32 value slots (they widen to fp64 exactly), r / d = fp64 rewards / terminals of the first step, a = L doubles of LDS that hold the raw
 // advantages on return.  The deltas do not depend on each other: all lanes form them; the recurrence is serial and lane 0 walks it in the dense kernel's order.
 // SKIP_BEHIND_DONE: behind a terminal LAST step the bootstrap value is 0.0 and slot L is not read; without it slot L is read and the terminal flag masks it (the two
-// differ in the sign of a zero and in what a NaN in slot L does).
-template <bool SKIP_BEHIND_DONE>
-__device__ __forceinline__ void finish_gae(double* a, const float* v, const double* r, const double* d, int L, double gamma, double gl, int lane) {
+// differ in the sign of a zero and in what a NaN in slot L does).  FINAL with v_final != NULL (a TRUNCATED segment: the episode stopped without being terminal): the
+// value behind the last step is *v_final and slot L is not read; the terminal flag of the last step masks it as it masks slot L.
+template <bool SKIP_BEHIND_DONE, bool FINAL = false>
+__device__ __forceinline__ void finish_gae(double* a, const float* v, const double* r, const double* d, int L, double gamma, double gl, int lane, const float* v_final = nullptr) {
     for (int t = lane; t < L; t += WAVE) {
         double vnext = 0.0;
-        if (!SKIP_BEHIND_DONE || t < L - 1 || d[t] == 0.0) vnext = (double)v[t + 1];
+        if (FINAL && v_final && t == L - 1) vnext = (double)v_final[0];
+        else if (!SKIP_BEHIND_DONE || t < L - 1 || d[t] == 0.0) vnext = (double)v[t + 1];
         a[t] = gae_delta(r[t], d[t], vnext, (double)v[t], gamma);
     }
     __syncthreads();
@@ -276,6 +278,38 @@ __global__ __launch_bounds__(64) void rollout_finish_seg_kernel(const float* __r
     }
     const float* v = values + tab;
     finish_gae<true>(a, v, rewards + flat, terminals + flat, L, gamma, gl, lane);
+    const double s = finish_returns<NORM != 0>(a, v, L, lane, tab, flat, tab_returns, returns, adv_raw);
+    if (NORM) {
+        if (lane == 0) part[seg] = s;
+        return;
+    }
+    finish_normalize(a, s, L, lane, tab, flat, tab_adv, adv_norm);
+}
+
+// mi_rollout_finish_segments_boot: rollout_finish_seg_kernel with a per-segment bootstrap source.  seg_boot[seg] == 0: that kernel's rule.  seg_boot[seg] != 0 (the
+// segment was TRUNCATED: its episode stopped without being terminal and the lane went on with a reset observation): the value behind the last step is
+// final_values[row of the last step] -- the value of the episode's final observation, which is no step of the lane and so has no slot in `values` -- and the slot
+// behind the segment, the next episode's first value or a stale one, is not read.  The same helpers: a truncated segment comes out bit for bit as the dense kernels
+// give it on [v_0 .. v_{L-1}, v_final].  A kernel of its own, so that the one above stays the code it was.  NORM = 1: as above, the same kernels follow.
+template <int NORM>
+__global__ __launch_bounds__(64) void rollout_finish_seg_boot_kernel(const float* __restrict__ values, const float* __restrict__ final_values, const double* __restrict__ rewards,
+                                                                     const double* __restrict__ terminals, const int* __restrict__ seg_row, const int* __restrict__ seg_len,
+                                                                     const int* __restrict__ seg_boot, int num_envs, int T, double gamma, double gl,
+                                                                     float* __restrict__ tab_returns, float* __restrict__ tab_adv, double* __restrict__ adv_raw,
+                                                                     double* __restrict__ returns, double* __restrict__ adv_norm, double* __restrict__ part) {
+    extern __shared__ double seg_boot_a[];                 // T doubles
+    double* a = seg_boot_a;
+    const int seg = blockIdx.x, lane = threadIdx.x;
+    const int L = seg_len[seg];
+    const long long tab = seg_row[seg];
+    long long flat;
+    if (!rollout_seg_decode((int)tab, L, num_envs, T, flat)) {
+        if (NORM && lane == 0) part[seg] = 0.0;
+        return;
+    }
+    const float* v = values + tab;
+    const float* v_final = seg_boot[seg] != 0 ? final_values + tab + (L - 1) : nullptr;      // (inside the table: the segment lies inside one lane's step slots)
+    finish_gae<true, true>(a, v, rewards + flat, terminals + flat, L, gamma, gl, lane, v_final);
     const double s = finish_returns<NORM != 0>(a, v, L, lane, tab, flat, tab_returns, returns, adv_raw);
     if (NORM) {
         if (lane == 0) part[seg] = s;
@@ -418,34 +452,60 @@ int mi_rollout_finish(void* stream, const float* tab_values, const double* rewar
 // scratch of normalize = 1: per-segment sums | per-segment sums of squared deviations | mean, std
 long long mi_rollout_finish_segments_scratch_doubles(int n_seg) { return n_seg < 1 ? -1 : 2LL * n_seg + 2; }
 
-// mi_rollout_finish with segment descriptors in place of len: seg_row / seg_len int32 [n_seg] (device)
-int mi_rollout_finish_segments(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* seg_row, const int* seg_len, int n_seg,
-                               int num_envs, int T, double gamma, double lam, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw,
-                               double* returns, double* adv_norm) {
-    if (!tab_values || !rewards || !terminals || !seg_row || !seg_len || !tab_returns || !tab_advantages)
-        return mi_fail(MI_ERR_ARG, "mi_rollout_finish_segments: missing buffers");
-    if (n_seg < 1 || num_envs < 1 || T < 1) return mi_fail(MI_ERR_ARG, "mi_rollout_finish_segments: empty input (n_seg >= 1, num_envs >= 1, T >= 1)");
-    if (T > MI_ROLLOUT_MAX_HORIZON) return mi_fail(MI_ERR_ARG, "mi_rollout_finish_segments: the horizon exceeds MI_ROLLOUT_MAX_HORIZON");
-    if (normalize != 0 && normalize != 1) return mi_fail(MI_ERR_ARG, "mi_rollout_finish_segments: normalize is 0 (per segment) or 1 (per batch)");
-    if (normalize == 1 && (!scratch || !adv_raw)) return mi_fail(MI_ERR_ARG, "mi_rollout_finish_segments: normalize = 1 needs scratch and adv_raw (missing buffers)");
+// mi_rollout_finish with segment descriptors in place of len: seg_row / seg_len int32 [n_seg] (device).  One body for mi_rollout_finish_segments (boot = false: its
+// kernel, its launches) and mi_rollout_finish_segments_boot (the first kernel takes the per-segment bootstrap source; the batch normalisation behind it is the same).
+#define SEG_FAIL(text) return mi_fail(MI_ERR_ARG, boot ? "mi_rollout_finish_segments_boot: " text : "mi_rollout_finish_segments: " text)
+static int finish_segments(bool boot, void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* seg_row, const int* seg_len, int n_seg,
+                           int num_envs, int T, double gamma, double lam, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw,
+                           double* returns, double* adv_norm, const float* tab_final_values, const int* seg_boot) {
+    if (!tab_values || !rewards || !terminals || !seg_row || !seg_len || !tab_returns || !tab_advantages) SEG_FAIL("missing buffers");
+    if (boot && (!tab_final_values || !seg_boot)) SEG_FAIL("missing buffers (tab_final_values, seg_boot)");
+    if (n_seg < 1 || num_envs < 1 || T < 1) SEG_FAIL("empty input (n_seg >= 1, num_envs >= 1, T >= 1)");
+    if (T > MI_ROLLOUT_MAX_HORIZON) SEG_FAIL("the horizon exceeds MI_ROLLOUT_MAX_HORIZON");
+    if (normalize != 0 && normalize != 1) SEG_FAIL("normalize is 0 (per segment) or 1 (per batch)");
+    if (normalize == 1 && (!scratch || !adv_raw)) SEG_FAIL("normalize = 1 needs scratch and adv_raw (missing buffers)");
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)T * sizeof(double);
     const double gl = gamma * lam;
-    if (normalize == 0) {
+    double* part = normalize ? scratch : nullptr;
+    if (boot) {
+        if (normalize == 0)
+            hipLaunchKernelGGL(rollout_finish_seg_boot_kernel<0>, dim3(n_seg), dim3(64), lds, st, tab_values, tab_final_values, rewards, terminals, seg_row, seg_len, seg_boot,
+                               num_envs, T, gamma, gl, tab_returns, tab_advantages, adv_raw, returns, adv_norm, part);
+        else
+            hipLaunchKernelGGL(rollout_finish_seg_boot_kernel<1>, dim3(n_seg), dim3(64), lds, st, tab_values, tab_final_values, rewards, terminals, seg_row, seg_len, seg_boot,
+                               num_envs, T, gamma, gl, tab_returns, tab_advantages, adv_raw, returns, adv_norm, part);
+    } else if (normalize == 0) {
         hipLaunchKernelGGL(rollout_finish_seg_kernel<0>, dim3(n_seg), dim3(64), lds, st, tab_values, rewards, terminals, seg_row, seg_len, num_envs, T, gamma, gl, tab_returns,
-                           tab_advantages, adv_raw, returns, adv_norm, (double*)nullptr);
-        return mi_check_launch("rollout_finish_seg");
+                           tab_advantages, adv_raw, returns, adv_norm, part);
+    } else {
+        hipLaunchKernelGGL(rollout_finish_seg_kernel<1>, dim3(n_seg), dim3(64), lds, st, tab_values, rewards, terminals, seg_row, seg_len, num_envs, T, gamma, gl, tab_returns,
+                           tab_advantages, adv_raw, returns, adv_norm, part);
     }
-    double* part = scratch;
+    if (normalize == 0) return mi_check_launch(boot ? "rollout_finish_seg_boot" : "rollout_finish_seg");
     double* part2 = scratch + n_seg;
     double* stat = scratch + 2LL * n_seg;
-    hipLaunchKernelGGL(rollout_finish_seg_kernel<1>, dim3(n_seg), dim3(64), lds, st, tab_values, rewards, terminals, seg_row, seg_len, num_envs, T, gamma, gl, tab_returns,
-                       tab_advantages, adv_raw, returns, adv_norm, part);
     hipLaunchKernelGGL(rollout_seg_reduce_kernel<0>, dim3(1), dim3(64), 0, st, part, seg_row, seg_len, n_seg, num_envs, T, stat);
     hipLaunchKernelGGL(rollout_seg_norm_kernel<0>, dim3(n_seg), dim3(64), 0, st, adv_raw, seg_row, seg_len, num_envs, T, stat, part2, tab_advantages, adv_norm);
     hipLaunchKernelGGL(rollout_seg_reduce_kernel<1>, dim3(1), dim3(64), 0, st, part2, seg_row, seg_len, n_seg, num_envs, T, stat);
     hipLaunchKernelGGL(rollout_seg_norm_kernel<1>, dim3(n_seg), dim3(64), 0, st, adv_raw, seg_row, seg_len, num_envs, T, stat, part2, tab_advantages, adv_norm);
-    return mi_check_launch("rollout_finish_seg (batch normalisation)");
+    return mi_check_launch(boot ? "rollout_finish_seg_boot (batch normalisation)" : "rollout_finish_seg (batch normalisation)");
+}
+#undef SEG_FAIL
+
+int mi_rollout_finish_segments(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* seg_row, const int* seg_len, int n_seg,
+                               int num_envs, int T, double gamma, double lam, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw,
+                               double* returns, double* adv_norm) {
+    return finish_segments(false, stream, tab_values, rewards, terminals, seg_row, seg_len, n_seg, num_envs, T, gamma, lam, normalize, scratch, tab_returns, tab_advantages,
+                           adv_raw, returns, adv_norm, nullptr, nullptr);
+}
+
+// seg_boot int32 [n_seg] (device): != 0 = the segment was truncated and bootstraps from tab_final_values[row of its last step] (fp32 [num_envs (T + 1)])
+int mi_rollout_finish_segments_boot(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* seg_row, const int* seg_len, int n_seg,
+                                    int num_envs, int T, double gamma, double lam, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw,
+                                    double* returns, double* adv_norm, const float* tab_final_values, const int* seg_boot) {
+    return finish_segments(true, stream, tab_values, rewards, terminals, seg_row, seg_len, n_seg, num_envs, T, gamma, lam, normalize, scratch, tab_returns, tab_advantages,
+                           adv_raw, returns, adv_norm, tab_final_values, seg_boot);
 }
 
 }  // extern "C"

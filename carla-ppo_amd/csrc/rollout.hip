@@ -375,6 +375,37 @@ __global__ __launch_bounds__(256) void rollout_head_rec_kernel(const RollHeadPar
     roll_head<NA, true>(q, red, n * q.H2, rec);
 }
 
+// the value-only heads (mi_rollout_value_batch_rec): the value of roll_head for environment e = blockIdx.x -- the same terms in the same order: thread-strided partial
+// sums over H2, the wave butterfly, the four waves as (w0 + w1) + (w2 + w3), + bias -- from the VALUE trunk's raw layer-2 sums alone; nothing of the policy net is read.
+// The value goes to out[e] and, as a plain vector store, to final_values[table_rows[e]]; a row outside [0, n_table_rows) records nothing.
+struct RollValueParams {
+    const float *h2raw, *b2v, *Wv, *bv;                   // h2raw: row 0 of the value trunk's raw sums [n][H2]
+    int H2;
+    const int* table_rows; long long n_table_rows;
+    float *out, *final_values;
+};
+
+__global__ __launch_bounds__(256) void rollout_value_rec_kernel(const RollValueParams q) {
+    __shared__ float red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, H2 = q.H2;
+    const long long e = blockIdx.x;
+    const float* h2 = q.h2raw + e * H2;
+    float av = 0.f;
+    for (int j = tid; j < H2; j += 256) {
+        const float hv = fmaxf(h2[j] + q.b2v[j], 0.f);
+        av += hv * q.Wv[j];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) av += __shfl_xor(av, o, 64);
+    if (lane == 0) red[wave] = av;
+    __syncthreads();
+    if (tid != 0) return;
+    const float v = ((red[0] + red[1]) + (red[2] + red[3])) + q.bv[0];
+    q.out[e] = v;
+    const long long r = q.table_rows[e];
+    if (r >= 0 && r < q.n_table_rows) q.final_values[r] = v;
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -500,16 +531,14 @@ int mi_rollout_conv_batch(hipStream_t st, const float* x, const float* x_bias, i
     return mi_check_launch("rollout_conv_batch_kernel");
 }
 
-// trunks and heads of n environments: mean_raw [n][z_dim], measurements [n][din - z_dim], noise [n][A], out [n][A + 1 + z_dim]; raw sums in q.h1 / q.h2 as [net][n][H]
-static int policy_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
-                        const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec) {
+// the two trunk layers of n environments as batched split-K stages: rows run over the environments, raw sums in q.h1 / q.h2 as [net][n][H]; grid.y = 2 nets x row tiles
+static int fill_trunks_batch(RollConvBatchParams& l1, dim3& g1, RollConvBatchParams& l2, dim3& g2, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim,
+                             const float* measurements, int n) {
     if (q.A < 1 || q.A > 8) return mi_fail(MI_ERR_ARG, "rollout step: 1 <= num_actions <= 8");
     if (q.H1 % 4 != 0) return mi_fail(MI_ERR_SHAPE, "rollout step: hidden sizes must be multiples of 4");
     if ((long long)n * (q.H1 > q.H2 ? q.H1 : q.H2) * 4 >= 0x40000000ll || (long long)n * q.din * 4 >= 0x40000000ll) return mi_fail(MI_ERR_SHAPE, "rollout step: operand beyond 1 GiB");
-    RollConvParams b1, b2; dim3 g1, g2; RollHeadParams h;
+    RollConvParams b1, b2;
     fill_trunks(b1, g1, b2, g2, q, mean_raw, mean_bias, z_dim, measurements);
-    fill_head(h, q, mean_raw, mean_bias, z_dim, noise, greedy, out);
-    RollConvBatchParams l1, l2;
     const unsigned un = (unsigned)n;
     static_cast<RollConvParams&>(l1) = b1; static_cast<RollConvParams&>(l2) = b2;
     l1.OHW = l2.OHW = 1; l1.img_stride = l2.img_stride = 0; l1.row_tiles = l2.row_tiles = (n + 31) / 32;
@@ -517,6 +546,16 @@ static int policy_batch(hipStream_t st, const PpoFusedParams& q, const float* me
     l1.x_row = (unsigned)z_dim; l1.t_row = (unsigned)(q.din - z_dim); l1.x_bytes *= un; l1.tail_bytes *= un; l1.out_bytes *= un; l1.out_net = (long long)n * q.H1;
     l2.x_row = (unsigned)q.H1; l2.t_row = 0; l2.x_bytes *= un; l2.out_bytes *= un; l2.x_net = (long long)n * q.H1; l2.out_net = (long long)n * q.H2;
     g1.y = g2.y = 2 * l1.row_tiles;
+    return MI_OK;
+}
+
+// trunks and heads of n environments: mean_raw [n][z_dim], measurements [n][din - z_dim], noise [n][A], out [n][A + 1 + z_dim]; raw sums in q.h1 / q.h2 as [net][n][H]
+static int policy_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
+                        const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec) {
+    RollConvBatchParams l1, l2; dim3 g1, g2; RollHeadParams h;
+    const int rc = fill_trunks_batch(l1, g1, l2, g2, q, mean_raw, mean_bias, z_dim, measurements, n);
+    if (rc != MI_OK) return rc;
+    fill_head(h, q, mean_raw, mean_bias, z_dim, noise, greedy, out);
     launch_conv_batch(st, g1, l1);
     launch_conv_batch(st, g2, l2);
     if (rec) {
@@ -528,6 +567,23 @@ static int policy_batch(hipStream_t st, const PpoFusedParams& q, const float* me
     if (q.A <= 2) hipLaunchKernelGGL(rollout_head_batch_kernel<2>, dim3(n), dim3(256), 0, st, h, n);
     else hipLaunchKernelGGL(rollout_head_batch_kernel<8>, dim3(n), dim3(256), 0, st, h, n);
     return mi_check_launch("rollout_policy_batch");
+}
+
+// the VALUE trunk alone and the value-only heads: the batched trunk stages with their operands moved to net 1 and half the grid (the policy net's half of q.h1 / q.h2
+// is neither cleared, written nor read), out [n] = the values, also left in rec.final_values[rec.table_rows[e]]
+int mi_rollout_value_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, int n, float* out,
+                           const MiRolloutValueRec& rec) {
+    RollConvBatchParams l1, l2; dim3 g1, g2;
+    const int rc = fill_trunks_batch(l1, g1, l2, g2, q, mean_raw, mean_bias, z_dim, measurements, n);
+    if (rc != MI_OK) return rc;
+    l1.x += l1.x_net; l1.x_bias += l1.xb_net; l1.w += l1.w_net; l1.out += l1.out_net;      // (layer 1's x / bias strides are 0: both nets read the one state)
+    l2.x += l2.x_net; l2.x_bias += l2.xb_net; l2.w += l2.w_net; l2.out += l2.out_net;
+    g1.y = l1.row_tiles; g2.y = l2.row_tiles;                                              // blockIdx.y / row_tiles = 0: the kernels' "net 0" is the value net
+    launch_conv_batch(st, g1, l1);
+    launch_conv_batch(st, g2, l2);
+    const RollValueParams v = {l2.out, q.theta + q.off[10], q.theta + q.off[11], q.theta + q.off[12], q.H2, rec.table_rows, rec.n_table_rows, out, rec.final_values};
+    hipLaunchKernelGGL(rollout_value_rec_kernel, dim3(n), dim3(256), 0, st, v);
+    return mi_check_launch("rollout_value_batch");
 }
 
 int mi_rollout_policy_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,

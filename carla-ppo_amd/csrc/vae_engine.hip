@@ -976,16 +976,19 @@ long long mi_rollout_batch_workspace_bytes(void* vae_h, void* ppo_h, int n_envs)
     return roll_env_floats(e) * 4 * n_envs;
 }
 
-// one body for the plain and the recording call (rec != NULL: mi_rollout_step_batch_rec, whose last launch is the recording heads)
+// one body for the plain call, the recording call (rec != NULL: mi_rollout_step_batch_rec, whose last launch is the recording heads) and the value-only call (vrec != NULL:
+// mi_rollout_value_batch_rec: the same encoder chain, then the value trunk and the value-only heads; out holds n floats)
+#define ROLL_FAIL(code, text) return mi_fail(code, vrec ? "mi_rollout_value_batch_rec: " text : "mi_rollout_step_batch: " text)
 static int rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
-                              void* scratch, long long scratch_bytes, float* out, const MiRolloutRec* rec) {
+                              void* scratch, long long scratch_bytes, float* out, const MiRolloutRec* rec, const MiRolloutValueRec* vrec = nullptr) {
     VaeEngine* e = (VaeEngine*)vae_h;
-    if (!e || !ppo_h) return mi_fail(MI_ERR_STATE, rec ? "mi_rollout_step_batch_rec: null handle" : "mi_rollout_step_batch: null handle");
-    if (!frames_u8 || !out || !scratch || (n_meas > 0 && !measurements) || (!greedy && !noise)) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: missing buffers");
+    if (!e || !ppo_h) return mi_fail(MI_ERR_STATE, vrec ? "mi_rollout_value_batch_rec: null handle" : rec ? "mi_rollout_step_batch_rec: null handle" : "mi_rollout_step_batch: null handle");
+    if (!frames_u8 || !out || !scratch || (n_meas > 0 && !measurements) || (!greedy && !noise)) ROLL_FAIL(MI_ERR_ARG, "missing buffers");
     if (rec && (!rec->table_rows || !rec->states || !rec->actions || !rec->values || rec->n_table_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch_rec: missing tables");
-    if (n < 1 || n > MI_ROLLOUT_MAX_ENVS) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: 1 <= n <= MI_ROLLOUT_MAX_ENVS");
-    if (((uintptr_t)scratch) & 15) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: the scratch must be 16-byte aligned");
-    if (scratch_bytes < roll_env_floats(e) * 4 * n) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: scratch too small (mi_rollout_batch_workspace_bytes)");
+    if (vrec && (!vrec->table_rows || !vrec->final_values || vrec->n_table_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_rollout_value_batch_rec: missing tables");
+    if (n < 1 || n > MI_ROLLOUT_MAX_ENVS) ROLL_FAIL(MI_ERR_ARG, "1 <= n <= MI_ROLLOUT_MAX_ENVS");
+    if (((uintptr_t)scratch) & 15) ROLL_FAIL(MI_ERR_ARG, "the scratch must be 16-byte aligned");
+    if (scratch_bytes < roll_env_floats(e) * 4 * n) ROLL_FAIL(MI_ERR_ARG, "scratch too small (mi_rollout_batch_workspace_bytes)");
     const MiVaeDesc& d = e->d; const Geom& g = e->g;
     hipStream_t st = (hipStream_t)stream;
     float* act[NCONV + 1]; act[0] = nullptr;
@@ -994,20 +997,26 @@ static int rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsi
     float* mean_raw = (float*)scratch + o;
     mi::PpoFusedParams q;
     CK(mi_ppo_internal_fill(ppo_h, &q, mean_raw, 1));
-    if (q.din != d.z_dim + n_meas) return mi_fail(MI_ERR_SHAPE, "mi_rollout_step_batch: z_dim + measurements must equal the policy's input size");
-    if (q.A > 8) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: at most 8 actions");
-    if (mi_ppo_internal_fill(ppo_h, &q, mean_raw, n) != MI_OK) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch: n exceeds the PPO engine's max_batch");
+    if (q.din != d.z_dim + n_meas) ROLL_FAIL(MI_ERR_SHAPE, "z_dim + measurements must equal the policy's input size");
+    if (q.A > 8) ROLL_FAIL(MI_ERR_ARG, "at most 8 actions");
+    if (mi_ppo_internal_fill(ppo_h, &q, mean_raw, n) != MI_OK) ROLL_FAIL(MI_ERR_ARG, "n exceeds the PPO engine's max_batch");
     MiZeroList zl = {};
     zl.p[0] = act[2]; zl.n[0] = (mean_raw + (long long)n * d.z_dim) - act[2];
     zl.p[1] = q.h1; zl.n[1] = 2LL * n * q.H1;
     zl.p[2] = q.h2; zl.n[2] = 2LL * n * q.H2;
+    if (vrec) {                                          // the value net's halves of the trunks' raw sums alone ([net][n][H]: net 1)
+        zl.p[1] = q.h1 + (long long)n * q.H1; zl.n[1] = (long long)n * q.H1;
+        zl.p[2] = q.h2 + (long long)n * q.H2; zl.n[2] = (long long)n * q.H2;
+    }
     CK(mi_rollout_conv1_batch(st, frames_u8, e->params + e->L.off[0], e->bptr(1), act[1], g.ih[0], g.iw[0], g.c[0], 4, 4, g.c[1], n, &zl));
     for (int i = 1; i < NCONV; ++i)                      // conv(i+1): conv2 reads conv1's finished output, the others raw sums + bias + ReLU on load
         CK(mi_rollout_conv_batch(st, act[i], i == 1 ? nullptr : e->bptr(2 * (i - 1) + 1), g.ih[i], g.iw[i], g.c[i], e->params + e->L.off[2 * i], g.c[i + 1], g.c[i + 1], 4, 4, act[i + 1], 0, n));
     CK(mi_rollout_conv_batch(st, act[NCONV], e->bptr(2 * (NCONV - 1) + 1), 1, 1, g.c[NCONV], e->params + e->L.off[8], 2 * d.z_dim, d.z_dim, 1, 1, mean_raw, g.flat, n));
+    if (vrec) return mi_rollout_value_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, n, out, *vrec);
     if (rec) return mi_rollout_policy_batch_rec(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out, *rec);
     return mi_rollout_policy_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out);
 }
+#undef ROLL_FAIL
 
 int mi_rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
                           void* scratch, long long scratch_bytes, float* out) {
@@ -1018,6 +1027,13 @@ int mi_rollout_step_batch_rec(void* vae_h, void* ppo_h, void* stream, const unsi
                               void* scratch, long long scratch_bytes, float* out, const int* table_rows, long long n_table_rows, float* tab_states, float* tab_actions, float* tab_values) {
     const MiRolloutRec rec = {table_rows, n_table_rows, tab_states, tab_actions, tab_values};
     return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, &rec);
+}
+
+// the value of n observations and nothing else (the final observations of truncated episodes): out [n], and tab_final_values[table_rows[e]] = out[e]
+int mi_rollout_value_batch_rec(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n, void* scratch,
+                               long long scratch_bytes, float* out, const int* table_rows, long long n_table_rows, float* tab_final_values) {
+    const MiRolloutValueRec vrec = {table_rows, n_table_rows, tab_final_values};
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, nullptr, &vrec);
 }
 
 // VAE.encode (vae/models.py:199-202): frames -> mean [B,Z] fp32

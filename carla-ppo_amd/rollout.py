@@ -60,6 +60,25 @@ advantages over all samples of the update instead (tail segments of one or two s
     buf.bootstrap(frames[need], measurements[need], env_ids=need)
     out = buf.update(num_epochs=3, batch_size=32)                  # exactly 8 x 128 samples
 
+An episode can also stop WITHOUT being terminal and be followed by a reset in the same lane: a simulator-side step or time limit, a simulator that timed out and was
+restarted, a route switch.  Reported as a done it pulls the value target of its last steps towards "the car crashed here"; not reported at all, GAE runs across the reset.
+truncate() is the third way for a segment to end: it takes the FINAL observation of the stopped episodes -- no step of the lane, the lane's next step is the reset
+observation -- and one value-only device call (mi_rollout_value_batch_rec: encoder chain, value trunk, value head) leaves its value in `buf.final_values` at the table row
+of the episode's last step; update() then bootstraps that segment from it (mi_rollout_finish_segments_boot) and never reads the slot behind it:
+
+    for _ in range(buf.horizon):
+        actions, values, states = buf.step(frames, measurements)
+        rewards, dones, truncated, frames, measurements, final_frames, final_measurements = simulators_step(actions)   # done or truncated: frames[e] is the reset observation
+        buf.outcome(rewards, dones)                                # a truncated step reports done False
+        cut = np.nonzero(truncated & ~dones)[0]
+        if len(cut):
+            buf.truncate(final_frames[cut], final_measurements[cut], env_ids=cut)   # after outcome(), before these lanes' next step
+    need = buf.rows.needs_bootstrap()                              # a lane whose last step is a done or truncated needs none
+    buf.bootstrap(frames[need], measurements[need], env_ids=need)
+    out = buf.update(num_epochs=3, batch_size=32)                  # out["segment_truncated"], out["final_values"]
+
+A collection on which truncate() is never called takes the path it always took (mi_rollout_finish_segments, the same launches).
+
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import os
@@ -217,6 +236,27 @@ class BatchedRolloutStep(_StepBase):
         o = self._out_np[:n]
         return o[:, :self.A].copy(), o[:, self.A].copy(), np.concatenate([o[:, self.A + 1:].astype(np.float64), meas], axis=1)
 
+    def record_value(self, f, n, meas, table_rows, final_values):
+        """The value-only device call on checked inputs (mi_rollout_value_batch_rec: the encoder chain, the value trunk and the value head; no action, no latent comes
+        back): the int32 table rows go behind the measurements and the value of row i is also left in final_values[table_rows[i]].  -> float32 [n]."""
+        import torch
+        nm = n * self.n_meas
+        self._in_np[:n * self.frame_bytes] = f.reshape(-1)
+        self._f_np[:nm] = meas.reshape(-1)
+        self._i_np[nm:nm + n] = table_rows
+        st = torch.cuda.current_stream(self.device)
+        used = self._f_off + 4 * (nm + n)
+        if self.d_in is not None:
+            self.d_in[:used].copy_(self.h_in[:used], non_blocking=True)
+        base = (self.h_in if self.d_in is None else self.d_in).data_ptr()
+        fptr = base + self._f_off
+        self.L.mi_rollout_value_batch_rec(self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, n, self.scratch.data_ptr(), self.scratch_bytes,
+                                          (self.h_out if self.d_out is None else self.d_out).data_ptr(), fptr + 4 * nm, int(final_values.shape[0]), final_values.data_ptr())
+        if self.d_out is not None:
+            self.h_out[:n].copy_(self.d_out[:n], non_blocking=True)
+        st.synchronize()
+        return self.h_out.numpy()[:n].copy()
+
 
 MAX_HORIZON = 4096                                                                   # MI_ROLLOUT_MAX_HORIZON of include/mi355_carla.h
 
@@ -348,18 +388,43 @@ class RolloutRows:
 class SegmentedRows(RolloutRows):
     """RolloutRows for lanes that hold SEVERAL episodes (ContinuousRolloutBuffer): a done does not end a lane, the next step of that environment records at slot
     lengths[e] and starts a new segment; a lane is ended only when it is full.  A segment is a maximal run of recorded steps of a lane that ends at a step with
-    done != 0 or at the lane's last recorded step; only a lane's last segment can end without a done, and slot lengths[e] behind it is the lane's bootstrap slot."""
+    done != 0, at a TRUNCATED step or at the lane's last recorded step; only a lane's last segment can end without either, and slot lengths[e] behind it is the lane's
+    bootstrap slot.  A truncated step (truncate_rows) is the last step of an episode that stopped without being terminal -- a step or time limit, a restarted simulator,
+    a route switch -- and is followed by a reset in the same lane: its segment bootstraps from the value of the episode's final observation, which is no step of the
+    lane and is kept beside the step's own row (ContinuousRolloutBuffer.final_values)."""
+
+    def reset(self):
+        super().reset()
+        self.truncs = np.zeros((self.num_envs, self.horizon), bool)
 
     def _ends(self, done, length):
         return length >= self.horizon
 
     def _last_done(self):
-        """Per lane: its last counted step reported done (False for an empty lane)."""
+        """Per lane: its last counted step reported done or was truncated -- nothing behind it is read (False for an empty lane)."""
         last = np.maximum(self.lengths, 1) - 1
-        return (self.lengths > 0) & (self.dones[self._all, last] != 0)
+        return (self.lengths > 0) & ((self.dones[self._all, last] != 0) | self.truncs[self._all, last])
+
+    def truncate_rows(self, env_ids, n):
+        """The table rows of the last counted step (slot lengths[e] - 1) of these lanes; marks the steps as truncated.  The lanes go on as they were: an open lane takes
+        its next step (the reset observation), a full one needs no bootstrap any more."""
+        ids = self.env_ids(env_ids, n)
+        st = self.state[ids]
+        self._refuse("truncation of", ids, st, ((self.CLOSED, "a closed row"), (self.AWAITING, "a row whose last step has no outcome yet")))
+        if (self.lengths[ids] < 1).any():
+            raise ValueError("RolloutBuffer: truncation of an empty row (environments %s)" % ids[self.lengths[ids] < 1].tolist())
+        last = self.lengths[ids] - 1
+        if (self.dones[ids, last] != 0).any():
+            raise ValueError("RolloutBuffer: truncation of a row whose last step reported done -- a terminal stays a terminal (environments %s)"
+                             % ids[self.dones[ids, last] != 0].tolist())
+        if self.truncs[ids, last].any():
+            raise ValueError("RolloutBuffer: truncation of a row whose last step is already truncated (environments %s)" % ids[self.truncs[ids, last]].tolist())
+        self.truncs[ids, last] = True
+        return self._base[ids] + last                                                # int32
 
     def needs_bootstrap(self):
-        """Lanes that are non-empty, not closed, not awaiting an outcome, and whose last counted step has done == 0: their last segment bootstraps from slot lengths[e]."""
+        """Lanes that are non-empty, not closed, not awaiting an outcome, and whose last counted step has done == 0 and is not truncated: their last segment bootstraps
+        from slot lengths[e]."""
         return np.nonzero((self.lengths > 0) & (self.state != self.CLOSED) & (self.state != self.AWAITING) & ~self._last_done())[0]
 
     def check_update(self):
@@ -377,7 +442,7 @@ class SegmentedRows(RolloutRows):
         out = []
         for e in range(self.num_envs):
             n = int(self.lengths[e])
-            ends = (np.nonzero(self.dones[e, :n] != 0)[0] + 1).tolist()
+            ends = (np.nonzero((self.dones[e, :n] != 0) | self.truncs[e, :n])[0] + 1).tolist()
             if n and (not ends or ends[-1] != n):
                 ends.append(n)
             first = 0
@@ -385,6 +450,13 @@ class SegmentedRows(RolloutRows):
                 out.append((e, first, end - first))
                 first = end
         return np.asarray(out, np.int32).reshape(-1, 3)
+
+    def segment_truncated(self):
+        """int32 [n_seg], in the order of segments(): 1 where the segment's last step is truncated."""
+        return self._truncated(self.segments())
+
+    def _truncated(self, segs):
+        return self.truncs[segs[:, 0], segs[:, 1] + segs[:, 2] - 1].astype(np.int32)
 
 
 class _RecordingStep(BatchedRolloutStep):
@@ -516,37 +588,67 @@ class RolloutBuffer:
 
 class ContinuousRolloutBuffer(RolloutBuffer):
     """RolloutBuffer whose lanes go on after a done (see the module docstring): every environment steps `horizon` times per update, a simulator that reports done is
-    stepped again with its reset observation, and update() finishes the lanes segment by segment (mi_rollout_finish_segments).  Same tables and recording step."""
+    stepped again with its reset observation, and update() finishes the lanes segment by segment (mi_rollout_finish_segments).  Same tables and recording step, and
+    `final_values` (fp32, num_envs (horizon + 1) entries like the other tables): entry r holds the value of the final observation of the episode that truncate() ended
+    at table row r."""
 
     _rows_class = SegmentedRows
 
+    def __init__(self, vae, ppo, num_envs, horizon, seed=None, io=None):
+        import torch
+        super().__init__(vae, ppo, num_envs, horizon, seed=seed, io=io)
+        self.final_values = torch.zeros(self.n_table_rows, device=self.device)
+
     def bootstrap(self, frames_u8, measurements, env_ids=None):
-        """RolloutBuffer.bootstrap; env_ids None: rows.needs_bootstrap() -- a lane whose last step reported done needs none (given one, it is recorded and never read).
-        With no such lane and no frames the call does nothing."""
+        """RolloutBuffer.bootstrap; env_ids None: rows.needs_bootstrap() -- a lane whose last step reported done or was truncated needs none (given one, it is recorded and
+        never read).  With no such lane and no frames the call does nothing."""
         if env_ids is None:
             env_ids = self.rows.needs_bootstrap()
         if len(env_ids) == 0 and (frames_u8 is None or len(frames_u8) == 0):         # (the loop's frames[need] with every lane ending in a done)
             return None
         return super().bootstrap(frames_u8, measurements, env_ids)
 
+    def truncate(self, final_frames_u8, final_measurements, env_ids=None):
+        """The episodes of these environments (None: 0 .. n-1) stopped at their last counted step WITHOUT being terminal, and their lanes go on with a reset observation:
+        call it after outcome() (done False) and before these lanes' next step, with the final observation of the stopped episodes.  One value-only device call
+        (mi_rollout_value_batch_rec) leaves V(final observation) in final_values at the row of that step; update() bootstraps the segment from it.  -> float32 [n]."""
+        f, n, meas, _ = self._step.check(final_frames_u8, final_measurements, True, None)
+        rows = self.rows.truncate_rows(env_ids, n)
+        return self._step.record_value(f, n, meas, rows, self.final_values)
+
     def update(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, normalize="segment", stage_times=None):
-        """RolloutBuffer.update with one mi_rollout_finish_segments call for the finish.  normalize: "segment" (train.py:176-177 on every segment alone, the reference's
-        semantics) or "batch" (mean and population std over all samples of the update: a 1-step tail segment's advantage is not forced to 0).  Returns RolloutBuffer.update's
-        keys and `segments` (SegmentedRows.segments()); `bootstrap_values` is NaN for lanes whose last step reported done."""
+        """RolloutBuffer.update with one mi_rollout_finish_segments call for the finish (mi_rollout_finish_segments_boot, which also takes the per-segment bootstrap
+        source, if and only if a step of this collection was truncated).  normalize: "segment" (train.py:176-177 on every segment alone, the reference's semantics) or
+        "batch" (mean and population std over all samples of the update: a 1-step tail segment's advantage is not forced to 0).  Returns RolloutBuffer.update's keys,
+        `segments` (SegmentedRows.segments()), `segment_truncated` (SegmentedRows.segment_truncated()) and `final_values`, float32 [num_envs, T]: the value a truncated
+        step's segment bootstrapped from, NaN where no truncation was recorded; `bootstrap_values` is NaN for lanes whose last step reported done or was truncated."""
         if normalize not in ("segment", "batch"):
             raise ValueError("ContinuousRolloutBuffer.update: normalize is 'segment' or 'batch'")
         segs = self.rows.segments()
+        truncs = self.rows.truncs.copy()
+        seg_trunc = self.rows._truncated(segs)                                      # = segment_truncated(), from the one segments() walk
 
         def finish(st, r, d, lengths, f64):
             import torch
             n_seg, T = int(segs.shape[0]), self.horizon
-            desc = torch.from_numpy(np.stack([segs[:, 0] * (T + 1) + segs[:, 1], segs[:, 2]]).astype(np.int32)).to(self.device)     # table row of the first slot | length
+            desc = [segs[:, 0] * (T + 1) + segs[:, 1], segs[:, 2]]                   # table row of the first slot | length
+            if truncs.any():
+                desc.append(seg_trunc)                                               # | bootstraps from final_values
+            desc = torch.from_numpy(np.stack(desc).astype(np.int32)).to(self.device)
             batch = normalize == "batch"
             scratch = torch.empty(int(self.L.mi_rollout_finish_segments_scratch_doubles(n_seg)), dtype=torch.float64, device=self.device) if batch else None
-            self.L.mi_rollout_finish_segments(st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), n_seg, self.num_envs, T,
-                                              float(gamma), float(lam), 1 if batch else 0, milib.ptr(scratch), self.returns.data_ptr(), self.advantages.data_ptr(),
-                                              f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
+            args = (st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), n_seg, self.num_envs, T, float(gamma), float(lam),
+                    1 if batch else 0, milib.ptr(scratch), self.returns.data_ptr(), self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
+            if truncs.any():
+                self.L.mi_rollout_finish_segments_boot(*args, self.final_values.data_ptr(), desc[2].data_ptr())
+            else:
+                self.L.mi_rollout_finish_segments(*args)
+        last_done = self.rows._last_done()
         out = self._update(finish, num_epochs, batch_size, stage_times)
-        out["segments"] = segs
-        out["bootstrap_values"] = np.where(self.rows._last_done(), np.float32(np.nan), out["bootstrap_values"]).astype(np.float32)
+        out["segments"], out["segment_truncated"] = segs, seg_trunc
+        out["bootstrap_values"] = np.where(last_done, np.float32(np.nan), out["bootstrap_values"]).astype(np.float32)
+        final = np.full(truncs.shape, np.nan, np.float32)
+        if truncs.any():
+            final[truncs] = self.final_values.view(self.num_envs, self.horizon + 1)[:, :self.horizon].cpu().numpy()[truncs]
+        out["final_values"] = final
         return out

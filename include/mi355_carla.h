@@ -397,6 +397,12 @@ int mi_rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned
  * (-1 = "do not record this environment") is skipped: no value of it stores outside the tables.  The tables are HBM with n_table_rows rows each.  Same checks as
  * mi_rollout_step_batch, plus missing tables. */
 int mi_rollout_step_batch_rec(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n, void* scratch, long long scratch_bytes, float* out, const int* table_rows, long long n_table_rows, float* tab_states, float* tab_actions, float* tab_values);
+/* the VALUE of n observations and nothing else -- the final observations of episodes that were TRUNCATED (stopped without being terminal, train.py:172's bootstrap value
+ * for an episode whose lane goes on with a reset observation): the encoder chain of mi_rollout_step_batch, the value trunk alone and a value head whose arithmetic is
+ * the step's (ppo.py:70-71), eight launches like the step.  out [n] = the values; call row e is also stored as tab_final_values[table_rows[e]] (fp32, n_table_rows entries, HBM; plain
+ * vector stores); a row outside [0, n_table_rows) records nothing.  frames_u8 / measurements / table_rows / out: HBM or pinned host memory; `scratch` as for
+ * mi_rollout_step_batch (the same bytes).  The policy net's raw sums in the PPO engine are neither cleared nor read.  Same checks as mi_rollout_step_batch, plus missing tables. */
+int mi_rollout_value_batch_rec(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n, void* scratch, long long scratch_bytes, float* out, const int* table_rows, long long n_table_rows, float* tab_final_values);
 /* finishes a RAGGED rollout buffer in one launch — compute_gae (utils.py:45-50) + returns and advantage normalisation (train.py:175-177) per row: row e of num_envs has
  * len[e] = L <= T recorded steps in slots 0 .. L-1 of its T + 1 table slots (table row e (T + 1) + t) and the bootstrap value in slot L.  tab_values: the fp32 values table;
  * rewards / terminals: fp64 [num_envs, T]; len: int32 [num_envs] (all device).  fp64 with the rounding sequence of mi_gae_scan + mi_adv_normalize on that row alone (divisor L,
@@ -416,6 +422,12 @@ int mi_rollout_finish(void* stream, const float* tab_values, const double* rewar
  * belong to no executed segment are not written.  n_seg, num_envs, T >= 1, T <= MI_ROLLOUT_MAX_HORIZON. */
 long long mi_rollout_finish_segments_scratch_doubles(int n_seg);
 int mi_rollout_finish_segments(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* seg_row, const int* seg_len, int n_seg, int num_envs, int T, double gamma, double lam, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw, double* returns, double* adv_norm);
+/* mi_rollout_finish_segments with a per-segment bootstrap source — compute_gae (utils.py:45-50) + train.py:175-177 per segment: seg_boot: int32 [n_seg] on the device.
+ * seg_boot[i] == 0: exactly mi_rollout_finish_segments' rule.  seg_boot[i] != 0 (the segment was TRUNCATED: its episode stopped without being terminal and the lane went
+ * on): the value behind the last step is tab_final_values[seg_row[i] + seg_len[i] - 1] (fp32 [num_envs (T + 1)], what mi_rollout_value_batch_rec left at the row of
+ * that step) and the slot behind the segment in tab_values is NOT read (it holds the next episode's first value, or a stale one); the segment comes out bit for bit as
+ * mi_gae_scan + mi_adv_normalize give it on [v_0 .. v_{n-1}, v_final].  normalize, scratch and every other argument as in mi_rollout_finish_segments, and the same checks. */
+int mi_rollout_finish_segments_boot(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* seg_row, const int* seg_len, int n_seg, int num_envs, int T, double gamma, double lam, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw, double* returns, double* adv_norm, const float* tab_final_values, const int* seg_boot);
 
 /* ---- collectives of the data-parallel path (no reference counterpart: the reference is single-process) ----
  * RCCL over xGMI, one communicator per process = per GPU; librccl.so.1 is bound at mi_comm_init (a single-GPU process never loads it).

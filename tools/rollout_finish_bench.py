@@ -1,11 +1,13 @@
 """Microseconds per finish call of a rollout buffer: mi_rollout_finish_segments (normalize 0 and 1) against mi_rollout_finish on the same tables in the same process.
 
-    python tools/rollout_finish_bench.py [--shapes 64x128,1024x128] [--calls 200] [--rounds 3] [--no-box]
+    python tools/rollout_finish_bench.py [--shapes 64x128,1024x128] [--calls 200] [--rounds 3] [--boot] [--no-box]
 
 Layouts of the segment descriptors: `one` = one full segment per lane (what mi_rollout_finish computes, the yardstick applies), `few` = 2-4 segments per lane at seeded
 random cuts, `short` = every segment 1-4 steps (the worst case: E x T / 2.5 one-wave blocks).  The dense call is timed next to every layout on the same tables (its work
 does not depend on the descriptors).  A figure is device time between two events around `--calls` back-to-back calls, divided by the calls; the variants are interleaved in
-every round and every round is printed."""
+every round and every round is printed.  --boot adds mi_rollout_finish_segments_boot (the finish that takes a per-segment bootstrap source) to every layout, with all
+flags 0 (the same work as mi_rollout_finish_segments: the same bits, asserted) and with the LAST segment of every lane truncated (one truncation per lane), both
+normalisations."""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
@@ -17,6 +19,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--shapes", default="64x128,1024x128")
 ap.add_argument("--calls", type=int, default=200)
 ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--boot", action="store_true", help="also time mi_rollout_finish_segments_boot, all flags 0 and one truncation per lane")
 ap.add_argument("--no-box", action="store_true")
 args = ap.parse_args()
 if not torch.cuda.is_available():
@@ -80,6 +83,23 @@ for shape in args.shapes.split(","):
             L.mi_rollout_finish_segments(st, values.data_ptr(), rewards.data_ptr(), d_d.data_ptr(), row_d.data_ptr(), len_d.data_ptr(), n_seg, E, T, 0.99, 0.95, normalize,
                                          scratch.data_ptr(), ret32.data_ptr(), adv32.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
         variants = [("mi_rollout_finish", dense), ("segments, normalize 0", lambda: seg(0)), ("segments, normalize 1", lambda: seg(1))]
+        if args.boot:
+            final = torch.from_numpy(rng.standard_normal(E * (T + 1)).astype(np.float32)).cuda()
+            last = np.zeros(n_seg, np.int32)
+            last[np.nonzero(desc[:, 0] + desc[:, 1] == (desc[:, 0] // (T + 1)) * (T + 1) + T)[0]] = 1      # the segment that ends at the lane's last slot
+            flags = {"flags 0": torch.zeros(n_seg, dtype=torch.int32, device="cuda"), "1 truncation per lane": torch.from_numpy(last).cuda()}
+
+            def boot(normalize, which):
+                L.mi_rollout_finish_segments_boot(st, values.data_ptr(), rewards.data_ptr(), d_d.data_ptr(), row_d.data_ptr(), len_d.data_ptr(), n_seg, E, T, 0.99, 0.95, normalize,
+                                                  scratch.data_ptr(), ret32.data_ptr(), adv32.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr(), final.data_ptr(),
+                                                  flags[which].data_ptr())
+            for normalize in (0, 1):
+                seg(normalize)
+                want = (ret32.clone(), adv32.clone(), f64.clone())
+                boot(normalize, "flags 0")
+                assert all(torch.equal(x, y) for x, y in zip(want, (ret32, adv32, f64))), "mi_rollout_finish_segments_boot with no flag set differs from mi_rollout_finish_segments"
+                for which in flags:
+                    variants.append(("boot, normalize %d, %s" % (normalize, which), lambda normalize=normalize, which=which: boot(normalize, which)))
         if layout == "one":                                                          # same work: same bits
             dense()
             want = (ret32.clone(), adv32.clone(), f64.clone())
@@ -105,4 +125,4 @@ for shape in args.shapes.split(","):
         print("E x T = %d x %d, layout %-5s %6d segments (%.1f steps each):" % (E, T, layout, n_seg, E * T / n_seg), flush=True)
         for name, _ in variants:
             r = res[name]
-            print("  %-22s %8.1f us per call (rounds %s)" % (name, sorted(r)[len(r) // 2], " ".join("%.1f" % x for x in r)), flush=True)
+            print("  %-40s %8.1f us per call (rounds %s)" % (name, sorted(r)[len(r) // 2], " ".join("%.1f" % x for x in r)), flush=True)

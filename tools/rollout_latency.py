@@ -1,13 +1,15 @@
 """Latency of the rollout-loop inference path at batch 1 (SURVEY 8f.3 callers: vae_common.py:45-61, train.py:142, run_eval.py:54):
 VAE.encode([frame]) (host frame -> device, conv stack, mean to host) followed by PPO.predict(state) (host -> device, two MLP trunks, action to host).
 
-    python tools/rollout_latency.py --envs [1,2,4,8,16,32,64] [--rounds 3] [--calls 200] [--batched-only | --record] [--no-box]
+    python tools/rollout_latency.py --envs [1,2,4,8,16,32,64] [--rounds 3] [--calls 200] [--batched-only | --record | --value] [--no-box]
 
 times, for each number of environments E, one BatchedRolloutStep call against a loop of E RolloutStep calls and against the two-call path (VAE.encode of E float
 frames + PPO.predict of E states) on the same engines: the three are interleaved in every round, the line gives the median of the rounds' medians, the spread of
 those medians (min - max) and the p90 over all calls.  --batched-only runs the batched calls alone (the form a kernel trace is taken of).  --record times
 RolloutBuffer.step (the recording step, mi_rollout_step_batch_rec: the same eight launches, the heads also store state / action / value into the device tables)
-against BatchedRolloutStep, interleaved; the buffer's outcome() / reset() book-keeping runs between the timed calls."""
+against BatchedRolloutStep, interleaved; the buffer's outcome() / reset() book-keeping runs between the timed calls.  --value times the value-only call of
+ContinuousRolloutBuffer.truncate (mi_rollout_value_batch_rec: the encoder chain, the value trunk and the value head) against the GREEDY recording call (what a bootstrap
+is: mi_rollout_step_batch_rec) on the same frames, both without the row book-keeping and at fixed table rows, interleaved."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
@@ -28,6 +30,7 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--calls", type=int, default=200, help="timed calls per path, E and round")
 ap.add_argument("--batched-only", action="store_true")
 ap.add_argument("--record", action="store_true", help="RolloutBuffer.step against BatchedRolloutStep")
+ap.add_argument("--value", action="store_true", help="the value-only call (mi_rollout_value_batch_rec) against the greedy recording call")
 ap.add_argument("--no-box", action="store_true")
 args = ap.parse_args()
 rng = np.random.RandomState(0)
@@ -82,6 +85,17 @@ def envs_table():
             def device_only(i):                                      # the recording call without the row book-keeping: always slot 0
                 buf._step.record(*buf._step.check(u8[sl(i)], ms[sl(i)], False, None), False, fixed, buf.states, buf.actions, buf.values)
             paths, after = [("batched", batched), ("recording", recording), ("recording w/o book-keeping", device_only)], {"recording": book}
+        if args.value:
+            from rollout import ContinuousRolloutBuffer
+            cbuf = ContinuousRolloutBuffer(vae, agent, E, horizon=64, io=many.io)
+            slot0 = (np.arange(E) * (cbuf.horizon + 1)).astype(np.int32)
+
+            def greedy_recording(i):
+                cbuf._step.record(*cbuf._step.check(u8[sl(i)], ms[sl(i)], True, None), True, slot0, cbuf.states, cbuf.actions, cbuf.values)
+            def value_only(i):
+                f, n, meas, _ = cbuf._step.check(u8[sl(i)], ms[sl(i)], True, None)
+                cbuf._step.record_value(f, n, meas, slot0, cbuf.final_values)
+            paths, after = [("greedy recording", greedy_recording), ("value-only", value_only)], {}
         ts = {name: [] for name, _ in paths}
         for _ in range(args.rounds):
             for name, fn in paths:
@@ -91,8 +105,10 @@ def envs_table():
             meds = [np.median(t) for t in ts[name]]
             med[name] = np.median(meds)
             line += "  %s %.1f us (rounds %.1f - %.1f, p90 %.1f)" % (name, med[name], min(meds), max(meds), np.percentile(np.concatenate(ts[name]), 90))
-        if args.record:
+        if args.record and not args.value:
             line += "  | recording - batched %+.2f us, w/o book-keeping %+.2f us" % (med["recording"] - med["batched"], med["recording w/o book-keeping"] - med["batched"])
+        elif args.value:
+            line += "  | value-only - greedy recording %+.2f us" % (med["value-only"] - med["greedy recording"])
         elif not args.batched_only:
             line += "  | loop / batched %.2f x, two-call / batched %.2f x" % (med["loop of B=1"] / med["batched"], med["two-call"] / med["batched"])
         print(line, flush=True)
