@@ -396,6 +396,33 @@ int mi_ppo_logp_old(void* h, void* stream, const float* states, const float* act
     return mi_ppo_fused_logp_old((hipStream_t)stream, q, out, x3(e));
 }
 
+// Per-epoch update diagnostics (include/mi355_carla.h): the sums behind approx KL (k3 and k1), clipped fraction, mean ratio, value error and explained variance of M
+// gathered table rows under the CURRENT theta against the cached log pi_old -- forward only, ordered reduction, nothing of the training state is written.
+long long mi_ppo_update_stats_scratch_doubles(int M) { return (long long)MI_PPO_N_STATS * (M < 1 ? 1 : (M + 31) / 32); }
+
+int mi_ppo_update_stats_idx(void* h, void* stream, const float* states, const float* actions, const float* returns, const float* logp_old,
+                            const int* row_idx, int n_rows, int M, int accumulate, double* scratch, double* stats, float* logp_new_out, float* value_out) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_update_stats_idx: null handle");
+    // (what needs no engine is checked before the handle is looked at)
+    if (M < 1 || n_rows < 1) return mi_fail(MI_ERR_ARG, "mi_ppo_update_stats_idx: batch outside [1, max_batch] or empty tables");
+    {
+        const void* need[7] = {states, actions, returns, logp_old, row_idx, scratch, stats};
+        static const char* const msg[7] = {"mi_ppo_update_stats_idx: missing buffers (states)", "mi_ppo_update_stats_idx: missing buffers (actions)",
+                                           "mi_ppo_update_stats_idx: missing buffers (returns)", "mi_ppo_update_stats_idx: missing buffers (logp_old)",
+                                           "mi_ppo_update_stats_idx: missing buffers (row_idx)", "mi_ppo_update_stats_idx: missing buffers (scratch)",
+                                           "mi_ppo_update_stats_idx: missing buffers (stats)"};
+        for (int i = 0; i < 7; ++i) if (!need[i]) return mi_fail(MI_ERR_ARG, msg[i]);
+    }
+    if (accumulate != 0 && accumulate != 1) return mi_fail(MI_ERR_ARG, "mi_ppo_update_stats_idx: accumulate is 0 (store the sums) or 1 (add them to stats)");
+    if (M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_update_stats_idx: batch outside [1, max_batch] or empty tables");
+    if (!fused_enabled(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_update_stats_idx: needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0)");
+    PpoFusedParams q; fill_fused(e, q, states, M);
+    q.actions = actions; q.returns = returns; q.logp_old = logp_old;
+    q.row_idx = row_idx; q.n_rows = n_rows;
+    return mi_ppo_fused_update_stats((hipStream_t)stream, q, accumulate, scratch, stats, logp_new_out, value_out, x3(e));
+}
+
 // precision of the engine's training forms (mi_ppo_train_step[_idx|_dp], the fused mi_ppo_forward_backward, mi_ppo_logp_old): MI_F32 (exact fp32, the default) or
 // MI_BF16X3 (split-bf16 GEMM stages, ppo_fused.hip).  MI_BF16 has no PPO form; the split form exists only as fused kernels, so an engine that runs the per-layer
 // path refuses it instead of training in fp32.  mi_ppo_predict and the rollout step stay exact fp32 in both modes.

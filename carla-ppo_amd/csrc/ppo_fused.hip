@@ -678,6 +678,84 @@ __global__ __launch_bounds__(256) void ppo_predict_head_kernel(const PpoFusedPar
     if (logp_out) logp_out[m] = lp; else value[m] = av + bv[0];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// update diagnostics (mi_ppo_update_stats_idx): heads of the CURRENT policy and value net on the trunks of nets 0 / 1, and the per-sample terms of the
+// MI_PPO_N_STATS running sums in double precision.  grid ceil(M / 32) blocks; 8 threads per sample, sample m = table row row_idx[m] (clamped).
+//   lp = log pi(a | s) under theta: the loop, the shuffles and the libm calls of ppo_predict_head_kernel<NA, 3>'s log-probability path, so that with
+//        theta == theta_old it is the cached logp_old bit for bit;  v = h2_v Wv + bv in that kernel's order
+//   d = lp - logp_old, r = exp(d), ret = returns: terms 1, d, r - 1 - d (k3), |r - 1| > clip_eps, r, ret, ret^2, ret - v, (ret - v)^2
+// Ordered reduction, no atomics: the 8 samples of a wave meet by an xor tree of shuffles (every lane forms the same sums), the four waves' sums in LDS are added
+// in wave order and stored as this block's row of `scratch`; ppo_update_stats_reduce_kernel adds the rows in block order.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int PF_NSTATS = MI_PPO_N_STATS;
+template <int NA>
+__global__ __launch_bounds__(256) void ppo_update_stats_head_kernel(const PpoFusedParams q, double* __restrict__ scratch, float* __restrict__ logp_new_out, float* __restrict__ value_out) {
+    __shared__ double swave[4][PF_NSTATS];
+    const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
+    const int sm = tid >> 3, part = tid & 7, m = m0 + sm, wave = tid >> 6;
+    const float* Wm = q.theta + q.off[4]; const float* bm = q.theta + q.off[5]; const float* logstd = q.theta + q.off[6];
+    const float* Wv = q.theta + q.off[11]; const float* bv = q.theta + q.off[12];
+    const float* h2p = q.h2; const float* h2v = q.h2 + (long long)q.M * H2;
+    float au[NA], av = 0.f;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) au[a] = 0.f;
+    if (m < q.M) {
+        for (int j = part; j < H2; j += 8) {
+            const float hp = h2p[(long long)m * H2 + j];
+            av += h2v[(long long)m * H2 + j] * Wv[j];
+            _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) au[a] += hp * Wm[(long long)j * A + a];
+        }
+    }
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) {
+        av += __shfl_xor(av, o, 64);
+#pragma unroll
+        for (int a = 0; a < NA; ++a) au[a] += __shfl_xor(au[a], o, 64);
+    }
+    double term[PF_NSTATS];
+#pragma unroll
+    for (int k = 0; k < PF_NSTATS; ++k) term[k] = 0.0;
+    if (part == 0 && m < q.M) {
+        const long long mr = min(max(q.row_idx[m], 0), q.n_rows - 1);
+        float lp = 0.f;
+        _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) {
+            const float lo = q.low[a], hi = q.high[a];
+            const float mean = lo + ((tanhf(au[a] + bm[a]) + 1.0f) * 0.5f) * (hi - lo);
+            const float sigma = expf(logstd[a]);
+            const float z = (q.actions[mr * A + a] - mean) / sigma;
+            lp += -0.5f * z * z - (PF_HALF_LOG_2PI + logf(sigma));
+        }
+        const float v = av + bv[0];
+        if (logp_new_out) logp_new_out[mr] = lp;
+        if (value_out) value_out[mr] = v;
+        const double d = (double)lp - (double)q.logp_old[mr];
+        const double r = exp(d);
+        const double ret = (double)q.returns[mr], e = ret - (double)v;
+        term[0] = 1.0; term[1] = d; term[2] = (r - 1.0) - d; term[3] = fabs(r - 1.0) > (double)q.clip_eps ? 1.0 : 0.0; term[4] = r;
+        term[5] = ret; term[6] = ret * ret; term[7] = e; term[8] = e * e;
+    }
+#pragma unroll
+    for (int k = 0; k < PF_NSTATS; ++k) {
+#pragma unroll
+        for (int o = 8; o < 64; o <<= 1) term[k] += __shfl_xor(term[k], o, 64);
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < PF_NSTATS; ++k) swave[wave][k] = term[k];
+    }
+    __syncthreads();
+    if (tid < PF_NSTATS) scratch[(long long)blockIdx.x * PF_NSTATS + tid] = ((swave[0][tid] + swave[1][tid]) + swave[2][tid]) + swave[3][tid];
+}
+
+// one wave: lane k adds column k of the block rows in block order, then stores (accumulate 0) or adds to (1) stats[k]
+__global__ __launch_bounds__(64) void ppo_update_stats_reduce_kernel(const double* __restrict__ scratch, int n_blocks, int accumulate, double* __restrict__ stats) {
+    const int k = threadIdx.x;
+    if (k >= PF_NSTATS) return;
+    double sum = 0.0;
+    for (int b = 0; b < n_blocks; ++b) sum += scratch[(long long)b * PF_NSTATS + k];
+    stats[k] = accumulate ? stats[k] + sum : sum;
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -715,6 +793,21 @@ int mi_ppo_fused_logp_old(hipStream_t st, PpoFusedParams& q, float* out, bool x3
     if (q.A <= 2) hipLaunchKernelGGL((ppo_predict_head_kernel<2, 3>), dim3((q.M + 31) / 32), dim3(256), 0, st, q, (const float*)nullptr, 1, (float*)nullptr, (float*)nullptr, out, 2);
     else hipLaunchKernelGGL((ppo_predict_head_kernel<PF_MAX_ACT, 3>), dim3((q.M + 31) / 32), dim3(256), 0, st, q, (const float*)nullptr, 1, (float*)nullptr, (float*)nullptr, out, 2);
     return mi_check_launch("ppo_logp_old");
+}
+
+// update diagnostics of M gathered rows under the current theta (q.row_idx / n_rows / actions / returns / logp_old set by the caller): the policy and value trunks,
+// the statistics head, the ordered sum of its block rows into stats.  Nothing but the activation workspace, scratch, stats and the two optional tables is written.
+int mi_ppo_fused_update_stats(hipStream_t st, PpoFusedParams& q, int accumulate, double* scratch, double* stats, float* logp_new_out, float* value_out, bool x3) {
+    { const int rc0 = pf_check_shape(q, "ppo fused update stats"); if (rc0 != MI_OK) return rc0; }
+    q.n_nets = 2;
+    q.s_gath = nullptr;                                   // (no filter gradient behind this pass: layer 1 gathers its operand rows and leaves no copy)
+    int rc = mi_ppo_fused_trunks(st, q, x3);
+    if (rc != MI_OK) return rc;
+    const int nb = (q.M + 31) / 32;
+    if (q.A <= 2) hipLaunchKernelGGL(ppo_update_stats_head_kernel<2>, dim3(nb), dim3(256), 0, st, q, scratch, logp_new_out, value_out);
+    else hipLaunchKernelGGL(ppo_update_stats_head_kernel<PF_MAX_ACT>, dim3(nb), dim3(256), 0, st, q, scratch, logp_new_out, value_out);
+    hipLaunchKernelGGL(ppo_update_stats_reduce_kernel, dim3(1), dim3(64), 0, st, (const double*)scratch, nb, accumulate, stats);
+    return mi_check_launch("ppo_update_stats");
 }
 
 int mi_ppo_fused_partial_floats(int M) { return ((M + 31) / 32) * PF_NPART; }

@@ -37,6 +37,7 @@ bool mi_ppo_fused_shape_in_range(int A, int H2, int kin);
 int mi_ppo_fused_step(hipStream_t st, mi::PpoFusedParams& q, int fuse_adam, bool x3);      // x3: split-bf16 GEMM stages (MI_BF16X3)
 int mi_ppo_fused_predict(hipStream_t st, mi::PpoFusedParams& q, const float* noise, int greedy, float* action, float* value);
 int mi_ppo_fused_logp_old(hipStream_t st, mi::PpoFusedParams& q, float* out, bool x3);
+int mi_ppo_fused_update_stats(hipStream_t st, mi::PpoFusedParams& q, int accumulate, double* scratch, double* stats, float* logp_new_out, float* value_out, bool x3);
 // internal accessors of the two engines for the rollout step (rollout path only)
 int mi_ppo_internal_fill(void* ppo_handle, mi::PpoFusedParams* q, const float* states, int M);
 struct MiZeroList { float* p[3]; long long n[3]; };     // raw-sum buffers conv1's launch clears for the split-K layers behind it

@@ -11,6 +11,25 @@ from .init import ppo_variables
 from .vae_device import require_gpu
 
 
+N_STATS = 9                                       # MI_PPO_N_STATS of include/mi355_carla.h
+
+
+def update_stats_summary(sums):
+    """The MI_PPO_N_STATS running sums of mi_ppo_update_stats_idx (count, sum d, sum (r - 1 - d), clipped count, sum r, sum ret, sum ret^2, sum (ret - v),
+    sum (ret - v)^2; d = log pi - log pi_old, r = exp(d)) -> the update diagnostics of those samples.  approx_kl is the k3 estimator, mean of r - 1 - log r;
+    explained_variance is 1 - Var(ret - v) / Var(ret) with population variances, NaN when Var(ret) is 0.  Host arithmetic in float64; no GPU involved."""
+    s = np.asarray(sums, np.float64).reshape(-1)
+    if s.shape[0] != N_STATS:
+        raise ValueError("update_stats_summary: expected %d sums, got %d" % (N_STATS, s.shape[0]))
+    n = float(s[0])
+    if not n > 0:
+        raise ValueError("update_stats_summary: the sums hold no sample")
+    var_ret = s[6] / n - (s[5] / n) ** 2
+    var_err = s[8] / n - (s[7] / n) ** 2
+    return {"samples": int(round(n)), "approx_kl": float(s[2] / n), "approx_kl_k1": float(-s[1] / n), "clip_fraction": float(s[3] / n), "ratio_mean": float(s[4] / n),
+            "value_mse": float(s[8] / n), "explained_variance": float(1.0 - var_err / var_ret) if var_ret > 0 else float("nan")}
+
+
 class PpoDevice:
     def __init__(self, input_dim, num_actions, action_low, action_high, clip_eps, value_scale, entropy_scale,
                  hidden=(500, 300), max_batch=256, device=None, precision="fp32"):
@@ -186,6 +205,19 @@ class PpoDevice:
         self.ensure_batch(M)
         p = milib.ptr
         self.L.mi_ppo_logp_old(self.handle, self.stream(), p(states), p(actions), int(M), p(out))
+
+    def update_stats(self, states, actions, returns, logp_old, row_idx, M, stats, scratch, accumulate=False, logp_new_out=None, value_out=None):
+        """The N_STATS sums of the update diagnostics (mi_ppo_update_stats_idx; update_stats_summary turns them into a dict) over rows `row_idx` (int32 device tensor
+        [M]) of the horizon-batch tables under the CURRENT parameters, into `stats` (float64 device tensor [N_STATS]; accumulate: added to it).  scratch: float64
+        device tensor of stats_scratch_doubles(M) entries.  logp_new_out / value_out: float32 tables of states.shape[0] entries, written at the named rows only.
+        Forward only: parameters, optimiser state, gradients and the losses buffer keep their contents."""
+        self.ensure_batch(M)
+        p = milib.ptr
+        self.L.mi_ppo_update_stats_idx(self.handle, self.stream(), p(states), p(actions), p(returns), p(logp_old), p(row_idx), int(states.shape[0]), int(M),
+                                       1 if accumulate else 0, p(scratch), p(stats), p(logp_new_out), p(value_out))
+
+    def stats_scratch_doubles(self, M):
+        return int(self.L.mi_ppo_update_stats_scratch_doubles(int(M)))
 
     def apply_adam(self, alpha, beta1=0.9, beta2=0.999, epsilon=1e-8):
         self.L.mi_ppo_apply_adam(self.handle, self.stream(), float(alpha), float(beta1), float(beta2), float(epsilon))

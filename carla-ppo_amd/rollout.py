@@ -79,6 +79,17 @@ of the episode's last step; update() then bootstraps that segment from it (mi_ro
 
 A collection on which truncate() is never called takes the path it always took (mi_rollout_finish_segments, the same launches).
 
+Both buffers can watch how far an update moves the policy.  update_with_diagnostics() is update() plus one forward-only statistics pass over all valid rows after
+every epoch (mi_ppo_update_stats_idx: the current policy against the cached log pi_old; ordered double-precision sums, bitwise reproducible), and target_kl ends the
+epochs once the approximate KL to the old policy (k3, mean of r - 1 - log r) is greater than it:
+
+    out = buf.update_with_diagnostics(num_epochs=10, batch_size=32, target_kl=0.03)
+    for e in out["epochs"]:                                        # one dict per epoch that ran
+        print(e["approx_kl"], e["clip_fraction"], e["explained_variance"])
+    out["epochs_run"], out["stopped_early"]                        # e.g. 4, True
+
+update() itself is unchanged: the same launches, the same numpy RNG draws, the same keys.
+
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import os
@@ -459,6 +470,15 @@ class SegmentedRows(RolloutRows):
         return self.truncs[segs[:, 0], segs[:, 1] + segs[:, 2] - 1].astype(np.int32)
 
 
+def _diagnostics(who, target_kl):
+    """The checked arguments of update_with_diagnostics (raises before any device work): target_kl is None or a positive finite float."""
+    if target_kl is not None:
+        if isinstance(target_kl, (bool, str)) or not isinstance(target_kl, (int, float, np.integer, np.floating)) or not np.isfinite(target_kl) or not target_kl > 0:
+            raise ValueError("%s.update_with_diagnostics: target_kl is None or a positive finite float, got %r" % (who, target_kl))
+        target_kl = float(target_kl)
+    return {"target_kl": target_kl}
+
+
 class _RecordingStep(BatchedRolloutStep):
     """The step of a RolloutBuffer: BatchedRolloutStep with room for the int32 table rows in its input buffer, called through check() and record(.., table_rows, tables)."""
 
@@ -516,16 +536,32 @@ class RolloutBuffer:
         """One PPO update from the tables (train.py:175-207 over the recorded rows): mi_rollout_finish, update_old_policy, log pi_old once, num_epochs x shuffled
         minibatches of batch_size (the last one partial) with the gather inside the step's kernels.  Returns the per-minibatch loss records (replay_update's keys),
         `lengths`, and fp64 `returns` / `advantages` / `raw_advantages` and fp32 `values` as [num_envs, T] arrays, NaN beyond a row's length."""
+        return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, None)
+
+    def update_with_diagnostics(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, stage_times=None, target_kl=None):
+        """update() that also OBSERVES every epoch: after an epoch's last minibatch one forward-only statistics pass (mi_ppo_update_stats_idx) runs over all valid rows of
+        the tables `states`, `actions`, `returns`, `logp_old` in chunks of at most 4096 entries of valid_rows() (the first stores its sums, the later ones add to them),
+        with one readback per epoch.  The result gains `epochs`, one dict per epoch that ran (mi355.ppo_device.update_stats_summary: samples, approx_kl -- the k3
+        estimator, mean of r - 1 - log r against the old policy --, approx_kl_k1, clip_fraction, ratio_mean, value_mse, explained_variance), `epochs_run` and
+        `stopped_early`; `stage_times` gains a "stats" stage.  The pass changes nothing the SGD steps read: parameters and losses are bitwise those of update() on the
+        same inputs and numpy seed.
+        target_kl (None, or a positive finite float): after an epoch whose approx_kl is greater than target_kl -- a plain `>`; other libraries stop at 1.5 x their
+        target_kl, so pass 1.5 x theirs to compare -- no further epoch runs and `stopped_early` is True.  np.random.shuffle is then called once per epoch that RAN, so
+        the legacy numpy stream is left where an update of `epochs_run` epochs leaves it.
+        Needs the cached log pi_old, i.e. the fused kernels (PpoDevice.fused_ok()): ValueError otherwise, before anything is launched or changed."""
+        return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, _diagnostics(type(self).__name__, target_kl))
+
+    def _run_update(self, gamma, lam, num_epochs, batch_size, stage_times, diag):
         def finish(st, r, d, lengths, f64):
             import torch
             ln = torch.from_numpy(lengths).to(self.device)
             self.L.mi_rollout_finish(st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), ln.data_ptr(), self.num_envs, self.horizon, float(gamma), float(lam),
                                      self.returns.data_ptr(), self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
-        return self._update(finish, num_epochs, batch_size, stage_times)
+        return self._update(finish, num_epochs, batch_size, stage_times, diag)
 
-    def _update(self, finish, num_epochs, batch_size, stage_times):
+    def _update(self, finish, num_epochs, batch_size, stage_times, diag=None):
         """What every buffer's update does around its finish call `finish(stream, rewards, dones, lengths, f64)` (device rewards / dones, fp64 [3, E, T] of NaN for the raw
-        advantages, returns and normalised advantages)."""
+        advantages, returns and normalised advantages).  diag: None, or update_with_diagnostics' {"target_kl": None or float}."""
         import time
         import torch
         from mi355 import dist as midist
@@ -534,6 +570,9 @@ class RolloutBuffer:
             raise ValueError(who + ".update: single rank only (ragged rows give ranks different numbers of gradient all-reduces)")
         if int(batch_size) < 1 or int(num_epochs) < 0:
             raise ValueError(who + ".update: batch_size >= 1, num_epochs >= 0")
+        if diag is not None and not self.ppo._need_dev().fused_ok():
+            raise ValueError(who + ".update_with_diagnostics: the statistics pass reads the cached log pi_old, which only the fused kernels fill "
+                             "(this policy's shape is outside their range or MI355_PPO_FUSED=0)")
         self.rows.check_update()
         batch_size = int(batch_size)
         E, T, ppo, device = self.num_envs, self.horizon, self.ppo, self.device
@@ -566,6 +605,13 @@ class RolloutBuffer:
                     pdev.logp_old(self.states[lo:hi], self.actions[lo:hi], hi - lo, self.logp_old[lo:hi])
         t_stage = mark("logp_old", t_stage)
         records = []
+        if diag is not None:
+            from mi355.ppo_device import N_STATS, update_stats_summary
+            chunk = 4096
+            valid_dev = torch.from_numpy(valid).to(device)
+            stats = torch.zeros(N_STATS, dtype=torch.float64, device=device)
+            stats_scratch = torch.empty(pdev.stats_scratch_doubles(min(n_valid, chunk)), dtype=torch.float64, device=device)
+            epochs, stopped = [], False
         for _ in range(int(num_epochs)):
             indices = np.arange(n_valid)
             np.random.shuffle(indices)                                               # legacy numpy RNG, as train.py:194-195
@@ -576,14 +622,27 @@ class RolloutBuffer:
                 ppo._step_rows(self.states, self.actions, self.returns, self.advantages, logp_old, mb, m, m)
                 ppo.train_step_counter += 1
                 records.append(pdev.losses.clone())
+            if diag is not None:                                                     # observe the epoch: all valid rows under the parameters it ended with
+                t_stage = mark("sgd", t_stage)
+                for lo in range(0, n_valid, chunk):
+                    rows = valid_dev[lo:lo + chunk]
+                    pdev.update_stats(self.states, self.actions, self.returns, self.logp_old, rows, int(rows.numel()), stats, stats_scratch, accumulate=lo > 0)
+                epochs.append(update_stats_summary(stats.cpu().numpy()))             # the epoch's one readback
+                t_stage = mark("stats", t_stage)
+                if diag["target_kl"] is not None and epochs[-1]["approx_kl"] > diag["target_kl"]:
+                    stopped = True
+                    break
         losses = torch.stack(records).cpu().numpy() if records else np.zeros((0, 5), np.float32)
         mark("sgd", t_stage)
         keys = ("policy_loss", "value_loss", "entropy_loss", "loss", "prob_ratio")
         f64 = f64.cpu().numpy()
         v_all = self.values.view(E, T + 1).cpu().numpy()
         values = np.where(np.arange(T)[None, :] < lengths[:, None], v_all[:, :T], np.float32(np.nan)).astype(np.float32)
-        return {"losses": [dict(zip(keys, (float(x) for x in row))) for row in losses], "lengths": lengths, "raw_advantages": f64[0], "returns": f64[1],
-                "advantages": f64[2], "values": values, "bootstrap_values": np.where(lengths > 0, v_all[np.arange(E), lengths], np.float32(np.nan)).astype(np.float32), "samples": n_valid}
+        out = {"losses": [dict(zip(keys, (float(x) for x in row))) for row in losses], "lengths": lengths, "raw_advantages": f64[0], "returns": f64[1],
+               "advantages": f64[2], "values": values, "bootstrap_values": np.where(lengths > 0, v_all[np.arange(E), lengths], np.float32(np.nan)).astype(np.float32), "samples": n_valid}
+        if diag is not None:
+            out["epochs"], out["epochs_run"], out["stopped_early"] = epochs, len(epochs), stopped
+        return out
 
 
 class ContinuousRolloutBuffer(RolloutBuffer):
@@ -622,6 +681,13 @@ class ContinuousRolloutBuffer(RolloutBuffer):
         "batch" (mean and population std over all samples of the update: a 1-step tail segment's advantage is not forced to 0).  Returns RolloutBuffer.update's keys,
         `segments` (SegmentedRows.segments()), `segment_truncated` (SegmentedRows.segment_truncated()) and `final_values`, float32 [num_envs, T]: the value a truncated
         step's segment bootstrapped from, NaN where no truncation was recorded; `bootstrap_values` is NaN for lanes whose last step reported done or was truncated."""
+        return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, None, normalize)
+
+    def update_with_diagnostics(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, normalize="segment", stage_times=None, target_kl=None):
+        """This class's update() with RolloutBuffer.update_with_diagnostics' per-epoch statistics pass, `epochs` / `epochs_run` / `stopped_early` and target_kl."""
+        return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, _diagnostics(type(self).__name__, target_kl), normalize)
+
+    def _run_update(self, gamma, lam, num_epochs, batch_size, stage_times, diag, normalize="segment"):
         if normalize not in ("segment", "batch"):
             raise ValueError("ContinuousRolloutBuffer.update: normalize is 'segment' or 'batch'")
         segs = self.rows.segments()
@@ -644,7 +710,7 @@ class ContinuousRolloutBuffer(RolloutBuffer):
             else:
                 self.L.mi_rollout_finish_segments(*args)
         last_done = self.rows._last_done()
-        out = self._update(finish, num_epochs, batch_size, stage_times)
+        out = self._update(finish, num_epochs, batch_size, stage_times, diag)
         out["segments"], out["segment_truncated"] = segs, seg_trunc
         out["bootstrap_values"] = np.where(last_done, np.float32(np.nan), out["bootstrap_values"]).astype(np.float32)
         final = np.full(truncs.shape, np.nan, np.float32)

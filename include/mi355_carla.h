@@ -515,6 +515,27 @@ int mi_ppo_logp_old(void* h, void* stream, const float* states, const float* act
 int mi_ppo_set_precision(void* h, int dtype);
 /* the engine's current precision (MI_F32 or MI_BF16X3) — ppo.py:42-66,112-147,218-229 */
 int mi_ppo_precision(void* h);
+/* per-epoch update diagnostics: how far the CURRENT policy theta has moved from the old one on M rows of the horizon-batch tables, and how well the value net
+ * fits the returns -- one forward-only pass (policy and value trunks of theta in the engine's precision mode, one head kernel, one ordered reduction; four
+ * launches, no backward, no optimiser).  Sample m is row row_idx[m] (int32, device; clamped into [0, n_rows)) of states / actions / returns / logp_old, gathered
+ * inside the kernels as in mi_ppo_train_step_idx; 1 <= M <= max_batch.  logp_old is the cache mi_ppo_logp_old filled: log pi_old(a|s) per table row.  Per sample
+ *   lp = log pi(a|s) under theta (fp32, the arithmetic and summation order of mi_ppo_logp_old: with theta == theta_old it equals logp_old bit for bit),
+ *   v = h2_v Wv + bv (fp32), and in double precision  d = lp - logp_old,  r = exp(d),  ret = returns[row];
+ * stats [MI_PPO_N_STATS] (double, device) receives the sums over the M samples of
+ *   [0] 1 (the count)   [1] d   [2] r - 1 - d   [3] 1 where |r - 1| > clip_eps (the engine's), else 0   [4] r   [5] ret   [6] ret^2   [7] ret - v   [8] (ret - v)^2
+ * so that [2] / [0] is the k3 estimator of KL(pi_old || pi), the mean of r - 1 - log r; -[1] / [0] the k1 estimator; [3] / [0] the clipped fraction; [4] / [0] the
+ * mean ratio; [8] / [0] the value error; 1 - Var(ret - v) / Var(ret) from [5]..[8] the explained variance.  The reduction is ordered (no atomics): every block of
+ * 32 samples stores its partial sums to scratch (mi_ppo_update_stats_scratch_doubles(M) doubles, device), one wave adds them in block order; two runs on the same
+ * inputs give bitwise equal stats.  accumulate 0: stats is overwritten; accumulate 1: the sums are added to what stats holds -- a caller covers more than
+ * max_batch rows as a chain of calls, the first with 0.  logp_new_out / value_out (each may be NULL): tables of n_rows floats, lp / v of sample m goes to entry
+ * row_idx[m], every other entry is left alone.  NOT modified: parameters, theta_old, the optimiser state, the gradient buffer, the losses and action_mean buffers
+ * (mi_ppo_buffer) -- only the engine's activation workspace, scratch, stats and the two optional tables are written.  A row that row_idx does not name is not
+ * read, except that layer 1 (as in mi_ppo_train_step_idx) reads the first few state entries of the table row behind a named one against zero weights: those must
+ * be finite.  MI_ERR_STATE: null handle; MI_ERR_ARG: M outside [1, max_batch], n_rows < 1, a missing buffer (named in the message), accumulate not 0 / 1;
+ * MI_ERR_SHAPE: mi_ppo_fused_shape_ok(h) is 0 (there is no per-layer form of this pass). */
+#define MI_PPO_N_STATS 9
+long long mi_ppo_update_stats_scratch_doubles(int M);
+int mi_ppo_update_stats_idx(void* h, void* stream, const float* states, const float* actions, const float* returns, const float* logp_old, const int* row_idx, int n_rows, int M, int accumulate, double* scratch, double* stats, float* logp_new_out, float* value_out);
 
 #ifdef __cplusplus
 }

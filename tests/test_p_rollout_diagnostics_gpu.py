@@ -1,0 +1,363 @@
+"""Update diagnostics on the GPU (mi_ppo_update_stats_idx / PpoDevice.update_stats / RolloutBuffer.update_with_diagnostics and its target_kl).
+a. identity at theta == theta_old: log pi of the statistics pass is the cached log pi_old bit for bit, the KL sums are exactly 0;
+b. the ordered reduction against numpy float64 sums of the device's own per-row values (1e-9 relative, counts exact), run-to-run bitwise, what the call must not
+   write and must not read, for M = 1, 31, 33, 70 and a chain of 32 + 32 + 6 rows;
+c. the statistics against a float64 evaluation of the exported parameters (oracle.ppo_oracle), fp32 and bf16x3 mode;
+d. the buffers: diagnostics observe only (parameters and losses bitwise those of update()), every epoch record against a direct evaluation, and the early stop.
+Set-up of the buffers and tolerances between device paths are rollout_gpu_common.py's.  Synthetic tables (b, c): the float64 probe of the issue -- OraclePPO seed 2,
+learning rate 3e-4, 67 N(0, 1) inputs, 64 samples in minibatches of 16, four epochs."""
+import math
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+from oracle import ppo_oracle as po  # noqa: E402
+from rollout_gpu_common import A, SENTINEL, close, inputs, make_pair, make_world, tables  # noqa: E402
+from test_rollout_diagnostics_host import sums_of  # noqa: E402
+
+E, T, BATCH = 4, 16, 16
+N_ROWS, TRAINED, POOL = 96, 64, 90                       # synthetic tables: rows, rows the SGD steps train on (the first ones), rows a row_idx may name (the first ones)
+NAN_ROW = 93                                             # never named, and neither is the row in front of it (layer 1 reads the first kin - input_dim state entries of
+                                                         # the row BEHIND a named one against zero weight rows, as in mi_ppo_train_step_idx: those must be finite)
+LR = 3e-4                                                # the default learning rate (make_pair's own default is 1e-4)
+EPS = 0.2
+STAT_KEYS = ("approx_kl", "approx_kl_k1", "ratio_mean", "value_mse", "explained_variance")
+# Tolerances of c, relative to float64.  The goal is 1e-4; the project's rule where a statistic misses it: max(1e-4, 4 x the distance of the fp32 torch-CPU evaluation
+# of the same formulas from float64).  Measured on this case (fp32 torch-CPU | device fp32 mode | device bf16x3 mode), see profiles/r14_rollout_diagnostics.md:
+STAT_MEASURED = {
+    "approx_kl": (6.9e-8, 1.8e-7, 7.5e-8), "approx_kl_k1": (8.6e-7, 7.3e-7, 9.7e-7), "ratio_mean": (7.7e-8, 5.2e-8, 7.8e-8), "value_mse": (4.1e-7, 1.0e-7, 7.6e-7),
+    "explained_variance": (1.4e-8, 3.8e-9, 3.4e-8),
+}                                                        # per-row log pi against float64: 9.6e-8 (fp32 mode), 4.3e-7 (bf16x3) of max |log pi|; no sample near the threshold
+STAT_TOL = {k: max(1e-4, 4 * STAT_MEASURED[k][0]) for k in STAT_KEYS}               # every statistic meets the goal: 1e-4
+# bf16x3: the rule of tests/test_j_ppo_bf16x3_gpu.py -- 1e-4, else 4 x the fp32 mode's measured distance
+STAT_TOL_X3 = {k: max(1e-4, 4 * STAT_MEASURED[k][1]) for k in STAT_KEYS}            # 1e-4 as well
+# d: numpy seeds of the update cases.  The early stop needs kl[1] > kl[0] (asserted): measured 5.2e-3 then 2.9e-2 (RolloutBuffer, seed 2) and 1.1e-3 then 1.8e-2
+# (ContinuousRolloutBuffer, seed 5); of the seeds 0 .. 7, two and one have that order on these collections
+SEED_BUFFER, SEED_CONTINUOUS = 2, 5
+
+
+@pytest.fixture(scope="module")
+def world(tmp_path_factory):
+    return make_world(tmp_path_factory, "rollout_diagnostics", policy=False)
+
+
+def make_tables(o, seed=11):
+    """float32 host tables of N_ROWS rows: N(0, 1) states, actions the (initial) policy samples for them, returns around its values, normalised advantages."""
+    rng = np.random.RandomState(seed)
+    s = rng.standard_normal((N_ROWS, 67)).astype(np.float32)
+    a, v = o.predict(s, greedy=False, noise=rng.standard_normal((N_ROWS, A)).astype(np.float32))
+    ret = (v + 0.5 * rng.standard_normal(N_ROWS)).astype(np.float32)
+    adv = rng.standard_normal(N_ROWS)
+    return s, np.asarray(a, np.float32), ret, ((adv - adv.mean()) / adv.std()).astype(np.float32)
+
+
+def schedule(seed=2):
+    np.random.seed(seed)
+    return po.minibatch_schedule(TRAINED, 16, 4)
+
+
+class Trained:
+    """A device policy after the probe's update on device tables: update_old_policy, the log pi_old cache, 4 epochs x 4 minibatches of 16 over rows 0 .. 63."""
+
+    def __init__(self, tmp, precision=None):
+        import torch
+        from mi355.ppo_device import N_STATS
+        self.o, self.m = make_pair(tmp, precision=precision, learning_rate=LR)
+        self.pdev = self.m._need_dev()
+        self.host = make_tables(self.o)
+        up = lambda x: torch.from_numpy(x).to(self.pdev.device)      # noqa: E731
+        self.s, self.a, self.ret, self.adv = (up(x) for x in self.host)
+        self.lpo = torch.zeros(N_ROWS, device=self.pdev.device)
+        self.m.update_old_policy()
+        self.pdev.logp_old(self.s, self.a, N_ROWS, self.lpo)
+        for mb in schedule():
+            rows = up(mb.astype(np.int32))
+            self.m._step_rows(self.s, self.a, self.ret, self.adv, self.lpo, rows, len(mb), len(mb))
+        self.stats = torch.full((N_STATS,), SENTINEL, dtype=torch.float64, device=self.pdev.device)
+        self.scratch = torch.zeros(self.pdev.stats_scratch_doubles(N_ROWS), dtype=torch.float64, device=self.pdev.device)
+
+    def run(self, rows, accumulate=False, outs=None, tabs=None):
+        """One update_stats call over table rows `rows` -> the nine sums (host)."""
+        import torch
+        rows_d = torch.from_numpy(np.asarray(rows, np.int32)).to(self.pdev.device)
+        s, a, ret, lpo = tabs or (self.s, self.a, self.ret, self.lpo)
+        lp_out, v_out = outs or (None, None)
+        self.pdev.update_stats(s, a, ret, lpo, rows_d, len(rows), self.stats, self.scratch, accumulate=accumulate, logp_new_out=lp_out, value_out=v_out)
+        torch.cuda.synchronize()
+        return self.stats.cpu().numpy().copy()
+
+
+@pytest.fixture(scope="module")
+def trained(tmp_path_factory):
+    return Trained(tmp_path_factory.mktemp("diag_trained"))
+
+
+def state_of(pdev):
+    return [x.clone() for x in (pdev.params, pdev.params_old, pdev.adam_m, pdev.adam_v, pdev.grads, pdev.losses, pdev.action_mean)]
+
+
+def same_state(pdev, before):
+    import torch
+    return all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(state_of(pdev), before))      # bitwise (NaN-proof)
+
+
+def collect(world, tmp, continuous=False, precision=None, seed=571):
+    """A full E x T collection through the buffer's own step.  continuous: lane 1 reports a done at its step 6, lane 2 is truncated behind its step 9."""
+    from rollout import ContinuousRolloutBuffer, RolloutBuffer
+    _, m = make_pair(tmp, precision=precision, learning_rate=LR)
+    buf = (ContinuousRolloutBuffer if continuous else RolloutBuffer)(world["vae"], m, E, T)
+    rng = np.random.RandomState(seed)
+    buf.reset()
+    for t in range(1, T + 1):
+        f, ms, nz = inputs(rng, E)
+        buf.step(f, ms, noise=nz)
+        buf.outcome(rng.uniform(0, 1, E), np.array([continuous and e == 1 and t == 6 for e in range(E)]))
+        if continuous and t == 9:
+            f, ms, _ = inputs(rng, 1)
+            buf.truncate(f, ms, env_ids=np.array([2]))
+    f, ms, _ = inputs(rng, E)
+    if continuous:
+        need = buf.rows.needs_bootstrap()
+        buf.bootstrap(f[need], ms[need], env_ids=need)
+        assert buf.rows.segments().tolist() == [[0, 0, 16], [1, 0, 6], [1, 6, 10], [2, 0, 9], [2, 9, 7], [3, 0, 16]]
+    else:
+        buf.bootstrap(f, ms)
+    return m, buf
+
+
+def direct_stats(buf, pdev):
+    """The statistics of all valid rows of a buffer's tables under the policy's current parameters, by a direct call -> (sums, log pi table, value table)."""
+    import torch
+    from mi355.ppo_device import N_STATS
+    valid = buf.rows.valid_rows()
+    rows = torch.from_numpy(valid).to(buf.device)
+    stats = torch.zeros(N_STATS, dtype=torch.float64, device=buf.device)
+    scratch = torch.zeros(pdev.stats_scratch_doubles(len(valid)), dtype=torch.float64, device=buf.device)
+    lp, v = torch.full_like(buf.logp_old, SENTINEL), torch.full_like(buf.logp_old, SENTINEL)
+    pdev.update_stats(buf.states, buf.actions, buf.returns, buf.logp_old, rows, len(valid), stats, scratch, logp_new_out=lp, value_out=v)
+    torch.cuda.synchronize()
+    return stats.cpu().numpy(), lp.cpu().numpy(), v.cpu().numpy()
+
+
+def test_identity_at_theta_equal_theta_old(world, tmp_path):
+    """fp32 mode, after update(num_epochs=0) (the finish, update_old_policy and the log pi_old fill): the pass reproduces the cache bit for bit."""
+    from mi355.ppo_device import update_stats_summary
+    m, buf = collect(world, tmp_path / "m")
+    out = buf.update(num_epochs=0)
+    assert out["samples"] == E * T and out["losses"] == []
+    valid = buf.rows.valid_rows()
+    sums, lp, v = direct_stats(buf, m.dev)
+    lpo = buf.logp_old.cpu().numpy()
+    assert np.array_equal(lp[valid].view(np.int32), lpo[valid].view(np.int32))
+    other = np.setdiff1d(np.arange(len(lp)), valid)
+    assert len(other) == E and np.all(lp[other] == SENTINEL) and np.all(v[other] == SENTINEL)
+    assert sums[0] == E * T and sums[1] == 0.0 and sums[2] == 0.0 and sums[3] == 0.0 and sums[4] == float(E * T)
+    rec = update_stats_summary(sums)
+    assert rec["approx_kl"] == 0.0 and rec["approx_kl_k1"] == 0.0 and rec["clip_fraction"] == 0.0 and rec["ratio_mean"] == 1.0 and rec["samples"] == E * T
+    v_step = tables(buf)[2]
+    print("\nvalue_out against the recording step's values: max |diff| = %.3e" % np.abs(v[valid] - v_step[valid]).max())
+    assert close([v[valid]], [v_step[valid]], 1e-5)
+    ret = buf.returns.cpu().numpy()[valid].astype(np.float64)
+    want = sums_of(lp[valid].astype(np.float64), lpo[valid].astype(np.float64), ret, v[valid].astype(np.float64), EPS)
+    assert np.allclose(sums, want, rtol=1e-9, atol=0)
+
+
+def row_cases():
+    rng = np.random.RandomState(77)
+    perm = rng.permutation(POOL)
+    return {M: perm[:M].astype(np.int32) for M in (1, 31, 33, 70)}
+
+
+@pytest.mark.parametrize("M", [1, 31, 33, 70, "chained"])
+def test_reduction_against_numpy_and_what_the_call_leaves_alone(trained, M):
+    import torch
+    tr = trained
+    rows = row_cases()[70 if M == "chained" else M]
+    assert NAN_ROW not in rows and NAN_ROW - 1 not in rows and rows.max() < POOL and len(np.unique(rows)) == len(rows)
+    dev = tr.pdev.device
+    lp_d, v_d = torch.full((N_ROWS,), SENTINEL, device=dev), torch.full((N_ROWS,), SENTINEL, device=dev)
+    tr.run(np.arange(N_ROWS, dtype=np.int32))                 # (the engine grows to the largest batch of this module before the state is snapshotted)
+    before = state_of(tr.pdev)
+
+    def run(tabs=None, outs=(lp_d, v_d)):
+        if M != "chained":
+            return tr.run(rows, outs=outs, tabs=tabs)
+        tr.stats.fill_(SENTINEL)
+        for i, lo in enumerate((0, 32, 64)):                 # 32 + 32 + 6
+            got = tr.run(rows[lo:lo + 32], accumulate=i > 0, outs=outs, tabs=tabs)
+        return got
+    sums = run()
+    assert same_state(tr.pdev, before)                       # parameters, theta_old, Adam slots, grads, the losses and action_mean buffers: bitwise what they were
+    lp, v = lp_d.cpu().numpy(), v_d.cpu().numpy()
+    other = np.setdiff1d(np.arange(N_ROWS), rows)
+    assert np.all(lp[other] == SENTINEL) and np.all(v[other] == SENTINEL) and np.all(lp[rows] != SENTINEL) and np.all(v[rows] != SENTINEL)
+    lpo, ret = tr.lpo.cpu().numpy(), tr.host[2]
+    d = lp[rows].astype(np.float64) - lpo[rows].astype(np.float64)
+    r = np.exp(d)
+    gap = np.abs(np.abs(r - 1) - np.float64(np.float32(EPS))).min()
+    assert gap >= 1e-9, gap                                  # no sample on the clip threshold: the two counts are comparable
+    want = sums_of(lp[rows].astype(np.float64), lpo[rows].astype(np.float64), ret[rows].astype(np.float64), v[rows].astype(np.float64), np.float64(np.float32(EPS)))
+    rel = np.abs(sums - want) / np.maximum(np.abs(want), 1e-300)
+    print("\nM = %s: sums %s\n  against numpy float64, relative: %s" % (M, sums, rel))
+    assert sums[0] == want[0] == len(rows) and sums[3] == want[3]
+    for k in (1, 2, 4, 5, 6, 7, 8):
+        assert abs(sums[k] - want[k]) <= 1e-9 * abs(want[k]), (k, sums[k], want[k])
+    if len(rows) > 8:
+        assert 0 < sums[3] < len(rows) and sums[2] / sums[0] > 1e-3      # the policy has moved: not the identity case
+    again = run()
+    assert np.array_equal(sums.view(np.int64), again.view(np.int64))     # two runs: bitwise equal
+    assert np.array_equal(run(outs=None).view(np.int64), sums.view(np.int64))      # without the two optional tables
+    # a NaN in a row row_idx does not name changes nothing
+    tabs = [x.clone() for x in (tr.s, tr.a, tr.ret, tr.lpo)]
+    for x in tabs:
+        x[NAN_ROW] = float("nan")
+    tabs[1][other] = float("nan")                            # actions, returns, log pi_old: every row that is not named
+    tabs[2][other] = float("nan")
+    tabs[3][other] = float("nan")
+    poisoned = run(tabs=tabs)
+    assert np.array_equal(poisoned.view(np.int64), sums.view(np.int64))
+    assert same_state(tr.pdev, before)
+    assert np.array_equal(lp_d.cpu().numpy().view(np.int32), lp.view(np.int32)) and np.array_equal(v_d.cpu().numpy().view(np.int32), v.view(np.int32))
+
+
+def test_argument_errors_that_need_an_engine(trained):
+    import torch
+    tr = trained
+    L, pdev = tr.pdev.L, tr.pdev
+    p = lambda t: t.data_ptr()      # noqa: E731
+    rows = torch.zeros(8, dtype=torch.int32, device=pdev.device)
+    tr.stats.fill_(SENTINEL)
+    assert L.cdll.mi_ppo_update_stats_idx(pdev.handle, None, p(tr.s), p(tr.a), p(tr.ret), p(tr.lpo), p(rows), N_ROWS, pdev.max_batch + 1, 0, p(tr.scratch), p(tr.stats),
+                                          None, None) == -1
+    assert L.cdll.mi_last_error().startswith(b"mi_ppo_update_stats_idx: batch outside [1, max_batch]")
+    torch.cuda.synchronize()
+    assert bool((tr.stats == SENTINEL).all())                # nothing was launched
+
+
+def float64_reference(tr, rows):
+    """-> dict of the float64 statistics, per-row float64 log pi, and the distance of the fp32 torch-CPU evaluation of the same formulas from it."""
+    import torch
+    from mi355.ppo_device import update_stats_summary
+    new, old = tr.pdev.export_params(), tr.pdev.export_old()
+    s, a, ret = tr.host[0][rows], tr.host[1][rows], tr.host[2][rows]
+    space = po.ActionSpace()
+    out = {}
+    for dt in (torch.float64, torch.float32):
+        with torch.no_grad():
+            t = lambda x: po._t(np.asarray(x, np.float32), dt)      # noqa: E731
+            mean, logstd, value = po.policy_forward({k: t(v) for k, v in new.items()}, t(s), space.low, space.high)
+            mean_o, logstd_o, _ = po.policy_forward({k: t(v) for k, v in old.items()}, t(s), space.low, space.high, "policy_old")
+            lp = po.normal_log_prob(t(a), mean, logstd).sum(dim=-1)
+            lpo = po.normal_log_prob(t(a), mean_o, logstd_o).sum(dim=-1)
+            if dt == torch.float32:                            # the same formulas in fp32: ratio, terms and sums
+                d = lp - lpo
+                r = torch.exp(d)
+                e = t(ret) - value
+                eps = torch.tensor(EPS, dtype=dt)
+                sums = [float(len(rows)), d.sum(), (r - 1 - d).sum(), (torch.abs(r - 1) > eps).sum(), r.sum(), t(ret).sum(), (t(ret) * t(ret)).sum(), e.sum(), (e * e).sum()]
+                out[dt] = update_stats_summary(np.array([float(x) for x in sums]))
+            else:
+                lp64, lpo64, v64 = lp.numpy(), lpo.numpy(), value.numpy()
+                out[dt] = update_stats_summary(sums_of(lp64, lpo64, ret.astype(np.float64), v64, np.float64(np.float32(EPS))))
+    r64 = np.exp(lp64 - lpo64)
+    near = int((np.abs(np.abs(r64 - 1) - np.float64(np.float32(EPS))) < 1e-4).sum())
+    return out[torch.float64], out[torch.float32], lp64, near
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+def test_statistics_against_float64(trained, tmp_path, precision):
+    import torch
+    from mi355.ppo_device import update_stats_summary
+    tr = trained if precision == "fp32" else Trained(tmp_path / "x3", precision="bf16x3")
+    assert tr.pdev.precision == precision
+    rows = np.arange(TRAINED, dtype=np.int32)
+    lp_d = torch.full((N_ROWS,), SENTINEL, device=tr.pdev.device)
+    got = update_stats_summary(tr.run(rows, outs=(lp_d, None)))
+    want, want32, lp64, near = float64_reference(tr, rows)
+    lp = lp_d.cpu().numpy()[rows].astype(np.float64)
+    err_lp = np.abs(lp - lp64).max() / np.abs(lp64).max()
+    print("\n%s: float64 reference %s\n  device %s" % (precision, want, got))
+    print("  per-row log pi: max |diff| / max |log pi| = %.3e; samples within 1e-4 of the clip threshold: %d" % (err_lp, near))
+    # the case is not degenerate
+    assert want["approx_kl"] >= 1e-2 and 0.05 < want["clip_fraction"] < 0.95, want
+    assert err_lp <= 1e-4, err_lp
+    tol = STAT_TOL if precision == "fp32" else STAT_TOL_X3
+    dist = {}
+    for k in STAT_KEYS:
+        dist[k] = abs(got[k] - want[k]) / abs(want[k])
+        print("  %-20s device %.3e, fp32 torch-CPU %.3e from float64 (relative); bound %.1e" % (k, dist[k], abs(want32[k] - want[k]) / abs(want[k]), tol[k]))
+    assert near <= 2, near
+    assert abs(got["clip_fraction"] - want["clip_fraction"]) * TRAINED <= near + 1e-9, (got["clip_fraction"], want["clip_fraction"], near)
+    assert got["samples"] == TRAINED == want["samples"]
+    for k in STAT_KEYS:
+        assert dist[k] <= tol[k], (k, got[k], want[k], dist[k])
+
+
+def params_of(m):
+    return [m.dev.params.clone(), m.dev.adam_m.clone(), m.dev.adam_v.clone()]
+
+
+def bitwise(x, y):
+    import torch
+    return all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(x, y))
+
+
+@pytest.mark.parametrize("continuous", [False, True])
+def test_update_with_diagnostics_observes_only_and_stops_early(world, tmp_path, continuous):
+    """Identical worlds, the same numpy seed.  1: update_with_diagnostics(4 epochs) against 2: update(4 epochs): bitwise parameters, equal losses; 3: target_kl between
+    kl[0] and kl[1] stops behind epoch 2 and is bitwise 4: update(2 epochs); 5: a target_kl above every epoch's KL runs all four."""
+    from mi355.ppo_device import update_stats_summary
+    seed = SEED_CONTINUOUS if continuous else SEED_BUFFER
+    n = E * T
+
+    source = []
+
+    def fresh(i):
+        """World i: its own policy and buffer, the same scripted collection.  The recording step's split-K layers end in fp32 atomics, so two collections of the same
+        frames can differ in the last bit (rollout_gpu_common.py): worlds 2 .. 5 take the device tables of world 1, which makes the inputs identical."""
+        m, buf = collect(world, tmp_path / ("w%d" % i), continuous)
+        mine = [buf.states, buf.actions, buf.values] + ([buf.final_values] if continuous else [])
+        if not source:
+            source.extend(x.clone() for x in mine)
+        for x, y in zip(mine, source):
+            assert close([x.cpu().numpy()], [y.cpu().numpy()], 1e-5)
+            x.copy_(y)
+        np.random.seed(seed)
+        return m, buf
+    m1, b1 = fresh(1)
+    times = {}
+    out1 = b1.update_with_diagnostics(num_epochs=4, batch_size=BATCH, stage_times=times)
+    m2, b2 = fresh(2)
+    out2 = b2.update(num_epochs=4, batch_size=BATCH)
+    assert bitwise(params_of(m1), params_of(m2)) and out1["losses"] == out2["losses"] and len(out1["losses"]) == 4 * math.ceil(n / BATCH)
+    assert set(out1) - set(out2) == {"epochs", "epochs_run", "stopped_early"} and "epochs" not in out2
+    for k in set(out2) - {"losses"}:
+        assert np.array_equal(np.asarray(out1[k]), np.asarray(out2[k]), equal_nan=True), k
+    assert len(out1["epochs"]) == 4 and out1["epochs_run"] == 4 and out1["stopped_early"] is False and out1["samples"] == n
+    assert set(times) == {"finish", "logp_old", "sgd", "stats"} and all(v > 0 for v in times.values())
+    for rec in out1["epochs"]:
+        assert rec["samples"] == out1["samples"] and all(np.isfinite(rec[k]) for k in STAT_KEYS) and 0 <= rec["clip_fraction"] <= 1
+    # the last epoch's record is the direct evaluation of the final parameters, bitwise; the earlier ones are checked in the early-stop worlds below
+    direct = update_stats_summary(direct_stats(b1, m1.dev)[0])
+    assert direct == out1["epochs"][3]
+    kl = [rec["approx_kl"] for rec in out1["epochs"]]
+    print("\ncontinuous=%s: approx_kl per epoch %s, clip fraction %s" % (continuous, kl, [rec["clip_fraction"] for rec in out1["epochs"]]))
+    assert kl[1] > kl[0] > 0, kl                             # a condition on the case (the seed)
+    # early stop
+    m3, b3 = fresh(3)
+    out3 = b3.update_with_diagnostics(num_epochs=4, batch_size=BATCH, target_kl=(kl[0] + kl[1]) / 2)
+    assert out3["epochs_run"] == 2 and out3["stopped_early"] is True and len(out3["epochs"]) == 2 and len(out3["losses"]) == 2 * math.ceil(n / BATCH)
+    assert out3["epochs"] == out1["epochs"][:2] and out3["losses"] == out1["losses"][:len(out3["losses"])]
+    draw3 = np.random.randint(1 << 30)
+    assert update_stats_summary(direct_stats(b3, m3.dev)[0]) == out1["epochs"][1]      # epoch 2's record against a direct evaluation, bitwise
+    m4, b4 = fresh(4)
+    b4.update(num_epochs=2, batch_size=BATCH)
+    assert bitwise(params_of(m3), params_of(m4))
+    assert draw3 == np.random.randint(1 << 30)               # np.random.shuffle was called once per epoch that ran: the numpy stream is where update(2 epochs) leaves it
+    m5, b5 = fresh(5)
+    out5 = b5.update_with_diagnostics(num_epochs=4, batch_size=BATCH, target_kl=2 * max(kl))
+    assert out5["epochs_run"] == 4 and out5["stopped_early"] is False and out5["epochs"] == out1["epochs"] and bitwise(params_of(m5), params_of(m1))
+    with pytest.raises(ValueError, match="target_kl is None or a positive finite float"):
+        b5.update_with_diagnostics(target_kl=0.0)

@@ -12,7 +12,12 @@ on every path; what differs is everything in front of it: upload + encode + valu
 
 drives ONE scripted set of simulators (episode lengths from a seeded geometric draw with mean N, default a third of the horizon) through rollout.RolloutBuffer (a lane is
 one episode segment: a simulator that reported done waits for the update) and through rollout.ContinuousRolloutBuffer (the simulator goes on from its reset observation),
-and prints for both: step calls per update, samples per update, samples per step call, seconds per collection and seconds per update with the stage times."""
+and prints for both: step calls per update, samples per update, samples per step call, seconds per collection and seconds per update with the stage times.
+
+    python tools/rollout_buffer_bench.py --diagnostics [--envs 64] [--steps 128] [--batch 32,2048] [--epochs 3] ...
+
+adds the same update through RolloutBuffer.update_with_diagnostics (one statistics pass per epoch, mi_ppo_update_stats_idx) to the interleaved rounds, without the
+replay paths: the "stats" stage is the cost of the passes, everything else is the plain update's."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
@@ -33,6 +38,7 @@ ap.add_argument("--pool", type=int, default=512, help="distinct random frames th
 ap.add_argument("--no-host-frames", action="store_true", help="skip replay_update from host frames (E x (T + 1) x 38400 bytes of host memory)")
 ap.add_argument("--no-box", action="store_true")
 ap.add_argument("--continuous", action="store_true", help="RolloutBuffer against ContinuousRolloutBuffer on one scripted set of simulators (no replay paths)")
+ap.add_argument("--diagnostics", action="store_true", help="RolloutBuffer.update against update_with_diagnostics in interleaved rounds (no replay paths)")
 ap.add_argument("--mean-episode", type=float, default=None, help="mean of the geometric episode lengths of --continuous (default: steps / 3)")
 args = ap.parse_args()
 
@@ -118,8 +124,8 @@ if args.continuous:
 idx = rng.randint(0, args.pool, (E, T + 1))
 meas = np.stack([rng.uniform(-1, 1, (E, T + 1)), rng.uniform(0, 1, (E, T + 1)), rng.uniform(0, 30, (E, T + 1))], axis=-1).astype(np.float32)
 rewards, dones = rng.uniform(0, 1, (E, T)), np.zeros((E, T))
-frames_d = torch.from_numpy(pool).to("cuda")[torch.from_numpy(idx).to("cuda")]           # [E, T + 1, 80, 160, 3] uint8 in HBM
-frames_h = None if args.no_host_frames else pool[idx]
+frames_d = None if args.diagnostics else torch.from_numpy(pool).to("cuda")[torch.from_numpy(idx).to("cuda")]           # [E, T + 1, 80, 160, 3] uint8 in HBM
+frames_h = None if args.no_host_frames or args.diagnostics else pool[idx]
 
 buf = RolloutBuffer(vae, agent, E, T)
 
@@ -146,6 +152,8 @@ def run(path, batch):
     t0 = time.perf_counter()
     if path == "buffer":
         buf.update(num_epochs=args.epochs, batch_size=batch, stage_times=st)
+    elif path == "buffer + diagnostics":
+        buf.update_with_diagnostics(num_epochs=args.epochs, batch_size=batch, stage_times=st)
     else:
         replay.replay_update(vae, agent, frames_h if path == "replay, host frames" else frames_d, meas, actions, rewards, dones, num_epochs=args.epochs, batch_size=batch, stage_times=st)
     torch.cuda.synchronize()
@@ -153,6 +161,8 @@ def run(path, batch):
 
 
 paths = ["buffer", "replay, device frames"] + ([] if frames_h is None else ["replay, host frames"])
+if args.diagnostics:
+    paths = ["buffer", "buffer + diagnostics"]
 for batch in [int(x) for x in args.batch.split(",") if x]:
     for p in paths:
         run(p, batch)                                                                     # warm-up (engine growth, allocator)
@@ -165,5 +175,8 @@ for batch in [int(x) for x in args.batch.split(",") if x]:
         tot = sorted(r[0] for r in res[p])
         med = tot[len(tot) // 2]
         stages = next(r[1] for r in res[p] if r[0] == med)
-        front = sum(v for k, v in stages.items() if k != "sgd")
+        front = sum(v for k, v in stages.items() if k not in ("sgd", "stats"))
         print("  %-22s %.4f s (rounds %.4f - %.4f)  in front of the SGD loop %.4f s  | %s" % (p, med, tot[0], tot[-1], front, "  ".join("%s %.4f" % kv for kv in stages.items())), flush=True)
+        if args.diagnostics:
+            print("    every round: %s" % "  ".join("%.4f" % r[0] for r in res[p]) + ("" if "stats" not in stages else
+                  "   stats stage %.4f s = %.4f s per epoch, %.1f %% of the update" % (stages["stats"], stages["stats"] / max(args.epochs, 1), 100.0 * stages["stats"] / med)), flush=True)
