@@ -355,6 +355,91 @@ __global__ __launch_bounds__(256) void adam_tf_kernel(float* __restrict__ p, flo
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Global-norm gradient clipping (tf.clip_by_global_norm) in front of TF ApplyAdam, for the PPO engine's flat gradient buffer.
+//   grad_sumsq_kernel      : sum of (double)g * (double)g over the listed tensors of the buffer (NOT the alignment gaps between them), one double per block
+//   grad_norm_finish_kernel: the partials added in block order -> {norm, scale, c, 0}
+//   adam_tf_clipped_kernel : the same sum in every block's prologue, then adam_tf_update on __fmul_rn(g, scale) -- the arithmetic of adam_tf_kernel on a gradient
+//                            buffer that was multiplied by scale in fp32 beforehand, bit for bit
+// Every sum has a fixed order (lane: the tensors' 16-byte vectors as one grid-stride walk, then the odd elements; wave: xor butterfly; block: waves 0..3; grid: blocks 0..n-1), there
+// is no atomic and no hand-off inside a launch: the partials cross a kernel boundary.  Two runs on the same buffer give bitwise equal results.
+// ---------------------------------------------------------------------------------------------------
+constexpr int GN_BLOCKS = MI_GRAD_NORM_BLOCKS;      // latency, not bandwidth: 1.5 MB over 64 x 256 lanes is 5 or 6 16-byte loads per lane
+constexpr int GN_T = MI_GRAD_NORM_MAX_TENSORS;
+// The listed tensors as ONE walk: vector v of the walk (16 bytes) belongs to the last tensor t with vstart[t] <= v, at float off[t] + 4 (v - vstart[t]); the elements
+// behind a tensor's last whole vector (size % 4 of them) form a second, short walk of the same kind.  Entries past the last tensor hold INT_MAX and are never chosen.
+// Every index below is a compile-time one after unrolling, so the table stays in the kernel's argument registers: no lane-indexed copy, no private segment.
+struct GradNormTable { long long off[GN_T], tail_off[GN_T]; int vstart[GN_T], tstart[GN_T]; int n_vec, n_tail; };
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, const GradNormTable tb, double* __restrict__ partial) {
+    __shared__ double wsum[4];
+    const int tid = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int v = tid; v < tb.n_vec; v += stride) {           // the loads of one lane do not depend on each other: they are in flight together
+        long long o = tb.off[0];
+        int first = 0;
+#pragma unroll
+        for (int t = 1; t < GN_T; ++t) if (v >= tb.vstart[t]) { o = tb.off[t]; first = tb.vstart[t]; }
+        const f32x4 x = *(const f32x4*)(g + o + 4ll * (v - first));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc += (double)x[e] * (double)x[e];
+    }
+    if (tid < tb.n_tail) {                                   // a handful of lanes of block 0
+        long long o = tb.tail_off[0];
+        int first = 0;
+#pragma unroll
+        for (int t = 1; t < GN_T; ++t) if (tid >= tb.tstart[t]) { o = tb.tail_off[t]; first = tb.tstart[t]; }
+        const float x = g[o + (tid - first)];
+        acc += (double)x * (double)x;
+    }
+    acc = wave_sum_f64(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// partials of grad_sumsq_kernel -> norm (double) and the fp32 factor of clip_by_global_norm: c / norm where the norm is finite and above c, else 1 (c = +inf: never clips)
+__device__ __forceinline__ float grad_clip_scale(const double* __restrict__ partial, const int nb, const float c, double& norm) {
+    double s = 0.0;
+    for (int b = 0; b < nb; ++b) s += partial[b];
+    norm = sqrt(s);
+    return (norm > (double)c && norm < __builtin_huge_val()) ? (float)((double)c / norm) : 1.0f;
+}
+
+__global__ __launch_bounds__(64) void grad_norm_finish_kernel(const double* __restrict__ partial, int nb, float c, float* __restrict__ clip_out) {
+    double norm;
+    const float scale = grad_clip_scale(partial, nb, c, norm);
+    if (threadIdx.x == 0) *(f32x4*)clip_out = f32x4{(float)norm, scale, c, 0.f};
+}
+
+__global__ __launch_bounds__(256) void adam_tf_clipped_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, float* __restrict__ g, long long n,
+                                                              float alpha, float omb1, float omb2, float epsilon, const double* __restrict__ partial, int nb, float c,
+                                                              float* __restrict__ clip_out, int clear_grad) {
+    double norm;
+    const float scale = grad_clip_scale(partial, nb, c, norm);       // the same loads and the same order in every block: every block forms the same factor
+    if (blockIdx.x == 0 && threadIdx.x == 0) *(f32x4*)clip_out = f32x4{(float)norm, scale, c, 0.f};
+    const long long n4 = n >> 2;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        f32x4 pv = ((f32x4*)p)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i], gv = ((f32x4*)g)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float pp = pv[e], mm = mv[e], v1 = vv[e];
+            adam_tf_update(pp, mm, v1, __fmul_rn(gv[e], scale), alpha, omb1, omb2, epsilon);      // rounded to fp32 before it enters the update
+            pv[e] = pp; mv[e] = mm; vv[e] = v1;
+        }
+        ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
+        if (clear_grad) { f32x4 zz = {0.f, 0.f, 0.f, 0.f}; ((f32x4*)g)[i] = zz; }
+    }
+    for (long long i = (n4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        float mm = m[i], vv = v[i], pp = p[i];
+        adam_tf_update(pp, mm, vv, __fmul_rn(g[i], scale), alpha, omb1, omb2, epsilon);
+        p[i] = pp; m[i] = mm; v[i] = vv;
+        if (clear_grad) g[i] = 0.f;
+    }
+}
+
 __global__ __launch_bounds__(256) void cast_f32_split_kernel(const float* __restrict__ src, split_t* __restrict__ dst, long long n) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = split_from_f32(src[i]);
@@ -758,6 +843,40 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restr
 }
 
 }  // namespace mi
+
+// ---- global-norm gradient clipping (mi_internal.hpp; the PPO engine's mi_ppo_grad_norm / mi_ppo_apply_adam) ----
+int mi_grad_sumsq(hipStream_t st, const float* grad, const long long* off, const long long* size, int count, double* partial) {
+    if (!grad || !partial || count < 1 || count > MI_GRAD_NORM_MAX_TENSORS) return mi_fail(MI_ERR_ARG, "mi_grad_sumsq: bad arguments");
+    if (((uintptr_t)grad) & 15) return mi_fail(MI_ERR_ARG, "mi_grad_sumsq: the gradient buffer must be 16-byte aligned");
+    GradNormTable tb{};
+    long long nv = 0, nt = 0;
+    for (int t = 0; t < GN_T; ++t) {
+        if (t >= count) { tb.vstart[t] = tb.tstart[t] = 0x7fffffff; continue; }
+        if (off[t] < 0 || size[t] < 0 || off[t] % 4 != 0) return mi_fail(MI_ERR_ARG, "mi_grad_sumsq: tensor offsets must be multiples of 4 floats");
+        tb.off[t] = off[t]; tb.tail_off[t] = off[t] + (size[t] / 4) * 4;
+        tb.vstart[t] = (int)nv; tb.tstart[t] = (int)nt;
+        nv += size[t] / 4; nt += size[t] % 4;
+        if (nv >= 0x7fffffff) return mi_fail(MI_ERR_ARG, "mi_grad_sumsq: more than 2^31 vectors");
+    }
+    tb.n_vec = (int)nv; tb.n_tail = (int)nt;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(GN_BLOCKS), dim3(256), 0, st, grad, tb, partial);
+    return mi_check_launch("grad_sumsq");
+}
+
+int mi_grad_norm_finish(hipStream_t st, const double* partial, float max_norm, float* clip_out) {
+    if (!partial || !clip_out || (((uintptr_t)clip_out) & 15)) return mi_fail(MI_ERR_ARG, "mi_grad_norm_finish: bad arguments");
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(64), 0, st, partial, GN_BLOCKS, max_norm, clip_out);
+    return mi_check_launch("grad_norm_finish");
+}
+
+int mi_adam_tf_flat_clipped(hipStream_t st, float* param, float* m, float* v, float* grad, long long n, float alpha, float beta1, float beta2, float epsilon,
+                            const double* partial, float max_norm, float* clip_out, int clear_grad) {
+    if ((((uintptr_t)param) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)grad) | ((uintptr_t)clip_out)) & 15) return mi_fail(MI_ERR_ARG, "mi_adam_tf_flat_clipped: buffers must be 16-byte aligned");
+    if (!partial || !clip_out) return mi_fail(MI_ERR_ARG, "mi_adam_tf_flat_clipped: missing partial sums or output");
+    hipLaunchKernelGGL(adam_tf_clipped_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, st, param, m, v, grad, n, alpha, 1.0f - beta1, 1.0f - beta2, epsilon,
+                       partial, GN_BLOCKS, max_norm, clip_out, clear_grad);
+    return mi_check_launch("adam_tf_clipped");
+}
 
 extern "C" {
 

@@ -43,3 +43,14 @@ extern "C" int mi_small_reduce_defer(int on);
 extern "C" int mi_small_reduce_flush(void* stream);
 extern "C" int mi_small_reduce_bind(void* stream);      // the list of the deferring pass belongs to `stream`; mi_reduce_slabs calls from other streams launch immediately (round 5)
 extern "C" int mi_small_reduce_deferring(void);
+
+// global-norm gradient clipping in front of TF ApplyAdam (elementwise.hip; the PPO engine).  mi_grad_sumsq: sum of (double)g * (double)g over `count` tensors of a
+// flat fp32 buffer (offsets in floats, multiples of 4; what lies between the tensors is not read) as MI_GRAD_NORM_BLOCKS ordered block partials.  mi_grad_norm_finish:
+// partials -> clip_out {norm, scale, max_norm, 0} (16-byte aligned), scale = (float)(max_norm / norm) where the norm is finite and above max_norm, else 1.
+// mi_adam_tf_flat_clipped: mi_adam_tf_flat on __fmul_rn(g, scale), scale formed from the partials by every block; block 0 also stores clip_out.  No atomics.
+#define MI_GRAD_NORM_BLOCKS 64
+#define MI_GRAD_NORM_MAX_TENSORS 16
+int mi_grad_sumsq(hipStream_t st, const float* grad, const long long* off, const long long* size, int count, double* partial);
+int mi_grad_norm_finish(hipStream_t st, const double* partial, float max_norm, float* clip_out);
+int mi_adam_tf_flat_clipped(hipStream_t st, float* param, float* m, float* v, float* grad, long long n, float alpha, float beta1, float beta2, float epsilon,
+                            const double* partial, float max_norm, float* clip_out, int clear_grad);

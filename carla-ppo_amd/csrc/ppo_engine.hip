@@ -27,6 +27,8 @@ struct PpoEngine {
     // workspace offsets (bytes)
     long long s_pad, h1, h2, g1, g2, u, vraw, h1o, h2o, uo, du, dv, dh2, dh1, dg2, dg1, partial, losses, mean, low, high, ws_total;
     long long f_gslab;                            // per-chunk gradient slabs of the large-minibatch step (max_batch > 256): [ceil(max_batch / 256)][total]
+    long long gn_part, clip;                      // global-norm clipping: the block partials of the sum of squares (doubles), and {norm, scale, c, 0} of the last norm (mi_ppo_buffer(h, 2))
+    float max_grad_norm;                          // 0 (calloc: the default): no clipping; > 0 or +inf: mi_ppo_apply_adam clips by the global norm (mi_ppo_set_max_grad_norm)
     long long f_h1, f_h2, f_dh1, f_dh2, f_part;   // fused step (ppo_fused.hip): [3][M][H1], [3][M][H2], [2][M][H1], [2][M][H2], loss-block partials
     int last_M;
     int precision;                                // MI_F32 (calloc: the default) or MI_BF16X3 (mi_ppo_set_precision): which instantiation of the fused GEMM stages runs
@@ -60,6 +62,7 @@ void layout(PpoEngine& e) {
     e.f_h1 = wa(3 * M * d.h1 * 4); e.f_h2 = wa(3 * M * d.h2 * 4); e.f_dh1 = wa(2 * M * d.h1 * 4); e.f_dh2 = wa(2 * M * d.h2 * 4);
     e.f_part = wa((long long)mi_ppo_fused_partial_floats((int)M) * 4);
     e.f_gslab = wa(M > 256 ? ((M + 255) / 256) * e.total * 4 : 0);
+    e.gn_part = wa(MI_GRAD_NORM_BLOCKS * 8); e.clip = wa(16);
     e.ws_total = w;
 }
 
@@ -97,6 +100,13 @@ bool fused_enabled(const PpoEngine* e);
 bool fused_enabled(const PpoEngine* e) { return knob(K_PPO_FUSED) && mi_ppo_fused_shape_in_range(e->d.num_actions, e->d.h2, e->kin); }
 
 bool x3(const PpoEngine* e) { return e->precision == MI_BF16X3; }
+
+bool clipping(const PpoEngine* e) { return e->max_grad_norm > 0.f; }
+
+// the ordered sum of squares over the 13 variables of the gradient buffer (not the alignment gaps behind the odd-sized ones) -> MI_GRAD_NORM_BLOCKS partials
+int grad_sumsq(PpoEngine* e, void* stream) {
+    return mi_grad_sumsq((hipStream_t)stream, e->grads, e->off, e->size, PPO_TENSORS, (double*)e->at(e->gn_part));
+}
 
 void fill_fused(const PpoEngine* e, PpoFusedParams& q, const float* states, int M) {
     const MiPpoDesc& d = e->d;
@@ -184,6 +194,7 @@ void* mi_ppo_create(const MiPpoDesc* d, float* params, float* params_old, float*
         hipMemcpy(e->at(e->high), action_high, d->num_actions * 4, hipMemcpyHostToDevice) != hipSuccess) {
         free(e); mi_fail(MI_ERR_STATE, "mi_ppo_create: copying action bounds failed"); return nullptr;
     }
+    if (hipMemset(e->at(e->clip), 0, 16) != hipSuccess) { free(e); mi_fail(MI_ERR_STATE, "mi_ppo_create: clearing the clip record failed"); return nullptr; }
     return e;
 }
 
@@ -193,11 +204,11 @@ void mi_ppo_destroy(void* h) {
     free(h);
 }
 
-// 0 losses[5] (policy, value, entropy, total, mean ratio)   1 action_mean [M,A] of the last predict
+// 0 losses[5] (policy, value, entropy, total, mean ratio)   1 action_mean [M,A] of the last predict   2 {norm, scale, c, 0} of the last gradient norm
 void* mi_ppo_buffer(void* h, int which) {
     PpoEngine* e = (PpoEngine*)h;
     if (!e) return nullptr;
-    return which == 0 ? e->at(e->losses) : which == 1 ? e->at(e->mean) : nullptr;
+    return which == 0 ? e->at(e->losses) : which == 1 ? e->at(e->mean) : which == 2 ? e->at(e->clip) : nullptr;
 }
 
 // PPO.update_old_policy (ppo.py:275-276): theta_old <- theta, one device copy of the flat buffer
@@ -305,7 +316,8 @@ int mi_ppo_train_step(void* h, void* stream, const float* states, const float* a
     if (!e) return mi_fail(MI_ERR_STATE, "ppo engine: null handle");
     if (M < 1 || M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step: batch outside [1, max_batch]");
     if (!e->grads || !e->m || !e->v) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step: engine created without optimiser buffers");
-    if (M > 256 || !fused_enabled(e)) {
+    if (M > 256 || !fused_enabled(e) || clipping(e)) {
+        // clipping by the global norm needs the whole gradient at one moment: the route of the large minibatches, for every M
         // large minibatches (the synthetic replay: 2048 rows per GPU): the weight-gradient launch splits the rows into chunks of 256 whose partial
         // sums are added in a fixed order (round 4: no atomics), so the Adam update is its own (flat) launch; everything before it is the same five-kernel chain
         if (!fused_enabled(e)) { CK(mi_ppo_forward_backward(h, stream, states, actions, returns, advantage, M, inv_m, grad_scale)); }
@@ -350,7 +362,7 @@ int mi_ppo_train_step_idx(void* h, void* stream, const float* states, const floa
     q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
     q.row_idx = row_idx; q.n_rows = n_rows; q.s_gath = (float*)e->at(e->s_pad);
     e->last_M = M;
-    if (M > 256) {
+    if (M > 256 || clipping(e)) {
         CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));
         return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
     }
@@ -447,7 +459,38 @@ int mi_ppo_apply_adam(void* h, void* stream, float alpha, float beta1, float bet
     PpoEngine* e = (PpoEngine*)h;
     if (!e) return mi_fail(MI_ERR_STATE, "ppo engine: null handle");
     if (!e->grads || !e->m || !e->v) return mi_fail(MI_ERR_STATE, "mi_ppo_apply_adam: engine created without optimiser buffers");
+    if (clipping(e)) {      // two launches: the ordered sum of squares, then Adam on g * scale with the factor formed from the partials by every block
+        CK(grad_sumsq(e, stream));
+        return mi_adam_tf_flat_clipped((hipStream_t)stream, e->params, e->m, e->v, e->grads, e->total, alpha, beta1, beta2, epsilon,
+                                       (const double*)e->at(e->gn_part), e->max_grad_norm, (float*)e->at(e->clip), 1);
+    }
     return mi_adam_tf_flat(stream, e->params, e->m, e->v, e->grads, e->total, alpha, beta1, beta2, epsilon, nullptr, 1);
+}
+
+// Global-norm gradient clipping (tf.clip_by_global_norm in front of the optimiser; include/mi355_carla.h).  0: off, the default of a new engine.
+int mi_ppo_set_max_grad_norm(void* h, float max_norm) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_set_max_grad_norm: null handle");
+    // (what needs no engine is checked before the handle is looked at)
+    if (!(max_norm >= 0.f)) return mi_fail(MI_ERR_ARG, "mi_ppo_set_max_grad_norm: max_norm is 0 (off), a positive float or +inf");
+    e->max_grad_norm = max_norm;
+    return MI_OK;
+}
+
+float mi_ppo_max_grad_norm(void* h) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) { mi_fail(MI_ERR_STATE, "mi_ppo_max_grad_norm: null handle"); return -1.0f; }
+    return e->max_grad_norm;
+}
+
+// the norm of the gradient buffer as it stands and the factor a limit of max_norm gives -> buffer 2; nothing else is written
+int mi_ppo_grad_norm(void* h, void* stream, float max_norm) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_grad_norm: null handle");
+    if (!(max_norm > 0.f)) return mi_fail(MI_ERR_ARG, "mi_ppo_grad_norm: max_norm is a positive float or +inf");
+    if (!e->grads) return mi_fail(MI_ERR_STATE, "mi_ppo_grad_norm: engine created without a gradient buffer");
+    CK(grad_sumsq(e, stream));
+    return mi_grad_norm_finish((hipStream_t)stream, (const double*)e->at(e->gn_part), max_norm, (float*)e->at(e->clip));
 }
 
 }  // extern "C"

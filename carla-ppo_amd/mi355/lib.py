@@ -4,6 +4,7 @@ There is NO fallback: if the shared library is missing the import of anything th
 (the product path must fail loudly without the HIP extension).
 """
 import ctypes
+import numbers
 import os
 import re
 
@@ -23,6 +24,16 @@ def ppo_precision_name(precision):
     if p not in PPO_PRECISIONS:
         raise ValueError("PPO precision %r: expected one of %s" % (precision, ", ".join(sorted(PPO_PRECISIONS))))
     return "fp32" if p == "f32" else p
+
+
+def max_grad_norm_value(value, who="max_grad_norm"):
+    """The limit of global-norm gradient clipping (mi_ppo_set_max_grad_norm): None (off) or a positive float (inf: measure the norm, never clip) -> None or float;
+    bool, str, 0, a negative value or NaN raise ValueError.  No device and no library involved."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not value > 0:      # (numpy's scalar types are registered as numbers.Real)
+        raise ValueError("%s: the value is None or a positive float (inf: measure the norm, never clip), got %r" % (who, value))
+    return float(value)
 
 
 _CTYPES = {

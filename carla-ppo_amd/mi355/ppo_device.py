@@ -56,6 +56,7 @@ class PpoDevice:
         self.params, self.params_old, self.grads, self.adam_m, self.adam_v = z(), z(), z(), z(), z()
         self.handle = None
         self.max_batch = 0
+        self.max_grad_norm = None                     # global-norm gradient clipping (set_max_grad_norm); None: off
         self._create(max_batch)
 
     def _desc(self, max_batch):
@@ -89,6 +90,12 @@ class PpoDevice:
         addr = self.L.mi_ppo_buffer(self.handle, 1)
         o = addr - self.workspace.data_ptr()
         self.action_mean = self.workspace[o:o + 4 * int(max_batch) * self.num_actions].view(torch.float32).view(int(max_batch), self.num_actions)
+        addr = self.L.mi_ppo_buffer(self.handle, 2)
+        o = addr - self.workspace.data_ptr()
+        # [gradient norm, clip factor, the limit, 0] of the last norm the engine formed (a clipped step, or grad_norm())
+        self.grad_clip = self.workspace[o:o + 16].view(torch.float32)
+        # like the precision, the clipping limit is applied to every engine this object creates
+        self.L.mi_ppo_set_max_grad_norm(self.handle, 0.0 if self.max_grad_norm is None else self.max_grad_norm)
 
     def ensure_batch(self, m):
         if m > self.max_batch:
@@ -218,6 +225,21 @@ class PpoDevice:
 
     def stats_scratch_doubles(self, M):
         return int(self.L.mi_ppo_update_stats_scratch_doubles(int(M)))
+
+    def set_max_grad_norm(self, max_norm):
+        """Global-norm gradient clipping in front of Adam (mi_ppo_set_max_grad_norm): None switches it off, a positive float (inf: measure only) switches it on for
+        apply_adam and every train_step form.  Kept across ensure_batch."""
+        self.max_grad_norm = milib.max_grad_norm_value(max_norm, "PpoDevice.set_max_grad_norm")
+        self.L.mi_ppo_set_max_grad_norm(self.handle, 0.0 if self.max_grad_norm is None else self.max_grad_norm)
+
+    def engine_max_grad_norm(self):
+        """The engine's own record of the limit (mi_ppo_max_grad_norm): 0.0 = off."""
+        return float(self.L.mi_ppo_max_grad_norm(self.handle))
+
+    def grad_norm(self, max_norm):
+        """The global L2 norm of the gradient buffer as it stands (e.g. behind forward_backward) and the factor a limit of max_norm (a positive float or inf) gives,
+        into `grad_clip` ([norm, scale, max_norm, 0], device).  Nothing else is written: parameters, optimiser state and gradients keep their contents."""
+        self.L.mi_ppo_grad_norm(self.handle, self.stream(), float(max_norm))
 
     def apply_adam(self, alpha, beta1=0.9, beta2=0.999, epsilon=1e-8):
         self.L.mi_ppo_apply_adam(self.handle, self.stream(), float(alpha), float(beta1), float(beta2), float(epsilon))

@@ -21,6 +21,17 @@ from mi355.init import init_ppo, ppo_variables
 ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON = 0.9, 0.999, 1e-8
 
 
+def _max_grad_norm_from_env():
+    """MI355_PPO_MAX_GRAD_NORM (unset or empty: off) -> None or a positive float; anything else raises ValueError."""
+    text = os.environ.get("MI355_PPO_MAX_GRAD_NORM", "").strip()
+    if not text:
+        return None
+    try:
+        return milib.max_grad_norm_value(float(text), "MI355_PPO_MAX_GRAD_NORM=%r" % text)
+    except ValueError:
+        raise ValueError("MI355_PPO_MAX_GRAD_NORM=%r: expected a positive float or inf" % text) from None
+
+
 def _adam_alpha(lr, b1p, b2p):
     one = np.float32(1.0)
     return np.float32(np.float32(lr) * np.sqrt(one - np.float32(b2p), dtype=np.float32) / (one - np.float32(b1p)))
@@ -37,6 +48,9 @@ class PPO():
         # include/mi355_carla.h mi_ppo_set_precision).  MI355_PPO_PRECISION supplies it when the argument is not given; MI355_PRECISION is the VAE's knob
         # and does not apply here.  Not part of a checkpoint: weights and optimiser state are fp32 in both modes.
         self.precision = milib.ppo_precision_name(precision or os.environ.get("MI355_PPO_PRECISION", "fp32"))
+        # global-norm gradient clipping in front of Adam (set_max_grad_norm): None = off.  MI355_PPO_MAX_GRAD_NORM supplies it when set_max_grad_norm is not called
+        # (the reference's train.py builds this object itself).  Not part of a checkpoint.
+        self.max_grad_norm = _max_grad_norm_from_env()
         self.input_dim = int(np.asarray(input_shape).reshape(-1)[0])
         self.num_actions = int(action_space.shape[0])
         self.action_low = np.asarray(action_space.low, np.float32).reshape(-1)
@@ -76,6 +90,7 @@ class PPO():
             self.seed = seed_from_numpy_state()
         self.dev = PpoDevice(self.input_dim, self.num_actions, self.action_low, self.action_high,
                              self.epsilon, self.value_scale, self.entropy_scale, precision=self.precision)
+        self.dev.set_max_grad_norm(self.max_grad_norm)
         values = self._init_values or init_ppo(self.seed, self.input_dim, self.num_actions, self.initial_std)
         # policy_old is a separately initialised copy in the reference; the trainer overwrites it with
         # update_old_policy() before the first train() (train.py:192), so it starts as a copy of policy.
@@ -91,6 +106,20 @@ class PPO():
         if self.dev is None:
             raise RuntimeError("call init_session() first")
         return self.dev
+
+    def set_max_grad_norm(self, value):
+        """Clip every SGD step's gradient by its global L2 norm over the 13 policy/ variables before Adam (tf.clip_by_global_norm; other libraries' max_grad_norm):
+        None switches it off (the default), a positive float switches it on, inf measures the norm and never clips.  Usable before or after init_session(); bool,
+        str, 0, a negative value or NaN raise ValueError before anything touches a device.  With it on, every step forms the whole gradient first (the fused chain,
+        a sum-of-squares launch, Adam) instead of applying Adam inside the gradient kernels, and last_grad_norm() / the rollout buffers' update() report the norms."""
+        self.max_grad_norm = milib.max_grad_norm_value(value, "PPO.set_max_grad_norm")
+        if self.dev is not None:
+            self.dev.set_max_grad_norm(self.max_grad_norm)
+
+    def last_grad_norm(self):
+        """{"grad_norm", "clip_scale"} of the last step that formed a norm (one readback); zeros before the first one."""
+        g = self._need_dev().grad_clip.cpu().numpy()
+        return {"grad_norm": float(g[0]), "clip_scale": float(g[1])}
 
     def set_weights(self, named):
         if self.dev is None:
@@ -232,6 +261,10 @@ class PPO():
             self._metric_sums["train/returns"] = self._metric_sums.get("train/returns", 0.0) + float(np.mean(returns))
             self._metric_sums["train/advantage"] = self._metric_sums.get("train/advantage", 0.0) + float(np.mean(advantage))
             self._metric_sums["train/learning_rate"] = self._metric_sums.get("train/learning_rate", 0.0) + float(self.current_learning_rate())
+            if self.max_grad_norm is not None:
+                g = self.last_grad_norm()
+                self._metric_sums["train/grad_norm"] = self._metric_sums.get("train/grad_norm", 0.0) + g["grad_norm"]
+                self._metric_sums["train/clip_scale"] = self._metric_sums.get("train/clip_scale", 0.0) + g["clip_scale"]
             self._metric_n += 1
         self.train_step_counter += 1
 

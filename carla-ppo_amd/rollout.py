@@ -90,6 +90,17 @@ epochs once the approximate KL to the old policy (k3, mean of r - 1 - log r) is 
 
 update() itself is unchanged: the same launches, the same numpy RNG draws, the same keys.
 
+Both buffers report the size of every SGD step once the policy clips its gradient by the global L2 norm (PPO.set_max_grad_norm, or MI355_PPO_MAX_GRAD_NORM under
+the unchanged reference scripts; tf.clip_by_global_norm in front of Adam: an ordered double-precision sum of squares over the 13 policy/ variables, no atomics,
+bitwise reproducible):
+
+    ppo.set_max_grad_norm(0.5)                                     # float("inf"): measure the norm, never clip;  None: off
+    out = buf.update(num_epochs=10, batch_size=32)
+    out["grad_norms"], out["clip_scales"]                          # float32 [number of SGD steps]: the norm before clipping, the factor applied (1.0 = not clipped)
+
+and every dict in `epochs` of update_with_diagnostics() gains `grad_norm_max` and `clipped_steps`.  With the setting off none of these keys appears, and the update
+makes the launches it always made.
+
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import os
@@ -535,7 +546,9 @@ class RolloutBuffer:
     def update(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, stage_times=None):
         """One PPO update from the tables (train.py:175-207 over the recorded rows): mi_rollout_finish, update_old_policy, log pi_old once, num_epochs x shuffled
         minibatches of batch_size (the last one partial) with the gather inside the step's kernels.  Returns the per-minibatch loss records (replay_update's keys),
-        `lengths`, and fp64 `returns` / `advantages` / `raw_advantages` and fp32 `values` as [num_envs, T] arrays, NaN beyond a row's length."""
+        `lengths`, and fp64 `returns` / `advantages` / `raw_advantages` and fp32 `values` as [num_envs, T] arrays, NaN beyond a row's length.  With
+        ppo.max_grad_norm set (PPO.set_max_grad_norm) also `grad_norms` and `clip_scales`, float32 [number of SGD steps]: each step's global gradient norm before
+        clipping and the factor it was scaled by."""
         return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, None)
 
     def update_with_diagnostics(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, stage_times=None, target_kl=None):
@@ -548,6 +561,8 @@ class RolloutBuffer:
         target_kl (None, or a positive finite float): after an epoch whose approx_kl is greater than target_kl -- a plain `>`; other libraries stop at 1.5 x their
         target_kl, so pass 1.5 x theirs to compare -- no further epoch runs and `stopped_early` is True.  np.random.shuffle is then called once per epoch that RAN, so
         the legacy numpy stream is left where an update of `epochs_run` epochs leaves it.
+        With ppo.max_grad_norm set, every dict of `epochs` also holds `grad_norm_max` (the largest norm among the epoch's steps) and `clipped_steps` (how many of them
+        were scaled down), from the same arrays as `grad_norms` / `clip_scales`: no further readback.
         Needs the cached log pi_old, i.e. the fused kernels (PpoDevice.fused_ok()): ValueError otherwise, before anything is launched or changed."""
         return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, _diagnostics(type(self).__name__, target_kl))
 
@@ -605,6 +620,8 @@ class RolloutBuffer:
                     pdev.logp_old(self.states[lo:hi], self.actions[lo:hi], hi - lo, self.logp_old[lo:hi])
         t_stage = mark("logp_old", t_stage)
         records = []
+        clip = ppo.max_grad_norm is not None                                         # global-norm clipping on: every step's {norm, scale, c, 0} is kept as well
+        clips, epoch_first = [], [0]
         if diag is not None:
             from mi355.ppo_device import N_STATS, update_stats_summary
             chunk = 4096
@@ -622,12 +639,15 @@ class RolloutBuffer:
                 ppo._step_rows(self.states, self.actions, self.returns, self.advantages, logp_old, mb, m, m)
                 ppo.train_step_counter += 1
                 records.append(pdev.losses.clone())
+                if clip:
+                    clips.append(pdev.grad_clip.clone())
             if diag is not None:                                                     # observe the epoch: all valid rows under the parameters it ended with
                 t_stage = mark("sgd", t_stage)
                 for lo in range(0, n_valid, chunk):
                     rows = valid_dev[lo:lo + chunk]
                     pdev.update_stats(self.states, self.actions, self.returns, self.logp_old, rows, int(rows.numel()), stats, stats_scratch, accumulate=lo > 0)
                 epochs.append(update_stats_summary(stats.cpu().numpy()))             # the epoch's one readback
+                epoch_first.append(len(clips))                                       # (the epoch's norms are read back with all the others, behind the last epoch)
                 t_stage = mark("stats", t_stage)
                 if diag["target_kl"] is not None and epochs[-1]["approx_kl"] > diag["target_kl"]:
                     stopped = True
@@ -640,6 +660,13 @@ class RolloutBuffer:
         values = np.where(np.arange(T)[None, :] < lengths[:, None], v_all[:, :T], np.float32(np.nan)).astype(np.float32)
         out = {"losses": [dict(zip(keys, (float(x) for x in row))) for row in losses], "lengths": lengths, "raw_advantages": f64[0], "returns": f64[1],
                "advantages": f64[2], "values": values, "bootstrap_values": np.where(lengths > 0, v_all[np.arange(E), lengths], np.float32(np.nan)).astype(np.float32), "samples": n_valid}
+        if clip:
+            gc = torch.stack(clips).cpu().numpy() if clips else np.zeros((0, 4), np.float32)
+            out["grad_norms"], out["clip_scales"] = gc[:, 0].astype(np.float32).copy(), gc[:, 1].astype(np.float32).copy()
+            if diag is not None:
+                for e, lo, hi in zip(epochs, epoch_first[:-1], epoch_first[1:]):     # NaN norms count as the maximum (np.max propagates them)
+                    e["grad_norm_max"] = float(gc[lo:hi, 0].max()) if hi > lo else float("nan")
+                    e["clipped_steps"] = int((gc[lo:hi, 1] < 1.0).sum())
         if diag is not None:
             out["epochs"], out["epochs_run"], out["stopped_early"] = epochs, len(epochs), stopped
         return out

@@ -536,6 +536,29 @@ int mi_ppo_precision(void* h);
 #define MI_PPO_N_STATS 9
 long long mi_ppo_update_stats_scratch_doubles(int M);
 int mi_ppo_update_stats_idx(void* h, void* stream, const float* states, const float* actions, const float* returns, const float* logp_old, const int* row_idx, int n_rows, int M, int accumulate, double* scratch, double* stats, float* logp_new_out, float* value_out);
+/* global-norm gradient clipping in front of the optimiser (tf.clip_by_global_norm; the `max_grad_norm` of other PPO implementations) -- ppo.py:143-144.  With a
+ * limit c the order of operations of an optimiser step is:
+ *   sumsq = sum of (double)g * (double)g over every element of the 13 policy/ variables of the gradient buffer -- the variables, not the flat buffer: the alignment
+ *           gaps behind the tensors whose size is no multiple of 8 (action bias, action_logstd, value bias) may hold anything and do not count --
+ *   norm  = sqrt(sumsq) in double;   scale = (float)(c / norm) where norm is finite and norm > (double)c, else 1.0f (so c = +inf measures and never clips, and a
+ *           non-finite norm leaves the gradient as it is and is reported as it is);
+ *   g'    = g * scale, rounded to fp32, and g' goes through the TF ApplyAdam arithmetic of mi_ppo_apply_adam unchanged:
+ * a clipped step equals multiplying the gradient buffer by scale in fp32 and then calling mi_ppo_apply_adam with clipping off, bit for bit.  The sum is ordered
+ * (one kernel stores one double per block, the optimiser kernel adds them in block order, the same order in every block): no atomics, and two runs on the same
+ * gradients give bitwise equal results.  Two launches (sum of squares, Adam) in place of the one Adam launch.
+ * mi_ppo_set_max_grad_norm: max_norm 0 switches clipping off (the default of a new engine), > 0 or +inf switches it on; MI_ERR_ARG for a negative value or NaN,
+ * MI_ERR_STATE for a null handle.  With clipping on, mi_ppo_apply_adam clips, and mi_ppo_train_step / mi_ppo_train_step_idx take, for every M, the route they take
+ * above 256 rows (the fused chain with the gradients left in the flat buffer, then mi_ppo_apply_adam) instead of applying Adam inside the gradient kernels;
+ * mi_ppo_train_step_dp clips behind its all-reduce, so every rank forms the same factor.  The gradient buffer is zero after the step, gaps included.  With
+ * clipping off every entry makes exactly the launches it made before.  Both precision modes.  mi_ppo_buffer(h, 2): four floats {norm, scale, c, 0} of the last
+ * norm that was formed (zeros in a new engine); NOT written while clipping is off.
+ * mi_ppo_max_grad_norm: the current setting (0 = off); -1 for a null handle.
+ * mi_ppo_grad_norm: the building block alone -- the norm of the gradient buffer as it stands (e.g. behind mi_ppo_forward_backward) and the factor that max_norm
+ * (> 0 or +inf; MI_ERR_ARG otherwise) gives, left in mi_ppo_buffer(h, 2); two launches.  NOT modified: parameters, theta_old, the optimiser state, the gradient
+ * buffer, the losses and action_mean buffers, the engine's setting. */
+int mi_ppo_set_max_grad_norm(void* h, float max_norm);
+float mi_ppo_max_grad_norm(void* h);
+int mi_ppo_grad_norm(void* h, void* stream, float max_norm);
 
 #ifdef __cplusplus
 }
