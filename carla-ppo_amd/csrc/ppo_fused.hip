@@ -243,14 +243,15 @@ __global__ __launch_bounds__(256) void ppo_l2_kernel(const PpoFusedParams q) {
 //   mean = low + (tanh(u)+1)/2 (high-low) ; logp = sum_a -.5 z^2 - (.5 log 2pi + log sigma) ; ratio = exp(logp - logp_old)
 //   loss = -mean(min(r A, clip(r) A)) + vs mean((V-R)^2) - es sum_a(entropy)        (ppo.py:58-66,112-132; tf.minimum's tie rule)
 //   du, dv = d loss / d head pre-activations ; dh2_pi[m,j] = relu'(h2) sum_a du[m,a] Wm[j,a] ; dh2_v[m,j] = relu'(h2) dv[m] Wv[j]
-// Every thread requests its whole share of the three h2 rows (<= 10 float4 each) before anything is used, the head kernels are staged in
-// LDS meanwhile, and the same registers produce dh2 at the end: one memory latency for the whole kernel.
+// Every thread requests its whole share of the policy's and the value net's h2 rows (<= 10 float4 each) before anything is used, the head kernels are staged in
+// LDS meanwhile, and the same registers produce dh2 at the end: one memory latency for the whole kernel.  (Without a cached log pi_old the old policy's h2 row is
+// requested with them, in the column order of the kernel that fills that cache, see below.)
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int PF_H2MAX = 320;                             // head kernels staged in LDS: H2 <= 320 (the reference: 300)
 template <int NA>
 __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams q) {
     __shared__ __attribute__((aligned(16))) float sWm[PF_H2MAX * PF_MAX_ACT], sWo[PF_H2MAX * PF_MAX_ACT], sWv[PF_H2MAX];
-    __shared__ float su[32][NA], suo[32][NA], sv[32], sdu[32][NA], sdv[32], spart[32][PF_NPART];
+    __shared__ float su[32][NA], sv[32], sdu[32][NA], sdv[32], spart[32][PF_NPART];
     const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
     const float* __restrict__ Wm = q.theta + q.off[4]; const float* __restrict__ bm = q.theta + q.off[5];
     const float* __restrict__ Wmo = q.theta_old + q.off[4]; const float* __restrict__ bmo = q.theta_old + q.off[5];
@@ -261,14 +262,24 @@ __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams
     const bool mok = m < q.M;
     constexpr int NV = (PF_H2MAX / 4 + 7) / 8;            // float4 pieces per thread and row (10)
     const int nf = H2 >> 2;                               // float4 per row (H2 % 4 == 0)
-    f32x4 hp[NV], hv[NV], ho[NV];
+    f32x4 hp[NV], hv[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int f = part + 8 * i;
         const bool ok = mok && f < nf;
         hp[i] = ok ? *(const f32x4*)(h2p + (long long)m * H2 + 4 * f) : f32x4{0.f, 0.f, 0.f, 0.f};
         hv[i] = ok ? *(const f32x4*)(h2v + (long long)m * H2 + 4 * f) : f32x4{0.f, 0.f, 0.f, 0.f};
-        ho[i] = (ok && old_net) ? *(const f32x4*)(h2o + (long long)m * H2 + 4 * f) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // the old policy's row (only without a cached log pi_old), requested with the others: this thread's columns are j = part, part + 8, .. as in the kernel that
+    // fills the cache (see the head sums below), so single floats instead of 16-byte pieces
+    constexpr int NH = PF_H2MAX / 8;                      // columns per thread (40)
+    float ho[NH];
+    if (old_net) {                                        // (uniform: with a cache none of this is issued)
+#pragma unroll
+        for (int k = 0; k < NH; ++k) { const int j = part + 8 * k; ho[k] = (mok && j < H2) ? h2o[(long long)m * H2 + j] : 0.f; }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NH; ++k) ho[k] = 0.f;
     }
     // head kernels -> LDS through registers (all requests in flight together), and the per-sample scalars the loss thread will need
     constexpr int NST = (PF_H2MAX * NA + 255) / 256;
@@ -292,6 +303,7 @@ __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams
 #pragma unroll
     for (int i = 0; i < (PF_H2MAX + 255) / 256; ++i) { const int x = tid + 256 * i; if (x < H2) sWv[x] = stv[i]; }
     __syncthreads();
+    float lp_old_s = 0.f;
     {
         float au[NA], ao[NA], av = 0.f;
 #pragma unroll
@@ -302,14 +314,11 @@ __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams
                 const int f = min(part + 8 * i, nf - 1);  // (threads past the row re-read its last piece: their h2 registers are zero)
                 const f32x4 wv = *(const f32x4*)(sWv + 4 * f);
                 const f32x4 wa = *(const f32x4*)(sWm + 8 * f), wb = *(const f32x4*)(sWm + 8 * f + 4);
-                const f32x4 oa = *(const f32x4*)(sWo + 8 * f), ob = *(const f32x4*)(sWo + 8 * f + 4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     av += hv[i][e] * wv[e];
                     const float w0 = e < 2 ? wa[2 * e] : wb[2 * e - 4], w1 = e < 2 ? wa[2 * e + 1] : wb[2 * e - 3];
-                    const float o0 = e < 2 ? oa[2 * e] : ob[2 * e - 4], o1 = e < 2 ? oa[2 * e + 1] : ob[2 * e - 3];
                     au[0] += hp[i][e] * w0; au[NA > 1 ? 1 : 0] += hp[i][e] * w1;
-                    ao[0] += ho[i][e] * o0; ao[NA > 1 ? 1 : 0] += ho[i][e] * o1;
                 }
             }
         } else {
@@ -321,9 +330,22 @@ __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams
             for (int e = 0; e < 4; ++e) {
                 const int j = 4 * f + e;
                 av += hv[i][e] * sWv[j];
-                _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) { au[a] += hp[i][e] * sWm[j * A + a]; ao[a] += ho[i][e] * sWo[j * A + a]; }
+                _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) au[a] += hp[i][e] * sWm[j * A + a];
             }
         }
+        }
+        // the old policy's log pi_old is spelled as ppo_predict_head_kernel<NA, 3> spells the cache of it (mi_ppo_logp_old): columns j = part, part + 8, .. of the
+        // row in ascending order against the old head kernel (here from LDS: the same values), the same shuffles, then libm tanhf / expf / logf and a serial sum
+        // over the actions -- so that the step gives the same parameters whether log pi_old comes from the cache or from here (in another order the two differ by
+        // an ulp of log pi_old, and Adam's first step multiplies what that does to a gradient near zero by lr / 3.2e-7).  The price is paid only without a cache:
+        // up to A libm chains per thread where the new policy's terms go through the hardware units (see below)
+        if (old_net && mok) {
+#pragma unroll
+            for (int k = 0; k < NH; ++k) {
+                const int j = part + 8 * k;
+                if (j >= H2) continue;
+                _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) ao[a] += ho[k] * sWo[j * A + a];
+            }
         }
 #pragma unroll
         for (int o = 4; o > 0; o >>= 1) {
@@ -331,21 +353,32 @@ __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams
 #pragma unroll
             for (int a = 0; a < NA; ++a) { au[a] += __shfl_xor(au[a], o, 64); ao[a] += __shfl_xor(ao[a], o, 64); }
         }
+        if (old_net) {                                    // (all 8 threads of a sample hold the same sums and form the same value)
+            float lp = 0.f;
+            _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) {
+                const float lo = p_lo[a], hi = p_hi[a];
+                const float mean = lo + ((tanhf(ao[a] + bmo[a]) + 1.0f) * 0.5f) * (hi - lo);
+                const float sigma = expf(p_lso[a]);
+                const float z = (p_act[a] - mean) / sigma;
+                lp += -0.5f * z * z - (PF_HALF_LOG_2PI + logf(sigma));
+            }
+            lp_old_s = lp;
+        }
         if (part == 0) {
             sv[sm] = av + bv[0];
-            _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) { su[sm][a] = au[a] + bm[a]; suo[sm][a] = old_net ? ao[a] + bmo[a] : 0.f; }
+            _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) su[sm][a] = au[a] + bm[a];
         }
     }
     __syncthreads();
-    // ---- per-sample loss terms: lane `part` of a sample's 8 threads owns action `part` (new and old policy), the terms meet by shuffles.
+    // ---- per-sample loss terms: lane `part` of a sample's 8 threads owns action `part` of the new policy, the terms meet by shuffles (log pi_old: lp_old_s above, or the cache).
     //      exp / log / tanh through the hardware transcendental units (v_exp_f32 / v_log_f32: ~1 ulp; tanh(u) = 1 - 2 / (e^2u + 1)): the
     //      libm sequences are ~100-instruction dependent chains, which at one wave per block was most of this kernel ----
     {
         auto fast_tanh = [](float x) { const float xc = fminf(fmaxf(x, -15.f), 15.f); return 1.0f - 2.0f / (__expf(2.0f * xc) + 1.0f); };
-        float lp_n = 0.f, lp_o = 0.f, dl = 0.f, zsq = 0.f, mean = 0.f;
-        float act = 0.f, ls = 0.f, lso = 0.f, lo = 0.f, hi = 0.f;
+        float lp_n = 0.f, dl = 0.f, zsq = 0.f, mean = 0.f;
+        float act = 0.f, ls = 0.f, lo = 0.f, hi = 0.f;
 #pragma unroll
-        for (int a = 0; a < NA; ++a) if (a == part) { act = p_act[a]; ls = p_ls[a]; lso = p_lso[a]; lo = p_lo[a]; hi = p_hi[a]; }
+        for (int a = 0; a < NA; ++a) if (a == part) { act = p_act[a]; ls = p_ls[a]; lo = p_lo[a]; hi = p_hi[a]; }
         const bool aok = part < A && mok;
         if (aok) {
             const float t = fast_tanh(su[sm][part < NA ? part : 0]);
@@ -356,17 +389,10 @@ __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams
             dl = (z / sigma) * (0.5f * (hi - lo)) * (1.0f - t * t);
             zsq = z * z;
             if (q.mean_out) q.mean_out[(long long)m * A + part] = mean;
-            if (old_net) {
-                const float to = fast_tanh(suo[sm][part < NA ? part : 0]);
-                const float mo = lo + ((to + 1.0f) * 0.5f) * (hi - lo);
-                const float so = __expf(lso);
-                const float zo = (act - mo) / so;
-                lp_o = -0.5f * zo * zo - (PF_HALF_LOG_2PI + __logf(so));
-            }
         }
 #pragma unroll
-        for (int o = 4; o > 0; o >>= 1) { lp_n += __shfl_xor(lp_n, o, 64); lp_o += __shfl_xor(lp_o, o, 64); }
-        if (!old_net) lp_o = p_lpo_s;
+        for (int o = 4; o > 0; o >>= 1) lp_n += __shfl_xor(lp_n, o, 64);
+        const float lp_o = old_net ? lp_old_s : p_lpo_s;
         const float r = __expf(lp_n - lp_o);
         const float ad = p_adv_s;
         const float rc = fminf(fmaxf(r, 1.0f - q.clip_eps), 1.0f + q.clip_eps);

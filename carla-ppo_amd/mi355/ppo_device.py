@@ -64,15 +64,19 @@ class PpoDevice:
                                self.clip_eps, self.value_scale, self.entropy_scale)
 
     def _create(self, max_batch):
-        if self.handle is not None:
-            self.L.mi_ppo_destroy(self.handle)
-            self.handle = None
+        # the new engine is created while the old one still exists, and the old one is destroyed behind it: freed first, the C side's allocator hands the same
+        # address out again unless something else took it in between, so whether `handle` changed across ensure_batch() depended on the heap's state
+        # (tests/test_q_grad_clip_gpu.py::test_setting_survives_ensure_batch tells a recreated engine by it).  Both engines share the parameter buffers; the
+        # two workspaces coexist for this call only
+        old = self.handle
         d = self._desc(max_batch)
         nbytes = int(self.L.mi_ppo_workspace_bytes(ctypes.byref(d)))
         self.workspace = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
         p = milib.ptr
         self.handle = self.L.mi_ppo_create(ctypes.byref(d), p(self.params), p(self.params_old), p(self.grads), p(self.adam_m), p(self.adam_v),
                                            p(self.workspace), nbytes, self.low.ctypes.data, self.high.ctypes.data)
+        if old is not None:
+            self.L.mi_ppo_destroy(old)
         if not self.handle:
             raise milib.MiError("mi_ppo_create: " + self.L.cdll.mi_last_error().decode())
         # a new engine starts in fp32: the mode is applied to every engine this object creates (ensure_batch recreates it for larger batches)

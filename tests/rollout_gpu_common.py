@@ -47,10 +47,10 @@ def make_vae(tmp_path, vparams, precision="fp32"):
     return vae
 
 
-def inputs(rng, n):
+def inputs(rng, n, n_act=A):
     frames = rng.randint(0, 256, (n, 80, 160, 3), dtype=np.uint8)
     meas = np.stack([rng.uniform(-1, 1, n), rng.uniform(0, 1, n), rng.uniform(0, 30, n)], axis=1)
-    noise = rng.standard_normal((n, A)).astype(np.float32)
+    noise = rng.standard_normal((n, n_act)).astype(np.float32)
     return frames, meas, noise
 
 
@@ -66,7 +66,7 @@ class Oracle:
     def predict(self, z, meas, noise, greedy):
         states = np.stack([np.append(z[e], meas[e]) for e in range(len(z))])
         a, v = self.o.predict(states, greedy=greedy, noise=None if greedy else noise)
-        return np.asarray(a).reshape(len(z), A), np.asarray(v).reshape(len(z)), states
+        return np.asarray(a).reshape(len(z), self.o.num_actions), np.asarray(v).reshape(len(z)), states
 
 
 def make_world(tmp_path_factory, name, policy=True):
@@ -82,10 +82,10 @@ def make_world(tmp_path_factory, name, policy=True):
     return w
 
 
-def check_against_oracle(got, z_o, a_o, v_o, meas, tag):
+def check_against_oracle(got, z_o, a_o, v_o, meas, tag, n_act=A):
     a, v, states = got
     n = len(z_o)
-    assert a.shape == (n, A) and a.dtype == np.float32 and v.shape == (n,) and v.dtype == np.float32, tag
+    assert a.shape == (n, n_act) and a.dtype == np.float32 and v.shape == (n,) and v.dtype == np.float32, tag
     assert states.shape == (n, Z + K) and states.dtype == np.float64, tag
     assert np.array_equal(states[:, Z:], np.asarray(meas, np.float64)), tag
     for e in range(n):

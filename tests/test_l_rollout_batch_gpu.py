@@ -34,6 +34,47 @@ def test_every_row_matches_the_oracle(world, precision):
                 check_against_oracle(step(f, ms, greedy=greedy, noise=nz), z_o, a_o, v_o, ms, (precision, io, E, greedy))
 
 
+def test_rows_match_the_oracle_at_one_and_three_actions(world, tmp_path):
+    """The rollout heads at action counts other than the reference's 2 (rollout_head_kernel<2> with A = 1, the <8> forms with A = 3): a policy on action spaces of
+    1 and of 3 actions (bounds and logstd per action: tests/ppo_shape_cases.py; N(0, 0.05) biases), the batched step at E in {1, 9}, sampled and greedy, and one
+    single-frame RolloutStep call, against OraclePPO.predict per row with the tolerances of the test above."""
+    import ppo_shape_cases as pc
+    from oracle import ppo_oracle as po
+    from ppo import PPO
+    from rollout import BatchedRolloutStep, RolloutStep
+    hp = dict(learning_rate=1e-4, lr_decay=1.0, epsilon=0.2, value_scale=1.0, entropy_scale=0.01, initial_std=1.0)
+    for n_act in (1, 3):
+        space = po.ActionSpace(*pc.bounds(n_act))
+        o = po.OraclePPO([Z + K], space, seed=4, **hp)
+        rng = np.random.RandomState(41 + n_act)
+        for k in o.params:
+            if k.endswith("bias"):
+                o.params[k] = (0.05 * rng.standard_normal(o.params[k].shape)).astype(np.float32)
+        o.params["policy/action_logstd"] = pc.logstd_of(n_act)
+        m = PPO(np.array([Z + K]), space, model_dir=str(tmp_path / ("ppo_%d" % n_act)), seed=4, **hp)
+        m.set_weights(o.params)
+        m.init_session(init_logging=False)
+        assert m.num_actions == n_act and m.dev.fused_ok()
+        orc = Oracle(world["vparams"], o)
+        frames, meas, noise = inputs(rng, 9, n_act)
+        noise *= 2.0                                                   # some samples leave the bounds on each side
+        z_all = orc.latents(frames)
+        clamped = np.zeros(2, bool)
+        for E in (1, 9):
+            step = BatchedRolloutStep(world["vae"], m, E)
+            for greedy in (False, True):
+                a_o, v_o, _ = orc.predict(z_all[:E], meas[:E], noise[:E], greedy)
+                check_against_oracle(step(frames[:E], meas[:E], greedy=greedy, noise=noise[:E]), z_all[:E], a_o, v_o, meas[:E], (n_act, E, greedy), n_act)
+                if not greedy:
+                    clamped |= [(a_o == space.low).any(), (a_o == space.high).any()]
+        assert clamped.all(), (n_act, clamped)
+        one = RolloutStep(world["vae"], m)
+        for greedy in (False, True):
+            a_o, v_o, _ = orc.predict(z_all[3:4], meas[3:4], noise[3:4], greedy)
+            a, v, state = one(frames[3], meas[3], greedy=greedy, noise=noise[3])
+            check_against_oracle((a[None], np.float32([v]), state[None]), z_all[3:4], a_o, v_o, meas[3:4], (n_act, "single", greedy), n_act)
+
+
 def test_rows_match_the_single_frame_path(world):
     from rollout import BatchedRolloutStep, RolloutStep
     rng = np.random.RandomState(34)

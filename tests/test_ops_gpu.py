@@ -760,51 +760,48 @@ def test_sigmoid_range_check_cast():
     assert torch.equal(bf.cpu(), torch.from_numpy(x).to(torch.bfloat16))
 
 
-def test_ppo_loss_and_head_vs_oracle_formulas():
-    from oracle import ppo_oracle as po
+def _ppo_head_cases():
+    import ppo_shape_cases as pc
+    return list(pc.HEAD_CASES)
+
+
+@pytest.mark.parametrize("A,M", _ppo_head_cases())
+def test_ppo_loss_and_head_vs_oracle_formulas(A, M):
+    """mi_ppo_loss_fwd_bwd and mi_policy_head for 1, 2, 3 and 8 actions at one sample, one short of, at and past a 256-sample block and two blocks, on the problems
+    of tests/ppo_shape_cases.py (u, u_old, vraw drawn directly; bounds and logstd per action; 10 % .. 60 % of the samples on the zero-slope branch, none within 1e-3
+    of a clip edge: asserted on the float64 reference.  One sample cannot have such a share nor a sample on each side: at M = 1 the sample is on the sloped
+    branch, its ratio at least 2 % away from 1, and the gap and range conditions hold -- conditions_met(single=True)).  dlogstd is added into a buffer that holds 1.5."""
+    import ppo_shape_cases as pc
     L = milib.get()
-    rng = np.random.RandomState(3)
-    M, A = 300, 2
-    u, uo = rng.randn(M, A).astype(np.float32), rng.randn(M, A).astype(np.float32)
-    uo = (u + 0.2 * uo).astype(np.float32)
-    ls, lso = np.array([-0.3, 0.1], np.float32), np.array([-0.25, 0.05], np.float32)
-    v, R, Ad = rng.randn(M).astype(np.float32), rng.randn(M).astype(np.float32), rng.randn(M).astype(np.float32)
-    act = rng.uniform(-1, 1, (M, A)).astype(np.float32)
-    low, high = np.array([-1, 0], np.float32), np.array([1, 1], np.float32)
-    ut = torch.tensor(u, dtype=torch.float64, requires_grad=True)
-    lst = torch.tensor(ls, dtype=torch.float64, requires_grad=True)
-    vt = torch.tensor(v, dtype=torch.float64, requires_grad=True)
-    lo, hi = torch.tensor(low).double(), torch.tensor(high).double()
-    mean = lo + ((torch.tanh(ut) + 1) / 2) * (hi - lo)
-    mean_o = lo + ((torch.tanh(torch.tensor(uo).double()) + 1) / 2) * (hi - lo)
-    a = torch.tensor(act).double()
-    logp = po.normal_log_prob(a, mean, lst).sum(-1, keepdim=True)
-    logpo = po.normal_log_prob(a, mean_o, torch.tensor(lso).double()).sum(-1, keepdim=True)
-    ratio = torch.exp(logp - logpo)
-    adv = torch.tensor(Ad).double().unsqueeze(-1)
-    pl = torch.minimum(ratio * adv, torch.clamp(ratio, 0.8, 1.2) * adv).mean()
-    vl = ((vt - torch.tensor(R).double()) ** 2).mean() * 0.7
-    el = (0.5 + po.HALF_LOG_2PI + torch.log(torch.exp(lst))).sum() * 0.02
-    loss = -pl + vl - el
-    loss.backward()
-    du, dv = torch.empty(M, A, device="cuda"), torch.empty(M, device="cuda")
+    c = pc.head_case(A, M)
+    assert pc.conditions_met(c.cond, single=M == 1), c.cond
+    u, uo, ls, lso, v, R, Ad, act, low, high = c.u, c.uo, c.ls, c.lso, c.v, c.R, c.adv, c.act, c.low, c.high
+    du, dv = torch.full((M + 1, A), -777.0, device="cuda"), torch.full((M + 1,), -777.0, device="cuda")
     part = torch.zeros(L.mi_ppo_loss_partial_floats(M), device="cuda")
-    losses, dls = torch.zeros(5, device="cuda"), torch.zeros(A, device="cuda")
+    losses, dls = torch.zeros(5, device="cuda"), torch.full((A + 1,), 1.5, device="cuda")
     L.mi_ppo_loss_fwd_bwd(stream(), P(dev(u)), P(dev(uo)), P(dev(ls)), P(dev(lso)), P(dev(v)), P(dev(act)),
                           P(dev(R)), P(dev(Ad)), P(dev(low)), P(dev(high)), M, A, 0.2, 0.7, 0.02, 1.0 / M, 1.0,
                           du.data_ptr(), dv.data_ptr(), part.data_ptr(), losses.data_ptr(), dls.data_ptr())
     got = host(losses)
-    assert np.allclose(got[:4], [float(pl), float(vl), float(el), float(loss)], rtol=2e-5, atol=1e-6)
-    assert got[4] == pytest.approx(float(ratio.mean()), rel=2e-5)
-    assert_close(host(du), ut.grad.numpy(), 2e-4, 1e-6, "du")
-    assert_close(host(dv), vt.grad.numpy(), 1e-5, 1e-7, "dv")
-    assert_close(host(dls), lst.grad.numpy(), 2e-4, 1e-6, "dlogstd")
-    noise = rng.randn(M, A).astype(np.float32)
-    actd, meand = torch.empty(M, A, device="cuda"), torch.empty(M, A, device="cuda")
-    L.mi_policy_head(stream(), P(dev(u)), P(dev(ls)), P(dev(noise)), P(dev(low)), P(dev(high)), M, A, 0, actd.data_ptr(), meand.data_ptr())
-    ref = np.clip(mean.detach().numpy() + np.exp(ls.astype(np.float64)) * noise, low, high)
-    assert_close(host(actd), ref, 1e-5, 1e-6, "sampled action")
-    assert_close(host(meand), mean.detach().numpy(), 1e-5, 1e-6, "action mean")
+    print("\nA = %d, M = %d: loss scalars %.2e relative (bound 2e-5), du %.2e, dv %.2e, dlogstd %.2e of max" % (
+        A, M, np.abs(got[:4] - c.losses).max() / np.abs(c.losses).max(), np.abs(host(du)[:M] - c.du).max() / np.abs(c.du).max(),
+        np.abs(host(dv)[:M] - c.dv).max() / np.abs(c.dv).max(), np.abs(host(dls)[:A] - 1.5 - c.dls).max() / np.abs(c.dls).max()))
+    assert np.allclose(got[:4], c.losses, rtol=2e-5, atol=1e-6)
+    assert got[4] == pytest.approx(c.ratio_mean, rel=2e-5)
+    assert_close(host(du)[:M], c.du, 2e-4, 1e-6, "du")
+    assert_close(host(dv)[:M], c.dv, 1e-5, 1e-7, "dv")
+    assert_close(host(dls)[:A] - 1.5, c.dls, 2e-4, 1e-6, "dlogstd")
+    assert np.all(host(du)[M:] == -777.0) and host(dv)[M] == -777.0 and host(dls)[A] == 1.5      # nothing past M samples / A actions is written
+    if M >= 4:
+        assert c.sides["low"].all() and c.sides["high"].all() and c.sides["inside"], c.sides     # every action index is clamped at `low` and at `high` somewhere
+    else:
+        assert (c.sides["low"] | c.sides["high"]).all()
+    for greedy in (0, 1):
+        actd, meand = torch.full((M + 1, A), -777.0, device="cuda"), torch.full((M + 1, A), -777.0, device="cuda")
+        L.mi_policy_head(stream(), P(dev(u)), P(dev(ls)), P(dev(c.noise)), P(dev(low)), P(dev(high)), M, A, greedy, actd.data_ptr(), meand.data_ptr())
+        assert_close(host(actd)[:M], c.mean if greedy else c.sampled, 1e-5, 1e-6, "greedy action" if greedy else "sampled action")
+        assert_close(host(meand)[:M], c.mean, 1e-5, 1e-6, "action mean")
+        assert np.all(host(actd)[M:] == -777.0) and np.all(host(meand)[M:] == -777.0)
 
 
 def test_gae_scan_bit_exact_and_normalize():

@@ -236,34 +236,39 @@ def test_argument_errors_that_need_an_engine(trained):
     assert bool((tr.stats == SENTINEL).all())                # nothing was launched
 
 
-def float64_reference(tr, rows):
-    """-> dict of the float64 statistics, per-row float64 log pi, and the distance of the fp32 torch-CPU evaluation of the same formulas from it."""
+def float64_statistics(new, old, s, a, ret, low, high, eps=EPS):
+    """The update statistics of samples (s, a, ret) under parameters `new` against `old` (TF-named dicts, any shape the oracle takes; bounds low / high) -> dict of
+    the float64 statistics, per-row float64 log pi, the distance of the fp32 torch-CPU evaluation of the same formulas from it, samples within 1e-4 of the threshold."""
     import torch
     from mi355.ppo_device import update_stats_summary
-    new, old = tr.pdev.export_params(), tr.pdev.export_old()
-    s, a, ret = tr.host[0][rows], tr.host[1][rows], tr.host[2][rows]
-    space = po.ActionSpace()
+    n = len(s)
     out = {}
     for dt in (torch.float64, torch.float32):
         with torch.no_grad():
             t = lambda x: po._t(np.asarray(x, np.float32), dt)      # noqa: E731
-            mean, logstd, value = po.policy_forward({k: t(v) for k, v in new.items()}, t(s), space.low, space.high)
-            mean_o, logstd_o, _ = po.policy_forward({k: t(v) for k, v in old.items()}, t(s), space.low, space.high, "policy_old")
+            mean, logstd, value = po.policy_forward({k: t(v) for k, v in new.items()}, t(s), low, high)
+            mean_o, logstd_o, _ = po.policy_forward({k: t(v) for k, v in old.items()}, t(s), low, high, "policy_old")
             lp = po.normal_log_prob(t(a), mean, logstd).sum(dim=-1)
             lpo = po.normal_log_prob(t(a), mean_o, logstd_o).sum(dim=-1)
             if dt == torch.float32:                            # the same formulas in fp32: ratio, terms and sums
                 d = lp - lpo
                 r = torch.exp(d)
                 e = t(ret) - value
-                eps = torch.tensor(EPS, dtype=dt)
-                sums = [float(len(rows)), d.sum(), (r - 1 - d).sum(), (torch.abs(r - 1) > eps).sum(), r.sum(), t(ret).sum(), (t(ret) * t(ret)).sum(), e.sum(), (e * e).sum()]
+                eps32 = torch.tensor(eps, dtype=dt)
+                sums = [float(n), d.sum(), (r - 1 - d).sum(), (torch.abs(r - 1) > eps32).sum(), r.sum(), t(ret).sum(), (t(ret) * t(ret)).sum(), e.sum(), (e * e).sum()]
                 out[dt] = update_stats_summary(np.array([float(x) for x in sums]))
             else:
                 lp64, lpo64, v64 = lp.numpy(), lpo.numpy(), value.numpy()
-                out[dt] = update_stats_summary(sums_of(lp64, lpo64, ret.astype(np.float64), v64, np.float64(np.float32(EPS))))
+                out[dt] = update_stats_summary(sums_of(lp64, lpo64, np.asarray(ret, np.float32).astype(np.float64), v64, np.float64(np.float32(eps))))
     r64 = np.exp(lp64 - lpo64)
-    near = int((np.abs(np.abs(r64 - 1) - np.float64(np.float32(EPS))) < 1e-4).sum())
+    near = int((np.abs(np.abs(r64 - 1) - np.float64(np.float32(eps))) < 1e-4).sum())
     return out[torch.float64], out[torch.float32], lp64, near
+
+
+def float64_reference(tr, rows):
+    """float64_statistics of table rows `rows` under the parameters the device holds."""
+    space = po.ActionSpace()
+    return float64_statistics(tr.pdev.export_params(), tr.pdev.export_old(), tr.host[0][rows], tr.host[1][rows], tr.host[2][rows], space.low, space.high)
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
