@@ -205,10 +205,11 @@ void mi_ppo_destroy(void* h) {
 }
 
 // 0 losses[5] (policy, value, entropy, total, mean ratio)   1 action_mean [M,A] of the last predict   2 {norm, scale, c, 0} of the last gradient norm
+// 3 dv [M] of the last step: d loss / d value-head output per sample (workspace of the step; what value clipping zeroes)
 void* mi_ppo_buffer(void* h, int which) {
     PpoEngine* e = (PpoEngine*)h;
     if (!e) return nullptr;
-    return which == 0 ? e->at(e->losses) : which == 1 ? e->at(e->mean) : which == 2 ? e->at(e->clip) : nullptr;
+    return which == 0 ? e->at(e->losses) : which == 1 ? e->at(e->mean) : which == 2 ? e->at(e->clip) : which == 3 ? e->at(e->dv) : nullptr;
 }
 
 // PPO.update_old_policy (ppo.py:275-276): theta_old <- theta, one device copy of the flat buffer
@@ -395,6 +396,40 @@ int mi_ppo_train_step_dp(void* h, void* comm, void* stream, const float* states,
         CK(mi_ppo_forward_backward(h, stream, states, actions, returns, advantage, M, inv_m, grad_scale));
     }
     CK(mi_allreduce_sum_f32(comm, stream, e->grads, e->total));
+    return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
+}
+
+// The minibatch step with the clipped value loss of PPO2 (include/mi355_carla.h; the definition is in ppo_fused.hip's head / loss kernel): ONE entry for the three
+// existing forms -- row_idx == NULL: contiguous minibatch tensors as mi_ppo_train_step, row_idx != NULL: the tables (old_values among them) gathered in-kernel as
+// mi_ppo_train_step_idx, comm != NULL: the all-reduce of the flat buffer in front of Adam as mi_ppo_train_step_dp -- and for mi_ppo_forward_backward's role
+// (adam == 0: the gradients stay in the flat buffer).  adam == 1 takes the routes those entries take: the in-tile Adam for M <= 256 with clipping by the global norm
+// off and no communicator, else the flat buffer and mi_ppo_apply_adam.  Fused kernels only: there is no per-layer form.
+int mi_ppo_train_step_vclip(void* h, void* comm, void* stream, const float* states, const float* actions, const float* returns, const float* advantage,
+                            const float* logp_old, const float* old_values, float clip_range_vf, const int* row_idx, int n_rows, int M,
+                            float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step_vclip: null handle");
+    // (what needs no engine is checked before the handle is looked at)
+    if (M < 1 || (row_idx && n_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_vclip: batch outside [1, max_batch] or empty tables");
+    if (!old_values) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_vclip: missing old_values (an unclipped step: mi_ppo_train_step / _idx / _dp)");
+    if (!(clip_range_vf > 0.f)) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_vclip: clip_range_vf is a positive float or +inf");
+    if (adam != 0 && adam != 1) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_vclip: adam is 0 (stop with the gradients in the flat buffer) or 1 (apply the optimiser)");
+    if (M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_vclip: batch outside [1, max_batch] or empty tables");
+    if (!e->grads || (adam && (!e->m || !e->v))) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step_vclip: engine created without gradient / optimiser buffers");
+    if (!fused_enabled(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_train_step_vclip: needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0): there is no per-layer form of the clipped value loss");
+    PpoFusedParams q; fill_fused(e, q, states, M);
+    q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
+    q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
+    q.v_old = old_values; q.clip_range_vf = clip_range_vf;
+    if (row_idx) { q.row_idx = row_idx; q.n_rows = n_rows; q.s_gath = (float*)e->at(e->s_pad); }
+    e->last_M = M;
+    if (adam && !comm && M <= 256 && !clipping(e)) {
+        q.alpha = alpha; q.omb1 = 1.0f - beta1; q.omb2 = 1.0f - beta2; q.epsilon = epsilon;
+        return mi_ppo_fused_step((hipStream_t)stream, q, 1, x3(e));
+    }
+    CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));      // gradients written into the flat buffer (M > 256: ordered row chunks)
+    if (!adam) return MI_OK;
+    if (comm) CK(mi_allreduce_sum_f32(comm, stream, e->grads, e->total));
     return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
 }
 

@@ -246,10 +246,21 @@ __global__ __launch_bounds__(256) void ppo_l2_kernel(const PpoFusedParams q) {
 // Every thread requests its whole share of the policy's and the value net's h2 rows (<= 10 float4 each) before anything is used, the head kernels are staged in
 // LDS meanwhile, and the same registers produce dh2 at the end: one memory latency for the whole kernel.  (Without a cached log pi_old the old policy's h2 row is
 // requested with them, in the column order of the kernel that fills that cache, see below.)
+//
+// VCLIP (ppo_head_loss_vclip_kernel; mi_ppo_train_step_vclip): the clipped value loss of the original PPO2 code (baselines ppo2, tf.clip_by_value + tf.maximum).
+// Per sample, with V the value head's output under theta, V_old = q.v_old[row] the value recorded when the data was collected, R the return, eps_v = q.clip_range_vf > 0:
+//   V_c  = min(max(V, V_old - eps_v), V_old + eps_v)     a clamp of V itself, so V_c == V bit for bit inside the range
+//   l_u  = (V - R)^2 ,  l_c = (V_c - R)^2
+//   value_loss = value_scale * mean(max(l_u, l_c))        the max form of baselines ppo2, not the V_c-only form
+//   dLoss/dV   = (l_c > l_u) ? 0 : 2 * value_scale * (V - R) / M_global
+// tf.maximum's tie rule: on a tie the gradient goes to the first argument.  Inside the range and at its edge both terms are the same number, so the plain gradient
+// flows; the clipped branch is chosen only outside the range, where its slope is 0.  eps_v = +inf gives the unclipped step bit for bit.  V_old is one more 4-byte
+// gather per sample, requested with returns / advantages / log pi_old (the same clamped table row) before the first barrier; nothing on the policy side changes, and
+// the partial layout, the LDS and the finalisation in ppo_wgrad_kernel are those of the plain kernel.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int PF_H2MAX = 320;                             // head kernels staged in LDS: H2 <= 320 (the reference: 300)
-template <int NA>
-__global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams q) {
+template <int NA, bool VCLIP>
+__device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
     __shared__ __attribute__((aligned(16))) float sWm[PF_H2MAX * PF_MAX_ACT], sWo[PF_H2MAX * PF_MAX_ACT], sWv[PF_H2MAX];
     __shared__ float su[32][NA], sv[32], sdu[32][NA], sdv[32], spart[32][PF_NPART];
     const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
@@ -288,7 +299,7 @@ __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams
     for (int i = 0; i < NST; ++i) { const int x = tid + 256 * i; stm[i] = x < H2 * A ? Wm[x] : 0.f; sto[i] = (old_net && x < H2 * A) ? Wmo[x] : 0.f; }
 #pragma unroll
     for (int i = 0; i < (PF_H2MAX + 255) / 256; ++i) { const int x = tid + 256 * i; stv[i] = x < H2 ? Wv[x] : 0.f; }
-    float p_act[NA], p_adv_s = 0.f, p_ret_s = 0.f, p_lpo_s = 0.f, p_ls[NA], p_lso[NA], p_lo[NA], p_hi[NA];
+    float p_act[NA], p_adv_s = 0.f, p_ret_s = 0.f, p_lpo_s = 0.f, p_vold_s = 0.f, p_ls[NA], p_lso[NA], p_lo[NA], p_hi[NA];
     const int mr = (q.row_idx && mok) ? min(max(q.row_idx[m], 0), q.n_rows - 1) : m;     // the sample's row in the horizon-batch tables (actions / returns / advantages / cached log pi_old)
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
@@ -298,6 +309,7 @@ __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams
         p_lo[a] = aok ? q.low[a] : 0.f; p_hi[a] = aok ? q.high[a] : 0.f;
     }
     if (mok) { p_adv_s = q.adv[mr]; p_ret_s = q.returns[mr]; if (!old_net) p_lpo_s = q.logp_old[mr]; }
+    if constexpr (VCLIP) { if (mok) p_vold_s = q.v_old[mr]; }
 #pragma unroll
     for (int i = 0; i < NST; ++i) { const int x = tid + 256 * i; if (x < H2 * A) { sWm[x] = stm[i]; sWo[x] = sto[i]; } }
 #pragma unroll
@@ -403,13 +415,21 @@ __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams
         if (part < NA) sdu[sm][part < NA ? part : 0] = aok ? d : 0.f;
         if (aok) q.du[(long long)m * A + part] = d;
         const float dvv = sv[sm] - p_ret_s;
-        const float dvm = mok ? 2.0f * q.value_scale * dvv * q.inv_m : 0.f;
+        float dvm = mok ? 2.0f * q.value_scale * dvv * q.inv_m : 0.f;
+        float lv = dvv * dvv;
+        if constexpr (VCLIP) {                            // (see the header: the clamp of V itself, tf.maximum's tie rule)
+            const float vcl = fminf(fmaxf(sv[sm], p_vold_s - q.clip_range_vf), p_vold_s + q.clip_range_vf);
+            const float dvc = vcl - p_ret_s;
+            const float l_c = dvc * dvc;
+            if (l_c > lv) dvm = 0.f;
+            lv = fmaxf(lv, l_c);
+        }
 #pragma unroll
         for (int k = part; k < PF_NPART; k += 8) spart[sm][k] = 0.f;
         __builtin_amdgcn_wave_barrier();
         if (part == 0) {
             sdv[sm] = dvm;
-            if (mok) { q.dv[m] = dvm; if (q.logp_out) q.logp_out[m] = lp_n; spart[sm][0] = fminf(s1, s2); spart[sm][1] = dvv * dvv; spart[sm][2] = r; }
+            if (mok) { q.dv[m] = dvm; if (q.logp_out) q.logp_out[m] = lp_n; spart[sm][0] = fminf(s1, s2); spart[sm][1] = lv; spart[sm][2] = r; }
         }
         if (aok) { spart[sm][3 + part] = coef * (zsq - 1.0f); spart[sm][3 + PF_MAX_ACT + part] = mean; }
     }
@@ -456,6 +476,8 @@ __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams
         }
     }
 }
+template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, false>(q); }
+template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_vclip_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, true>(q); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // input gradient of layer 2: grid (ceil(H1 / 32), 2 nets, ceil(M / 32)); block = a 32 x 32 tile of
@@ -876,7 +898,10 @@ int mi_ppo_fused_step(hipStream_t st, PpoFusedParams& q, int fuse_adam, bool x3)
     if (rc != MI_OK) return rc;
     rc = ppo_pad(st, q.losses);
     if (rc != MI_OK) return rc;
-    if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_kernel<2>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);     // (action loops are compile-time unrolled)
+    if (q.v_old) {                                        // the clipped value loss (mi_ppo_train_step_vclip): the same kernel body with one more gather per sample
+        if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_vclip_kernel<2>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);
+        else hipLaunchKernelGGL(ppo_head_loss_vclip_kernel<PF_MAX_ACT>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);
+    } else if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_kernel<2>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);     // (action loops are compile-time unrolled)
     else hipLaunchKernelGGL(ppo_head_loss_kernel<PF_MAX_ACT>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);
     if (x3) hipLaunchKernelGGL(ppo_dh1_kernel<true>, dim3((q.H1 + 31) / 32, 2, (q.M + 31) / 32), dim3(256), 0, st, q);
     else hipLaunchKernelGGL(ppo_dh1_kernel<false>, dim3((q.H1 + 31) / 32, 2, (q.M + 31) / 32), dim3(256), 0, st, q);

@@ -27,6 +27,9 @@ struct PpoFusedParams {
                                                           // blockIdx.y (multiple of 32): chunk c STORES its partial gradient into gslab + c * gslab_stride and one ordered
                                                           // pass adds the chunks (round 4: no atomics, two runs bitwise equal; no fused Adam)
     float* gslab; long long gslab_stride;                 // per-chunk gradient slabs of the large-minibatch form (engine workspace; nullptr when max_batch <= 256)
+    // PPO2-style value clipping (mi_ppo_train_step_vclip; appended, so that no other field moves): the values recorded at collection time, indexed like returns
+    // (nullptr: the plain value loss), and the range eps_v > 0 (+inf: never clips)
+    const float* v_old; float clip_range_vf;
 };
 
 }  // namespace mi

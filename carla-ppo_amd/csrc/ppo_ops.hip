@@ -360,6 +360,52 @@ __global__ __launch_bounds__(64) void rollout_seg_norm_kernel(const double* __re
 }
 }  // namespace mi
 
+// ---------------------------------------------------------------------------------------------------
+// mi_ppo_value_clip_stats: the sums behind the value-clipping diagnostics over M rows row_idx[m] (clamped) of three fp32 tables -- v = V under the current parameters
+// (the value_out table of mi_ppo_update_stats_idx), vo = the value recorded at collection time, ret = the return -- formed in double from the fp32 inputs:
+//   v_c = min(max(v, vo - eps), vo + eps), l_u = (v - ret)^2, l_c = (v_c - ret)^2: terms 1, |v - vo| > eps, max(l_u, l_c), l_c > l_u
+// One thread per sample.  Ordered reduction as in ppo_update_stats_head_kernel, no atomics: an xor tree of shuffles inside a wave, the four waves' sums in LDS added in
+// wave order and stored as this block's row of `scratch`; ppo_value_clip_reduce_kernel adds the rows in block order.  Rows that row_idx does not name are not read.
+// ---------------------------------------------------------------------------------------------------
+namespace mi {
+constexpr int VC_NSTATS = MI_PPO_N_VCLIP_STATS;
+__global__ __launch_bounds__(256) void ppo_value_clip_stats_kernel(const float* __restrict__ values_new, const float* __restrict__ old_values, const float* __restrict__ returns,
+                                                                   const int* __restrict__ row_idx, int n_rows, int M, double eps, double* __restrict__ scratch) {
+    __shared__ double swave[4][VC_NSTATS];
+    const int tid = threadIdx.x, m = blockIdx.x * 256 + tid, wave = tid >> 6;
+    double term[VC_NSTATS];
+#pragma unroll
+    for (int k = 0; k < VC_NSTATS; ++k) term[k] = 0.0;
+    if (m < M) {
+        const long long mr = min(max(row_idx[m], 0), n_rows - 1);
+        const double v = (double)values_new[mr], vo = (double)old_values[mr], ret = (double)returns[mr];
+        const double vc = fmin(fmax(v, vo - eps), vo + eps);
+        const double lu = (v - ret) * (v - ret), lc = (vc - ret) * (vc - ret);
+        term[0] = 1.0; term[1] = fabs(v - vo) > eps ? 1.0 : 0.0; term[2] = fmax(lu, lc); term[3] = lc > lu ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < VC_NSTATS; ++k) {
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) term[k] += __shfl_xor(term[k], o, 64);
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < VC_NSTATS; ++k) swave[wave][k] = term[k];
+    }
+    __syncthreads();
+    if (tid < VC_NSTATS) scratch[(long long)blockIdx.x * VC_NSTATS + tid] = ((swave[0][tid] + swave[1][tid]) + swave[2][tid]) + swave[3][tid];
+}
+
+// one wave: lane k adds column k of the block rows in block order, then stores (accumulate 0) or adds to (1) stats[k]
+__global__ __launch_bounds__(64) void ppo_value_clip_reduce_kernel(const double* __restrict__ scratch, int n_blocks, int accumulate, double* __restrict__ stats) {
+    const int k = threadIdx.x;
+    if (k >= VC_NSTATS) return;
+    double sum = 0.0;
+    for (int b = 0; b < n_blocks; ++b) sum += scratch[(long long)b * VC_NSTATS + k];
+    stats[k] = accumulate ? stats[k] + sum : sum;
+}
+}  // namespace mi
+
 namespace {
 __global__ __launch_bounds__(256) void relu_grad_kernel(const float* __restrict__ g, const float* __restrict__ h, long long n, float* __restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -384,6 +430,20 @@ int mi_ppo_loss_fwd_bwd(void* stream, const float* u, const float* u_old, const 
     hipLaunchKernelGGL(ppo_loss_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, nb, logstd, A, inv_m, value_scale,
                        entropy_scale, grad_scale, losses5, dlogstd);
     return mi_check_launch("ppo_loss");
+}
+
+long long mi_ppo_value_clip_stats_scratch_doubles(int M) { return (long long)MI_PPO_N_VCLIP_STATS * (M < 1 ? 1 : (M + 255) / 256); }
+
+int mi_ppo_value_clip_stats(void* stream, const float* values_new, const float* old_values, const float* returns, const int* row_idx, int n_rows, int M,
+                            float clip_range_vf, int accumulate, double* scratch, double* stats) {
+    if (M < 1 || n_rows < 1) return mi_fail(MI_ERR_ARG, "mi_ppo_value_clip_stats: empty input (M >= 1, n_rows >= 1)");
+    if (!values_new || !old_values || !returns || !row_idx || !scratch || !stats) return mi_fail(MI_ERR_ARG, "mi_ppo_value_clip_stats: missing buffers");
+    if (!(clip_range_vf > 0.f)) return mi_fail(MI_ERR_ARG, "mi_ppo_value_clip_stats: clip_range_vf is a positive float or +inf");
+    if (accumulate != 0 && accumulate != 1) return mi_fail(MI_ERR_ARG, "mi_ppo_value_clip_stats: accumulate is 0 (store the sums) or 1 (add them to stats)");
+    const int nb = (M + 255) / 256;
+    hipLaunchKernelGGL(ppo_value_clip_stats_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, values_new, old_values, returns, row_idx, n_rows, M, (double)clip_range_vf, scratch);
+    hipLaunchKernelGGL(ppo_value_clip_reduce_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)scratch, nb, accumulate, stats);
+    return mi_check_launch("ppo_value_clip_stats");
 }
 
 int mi_policy_head(void* stream, const float* u, const float* logstd, const float* noise, const float* low, const float* high,

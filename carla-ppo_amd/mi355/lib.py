@@ -36,6 +36,16 @@ def max_grad_norm_value(value, who="max_grad_norm"):
     return float(value)
 
 
+def value_clip_value(value, who="value_clip"):
+    """The range eps_v of PPO2-style value-function clipping (mi_ppo_train_step_vclip): None (off) or a positive float (inf: the clipped entry, never a clipped
+    sample) -> None or float; bool, str, 0, a negative value or NaN raise ValueError.  No device and no library involved."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not value > 0:
+        raise ValueError("%s: the value is None or a positive float (inf: the value is never clipped), got %r" % (who, value))
+    return float(value)
+
+
 _CTYPES = {
     "void*": ctypes.c_void_p, "const void*": ctypes.c_void_p,
     "float*": ctypes.c_void_p, "const float*": ctypes.c_void_p,

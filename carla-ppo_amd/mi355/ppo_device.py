@@ -30,6 +30,22 @@ def update_stats_summary(sums):
             "value_mse": float(s[8] / n), "explained_variance": float(1.0 - var_err / var_ret) if var_ret > 0 else float("nan")}
 
 
+N_VCLIP_STATS = 4                                 # MI_PPO_N_VCLIP_STATS of include/mi355_carla.h
+
+
+def value_clip_summary(sums):
+    """The MI_PPO_N_VCLIP_STATS running sums of mi_ppo_value_clip_stats (count, count of |V - V_old| > eps_v, sum of max((V - R)^2, (V_c - R)^2), count of samples
+    whose clipped term is the larger one) -> value_clip_fraction, value_loss_clipped (the mean of the clipped objective, not scaled by value_scale, like value_mse)
+    and value_grad_zero_fraction (the share of samples the value gradient does not flow from).  Host arithmetic in float64; no GPU involved."""
+    s = np.asarray(sums, np.float64).reshape(-1)
+    if s.shape[0] != N_VCLIP_STATS:
+        raise ValueError("value_clip_summary: expected %d sums, got %d" % (N_VCLIP_STATS, s.shape[0]))
+    n = float(s[0])
+    if not n > 0:
+        raise ValueError("value_clip_summary: the sums hold no sample")
+    return {"value_clip_fraction": float(s[1] / n), "value_loss_clipped": float(s[2] / n), "value_grad_zero_fraction": float(s[3] / n)}
+
+
 class PpoDevice:
     def __init__(self, input_dim, num_actions, action_low, action_high, clip_eps, value_scale, entropy_scale,
                  hidden=(500, 300), max_batch=256, device=None, precision="fp32"):
@@ -98,6 +114,10 @@ class PpoDevice:
         o = addr - self.workspace.data_ptr()
         # [gradient norm, clip factor, the limit, 0] of the last norm the engine formed (a clipped step, or grad_norm())
         self.grad_clip = self.workspace[o:o + 16].view(torch.float32)
+        addr = self.L.mi_ppo_buffer(self.handle, 3)
+        o = addr - self.workspace.data_ptr()
+        # d loss / d value-head output per sample of the last step (the step's workspace; exactly 0 where value clipping stops the gradient)
+        self.value_head_grad = self.workspace[o:o + 4 * int(max_batch)].view(torch.float32)
         # like the precision, the clipping limit is applied to every engine this object creates
         self.L.mi_ppo_set_max_grad_norm(self.handle, 0.0 if self.max_grad_norm is None else self.max_grad_norm)
 
@@ -202,6 +222,29 @@ class PpoDevice:
         p = milib.ptr
         self.L.mi_ppo_train_step_dp(self.handle, comm_handle, self.stream(), p(states), p(actions), p(returns), p(advantage), p(logp_old), p(row_idx),
                                     int(states.shape[0]), int(M), float(inv_m), float(grad_scale), float(alpha), float(beta1), float(beta2), float(epsilon))
+
+    def train_step_vclip(self, comm_handle, states, actions, returns, advantage, logp_old, old_values, clip_range_vf, row_idx, M, inv_m, grad_scale, alpha,
+                         beta1=0.9, beta2=0.999, epsilon=1e-8, adam=True):
+        """The minibatch step with PPO2-style value-function clipping (mi_ppo_train_step_vclip): the value term is max((V - R)^2, (V_c - R)^2) with V_c = V clamped
+        into old_values +- clip_range_vf (a positive float or inf).  One entry for the three forms: row_idx None (contiguous minibatch tensors, as train_step) or an
+        int32 device tensor [M] naming rows of the horizon-batch tables, old_values among them (as train_step_idx); comm_handle None or a communicator (as
+        train_step_dp).  adam False: stops with the gradients in the flat buffer (forward_backward's role)."""
+        self.ensure_batch(M)
+        p = milib.ptr
+        self.L.mi_ppo_train_step_vclip(self.handle, comm_handle, self.stream(), p(states), p(actions), p(returns), p(advantage), p(logp_old), p(old_values),
+                                       float(clip_range_vf), p(row_idx), int(states.shape[0]), int(M), float(inv_m), float(grad_scale), 1 if adam else 0,
+                                       float(alpha), float(beta1), float(beta2), float(epsilon))
+
+    def value_clip_stats(self, values_new, old_values, returns, row_idx, M, clip_range_vf, stats, scratch, accumulate=False):
+        """The N_VCLIP_STATS sums of the value-clipping diagnostics (mi_ppo_value_clip_stats; value_clip_summary turns them into a dict) over rows `row_idx` (int32
+        device tensor [M]) of the tables values_new (the value_out table update_stats fills) / old_values / returns, into `stats` (float64 device tensor
+        [N_VCLIP_STATS]; accumulate: added to it).  scratch: float64 device tensor of value_clip_scratch_doubles(M) entries.  Needs no engine."""
+        p = milib.ptr
+        self.L.mi_ppo_value_clip_stats(self.stream(), p(values_new), p(old_values), p(returns), p(row_idx), int(values_new.shape[0]), int(M), float(clip_range_vf),
+                                       1 if accumulate else 0, p(scratch), p(stats))
+
+    def value_clip_scratch_doubles(self, M):
+        return int(self.L.mi_ppo_value_clip_stats_scratch_doubles(int(M)))
 
     def engine_precision(self):
         """The engine's own record of its mode (mi_ppo_precision): MI_F32 or MI_BF16X3."""

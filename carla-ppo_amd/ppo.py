@@ -51,6 +51,9 @@ class PPO():
         # global-norm gradient clipping in front of Adam (set_max_grad_norm): None = off.  MI355_PPO_MAX_GRAD_NORM supplies it when set_max_grad_norm is not called
         # (the reference's train.py builds this object itself).  Not part of a checkpoint.
         self.max_grad_norm = _max_grad_norm_from_env()
+        # PPO2-style value-function clipping (set_value_clip): None = off.  No environment knob: only the rollout buffers record the old values a clipped step needs.
+        # Not part of a checkpoint.
+        self.value_clip = None
         self.input_dim = int(np.asarray(input_shape).reshape(-1)[0])
         self.num_actions = int(action_space.shape[0])
         self.action_low = np.asarray(action_space.low, np.float32).reshape(-1)
@@ -115,6 +118,15 @@ class PPO():
         self.max_grad_norm = milib.max_grad_norm_value(value, "PPO.set_max_grad_norm")
         if self.dev is not None:
             self.dev.set_max_grad_norm(self.max_grad_norm)
+
+    def set_value_clip(self, value):
+        """Clip the value loss as the original PPO2 code does (baselines ppo2; clip_vloss / clip_range_vf elsewhere): with eps_v = value the value term of a sample is
+        max((V - R)^2, (V_c - R)^2), V_c = V clamped into [V_old - eps_v, V_old + eps_v], V_old the value recorded when the data was collected -- the value net gets no
+        gradient from a sample whose value has moved further than eps_v from V_old in the direction of its return.  None switches it off (the default), a positive
+        float switches it on, inf runs the clipped step and never clips.  Usable before or after init_session(); bool, str, 0, a negative value or NaN raise
+        ValueError before anything touches a device.  The rollout buffers' update() passes the recorded values; train() / train_step() take no old values and refuse
+        to run while it is set."""
+        self.value_clip = milib.value_clip_value(value, "PPO.set_value_clip")
 
     def last_grad_norm(self):
         """{"grad_norm", "clip_scale"} of the last step that formed a norm (one readback); zeros before the first one."""
@@ -210,10 +222,25 @@ class PPO():
             comm = midist.recording_comm()
         return comm
 
-    def _step_rows(self, s_all, a_all, r_all, adv_all, logp_old_all, rows, m_local, m_global):
+    def _step_rows(self, s_all, a_all, r_all, adv_all, logp_old_all, rows, m_local, m_global, old_values_all=None):
         """One SGD step on rows `rows` (int32 device tensor) of device-resident horizon-batch tables: the minibatch gather of train.py:199-204 runs inside
-        the step's kernels (single rank, fused kernels); otherwise the rows are gathered here and _step_resident takes over."""
+        the step's kernels (single rank, fused kernels); otherwise the rows are gathered here and _step_resident takes over.  old_values_all: the table of the values
+        recorded at collection time -- the step clips the value loss with self.value_clip (mi_ppo_train_step_vclip), which only the one-call forms can."""
         dev = self.dev
+        if old_values_all is not None:
+            if self.value_clip is None:
+                raise ValueError("PPO._step_rows: old values were passed but value clipping is off (set_value_clip)")
+            one_call = os.environ.get("MI355_PPO_FUSED", "1") != "0" and os.environ.get("MI355_PPO_IDX", "1") != "0" and dev.fused_ok()
+            comm = None if midist.world_size() == 1 else self._dp_comm()
+            if not one_call or (midist.world_size() > 1 and comm is None):
+                raise ValueError("PPO._step_rows: value clipping needs the fused one-call step (this policy's shape is outside the fused kernels' range, "
+                                 "MI355_PPO_FUSED=0 / MI355_PPO_IDX=0, or data parallel without the library's communicator)")
+            alpha = _adam_alpha(self.current_learning_rate(), self.beta1_power, self.beta2_power)
+            dev.train_step_vclip(None if comm is None else comm.handle, s_all, a_all, r_all, adv_all, logp_old_all, old_values_all, self.value_clip, rows, m_local,
+                                 1.0 / m_global, m_local / float(m_global), alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON)
+            self.beta1_power = np.float32(self.beta1_power * np.float32(ADAM_BETA1))
+            self.beta2_power = np.float32(self.beta2_power * np.float32(ADAM_BETA2))
+            return
         # (shapes outside the fused kernels' range -- e.g. more than 8 actions -- have no in-kernel gather: mi_ppo_fused_shape_ok says so up front and the rows
         #  are gathered here instead; row values themselves are clamped into the tables by the kernels, ADVICE r03)
         if midist.world_size() == 1 and os.environ.get("MI355_PPO_FUSED", "1") != "0" and os.environ.get("MI355_PPO_IDX", "1") != "0" and dev.fused_ok():
@@ -237,6 +264,9 @@ class PPO():
 
     def train(self, input_states, taken_actions, returns, advantage):
         """One SGD step on a minibatch + metric update + train_step_counter += 1; returns None (ppo.py:218-229)."""
+        if self.value_clip is not None:
+            raise ValueError("PPO.train: value clipping is on (set_value_clip) and this call takes no old values: train through a rollout buffer's update(), or "
+                             "switch it off with set_value_clip(None)")
         dev = self._need_dev()
         m = len(input_states)
         s = self._to_dev(input_states, (m, self.input_dim))

@@ -101,6 +101,21 @@ bitwise reproducible):
 and every dict in `epochs` of update_with_diagnostics() gains `grad_norm_max` and `clipped_steps`.  With the setting off none of these keys appears, and the update
 makes the launches it always made.
 
+Both buffers can clip the value loss as the original PPO2 code does (baselines ppo2; clip_vloss / clip_range_vf elsewhere).  The tables already hold the value of
+every step as it was when the data was collected; with PPO.set_value_clip(eps_v) every SGD step of update() passes that table along (mi_ppo_train_step_vclip: one more
+gather per sample in the loss kernel) and a sample's value term becomes max((V - R)^2, (V_c - R)^2) with V_c = V clamped into V_old +- eps_v: the value net gets no
+gradient from a sample whose value has already moved further than eps_v from V_old towards its return.  `value_loss` in the loss records is then the clipped objective:
+
+    ppo.set_value_clip(0.2)                                        # float("inf"): the clipped step, never a clipped sample;  None: off
+    out = buf.update_with_diagnostics(num_epochs=10, batch_size=32)
+    for e in out["epochs"]:
+        print(e["value_clip_fraction"], e["value_loss_clipped"], e["value_grad_zero_fraction"])
+
+The three keys come from one more small launch pair per statistics chunk (mi_ppo_value_clip_stats over the value table the statistics pass writes; ordered double sums,
+no atomics) and are read back with the epoch's other sums.  There is no environment knob (the reference's train.py passes no old values), PPO.train() refuses to run
+with the setting on, and the policy must be on the fused kernels (ValueError otherwise, before anything is launched).  With the setting off the keys, launches and numbers
+are what they were.
+
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import os
@@ -563,6 +578,9 @@ class RolloutBuffer:
         the legacy numpy stream is left where an update of `epochs_run` epochs leaves it.
         With ppo.max_grad_norm set, every dict of `epochs` also holds `grad_norm_max` (the largest norm among the epoch's steps) and `clipped_steps` (how many of them
         were scaled down), from the same arrays as `grad_norms` / `clip_scales`: no further readback.
+        With ppo.value_clip set (PPO.set_value_clip), every dict of `epochs` also holds `value_clip_fraction`, `value_loss_clipped` and `value_grad_zero_fraction`
+        (mi355.ppo_device.value_clip_summary): the statistics pass also writes V per table row, mi_ppo_value_clip_stats runs over the same chunks, and both sets of
+        sums come back in the epoch's one readback.
         Needs the cached log pi_old, i.e. the fused kernels (PpoDevice.fused_ok()): ValueError otherwise, before anything is launched or changed."""
         return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, _diagnostics(type(self).__name__, target_kl))
 
@@ -585,6 +603,10 @@ class RolloutBuffer:
             raise ValueError(who + ".update: single rank only (ragged rows give ranks different numbers of gradient all-reduces)")
         if int(batch_size) < 1 or int(num_epochs) < 0:
             raise ValueError(who + ".update: batch_size >= 1, num_epochs >= 0")
+        vclip = getattr(self.ppo, "value_clip", None)                                # PPO2-style value clipping (PPO.set_value_clip): None = off
+        if vclip is not None and not self.ppo._need_dev().fused_ok():
+            raise ValueError(who + ".update: value clipping (PPO.set_value_clip) exists only in the fused kernels (this policy's shape is outside their range or "
+                             "MI355_PPO_FUSED=0)")
         if diag is not None and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update_with_diagnostics: the statistics pass reads the cached log pi_old, which only the fused kernels fill "
                              "(this policy's shape is outside their range or MI355_PPO_FUSED=0)")
@@ -592,6 +614,7 @@ class RolloutBuffer:
         batch_size = int(batch_size)
         E, T, ppo, device = self.num_envs, self.horizon, self.ppo, self.device
         pdev = ppo._need_dev()
+        step_kw = {} if vclip is None else {"old_values_all": self.values}           # the values recorded at collection time: the table the finish call read
         valid = self.rows.valid_rows()
         n_valid = int(valid.shape[0])
         lengths = self.rows.lengths.copy()
@@ -626,7 +649,15 @@ class RolloutBuffer:
             from mi355.ppo_device import N_STATS, update_stats_summary
             chunk = 4096
             valid_dev = torch.from_numpy(valid).to(device)
-            stats = torch.zeros(N_STATS, dtype=torch.float64, device=device)
+            if vclip is None:
+                stats = torch.zeros(N_STATS, dtype=torch.float64, device=device)
+            else:                                                                    # both sets of sums in one tensor: still one readback per epoch
+                from mi355.ppo_device import N_VCLIP_STATS, value_clip_summary
+                stats_all = torch.zeros(N_STATS + N_VCLIP_STATS, dtype=torch.float64, device=device)
+                stats, vstats = stats_all[:N_STATS], stats_all[N_STATS:]
+                vscratch = torch.empty(pdev.value_clip_scratch_doubles(min(n_valid, chunk)), dtype=torch.float64, device=device)
+                if getattr(self, "_values_new", None) is None:                       # V under the current parameters per table row, written by the statistics pass
+                    self._values_new = torch.zeros(self.n_table_rows, device=device)
             stats_scratch = torch.empty(pdev.stats_scratch_doubles(min(n_valid, chunk)), dtype=torch.float64, device=device)
             epochs, stopped = [], False
         for _ in range(int(num_epochs)):
@@ -636,7 +667,7 @@ class RolloutBuffer:
             for i in range(0, n_valid, batch_size):
                 mb = perm[i:i + batch_size]                                          # the last one may be partial (train.py:199-201)
                 m = int(mb.numel())
-                ppo._step_rows(self.states, self.actions, self.returns, self.advantages, logp_old, mb, m, m)
+                ppo._step_rows(self.states, self.actions, self.returns, self.advantages, logp_old, mb, m, m, **step_kw)
                 ppo.train_step_counter += 1
                 records.append(pdev.losses.clone())
                 if clip:
@@ -645,8 +676,18 @@ class RolloutBuffer:
                 t_stage = mark("sgd", t_stage)
                 for lo in range(0, n_valid, chunk):
                     rows = valid_dev[lo:lo + chunk]
-                    pdev.update_stats(self.states, self.actions, self.returns, self.logp_old, rows, int(rows.numel()), stats, stats_scratch, accumulate=lo > 0)
-                epochs.append(update_stats_summary(stats.cpu().numpy()))             # the epoch's one readback
+                    if vclip is None:
+                        pdev.update_stats(self.states, self.actions, self.returns, self.logp_old, rows, int(rows.numel()), stats, stats_scratch, accumulate=lo > 0)
+                    else:
+                        pdev.update_stats(self.states, self.actions, self.returns, self.logp_old, rows, int(rows.numel()), stats, stats_scratch, accumulate=lo > 0,
+                                          value_out=self._values_new)
+                        pdev.value_clip_stats(self._values_new, self.values, self.returns, rows, int(rows.numel()), vclip, vstats, vscratch, accumulate=lo > 0)
+                if vclip is None:
+                    epochs.append(update_stats_summary(stats.cpu().numpy()))         # the epoch's one readback
+                else:
+                    both = stats_all.cpu().numpy()                                   # (the same one readback)
+                    epochs.append(update_stats_summary(both[:N_STATS]))
+                    epochs[-1].update(value_clip_summary(both[N_STATS:]))
                 epoch_first.append(len(clips))                                       # (the epoch's norms are read back with all the others, behind the last epoch)
                 t_stage = mark("stats", t_stage)
                 if diag["target_kl"] is not None and epochs[-1]["approx_kl"] > diag["target_kl"]:

@@ -483,7 +483,8 @@ void* mi_ppo_buffer(void* h, int which);
 /* PPO.update_old_policy — ppo.py:275-276 */
 int mi_ppo_update_old(void* h, void* stream);
 /* PPO.predict — ppo.py:231-251.  mi_ppo_buffer(h, 0): losses of the last step: [policy, value, entropy, total, mean ratio, mean action_mean[A], std[A]] (the
- * scalars of ppo.py:150-163); mi_ppo_buffer(h, 1): action_mean [M,A] of the last predict / train step */
+ * scalars of ppo.py:150-163); mi_ppo_buffer(h, 1): action_mean [M,A] of the last predict / train step; mi_ppo_buffer(h, 3): the step's workspace dv [M], the
+ * gradient of the loss with respect to each sample's value-head output as the last step formed it (exactly 0 where value clipping stops it) */
 int mi_ppo_predict(void* h, void* stream, const float* states, int M, const float* noise, int greedy, float* action, float* value);
 /* gradient half + optimiser half of PPO.train (= north_star "learn") — ppo.py:218-229 */
 int mi_ppo_forward_backward(void* h, void* stream, const float* states, const float* actions, const float* returns, const float* advantage, int M, float inv_m, float grad_scale);
@@ -559,6 +560,37 @@ int mi_ppo_update_stats_idx(void* h, void* stream, const float* states, const fl
 int mi_ppo_set_max_grad_norm(void* h, float max_norm);
 float mi_ppo_max_grad_norm(void* h);
 int mi_ppo_grad_norm(void* h, void* stream, float max_norm);
+/* PPO2-style value-function clipping (the clipped value loss of baselines ppo2; clip_vloss / clip_range_vf of other PPO implementations) -- the value term of
+ * ppo.py:112-132.  Per sample, with V the value head's output under theta, V_old = old_values[row] the value recorded when the data was collected, R the return and
+ * eps_v = clip_range_vf > 0:
+ *   V_c  = min(max(V, V_old - eps_v), V_old + eps_v)     a clamp of V itself, so V_c == V bit for bit inside the range
+ *   l_u  = (V - R)^2 ,  l_c = (V_c - R)^2
+ *   value_loss = value_scale * mean(max(l_u, l_c))        the max form of baselines ppo2, not the V_c-only form
+ *   dLoss/dV   = (l_c > l_u) ? 0 : 2 * value_scale * (V - R) / M_global
+ * i.e. tf.maximum(l_u, l_c) over tf.clip_by_value: on a tie the gradient goes to the first argument; inside the range and at its edge both terms are the same
+ * number, so the plain gradient flows, and the clipped branch is chosen only outside the range, where its slope is 0.  eps_v = +inf gives the unclipped step bit
+ * for bit.  losses[1] (value_loss, mi_ppo_buffer(h, 0)) of a clipped step is the clipped objective.  Nothing on the policy side changes.
+ * mi_ppo_train_step_vclip is ONE entry for the three unclipped forms: row_idx == NULL: contiguous minibatch tensors (n_rows ignored) as mi_ppo_train_step;
+ * row_idx != NULL: states / actions / returns / advantage / logp_old and old_values are horizon-batch tables of n_rows rows gathered inside the kernels (rows
+ * clamped) as mi_ppo_train_step_idx -- V_old is one more 4-byte gather per sample in the head / loss kernel, rows that row_idx does not name are not read; comm !=
+ * NULL: one all-reduce of the flat gradient buffer in front of Adam as mi_ppo_train_step_dp.  logp_old may be NULL (the old policy's forward runs in the step).
+ * adam == 0: the step stops with the gradients in the flat buffer (the role of mi_ppo_forward_backward; no all-reduce, no optimiser); adam == 1: the routes the
+ * existing entries take -- Adam inside the gradient kernels for M <= 256 with mi_ppo_set_max_grad_norm off and no communicator, else the flat buffer and
+ * mi_ppo_apply_adam (which clips by the global norm when that is on).  The same launches as the unclipped step, no atomics, bitwise reproducible, both precision
+ * modes.  MI_ERR_STATE: null handle; MI_ERR_ARG: M outside [1, max_batch], row_idx set with n_rows < 1, old_values == NULL (an unclipped step: the existing
+ * entries), clip_range_vf not > 0 (NaN included), adam not 0 / 1; MI_ERR_SHAPE: mi_ppo_fused_shape_ok(h) is 0 (there is no per-layer form).
+ * mi_ppo_value_clip_stats: the diagnostics of it, without an engine: over the M rows row_idx[m] (int32, device; clamped into [0, n_rows)) of three fp32 tables --
+ * values_new (V under the current parameters: the value_out table mi_ppo_update_stats_idx writes), old_values, returns -- the sums, formed in double from the fp32
+ * inputs, of
+ *   [0] 1 (the count)   [1] 1 where |V - V_old| > eps_v   [2] max(l_u, l_c)   [3] 1 where l_c > l_u (no value gradient from this sample)
+ * into stats [MI_PPO_N_VCLIP_STATS] (double, device).  Ordered: every block of 256 samples stores its sums to scratch
+ * (mi_ppo_value_clip_stats_scratch_doubles(M) doubles, device), one wave adds them in block order; no atomics, two runs are bitwise equal.  accumulate 0: stats is
+ * overwritten, 1: added to.  Rows not named are not read; nothing but scratch and stats is written.  MI_ERR_ARG: M < 1, n_rows < 1, a missing buffer,
+ * clip_range_vf not > 0, accumulate not 0 / 1. */
+#define MI_PPO_N_VCLIP_STATS 4
+int mi_ppo_train_step_vclip(void* h, void* comm, void* stream, const float* states, const float* actions, const float* returns, const float* advantage, const float* logp_old, const float* old_values, float clip_range_vf, const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon);
+long long mi_ppo_value_clip_stats_scratch_doubles(int M);
+int mi_ppo_value_clip_stats(void* stream, const float* values_new, const float* old_values, const float* returns, const int* row_idx, int n_rows, int M, float clip_range_vf, int accumulate, double* scratch, double* stats);
 
 #ifdef __cplusplus
 }

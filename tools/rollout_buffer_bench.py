@@ -17,7 +17,9 @@ and prints for both: step calls per update, samples per update, samples per step
     python tools/rollout_buffer_bench.py --diagnostics [--envs 64] [--steps 128] [--batch 32,2048] [--epochs 3] ...
 
 adds the same update through RolloutBuffer.update_with_diagnostics (one statistics pass per epoch, mi_ppo_update_stats_idx) to the interleaved rounds, without the
-replay paths: the "stats" stage is the cost of the passes, everything else is the plain update's."""
+replay paths: the "stats" stage is the cost of the passes, everything else is the plain update's.  A third path runs it with PPO.set_value_clip(--value-clip) on:
+its "stats" stage also holds the mi_ppo_value_clip_stats launches (the difference of the two "stats" stages per epoch is their cost) and its SGD steps are
+mi_ppo_train_step_vclip calls."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
@@ -39,6 +41,7 @@ ap.add_argument("--no-host-frames", action="store_true", help="skip replay_updat
 ap.add_argument("--no-box", action="store_true")
 ap.add_argument("--continuous", action="store_true", help="RolloutBuffer against ContinuousRolloutBuffer on one scripted set of simulators (no replay paths)")
 ap.add_argument("--diagnostics", action="store_true", help="RolloutBuffer.update against update_with_diagnostics in interleaved rounds (no replay paths)")
+ap.add_argument("--value-clip", type=float, default=0.2, help="eps_v of the value-clipped path of --diagnostics")
 ap.add_argument("--mean-episode", type=float, default=None, help="mean of the geometric episode lengths of --continuous (default: steps / 3)")
 args = ap.parse_args()
 
@@ -154,6 +157,12 @@ def run(path, batch):
         buf.update(num_epochs=args.epochs, batch_size=batch, stage_times=st)
     elif path == "buffer + diagnostics":
         buf.update_with_diagnostics(num_epochs=args.epochs, batch_size=batch, stage_times=st)
+    elif path == "+ value clip":
+        agent.set_value_clip(args.value_clip)
+        try:
+            buf.update_with_diagnostics(num_epochs=args.epochs, batch_size=batch, stage_times=st)
+        finally:
+            agent.set_value_clip(None)
     else:
         replay.replay_update(vae, agent, frames_h if path == "replay, host frames" else frames_d, meas, actions, rewards, dones, num_epochs=args.epochs, batch_size=batch, stage_times=st)
     torch.cuda.synchronize()
@@ -162,7 +171,7 @@ def run(path, batch):
 
 paths = ["buffer", "replay, device frames"] + ([] if frames_h is None else ["replay, host frames"])
 if args.diagnostics:
-    paths = ["buffer", "buffer + diagnostics"]
+    paths = ["buffer", "buffer + diagnostics", "+ value clip"]
 for batch in [int(x) for x in args.batch.split(",") if x]:
     for p in paths:
         run(p, batch)                                                                     # warm-up (engine growth, allocator)
