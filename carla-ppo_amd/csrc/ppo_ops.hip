@@ -1,6 +1,8 @@
 // ppo_ops.hip — wavefront-fused PPO kernels (gfx950, wave64):
 //   clipped-surrogate / value / entropy losses with analytic gradients wrt the network heads,
 //   Gaussian policy head (tanh squash, sample, clip), GAE reverse scan and advantage normalisation in fp64.
+#include <cmath>
+
 #include "common.hpp"
 #include "mi_internal.hpp"
 #include "mi355_carla.h"
@@ -358,6 +360,100 @@ __global__ __launch_bounds__(64) void rollout_seg_norm_kernel(const double* __re
         store_normalized(a, mean, stat[1], L, lane, tab, flat, tab_adv, adv_norm);
     }
 }
+
+// ---------------------------------------------------------------------------------------------------
+// mi_rollout_scale_rewards: the rewards of one collection divided by the running standard deviation of the discounted return (baselines' VecNormalize, at the
+// granularity of an update), in front of the finish kernels above.  Lane e has L = min(len[e], T) recorded steps; G[e,t] = c * gamma + r[e,t] with c = carry[e] at t = 0,
+// c = G[e,t] behind a step that neither is terminal nor truncated and 0.0 behind one that is.  Four launches, fp64, no atomics, every sum in a fixed order:
+//   rollout_reward_scan_kernel    one wave (= one block) per lane, the shape of finish_gae: all lanes stage the rewards and the reset flags in LDS (T doubles + T bytes:
+//                                 the launch sizes the dynamic LDS by T), lane 0 walks the recurrence, all lanes store G and sum it lane-strided: part[e] = the lane's sum
+//   rollout_reward_dev_kernel     one wave per lane: the batch mean from the partials (every block adds them alike, in lane-strided order, so all blocks hold the same
+//                                 bits; block 0 leaves n_b and m_b in stat), then part2[e] = the lane's sum of (G - m_b)^2
+//   rollout_reward_merge_kernel   one wave: M2_b from part2 in lane-strided order, the Chan / Welford merge into state (merge = 1) and den = sqrt(var + epsilon)
+//   rollout_reward_scale_kernel   one wave per lane: rewards_out = min(max(r / den, -clip), clip)
+// Slots >= L are neither read nor written; a lane with L < 1 adds 0.0 and keeps its carry.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void rollout_reward_scan_kernel(const double* __restrict__ rewards, const double* __restrict__ terminals, const unsigned char* __restrict__ truncs,
+                                                                 const int* __restrict__ len, int T, double gamma, double* __restrict__ carry, double* __restrict__ g_out,
+                                                                 double* __restrict__ part) {
+    extern __shared__ double scan_g[];                     // T doubles, then T bytes of reset flags
+    double* g = scan_g;
+    unsigned char* cut = reinterpret_cast<unsigned char*>(scan_g + T);
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const int L = min(len[row], T);                        // a length beyond the horizon cannot index past the row
+    if (L < 1) {
+        if (lane == 0) part[row] = 0.0;                    // adds nothing to the batch sum
+        return;
+    }
+    const long long flat = (long long)row * T;
+    for (int t = lane; t < L; t += WAVE) {
+        g[t] = rewards[flat + t];
+        cut[t] = (terminals[flat + t] != 0.0 || (truncs && truncs[flat + t])) ? 1 : 0;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        double c = carry[row];
+        for (int t = 0; t < L; ++t) {
+            const double y = __dadd_rn(__dmul_rn(c, gamma), g[t]);      // one multiply, one add
+            g[t] = y;
+            c = cut[t] ? 0.0 : y;
+        }
+        carry[row] = c;
+    }
+    __syncthreads();
+    double s = 0.0;
+    for (int t = lane; t < L; t += WAVE) { s += g[t]; g_out[flat + t] = g[t]; }
+    s = wave_sum_f64(s);
+    if (lane == 0) part[row] = s;
+}
+
+// -> the sum of the num_envs partials in lane-strided order + the wave reduction: the same bits in every wave that calls it
+__device__ __forceinline__ double reward_partials_sum(const double* part, int num_envs, int lane) {
+    double s = 0.0;
+    for (int i = lane; i < num_envs; i += WAVE) s += part[i];
+    return wave_sum_f64(s);
+}
+
+__global__ __launch_bounds__(64) void rollout_reward_dev_kernel(const double* __restrict__ g_out, const int* __restrict__ len, int num_envs, int T,
+                                                                const double* __restrict__ part, double* __restrict__ part2, double* __restrict__ stat) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    double cnt = 0.0;                                      // the count is exact in fp64 (at most 2^22 steps)
+    for (int i = lane; i < num_envs; i += WAVE) cnt += (double)max(min(len[i], T), 0);
+    cnt = wave_sum_f64(cnt);
+    const double s = reward_partials_sum(part, num_envs, lane);
+    const double mean = cnt < 1.0 ? 0.0 : s / cnt;
+    if (row == 0 && lane == 0) { stat[0] = cnt; stat[1] = mean; }
+    const int L = min(len[row], T);
+    const double ss = L < 1 ? 0.0 : sum_sq_dev(g_out + (long long)row * T, mean, L, lane);
+    if (lane == 0) part2[row] = ss;
+}
+
+// state = {count, mean, M2, den}.  merge = 0 (frozen statistics) and an empty batch leave count, mean and M2 as they were.
+__global__ __launch_bounds__(64) void rollout_reward_merge_kernel(const double* __restrict__ part2, const double* __restrict__ stat, int num_envs, int merge, double epsilon,
+                                                                  double* __restrict__ state) {
+    const int lane = threadIdx.x;
+    const double m2_b = reward_partials_sum(part2, num_envs, lane);
+    if (lane != 0) return;
+    double count = state[0];
+    const double n_b = stat[0];
+    if (merge && n_b >= 1.0) {
+        const double mean = state[1], delta = stat[1] - mean, n_new = count + n_b;
+        state[1] = mean + delta * n_b / n_new;
+        state[2] = state[2] + (m2_b + delta * delta * count * n_b / n_new);
+        state[0] = count = n_new;
+    }
+    const double var = count > 0.0 ? state[2] / count : 1.0;
+    state[3] = sqrt(var + epsilon);
+}
+
+__global__ __launch_bounds__(64) void rollout_reward_scale_kernel(const double* __restrict__ rewards, const int* __restrict__ len, int T, const double* __restrict__ state,
+                                                                  double clip, double* __restrict__ rewards_out) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const int L = min(len[row], T);
+    const long long flat = (long long)row * T;
+    const double den = state[3];
+    for (int t = lane; t < L; t += WAVE) rewards_out[flat + t] = fmin(fmax(rewards[flat + t] / den, -clip), clip);
+}
 }  // namespace mi
 
 // ---------------------------------------------------------------------------------------------------
@@ -567,5 +663,34 @@ int mi_rollout_finish_segments_boot(void* stream, const float* tab_values, const
     return finish_segments(true, stream, tab_values, rewards, terminals, seg_row, seg_len, n_seg, num_envs, T, gamma, lam, normalize, scratch, tab_returns, tab_advantages,
                            adv_raw, returns, adv_norm, tab_final_values, seg_boot);
 }
+
+// scratch: per-lane sums of G | per-lane sums of squared deviations | n_b, m_b
+long long mi_rollout_scale_rewards_scratch_doubles(int num_envs) { return num_envs < 1 ? -1 : 2LL * num_envs + 2; }
+
+// rewards / terminals fp64 [num_envs, T], truncs uint8 [num_envs, T] or NULL, len int32 [num_envs], state [4], carry [num_envs] (all device) -> g_out / rewards_out fp64
+// [num_envs, T], state and carry advanced.  Every check runs before the first launch.
+#define SCALE_FAIL(text) return mi_fail(MI_ERR_ARG, "mi_rollout_scale_rewards: " text)
+int mi_rollout_scale_rewards(void* stream, const double* rewards, const double* terminals, const unsigned char* truncs, const int* len, int num_envs, int T, double gamma,
+                             double epsilon, double clip, int merge, double* state, double* carry, double* scratch, double* g_out, double* rewards_out) {
+    if (!rewards || !terminals || !len || !state || !carry || !scratch || !g_out || !rewards_out) SCALE_FAIL("missing buffers");
+    if (num_envs < 1 || T < 1) SCALE_FAIL("empty input (num_envs >= 1, T >= 1)");
+    if (T > MI_ROLLOUT_MAX_HORIZON) SCALE_FAIL("the horizon exceeds MI_ROLLOUT_MAX_HORIZON");
+    if (num_envs > MI_ROLLOUT_MAX_ENVS) SCALE_FAIL("num_envs exceeds MI_ROLLOUT_MAX_ENVS");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) SCALE_FAIL("gamma outside [0, 1]");
+    if (!std::isfinite(epsilon) || epsilon < 0.0) SCALE_FAIL("epsilon is a finite value >= 0");
+    if (!(clip > 0.0)) SCALE_FAIL("clip is a positive value (+inf: never clamp)");
+    if (merge != 0 && merge != 1) SCALE_FAIL("merge is 0 (frozen statistics) or 1");
+    hipStream_t st = (hipStream_t)stream;
+    double* part = scratch;
+    double* part2 = scratch + num_envs;
+    double* stat = scratch + 2LL * num_envs;
+    const size_t lds = (size_t)T * (sizeof(double) + 1);
+    hipLaunchKernelGGL(rollout_reward_scan_kernel, dim3(num_envs), dim3(64), lds, st, rewards, terminals, truncs, len, T, gamma, carry, g_out, part);
+    hipLaunchKernelGGL(rollout_reward_dev_kernel, dim3(num_envs), dim3(64), 0, st, g_out, len, num_envs, T, part, part2, stat);
+    hipLaunchKernelGGL(rollout_reward_merge_kernel, dim3(1), dim3(64), 0, st, part2, stat, num_envs, merge, epsilon, state);
+    hipLaunchKernelGGL(rollout_reward_scale_kernel, dim3(num_envs), dim3(64), 0, st, rewards, len, T, state, clip, rewards_out);
+    return mi_check_launch("rollout_scale_rewards");
+}
+#undef SCALE_FAIL
 
 }  // extern "C"

@@ -116,6 +116,28 @@ no atomics) and are read back with the epoch's other sums.  There is no environm
 with the setting on, and the policy must be on the fused kernels (ValueError otherwise, before anything is launched).  With the setting off the keys, launches and numbers
 are what they were.
 
+Both buffers can scale the rewards by the running standard deviation of the discounted return, as every code base does that eps_v = 0.2 and max_grad_norm = 0.5 come
+from (baselines VecNormalize and its descendants).  eps_v, value_scale and the gradient norm are in units of the return, and CARLA's reward functions differ by orders of
+magnitude; the advantages are normalised already, the rewards -- and with them the returns, the value targets and the value net's gradients -- are not.  With
+set_reward_scaling() one device call of its own (mi_rollout_scale_rewards: four small launches, fp64, ordered sums, no atomics, bitwise reproducible) runs between the
+upload of the rewards and the finish call: it continues every lane's discounted return G = G * gamma + r from the carry the last update left (0.0 behind a done or a
+truncated step), merges the moments of the collection's G into the running {count, mean, M2} kept on the device (Chan / Welford), and hands the finish kernels
+r / sqrt(var + epsilon), clamped into +-clip.  The finish kernels, the SGD steps and the statistics pass are the code they were:
+
+    buf.set_reward_scaling(clip=10.0, epsilon=1e-8)               # frozen=True: scale by the statistics as they are (evaluation, fine-tuning);  None: off
+    out = buf.update(num_epochs=10, batch_size=32)
+    out["return_rms"], out["reward_scale_den"]                     # {"count", "mean", "var"} of the discounted returns so far, the divisor of this update
+    out["scaled_rewards"], out["discounted_returns"]               # fp64 [num_envs, T], NaN beyond a lane's length
+    out["reward_clip_fraction"], out["return_carry"]               # the share of rewards the clamp changed to +-clip; fp64 [num_envs]
+    ckpt = buf.reward_scaling_state()                              # ... buf.load_reward_scaling_state(ckpt) in the run that resumes
+    buf.zero_return_carry([3])                                     # environment 3 was reset without a done or a truncation being reported
+
+Two deviations from baselines, both on purpose: a collection is scaled by ONE factor, from statistics that already include it ("update ret_rms, then divide" per update
+instead of per step -- per-step scaling needs the reward on the device at every step and puts the rewards of one collection on different scales), and the statistics
+start from count 0 instead of the prior count = 1e-4, var = 1.  reset() starts a collection and touches neither the statistics nor the carries.  A non-finite reward in
+a recorded step would poison the statistics for good: update() raises ValueError before anything is launched or changed.  The value error and the explained variance of
+update_with_diagnostics() are then measured on the scaled returns.  With the setting off none of these keys appears and the update makes the launches it always made.
+
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import os
@@ -496,6 +518,43 @@ class SegmentedRows(RolloutRows):
         return self.truncs[segs[:, 0], segs[:, 1] + segs[:, 2] - 1].astype(np.int32)
 
 
+def _real(x):
+    return not isinstance(x, (bool, str)) and isinstance(x, (int, float, np.integer, np.floating))
+
+
+def reward_scaling_settings(clip=10.0, epsilon=1e-8, frozen=False, who="RolloutBuffer.set_reward_scaling"):
+    """The checked settings of running-return reward scaling (mi_rollout_scale_rewards) -> {"clip": float, "epsilon": float, "frozen": bool}.  clip: a positive float
+    (inf: never clamp); epsilon: a finite float >= 0; frozen: a bool.  Anything else raises ValueError.  numpy only: no device and no library involved."""
+    if not _real(clip) or not clip > 0:
+        raise ValueError("%s: clip is a positive float (inf: never clamp), got %r" % (who, clip))
+    if not _real(epsilon) or not np.isfinite(epsilon) or epsilon < 0:
+        raise ValueError("%s: epsilon is a finite float >= 0, got %r" % (who, epsilon))
+    if not isinstance(frozen, (bool, np.bool_)):
+        raise ValueError("%s: frozen is a bool, got %r" % (who, frozen))
+    return {"clip": float(clip), "epsilon": float(epsilon), "frozen": bool(frozen)}
+
+
+def reward_scaling_state_checked(d, num_envs, who="RolloutBuffer.load_reward_scaling_state"):
+    """The checked dict of reward_scaling_state() for a buffer of num_envs lanes -> {"count", "mean", "m2": float, "carry": float64 [num_envs], and the settings}.
+    count and m2 are finite and >= 0, mean and every carry finite, carry has one entry per lane.  ValueError otherwise.  numpy only."""
+    keys = ("count", "mean", "m2", "carry", "clip", "epsilon", "frozen")
+    if not isinstance(d, dict) or any(k not in d for k in keys):
+        raise ValueError("%s: expected a dict with the keys %s" % (who, ", ".join(keys)))
+    out = reward_scaling_settings(d["clip"], d["epsilon"], d["frozen"], who)
+    for k in ("count", "mean", "m2"):
+        if not _real(d[k]) or not np.isfinite(d[k]) or (k != "mean" and d[k] < 0):
+            raise ValueError("%s: %s is a finite float%s, got %r" % (who, k, "" if k == "mean" else " >= 0", d[k]))
+        out[k] = float(d[k])
+    carry = np.asarray(d["carry"])
+    if carry.dtype.kind not in "fiu" or carry.shape != (int(num_envs),):
+        raise ValueError("%s: carry must hold one number per environment, shape (%d,), got %s %s" % (who, num_envs, carry.dtype, carry.shape))
+    carry = carry.astype(np.float64)
+    if not np.isfinite(carry).all():
+        raise ValueError("%s: carry holds a value that is not finite" % who)
+    out["carry"] = carry
+    return out
+
+
 def _diagnostics(who, target_kl):
     """The checked arguments of update_with_diagnostics (raises before any device work): target_kl is None or a positive finite float."""
     if target_kl is not None:
@@ -530,13 +589,67 @@ class RolloutBuffer:
         self.states = torch.zeros(n, int(ppo.input_dim), device=self.device)
         self.actions = torch.zeros(n, int(ppo.num_actions), device=self.device)
         self.values, self.returns, self.advantages, self.logp_old = (torch.zeros(n, device=self.device) for _ in range(4))
+        self._reward_scaling = None                                                  # running-return reward scaling (set_reward_scaling): None = off
+
+    def set_reward_scaling(self, clip=10.0, epsilon=1e-8, frozen=False):
+        """Turns running-return reward scaling on (see the module docstring): every update divides its rewards by sqrt(var + epsilon) of the discounted returns seen so
+        far, this collection included, and clamps them into +-clip (inf: never).  frozen=True: the statistics are used and not updated (the carries still advance).
+        Turning it on allocates the statistics {count, mean, M2, den} and the per-lane carries on the buffer's device, all zeros; calling it again with the setting on
+        changes clip / epsilon / frozen and keeps both.  set_reward_scaling(None) turns it off and drops them.  ValueError before anything touches a device."""
+        if clip is None:
+            self._reward_scaling = None
+            return
+        self._reward_scaling_on(reward_scaling_settings(clip, epsilon, frozen))
+
+    def _reward_scaling_on(self, settings):
+        import torch
+        rs = self._reward_scaling
+        if rs is None:
+            rs = {"state": torch.zeros(4, dtype=torch.float64, device=self.device), "carry": torch.zeros(self.num_envs, dtype=torch.float64, device=self.device),
+                  "scratch": torch.empty(int(self.L.mi_rollout_scale_rewards_scratch_doubles(self.num_envs)), dtype=torch.float64, device=self.device)}
+        rs.update(settings)
+        self._reward_scaling = rs
+        return rs
+
+    def _need_reward_scaling(self, what):
+        if self._reward_scaling is None:
+            raise ValueError("%s.%s: reward scaling is off (set_reward_scaling)" % (type(self).__name__, what))
+        return self._reward_scaling
+
+    def reward_scaling_state(self):
+        """What a training script writes to its checkpoint: {"count", "mean", "m2": floats, "carry": float64 [num_envs], "clip", "epsilon", "frozen"}."""
+        rs = self._need_reward_scaling("reward_scaling_state")
+        state = rs["state"].cpu().numpy()
+        return {"count": float(state[0]), "mean": float(state[1]), "m2": float(state[2]), "carry": rs["carry"].cpu().numpy(), "clip": rs["clip"],
+                "epsilon": rs["epsilon"], "frozen": rs["frozen"]}
+
+    def load_reward_scaling_state(self, d):
+        """Takes reward_scaling_state()'s dict back (of this buffer or of another with as many environments): the setting is on afterwards, with these statistics, carries
+        and settings.  The whole dict is checked before anything changes (ValueError)."""
+        import torch
+        d = reward_scaling_state_checked(d, self.num_envs)
+        rs = self._reward_scaling_on({k: d[k] for k in ("clip", "epsilon", "frozen")})
+        rs["state"].copy_(torch.tensor([d["count"], d["mean"], d["m2"], 0.0], dtype=torch.float64))       # (den is written by every update before it is read)
+        rs["carry"].copy_(torch.from_numpy(d["carry"]))
+
+    def zero_return_carry(self, env_ids=None):
+        """The running discounted return of these environments (None: all) starts from 0.0 again: for an environment the caller reset without reporting a done or a
+        truncation."""
+        import torch
+        rs = self._need_reward_scaling("zero_return_carry")
+        if env_ids is None:
+            rs["carry"].zero_()
+        else:
+            ids = np.asarray(env_ids)
+            ids = self.rows.env_ids(ids, ids.shape[0] if ids.ndim == 1 else 0)
+            rs["carry"][torch.from_numpy(ids).to(self.device)] = 0.0
 
     @property
     def lengths(self):
         return self.rows.lengths
 
     def reset(self):
-        """All rows empty and open."""
+        """All rows empty and open.  (The statistics and carries of reward scaling belong to the run, not to a collection: they stay.)"""
         self.rows.reset()
 
     def step(self, frames_u8, measurements, env_ids=None, greedy=False, noise=None):
@@ -563,7 +676,10 @@ class RolloutBuffer:
         minibatches of batch_size (the last one partial) with the gather inside the step's kernels.  Returns the per-minibatch loss records (replay_update's keys),
         `lengths`, and fp64 `returns` / `advantages` / `raw_advantages` and fp32 `values` as [num_envs, T] arrays, NaN beyond a row's length.  With
         ppo.max_grad_norm set (PPO.set_max_grad_norm) also `grad_norms` and `clip_scales`, float32 [number of SGD steps]: each step's global gradient norm before
-        clipping and the factor it was scaled by."""
+        clipping and the factor it was scaled by.  With reward scaling on (set_reward_scaling) mi_rollout_scale_rewards runs in front of the finish call with this
+        update's gamma, the finish reads the scaled rewards, and the result gains `return_rms`, `reward_scale_den`, `scaled_rewards`, `discounted_returns`,
+        `reward_clip_fraction` and `return_carry`; `stage_times` gains "reward_scaling", which is also part of "finish".  A reward that is not finite in a recorded
+        step then raises ValueError before anything is launched or changed."""
         return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, None)
 
     def update_with_diagnostics(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, stage_times=None, target_kl=None):
@@ -581,6 +697,7 @@ class RolloutBuffer:
         With ppo.value_clip set (PPO.set_value_clip), every dict of `epochs` also holds `value_clip_fraction`, `value_loss_clipped` and `value_grad_zero_fraction`
         (mi355.ppo_device.value_clip_summary): the statistics pass also writes V per table row, mi_ppo_value_clip_stats runs over the same chunks, and both sets of
         sums come back in the epoch's one readback.
+        With reward scaling on (set_reward_scaling) the returns table holds returns of the SCALED rewards: value_mse and explained_variance are measured on those.
         Needs the cached log pi_old, i.e. the fused kernels (PpoDevice.fused_ok()): ValueError otherwise, before anything is launched or changed."""
         return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, _diagnostics(type(self).__name__, target_kl))
 
@@ -590,11 +707,12 @@ class RolloutBuffer:
             ln = torch.from_numpy(lengths).to(self.device)
             self.L.mi_rollout_finish(st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), ln.data_ptr(), self.num_envs, self.horizon, float(gamma), float(lam),
                                      self.returns.data_ptr(), self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
-        return self._update(finish, num_epochs, batch_size, stage_times, diag)
+        return self._update(finish, num_epochs, batch_size, stage_times, diag, gamma)
 
-    def _update(self, finish, num_epochs, batch_size, stage_times, diag=None):
+    def _update(self, finish, num_epochs, batch_size, stage_times, diag=None, gamma=None, truncs=None):
         """What every buffer's update does around its finish call `finish(stream, rewards, dones, lengths, f64)` (device rewards / dones, fp64 [3, E, T] of NaN for the raw
-        advantages, returns and normalised advantages).  diag: None, or update_with_diagnostics' {"target_kl": None or float}."""
+        advantages, returns and normalised advantages).  diag: None, or update_with_diagnostics' {"target_kl": None or float}.  gamma, truncs (host bool [E, T] or None):
+        what the reward scaling pass in front of the finish call takes, read only with the setting on."""
         import time
         import torch
         from mi355 import dist as midist
@@ -611,6 +729,11 @@ class RolloutBuffer:
             raise ValueError(who + ".update_with_diagnostics: the statistics pass reads the cached log pi_old, which only the fused kernels fill "
                              "(this policy's shape is outside their range or MI355_PPO_FUSED=0)")
         self.rows.check_update()
+        rs = self._reward_scaling                                                    # running-return reward scaling (set_reward_scaling): None = off
+        if rs is not None:
+            recorded = np.arange(self.horizon)[None, :] < self.rows.lengths[:, None]
+            if not np.isfinite(self.rows.rewards[recorded]).all():
+                raise ValueError(who + ".update: a recorded reward is not finite; it would poison the statistics of reward scaling for good")
         batch_size = int(batch_size)
         E, T, ppo, device = self.num_envs, self.horizon, self.ppo, self.device
         pdev = ppo._need_dev()
@@ -629,6 +752,18 @@ class RolloutBuffer:
         r = torch.from_numpy(self.rows.rewards).to(device)
         d = torch.from_numpy(self.rows.dones).to(device)
         f64 = torch.full((3, E, T), float("nan"), dtype=torch.float64, device=device)      # raw advantages, returns, normalised advantages (inspection)
+        if rs is not None:
+            if stage_times is not None:
+                torch.cuda.synchronize(device)
+            t_rs = time.perf_counter()
+            scaled = torch.full((2, E, T), float("nan"), dtype=torch.float64, device=device)   # discounted returns G, scaled rewards
+            tr = None if truncs is None else torch.from_numpy(truncs.astype(np.uint8)).to(device)
+            ln = torch.from_numpy(np.ascontiguousarray(lengths, np.int32)).to(device)
+            self.L.mi_rollout_scale_rewards(st, r.data_ptr(), d.data_ptr(), milib.ptr(tr), ln.data_ptr(), E, T, float(gamma), rs["epsilon"], rs["clip"],
+                                            0 if rs["frozen"] else 1, rs["state"].data_ptr(), rs["carry"].data_ptr(), rs["scratch"].data_ptr(), scaled[0].data_ptr(),
+                                            scaled[1].data_ptr())
+            r = scaled[1]                                                            # what the finish call reads
+            mark("reward_scaling", t_rs)
         finish(st, r, d, lengths, f64)
         t_stage = mark("finish", t_stage)
         ppo.update_old_policy()
@@ -710,6 +845,13 @@ class RolloutBuffer:
                     e["clipped_steps"] = int((gc[lo:hi, 1] < 1.0).sum())
         if diag is not None:
             out["epochs"], out["epochs_run"], out["stopped_early"] = epochs, len(epochs), stopped
+        if rs is not None:
+            state, scaled = rs["state"].cpu().numpy(), scaled.cpu().numpy()
+            out["return_rms"] = {"count": float(state[0]), "mean": float(state[1]), "var": float(state[2] / state[0]) if state[0] > 0 else 1.0}
+            out["reward_scale_den"] = float(state[3])
+            out["discounted_returns"], out["scaled_rewards"] = scaled[0], scaled[1]
+            out["reward_clip_fraction"] = float((np.abs(scaled[1][recorded]) == rs["clip"]).mean())
+            out["return_carry"] = rs["carry"].cpu().numpy()
         return out
 
 
@@ -778,7 +920,7 @@ class ContinuousRolloutBuffer(RolloutBuffer):
             else:
                 self.L.mi_rollout_finish_segments(*args)
         last_done = self.rows._last_done()
-        out = self._update(finish, num_epochs, batch_size, stage_times, diag)
+        out = self._update(finish, num_epochs, batch_size, stage_times, diag, gamma, truncs)
         out["segments"], out["segment_truncated"] = segs, seg_trunc
         out["bootstrap_values"] = np.where(last_done, np.float32(np.nan), out["bootstrap_values"]).astype(np.float32)
         final = np.full(truncs.shape, np.nan, np.float32)

@@ -428,6 +428,27 @@ int mi_rollout_finish_segments(void* stream, const float* tab_values, const doub
  * that step) and the slot behind the segment in tab_values is NOT read (it holds the next episode's first value, or a stale one); the segment comes out bit for bit as
  * mi_gae_scan + mi_adv_normalize give it on [v_0 .. v_{n-1}, v_final].  normalize, scratch and every other argument as in mi_rollout_finish_segments, and the same checks. */
 int mi_rollout_finish_segments_boot(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* seg_row, const int* seg_len, int n_seg, int num_envs, int T, double gamma, double lam, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw, double* returns, double* adv_norm, const float* tab_final_values, const int* seg_boot);
+/* running-return reward scaling in front of the finish calls above — baselines' VecNormalize (ret = ret * gamma + rew; ret_rms.update(ret); rew / sqrt(ret_rms.var + epsilon),
+ * clipped), no reference counterpart in train.py: the rewards of one collection divided by the running standard deviation of the discounted return.  No engine handle.
+ * rewards / terminals: fp64 [num_envs, T]; truncs: uint8 [num_envs, T] or NULL (none); len: int32 [num_envs], the recorded steps per lane (0: an unused lane; a value
+ * beyond T is clamped to T); state: double [4] = {count, mean, M2, den}; carry: double [num_envs], the discounted return each lane's running episode has reached;
+ * g_out / rewards_out: fp64 [num_envs, T] (all device; rewards_out must not overlap rewards).  fp64 throughout, per lane e with L = len[e] >= 1:
+ *   c = carry[e];  for t = 0 .. L-1:  G[e,t] = c * gamma + r[e,t]  (one multiply, then one add: no fused multiply-add);  c = (terminals[e,t] != 0 || truncs[e,t]) ? 0.0 : G[e,t]
+ *   carry[e] = c   (a lane with L = 0 keeps its carry and writes nothing)
+ *   n_b = sum of L,  m_b = sum of G / n_b,  M2_b = sum of (G - m_b)^2   (two passes; per-lane partials by lane-strided sums and a wave reduction, the lanes' partials added
+ *                                                                        by one wave in lane-strided order; no floating-point atomics: two calls are bitwise equal)
+ *   merge = 1 (Chan / Welford):  delta = m_b - mean;  n' = count + n_b;  mean += delta * n_b / n';  M2 += M2_b + delta^2 * count * n_b / n';  count = n'
+ *   merge = 0 (frozen statistics): state[0..2] stay bitwise as they were; the carry still advances.  An empty batch (n_b = 0) merges nothing.
+ *   var = count > 0 ? M2 / count : 1.0;  den = state[3] = sqrt(var + epsilon);  rewards_out[e,t] = min(max(r[e,t] / den, -clip), clip)  (a true division)
+ * Entries of g_out / rewards_out at t >= L are not written and entries of the inputs at t >= L are not read.  DEVIATIONS from baselines, both on purpose: a collection is
+ * scaled by ONE factor, from statistics that already include it ("update ret_rms, then divide" per update instead of per step: per-step scaling needs the reward on the
+ * device at every step and puts the rewards of one collection on different scales), and the statistics start from count = 0, not from the prior count = 1e-4, var = 1.
+ * scratch: device doubles, at least mi_rollout_scale_rewards_scratch_doubles(num_envs) = 2 num_envs + 2 (needs no GPU; -1 for num_envs < 1).  Four small launches
+ * (scan + per-lane sums; batch mean + per-lane squared deviations; merge; scaling stores), dynamic LDS sized by T.  Errors (checked before any launch, nothing is written):
+ * missing buffers; num_envs < 1 or T < 1; T > MI_ROLLOUT_MAX_HORIZON; num_envs > MI_ROLLOUT_MAX_ENVS; gamma outside [0, 1] or NaN; epsilon not finite or < 0; clip NaN
+ * or <= 0 (+inf is valid: never clamp); merge outside {0, 1}. */
+long long mi_rollout_scale_rewards_scratch_doubles(int num_envs);
+int mi_rollout_scale_rewards(void* stream, const double* rewards, const double* terminals, const unsigned char* truncs, const int* len, int num_envs, int T, double gamma, double epsilon, double clip, int merge, double* state, double* carry, double* scratch, double* g_out, double* rewards_out);
 
 /* ---- collectives of the data-parallel path (no reference counterpart: the reference is single-process) ----
  * RCCL over xGMI, one communicator per process = per GPU; librccl.so.1 is bound at mi_comm_init (a single-GPU process never loads it).
