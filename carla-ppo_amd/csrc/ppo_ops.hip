@@ -502,6 +502,65 @@ __global__ __launch_bounds__(64) void ppo_value_clip_reduce_kernel(const double*
 }
 }  // namespace mi
 
+// ---------------------------------------------------------------------------------------------------
+// mi_ppo_minibatch_advantages: the advantages of one epoch normalised PER MINIBATCH (SB3 normalize_advantage, CleanRL norm_adv; no counterpart in train.py), between the
+// finish kernels above, which leave the raw advantages in fp64 [num_envs, T], and the SGD steps, which gather their advantage from an fp32 table by row.  Minibatch b is
+// perm[b batch_size .. min((b + 1) batch_size, n)), table rows e (T + 1) + t; an entry that names no step slot (rollout_seg_decode's rule for a one-step segment: row < 0,
+// lane >= num_envs, slot T) is skipped: it does not count and nothing is stored for it.  One launch, one block of four waves per minibatch, fp64, three passes over the
+// minibatch's positions, each of which reads perm and the gathered doubles from global memory again (a minibatch can be the whole collection: no LDS is sized by it):
+//   1  c = the counted entries, mean = sum(a) / c        2  ss = sum((a - mean)^2), std = c - ddof >= 1 ? sqrt(ss / (c - ddof)) : 0
+//   3  tab_adv_out[row] = (float)((a - mean) / (std + 1e-8))      (store_normalized's true division)
+// Every sum in ONE order, no atomics: thread i adds positions i, i + 256, .. from the first, wave_sum_f64 inside each wave, the four waves' partials through LDS and
+// added in wave order by thread 0, which hands the result to the block.  stats[b] = {c, mean, std}; {0, 0, 0} and no store for a minibatch without a counted entry.
+// ---------------------------------------------------------------------------------------------------
+namespace mi {
+constexpr int MBA_THREADS = 256;
+static_assert(MBA_THREADS == 4 * WAVE, "mba_block_sum adds four waves' partials");
+
+// -> the block's sum of v, the same bits in every thread.  red: MBA_THREADS / WAVE + 1 doubles of LDS; every thread of the block calls it.
+__device__ __forceinline__ double mba_block_sum(double v, double* red, int tid) {
+    v = wave_sum_f64(v);
+    if ((tid & (WAVE - 1)) == 0) red[tid / WAVE] = v;
+    __syncthreads();
+    if (tid == 0) red[MBA_THREADS / WAVE] = ((red[0] + red[1]) + red[2]) + red[3];
+    __syncthreads();
+    const double s = red[MBA_THREADS / WAVE];
+    __syncthreads();                                       // (the next call stores into red)
+    return s;
+}
+
+__global__ __launch_bounds__(MBA_THREADS) void ppo_minibatch_adv_kernel(const double* __restrict__ adv_raw, const int* __restrict__ perm, int n, int batch_size, int num_envs,
+                                                                        int T, int ddof, float* __restrict__ tab_adv_out, double* __restrict__ stats) {
+    __shared__ double red[MBA_THREADS / WAVE + 1];
+    const int tid = threadIdx.x;
+    const long long first = (long long)blockIdx.x * batch_size;
+    const long long left = (long long)n - first;           // >= 1: the grid is ceil(n / batch_size) blocks
+    const int m = left < batch_size ? (int)left : batch_size;
+    const int* rows = perm + first;
+    long long flat;
+    double s = 0.0, cnt = 0.0;                             // the count is exact in fp64
+    for (int i = tid; i < m; i += MBA_THREADS)
+        if (rollout_seg_decode(rows[i], 1, num_envs, T, flat)) { s += adv_raw[flat]; cnt += 1.0; }
+    const double c = mba_block_sum(cnt, red, tid);
+    s = mba_block_sum(s, red, tid);
+    double* out = stats + 3LL * blockIdx.x;
+    if (c < 1.0) {                                         // (the same c in every thread: the whole block leaves)
+        if (tid < 3) out[tid] = 0.0;
+        return;
+    }
+    const double mean = s / c;
+    double ss = 0.0;
+    for (int i = tid; i < m; i += MBA_THREADS)
+        if (rollout_seg_decode(rows[i], 1, num_envs, T, flat)) { const double dd = adv_raw[flat] - mean; ss += dd * dd; }
+    ss = mba_block_sum(ss, red, tid);
+    const double dof = c - (double)ddof;
+    const double sd = dof >= 1.0 ? sqrt(ss / dof) : 0.0;
+    for (int i = tid; i < m; i += MBA_THREADS)
+        if (rollout_seg_decode(rows[i], 1, num_envs, T, flat)) tab_adv_out[rows[i]] = (float)((adv_raw[flat] - mean) / (sd + 1e-8));
+    if (tid == 0) { out[0] = c; out[1] = mean; out[2] = sd; }
+}
+}  // namespace mi
+
 namespace {
 __global__ __launch_bounds__(256) void relu_grad_kernel(const float* __restrict__ g, const float* __restrict__ h, long long n, float* __restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -541,6 +600,32 @@ int mi_ppo_value_clip_stats(void* stream, const float* values_new, const float* 
     hipLaunchKernelGGL(ppo_value_clip_reduce_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)scratch, nb, accumulate, stats);
     return mi_check_launch("ppo_value_clip_stats");
 }
+
+// stats: {count, mean, std} per minibatch
+long long mi_ppo_minibatch_advantages_stats_doubles(int n, int batch_size) {
+    return (n < 1 || batch_size < 1) ? -1 : 3LL * (((long long)n + batch_size - 1) / batch_size);
+}
+
+// adv_raw fp64 [num_envs, T], perm int32 [n] table rows, tab_adv_out fp32 [num_envs (T + 1)], stats fp64 [ceil(n / batch_size), 3] (all device).  Every check runs
+// before the launch.
+#define MBA_FAIL(text) return mi_fail(MI_ERR_ARG, "mi_ppo_minibatch_advantages: " text)
+int mi_ppo_minibatch_advantages(void* stream, const double* adv_raw, const int* perm, int n, int batch_size, int num_envs, int T, int ddof, float* tab_adv_out,
+                                double* stats) {
+    if (!adv_raw) MBA_FAIL("adv_raw is missing");
+    if (!perm) MBA_FAIL("perm is missing");
+    if (!tab_adv_out) MBA_FAIL("tab_adv_out is missing");
+    if (!stats) MBA_FAIL("stats is missing");
+    if (n < 1) MBA_FAIL("n: perm holds at least one entry (n >= 1)");
+    if (batch_size < 1) MBA_FAIL("batch_size >= 1");
+    if (num_envs < 1 || num_envs > MI_ROLLOUT_MAX_ENVS) MBA_FAIL("num_envs outside [1, MI_ROLLOUT_MAX_ENVS]");
+    if (T < 1 || T > MI_ROLLOUT_MAX_HORIZON) MBA_FAIL("T outside [1, MI_ROLLOUT_MAX_HORIZON]");
+    if (ddof != 0 && ddof != 1) MBA_FAIL("ddof is 0 (population std) or 1 (sample std)");
+    const long long n_mb = ((long long)n + batch_size - 1) / batch_size;
+    hipLaunchKernelGGL(ppo_minibatch_adv_kernel, dim3((unsigned)n_mb), dim3(MBA_THREADS), 0, (hipStream_t)stream, adv_raw, perm, n, batch_size, num_envs, T, ddof,
+                       tab_adv_out, stats);
+    return mi_check_launch("ppo_minibatch_advantages");
+}
+#undef MBA_FAIL
 
 int mi_policy_head(void* stream, const float* u, const float* logstd, const float* noise, const float* low, const float* high,
                    int M, int A, int greedy, float* action, float* mean_out) {

@@ -138,6 +138,24 @@ start from count 0 instead of the prior count = 1e-4, var = 1.  reset() starts a
 a recorded step would poison the statistics for good: update() raises ValueError before anything is launched or changed.  The value error and the explained variance of
 update_with_diagnostics() are then measured on the scaled returns.  With the setting off none of these keys appears and the update makes the launches it always made.
 
+Both buffers can normalise the advantages PER MINIBATCH, inside the SGD loop, as the libraries do whose defaults clip_range, max_grad_norm = 0.5 and target_kl come from
+(SB3 normalize_advantage=True, CleanRL norm_adv=True): the scale of every step's policy gradient is then set by that step's batch_size samples, not by a segment
+(normalize="segment", train.py:176-177) or by the whole collection (normalize="batch").  The finish call runs as it always did; with set_minibatch_normalization() one
+device call per epoch (mi_ppo_minibatch_advantages: one launch, one block per minibatch, fp64, ordered sums, no atomics, bitwise reproducible) runs between the upload
+of the epoch's shuffled rows and its first step: it takes the RAW advantages the finish call left, normalises every minibatch of the epoch by its own mean and std
+((a - mean) / (std + 1e-8)) and writes a second fp32 table, which the epoch's SGD steps gather from in place of `advantages`.  The steps themselves are the code they were:
+
+    buf.set_minibatch_normalization()                              # ddof=0: population std;  ddof=1: torch's .std(), what SB3 / CleanRL divide by;  None: off
+    out = buf.update(num_epochs=10, batch_size=32)
+    out["minibatch_adv_stats"]                                     # float64 [number of SGD steps, 3]: {count, mean, std} of every step's raw advantages
+    out["minibatch_advantages"]                                    # float32 [num_envs, T]: what the last epoch's steps read;  out["advantages"]: the finish call's, NOT read by the steps
+
+Two deviations from SB3, both on purpose: ddof=0 by default (the population std, as everywhere else in this project; SB3 and CleanRL use the sample std: pass ddof=1
+to compare), and a one-sample minibatch -- the partial last one of an epoch -- yields 0 (its std is 0 with either ddof) instead of being left unnormalised: that step's
+surrogate term has no gradient, its value and entropy terms have theirs.  The numpy RNG draws, the launches of every step, the statistics pass of update_with_diagnostics() and reward scaling are
+unchanged; `stage_times` gains "minibatch_norm", which is also part of "sgd".  With the setting off none of these keys appears and the update makes the launches it
+always made.
+
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import os
@@ -555,6 +573,14 @@ def reward_scaling_state_checked(d, num_envs, who="RolloutBuffer.load_reward_sca
     return out
 
 
+def minibatch_normalization_ddof(ddof=0, who="RolloutBuffer.set_minibatch_normalization"):
+    """The checked delta degrees of freedom of per-minibatch advantage normalisation (mi_ppo_minibatch_advantages) -> int: 0 (population std, the project's) or 1
+    (sample std, torch's .std()).  bool, str, float and every other value raise ValueError.  numpy only: no device and no library involved."""
+    if isinstance(ddof, (bool, np.bool_)) or not isinstance(ddof, (int, np.integer)) or int(ddof) not in (0, 1):
+        raise ValueError("%s: ddof is 0 (population std) or 1 (sample std, torch's .std()), got %r" % (who, ddof))
+    return int(ddof)
+
+
 def _diagnostics(who, target_kl):
     """The checked arguments of update_with_diagnostics (raises before any device work): target_kl is None or a positive finite float."""
     if target_kl is not None:
@@ -590,6 +616,8 @@ class RolloutBuffer:
         self.actions = torch.zeros(n, int(ppo.num_actions), device=self.device)
         self.values, self.returns, self.advantages, self.logp_old = (torch.zeros(n, device=self.device) for _ in range(4))
         self._reward_scaling = None                                                  # running-return reward scaling (set_reward_scaling): None = off
+        self._minibatch_norm = None                                                  # per-minibatch advantage normalisation (set_minibatch_normalization): None = off
+        self._minibatch_advantages = None                                            # its fp32 table, allocated by the first update that needs it
 
     def set_reward_scaling(self, clip=10.0, epsilon=1e-8, frozen=False):
         """Turns running-return reward scaling on (see the module docstring): every update divides its rewards by sqrt(var + epsilon) of the discounted returns seen so
@@ -644,6 +672,16 @@ class RolloutBuffer:
             ids = self.rows.env_ids(ids, ids.shape[0] if ids.ndim == 1 else 0)
             rs["carry"][torch.from_numpy(ids).to(self.device)] = 0.0
 
+    def set_minibatch_normalization(self, ddof=0):
+        """Turns per-minibatch advantage normalisation on (see the module docstring): in front of every epoch one mi_ppo_minibatch_advantages call normalises the raw
+        advantages of each of the epoch's minibatches by that minibatch's own mean and std (ddof = 0: population std; 1: sample std, torch's .std()) into a table of its
+        own, which the epoch's SGD steps read in place of `advantages`.  set_minibatch_normalization(None) turns it off and drops the table.  ValueError before anything
+        touches a device."""
+        if ddof is None:
+            self._minibatch_norm = self._minibatch_advantages = None
+            return
+        self._minibatch_norm = {"ddof": minibatch_normalization_ddof(ddof)}
+
     @property
     def lengths(self):
         return self.rows.lengths
@@ -679,7 +717,11 @@ class RolloutBuffer:
         clipping and the factor it was scaled by.  With reward scaling on (set_reward_scaling) mi_rollout_scale_rewards runs in front of the finish call with this
         update's gamma, the finish reads the scaled rewards, and the result gains `return_rms`, `reward_scale_den`, `scaled_rewards`, `discounted_returns`,
         `reward_clip_fraction` and `return_carry`; `stage_times` gains "reward_scaling", which is also part of "finish".  A reward that is not finite in a recorded
-        step then raises ValueError before anything is launched or changed."""
+        step then raises ValueError before anything is launched or changed.  With per-minibatch normalisation on (set_minibatch_normalization) one
+        mi_ppo_minibatch_advantages call runs in front of every epoch's first step over that epoch's shuffled rows, and the steps gather their advantage from the table
+        it writes: `advantages` is still the finish call's output, but the SGD steps did NOT read it.  The result gains `minibatch_adv_stats`, float64 [number of SGD
+        steps, 3] = every step's {count, mean, std} in step order, and `minibatch_advantages`, float32 [num_envs, T]: what the steps of the last epoch that ran read
+        (NaN beyond a row's length, all NaN for num_epochs = 0); `stage_times` gains "minibatch_norm", which is also part of "sgd"."""
         return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, None)
 
     def update_with_diagnostics(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, stage_times=None, target_kl=None):
@@ -734,6 +776,7 @@ class RolloutBuffer:
             recorded = np.arange(self.horizon)[None, :] < self.rows.lengths[:, None]
             if not np.isfinite(self.rows.rewards[recorded]).all():
                 raise ValueError(who + ".update: a recorded reward is not finite; it would poison the statistics of reward scaling for good")
+        mbn = getattr(self, "_minibatch_norm", None)                                 # per-minibatch advantage normalisation (set_minibatch_normalization): None = off
         batch_size = int(batch_size)
         E, T, ppo, device = self.num_envs, self.horizon, self.ppo, self.device
         pdev = ppo._need_dev()
@@ -795,14 +838,28 @@ class RolloutBuffer:
                     self._values_new = torch.zeros(self.n_table_rows, device=device)
             stats_scratch = torch.empty(pdev.stats_scratch_doubles(min(n_valid, chunk)), dtype=torch.float64, device=device)
             epochs, stopped = [], False
+        adv_table, mb_epochs = self.advantages, 0                                    # the table the steps gather their advantage from
+        if mbn is not None:
+            if getattr(self, "_minibatch_advantages", None) is None:
+                self._minibatch_advantages = torch.zeros(self.n_table_rows, device=device)
+            adv_table = self._minibatch_advantages
+            mb_stats = torch.zeros(int(num_epochs), -(-n_valid // batch_size), 3, dtype=torch.float64, device=device)      # {count, mean, std} of every step
         for _ in range(int(num_epochs)):
             indices = np.arange(n_valid)
             np.random.shuffle(indices)                                               # legacy numpy RNG, as train.py:194-195
             perm = torch.from_numpy(valid[indices]).to(device)                       # shuffled positions -> table rows
+            if mbn is not None:                                                      # this epoch's minibatches, each normalised alone, from the raw advantages
+                if stage_times is not None:
+                    torch.cuda.synchronize(device)
+                t_mb = time.perf_counter()
+                self.L.mi_ppo_minibatch_advantages(st, f64[0].data_ptr(), perm.data_ptr(), n_valid, batch_size, E, T, mbn["ddof"], adv_table.data_ptr(),
+                                                   mb_stats[mb_epochs].data_ptr())
+                mb_epochs += 1
+                mark("minibatch_norm", t_mb)
             for i in range(0, n_valid, batch_size):
                 mb = perm[i:i + batch_size]                                          # the last one may be partial (train.py:199-201)
                 m = int(mb.numel())
-                ppo._step_rows(self.states, self.actions, self.returns, self.advantages, logp_old, mb, m, m, **step_kw)
+                ppo._step_rows(self.states, self.actions, self.returns, adv_table, logp_old, mb, m, m, **step_kw)
                 ppo.train_step_counter += 1
                 records.append(pdev.losses.clone())
                 if clip:
@@ -845,6 +902,10 @@ class RolloutBuffer:
                     e["clipped_steps"] = int((gc[lo:hi, 1] < 1.0).sum())
         if diag is not None:
             out["epochs"], out["epochs_run"], out["stopped_early"] = epochs, len(epochs), stopped
+        if mbn is not None:                                                          # one readback behind the last epoch; only the epochs that ran
+            out["minibatch_adv_stats"] = mb_stats[:mb_epochs].reshape(-1, 3).cpu().numpy()
+            seen = (np.arange(T)[None, :] < lengths[:, None]) & (mb_epochs > 0)
+            out["minibatch_advantages"] = np.where(seen, adv_table.view(E, T + 1)[:, :T].cpu().numpy(), np.float32(np.nan)).astype(np.float32)
         if rs is not None:
             state, scaled = rs["state"].cpu().numpy(), scaled.cpu().numpy()
             out["return_rms"] = {"count": float(state[0]), "mean": float(state[1]), "var": float(state[2] / state[0]) if state[0] > 0 else 1.0}

@@ -612,6 +612,27 @@ int mi_ppo_grad_norm(void* h, void* stream, float max_norm);
 int mi_ppo_train_step_vclip(void* h, void* comm, void* stream, const float* states, const float* actions, const float* returns, const float* advantage, const float* logp_old, const float* old_values, float clip_range_vf, const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon);
 long long mi_ppo_value_clip_stats_scratch_doubles(int M);
 int mi_ppo_value_clip_stats(void* stream, const float* values_new, const float* old_values, const float* returns, const int* row_idx, int n_rows, int M, float clip_range_vf, int accumulate, double* scratch, double* stats);
+/* advantages normalised PER MINIBATCH, inside the SGD loop — SB3's normalize_advantage, CleanRL's norm_adv; no reference counterpart in train.py, which normalises per
+ * trajectory (train.py:176-177): one pass per epoch between the finish calls (mi_rollout_finish*, which leave the raw advantages in fp64) and the epoch's SGD steps, which
+ * gather their advantage from an fp32 table by row index.  No engine handle.  adv_raw: fp64 [num_envs, T], the raw advantages (entries beyond a lane's length may hold
+ * NaN); perm: int32 [n], table rows e (T + 1) + t = slot t of lane e, the epoch's shuffled rows in the order the steps take them; tab_adv_out: fp32 [num_envs (T + 1)],
+ * the layout of the advantages table; stats: fp64 [n_mb, 3] with n_mb = ceil(n / batch_size) (all device).  Minibatch b is perm[b batch_size .. min((b + 1) batch_size, n)).
+ * An entry that names no step slot -- row < 0, row >= num_envs (T + 1), slot == T (a lane's bootstrap slot) -- is skipped: it does not count and nothing is written for
+ * it (the rule of the finish calls' segment descriptors for a one-step segment).  Over the c counted entries a of minibatch b, in fp64:
+ *   mean = sum(a) / c;   ss = sum((a - mean)^2)  (two passes);   std = (c - ddof >= 1) ? sqrt(ss / (c - ddof)) : 0.0
+ *   tab_adv_out[row] = (float)((a - mean) / (std + 1e-8))   (a true division, round to nearest even; the + 1e-8 of mi_adv_normalize)
+ *   stats[b] = {c, mean, std};  c == 0: stats[b] = {0, 0, 0} and nothing else is written
+ * ddof = 0: the population std the finish calls use; ddof = 1: the sample std (torch's .std(), what SB3 / CleanRL compute).  A one-sample minibatch has std 0 with
+ * either and its entry becomes 0.0; equal advantages give exactly 0.0 wherever their sum is exact (mean == a).  One launch, one block per minibatch; the gathered
+ * doubles are read from global memory again in each of the three passes (no LDS is sized by the minibatch, which can be the whole collection).  Every sum in ONE
+ * order: thread i of the block's 256 adds positions i, i + 256, .. of the minibatch from the first, a wave reduction (xor tree of shuffles) inside each of the four
+ * waves, the waves' partials added in wave order by one thread; no floating-point atomics: two calls are bitwise equal.  Rows that perm does not name are neither read
+ * from adv_raw nor written in tab_adv_out; perm and adv_raw are not written.  A row named twice inside one call is stored twice (by its minibatches, in no order).
+ * mi_ppo_minibatch_advantages_stats_doubles(n, batch_size) = 3 ceil(n / batch_size), the doubles of `stats` (needs no GPU; -1 for n < 1 or batch_size < 1).
+ * Errors (MI_ERR_ARG, checked before the launch, nothing is written; the message names the argument): adv_raw, perm, tab_adv_out or stats missing; n < 1;
+ * batch_size < 1; num_envs < 1 or > MI_ROLLOUT_MAX_ENVS; T < 1 or > MI_ROLLOUT_MAX_HORIZON; ddof outside {0, 1}. */
+long long mi_ppo_minibatch_advantages_stats_doubles(int n, int batch_size);
+int mi_ppo_minibatch_advantages(void* stream, const double* adv_raw, const int* perm, int n, int batch_size, int num_envs, int T, int ddof, float* tab_adv_out, double* stats);
 
 #ifdef __cplusplus
 }

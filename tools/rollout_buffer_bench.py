@@ -19,7 +19,12 @@ and prints for both: step calls per update, samples per update, samples per step
 adds the same update through RolloutBuffer.update_with_diagnostics (one statistics pass per epoch, mi_ppo_update_stats_idx) to the interleaved rounds, without the
 replay paths: the "stats" stage is the cost of the passes, everything else is the plain update's.  A third path runs it with PPO.set_value_clip(--value-clip) on:
 its "stats" stage also holds the mi_ppo_value_clip_stats launches (the difference of the two "stats" stages per epoch is their cost) and its SGD steps are
-mi_ppo_train_step_vclip calls."""
+mi_ppo_train_step_vclip calls.
+
+    python tools/rollout_buffer_bench.py --minibatch-norm [--ddof 0] [--envs 1024] [--steps 128] [--batch 32,2048] [--epochs 3] ...
+
+runs the same update with RolloutBuffer.set_minibatch_normalization off and on in interleaved rounds, without the replay paths: the "minibatch_norm" stage (part of
+"sgd") is the cost of the one mi_ppo_minibatch_advantages call per epoch, and the line ends with the on / off ratio of the medians."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
@@ -41,6 +46,8 @@ ap.add_argument("--no-host-frames", action="store_true", help="skip replay_updat
 ap.add_argument("--no-box", action="store_true")
 ap.add_argument("--continuous", action="store_true", help="RolloutBuffer against ContinuousRolloutBuffer on one scripted set of simulators (no replay paths)")
 ap.add_argument("--diagnostics", action="store_true", help="RolloutBuffer.update against update_with_diagnostics in interleaved rounds (no replay paths)")
+ap.add_argument("--minibatch-norm", action="store_true", help="RolloutBuffer.update with per-minibatch advantage normalisation off and on in interleaved rounds (no replay paths)")
+ap.add_argument("--ddof", type=int, default=0, help="ddof of the normalised path of --minibatch-norm")
 ap.add_argument("--value-clip", type=float, default=0.2, help="eps_v of the value-clipped path of --diagnostics")
 ap.add_argument("--mean-episode", type=float, default=None, help="mean of the geometric episode lengths of --continuous (default: steps / 3)")
 args = ap.parse_args()
@@ -127,8 +134,8 @@ if args.continuous:
 idx = rng.randint(0, args.pool, (E, T + 1))
 meas = np.stack([rng.uniform(-1, 1, (E, T + 1)), rng.uniform(0, 1, (E, T + 1)), rng.uniform(0, 30, (E, T + 1))], axis=-1).astype(np.float32)
 rewards, dones = rng.uniform(0, 1, (E, T)), np.zeros((E, T))
-frames_d = None if args.diagnostics else torch.from_numpy(pool).to("cuda")[torch.from_numpy(idx).to("cuda")]           # [E, T + 1, 80, 160, 3] uint8 in HBM
-frames_h = None if args.no_host_frames or args.diagnostics else pool[idx]
+frames_d = None if args.diagnostics or args.minibatch_norm else torch.from_numpy(pool).to("cuda")[torch.from_numpy(idx).to("cuda")]           # [E, T + 1, 80, 160, 3] uint8 in HBM
+frames_h = None if args.no_host_frames or args.diagnostics or args.minibatch_norm else pool[idx]
 
 buf = RolloutBuffer(vae, agent, E, T)
 
@@ -157,6 +164,12 @@ def run(path, batch):
         buf.update(num_epochs=args.epochs, batch_size=batch, stage_times=st)
     elif path == "buffer + diagnostics":
         buf.update_with_diagnostics(num_epochs=args.epochs, batch_size=batch, stage_times=st)
+    elif path == "+ minibatch norm":
+        buf.set_minibatch_normalization(args.ddof)
+        try:
+            buf.update(num_epochs=args.epochs, batch_size=batch, stage_times=st)
+        finally:
+            buf.set_minibatch_normalization(None)
     elif path == "+ value clip":
         agent.set_value_clip(args.value_clip)
         try:
@@ -172,6 +185,8 @@ def run(path, batch):
 paths = ["buffer", "replay, device frames"] + ([] if frames_h is None else ["replay, host frames"])
 if args.diagnostics:
     paths = ["buffer", "buffer + diagnostics", "+ value clip"]
+if args.minibatch_norm:
+    paths = ["buffer", "+ minibatch norm"]
 for batch in [int(x) for x in args.batch.split(",") if x]:
     for p in paths:
         run(p, batch)                                                                     # warm-up (engine growth, allocator)
@@ -184,8 +199,13 @@ for batch in [int(x) for x in args.batch.split(",") if x]:
         tot = sorted(r[0] for r in res[p])
         med = tot[len(tot) // 2]
         stages = next(r[1] for r in res[p] if r[0] == med)
-        front = sum(v for k, v in stages.items() if k not in ("sgd", "stats"))
+        front = sum(v for k, v in stages.items() if k not in ("sgd", "stats", "minibatch_norm"))
         print("  %-22s %.4f s (rounds %.4f - %.4f)  in front of the SGD loop %.4f s  | %s" % (p, med, tot[0], tot[-1], front, "  ".join("%s %.4f" % kv for kv in stages.items())), flush=True)
+        if args.minibatch_norm:
+            off = sorted(r[0] for r in res["buffer"])[args.rounds // 2]
+            print("    every round: %s" % "  ".join("%.4f" % r[0] for r in res[p]) + ("" if "minibatch_norm" not in stages else
+                  "   minibatch_norm stage %.6f s = %.1f us per epoch, %.3f %% of the update;  on / off %.4f" % (stages["minibatch_norm"], 1e6 * stages["minibatch_norm"] / max(args.epochs, 1),
+                                                                                                                   100.0 * stages["minibatch_norm"] / med, med / off)), flush=True)
         if args.diagnostics:
             print("    every round: %s" % "  ".join("%.4f" % r[0] for r in res[p]) + ("" if "stats" not in stages else
                   "   stats stage %.4f s = %.4f s per epoch, %.1f %% of the update" % (stages["stats"], stages["stats"] / max(args.epochs, 1), 100.0 * stages["stats"] / med)), flush=True)
