@@ -67,6 +67,12 @@ __host__ __device__ __forceinline__ float u8_to_unit_exact(float k) {
     const float r = __builtin_fmaf(-q, 255.0f, k);
     return __builtin_fmaf(r, U8_RCP255, q);
 }
+// ---- one entry of a normalised observation (running observation normalisation, include/mi355_carla.h: mi_rollout_step_batch_norm) ----
+// fp32: one subtract, one multiply (never contracted: there is no add behind the product), then the clamp into +-clip (+inf: never).  The normalise kernel of the
+// rollout step and the clamped counts of mi_rollout_obs_stats both spell it through this function.
+__host__ __device__ __forceinline__ float obs_normalize(float s, float mean, float inv_std, float clip) {
+    return fminf(fmaxf((s - mean) * inv_std, -clip), clip);
+}
 // source element -> float for the narrow-layer loaders: float / bf16 bits / uint8 camera byte (bf16-exact form, see above)
 template <typename TS> __device__ __forceinline__ float src_to_f32(TS v);
 template <> __device__ __forceinline__ float src_to_f32<float>(float v) { return v; }

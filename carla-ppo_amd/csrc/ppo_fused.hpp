@@ -57,5 +57,10 @@ int mi_rollout_policy_batch_rec(hipStream_t st, const mi::PpoFusedParams& q, con
                                 const MiRolloutRec& rec);
 // the value-only form (mi_rollout_value_batch_rec): the value trunk and the value head alone; out [n], and the value of call row e is also stored as final_values[table_rows[e]]
 struct MiRolloutValueRec { const int* table_rows; long long n_table_rows; float* final_values; };
+// running observation normalisation (mi_rollout_step_batch_norm / mi_rollout_value_batch_norm): fp32 mean / inv_std [din] on the device, the clamp, the caller's
+// n x din buffer the normalised rows go to, and where they are recorded (table_rows NULL: nowhere; tab_states unused by the value-only form)
+struct MiRolloutObsNorm { const float* mean; const float* inv_std; float clip; float* nstate; const int* table_rows; long long n_table_rows; float* tab_states; };
 int mi_rollout_value_batch(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, int n, float* out,
-                           const MiRolloutValueRec& rec);
+                           const MiRolloutValueRec& rec, const MiRolloutObsNorm* nrm = nullptr);
+int mi_rollout_policy_batch_norm(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n,
+                                 float* out, const MiRolloutRec* rec, const MiRolloutObsNorm& nrm);

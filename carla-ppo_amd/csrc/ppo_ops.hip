@@ -454,6 +454,103 @@ __global__ __launch_bounds__(64) void rollout_reward_scale_kernel(const double* 
     const double den = state[3];
     for (int t = lane; t < L; t += WAVE) rewards_out[flat + t] = fmin(fmax(rewards[flat + t] / den, -clip), clip);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// mi_rollout_obs_stats: the running per-column moments behind observation normalisation (the other half of baselines' VecNormalize), in the style of the pass above:
+// fp64, ordered sums, no atomics.  The n rows row_idx[i] of the fp32 table tab [n_table_rows][din] (a row outside the table is skipped and does not count) are cut into
+// nb = ceil(n / chunk) blocks of `chunk` consecutive list entries -- chunk = max(32, ceil(n / 256)), a function of n alone, so two runs add the same terms in the same
+// order --; thread t of a block owns the columns t, t + 128, .. and walks its block's rows in list order (neighbouring threads read neighbouring floats of a row).
+//   rollout_obs_sum_kernel     part[b][j] = the block's column sum, cnt[b] = its rows inside the table, clampc[b][j] = how many of its entries obs_normalize() -- the
+//                              normalise kernel's expression -- puts at +-clip under the mean32 / inv32 the collection was normalised with
+//   rollout_obs_dev_kernel     the batch mean of column j from the partials in block order (every block adds them alike: the same bits everywhere; block 0 leaves
+//                              them and the count in scratch), then part2[b][j] = the block's sum of (x - m_b[j])^2
+//   rollout_obs_merge_kernel   one block: M2_b[j] from part2 in block order, the Chan / Welford merge into state = {count, mean[din], M2[din]} (merge = 1) and the
+//                              derived fp32 mean32[j] / inv32[j] = 1 / sqrt(M2[j] / count + epsilon)  (columns below first_col: 0 / 1)
+//                              A batch with an entry that is not finite (some batch mean is not finite) is not merged at all: state stays bitwise as it was
+// ---------------------------------------------------------------------------------------------------
+constexpr int OBS_THREADS = 128;
+
+__global__ __launch_bounds__(OBS_THREADS) void rollout_obs_sum_kernel(const float* __restrict__ tab, long long n_table_rows, const int* __restrict__ row_idx, long long n, int din,
+                                                                      int chunk, const float* __restrict__ obs_mean, const float* __restrict__ obs_inv_std, float clip,
+                                                                      double* __restrict__ part, double* __restrict__ clampc, double* __restrict__ cnt) {
+    const long long b = blockIdx.x, lo = b * chunk, hi = min(lo + (long long)chunk, n);
+    for (int j = threadIdx.x; j < din; j += OBS_THREADS) {
+        const float m32 = obs_mean[j], inv32 = obs_inv_std[j];
+        double s = 0.0, c = 0.0, k = 0.0;
+        for (long long i = lo; i < hi; ++i) {
+            const long long r = row_idx[i];
+            if (r < 0 || r >= n_table_rows) continue;
+            const float x = tab[r * din + j];
+            s += (double)x;
+            k += 1.0;
+            if (fabsf(obs_normalize(x, m32, inv32, clip)) == clip) c += 1.0;
+        }
+        part[b * din + j] = s;
+        clampc[b * din + j] = c;
+        if (j == 0) cnt[b] = k;
+    }
+}
+
+__global__ __launch_bounds__(OBS_THREADS) void rollout_obs_dev_kernel(const float* __restrict__ tab, long long n_table_rows, const int* __restrict__ row_idx, long long n, int din,
+                                                                      int chunk, int nb, const double* __restrict__ part, const double* __restrict__ cnt,
+                                                                      double* __restrict__ part2, double* __restrict__ bmean, double* __restrict__ bcount) {
+    const long long b = blockIdx.x, lo = b * chunk, hi = min(lo + (long long)chunk, n);
+    for (int j = threadIdx.x; j < din; j += OBS_THREADS) {
+        double tot = 0.0, k = 0.0;                         // (the count is exact in fp64)
+        for (int bb = 0; bb < nb; ++bb) { tot += part[(long long)bb * din + j]; k += cnt[bb]; }
+        const double mean = k < 1.0 ? 0.0 : tot / k;
+        if (b == 0) {
+            bmean[j] = mean;
+            if (j == 0) bcount[0] = k;
+        }
+        double ss = 0.0;
+        for (long long i = lo; i < hi; ++i) {
+            const long long r = row_idx[i];
+            if (r < 0 || r >= n_table_rows) continue;
+            const double d = (double)tab[r * din + j] - mean;
+            ss += d * d;
+        }
+        part2[b * din + j] = ss;
+    }
+}
+
+// nb = 0 (an empty list): nothing is merged and the batch figures are 0.  merge = 0, an empty batch and a batch that is not finite leave state bitwise as it was.
+__global__ __launch_bounds__(OBS_THREADS) void rollout_obs_merge_kernel(int din, int nb, int first_col, int merge, double epsilon, const double* __restrict__ part2,
+                                                                        const double* __restrict__ clampc, const double* __restrict__ bmean,
+                                                                        const double* __restrict__ bcount, double* __restrict__ state, float* __restrict__ obs_mean,
+                                                                        float* __restrict__ obs_inv_std, double* __restrict__ batch_out) {
+    const double count = state[0], n_b = nb > 0 ? bcount[0] : 0.0;
+    // a batch with an entry that is not finite is not merged, in any column: it would make mean / M2 NaN for good.  A column's batch mean is finite exactly when all
+    // its entries are (fewer than 2^31 fp32 terms cannot overflow an fp64 sum); the caller sees the refusal in batch_out's means.
+    int fin = 1;                                           // (each wave looks at every column, a lane at every 64th, and votes: no LDS)
+    for (int j = threadIdx.x & (WAVE - 1); j < din && nb > 0; j += WAVE) fin &= isfinite(bmean[j]) ? 1 : 0;
+    const bool finite = __all(fin);
+    __syncthreads();                                       // every thread holds the old count before thread 0 stores the new one
+    const bool do_merge = merge && n_b >= 1.0 && finite;
+    const double n_new = do_merge ? count + n_b : count;
+    for (int j = threadIdx.x; j < din; j += OBS_THREADS) {
+        double m2_b = 0.0, cl = 0.0;
+        for (int bb = 0; bb < nb; ++bb) { m2_b += part2[(long long)bb * din + j]; cl += clampc[(long long)bb * din + j]; }
+        const double m_b = nb > 0 ? bmean[j] : 0.0;
+        double mean = state[1 + j], m2 = state[1 + din + j];
+        if (do_merge) {
+            const double delta = m_b - mean;
+            mean = mean + delta * n_b / n_new;
+            m2 = m2 + (m2_b + delta * delta * count * n_b / n_new);
+            state[1 + j] = mean;
+            state[1 + din + j] = m2;
+        }
+        const double var = n_new > 0.0 ? m2 / n_new : 1.0;
+        const double inv = 1.0 / sqrt(var + epsilon);
+        const bool normalized = j >= first_col;
+        obs_mean[j] = normalized ? (float)mean : 0.f;
+        obs_inv_std[j] = normalized ? (float)inv : 1.f;
+        batch_out[j] = m_b;
+        batch_out[din + j] = m2_b;
+        batch_out[2 * din + j] = cl;
+    }
+    if (threadIdx.x == 0 && do_merge) state[0] = n_new;
+}
 }  // namespace mi
 
 // ---------------------------------------------------------------------------------------------------
@@ -777,5 +874,48 @@ int mi_rollout_scale_rewards(void* stream, const double* rewards, const double* 
     return mi_check_launch("rollout_scale_rewards");
 }
 #undef SCALE_FAIL
+
+// rows per block of the moments pass and the number of blocks: functions of n alone
+static int obs_stats_chunk(long long n) { const long long c = (n + 255) / 256; return (int)(c < 32 ? 32 : c); }
+static int obs_stats_blocks(long long n) { const int c = obs_stats_chunk(n); return (int)((n + c - 1) / c); }
+
+// scratch: column sums | squared deviations | clamped counts, [nb][din] each | rows per block [nb] | batch mean [din] | batch count
+long long mi_rollout_obs_stats_scratch_doubles(long long n, int din) {
+    if (n < 1 || din < 1 || n > 0x7fffffffLL) return -1;
+    const long long nb = obs_stats_blocks(n);
+    return 3 * nb * din + nb + din + 1;
+}
+
+// Every check runs before the first launch.
+#define OBS_FAIL(text) return mi_fail(MI_ERR_ARG, "mi_rollout_obs_stats: " text)
+int mi_rollout_obs_stats(void* stream, const float* tab_raw_states, long long n_table_rows, const int* row_idx, long long n, int din, int first_col, int merge,
+                         double epsilon, float clip, double* state, float* obs_mean, float* obs_inv_std, double* scratch, double* batch_out) {
+    if (!state || !obs_mean || !obs_inv_std || !batch_out) OBS_FAIL("missing buffers");
+    if (n < 0 || n > 0x7fffffffLL) OBS_FAIL("n is the length of the row list, 0 <= n < 2^31 (0: derive only)");
+    if (n > 0 && (!tab_raw_states || !row_idx || !scratch)) OBS_FAIL("missing buffers");
+    if (din < 1 || (n > 0 && n_table_rows < 1)) OBS_FAIL("empty input (din >= 1, n_table_rows >= 1)");
+    if (first_col < 0 || first_col > din) OBS_FAIL("first_col outside [0, din]");
+    if (merge != 0 && merge != 1) OBS_FAIL("merge is 0 (frozen statistics) or 1");
+    if (!std::isfinite(epsilon) || epsilon < 0.0) OBS_FAIL("epsilon is a finite value >= 0");
+    if (!(clip > 0.f)) OBS_FAIL("clip is a positive value (+inf: never clamp)");
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = n > 0 ? obs_stats_blocks(n) : 0, chunk = n > 0 ? obs_stats_chunk(n) : 0;
+    double* part = scratch;
+    double* part2 = nb ? part + (long long)nb * din : nullptr;
+    double* clampc = nb ? part2 + (long long)nb * din : nullptr;
+    double* cnt = nb ? clampc + (long long)nb * din : nullptr;
+    double* bmean = nb ? cnt + nb : nullptr;
+    double* bcount = nb ? bmean + din : nullptr;
+    if (nb) {
+        hipLaunchKernelGGL(rollout_obs_sum_kernel, dim3(nb), dim3(OBS_THREADS), 0, st, tab_raw_states, n_table_rows, row_idx, n, din, chunk, obs_mean, obs_inv_std, clip,
+                           part, clampc, cnt);
+        hipLaunchKernelGGL(rollout_obs_dev_kernel, dim3(nb), dim3(OBS_THREADS), 0, st, tab_raw_states, n_table_rows, row_idx, n, din, chunk, nb, part, cnt, part2, bmean,
+                           bcount);
+    }
+    hipLaunchKernelGGL(rollout_obs_merge_kernel, dim3(1), dim3(OBS_THREADS), 0, st, din, nb, first_col, merge, epsilon, part2, clampc, bmean, bcount, state, obs_mean,
+                       obs_inv_std, batch_out);
+    return mi_check_launch("rollout_obs_stats");
+}
+#undef OBS_FAIL
 
 }  // extern "C"

@@ -406,6 +406,38 @@ __global__ __launch_bounds__(256) void rollout_value_rec_kernel(const RollValueP
     if (r >= 0 && r < q.n_table_rows) q.final_values[r] = v;
 }
 
+// the observation normaliser (mi_rollout_step_batch_norm / mi_rollout_value_batch_norm), launched between the mean layer and trunk layer 1: block e normalises the
+// din entries of environment e's state, thread t the columns t, t + 128, .. (no division anywhere: the kernel is its latency).  s = the raw entry (mean_raw + mean_bias
+// for a latent column -- the sum the heads return as z --, the measurement as fed for the others); nstate[e][j] = obs_normalize(s, obs_mean[j], obs_inv_std[j], clip),
+// and the same register as a plain vector store to tab_states[table_rows[e]][j] where that row lies in [0, n_table_rows) (table_rows NULL: nothing is recorded).
+// Trunk layer 1 then reads nstate as a state vector without bias or tail.
+struct RollObsNormParams {
+    const float *mean_raw, *mean_bias, *meas;             // raw means [n][z_dim], the mean layer's bias [z_dim], measurements [n][din - z_dim]
+    const float *obs_mean, *obs_inv_std; float clip;      // fp32 [din] each; clip > 0 (+inf: never clamps)
+    float* nstate;                                        // [n][din]
+    const int* table_rows; long long n_table_rows; float* tab_states;
+    int n, z_dim, din;
+};
+
+__global__ __launch_bounds__(128) void rollout_obs_norm_kernel(const RollObsNormParams p) {
+    const long long e = blockIdx.x;
+    if (e >= p.n) return;
+    const float* z = p.mean_raw + e * p.z_dim;
+    const long long ms = e * (p.din - p.z_dim) - p.z_dim;             // measurement j - z_dim of environment e is p.meas[ms + j]
+    float* dst = p.nstate + e * p.din;
+    float* tab = nullptr;
+    if (p.table_rows) {
+        const long long r = p.table_rows[e];
+        if (r >= 0 && r < p.n_table_rows) tab = p.tab_states + r * p.din;
+    }
+    for (int j = threadIdx.x; j < p.din; j += 128) {
+        const float s = j < p.z_dim ? z[j] + p.mean_bias[j] : p.meas[ms + j];
+        const float v = obs_normalize(s, p.obs_mean[j], p.obs_inv_std[j], p.clip);
+        dst[j] = v;
+        if (tab) tab[j] = v;
+    }
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -549,13 +581,25 @@ static int fill_trunks_batch(RollConvBatchParams& l1, dim3& g1, RollConvBatchPar
     return MI_OK;
 }
 
+// running observation normalisation (nrm != NULL): the normalise launch, and trunk layer 1 re-aimed at what it wrote -- the same rollout_conv_batch_kernel<3> with
+// x = nstate [n][din], split = K = din, no bias and no tail (both descriptors empty: every load of them returns 0.0)
+static void obs_norm_layer1(hipStream_t st, RollConvBatchParams& l1, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim,
+                            const float* measurements, int n, const MiRolloutObsNorm& nrm) {
+    const RollObsNormParams p = {mean_raw, mean_bias, measurements, nrm.mean, nrm.inv_std, nrm.clip, nrm.nstate, nrm.table_rows, nrm.n_table_rows, nrm.tab_states, n, z_dim, q.din};
+    hipLaunchKernelGGL(rollout_obs_norm_kernel, dim3(n), dim3(128), 0, st, p);
+    l1.x = nrm.nstate; l1.x_bias = nullptr; l1.x_tail = nullptr; l1.split = q.din;
+    l1.x_row = (unsigned)q.din; l1.t_row = 0;
+    l1.x_bytes = (unsigned)n * (unsigned)q.din * 4u; l1.xb_bytes = 0; l1.tail_bytes = 0;
+}
+
 // trunks and heads of n environments: mean_raw [n][z_dim], measurements [n][din - z_dim], noise [n][A], out [n][A + 1 + z_dim]; raw sums in q.h1 / q.h2 as [net][n][H]
 static int policy_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
-                        const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec) {
+                        const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec, const MiRolloutObsNorm* nrm = nullptr) {
     RollConvBatchParams l1, l2; dim3 g1, g2; RollHeadParams h;
     const int rc = fill_trunks_batch(l1, g1, l2, g2, q, mean_raw, mean_bias, z_dim, measurements, n);
     if (rc != MI_OK) return rc;
     fill_head(h, q, mean_raw, mean_bias, z_dim, noise, greedy, out);
+    if (nrm) obs_norm_layer1(st, l1, q, mean_raw, mean_bias, z_dim, measurements, n, *nrm);
     launch_conv_batch(st, g1, l1);
     launch_conv_batch(st, g2, l2);
     if (rec) {
@@ -572,11 +616,12 @@ static int policy_batch(hipStream_t st, const PpoFusedParams& q, const float* me
 // the VALUE trunk alone and the value-only heads: the batched trunk stages with their operands moved to net 1 and half the grid (the policy net's half of q.h1 / q.h2
 // is neither cleared, written nor read), out [n] = the values, also left in rec.final_values[rec.table_rows[e]]
 int mi_rollout_value_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, int n, float* out,
-                           const MiRolloutValueRec& rec) {
+                           const MiRolloutValueRec& rec, const MiRolloutObsNorm* nrm) {
     RollConvBatchParams l1, l2; dim3 g1, g2;
     const int rc = fill_trunks_batch(l1, g1, l2, g2, q, mean_raw, mean_bias, z_dim, measurements, n);
     if (rc != MI_OK) return rc;
-    l1.x += l1.x_net; l1.x_bias += l1.xb_net; l1.w += l1.w_net; l1.out += l1.out_net;      // (layer 1's x / bias strides are 0: both nets read the one state)
+    if (nrm) obs_norm_layer1(st, l1, q, mean_raw, mean_bias, z_dim, measurements, n, *nrm);
+    l1.w += l1.w_net; l1.out += l1.out_net;                                                // (layer 1's x / bias strides are 0: both nets read the one state)
     l2.x += l2.x_net; l2.x_bias += l2.xb_net; l2.w += l2.w_net; l2.out += l2.out_net;
     g1.y = l1.row_tiles; g2.y = l2.row_tiles;                                              // blockIdx.y / row_tiles = 0: the kernels' "net 0" is the value net
     launch_conv_batch(st, g1, l1);
@@ -594,4 +639,10 @@ int mi_rollout_policy_batch(hipStream_t st, const PpoFusedParams& q, const float
 int mi_rollout_policy_batch_rec(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
                                 const float* noise, int greedy, int n, float* out, const MiRolloutRec& rec) {
     return policy_batch(st, q, mean_raw, mean_bias, z_dim, measurements, noise, greedy, n, out, &rec);
+}
+
+// the normalised step (mi_rollout_step_batch_norm): rec NULL = the evaluation step, the plain batched heads; else the recording heads, whose rec->states is the RAW table
+int mi_rollout_policy_batch_norm(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
+                                 const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec, const MiRolloutObsNorm& nrm) {
+    return policy_batch(st, q, mean_raw, mean_bias, z_dim, measurements, noise, greedy, n, out, rec, &nrm);
 }

@@ -978,14 +978,25 @@ long long mi_rollout_batch_workspace_bytes(void* vae_h, void* ppo_h, int n_envs)
 
 // one body for the plain call, the recording call (rec != NULL: mi_rollout_step_batch_rec, whose last launch is the recording heads) and the value-only call (vrec != NULL:
 // mi_rollout_value_batch_rec: the same encoder chain, then the value trunk and the value-only heads; out holds n floats)
-#define ROLL_FAIL(code, text) return mi_fail(code, vrec ? "mi_rollout_value_batch_rec: " text : "mi_rollout_step_batch: " text)
+// (the caller's own name in front of every message: the _norm entries share these checks)
+#define ROLL_FAIL(code, text) return mi_fail(code, nrm ? (vrec ? "mi_rollout_value_batch_norm: " text : "mi_rollout_step_batch_norm: " text) \
+                                                       : (vrec ? "mi_rollout_value_batch_rec: " text : "mi_rollout_step_batch: " text))
 static int rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
-                              void* scratch, long long scratch_bytes, float* out, const MiRolloutRec* rec, const MiRolloutValueRec* vrec = nullptr) {
+                              void* scratch, long long scratch_bytes, float* out, const MiRolloutRec* rec, const MiRolloutValueRec* vrec = nullptr,
+                              const MiRolloutObsNorm* nrm = nullptr) {
     VaeEngine* e = (VaeEngine*)vae_h;
+    if (nrm && (!e || !ppo_h)) return mi_fail(MI_ERR_STATE, vrec ? "mi_rollout_value_batch_norm: null handle" : "mi_rollout_step_batch_norm: null handle");
     if (!e || !ppo_h) return mi_fail(MI_ERR_STATE, vrec ? "mi_rollout_value_batch_rec: null handle" : rec ? "mi_rollout_step_batch_rec: null handle" : "mi_rollout_step_batch: null handle");
     if (!frames_u8 || !out || !scratch || (n_meas > 0 && !measurements) || (!greedy && !noise)) ROLL_FAIL(MI_ERR_ARG, "missing buffers");
     if (rec && (!rec->table_rows || !rec->states || !rec->actions || !rec->values || rec->n_table_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch_rec: missing tables");
-    if (vrec && (!vrec->table_rows || !vrec->final_values || vrec->n_table_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_rollout_value_batch_rec: missing tables");
+    if (vrec && (!vrec->table_rows || !vrec->final_values || vrec->n_table_rows < 1)) ROLL_FAIL(MI_ERR_ARG, "missing tables");
+    if (nrm) {                                           // running observation normalisation: every check before any launch
+#define NORM_FAIL(text) return mi_fail(MI_ERR_ARG, vrec ? "mi_rollout_value_batch_norm: " text : "mi_rollout_step_batch_norm: " text)
+        if (!nrm->mean || !nrm->inv_std || !nrm->nstate) NORM_FAIL("missing obs_mean / obs_inv_std / nstate");
+        if (((uintptr_t)nrm->nstate) & 15) NORM_FAIL("nstate must be 16-byte aligned");
+        if (!(nrm->clip > 0.f)) NORM_FAIL("obs_clip is a positive value (+inf: never clamp)");
+#undef NORM_FAIL
+    }
     if (n < 1 || n > MI_ROLLOUT_MAX_ENVS) ROLL_FAIL(MI_ERR_ARG, "1 <= n <= MI_ROLLOUT_MAX_ENVS");
     if (((uintptr_t)scratch) & 15) ROLL_FAIL(MI_ERR_ARG, "the scratch must be 16-byte aligned");
     if (scratch_bytes < roll_env_floats(e) * 4 * n) ROLL_FAIL(MI_ERR_ARG, "scratch too small (mi_rollout_batch_workspace_bytes)");
@@ -1012,7 +1023,8 @@ static int rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsi
     for (int i = 1; i < NCONV; ++i)                      // conv(i+1): conv2 reads conv1's finished output, the others raw sums + bias + ReLU on load
         CK(mi_rollout_conv_batch(st, act[i], i == 1 ? nullptr : e->bptr(2 * (i - 1) + 1), g.ih[i], g.iw[i], g.c[i], e->params + e->L.off[2 * i], g.c[i + 1], g.c[i + 1], 4, 4, act[i + 1], 0, n));
     CK(mi_rollout_conv_batch(st, act[NCONV], e->bptr(2 * (NCONV - 1) + 1), 1, 1, g.c[NCONV], e->params + e->L.off[8], 2 * d.z_dim, d.z_dim, 1, 1, mean_raw, g.flat, n));
-    if (vrec) return mi_rollout_value_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, n, out, *vrec);
+    if (vrec) return mi_rollout_value_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, n, out, *vrec, nrm);
+    if (nrm) return mi_rollout_policy_batch_norm(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out, rec, *nrm);
     if (rec) return mi_rollout_policy_batch_rec(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out, *rec);
     return mi_rollout_policy_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out);
 }
@@ -1034,6 +1046,26 @@ int mi_rollout_value_batch_rec(void* vae_h, void* ppo_h, void* stream, const uns
                                long long scratch_bytes, float* out, const int* table_rows, long long n_table_rows, float* tab_final_values) {
     const MiRolloutValueRec vrec = {table_rows, n_table_rows, tab_final_values};
     return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, nullptr, &vrec);
+}
+
+// the step behind running observation normalisation: the normalise launch in front of trunk layer 1 (nstate [n][din], caller-supplied), the normalised rows into
+// tab_states and -- through the existing recording heads -- the raw rows into tab_raw_states.  table_rows NULL: the evaluation step, nothing is recorded
+int mi_rollout_step_batch_norm(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
+                               void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate,
+                               const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values) {
+    const MiRolloutRec rec = {table_rows, n_table_rows, tab_raw_states, tab_actions, tab_values};
+    const MiRolloutObsNorm nrm = {obs_mean, obs_inv_std, obs_clip, nstate, table_rows, n_table_rows, tab_states};
+    if (table_rows && (!tab_states || !tab_raw_states || !tab_actions || !tab_values || n_table_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch_norm: missing tables");
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, table_rows ? &rec : nullptr, nullptr, &nrm);
+}
+
+// mi_rollout_value_batch_rec on the normalised observation (no table of states is written: the final observation of a truncated episode is no step)
+int mi_rollout_value_batch_norm(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n, void* scratch,
+                                long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate,
+                                const int* table_rows, long long n_table_rows, float* tab_final_values) {
+    const MiRolloutValueRec vrec = {table_rows, n_table_rows, tab_final_values};
+    const MiRolloutObsNorm nrm = {obs_mean, obs_inv_std, obs_clip, nstate, nullptr, 0, nullptr};
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, nullptr, &vrec, &nrm);
 }
 
 // VAE.encode (vae/models.py:199-202): frames -> mean [B,Z] fp32

@@ -156,6 +156,36 @@ surrogate term has no gradient, its value and entropy terms have theirs.  The nu
 unchanged; `stage_times` gains "minibatch_norm", which is also part of "sgd".  With the setting off none of these keys appears and the update makes the launches it
 always made.
 
+Both buffers can normalise the OBSERVATIONS by their running mean and standard deviation -- the other half of VecNormalize.  The policy's input is [z | steer, throttle,
+speed]: a speed of 0..30 next to 66 columns of unit scale, in front of settings (max_grad_norm = 0.5, eps_v = 0.2, the learning rate) that were tuned for standardised
+inputs.  The state is assembled inside the step's device call, so the normalisation lives there too: with set_observation_normalization() step(), bootstrap() and
+truncate() go through mi_rollout_step_batch_norm / mi_rollout_value_batch_norm -- one more launch (rollout_obs_norm_kernel) between the mean layer and trunk layer 1
+writes clamp((s - mean32[j]) * inv32[j], -clip, +clip) per column (fp32: one subtract, one multiply; clip = inf is allowed) into a buffer trunk layer 1 then reads.  The
+table `states` holds the NORMALISED rows, so log pi_old, the SGD steps, the statistics pass and every other reader of that table are the code they were and see the inputs
+the policy acted on; a second fp32 table `raw_states` takes the raw rows through the existing recording heads.  The last launch of update() (mi_rollout_obs_stats: fp64,
+ordered sums, no atomics, bitwise reproducible) merges the raw rows of rows.valid_rows() -- recorded steps only, no bootstrap slot -- into {count, mean[din], M2[din]} on
+the device (Chan / Welford per column) and derives mean32 = float32(mean), inv32 = float32(1 / sqrt(M2 / count + epsilon)) for the next collection:
+
+    buf.set_observation_normalization(clip=10.0, epsilon=1e-8)     # frozen=True: use the statistics, never update them;  normalize_latents=False;  None: off
+    buf.reset(); ...warm-up steps...; buf.merge_observation_statistics(); buf.reset()      # optional: the first collection otherwise clamps a raw speed of 30 to clip
+    out = buf.update(num_epochs=10, batch_size=32)
+    out["observation_rms"]                                         # {"count", "mean" [din], "var" [din]} after this update's merge
+    out["observation_clip_fraction"]                               # float64 [din]: the share of this collection's entries the clamp put at +-clip
+    ckpt = buf.observation_normalization_state()                   # ... buf.load_observation_normalization_state(ckpt) in the run that resumes
+    step = BatchedRolloutStep(vae, ppo, num_envs=1); step.set_observation_normalization(ckpt)      # evaluation: applies the statistics, never updates them
+    ppo.predict(normalize_observations(states, ckpt))              # the same formula in numpy float32, for callers that feed host states
+
+Two deviations from VecNormalize, both on purpose and the ones reward scaling made: ONE set of statistics per collection (VecNormalize updates obs_rms at every step,
+before it normalises that step; here nothing changes mean32 / inv32 between two updates, so every row of a collection is normalised alike and an update trains on the
+inputs the policy acted on), and the statistics start from count 0 (mean 0, inv_std exactly 1.0: the first collection is the identity apart from the clamp) instead of the
+prior count = 1e-4.  normalize_latents=False writes mean 0 / inv_std 1 for the first z_dim columns (their moments are still tracked, the clamp still applies): for VAEs
+whose latents are at prior scale already, and for latent columns of near-zero variance, which would otherwise be blown up to +-clip.  The states a step RETURNS, and the
+latents in its output row, stay the raw observation.  An update that raises leaves the statistics as they were; a recorded observation that is not finite (NaN,
++-inf) is such a case -- the merge kernels refuse the whole batch, since one NaN would stay in mean / M2 for good, and update() / merge_observation_statistics() raise
+ValueError behind that launch (the SGD steps of that update have run by then; the statistics are as they were); reset() does not touch them; RolloutStep, the
+single-frame entry, has no normalised form (ValueError: use BatchedRolloutStep(num_envs=1)).  `stage_times` gains "observation_stats".  With the setting off none of
+these keys appears, no table is allocated and every call makes the launches it always made.
+
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import os
@@ -186,6 +216,7 @@ class _StepBase:
             raise ValueError(who + ": io must be 'pinned' or 'device'")
         self.frame_bytes = int(np.prod(vdev.source_shape))
         self._rng = np.random.Generator(np.random.Philox(int(seed if seed is not None else (ppo.seed or 0)) + 0xAC7))
+        self._obs_norm = None                                                        # running observation normalisation (set_observation_normalization): None = off
         return vdev, pdev
 
     def _io_buffers(self, in_bytes, out_floats):
@@ -206,6 +237,11 @@ class RolloutStep(_StepBase):
         self._io_buffers(self._noise_off + 4 * (self.n_meas + self.A), self.A + 1 + self.z_dim)
         self._f_np = self._in_np[self._noise_off:].view(np.float32)
         self._out_np = self.h_out.numpy()
+
+    def set_observation_normalization(self, state_dict):
+        """The single-frame entry has no normalised form: ValueError for anything but None."""
+        if state_dict is not None:
+            raise ValueError("RolloutStep: observation normalisation exists in the batched step only: use BatchedRolloutStep(vae, ppo, num_envs=1)")
 
     def __call__(self, frame_u8, measurements, greedy=False, noise=None):
         """frame_u8: uint8 [H, W, 3] camera frame; measurements: the k values appended to the latent.  Returns (action [A], value, state [z + k])."""
@@ -265,6 +301,21 @@ class BatchedRolloutStep(_StepBase):
     def __call__(self, frames_u8, measurements, greedy=False, noise=None):
         return self.record(*self.check(frames_u8, measurements, greedy, noise), greedy)
 
+    def set_observation_normalization(self, state_dict):
+        """The FROZEN evaluation step: a checkpointed observation_normalization_state() of a buffer (None: off) is applied by every call from now on
+        (mi_rollout_step_batch_norm with table_rows = NULL) and never updated.  The whole dict is checked before anything changes (ValueError).  The states a call
+        returns stay the raw observation."""
+        if state_dict is None:
+            self._obs_norm = None
+            return
+        d = observation_normalization_state_checked(state_dict, self.z_dim + self.n_meas, self._who + ".set_observation_normalization")
+        if d["z_dim"] != self.z_dim:
+            raise ValueError("%s.set_observation_normalization: the state was taken with z_dim = %d, this step has %d" % (self._who, d["z_dim"], self.z_dim))
+        on = _obs_norm_tensors(self.device, self.z_dim + self.n_meas, self.num_envs)
+        on.update({k: d[k] for k in ("clip", "epsilon", "frozen", "normalize_latents")})
+        _obs_norm_load(self.L, on, d, self.z_dim)
+        self._obs_norm = on
+
     def check(self, frames_u8, measurements, greedy, noise):
         """The host-side checks of a call -> (frames, n, measurements float64 [n, k], noise float32 [n, A] or None)."""
         f = np.asarray(frames_u8)
@@ -283,9 +334,10 @@ class BatchedRolloutStep(_StepBase):
                 raise ValueError("%s: expected noise [%d, %d]" % (self._who, n, self.A))
         return f, n, meas, nz
 
-    def record(self, f, n, meas, nz, greedy, table_rows=None, states=None, actions=None, values=None):
+    def record(self, f, n, meas, nz, greedy, table_rows=None, states=None, actions=None, values=None, raw_states=None):
         """One device call on checked inputs.  table_rows None: mi_rollout_step_batch; else the int32 table rows go behind the noise and mi_rollout_step_batch_rec also
-        leaves state / action / value of row i in row table_rows[i] of the device tables `states`, `actions`, `values`."""
+        leaves state / action / value of row i in row table_rows[i] of the device tables `states`, `actions`, `values`.  With observation normalisation on
+        (set_observation_normalization) either becomes mi_rollout_step_batch_norm: `states` then takes the normalised rows and `raw_states` the raw ones."""
         import torch
         nm, na = n * self.n_meas, n * self.A
         nr = 0 if table_rows is None else n
@@ -303,7 +355,15 @@ class BatchedRolloutStep(_StepBase):
         fptr = base + self._f_off
         args = (self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, None if greedy else fptr + 4 * nm, 1 if greedy else 0, n,
                 self.scratch.data_ptr(), self.scratch_bytes, (self.h_out if self.d_out is None else self.d_out).data_ptr())
-        if table_rows is None:
+        on = self._obs_norm
+        if on is not None:
+            norm = (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr())
+            if table_rows is None:
+                self.L.mi_rollout_step_batch_norm(*args, *norm, None, 0, None, None, None, None)
+            else:
+                self.L.mi_rollout_step_batch_norm(*args, *norm, fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), raw_states.data_ptr(), actions.data_ptr(),
+                                                  values.data_ptr())
+        elif table_rows is None:
             self.L.mi_rollout_step_batch(*args)
         else:
             self.L.mi_rollout_step_batch_rec(*args, fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), actions.data_ptr(), values.data_ptr())
@@ -314,8 +374,8 @@ class BatchedRolloutStep(_StepBase):
         return o[:, :self.A].copy(), o[:, self.A].copy(), np.concatenate([o[:, self.A + 1:].astype(np.float64), meas], axis=1)
 
     def record_value(self, f, n, meas, table_rows, final_values):
-        """The value-only device call on checked inputs (mi_rollout_value_batch_rec: the encoder chain, the value trunk and the value head; no action, no latent comes
-        back): the int32 table rows go behind the measurements and the value of row i is also left in final_values[table_rows[i]].  -> float32 [n]."""
+        """The value-only device call on checked inputs (mi_rollout_value_batch_rec; with observation normalisation on, mi_rollout_value_batch_norm: the encoder chain,
+        the value trunk and the value head; no action, no latent comes back): the int32 table rows go behind the measurements and the value of row i is also left in final_values[table_rows[i]].  -> float32 [n]."""
         import torch
         nm = n * self.n_meas
         self._in_np[:n * self.frame_bytes] = f.reshape(-1)
@@ -327,8 +387,14 @@ class BatchedRolloutStep(_StepBase):
             self.d_in[:used].copy_(self.h_in[:used], non_blocking=True)
         base = (self.h_in if self.d_in is None else self.d_in).data_ptr()
         fptr = base + self._f_off
-        self.L.mi_rollout_value_batch_rec(self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, n, self.scratch.data_ptr(), self.scratch_bytes,
-                                          (self.h_out if self.d_out is None else self.d_out).data_ptr(), fptr + 4 * nm, int(final_values.shape[0]), final_values.data_ptr())
+        args = (self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, n, self.scratch.data_ptr(), self.scratch_bytes,
+                (self.h_out if self.d_out is None else self.d_out).data_ptr())
+        rec = (fptr + 4 * nm, int(final_values.shape[0]), final_values.data_ptr())
+        on = self._obs_norm
+        if on is not None:
+            self.L.mi_rollout_value_batch_norm(*args, on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr(), *rec)
+        else:
+            self.L.mi_rollout_value_batch_rec(*args, *rec)
         if self.d_out is not None:
             self.h_out[:n].copy_(self.d_out[:n], non_blocking=True)
         st.synchronize()
@@ -581,6 +647,91 @@ def minibatch_normalization_ddof(ddof=0, who="RolloutBuffer.set_minibatch_normal
     return int(ddof)
 
 
+def observation_normalization_settings(clip=10.0, epsilon=1e-8, frozen=False, normalize_latents=True, who="RolloutBuffer.set_observation_normalization"):
+    """The checked settings of running observation normalisation (mi_rollout_step_batch_norm / mi_rollout_obs_stats) -> {"clip": float, "epsilon": float, "frozen":
+    bool, "normalize_latents": bool}.  clip: a positive float (inf: never clamp); epsilon: a finite float >= 0; frozen, normalize_latents: bools.  Anything else raises
+    ValueError.  numpy only: no device and no library involved."""
+    out = reward_scaling_settings(clip, epsilon, frozen, who)
+    if not isinstance(normalize_latents, (bool, np.bool_)):
+        raise ValueError("%s: normalize_latents is a bool, got %r" % (who, normalize_latents))
+    out["normalize_latents"] = bool(normalize_latents)
+    return out
+
+
+def observation_normalization_state_checked(d, din, who="RolloutBuffer.load_observation_normalization_state"):
+    """The checked dict of observation_normalization_state() for observations of din columns -> {"count": float, "mean", "m2": float64 [din], "z_dim": int, and the
+    settings}.  count is finite and >= 0, every mean finite, every m2 finite and >= 0, 0 <= z_dim <= din.  ValueError otherwise.  numpy only."""
+    keys = ("count", "mean", "m2", "z_dim", "clip", "epsilon", "frozen", "normalize_latents")
+    if not isinstance(d, dict) or any(k not in d for k in keys):
+        raise ValueError("%s: expected a dict with the keys %s" % (who, ", ".join(keys)))
+    out = observation_normalization_settings(d["clip"], d["epsilon"], d["frozen"], d["normalize_latents"], who)
+    if not _real(d["count"]) or not np.isfinite(d["count"]) or d["count"] < 0:
+        raise ValueError("%s: count is a finite float >= 0, got %r" % (who, d["count"]))
+    out["count"] = float(d["count"])
+    z_dim = d["z_dim"]
+    if isinstance(z_dim, (bool, np.bool_)) or not isinstance(z_dim, (int, np.integer)) or not 0 <= int(z_dim) <= int(din):
+        raise ValueError("%s: z_dim is an int in [0, %d], got %r" % (who, din, z_dim))
+    out["z_dim"] = int(z_dim)
+    for k in ("mean", "m2"):
+        v = np.asarray(d[k])
+        if v.dtype.kind not in "fiu" or v.shape != (int(din),):
+            raise ValueError("%s: %s must hold one number per observation column, shape (%d,), got %s %s" % (who, k, din, v.dtype, v.shape))
+        v = v.astype(np.float64)
+        if not np.isfinite(v).all() or (k == "m2" and (v < 0).any()):
+            raise ValueError("%s: %s holds a value that is not finite%s" % (who, k, " or is negative" if k == "m2" else ""))
+        out[k] = v
+    return out
+
+
+def observation_normalization_fp32(d):
+    """What the device derives from a checked state: (mean32, inv32), float32 [din] -- float32(mean) and float32(1 / sqrt(M2 / count + epsilon)) (count 0: the variance
+    is 1.0), and 0 / 1 for the first z_dim columns with normalize_latents False."""
+    var = d["m2"] / d["count"] if d["count"] > 0 else np.ones_like(d["m2"])
+    mean32, inv32 = d["mean"].astype(np.float32), (1.0 / np.sqrt(var + np.float64(d["epsilon"]))).astype(np.float32)
+    if not d["normalize_latents"]:
+        mean32[:d["z_dim"]], inv32[:d["z_dim"]] = 0.0, 1.0
+    return mean32, inv32
+
+
+def normalize_observations(states, state_dict):
+    """The formula of the normalise kernel in numpy float32, for states [..., din] and an observation_normalization_state() dict: clamp((s - mean32) * inv32, -clip,
+    +clip) with one subtract and one multiply.  What a policy trained behind set_observation_normalization() must be fed by a caller that runs PPO.predict() on host
+    states; also the reference of the tests.  -> float32, the shape of `states`."""
+    s = np.asarray(states, np.float32)
+    d = observation_normalization_state_checked(state_dict, s.shape[-1] if s.ndim else 0, "normalize_observations")
+    mean32, inv32 = observation_normalization_fp32(d)
+    clip = np.float32(d["clip"])
+    return np.minimum(np.maximum((s - mean32) * inv32, -clip), clip)
+
+
+def _obs_norm_tensors(device, din, num_envs):
+    """The device side of the setting, fresh: state fp64 {count, mean[din], M2[din]}, the fp32 pair the step reads, the step's n x din buffer, the batch figures."""
+    import torch
+    return {"state": torch.zeros(1 + 2 * din, dtype=torch.float64, device=device), "mean32": torch.zeros(din, device=device), "inv32": torch.ones(din, device=device),
+            "nstate": torch.empty(num_envs, din, device=device), "batch": torch.zeros(3, din, dtype=torch.float64, device=device)}
+
+
+def _obs_norm_derive(L, on, z_dim):
+    """mean32 / inv32 from the statistics as they are (mi_rollout_obs_stats with an empty list: one launch)."""
+    import torch
+    din = int(on["mean32"].shape[0])
+    L.mi_rollout_obs_stats(torch.cuda.current_stream(on["state"].device).cuda_stream, None, 0, None, 0, din, 0 if on["normalize_latents"] else z_dim, 0, on["epsilon"],
+                           on["clip"], on["state"].data_ptr(), on["mean32"].data_ptr(), on["inv32"].data_ptr(), None, on["batch"].data_ptr())
+
+
+def _obs_norm_load(L, on, d, z_dim):
+    import torch
+    on["state"].copy_(torch.from_numpy(np.concatenate([[d["count"]], d["mean"], d["m2"]])))
+    _obs_norm_derive(L, on, z_dim)
+
+
+def _obs_norm_rms(on):
+    state = on["state"].cpu().numpy()
+    din = (state.shape[0] - 1) // 2
+    count = float(state[0])
+    return {"count": count, "mean": state[1:1 + din].copy(), "var": state[1 + din:] / count if count > 0 else np.ones(din)}
+
+
 def _diagnostics(who, target_kl):
     """The checked arguments of update_with_diagnostics (raises before any device work): target_kl is None or a positive finite float."""
     if target_kl is not None:
@@ -618,6 +769,94 @@ class RolloutBuffer:
         self._reward_scaling = None                                                  # running-return reward scaling (set_reward_scaling): None = off
         self._minibatch_norm = None                                                  # per-minibatch advantage normalisation (set_minibatch_normalization): None = off
         self._minibatch_advantages = None                                            # its fp32 table, allocated by the first update that needs it
+        self._obs_norm = None                                                        # running observation normalisation (set_observation_normalization): None = off
+        self.raw_states = None                                                       # its fp32 table of the raw rows, allocated when the setting is turned on
+
+    def set_observation_normalization(self, clip=10.0, epsilon=1e-8, frozen=False, normalize_latents=True):
+        """Turns running observation normalisation on (see the module docstring): step(), bootstrap() and truncate() feed the trunks clamp((s - mean) * inv_std, +-clip)
+        per column of [z | measurements] (clip inf: never clamps), `states` records the normalised rows and `raw_states` the raw ones, and the last launch of every
+        update() merges the collection's raw rows into the running {count, mean, M2} kept on the device.  frozen=True: the statistics are used and not updated.
+        normalize_latents=False: the first z_dim columns get mean 0 / inv_std 1 (their moments are still tracked, the clamp still applies).  Turning it on allocates the
+        statistics (count 0: mean 0, inv_std 1.0) and `raw_states`; calling it again with the setting on changes the settings and keeps both.
+        set_observation_normalization(None) turns it off and drops them.  Only with no step recorded (after reset()): a collection is normalised by ONE set of statistics
+        and its tables hold one kind of row.  ValueError before anything touches a device."""
+        settings = None if clip is None else observation_normalization_settings(clip, epsilon, frozen, normalize_latents)
+        self._obs_norm_between_collections("set_observation_normalization")
+        if settings is None:
+            self._obs_norm = self.raw_states = self._step._obs_norm = None
+            return
+        _obs_norm_derive(self.L, self._obs_norm_on(settings), self._step.z_dim)
+
+    def _obs_norm_between_collections(self, what):
+        if (self.rows.lengths > 0).any() or self.rows.awaiting.any():
+            raise ValueError("%s.%s: steps are recorded; call it after reset() -- a collection is normalised by one set of statistics" % (type(self).__name__, what))
+
+    def _obs_norm_on(self, settings):
+        import torch
+        on = self._obs_norm
+        if on is None:
+            on = _obs_norm_tensors(self.device, int(self.states.shape[1]), self.num_envs)
+            self.raw_states = torch.zeros_like(self.states)
+        on.update(settings)
+        self._obs_norm = self._step._obs_norm = on
+        return on
+
+    def _need_obs_norm(self, what):
+        if self._obs_norm is None:
+            raise ValueError("%s.%s: observation normalisation is off (set_observation_normalization)" % (type(self).__name__, what))
+        return self._obs_norm
+
+    def observation_normalization_state(self):
+        """What a training script writes to its checkpoint, and what BatchedRolloutStep.set_observation_normalization() and normalize_observations() take:
+        {"count": float, "mean", "m2": float64 [input_dim], "z_dim", "clip", "epsilon", "frozen", "normalize_latents"}."""
+        on = self._need_obs_norm("observation_normalization_state")
+        state = on["state"].cpu().numpy()
+        din = int(self.states.shape[1])
+        return {"count": float(state[0]), "mean": state[1:1 + din].copy(), "m2": state[1 + din:].copy(), "z_dim": self._step.z_dim, "clip": on["clip"],
+                "epsilon": on["epsilon"], "frozen": on["frozen"], "normalize_latents": on["normalize_latents"]}
+
+    def load_observation_normalization_state(self, d):
+        """Takes observation_normalization_state()'s dict back: the setting is on afterwards, with these statistics and settings.  The whole dict is checked before
+        anything changes (ValueError); only with no step recorded, like set_observation_normalization()."""
+        d = observation_normalization_state_checked(d, int(self.states.shape[1]))
+        if d["z_dim"] != self._step.z_dim:
+            raise ValueError("%s.load_observation_normalization_state: the state was taken with z_dim = %d, this buffer has %d" % (type(self).__name__, d["z_dim"], self._step.z_dim))
+        self._obs_norm_between_collections("load_observation_normalization_state")
+        on = self._obs_norm_on({k: d[k] for k in ("clip", "epsilon", "frozen", "normalize_latents")})
+        _obs_norm_load(self.L, on, d, self._step.z_dim)
+
+    def merge_observation_statistics(self):
+        """Merges the raw rows of the steps recorded so far (rows.valid_rows()) into the statistics NOW, without an update, and re-derives what the step reads: for a
+        warm-up collection, followed by reset() -- without one the first collection runs on mean 0 / inv_std 1 and clamps a raw speed of 30 to `clip`.  The rows stay
+        recorded: an update() of the same collection would merge them a second time.  ValueError with the setting off or frozen, with no step recorded, or (behind
+        the launch, the statistics as they were) with a recorded observation that is not finite.
+        -> update()'s `observation_rms`."""
+        on = self._need_obs_norm("merge_observation_statistics")
+        if on["frozen"]:
+            raise ValueError("%s.merge_observation_statistics: the statistics are frozen" % type(self).__name__)
+        valid = self.rows.valid_rows()
+        if valid.shape[0] < 1:
+            raise ValueError("%s.merge_observation_statistics: no step is recorded" % type(self).__name__)
+        self._obs_norm_stats(valid, 1, "merge_observation_statistics")
+        return _obs_norm_rms(on)
+
+    def _obs_norm_stats(self, valid, merge, what):
+        """One mi_rollout_obs_stats call over the table rows `valid` (host int32) -> its batch figures, float64 [3, din] on the host (batch mean, batch M2, clamped
+        counts).  The device refuses to merge a batch with an entry that is not finite (one NaN would stay in mean / M2 for good, and every later step would feed the
+        trunks NaN): the statistics are then as they were and this raises ValueError."""
+        import torch
+        on = self._obs_norm
+        n, din = int(valid.shape[0]), int(self.states.shape[1])
+        rows = torch.from_numpy(np.ascontiguousarray(valid, np.int32)).to(self.device)
+        scratch = torch.empty(int(self.L.mi_rollout_obs_stats_scratch_doubles(n, din)), dtype=torch.float64, device=self.device)
+        self.L.mi_rollout_obs_stats(torch.cuda.current_stream(self.device).cuda_stream, self.raw_states.data_ptr(), self.n_table_rows, rows.data_ptr(), n, din,
+                                    0 if on["normalize_latents"] else self._step.z_dim, merge, on["epsilon"], on["clip"], on["state"].data_ptr(), on["mean32"].data_ptr(),
+                                    on["inv32"].data_ptr(), scratch.data_ptr(), on["batch"].data_ptr())
+        batch = on["batch"].cpu().numpy()
+        if merge and not np.isfinite(batch[0]).all():
+            raise ValueError("%s.%s: a recorded observation is not finite (column %d of raw_states); it would poison the statistics of observation normalisation for "
+                             "good, so nothing was merged and they are as they were" % (type(self).__name__, what, int(np.flatnonzero(~np.isfinite(batch[0]))[0])))
+        return batch
 
     def set_reward_scaling(self, clip=10.0, epsilon=1e-8, frozen=False):
         """Turns running-return reward scaling on (see the module docstring): every update divides its rewards by sqrt(var + epsilon) of the discounted returns seen so
@@ -694,7 +933,7 @@ class RolloutBuffer:
         """BatchedRolloutStep.__call__ of these frames, and row i of the call is recorded at slot lengths[env_ids[i]] of environment env_ids[i] (None: 0 .. n-1)."""
         f, n, meas, nz = self._step.check(frames_u8, measurements, greedy, noise)
         rows = self.rows.step_rows(env_ids, n)
-        return self._step.record(f, n, meas, nz, greedy, rows, self.states, self.actions, self.values)
+        return self._step.record(f, n, meas, nz, greedy, rows, self.states, self.actions, self.values, self.raw_states)
 
     def outcome(self, rewards, dones, env_ids=None):
         """Reward and done of the step just recorded for these environments (the simulator's answer to the action); the row's length grows by one."""
@@ -707,7 +946,7 @@ class RolloutBuffer:
             env_ids = self.rows.stepped()
         f, n, meas, _ = self._step.check(frames_u8, measurements, True, None)
         rows = self.rows.bootstrap_rows(env_ids, n)
-        return self._step.record(f, n, meas, None, True, rows, self.states, self.actions, self.values)
+        return self._step.record(f, n, meas, None, True, rows, self.states, self.actions, self.values, self.raw_states)
 
     def update(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, stage_times=None):
         """One PPO update from the tables (train.py:175-207 over the recorded rows): mi_rollout_finish, update_old_policy, log pi_old once, num_epochs x shuffled
@@ -721,7 +960,10 @@ class RolloutBuffer:
         mi_ppo_minibatch_advantages call runs in front of every epoch's first step over that epoch's shuffled rows, and the steps gather their advantage from the table
         it writes: `advantages` is still the finish call's output, but the SGD steps did NOT read it.  The result gains `minibatch_adv_stats`, float64 [number of SGD
         steps, 3] = every step's {count, mean, std} in step order, and `minibatch_advantages`, float32 [num_envs, T]: what the steps of the last epoch that ran read
-        (NaN beyond a row's length, all NaN for num_epochs = 0); `stage_times` gains "minibatch_norm", which is also part of "sgd"."""
+        (NaN beyond a row's length, all NaN for num_epochs = 0); `stage_times` gains "minibatch_norm", which is also part of "sgd".  With observation normalisation on
+        (set_observation_normalization) the last launch is mi_rollout_obs_stats over `raw_states` at rows.valid_rows() (merging unless frozen), and the result gains
+        `observation_rms` = {"count", "mean" [input_dim], "var" [input_dim]} and `observation_clip_fraction`, float64 [input_dim]; `stage_times` gains
+        "observation_stats".  A recorded observation that is not finite is not merged: ValueError behind that last launch, the statistics as they were."""
         return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, None)
 
     def update_with_diagnostics(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, stage_times=None, target_kl=None):
@@ -913,6 +1155,15 @@ class RolloutBuffer:
             out["discounted_returns"], out["scaled_rewards"] = scaled[0], scaled[1]
             out["reward_clip_fraction"] = float((np.abs(scaled[1][recorded]) == rs["clip"]).mean())
             out["return_carry"] = rs["carry"].cpu().numpy()
+        on = getattr(self, "_obs_norm", None)                                        # running observation normalisation (set_observation_normalization): None = off
+        if on is not None:                                                           # the update's last launch: nothing above can raise behind it
+            if stage_times is not None:
+                torch.cuda.synchronize(device)
+            t_on = time.perf_counter()
+            batch = self._obs_norm_stats(valid, 0 if on["frozen"] else 1, "update")
+            mark("observation_stats", t_on)
+            out["observation_rms"] = _obs_norm_rms(on)
+            out["observation_clip_fraction"] = batch[2] / n_valid
         return out
 
 
@@ -941,7 +1192,7 @@ class ContinuousRolloutBuffer(RolloutBuffer):
     def truncate(self, final_frames_u8, final_measurements, env_ids=None):
         """The episodes of these environments (None: 0 .. n-1) stopped at their last counted step WITHOUT being terminal, and their lanes go on with a reset observation:
         call it after outcome() (done False) and before these lanes' next step, with the final observation of the stopped episodes.  One value-only device call
-        (mi_rollout_value_batch_rec) leaves V(final observation) in final_values at the row of that step; update() bootstraps the segment from it.  -> float32 [n]."""
+        (mi_rollout_value_batch_rec; with observation normalisation on, mi_rollout_value_batch_norm) leaves V(final observation) in final_values at the row of that step; update() bootstraps the segment from it.  -> float32 [n]."""
         f, n, meas, _ = self._step.check(final_frames_u8, final_measurements, True, None)
         rows = self.rows.truncate_rows(env_ids, n)
         return self._step.record_value(f, n, meas, rows, self.final_values)

@@ -449,6 +449,41 @@ int mi_rollout_finish_segments_boot(void* stream, const float* tab_values, const
  * or <= 0 (+inf is valid: never clamp); merge outside {0, 1}. */
 long long mi_rollout_scale_rewards_scratch_doubles(int num_envs);
 int mi_rollout_scale_rewards(void* stream, const double* rewards, const double* terminals, const unsigned char* truncs, const int* len, int num_envs, int T, double gamma, double epsilon, double clip, int merge, double* state, double* carry, double* scratch, double* g_out, double* rewards_out);
+/* running OBSERVATION normalisation, the other half of baselines' VecNormalize (obs_rms; clip(obs - mean) / sqrt(var + epsilon)), no reference counterpart in train.py:
+ * the batched step of vae_common.py:45-61 + ppo.py:231-251 with the state [z | measurements] standardised per column in front of trunk layer 1.
+ * mi_rollout_step_batch_norm: the arguments and checks of mi_rollout_step_batch, and obs_mean / obs_inv_std: fp32 [din] on the device (din = z_dim + n_meas), obs_clip > 0
+ * (+inf is valid: never clamp), nstate: fp32 [n][din], HBM, 16-byte aligned, the caller's (mi_rollout_batch_workspace_bytes does not grow).  One more launch than
+ * mi_rollout_step_batch, between the mean layer and trunk layer 1: with s = the raw state entry (mean_raw + mean_bias for a latent column, the measurement as fed for the others)
+ *   nstate[e][j] = min(max((s - obs_mean[j]) * obs_inv_std[j], -obs_clip), obs_clip)      (fp32: one subtract, one multiply)
+ * and trunk layer 1 reads nstate.  Nothing changes obs_mean / obs_inv_std during the call: every row is normalised alike.  `out` is what mi_rollout_step_batch returns: its
+ * latents are the RAW z.  table_rows != NULL: the recording step; call row e is stored as row r = table_rows[e] (inside [0, n_table_rows), else skipped) of tab_states[r] = the
+ * NORMALISED row (plain vector stores), tab_raw_states[r] = [z | measurements[e]] (the bits mi_rollout_step_batch_rec stores), tab_actions[r], tab_values[r].  table_rows ==
+ * NULL records nothing (the evaluation step; the four tables are not read).
+ * mi_rollout_value_batch_norm: mi_rollout_value_batch_rec (train.py:172's bootstrap value of a truncated episode) with the same normalise launch in front of the value trunk;
+ * no table of states is written.  Errors of both (MI_ERR_ARG, before any launch): those of the entries they extend; obs_mean / obs_inv_std / nstate NULL; nstate not 16-byte
+ * aligned; obs_clip <= 0 or NaN; table_rows without all four tables. */
+int mi_rollout_step_batch_norm(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n, void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate, const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values);
+int mi_rollout_value_batch_norm(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n, void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate, const int* table_rows, long long n_table_rows, float* tab_final_values);
+/* the moments pass behind it — VecNormalize's obs_rms.update at the granularity of a collection, no reference counterpart in train.py.  No engine handle.  The rows
+ * row_idx[i], i < n (int32, device; a row outside [0, n_table_rows) is skipped and does not count) of tab_raw_states (fp32 [n_table_rows][din]) are merged into
+ * state: double [1 + 2 din] = {count, mean[din], M2[din]}, per column j, fp64 throughout:
+ *   n_b = rows inside the table,  m_b = sum of x / n_b,  M2_b = sum of (x - m_b)^2      (two passes over the rows; ordered sums: per-block partials over consecutive list
+ *                                                                                       entries, added in block order; the partition is a function of n alone; no
+ *                                                                                       floating-point atomics: two calls are bitwise equal)
+ *   merge = 1 (Chan / Welford):  delta = m_b - mean;  n' = count + n_b;  mean += delta * n_b / n';  M2 += M2_b + delta^2 * count * n_b / n';  count = n'
+ *   merge = 0 (frozen statistics) and an empty batch (n_b = 0) leave state bitwise as it was.
+ *   A batch with an entry that is not finite (NaN, +-inf: then some m_b is not finite) is NOT merged, in any column: state stays bitwise as it was, the fp32 pair is
+ *   derived from it, and batch_out holds the m_b that show it -- one such entry would otherwise make mean / M2 NaN for good.
+ *   var = count > 0 ? M2 / count : 1.0;  obs_mean[j] = float32(mean);  obs_inv_std[j] = float32(1 / sqrt(var + epsilon));  j < first_col: obs_mean[j] = 0, obs_inv_std[j] = 1
+ * (fresh statistics give mean 0 and inv_std exactly 1.0f).  batch_out: double [3][din] = m_b | M2_b | the number of the batch's entries of column j whose normalised value
+ * under obs_mean / obs_inv_std AS THEY WERE ON ENTRY has magnitude clip (the normalise kernel's expression).  n = 0: nothing is read but state, the fp32 pair is derived
+ * (tab_raw_states, row_idx and scratch may be NULL).  DEVIATIONS from baselines, both on purpose: the statistics move once per collection, not per step, so every row of a
+ * collection is normalised alike, and they start from count = 0, not from the prior count = 1e-4.
+ * scratch: device doubles, at least mi_rollout_obs_stats_scratch_doubles(n, din) = 3 nb din + nb + din + 1 with nb = ceil(n / max(32, ceil(n / 256))) (needs no GPU; -1 for
+ * n < 1 or din < 1).  Three small launches.  Errors (MI_ERR_ARG, checked before any launch, nothing is written): missing buffers; n < 0; din < 1 or n_table_rows < 1;
+ * first_col outside [0, din]; merge outside {0, 1}; epsilon not finite or < 0; clip NaN or <= 0 (+inf is valid). */
+long long mi_rollout_obs_stats_scratch_doubles(long long n, int din);
+int mi_rollout_obs_stats(void* stream, const float* tab_raw_states, long long n_table_rows, const int* row_idx, long long n, int din, int first_col, int merge, double epsilon, float clip, double* state, float* obs_mean, float* obs_inv_std, double* scratch, double* batch_out);
 
 /* ---- collectives of the data-parallel path (no reference counterpart: the reference is single-process) ----
  * RCCL over xGMI, one communicator per process = per GPU; librccl.so.1 is bound at mi_comm_init (a single-GPU process never loads it).

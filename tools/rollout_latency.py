@@ -1,7 +1,7 @@
 """Latency of the rollout-loop inference path at batch 1 (SURVEY 8f.3 callers: vae_common.py:45-61, train.py:142, run_eval.py:54):
 VAE.encode([frame]) (host frame -> device, conv stack, mean to host) followed by PPO.predict(state) (host -> device, two MLP trunks, action to host).
 
-    python tools/rollout_latency.py --envs [1,2,4,8,16,32,64] [--rounds 3] [--calls 200] [--batched-only | --record | --value] [--no-box]
+    python tools/rollout_latency.py --envs [1,2,4,8,16,32,64] [--rounds 3] [--calls 200] [--batched-only | --record | --value | --obs-norm] [--no-box]
 
 times, for each number of environments E, one BatchedRolloutStep call against a loop of E RolloutStep calls and against the two-call path (VAE.encode of E float
 frames + PPO.predict of E states) on the same engines: the three are interleaved in every round, the line gives the median of the rounds' medians, the spread of
@@ -9,7 +9,10 @@ those medians (min - max) and the p90 over all calls.  --batched-only runs the b
 RolloutBuffer.step (the recording step, mi_rollout_step_batch_rec: the same eight launches, the heads also store state / action / value into the device tables)
 against BatchedRolloutStep, interleaved; the buffer's outcome() / reset() book-keeping runs between the timed calls.  --value times the value-only call of
 ContinuousRolloutBuffer.truncate (mi_rollout_value_batch_rec: the encoder chain, the value trunk and the value head) against the GREEDY recording call (what a bootstrap
-is: mi_rollout_step_batch_rec) on the same frames, both without the row book-keeping and at fixed table rows, interleaved."""
+is: mi_rollout_step_batch_rec) on the same frames, both without the row book-keeping and at fixed table rows, interleaved.  --obs-norm times the recording call and
+the value-only call with running observation normalisation on (mi_rollout_step_batch_norm / mi_rollout_value_batch_norm: one more launch, rollout_obs_norm_kernel)
+against the same calls of a twin buffer with the setting off, without the row book-keeping and at fixed table rows, interleaved; behind the table it times the merge
+(mi_rollout_obs_stats alone, device events) over 1024 rows of 128 columns."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
@@ -31,6 +34,7 @@ ap.add_argument("--calls", type=int, default=200, help="timed calls per path, E 
 ap.add_argument("--batched-only", action="store_true")
 ap.add_argument("--record", action="store_true", help="RolloutBuffer.step against BatchedRolloutStep")
 ap.add_argument("--value", action="store_true", help="the value-only call (mi_rollout_value_batch_rec) against the greedy recording call")
+ap.add_argument("--obs-norm", action="store_true", help="the recording and value-only calls with observation normalisation on against the setting off; the merge at 1024 x 128")
 ap.add_argument("--no-box", action="store_true")
 args = ap.parse_args()
 rng = np.random.RandomState(0)
@@ -96,6 +100,20 @@ def envs_table():
                 f, n, meas, _ = cbuf._step.check(u8[sl(i)], ms[sl(i)], True, None)
                 cbuf._step.record_value(f, n, meas, slot0, cbuf.final_values)
             paths, after = [("greedy recording", greedy_recording), ("value-only", value_only)], {}
+        if args.obs_norm:
+            from rollout import ContinuousRolloutBuffer
+            off, on = (ContinuousRolloutBuffer(vae, agent, E, horizon=64, io=many.io) for _ in range(2))
+            on.set_observation_normalization()
+            slot0 = (np.arange(E) * (off.horizon + 1)).astype(np.int32)
+
+            def recording_of(b):
+                return lambda i: b._step.record(*b._step.check(u8[sl(i)], ms[sl(i)], False, None), False, slot0, b.states, b.actions, b.values, b.raw_states)
+            def value_of(b):
+                def call(i):
+                    f, n, meas, _ = b._step.check(u8[sl(i)], ms[sl(i)], True, None)
+                    b._step.record_value(f, n, meas, slot0, b.final_values)
+                return call
+            paths, after = [("recording", recording_of(off)), ("recording, obs-norm", recording_of(on)), ("value-only", value_of(off)), ("value-only, obs-norm", value_of(on))], {}
         ts = {name: [] for name, _ in paths}
         for _ in range(args.rounds):
             for name, fn in paths:
@@ -107,6 +125,8 @@ def envs_table():
             line += "  %s %.1f us (rounds %.1f - %.1f, p90 %.1f)" % (name, med[name], min(meds), max(meds), np.percentile(np.concatenate(ts[name]), 90))
         if args.record and not args.value:
             line += "  | recording - batched %+.2f us, w/o book-keeping %+.2f us" % (med["recording"] - med["batched"], med["recording w/o book-keeping"] - med["batched"])
+        elif args.obs_norm:
+            line += "  | obs-norm - off: recording %+.2f us, value-only %+.2f us" % (med["recording, obs-norm"] - med["recording"], med["value-only, obs-norm"] - med["value-only"])
         elif args.value:
             line += "  | value-only - greedy recording %+.2f us" % (med["value-only"] - med["greedy recording"])
         elif not args.batched_only:
@@ -114,8 +134,33 @@ def envs_table():
         print(line, flush=True)
 
 
+def merge_time(n=1024, din=128, calls=50):
+    """mi_rollout_obs_stats alone over n rows of din columns (every row of the table, in order): device events around each call."""
+    from mi355 import lib as milib
+    L = milib.get()
+    tab = torch.randn(n, din, device="cuda")
+    rows = torch.arange(n, dtype=torch.int32, device="cuda")
+    state = torch.zeros(1 + 2 * din, dtype=torch.float64, device="cuda")
+    m32, i32 = torch.zeros(din, device="cuda"), torch.ones(din, device="cuda")
+    scratch = torch.empty(int(L.mi_rollout_obs_stats_scratch_doubles(n, din)), dtype=torch.float64, device="cuda")
+    batch = torch.zeros(3, din, dtype=torch.float64, device="cuda")
+    st = torch.cuda.current_stream()
+    ts = []
+    for i in range(calls + 5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(st)
+        L.mi_rollout_obs_stats(st.cuda_stream, tab.data_ptr(), n, rows.data_ptr(), n, din, 0, 1, 1e-8, 10.0, state.data_ptr(), m32.data_ptr(), i32.data_ptr(), scratch.data_ptr(),
+                               batch.data_ptr())
+        b.record(st)
+        b.synchronize()
+        if i >= 5: ts.append(a.elapsed_time(b) * 1e3)
+    print("mi_rollout_obs_stats, %d x %d (three launches, device events): median %.1f us, min %.1f us, p90 %.1f us" % (n, din, np.median(ts), min(ts), np.percentile(ts, 90)), flush=True)
+
+
 if args.envs is not None:
     envs_table()
+    if args.obs_norm:
+        merge_time()
     sys.exit(0)
 frames = rng.randint(0, 256, (64, 80, 160, 3)).astype(np.float32) / 255.0
 meas = rng.rand(64, 3).astype(np.float32)
