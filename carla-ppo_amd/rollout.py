@@ -188,7 +188,10 @@ these keys appears, no table is allocated and every call makes the launches it a
 
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
+import contextlib
 import os
+import time
+import types
 
 import numpy as np
 
@@ -308,11 +311,11 @@ class BatchedRolloutStep(_StepBase):
         if state_dict is None:
             self._obs_norm = None
             return
-        d = observation_normalization_state_checked(state_dict, self.z_dim + self.n_meas, self._who + ".set_observation_normalization")
-        if d["z_dim"] != self.z_dim:
-            raise ValueError("%s.set_observation_normalization: the state was taken with z_dim = %d, this step has %d" % (self._who, d["z_dim"], self.z_dim))
+        who = self._who + ".set_observation_normalization"
+        d = observation_normalization_state_checked(state_dict, self.z_dim + self.n_meas, who)
+        settings = _obs_norm_settings_of(d, self.z_dim, who, "step")
         on = _obs_norm_tensors(self.device, self.z_dim + self.n_meas, self.num_envs)
-        on.update({k: d[k] for k in ("clip", "epsilon", "frozen", "normalize_latents")})
+        on.update(settings)
         _obs_norm_load(self.L, on, d, self.z_dim)
         self._obs_norm = on
 
@@ -443,18 +446,17 @@ class RolloutRows:
 
     def env_ids(self, env_ids, n):
         """env_ids (None = 0 .. n-1) of a call with n rows -> int64 [n], distinct, inside [0, num_envs)."""
-        if env_ids is None:                                                          # 0 .. n-1: distinct and in range once n is
-            if n < 1 or n > self.num_envs:
-                raise ValueError("RolloutBuffer: 1 <= n <= num_envs = %d, got %d" % (self.num_envs, n))
-            return self._all[:n]
-        ids = np.asarray(env_ids)
-        if ids.ndim != 1 or ids.dtype.kind not in "iu":
-            raise ValueError("RolloutBuffer: env_ids must be a vector of integers")
-        ids = ids.astype(np.int64)
-        if ids.shape[0] != n:
-            raise ValueError("RolloutBuffer: %d env_ids for %d rows" % (ids.shape[0], n))
+        if env_ids is not None:
+            ids = np.asarray(env_ids)
+            if ids.ndim != 1 or ids.dtype.kind not in "iu":
+                raise ValueError("RolloutBuffer: env_ids must be a vector of integers")
+            ids = ids.astype(np.int64)
+            if ids.shape[0] != n:
+                raise ValueError("RolloutBuffer: %d env_ids for %d rows" % (ids.shape[0], n))
         if n < 1 or n > self.num_envs:
             raise ValueError("RolloutBuffer: 1 <= n <= num_envs = %d, got %d" % (self.num_envs, n))
+        if env_ids is None:                                                          # 0 .. n-1: distinct and in range once n is
+            return self._all[:n]
         if ids.min() < 0 or ids.max() >= self.num_envs:
             raise ValueError("RolloutBuffer: env_ids outside [0, %d)" % self.num_envs)
         if np.unique(ids).shape[0] != n:
@@ -606,6 +608,24 @@ def _real(x):
     return not isinstance(x, (bool, str)) and isinstance(x, (int, float, np.integer, np.floating))
 
 
+def _finite_scalar(who, k, x, nonneg):
+    """A checkpointed state's scalar `k` -> float: finite, and >= 0 with `nonneg`."""
+    if not _real(x) or not np.isfinite(x) or (nonneg and x < 0):
+        raise ValueError("%s: %s is a finite float%s, got %r" % (who, k, " >= 0" if nonneg else "", x))
+    return float(x)
+
+
+def _finite_vector(who, k, x, n, per, nonneg):
+    """A checkpointed state's vector `k` -> float64 [n]: one finite number per `per`, and >= 0 with `nonneg`."""
+    v = np.asarray(x)
+    if v.dtype.kind not in "fiu" or v.shape != (int(n),):
+        raise ValueError("%s: %s must hold one number per %s, shape (%d,), got %s %s" % (who, k, per, n, v.dtype, v.shape))
+    v = v.astype(np.float64)
+    if not np.isfinite(v).all() or (nonneg and (v < 0).any()):
+        raise ValueError("%s: %s holds a value that is not finite%s" % (who, k, " or is negative" if nonneg else ""))
+    return v
+
+
 def reward_scaling_settings(clip=10.0, epsilon=1e-8, frozen=False, who="RolloutBuffer.set_reward_scaling"):
     """The checked settings of running-return reward scaling (mi_rollout_scale_rewards) -> {"clip": float, "epsilon": float, "frozen": bool}.  clip: a positive float
     (inf: never clamp); epsilon: a finite float >= 0; frozen: a bool.  Anything else raises ValueError.  numpy only: no device and no library involved."""
@@ -626,16 +646,8 @@ def reward_scaling_state_checked(d, num_envs, who="RolloutBuffer.load_reward_sca
         raise ValueError("%s: expected a dict with the keys %s" % (who, ", ".join(keys)))
     out = reward_scaling_settings(d["clip"], d["epsilon"], d["frozen"], who)
     for k in ("count", "mean", "m2"):
-        if not _real(d[k]) or not np.isfinite(d[k]) or (k != "mean" and d[k] < 0):
-            raise ValueError("%s: %s is a finite float%s, got %r" % (who, k, "" if k == "mean" else " >= 0", d[k]))
-        out[k] = float(d[k])
-    carry = np.asarray(d["carry"])
-    if carry.dtype.kind not in "fiu" or carry.shape != (int(num_envs),):
-        raise ValueError("%s: carry must hold one number per environment, shape (%d,), got %s %s" % (who, num_envs, carry.dtype, carry.shape))
-    carry = carry.astype(np.float64)
-    if not np.isfinite(carry).all():
-        raise ValueError("%s: carry holds a value that is not finite" % who)
-    out["carry"] = carry
+        out[k] = _finite_scalar(who, k, d[k], k != "mean")
+    out["carry"] = _finite_vector(who, "carry", d["carry"], num_envs, "environment", False)
     return out
 
 
@@ -665,22 +677,21 @@ def observation_normalization_state_checked(d, din, who="RolloutBuffer.load_obse
     if not isinstance(d, dict) or any(k not in d for k in keys):
         raise ValueError("%s: expected a dict with the keys %s" % (who, ", ".join(keys)))
     out = observation_normalization_settings(d["clip"], d["epsilon"], d["frozen"], d["normalize_latents"], who)
-    if not _real(d["count"]) or not np.isfinite(d["count"]) or d["count"] < 0:
-        raise ValueError("%s: count is a finite float >= 0, got %r" % (who, d["count"]))
-    out["count"] = float(d["count"])
+    out["count"] = _finite_scalar(who, "count", d["count"], True)
     z_dim = d["z_dim"]
     if isinstance(z_dim, (bool, np.bool_)) or not isinstance(z_dim, (int, np.integer)) or not 0 <= int(z_dim) <= int(din):
         raise ValueError("%s: z_dim is an int in [0, %d], got %r" % (who, din, z_dim))
     out["z_dim"] = int(z_dim)
     for k in ("mean", "m2"):
-        v = np.asarray(d[k])
-        if v.dtype.kind not in "fiu" or v.shape != (int(din),):
-            raise ValueError("%s: %s must hold one number per observation column, shape (%d,), got %s %s" % (who, k, din, v.dtype, v.shape))
-        v = v.astype(np.float64)
-        if not np.isfinite(v).all() or (k == "m2" and (v < 0).any()):
-            raise ValueError("%s: %s holds a value that is not finite%s" % (who, k, " or is negative" if k == "m2" else ""))
-        out[k] = v
+        out[k] = _finite_vector(who, k, d[k], din, "observation column", k == "m2")
     return out
+
+
+def _obs_norm_settings_of(d, z_dim, who, what):
+    """The settings in a checked observation_normalization_state() dict, for a step or a buffer (`what`) whose latents have z_dim columns: ValueError on another z_dim."""
+    if d["z_dim"] != z_dim:
+        raise ValueError("%s: the state was taken with z_dim = %d, this %s has %d" % (who, d["z_dim"], what, z_dim))
+    return {k: d[k] for k in ("clip", "epsilon", "frozen", "normalize_latents")}
 
 
 def observation_normalization_fp32(d):
@@ -735,10 +746,38 @@ def _obs_norm_rms(on):
 def _diagnostics(who, target_kl):
     """The checked arguments of update_with_diagnostics (raises before any device work): target_kl is None or a positive finite float."""
     if target_kl is not None:
-        if isinstance(target_kl, (bool, str)) or not isinstance(target_kl, (int, float, np.integer, np.floating)) or not np.isfinite(target_kl) or not target_kl > 0:
+        if not _real(target_kl) or not np.isfinite(target_kl) or not target_kl > 0:
             raise ValueError("%s.update_with_diagnostics: target_kl is None or a positive finite float, got %r" % (who, target_kl))
         target_kl = float(target_kl)
     return {"target_kl": target_kl}
+
+
+class _StageClock:
+    """The `stage_times` of an update: lap(name) closes the stage the update's chain is in and opens the next, `with stage(name)` times a stage of its own or one inside a
+    chain stage; a stage ends, and one under `with` also starts, once the device is idle.  With times = None nothing is recorded and the device is never waited for."""
+
+    def __init__(self, times, device):
+        self.times, self.device, self.t = times, device, time.perf_counter()
+
+    def _now(self):
+        if self.times is not None:
+            import torch
+            torch.cuda.synchronize(self.device)
+        return time.perf_counter()
+
+    def _add(self, name, t0):
+        if self.times is not None:
+            self.times[name] = self.times.get(name, 0.0) + self._now() - t0
+
+    def lap(self, name):
+        self._add(name, self.t)
+        self.t = time.perf_counter()
+
+    @contextlib.contextmanager
+    def stage(self, name):
+        t0 = self._now()
+        yield
+        self._add(name, t0)
 
 
 class _RecordingStep(BatchedRolloutStep):
@@ -769,6 +808,7 @@ class RolloutBuffer:
         self._reward_scaling = None                                                  # running-return reward scaling (set_reward_scaling): None = off
         self._minibatch_norm = None                                                  # per-minibatch advantage normalisation (set_minibatch_normalization): None = off
         self._minibatch_advantages = None                                            # its fp32 table, allocated by the first update that needs it
+        self._values_new = None                                                      # V per table row under the current parameters, allocated by the first statistics pass with value clipping on
         self._obs_norm = None                                                        # running observation normalisation (set_observation_normalization): None = off
         self.raw_states = None                                                       # its fp32 table of the raw rows, allocated when the setting is turned on
 
@@ -819,10 +859,9 @@ class RolloutBuffer:
         """Takes observation_normalization_state()'s dict back: the setting is on afterwards, with these statistics and settings.  The whole dict is checked before
         anything changes (ValueError); only with no step recorded, like set_observation_normalization()."""
         d = observation_normalization_state_checked(d, int(self.states.shape[1]))
-        if d["z_dim"] != self._step.z_dim:
-            raise ValueError("%s.load_observation_normalization_state: the state was taken with z_dim = %d, this buffer has %d" % (type(self).__name__, d["z_dim"], self._step.z_dim))
+        settings = _obs_norm_settings_of(d, self._step.z_dim, type(self).__name__ + ".load_observation_normalization_state", "buffer")
         self._obs_norm_between_collections("load_observation_normalization_state")
-        on = self._obs_norm_on({k: d[k] for k in ("clip", "epsilon", "frozen", "normalize_latents")})
+        on = self._obs_norm_on(settings)
         _obs_norm_load(self.L, on, d, self._step.z_dim)
 
     def merge_observation_statistics(self):
@@ -995,17 +1034,50 @@ class RolloutBuffer:
 
     def _update(self, finish, num_epochs, batch_size, stage_times, diag=None, gamma=None, truncs=None):
         """What every buffer's update does around its finish call `finish(stream, rewards, dones, lengths, f64)` (device rewards / dones, fp64 [3, E, T] of NaN for the raw
-        advantages, returns and normalised advantages).  diag: None, or update_with_diagnostics' {"target_kl": None or float}.  gamma, truncs (host bool [E, T] or None):
-        what the reward scaling pass in front of the finish call takes, read only with the setting on."""
-        import time
+        advantages, returns and normalised advantages): check, upload, scale the rewards, finish, cache log pi_old, the epochs, the result, the observation statistics.
+        A stage of an optional setting runs only with that setting on.  diag: None, or update_with_diagnostics' {"target_kl": None or float}.  gamma, truncs (host bool
+        [E, T] or None): what the reward scaling pass in front of the finish call takes, read only with the setting on."""
         import torch
+        vclip = getattr(self.ppo, "value_clip", None)                                # PPO2-style value clipping (PPO.set_value_clip): None = off
+        recorded = self._check_update(num_epochs, batch_size, vclip, diag)
+        rs = self._reward_scaling                                                    # running-return reward scaling (set_reward_scaling): None = off
+        mbn = getattr(self, "_minibatch_norm", None)                                 # per-minibatch advantage normalisation (set_minibatch_normalization): None = off
+        on = getattr(self, "_obs_norm", None)                                        # running observation normalisation (set_observation_normalization): None = off
+        E, T, device = self.num_envs, self.horizon, self.device
+        valid = self.rows.valid_rows()
+        # this update: what its stages share, and what they leave for the result
+        u = types.SimpleNamespace(batch_size=int(batch_size), num_epochs=int(num_epochs), vclip=vclip, diag=diag, mbn=mbn, valid=valid, n_valid=int(valid.shape[0]),
+                                  lengths=self.rows.lengths.copy(), recorded=recorded, clock=_StageClock(stage_times, device),
+                                  st=torch.cuda.current_stream(device).cuda_stream)
+        r = torch.from_numpy(self.rows.rewards).to(device)
+        d = torch.from_numpy(self.rows.dones).to(device)
+        u.f64 = torch.full((3, E, T), float("nan"), dtype=torch.float64, device=device)    # raw advantages, returns, normalised advantages (inspection)
+        if rs is not None:
+            scaled = self._scale_rewards(u, rs, r, d, gamma, truncs)
+            r = scaled[1]                                                            # what the finish call reads
+        finish(u.st, r, d, u.lengths, u.f64)
+        u.clock.lap("finish")
+        self.ppo.update_old_policy()
+        logp_old = self._cache_logp_old(valid)
+        u.clock.lap("logp_old")
+        self._run_epochs(u, logp_old)
+        out = self._result(u)
+        if mbn is not None:
+            self._minibatch_norm_result(u, out)
+        if rs is not None:
+            self._reward_scaling_result(u, rs, scaled, out)
+        if on is not None:                                                           # the update's last launch: nothing above can raise behind it
+            self._observation_stats(u, on, out)
+        return out
+
+    def _check_update(self, num_epochs, batch_size, vclip, diag):
+        """Every refusal of an update, before anything is launched or changed -> the slots that hold a recorded step, bool [num_envs, horizon]."""
         from mi355 import dist as midist
         who = type(self).__name__
         if midist.world_size() > 1:
             raise ValueError(who + ".update: single rank only (ragged rows give ranks different numbers of gradient all-reduces)")
         if int(batch_size) < 1 or int(num_epochs) < 0:
             raise ValueError(who + ".update: batch_size >= 1, num_epochs >= 0")
-        vclip = getattr(self.ppo, "value_clip", None)                                # PPO2-style value clipping (PPO.set_value_clip): None = off
         if vclip is not None and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update: value clipping (PPO.set_value_clip) exists only in the fused kernels (this policy's shape is outside their range or "
                              "MI355_PPO_FUSED=0)")
@@ -1013,91 +1085,70 @@ class RolloutBuffer:
             raise ValueError(who + ".update_with_diagnostics: the statistics pass reads the cached log pi_old, which only the fused kernels fill "
                              "(this policy's shape is outside their range or MI355_PPO_FUSED=0)")
         self.rows.check_update()
-        rs = self._reward_scaling                                                    # running-return reward scaling (set_reward_scaling): None = off
-        if rs is not None:
-            recorded = np.arange(self.horizon)[None, :] < self.rows.lengths[:, None]
-            if not np.isfinite(self.rows.rewards[recorded]).all():
-                raise ValueError(who + ".update: a recorded reward is not finite; it would poison the statistics of reward scaling for good")
-        mbn = getattr(self, "_minibatch_norm", None)                                 # per-minibatch advantage normalisation (set_minibatch_normalization): None = off
-        batch_size = int(batch_size)
-        E, T, ppo, device = self.num_envs, self.horizon, self.ppo, self.device
-        pdev = ppo._need_dev()
-        step_kw = {} if vclip is None else {"old_values_all": self.values}           # the values recorded at collection time: the table the finish call read
-        valid = self.rows.valid_rows()
-        n_valid = int(valid.shape[0])
-        lengths = self.rows.lengths.copy()
+        recorded = np.arange(self.horizon)[None, :] < self.rows.lengths[:, None]
+        if self._reward_scaling is not None and not np.isfinite(self.rows.rewards[recorded]).all():
+            raise ValueError(who + ".update: a recorded reward is not finite; it would poison the statistics of reward scaling for good")
+        return recorded
 
-        def mark(name, t0):
-            if stage_times is not None:
-                torch.cuda.synchronize(device)
-                stage_times[name] = stage_times.get(name, 0.0) + time.perf_counter() - t0
-            return time.perf_counter()
-        t_stage = time.perf_counter()
-        st = torch.cuda.current_stream(device).cuda_stream
-        r = torch.from_numpy(self.rows.rewards).to(device)
-        d = torch.from_numpy(self.rows.dones).to(device)
-        f64 = torch.full((3, E, T), float("nan"), dtype=torch.float64, device=device)      # raw advantages, returns, normalised advantages (inspection)
-        if rs is not None:
-            if stage_times is not None:
-                torch.cuda.synchronize(device)
-            t_rs = time.perf_counter()
-            scaled = torch.full((2, E, T), float("nan"), dtype=torch.float64, device=device)   # discounted returns G, scaled rewards
+    def _scale_rewards(self, u, rs, r, d, gamma, truncs):
+        """The reward-scaling pass in front of the finish call (mi_rollout_scale_rewards) -> fp64 [2, E, T] on the device: discounted returns G, scaled rewards."""
+        import torch
+        E, T, device = self.num_envs, self.horizon, self.device
+        with u.clock.stage("reward_scaling"):
+            scaled = torch.full((2, E, T), float("nan"), dtype=torch.float64, device=device)
             tr = None if truncs is None else torch.from_numpy(truncs.astype(np.uint8)).to(device)
-            ln = torch.from_numpy(np.ascontiguousarray(lengths, np.int32)).to(device)
-            self.L.mi_rollout_scale_rewards(st, r.data_ptr(), d.data_ptr(), milib.ptr(tr), ln.data_ptr(), E, T, float(gamma), rs["epsilon"], rs["clip"],
+            ln = torch.from_numpy(np.ascontiguousarray(u.lengths, np.int32)).to(device)
+            self.L.mi_rollout_scale_rewards(u.st, r.data_ptr(), d.data_ptr(), milib.ptr(tr), ln.data_ptr(), E, T, float(gamma), rs["epsilon"], rs["clip"],
                                             0 if rs["frozen"] else 1, rs["state"].data_ptr(), rs["carry"].data_ptr(), rs["scratch"].data_ptr(), scaled[0].data_ptr(),
                                             scaled[1].data_ptr())
-            r = scaled[1]                                                            # what the finish call reads
-            mark("reward_scaling", t_rs)
-        finish(st, r, d, lengths, f64)
-        t_stage = mark("finish", t_stage)
-        ppo.update_old_policy()
-        # theta_old is fixed for the whole update: log pi_old(a | s) once per table row, in chunks of 4096 rows that hold a recorded step (slots that hold none are
-        # computed along and never read: the tables start as zeros)
-        fused = pdev.fused_ok()
-        logp_old = self.logp_old if fused else None
-        if fused:
-            for lo in range(0, self.n_table_rows, 4096):
-                hi = min(lo + 4096, self.n_table_rows)
-                if np.any((valid >= lo) & (valid < hi)):
-                    pdev.logp_old(self.states[lo:hi], self.actions[lo:hi], hi - lo, self.logp_old[lo:hi])
-        t_stage = mark("logp_old", t_stage)
-        records = []
+        return scaled
+
+    def _reward_scaling_result(self, u, rs, scaled, out):
+        state, scaled = rs["state"].cpu().numpy(), scaled.cpu().numpy()
+        out["return_rms"] = {"count": float(state[0]), "mean": float(state[1]), "var": float(state[2] / state[0]) if state[0] > 0 else 1.0}
+        out["reward_scale_den"] = float(state[3])
+        out["discounted_returns"], out["scaled_rewards"] = scaled[0], scaled[1]
+        out["reward_clip_fraction"] = float((np.abs(scaled[1][u.recorded]) == rs["clip"]).mean())
+        out["return_carry"] = rs["carry"].cpu().numpy()
+
+    def _cache_logp_old(self, valid):
+        """theta_old is fixed for the whole update: log pi_old(a | s) once per table row, in chunks of 4096 rows that hold a recorded step (slots that hold none are
+        computed along and never read: the tables start as zeros).  -> the table, or None without the fused kernels."""
+        pdev = self.ppo._need_dev()
+        if not pdev.fused_ok():
+            return None
+        for lo in range(0, self.n_table_rows, 4096):
+            hi = min(lo + 4096, self.n_table_rows)
+            if np.any((valid >= lo) & (valid < hi)):
+                pdev.logp_old(self.states[lo:hi], self.actions[lo:hi], hi - lo, self.logp_old[lo:hi])
+        return self.logp_old
+
+    def _run_epochs(self, u, logp_old):
+        """The epochs of shuffled minibatches.  Leaves in `u`: records (every step's losses), clips (with gradient clipping on, every step's {norm, scale, c, 0}), with
+        diagnostics epochs (a dict per epoch that ran), epoch_first (the index into clips of every epoch's first step) and stopped (the KL stop), and with per-minibatch
+        normalisation mb_stats ({count, mean, std} of every step) and mb_epochs (how many epochs it holds)."""
+        import torch
+        ppo, pdev, device, n_valid, batch_size = self.ppo, self.ppo._need_dev(), self.device, u.n_valid, u.batch_size
+        step_kw = {} if u.vclip is None else {"old_values_all": self.values}         # the values recorded at collection time: the table the finish call read
         clip = ppo.max_grad_norm is not None                                         # global-norm clipping on: every step's {norm, scale, c, 0} is kept as well
-        clips, epoch_first = [], [0]
-        if diag is not None:
-            from mi355.ppo_device import N_STATS, update_stats_summary
-            chunk = 4096
-            valid_dev = torch.from_numpy(valid).to(device)
-            if vclip is None:
-                stats = torch.zeros(N_STATS, dtype=torch.float64, device=device)
-            else:                                                                    # both sets of sums in one tensor: still one readback per epoch
-                from mi355.ppo_device import N_VCLIP_STATS, value_clip_summary
-                stats_all = torch.zeros(N_STATS + N_VCLIP_STATS, dtype=torch.float64, device=device)
-                stats, vstats = stats_all[:N_STATS], stats_all[N_STATS:]
-                vscratch = torch.empty(pdev.value_clip_scratch_doubles(min(n_valid, chunk)), dtype=torch.float64, device=device)
-                if getattr(self, "_values_new", None) is None:                       # V under the current parameters per table row, written by the statistics pass
-                    self._values_new = torch.zeros(self.n_table_rows, device=device)
-            stats_scratch = torch.empty(pdev.stats_scratch_doubles(min(n_valid, chunk)), dtype=torch.float64, device=device)
-            epochs, stopped = [], False
-        adv_table, mb_epochs = self.advantages, 0                                    # the table the steps gather their advantage from
-        if mbn is not None:
+        records, clips = [], []
+        u.records, u.clips, u.epoch_first, u.epochs, u.stopped, u.mb_epochs = records, clips, [0], [], False, 0
+        observe = self._stats_pass(u) if u.diag is not None else None
+        adv_table = self.advantages                                                  # the table the steps gather their advantage from
+        if u.mbn is not None:
             if getattr(self, "_minibatch_advantages", None) is None:
                 self._minibatch_advantages = torch.zeros(self.n_table_rows, device=device)
             adv_table = self._minibatch_advantages
-            mb_stats = torch.zeros(int(num_epochs), -(-n_valid // batch_size), 3, dtype=torch.float64, device=device)      # {count, mean, std} of every step
-        for _ in range(int(num_epochs)):
+            u.mb_stats = torch.zeros(u.num_epochs, -(-n_valid // batch_size), 3, dtype=torch.float64, device=device)
+        for _ in range(u.num_epochs):
             indices = np.arange(n_valid)
             np.random.shuffle(indices)                                               # legacy numpy RNG, as train.py:194-195
-            perm = torch.from_numpy(valid[indices]).to(device)                       # shuffled positions -> table rows
-            if mbn is not None:                                                      # this epoch's minibatches, each normalised alone, from the raw advantages
-                if stage_times is not None:
-                    torch.cuda.synchronize(device)
-                t_mb = time.perf_counter()
-                self.L.mi_ppo_minibatch_advantages(st, f64[0].data_ptr(), perm.data_ptr(), n_valid, batch_size, E, T, mbn["ddof"], adv_table.data_ptr(),
-                                                   mb_stats[mb_epochs].data_ptr())
-                mb_epochs += 1
-                mark("minibatch_norm", t_mb)
+            perm = torch.from_numpy(u.valid[indices]).to(device)                     # shuffled positions -> table rows
+            if u.mbn is not None:                                                    # this epoch's minibatches, each normalised alone, from the raw advantages
+                with u.clock.stage("minibatch_norm"):
+                    self.L.mi_ppo_minibatch_advantages(u.st, u.f64[0].data_ptr(), perm.data_ptr(), n_valid, batch_size, self.num_envs, self.horizon, u.mbn["ddof"],
+                                                       adv_table.data_ptr(), u.mb_stats[u.mb_epochs].data_ptr())
+                    u.mb_epochs += 1
             for i in range(0, n_valid, batch_size):
                 mb = perm[i:i + batch_size]                                          # the last one may be partial (train.py:199-201)
                 m = int(mb.numel())
@@ -1106,65 +1157,80 @@ class RolloutBuffer:
                 records.append(pdev.losses.clone())
                 if clip:
                     clips.append(pdev.grad_clip.clone())
-            if diag is not None:                                                     # observe the epoch: all valid rows under the parameters it ended with
-                t_stage = mark("sgd", t_stage)
-                for lo in range(0, n_valid, chunk):
-                    rows = valid_dev[lo:lo + chunk]
-                    if vclip is None:
-                        pdev.update_stats(self.states, self.actions, self.returns, self.logp_old, rows, int(rows.numel()), stats, stats_scratch, accumulate=lo > 0)
-                    else:
-                        pdev.update_stats(self.states, self.actions, self.returns, self.logp_old, rows, int(rows.numel()), stats, stats_scratch, accumulate=lo > 0,
-                                          value_out=self._values_new)
-                        pdev.value_clip_stats(self._values_new, self.values, self.returns, rows, int(rows.numel()), vclip, vstats, vscratch, accumulate=lo > 0)
-                if vclip is None:
-                    epochs.append(update_stats_summary(stats.cpu().numpy()))         # the epoch's one readback
-                else:
-                    both = stats_all.cpu().numpy()                                   # (the same one readback)
-                    epochs.append(update_stats_summary(both[:N_STATS]))
-                    epochs[-1].update(value_clip_summary(both[N_STATS:]))
-                epoch_first.append(len(clips))                                       # (the epoch's norms are read back with all the others, behind the last epoch)
-                t_stage = mark("stats", t_stage)
-                if diag["target_kl"] is not None and epochs[-1]["approx_kl"] > diag["target_kl"]:
-                    stopped = True
+            if observe is not None:                                                  # observe the epoch: all valid rows under the parameters it ended with
+                u.clock.lap("sgd")
+                u.epochs.append(observe())
+                u.epoch_first.append(len(clips))                                     # (the epoch's norms are read back with all the others, behind the last epoch)
+                u.clock.lap("stats")
+                if u.diag["target_kl"] is not None and u.epochs[-1]["approx_kl"] > u.diag["target_kl"]:
+                    u.stopped = True
                     break
-        losses = torch.stack(records).cpu().numpy() if records else np.zeros((0, 5), np.float32)
-        mark("sgd", t_stage)
+
+    def _minibatch_norm_result(self, u, out):
+        E, T = self.num_envs, self.horizon                                           # one readback behind the last epoch; only the epochs that ran
+        out["minibatch_adv_stats"] = u.mb_stats[:u.mb_epochs].reshape(-1, 3).cpu().numpy()
+        table = self._minibatch_advantages.view(E, T + 1)[:, :T].cpu().numpy()
+        out["minibatch_advantages"] = np.where(u.recorded & (u.mb_epochs > 0), table, np.float32(np.nan)).astype(np.float32)
+
+    def _stats_pass(self, u):
+        """The statistics pass of update_with_diagnostics -> observe(): the pass over all valid rows in chunks of 4096 and the epoch's one readback -> the epoch's dict.
+        With value clipping on the pass also writes V per table row (_values_new), mi_ppo_value_clip_stats runs over the same chunks, and its sums sit behind the others."""
+        import torch
+        from mi355.ppo_device import N_STATS, N_VCLIP_STATS, update_stats_summary, value_clip_summary
+        pdev, device, vclip, chunk = self.ppo._need_dev(), self.device, u.vclip, 4096
+        valid_dev = torch.from_numpy(u.valid).to(device)
+        sums = torch.zeros(N_STATS + (0 if vclip is None else N_VCLIP_STATS), dtype=torch.float64, device=device)
+        stats, vstats, value_out = sums[:N_STATS], sums[N_STATS:], None
+        if vclip is not None:
+            vscratch = torch.empty(pdev.value_clip_scratch_doubles(min(u.n_valid, chunk)), dtype=torch.float64, device=device)
+            if getattr(self, "_values_new", None) is None:
+                self._values_new = torch.zeros(self.n_table_rows, device=device)
+            value_out = self._values_new
+        stats_scratch = torch.empty(pdev.stats_scratch_doubles(min(u.n_valid, chunk)), dtype=torch.float64, device=device)
+
+        def observe():
+            for lo in range(0, u.n_valid, chunk):
+                rows = valid_dev[lo:lo + chunk]
+                pdev.update_stats(self.states, self.actions, self.returns, self.logp_old, rows, int(rows.numel()), stats, stats_scratch, accumulate=lo > 0,
+                                  value_out=value_out)
+                if vclip is not None:
+                    pdev.value_clip_stats(value_out, self.values, self.returns, rows, int(rows.numel()), vclip, vstats, vscratch, accumulate=lo > 0)
+            both = sums.cpu().numpy()                                                # the epoch's one readback
+            epoch = update_stats_summary(both[:N_STATS])
+            if vclip is not None:
+                epoch.update(value_clip_summary(both[N_STATS:]))
+            return epoch
+        return observe
+
+    def _result(self, u):
+        """The keys of every update -- the loss records, the finish call's outputs as [num_envs, T] arrays, NaN beyond a row's length -- and what the SGD loop recorded
+        with gradient clipping or diagnostics on."""
+        import torch
+        E, T, lengths = self.num_envs, self.horizon, u.lengths
+        losses = torch.stack(u.records).cpu().numpy() if u.records else np.zeros((0, 5), np.float32)
+        u.clock.lap("sgd")
         keys = ("policy_loss", "value_loss", "entropy_loss", "loss", "prob_ratio")
-        f64 = f64.cpu().numpy()
+        f64 = u.f64.cpu().numpy()
         v_all = self.values.view(E, T + 1).cpu().numpy()
-        values = np.where(np.arange(T)[None, :] < lengths[:, None], v_all[:, :T], np.float32(np.nan)).astype(np.float32)
+        values = np.where(u.recorded, v_all[:, :T], np.float32(np.nan)).astype(np.float32)
         out = {"losses": [dict(zip(keys, (float(x) for x in row))) for row in losses], "lengths": lengths, "raw_advantages": f64[0], "returns": f64[1],
-               "advantages": f64[2], "values": values, "bootstrap_values": np.where(lengths > 0, v_all[np.arange(E), lengths], np.float32(np.nan)).astype(np.float32), "samples": n_valid}
-        if clip:
-            gc = torch.stack(clips).cpu().numpy() if clips else np.zeros((0, 4), np.float32)
+               "advantages": f64[2], "values": values, "bootstrap_values": np.where(lengths > 0, v_all[np.arange(E), lengths], np.float32(np.nan)).astype(np.float32),
+               "samples": u.n_valid}
+        if self.ppo.max_grad_norm is not None:
+            gc = torch.stack(u.clips).cpu().numpy() if u.clips else np.zeros((0, 4), np.float32)
             out["grad_norms"], out["clip_scales"] = gc[:, 0].astype(np.float32).copy(), gc[:, 1].astype(np.float32).copy()
-            if diag is not None:
-                for e, lo, hi in zip(epochs, epoch_first[:-1], epoch_first[1:]):     # NaN norms count as the maximum (np.max propagates them)
-                    e["grad_norm_max"] = float(gc[lo:hi, 0].max()) if hi > lo else float("nan")
-                    e["clipped_steps"] = int((gc[lo:hi, 1] < 1.0).sum())
-        if diag is not None:
-            out["epochs"], out["epochs_run"], out["stopped_early"] = epochs, len(epochs), stopped
-        if mbn is not None:                                                          # one readback behind the last epoch; only the epochs that ran
-            out["minibatch_adv_stats"] = mb_stats[:mb_epochs].reshape(-1, 3).cpu().numpy()
-            seen = (np.arange(T)[None, :] < lengths[:, None]) & (mb_epochs > 0)
-            out["minibatch_advantages"] = np.where(seen, adv_table.view(E, T + 1)[:, :T].cpu().numpy(), np.float32(np.nan)).astype(np.float32)
-        if rs is not None:
-            state, scaled = rs["state"].cpu().numpy(), scaled.cpu().numpy()
-            out["return_rms"] = {"count": float(state[0]), "mean": float(state[1]), "var": float(state[2] / state[0]) if state[0] > 0 else 1.0}
-            out["reward_scale_den"] = float(state[3])
-            out["discounted_returns"], out["scaled_rewards"] = scaled[0], scaled[1]
-            out["reward_clip_fraction"] = float((np.abs(scaled[1][recorded]) == rs["clip"]).mean())
-            out["return_carry"] = rs["carry"].cpu().numpy()
-        on = getattr(self, "_obs_norm", None)                                        # running observation normalisation (set_observation_normalization): None = off
-        if on is not None:                                                           # the update's last launch: nothing above can raise behind it
-            if stage_times is not None:
-                torch.cuda.synchronize(device)
-            t_on = time.perf_counter()
-            batch = self._obs_norm_stats(valid, 0 if on["frozen"] else 1, "update")
-            mark("observation_stats", t_on)
-            out["observation_rms"] = _obs_norm_rms(on)
-            out["observation_clip_fraction"] = batch[2] / n_valid
+            for e, lo, hi in zip(u.epochs, u.epoch_first[:-1], u.epoch_first[1:]):   # (diagnostics)  NaN norms count as the maximum (np.max propagates them)
+                e["grad_norm_max"] = float(gc[lo:hi, 0].max()) if hi > lo else float("nan")
+                e["clipped_steps"] = int((gc[lo:hi, 1] < 1.0).sum())
+        if u.diag is not None:
+            out["epochs"], out["epochs_run"], out["stopped_early"] = u.epochs, len(u.epochs), u.stopped
         return out
+
+    def _observation_stats(self, u, on, out):
+        with u.clock.stage("observation_stats"):
+            batch = self._obs_norm_stats(u.valid, 0 if on["frozen"] else 1, "update")
+        out["observation_rms"] = _obs_norm_rms(on)
+        out["observation_clip_fraction"] = batch[2] / u.n_valid
 
 
 class ContinuousRolloutBuffer(RolloutBuffer):

@@ -1,7 +1,8 @@
 """Shared helpers of the GPU rollout tests (test_l_rollout_batch_gpu.py, test_m_rollout_buffer_gpu.py, test_n_rollout_segments_gpu.py): the set-up of
 test_c_c3_ppo_gpu.py::test_rollout_step_one_call_matches_encode_then_predict (oracle VAE with N(0, 0.05) biases, an oracle / device policy pair with the same weights,
 random camera bytes), the per-row oracle, and the comparisons.  Tolerances: against the oracle latents 1e-4 relative, actions rtol 1e-4 / atol 1e-5, value rel 1e-4 /
-abs 1e-5; 1e-5 between the device paths (both end in fp32 atomics, so bit equality is not asked); the update's losses at test_e_c5_replay_gpu.py's."""
+abs 1e-5; 1e-5 between the device paths (both end in fp32 atomics, so bit equality is not asked); the update's losses at test_e_c5_replay_gpu.py's.  Also the
+comparisons of the twin tests (test_p .. test_v): bitwise tensors, a policy's flat state, two updates' results."""
 import numpy as np
 import pytest
 
@@ -129,3 +130,18 @@ def check_losses(got, want, tag):
         assert g["value_loss"] == pytest.approx(w["value_loss"], rel=1e-4), (tag, i, g, w)
         assert g["policy_loss"] == pytest.approx(w["policy_loss"], abs=1e-4), (tag, i, g, w)
         assert g["prob_ratio"] == pytest.approx(w["ratio_mean"] if "ratio_mean" in w else w["prob_ratio"], rel=1e-4), (tag, i, g, w)
+
+
+def bitwise(x, y):
+    """Two tensors, or two lists of tensors, hold the same bits."""
+    import torch
+    x, y = (x, y) if isinstance(x, (list, tuple)) else ([x], [y])
+    return all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(x, y))
+
+
+def flat_state(m):
+    return [m.dev.params.clone(), m.dev.adam_m.clone(), m.dev.adam_v.clone(), m.dev.params_old.clone()]
+
+
+def same_update(a, b, keys=("returns", "advantages", "raw_advantages", "values", "bootstrap_values", "lengths")):
+    return a["losses"] == b["losses"] and a["samples"] == b["samples"] and all(np.array_equal(a[k], b[k], equal_nan=True) for k in keys)

@@ -14,7 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import ppo_oracle as po  # noqa: E402
-from rollout_gpu_common import A, SENTINEL, close, inputs, make_pair, make_world, tables  # noqa: E402
+from rollout_gpu_common import A, SENTINEL, bitwise, close, inputs, make_pair, make_world, tables  # noqa: E402
 from test_rollout_diagnostics_host import sums_of  # noqa: E402
 
 E, T, BATCH = 4, 16, 16
@@ -302,11 +302,6 @@ def test_statistics_against_float64(trained, tmp_path, precision):
 
 def params_of(m):
     return [m.dev.params.clone(), m.dev.adam_m.clone(), m.dev.adam_v.clone()]
-
-
-def bitwise(x, y):
-    import torch
-    return all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(x, y))
 
 
 @pytest.mark.parametrize("continuous", [False, True])

@@ -21,7 +21,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import ppo_oracle as po  # noqa: E402
-from rollout_gpu_common import inputs, make_pair, make_world, rel_err  # noqa: E402
+from rollout_gpu_common import bitwise, inputs, make_pair, make_world, rel_err  # noqa: E402
 
 MS = (5, 32, 256, 257)
 ULP2 = 2.4e-7                                            # 2 fp32 ulps, relative
@@ -67,11 +67,6 @@ class State:
 
 def result(d):
     return [x.clone() for x in (d.params, d.adam_m, d.adam_v)]
-
-
-def bitwise(x, y):
-    import torch
-    return all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(x, y))
 
 
 def gap_mask(d):

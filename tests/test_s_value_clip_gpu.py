@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 import ppo_shape_cases as pc  # noqa: E402
 from oracle import ppo_oracle as po  # noqa: E402
-from rollout_gpu_common import inputs, make_pair, make_world  # noqa: E402
+from rollout_gpu_common import bitwise, flat_state, inputs, make_pair, make_world  # noqa: E402
 
 EPS_V = 0.2
 EPS32 = float(np.float32(EPS_V))                          # the range as the kernels see it
@@ -184,12 +184,6 @@ class Rig:
         else:
             d.train_step_vclip(comm, *tabs, lp_t, q.tab[v_old], eps, q.rows, M, *a, adam=adam)
         return [x.clone() for x in (d.params, d.adam_m, d.adam_v)], d.losses.clone(), d.grads.clone(), d.value_head_grad[:M].clone()
-
-
-def bitwise(x, y):
-    import torch
-    x, y = (x, y) if isinstance(x, (list, tuple)) else ([x], [y])
-    return all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(x, y))
 
 
 @pytest.fixture(scope="module")
@@ -452,10 +446,6 @@ def collect(world, tmp, continuous, source):
         x.copy_(y)
     np.random.seed(SEED)
     return m, buf
-
-
-def flat_state(m):
-    return [m.dev.params.clone(), m.dev.adam_m.clone(), m.dev.adam_v.clone()]
 
 
 @pytest.mark.parametrize("continuous", [False, True])

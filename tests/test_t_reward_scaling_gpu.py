@@ -15,7 +15,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from rollout_gpu_common import inputs, make_pair, make_world  # noqa: E402
+from rollout_gpu_common import bitwise, flat_state, inputs, make_pair, make_world, same_update  # noqa: E402
 from test_reward_scaling_host import reference, rel  # noqa: E402
 
 GAMMA, EPSILON, CLIP = 0.99, 1e-8, 1.5
@@ -259,19 +259,6 @@ def new_buffer(world, tmp, continuous, ppo=None):
 def run_update(buf, diagnostics=False, **kw):
     np.random.seed(SEED)
     return (buf.update_with_diagnostics if diagnostics else buf.update)(num_epochs=EPOCHS, batch_size=BATCH, **kw)
-
-
-def flat_state(m):
-    return [m.dev.params.clone(), m.dev.adam_m.clone(), m.dev.adam_v.clone(), m.dev.params_old.clone()]
-
-
-def bitwise(x, y):
-    import torch
-    return all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(x, y))
-
-
-def same_update(a, b, keys=("returns", "advantages", "raw_advantages", "values", "bootstrap_values", "lengths")):
-    return a["losses"] == b["losses"] and a["samples"] == b["samples"] and all(np.array_equal(a[k], b[k], equal_nan=True) for k in keys)
 
 
 def host_truncs(buf):

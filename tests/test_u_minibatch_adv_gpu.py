@@ -14,7 +14,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from rollout_gpu_common import SENTINEL, inputs, make_pair, make_world  # noqa: E402
+from rollout_gpu_common import SENTINEL, bitwise, flat_state, inputs, make_pair, make_world  # noqa: E402
 from test_minibatch_adv_host import CASES, case_lengths, make_case, reference  # noqa: E402
 
 PAD = 8                                                     # sentinel entries behind the table: a row outside the table that was stored after all would land here
@@ -222,15 +222,6 @@ def new_buffer(world, tmp, continuous, E, T, ppo=None):
 def run_update(buf, batch, diagnostics=False, epochs=EPOCHS, **kw):
     np.random.seed(SEED)
     return (buf.update_with_diagnostics if diagnostics else buf.update)(num_epochs=epochs, batch_size=batch, **kw)
-
-
-def flat_state(m):
-    return [m.dev.params.clone(), m.dev.adam_m.clone(), m.dev.adam_v.clone(), m.dev.params_old.clone()]
-
-
-def bitwise(x, y):
-    import torch
-    return all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(x, y))
 
 
 FINISH_KEYS = ("returns", "raw_advantages", "advantages", "values", "bootstrap_values", "lengths")

@@ -19,7 +19,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from rollout_gpu_common import A, K, SENTINEL, Z, close, inputs, make_pair, make_world  # noqa: E402
+from rollout_gpu_common import A, K, SENTINEL, Z, bitwise, close, flat_state, inputs, make_pair, make_world, same_update  # noqa: E402
 from test_observation_normalization_host import check_moments, columns, derive, reference  # noqa: E402
 
 DIN = Z + K
@@ -351,19 +351,6 @@ def new_buffer(world, tmp, continuous, E, T, ppo=None):
 def run_update(buf, **kw):
     np.random.seed(SEED)
     return buf.update(num_epochs=EPOCHS, batch_size=BATCH, **kw)
-
-
-def flat_state(m):
-    return [m.dev.params.clone(), m.dev.adam_m.clone(), m.dev.adam_v.clone(), m.dev.params_old.clone()]
-
-
-def bitwise(x, y):
-    import torch
-    return all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(x, y))
-
-
-def same_update(a, b, keys=("returns", "advantages", "raw_advantages", "values", "bootstrap_values", "lengths")):
-    return a["losses"] == b["losses"] and a["samples"] == b["samples"] and all(np.array_equal(a[k], b[k], equal_nan=True) for k in keys)
 
 
 def as_state(d):
