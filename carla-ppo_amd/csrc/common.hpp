@@ -37,6 +37,8 @@ __host__ __device__ __forceinline__ bf16_t f32_to_bf16(float f) {
 // against that fragment with the halves of every dword swapped sum(la hb + ha lb): TWO v_mfma_f32_32x32x16_bf16 (64 cycles) give the full
 // (ha + la)(hb + lb) products of 8 k-values, fp32-accumulated, where exact fp32 needs four v_mfma_f32_32x32x2_f32 (256 cycles).  Every tensor keeps
 // the element size, alignment and addressing of the fp32 engine, so the LDS-DMA tile kernels move split tiles exactly as they move fp32 tiles.
+// Range: from the bf16 overflow point on (0x7f7f8000, just under 2^128; the tests stay below 2^127) the high half rounds to infinity and the pair decodes to NaN (inf + -inf); below 2^-117 lo's bits fall under the smallest bf16 step
+// (2^-133) and the pair is good to 2^-134 absolute, not 2^-17 relative.
 struct split_t { uint32_t u; };
 __host__ __device__ __forceinline__ split_t split_from_f32(float x) {
     const bf16_t h = f32_to_bf16(x);
