@@ -29,6 +29,7 @@ struct PpoEngine {
     long long f_gslab;                            // per-chunk gradient slabs of the large-minibatch step (max_batch > 256): [ceil(max_batch / 256)][total]
     long long gn_part, clip;                      // global-norm clipping: the block partials of the sum of squares (doubles), and {norm, scale, c, 0} of the last norm (mi_ppo_buffer(h, 2))
     float max_grad_norm;                          // 0 (calloc: the default): no clipping; > 0 or +inf: mi_ppo_apply_adam clips by the global norm (mi_ppo_set_max_grad_norm)
+    long long f_klpart;                           // KL penalty (mi_ppo_train_step_kl): one float per loss block
     long long f_h1, f_h2, f_dh1, f_dh2, f_part;   // fused step (ppo_fused.hip): [3][M][H1], [3][M][H2], [2][M][H1], [2][M][H2], loss-block partials
     int last_M;
     int precision;                                // MI_F32 (calloc: the default) or MI_BF16X3 (mi_ppo_set_precision): which instantiation of the fused GEMM stages runs
@@ -63,6 +64,7 @@ void layout(PpoEngine& e) {
     e.f_part = wa((long long)mi_ppo_fused_partial_floats((int)M) * 4);
     e.f_gslab = wa(M > 256 ? ((M + 255) / 256) * e.total * 4 : 0);
     e.gn_part = wa(MI_GRAD_NORM_BLOCKS * 8); e.clip = wa(16);
+    e.f_klpart = wa(((M + 31) / 32) * 4);
     e.ws_total = w;
 }
 
@@ -117,7 +119,7 @@ void fill_fused(const PpoEngine* e, PpoFusedParams& q, const float* states, int 
     q.states = states; q.low = (const float*)e->at(e->low); q.high = (const float*)e->at(e->high);
     q.h1 = (float*)e->at(e->f_h1); q.h2 = (float*)e->at(e->f_h2); q.dh1 = (float*)e->at(e->f_dh1); q.dh2 = (float*)e->at(e->f_dh2);
     q.du = (float*)e->at(e->du); q.dv = (float*)e->at(e->dv); q.partial = (float*)e->at(e->f_part); q.losses = (float*)e->at(e->losses);
-    q.mean_out = (float*)e->at(e->mean);
+    q.mean_out = (float*)e->at(e->mean); q.kl_partial = (float*)e->at(e->f_klpart);
     q.gslab = d.max_batch > 256 ? (float*)e->at(e->f_gslab) : nullptr; q.gslab_stride = e->total;      // (total is a multiple of 8 floats: pad8 per tensor)
     q.n_nets = 3;
     q.clip_eps = d.clip_eps; q.value_scale = d.value_scale; q.entropy_scale = d.entropy_scale;
@@ -431,6 +433,71 @@ int mi_ppo_train_step_vclip(void* h, void* comm, void* stream, const float* stat
     if (!adam) return MI_OK;
     if (comm) CK(mi_allreduce_sum_f32(comm, stream, e->grads, e->total));
     return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
+}
+
+// The minibatch step with the adaptive-KL penalty of the PPO paper added to the clipped surrogate (include/mi355_carla.h; the definition is in ppo_fused.hip's head /
+// loss kernel): ONE entry for every form, as mi_ppo_train_step_vclip is -- row_idx NULL or not, comm NULL or not, adam 0 / 1, old_values NULL (the plain value loss)
+// or the clipped one -- on the routes of that entry.  kl_coef = 0 measures: the KL slots are filled and nothing is added.  Fused kernels only.
+int mi_ppo_train_step_kl(void* h, void* comm, void* stream, const float* states, const float* actions, const float* returns, const float* advantage,
+                         const float* logp_old, const float* mean_old, float kl_coef, const float* old_values, float clip_range_vf,
+                         const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step_kl: null handle");
+    // (what needs no engine is checked before the handle is looked at)
+    if (M < 1 || (row_idx && n_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_kl: batch outside [1, max_batch] or empty tables");
+    if ((logp_old != nullptr) != (mean_old != nullptr))
+        return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_kl: logp_old and mean_old come together (mi_ppo_old_policy_cache) or are both NULL (the step evaluates the old policy)");
+    if (!(kl_coef >= 0.f) || !(kl_coef <= 3.402823466e+38f)) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_kl: kl_coef is a finite float >= 0 (0: measure the KL, add nothing)");
+    if (old_values && !(clip_range_vf > 0.f)) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_kl: with old_values, clip_range_vf is a positive float or +inf");
+    if (adam != 0 && adam != 1) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_kl: adam is 0 (stop with the gradients in the flat buffer) or 1 (apply the optimiser)");
+    if (M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_kl: batch outside [1, max_batch] or empty tables");
+    if (!e->grads || (adam && (!e->m || !e->v))) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step_kl: engine created without gradient / optimiser buffers");
+    if (!fused_enabled(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_train_step_kl: needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0): there is no per-layer form of the KL penalty");
+    PpoFusedParams q; fill_fused(e, q, states, M);
+    q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
+    q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
+    q.kl_on = 1; q.kl_coef = kl_coef; q.mean_old = mean_old;
+    if (old_values) { q.v_old = old_values; q.clip_range_vf = clip_range_vf; }
+    if (row_idx) { q.row_idx = row_idx; q.n_rows = n_rows; q.s_gath = (float*)e->at(e->s_pad); }
+    e->last_M = M;
+    if (adam && !comm && M <= 256 && !clipping(e)) {
+        q.alpha = alpha; q.omb1 = 1.0f - beta1; q.omb2 = 1.0f - beta2; q.epsilon = epsilon;
+        return mi_ppo_fused_step((hipStream_t)stream, q, 1, x3(e));
+    }
+    CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));      // gradients written into the flat buffer (M > 256: ordered row chunks)
+    if (!adam) return MI_OK;
+    if (comm) CK(mi_allreduce_sum_f32(comm, stream, e->grads, e->total));
+    return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
+}
+
+// mi_ppo_logp_old that keeps the old policy's action means as well: logp_out [M] (bit for bit mi_ppo_logp_old's), mean_out [M, A] -- the two tables of the KL penalty
+int mi_ppo_old_policy_cache(void* h, void* stream, const float* states, const float* actions, int M, float* logp_out, float* mean_out) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_old_policy_cache: null handle");
+    if (M < 1 || M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_old_policy_cache: batch outside [1, max_batch]");
+    if (!states || !actions || !logp_out || !mean_out) return mi_fail(MI_ERR_ARG, "mi_ppo_old_policy_cache: missing buffers");
+    if (!fused_enabled(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_old_policy_cache: needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0)");
+    PpoFusedParams q; fill_fused(e, q, states, M);
+    q.actions = actions; q.mean_old_out = mean_out;
+    return mi_ppo_fused_logp_old((hipStream_t)stream, q, logp_out, x3(e));
+}
+
+// The exact-KL statistics pass (include/mi355_carla.h): the sums behind the mean / spread of the closed-form KL(pi_old || pi_theta) of M gathered table rows under
+// the CURRENT theta against the cached old means -- forward only, ordered reduction, nothing of the training state is written.
+long long mi_ppo_kl_stats_scratch_doubles(int M) { return (long long)MI_PPO_N_KL_STATS * (M < 1 ? 1 : (M + 31) / 32); }
+
+int mi_ppo_kl_stats_idx(void* h, void* stream, const float* states, const float* mean_old, const int* row_idx, int n_rows, int M, int accumulate, double* scratch, double* stats) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_kl_stats_idx: null handle");
+    // (what needs no engine is checked before the handle is looked at)
+    if (M < 1 || n_rows < 1) return mi_fail(MI_ERR_ARG, "mi_ppo_kl_stats_idx: batch outside [1, max_batch] or empty tables");
+    if (!states || !mean_old || !row_idx || !scratch || !stats) return mi_fail(MI_ERR_ARG, "mi_ppo_kl_stats_idx: missing buffers (states, mean_old, row_idx, scratch, stats)");
+    if (accumulate != 0 && accumulate != 1) return mi_fail(MI_ERR_ARG, "mi_ppo_kl_stats_idx: accumulate is 0 (store the sums) or 1 (add them to stats)");
+    if (M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_kl_stats_idx: batch outside [1, max_batch] or empty tables");
+    if (!fused_enabled(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_kl_stats_idx: needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0)");
+    PpoFusedParams q; fill_fused(e, q, states, M);
+    q.mean_old = mean_old; q.row_idx = row_idx; q.n_rows = n_rows;
+    return mi_ppo_fused_kl_stats((hipStream_t)stream, q, accumulate, scratch, stats, x3(e));
 }
 
 // log pi_old(a | s) of M samples under theta_old -> out [M] (the per-horizon cache for mi_ppo_train_step)

@@ -257,12 +257,25 @@ __global__ __launch_bounds__(256) void ppo_l2_kernel(const PpoFusedParams q) {
 // flows; the clipped branch is chosen only outside the range, where its slope is 0.  eps_v = +inf gives the unclipped step bit for bit.  V_old is one more 4-byte
 // gather per sample, requested with returns / advantages / log pi_old (the same clamped table row) before the first barrier; nothing on the policy side changes, and
 // the partial layout, the LDS and the finalisation in ppo_wgrad_kernel are those of the plain kernel.
+//
+// KLP (ppo_head_loss_kl[_vclip]_kernel; mi_ppo_train_step_kl): the KL-penalised surrogate of the PPO paper (Schulman et al. 2017, section 4) on top of the clip.
+// Direction KL(pi_old || pi_theta), closed form for the diagonal Gaussian.  Per (sample m, action a), with ls / lso the current / old action_logstd, mu / mu_o the
+// current / old action means (after the low + (tanh(u) + 1) / 2 (high - low) map), d = ls - lso, D = mu - mu_o, sigma = exp(ls), beta = q.kl_coef >= 0:
+//   KL[m,a] = d + expm1(-2 d) / 2 + D^2 / (2 sigma^2) ,  KL[m] = sum_a KL[m,a] ,  loss += beta mean_m KL[m]
+//   du[m,a]    += beta inv_m (D / sigma^2) (high - low) / 2 (1 - t^2)
+//   dlogstd[a] += beta inv_m sum_m (-expm1(-2 d) - D^2 / sigma^2)          (summed per sample with inv_m = 1 / M_global: no grad_scale, unlike the entropy term)
+// Lane `part` of a sample forms the terms of action `part` from mean, t, sigma it already holds; the per-sample KL meets with lp_n's shuffles; the du / dlogstd
+// terms are added into sdu / du / spart[3 + part], so nothing behind this kernel changes.  mu_o: with a cached log pi_old one more 4-byte gather per (sample,
+// action) from q.mean_old at the clamped row mr, requested with actions / returns / advantage; without a cache it is the mean the old-policy block below forms
+// (tanhf, the cache kernel's spelling: both sources give the same mu_o).  lso comes from theta_old in both.  The block's sum of KL[m] (samples in order, one
+// thread) goes to q.kl_partial[block]; ppo_wgrad_kernel's spare wave adds those in block order.  beta = 0 measures: every added term is 0.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int PF_H2MAX = 320;                             // head kernels staged in LDS: H2 <= 320 (the reference: 300)
-template <int NA, bool VCLIP>
+template <int NA, bool VCLIP, bool KLP>
 __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
     __shared__ __attribute__((aligned(16))) float sWm[PF_H2MAX * PF_MAX_ACT], sWo[PF_H2MAX * PF_MAX_ACT], sWv[PF_H2MAX];
     __shared__ float su[32][NA], sv[32], sdu[32][NA], sdv[32], spart[32][PF_NPART];
+    __shared__ float skl[KLP ? 32 : 1];                   // KLP: KL[m] of the block's samples
     const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
     const float* __restrict__ Wm = q.theta + q.off[4]; const float* __restrict__ bm = q.theta + q.off[5];
     const float* __restrict__ Wmo = q.theta_old + q.off[4]; const float* __restrict__ bmo = q.theta_old + q.off[5];
@@ -299,17 +312,18 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
     for (int i = 0; i < NST; ++i) { const int x = tid + 256 * i; stm[i] = x < H2 * A ? Wm[x] : 0.f; sto[i] = (old_net && x < H2 * A) ? Wmo[x] : 0.f; }
 #pragma unroll
     for (int i = 0; i < (PF_H2MAX + 255) / 256; ++i) { const int x = tid + 256 * i; stv[i] = x < H2 ? Wv[x] : 0.f; }
-    float p_act[NA], p_adv_s = 0.f, p_ret_s = 0.f, p_lpo_s = 0.f, p_vold_s = 0.f, p_ls[NA], p_lso[NA], p_lo[NA], p_hi[NA];
+    float p_act[NA], p_adv_s = 0.f, p_ret_s = 0.f, p_lpo_s = 0.f, p_vold_s = 0.f, p_muo_s = 0.f, p_ls[NA], p_lso[NA], p_lo[NA], p_hi[NA];
     const int mr = (q.row_idx && mok) ? min(max(q.row_idx[m], 0), q.n_rows - 1) : m;     // the sample's row in the horizon-batch tables (actions / returns / advantages / cached log pi_old)
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
         const bool aok = a < A;
         p_act[a] = (mok && aok) ? q.actions[(long long)mr * A + a] : 0.f;
-        p_ls[a] = aok ? q.theta[q.off[6] + a] : 0.f; p_lso[a] = (aok && old_net) ? q.theta_old[q.off[6] + a] : 0.f;
+        p_ls[a] = aok ? q.theta[q.off[6] + a] : 0.f; p_lso[a] = (aok && (old_net || KLP)) ? q.theta_old[q.off[6] + a] : 0.f;
         p_lo[a] = aok ? q.low[a] : 0.f; p_hi[a] = aok ? q.high[a] : 0.f;
     }
     if (mok) { p_adv_s = q.adv[mr]; p_ret_s = q.returns[mr]; if (!old_net) p_lpo_s = q.logp_old[mr]; }
     if constexpr (VCLIP) { if (mok) p_vold_s = q.v_old[mr]; }
+    if constexpr (KLP) { if (mok && !old_net && part < A) p_muo_s = q.mean_old[(long long)mr * A + part]; }
 #pragma unroll
     for (int i = 0; i < NST; ++i) { const int x = tid + 256 * i; if (x < H2 * A) { sWm[x] = stm[i]; sWo[x] = sto[i]; } }
 #pragma unroll
@@ -373,6 +387,7 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
                 const float sigma = expf(p_lso[a]);
                 const float z = (p_act[a] - mean) / sigma;
                 lp += -0.5f * z * z - (PF_HALF_LOG_2PI + logf(sigma));
+                if constexpr (KLP) { if (a == part) p_muo_s = mean; }
             }
             lp_old_s = lp;
         }
@@ -389,8 +404,9 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
         auto fast_tanh = [](float x) { const float xc = fminf(fmaxf(x, -15.f), 15.f); return 1.0f - 2.0f / (__expf(2.0f * xc) + 1.0f); };
         float lp_n = 0.f, dl = 0.f, zsq = 0.f, mean = 0.f;
         float act = 0.f, ls = 0.f, lo = 0.f, hi = 0.f;
+        float lso = 0.f, kl = 0.f, kdu = 0.f, kdls = 0.f;  // KLP: this lane's old logstd, KL[m,part] and the penalty's du / dlogstd terms (without beta inv_m)
 #pragma unroll
-        for (int a = 0; a < NA; ++a) if (a == part) { act = p_act[a]; ls = p_ls[a]; lo = p_lo[a]; hi = p_hi[a]; }
+        for (int a = 0; a < NA; ++a) if (a == part) { act = p_act[a]; ls = p_ls[a]; lo = p_lo[a]; hi = p_hi[a]; if constexpr (KLP) lso = p_lso[a]; }
         const bool aok = part < A && mok;
         if (aok) {
             const float t = fast_tanh(su[sm][part < NA ? part : 0]);
@@ -401,9 +417,20 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
             dl = (z / sigma) * (0.5f * (hi - lo)) * (1.0f - t * t);
             zsq = z * z;
             if (q.mean_out) q.mean_out[(long long)m * A + part] = mean;
+            if constexpr (KLP) {
+                const float dd = ls - lso, dm = mean - p_muo_s, em = expm1f(-2.0f * dd);
+                const float qv = (dm * dm) / (sigma * sigma);          // D^2 / sigma^2
+                kl = dd + 0.5f * em + 0.5f * qv;
+                kdu = (dm / (sigma * sigma)) * (0.5f * (hi - lo)) * (1.0f - t * t);
+                kdls = -em - qv;
+            }
         }
 #pragma unroll
         for (int o = 4; o > 0; o >>= 1) lp_n += __shfl_xor(lp_n, o, 64);
+        if constexpr (KLP) {
+#pragma unroll
+            for (int o = 4; o > 0; o >>= 1) kl += __shfl_xor(kl, o, 64);
+        }
         const float lp_o = old_net ? lp_old_s : p_lpo_s;
         const float r = __expf(lp_n - lp_o);
         const float ad = p_adv_s;
@@ -411,7 +438,9 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
         const float s1 = r * ad, s2 = rc * ad;
         const float dr = (s1 <= s2) ? ad : 0.f;           // tf.minimum: gradient to the first argument on ties; the clipped branch has zero slope
         const float coef = -dr * r * q.inv_m;
-        const float d = coef * dl;
+        float d = coef * dl;
+        const float kb = KLP ? q.kl_coef * q.inv_m : 0.f;
+        if constexpr (KLP) d += kb * kdu;
         if (part < NA) sdu[sm][part < NA ? part : 0] = aok ? d : 0.f;
         if (aok) q.du[(long long)m * A + part] = d;
         const float dvv = sv[sm] - p_ret_s;
@@ -429,15 +458,27 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
         __builtin_amdgcn_wave_barrier();
         if (part == 0) {
             sdv[sm] = dvm;
+            if constexpr (KLP) skl[sm] = mok ? kl : 0.f;
             if (mok) { q.dv[m] = dvm; if (q.logp_out) q.logp_out[m] = lp_n; spart[sm][0] = fminf(s1, s2); spart[sm][1] = lv; spart[sm][2] = r; }
         }
-        if (aok) { spart[sm][3 + part] = coef * (zsq - 1.0f); spart[sm][3 + PF_MAX_ACT + part] = mean; }
+        if (aok) {
+            float dls = coef * (zsq - 1.0f);
+            if constexpr (KLP) dls += kb * kdls;
+            spart[sm][3 + part] = dls; spart[sm][3 + PF_MAX_ACT + part] = mean;
+        }
     }
     __syncthreads();
     if (tid < PF_NPART) {                                 // fixed-order block partial sums
         float sum = 0.f;
         for (int i = 0; i < 32; ++i) sum += spart[i][tid];
         q.partial[(long long)blockIdx.x * PF_NPART + tid] = sum;
+    }
+    if constexpr (KLP) {
+        if (tid == 32) {                                  // the block's KL sum, samples in order
+            float sum = 0.f;
+            for (int i = 0; i < 32; ++i) sum += skl[i];
+            q.kl_partial[blockIdx.x] = sum;
+        }
     }
     // ---- head input gradients of this thread's columns of its sample, masked by relu'(h2): from the rows still held in registers ----
     if (mok) {
@@ -476,8 +517,10 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
         }
     }
 }
-template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, false>(q); }
-template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_vclip_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, true>(q); }
+template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, false, false>(q); }
+template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_vclip_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, true, false>(q); }
+template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kl_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, false, true>(q); }
+template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kl_vclip_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, true, true>(q); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // input gradient of layer 2: grid (ceil(H1 / 32), 2 nets, ceil(M / 32)); block = a 32 x 32 tile of
@@ -555,6 +598,8 @@ __global__ __launch_bounds__(256) void ppo_wgrad_kernel(const PpoFusedParams q) 
         // the kernel's duration), lane 0 collects them with shuffles; exp / log through the hardware units (arguments O(1), ~1e-7 relative)
         float col = 0.f;
         if (lane < PF_NPART) for (int b = 0; b < q.n_loss_blocks; ++b) col += q.partial[(long long)b * PF_NPART + lane];
+        else if (lane == PF_NPART && q.kl_on) for (int b = 0; b < q.n_loss_blocks; ++b) col += q.kl_partial[b];      // the KL penalty's block sums, on a lane of their own
+        const float kl_sum = __shfl(col, PF_NPART, 64);
         float sum[PF_NPART];
 #pragma unroll
         for (int k = 0; k < PF_NPART; ++k) sum[k] = __shfl(col, k, 64);
@@ -569,6 +614,10 @@ __global__ __launch_bounds__(256) void ppo_wgrad_kernel(const PpoFusedParams q) 
         L[0] = pl; L[1] = vl; L[2] = el; L[3] = -pl + vl - el; L[4] = sum[2] * q.inv_m;
 #pragma unroll
         for (int a = 0; a < PF_MAX_ACT; ++a) if (a < q.A) { L[5 + a] = sum[3 + PF_MAX_ACT + a] * q.inv_m; L[5 + q.A + a] = sd[a]; }
+        if (q.kl_on) {                                    // [5+2A] mean KL(pi_old || pi), [5+2A+1] beta x that, which the total loss also takes
+            const float klm = kl_sum * q.inv_m, pen = q.kl_coef * klm;
+            L[5 + 2 * q.A] = klm; L[5 + 2 * q.A + 1] = pen; L[3] = (-pl + vl - el) + pen;
+        }
         // the entropy term is state independent: under data parallelism grad_scale = local_M / global_M shares it across the ranks
 #pragma unroll
         for (int a = 0; a < PF_MAX_ACT; ++a) if (a < q.A) pf_emit<FUSE>(q, q.off[6] + a, sum[3 + a] - q.entropy_scale * q.grad_scale, gb);
@@ -716,6 +765,7 @@ __global__ __launch_bounds__(256) void ppo_predict_head_kernel(const PpoFusedPar
             const float sigma = expf(logstd[a]);
             const float z = (q.actions[(long long)m * A + a] - mean) / sigma;
             lp += -0.5f * z * z - (PF_HALF_LOG_2PI + logf(sigma));
+            if (q.mean_old_out) q.mean_old_out[(long long)m * A + a] = mean;      // (mi_ppo_old_policy_cache: the means the KL penalty reads)
         } else {
             if (q.mean_out) q.mean_out[(long long)m * A + a] = mean;
             float act = mean;
@@ -804,6 +854,74 @@ __global__ __launch_bounds__(64) void ppo_update_stats_reduce_kernel(const doubl
     stats[k] = accumulate ? stats[k] + sum : sum;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// exact-KL statistics (mi_ppo_kl_stats_idx): the head of the CURRENT policy on the trunk of net 0, and per sample the closed-form KL(pi_old || pi_theta) of the
+// diagonal Gaussians in double precision from the fp32 means (this pass: the loop, the shuffles and the libm tanhf of ppo_predict_head_kernel<NA, 3>, so that with
+// theta == theta_old the mean is the cached one bit for bit and the KL is 0; old: q.mean_old[row]) and the two log-stds:
+//   KL[m] = sum_a d + expm1(-2 d) / 2 + D^2 / (2 sigma^2) ,  d = ls - lso, D = mu - mu_o, sigma = exp(ls)
+// terms 1, KL, KL^2, sum_a D^2 / (2 sigma^2) (the mean part).  grid ceil(M / 32) blocks; 8 threads per sample, sample m = table row row_idx[m] (clamped).  The
+// reduction is that of ppo_update_stats_head_kernel: xor tree over the wave's 8 samples, the four waves in order, one scratch row per block.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int PF_NKLSTATS = MI_PPO_N_KL_STATS;
+template <int NA>
+__global__ __launch_bounds__(256) void ppo_kl_stats_head_kernel(const PpoFusedParams q, double* __restrict__ scratch) {
+    __shared__ double swave[4][PF_NKLSTATS];
+    const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
+    const int sm = tid >> 3, part = tid & 7, m = m0 + sm, wave = tid >> 6;
+    const float* Wm = q.theta + q.off[4]; const float* bm = q.theta + q.off[5]; const float* logstd = q.theta + q.off[6]; const float* logstd_o = q.theta_old + q.off[6];
+    const float* h2p = q.h2;
+    float au[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) au[a] = 0.f;
+    if (m < q.M) {
+        for (int j = part; j < H2; j += 8) {
+            const float hp = h2p[(long long)m * H2 + j];
+            _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) au[a] += hp * Wm[(long long)j * A + a];
+        }
+    }
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) {
+#pragma unroll
+        for (int a = 0; a < NA; ++a) au[a] += __shfl_xor(au[a], o, 64);
+    }
+    double term[PF_NKLSTATS];
+#pragma unroll
+    for (int k = 0; k < PF_NKLSTATS; ++k) term[k] = 0.0;
+    if (part == 0 && m < q.M) {
+        const long long mr = min(max(q.row_idx[m], 0), q.n_rows - 1);
+        double kl = 0.0, mp = 0.0;
+        _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) {
+            const float lo = q.low[a], hi = q.high[a];
+            const float mean = lo + ((tanhf(au[a] + bm[a]) + 1.0f) * 0.5f) * (hi - lo);
+            const double ls = (double)logstd[a], d = ls - (double)logstd_o[a], dm = (double)mean - (double)q.mean_old[mr * A + a];
+            const double qh = 0.5 * dm * dm * exp(-2.0 * ls);      // D^2 / (2 sigma^2)
+            kl += d + 0.5 * expm1(-2.0 * d) + qh;
+            mp += qh;
+        }
+        term[0] = 1.0; term[1] = kl; term[2] = kl * kl; term[3] = mp;
+    }
+#pragma unroll
+    for (int k = 0; k < PF_NKLSTATS; ++k) {
+#pragma unroll
+        for (int o = 8; o < 64; o <<= 1) term[k] += __shfl_xor(term[k], o, 64);
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < PF_NKLSTATS; ++k) swave[wave][k] = term[k];
+    }
+    __syncthreads();
+    if (tid < PF_NKLSTATS) scratch[(long long)blockIdx.x * PF_NKLSTATS + tid] = ((swave[0][tid] + swave[1][tid]) + swave[2][tid]) + swave[3][tid];
+}
+
+// one wave: lane k adds column k of the block rows in block order, then stores (accumulate 0) or adds to (1) stats[k]
+__global__ __launch_bounds__(64) void ppo_kl_stats_reduce_kernel(const double* __restrict__ scratch, int n_blocks, int accumulate, double* __restrict__ stats) {
+    const int k = threadIdx.x;
+    if (k >= PF_NKLSTATS) return;
+    double sum = 0.0;
+    for (int b = 0; b < n_blocks; ++b) sum += scratch[(long long)b * PF_NKLSTATS + k];
+    stats[k] = accumulate ? stats[k] + sum : sum;
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -858,6 +976,21 @@ int mi_ppo_fused_update_stats(hipStream_t st, PpoFusedParams& q, int accumulate,
     return mi_check_launch("ppo_update_stats");
 }
 
+// exact KL(pi_old || pi_theta) sums of M gathered rows under the current theta (q.row_idx / n_rows / mean_old set by the caller): the policy trunk alone, the
+// statistics head, the ordered sum of its block rows into stats.  Nothing but the activation workspace, scratch and stats is written.
+int mi_ppo_fused_kl_stats(hipStream_t st, PpoFusedParams& q, int accumulate, double* scratch, double* stats, bool x3) {
+    { const int rc0 = pf_check_shape(q, "ppo fused kl stats"); if (rc0 != MI_OK) return rc0; }
+    q.n_nets = 1;                                         // (net 0: the policy)
+    q.s_gath = nullptr;
+    int rc = mi_ppo_fused_trunks(st, q, x3);
+    if (rc != MI_OK) return rc;
+    const int nb = (q.M + 31) / 32;
+    if (q.A <= 2) hipLaunchKernelGGL(ppo_kl_stats_head_kernel<2>, dim3(nb), dim3(256), 0, st, q, scratch);
+    else hipLaunchKernelGGL(ppo_kl_stats_head_kernel<PF_MAX_ACT>, dim3(nb), dim3(256), 0, st, q, scratch);
+    hipLaunchKernelGGL(ppo_kl_stats_reduce_kernel, dim3(1), dim3(64), 0, st, (const double*)scratch, nb, accumulate, stats);
+    return mi_check_launch("ppo_kl_stats");
+}
+
 int mi_ppo_fused_partial_floats(int M) { return ((M + 31) / 32) * PF_NPART; }
 
 // forward only (PPO.predict, the cache of log pi_old): layers 1-2 of `n_nets` nets, then the caller's head kernel; x3: split-bf16 instantiations
@@ -893,12 +1026,21 @@ static inline int ppo_pad(hipStream_t, float*) { return MI_OK; }
 int mi_ppo_fused_step(hipStream_t st, PpoFusedParams& q, int fuse_adam, bool x3) {
     { const int rc0 = pf_check_shape(q, "ppo fused step"); if (rc0 != MI_OK) return rc0; }         // before the first launch
     if (fuse_adam && q.M > 256) return mi_fail(MI_ERR_ARG, "ppo fused step: the in-kernel Adam update needs the whole minibatch in one wave (M <= 256)");
+    if (q.kl_on && (!q.kl_partial || (q.logp_old != nullptr) != (q.mean_old != nullptr)))
+        return mi_fail(MI_ERR_ARG, "ppo fused step: the KL penalty needs its partial buffer, and logp_old / mean_old both or neither");
     q.n_loss_blocks = (q.M + 31) / 32;
     int rc = mi_ppo_fused_trunks(st, q, x3);
     if (rc != MI_OK) return rc;
     rc = ppo_pad(st, q.losses);
     if (rc != MI_OK) return rc;
-    if (q.v_old) {                                        // the clipped value loss (mi_ppo_train_step_vclip): the same kernel body with one more gather per sample
+    if (q.kl_on) {                                        // the KL-penalised surrogate (mi_ppo_train_step_kl), with or without the clipped value loss
+        const dim3 g(q.n_loss_blocks), b(256);
+        if (q.v_old) {
+            if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_kl_vclip_kernel<2>, g, b, 0, st, q);
+            else hipLaunchKernelGGL(ppo_head_loss_kl_vclip_kernel<PF_MAX_ACT>, g, b, 0, st, q);
+        } else if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_kl_kernel<2>, g, b, 0, st, q);
+        else hipLaunchKernelGGL(ppo_head_loss_kl_kernel<PF_MAX_ACT>, g, b, 0, st, q);
+    } else if (q.v_old) {                                 // the clipped value loss (mi_ppo_train_step_vclip): the same kernel body with one more gather per sample
         if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_vclip_kernel<2>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);
         else hipLaunchKernelGGL(ppo_head_loss_vclip_kernel<PF_MAX_ACT>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);
     } else if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_kernel<2>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);     // (action loops are compile-time unrolled)

@@ -30,6 +30,11 @@ struct PpoFusedParams {
     // PPO2-style value clipping (mi_ppo_train_step_vclip; appended, so that no other field moves): the values recorded at collection time, indexed like returns
     // (nullptr: the plain value loss), and the range eps_v > 0 (+inf: never clips)
     const float* v_old; float clip_range_vf;
+    // adaptive KL penalty (mi_ppo_train_step_kl; appended likewise).  kl_on: the penalised head / loss kernel runs (kl_coef >= 0; 0 measures only).  mean_old: the
+    // old policy's action means per table row, indexed like logp_old (nullptr with logp_old == nullptr: formed in the step from net 2).  kl_partial: one float per
+    // loss block, that block's sum of KL[m] (engine workspace).  mean_old_out: where the log pi_old pass of ppo_predict_head_kernel also stores its means
+    // (mi_ppo_old_policy_cache; nullptr: nowhere)
+    int kl_on; float kl_coef; const float* mean_old; float* kl_partial; float* mean_old_out;
 };
 
 }  // namespace mi
@@ -39,7 +44,8 @@ int mi_ppo_fused_trunks(hipStream_t st, const mi::PpoFusedParams& q, bool x3);
 bool mi_ppo_fused_shape_in_range(int A, int H2, int kin);
 int mi_ppo_fused_step(hipStream_t st, mi::PpoFusedParams& q, int fuse_adam, bool x3);      // x3: split-bf16 GEMM stages (MI_BF16X3)
 int mi_ppo_fused_predict(hipStream_t st, mi::PpoFusedParams& q, const float* noise, int greedy, float* action, float* value);
-int mi_ppo_fused_logp_old(hipStream_t st, mi::PpoFusedParams& q, float* out, bool x3);
+int mi_ppo_fused_logp_old(hipStream_t st, mi::PpoFusedParams& q, float* out, bool x3);      // (q.mean_old_out set: the old policy's means as well)
+int mi_ppo_fused_kl_stats(hipStream_t st, mi::PpoFusedParams& q, int accumulate, double* scratch, double* stats, bool x3);
 int mi_ppo_fused_update_stats(hipStream_t st, mi::PpoFusedParams& q, int accumulate, double* scratch, double* stats, float* logp_new_out, float* value_out, bool x3);
 // internal accessors of the two engines for the rollout step (rollout path only)
 int mi_ppo_internal_fill(void* ppo_handle, mi::PpoFusedParams* q, const float* states, int M);

@@ -46,6 +46,25 @@ def value_clip_value(value, who="value_clip"):
     return float(value)
 
 
+def kl_penalty_value(value, who="kl_penalty"):
+    """The coefficient beta of the KL penalty (mi_ppo_train_step_kl): None (off) or a finite float >= 0 (0: the penalised step, nothing added: it measures the KL)
+    -> None or float; bool, str, a negative value, inf or NaN raise ValueError.  No device and no library involved."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not (value >= 0 and value < float("inf")):
+        raise ValueError("%s: the value is None or a finite float >= 0 (0: measure the KL, add nothing), got %r" % (who, value))
+    return float(value)
+
+
+def kl_target_value(value, who="kl_target"):
+    """The target of the adaptive KL penalty: None (beta stays fixed) or a finite float > 0 -> None or float; anything else raises ValueError."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not (value > 0 and value < float("inf")):
+        raise ValueError("%s: the value is None (a fixed coefficient) or a finite float > 0, got %r" % (who, value))
+    return float(value)
+
+
 _CTYPES = {
     "void*": ctypes.c_void_p, "const void*": ctypes.c_void_p,
     "float*": ctypes.c_void_p, "const float*": ctypes.c_void_p,

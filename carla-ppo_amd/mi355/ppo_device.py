@@ -46,6 +46,23 @@ def value_clip_summary(sums):
     return {"value_clip_fraction": float(s[1] / n), "value_loss_clipped": float(s[2] / n), "value_grad_zero_fraction": float(s[3] / n)}
 
 
+N_KL_STATS = 4                                    # MI_PPO_N_KL_STATS of include/mi355_carla.h
+
+
+def kl_stats_summary(sums):
+    """The MI_PPO_N_KL_STATS running sums of mi_ppo_kl_stats_idx (count, sum KL, sum KL^2, sum of the mean part D^2 / (2 sigma^2); KL = the closed-form
+    KL(pi_old || pi_theta) per sample) -> {"samples", "kl", "kl_std", "kl_mean_part"}: the mean KL, its population standard deviation over the samples and the
+    mean of the part the means contribute (the rest, kl - kl_mean_part, is the state-independent log-std part).  Host arithmetic in float64; no GPU involved."""
+    s = np.asarray(sums, np.float64).reshape(-1)
+    if s.shape[0] != N_KL_STATS:
+        raise ValueError("kl_stats_summary: expected %d sums, got %d" % (N_KL_STATS, s.shape[0]))
+    n = float(s[0])
+    if not n > 0:
+        raise ValueError("kl_stats_summary: the sums hold no sample")
+    mean = s[1] / n
+    return {"samples": int(round(n)), "kl": float(mean), "kl_std": float(np.sqrt(max(s[2] / n - mean * mean, 0.0))), "kl_mean_part": float(s[3] / n)}
+
+
 class PpoDevice:
     def __init__(self, input_dim, num_actions, action_low, action_high, clip_eps, value_scale, entropy_scale,
                  hidden=(500, 300), max_batch=256, device=None, precision="fp32"):
@@ -107,6 +124,8 @@ class PpoDevice:
         o = addr - self.workspace.data_ptr()
         # [policy, value, entropy, total, mean prob ratio, mean action_mean[A], std[A]] of the last minibatch step
         self.losses = self.workspace[o:o + 4 * (5 + 2 * self.num_actions)].view(torch.float32)
+        # [mean KL(pi_old || pi), beta x mean KL] of the last train_step_kl: the two floats behind `losses` (no other step writes them)
+        self.kl_losses = self.workspace[o + 4 * (5 + 2 * self.num_actions):o + 4 * (7 + 2 * self.num_actions)].view(torch.float32)
         addr = self.L.mi_ppo_buffer(self.handle, 1)
         o = addr - self.workspace.data_ptr()
         self.action_mean = self.workspace[o:o + 4 * int(max_batch) * self.num_actions].view(torch.float32).view(int(max_batch), self.num_actions)
@@ -234,6 +253,36 @@ class PpoDevice:
         self.L.mi_ppo_train_step_vclip(self.handle, comm_handle, self.stream(), p(states), p(actions), p(returns), p(advantage), p(logp_old), p(old_values),
                                        float(clip_range_vf), p(row_idx), int(states.shape[0]), int(M), float(inv_m), float(grad_scale), 1 if adam else 0,
                                        float(alpha), float(beta1), float(beta2), float(epsilon))
+
+    def old_policy_cache(self, states, actions, M, logp_out, mean_out):
+        """logp_old() that keeps the old policy's action means as well (mi_ppo_old_policy_cache): logp_out [M] (bit for bit logp_old's), mean_out [M, A] -- the two
+        tables train_step_kl and kl_stats read."""
+        self.ensure_batch(M)
+        p = milib.ptr
+        self.L.mi_ppo_old_policy_cache(self.handle, self.stream(), p(states), p(actions), int(M), p(logp_out), p(mean_out))
+
+    def train_step_kl(self, comm_handle, states, actions, returns, advantage, logp_old, mean_old, kl_coef, row_idx, M, inv_m, grad_scale, alpha,
+                      beta1=0.9, beta2=0.999, epsilon=1e-8, adam=True, old_values=None, clip_range_vf=None):
+        """The minibatch step with the KL penalty kl_coef x mean KL(pi_old || pi_theta) added to the clipped surrogate (mi_ppo_train_step_kl; kl_coef a finite float
+        >= 0, 0 measures only).  logp_old / mean_old: the tables old_policy_cache filled, or both None (the step evaluates the old policy itself).  One entry for
+        every form, as train_step_vclip: row_idx None or an int32 device tensor [M] naming rows of the tables; comm_handle None or a communicator; adam False stops
+        with the gradients in the flat buffer; old_values / clip_range_vf: the clipped value loss of train_step_vclip on top.  `kl_losses` holds [mean KL, penalty]."""
+        self.ensure_batch(M)
+        p = milib.ptr
+        self.L.mi_ppo_train_step_kl(self.handle, comm_handle, self.stream(), p(states), p(actions), p(returns), p(advantage), p(logp_old), p(mean_old), float(kl_coef),
+                                    p(old_values), 0.0 if old_values is None else float(clip_range_vf), p(row_idx), int(states.shape[0]), int(M), float(inv_m),
+                                    float(grad_scale), 1 if adam else 0, float(alpha), float(beta1), float(beta2), float(epsilon))
+
+    def kl_stats(self, states, mean_old, row_idx, M, stats, scratch, accumulate=False):
+        """The N_KL_STATS sums of the exact KL(pi_old || pi_theta) (mi_ppo_kl_stats_idx; kl_stats_summary turns them into a dict) over rows `row_idx` (int32 device
+        tensor [M]) of the tables states / mean_old under the CURRENT parameters, into `stats` (float64 device tensor [N_KL_STATS]; accumulate: added to it).
+        scratch: float64 device tensor of kl_stats_scratch_doubles(M) entries.  Forward only: nothing of the training state is written."""
+        self.ensure_batch(M)
+        p = milib.ptr
+        self.L.mi_ppo_kl_stats_idx(self.handle, self.stream(), p(states), p(mean_old), p(row_idx), int(states.shape[0]), int(M), 1 if accumulate else 0, p(scratch), p(stats))
+
+    def kl_stats_scratch_doubles(self, M):
+        return int(self.L.mi_ppo_kl_stats_scratch_doubles(int(M)))
 
     def value_clip_stats(self, values_new, old_values, returns, row_idx, M, clip_range_vf, stats, scratch, accumulate=False):
         """The N_VCLIP_STATS sums of the value-clipping diagnostics (mi_ppo_value_clip_stats; value_clip_summary turns them into a dict) over rows `row_idx` (int32

@@ -32,6 +32,31 @@ def _max_grad_norm_from_env():
         raise ValueError("MI355_PPO_MAX_GRAD_NORM=%r: expected a positive float or inf" % text) from None
 
 
+def _kl_coef_from_env():
+    """MI355_PPO_KL_COEF (unset or empty: off) -> None or a finite float >= 0 (a fixed coefficient, no target); anything else raises ValueError."""
+    text = os.environ.get("MI355_PPO_KL_COEF", "").strip()
+    if not text:
+        return None
+    try:
+        return milib.kl_penalty_value(float(text), "MI355_PPO_KL_COEF=%r" % text)
+    except ValueError:
+        raise ValueError("MI355_PPO_KL_COEF=%r: expected a finite float >= 0" % text) from None
+
+
+def adapted_kl_coef(coef, target, kl):
+    """The PPO paper's rule (Schulman et al. 2017, section 4): kl < target / 1.5 halves the coefficient, kl > 1.5 target doubles it, both comparisons strict;
+    target None leaves it.  kl: the mean KL(pi_old || pi_theta) behind the update's last epoch, finite and >= 0 (else ValueError)."""
+    if isinstance(kl, bool) or not isinstance(kl, (int, float, np.floating, np.integer)) or not (kl >= 0 and kl < float("inf")):
+        raise ValueError("adapt_kl_penalty: kl is a finite float >= 0, got %r" % (kl,))
+    if target is None:
+        return float(coef)
+    if kl < target / 1.5:
+        return float(coef) / 2.0
+    if kl > 1.5 * target:
+        return float(coef) * 2.0
+    return float(coef)
+
+
 def _adam_alpha(lr, b1p, b2p):
     one = np.float32(1.0)
     return np.float32(np.float32(lr) * np.sqrt(one - np.float32(b2p), dtype=np.float32) / (one - np.float32(b1p)))
@@ -54,6 +79,11 @@ class PPO():
         # PPO2-style value-function clipping (set_value_clip): None = off.  No environment knob: only the rollout buffers record the old values a clipped step needs.
         # Not part of a checkpoint.
         self.value_clip = None
+        # adaptive KL penalty (set_kl_penalty): beta x mean KL(pi_old || pi_theta) added to the clipped surrogate; None = off.  MI355_PPO_KL_COEF supplies a fixed beta
+        # when set_kl_penalty is not called.  kl_target: None (beta fixed) or the KL the rollout buffers steer beta towards.  Not part of a checkpoint's state_dict():
+        # kl_penalty_state() / load_kl_penalty_state() carry it.
+        self.kl_penalty = _kl_coef_from_env()
+        self.kl_target = None
         self.input_dim = int(np.asarray(input_shape).reshape(-1)[0])
         self.num_actions = int(action_space.shape[0])
         self.action_low = np.asarray(action_space.low, np.float32).reshape(-1)
@@ -128,6 +158,56 @@ class PPO():
         to run while it is set."""
         self.value_clip = milib.value_clip_value(value, "PPO.set_value_clip")
 
+    def set_kl_penalty(self, coef, target=None):
+        """Add the KL penalty of the PPO paper (section 4) to the clipped surrogate: loss += coef x mean_m KL(pi_old || pi_theta)[m], the closed form for this
+        diagonal Gaussian policy (include/mi355_carla.h, mi_ppo_train_step_kl); the clip stays as configured.  coef None switches it off (the default), a finite float
+        >= 0 switches it on (0: the penalised step that only measures the KL).  target None keeps coef fixed; a finite float > 0 lets the rollout buffers' update()
+        adapt it after every update (adapt_kl_penalty).  Usable before or after init_session(); bool, str, NaN, inf or a negative value raise ValueError before
+        anything touches a device."""
+        coef = milib.kl_penalty_value(coef, "PPO.set_kl_penalty")
+        target = milib.kl_target_value(target, "PPO.set_kl_penalty: target")
+        if coef is None and target is not None:
+            raise ValueError("PPO.set_kl_penalty: a target without a coefficient")
+        self.kl_penalty, self.kl_target = coef, target
+
+    def adapt_kl_penalty(self, kl):
+        """The paper's rule on the mean KL behind an update's last epoch: kl < target / 1.5 halves beta, kl > 1.5 target doubles it (both strict), else -- or with no
+        target -- beta stays.  -> the new beta.  A kl that is not finite or is negative raises ValueError and leaves beta unchanged."""
+        if self.kl_penalty is None:
+            raise ValueError("PPO.adapt_kl_penalty: the KL penalty is off (set_kl_penalty)")
+        self.kl_penalty = adapted_kl_coef(self.kl_penalty, self.kl_target, kl)
+        return self.kl_penalty
+
+    def kl_penalty_state(self):
+        """{"kl_coef", "kl_target"}: what load_kl_penalty_state restores (beta moves with every adapted update; it is not part of state_dict())."""
+        return {"kl_coef": self.kl_penalty, "kl_target": self.kl_target}
+
+    def load_kl_penalty_state(self, d):
+        if set(d) != {"kl_coef", "kl_target"}:
+            raise ValueError("PPO.load_kl_penalty_state: expected the keys kl_coef and kl_target, got %s" % sorted(d))
+        self.set_kl_penalty(d["kl_coef"], d["kl_target"])
+
+    def _kl_step(self, s, a, r, adv, logp_old, mean_old, rows, m_local, m_global, old_values=None):
+        """One SGD step through mi_ppo_train_step_kl (the penalty is on): contiguous tensors (rows None) or table rows `rows` (int32 device tensor) of the
+        horizon-batch tables; mean_old: the old policy's means, indexed like logp_old (None: the cached log pi_old is dropped and the step evaluates the old policy
+        itself -- correct, slower); with old_values also the clipped value loss (self.value_clip)."""
+        dev = self.dev
+        if old_values is not None and self.value_clip is None:
+            raise ValueError("PPO._kl_step: old values were passed but value clipping is off (set_value_clip)")
+        one_call = os.environ.get("MI355_PPO_FUSED", "1") != "0" and (rows is None or os.environ.get("MI355_PPO_IDX", "1") != "0") and dev.fused_ok()
+        comm = None if midist.world_size() == 1 else self._dp_comm()
+        if not one_call or (midist.world_size() > 1 and comm is None):
+            raise ValueError("PPO: the KL penalty needs the fused one-call step (this policy's shape is outside the fused kernels' range, "
+                             "MI355_PPO_FUSED=0 / MI355_PPO_IDX=0, or data parallel without the library's communicator)")
+        if mean_old is None:                                   # no table of old means (replay.py): the step evaluates the old policy itself -- correct, slower
+            logp_old = None
+        alpha = _adam_alpha(self.current_learning_rate(), self.beta1_power, self.beta2_power)
+        dev.train_step_kl(None if comm is None else comm.handle, s, a, r, adv, logp_old, mean_old, self.kl_penalty, rows, m_local, 1.0 / m_global,
+                          m_local / float(m_global), alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON, old_values=old_values,
+                          clip_range_vf=None if old_values is None else self.value_clip)
+        self.beta1_power = np.float32(self.beta1_power * np.float32(ADAM_BETA1))
+        self.beta2_power = np.float32(self.beta2_power * np.float32(ADAM_BETA2))
+
     def last_grad_norm(self):
         """{"grad_norm", "clip_scale"} of the last step that formed a norm (one readback); zeros before the first one."""
         g = self._need_dev().grad_clip.cpu().numpy()
@@ -192,10 +272,13 @@ class PPO():
         a = np.ascontiguousarray(np.asarray(a, np.float32).reshape(shape))      # f64 -> f32 at the feed (ppo.py:108-109)
         return torch.from_numpy(a).to(self.dev.device)
 
-    def _step_resident(self, s, a, r, adv, m_local, m_global, logp_old=None):
+    def _step_resident(self, s, a, r, adv, m_local, m_global, logp_old=None, mean_old=None):
         """One SGD step on device-resident minibatch tensors.  Single rank: one C call (fused forward / losses / backward / Adam, five launches);
-        data parallel: gradients, all-reduce, Adam.  logp_old: cached log pi_old(a|s) of these samples (PpoDevice.logp_old), optional."""
+        data parallel: gradients, all-reduce, Adam.  logp_old: cached log pi_old(a|s) of these samples (PpoDevice.logp_old), optional.  mean_old: the old policy's
+        means of these samples (PpoDevice.old_policy_cache), read with the KL penalty on; without it the penalised step evaluates the old policy itself."""
         dev = self.dev
+        if self.kl_penalty is not None:
+            return self._kl_step(s, a, r, adv, logp_old, mean_old, None, m_local, m_global)
         alpha = _adam_alpha(self.current_learning_rate(), self.beta1_power, self.beta2_power)
         comm = self._dp_comm()
         if midist.world_size() == 1 and os.environ.get("MI355_PPO_FUSED", "1") != "0":
@@ -225,11 +308,16 @@ class PPO():
     def _step_rows(self, s_all, a_all, r_all, adv_all, logp_old_all, rows, m_local, m_global, old_values_all=None):
         """One SGD step on rows `rows` (int32 device tensor) of device-resident horizon-batch tables: the minibatch gather of train.py:199-204 runs inside
         the step's kernels (single rank, fused kernels); otherwise the rows are gathered here and _step_resident takes over.  old_values_all: the table of the values
-        recorded at collection time -- the step clips the value loss with self.value_clip (mi_ppo_train_step_vclip), which only the one-call forms can."""
+        recorded at collection time -- the step clips the value loss with self.value_clip (mi_ppo_train_step_vclip), which only the one-call forms can.  With the KL
+        penalty on (set_kl_penalty) the step goes through _kl_step."""
         dev = self.dev
+        if old_values_all is not None and self.value_clip is None:
+            raise ValueError("PPO._step_rows: old values were passed but value clipping is off (set_value_clip)")
+        if self.kl_penalty is not None:
+            # this entry carries no table of the old policy's means (the rollout buffers pass theirs to _kl_step): the cached log pi_old is dropped and the penalised
+            # step evaluates the old policy itself
+            return self._kl_step(s_all, a_all, r_all, adv_all, logp_old_all, None, rows, m_local, m_global, old_values=old_values_all)
         if old_values_all is not None:
-            if self.value_clip is None:
-                raise ValueError("PPO._step_rows: old values were passed but value clipping is off (set_value_clip)")
             one_call = os.environ.get("MI355_PPO_FUSED", "1") != "0" and os.environ.get("MI355_PPO_IDX", "1") != "0" and dev.fused_ok()
             comm = None if midist.world_size() == 1 else self._dp_comm()
             if not one_call or (midist.world_size() > 1 and comm is None):
@@ -291,6 +379,10 @@ class PPO():
             self._metric_sums["train/returns"] = self._metric_sums.get("train/returns", 0.0) + float(np.mean(returns))
             self._metric_sums["train/advantage"] = self._metric_sums.get("train/advantage", 0.0) + float(np.mean(advantage))
             self._metric_sums["train/learning_rate"] = self._metric_sums.get("train/learning_rate", 0.0) + float(self.current_learning_rate())
+            if self.kl_penalty is not None:
+                K = self._local_kl_losses()
+                for k, v in (("train/kl", K[0]), ("train_loss/kl_penalty", K[1]), ("train/kl_coef", self.kl_penalty)):
+                    self._metric_sums[k] = self._metric_sums.get(k, 0.0) + float(v)
             if self.max_grad_norm is not None:
                 g = self.last_grad_norm()
                 self._metric_sums["train/grad_norm"] = self._metric_sums.get("train/grad_norm", 0.0) + g["grad_norm"]
@@ -309,7 +401,20 @@ class PPO():
             L[[0, 1, 4]] *= w
             L[5:5 + A] *= w
             L[3] = -L[0] + L[1] - L[2]
+            if self.kl_penalty is not None:
+                L[3] += self._local_kl_losses()[1]
         return L
+
+    def _local_kl_losses(self):
+        """[mean KL, penalty] of the last penalised step from THIS rank's rows: per-sample means like the policy / value terms (times the world size)."""
+        return self.dev.kl_losses.clone().cpu().numpy() * midist.world_size()
+
+    def _global_kl_losses(self):
+        """[mean KL, penalty] of the last penalised step; data parallel: summed over the ranks like the other per-sample means (COLLECTIVE)."""
+        K = self.dev.kl_losses.clone()
+        if midist.world_size() > 1:
+            midist.all_reduce_sum(K)
+        return K.cpu().numpy()
 
     def _global_losses(self):
         """The five loss scalars of the last step as numpy.  Data parallel: the device holds this rank's share of the batch means (sums over
@@ -322,6 +427,8 @@ class PPO():
             midist.all_reduce_sum(L)
             L[[2] + list(range(5 + A, 5 + 2 * A))] = keep
             L[3] = -L[0] + L[1] - L[2]
+            if self.kl_penalty is not None:
+                L[3] += float(self._global_kl_losses()[1])
         return L.cpu().numpy()
 
     learn = train                                              # north-star alias
@@ -330,7 +437,11 @@ class PPO():
         """train() that also returns the five loss scalars {policy, value, entropy, loss, prob_ratio} (for parity tests/benchmarks)."""
         self.train(input_states, taken_actions, returns, advantage)
         L = self._global_losses()
-        return dict(policy_loss=float(L[0]), value_loss=float(L[1]), entropy_loss=float(L[2]), loss=float(L[3]), prob_ratio=float(L[4]))
+        out = dict(policy_loss=float(L[0]), value_loss=float(L[1]), entropy_loss=float(L[2]), loss=float(L[3]), prob_ratio=float(L[4]))
+        if self.kl_penalty is not None:
+            K = self._global_kl_losses()
+            out["kl"], out["kl_penalty"] = float(K[0]), float(K[1])
+        return out
 
     def update_old_policy(self):
         self._need_dev().update_old()

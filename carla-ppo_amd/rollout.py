@@ -186,6 +186,21 @@ ValueError behind that launch (the SGD steps of that update have run by then; th
 single-frame entry, has no normalised form (ValueError: use BatchedRolloutStep(num_envs=1)).  `stage_times` gains "observation_stats".  With the setting off none of
 these keys appears, no table is allocated and every call makes the launches it always made.
 
+Adaptive KL penalty (the PPO paper's other objective, section 4; no setter here: the buffers read ppo.kl_penalty / ppo.kl_target as they read ppo.value_clip):
+
+    ppo.set_kl_penalty(0.2, target=0.01)                           # beta x mean KL(pi_old || pi_theta) added to the clipped surrogate; target None: beta stays fixed
+    out = buf.update(num_epochs=3, batch_size=32)
+    out["kl"], out["kl_coef"], out["kl_coef_next"], out["kl_adapted"]
+
+With it on, the pass that caches log pi_old also fills `mean_old` [n_table_rows, A] (mi_ppo_old_policy_cache), every SGD step goes through mi_ppo_train_step_kl
+(together with the recorded values when value clipping is on as well) and its record in `losses` gains `kl` / `kl_penalty`; behind the last epoch one forward-only pass
+(mi_ppo_kl_stats_idx over valid_rows() in chunks of 4096, one readback; `stage_times` gains "kl_stats") measures the exact KL under the parameters the update ended
+with -- `kl` = {"samples", "kl", "kl_std", "kl_mean_part"} -- and PPO.adapt_kl_penalty applies the paper's rule on the host: kl < target / 1.5 halves beta, kl >
+1.5 target doubles it, both strict.  `kl_coef` is the beta this update used, `kl_coef_next` the one the next will; `kl_adapted` is False when there is no target or the
+measured KL is not finite (beta then stays, nothing is raised).  All of it comes before the observation-statistics launch.  beta and the target are not part of
+ppo.state_dict(): ppo.kl_penalty_state() / load_kl_penalty_state() carry them.  With the setting off none of these keys appears, no table is allocated and not one
+launch or readback is added.
+
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import contextlib
@@ -811,6 +826,7 @@ class RolloutBuffer:
         self._values_new = None                                                      # V per table row under the current parameters, allocated by the first statistics pass with value clipping on
         self._obs_norm = None                                                        # running observation normalisation (set_observation_normalization): None = off
         self.raw_states = None                                                       # its fp32 table of the raw rows, allocated when the setting is turned on
+        self.mean_old = None                                                         # the old policy's action means per table row, allocated by the first update with the KL penalty on (PPO.set_kl_penalty)
 
     def set_observation_normalization(self, clip=10.0, epsilon=1e-8, frozen=False, normalize_latents=True):
         """Turns running observation normalisation on (see the module docstring): step(), bootstrap() and truncate() feed the trunks clamp((s - mean) * inv_std, +-clip)
@@ -1039,14 +1055,15 @@ class RolloutBuffer:
         [E, T] or None): what the reward scaling pass in front of the finish call takes, read only with the setting on."""
         import torch
         vclip = getattr(self.ppo, "value_clip", None)                                # PPO2-style value clipping (PPO.set_value_clip): None = off
-        recorded = self._check_update(num_epochs, batch_size, vclip, diag)
+        klp = getattr(self.ppo, "kl_penalty", None)                                  # adaptive KL penalty (PPO.set_kl_penalty): None = off
+        recorded = self._check_update(num_epochs, batch_size, vclip, diag, klp)
         rs = self._reward_scaling                                                    # running-return reward scaling (set_reward_scaling): None = off
         mbn = getattr(self, "_minibatch_norm", None)                                 # per-minibatch advantage normalisation (set_minibatch_normalization): None = off
         on = getattr(self, "_obs_norm", None)                                        # running observation normalisation (set_observation_normalization): None = off
         E, T, device = self.num_envs, self.horizon, self.device
         valid = self.rows.valid_rows()
         # this update: what its stages share, and what they leave for the result
-        u = types.SimpleNamespace(batch_size=int(batch_size), num_epochs=int(num_epochs), vclip=vclip, diag=diag, mbn=mbn, valid=valid, n_valid=int(valid.shape[0]),
+        u = types.SimpleNamespace(batch_size=int(batch_size), num_epochs=int(num_epochs), vclip=vclip, klp=klp, diag=diag, mbn=mbn, valid=valid, n_valid=int(valid.shape[0]),
                                   lengths=self.rows.lengths.copy(), recorded=recorded, clock=_StageClock(stage_times, device),
                                   st=torch.cuda.current_stream(device).cuda_stream)
         r = torch.from_numpy(self.rows.rewards).to(device)
@@ -1058,10 +1075,12 @@ class RolloutBuffer:
         finish(u.st, r, d, u.lengths, u.f64)
         u.clock.lap("finish")
         self.ppo.update_old_policy()
-        logp_old = self._cache_logp_old(valid)
+        logp_old = self._cache_logp_old(valid, klp is not None)
         u.clock.lap("logp_old")
         self._run_epochs(u, logp_old)
         out = self._result(u)
+        if klp is not None:
+            self._kl_penalty_result(u, out)
         if mbn is not None:
             self._minibatch_norm_result(u, out)
         if rs is not None:
@@ -1070,7 +1089,7 @@ class RolloutBuffer:
             self._observation_stats(u, on, out)
         return out
 
-    def _check_update(self, num_epochs, batch_size, vclip, diag):
+    def _check_update(self, num_epochs, batch_size, vclip, diag, klp=None):
         """Every refusal of an update, before anything is launched or changed -> the slots that hold a recorded step, bool [num_envs, horizon]."""
         from mi355 import dist as midist
         who = type(self).__name__
@@ -1080,6 +1099,9 @@ class RolloutBuffer:
             raise ValueError(who + ".update: batch_size >= 1, num_epochs >= 0")
         if vclip is not None and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update: value clipping (PPO.set_value_clip) exists only in the fused kernels (this policy's shape is outside their range or "
+                             "MI355_PPO_FUSED=0)")
+        if klp is not None and not self.ppo._need_dev().fused_ok():
+            raise ValueError(who + ".update: the KL penalty (PPO.set_kl_penalty) exists only in the fused kernels (this policy's shape is outside their range or "
                              "MI355_PPO_FUSED=0)")
         if diag is not None and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update_with_diagnostics: the statistics pass reads the cached log pi_old, which only the fused kernels fill "
@@ -1111,16 +1133,23 @@ class RolloutBuffer:
         out["reward_clip_fraction"] = float((np.abs(scaled[1][u.recorded]) == rs["clip"]).mean())
         out["return_carry"] = rs["carry"].cpu().numpy()
 
-    def _cache_logp_old(self, valid):
+    def _cache_logp_old(self, valid, with_means=False):
         """theta_old is fixed for the whole update: log pi_old(a | s) once per table row, in chunks of 4096 rows that hold a recorded step (slots that hold none are
-        computed along and never read: the tables start as zeros).  -> the table, or None without the fused kernels."""
+        computed along and never read: the tables start as zeros).  -> the table, or None without the fused kernels.  with_means (the KL penalty is on): the same
+        pass also fills the table `mean_old` [n_table_rows, A] with the old policy's action means (mi_ppo_old_policy_cache)."""
         pdev = self.ppo._need_dev()
         if not pdev.fused_ok():
             return None
+        if with_means and self.mean_old is None:
+            import torch
+            self.mean_old = torch.zeros(self.n_table_rows, int(self.ppo.num_actions), device=self.device)
         for lo in range(0, self.n_table_rows, 4096):
             hi = min(lo + 4096, self.n_table_rows)
             if np.any((valid >= lo) & (valid < hi)):
-                pdev.logp_old(self.states[lo:hi], self.actions[lo:hi], hi - lo, self.logp_old[lo:hi])
+                if with_means:
+                    pdev.old_policy_cache(self.states[lo:hi], self.actions[lo:hi], hi - lo, self.logp_old[lo:hi], self.mean_old[lo:hi])
+                else:
+                    pdev.logp_old(self.states[lo:hi], self.actions[lo:hi], hi - lo, self.logp_old[lo:hi])
         return self.logp_old
 
     def _run_epochs(self, u, logp_old):
@@ -1130,6 +1159,8 @@ class RolloutBuffer:
         import torch
         ppo, pdev, device, n_valid, batch_size = self.ppo, self.ppo._need_dev(), self.device, u.n_valid, u.batch_size
         step_kw = {} if u.vclip is None else {"old_values_all": self.values}         # the values recorded at collection time: the table the finish call read
+        if u.klp is not None:                                                        # the KL penalty: every step's [mean KL, penalty] is kept as well
+            u.kl_coef, u.kl_records = ppo.kl_penalty, []
         clip = ppo.max_grad_norm is not None                                         # global-norm clipping on: every step's {norm, scale, c, 0} is kept as well
         records, clips = [], []
         u.records, u.clips, u.epoch_first, u.epochs, u.stopped, u.mb_epochs = records, clips, [0], [], False, 0
@@ -1152,9 +1183,14 @@ class RolloutBuffer:
             for i in range(0, n_valid, batch_size):
                 mb = perm[i:i + batch_size]                                          # the last one may be partial (train.py:199-201)
                 m = int(mb.numel())
-                ppo._step_rows(self.states, self.actions, self.returns, adv_table, logp_old, mb, m, m, **step_kw)
+                if u.klp is not None:                                                # (the penalised step reads the old policy's means next to its log-probabilities)
+                    ppo._kl_step(self.states, self.actions, self.returns, adv_table, logp_old, self.mean_old, mb, m, m, old_values=step_kw.get("old_values_all"))
+                else:
+                    ppo._step_rows(self.states, self.actions, self.returns, adv_table, logp_old, mb, m, m, **step_kw)
                 ppo.train_step_counter += 1
                 records.append(pdev.losses.clone())
+                if u.klp is not None:
+                    u.kl_records.append(pdev.kl_losses.clone())
                 if clip:
                     clips.append(pdev.grad_clip.clone())
             if observe is not None:                                                  # observe the epoch: all valid rows under the parameters it ended with
@@ -1165,6 +1201,28 @@ class RolloutBuffer:
                 if u.diag["target_kl"] is not None and u.epochs[-1]["approx_kl"] > u.diag["target_kl"]:
                     u.stopped = True
                     break
+
+    def _kl_penalty_result(self, u, out):
+        """Behind the last epoch: the exact KL(pi_old || pi_theta) over all valid rows under the parameters the update ended with (mi_ppo_kl_stats_idx in the 4096-row
+        chunks of the diagnostics pass, one readback), then the coefficient's adaptation on the host (PPO.adapt_kl_penalty)."""
+        import torch
+        from mi355.ppo_device import N_KL_STATS, kl_stats_summary
+        pdev, device, chunk = self.ppo._need_dev(), self.device, 4096
+        with u.clock.stage("kl_stats"):
+            valid_dev = torch.from_numpy(u.valid).to(device)
+            sums = torch.zeros(N_KL_STATS, dtype=torch.float64, device=device)
+            scratch = torch.empty(pdev.kl_stats_scratch_doubles(min(u.n_valid, chunk)), dtype=torch.float64, device=device)
+            for lo in range(0, u.n_valid, chunk):
+                rows = valid_dev[lo:lo + chunk]
+                pdev.kl_stats(self.states, self.mean_old, rows, int(rows.numel()), sums, scratch, accumulate=lo > 0)
+            kl = kl_stats_summary(sums.cpu().numpy())                                # the one readback
+            kls = torch.stack(u.kl_records).cpu().numpy() if u.kl_records else np.zeros((0, 2), np.float32)
+        for rec, row in zip(out["losses"], kls):
+            rec["kl"], rec["kl_penalty"] = float(row[0]), float(row[1])
+        out["kl"], out["kl_coef"] = kl, float(u.kl_coef)
+        adapt = self.ppo.kl_target is not None and bool(np.isfinite(kl["kl"])) and kl["kl"] >= 0
+        out["kl_coef_next"] = float(self.ppo.adapt_kl_penalty(kl["kl"])) if adapt else float(self.ppo.kl_penalty)
+        out["kl_adapted"] = bool(adapt)
 
     def _minibatch_norm_result(self, u, out):
         E, T = self.num_envs, self.horizon                                           # one readback behind the last epoch; only the epochs that ran

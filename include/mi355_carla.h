@@ -647,6 +647,42 @@ int mi_ppo_grad_norm(void* h, void* stream, float max_norm);
 int mi_ppo_train_step_vclip(void* h, void* comm, void* stream, const float* states, const float* actions, const float* returns, const float* advantage, const float* logp_old, const float* old_values, float clip_range_vf, const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon);
 long long mi_ppo_value_clip_stats_scratch_doubles(int M);
 int mi_ppo_value_clip_stats(void* stream, const float* values_new, const float* old_values, const float* returns, const int* row_idx, int n_rows, int M, float clip_range_vf, int accumulate, double* scratch, double* stats);
+/* adaptive KL penalty: the other objective of the PPO paper (Schulman et al. 2017, section 4), the KL-penalised surrogate, ADDED to the clipped surrogate (the clip
+ * stays as configured; RLlib runs both by default).  Direction: KL(pi_old || pi_theta), as in the paper.  For the diagonal Gaussian policy it is a closed form of the
+ * means and log-stds, so it enters the loss exactly.  Per sample m and action a, with ls / lso the current / old action_logstd, mu / mu_o the current / old action
+ * means (after the low + (tanh(u) + 1) / 2 (high - low) map), d = ls - lso, D = mu - mu_o, sigma = exp(ls):
+ *   KL[m,a]  = d + expm1(-2 d) / 2 + D^2 / (2 sigma^2)        (= ls - lso + (sigma_o^2 + D^2) / (2 sigma^2) - 1/2, spelled without the cancellation)
+ *   KL[m]    = sum_a KL[m,a]
+ *   loss     = -policy_loss + value_loss - entropy_loss + beta * mean_m KL[m]
+ *   dKL/dmu  = D / sigma^2                   -> du[m,a]    += beta * inv_m * (D / sigma^2) * (high - low) / 2 * (1 - t^2)
+ *   dKL/dls  = -expm1(-2 d) - D^2 / sigma^2  -> dlogstd[a] += beta * inv_m * sum_m (...)
+ * The value side and the entropy term are untouched.  The ls part is state independent but is summed per sample with inv_m = 1 / M_global, so under data parallelism
+ * it needs no grad_scale (unlike the entropy term).  beta = kl_coef, a finite float >= 0; 0 runs the penalised kernel as measure-only (the KL slot is filled, nothing
+ * is added: parameters, optimiser state and the five loss scalars are those of the unpenalised step).  The losses buffer (mi_ppo_buffer(h, 0)) gains two floats
+ * behind the 5 + 2 A defined above: [5 + 2 A] mean_m KL[m] and [5 + 2 A + 1] beta times that, which losses[3] (total) also takes.  Only this entry writes them.
+ * mi_ppo_old_policy_cache: mi_ppo_logp_old that keeps the old policy's means -- logp_out [M] (bit for bit what mi_ppo_logp_old gives) and mean_out [M, A].
+ * mi_ppo_train_step_kl: ONE entry for every form, as mi_ppo_train_step_vclip: row_idx NULL (contiguous minibatch tensors, n_rows ignored) or the in-kernel gather
+ * from tables of n_rows rows (mean_old [n_rows, A] and logp_old among them; rows clamped; mu_o is one more 4-byte gather per (sample, action) in the head / loss
+ * kernel, rows that row_idx does not name are not read); comm NULL or a communicator (one all-reduce in front of Adam); adam 0 (the gradients stay in the flat
+ * buffer) or 1 (Adam inside the gradient kernels for M <= 256 with no communicator and mi_ppo_set_max_grad_norm off, else the flat buffer and mi_ppo_apply_adam).
+ * logp_old and mean_old are both NULL (the step evaluates the old policy itself, and forms mu_o as the cache does: the same step either way) or both given.
+ * old_values NULL: the plain value loss; else the value term is clipped with clip_range_vf exactly as mi_ppo_train_step_vclip does.  The same launches as the
+ * unpenalised step, a fixed summation order, no atomics, both precision modes.  MI_ERR_STATE: null handle; MI_ERR_ARG: M outside [1, max_batch], row_idx set with
+ * n_rows < 1, one of logp_old / mean_old without the other, kl_coef negative, NaN or infinite, old_values with clip_range_vf not > 0, adam not 0 / 1; MI_ERR_SHAPE:
+ * mi_ppo_fused_shape_ok(h) is 0 (there is no per-layer form; nothing is written).
+ * mi_ppo_kl_stats_idx: the exact KL of M rows row_idx[m] (int32, device; clamped into [0, n_rows)) of the tables states / mean_old under the CURRENT theta --
+ * forward only (the policy trunk in the engine's precision mode, one head kernel, one ordered reduction).  The means are fp32 (this pass: the arithmetic of
+ * mi_ppo_old_policy_cache, so theta == theta_old gives KL = 0 exactly), the KL per sample is formed in double from them and the two log-stds.  stats
+ * [MI_PPO_N_KL_STATS] (double, device) receives the sums of
+ *   [0] 1 (the count)   [1] KL[m]   [2] KL[m]^2   [3] sum_a D^2 / (2 sigma^2) (the mean part of the KL)
+ * Ordered like mi_ppo_update_stats_idx: a scratch row per block of 32 samples (mi_ppo_kl_stats_scratch_doubles(M) doubles), one wave adds them in block order; two
+ * runs are bitwise equal; accumulate 0 / 1 as there.  NOT modified: parameters, theta_old, optimiser state, gradient buffer, the losses and action_mean buffers.
+ * MI_ERR_ARG: M outside [1, max_batch], n_rows < 1, a missing buffer, accumulate not 0 / 1; MI_ERR_SHAPE: mi_ppo_fused_shape_ok(h) is 0. */
+#define MI_PPO_N_KL_STATS 4
+int mi_ppo_old_policy_cache(void* h, void* stream, const float* states, const float* actions, int M, float* logp_out, float* mean_out);
+int mi_ppo_train_step_kl(void* h, void* comm, void* stream, const float* states, const float* actions, const float* returns, const float* advantage, const float* logp_old, const float* mean_old, float kl_coef, const float* old_values, float clip_range_vf, const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon);
+long long mi_ppo_kl_stats_scratch_doubles(int M);
+int mi_ppo_kl_stats_idx(void* h, void* stream, const float* states, const float* mean_old, const int* row_idx, int n_rows, int M, int accumulate, double* scratch, double* stats);
 /* advantages normalised PER MINIBATCH, inside the SGD loop — SB3's normalize_advantage, CleanRL's norm_adv; no reference counterpart in train.py, which normalises per
  * trajectory (train.py:176-177): one pass per epoch between the finish calls (mi_rollout_finish*, which leave the raw advantages in fp64) and the epoch's SGD steps, which
  * gather their advantage from an fp32 table by row index.  No engine handle.  adv_raw: fp64 [num_envs, T], the raw advantages (entries beyond a lane's length may hold
