@@ -125,6 +125,37 @@ void fill_fused(const PpoEngine* e, PpoFusedParams& q, const float* states, int 
     q.clip_eps = d.clip_eps; q.value_scale = d.value_scale; q.entropy_scale = d.entropy_scale;
 }
 
+// One minibatch step of the fused kernels, described ONCE for the six entries below (mi_ppo_forward_backward's fused branch, mi_ppo_train_step[_idx|_dp|_vclip|_kl]):
+// what they put into PpoFusedParams behind fill_fused.  logp_old NULL: the step evaluates the old policy itself (three networks); row_idx given: states / actions /
+// returns / advantage / logp_old (/ old_values / mean_old) are tables of n_rows rows gathered in-kernel; old_values given: the clipped value loss; kl: the KL penalty.
+void fill_step(PpoEngine* e, PpoFusedParams& q, const float* states, const float* actions, const float* returns, const float* advantage, const float* logp_old,
+               const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, const float* old_values = nullptr, float clip_range_vf = 0.f,
+               bool kl = false, float kl_coef = 0.f, const float* mean_old = nullptr) {
+    fill_fused(e, q, states, M);
+    q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
+    q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
+    if (row_idx) { q.row_idx = row_idx; q.n_rows = n_rows; q.s_gath = (float*)e->at(e->s_pad); }
+    if (old_values) { q.v_old = old_values; q.clip_range_vf = clip_range_vf; }
+    if (kl) { q.kl_on = 1; q.kl_coef = kl_coef; q.mean_old = mean_old; }
+    e->last_M = M;
+}
+
+// ... and the ONE route rule.  In-tile Adam (five launches, the optimiser update applied by the blocks that produce each gradient tile: no gradient buffer is written)
+// iff the optimiser is wanted, there is no communicator, M <= 256 and clipping by the global norm is off.  Else the same five-kernel chain writes (not accumulates) the
+// gradients into the flat buffer and the rest follows as launches of its own: clipping by the global norm needs the whole gradient at one moment, a communicator sums
+// the buffer over the ranks, and large minibatches (the synthetic replay: 2048 rows per GPU) split the weight-gradient launch into row chunks of 256 whose partial sums
+// are added in a fixed order (round 4: no atomics).  adam == 0 stops with the gradients in the buffer.
+int route_step(PpoEngine* e, void* stream, PpoFusedParams& q, void* comm, int adam, float alpha, float beta1, float beta2, float epsilon) {
+    if (adam && !comm && q.M <= 256 && !clipping(e)) {
+        q.alpha = alpha; q.omb1 = 1.0f - beta1; q.omb2 = 1.0f - beta2; q.epsilon = epsilon;
+        return mi_ppo_fused_step((hipStream_t)stream, q, 1, x3(e));
+    }
+    CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));
+    if (!adam) return MI_OK;
+    if (comm) CK(mi_allreduce_sum_f32(comm, stream, e->grads, e->total));
+    return mi_ppo_apply_adam(e, stream, alpha, beta1, beta2, epsilon);
+}
+
 int policy_fwd(PpoEngine* e, void* st, const float* prm, const long long* off, int M, void* h1, void* h2, void* u) {
     const MiPpoDesc& d = e->d;
     CK(mi_gemm_bias_act(st, MI_F32, e->at(e->s_pad), M, e->kin, prm + off[0], 0, d.h1, prm + off[1], 1, nullptr, h1, 1, 1));
@@ -248,10 +279,8 @@ int mi_ppo_forward_backward(void* h, void* stream, const float* states, const fl
     if (M < 1 || M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_forward_backward: batch outside [1, max_batch]");
     if (!e->grads) return mi_fail(MI_ERR_STATE, "mi_ppo_forward_backward: engine created without a gradient buffer");
     if (fused_enabled(e)) {                                // 5 launches; gradients written (not accumulated) into the flat buffer (M > 256: the row chunks' partial sums are added in a fixed order, round 4)
-        PpoFusedParams q; fill_fused(e, q, states, M);
-        q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
-        e->last_M = M;
-        return mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e));
+        PpoFusedParams q; fill_step(e, q, states, actions, returns, advantage, nullptr, nullptr, 0, M, inv_m, grad_scale);
+        return route_step(e, stream, q, nullptr, 0, 0.f, 0.f, 0.f, 0.f);
     }
     if (x3(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_forward_backward: the split-bf16 mode needs the fused kernels (no per-layer form of it)");
     const MiPpoDesc& d = e->d;
@@ -319,26 +348,12 @@ int mi_ppo_train_step(void* h, void* stream, const float* states, const float* a
     if (!e) return mi_fail(MI_ERR_STATE, "ppo engine: null handle");
     if (M < 1 || M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step: batch outside [1, max_batch]");
     if (!e->grads || !e->m || !e->v) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step: engine created without optimiser buffers");
-    if (M > 256 || !fused_enabled(e) || clipping(e)) {
-        // clipping by the global norm needs the whole gradient at one moment: the route of the large minibatches, for every M
-        // large minibatches (the synthetic replay: 2048 rows per GPU): the weight-gradient launch splits the rows into chunks of 256 whose partial
-        // sums are added in a fixed order (round 4: no atomics), so the Adam update is its own (flat) launch; everything before it is the same five-kernel chain
-        if (!fused_enabled(e)) { CK(mi_ppo_forward_backward(h, stream, states, actions, returns, advantage, M, inv_m, grad_scale)); }
-        else {
-            PpoFusedParams q; fill_fused(e, q, states, M);
-            q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
-            q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
-            e->last_M = M;
-            CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));
-        }
+    if (!fused_enabled(e)) {                               // the per-layer pass (logp_old is not used), then Adam
+        CK(mi_ppo_forward_backward(h, stream, states, actions, returns, advantage, M, inv_m, grad_scale));
         return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
     }
-    PpoFusedParams q; fill_fused(e, q, states, M);
-    q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
-    q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
-    q.alpha = alpha; q.omb1 = 1.0f - beta1; q.omb2 = 1.0f - beta2; q.epsilon = epsilon;
-    e->last_M = M;
-    return mi_ppo_fused_step((hipStream_t)stream, q, 1, x3(e));
+    PpoFusedParams q; fill_step(e, q, states, actions, returns, advantage, logp_old, nullptr, 0, M, inv_m, grad_scale);
+    return route_step(e, stream, q, nullptr, 1, alpha, beta1, beta2, epsilon);
 }
 
 // 1: this engine's shape (num_actions, hidden sizes, input width) is inside the range of the fused kernels (csrc/ppo_fused.hip) and they are switched on, i.e.
@@ -360,17 +375,8 @@ int mi_ppo_train_step_idx(void* h, void* stream, const float* states, const floa
     if (!row_idx) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_idx: missing row index (use mi_ppo_train_step for contiguous minibatches)");
     if (!e->grads || !e->m || !e->v) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step_idx: engine created without optimiser buffers");
     if (!fused_enabled(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_train_step_idx: needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0): gather on the host side and call mi_ppo_train_step");
-    PpoFusedParams q; fill_fused(e, q, states, M);
-    q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
-    q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
-    q.row_idx = row_idx; q.n_rows = n_rows; q.s_gath = (float*)e->at(e->s_pad);
-    e->last_M = M;
-    if (M > 256 || clipping(e)) {
-        CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));
-        return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
-    }
-    q.alpha = alpha; q.omb1 = 1.0f - beta1; q.omb2 = 1.0f - beta2; q.epsilon = epsilon;
-    return mi_ppo_fused_step((hipStream_t)stream, q, 1, x3(e));
+    PpoFusedParams q; fill_step(e, q, states, actions, returns, advantage, logp_old, row_idx, n_rows, M, inv_m, grad_scale);
+    return route_step(e, stream, q, nullptr, 1, alpha, beta1, beta2, epsilon);
 }
 
 // One DATA-PARALLEL SGD step of PPO.train (ppo.py:218-229 behind train.py:193-207) in ONE call (round 6): the fused five-launch chain of
@@ -386,17 +392,12 @@ int mi_ppo_train_step_dp(void* h, void* comm, void* stream, const float* states,
     if (!comm) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_dp: null communicator (single rank: mi_ppo_train_step)");
     if (M < 1 || M > e->d.max_batch || (row_idx && n_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_dp: batch outside [1, max_batch] or empty tables");
     if (!e->grads || !e->m || !e->v) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step_dp: engine created without optimiser buffers");
-    if (fused_enabled(e)) {
-        PpoFusedParams q; fill_fused(e, q, states, M);
-        q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
-        q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
-        if (row_idx) { q.row_idx = row_idx; q.n_rows = n_rows; q.s_gath = (float*)e->at(e->s_pad); }
-        e->last_M = M;
-        CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));      // gradients written into the flat buffer (M > 256: ordered row chunks)
-    } else {
-        if (row_idx) return mi_fail(MI_ERR_SHAPE, "mi_ppo_train_step_dp: the in-kernel gather needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0): gather on the host side and pass row_idx = NULL");
-        CK(mi_ppo_forward_backward(h, stream, states, actions, returns, advantage, M, inv_m, grad_scale));
+    if (fused_enabled(e)) {                                // a communicator: the flat route at every M
+        PpoFusedParams q; fill_step(e, q, states, actions, returns, advantage, logp_old, row_idx, n_rows, M, inv_m, grad_scale);
+        return route_step(e, stream, q, comm, 1, alpha, beta1, beta2, epsilon);
     }
+    if (row_idx) return mi_fail(MI_ERR_SHAPE, "mi_ppo_train_step_dp: the in-kernel gather needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0): gather on the host side and pass row_idx = NULL");
+    CK(mi_ppo_forward_backward(h, stream, states, actions, returns, advantage, M, inv_m, grad_scale));      // the per-layer pass (logp_old is not used)
     CK(mi_allreduce_sum_f32(comm, stream, e->grads, e->total));
     return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
 }
@@ -419,20 +420,8 @@ int mi_ppo_train_step_vclip(void* h, void* comm, void* stream, const float* stat
     if (M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_vclip: batch outside [1, max_batch] or empty tables");
     if (!e->grads || (adam && (!e->m || !e->v))) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step_vclip: engine created without gradient / optimiser buffers");
     if (!fused_enabled(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_train_step_vclip: needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0): there is no per-layer form of the clipped value loss");
-    PpoFusedParams q; fill_fused(e, q, states, M);
-    q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
-    q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
-    q.v_old = old_values; q.clip_range_vf = clip_range_vf;
-    if (row_idx) { q.row_idx = row_idx; q.n_rows = n_rows; q.s_gath = (float*)e->at(e->s_pad); }
-    e->last_M = M;
-    if (adam && !comm && M <= 256 && !clipping(e)) {
-        q.alpha = alpha; q.omb1 = 1.0f - beta1; q.omb2 = 1.0f - beta2; q.epsilon = epsilon;
-        return mi_ppo_fused_step((hipStream_t)stream, q, 1, x3(e));
-    }
-    CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));      // gradients written into the flat buffer (M > 256: ordered row chunks)
-    if (!adam) return MI_OK;
-    if (comm) CK(mi_allreduce_sum_f32(comm, stream, e->grads, e->total));
-    return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
+    PpoFusedParams q; fill_step(e, q, states, actions, returns, advantage, logp_old, row_idx, n_rows, M, inv_m, grad_scale, old_values, clip_range_vf);
+    return route_step(e, stream, q, comm, adam, alpha, beta1, beta2, epsilon);
 }
 
 // The minibatch step with the adaptive-KL penalty of the PPO paper added to the clipped surrogate (include/mi355_carla.h; the definition is in ppo_fused.hip's head /
@@ -453,21 +442,8 @@ int mi_ppo_train_step_kl(void* h, void* comm, void* stream, const float* states,
     if (M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_kl: batch outside [1, max_batch] or empty tables");
     if (!e->grads || (adam && (!e->m || !e->v))) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step_kl: engine created without gradient / optimiser buffers");
     if (!fused_enabled(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_train_step_kl: needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0): there is no per-layer form of the KL penalty");
-    PpoFusedParams q; fill_fused(e, q, states, M);
-    q.actions = actions; q.returns = returns; q.adv = advantage; q.inv_m = inv_m; q.grad_scale = grad_scale;
-    q.logp_old = logp_old; q.n_nets = logp_old ? 2 : 3;
-    q.kl_on = 1; q.kl_coef = kl_coef; q.mean_old = mean_old;
-    if (old_values) { q.v_old = old_values; q.clip_range_vf = clip_range_vf; }
-    if (row_idx) { q.row_idx = row_idx; q.n_rows = n_rows; q.s_gath = (float*)e->at(e->s_pad); }
-    e->last_M = M;
-    if (adam && !comm && M <= 256 && !clipping(e)) {
-        q.alpha = alpha; q.omb1 = 1.0f - beta1; q.omb2 = 1.0f - beta2; q.epsilon = epsilon;
-        return mi_ppo_fused_step((hipStream_t)stream, q, 1, x3(e));
-    }
-    CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));      // gradients written into the flat buffer (M > 256: ordered row chunks)
-    if (!adam) return MI_OK;
-    if (comm) CK(mi_allreduce_sum_f32(comm, stream, e->grads, e->total));
-    return mi_ppo_apply_adam(h, stream, alpha, beta1, beta2, epsilon);
+    PpoFusedParams q; fill_step(e, q, states, actions, returns, advantage, logp_old, row_idx, n_rows, M, inv_m, grad_scale, old_values, clip_range_vf, true, kl_coef, mean_old);
+    return route_step(e, stream, q, comm, adam, alpha, beta1, beta2, epsilon);
 }
 
 // mi_ppo_logp_old that keeps the old policy's action means as well: logp_out [M] (bit for bit mi_ppo_logp_old's), mean_out [M, A] -- the two tables of the KL penalty

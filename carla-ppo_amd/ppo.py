@@ -191,22 +191,9 @@ class PPO():
         """One SGD step through mi_ppo_train_step_kl (the penalty is on): contiguous tensors (rows None) or table rows `rows` (int32 device tensor) of the
         horizon-batch tables; mean_old: the old policy's means, indexed like logp_old (None: the cached log pi_old is dropped and the step evaluates the old policy
         itself -- correct, slower); with old_values also the clipped value loss (self.value_clip)."""
-        dev = self.dev
         if old_values is not None and self.value_clip is None:
             raise ValueError("PPO._kl_step: old values were passed but value clipping is off (set_value_clip)")
-        one_call = os.environ.get("MI355_PPO_FUSED", "1") != "0" and (rows is None or os.environ.get("MI355_PPO_IDX", "1") != "0") and dev.fused_ok()
-        comm = None if midist.world_size() == 1 else self._dp_comm()
-        if not one_call or (midist.world_size() > 1 and comm is None):
-            raise ValueError("PPO: the KL penalty needs the fused one-call step (this policy's shape is outside the fused kernels' range, "
-                             "MI355_PPO_FUSED=0 / MI355_PPO_IDX=0, or data parallel without the library's communicator)")
-        if mean_old is None:                                   # no table of old means (replay.py): the step evaluates the old policy itself -- correct, slower
-            logp_old = None
-        alpha = _adam_alpha(self.current_learning_rate(), self.beta1_power, self.beta2_power)
-        dev.train_step_kl(None if comm is None else comm.handle, s, a, r, adv, logp_old, mean_old, self.kl_penalty, rows, m_local, 1.0 / m_global,
-                          m_local / float(m_global), alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON, old_values=old_values,
-                          clip_range_vf=None if old_values is None else self.value_clip)
-        self.beta1_power = np.float32(self.beta1_power * np.float32(ADAM_BETA1))
-        self.beta2_power = np.float32(self.beta2_power * np.float32(ADAM_BETA2))
+        self._dispatch_step(s, a, r, adv, rows, logp_old, mean_old, old_values, m_local, m_global)
 
     def last_grad_norm(self):
         """{"grad_norm", "clip_scale"} of the last step that formed a norm (one readback); zeros before the first one."""
@@ -276,19 +263,51 @@ class PPO():
         """One SGD step on device-resident minibatch tensors.  Single rank: one C call (fused forward / losses / backward / Adam, five launches);
         data parallel: gradients, all-reduce, Adam.  logp_old: cached log pi_old(a|s) of these samples (PpoDevice.logp_old), optional.  mean_old: the old policy's
         means of these samples (PpoDevice.old_policy_cache), read with the KL penalty on; without it the penalised step evaluates the old policy itself."""
-        dev = self.dev
-        if self.kl_penalty is not None:
-            return self._kl_step(s, a, r, adv, logp_old, mean_old, None, m_local, m_global)
+        self._dispatch_step(s, a, r, adv, None, logp_old, mean_old, None, m_local, m_global)
+
+    def _dispatch_step(self, s, a, r, adv, rows, logp_old, mean_old, old_values, m_local, m_global):
+        """The ONE decision behind _step_resident / _step_rows / _kl_step: which device call this minibatch step is.  rows None: contiguous minibatch tensors; else
+        the tensors are horizon-batch tables and `rows` (int32 device tensor) names this minibatch.  The switches, the world and the communicator are read once.
+          the one-call forms    the KL penalty (train_step_kl), old values (train_step_vclip) and the in-kernel gather (train_step_idx; data parallel train_step_dp
+                                with the rows) need MI355_PPO_FUSED / MI355_PPO_IDX (the latter not for the penalised contiguous step) not "0", dev.fused_ok() and, data parallel, the
+                                library's communicator.  Without them the first two refuse and plain rows are gathered here into the contiguous forms:
+          contiguous, plain     single rank: train_step unless MI355_PPO_FUSED=0 (fused_ok() is not asked: the C entry falls back by itself); a communicator:
+                                train_step_dp, one C call; else forward_backward, the all-reduce of the gradient buffer (data parallel), apply_adam."""
+        dev, world = self.dev, midist.world_size()
+        comm = None if world == 1 else self._dp_comm()
+        handle = None if comm is None else comm.handle
+        fused, kl = os.environ.get("MI355_PPO_FUSED", "1") != "0", self.kl_penalty is not None
+        if rows is not None or kl or old_values is not None:
+            # (MI355_PPO_IDX is the in-kernel gather's switch; the value-clipped step without the penalty asks it with or without rows, as it always has)
+            if not (fused and ((kl and rows is None) or os.environ.get("MI355_PPO_IDX", "1") != "0") and (world == 1 or comm is not None) and dev.fused_ok()):
+                if kl or old_values is not None:
+                    raise ValueError("%s needs the fused one-call step (this policy's shape is outside the fused kernels' range, MI355_PPO_FUSED=0 / MI355_PPO_IDX=0, "
+                                     "or data parallel without the library's communicator)" % ("PPO: the KL penalty" if kl else "PPO._step_rows: value clipping"))
+                # (shapes outside the fused kernels' range -- e.g. more than 8 actions -- have no in-kernel gather: mi_ppo_fused_shape_ok says so up front and the
+                #  rows are gathered here instead; row values themselves are clamped into the tables by the kernels, ADVICE r03)
+                mb = rows.to("cuda" if rows.is_cuda else rows.device).long()
+                s, a, r, adv = s[mb].contiguous(), a[mb].contiguous(), r[mb].contiguous(), adv[mb].contiguous()
+                logp_old, rows = None if logp_old is None else logp_old[mb].contiguous(), None
+        inv_m, gs = 1.0 / m_global, m_local / float(m_global)
         alpha = _adam_alpha(self.current_learning_rate(), self.beta1_power, self.beta2_power)
-        comm = self._dp_comm()
-        if midist.world_size() == 1 and os.environ.get("MI355_PPO_FUSED", "1") != "0":
-            dev.train_step(s, a, r, adv, m_local, 1.0 / m_global, m_local / float(m_global), alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON, logp_old=logp_old)
+        if kl:
+            if mean_old is None:                               # no table of old means (replay.py): the step evaluates the old policy itself -- correct, slower
+                logp_old = None
+            dev.train_step_kl(handle, s, a, r, adv, logp_old, mean_old, self.kl_penalty, rows, m_local, inv_m, gs, alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON,
+                              old_values=old_values, clip_range_vf=None if old_values is None else self.value_clip)
+        elif old_values is not None:
+            dev.train_step_vclip(handle, s, a, r, adv, logp_old, old_values, self.value_clip, rows, m_local, inv_m, gs, alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON)
+        elif rows is not None and world == 1:
+            dev.train_step_idx(s, a, r, adv, logp_old, rows, m_local, inv_m, gs, alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON)
         elif comm is not None:
-            # data parallel with the library's communicator live: the step is ONE C call -- the fused chain, the all-reduce of the flat gradient buffer, Adam (round 6)
-            dev.train_step_dp(comm.handle, s, a, r, adv, logp_old, None, m_local, 1.0 / m_global, m_local / float(m_global), alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON)
+            # data parallel with the library's communicator live: the step is ONE C call -- the fused chain, the all-reduce of the flat gradient buffer, Adam (round 6);
+            # with rows the in-kernel gather is kept: they index THIS rank's tables
+            dev.train_step_dp(handle, s, a, r, adv, logp_old, rows, m_local, inv_m, gs, alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON)
+        elif world == 1 and fused:
+            dev.train_step(s, a, r, adv, m_local, inv_m, gs, alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON, logp_old=logp_old)
         else:
-            dev.forward_backward(s, a, r, adv, m_local, 1.0 / m_global, m_local / float(m_global))
-            if midist.world_size() > 1:
+            dev.forward_backward(s, a, r, adv, m_local, inv_m, gs)
+            if world > 1:
                 midist.all_reduce_sum(dev.grads)
             dev.apply_adam(alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON)
         self.beta1_power = np.float32(self.beta1_power * np.float32(ADAM_BETA1))
@@ -307,48 +326,14 @@ class PPO():
 
     def _step_rows(self, s_all, a_all, r_all, adv_all, logp_old_all, rows, m_local, m_global, old_values_all=None):
         """One SGD step on rows `rows` (int32 device tensor) of device-resident horizon-batch tables: the minibatch gather of train.py:199-204 runs inside
-        the step's kernels (single rank, fused kernels); otherwise the rows are gathered here and _step_resident takes over.  old_values_all: the table of the values
-        recorded at collection time -- the step clips the value loss with self.value_clip (mi_ppo_train_step_vclip), which only the one-call forms can.  With the KL
-        penalty on (set_kl_penalty) the step goes through _kl_step."""
-        dev = self.dev
+        the step's kernels (fused kernels; data parallel: the library's communicator); otherwise the rows are gathered and the contiguous forms take over.
+        old_values_all: the table of the values recorded at collection time -- the step clips the value loss with self.value_clip (mi_ppo_train_step_vclip), which only the one-call forms can.  With the KL
+        penalty on (set_kl_penalty) the step is _kl_step's without a table of old means.  The decision is _dispatch_step's."""
         if old_values_all is not None and self.value_clip is None:
             raise ValueError("PPO._step_rows: old values were passed but value clipping is off (set_value_clip)")
-        if self.kl_penalty is not None:
-            # this entry carries no table of the old policy's means (the rollout buffers pass theirs to _kl_step): the cached log pi_old is dropped and the penalised
-            # step evaluates the old policy itself
-            return self._kl_step(s_all, a_all, r_all, adv_all, logp_old_all, None, rows, m_local, m_global, old_values=old_values_all)
-        if old_values_all is not None:
-            one_call = os.environ.get("MI355_PPO_FUSED", "1") != "0" and os.environ.get("MI355_PPO_IDX", "1") != "0" and dev.fused_ok()
-            comm = None if midist.world_size() == 1 else self._dp_comm()
-            if not one_call or (midist.world_size() > 1 and comm is None):
-                raise ValueError("PPO._step_rows: value clipping needs the fused one-call step (this policy's shape is outside the fused kernels' range, "
-                                 "MI355_PPO_FUSED=0 / MI355_PPO_IDX=0, or data parallel without the library's communicator)")
-            alpha = _adam_alpha(self.current_learning_rate(), self.beta1_power, self.beta2_power)
-            dev.train_step_vclip(None if comm is None else comm.handle, s_all, a_all, r_all, adv_all, logp_old_all, old_values_all, self.value_clip, rows, m_local,
-                                 1.0 / m_global, m_local / float(m_global), alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON)
-            self.beta1_power = np.float32(self.beta1_power * np.float32(ADAM_BETA1))
-            self.beta2_power = np.float32(self.beta2_power * np.float32(ADAM_BETA2))
-            return
-        # (shapes outside the fused kernels' range -- e.g. more than 8 actions -- have no in-kernel gather: mi_ppo_fused_shape_ok says so up front and the rows
-        #  are gathered here instead; row values themselves are clamped into the tables by the kernels, ADVICE r03)
-        if midist.world_size() == 1 and os.environ.get("MI355_PPO_FUSED", "1") != "0" and os.environ.get("MI355_PPO_IDX", "1") != "0" and dev.fused_ok():
-            alpha = _adam_alpha(self.current_learning_rate(), self.beta1_power, self.beta2_power)
-            dev.train_step_idx(s_all, a_all, r_all, adv_all, logp_old_all, rows, m_local, 1.0 / m_global, m_local / float(m_global), alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON)
-            self.beta1_power = np.float32(self.beta1_power * np.float32(ADAM_BETA1))
-            self.beta2_power = np.float32(self.beta2_power * np.float32(ADAM_BETA2))
-            return
-        comm = self._dp_comm()
-        if comm is not None and os.environ.get("MI355_PPO_FUSED", "1") != "0" and os.environ.get("MI355_PPO_IDX", "1") != "0" and dev.fused_ok():
-            # data parallel: the in-kernel gather is kept -- `rows` index THIS rank's tables -- and the step stays one C call (round 6; before, world_size > 1 gathered here
-            # and sequenced forward_backward -> all-reduce -> Adam from Python)
-            alpha = _adam_alpha(self.current_learning_rate(), self.beta1_power, self.beta2_power)
-            dev.train_step_dp(comm.handle, s_all, a_all, r_all, adv_all, logp_old_all, rows, m_local, 1.0 / m_global, m_local / float(m_global), alpha, ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON)
-            self.beta1_power = np.float32(self.beta1_power * np.float32(ADAM_BETA1))
-            self.beta2_power = np.float32(self.beta2_power * np.float32(ADAM_BETA2))
-            return
-        mb = rows.to("cuda" if rows.is_cuda else rows.device).long()
-        self._step_resident(s_all[mb].contiguous(), a_all[mb].contiguous(), r_all[mb].contiguous(), adv_all[mb].contiguous(), m_local, m_global,
-                            logp_old=None if logp_old_all is None else logp_old_all[mb].contiguous())
+        # this entry carries no table of the old policy's means (the rollout buffers pass theirs to _kl_step): with the penalty on, the cached log pi_old is dropped and
+        # the penalised step evaluates the old policy itself
+        self._dispatch_step(s_all, a_all, r_all, adv_all, rows, logp_old_all, None, old_values_all, m_local, m_global)
 
     def train(self, input_states, taken_actions, returns, advantage):
         """One SGD step on a minibatch + metric update + train_step_counter += 1; returns None (ppo.py:218-229)."""
