@@ -311,11 +311,12 @@ def gen1_conv_ok(dt, in_f32, ih, iw, c, k):
     return None
 
 
-def gen1_wgrad_plan(dt, M, Kc, N):
-    """wgrad_splits / prepare_wgrad: {splits, mps, slab_bytes, wide}."""
+def gen1_wgrad_plan(dt, M, Kc, N, target=GEN1_WGRAD_TARGET):
+    """wgrad_splits / prepare_wgrad: {splits, mps, slab_bytes, wide}.  target: the launch's target block count (the layer-op entry points' 1024; the dense entry
+    points pass tuning key 11)."""
     bp = WGRAD_BP[dt]
     gx, gy = (ceil_div(Kc, 128) if Kc > 64 else 1), ceil_div(N, 64)
-    splits = max(1, GEN1_WGRAD_TARGET // (gx * gy))
+    splits = max(1, target // (gx * gy))
     mps = max(bp, ceil_div(ceil_div(M, splits), bp) * bp)
     splits = ceil_div(M, mps)
     return {"splits": splits, "mps": mps, "wide": Kc > 64, "slab_bytes": splits * ceil_div(Kc * N, 4) * 4 * 4}

@@ -383,7 +383,8 @@ def test_dense_wgrad_whole_tiles_over_all_rows(shape):
     assert np.array_equal(host(dw), outs[0][0])
 
 
-@pytest.mark.parametrize("shape", [(512, 512, 256), (512, 256, 128), (512, 64, 256), (16, 64, 64), (48, 128, 192), (80, 512, 256), (2048, 256, 128), (32, 256, 512)])
+@pytest.mark.parametrize("shape", [(512, 512, 256), (512, 256, 128), (512, 64, 256), (16, 64, 64), (48, 128, 192), (80, 512, 256), (2048, 256, 128), (32, 256, 512),
+                                   (64, 128, 192), (96, 64, 64)])     # (the last two: two waves per tile -- M / 16 even, not a multiple of 4 or below 8)
 def test_dense_wgrad_one_wave_per_tile_without_lds(shape):
     """Round 5 (dwgs_tile.hpp): the dense filter gradient without operand staging -- one block of 1 / 2 / 4 waves per 64 x 64 tile of dW over ALL rows
     (the waves split the rows and meet in a fixed order through a 16 KB LDS tile), fragments gathered as column-pair dwords and split by v_perm_b32, four steps of loads in
