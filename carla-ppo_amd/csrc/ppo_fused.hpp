@@ -70,3 +70,6 @@ int mi_rollout_value_batch(hipStream_t st, const mi::PpoFusedParams& q, const fl
                            const MiRolloutValueRec& rec, const MiRolloutObsNorm* nrm = nullptr);
 int mi_rollout_policy_batch_norm(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n,
                                  float* out, const MiRolloutRec* rec, const MiRolloutObsNorm& nrm);
+// layer 1 of the MlpVAE encoder from the camera bytes of n environments (rollout_mlp.hip; mi_mlp_rollout_step_batch): clears `zero` -- the raw-sum buffers of the whole
+// call, raw1 among them -- in a launch of its own, then adds frames / 255 x w1 [S][N1] onto raw1 [n][N1] (fp32 atomics).  frames: 4-byte aligned.
+int mi_rollout_mlp_layer1(hipStream_t st, const unsigned char* frames, const float* w1, float* raw1, int S, int N1, int n, const MiZeroList* zero);

@@ -16,6 +16,8 @@ from .vae_device import LOSS_KINDS, PRECISIONS, require_gpu
 
 
 class MlpVaeDevice:
+    rollout_kind = "mlp"                                # rollout.py: this handle goes to mi_mlp_rollout_step_batch / _value_batch, never to the ConvVAE's mi_rollout_* entries
+
     def __init__(self, source_shape, target_shape, z_dim, beta, kl_tolerance, loss_fn, precision, encoder_sizes=(512, 256),
                  decoder_sizes=(256, 512), max_batch=128, with_optimizer=True, device=None):
         require_gpu()

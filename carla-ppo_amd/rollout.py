@@ -201,6 +201,16 @@ measured KL is not finite (beta then stays, nothing is raised).  All of it comes
 ppo.state_dict(): ppo.kl_penalty_state() / load_kl_penalty_state() carry them.  With the setting off none of these keys appears, no table is allocated and not one
 launch or readback is added.
 
+The encoder may be an MlpVAE (the reference's --vae_model_type mlp).  BatchedRolloutStep, RolloutBuffer and ContinuousRolloutBuffer then go through
+mi_mlp_rollout_step_batch / mi_mlp_rollout_value_batch (an MlpVaeDevice says rollout_kind = "mlp"; its handle never reaches the mi_rollout_* entries, which read theirs
+as a ConvVAE engine): a clear launch, layer 1 of the encoder straight from the camera bytes (csrc/rollout_mlp.hip: the fp32 master kernel streamed once per call, every
+frame byte fetched once, K split over the chip and met by fp32 atomics), the remaining hidden layers and the mean head as flat split-K layers, then the trunks, heads,
+normaliser and value-only heads of the ConvVAE step -- exact fp32 on the master weights whatever the VAE's storage type.  Everything above works unchanged: recording,
+truncation, diagnostics, value clipping, the KL penalty, reward scaling, observation and minibatch normalisation.  The scratch is 4 n (sum of the encoder widths +
+z_dim) bytes (mi_mlp_rollout_workspace_bytes).  On the measured box one call takes 84 / 91 / 223 us for 1 / 8 / 64 environments against 185 / 213 / 389 us for the
+two-call path on the same model (profiles/r27_mlp_rollout.md).  RolloutStep, the single-frame entry, has no MLP form (ValueError: use BatchedRolloutStep(vae, ppo,
+num_envs=1)).
+
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import contextlib
@@ -235,6 +245,9 @@ class _StepBase:
         self.frame_bytes = int(np.prod(vdev.source_shape))
         self._rng = np.random.Generator(np.random.Philox(int(seed if seed is not None else (ppo.seed or 0)) + 0xAC7))
         self._obs_norm = None                                                        # running observation normalisation (set_observation_normalization): None = off
+        self._kind = getattr(vdev, "rollout_kind", "conv")                           # "mlp": an MlpVaeDevice, whose handle goes to the mi_mlp_rollout_* entries alone
+        if self._kind not in ("conv", "mlp"):
+            raise ValueError(who + ": unknown encoder kind %r" % (self._kind,))
         return vdev, pdev
 
     def _io_buffers(self, in_bytes, out_floats):
@@ -251,6 +264,8 @@ class _StepBase:
 class RolloutStep(_StepBase):
     def __init__(self, vae, ppo, seed=None, io=None):
         self._setup("RolloutStep", vae, ppo, seed, io)
+        if self._kind != "conv":                                                     # (mi_rollout_step would read the MLP engine as a ConvVAE engine)
+            raise ValueError("RolloutStep: the single-frame entry exists for the ConvVAE only: use BatchedRolloutStep(vae, ppo, num_envs=1)")
         self._noise_off = (self.frame_bytes + 15) // 16 * 16                         # float region: measurements, then noise
         self._io_buffers(self._noise_off + 4 * (self.n_meas + self.A), self.A + 1 + self.z_dim)
         self._f_np = self._in_np[self._noise_off:].view(np.float32)
@@ -293,7 +308,8 @@ class RolloutStep(_StepBase):
 class BatchedRolloutStep(_StepBase):
     """RolloutStep for up to `num_envs` environments per call (mi_rollout_step_batch): frames_u8 [n, H, W, 3] uint8 and measurements [n, k] in,
     (actions float32 [n, A], values float32 [n], states float64 [n, z_dim + k]) out, 1 <= n <= num_envs -- environments finish their episodes at
-    different times.  Row e is what RolloutStep gives for frame e: np.append(vae.encode([frame_e])[0], meas_e) and model.predict of it."""
+    different times.  Row e is what RolloutStep gives for frame e: np.append(vae.encode([frame_e])[0], meas_e) and model.predict of it.  With an MlpVAE every device
+    call is mi_mlp_rollout_step_batch / mi_mlp_rollout_value_batch instead (one entry each for the plain, recording and normalised forms)."""
 
     _who = "BatchedRolloutStep"                                                      # the prefix of check()'s messages
     _row_ints = 0                                                                    # int32 per environment behind the noise (the recording step's table rows)
@@ -308,9 +324,13 @@ class BatchedRolloutStep(_StepBase):
         E, self.row = self.num_envs, self.A + 1 + self.z_dim
         self._f_off = (E * self.frame_bytes + 15) // 16 * 16                         # float region: measurements [E, k], then noise [E, A], then _row_ints [E]
         self._io_buffers(self._f_off + 4 * E * (self.n_meas + self.A + self._row_ints), E * self.row)
-        self.scratch_bytes = int(self.L.mi_rollout_batch_workspace_bytes(vae.dev.handle, ppo.dev.handle, E))
+        if self._kind == "mlp":                                                      # sized from the descriptor: no handle involved
+            import ctypes
+            entry, self.scratch_bytes = "mi_mlp_rollout_workspace_bytes", int(self.L.mi_mlp_rollout_workspace_bytes(ctypes.byref(vdev._desc(1)), E))
+        else:
+            entry, self.scratch_bytes = "mi_rollout_batch_workspace_bytes", int(self.L.mi_rollout_batch_workspace_bytes(vae.dev.handle, ppo.dev.handle, E))
         if self.scratch_bytes <= 0:
-            raise milib.MiError("mi_rollout_batch_workspace_bytes: " + self.L.cdll.mi_last_error().decode())
+            raise milib.MiError(entry + ": " + self.L.cdll.mi_last_error().decode())
         self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=self.device)
         self._f_np = self._in_np[self._f_off:].view(np.float32)
         self._i_np = self._in_np[self._f_off:].view(np.int32)
@@ -374,7 +394,14 @@ class BatchedRolloutStep(_StepBase):
         args = (self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, None if greedy else fptr + 4 * nm, 1 if greedy else 0, n,
                 self.scratch.data_ptr(), self.scratch_bytes, (self.h_out if self.d_out is None else self.d_out).data_ptr())
         on = self._obs_norm
-        if on is not None:
+        if getattr(self, "_kind", "conv") == "mlp":                                  # one entry: obs_mean NULL = not normalised, table_rows NULL = nothing recorded
+            norm = (None, None, 0.0, None) if on is None else (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr())
+            if table_rows is None:
+                tabs = (None, 0, None, None, None, None)
+            else:
+                tabs = (fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), None if on is None else raw_states.data_ptr(), actions.data_ptr(), values.data_ptr())
+            self.L.mi_mlp_rollout_step_batch(*args, *norm, *tabs)
+        elif on is not None:
             norm = (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr())
             if table_rows is None:
                 self.L.mi_rollout_step_batch_norm(*args, *norm, None, 0, None, None, None, None)
@@ -409,7 +436,10 @@ class BatchedRolloutStep(_StepBase):
                 (self.h_out if self.d_out is None else self.d_out).data_ptr())
         rec = (fptr + 4 * nm, int(final_values.shape[0]), final_values.data_ptr())
         on = self._obs_norm
-        if on is not None:
+        if getattr(self, "_kind", "conv") == "mlp":
+            norm = (None, None, 0.0, None) if on is None else (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr())
+            self.L.mi_mlp_rollout_value_batch(*args, *norm, *rec)
+        elif on is not None:
             self.L.mi_rollout_value_batch_norm(*args, on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr(), *rec)
         else:
             self.L.mi_rollout_value_batch_rec(*args, *rec)

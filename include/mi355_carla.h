@@ -464,6 +464,23 @@ int mi_rollout_scale_rewards(void* stream, const double* rewards, const double* 
  * aligned; obs_clip <= 0 or NaN; table_rows without all four tables. */
 int mi_rollout_step_batch_norm(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n, void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate, const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values);
 int mi_rollout_value_batch_norm(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n, void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate, const int* table_rows, long long n_table_rows, float* tab_final_values);
+/* the batched rollout step for the MlpVAE encoder (--vae_model_type mlp; vae/models.py:271-299 in front of vae_common.py:45-61 + ppo.py:231-251): mlp_h is a handle of
+ * mi_mlpvae_create.  The mi_rollout_* entries above read their vae_h as a ConvVAE engine and never inspect it: an MlpVAE handle goes to these two entries only.
+ * Exact fp32 on the fp32 master weights (params), whatever the engine's storage type.  Launches: clear (every raw-sum buffer of the call: nothing depends on what the
+ * scratch held on entry) -> layer 1 from the camera bytes (rollout_mlp.hip: W1 streamed once, every frame byte fetched once, K split over ceil(S / KS) blocks, KS = 64 .. 256 by n, that meet by
+ * fp32 atomics) -> hidden layers 2.. and the mean head as the flat split-K layers of mi_rollout_step_batch -> the trunks and heads of mi_rollout_step_batch.
+ * scratch: HBM, 16-byte aligned, at least mi_mlp_rollout_workspace_bytes(d, n) = 4 n (enc[0] + .. + enc[n_enc - 1] + z_dim) bytes (raw sums [n][enc[0]] | .. | raw means
+ * [n][z_dim]; needs no handle and no GPU; MI_ERR_ARG for n_envs outside 1 .. MI_ROLLOUT_MAX_ENVS, MI_ERR_SHAPE for a desc mi_mlpvae_create refuses).  frames_u8: uint8
+ * [n][source_size], HBM or pinned host memory, 4-byte aligned.  measurements / noise / out / n / greedy as in mi_rollout_step_batch.
+ * mi_mlp_rollout_step_batch is the plain, the recording and the normalised step in one: obs_mean == NULL: no normalisation (obs_inv_std, nstate and tab_raw_states must be NULL
+ * too; tab_states takes the raw rows [z | measurements], as mi_rollout_step_batch_rec stores them); else the arguments of mi_rollout_step_batch_norm.  table_rows == NULL
+ * records nothing (no table is read).  mi_mlp_rollout_value_batch: the value-only call (mi_rollout_value_batch_rec / _norm); table_rows may be NULL: the values go to out alone.
+ * Errors, each message under the entry's own name, everything that needs no device before the first launch: null handle (MI_ERR_STATE); missing buffers or tables, n outside
+ * 1 .. MI_ROLLOUT_MAX_ENVS, frames not 4-byte / scratch or nstate not 16-byte aligned, obs_clip <= 0 or NaN, scratch too small, more than 8 actions, n above the PPO
+ * engine's max_batch (MI_ERR_ARG); z_dim + n_meas != the policy's input size (MI_ERR_SHAPE). */
+long long mi_mlp_rollout_workspace_bytes(const MiMlpVaeDesc* d, int n_envs);
+int mi_mlp_rollout_step_batch(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n, void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate, const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values);
+int mi_mlp_rollout_value_batch(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n, void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate, const int* table_rows, long long n_table_rows, float* tab_final_values);
 /* the moments pass behind it — VecNormalize's obs_rms.update at the granularity of a collection, no reference counterpart in train.py.  No engine handle.  The rows
  * row_idx[i], i < n (int32, device; a row outside [0, n_table_rows) is skipped and does not count) of tab_raw_states (fp32 [n_table_rows][din]) are merged into
  * state: double [1 + 2 din] = {count, mean[din], M2[din]}, per column j, fp64 throughout:

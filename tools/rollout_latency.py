@@ -2,6 +2,7 @@
 VAE.encode([frame]) (host frame -> device, conv stack, mean to host) followed by PPO.predict(state) (host -> device, two MLP trunks, action to host).
 
     python tools/rollout_latency.py --envs [1,2,4,8,16,32,64] [--rounds 3] [--calls 200] [--batched-only | --record | --value | --obs-norm] [--no-box]
+    python tools/rollout_latency.py --mlp [--envs 1,8,64] [--rounds 3] [--calls 200] [--no-box]
 
 times, for each number of environments E, one BatchedRolloutStep call against a loop of E RolloutStep calls and against the two-call path (VAE.encode of E float
 frames + PPO.predict of E states) on the same engines: the three are interleaved in every round, the line gives the median of the rounds' medians, the spread of
@@ -12,21 +13,17 @@ ContinuousRolloutBuffer.truncate (mi_rollout_value_batch_rec: the encoder chain,
 is: mi_rollout_step_batch_rec) on the same frames, both without the row book-keeping and at fixed table rows, interleaved.  --obs-norm times the recording call and
 the value-only call with running observation normalisation on (mi_rollout_step_batch_norm / mi_rollout_value_batch_norm: one more launch, rollout_obs_norm_kernel)
 against the same calls of a twin buffer with the setting off, without the row book-keeping and at fixed table rows, interleaved; behind the table it times the merge
-(mi_rollout_obs_stats alone, device events) over 1024 rows of 128 columns."""
+(mi_rollout_obs_stats alone, device events) over 1024 rows of 128 columns.  --mlp builds an MlpVAE (38400 -> 512 -> 256 -> 64) in place of the ConvVAE and times, at
+E = 1, 8, 64 in interleaved rounds, the batched step (mi_mlp_rollout_step_batch), the two-call path on the same model and the recording call at fixed table rows, next to
+the floor of layer 1: the 78.6 MB of its fp32 kernel at the box's measured read rate."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
     sys.path.insert(0, p)
 import numpy as np, torch
-from vae.models import ConvVAE
+from vae.models import ConvVAE, MlpVAE
 from ppo import PPO
 
-class Box:
-    low, high, shape = np.array([-1.0, 0.0], np.float32), np.array([1.0, 1.0], np.float32), (2,)
-vae = ConvVAE(np.array([80, 160, 3]), z_dim=64, model_dir=tempfile.mkdtemp(), precision=os.environ.get("MI355_PRECISION", "bf16"), training=False)
-vae.init_session(init_logging=False)
-agent = PPO(np.array([67]), Box(), model_dir=tempfile.mkdtemp())
-agent.init_session(init_logging=False)
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", nargs="?", const="1,2,4,8,16,32,64", default=None)
 ap.add_argument("--rounds", type=int, default=3)
@@ -35,8 +32,16 @@ ap.add_argument("--batched-only", action="store_true")
 ap.add_argument("--record", action="store_true", help="RolloutBuffer.step against BatchedRolloutStep")
 ap.add_argument("--value", action="store_true", help="the value-only call (mi_rollout_value_batch_rec) against the greedy recording call")
 ap.add_argument("--obs-norm", action="store_true", help="the recording and value-only calls with observation normalisation on against the setting off; the merge at 1024 x 128")
+ap.add_argument("--mlp", action="store_true", help="an MlpVAE encoder: the batched step, the two-call path and the recording call at E = 1, 8, 64 (or --envs)")
 ap.add_argument("--no-box", action="store_true")
 args = ap.parse_args()
+
+class Box:
+    low, high, shape = np.array([-1.0, 0.0], np.float32), np.array([1.0, 1.0], np.float32), (2,)
+vae = (MlpVAE if args.mlp else ConvVAE)(np.array([80, 160, 3]), z_dim=64, model_dir=tempfile.mkdtemp(), precision=os.environ.get("MI355_PRECISION", "bf16"), training=False)
+vae.init_session(init_logging=False)
+agent = PPO(np.array([67]), Box(), model_dir=tempfile.mkdtemp())
+agent.init_session(init_logging=False)
 rng = np.random.RandomState(0)
 
 
@@ -134,6 +139,50 @@ def envs_table():
         print(line, flush=True)
 
 
+def mlp_table():
+    """The MlpVAE's batched step against the two-call path on the same model and the recording call, and the floor of layer 1's weight stream."""
+    from rollout import BatchedRolloutStep, RolloutBuffer
+    if args.rounds < 3:
+        ap.error("--rounds must be at least 3")
+    w1_bytes = 4 * int(np.prod(vae.dev.source_shape)) * vae.dev.enc_sizes[0]
+    rate = None
+    if not args.no_box:
+        from bench import box_probe
+        b = box_probe(agent.dev, 0)
+        rate = b["hbm_read_tbps"]
+        print("box: %.0f TFLOP/s bf16 MFMA at %.0f MHz, %.2f TB/s read" % (b["mfma_bf16_tflops"], b["sclk_mhz"], rate))
+        print("layer 1: %.1f MB of fp32 weights, %.1f us at that read rate" % (w1_bytes / 1e6, w1_bytes / (rate * 1e12) * 1e6))
+    u8 = rng.randint(0, 256, (128, 80, 160, 3), dtype=np.uint8)
+    f32 = u8.astype(np.float32) / 255.0
+    ms = rng.rand(128, 3).astype(np.float32)
+    for E in [int(x) for x in (args.envs or "1,8,64").split(",") if x]:
+        many = BatchedRolloutStep(vae, agent, E)
+        buf = RolloutBuffer(vae, agent, E, horizon=64, io=many.io)
+        fixed = (np.arange(E) * (buf.horizon + 1)).astype(np.int32)
+        sl = lambda i: slice((i * E) % 64, (i * E) % 64 + E)       # noqa: E731
+
+        def batched(i): many(u8[sl(i)], ms[sl(i)])
+        def two_call(i):
+            z = vae.encode(f32[sl(i)])
+            agent.predict(np.concatenate([z, ms[sl(i)]], axis=1))
+        def recording(i):                                            # the recording call without the row book-keeping: always slot 0
+            buf._step.record(*buf._step.check(u8[sl(i)], ms[sl(i)], False, None), False, fixed, buf.states, buf.actions, buf.values)
+        paths = [("batched", batched), ("two-call", two_call), ("recording", recording)]
+        ts = {name: [] for name, _ in paths}
+        for _ in range(args.rounds):
+            for name, fn in paths:
+                ts[name].append(timed(fn, args.calls))
+        line, med = "E = %3d (io=%s, MlpVAE %s):" % (E, many.io, vae.precision), {}
+        for name, _ in paths:
+            meds = [np.median(t) for t in ts[name]]
+            med[name] = np.median(meds)
+            line += "  %s %.1f us (rounds %.1f - %.1f, p90 %.1f)" % (name, med[name], min(meds), max(meds), np.percentile(np.concatenate(ts[name]), 90))
+        line += "  | two-call / batched %.2f x, recording - batched %+.2f us" % (med["two-call"] / med["batched"], med["recording"] - med["batched"])
+        if rate:
+            line += ", batched / W1 floor %.2f x" % (med["batched"] / (w1_bytes / (rate * 1e12) * 1e6))
+        print(line, flush=True)
+
+
 def merge_time(n=1024, din=128, calls=50):
     """mi_rollout_obs_stats alone over n rows of din columns (every row of the table, in order): device events around each call."""
     from mi355 import lib as milib
@@ -157,6 +206,9 @@ def merge_time(n=1024, din=128, calls=50):
     print("mi_rollout_obs_stats, %d x %d (three launches, device events): median %.1f us, min %.1f us, p90 %.1f us" % (n, din, np.median(ts), min(ts), np.percentile(ts, 90)), flush=True)
 
 
+if args.mlp:
+    mlp_table()
+    sys.exit(0)
 if args.envs is not None:
     envs_table()
     if args.obs_norm:
