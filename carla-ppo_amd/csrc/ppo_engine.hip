@@ -30,9 +30,11 @@ struct PpoEngine {
     long long gn_part, clip;                      // global-norm clipping: the block partials of the sum of squares (doubles), and {norm, scale, c, 0} of the last norm (mi_ppo_buffer(h, 2))
     float max_grad_norm;                          // 0 (calloc: the default): no clipping; > 0 or +inf: mi_ppo_apply_adam clips by the global norm (mi_ppo_set_max_grad_norm)
     long long f_klpart;                           // KL penalty (mi_ppo_train_step_kl): one float per loss block
+    long long wg_scr[2], wg_bytes;                // per-layer path: row-split slabs of its filter and bias gradients (mi_gemm_wgrad_bias_ws), one piece per stream of the backward pass
     long long f_h1, f_h2, f_dh1, f_dh2, f_part;   // fused step (ppo_fused.hip): [3][M][H1], [3][M][H2], [2][M][H1], [2][M][H2], loss-block partials
     int last_M;
     int precision;                                // MI_F32 (calloc: the default) or MI_BF16X3 (mi_ppo_set_precision): which instantiation of the fused GEMM stages runs
+    int wide;                                     // 0 (calloc: the default): the fused range ends at kin = 96; 1 / 2: at kin = 1024 (mi_ppo_set_wide_inputs).  Routing only
     hipStream_t side; hipEvent_t ev_fork, ev_join; int side_ok;     // second stream of the forked minibatch step (0 = not tried, 1 = ok, -1 = unavailable)
     float* P(int t) const { return params + off[t]; }
     float* PO(int t) const { return params_old + off[t]; }
@@ -65,6 +67,15 @@ void layout(PpoEngine& e) {
     e.f_gslab = wa(M > 256 ? ((M + 255) / 256) * e.total * 4 : 0);
     e.gn_part = wa(MI_GRAD_NORM_BLOCKS * 8); e.clip = wa(16);
     e.f_klpart = wa(((M + 31) / 32) * 4);
+    // the per-layer path's filter gradients, with the bias gradient as one more row of the same product (mi_gemm_wgrad_bias_ws: no column-sum launches), sum their
+    // row splits through slabs in a fixed order, not through fp32 atomics: two runs are bitwise equal, as on the fused path.  One piece per stream, sized for the
+    // largest layer of a side at the row count with the most splits (the launches of a side are ordered on its stream)
+    e.wg_bytes = 0;
+    {
+        const int kn[4][2] = {{d.h2, d.num_actions}, {d.h1, d.h2}, {e.kin, d.h1}, {d.h2, 1}};
+        for (int i = 0; i < 4; ++i) { const long long nb = mi_gemm_wgrad_scratch_bytes(MI_F32, 1 << 20, kn[i][0], kn[i][1]); if (nb > e.wg_bytes) e.wg_bytes = nb; }
+    }
+    e.wg_scr[0] = wa(e.wg_bytes); e.wg_scr[1] = wa(e.wg_bytes);
     e.ws_total = w;
 }
 
@@ -96,10 +107,14 @@ __global__ void head_dgrad_kernel(const float* __restrict__ du, const float* __r
 
 #define CK(call) do { int rc__ = (call); if (rc__ != MI_OK) return rc__; } while (0)
 
-// the fused kernels serve the shapes they were built for (the reference's 500 / 300 trunk, <= 8 actions); anything else takes the per-layer path
+// the fused kernels serve the shapes they were built for (the reference's 500 / 300 trunk, <= 8 actions, and the input widths the engine's mode allows:
+// mi_ppo_set_wide_inputs); anything else takes the per-layer path
 bool fused_enabled(const PpoEngine* e);
 
-bool fused_enabled(const PpoEngine* e) { return knob(K_PPO_FUSED) && mi_ppo_fused_shape_in_range(e->d.num_actions, e->d.h2, e->kin); }
+bool fused_enabled(const PpoEngine* e) {
+    if (!knob(K_PPO_FUSED)) return false;
+    return e->wide ? mi_ppo_fused_shape_in_wide_range(e->d.num_actions, e->d.h2, e->kin) : mi_ppo_fused_shape_in_range(e->d.num_actions, e->d.h2, e->kin);
+}
 
 bool x3(const PpoEngine* e) { return e->precision == MI_BF16X3; }
 
@@ -123,6 +138,7 @@ void fill_fused(const PpoEngine* e, PpoFusedParams& q, const float* states, int 
     q.gslab = d.max_batch > 256 ? (float*)e->at(e->f_gslab) : nullptr; q.gslab_stride = e->total;      // (total is a multiple of 8 floats: pad8 per tensor)
     q.n_nets = 3;
     q.clip_eps = d.clip_eps; q.value_scale = d.value_scale; q.entropy_scale = d.entropy_scale;
+    q.wide = e->wide; q.max_batch = d.max_batch;
 }
 
 // One minibatch step of the fused kernels, described ONCE for the six entries below (mi_ppo_forward_backward's fused branch, mi_ppo_train_step[_idx|_dp|_vclip|_kl]):
@@ -317,22 +333,16 @@ int mi_ppo_forward_backward(void* h, void* stream, const float* states, const fl
         CK(mi_check_launch("head_dgrad"));
     }
     release();
-    // policy side (caller's stream): head, trunk
-    CK(mi_colsum(st, MI_F32, e->at(e->du), M, A, e->G(5)));
-    CK(mi_gemm_wgrad(st, MI_F32, e->at(e->h2), e->at(e->du), M, d.h2, A, e->G(4)));
-    CK(mi_colsum(st, MI_F32, e->at(e->dh2), M, d.h2, e->G(3)));
-    CK(mi_gemm_wgrad(st, MI_F32, e->at(e->h1), e->at(e->dh2), M, d.h1, d.h2, e->G(2)));
+    // policy side (caller's stream): head, trunk.  (Filter + bias gradients: the ordered form, see layout())
+    CK(mi_gemm_wgrad_bias_ws(st, MI_F32, e->at(e->h2), e->at(e->du), M, d.h2, A, e->G(4), e->G(5), e->at(e->wg_scr[0]), e->wg_bytes));
+    CK(mi_gemm_wgrad_bias_ws(st, MI_F32, e->at(e->h1), e->at(e->dh2), M, d.h1, d.h2, e->G(2), e->G(3), e->at(e->wg_scr[0]), e->wg_bytes));
     CK(mi_gemm_bias_act(st, MI_F32, e->at(e->dh2), M, d.h2, e->P(2), 1, d.h1, nullptr, 0, e->at(e->h1), e->at(e->dh1), 1, 1));
-    CK(mi_colsum(st, MI_F32, e->at(e->dh1), M, d.h1, e->G(1)));
-    CK(mi_gemm_wgrad(st, MI_F32, e->at(e->s_pad), e->at(e->dh1), M, e->kin, d.h1, e->G(0)));
+    CK(mi_gemm_wgrad_bias_ws(st, MI_F32, e->at(e->s_pad), e->at(e->dh1), M, e->kin, d.h1, e->G(0), e->G(1), e->at(e->wg_scr[0]), e->wg_bytes));
     // value side (second stream): head, trunk
-    CK(mi_colsum(sw, MI_F32, e->at(e->dv), M, 1, e->G(12)));
-    CK(mi_gemm_wgrad(sw, MI_F32, e->at(e->g2), e->at(e->dv), M, d.h2, 1, e->G(11)));
-    CK(mi_colsum(sw, MI_F32, e->at(e->dg2), M, d.h2, e->G(10)));
-    CK(mi_gemm_wgrad(sw, MI_F32, e->at(e->g1), e->at(e->dg2), M, d.h1, d.h2, e->G(9)));
+    CK(mi_gemm_wgrad_bias_ws(sw, MI_F32, e->at(e->g2), e->at(e->dv), M, d.h2, 1, e->G(11), e->G(12), e->at(e->wg_scr[1]), e->wg_bytes));
+    CK(mi_gemm_wgrad_bias_ws(sw, MI_F32, e->at(e->g1), e->at(e->dg2), M, d.h1, d.h2, e->G(9), e->G(10), e->at(e->wg_scr[1]), e->wg_bytes));
     CK(mi_gemm_bias_act(sw, MI_F32, e->at(e->dg2), M, d.h2, e->P(9), 1, d.h1, nullptr, 0, e->at(e->g1), e->at(e->dg1), 1, 1));
-    CK(mi_colsum(sw, MI_F32, e->at(e->dg1), M, d.h1, e->G(8)));
-    CK(mi_gemm_wgrad(sw, MI_F32, e->at(e->s_pad), e->at(e->dg1), M, e->kin, d.h1, e->G(7)));
+    CK(mi_gemm_wgrad_bias_ws(sw, MI_F32, e->at(e->s_pad), e->at(e->dg1), M, e->kin, d.h1, e->G(7), e->G(8), e->at(e->wg_scr[1]), e->wg_bytes));
     join();
     e->last_M = M;
     return MI_OK;
@@ -524,6 +534,24 @@ int mi_ppo_set_precision(void* h, int dtype) {
         return mi_fail(MI_ERR_SHAPE, "mi_ppo_set_precision: the split-bf16 mode needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0)");
     e->precision = dtype;
     return MI_OK;
+}
+
+// Wide inputs (include/mi355_carla.h): which input widths the fused kernels take, and which layer-1 kernel serves the wide ones.  Routing only: the parameter
+// layout (kin rows of W1, the last kin - din of them zero) is the same on every path, so the mode may change between two steps.
+int mi_ppo_set_wide_inputs(void* h, int mode) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_set_wide_inputs: null handle");
+    if (mode < 0 || mode > 2) return mi_fail(MI_ERR_ARG, "mi_ppo_set_wide_inputs: mode is 0 (fused range kin <= 96), 1 (kin <= 1024, the K-split layer 1) or 2 (kin <= 1024, ppo_l1_kernel)");
+    if (x3(e) && mode == 0 && !mi_ppo_fused_shape_in_range(e->d.num_actions, e->d.h2, e->kin))
+        return mi_fail(MI_ERR_SHAPE, "mi_ppo_set_wide_inputs: the engine is in the split-bf16 mode, which has no per-layer form (mi_ppo_set_precision(MI_F32) first)");
+    e->wide = mode;
+    return MI_OK;
+}
+
+int mi_ppo_wide_inputs(void* h) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_wide_inputs: null handle");
+    return e->wide;
 }
 
 int mi_ppo_precision(void* h) {

@@ -185,6 +185,83 @@ __global__ __launch_bounds__(256) void ppo_l1_kernel(const PpoFusedParams q) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// layer 1 at wide K (mi_ppo_set_wide_inputs mode 1, kin > 96): grid (ceil(H1 / 32), n_nets, ceil(M / 32)); the four waves of a block own ONE 32 x 32 output tile and
+// split K = kin as ppo_l2_kernel splits H1: wave w takes the contiguous k-steps [w per, min(ksteps, (w + 1) per)), per = ceil(ksteps / 4) (steps of 8; X3: k-blocks
+// of 16), requests its share a chunk of 16 steps (X3: 8 k-blocks) at a time -- kin <= 512 is one chunk --, and the partial tiles meet in LDS and are added in that
+// kernel's fixed order.  Where ppo_l1_kernel gives one wave the whole K (kin = 520: 65 dependent steps in 8 latency rounds), this is 17 steps in 2.
+//   - a wave whose share is empty (X3 at kin = 136: 9 k-blocks, 3 per wave, none for wave 3) runs no step, stores its zero tile and reaches the barrier;
+//   - there is no return in front of the barrier: the grid has no column tile past H1;
+//   - a k at or past din contributes 0.0 whatever the table holds behind the row (ppo_l1_kernel reads the next row against a zero weight row: NaN x 0 there);
+//   - block column 0 of net 0 writes the gathered minibatch s_gath, all of its columns, for every H1.
+// ---------------------------------------------------------------------------------------------------------------------
+template <bool X3>
+__global__ __launch_bounds__(256) void ppo_l1_wide_kernel(const PpoFusedParams q) {
+    __shared__ float red[3][16][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lrow = lane & 31, lgrp = lane >> 5;
+    const int net = blockIdx.y, m0 = blockIdx.z * 32, n0 = blockIdx.x * 32;
+    const int din = q.din;
+    if (q.row_idx && q.s_gath && net == 0 && blockIdx.x == 0) {      // rows m0 .. m0 + 31, columns dealt to the block's 8 half-waves
+        const int m = m0 + lrow;
+        if (m < q.M) {
+            const long long srow_g = min(max(q.row_idx[m], 0), q.n_rows - 1);
+            for (int k = wave * 2 + lgrp; k < din; k += 8) q.s_gath[(long long)m * din + k] = q.states[srow_g * din + k];
+        }
+    }
+    const float* th = pf_theta(q, net);
+    const float* W = th + pf_off(q, net, 0);
+    const float* bias = th + pf_off(q, net, 1);
+    const int n = n0 + lrow;
+    const int ksteps = X3 ? (q.kin + 15) / 16 : (q.kin + 7) / 8, per = (ksteps + 3) / 4;
+    const int sb = wave * per, se = min(ksteps, sb + per);
+    const int mrow = min(m0 + lrow, q.M - 1);
+    const int srow = q.row_idx ? min(max(q.row_idx[mrow], 0), q.n_rows - 1) : mrow;
+    // (both sizes are below 2^31 bytes: checked by the host before the launch)
+    const __amdgpu_buffer_rsrc_t rsS = PF_RSRC(q.states, (long long)(q.row_idx ? q.n_rows : q.M) * din * 4), rsW = PF_RSRC(W, (long long)q.kin * q.H1 * 4);
+    const unsigned arow = (unsigned)srow * (unsigned)din, H1u = (unsigned)q.H1;
+    f32x16_t acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    // the state operand: k < din is the row's own entry; a k in [din, kin + 7] is the zero padding -- the load is issued (inside the table or answered 0.0 by the
+    // range check) and its value dropped, so that neither a NaN of the next row nor a lane-dependent branch gets in
+    if constexpr (X3) {
+        pf_mma_x3_chunked<8>(sb, se,
+            [&](int s_) { const int k = s_ * 16 + lgrp * 8; f32x8_t a;
+#pragma unroll
+                          for (int e = 0; e < 8; ++e) { const float x = pf_ld(rsS, (arow + (unsigned)(k + e)) * 4u); a[e] = k + e < din ? x : 0.f; }
+                          return a; },
+            [&](int s_) { const unsigned k = (unsigned)(s_ * 16 + lgrp * 8); f32x8_t b;
+#pragma unroll
+                          for (int e = 0; e < 8; ++e) b[e] = pf_ld(rsW, ((k + e) * H1u + (unsigned)n) * 4u);
+                          return b; }, acc);
+    } else {
+        pf_mma_chunked<16>(sb, se,
+            [&](int s_) { const int k = s_ * 8 + lgrp * 4; f32x4 a;
+#pragma unroll
+                          for (int e = 0; e < 4; ++e) { const float x = pf_ld(rsS, (arow + (unsigned)(k + e)) * 4u); a[e] = k + e < din ? x : 0.f; }
+                          return a; },
+            [&](int s_) { const unsigned k = (unsigned)(s_ * 8 + lgrp * 4); f32x4 b;
+#pragma unroll
+                          for (int e = 0; e < 4; ++e) b[e] = pf_ld(rsW, ((k + e) * H1u + (unsigned)n) * 4u);
+                          return b; }, acc);
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) red[wave - 1][r][lane] = acc[r];
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const float bn = pf_ld(PF_RSRC(bias, (long long)q.H1 * 4), (unsigned)n * 4u);
+        const __amdgpu_buffer_rsrc_t rsO = PF_RSRC(q.h1 + (long long)net * q.M * q.H1, (long long)q.M * q.H1 * 4);
+        const unsigned col = n < q.H1 ? (unsigned)n * 4u : PF_OOB;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float v = ((acc[r] + red[0][r][lane]) + (red[1][r][lane] + red[2][r][lane]));
+            pf_st(rsO, (unsigned)(m0 + pf_row(r, lgrp)) * H1u * 4u + col, fmaxf(v + bn, 0.f));      // rows past M fall outside the descriptor
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // layer 2: grid (ceil(H2 / 32), n_nets, ceil(M / 32)); the four waves split K = H1, partial tiles meet in LDS.
 // ---------------------------------------------------------------------------------------------------------------------
 template <bool X3>
@@ -928,11 +1005,24 @@ using namespace mi;
 
 // shapes the fused kernels are built for (checked BEFORE anything is launched; the engine falls back to the per-layer path otherwise)
 bool mi_ppo_fused_shape_in_range(int A, int H2, int kin) { return A >= 1 && A <= PF_MAX_ACT && H2 <= PF_H2MAX && H2 % 4 == 0 && kin <= 96; }
+// ... and with wide inputs switched on (mi_ppo_set_wide_inputs): the same limits on A and H2, kin <= 1024
+constexpr int PF_KIN_WIDE = 1024;
+bool mi_ppo_fused_shape_in_wide_range(int A, int H2, int kin) { return A >= 1 && A <= PF_MAX_ACT && H2 <= PF_H2MAX && H2 % 4 == 0 && kin <= PF_KIN_WIDE; }
 static int pf_check_shape(const PpoFusedParams& q, const char* who) {
-    if (mi_ppo_fused_shape_in_range(q.A, q.H2, q.kin)) return MI_OK;
-    static thread_local char msg[160];
-    snprintf(msg, sizeof(msg), "%s: shape outside the fused kernels' range (1 <= num_actions <= 8, H2 <= 320 and a multiple of 4, inputs <= 96)", who);
-    return mi_fail(MI_ERR_SHAPE, msg);
+    static thread_local char msg[224];
+    if (!(q.wide ? mi_ppo_fused_shape_in_wide_range(q.A, q.H2, q.kin) : mi_ppo_fused_shape_in_range(q.A, q.H2, q.kin))) {
+        snprintf(msg, sizeof(msg), "%s: shape outside the fused kernels' range (1 <= num_actions <= 8, H2 <= 320 and a multiple of 4, inputs <= %d)", who, q.wide ? PF_KIN_WIDE : 96);
+        return mi_fail(MI_ERR_SHAPE, msg);
+    }
+    // the buffer descriptors take their size as an int and the kernels form 32-bit byte offsets: a state table (n_rows rows with a row index, else the M rows of the
+    // call), the padded minibatch of the engine's max_batch rows and a layer-1 kernel stay below 2 GiB
+    const long long lim = 1ll << 31, rows = q.row_idx ? q.n_rows : q.M;
+    if (rows * q.din * 4 >= lim || (long long)(q.max_batch > q.M ? q.max_batch : q.M) * q.kin * 4 >= lim || (long long)q.kin * q.H1 * 4 >= lim) {
+        snprintf(msg, sizeof(msg), "%s: a state table of %lld rows x %d inputs (or max_batch x the padded width, or the layer-1 kernel) reaches 2 GiB: the fused kernels address it with 32-bit byte offsets",
+                 who, rows, q.din);
+        return mi_fail(MI_ERR_SHAPE, msg);
+    }
+    return MI_OK;
 }
 
 int mi_ppo_fused_predict(hipStream_t st, PpoFusedParams& q, const float* noise, int greedy, float* action, float* value) {
@@ -996,11 +1086,15 @@ int mi_ppo_fused_partial_floats(int M) { return ((M + 31) / 32) * PF_NPART; }
 // forward only (PPO.predict, the cache of log pi_old): layers 1-2 of `n_nets` nets, then the caller's head kernel; x3: split-bf16 instantiations
 int mi_ppo_fused_trunks(hipStream_t st, const PpoFusedParams& q, bool x3) {
     const dim3 g1((q.H1 + 127) / 128, q.n_nets, (q.M + 31) / 32), g2((q.H2 + 31) / 32, q.n_nets, (q.M + 31) / 32);
+    const dim3 g1w((q.H1 + 31) / 32, q.n_nets, (q.M + 31) / 32);
+    const bool wide_l1 = q.wide == 1 && q.kin > 96;       // (mi_ppo_set_wide_inputs: mode 2 keeps ppo_l1_kernel at every width)
     if (x3) {
-        hipLaunchKernelGGL(ppo_l1_kernel<true>, g1, dim3(256), 0, st, q);
+        if (wide_l1) hipLaunchKernelGGL(ppo_l1_wide_kernel<true>, g1w, dim3(256), 0, st, q);
+        else hipLaunchKernelGGL(ppo_l1_kernel<true>, g1, dim3(256), 0, st, q);
         hipLaunchKernelGGL(ppo_l2_kernel<true>, g2, dim3(256), 0, st, q);
     } else {
-        hipLaunchKernelGGL(ppo_l1_kernel<false>, g1, dim3(256), 0, st, q);
+        if (wide_l1) hipLaunchKernelGGL(ppo_l1_wide_kernel<false>, g1w, dim3(256), 0, st, q);
+        else hipLaunchKernelGGL(ppo_l1_kernel<false>, g1, dim3(256), 0, st, q);
         hipLaunchKernelGGL(ppo_l2_kernel<false>, g2, dim3(256), 0, st, q);
     }
     return mi_check_launch("ppo_fused_trunks");

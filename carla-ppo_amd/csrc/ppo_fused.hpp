@@ -16,7 +16,11 @@ struct PpoFusedParams {
     float *du, *dv, *partial, *losses, *mean_out;
     // minibatch gather fused into the step (mi_ppo_train_step_idx): sample m of the minibatch is row row_idx[m] of the horizon-batch tables
     // states / actions / returns / adv / logp_old (n_rows rows each); layer 1 also leaves the gathered states in s_gath [M, din] for the filter gradient
-    const int* row_idx; int n_rows; float* s_gath;
+    const int* row_idx; int n_rows;
+    // wide inputs (mi_ppo_set_wide_inputs), in the 4 bytes of padding behind n_rows, so that no field moves and no kernel's argument offsets change.  The engine's
+    // mode -- 0: the fused range ends at kin = 96; 1 / 2: at kin = 1024, and layer 1 of kin > 96 runs as ppo_l1_wide_kernel (1) or as ppo_l1_kernel (2)
+    int wide;
+    float* s_gath;
     const float* logp_old;                                // cached log pi_old(a|s) per sample (nullptr: recomputed from net 2)
     float* logp_out;                                      // when set: the loss kernel also stores log pi(a|s) (used to fill the cache)
     int n_nets;                                           // 3, or 2 with the cache
@@ -34,14 +38,18 @@ struct PpoFusedParams {
     // old policy's action means per table row, indexed like logp_old (nullptr with logp_old == nullptr: formed in the step from net 2).  kl_partial: one float per
     // loss block, that block's sum of KL[m] (engine workspace).  mean_old_out: where the log pi_old pass of ppo_predict_head_kernel also stores its means
     // (mi_ppo_old_policy_cache; nullptr: nowhere)
-    int kl_on; float kl_coef; const float* mean_old; float* kl_partial; float* mean_old_out;
+    int kl_on; float kl_coef;
+    int max_batch;                                        // the engine's, for the 2 GiB limit of the 32-bit byte offsets (host side only; in the padding behind kl_coef)
+    const float* mean_old; float* kl_partial; float* mean_old_out;
 };
+static_assert(sizeof(PpoFusedParams) == 448, "PpoFusedParams: a field moved (the kernels' argument offsets are pinned by profiles/r28_ppo_wide_inputs.md)");
 
 }  // namespace mi
 
 int mi_ppo_fused_partial_floats(int M);
 int mi_ppo_fused_trunks(hipStream_t st, const mi::PpoFusedParams& q, bool x3);
 bool mi_ppo_fused_shape_in_range(int A, int H2, int kin);
+bool mi_ppo_fused_shape_in_wide_range(int A, int H2, int kin);      // the same limits on A and H2, kin <= 1024 (mi_ppo_set_wide_inputs)
 int mi_ppo_fused_step(hipStream_t st, mi::PpoFusedParams& q, int fuse_adam, bool x3);      // x3: split-bf16 GEMM stages (MI_BF16X3)
 int mi_ppo_fused_predict(hipStream_t st, mi::PpoFusedParams& q, const float* noise, int greedy, float* action, float* value);
 int mi_ppo_fused_logp_old(hipStream_t st, mi::PpoFusedParams& q, float* out, bool x3);      // (q.mean_old_out set: the old policy's means as well)

@@ -63,10 +63,20 @@ def kl_stats_summary(sums):
     return {"samples": int(round(n)), "kl": float(mean), "kl_std": float(np.sqrt(max(s[2] / n - mean * mean, 0.0))), "kl_mean_part": float(s[3] / n)}
 
 
+def wide_inputs_mode(mode, who="wide_inputs"):
+    """The mode of mi_ppo_set_wide_inputs: False / 0, True / 1 or 2 -> 0, 1 or 2; anything else raises ValueError.  No device and no library involved."""
+    if isinstance(mode, bool):
+        return int(mode)
+    if isinstance(mode, (int, np.integer)) and 0 <= int(mode) <= 2:
+        return int(mode)
+    raise ValueError("%s: the mode is 0 (fused kernels up to 96 inputs), 1 (up to 1024, K-split layer 1) or 2 (up to 1024, narrow layer 1), got %r" % (who, mode))
+
+
 class PpoDevice:
     def __init__(self, input_dim, num_actions, action_low, action_high, clip_eps, value_scale, entropy_scale,
-                 hidden=(500, 300), max_batch=256, device=None, precision="fp32"):
+                 hidden=(500, 300), max_batch=256, device=None, precision="fp32", wide_inputs=0):
         self.precision = milib.ppo_precision_name(precision)
+        self.wide_inputs = wide_inputs_mode(wide_inputs, "PpoDevice")      # mi_ppo_set_wide_inputs: 0 = the fused range ends at 96 inputs (set_wide_inputs)
         require_gpu()
         self.L = milib.get()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -112,8 +122,10 @@ class PpoDevice:
             self.L.mi_ppo_destroy(old)
         if not self.handle:
             raise milib.MiError("mi_ppo_create: " + self.L.cdll.mi_last_error().decode())
-        # a new engine starts in fp32: the mode is applied to every engine this object creates (ensure_batch recreates it for larger batches)
+        # a new engine starts in fp32 and with the narrow fused range: both modes are applied to every engine this object creates (ensure_batch recreates it for
+        # larger batches), the range first -- it decides whether the split mode has kernels
         try:
+            self.L.mi_ppo_set_wide_inputs(self.handle, self.wide_inputs)
             self.L.mi_ppo_set_precision(self.handle, milib.PPO_PRECISIONS[self.precision])      # raises MiError (no fp32 fallback) where the mode has no kernels
         except milib.MiError:
             self.L.mi_ppo_destroy(self.handle)
@@ -298,6 +310,25 @@ class PpoDevice:
     def engine_precision(self):
         """The engine's own record of its mode (mi_ppo_precision): MI_F32 or MI_BF16X3."""
         return int(self.L.cdll.mi_ppo_precision(self.handle))      # (the raw call: a mode is a non-zero return, not an error)
+
+    def set_precision(self, precision):
+        """The precision of the training forms (mi_ppo_set_precision): "fp32" or "bf16x3".  MiError where the split mode has no kernels (an engine on the per-layer
+        path); the mode is then unchanged.  Kept across ensure_batch."""
+        name = milib.ppo_precision_name(precision)
+        self.L.mi_ppo_set_precision(self.handle, milib.PPO_PRECISIONS[name])
+        self.precision = name
+
+    def set_wide_inputs(self, mode):
+        """Which input widths the fused kernels take (mi_ppo_set_wide_inputs): 0 (the default) up to 96 padded inputs; 1 up to 1024, layer 1 of a wide policy through
+        the K-split kernel; 2 up to 1024 with the narrow layer-1 kernel at every width (kept for measuring 1 against).  Routing only: parameters and optimiser state
+        are laid out the same on every path, so it may change between two steps.  Kept across ensure_batch."""
+        mode = wide_inputs_mode(mode, "PpoDevice.set_wide_inputs")
+        self.L.mi_ppo_set_wide_inputs(self.handle, mode)
+        self.wide_inputs = mode
+
+    def engine_wide_inputs(self):
+        """The engine's own record of the mode (mi_ppo_wide_inputs)."""
+        return int(self.L.cdll.mi_ppo_wide_inputs(self.handle))      # (the raw call: a mode is a non-zero return, not an error)
 
     def fused_ok(self):
         """True when the fused kernels (in-kernel minibatch gather, cached log pi_old) take this engine's shape; else only the per-layer path runs."""

@@ -32,6 +32,16 @@ def _max_grad_norm_from_env():
         raise ValueError("MI355_PPO_MAX_GRAD_NORM=%r: expected a positive float or inf" % text) from None
 
 
+def _wide_inputs_from_env():
+    """MI355_PPO_WIDE_INPUTS (unset or empty: off) -> False for "0", True for "1"; anything else raises ValueError."""
+    text = os.environ.get("MI355_PPO_WIDE_INPUTS", "").strip()
+    if text in ("", "0"):
+        return False
+    if text == "1":
+        return True
+    raise ValueError("MI355_PPO_WIDE_INPUTS=%r: expected 0 or 1" % text)
+
+
 def _kl_coef_from_env():
     """MI355_PPO_KL_COEF (unset or empty: off) -> None or a finite float >= 0 (a fixed coefficient, no target); anything else raises ValueError."""
     text = os.environ.get("MI355_PPO_KL_COEF", "").strip()
@@ -84,6 +94,9 @@ class PPO():
         # kl_penalty_state() / load_kl_penalty_state() carry it.
         self.kl_penalty = _kl_coef_from_env()
         self.kl_target = None
+        # wide inputs (set_wide_inputs): the fused kernels for a policy of more than 96 inputs (a VAE of more than 93 latents).  MI355_PPO_WIDE_INPUTS=1 supplies it
+        # when set_wide_inputs is not called (the reference's train.py builds this object itself).  Routing only; not part of a checkpoint.
+        self.wide_inputs = _wide_inputs_from_env()
         self.input_dim = int(np.asarray(input_shape).reshape(-1)[0])
         self.num_actions = int(action_space.shape[0])
         self.action_low = np.asarray(action_space.low, np.float32).reshape(-1)
@@ -122,7 +135,7 @@ class PPO():
             from mi355.init import seed_from_numpy_state
             self.seed = seed_from_numpy_state()
         self.dev = PpoDevice(self.input_dim, self.num_actions, self.action_low, self.action_high,
-                             self.epsilon, self.value_scale, self.entropy_scale, precision=self.precision)
+                             self.epsilon, self.value_scale, self.entropy_scale, precision=self.precision, wide_inputs=int(self.wide_inputs))
         self.dev.set_max_grad_norm(self.max_grad_norm)
         values = self._init_values or init_ppo(self.seed, self.input_dim, self.num_actions, self.initial_std)
         # policy_old is a separately initialised copy in the reference; the trainer overwrites it with
@@ -148,6 +161,18 @@ class PPO():
         self.max_grad_norm = milib.max_grad_norm_value(value, "PPO.set_max_grad_norm")
         if self.dev is not None:
             self.dev.set_max_grad_norm(self.max_grad_norm)
+
+    def set_wide_inputs(self, on=True):
+        """Let the fused kernels take a policy of up to 1024 (padded) inputs instead of 96 -- a VAE of more than 93 latents: train_vae.py --z_dim 128, ConvVAE's own
+        default of 512 (include/mi355_carla.h, mi_ppo_set_wide_inputs mode 1).  Off (the default), such a policy trains on the per-layer path, where the in-kernel
+        minibatch gather, the cached log pi_old, value clipping, the KL penalty, the update diagnostics and the bf16x3 precision do not exist.  A policy of at most 96
+        inputs runs the same launches either way.  Usable before or after init_session(); anything but a bool raises ValueError.  Routing only: it may change between
+        two updates and is no part of a checkpoint."""
+        if not isinstance(on, bool):
+            raise ValueError("PPO.set_wide_inputs: on is True or False, got %r" % (on,))
+        self.wide_inputs = on
+        if self.dev is not None:
+            self.dev.set_wide_inputs(int(on))
 
     def set_value_clip(self, value):
         """Clip the value loss as the original PPO2 code does (baselines ppo2; clip_vloss / clip_range_vf elsewhere): with eps_v = value the value term of a sample is
@@ -283,6 +308,7 @@ class PPO():
                 if kl or old_values is not None:
                     raise ValueError("%s needs the fused one-call step (this policy's shape is outside the fused kernels' range, MI355_PPO_FUSED=0 / MI355_PPO_IDX=0, "
                                      "or data parallel without the library's communicator)" % ("PPO: the KL penalty" if kl else "PPO._step_rows: value clipping"))
+                # (the texts above are pinned word for word by tests/test_ppo_step_dispatch_host.py; more than 96 inputs: PPO.set_wide_inputs(), as rollout.py's say)
                 # (shapes outside the fused kernels' range -- e.g. more than 8 actions -- have no in-kernel gather: mi_ppo_fused_shape_ok says so up front and the
                 #  rows are gathered here instead; row values themselves are clamped into the tables by the kernels)
                 mb = rows.to("cuda" if rows.is_cuda else rows.device).long()

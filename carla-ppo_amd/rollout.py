@@ -101,6 +101,11 @@ bitwise reproducible):
 and every dict in `epochs` of update_with_diagnostics() gains `grad_norm_max` and `clipped_steps`.  With the setting off none of these keys appears, and the update
 makes the launches it always made.
 
+A policy of more than 96 inputs -- a VAE of more than 93 latents: train_vae.py --z_dim 128, ConvVAE's default of 512 -- is outside the fused kernels' default range:
+update() then gathers every minibatch on the host side and evaluates the old policy in every step, and update_with_diagnostics(), PPO.set_value_clip() and
+PPO.set_kl_penalty() raise ValueError.  ppo.set_wide_inputs() (MI355_PPO_WIDE_INPUTS=1 under the unchanged reference scripts) extends the range to 1024 inputs:
+the step classes, both buffers and every setting below then take the routes they take for the shipped 67-input agent.  State tables stay below 2 GiB.
+
 Both buffers can clip the value loss as the original PPO2 code does (baselines ppo2; clip_vloss / clip_range_vf elsewhere).  The tables already hold the value of
 every step as it was when the data was collected; with PPO.set_value_clip(eps_v) every SGD step of update() passes that table along (mi_ppo_train_step_vclip: one more
 gather per sample in the loss kernel) and a sample's value term becomes max((V - R)^2, (V_c - R)^2) with V_c = V clamped into V_old +- eps_v: the value net gets no
@@ -1128,14 +1133,14 @@ class RolloutBuffer:
         if int(batch_size) < 1 or int(num_epochs) < 0:
             raise ValueError(who + ".update: batch_size >= 1, num_epochs >= 0")
         if vclip is not None and not self.ppo._need_dev().fused_ok():
-            raise ValueError(who + ".update: value clipping (PPO.set_value_clip) exists only in the fused kernels (this policy's shape is outside their range or "
+            raise ValueError(who + ".update: value clipping (PPO.set_value_clip) exists only in the fused kernels (this policy's shape is outside their range (more than 96 inputs: PPO.set_wide_inputs()) or "
                              "MI355_PPO_FUSED=0)")
         if klp is not None and not self.ppo._need_dev().fused_ok():
-            raise ValueError(who + ".update: the KL penalty (PPO.set_kl_penalty) exists only in the fused kernels (this policy's shape is outside their range or "
+            raise ValueError(who + ".update: the KL penalty (PPO.set_kl_penalty) exists only in the fused kernels (this policy's shape is outside their range (more than 96 inputs: PPO.set_wide_inputs()) or "
                              "MI355_PPO_FUSED=0)")
         if diag is not None and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update_with_diagnostics: the statistics pass reads the cached log pi_old, which only the fused kernels fill "
-                             "(this policy's shape is outside their range or MI355_PPO_FUSED=0)")
+                             "(this policy's shape is outside their range (more than 96 inputs: PPO.set_wide_inputs()) or MI355_PPO_FUSED=0)")
         self.rows.check_update()
         recorded = np.arange(self.horizon)[None, :] < self.rows.lengths[:, None]
         if self._reward_scaling is not None and not np.isfinite(self.rows.rewards[recorded]).all():

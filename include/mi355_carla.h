@@ -559,7 +559,9 @@ int mi_ppo_update_old(void* h, void* stream);
  * scalars of ppo.py:150-163); mi_ppo_buffer(h, 1): action_mean [M,A] of the last predict / train step; mi_ppo_buffer(h, 3): the step's workspace dv [M], the
  * gradient of the loss with respect to each sample's value-head output as the last step formed it (exactly 0 where value clipping stops it) */
 int mi_ppo_predict(void* h, void* stream, const float* states, int M, const float* noise, int greedy, float* action, float* value);
-/* gradient half + optimiser half of PPO.train (= north_star "learn") — ppo.py:218-229 */
+/* gradient half + optimiser half of PPO.train (= north_star "learn") — ppo.py:218-229.  Both paths of mi_ppo_forward_backward are bitwise reproducible: the
+ * per-layer one (shapes outside the fused range, MI355_PPO_FUSED=0) adds the row splits of its filter and bias gradients in a fixed order (mi_gemm_wgrad_bias_ws on
+ * slabs in the workspace), as the fused kernels do */
 int mi_ppo_forward_backward(void* h, void* stream, const float* states, const float* actions, const float* returns, const float* advantage, int M, float inv_m, float grad_scale);
 int mi_ppo_apply_adam(void* h, void* stream, float alpha, float beta1, float beta2, float epsilon);
 /* PPO.train's device work in ONE call (single rank): fused forward / losses / backward / Adam, five launches — ppo.py:218-229; logp_old (optional):
@@ -573,8 +575,8 @@ int mi_ppo_train_step_idx(void* h, void* stream, const float* states, const floa
  * buffer through `comm` in stream order, tf.train.AdamOptimizer.  row_idx != NULL: the operands are this rank's horizon-batch tables (n_rows rows) and the gather of
  * train.py:199-204 stays inside the kernels; row_idx == NULL: contiguous minibatch tensors. */
 int mi_ppo_train_step_dp(void* h, void* comm, void* stream, const float* states, const float* actions, const float* returns, const float* advantage, const float* logp_old, const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, float alpha, float beta1, float beta2, float epsilon);
-/* 1: this engine's shape (1 <= num_actions <= 8, h2 <= 320 and a multiple of 4, padded input width <= 96) is inside the range of the fused kernels and they are
- * switched on, i.e. mi_ppo_train_step_idx / mi_ppo_logp_old will run; 0: only the per-layer path exists for it (mi_ppo_train_step and mi_ppo_forward_backward fall
+/* 1: this engine's shape (1 <= num_actions <= 8, h2 <= 320 and a multiple of 4, padded input width <= 96 -- <= 1024 with mi_ppo_set_wide_inputs(h, 1 or 2)) is inside
+ * the range of the fused kernels and they are switched on, i.e. mi_ppo_train_step_idx / mi_ppo_logp_old will run; 0: only the per-layer path exists for it (mi_ppo_train_step and mi_ppo_forward_backward fall
  * back by themselves; gather the minibatch on the host side instead of calling the _idx form).  Row indices are clamped into [0, n_rows) by the kernels. */
 int mi_ppo_fused_shape_ok(void* h);
 int mi_ppo_logp_old(void* h, void* stream, const float* states, const float* actions, int M, float* out);
@@ -589,6 +591,25 @@ int mi_ppo_logp_old(void* h, void* stream, const float* states, const float* act
 int mi_ppo_set_precision(void* h, int dtype);
 /* the engine's current precision (MI_F32 or MI_BF16X3) — ppo.py:42-66,112-147,218-229 */
 int mi_ppo_precision(void* h);
+/* wide inputs: which padded input widths kin = ceil(input_dim / 8) * 8 the fused kernels take -- ppo.py:16-66 with a VAE of more than 93 latents (train_vae.py
+ * --z_dim 128: 131 inputs; ConvVAE's own default z_dim = 512: 515).
+ *   mode 0 (the default of a new engine): kin <= 96, every launch as it always was; a wider policy runs the per-layer path, on which mi_ppo_train_step_idx,
+ *          _vclip, _kl, mi_ppo_old_policy_cache, mi_ppo_logp_old, mi_ppo_update_stats_idx, mi_ppo_kl_stats_idx and MI_BF16X3 return MI_ERR_SHAPE;
+ *   mode 1: kin <= 1024; layer 1 of an engine with kin > 96 runs as ppo_l1_wide_kernel (the four waves of a block split K and meet in LDS in a fixed order: no
+ *          atomics, two runs bitwise equal; a state entry at or past input_dim counts as 0.0 whatever the table holds there), every launch behind it is the one
+ *          the narrow range takes; an engine with kin <= 96 takes the launches of mode 0 bit for bit;
+ *   mode 2: kin <= 1024 with ppo_l1_kernel at every width (one wave walks the whole K; like mode 0 it reads up to 7 entries of the table row BEHIND a gathered
+ *          row against zero weights, so those must be finite) -- kept for measuring mode 1 against (tools/ppo_wide_bench.py).
+ * The other limits stay: 1 <= num_actions <= 8, h2 <= 320 and a multiple of 4.  The setting changes routing only -- the parameter layout (kin rows of W1, the
+ * last kin - input_dim of them zero, and zero in both Adam slots) is the same on every path -- so it may be switched between two steps, and it is no part of a
+ * checkpoint.  mi_ppo_fused_shape_ok reports the result.
+ * 2 GiB limit (every mode): the fused kernels address a state table through 32-bit byte offsets, so every fused entry returns MI_ERR_SHAPE and launches nothing
+ * when n_rows * input_dim * 4 >= 2^31 (a table handed over with row_idx: 1.04 M rows at 515 inputs; without row_idx the M rows of the call) or
+ * max_batch * kin * 4 >= 2^31.
+ * MI_ERR_ARG: mode outside 0..2; MI_ERR_SHAPE: mode 0 on an engine in MI_BF16X3 whose kin exceeds 96 (the split form has no per-layer path). */
+int mi_ppo_set_wide_inputs(void* h, int mode);
+/* the engine's mode (0, 1 or 2) */
+int mi_ppo_wide_inputs(void* h);
 /* per-epoch update diagnostics: how far the CURRENT policy theta has moved from the old one on M rows of the horizon-batch tables, and how well the value net
  * fits the returns -- one forward-only pass (policy and value trunks of theta in the engine's precision mode, one head kernel, one ordered reduction; four
  * launches, no backward, no optimiser).  Sample m is row row_idx[m] (int32, device; clamped into [0, n_rows)) of states / actions / returns / logp_old, gathered
