@@ -494,9 +494,11 @@ struct MlpRollArgs {
     const float *obs_mean, *obs_inv_std; float obs_clip; float* nstate;
     const int* table_rows; long long n_table_rows;
     float *tab_states, *tab_raw_states, *tab_actions, *tab_values, *tab_final_values;
+    const MiRolloutStack* stk;                               // latent stacking (the _stack entries): the statistics, table_rows and the states tables are read from it
 };
 
-#define MROLL_FAIL(code, text) return mi_fail(code, value ? "mi_mlp_rollout_value_batch: " text : "mi_mlp_rollout_step_batch: " text)
+#define MROLL_FAIL(code, text) return mi_fail(code, a.stk ? (value ? "mi_mlp_rollout_value_batch_stack: " text : "mi_mlp_rollout_step_batch_stack: " text) \
+                                                          : (value ? "mi_mlp_rollout_value_batch: " text : "mi_mlp_rollout_step_batch: " text))
 int mlp_rollout(bool value, void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
                 void* scratch, long long scratch_bytes, float* out, const MlpRollArgs& a) {
     MlpEngine* e = (MlpEngine*)mlp_h;
@@ -505,7 +507,8 @@ int mlp_rollout(bool value, void* mlp_h, void* ppo_h, void* stream, const unsign
     const bool norm = a.obs_mean != nullptr;
     if (a.table_rows && (a.n_table_rows < 1 || (value ? !a.tab_final_values : (!a.tab_states || !a.tab_actions || !a.tab_values || (norm && !a.tab_raw_states)))))
         MROLL_FAIL(MI_ERR_ARG, "missing tables");
-    if (norm) {
+    if (a.stk) CK(mi_rollout_stack_check(*a.stk, 0, 0, -1, value ? "mi_mlp_rollout_value_batch_stack" : "mi_mlp_rollout_step_batch_stack"));
+    else if (norm) {
         if (!a.obs_inv_std || !a.nstate) MROLL_FAIL(MI_ERR_ARG, "missing obs_mean / obs_inv_std / nstate");
         if (((uintptr_t)a.nstate) & 15) MROLL_FAIL(MI_ERR_ARG, "nstate must be 16-byte aligned");
         if (!(a.obs_clip > 0.f)) MROLL_FAIL(MI_ERR_ARG, "obs_clip is a positive value (+inf: never clamp)");
@@ -525,7 +528,8 @@ int mlp_rollout(bool value, void* mlp_h, void* ppo_h, void* stream, const unsign
     o += (long long)n * Z;
     mi::PpoFusedParams q;
     CK(mi_ppo_internal_fill(ppo_h, &q, mean_raw, 1));
-    if (q.din != Z + n_meas) MROLL_FAIL(MI_ERR_SHAPE, "z_dim + measurements must equal the policy's input size");
+    if (a.stk) CK(mi_rollout_stack_check(*a.stk, Z, n_meas, q.din, value ? "mi_mlp_rollout_value_batch_stack" : "mi_mlp_rollout_step_batch_stack"));
+    else if (q.din != Z + n_meas) MROLL_FAIL(MI_ERR_SHAPE, "z_dim + measurements must equal the policy's input size");
     if (q.A > 8) MROLL_FAIL(MI_ERR_ARG, "at most 8 actions");
     if (mi_ppo_internal_fill(ppo_h, &q, mean_raw, n) != MI_OK) MROLL_FAIL(MI_ERR_ARG, "n exceeds the PPO engine's max_batch");
     // every raw-sum buffer of the call starts at zero: the whole scratch as one piece, and the trunks' raw sums [net][n][H] (the value call: the value net's halves alone)
@@ -548,9 +552,10 @@ int mlp_rollout(bool value, void* mlp_h, void* ppo_h, void* stream, const unsign
         // table_rows NULL: the value heads read one int per environment whatever the tables are; with n_table_rows = 0 no row lies inside the table and nothing is
         // stored, so the list may be any n readable ints: the raw means
         const MiRolloutValueRec vrec = {a.table_rows ? a.table_rows : (const int*)mean_raw, a.table_rows ? a.n_table_rows : 0, a.tab_final_values};
-        return mi_rollout_value_batch(st, q, mean_raw, mean_bias, Z, measurements, n, out, vrec, norm ? &nrm : nullptr);
+        return mi_rollout_value_batch(st, q, mean_raw, mean_bias, Z, measurements, n, out, vrec, norm && !a.stk ? &nrm : nullptr, a.stk);
     }
     const MiRolloutRec rec = {a.table_rows, a.n_table_rows, norm ? a.tab_raw_states : a.tab_states, a.tab_actions, a.tab_values};
+    if (a.stk) return mi_rollout_policy_batch_stack(st, q, mean_raw, mean_bias, Z, measurements, noise, greedy, n, out, a.table_rows ? &rec : nullptr, *a.stk);
     if (norm) return mi_rollout_policy_batch_norm(st, q, mean_raw, mean_bias, Z, measurements, noise, greedy, n, out, a.table_rows ? &rec : nullptr, nrm);
     if (a.table_rows) return mi_rollout_policy_batch_rec(st, q, mean_raw, mean_bias, Z, measurements, noise, greedy, n, out, rec);
     return mi_rollout_policy_batch(st, q, mean_raw, mean_bias, Z, measurements, noise, greedy, n, out);
@@ -571,14 +576,33 @@ long long mi_mlp_rollout_workspace_bytes(const MiMlpVaeDesc* d, int n_envs) {
 int mi_mlp_rollout_step_batch(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
                               void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate,
                               const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values) {
-    const MlpRollArgs a = {obs_mean, obs_inv_std, obs_clip, nstate, table_rows, n_table_rows, tab_states, tab_raw_states, tab_actions, tab_values, nullptr};
+    const MlpRollArgs a = {obs_mean, obs_inv_std, obs_clip, nstate, table_rows, n_table_rows, tab_states, tab_raw_states, tab_actions, tab_values, nullptr, nullptr};
     return mlp_rollout(false, mlp_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, a);
 }
 
 int mi_mlp_rollout_value_batch(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n,
                                void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate,
                                const int* table_rows, long long n_table_rows, float* tab_final_values) {
-    const MlpRollArgs a = {obs_mean, obs_inv_std, obs_clip, nstate, table_rows, n_table_rows, nullptr, nullptr, nullptr, nullptr, tab_final_values};
+    const MlpRollArgs a = {obs_mean, obs_inv_std, obs_clip, nstate, table_rows, n_table_rows, nullptr, nullptr, nullptr, nullptr, tab_final_values, nullptr};
+    return mlp_rollout(true, mlp_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, a);
+}
+
+// the two entries with latent stacking (mi_rollout_step_batch_stack / mi_rollout_value_batch_stack behind this encoder chain)
+int mi_mlp_rollout_step_batch_stack(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
+                                    void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip,
+                                    const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values,
+                                    int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, int advance, float* sstate, float* older_out) {
+    const MiRolloutStack stk = {latent_stack, hist, n_lanes, lanes, first, advance, sstate, older_out, obs_mean, obs_inv_std, obs_clip, table_rows, n_table_rows, tab_states, tab_raw_states};
+    const MlpRollArgs a = {obs_mean, obs_inv_std, obs_clip, nullptr, table_rows, n_table_rows, tab_states, tab_raw_states, tab_actions, tab_values, nullptr, &stk};
+    return mlp_rollout(false, mlp_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, a);
+}
+
+int mi_mlp_rollout_value_batch_stack(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n,
+                                     void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip,
+                                     const int* table_rows, long long n_table_rows, float* tab_final_values,
+                                     int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, float* sstate) {
+    const MiRolloutStack stk = {latent_stack, hist, n_lanes, lanes, first, 0, sstate, nullptr, obs_mean, obs_inv_std, obs_clip, nullptr, 0, nullptr, nullptr};
+    const MlpRollArgs a = {obs_mean, obs_inv_std, obs_clip, nullptr, table_rows, n_table_rows, nullptr, nullptr, nullptr, nullptr, tab_final_values, &stk};
     return mlp_rollout(true, mlp_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, a);
 }
 

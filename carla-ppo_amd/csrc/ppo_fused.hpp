@@ -74,8 +74,22 @@ struct MiRolloutValueRec { const int* table_rows; long long n_table_rows; float*
 // running observation normalisation (mi_rollout_step_batch_norm / mi_rollout_value_batch_norm): fp32 mean / inv_std [din] on the device, the clamp, the caller's
 // n x din buffer the normalised rows go to, and where they are recorded (table_rows NULL: nowhere; tab_states unused by the value-only form)
 struct MiRolloutObsNorm { const float* mean; const float* inv_std; float clip; float* nstate; const int* table_rows; long long n_table_rows; float* tab_states; };
+// latent stacking (mi_rollout_step_batch_stack / mi_rollout_value_batch_stack): the state is [z_t | the k - 1 latents before it | measurements].  hist: fp32
+// [n_lanes][k - 1][z_dim] on the device, slot 0 = the latent of the lane's previous step; lanes / first: int32 [n] (the step's input buffer); sstate: the caller's
+// n x din buffer trunk layer 1 reads; older: [n][(k - 1) z_dim] or NULL, where the older latents of every row go (HBM or pinned host memory).  obs_mean NULL: not
+// normalised (tab_states takes the raw rows); else sstate / tab_states take the normalised rows and tab_raw_states the raw ones.  table_rows NULL: no table is written.
+struct MiRolloutStack {
+    int k; float* hist; int n_lanes; const int* lanes; const int* first; int advance; float* sstate; float* older;
+    const float* obs_mean; const float* obs_inv_std; float clip;
+    const int* table_rows; long long n_table_rows; float* tab_states; float* tab_raw_states;
+};
+// every refusal of the stacked form, before any launch: records "<who>: .." and returns MI_ERR_ARG / MI_ERR_SHAPE, or MI_OK (din < 0: the argument checks alone)
+int mi_rollout_stack_check(const MiRolloutStack& s, int z_dim, int n_meas, int din, const char* who);
 int mi_rollout_value_batch(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, int n, float* out,
-                           const MiRolloutValueRec& rec, const MiRolloutObsNorm* nrm = nullptr);
+                           const MiRolloutValueRec& rec, const MiRolloutObsNorm* nrm = nullptr, const MiRolloutStack* stk = nullptr);
+// the stacked step: rec NULL = the plain heads; else the recording heads, which store action and value (rec->states is not read: the stack kernel has written the row)
+int mi_rollout_policy_batch_stack(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n,
+                                  float* out, const MiRolloutRec* rec, const MiRolloutStack& stk);
 int mi_rollout_policy_batch_norm(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n,
                                  float* out, const MiRolloutRec* rec, const MiRolloutObsNorm& nrm);
 // layer 1 of the MlpVAE encoder from the camera bytes of n environments (rollout_mlp.hip; mi_mlp_rollout_step_batch): clears `zero` -- the raw-sum buffers of the whole

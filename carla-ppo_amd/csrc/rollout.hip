@@ -8,6 +8,7 @@
 // bias + ReLU of a layer are applied by the NEXT layer's operand loader, so no layer needs a finishing pass, and the step is a chain of
 // eight launches whose cost is their latency, not their work:
 //     conv1 (also clears the raw buffers) -> conv2 -> conv3 -> conv4 -> mean -> trunk layer 1 (both nets) -> trunk layer 2 (both nets) -> heads
+#include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 #include "common.hpp"
@@ -369,8 +370,11 @@ __global__ __launch_bounds__(256) void rollout_head_rec_kernel(const RollHeadPar
     const long long r = t.table_rows[e];
     RollRecRow rec = {};
     if (r >= 0 && r < t.n_table_rows) {
-        rec.state = t.states + r * t.din; rec.action = t.actions + r * q.A; rec.value = t.values + r;
-        for (int j = threadIdx.x; j < t.n_meas; j += 256) rec.state[q.z_dim + j] = t.meas[e * t.n_meas + j];
+        rec.action = t.actions + r * q.A; rec.value = t.values + r;
+        if (t.states) {                                   // (NULL: the stacked form, whose row rollout_stack_kernel has written)
+            rec.state = t.states + r * t.din;
+            for (int j = threadIdx.x; j < t.n_meas; j += 256) rec.state[q.z_dim + j] = t.meas[e * t.n_meas + j];
+        }
     }
     roll_head<NA, true>(q, red, n * q.H2, rec);
 }
@@ -435,6 +439,73 @@ __global__ __launch_bounds__(128) void rollout_obs_norm_kernel(const RollObsNorm
         const float v = obs_normalize(s, p.obs_mean[j], p.obs_inv_std[j], p.clip);
         dst[j] = v;
         if (tab) tab[j] = v;
+    }
+}
+
+// latent stacking (mi_rollout_step_batch_stack / mi_rollout_value_batch_stack), launched where the normaliser runs: block e assembles environment e's state
+//     [z_t | old_1 | .. | old_{k-1} | measurements],   z_t = mean_raw + mean_bias (the sum the heads return as z),   old_i = first ? z_t : hist[lane][i - 1]
+// (a select: what a `first` row's lane holds never reaches the row; a lane outside [0, n_lanes) is `first` and its history is neither read nor written).  Thread t
+// holds the columns t, t + 128, .. in registers -- din <= 1024: at most 8 -- and every store is a plain vector store of such a register: the raw row to sstate (with
+// obs_mean: obs_normalize of it, the normaliser's formula) and, where table_rows[e] lies in [0, n_table_rows), to tab_states (with obs_mean: the normalised row there,
+// the raw one to tab_raw_states); the k - 1 older latents to older[e].  Then a barrier -- every read of the lane's history lies before it -- and with `advance` the
+// lane's history becomes the row's first (k - 1) z_dim columns, [z_t | old_1 | .. | old_{k-2}].  Lanes of one call are distinct (the caller's duty): block e alone
+// touches hist[lanes[e]].  Trunk layer 1 then reads sstate as a state vector without bias or tail.
+struct RollStackParams {
+    const float *mean_raw, *mean_bias, *meas;             // raw means [n][z_dim], the mean layer's bias [z_dim], measurements [n][din - k z_dim]
+    float* hist; const int *lanes, *first;                // [n_lanes][k - 1][z_dim]; [n] each
+    const float *obs_mean, *obs_inv_std; float clip;      // NULL: not normalised
+    float *sstate, *older;                                // [n][din]; [n][(k - 1) z_dim] or NULL
+    const int* table_rows; long long n_table_rows; float *tab_states, *tab_raw_states;
+    int n, z_dim, k, din, n_lanes, advance;
+};
+
+constexpr int ROLL_STACK_THREADS = 128, ROLL_STACK_REGS = 8;     // 128 x 8 = 1024 columns: MI_ROLLOUT_MAX_STACK latents of 64 and nothing else, or fewer and measurements
+
+__global__ __launch_bounds__(ROLL_STACK_THREADS) void rollout_stack_kernel(const RollStackParams p) {
+    const long long e = blockIdx.x;
+    if (e >= p.n) return;                                 // (block-uniform)
+    const int Z = p.z_dim, KZ = p.k * p.z_dim, HZ = KZ - Z, n_meas = p.din - KZ;
+    const float* z = p.mean_raw + e * Z;
+    const long long ms = e * n_meas - KZ;                 // measurement j - KZ of environment e is p.meas[ms + j]
+    const int lane = p.lanes[e];
+    const bool in_hist = lane >= 0 && lane < p.n_lanes;
+    const bool first = !in_hist || p.first[e] != 0;
+    float* h = p.hist + (in_hist ? (long long)lane * HZ : 0);
+    float *tab = nullptr, *tab_raw = nullptr;
+    if (p.table_rows) {
+        const long long r = p.table_rows[e];
+        if (r >= 0 && r < p.n_table_rows) {
+            tab = p.tab_states + r * p.din;
+            if (p.obs_mean) tab_raw = p.tab_raw_states + r * p.din;
+        }
+    }
+    float* dst = p.sstate + e * p.din;
+    float* old = p.older ? p.older + e * HZ : nullptr;
+    float s[ROLL_STACK_REGS];
+#pragma unroll
+    for (int i = 0; i < ROLL_STACK_REGS; ++i) {
+        const int j = threadIdx.x + i * ROLL_STACK_THREADS;
+        s[i] = 0.f;
+        if (j >= p.din) continue;
+        if (j < KZ) {
+            const int c = j < Z ? j : j % Z;
+            if (j < Z || first) s[i] = z[c] + p.mean_bias[c];
+            else s[i] = h[j - Z];
+        } else {
+            s[i] = p.meas[ms + j];
+        }
+        const float v = p.obs_mean ? obs_normalize(s[i], p.obs_mean[j], p.obs_inv_std[j], p.clip) : s[i];
+        dst[j] = v;
+        if (tab) tab[j] = v;
+        if (tab_raw) tab_raw[j] = s[i];
+        if (old && j >= Z && j < KZ) old[j - Z] = s[i];
+    }
+    __syncthreads();
+    if (!p.advance || !in_hist) return;
+#pragma unroll
+    for (int i = 0; i < ROLL_STACK_REGS; ++i) {
+        const int j = threadIdx.x + i * ROLL_STACK_THREADS;
+        if (j < HZ) h[j] = s[i];
     }
 }
 
@@ -581,29 +652,62 @@ static int fill_trunks_batch(RollConvBatchParams& l1, dim3& g1, RollConvBatchPar
     return MI_OK;
 }
 
-// running observation normalisation (nrm != NULL): the normalise launch, and trunk layer 1 re-aimed at what it wrote -- the same rollout_conv_batch_kernel<3> with
-// x = nstate [n][din], split = K = din, no bias and no tail (both descriptors empty: every load of them returns 0.0)
+// trunk layer 1 re-aimed at finished state rows [n][din]: the same rollout_conv_batch_kernel<3> with x = rows, split = K = din, no bias and no tail (both
+// descriptors empty: every load of them returns 0.0)
+static void layer1_reads_rows(RollConvBatchParams& l1, const float* rows, int din, int n) {
+    l1.x = rows; l1.x_bias = nullptr; l1.x_tail = nullptr; l1.split = din;
+    l1.x_row = (unsigned)din; l1.t_row = 0;
+    l1.x_bytes = (unsigned)n * (unsigned)din * 4u; l1.xb_bytes = 0; l1.tail_bytes = 0;
+}
+
+// running observation normalisation (nrm != NULL): the normalise launch, and trunk layer 1 re-aimed at what it wrote
 static void obs_norm_layer1(hipStream_t st, RollConvBatchParams& l1, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim,
                             const float* measurements, int n, const MiRolloutObsNorm& nrm) {
     const RollObsNormParams p = {mean_raw, mean_bias, measurements, nrm.mean, nrm.inv_std, nrm.clip, nrm.nstate, nrm.table_rows, nrm.n_table_rows, nrm.tab_states, n, z_dim, q.din};
     hipLaunchKernelGGL(rollout_obs_norm_kernel, dim3(n), dim3(128), 0, st, p);
-    l1.x = nrm.nstate; l1.x_bias = nullptr; l1.x_tail = nullptr; l1.split = q.din;
-    l1.x_row = (unsigned)q.din; l1.t_row = 0;
-    l1.x_bytes = (unsigned)n * (unsigned)q.din * 4u; l1.xb_bytes = 0; l1.tail_bytes = 0;
+    layer1_reads_rows(l1, nrm.nstate, q.din, n);
+}
+
+// latent stacking (stk != NULL): every refusal, for the entries to call before their first launch
+int mi_rollout_stack_check(const MiRolloutStack& s, int z_dim, int n_meas, int din, const char* who) {
+    static thread_local char msg[192];
+    const char* text = nullptr; int code = MI_ERR_ARG;
+    if (s.k < 2 || s.k > MI_ROLLOUT_MAX_STACK) text = "2 <= latent_stack <= MI_ROLLOUT_MAX_STACK";
+    else if (!s.hist || !s.lanes || !s.first || !s.sstate || s.n_lanes < 1) text = "missing hist / lanes / first / sstate";
+    else if (((uintptr_t)s.sstate) & 15) text = "sstate must be 16-byte aligned";
+    else if (s.obs_mean && (!s.obs_inv_std || !(s.clip > 0.f))) text = "obs_inv_std is missing or obs_clip is not a positive value (+inf: never clamp)";
+    else if (!s.obs_mean && (s.obs_inv_std || s.tab_raw_states)) text = "obs_inv_std and tab_raw_states are NULL where obs_mean is";
+    else if (s.table_rows && (s.n_table_rows < 1 || !s.tab_states || (s.obs_mean && !s.tab_raw_states))) text = "missing tables";
+    else if (din < 0) {}                                 // (the early call, before the handles are read: the shape checks follow once the policy's size is known)
+    else if ((long long)s.k * z_dim + n_meas != din) { text = "latent_stack x z_dim + measurements must equal the policy's input size"; code = MI_ERR_SHAPE; }
+    else if (din > ROLL_STACK_THREADS * ROLL_STACK_REGS) { text = "at most 1024 inputs"; code = MI_ERR_SHAPE; }
+    if (!text) return MI_OK;
+    snprintf(msg, sizeof(msg), "%s: %s", who, text);
+    return mi_fail(code, msg);
+}
+
+// the stack launch, and trunk layer 1 re-aimed at the rows it wrote, as the normaliser's launch re-aims it
+static void stack_layer1(hipStream_t st, RollConvBatchParams& l1, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim,
+                         const float* measurements, int n, const MiRolloutStack& s) {
+    const RollStackParams p = {mean_raw, mean_bias, measurements, s.hist, s.lanes, s.first, s.obs_mean, s.obs_inv_std, s.clip, s.sstate, s.older,
+                               s.table_rows, s.n_table_rows, s.tab_states, s.tab_raw_states, n, z_dim, s.k, q.din, s.n_lanes, s.advance};
+    hipLaunchKernelGGL(rollout_stack_kernel, dim3(n), dim3(ROLL_STACK_THREADS), 0, st, p);
+    layer1_reads_rows(l1, s.sstate, q.din, n);
 }
 
 // trunks and heads of n environments: mean_raw [n][z_dim], measurements [n][din - z_dim], noise [n][A], out [n][A + 1 + z_dim]; raw sums in q.h1 / q.h2 as [net][n][H]
 static int policy_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
-                        const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec, const MiRolloutObsNorm* nrm = nullptr) {
+                        const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec, const MiRolloutObsNorm* nrm = nullptr, const MiRolloutStack* stk = nullptr) {
     RollConvBatchParams l1, l2; dim3 g1, g2; RollHeadParams h;
     const int rc = fill_trunks_batch(l1, g1, l2, g2, q, mean_raw, mean_bias, z_dim, measurements, n);
     if (rc != MI_OK) return rc;
     fill_head(h, q, mean_raw, mean_bias, z_dim, noise, greedy, out);
     if (nrm) obs_norm_layer1(st, l1, q, mean_raw, mean_bias, z_dim, measurements, n, *nrm);
+    if (stk) stack_layer1(st, l1, q, mean_raw, mean_bias, z_dim, measurements, n, *stk);
     launch_conv_batch(st, g1, l1);
     launch_conv_batch(st, g2, l2);
-    if (rec) {
-        const RollRecParams t = {rec->table_rows, rec->n_table_rows, measurements, q.din - z_dim, q.din, rec->states, rec->actions, rec->values};
+    if (rec) {                                           // (stacked: the row is written already; the heads store action and value)
+        const RollRecParams t = {rec->table_rows, rec->n_table_rows, measurements, q.din - z_dim, q.din, stk ? nullptr : rec->states, rec->actions, rec->values};
         if (q.A <= 2) hipLaunchKernelGGL(rollout_head_rec_kernel<2>, dim3(n), dim3(256), 0, st, h, n, t);
         else hipLaunchKernelGGL(rollout_head_rec_kernel<8>, dim3(n), dim3(256), 0, st, h, n, t);
         return mi_check_launch("rollout_policy_batch_rec");
@@ -616,11 +720,12 @@ static int policy_batch(hipStream_t st, const PpoFusedParams& q, const float* me
 // the VALUE trunk alone and the value-only heads: the batched trunk stages with their operands moved to net 1 and half the grid (the policy net's half of q.h1 / q.h2
 // is neither cleared, written nor read), out [n] = the values, also left in rec.final_values[rec.table_rows[e]]
 int mi_rollout_value_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, int n, float* out,
-                           const MiRolloutValueRec& rec, const MiRolloutObsNorm* nrm) {
+                           const MiRolloutValueRec& rec, const MiRolloutObsNorm* nrm, const MiRolloutStack* stk) {
     RollConvBatchParams l1, l2; dim3 g1, g2;
     const int rc = fill_trunks_batch(l1, g1, l2, g2, q, mean_raw, mean_bias, z_dim, measurements, n);
     if (rc != MI_OK) return rc;
     if (nrm) obs_norm_layer1(st, l1, q, mean_raw, mean_bias, z_dim, measurements, n, *nrm);
+    if (stk) stack_layer1(st, l1, q, mean_raw, mean_bias, z_dim, measurements, n, *stk);
     l1.w += l1.w_net; l1.out += l1.out_net;                                                // (layer 1's x / bias strides are 0: both nets read the one state)
     l2.x += l2.x_net; l2.x_bias += l2.xb_net; l2.w += l2.w_net; l2.out += l2.out_net;
     g1.y = l1.row_tiles; g2.y = l2.row_tiles;                                              // blockIdx.y / row_tiles = 0: the kernels' "net 0" is the value net
@@ -645,4 +750,10 @@ int mi_rollout_policy_batch_rec(hipStream_t st, const PpoFusedParams& q, const f
 int mi_rollout_policy_batch_norm(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
                                  const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec, const MiRolloutObsNorm& nrm) {
     return policy_batch(st, q, mean_raw, mean_bias, z_dim, measurements, noise, greedy, n, out, rec, &nrm);
+}
+
+// the stacked step (mi_rollout_step_batch_stack): the stack launch in front of trunk layer 1; rec NULL = the plain batched heads
+int mi_rollout_policy_batch_stack(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
+                                  const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec, const MiRolloutStack& stk) {
+    return policy_batch(st, q, mean_raw, mean_bias, z_dim, measurements, noise, greedy, n, out, rec, nullptr, &stk);
 }

@@ -979,16 +979,20 @@ long long mi_rollout_batch_workspace_bytes(void* vae_h, void* ppo_h, int n_envs)
 // one body for the plain call, the recording call (rec != NULL: mi_rollout_step_batch_rec, whose last launch is the recording heads) and the value-only call (vrec != NULL:
 // mi_rollout_value_batch_rec: the same encoder chain, then the value trunk and the value-only heads; out holds n floats)
 // (the caller's own name in front of every message: the _norm entries share these checks)
-#define ROLL_FAIL(code, text) return mi_fail(code, nrm ? (vrec ? "mi_rollout_value_batch_norm: " text : "mi_rollout_step_batch_norm: " text) \
-                                                       : (vrec ? "mi_rollout_value_batch_rec: " text : "mi_rollout_step_batch: " text))
+#define ROLL_FAIL(code, text) return mi_fail(code, stk ? (vrec ? "mi_rollout_value_batch_stack: " text : "mi_rollout_step_batch_stack: " text) \
+                                                   : nrm ? (vrec ? "mi_rollout_value_batch_norm: " text : "mi_rollout_step_batch_norm: " text) \
+                                                         : (vrec ? "mi_rollout_value_batch_rec: " text : "mi_rollout_step_batch: " text))
 static int rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
                               void* scratch, long long scratch_bytes, float* out, const MiRolloutRec* rec, const MiRolloutValueRec* vrec = nullptr,
-                              const MiRolloutObsNorm* nrm = nullptr) {
+                              const MiRolloutObsNorm* nrm = nullptr, const MiRolloutStack* stk = nullptr) {
     VaeEngine* e = (VaeEngine*)vae_h;
+    if (stk && (!e || !ppo_h)) ROLL_FAIL(MI_ERR_STATE, "null handle");
     if (nrm && (!e || !ppo_h)) return mi_fail(MI_ERR_STATE, vrec ? "mi_rollout_value_batch_norm: null handle" : "mi_rollout_step_batch_norm: null handle");
     if (!e || !ppo_h) return mi_fail(MI_ERR_STATE, vrec ? "mi_rollout_value_batch_rec: null handle" : rec ? "mi_rollout_step_batch_rec: null handle" : "mi_rollout_step_batch: null handle");
     if (!frames_u8 || !out || !scratch || (n_meas > 0 && !measurements) || (!greedy && !noise)) ROLL_FAIL(MI_ERR_ARG, "missing buffers");
-    if (rec && (!rec->table_rows || !rec->states || !rec->actions || !rec->values || rec->n_table_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch_rec: missing tables");
+    if (stk) CK(mi_rollout_stack_check(*stk, 0, 0, -1, vrec ? "mi_rollout_value_batch_stack" : "mi_rollout_step_batch_stack"));
+    if (stk && rec && (!rec->actions || !rec->values || rec->n_table_rows < 1)) ROLL_FAIL(MI_ERR_ARG, "missing tables");     // (the states tables: mi_rollout_stack_check)
+    if (!stk && rec && (!rec->table_rows || !rec->states || !rec->actions || !rec->values || rec->n_table_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch_rec: missing tables");
     if (vrec && (!vrec->table_rows || !vrec->final_values || vrec->n_table_rows < 1)) ROLL_FAIL(MI_ERR_ARG, "missing tables");
     if (nrm) {                                           // running observation normalisation: every check before any launch
 #define NORM_FAIL(text) return mi_fail(MI_ERR_ARG, vrec ? "mi_rollout_value_batch_norm: " text : "mi_rollout_step_batch_norm: " text)
@@ -1008,7 +1012,8 @@ static int rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsi
     float* mean_raw = (float*)scratch + o;
     mi::PpoFusedParams q;
     CK(mi_ppo_internal_fill(ppo_h, &q, mean_raw, 1));
-    if (q.din != d.z_dim + n_meas) ROLL_FAIL(MI_ERR_SHAPE, "z_dim + measurements must equal the policy's input size");
+    if (stk) CK(mi_rollout_stack_check(*stk, d.z_dim, n_meas, q.din, vrec ? "mi_rollout_value_batch_stack" : "mi_rollout_step_batch_stack"));
+    else if (q.din != d.z_dim + n_meas) ROLL_FAIL(MI_ERR_SHAPE, "z_dim + measurements must equal the policy's input size");
     if (q.A > 8) ROLL_FAIL(MI_ERR_ARG, "at most 8 actions");
     if (mi_ppo_internal_fill(ppo_h, &q, mean_raw, n) != MI_OK) ROLL_FAIL(MI_ERR_ARG, "n exceeds the PPO engine's max_batch");
     MiZeroList zl = {};
@@ -1023,7 +1028,8 @@ static int rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsi
     for (int i = 1; i < NCONV; ++i)                      // conv(i+1): conv2 reads conv1's finished output, the others raw sums + bias + ReLU on load
         CK(mi_rollout_conv_batch(st, act[i], i == 1 ? nullptr : e->bptr(2 * (i - 1) + 1), g.ih[i], g.iw[i], g.c[i], e->params + e->L.off[2 * i], g.c[i + 1], g.c[i + 1], 4, 4, act[i + 1], 0, n));
     CK(mi_rollout_conv_batch(st, act[NCONV], e->bptr(2 * (NCONV - 1) + 1), 1, 1, g.c[NCONV], e->params + e->L.off[8], 2 * d.z_dim, d.z_dim, 1, 1, mean_raw, g.flat, n));
-    if (vrec) return mi_rollout_value_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, n, out, *vrec, nrm);
+    if (vrec) return mi_rollout_value_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, n, out, *vrec, nrm, stk);
+    if (stk) return mi_rollout_policy_batch_stack(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out, rec, *stk);
     if (nrm) return mi_rollout_policy_batch_norm(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out, rec, *nrm);
     if (rec) return mi_rollout_policy_batch_rec(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out, *rec);
     return mi_rollout_policy_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out);
@@ -1066,6 +1072,27 @@ int mi_rollout_value_batch_norm(void* vae_h, void* ppo_h, void* stream, const un
     const MiRolloutValueRec vrec = {table_rows, n_table_rows, tab_final_values};
     const MiRolloutObsNorm nrm = {obs_mean, obs_inv_std, obs_clip, nstate, nullptr, 0, nullptr};
     return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, nullptr, &vrec, &nrm);
+}
+
+// the step with LATENT STACKING: state = [z_t | the latent_stack - 1 latents before it, from the lane's device-resident history | measurements]; the plain, the
+// recording (table_rows != NULL) and the normalised (obs_mean != NULL) step in one, in the style of mi_mlp_rollout_step_batch
+int mi_rollout_step_batch_stack(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
+                                void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip,
+                                const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values,
+                                int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, int advance, float* sstate, float* older_out) {
+    const MiRolloutRec rec = {table_rows, n_table_rows, nullptr, tab_actions, tab_values};
+    const MiRolloutStack stk = {latent_stack, hist, n_lanes, lanes, first, advance, sstate, older_out, obs_mean, obs_inv_std, obs_clip, table_rows, n_table_rows, tab_states, tab_raw_states};
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, table_rows ? &rec : nullptr, nullptr, nullptr, &stk);
+}
+
+// the value-only call on the stacked state: never advances the history, writes no table of states and no older latents
+int mi_rollout_value_batch_stack(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n, void* scratch,
+                                 long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip,
+                                 const int* table_rows, long long n_table_rows, float* tab_final_values,
+                                 int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, float* sstate) {
+    const MiRolloutValueRec vrec = {table_rows, n_table_rows, tab_final_values};
+    const MiRolloutStack stk = {latent_stack, hist, n_lanes, lanes, first, 0, sstate, nullptr, obs_mean, obs_inv_std, obs_clip, nullptr, 0, nullptr, nullptr};
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, nullptr, &vrec, nullptr, &stk);
 }
 
 // VAE.encode (vae/models.py:199-202): frames -> mean [B,Z] fp32

@@ -216,6 +216,40 @@ z_dim) bytes (mi_mlp_rollout_workspace_bytes).  On the measured box one call tak
 two-call path on the same model (profiles/r27_mlp_rollout.md).  RolloutStep, the single-frame entry, has no MLP form (ValueError: use BatchedRolloutStep(vae, ppo,
 num_envs=1)).
 
+The step classes and both buffers can STACK LATENTS.  One frame per step tells a feed-forward policy nothing about how fast another car is closing, the yaw rate, or a
+light that has just changed; the usual remedy is to stack the last k observations, and here the observation is compressed already, so the cheap form is
+s_t = [z_t | z_{t-1} | .. | z_{t-k+1} | measurements_t] with input_dim = k z_dim + n_meas.  Built by the classmethod `stacked(.., latent_stack=k)` of its class (the constructor's arguments and k = 2 .. 16, at most 1024 inputs) the step owns a
+device-resident `history` [num_envs, k - 1, z_dim] (fp32, zeros; slot 0 is the latent of the lane's previous step) and a host bool per lane, "fresh".  Every call is then
+mi_rollout_step_batch_stack / mi_rollout_value_batch_stack (mi_mlp_.. with an MlpVAE) -- one more launch, rollout_stack_kernel, where the normaliser runs: a block per row
+assembles the state from the frame's latent and its lane's history (a fresh lane repeats its own latent k times, as frame stacking pads with the first observation),
+stores it for trunk layer 1 and into the tables, normalises it where observation normalisation is on, hands the older latents back next to `out`, and behind a barrier
+shifts the lane's history.  The lanes and their fresh flags travel behind the table rows in the pinned input buffer; the states a call returns are float64
+[n, k z_dim + n_meas], bitwise the raw row the kernel assembled:
+
+    ppo = PPO(np.array([4 * 64 + 3]), space, ...); ppo.set_wide_inputs()       # a policy of more than 96 inputs wants ppo.set_wide_inputs() for its update
+    buf = ContinuousRolloutBuffer.stacked(vae, ppo, num_envs=8, horizon=128, latent_stack=4)
+    buf.reset()
+    for _ in range(buf.horizon):
+        actions, values, states = buf.step(frames, measurements)            # advances the history of the stepped lanes
+        rewards, dones, truncated, frames, measurements, final_frames, final_measurements = simulators_step(actions)
+        buf.outcome(rewards, dones)                                         # done: that lane's next step is fresh
+        cut = np.nonzero(truncated & ~dones)[0]
+        if len(cut):
+            buf.truncate(final_frames[cut], final_measurements[cut], env_ids=cut)   # valued on the episode's history, then fresh
+    need = buf.rows.needs_bootstrap()
+    buf.bootstrap(frames[need], measurements[need], env_ids=need)           # reads the history and does NOT advance it: the next collection steps this observation again
+    out = buf.update(num_epochs=3, batch_size=32)
+    buf.reset()                                                             # touches neither the history nor the flags: an episode may continue across an update
+    buf.restart_history([3])                                                # environment 3 was reset without a done or a truncation being reported
+    ckpt = buf.history_state()                                              # ... buf.load_history_state(ckpt) in the run that resumes
+    step = BatchedRolloutStep.stacked(vae, ppo, num_envs=1, latent_stack=4) # evaluation: step.step(frames, measurements, env_ids=..), step.restart() at an episode's start
+
+The tables `states` / `raw_states` are input_dim wide as they always were, and update(), update_with_diagnostics() and every setting above are the code they were.  The
+"latent columns" of observation normalisation (normalize_latents=False, the z_dim kept in its state) are the first k z_dim columns.  RolloutStep, the single-frame
+entry, has no stacked form (RolloutStep.stacked raises ValueError: use BatchedRolloutStep.stacked(num_envs=1)).  At k = 4 and 64 latents the recording call was measured at +6 to +7 / +8 to +10 / +18 to +21 us for 1 / 8 / 64 environments
+(one more launch, a trunk layer 1 of 259 inputs instead of 67, the older latents written out; profiles/r29_latent_stack.md).  With the setting off no tensor
+is allocated and every call makes the launches it always made.
+
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
 """
 import contextlib
@@ -229,21 +263,55 @@ from mi355 import lib as milib
 
 
 MAX_ENVS = 1024                                                                      # MI_ROLLOUT_MAX_ENVS of include/mi355_carla.h
+MAX_STACK = 16                                                                       # MI_ROLLOUT_MAX_STACK
+MAX_STACK_INPUTS = 1024                                                              # the widest state rollout_stack_kernel assembles (and PPO.set_wide_inputs() trains)
+
+
+def latent_stack_checked(latent_stack, z_dim, input_dim, who):
+    """The checked `latent_stack` of a step class or buffer -> (k, n_meas): an int in [1, MAX_STACK] with k z_dim <= input_dim and, for k > 1, at most
+    MAX_STACK_INPUTS inputs.  ValueError otherwise.  No device and no library involved."""
+    k = latent_stack
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_STACK:
+        raise ValueError("%s: latent_stack is an int in [1, %d], got %r" % (who, MAX_STACK, k))
+    k, z_dim, input_dim = int(k), int(z_dim), int(input_dim)
+    if k * z_dim > input_dim:
+        raise ValueError("the policy takes fewer inputs than the VAE's latent size" if k == 1 else
+                         "%s: latent_stack = %d latents of %d are %d inputs, the policy takes %d" % (who, k, z_dim, k * z_dim, input_dim))
+    if k > 1 and input_dim > MAX_STACK_INPUTS:
+        raise ValueError("%s: latent_stack = %d gives a state of %d inputs, the stacked step assembles at most %d" % (who, k, input_dim, MAX_STACK_INPUTS))
+    return k, input_dim - k * z_dim
+
+
+def latent_history_state_checked(d, k, z_dim, num_envs, who):
+    """The checked dict of history_state() for a step of `num_envs` lanes, latent_stack = k and latents of z_dim -> {"history": float32 [num_envs, k - 1, z_dim],
+    "fresh": bool [num_envs]}.  ValueError otherwise.  numpy only."""
+    keys = ("latent_stack", "z_dim", "history", "fresh")
+    if not isinstance(d, dict) or any(key not in d for key in keys):
+        raise ValueError("%s: expected a dict with the keys %s" % (who, ", ".join(keys)))
+    for key, want in (("latent_stack", k), ("z_dim", z_dim)):
+        got = d[key]
+        if isinstance(got, (bool, np.bool_)) or not isinstance(got, (int, np.integer)) or int(got) != want:
+            raise ValueError("%s: the state was taken with %s = %r, this one has %d" % (who, key, got, want))
+    h, f = np.asarray(d["history"]), np.asarray(d["fresh"])
+    if h.dtype.kind != "f" or h.shape != (num_envs, k - 1, z_dim):
+        raise ValueError("%s: history must be floats of shape (%d, %d, %d), got %s %s" % (who, num_envs, k - 1, z_dim, h.dtype, h.shape))
+    if f.dtype.kind != "b" or f.shape != (num_envs,):
+        raise ValueError("%s: fresh must be bools of shape (%d,), got %s %s" % (who, num_envs, f.dtype, f.shape))
+    return {"history": np.ascontiguousarray(h, np.float32), "fresh": f.copy()}
 
 
 class _StepBase:
     """What every step class starts from: the engines' handles, the sizes, the io mode and the Philox noise stream."""
 
-    def _setup(self, who, vae, ppo, seed, io):
+    def _setup(self, who, vae, ppo, seed, io, latent_stack=1):
         """-> (the VAE's device engine, the policy's)."""
         self.vae, self.ppo = vae, ppo
+        self.z_dim, self.A = int(vae.z_dim), int(ppo.num_actions)
+        self.k, self.n_meas = latent_stack_checked(latent_stack, self.z_dim, ppo.input_dim, getattr(self, "_who", who))      # (raises before anything touches a device)
+        self.latent_cols, self.din = self.k * self.z_dim, self.k * self.z_dim + self.n_meas            # the state's latent columns: what normalize_latents=False is about
         vdev, pdev = vae._need_dev(), ppo._need_dev()
         self.L = vdev.L
         self.device = vdev.device
-        self.z_dim, self.A = int(vae.z_dim), int(ppo.num_actions)
-        self.n_meas = int(ppo.input_dim) - self.z_dim
-        if self.n_meas < 0:
-            raise ValueError("the policy takes fewer inputs than the VAE's latent size")
         self.io = io or os.environ.get("MI355_ROLLOUT_IO", "pinned")
         if self.io not in ("pinned", "device"):
             raise ValueError(who + ": io must be 'pinned' or 'device'")
@@ -275,6 +343,13 @@ class RolloutStep(_StepBase):
         self._io_buffers(self._noise_off + 4 * (self.n_meas + self.A), self.A + 1 + self.z_dim)
         self._f_np = self._in_np[self._noise_off:].view(np.float32)
         self._out_np = self.h_out.numpy()
+
+    @classmethod
+    def stacked(cls, vae, ppo, latent_stack, seed=None, io=None):
+        """The single-frame entry has no stacked form: ValueError for anything but latent_stack = 1."""
+        if isinstance(latent_stack, (bool, np.bool_)) or not isinstance(latent_stack, (int, np.integer)) or int(latent_stack) != 1:
+            raise ValueError("RolloutStep: latent stacking exists in the batched step only: use BatchedRolloutStep.stacked(vae, ppo, num_envs=1, latent_stack=k)")
+        return cls(vae, ppo, seed=seed, io=io)
 
     def set_observation_normalization(self, state_dict):
         """The single-frame entry has no normalised form: ValueError for anything but None."""
@@ -320,15 +395,33 @@ class BatchedRolloutStep(_StepBase):
     _row_ints = 0                                                                    # int32 per environment behind the noise (the recording step's table rows)
 
     def __init__(self, vae, ppo, num_envs, seed=None, io=None):
+        self._init(vae, ppo, num_envs, seed, io, 1)
+
+    @classmethod
+    def stacked(cls, vae, ppo, num_envs, latent_stack, seed=None, io=None):
+        """The step with LATENT STACKING (see the module docstring): cls(vae, ppo, num_envs, seed, io) whose state is [z_t | the latent_stack - 1 latents before it |
+        measurements], from a device-resident `history` [num_envs, latent_stack - 1, z_dim] the step owns.  latent_stack: an int in [1, 16] (1: the plain step) with
+        latent_stack x z_dim <= the policy's input size <= 1024; ValueError otherwise, before anything touches a device."""
+        self = cls.__new__(cls)                                                      # (not cls(..): a subclass that needs more than these arguments overrides _init, as the buffers do)
+        self._init(vae, ppo, num_envs, seed, io, latent_stack)
+        return self
+
+    def _init(self, vae, ppo, num_envs, seed, io, latent_stack):
         import torch
         self.num_envs = int(num_envs)
         if not 1 <= self.num_envs <= MAX_ENVS:
             raise ValueError("BatchedRolloutStep: 1 <= num_envs <= %d" % MAX_ENVS)
-        vdev, pdev = self._setup("BatchedRolloutStep", vae, ppo, seed, io)
+        vdev, pdev = self._setup("BatchedRolloutStep", vae, ppo, seed, io, latent_stack)
         pdev.ensure_batch(self.num_envs)                                             # recreates the engine when it grows: ppo.dev.handle is read per call
         E, self.row = self.num_envs, self.A + 1 + self.z_dim
         self._f_off = (E * self.frame_bytes + 15) // 16 * 16                         # float region: measurements [E, k], then noise [E, A], then _row_ints [E]
-        self._io_buffers(self._f_off + 4 * E * (self.n_meas + self.A + self._row_ints), E * self.row)
+        stacked = self.k > 1                                                         # latent stacking: lanes and fresh flags [E] behind the table rows, the older latents behind the output rows
+        self._older_off = E * self.row
+        self._io_buffers(self._f_off + 4 * E * (self.n_meas + self.A + self._row_ints + (2 if stacked else 0)), E * (self.row + (self.k - 1) * self.z_dim))
+        if stacked:
+            self.history = torch.zeros(E, self.k - 1, self.z_dim, device=self.device)
+            self.fresh = np.ones(E, bool)
+            self.sstate = torch.empty(E, self.din, device=self.device)
         if self._kind == "mlp":                                                      # sized from the descriptor: no handle involved
             import ctypes
             entry, self.scratch_bytes = "mi_mlp_rollout_workspace_bytes", int(self.L.mi_mlp_rollout_workspace_bytes(ctypes.byref(vdev._desc(1)), E))
@@ -339,10 +432,57 @@ class BatchedRolloutStep(_StepBase):
         self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=self.device)
         self._f_np = self._in_np[self._f_off:].view(np.float32)
         self._i_np = self._in_np[self._f_off:].view(np.int32)
-        self._out_np = self.h_out.numpy().reshape(E, self.row)
+        self._out_np = self.h_out.numpy()[:E * self.row].reshape(E, self.row)
+        self._older_np = self.h_out.numpy()[E * self.row:]
 
     def __call__(self, frames_u8, measurements, greedy=False, noise=None):
         return self.record(*self.check(frames_u8, measurements, greedy, noise), greedy)
+
+    def step(self, frames_u8, measurements, env_ids=None, greedy=False, noise=None):
+        """__call__ with the environment of every row, in the buffers' argument order: env_ids (None: 0 .. n-1, what __call__ takes) are the history lanes of the rows --
+        read with latent stacking on only, checked whenever given (distinct, inside [0, num_envs): ValueError otherwise)."""
+        f, n, meas, nz = self.check(frames_u8, measurements, greedy, noise)
+        return self.record(f, n, meas, nz, greedy, lanes=None if env_ids is None else self.lanes_checked(env_ids, n))
+
+    def lanes_checked(self, env_ids, n):
+        """env_ids (None: 0 .. n-1) of a call with n rows -> int64 [n], distinct, inside [0, num_envs).  ValueError otherwise."""
+        if env_ids is None:
+            return np.arange(n, dtype=np.int64)
+        ids = np.asarray(env_ids)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu" or ids.shape[0] != n:
+            raise ValueError("%s: env_ids must be a vector of %d integers" % (self._who, n))
+        ids = ids.astype(np.int64)
+        if ids.min() < 0 or ids.max() >= self.num_envs:
+            raise ValueError("%s: env_ids outside [0, %d)" % (self._who, self.num_envs))
+        if np.unique(ids).shape[0] != n:
+            raise ValueError("%s: duplicate env_ids" % self._who)
+        return ids
+
+    def _need_stack(self, what):
+        if self.k < 2:
+            raise ValueError("%s.%s: latent stacking is off (build it with stacked(.., latent_stack=k))" % (self._who, what))
+
+    def restart(self, env_ids=None):
+        """These lanes (None: all) start an episode with their next call: its row repeats its own latent and the lane's old history is never read."""
+        self._need_stack("restart")
+        if env_ids is None:
+            self.fresh[:] = True
+        else:
+            ids = np.asarray(env_ids)
+            self.fresh[self.lanes_checked(ids, ids.shape[0] if ids.ndim == 1 else -1)] = True
+
+    def history_state(self):
+        """What a training script writes to its checkpoint: {"latent_stack", "z_dim", "history": float32 [num_envs, latent_stack - 1, z_dim], "fresh": bool [num_envs]}."""
+        self._need_stack("history_state")
+        return {"latent_stack": self.k, "z_dim": self.z_dim, "history": self.history.cpu().numpy(), "fresh": self.fresh.copy()}
+
+    def load_history_state(self, d):
+        """Takes history_state()'s dict back.  The whole dict is checked before anything changes (ValueError)."""
+        import torch
+        self._need_stack("load_history_state")
+        d = latent_history_state_checked(d, self.k, self.z_dim, self.num_envs, self._who + ".load_history_state")
+        self.history.copy_(torch.from_numpy(d["history"]))
+        self.fresh[:] = d["fresh"]
 
     def set_observation_normalization(self, state_dict):
         """The FROZEN evaluation step: a checkpointed observation_normalization_state() of a buffer (None: off) is applied by every call from now on
@@ -352,11 +492,11 @@ class BatchedRolloutStep(_StepBase):
             self._obs_norm = None
             return
         who = self._who + ".set_observation_normalization"
-        d = observation_normalization_state_checked(state_dict, self.z_dim + self.n_meas, who)
-        settings = _obs_norm_settings_of(d, self.z_dim, who, "step")
-        on = _obs_norm_tensors(self.device, self.z_dim + self.n_meas, self.num_envs)
+        d = observation_normalization_state_checked(state_dict, self.din, who)
+        settings = _obs_norm_settings_of(d, self.latent_cols, who, "step")
+        on = _obs_norm_tensors(self.device, self.din, self.num_envs)
         on.update(settings)
-        _obs_norm_load(self.L, on, d, self.z_dim)
+        _obs_norm_load(self.L, on, d, self.latent_cols)
         self._obs_norm = on
 
     def check(self, frames_u8, measurements, greedy, noise):
@@ -377,21 +517,31 @@ class BatchedRolloutStep(_StepBase):
                 raise ValueError("%s: expected noise [%d, %d]" % (self._who, n, self.A))
         return f, n, meas, nz
 
-    def record(self, f, n, meas, nz, greedy, table_rows=None, states=None, actions=None, values=None, raw_states=None):
+    def record(self, f, n, meas, nz, greedy, table_rows=None, states=None, actions=None, values=None, raw_states=None, lanes=None, advance=True):
         """One device call on checked inputs.  table_rows None: mi_rollout_step_batch; else the int32 table rows go behind the noise and mi_rollout_step_batch_rec also
         leaves state / action / value of row i in row table_rows[i] of the device tables `states`, `actions`, `values`.  With observation normalisation on
-        (set_observation_normalization) either becomes mi_rollout_step_batch_norm: `states` then takes the normalised rows and `raw_states` the raw ones."""
+        (set_observation_normalization) either becomes mi_rollout_step_batch_norm: `states` then takes the normalised rows and `raw_states` the raw ones.
+        With latent stacking on every form is mi_rollout_step_batch_stack: `lanes` (None: 0 .. n-1) and their fresh flags go behind the table rows, the lanes' history
+        advances unless `advance` is False, and the lanes are no longer fresh afterwards."""
         import torch
         nm, na = n * self.n_meas, n * self.A
         nr = 0 if table_rows is None else n
+        # (getattr, here and in the buffers, as for `_kind`: the host tests' stub steps -- tests/test_mlp_rollout_host.py, test_observation_normalization_host.py,
+        # test_rollout_update_sequence_host.py -- are built without _setup() and carry none of its attributes)
+        stacked = getattr(self, "k", 1) > 1
+        ns = 2 * n if stacked else 0
         if not greedy:
             self._f_np[nm:nm + na] = (self._rng.standard_normal((n, self.A)) if nz is None else nz).reshape(-1)
         self._in_np[:n * self.frame_bytes] = f.reshape(-1)
         self._f_np[:nm] = meas.reshape(-1)                                           # f64 -> f32 at the feed, as ppo.py:108-109
         if nr:
             self._i_np[nm + na:nm + na + nr] = table_rows
+        if stacked:
+            lanes = np.arange(n) if lanes is None else lanes
+            self._i_np[nm + na + nr:nm + na + nr + n] = lanes
+            self._i_np[nm + na + nr + n:nm + na + nr + ns] = self.fresh[lanes]
         st = torch.cuda.current_stream(self.device)
-        used = self._f_off + 4 * (nm + na + nr)
+        used = self._f_off + 4 * (nm + na + nr + ns)
         if self.d_in is not None:
             self.d_in[:used].copy_(self.h_in[:used], non_blocking=True)
         base = (self.h_in if self.d_in is None else self.d_in).data_ptr()
@@ -399,7 +549,18 @@ class BatchedRolloutStep(_StepBase):
         args = (self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, None if greedy else fptr + 4 * nm, 1 if greedy else 0, n,
                 self.scratch.data_ptr(), self.scratch_bytes, (self.h_out if self.d_out is None else self.d_out).data_ptr())
         on = self._obs_norm
-        if getattr(self, "_kind", "conv") == "mlp":                                  # one entry: obs_mean NULL = not normalised, table_rows NULL = nothing recorded
+        if stacked:                                                                  # one entry per encoder: obs_mean NULL = not normalised, table_rows NULL = nothing recorded
+            out_base = (self.h_out if self.d_out is None else self.d_out).data_ptr()
+            norm = (None, None, 0.0) if on is None else (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"])
+            if table_rows is None:
+                tabs = (None, 0, None, None, None, None)
+            else:
+                tabs = (fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), None if on is None else raw_states.data_ptr(), actions.data_ptr(), values.data_ptr())
+            iptr = fptr + 4 * (nm + na + nr)
+            entry = self.L.mi_mlp_rollout_step_batch_stack if getattr(self, "_kind", "conv") == "mlp" else self.L.mi_rollout_step_batch_stack
+            entry(*args, *norm, *tabs, self.k, self.history.data_ptr(), self.num_envs, iptr, iptr + 4 * n, 1 if advance else 0, self.sstate.data_ptr(),
+                  out_base + 4 * self._older_off)
+        elif getattr(self, "_kind", "conv") == "mlp":                                # one entry: obs_mean NULL = not normalised, table_rows NULL = nothing recorded
             norm = (None, None, 0.0, None) if on is None else (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr())
             if table_rows is None:
                 tabs = (None, 0, None, None, None, None)
@@ -419,20 +580,38 @@ class BatchedRolloutStep(_StepBase):
             self.L.mi_rollout_step_batch_rec(*args, fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), actions.data_ptr(), values.data_ptr())
         if self.d_out is not None:
             self.h_out[:n * self.row].copy_(self.d_out[:n * self.row], non_blocking=True)
+            if stacked:
+                lo, hi = self._older_off, self._older_off + n * (self.k - 1) * self.z_dim
+                self.h_out[lo:hi].copy_(self.d_out[lo:hi], non_blocking=True)
         st.synchronize()
         o = self._out_np[:n]
-        return o[:, :self.A].copy(), o[:, self.A].copy(), np.concatenate([o[:, self.A + 1:].astype(np.float64), meas], axis=1)
+        if not stacked:
+            return o[:, :self.A].copy(), o[:, self.A].copy(), np.concatenate([o[:, self.A + 1:].astype(np.float64), meas], axis=1)
+        if advance:
+            self.fresh[lanes] = False
+        older = self._older_np[:n * (self.k - 1) * self.z_dim].reshape(n, -1)       # the raw row the kernel assembled: [z_t | the older latents | measurements]
+        return o[:, :self.A].copy(), o[:, self.A].copy(), np.concatenate([o[:, self.A + 1:], older, meas.astype(np.float32)], axis=1).astype(np.float64)      # (the measurements as the kernel read them: fp32)
 
     def record_value(self, f, n, meas, table_rows, final_values):
         """The value-only device call on checked inputs (mi_rollout_value_batch_rec; with observation normalisation on, mi_rollout_value_batch_norm: the encoder chain,
         the value trunk and the value head; no action, no latent comes back): the int32 table rows go behind the measurements and the value of row i is also left in final_values[table_rows[i]].  -> float32 [n]."""
+        return self.record_value_lanes(f, n, meas, table_rows, final_values, None)
+
+    def record_value_lanes(self, f, n, meas, table_rows, final_values, lanes):
+        """record_value() with the history lanes of the rows (None: 0 .. n-1), which are read with latent stacking on only: the call is then
+        mi_rollout_value_batch_stack, which values the observation on its lane's history and never advances it."""
         import torch
         nm = n * self.n_meas
         self._in_np[:n * self.frame_bytes] = f.reshape(-1)
         self._f_np[:nm] = meas.reshape(-1)
         self._i_np[nm:nm + n] = table_rows
+        stacked = getattr(self, "k", 1) > 1                                          # latent stacking: mi_rollout_value_batch_stack; the history is read, never advanced
+        if stacked:
+            lanes = np.arange(n) if lanes is None else lanes
+            self._i_np[nm + n:nm + 2 * n] = lanes
+            self._i_np[nm + 2 * n:nm + 3 * n] = self.fresh[lanes]
         st = torch.cuda.current_stream(self.device)
-        used = self._f_off + 4 * (nm + n)
+        used = self._f_off + 4 * (nm + (3 * n if stacked else n))
         if self.d_in is not None:
             self.d_in[:used].copy_(self.h_in[:used], non_blocking=True)
         base = (self.h_in if self.d_in is None else self.d_in).data_ptr()
@@ -441,7 +620,12 @@ class BatchedRolloutStep(_StepBase):
                 (self.h_out if self.d_out is None else self.d_out).data_ptr())
         rec = (fptr + 4 * nm, int(final_values.shape[0]), final_values.data_ptr())
         on = self._obs_norm
-        if getattr(self, "_kind", "conv") == "mlp":
+        if stacked:
+            norm = (None, None, 0.0) if on is None else (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"])
+            iptr = fptr + 4 * (nm + n)
+            entry = self.L.mi_mlp_rollout_value_batch_stack if getattr(self, "_kind", "conv") == "mlp" else self.L.mi_rollout_value_batch_stack
+            entry(*args, *norm, *rec, self.k, self.history.data_ptr(), self.num_envs, iptr, iptr + 4 * n, self.sstate.data_ptr())
+        elif getattr(self, "_kind", "conv") == "mlp":
             norm = (None, None, 0.0, None) if on is None else (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr())
             self.L.mi_mlp_rollout_value_batch(*args, *norm, *rec)
         elif on is not None:
@@ -845,11 +1029,22 @@ class RolloutBuffer:
     _rows_class = RolloutRows
 
     def __init__(self, vae, ppo, num_envs, horizon, seed=None, io=None):
+        self._init(vae, ppo, num_envs, horizon, seed, io, 1)
+
+    @classmethod
+    def stacked(cls, vae, ppo, num_envs, horizon, latent_stack, seed=None, io=None):
+        """The buffer with LATENT STACKING (see the module docstring): cls(vae, ppo, num_envs, horizon, seed, io) whose step is BatchedRolloutStep.stacked(..,
+        latent_stack): the tables' states are [z_t | the latent_stack - 1 latents before it | measurements].  ValueError before anything touches a device."""
+        self = cls.__new__(cls)
+        self._init(vae, ppo, num_envs, horizon, seed, io, latent_stack)
+        return self
+
+    def _init(self, vae, ppo, num_envs, horizon, seed, io, latent_stack):
         import torch
         self.rows = self._rows_class(num_envs, horizon)                              # (raises before anything touches a device)
         self.vae, self.ppo = vae, ppo
         self.num_envs, self.horizon = self.rows.num_envs, self.rows.horizon
-        self._step = _RecordingStep(vae, ppo, self.num_envs, seed=seed, io=io)
+        self._step = _RecordingStep.stacked(vae, ppo, self.num_envs, latent_stack, seed=seed, io=io)
         self.io, self.device, self.L = self._step.io, self._step.device, self._step.L
         n = self.n_table_rows = self.num_envs * (self.horizon + 1)
         self.states = torch.zeros(n, int(ppo.input_dim), device=self.device)
@@ -876,7 +1071,11 @@ class RolloutBuffer:
         if settings is None:
             self._obs_norm = self.raw_states = self._step._obs_norm = None
             return
-        _obs_norm_derive(self.L, self._obs_norm_on(settings), self._step.z_dim)
+        _obs_norm_derive(self.L, self._obs_norm_on(settings), self._latent_cols())
+
+    def _latent_cols(self):
+        """The state's latent columns: z_dim, or latent_stack x z_dim with latent stacking on."""
+        return getattr(self._step, "latent_cols", self._step.z_dim)
 
     def _obs_norm_between_collections(self, what):
         if (self.rows.lengths > 0).any() or self.rows.awaiting.any():
@@ -903,17 +1102,17 @@ class RolloutBuffer:
         on = self._need_obs_norm("observation_normalization_state")
         state = on["state"].cpu().numpy()
         din = int(self.states.shape[1])
-        return {"count": float(state[0]), "mean": state[1:1 + din].copy(), "m2": state[1 + din:].copy(), "z_dim": self._step.z_dim, "clip": on["clip"],
+        return {"count": float(state[0]), "mean": state[1:1 + din].copy(), "m2": state[1 + din:].copy(), "z_dim": self._latent_cols(), "clip": on["clip"],
                 "epsilon": on["epsilon"], "frozen": on["frozen"], "normalize_latents": on["normalize_latents"]}
 
     def load_observation_normalization_state(self, d):
         """Takes observation_normalization_state()'s dict back: the setting is on afterwards, with these statistics and settings.  The whole dict is checked before
         anything changes (ValueError); only with no step recorded, like set_observation_normalization()."""
         d = observation_normalization_state_checked(d, int(self.states.shape[1]))
-        settings = _obs_norm_settings_of(d, self._step.z_dim, type(self).__name__ + ".load_observation_normalization_state", "buffer")
+        settings = _obs_norm_settings_of(d, self._latent_cols(), type(self).__name__ + ".load_observation_normalization_state", "buffer")
         self._obs_norm_between_collections("load_observation_normalization_state")
         on = self._obs_norm_on(settings)
-        _obs_norm_load(self.L, on, d, self._step.z_dim)
+        _obs_norm_load(self.L, on, d, self._latent_cols())
 
     def merge_observation_statistics(self):
         """Merges the raw rows of the steps recorded so far (rows.valid_rows()) into the statistics NOW, without an update, and re-derives what the step reads: for a
@@ -940,7 +1139,7 @@ class RolloutBuffer:
         rows = torch.from_numpy(np.ascontiguousarray(valid, np.int32)).to(self.device)
         scratch = torch.empty(int(self.L.mi_rollout_obs_stats_scratch_doubles(n, din)), dtype=torch.float64, device=self.device)
         self.L.mi_rollout_obs_stats(torch.cuda.current_stream(self.device).cuda_stream, self.raw_states.data_ptr(), self.n_table_rows, rows.data_ptr(), n, din,
-                                    0 if on["normalize_latents"] else self._step.z_dim, merge, on["epsilon"], on["clip"], on["state"].data_ptr(), on["mean32"].data_ptr(),
+                                    0 if on["normalize_latents"] else self._latent_cols(), merge, on["epsilon"], on["clip"], on["state"].data_ptr(), on["mean32"].data_ptr(),
                                     on["inv32"].data_ptr(), scratch.data_ptr(), on["batch"].data_ptr())
         batch = on["batch"].cpu().numpy()
         if merge and not np.isfinite(batch[0]).all():
@@ -1016,18 +1215,52 @@ class RolloutBuffer:
         return self.rows.lengths
 
     def reset(self):
-        """All rows empty and open.  (The statistics and carries of reward scaling belong to the run, not to a collection: they stay.)"""
+        """All rows empty and open.  (The statistics and carries of reward scaling belong to the run, not to a collection: they stay -- and so do the latent history
+        and its fresh flags: an episode may continue across an update.)"""
         self.rows.reset()
 
+    def _stacked(self):
+        return getattr(self._step, "k", 1) > 1                                       # latent stacking (latent_stack > 1)
+
+    def _lanes(self, env_ids, n):
+        """The history lanes of a call, with latent stacking on: its environments."""
+        return self.rows.env_ids(env_ids, n) if self._stacked() else None
+
+    @property
+    def history(self):
+        """Latent stacking: the device tensor [num_envs, latent_stack - 1, z_dim] (slot 0: the latent of the lane's previous step); None with the setting off."""
+        return getattr(self._step, "history", None)                                  # (never allocated with the setting off)
+
+    def restart_history(self, env_ids=None):
+        """These environments (None: all) were reset without a done or a truncation being reported: their next step starts an episode (its row repeats its own
+        latent), as zero_return_carry() does for reward scaling."""
+        if env_ids is not None:
+            ids = np.asarray(env_ids)
+            env_ids = self.rows.env_ids(ids, ids.shape[0] if ids.ndim == 1 else 0)
+        self._step.restart(env_ids)
+
+    def history_state(self):
+        """What a training script writes to its checkpoint: {"latent_stack", "z_dim", "history": float32 [num_envs, latent_stack - 1, z_dim], "fresh": bool [num_envs]}."""
+        return self._step.history_state()
+
+    def load_history_state(self, d):
+        """Takes history_state()'s dict back (of this buffer or of another of the same shape).  The whole dict is checked before anything changes (ValueError)."""
+        self._step.load_history_state(d)
+
     def step(self, frames_u8, measurements, env_ids=None, greedy=False, noise=None):
-        """BatchedRolloutStep.__call__ of these frames, and row i of the call is recorded at slot lengths[env_ids[i]] of environment env_ids[i] (None: 0 .. n-1)."""
+        """BatchedRolloutStep.__call__ of these frames, and row i of the call is recorded at slot lengths[env_ids[i]] of environment env_ids[i] (None: 0 .. n-1).
+        With latent stacking on the environments' history advances."""
         f, n, meas, nz = self._step.check(frames_u8, measurements, greedy, noise)
         rows = self.rows.step_rows(env_ids, n)
-        return self._step.record(f, n, meas, nz, greedy, rows, self.states, self.actions, self.values, self.raw_states)
+        return self._step.record(f, n, meas, nz, greedy, rows, self.states, self.actions, self.values, self.raw_states, lanes=self._lanes(env_ids, n))
 
     def outcome(self, rewards, dones, env_ids=None):
-        """Reward and done of the step just recorded for these environments (the simulator's answer to the action); the row's length grows by one."""
+        """Reward and done of the step just recorded for these environments (the simulator's answer to the action); the row's length grows by one.  With latent
+        stacking on, an environment that reports done starts its next step from a fresh history."""
         self.rows.outcome(rewards, dones, env_ids)
+        if self._stacked():
+            d = np.asarray(dones)
+            self._step.fresh[self.rows.env_ids(env_ids, d.shape[0])[d.astype(bool)]] = True
 
     def bootstrap(self, frames_u8, measurements, env_ids=None):
         """The state after the last step of these environments (None: every stepped row still open) and its value into slot lengths[e] (train.py:172; computed after a
@@ -1036,7 +1269,8 @@ class RolloutBuffer:
             env_ids = self.rows.stepped()
         f, n, meas, _ = self._step.check(frames_u8, measurements, True, None)
         rows = self.rows.bootstrap_rows(env_ids, n)
-        return self._step.record(f, n, meas, None, True, rows, self.states, self.actions, self.values, self.raw_states)
+        # (latent stacking: the history is read and not advanced -- the same observation is stepped again when the episode continues into the next collection)
+        return self._step.record(f, n, meas, None, True, rows, self.states, self.actions, self.values, self.raw_states, lanes=self._lanes(env_ids, n), advance=False)
 
     def update(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, stage_times=None):
         """One PPO update from the tables (train.py:175-207 over the recorded rows): mi_rollout_finish, update_old_policy, log pi_old once, num_epochs x shuffled
@@ -1335,8 +1569,11 @@ class ContinuousRolloutBuffer(RolloutBuffer):
     _rows_class = SegmentedRows
 
     def __init__(self, vae, ppo, num_envs, horizon, seed=None, io=None):
+        self._init(vae, ppo, num_envs, horizon, seed, io, 1)
+
+    def _init(self, vae, ppo, num_envs, horizon, seed, io, latent_stack):
         import torch
-        super().__init__(vae, ppo, num_envs, horizon, seed=seed, io=io)
+        super()._init(vae, ppo, num_envs, horizon, seed, io, latent_stack)
         self.final_values = torch.zeros(self.n_table_rows, device=self.device)
 
     def bootstrap(self, frames_u8, measurements, env_ids=None):
@@ -1354,7 +1591,12 @@ class ContinuousRolloutBuffer(RolloutBuffer):
         (mi_rollout_value_batch_rec; with observation normalisation on, mi_rollout_value_batch_norm) leaves V(final observation) in final_values at the row of that step; update() bootstraps the segment from it.  -> float32 [n]."""
         f, n, meas, _ = self._step.check(final_frames_u8, final_measurements, True, None)
         rows = self.rows.truncate_rows(env_ids, n)
-        return self._step.record_value(f, n, meas, rows, self.final_values)
+        if not self._stacked():
+            return self._step.record_value(f, n, meas, rows, self.final_values)
+        lanes = self.rows.env_ids(env_ids, n)                                        # latent stacking: the final observation is valued on the episode's history, the lane's next step starts afresh
+        values = self._step.record_value_lanes(f, n, meas, rows, self.final_values, lanes)
+        self._step.fresh[lanes] = True
+        return values
 
     def update(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, normalize="segment", stage_times=None):
         """RolloutBuffer.update with one mi_rollout_finish_segments call for the finish (mi_rollout_finish_segments_boot, which also takes the per-segment bootstrap

@@ -501,6 +501,34 @@ int mi_mlp_rollout_value_batch(void* mlp_h, void* ppo_h, void* stream, const uns
  * first_col outside [0, din]; merge outside {0, 1}; epsilon not finite or < 0; clip NaN or <= 0 (+inf is valid). */
 long long mi_rollout_obs_stats_scratch_doubles(long long n, int din);
 int mi_rollout_obs_stats(void* stream, const float* tab_raw_states, long long n_table_rows, const int* row_idx, long long n, int din, int first_col, int merge, double epsilon, float clip, double* state, float* obs_mean, float* obs_inv_std, double* scratch, double* batch_out);
+/* LATENT STACKING — frame stacking (the usual remedy for a feed-forward policy that sees one frame per step) on the compressed observation, no reference counterpart in
+ * train.py: the batched step of vae_common.py:45-61 + ppo.py:231-251 on the state
+ *   s_t = [ z_t | z_{t-1} | .. | z_{t-k+1} | measurements_t ],   din = k z_dim + n_meas <= 1024,   2 <= k = latent_stack <= MI_ROLLOUT_MAX_STACK
+ * One more launch than mi_rollout_step_batch (rollout_stack_kernel, where the normaliser of mi_rollout_step_batch_norm runs: between the mean layer and trunk layer 1), one
+ * block per call row e.  hist: fp32 [n_lanes][k - 1][z_dim], HBM, the per-environment memory: slot 0 of lane l is the latent of that lane's previous step.  lanes / first:
+ * int32 [n], HBM or pinned host memory like the other inputs: the history lane of call row e (the lanes of one call are distinct: the caller's duty) and whether the row
+ * is the first step of an episode.  With z_t = mean_raw + mean_bias, the sum `out` returns as z:
+ *   old_i = first[e] != 0 ? z_t : hist[lanes[e]][i - 1],  i = 1 .. k - 1        (a select: NaN in a history that `first` overrides does not reach the row)
+ *   row   = [ z_t | old_1 | .. | old_{k-1} | measurements[e] ]
+ * An episode's first step repeats its own latent, as frame stacking pads with the first observation.  A lane outside [0, n_lanes) is treated as `first` and no history is
+ * read or written for it.  The row goes, as plain vector stores of one register, to sstate[e] (fp32 [n][din], HBM, 16-byte aligned, the caller's: trunk layer 1 reads
+ * it) and, where table_rows != NULL and r = table_rows[e] lies in [0, n_table_rows), to tab_states[r]; old_1 .. old_{k-1} go to older_out[e] (fp32 [n][(k - 1) z_dim], HBM
+ * or pinned host memory; NULL: nowhere), so the caller can return the whole state without a copy of the history.  obs_mean != NULL (fp32 [din], with obs_inv_std and
+ * obs_clip as in mi_rollout_step_batch_norm): sstate[e] and tab_states[r] take min(max((s - obs_mean[j]) * obs_inv_std[j], -obs_clip), obs_clip) instead and
+ * tab_raw_states[r] the raw row; obs_mean == NULL: obs_inv_std and tab_raw_states must be NULL too.  The recording heads store tab_actions[r] and tab_values[r] and no
+ * state row.  Behind a barrier -- every read of a lane's history comes before every write of it -- and only with advance != 0:
+ *   hist[lanes[e]] = [ z_t | old_1 | .. | old_{k-2} ]
+ * advance == 0 writes nothing into hist (the bootstrap observation is stepped again when its episode continues).  `out`, noise, greedy, scratch: as in mi_rollout_step_batch.
+ * mi_rollout_value_batch_stack: mi_rollout_value_batch_rec on the stacked state; it never advances the history and writes neither a table of states nor older latents.
+ * The mi_mlp_ forms: the same two behind the encoder chain of mi_mlp_rollout_step_batch (an MlpVAE handle goes to these only; their value form takes table_rows == NULL).
+ * Errors, each under the entry's own name, before any launch, nothing written: those of the entries they extend; latent_stack < 2 or > MI_ROLLOUT_MAX_STACK; hist, lanes,
+ * first or sstate NULL, n_lanes < 1, sstate not 16-byte aligned; obs_clip <= 0 or NaN with obs_mean; table_rows without its tables (MI_ERR_ARG);
+ * latent_stack * z_dim + n_meas != the policy's input size; more than 1024 inputs (MI_ERR_SHAPE). */
+#define MI_ROLLOUT_MAX_STACK 16
+int mi_rollout_step_batch_stack(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n, void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values, int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, int advance, float* sstate, float* older_out);
+int mi_rollout_value_batch_stack(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n, void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, const int* table_rows, long long n_table_rows, float* tab_final_values, int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, float* sstate);
+int mi_mlp_rollout_step_batch_stack(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n, void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values, int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, int advance, float* sstate, float* older_out);
+int mi_mlp_rollout_value_batch_stack(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n, void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, const int* table_rows, long long n_table_rows, float* tab_final_values, int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, float* sstate);
 
 /* ---- collectives of the data-parallel path (no reference counterpart: the reference is single-process) ----
  * RCCL over xGMI, one communicator per process = per GPU; librccl.so.1 is bound at mi_comm_init (a single-GPU process never loads it).

@@ -3,6 +3,7 @@ VAE.encode([frame]) (host frame -> device, conv stack, mean to host) followed by
 
     python tools/rollout_latency.py --envs [1,2,4,8,16,32,64] [--rounds 3] [--calls 200] [--batched-only | --record | --value | --obs-norm] [--no-box]
     python tools/rollout_latency.py --mlp [--envs 1,8,64] [--rounds 3] [--calls 200] [--no-box]
+    python tools/rollout_latency.py --stack 4 [--envs 1,8,64] [--rounds 3] [--calls 200] [--no-box]
 
 times, for each number of environments E, one BatchedRolloutStep call against a loop of E RolloutStep calls and against the two-call path (VAE.encode of E float
 frames + PPO.predict of E states) on the same engines: the three are interleaved in every round, the line gives the median of the rounds' medians, the spread of
@@ -15,7 +16,10 @@ the value-only call with running observation normalisation on (mi_rollout_step_b
 against the same calls of a twin buffer with the setting off, without the row book-keeping and at fixed table rows, interleaved; behind the table it times the merge
 (mi_rollout_obs_stats alone, device events) over 1024 rows of 128 columns.  --mlp builds an MlpVAE (38400 -> 512 -> 256 -> 64) in place of the ConvVAE and times, at
 E = 1, 8, 64 in interleaved rounds, the batched step (mi_mlp_rollout_step_batch), the two-call path on the same model and the recording call at fixed table rows, next to
-the floor of layer 1: the 78.6 MB of its fp32 kernel at the box's measured read rate."""
+the floor of layer 1: the 78.6 MB of its fp32 kernel at the box's measured read rate.  --stack K times the recording call and the value-only call with latent stacking on
+(stacked(.., latent_stack=K) at z_dim = 64: a policy of 64 K + 3 inputs with PPO.set_wide_inputs(); mi_rollout_step_batch_stack / mi_rollout_value_batch_stack: one more launch,
+rollout_stack_kernel) against the same calls of a buffer with the setting off (the 67-input policy), without the row book-keeping and at fixed table rows, interleaved,
+at E = 1, 8, 64 (or --envs)."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
@@ -33,6 +37,7 @@ ap.add_argument("--record", action="store_true", help="RolloutBuffer.step agains
 ap.add_argument("--value", action="store_true", help="the value-only call (mi_rollout_value_batch_rec) against the greedy recording call")
 ap.add_argument("--obs-norm", action="store_true", help="the recording and value-only calls with observation normalisation on against the setting off; the merge at 1024 x 128")
 ap.add_argument("--mlp", action="store_true", help="an MlpVAE encoder: the batched step, the two-call path and the recording call at E = 1, 8, 64 (or --envs)")
+ap.add_argument("--stack", type=int, default=0, metavar="K", help="the recording and value-only calls with latent_stack=K against the setting off at E = 1, 8, 64 (or --envs)")
 ap.add_argument("--no-box", action="store_true")
 args = ap.parse_args()
 
@@ -105,6 +110,21 @@ def envs_table():
                 f, n, meas, _ = cbuf._step.check(u8[sl(i)], ms[sl(i)], True, None)
                 cbuf._step.record_value(f, n, meas, slot0, cbuf.final_values)
             paths, after = [("greedy recording", greedy_recording), ("value-only", value_only)], {}
+        if args.stack:
+            from rollout import ContinuousRolloutBuffer
+            off = ContinuousRolloutBuffer(vae, agent, E, horizon=64, io=many.io)
+            on = ContinuousRolloutBuffer.stacked(vae, stacked_agent(), E, 64, args.stack, io=many.io)
+            slot0, lanes = (np.arange(E) * (off.horizon + 1)).astype(np.int32), np.arange(E)
+
+            def recording_of(b):
+                kw = {"lanes": lanes} if b is on else {}
+                return lambda i: b._step.record(*b._step.check(u8[sl(i)], ms[sl(i)], False, None), False, slot0, b.states, b.actions, b.values, b.raw_states, **kw)
+            def value_of(b):
+                def call(i):
+                    f, n, meas, _ = b._step.check(u8[sl(i)], ms[sl(i)], True, None)
+                    b._step.record_value_lanes(f, n, meas, slot0, b.final_values, lanes)
+                return call
+            paths, after = [("recording", recording_of(off)), ("recording, stack", recording_of(on)), ("value-only", value_of(off)), ("value-only, stack", value_of(on))], {}
         if args.obs_norm:
             from rollout import ContinuousRolloutBuffer
             off, on = (ContinuousRolloutBuffer(vae, agent, E, horizon=64, io=many.io) for _ in range(2))
@@ -130,6 +150,8 @@ def envs_table():
             line += "  %s %.1f us (rounds %.1f - %.1f, p90 %.1f)" % (name, med[name], min(meds), max(meds), np.percentile(np.concatenate(ts[name]), 90))
         if args.record and not args.value:
             line += "  | recording - batched %+.2f us, w/o book-keeping %+.2f us" % (med["recording"] - med["batched"], med["recording w/o book-keeping"] - med["batched"])
+        elif args.stack:
+            line += "  | stack %d - off: recording %+.2f us, value-only %+.2f us" % (args.stack, med["recording, stack"] - med["recording"], med["value-only, stack"] - med["value-only"])
         elif args.obs_norm:
             line += "  | obs-norm - off: recording %+.2f us, value-only %+.2f us" % (med["recording, obs-norm"] - med["recording"], med["value-only, obs-norm"] - med["value-only"])
         elif args.value:
@@ -137,6 +159,19 @@ def envs_table():
         elif not args.batched_only:
             line += "  | loop / batched %.2f x, two-call / batched %.2f x" % (med["loop of B=1"] / med["batched"], med["two-call"] / med["batched"])
         print(line, flush=True)
+
+
+_stacked = []
+
+
+def stacked_agent():
+    """The policy of --stack K: 64 K + 3 inputs, on the fused kernels' wide range (one engine for every E)."""
+    if not _stacked:
+        a = PPO(np.array([64 * args.stack + 3]), Box(), model_dir=tempfile.mkdtemp())
+        a.set_wide_inputs()
+        a.init_session(init_logging=False)
+        _stacked.append(a)
+    return _stacked[0]
 
 
 def mlp_table():
@@ -209,6 +244,8 @@ def merge_time(n=1024, din=128, calls=50):
 if args.mlp:
     mlp_table()
     sys.exit(0)
+if args.stack and args.envs is None:
+    args.envs = "1,8,64"
 if args.envs is not None:
     envs_table()
     if args.obs_norm:
