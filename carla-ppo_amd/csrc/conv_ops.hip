@@ -248,12 +248,18 @@ extern "C" int mi_tapwgrad_defer(int on) {               // switching the mode d
 extern "C" int mi_tapwgrad_defer_pause(int pause) { const int prev = g_defer_pause; g_defer_pause = pause ? 1 : 0; return prev; }
 static thread_local int t_slab_bf16 = -1;                  // this thread's override for the pass it is issuing (-1: the process default, K_SLAB_BF16_DEFAULT)
 static inline int slab_bf16_now() { return t_slab_bf16 >= 0 ? t_slab_bf16 : knob(K_SLAB_BF16_DEFAULT); }
+static thread_local int t_bias_rows = 0;                   // this thread's pass wants the bias sums of a one-split launch ordered as well (see try_tapwgrad)
+extern "C" int mi_tapwgrad_bias_rows(int on) { const int prev = t_bias_rows; t_bias_rows = on ? 1 : 0; return prev; }
 extern "C" int mi_tapwgrad_slab_bf16(int on) { const int prev = t_slab_bf16; t_slab_bf16 = on < 0 ? -1 : (on ? 1 : 0); return prev; }
 static int tapwgrad_flush_reduces(void* stream);
 extern "C" int mi_tapwgrad_flush(void* stream) {
     int rc = tapwgrad_flush_reduces(stream);
     const int nf = g_nfolds;
     g_nfolds = 0;
+    // A fold reads its layer's bias sums (tmp_bias).  A LONE deferred filter gradient reduces them through mi_reduce_slabs, and inside a backward PART (mi_vae_backward,
+    // part != 0) that call only records a job in the pass's small-reduce list, which is bound to this very stream and flushed behind this function: the fold then read the
+    // zeros of the memset and the split-storage engine lost conv2's bias gradient in every data-parallel step.  The list runs first.
+    if (nf > 0 && rc == MI_OK) rc = mi_small_reduce_flush_bound(stream);
     for (int i = 0; i < nf && rc == MI_OK; ++i) rc = launch_fold((hipStream_t)stream, g_folds[i]);
     return rc;
 }
@@ -356,6 +362,12 @@ int try_tapwgrad(hipStream_t st, int dtype, int mode, const void* a, const void*
     if (scratch && splits > 1 && (((uintptr_t)scratch) & 15) == 0 && scratch_bytes >= slab_bytes + bias_bytes && slab_floats < (1ll << 29) && (!dbias || N <= 256)) {
         q.slabs = (float*)scratch;
         if (dbias) q.bias_part = (float*)((char*)scratch + slab_bytes);
+    } else if (t_bias_rows && scratch && splits == 1 && dbias && (((uintptr_t)scratch) & 15) == 0 && scratch_bytes >= bias_bytes && N <= 256) {
+        // ONE position split (a few frames of a small layer): dW needs no slabs, but every bias element is still the sum of bias_nh x NE / N partial sums (position halves, parity
+        // classes).  Through atomics they met in any order: two runs of a small-batch step differed in the last bit of a bias gradient.  Where the caller asked for it
+        // (mi_tapwgrad_bias_rows: the VAE engine) the partial sums take the FIRST bias_bytes of the scratch -- there are no slabs in front of them -- and the ordered pass below.
+        // Off (the layer-op entry points' default): a scratch that holds no slabs stays untouched, as before.
+        q.bias_part = (float*)scratch;
     }
     q.gx = splits; q.gy = gy;
     dim3 g((unsigned)((splits + 7) / 8 * 8 * gy), 1, 1);   // 1-D: the column blocks of a position split share an XCD (tapwgrad_tile.hpp)
@@ -388,6 +400,8 @@ int try_tapwgrad(hipStream_t st, int dtype, int mode, const void* a, const void*
         r.bpart = q.bias_part; r.bout = dbias; r.bnslab = splits * q.bias_nh * (q.NE / N); r.bN = N;
         if (g_defer_reduces && !g_defer_pause && g_npending < 16) g_pending[g_npending++] = r;
         else { launch_tiled_reduce(st, r); rc = mi_check_launch("reduce_tiled_kernel"); }
+    } else if (rc == MI_OK && q.bias_part) {
+        rc = mi_reduce_slabs(st, q.bias_part, (long long)N, splits * q.bias_nh * (q.NE / N), (long long)N, dbias);
     }
     return rc == MI_OK ? 1 : rc;
 }
@@ -412,6 +426,7 @@ int try_tapwgrad_split(hipStream_t st, int mode, const void* a, const void* d, i
     if (r <= 0) return r;
     PendingFold f = {tmp, out, tb, dbias, KH * KW, mode == TC_CONV ? C : N, mode == TC_CONV ? N : C, N};
     if (g_defer_reduces && !g_defer_pause && g_nfolds < 16) { g_folds[g_nfolds++] = f; return 1; }
+    { const int rcf = mi_small_reduce_flush_bound(st); if (rcf != MI_OK) return rcf; }      // (the fold reads the bias sums: a deferring pass on this stream may only have recorded them)
     const int rc = launch_fold(st, f);
     return rc == MI_OK ? 1 : rc;
 }
@@ -867,6 +882,11 @@ extern "C" int mi_small_reduce_flush(void* stream) {
     return sr_launch_params(t_sr_stream, t_sr);
 }
 extern "C" int mi_small_reduce_deferring(void) { return t_sr_defer; }
+// the recorded jobs now, if the list belongs to `stream` (anything else: nothing happens, nothing is an error)
+extern "C" int mi_small_reduce_flush_bound(void* stream) {
+    if (t_sr.njobs == 0 || (hipStream_t)stream != t_sr_stream) return MI_OK;
+    return sr_launch_params(t_sr_stream, t_sr);
+}
 
 void mi_get_trace(long long** buf, int* cap) { *buf = g_trace; *cap = g_trace_cap; }
 

@@ -26,6 +26,7 @@ int mi_check_launch(const char* what);           // hipGetLastError() -> MI_OK /
 extern "C" int mi_tapwgrad_defer(int on);        // returns the previous mode
 extern "C" int mi_tapwgrad_flush(void* stream);  // launches the recorded reduces on `stream`
 extern "C" int mi_tapwgrad_defer_pause(int pause);   // != 0: reduce right behind the launch although the pass defers (a layer issued on another stream); returns the previous setting
+extern "C" int mi_tapwgrad_bias_rows(int on);    // != 0: a filter gradient with ONE position split sums its bias partial rows through the scratch in a fixed order instead of atomics (public: mi355_carla.h); returns the previous setting
 extern "C" int mi_tapwgrad_slab_bf16(int on);    // partial-sum slabs rounded to bf16 (the engine's bf16 backward); returns the previous setting
 
 // register-weight kernel of the thin gather-form layers (rwconv.hip): 1 launched, 0 not eligible, < 0 error
@@ -43,6 +44,7 @@ extern "C" int mi_small_reduce_defer(int on);
 extern "C" int mi_small_reduce_flush(void* stream);
 extern "C" int mi_small_reduce_bind(void* stream);      // the list of the deferring pass belongs to `stream`; mi_reduce_slabs calls from other streams launch immediately (round 5)
 extern "C" int mi_small_reduce_deferring(void);
+extern "C" int mi_small_reduce_flush_bound(void* stream);      // issues the recorded jobs if the list belongs to `stream`; otherwise nothing (mi_tapwgrad_flush, in front of its folds)
 
 // global-norm gradient clipping in front of TF ApplyAdam (elementwise.hip; the PPO engine).  mi_grad_sumsq: sum of (double)g * (double)g over `count` tensors of a
 // flat fp32 buffer (offsets in floats, multiples of 4; what lies between the tensors is not read) as MI_GRAD_NORM_BLOCKS ordered block partials.  mi_grad_norm_finish:

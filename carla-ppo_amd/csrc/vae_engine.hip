@@ -45,7 +45,17 @@ bool make_geom(const MiVaeDesc& d, Geom& g) {
         g.dh[i + 1] = (g.dh[i] - 1) * 2 + DEC_K[i]; g.dw[i + 1] = (g.dw[i] - 1) * 2 + DEC_K[i];
         g.dc[i + 1] = i < 3 ? DEC_F[i] : d.ct;
     }
-    return true;
+    // source and target frames share height and width (the loss reads the target table with the logits' stride): the decoder must return the encoder's input size,
+    // which it does exactly when a side is 16 e + 32 (e = that side of conv4's output): 48, 64, 80, 96, ...
+    return g.dh[4] == d.ih && g.dw[4] == d.iw;
+}
+
+// The latent width is a reduction length of dense1's forward pass and filter gradient (K = z_dim) and of the heads' input gradient (K = 2 z_dim), and those kernels read
+// their rows in 16-byte vectors (mi_gemm_bias_act / mi_gemm_wgrad: "pad K"): eight bf16 elements, four fp32 / split-storage ones.  (The reparameterisation kernels and the
+// optimiser's weight copies take any even width.)  0: this storage type runs the width; otherwise the multiple it needs.
+int z_dim_multiple(const MiVaeDesc& d) {
+    const int m = d.dtype == MI_BF16 ? 8 : 4;
+    return (d.z_dim >= m && d.z_dim % m == 0) ? 0 : m;
 }
 
 void make_layout(const MiVaeDesc& d, const Geom& g, Layout& L) {
@@ -230,9 +240,22 @@ void make_workspace(VaeEngine& e) {
     W.total = o;
 }
 
-bool init_engine(VaeEngine& e, const MiVaeDesc* desc) {
+// false: the descriptor is refused, and mi_last_error() says why under the caller's name
+bool init_engine(VaeEngine& e, const MiVaeDesc* desc, const char* who) {
+    char msg[256];
+    if (!desc) { snprintf(msg, sizeof(msg), "%s: missing descriptor", who); mi_fail(MI_ERR_ARG, msg); return false; }
     e.d = *desc;
-    if (!make_geom(e.d, e.g)) return false;
+    if (!make_geom(e.d, e.g)) {
+        snprintf(msg, sizeof(msg), "%s: unsupported geometry (%d x %d frames: every side must be 16 e + 32 with e >= 1 -- 48, 64, 80, 96, ...)", who, desc->ih, desc->iw);
+        mi_fail(MI_ERR_SHAPE, msg);
+        return false;
+    }
+    if (const int m = z_dim_multiple(e.d)) {
+        snprintf(msg, sizeof(msg), "%s: unsupported z_dim %d: %s storage needs z_dim to be a positive multiple of %d (the latent layers read their rows in 16-byte vectors)",
+                 who, desc->z_dim, e.d.dtype == MI_BF16 ? "bf16" : "fp32 / split", m);
+        mi_fail(MI_ERR_SHAPE, msg);
+        return false;
+    }
     make_layout(e.d, e.g, e.L);
     e.esz = e.d.dtype == MI_BF16 ? 2 : 4;                  // MI_F32 and MI_BF16X3 (split storage) are 4-byte elements
     const int bk = e.d.dtype == MI_BF16 ? 32 : 16;
@@ -395,7 +418,7 @@ int mi_vae_tensor_count(void) { return N_TENSORS; }
 
 long long mi_vae_param_floats(const MiVaeDesc* d) {
     VaeEngine e;
-    if (!d || !init_engine(e, d)) { mi_fail(MI_ERR_SHAPE, "mi_vae_param_floats: unsupported geometry"); return -1; }
+    if (!init_engine(e, d, "mi_vae_param_floats")) return -1;
     return e.L.total;
 }
 
@@ -403,7 +426,7 @@ long long mi_vae_param_floats(const MiVaeDesc* d) {
 // conv1..4 {kernel,bias}, heads {kernel [flat,2Z] = [mean|logstd_sqare], bias [2Z]}, dense1 {kernel,bias}, deconv1..4 {kernel,bias}
 int mi_vae_param_layout(const MiVaeDesc* d, long long* offsets, long long* sizes, int n) {
     VaeEngine e;
-    if (!d || !init_engine(e, d)) return mi_fail(MI_ERR_SHAPE, "mi_vae_param_layout: unsupported geometry");
+    if (!init_engine(e, d, "mi_vae_param_layout")) return MI_ERR_SHAPE;
     if (n != N_TENSORS) return mi_fail(MI_ERR_ARG, "mi_vae_param_layout: expected 20 entries");
     for (int i = 0; i < N_TENSORS; ++i) { offsets[i] = e.L.off[i]; sizes[i] = e.L.size[i]; }
     return MI_OK;
@@ -411,7 +434,7 @@ int mi_vae_param_layout(const MiVaeDesc* d, long long* offsets, long long* sizes
 
 long long mi_vae_workspace_bytes(const MiVaeDesc* d) {
     VaeEngine e;
-    if (!d || !init_engine(e, d)) { mi_fail(MI_ERR_SHAPE, "mi_vae_workspace_bytes: unsupported geometry"); return -1; }
+    if (!init_engine(e, d, "mi_vae_workspace_bytes")) return -1;
     return e.W.total;
 }
 
@@ -419,7 +442,7 @@ void* mi_vae_create(const MiVaeDesc* d, float* params, float* grads, float* adam
                     void* weights_t, void* workspace, long long workspace_bytes) {
     VaeEngine* e = (VaeEngine*)calloc(1, sizeof(VaeEngine));
     if (!e) { mi_fail(MI_ERR_STATE, "mi_vae_create: out of host memory"); return nullptr; }
-    if (!d || !init_engine(*e, d)) { free(e); mi_fail(MI_ERR_SHAPE, "mi_vae_create: unsupported geometry"); return nullptr; }
+    if (!init_engine(*e, d, "mi_vae_create")) { free(e); return nullptr; }
     if (d->dtype != MI_F32 && d->dtype != MI_BF16 && d->dtype != MI_BF16X3) { free(e); mi_fail(MI_ERR_ARG, "mi_vae_create: dtype must be 0 (f32), 1 (bf16) or 2 (split storage, bf16x3)"); return nullptr; }
     if (d->dtype != MI_F32 && !bf16_shadow) { free(e); mi_fail(MI_ERR_ARG, "mi_vae_create: bf16 / split mode needs the shadow weight buffer (2 / 4 bytes per parameter)"); return nullptr; }
     if (d->inference_only && grads) { free(e); mi_fail(MI_ERR_ARG, "mi_vae_create: an inference_only engine takes no gradient buffer (its workspace has no gradient scratch)"); return nullptr; }
@@ -479,9 +502,17 @@ int mi_vae_sync_shadow(void* h, void* stream) {
 
 // device pointers into the workspace (valid after the corresponding call; fp32): 0 losses[2] (recon, kl), 1 mean [B,Z],
 // 2 logvar [B,Z], 3 kl_row [B];  4 logits [B,P] (T), 5 z [B,Z] (T)
+// (tests) 6..16 the fragment-ordered weight copies; the stored tensors of the last pass in the engine's storage type T, NHWC with the CURRENT batch: 20 + i act[i] (i = 1..4),
+// 30 + i dec[i] (i = 0..4), 40 + i gact[i] (i = 1..4), 50 + i gdec[i] (i = 0..4), 60 dheads [B,2Z].  NULL where the engine's workspace has no such region.
 void* mi_vae_buffer(void* h, int which) {
     VaeEngine* e = (VaeEngine*)h;
     if (!e) return nullptr;
+    auto region = [&](long long off) -> void* { return off < 0 ? nullptr : e->at(off); };
+    if (which >= 21 && which <= 24) return region(e->W.act[which - 20]);
+    if (which >= 30 && which <= 34) return region(e->W.dec[which - 30]);
+    if (which >= 41 && which <= 44) return region(e->W.gact[which - 40]);
+    if (which >= 50 && which <= 54) return region(e->W.gdec[which - 50]);
+    if (which == 60) return region(e->W.dheads);
     switch (which) {
         case 0: return e->at(e->W.out2);
         case 1: return e->at(e->W.mean);
@@ -642,6 +673,8 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
     };
     if (defer) mi_tapwgrad_defer(1);
     auto join = [&]() {
+        // (with a split-storage fold pending mi_tapwgrad_flush issues the part's recorded small reduces itself, in front of the folds that read their sums: everything in that
+        // list was recorded on sw and is complete there in stream order, so running it early is the same sums; the flush below then finds the list empty)
         if (defer) mi_tapwgrad_flush(sw);
         if (side_defer) { mi_small_reduce_flush(sw); mi_small_reduce_defer(0); side_defer = false; }
         if (fork && e->dp_open_join) {                      // (one-call data-parallel step, parts 1 and 3) everything of this part that ran on the caller's stream is complete on the other one
@@ -661,6 +694,8 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
     // Measured, three interleaved pairs on one box: 0.966 -> 0.943 ms per step.  MI355_SLAB_BF16=0: fp32 slabs.
     struct SlabGuard { int prev; bool on; ~SlabGuard() { if (on) mi_tapwgrad_slab_bf16(prev); } } slab_guard{-1, false};
     if (knob(K_SLAB_BF16) && d.dtype == MI_BF16) { slab_guard.prev = mi_tapwgrad_slab_bf16(1); slab_guard.on = true; }
+    // a small layer at a small batch has ONE position split: no slabs, and the 8 partial sums of each bias element met in fp32 atomics -- ordered rows for this pass (conv_ops.hip)
+    struct BiasRowsGuard { int prev; ~BiasRowsGuard() { mi_tapwgrad_bias_rows(prev); } } bias_rows_guard{mi_tapwgrad_bias_rows(1)};
     // Full two-stream backward (round 3): the latent-side filter / bias gradients (dense1, heads: ~60 us of the filter-gradient stream, which is the longer one) are
     // issued on the caller's stream at the very END of the pass, where that stream would otherwise wait ~100 us for the other one; their operands (gdec0, z, dheads,
     // act4) stay intact until then and no event is needed for them.  The parts and the one-stream pass issue them in place on the filter-gradient stream.
@@ -882,7 +917,8 @@ int mi_vae_train_step(void* h, void* stream, const void* src, const void* tgt, i
 // descriptor (no GPU); the host mirror (mi355/vae_device.py grad_buckets) and mi_vae_train_step_dp both follow it.
 int mi_vae_dp_buckets(const MiVaeDesc* d, long long* out9) {
     VaeEngine e;
-    if (!d || !out9 || !init_engine(e, d)) return mi_fail(MI_ERR_SHAPE, "mi_vae_dp_buckets: unsupported geometry or missing output");
+    if (!out9) return mi_fail(MI_ERR_ARG, "mi_vae_dp_buckets: missing output");
+    if (!init_engine(e, d, "mi_vae_dp_buckets")) return MI_ERR_SHAPE;
     const long long dec = e.L.off[10], c4 = e.L.off[6];
     const long long b[9] = {1, dec, e.L.total, 3, c4, dec, 4, 0, c4};
     for (int i = 0; i < 9; ++i) out9[i] = b[i];

@@ -23,6 +23,22 @@ def encoded_shape(source_shape):
     return (h, w, ENC_FILTERS[-1])
 
 
+def conv_map_shape(source_shape, i):
+    """(h, w, channels) of conv i's output, i = 1..4."""
+    h, w = int(source_shape[0]), int(source_shape[1])
+    for _ in range(i):
+        h, w = conv_out(h), conv_out(w)
+    return (h, w, ENC_FILTERS[i - 1])
+
+
+def deconv_map_shape(source_shape, target_shape, i):
+    """(h, w, channels) of dense1's reshaped output (i = 0) / of deconv i's output (i = 1..4)."""
+    h, w, c = encoded_shape(source_shape)
+    for k in DEC_KERNELS[:i]:
+        h, w = (h - 1) * 2 + k, (w - 1) * 2 + k
+    return (h, w, ((c,) + DEC_FILTERS + (int(target_shape[-1]),))[i])
+
+
 def vae_variables(z_dim, source_shape, target_shape):
     """name -> shape for the 22 trainable ConvVAE variables, TF creation order."""
     v = OrderedDict()

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import lib as milib
-from .init import vae_variables
+from .init import conv_map_shape, deconv_map_shape, vae_variables
 
 LOSS_KINDS = {"bce": 0, "bce_v2": 1, "mse": 2}
 PRECISIONS = {"fp32": milib.MI_F32, "f32": milib.MI_F32, "bf16": milib.MI_BF16, "bf16x3": milib.MI_BF16X3}
@@ -119,6 +119,30 @@ class VaeDevice:
         esz = torch.empty(0, dtype=dtype).element_size()
         off = addr - base
         return self.workspace[off:off + n * esz].view(dtype)
+
+    # the tensors the last pass stored, for tests (mi_vae_buffer 20..60): name -> (first `which`, indices)
+    _STORED = {"act": (20, (1, 2, 3, 4)), "dec": (30, (0, 1, 2, 3, 4)), "gact": (40, (1, 2, 3, 4)), "gdec": (50, (0, 1, 2, 3, 4)), "dheads": (60, (0,))}
+
+    def stored_shape(self, name, i=0):
+        """Per-frame NHWC shape of a stored tensor: act / gact i = output of conv i, dec / gdec i = dense1's output (0) / output of deconv i, dheads = [2 z]."""
+        base, idx = self._STORED[name]
+        if i not in idx:
+            raise ValueError("%s[%d]: no such stored tensor" % (name, i))
+        if name == "dheads":
+            return (2 * self.z_dim,)
+        if name in ("act", "gact"):
+            return conv_map_shape(self.source_shape, i)
+        return deconv_map_shape(self.source_shape, self.target_shape, i)
+
+    def stored(self, name, i, B):
+        """Zero-copy view [B, ...] of a tensor the last pass stored, in the engine's storage type (float32, bfloat16, or int32 words of split storage: hi | lo halves).
+        None where the workspace has no such region.  A fused route leaves the regions it skips unwritten.  For tests: nothing on a step's path reads this."""
+        base, _ = self._STORED[name]
+        shape = (int(B),) + self.stored_shape(name, i)
+        if self.L.mi_vae_buffer(self.handle, base + i) is None:
+            return None
+        dt = {milib.MI_F32: torch.float32, milib.MI_BF16: torch.bfloat16, milib.MI_BF16X3: torch.int32}[self.dtype]
+        return self._view(base + i, int(np.prod(shape)), dt).view(shape)
 
     def close(self):
         if self.handle is not None:

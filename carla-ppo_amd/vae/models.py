@@ -398,7 +398,12 @@ class VAE():
 
 class ConvVAE(VAE):
     """Convolutional VAE (reference vae/models.py:233-268): 4x conv k4 s2 relu 32/64/128/256, dense heads,
-    dense 64->6144, deconv k4/k4/k5/k4 s2 128/64/32/C_t.  Adjusted, like the reference, to 160x80 frames."""
+    dense 64->6144, deconv k4/k4/k5/k4 s2 128/64/32/C_t.  Adjusted, like the reference, to 160x80 frames.
+
+    Other cameras: the decoder returns the source's height and width exactly when each side is 16 e + 32 (e = that side of conv4's output, >= 1): 48, 64, 80, 96,
+    112, 128, 144, 160, 176, 192, ...; any other side fails the assertion below (vae/models.py:265).  Source and target share height and width and may differ in depth.
+    z_dim is a positive multiple of 8 in bf16 storage and of 4 in fp32 / bf16x3: the latent layers read their rows in 16-byte vectors (the engine refuses other widths,
+    csrc/vae_engine.hip z_dim_multiple; checked here so that nothing is allocated first)."""
 
     def __init__(self, source_shape, target_shape=None, **kwargs):
         target_shape = source_shape if target_shape is None else target_shape
@@ -414,6 +419,10 @@ class ConvVAE(VAE):
         assert (h, w) == tgt[:2], f"{(h, w, tgt[2])} != {tgt}"       # vae/models.py:265
         kwargs.pop("build_encoder_fn", None)
         kwargs.pop("build_decoder_fn", None)
+        precision = kwargs.get("precision") or os.environ.get("MI355_PRECISION", "fp32")       # (as VAE.__init__ resolves it)
+        z_dim, need = int(kwargs.get("z_dim", 512)), 8 if precision == "bf16" else 4
+        if z_dim < need or z_dim % need != 0:                                                    # before the base class creates the model's directories
+            raise ValueError("ConvVAE: unsupported z_dim %d: precision %r needs z_dim to be a positive multiple of %d" % (z_dim, precision, need))
         super().__init__(source_shape, target_shape, None, None, **kwargs)
 
 

@@ -116,6 +116,10 @@ int mi_device_probe(void* stream, void* scratch, long long scratch_bytes, int mi
  * gradient of round 5 (csrc/dwgs_tile.hpp; MI355_DWGS) on / off; key 23 (debug): ablation mask of the fused encoder-head forward kernel's timing instantiation
  * (tools/enc12_ablate.py; any bit set = wrong results; 0 = the product kernel).  Returns the previous value. */
 int mi_set_tuning(int key, int value);
+/* Per calling thread, default 0 (returns the previous setting).  != 0: a raw-staged filter gradient (mi_conv2d_nhwc_wgrad_ws / mi_deconv2d_nhwc_wgrad_ws on bf16 tensors) whose
+ * positions fit ONE split sums the partial rows of its bias gradient through the first bytes of the caller's scratch in a fixed order instead of fp32 atomics: two runs are
+ * bitwise equal.  The ConvVAE engine's backward pass switches it on for itself; 0 leaves a scratch that holds no slabs untouched. */
+int mi_tapwgrad_bias_rows(int on);
 /* debug only: s_memtime stamps of the tapconv kernel (32 int64 per wave per block) into a caller-provided device buffer; NULL = off */
 int mi_debug_set_trace(void* dev_ptr, int capacity_entries);
 
@@ -322,6 +326,11 @@ long long mi_vae_workspace_bytes(const MiVaeDesc* d);
 void* mi_vae_create(const MiVaeDesc* d, float* params, float* grads, float* adam_m, float* adam_v, void* bf16_shadow, void* weights_t, void* workspace, long long workspace_bytes);
 void mi_vae_destroy(void* h);
 int mi_vae_sync_shadow(void* h, void* stream);
+/* device pointers into the workspace: 0 losses[2] (recon, kl), 1 mean [B,Z], 2 logvar [B,Z], 3 kl_row [B] (fp32); 4 logits [B,P], 5 z [B,Z] (storage type T).
+ * For tests: 6..16 the fragment-ordered weight copies (NULL unless the activation-resident kernels take the model); the tensors the last pass stored, type T, NHWC at
+ * the CURRENT batch: 20 + i = output of conv i (i = 1..4), 30 + i = dense1's output (i = 0) / output of deconv i (i = 1..4), 40 + i and 50 + i = the gradients wrt those
+ * (pre-activation), 60 = dheads [B,2Z].  NULL where the workspace has no such region (an inference-only engine has no gradients, and no conv1 output behind the fused
+ * encoder head) and for any other `which`.  A fused route leaves a region it skips unwritten. */
 void* mi_vae_buffer(void* h, int which);
 /* Debug mode of the engine workspace (sanitizer row): with MI355_DEBUG_GUARDS=1 in the environment of BOTH mi_vae_workspace_bytes and mi_vae_create every
  * workspace region is followed by 256 guard bytes of a known pattern (armed by mi_vae_create).  *n_regions = guarded regions (0: mode off), *n_bad = guards that no longer

@@ -32,6 +32,15 @@ DEC_KERNELS = (4, 4, 5, 4)                # vae/models.py:261-264
 ENCODED_SHAPE = (3, 8, 256)               # conv4 output for an 80x160 input (vae/models.py:254)
 
 
+def encoded_shape(source_shape=(80, 160, 3)):
+    """conv4's output shape (H, W, 256) for a source shape: four k = 4, stride 2, VALID convolutions (vae/models.py:250-254).
+    The decoder returns the source's height and width exactly when each side is 16 e + 32 (e = that side here): 48, 64, 80, ..."""
+    h, w = int(source_shape[0]), int(source_shape[1])
+    for _ in ENC_FILTERS:
+        h, w = (h - 4) // 2 + 1, (w - 4) // 2 + 1
+    return (h, w, ENC_FILTERS[-1])
+
+
 def vae_variable_specs(z_dim=64, source_shape=(80, 160, 3), target_shape=None):
     """Trainable variables in TF creation order with TF shapes (pinned by tests/golden/ref_variables.json)."""
     target_shape = source_shape if target_shape is None else target_shape
@@ -41,14 +50,15 @@ def vae_variable_specs(z_dim=64, source_shape=(80, 160, 3), target_shape=None):
         specs["vae/encoder/conv%d/kernel" % (i + 1)] = (4, 4, cin, f)
         specs["vae/encoder/conv%d/bias" % (i + 1)] = (f,)
         cin = f
-    flat = int(np.prod(ENCODED_SHAPE))
+    enc = encoded_shape(source_shape)
+    flat = int(np.prod(enc))
     specs["vae/mean/kernel"] = (flat, z_dim)
     specs["vae/mean/bias"] = (z_dim,)
     specs["vae/logstd_sqare/kernel"] = (flat, z_dim)        # (sic) vae/models.py:98
     specs["vae/logstd_sqare/bias"] = (z_dim,)
     specs["vae/decoder/dense1/kernel"] = (z_dim, flat)
     specs["vae/decoder/dense1/bias"] = (flat,)
-    cin = ENCODED_SHAPE[-1]
+    cin = enc[-1]
     for i, (f, k) in enumerate(zip(DEC_FILTERS + (int(target_shape[-1]),), DEC_KERNELS)):
         specs["vae/decoder/deconv%d/kernel" % (i + 1)] = (k, k, f, cin)   # [kh,kw,out,in]
         specs["vae/decoder/deconv%d/bias" % (i + 1)] = (f,)
@@ -116,7 +126,7 @@ def _qw(w, storage):
 
 
 def vae_forward(params, src, eps=None, sample=True, dtype=torch.float32, storage="fp32", z_override=None,
-                keep=False):
+                keep=False, encoded=ENCODED_SHAPE):
     """Encoder -> heads -> z -> decoder (vae/models.py:97-113,249-266).
 
     params: dict name -> tensor in TF layout.  src: [B,H,W,C] in [0,1].  eps: [B,z] injected N(0,1) noise
@@ -124,6 +134,7 @@ def vae_forward(params, src, eps=None, sample=True, dtype=torch.float32, storage
     z_override feeds z in place of `self.sample` (generate_from_latent, vae/models.py:188-191).
     storage="bf16" rounds weights and every stored activation (and its gradient) to bf16, emulating the
     HIP path's bf16 HBM layout with fp32 accumulation.
+    encoded: conv4's output shape, encoded_shape(source_shape); only the decoder's reshape reads it.
     """
     out = {}
     if z_override is None:
@@ -146,7 +157,7 @@ def vae_forward(params, src, eps=None, sample=True, dtype=torch.float32, storage
         z = _t(z_override, dtype)
     out["z"] = z
     h = _q(z, storage) @ _qw(params["vae/decoder/dense1/kernel"], storage) + params["vae/decoder/dense1/bias"]
-    x = _q(h, storage).reshape(-1, *ENCODED_SHAPE).permute(0, 3, 1, 2)
+    x = _q(h, storage).reshape(-1, *encoded).permute(0, 3, 1, 2)
     for i in range(4):
         w = _qw(params["vae/decoder/deconv%d/kernel" % (i + 1)], storage).permute(3, 2, 0, 1)     # [kh,kw,out,in] -> [in,out,kh,kw]
         x = F.conv_transpose2d(x, w, params["vae/decoder/deconv%d/bias" % (i + 1)], stride=2)
@@ -246,10 +257,10 @@ def vae_losses(fw, tgt, beta=1.0, kl_tolerance=0.0, loss_fn="bce", z_dim=None, d
 
 
 def vae_loss_and_grads(params_np, src, tgt, eps, beta=1.0, kl_tolerance=0.0, loss_fn="bce",
-                       dtype=torch.float32, storage="fp32"):
+                       dtype=torch.float32, storage="fp32", encoded=ENCODED_SHAPE):
     """One forward+backward. Returns (recon, kl, loss) floats and grads dict (TF layouts, numpy)."""
     params = OrderedDict((k, _t(v, dtype).clone().requires_grad_(True)) for k, v in params_np.items())
-    fw = vae_forward(params, src, eps, sample=True, dtype=dtype, storage=storage)
+    fw = vae_forward(params, src, eps, sample=True, dtype=dtype, storage=storage, encoded=encoded)
     recon, kl, loss = vae_losses(fw, tgt, beta, kl_tolerance, loss_fn, dtype=dtype)
     loss.backward()
     grads = OrderedDict((k, (p.grad if p.grad is not None else torch.zeros_like(p)).detach().numpy()) for k, p in params.items())
@@ -306,6 +317,7 @@ class OracleVAE:
         self.z_dim, self.beta, self.kl_tolerance = int(z_dim), float(beta), float(kl_tolerance)
         self.learning_rate, self.lr_decay, self.loss_fn, self.training = learning_rate, lr_decay, loss_fn, training
         self.dtype, self.storage = dtype, storage
+        self.encoded_shape = encoded_shape(self.source_shape)
         src = init_vae_params(seed, z_dim, self.source_shape, self.target_shape) if params is None else params
         self.params = OrderedDict((k, np.array(v, np.float32)) for k, v in src.items())
         self.adam = AdamTF(OrderedDict((k, v.shape) for k, v in self.params.items()))
@@ -316,14 +328,14 @@ class OracleVAE:
     def train_step(self, src, tgt, eps):
         verify_range(src), verify_range(tgt)
         (recon, kl, loss), grads, _ = vae_loss_and_grads(self.params, src, tgt, eps, self.beta, self.kl_tolerance,
-                                                         self.loss_fn, self.dtype, self.storage)
+                                                         self.loss_fn, self.dtype, self.storage, self.encoded_shape)
         self.adam.step(self.params, grads, self.learning_rate)      # constant lr (vae/models.py:141)
         return recon, kl
 
     def eval_step(self, src, tgt, eps):
         with torch.no_grad():
             p = {k: _t(v, self.dtype) for k, v in self.params.items()}
-            fw = vae_forward(p, src, eps, sample=self.training, dtype=self.dtype, storage=self.storage)
+            fw = vae_forward(p, src, eps, sample=self.training, dtype=self.dtype, storage=self.storage, encoded=self.encoded_shape)
             recon, kl, _ = vae_losses(fw, tgt, self.beta, self.kl_tolerance, self.loss_fn, dtype=self.dtype)
         return float(recon), float(kl)
 
@@ -354,7 +366,7 @@ class OracleVAE:
     def _fw(self, **kw):
         with torch.no_grad():
             p = {k: _t(v, self.dtype) for k, v in self.params.items()}
-            return vae_forward(p, dtype=self.dtype, storage=self.storage, **kw)
+            return vae_forward(p, dtype=self.dtype, storage=self.storage, encoded=self.encoded_shape, **kw)
 
     def encode(self, source_states):
         src = np.asarray(source_states, np.float32)
