@@ -116,7 +116,10 @@ __device__ __forceinline__ void store_tile(const P& p, const f32x16 (&acc)[TM][T
         // v_permlane32_swap and write 16 bytes per lane.  Two phases: every address, bias vector and ReluGrad-mask vector is requested
         // first, then the results are converted and stored back to back -- a load between two stores makes the wave wait for the
         // acknowledgement of the earlier stores (vmcnt counts both), which cost more than the whole main loop of the small layers.
-        if ((p.N & 15) == 0 && !p.out_f32) {
+        // Whole 32-column subtiles only: both 16-channel groups (mq = 0, 1) of a subtile are stored without a column test, so with N = 16 (mod 32) the second
+        // group of the last subtile landed in the next row's first 16 channels (and, behind the last row, 32 bytes past the tensor), and its bias vector was read
+        // past the bias.  Such widths take the per-group path below (the MlpVAE engine at a layer width of 16 or 48; no layer of the two models' own sizes).
+        if ((p.N & 31) == 0 && !p.out_f32) {
             long long off[TM][TN][2]; bool ok[TM][TN];
             PackN<uint32_t, 4> mk[TM][TN][2];
             f32x4 bs[TN][2][2];

@@ -9,6 +9,7 @@
 //   * the bias gradients are a ones row of the filter gradients, and the filter gradients STORE their result (mi_gemm_wgrad_bias_set: no atomics on 79 MB per big
 //     layer, no zeroing of the 158 MB gradient buffer by the optimiser);
 //   * Adam writes both weight layouts the MFMA kernels read (mi_adam_tf_layouts: no transpose pass over the master weights behind every step).
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "common.hpp"
@@ -19,6 +20,7 @@
 namespace {
 
 constexpr int ML_MAX = MI_MLP_MAX_HIDDEN;                 // hidden layers per side
+constexpr int MAX_REGIONS = 4 * ML_MAX + 14;              // regions init_engine's reg() can carve: x, h[], heads, mean, logvar, klrow, z, d[], partial, out2, gd[], dz, dheads, gh[], slab, scratch
 constexpr long long SPLIT_K = 4096;                       // reductions at least this long are split over the chip (38400 -> 30 slabs) and finished by mi_splitk_finish
 
 struct Dense { long long wo, bo; int K, N; };             // kernel [K, N] at wo, bias [N] at bo (floats into the flat buffers)
@@ -37,6 +39,9 @@ struct MlpEngine {
     int last_B;
     const void* last_x;
     hipStream_t side; hipEvent_t ev_fork, ev_chain, ev_done; int side_ok;      // second stream of a full backward pass (created on first use)
+    // debug (MI355_DEBUG_GUARDS=1 at mi_mlpvae_workspace_bytes AND mi_mlpvae_create time, as in vae_engine.hip): 256 bytes of a known pattern behind every region;
+    // mi_mlpvae_debug_check_guards finds the region a kernel wrote past
+    int n_guards; long long guard_off[MAX_REGIONS];
     char* at(long long o) const { return ws + o; }
     const void* w(const Dense& l) const { return d.dtype == MI_BF16 ? (const void*)((const unsigned short*)shadow + l.wo) : (const void*)(params + l.wo); }
     const void* w_t(const Dense& l) const { return d.dtype == MI_BF16 ? (const void*)((const unsigned short*)wt + l.wo) : (const void*)((const float*)wt + l.wo); }
@@ -44,6 +49,7 @@ struct MlpEngine {
 };
 
 inline long long al256(long long n) { return (n + 255) / 256 * 256; }
+constexpr uint32_t GUARD_WORD = 0xC0DEFA11u;
 
 int splitk_slabs(long long K) {
     if (K < SPLIT_K || K % 128 != 0) return 1;
@@ -78,7 +84,16 @@ bool init_engine(MlpEngine& e, const MiMlpVaeDesc* dp, int max_batch_override = 
     const long long B = max_batch_override > 0 ? max_batch_override : d.max_batch;
     if (B < 1) return false;
     long long w = 0;
-    auto reg = [&](long long bytes) { const long long at = w; w += al256(bytes); return at; };
+    const bool guards = mi::knob_env_now(mi::K_DEBUG_GUARDS) != 0;
+    bool guard_overflow = false;
+    auto reg = [&](long long bytes) {
+        const long long at = w; w += al256(bytes);
+        if (guards) {
+            if (e.n_guards < MAX_REGIONS) { e.guard_off[e.n_guards++] = w; w += 256; }
+            else guard_overflow = true;                   // (a region added without raising MAX_REGIONS: the descriptor is refused below, never carved unguarded)
+        }
+        return at;
+    };
     e.o_x = reg(B * d.source_size * e.esz);
     for (int i = 0; i < e.ne; ++i) e.o_h[i] = reg(B * e.enc[i].N * e.esz);
     e.o_heads = reg(B * 2 * d.z_dim * 4);
@@ -106,7 +121,7 @@ bool init_engine(MlpEngine& e, const MiMlpVaeDesc* dp, int max_batch_override = 
     e.o_slab = reg(slab ? slab : 16);
     e.o_scratch = reg(scr ? scr : 16);
     e.ws_total = w;
-    return true;
+    return !guard_overflow;
 }
 
 #define CK(x) do { const int rc__ = (x); if (rc__ != MI_OK) return rc__; } while (0)
@@ -223,7 +238,39 @@ void* mi_mlpvae_create(const MiMlpVaeDesc* d, float* params, float* grads, float
     }
     if (workspace_bytes < e->ws_total || (((uintptr_t)workspace) & 255)) { delete e; mi_fail(MI_ERR_ARG, "mi_mlpvae_create: workspace too small or not 256-byte aligned"); return nullptr; }
     e->params = params; e->grads = grads; e->m = adam_m; e->v = adam_v; e->shadow = shadow; e->wt = weights_t; e->ws = (char*)workspace; e->ws_bytes = workspace_bytes;
+    if (e->n_guards > 0) {                                // debug mode: arm the guard words (synchronous copies; never on the production path)
+        uint32_t pat[64];
+        for (int i = 0; i < 64; ++i) pat[i] = GUARD_WORD ^ (uint32_t)i;
+        for (int k = 0; k < e->n_guards; ++k)
+            if (hipMemcpy(e->ws + e->guard_off[k], pat, 256, hipMemcpyHostToDevice) != hipSuccess) { delete e; mi_fail(MI_ERR_STATE, "mi_mlpvae_create: arming the debug guards failed"); return nullptr; }
+    }
     return e;
+}
+
+// Debug (MI355_DEBUG_GUARDS=1): *n_regions = guarded workspace regions (0: the mode is off), *n_bad = guards whose 256 bytes no longer hold the pattern, i.e. regions
+// some kernel wrote past; mi_last_error() names the first one.  Synchronises the device.  guard_index >= 0: also returns that guard's byte offset in *guard_offset
+// (tests corrupt one on purpose).  Reads the engine's own workspace only.
+int mi_mlpvae_debug_check_guards(void* h, int* n_regions, int* n_bad, int guard_index, long long* guard_offset) {
+    MlpEngine* e = (MlpEngine*)h;
+    if (!e || !n_regions || !n_bad) return mi_fail(MI_ERR_ARG, "mi_mlpvae_debug_check_guards: missing arguments");
+    *n_regions = e->n_guards; *n_bad = 0;
+    if (guard_offset) *guard_offset = (guard_index >= 0 && guard_index < e->n_guards) ? e->guard_off[guard_index] : -1;
+    if (e->n_guards == 0) return MI_OK;
+    if (hipDeviceSynchronize() != hipSuccess) return mi_fail(MI_ERR_STATE, "mi_mlpvae_debug_check_guards: device error before the check");
+    int first = -1;
+    for (int k = 0; k < e->n_guards; ++k) {
+        uint32_t got[64];
+        if (hipMemcpy(got, e->ws + e->guard_off[k], 256, hipMemcpyDeviceToHost) != hipSuccess) return mi_fail(MI_ERR_STATE, "mi_mlpvae_debug_check_guards: copy failed");
+        bool bad = false;
+        for (int i = 0; i < 64; ++i) bad |= got[i] != (GUARD_WORD ^ (uint32_t)i);
+        if (bad) { ++*n_bad; if (first < 0) first = k; }
+    }
+    if (first >= 0) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "workspace guard %d (byte offset %lld) overwritten: a kernel wrote past the region in front of it", first, e->guard_off[first]);
+        mi_fail(MI_OK, msg);
+    }
+    return MI_OK;
 }
 
 void mi_mlpvae_destroy(void* h) {
@@ -243,7 +290,11 @@ int mi_mlpvae_sync_shadow(void* h, void* stream) {
     return mi_transpose_weights(stream, e->d.dtype, e->params, e->wt, off, K, N, n);
 }
 
-// device pointers into the workspace (fp32 unless noted): 0 losses[2] (recon, kl), 1 mean [B,Z], 2 logvar [B,Z], 3 kl_row [B], 4 logits [B,P] (storage type), 5 z [B,Z] (storage type)
+// device pointers into the workspace (fp32 unless noted): 0 losses[2] (recon, kl), 1 mean [B,Z], 2 logvar [B,Z], 3 kl_row [B], 4 logits [B,P] (storage type), 5 z [B,Z] (storage type).
+// For tests, the other tensors the last pass stored (storage type unless noted, rows at the CURRENT batch): 10 the staged input x [B,S] (the fp32 engine with idx == NULL
+// and a float table reads the caller's table instead and leaves it unwritten), 11 the raw heads [B,2Z] fp32 (no bias), 12 the split-K slab region (fp32 [slabs][B][N] of the last split product, from its start); 20 + i = h[i], the output of encoder layer i;
+// 30 + i = d[i], the output of decoder layer i (the last one: the logits); 40 + i = gh[i] and 50 + i = gd[i], the gradients wrt those (pre-activation); 60 = dheads [B,2Z],
+// 61 = dz [B,Z] fp32.  NULL where the workspace has no such region (an inference-only engine has no gradients) and for any other `which`.
 void* mi_mlpvae_buffer(void* h, int which) {
     MlpEngine* e = (MlpEngine*)h;
     if (!e) return nullptr;
@@ -254,6 +305,19 @@ void* mi_mlpvae_buffer(void* h, int which) {
         case 3: return e->at(e->o_klrow);
         case 4: return e->at(e->o_d[e->nd - 1]);
         case 5: return e->at(e->o_z);
+        case 10: return e->at(e->o_x);
+        case 11: return e->at(e->o_heads);
+        case 12: return e->at(e->o_slab);
+        case 60: return e->d.with_optimizer ? e->at(e->o_dheads) : nullptr;
+        case 61: return e->d.with_optimizer ? e->at(e->o_dz) : nullptr;
+        default: break;
+    }
+    const int i = which % 10;
+    switch (which / 10) {
+        case 2: return i < e->ne ? e->at(e->o_h[i]) : nullptr;
+        case 3: return i < e->nd ? e->at(e->o_d[i]) : nullptr;
+        case 4: return e->d.with_optimizer && i < e->ne ? e->at(e->o_gh[i]) : nullptr;
+        case 5: return e->d.with_optimizer && i < e->nd ? e->at(e->o_gd[i]) : nullptr;
         default: return nullptr;
     }
 }

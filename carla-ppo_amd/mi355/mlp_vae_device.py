@@ -127,6 +127,36 @@ class MlpVaeDevice:
     def logvar(self):
         return self._view(2, self.max_batch * self.z_dim).view(self.max_batch, self.z_dim)
 
+    # the tensors the last pass stored, for tests (mi_mlpvae_buffer 10 .. 61): name -> (first `which`, fp32 whatever the storage type)
+    _STORED = {"x": (10, False), "heads": (11, True), "h": (20, False), "d": (30, False), "gh": (40, False), "gd": (50, False), "dheads": (60, False), "dz": (61, True)}
+
+    def stored_width(self, name, i=0):
+        """Row length of a stored tensor: x = the staged input; heads = the raw [mean | logstd_sqare] product (no bias); h / gh i = output of encoder layer i and its
+        gradient; d / gd i = output of decoder layer i (the last one: the logits) and its gradient; dheads [2 z]; dz [z]."""
+        if name not in self._STORED:
+            raise ValueError("%s: no such stored tensor" % name)
+        widths = {"x": (self.S,), "heads": (2 * self.z_dim,), "h": self.enc_sizes, "gh": self.enc_sizes, "d": self.dec_sizes + (self.P,), "gd": self.dec_sizes + (self.P,),
+                  "dheads": (2 * self.z_dim,), "dz": (self.z_dim,)}[name]
+        if not 0 <= i < len(widths):
+            raise ValueError("%s[%d]: no such stored tensor" % (name, i))
+        return widths[i]
+
+    def stored(self, name, i, B):
+        """Zero-copy view [B, width] of a tensor the last pass stored: float32 for heads and dz, the engine's storage type otherwise.  None where the workspace has no
+        such region (an inference-only engine has no gradients).  For tests: nothing on a step's path reads this."""
+        base, f32 = self._STORED[name]
+        n = self.stored_width(name, i)
+        if self.L.mi_mlpvae_buffer(self.handle, base + i) is None:
+            return None
+        return self._view(base + i, int(B) * n, torch.float32 if f32 else self.T).view(int(B), n)
+
+    def check_guards(self, guard_index=-1):
+        """Debug mode (MI355_DEBUG_GUARDS=1 when the engine was created): (guarded regions, overwritten guards, byte offset of guard `guard_index` or -1).
+        0 regions = the mode is off.  Synchronises the device."""
+        n, bad, off = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_longlong(-1)
+        self.L.mi_mlpvae_debug_check_guards(self.handle, ctypes.addressof(n), ctypes.addressof(bad), int(guard_index), ctypes.addressof(off))
+        return n.value, bad.value, off.value
+
     def close(self):
         if self.handle is not None:
             self.L.mi_mlpvae_destroy(self.handle)

@@ -370,7 +370,18 @@ long long mi_mlpvae_workspace_bytes(const MiMlpVaeDesc* d);
 void* mi_mlpvae_create(const MiMlpVaeDesc* d, float* params, float* grads, float* adam_m, float* adam_v, void* shadow, void* weights_t, void* workspace, long long workspace_bytes);
 void mi_mlpvae_destroy(void* h);
 int mi_mlpvae_sync_shadow(void* h, void* stream);
+/* device pointers into the workspace: 0 losses[2] (recon, kl), 1 mean [B,Z], 2 logvar [B,Z], 3 kl_row [B] (fp32); 4 logits [B,P], 5 z [B,Z] (storage type T).
+ * For tests, the other tensors the last pass stored (type T unless noted, rows at the CURRENT batch): 10 the staged input x [B,S] (left unwritten where the fp32 engine
+ * reads the caller's float table directly: idx == NULL), 11 the raw heads [B,2Z] fp32 (no bias), 12 the split-K slab region (fp32 [slabs][B][N] of the last
+ * split product, from the region's start; 16 bytes where no layer splits); 20 + i = output of encoder layer i, 30 + i = output of decoder layer i
+ * (the last one: the logits), 40 + i and 50 + i = the gradients wrt those (pre-activation), 60 = dheads [B,2Z], 61 = dz [B,Z] fp32.  NULL where the workspace has no
+ * such region (an inference-only engine has no gradients) and for any other `which`. */
 void* mi_mlpvae_buffer(void* h, int which);
+/* Debug mode of the workspace, as mi_vae_debug_check_guards: with MI355_DEBUG_GUARDS=1 in the environment of BOTH mi_mlpvae_workspace_bytes and mi_mlpvae_create every
+ * workspace region is followed by 256 guard bytes of a known pattern (armed by mi_mlpvae_create).  *n_regions = guarded regions (0: mode off), *n_bad = guards that no
+ * longer hold the pattern (mi_last_error() names the first); guard_index >= 0: that guard's byte offset in *guard_offset (-1: no such guard).  Synchronises the device;
+ * writes and reads the engine's own workspace only.  With the variable unset the workspace size and every offset are what they were. */
+int mi_mlpvae_debug_check_guards(void* h, int* n_regions, int* n_bad, int guard_index, long long* guard_offset);
 long long mi_mlpvae_decoder_offset(void* h);
 /* round 5: src / tgt are `const void*` + frames_u8 (bit 0: src is a uint8 table of raw camera bytes, bit 1: tgt is; 0: float32 tables as before): the bytes are normalised to
  * float32(k) / float32(255) -- the reference's host preprocessing, vae/train_vae.py:15-18 -- where the minibatch rows are staged / inside the loss kernel */
