@@ -554,36 +554,15 @@ long long roll_env_floats(const MlpEngine& e) {
     return o;
 }
 
-struct MlpRollArgs {
-    const float *obs_mean, *obs_inv_std; float obs_clip; float* nstate;
-    const int* table_rows; long long n_table_rows;
-    float *tab_states, *tab_raw_states, *tab_actions, *tab_values, *tab_final_values;
-    const MiRolloutStack* stk;                               // latent stacking (the _stack entries): the statistics, table_rows and the states tables are read from it
-};
-
-#define MROLL_FAIL(code, text) return mi_fail(code, a.stk ? (value ? "mi_mlp_rollout_value_batch_stack: " text : "mi_mlp_rollout_step_batch_stack: " text) \
-                                                          : (value ? "mi_mlp_rollout_value_batch: " text : "mi_mlp_rollout_step_batch: " text))
-int mlp_rollout(bool value, void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
-                void* scratch, long long scratch_bytes, float* out, const MlpRollArgs& a) {
+// one driver behind the four entries: what is this engine's own -- the frames' alignment, the scratch, the encoder chain -- around the shared check / prepare / finish
+int mlp_rollout(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, void* scratch, long long scratch_bytes, const MiRolloutCall& c) {
     MlpEngine* e = (MlpEngine*)mlp_h;
-    if (!e || !ppo_h) MROLL_FAIL(MI_ERR_STATE, "null handle");
-    if (!frames_u8 || !out || !scratch || (n_meas > 0 && !measurements) || (!greedy && !noise)) MROLL_FAIL(MI_ERR_ARG, "missing buffers");
-    const bool norm = a.obs_mean != nullptr;
-    if (a.table_rows && (a.n_table_rows < 1 || (value ? !a.tab_final_values : (!a.tab_states || !a.tab_actions || !a.tab_values || (norm && !a.tab_raw_states)))))
-        MROLL_FAIL(MI_ERR_ARG, "missing tables");
-    if (a.stk) CK(mi_rollout_stack_check(*a.stk, 0, 0, -1, value ? "mi_mlp_rollout_value_batch_stack" : "mi_mlp_rollout_step_batch_stack"));
-    else if (norm) {
-        if (!a.obs_inv_std || !a.nstate) MROLL_FAIL(MI_ERR_ARG, "missing obs_mean / obs_inv_std / nstate");
-        if (((uintptr_t)a.nstate) & 15) MROLL_FAIL(MI_ERR_ARG, "nstate must be 16-byte aligned");
-        if (!(a.obs_clip > 0.f)) MROLL_FAIL(MI_ERR_ARG, "obs_clip is a positive value (+inf: never clamp)");
-    } else if (a.obs_inv_std || a.nstate || a.tab_raw_states) {
-        MROLL_FAIL(MI_ERR_ARG, "obs_inv_std, nstate and tab_raw_states are NULL where obs_mean is");
-    }
-    if (n < 1 || n > MI_ROLLOUT_MAX_ENVS) MROLL_FAIL(MI_ERR_ARG, "1 <= n <= MI_ROLLOUT_MAX_ENVS");
-    if (((uintptr_t)frames_u8) & 3) MROLL_FAIL(MI_ERR_ARG, "the frames must be 4-byte aligned");
-    if (((uintptr_t)scratch) & 15) MROLL_FAIL(MI_ERR_ARG, "the scratch must be 16-byte aligned");
-    if (scratch_bytes < roll_env_floats(*e) * 4 * n) MROLL_FAIL(MI_ERR_ARG, "scratch too small (mi_mlp_rollout_workspace_bytes)");
-    const int Z = e->d.z_dim;
+    if (!e || !ppo_h) return mi_rollout_fail(MI_ERR_STATE, c.who, "null handle");
+    CK(mi_rollout_call_check(c, frames_u8, scratch));
+    if (((uintptr_t)frames_u8) & 3) return mi_rollout_fail(MI_ERR_ARG, c.who, "the frames must be 4-byte aligned");
+    if (((uintptr_t)scratch) & 15) return mi_rollout_fail(MI_ERR_ARG, c.who, "the scratch must be 16-byte aligned");
+    if (scratch_bytes < roll_env_floats(*e) * 4 * c.n) return mi_rollout_fail(MI_ERR_ARG, c.who, "scratch too small (mi_mlp_rollout_workspace_bytes)");
+    const int Z = e->d.z_dim, n = c.n;
     hipStream_t st = (hipStream_t)stream;
     float* raw[ML_MAX];
     long long o = 0;
@@ -591,40 +570,24 @@ int mlp_rollout(bool value, void* mlp_h, void* ppo_h, void* stream, const unsign
     float* mean_raw = (float*)scratch + o;
     o += (long long)n * Z;
     mi::PpoFusedParams q;
-    CK(mi_ppo_internal_fill(ppo_h, &q, mean_raw, 1));
-    if (a.stk) CK(mi_rollout_stack_check(*a.stk, Z, n_meas, q.din, value ? "mi_mlp_rollout_value_batch_stack" : "mi_mlp_rollout_step_batch_stack"));
-    else if (q.din != Z + n_meas) MROLL_FAIL(MI_ERR_SHAPE, "z_dim + measurements must equal the policy's input size");
-    if (q.A > 8) MROLL_FAIL(MI_ERR_ARG, "at most 8 actions");
-    if (mi_ppo_internal_fill(ppo_h, &q, mean_raw, n) != MI_OK) MROLL_FAIL(MI_ERR_ARG, "n exceeds the PPO engine's max_batch");
-    // every raw-sum buffer of the call starts at zero: the whole scratch as one piece, and the trunks' raw sums [net][n][H] (the value call: the value net's halves alone)
     MiZeroList zl = {};
-    zl.p[0] = (float*)scratch; zl.n[0] = o;
-    zl.p[1] = q.h1; zl.n[1] = 2LL * n * q.H1;
-    zl.p[2] = q.h2; zl.n[2] = 2LL * n * q.H2;
-    if (value) {
-        zl.p[1] = q.h1 + (long long)n * q.H1; zl.n[1] = (long long)n * q.H1;
-        zl.p[2] = q.h2 + (long long)n * q.H2; zl.n[2] = (long long)n * q.H2;
-    }
+    CK(mi_rollout_call_prepare(c, ppo_h, mean_raw, Z, &q, &zl));
+    zl.p[0] = (float*)scratch; zl.n[0] = o;                 // every raw-sum buffer of the encoder starts at zero: the whole scratch as one piece
     CK(mi_rollout_mlp_layer1(st, frames_u8, e->params + e->enc[0].wo, raw[0], e->enc[0].K, e->enc[0].N, n, &zl));
     for (int i = 1; i < e->ne; ++i)                         // a flat layer: x = the raw sums of layer i - 1, + its bias and ReLU on load; K values per row, bias indexed by k
         CK(mi_rollout_conv_batch(st, raw[i - 1], e->b(e->enc[i - 1]), 1, 1, e->enc[i].K, e->params + e->enc[i].wo, e->enc[i].N, e->enc[i].N, 1, 1, raw[i], e->enc[i].K, n));
     // the mean head: the first z_dim columns of the [K, 2 z] heads kernel
     CK(mi_rollout_conv_batch(st, raw[e->ne - 1], e->b(e->enc[e->ne - 1]), 1, 1, e->heads.K, e->params + e->heads.wo, 2 * Z, Z, 1, 1, mean_raw, e->heads.K, n));
-    const float* mean_bias = e->params + e->heads.bo;
-    const MiRolloutObsNorm nrm = {a.obs_mean, a.obs_inv_std, a.obs_clip, a.nstate, value ? nullptr : a.table_rows, value ? 0 : a.n_table_rows, value ? nullptr : a.tab_states};
-    if (value) {
-        // table_rows NULL: the value heads read one int per environment whatever the tables are; with n_table_rows = 0 no row lies inside the table and nothing is
-        // stored, so the list may be any n readable ints: the raw means
-        const MiRolloutValueRec vrec = {a.table_rows ? a.table_rows : (const int*)mean_raw, a.table_rows ? a.n_table_rows : 0, a.tab_final_values};
-        return mi_rollout_value_batch(st, q, mean_raw, mean_bias, Z, measurements, n, out, vrec, norm && !a.stk ? &nrm : nullptr, a.stk);
-    }
-    const MiRolloutRec rec = {a.table_rows, a.n_table_rows, norm ? a.tab_raw_states : a.tab_states, a.tab_actions, a.tab_values};
-    if (a.stk) return mi_rollout_policy_batch_stack(st, q, mean_raw, mean_bias, Z, measurements, noise, greedy, n, out, a.table_rows ? &rec : nullptr, *a.stk);
-    if (norm) return mi_rollout_policy_batch_norm(st, q, mean_raw, mean_bias, Z, measurements, noise, greedy, n, out, a.table_rows ? &rec : nullptr, nrm);
-    if (a.table_rows) return mi_rollout_policy_batch_rec(st, q, mean_raw, mean_bias, Z, measurements, noise, greedy, n, out, rec);
-    return mi_rollout_policy_batch(st, q, mean_raw, mean_bias, Z, measurements, noise, greedy, n, out);
+    return mi_rollout_call_finish(st, c, q, mean_raw, e->params + e->heads.bo, Z);
 }
-#undef MROLL_FAIL
+
+// the fields the four entries share: the statistics (obs_mean NULL: not normalised) and the tables (table_rows NULL: nothing is recorded)
+MiRolloutCall mlp_call(const char* who, bool value_only, const float* measurements, int n_meas, const float* noise, int greedy, int n, float* out, const float* obs_mean,
+                       const float* obs_inv_std, float obs_clip, const int* table_rows, long long n_table_rows) {
+    MiRolloutCall c = mi_rollout_call(who, value_only, measurements, n_meas, noise, greedy, n, out);
+    c.obs_mean = obs_mean; c.obs_inv_std = obs_inv_std; c.obs_clip = obs_clip; c.table_rows = table_rows; c.n_table_rows = n_table_rows;
+    return c;
+}
 
 }  // namespace
 
@@ -640,15 +603,17 @@ long long mi_mlp_rollout_workspace_bytes(const MiMlpVaeDesc* d, int n_envs) {
 int mi_mlp_rollout_step_batch(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
                               void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate,
                               const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values) {
-    const MlpRollArgs a = {obs_mean, obs_inv_std, obs_clip, nstate, table_rows, n_table_rows, tab_states, tab_raw_states, tab_actions, tab_values, nullptr, nullptr};
-    return mlp_rollout(false, mlp_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, a);
+    MiRolloutCall c = mlp_call("mi_mlp_rollout_step_batch", false, measurements, n_meas, noise, greedy, n, out, obs_mean, obs_inv_std, obs_clip, table_rows, n_table_rows);
+    c.nstate = nstate; c.tab_states = tab_states; c.tab_raw_states = tab_raw_states; c.tab_actions = tab_actions; c.tab_values = tab_values;
+    return mlp_rollout(mlp_h, ppo_h, stream, frames_u8, scratch, scratch_bytes, c);
 }
 
 int mi_mlp_rollout_value_batch(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n,
                                void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate,
                                const int* table_rows, long long n_table_rows, float* tab_final_values) {
-    const MlpRollArgs a = {obs_mean, obs_inv_std, obs_clip, nstate, table_rows, n_table_rows, nullptr, nullptr, nullptr, nullptr, tab_final_values, nullptr};
-    return mlp_rollout(true, mlp_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, a);
+    MiRolloutCall c = mlp_call("mi_mlp_rollout_value_batch", true, measurements, n_meas, nullptr, 1, n, out, obs_mean, obs_inv_std, obs_clip, table_rows, n_table_rows);
+    c.nstate = nstate; c.tab_final_values = tab_final_values;
+    return mlp_rollout(mlp_h, ppo_h, stream, frames_u8, scratch, scratch_bytes, c);
 }
 
 // the two entries with latent stacking (mi_rollout_step_batch_stack / mi_rollout_value_batch_stack behind this encoder chain)
@@ -656,18 +621,20 @@ int mi_mlp_rollout_step_batch_stack(void* mlp_h, void* ppo_h, void* stream, cons
                                     void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip,
                                     const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values,
                                     int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, int advance, float* sstate, float* older_out) {
-    const MiRolloutStack stk = {latent_stack, hist, n_lanes, lanes, first, advance, sstate, older_out, obs_mean, obs_inv_std, obs_clip, table_rows, n_table_rows, tab_states, tab_raw_states};
-    const MlpRollArgs a = {obs_mean, obs_inv_std, obs_clip, nullptr, table_rows, n_table_rows, tab_states, tab_raw_states, tab_actions, tab_values, nullptr, &stk};
-    return mlp_rollout(false, mlp_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, a);
+    MiRolloutCall c = mlp_call("mi_mlp_rollout_step_batch_stack", false, measurements, n_meas, noise, greedy, n, out, obs_mean, obs_inv_std, obs_clip, table_rows, n_table_rows);
+    c.tab_states = tab_states; c.tab_raw_states = tab_raw_states; c.tab_actions = tab_actions; c.tab_values = tab_values;
+    mi_rollout_call_stack(c, latent_stack, hist, n_lanes, lanes, first, advance, sstate, older_out);
+    return mlp_rollout(mlp_h, ppo_h, stream, frames_u8, scratch, scratch_bytes, c);
 }
 
 int mi_mlp_rollout_value_batch_stack(void* mlp_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n,
                                      void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip,
                                      const int* table_rows, long long n_table_rows, float* tab_final_values,
                                      int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, float* sstate) {
-    const MiRolloutStack stk = {latent_stack, hist, n_lanes, lanes, first, 0, sstate, nullptr, obs_mean, obs_inv_std, obs_clip, nullptr, 0, nullptr, nullptr};
-    const MlpRollArgs a = {obs_mean, obs_inv_std, obs_clip, nullptr, table_rows, n_table_rows, nullptr, nullptr, nullptr, nullptr, tab_final_values, &stk};
-    return mlp_rollout(true, mlp_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, a);
+    MiRolloutCall c = mlp_call("mi_mlp_rollout_value_batch_stack", true, measurements, n_meas, nullptr, 1, n, out, obs_mean, obs_inv_std, obs_clip, table_rows, n_table_rows);
+    c.tab_final_values = tab_final_values;
+    mi_rollout_call_stack(c, latent_stack, hist, n_lanes, lanes, first, 0, sstate, nullptr);
+    return mlp_rollout(mlp_h, ppo_h, stream, frames_u8, scratch, scratch_bytes, c);
 }
 
 }  // extern "C"

@@ -64,34 +64,43 @@ int mi_rollout_policy(hipStream_t st, const mi::PpoFusedParams& q, const float* 
 // batched forms (n environments per launch; mi_rollout_step_batch)
 int mi_rollout_conv1_batch(hipStream_t st, const unsigned char* frames, const float* w, const float* bias, float* out, int IH, int IW, int Cs, int KH, int KW, int N, int n, const MiZeroList* zero);
 int mi_rollout_conv_batch(hipStream_t st, const float* x, const float* x_bias, int IH, int IW, int C, const float* w, int ldw, int N, int KH, int KW, float* out_raw, int flat_k, int n);
-int mi_rollout_policy_batch(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n, float* out);
-// the recording form (mi_rollout_step_batch_rec): call row e is also stored as row table_rows[e] of the horizon-batch tables (rows outside [0, n_table_rows) are skipped)
-struct MiRolloutRec { const int* table_rows; long long n_table_rows; float* states; float* actions; float* values; };
-int mi_rollout_policy_batch_rec(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n, float* out,
-                                const MiRolloutRec& rec);
-// the value-only form (mi_rollout_value_batch_rec): the value trunk and the value head alone; out [n], and the value of call row e is also stored as final_values[table_rows[e]]
-struct MiRolloutValueRec { const int* table_rows; long long n_table_rows; float* final_values; };
-// running observation normalisation (mi_rollout_step_batch_norm / mi_rollout_value_batch_norm): fp32 mean / inv_std [din] on the device, the clamp, the caller's
-// n x din buffer the normalised rows go to, and where they are recorded (table_rows NULL: nowhere; tab_states unused by the value-only form)
-struct MiRolloutObsNorm { const float* mean; const float* inv_std; float clip; float* nstate; const int* table_rows; long long n_table_rows; float* tab_states; };
-// latent stacking (mi_rollout_step_batch_stack / mi_rollout_value_batch_stack): the state is [z_t | the k - 1 latents before it | measurements].  hist: fp32
-// [n_lanes][k - 1][z_dim] on the device, slot 0 = the latent of the lane's previous step; lanes / first: int32 [n] (the step's input buffer); sstate: the caller's
-// n x din buffer trunk layer 1 reads; older: [n][(k - 1) z_dim] or NULL, where the older latents of every row go (HBM or pinned host memory).  obs_mean NULL: not
-// normalised (tab_states takes the raw rows); else sstate / tab_states take the normalised rows and tab_raw_states the raw ones.  table_rows NULL: no table is written.
-struct MiRolloutStack {
-    int k; float* hist; int n_lanes; const int* lanes; const int* first; int advance; float* sstate; float* older;
-    const float* obs_mean; const float* obs_inv_std; float clip;
-    const int* table_rows; long long n_table_rows; float* tab_states; float* tab_raw_states;
+// One batched call -- any of the eleven mi_rollout_{step,value}_batch* / mi_mlp_rollout_{step,value}_batch* entries -- without its encoder chain, each field once.  The
+// entry fills it and hands it to its engine's driver; the three functions below do everything that does not depend on the encoder.
+struct MiRolloutCall {
+    // name and form.  who: in front of every message; who_rec: in front of "null handle" and "missing tables" (another name for mi_rollout_step_batch_rec alone).
+    // value_only: the value trunk and the value-only heads, out [n].  stacked: latent stacking.  must_record / must_normalise: the entry has no form without
+    // table_rows / without obs_mean (the ConvVAE _rec, _norm and value entries); elsewhere a NULL there turns recording / normalising off
+    const char *who, *who_rec; bool value_only, stacked, must_record, must_normalise;
+    const float* measurements; int n_meas; const float* noise; int greedy, n; float* out;       // out [n][A + 1 + z_dim]
+    // tables: call row e is also stored as row table_rows[e] of the horizon-batch tables (rows outside [0, n_table_rows) are skipped).  tab_states takes the state the
+    // trunks read, tab_raw_states the raw one beside a normalised one; the value-only call writes tab_final_values alone
+    const int* table_rows; long long n_table_rows; float *tab_states, *tab_raw_states, *tab_actions, *tab_values, *tab_final_values;
+    // running observation normalisation: fp32 mean / inv_std [din] on the device, the clamp, and (not stacked) the caller's n x din buffer the normalised rows go to
+    const float *obs_mean, *obs_inv_std; float obs_clip; float* nstate;
+    // latent stacking: the state is [z_t | the latent_stack - 1 latents before it | measurements].  hist: fp32 [n_lanes][latent_stack - 1][z_dim] on the device, slot 0 =
+    // the latent of the lane's previous step; lanes / first: int32 [n] (the step's input buffer); sstate: the caller's n x din buffer trunk layer 1 reads (the normalised
+    // rows with obs_mean: the normaliser runs inside the stack kernel and nstate is unused); older: [n][(latent_stack - 1) z_dim] or NULL, where the older latents of
+    // every row go (HBM or pinned host memory)
+    int latent_stack; float* hist; int n_lanes; const int *lanes, *first; int advance; float *sstate, *older;
 };
-// every refusal of the stacked form, before any launch: records "<who>: .." and returns MI_ERR_ARG / MI_ERR_SHAPE, or MI_OK (din < 0: the argument checks alone)
-int mi_rollout_stack_check(const MiRolloutStack& s, int z_dim, int n_meas, int din, const char* who);
-int mi_rollout_value_batch(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, int n, float* out,
-                           const MiRolloutValueRec& rec, const MiRolloutObsNorm* nrm = nullptr, const MiRolloutStack* stk = nullptr);
-// the stacked step: rec NULL = the plain heads; else the recording heads, which store action and value (rec->states is not read: the stack kernel has written the row)
-int mi_rollout_policy_batch_stack(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n,
-                                  float* out, const MiRolloutRec* rec, const MiRolloutStack& stk);
-int mi_rollout_policy_batch_norm(hipStream_t st, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, const float* noise, int greedy, int n,
-                                 float* out, const MiRolloutRec* rec, const MiRolloutObsNorm& nrm);
+// the fields every entry has; the rest start as 0 / NULL
+inline MiRolloutCall mi_rollout_call(const char* who, bool value_only, const float* measurements, int n_meas, const float* noise, int greedy, int n, float* out) {
+    MiRolloutCall c = {};
+    c.who = c.who_rec = who; c.value_only = value_only; c.measurements = measurements; c.n_meas = n_meas; c.noise = noise; c.greedy = greedy; c.n = n; c.out = out;
+    return c;
+}
+inline void mi_rollout_call_stack(MiRolloutCall& c, int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, int advance, float* sstate, float* older) {
+    c.stacked = true; c.latent_stack = latent_stack; c.hist = hist; c.n_lanes = n_lanes; c.lanes = lanes; c.first = first; c.advance = advance; c.sstate = sstate; c.older = older;
+}
+int mi_rollout_fail(int code, const char* who, const char* text);       // records "<who>: <text>" and returns code
+// every refusal that reads neither handle (buffers, tables, normaliser, stack, the range of n), before any launch: MI_ERR_ARG with its message, or MI_OK
+int mi_rollout_call_check(const MiRolloutCall& c, const void* frames, const void* scratch);
+// the PPO side: fills q for c.n rows (refusing a policy whose input size, action count or max_batch does not fit the call) and entries 1 and 2 of the zero list -- the
+// trunks' raw sums [net][n][H], or with value_only the value net's halves alone.  Entry 0 is the encoder's
+int mi_rollout_call_prepare(const MiRolloutCall& c, void* ppo_h, const float* mean_raw, int z_dim, mi::PpoFusedParams* q, MiZeroList* zero);
+// the launches behind the encoder: the normaliser or the stack kernel (trunk layer 1 then reads its rows), the two trunk stages (value_only: the value net at half the
+// grid), and the plain, the recording or the value-only heads
+int mi_rollout_call_finish(hipStream_t st, const MiRolloutCall& c, const mi::PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim);
 // layer 1 of the MlpVAE encoder from the camera bytes of n environments (rollout_mlp.hip; mi_mlp_rollout_step_batch): clears `zero` -- the raw-sum buffers of the whole
 // call, raw1 among them -- in a launch of its own, then adds frames / 255 x w1 [S][N1] onto raw1 [n][N1] (fp32 atomics).  frames: 4-byte aligned.
 int mi_rollout_mlp_layer1(hipStream_t st, const unsigned char* frames, const float* w1, float* raw1, int S, int N1, int n, const MiZeroList* zero);

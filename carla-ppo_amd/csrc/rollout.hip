@@ -660,54 +660,89 @@ static void layer1_reads_rows(RollConvBatchParams& l1, const float* rows, int di
     l1.x_bytes = (unsigned)n * (unsigned)din * 4u; l1.xb_bytes = 0; l1.tail_bytes = 0;
 }
 
-// running observation normalisation (nrm != NULL): the normalise launch, and trunk layer 1 re-aimed at what it wrote
-static void obs_norm_layer1(hipStream_t st, RollConvBatchParams& l1, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim,
-                            const float* measurements, int n, const MiRolloutObsNorm& nrm) {
-    const RollObsNormParams p = {mean_raw, mean_bias, measurements, nrm.mean, nrm.inv_std, nrm.clip, nrm.nstate, nrm.table_rows, nrm.n_table_rows, nrm.tab_states, n, z_dim, q.din};
-    hipLaunchKernelGGL(rollout_obs_norm_kernel, dim3(n), dim3(128), 0, st, p);
-    layer1_reads_rows(l1, nrm.nstate, q.din, n);
-}
-
-// latent stacking (stk != NULL): every refusal, for the entries to call before their first launch
-int mi_rollout_stack_check(const MiRolloutStack& s, int z_dim, int n_meas, int din, const char* who) {
-    static thread_local char msg[192];
-    const char* text = nullptr; int code = MI_ERR_ARG;
-    if (s.k < 2 || s.k > MI_ROLLOUT_MAX_STACK) text = "2 <= latent_stack <= MI_ROLLOUT_MAX_STACK";
-    else if (!s.hist || !s.lanes || !s.first || !s.sstate || s.n_lanes < 1) text = "missing hist / lanes / first / sstate";
-    else if (((uintptr_t)s.sstate) & 15) text = "sstate must be 16-byte aligned";
-    else if (s.obs_mean && (!s.obs_inv_std || !(s.clip > 0.f))) text = "obs_inv_std is missing or obs_clip is not a positive value (+inf: never clamp)";
-    else if (!s.obs_mean && (s.obs_inv_std || s.tab_raw_states)) text = "obs_inv_std and tab_raw_states are NULL where obs_mean is";
-    else if (s.table_rows && (s.n_table_rows < 1 || !s.tab_states || (s.obs_mean && !s.tab_raw_states))) text = "missing tables";
-    else if (din < 0) {}                                 // (the early call, before the handles are read: the shape checks follow once the policy's size is known)
-    else if ((long long)s.k * z_dim + n_meas != din) { text = "latent_stack x z_dim + measurements must equal the policy's input size"; code = MI_ERR_SHAPE; }
-    else if (din > ROLL_STACK_THREADS * ROLL_STACK_REGS) { text = "at most 1024 inputs"; code = MI_ERR_SHAPE; }
-    if (!text) return MI_OK;
+int mi_rollout_fail(int code, const char* who, const char* text) {
+    char msg[192];
     snprintf(msg, sizeof(msg), "%s: %s", who, text);
     return mi_fail(code, msg);
 }
 
-// the stack launch, and trunk layer 1 re-aimed at the rows it wrote, as the normaliser's launch re-aims it
-static void stack_layer1(hipStream_t st, RollConvBatchParams& l1, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim,
-                         const float* measurements, int n, const MiRolloutStack& s) {
-    const RollStackParams p = {mean_raw, mean_bias, measurements, s.hist, s.lanes, s.first, s.obs_mean, s.obs_inv_std, s.clip, s.sstate, s.older,
-                               s.table_rows, s.n_table_rows, s.tab_states, s.tab_raw_states, n, z_dim, s.k, q.din, s.n_lanes, s.advance};
-    hipLaunchKernelGGL(rollout_stack_kernel, dim3(n), dim3(ROLL_STACK_THREADS), 0, st, p);
-    layer1_reads_rows(l1, s.sstate, q.din, n);
+int mi_rollout_call_check(const MiRolloutCall& c, const void* frames, const void* scratch) {
+    const auto fail = [&c](const char* text) { return mi_rollout_fail(MI_ERR_ARG, c.who, text); };
+    const bool norm = c.must_normalise || c.obs_mean;
+    if (!frames || !c.out || !scratch || (c.n_meas > 0 && !c.measurements) || (!c.greedy && !c.noise)) return fail("missing buffers");
+    if ((c.must_record || c.table_rows) &&
+        (!c.table_rows || c.n_table_rows < 1 || (c.value_only ? !c.tab_final_values : (!c.tab_states || !c.tab_actions || !c.tab_values || (norm && !c.tab_raw_states)))))
+        return mi_rollout_fail(MI_ERR_ARG, c.who_rec, "missing tables");
+    if (c.stacked) {
+        if (c.latent_stack < 2 || c.latent_stack > MI_ROLLOUT_MAX_STACK) return fail("2 <= latent_stack <= MI_ROLLOUT_MAX_STACK");
+        if (!c.hist || !c.lanes || !c.first || !c.sstate || c.n_lanes < 1) return fail("missing hist / lanes / first / sstate");
+        if (((uintptr_t)c.sstate) & 15) return fail("sstate must be 16-byte aligned");
+        if (c.obs_mean && (!c.obs_inv_std || !(c.obs_clip > 0.f))) return fail("obs_inv_std is missing or obs_clip is not a positive value (+inf: never clamp)");
+        if (!c.obs_mean && (c.obs_inv_std || c.tab_raw_states)) return fail("obs_inv_std and tab_raw_states are NULL where obs_mean is");
+    } else if (norm) {
+        if (!c.obs_mean || !c.obs_inv_std || !c.nstate) return fail("missing obs_mean / obs_inv_std / nstate");
+        if (((uintptr_t)c.nstate) & 15) return fail("nstate must be 16-byte aligned");
+        if (!(c.obs_clip > 0.f)) return fail("obs_clip is a positive value (+inf: never clamp)");
+    } else if (c.obs_inv_std || c.nstate || c.tab_raw_states) {
+        return fail("obs_inv_std, nstate and tab_raw_states are NULL where obs_mean is");
+    }
+    if (c.n < 1 || c.n > MI_ROLLOUT_MAX_ENVS) return fail("1 <= n <= MI_ROLLOUT_MAX_ENVS");
+    return MI_OK;
 }
 
-// trunks and heads of n environments: mean_raw [n][z_dim], measurements [n][din - z_dim], noise [n][A], out [n][A + 1 + z_dim]; raw sums in q.h1 / q.h2 as [net][n][H]
-static int policy_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
-                        const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec, const MiRolloutObsNorm* nrm = nullptr, const MiRolloutStack* stk = nullptr) {
-    RollConvBatchParams l1, l2; dim3 g1, g2; RollHeadParams h;
-    const int rc = fill_trunks_batch(l1, g1, l2, g2, q, mean_raw, mean_bias, z_dim, measurements, n);
+int mi_rollout_call_prepare(const MiRolloutCall& c, void* ppo_h, const float* mean_raw, int z_dim, PpoFusedParams* q, MiZeroList* zero) {
+    const int rc = mi_ppo_internal_fill(ppo_h, q, mean_raw, 1);
     if (rc != MI_OK) return rc;
-    fill_head(h, q, mean_raw, mean_bias, z_dim, noise, greedy, out);
-    if (nrm) obs_norm_layer1(st, l1, q, mean_raw, mean_bias, z_dim, measurements, n, *nrm);
-    if (stk) stack_layer1(st, l1, q, mean_raw, mean_bias, z_dim, measurements, n, *stk);
+    if (c.stacked) {
+        if ((long long)c.latent_stack * z_dim + c.n_meas != q->din) return mi_rollout_fail(MI_ERR_SHAPE, c.who, "latent_stack x z_dim + measurements must equal the policy's input size");
+        if (q->din > ROLL_STACK_THREADS * ROLL_STACK_REGS) return mi_rollout_fail(MI_ERR_SHAPE, c.who, "at most 1024 inputs");
+    } else if (q->din != z_dim + c.n_meas) {
+        return mi_rollout_fail(MI_ERR_SHAPE, c.who, "z_dim + measurements must equal the policy's input size");
+    }
+    if (q->A > 8) return mi_rollout_fail(MI_ERR_ARG, c.who, "at most 8 actions");
+    if (mi_ppo_internal_fill(ppo_h, q, mean_raw, c.n) != MI_OK) return mi_rollout_fail(MI_ERR_ARG, c.who, "n exceeds the PPO engine's max_batch");
+    const long long nets = c.value_only ? 1 : 2, skip = 2 - nets;          // [net][n][H]: both nets, or net 1 (the value net's half) alone
+    zero->p[1] = q->h1 + skip * c.n * q->H1; zero->n[1] = nets * c.n * q->H1;
+    zero->p[2] = q->h2 + skip * c.n * q->H2; zero->n[2] = nets * c.n * q->H2;
+    return MI_OK;
+}
+
+// trunks and heads of n environments: mean_raw [n][z_dim], measurements [n][din - z_dim], noise [n][A]; raw sums in q.h1 / q.h2 as [net][n][H]
+int mi_rollout_call_finish(hipStream_t st, const MiRolloutCall& c, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim) {
+    RollConvBatchParams l1, l2; dim3 g1, g2;
+    const int n = c.n, rc = fill_trunks_batch(l1, g1, l2, g2, q, mean_raw, mean_bias, z_dim, c.measurements, n);
+    if (rc != MI_OK) return rc;
+    const int* state_rows = c.value_only ? nullptr : c.table_rows;       // the value-only call records no state: the final observation of a truncated episode is no step
+    if (c.stacked) {                                     // the stack launch (it normalises as well), and trunk layer 1 re-aimed at the rows it wrote
+        const RollStackParams p = {mean_raw, mean_bias, c.measurements, c.hist, c.lanes, c.first, c.obs_mean, c.obs_inv_std, c.obs_clip, c.sstate, c.older,
+                                   state_rows, c.n_table_rows, c.tab_states, c.tab_raw_states, n, z_dim, c.latent_stack, q.din, c.n_lanes, c.advance};
+        hipLaunchKernelGGL(rollout_stack_kernel, dim3(n), dim3(ROLL_STACK_THREADS), 0, st, p);
+        layer1_reads_rows(l1, c.sstate, q.din, n);
+    } else if (c.obs_mean) {                             // the normalise launch, likewise
+        const RollObsNormParams p = {mean_raw, mean_bias, c.measurements, c.obs_mean, c.obs_inv_std, c.obs_clip, c.nstate, state_rows, c.n_table_rows, c.tab_states, n, z_dim, q.din};
+        hipLaunchKernelGGL(rollout_obs_norm_kernel, dim3(n), dim3(128), 0, st, p);
+        layer1_reads_rows(l1, c.nstate, q.din, n);
+    }
+    if (c.value_only) {                                  // the VALUE trunk alone: the operands moved to net 1 and half the grid (the policy net's half of q.h1 / q.h2 is neither cleared, written nor read)
+        l1.w += l1.w_net; l1.out += l1.out_net;                                                // (layer 1's x / bias strides are 0: both nets read the one state)
+        l2.x += l2.x_net; l2.x_bias += l2.xb_net; l2.w += l2.w_net; l2.out += l2.out_net;
+        g1.y = l1.row_tiles; g2.y = l2.row_tiles;                                              // blockIdx.y / row_tiles = 0: the kernels' "net 0" is the value net
+    }
     launch_conv_batch(st, g1, l1);
     launch_conv_batch(st, g2, l2);
-    if (rec) {                                           // (stacked: the row is written already; the heads store action and value)
-        const RollRecParams t = {rec->table_rows, rec->n_table_rows, measurements, q.din - z_dim, q.din, stk ? nullptr : rec->states, rec->actions, rec->values};
+    if (c.value_only) {
+        // table_rows NULL (the MLP entries): the value heads read one int per environment whatever the tables are; with n_table_rows = 0 no row lies inside the table and
+        // nothing is stored, so the list may be any n readable ints: the raw means
+        const RollValueParams v = {l2.out, q.theta + q.off[10], q.theta + q.off[11], q.theta + q.off[12], q.H2, c.table_rows ? c.table_rows : (const int*)mean_raw,
+                                   c.table_rows ? c.n_table_rows : 0, c.out, c.tab_final_values};
+        hipLaunchKernelGGL(rollout_value_rec_kernel, dim3(n), dim3(256), 0, st, v);
+        return mi_check_launch("rollout_value_batch");
+    }
+    RollHeadParams h;
+    fill_head(h, q, mean_raw, mean_bias, z_dim, c.noise, c.greedy, c.out);
+    if (c.table_rows) {                                  // the recording heads store action, value and the raw state (stacked: the stack kernel has written the rows already)
+        const RollRecParams t = {c.table_rows, c.n_table_rows, c.measurements, q.din - z_dim, q.din, c.stacked ? nullptr : (c.obs_mean ? c.tab_raw_states : c.tab_states),
+                                 c.tab_actions, c.tab_values};
         if (q.A <= 2) hipLaunchKernelGGL(rollout_head_rec_kernel<2>, dim3(n), dim3(256), 0, st, h, n, t);
         else hipLaunchKernelGGL(rollout_head_rec_kernel<8>, dim3(n), dim3(256), 0, st, h, n, t);
         return mi_check_launch("rollout_policy_batch_rec");
@@ -715,45 +750,4 @@ static int policy_batch(hipStream_t st, const PpoFusedParams& q, const float* me
     if (q.A <= 2) hipLaunchKernelGGL(rollout_head_batch_kernel<2>, dim3(n), dim3(256), 0, st, h, n);
     else hipLaunchKernelGGL(rollout_head_batch_kernel<8>, dim3(n), dim3(256), 0, st, h, n);
     return mi_check_launch("rollout_policy_batch");
-}
-
-// the VALUE trunk alone and the value-only heads: the batched trunk stages with their operands moved to net 1 and half the grid (the policy net's half of q.h1 / q.h2
-// is neither cleared, written nor read), out [n] = the values, also left in rec.final_values[rec.table_rows[e]]
-int mi_rollout_value_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements, int n, float* out,
-                           const MiRolloutValueRec& rec, const MiRolloutObsNorm* nrm, const MiRolloutStack* stk) {
-    RollConvBatchParams l1, l2; dim3 g1, g2;
-    const int rc = fill_trunks_batch(l1, g1, l2, g2, q, mean_raw, mean_bias, z_dim, measurements, n);
-    if (rc != MI_OK) return rc;
-    if (nrm) obs_norm_layer1(st, l1, q, mean_raw, mean_bias, z_dim, measurements, n, *nrm);
-    if (stk) stack_layer1(st, l1, q, mean_raw, mean_bias, z_dim, measurements, n, *stk);
-    l1.w += l1.w_net; l1.out += l1.out_net;                                                // (layer 1's x / bias strides are 0: both nets read the one state)
-    l2.x += l2.x_net; l2.x_bias += l2.xb_net; l2.w += l2.w_net; l2.out += l2.out_net;
-    g1.y = l1.row_tiles; g2.y = l2.row_tiles;                                              // blockIdx.y / row_tiles = 0: the kernels' "net 0" is the value net
-    launch_conv_batch(st, g1, l1);
-    launch_conv_batch(st, g2, l2);
-    const RollValueParams v = {l2.out, q.theta + q.off[10], q.theta + q.off[11], q.theta + q.off[12], q.H2, rec.table_rows, rec.n_table_rows, out, rec.final_values};
-    hipLaunchKernelGGL(rollout_value_rec_kernel, dim3(n), dim3(256), 0, st, v);
-    return mi_check_launch("rollout_value_batch");
-}
-
-int mi_rollout_policy_batch(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
-                            const float* noise, int greedy, int n, float* out) {
-    return policy_batch(st, q, mean_raw, mean_bias, z_dim, measurements, noise, greedy, n, out, nullptr);
-}
-
-int mi_rollout_policy_batch_rec(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
-                                const float* noise, int greedy, int n, float* out, const MiRolloutRec& rec) {
-    return policy_batch(st, q, mean_raw, mean_bias, z_dim, measurements, noise, greedy, n, out, &rec);
-}
-
-// the normalised step (mi_rollout_step_batch_norm): rec NULL = the evaluation step, the plain batched heads; else the recording heads, whose rec->states is the RAW table
-int mi_rollout_policy_batch_norm(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
-                                 const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec, const MiRolloutObsNorm& nrm) {
-    return policy_batch(st, q, mean_raw, mean_bias, z_dim, measurements, noise, greedy, n, out, rec, &nrm);
-}
-
-// the stacked step (mi_rollout_step_batch_stack): the stack launch in front of trunk layer 1; rec NULL = the plain batched heads
-int mi_rollout_policy_batch_stack(hipStream_t st, const PpoFusedParams& q, const float* mean_raw, const float* mean_bias, int z_dim, const float* measurements,
-                                  const float* noise, int greedy, int n, float* out, const MiRolloutRec* rec, const MiRolloutStack& stk) {
-    return policy_batch(st, q, mean_raw, mean_bias, z_dim, measurements, noise, greedy, n, out, rec, nullptr, &stk);
 }

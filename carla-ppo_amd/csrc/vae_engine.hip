@@ -1012,82 +1012,57 @@ long long mi_rollout_batch_workspace_bytes(void* vae_h, void* ppo_h, int n_envs)
     return roll_env_floats(e) * 4 * n_envs;
 }
 
-// one body for the plain call, the recording call (rec != NULL: mi_rollout_step_batch_rec, whose last launch is the recording heads) and the value-only call (vrec != NULL:
-// mi_rollout_value_batch_rec: the same encoder chain, then the value trunk and the value-only heads; out holds n floats)
-// (the caller's own name in front of every message: the _norm entries share these checks)
-#define ROLL_FAIL(code, text) return mi_fail(code, stk ? (vrec ? "mi_rollout_value_batch_stack: " text : "mi_rollout_step_batch_stack: " text) \
-                                                   : nrm ? (vrec ? "mi_rollout_value_batch_norm: " text : "mi_rollout_step_batch_norm: " text) \
-                                                         : (vrec ? "mi_rollout_value_batch_rec: " text : "mi_rollout_step_batch: " text))
-static int rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
-                              void* scratch, long long scratch_bytes, float* out, const MiRolloutRec* rec, const MiRolloutValueRec* vrec = nullptr,
-                              const MiRolloutObsNorm* nrm = nullptr, const MiRolloutStack* stk = nullptr) {
+// one driver behind the seven entries: what is this engine's own -- the scratch, the encoder chain -- around the shared check / prepare / finish of rollout.hip
+static int rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, void* scratch, long long scratch_bytes, const MiRolloutCall& c) {
     VaeEngine* e = (VaeEngine*)vae_h;
-    if (stk && (!e || !ppo_h)) ROLL_FAIL(MI_ERR_STATE, "null handle");
-    if (nrm && (!e || !ppo_h)) return mi_fail(MI_ERR_STATE, vrec ? "mi_rollout_value_batch_norm: null handle" : "mi_rollout_step_batch_norm: null handle");
-    if (!e || !ppo_h) return mi_fail(MI_ERR_STATE, vrec ? "mi_rollout_value_batch_rec: null handle" : rec ? "mi_rollout_step_batch_rec: null handle" : "mi_rollout_step_batch: null handle");
-    if (!frames_u8 || !out || !scratch || (n_meas > 0 && !measurements) || (!greedy && !noise)) ROLL_FAIL(MI_ERR_ARG, "missing buffers");
-    if (stk) CK(mi_rollout_stack_check(*stk, 0, 0, -1, vrec ? "mi_rollout_value_batch_stack" : "mi_rollout_step_batch_stack"));
-    if (stk && rec && (!rec->actions || !rec->values || rec->n_table_rows < 1)) ROLL_FAIL(MI_ERR_ARG, "missing tables");     // (the states tables: mi_rollout_stack_check)
-    if (!stk && rec && (!rec->table_rows || !rec->states || !rec->actions || !rec->values || rec->n_table_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch_rec: missing tables");
-    if (vrec && (!vrec->table_rows || !vrec->final_values || vrec->n_table_rows < 1)) ROLL_FAIL(MI_ERR_ARG, "missing tables");
-    if (nrm) {                                           // running observation normalisation: every check before any launch
-#define NORM_FAIL(text) return mi_fail(MI_ERR_ARG, vrec ? "mi_rollout_value_batch_norm: " text : "mi_rollout_step_batch_norm: " text)
-        if (!nrm->mean || !nrm->inv_std || !nrm->nstate) NORM_FAIL("missing obs_mean / obs_inv_std / nstate");
-        if (((uintptr_t)nrm->nstate) & 15) NORM_FAIL("nstate must be 16-byte aligned");
-        if (!(nrm->clip > 0.f)) NORM_FAIL("obs_clip is a positive value (+inf: never clamp)");
-#undef NORM_FAIL
-    }
-    if (n < 1 || n > MI_ROLLOUT_MAX_ENVS) ROLL_FAIL(MI_ERR_ARG, "1 <= n <= MI_ROLLOUT_MAX_ENVS");
-    if (((uintptr_t)scratch) & 15) ROLL_FAIL(MI_ERR_ARG, "the scratch must be 16-byte aligned");
-    if (scratch_bytes < roll_env_floats(e) * 4 * n) ROLL_FAIL(MI_ERR_ARG, "scratch too small (mi_rollout_batch_workspace_bytes)");
+    if (!e || !ppo_h) return mi_rollout_fail(MI_ERR_STATE, c.who_rec, "null handle");
+    CK(mi_rollout_call_check(c, frames_u8, scratch));
+    if (((uintptr_t)scratch) & 15) return mi_rollout_fail(MI_ERR_ARG, c.who, "the scratch must be 16-byte aligned");
+    if (scratch_bytes < roll_env_floats(e) * 4 * c.n) return mi_rollout_fail(MI_ERR_ARG, c.who, "scratch too small (mi_rollout_batch_workspace_bytes)");
     const MiVaeDesc& d = e->d; const Geom& g = e->g;
+    const int n = c.n;
     hipStream_t st = (hipStream_t)stream;
     float* act[NCONV + 1]; act[0] = nullptr;
     long long o = 0;
     for (int i = 1; i <= NCONV; ++i) { act[i] = (float*)scratch + o; o += (long long)n * g.ih[i] * g.iw[i] * g.c[i]; }
     float* mean_raw = (float*)scratch + o;
     mi::PpoFusedParams q;
-    CK(mi_ppo_internal_fill(ppo_h, &q, mean_raw, 1));
-    if (stk) CK(mi_rollout_stack_check(*stk, d.z_dim, n_meas, q.din, vrec ? "mi_rollout_value_batch_stack" : "mi_rollout_step_batch_stack"));
-    else if (q.din != d.z_dim + n_meas) ROLL_FAIL(MI_ERR_SHAPE, "z_dim + measurements must equal the policy's input size");
-    if (q.A > 8) ROLL_FAIL(MI_ERR_ARG, "at most 8 actions");
-    if (mi_ppo_internal_fill(ppo_h, &q, mean_raw, n) != MI_OK) ROLL_FAIL(MI_ERR_ARG, "n exceeds the PPO engine's max_batch");
     MiZeroList zl = {};
+    CK(mi_rollout_call_prepare(c, ppo_h, mean_raw, d.z_dim, &q, &zl));
     zl.p[0] = act[2]; zl.n[0] = (mean_raw + (long long)n * d.z_dim) - act[2];
-    zl.p[1] = q.h1; zl.n[1] = 2LL * n * q.H1;
-    zl.p[2] = q.h2; zl.n[2] = 2LL * n * q.H2;
-    if (vrec) {                                          // the value net's halves of the trunks' raw sums alone ([net][n][H]: net 1)
-        zl.p[1] = q.h1 + (long long)n * q.H1; zl.n[1] = (long long)n * q.H1;
-        zl.p[2] = q.h2 + (long long)n * q.H2; zl.n[2] = (long long)n * q.H2;
-    }
     CK(mi_rollout_conv1_batch(st, frames_u8, e->params + e->L.off[0], e->bptr(1), act[1], g.ih[0], g.iw[0], g.c[0], 4, 4, g.c[1], n, &zl));
     for (int i = 1; i < NCONV; ++i)                      // conv(i+1): conv2 reads conv1's finished output, the others raw sums + bias + ReLU on load
         CK(mi_rollout_conv_batch(st, act[i], i == 1 ? nullptr : e->bptr(2 * (i - 1) + 1), g.ih[i], g.iw[i], g.c[i], e->params + e->L.off[2 * i], g.c[i + 1], g.c[i + 1], 4, 4, act[i + 1], 0, n));
     CK(mi_rollout_conv_batch(st, act[NCONV], e->bptr(2 * (NCONV - 1) + 1), 1, 1, g.c[NCONV], e->params + e->L.off[8], 2 * d.z_dim, d.z_dim, 1, 1, mean_raw, g.flat, n));
-    if (vrec) return mi_rollout_value_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, n, out, *vrec, nrm, stk);
-    if (stk) return mi_rollout_policy_batch_stack(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out, rec, *stk);
-    if (nrm) return mi_rollout_policy_batch_norm(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out, rec, *nrm);
-    if (rec) return mi_rollout_policy_batch_rec(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out, *rec);
-    return mi_rollout_policy_batch(st, q, mean_raw, e->bptr(9), d.z_dim, measurements, noise, greedy, n, out);
+    return mi_rollout_call_finish(st, c, q, mean_raw, e->bptr(9), d.z_dim);
 }
-#undef ROLL_FAIL
 
 int mi_rollout_step_batch(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
                           void* scratch, long long scratch_bytes, float* out) {
-    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, nullptr);
+    const MiRolloutCall c = mi_rollout_call("mi_rollout_step_batch", false, measurements, n_meas, noise, greedy, n, out);
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, scratch, scratch_bytes, c);
 }
 
+// the recording call: the last launch is the recording heads.  (Its buffer, n and scratch refusals carry the name of the entry it extends.)
 int mi_rollout_step_batch_rec(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
                               void* scratch, long long scratch_bytes, float* out, const int* table_rows, long long n_table_rows, float* tab_states, float* tab_actions, float* tab_values) {
-    const MiRolloutRec rec = {table_rows, n_table_rows, tab_states, tab_actions, tab_values};
-    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, &rec);
+    MiRolloutCall c = mi_rollout_call("mi_rollout_step_batch", false, measurements, n_meas, noise, greedy, n, out);
+    c.who_rec = "mi_rollout_step_batch_rec"; c.must_record = true;
+    c.table_rows = table_rows; c.n_table_rows = n_table_rows; c.tab_states = tab_states; c.tab_actions = tab_actions; c.tab_values = tab_values;
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, scratch, scratch_bytes, c);
 }
 
 // the value of n observations and nothing else (the final observations of truncated episodes): out [n], and tab_final_values[table_rows[e]] = out[e]
+static MiRolloutCall value_call(const char* who, const float* measurements, int n_meas, int n, float* out, const int* table_rows, long long n_table_rows, float* tab_final_values) {
+    MiRolloutCall c = mi_rollout_call(who, true, measurements, n_meas, nullptr, 1, n, out);
+    c.must_record = true; c.table_rows = table_rows; c.n_table_rows = n_table_rows; c.tab_final_values = tab_final_values;
+    return c;
+}
+
 int mi_rollout_value_batch_rec(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n, void* scratch,
                                long long scratch_bytes, float* out, const int* table_rows, long long n_table_rows, float* tab_final_values) {
-    const MiRolloutValueRec vrec = {table_rows, n_table_rows, tab_final_values};
-    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, nullptr, &vrec);
+    const MiRolloutCall c = value_call("mi_rollout_value_batch_rec", measurements, n_meas, n, out, table_rows, n_table_rows, tab_final_values);
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, scratch, scratch_bytes, c);
 }
 
 // the step behind running observation normalisation: the normalise launch in front of trunk layer 1 (nstate [n][din], caller-supplied), the normalised rows into
@@ -1095,19 +1070,19 @@ int mi_rollout_value_batch_rec(void* vae_h, void* ppo_h, void* stream, const uns
 int mi_rollout_step_batch_norm(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, const float* noise, int greedy, int n,
                                void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate,
                                const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values) {
-    const MiRolloutRec rec = {table_rows, n_table_rows, tab_raw_states, tab_actions, tab_values};
-    const MiRolloutObsNorm nrm = {obs_mean, obs_inv_std, obs_clip, nstate, table_rows, n_table_rows, tab_states};
-    if (table_rows && (!tab_states || !tab_raw_states || !tab_actions || !tab_values || n_table_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_rollout_step_batch_norm: missing tables");
-    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, table_rows ? &rec : nullptr, nullptr, &nrm);
+    MiRolloutCall c = mi_rollout_call("mi_rollout_step_batch_norm", false, measurements, n_meas, noise, greedy, n, out);
+    c.must_normalise = true; c.obs_mean = obs_mean; c.obs_inv_std = obs_inv_std; c.obs_clip = obs_clip; c.nstate = nstate;
+    c.table_rows = table_rows; c.n_table_rows = n_table_rows; c.tab_states = tab_states; c.tab_raw_states = tab_raw_states; c.tab_actions = tab_actions; c.tab_values = tab_values;
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, scratch, scratch_bytes, c);
 }
 
 // mi_rollout_value_batch_rec on the normalised observation (no table of states is written: the final observation of a truncated episode is no step)
 int mi_rollout_value_batch_norm(void* vae_h, void* ppo_h, void* stream, const unsigned char* frames_u8, const float* measurements, int n_meas, int n, void* scratch,
                                 long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip, float* nstate,
                                 const int* table_rows, long long n_table_rows, float* tab_final_values) {
-    const MiRolloutValueRec vrec = {table_rows, n_table_rows, tab_final_values};
-    const MiRolloutObsNorm nrm = {obs_mean, obs_inv_std, obs_clip, nstate, nullptr, 0, nullptr};
-    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, nullptr, &vrec, &nrm);
+    MiRolloutCall c = value_call("mi_rollout_value_batch_norm", measurements, n_meas, n, out, table_rows, n_table_rows, tab_final_values);
+    c.must_normalise = true; c.obs_mean = obs_mean; c.obs_inv_std = obs_inv_std; c.obs_clip = obs_clip; c.nstate = nstate;
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, scratch, scratch_bytes, c);
 }
 
 // the step with LATENT STACKING: state = [z_t | the latent_stack - 1 latents before it, from the lane's device-resident history | measurements]; the plain, the
@@ -1116,9 +1091,11 @@ int mi_rollout_step_batch_stack(void* vae_h, void* ppo_h, void* stream, const un
                                 void* scratch, long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip,
                                 const int* table_rows, long long n_table_rows, float* tab_states, float* tab_raw_states, float* tab_actions, float* tab_values,
                                 int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, int advance, float* sstate, float* older_out) {
-    const MiRolloutRec rec = {table_rows, n_table_rows, nullptr, tab_actions, tab_values};
-    const MiRolloutStack stk = {latent_stack, hist, n_lanes, lanes, first, advance, sstate, older_out, obs_mean, obs_inv_std, obs_clip, table_rows, n_table_rows, tab_states, tab_raw_states};
-    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, noise, greedy, n, scratch, scratch_bytes, out, table_rows ? &rec : nullptr, nullptr, nullptr, &stk);
+    MiRolloutCall c = mi_rollout_call("mi_rollout_step_batch_stack", false, measurements, n_meas, noise, greedy, n, out);
+    c.obs_mean = obs_mean; c.obs_inv_std = obs_inv_std; c.obs_clip = obs_clip;
+    c.table_rows = table_rows; c.n_table_rows = n_table_rows; c.tab_states = tab_states; c.tab_raw_states = tab_raw_states; c.tab_actions = tab_actions; c.tab_values = tab_values;
+    mi_rollout_call_stack(c, latent_stack, hist, n_lanes, lanes, first, advance, sstate, older_out);
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, scratch, scratch_bytes, c);
 }
 
 // the value-only call on the stacked state: never advances the history, writes no table of states and no older latents
@@ -1126,9 +1103,10 @@ int mi_rollout_value_batch_stack(void* vae_h, void* ppo_h, void* stream, const u
                                  long long scratch_bytes, float* out, const float* obs_mean, const float* obs_inv_std, float obs_clip,
                                  const int* table_rows, long long n_table_rows, float* tab_final_values,
                                  int latent_stack, float* hist, int n_lanes, const int* lanes, const int* first, float* sstate) {
-    const MiRolloutValueRec vrec = {table_rows, n_table_rows, tab_final_values};
-    const MiRolloutStack stk = {latent_stack, hist, n_lanes, lanes, first, 0, sstate, nullptr, obs_mean, obs_inv_std, obs_clip, nullptr, 0, nullptr, nullptr};
-    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, measurements, n_meas, nullptr, 1, n, scratch, scratch_bytes, out, nullptr, &vrec, nullptr, &stk);
+    MiRolloutCall c = value_call("mi_rollout_value_batch_stack", measurements, n_meas, n, out, table_rows, n_table_rows, tab_final_values);
+    c.obs_mean = obs_mean; c.obs_inv_std = obs_inv_std; c.obs_clip = obs_clip;
+    mi_rollout_call_stack(c, latent_stack, hist, n_lanes, lanes, first, 0, sstate, nullptr);
+    return rollout_step_batch(vae_h, ppo_h, stream, frames_u8, scratch, scratch_bytes, c);
 }
 
 // VAE.encode (vae/models.py:199-202): frames -> mean [B,Z] fp32

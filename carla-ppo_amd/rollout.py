@@ -517,79 +517,89 @@ class BatchedRolloutStep(_StepBase):
                 raise ValueError("%s: expected noise [%d, %d]" % (self._who, n, self.A))
         return f, n, meas, nz
 
+    # (class attributes, as defaults of what _setup() sets: the host tests' stub steps -- tests/test_mlp_rollout_host.py, test_observation_normalization_host.py,
+    # test_rollout_update_sequence_host.py -- are built without _setup() and carry none of its attributes: they are the ConvVAE step without stacking)
+    k, _kind = 1, "conv"
+
+    def _stage(self, f, n, meas, na, noise, table_rows, lanes):
+        """Stages the input of one device call: the frames, the measurements, the noise block of na floats (noise None: left as it is, the greedy step) and the int32
+        blocks behind it -- the table rows (None: none) and, with latent stacking on, the lanes (None: 0 .. n-1) and their fresh flags -- go into the pinned buffer,
+        and from there to the device where the io mode has a device buffer.  -> (stream, base, fptr, rows_ptr, lanes_ptr, lanes): the addresses of the frames, of the measurements (the noise lies 4 n n_meas bytes
+        behind), of the table rows and of the lanes (the fresh flags lie 4 n bytes behind)."""
+        import torch
+        self._in_np[:n * self.frame_bytes] = f.reshape(-1)
+        o = n * self.n_meas
+        self._f_np[:o] = meas.reshape(-1)                                            # f64 -> f32 at the feed, as ppo.py:108-109
+        if noise is not None:
+            self._f_np[o:o + na] = noise.reshape(-1)
+        o += na
+        rows_off = o
+        if table_rows is not None:
+            self._i_np[o:o + n] = table_rows
+            o += n
+        lanes_off = o
+        if self.k > 1:
+            lanes = np.arange(n) if lanes is None else lanes
+            self._i_np[o:o + n] = lanes
+            self._i_np[o + n:o + 2 * n] = self.fresh[lanes]
+            o += 2 * n
+        st = torch.cuda.current_stream(self.device)
+        used = self._f_off + 4 * o
+        if self.d_in is not None:
+            self.d_in[:used].copy_(self.h_in[:used], non_blocking=True)
+        base = (self.h_in if self.d_in is None else self.d_in).data_ptr()
+        fptr = base + self._f_off
+        return st, base, fptr, fptr + 4 * rows_off, fptr + 4 * lanes_off, lanes
+
+    def _norm_args(self, nstate):
+        """obs_mean, obs_inv_std, obs_clip [, nstate] of an entry: NULLs and 0.0 with observation normalisation off."""
+        on = self._obs_norm
+        args = (None, None, 0.0, None) if on is None else (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr())
+        return args if nstate else args[:3]
+
+    def _fetch(self, st, *ranges):
+        """The call's output in the host buffer: the copy of these [lo, hi) of the output buffer where the io mode has a device buffer, and the wait for the stream."""
+        if self.d_out is not None:
+            for lo, hi in ranges:
+                self.h_out[lo:hi].copy_(self.d_out[lo:hi], non_blocking=True)
+        st.synchronize()
+
     def record(self, f, n, meas, nz, greedy, table_rows=None, states=None, actions=None, values=None, raw_states=None, lanes=None, advance=True):
         """One device call on checked inputs.  table_rows None: mi_rollout_step_batch; else the int32 table rows go behind the noise and mi_rollout_step_batch_rec also
         leaves state / action / value of row i in row table_rows[i] of the device tables `states`, `actions`, `values`.  With observation normalisation on
         (set_observation_normalization) either becomes mi_rollout_step_batch_norm: `states` then takes the normalised rows and `raw_states` the raw ones.
         With latent stacking on every form is mi_rollout_step_batch_stack: `lanes` (None: 0 .. n-1) and their fresh flags go behind the table rows, the lanes' history
         advances unless `advance` is False, and the lanes are no longer fresh afterwards."""
-        import torch
-        nm, na = n * self.n_meas, n * self.A
-        nr = 0 if table_rows is None else n
-        # (getattr, here and in the buffers, as for `_kind`: the host tests' stub steps -- tests/test_mlp_rollout_host.py, test_observation_normalization_host.py,
-        # test_rollout_update_sequence_host.py -- are built without _setup() and carry none of its attributes)
-        stacked = getattr(self, "k", 1) > 1
-        ns = 2 * n if stacked else 0
-        if not greedy:
-            self._f_np[nm:nm + na] = (self._rng.standard_normal((n, self.A)) if nz is None else nz).reshape(-1)
-        self._in_np[:n * self.frame_bytes] = f.reshape(-1)
-        self._f_np[:nm] = meas.reshape(-1)                                           # f64 -> f32 at the feed, as ppo.py:108-109
-        if nr:
-            self._i_np[nm + na:nm + na + nr] = table_rows
-        if stacked:
-            lanes = np.arange(n) if lanes is None else lanes
-            self._i_np[nm + na + nr:nm + na + nr + n] = lanes
-            self._i_np[nm + na + nr + n:nm + na + nr + ns] = self.fresh[lanes]
-        st = torch.cuda.current_stream(self.device)
-        used = self._f_off + 4 * (nm + na + nr + ns)
-        if self.d_in is not None:
-            self.d_in[:used].copy_(self.h_in[:used], non_blocking=True)
-        base = (self.h_in if self.d_in is None else self.d_in).data_ptr()
-        fptr = base + self._f_off
-        args = (self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, None if greedy else fptr + 4 * nm, 1 if greedy else 0, n,
-                self.scratch.data_ptr(), self.scratch_bytes, (self.h_out if self.d_out is None else self.d_out).data_ptr())
-        on = self._obs_norm
-        if stacked:                                                                  # one entry per encoder: obs_mean NULL = not normalised, table_rows NULL = nothing recorded
-            out_base = (self.h_out if self.d_out is None else self.d_out).data_ptr()
-            norm = (None, None, 0.0) if on is None else (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"])
-            if table_rows is None:
-                tabs = (None, 0, None, None, None, None)
-            else:
-                tabs = (fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), None if on is None else raw_states.data_ptr(), actions.data_ptr(), values.data_ptr())
-            iptr = fptr + 4 * (nm + na + nr)
-            entry = self.L.mi_mlp_rollout_step_batch_stack if getattr(self, "_kind", "conv") == "mlp" else self.L.mi_rollout_step_batch_stack
-            entry(*args, *norm, *tabs, self.k, self.history.data_ptr(), self.num_envs, iptr, iptr + 4 * n, 1 if advance else 0, self.sstate.data_ptr(),
-                  out_base + 4 * self._older_off)
-        elif getattr(self, "_kind", "conv") == "mlp":                                # one entry: obs_mean NULL = not normalised, table_rows NULL = nothing recorded
-            norm = (None, None, 0.0, None) if on is None else (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr())
-            if table_rows is None:
-                tabs = (None, 0, None, None, None, None)
-            else:
-                tabs = (fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), None if on is None else raw_states.data_ptr(), actions.data_ptr(), values.data_ptr())
-            self.L.mi_mlp_rollout_step_batch(*args, *norm, *tabs)
+        noise = None if greedy else (self._rng.standard_normal((n, self.A)) if nz is None else nz)
+        st, base, fptr, rows_ptr, lanes_ptr, lanes = self._stage(f, n, meas, n * self.A, noise, table_rows, lanes)
+        out = (self.h_out if self.d_out is None else self.d_out).data_ptr()
+        args = (self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, None if greedy else fptr + 4 * n * self.n_meas, 1 if greedy else 0, n,
+                self.scratch.data_ptr(), self.scratch_bytes, out)
+        on, stacked, mlp = self._obs_norm, self.k > 1, self._kind == "mlp"
+        if table_rows is None:                                                       # table_rows NULL = nothing recorded
+            tabs = (None, 0, None, None, None, None)
+        else:
+            tabs = (rows_ptr, int(states.shape[0]), states.data_ptr(), None if on is None else raw_states.data_ptr(), actions.data_ptr(), values.data_ptr())
+        if stacked:                                                                  # one entry per encoder: obs_mean NULL = not normalised
+            entry = self.L.mi_mlp_rollout_step_batch_stack if mlp else self.L.mi_rollout_step_batch_stack
+            entry(*args, *self._norm_args(False), *tabs, self.k, self.history.data_ptr(), self.num_envs, lanes_ptr, lanes_ptr + 4 * n, 1 if advance else 0,
+                  self.sstate.data_ptr(), out + 4 * self._older_off)
+        elif mlp:                                                                    # one entry: obs_mean NULL = not normalised
+            self.L.mi_mlp_rollout_step_batch(*args, *self._norm_args(True), *tabs)
         elif on is not None:
-            norm = (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr())
-            if table_rows is None:
-                self.L.mi_rollout_step_batch_norm(*args, *norm, None, 0, None, None, None, None)
-            else:
-                self.L.mi_rollout_step_batch_norm(*args, *norm, fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), raw_states.data_ptr(), actions.data_ptr(),
-                                                  values.data_ptr())
+            self.L.mi_rollout_step_batch_norm(*args, *self._norm_args(True), *tabs)
         elif table_rows is None:
             self.L.mi_rollout_step_batch(*args)
         else:
-            self.L.mi_rollout_step_batch_rec(*args, fptr + 4 * (nm + na), int(states.shape[0]), states.data_ptr(), actions.data_ptr(), values.data_ptr())
-        if self.d_out is not None:
-            self.h_out[:n * self.row].copy_(self.d_out[:n * self.row], non_blocking=True)
-            if stacked:
-                lo, hi = self._older_off, self._older_off + n * (self.k - 1) * self.z_dim
-                self.h_out[lo:hi].copy_(self.d_out[lo:hi], non_blocking=True)
-        st.synchronize()
+            self.L.mi_rollout_step_batch_rec(*args, *tabs[:3], *tabs[4:])             # (no raw table without normalisation)
+        n_older = n * (self.k - 1) * self.z_dim
+        self._fetch(st, (0, n * self.row), *([(self._older_off, self._older_off + n_older)] if stacked else []))
         o = self._out_np[:n]
         if not stacked:
             return o[:, :self.A].copy(), o[:, self.A].copy(), np.concatenate([o[:, self.A + 1:].astype(np.float64), meas], axis=1)
         if advance:
             self.fresh[lanes] = False
-        older = self._older_np[:n * (self.k - 1) * self.z_dim].reshape(n, -1)       # the raw row the kernel assembled: [z_t | the older latents | measurements]
+        older = self._older_np[:n_older].reshape(n, -1)                              # the raw row the kernel assembled: [z_t | the older latents | measurements]
         return o[:, :self.A].copy(), o[:, self.A].copy(), np.concatenate([o[:, self.A + 1:], older, meas.astype(np.float32)], axis=1).astype(np.float64)      # (the measurements as the kernel read them: fp32)
 
     def record_value(self, f, n, meas, table_rows, final_values):
@@ -600,41 +610,21 @@ class BatchedRolloutStep(_StepBase):
     def record_value_lanes(self, f, n, meas, table_rows, final_values, lanes):
         """record_value() with the history lanes of the rows (None: 0 .. n-1), which are read with latent stacking on only: the call is then
         mi_rollout_value_batch_stack, which values the observation on its lane's history and never advances it."""
-        import torch
-        nm = n * self.n_meas
-        self._in_np[:n * self.frame_bytes] = f.reshape(-1)
-        self._f_np[:nm] = meas.reshape(-1)
-        self._i_np[nm:nm + n] = table_rows
-        stacked = getattr(self, "k", 1) > 1                                          # latent stacking: mi_rollout_value_batch_stack; the history is read, never advanced
-        if stacked:
-            lanes = np.arange(n) if lanes is None else lanes
-            self._i_np[nm + n:nm + 2 * n] = lanes
-            self._i_np[nm + 2 * n:nm + 3 * n] = self.fresh[lanes]
-        st = torch.cuda.current_stream(self.device)
-        used = self._f_off + 4 * (nm + (3 * n if stacked else n))
-        if self.d_in is not None:
-            self.d_in[:used].copy_(self.h_in[:used], non_blocking=True)
-        base = (self.h_in if self.d_in is None else self.d_in).data_ptr()
-        fptr = base + self._f_off
+        st, base, fptr, rows_ptr, lanes_ptr, lanes = self._stage(f, n, meas, 0, None, table_rows, lanes)
         args = (self.vae.dev.handle, self.ppo.dev.handle, st.cuda_stream, base, fptr, self.n_meas, n, self.scratch.data_ptr(), self.scratch_bytes,
                 (self.h_out if self.d_out is None else self.d_out).data_ptr())
-        rec = (fptr + 4 * nm, int(final_values.shape[0]), final_values.data_ptr())
-        on = self._obs_norm
-        if stacked:
-            norm = (None, None, 0.0) if on is None else (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"])
-            iptr = fptr + 4 * (nm + n)
-            entry = self.L.mi_mlp_rollout_value_batch_stack if getattr(self, "_kind", "conv") == "mlp" else self.L.mi_rollout_value_batch_stack
-            entry(*args, *norm, *rec, self.k, self.history.data_ptr(), self.num_envs, iptr, iptr + 4 * n, self.sstate.data_ptr())
-        elif getattr(self, "_kind", "conv") == "mlp":
-            norm = (None, None, 0.0, None) if on is None else (on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr())
-            self.L.mi_mlp_rollout_value_batch(*args, *norm, *rec)
-        elif on is not None:
-            self.L.mi_rollout_value_batch_norm(*args, on["mean32"].data_ptr(), on["inv32"].data_ptr(), on["clip"], on["nstate"].data_ptr(), *rec)
+        rec = (rows_ptr, int(final_values.shape[0]), final_values.data_ptr())
+        mlp = self._kind == "mlp"
+        if self.k > 1:                                                               # latent stacking: the history is read, never advanced
+            entry = self.L.mi_mlp_rollout_value_batch_stack if mlp else self.L.mi_rollout_value_batch_stack
+            entry(*args, *self._norm_args(False), *rec, self.k, self.history.data_ptr(), self.num_envs, lanes_ptr, lanes_ptr + 4 * n, self.sstate.data_ptr())
+        elif mlp:
+            self.L.mi_mlp_rollout_value_batch(*args, *self._norm_args(True), *rec)
+        elif self._obs_norm is not None:
+            self.L.mi_rollout_value_batch_norm(*args, *self._norm_args(True), *rec)
         else:
             self.L.mi_rollout_value_batch_rec(*args, *rec)
-        if self.d_out is not None:
-            self.h_out[:n].copy_(self.d_out[:n], non_blocking=True)
-        st.synchronize()
+        self._fetch(st, (0, n))
         return self.h_out.numpy()[:n].copy()
 
 
