@@ -121,8 +121,22 @@ bool x3(const PpoEngine* e) { return e->precision == MI_BF16X3; }
 bool clipping(const PpoEngine* e) { return e->max_grad_norm > 0.f; }
 
 // the ordered sum of squares over the 13 variables of the gradient buffer (not the alignment gaps behind the odd-sized ones) -> MI_GRAD_NORM_BLOCKS partials
-int grad_sumsq(PpoEngine* e, void* stream) {
-    return mi_grad_sumsq((hipStream_t)stream, e->grads, e->off, e->size, PPO_TENSORS, (double*)e->at(e->gn_part));
+int grad_sumsq(PpoEngine* e, void* stream, int tensors = PPO_TENSORS) {
+    return mi_grad_sumsq((hipStream_t)stream, e->grads, e->off, e->size, tensors, (double*)e->at(e->gn_part));
+}
+
+constexpr int PPO_POLICY_TENSORS = 7;                 // variables 0..6 (the policy net and action_logstd) lie in front of 7..12 (the value net) in the flat buffers
+
+// tf.train.AdamOptimizer over the first `tensors` variables of the flat buffers: all 13 (mi_ppo_apply_adam), or the policy's prefix (the policy-only clone step:
+// the value net's parameters and both of its slots are not touched, where a zero gradient would still decay the slots and move the parameters)
+int adam_prefix(PpoEngine* e, void* stream, int tensors, float alpha, float beta1, float beta2, float epsilon) {
+    const long long n = tensors == PPO_TENSORS ? e->total : e->off[tensors];
+    if (clipping(e)) {      // two launches: the ordered sum of squares, then Adam on g * scale with the factor formed from the partials by every block
+        CK(grad_sumsq(e, stream, tensors));
+        return mi_adam_tf_flat_clipped((hipStream_t)stream, e->params, e->m, e->v, e->grads, n, alpha, beta1, beta2, epsilon,
+                                       (const double*)e->at(e->gn_part), e->max_grad_norm, (float*)e->at(e->clip), 1);
+    }
+    return mi_adam_tf_flat(stream, e->params, e->m, e->v, e->grads, n, alpha, beta1, beta2, epsilon, nullptr, 1);
 }
 
 void fill_fused(const PpoEngine* e, PpoFusedParams& q, const float* states, int M) {
@@ -136,7 +150,7 @@ void fill_fused(const PpoEngine* e, PpoFusedParams& q, const float* states, int 
     q.du = (float*)e->at(e->du); q.dv = (float*)e->at(e->dv); q.partial = (float*)e->at(e->f_part); q.losses = (float*)e->at(e->losses);
     q.mean_out = (float*)e->at(e->mean); q.kl_partial = (float*)e->at(e->f_klpart);
     q.gslab = d.max_batch > 256 ? (float*)e->at(e->f_gslab) : nullptr; q.gslab_stride = e->total;      // (total is a multiple of 8 floats: pad8 per tensor)
-    q.n_nets = 3;
+    q.n_nets = 3; q.n_wnets = 2;
     q.clip_eps = d.clip_eps; q.value_scale = d.value_scale; q.entropy_scale = d.entropy_scale;
     q.wide = e->wide; q.max_batch = d.max_batch;
 }
@@ -168,8 +182,10 @@ int route_step(PpoEngine* e, void* stream, PpoFusedParams& q, void* comm, int ad
     }
     CK(mi_ppo_fused_step((hipStream_t)stream, q, 0, x3(e)));
     if (!adam) return MI_OK;
-    if (comm) CK(mi_allreduce_sum_f32(comm, stream, e->grads, e->total));
-    return mi_ppo_apply_adam(e, stream, alpha, beta1, beta2, epsilon);
+    // (the policy-only clone step: the all-reduce and the optimiser cover the policy's prefix of the flat buffers; the value net's range of the gradients is 0.0)
+    const int tensors = q.n_wnets == 1 ? PPO_POLICY_TENSORS : PPO_TENSORS;
+    if (comm) CK(mi_allreduce_sum_f32(comm, stream, e->grads, tensors == PPO_TENSORS ? e->total : e->off[tensors]));
+    return adam_prefix(e, stream, tensors, alpha, beta1, beta2, epsilon);
 }
 
 int policy_fwd(PpoEngine* e, void* st, const float* prm, const long long* off, int M, void* h1, void* h2, void* u) {
@@ -456,6 +472,28 @@ int mi_ppo_train_step_kl(void* h, void* comm, void* stream, const float* states,
     return route_step(e, stream, q, comm, adam, alpha, beta1, beta2, epsilon);
 }
 
+// Behaviour cloning (include/mi355_carla.h; the definition is in ppo_fused.hip's clone head / loss kernel): ONE entry for every form, as mi_ppo_train_step_kl is --
+// row_idx NULL or not, comm NULL or not, adam 0 / 1, returns NULL (policy only: the value net is neither run nor touched) or given (the value net is fitted to them)
+// -- on route_step's routes.  Fused kernels only.
+int mi_ppo_clone_step(void* h, void* comm, void* stream, const float* states, const float* expert_actions, const float* returns, int kind,
+                      const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_clone_step: null handle");
+    // (what needs no engine is checked before the handle is looked at)
+    if (M < 1 || (row_idx && n_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_ppo_clone_step: batch outside [1, max_batch] or empty tables");
+    if (!states || !expert_actions) return mi_fail(MI_ERR_ARG, "mi_ppo_clone_step: missing buffers (states, expert_actions)");
+    if (kind != 0 && kind != 1) return mi_fail(MI_ERR_ARG, "mi_ppo_clone_step: kind is 0 (the Gaussian negative log-likelihood) or 1 (the squared error of the mean)");
+    if (adam != 0 && adam != 1) return mi_fail(MI_ERR_ARG, "mi_ppo_clone_step: adam is 0 (stop with the gradients in the flat buffer) or 1 (apply the optimiser)");
+    if (M > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_clone_step: batch outside [1, max_batch] or empty tables");
+    if (!e->grads || (adam && (!e->m || !e->v))) return mi_fail(MI_ERR_STATE, "mi_ppo_clone_step: engine created without gradient / optimiser buffers");
+    if (!fused_enabled(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_clone_step: needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0): there is no per-layer form of the clone step");
+    PpoFusedParams q; fill_step(e, q, states, expert_actions, returns, nullptr, nullptr, row_idx, n_rows, M, inv_m, grad_scale);
+    // no old policy (net 2 is not run), no advantage, no entropy term; policy only: net 0 alone through the whole chain
+    q.clone = 1 + kind; q.entropy_scale = 0.f;
+    q.n_nets = q.n_wnets = returns ? 2 : 1;
+    return route_step(e, stream, q, comm, adam, alpha, beta1, beta2, epsilon);
+}
+
 // mi_ppo_logp_old that keeps the old policy's action means as well: logp_out [M] (bit for bit mi_ppo_logp_old's), mean_out [M, A] -- the two tables of the KL penalty
 int mi_ppo_old_policy_cache(void* h, void* stream, const float* states, const float* actions, int M, float* logp_out, float* mean_out) {
     PpoEngine* e = (PpoEngine*)h;
@@ -565,12 +603,7 @@ int mi_ppo_apply_adam(void* h, void* stream, float alpha, float beta1, float bet
     PpoEngine* e = (PpoEngine*)h;
     if (!e) return mi_fail(MI_ERR_STATE, "ppo engine: null handle");
     if (!e->grads || !e->m || !e->v) return mi_fail(MI_ERR_STATE, "mi_ppo_apply_adam: engine created without optimiser buffers");
-    if (clipping(e)) {      // two launches: the ordered sum of squares, then Adam on g * scale with the factor formed from the partials by every block
-        CK(grad_sumsq(e, stream));
-        return mi_adam_tf_flat_clipped((hipStream_t)stream, e->params, e->m, e->v, e->grads, e->total, alpha, beta1, beta2, epsilon,
-                                       (const double*)e->at(e->gn_part), e->max_grad_norm, (float*)e->at(e->clip), 1);
-    }
-    return mi_adam_tf_flat(stream, e->params, e->m, e->v, e->grads, e->total, alpha, beta1, beta2, epsilon, nullptr, 1);
+    return adam_prefix(e, stream, PPO_TENSORS, alpha, beta1, beta2, epsilon);
 }
 
 // Global-norm gradient clipping (tf.clip_by_global_norm in front of the optimiser; include/mi355_carla.h).  0: off, the default of a new engine.

@@ -8,6 +8,8 @@
 //   ppo_wgrad_kernel      every weight / bias gradient of both nets as independent 32 x 32 tiles, one wave each (dW2 = h1^T dh2, dW1 = s^T dh1,
 //                         head kernels, biases as all-ones MFMA rows) and -- single GPU -- its TF-Adam update straight from the accumulators;
 //                         one spare wave finalises the loss scalars and logstd
+// Behaviour cloning (mi_ppo_clone_step) is the same chain with ppo_head_clone_kernel in the third place -- a supervised loss on the expert's actions -- and, without
+// returns, with net 0 alone in every launch (PpoFusedParams::n_wnets).
 //
 // All arithmetic is exact fp32 (v_mfma_f32_32x32x2_f32 = fmaf chains; 1e-4 parity with the oracle).  The split-bf16 mode (X3 = true: MI_BF16X3 through
 // mi_ppo_set_precision) instantiates the four GEMM kernels with three v_mfma_f32_32x32x16_bf16 per k-block of 16 instead; everything else is shared.  The step is latency bound (78 MFLOP,
@@ -145,7 +147,8 @@ __global__ __launch_bounds__(256) void ppo_l1_kernel(const PpoFusedParams q) {
     const float* bias = th + pf_off(q, net, 1);
     const int n = n0 + lrow;
     // states rows are din long, W1 has kin >= din rows of which the last kin - din are zero (and stay zero: their gradient is never formed): a k past
-    // din reads the next row's finite values against a zero weight row; past the tensors the range check returns 0.0
+    // din reads the next row's values against a zero weight row -- the load is issued and its value dropped, as in ppo_l1_wide_kernel, so that a NaN in a table
+    // row the index does not name stays out (NaN x 0; the demonstration tables of mi_ppo_clone_step); past the tensors the range check returns 0.0
     // (with a row index: the state table has n_rows rows and sample m is its row row_idx[m] -- one dependent load per lane in front of the operand loads)
     const int mrow = min(m0 + lrow, q.M - 1);
     const int srow = q.row_idx ? min(max(q.row_idx[mrow], 0), q.n_rows - 1) : mrow;
@@ -156,9 +159,9 @@ __global__ __launch_bounds__(256) void ppo_l1_kernel(const PpoFusedParams q) {
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     if constexpr (X3) {
         pf_mma_x3_chunked<5>(0, (q.kin + 15) / 16,
-            [&](int s_) { const unsigned k = (unsigned)(s_ * 16 + lgrp * 8); f32x8_t a;
+            [&](int s_) { const int k = s_ * 16 + lgrp * 8; f32x8_t a;
 #pragma unroll
-                          for (int e = 0; e < 8; ++e) a[e] = pf_ld(rsS, (arow + k + e) * 4u);
+                          for (int e = 0; e < 8; ++e) { const float x = pf_ld(rsS, (arow + (unsigned)(k + e)) * 4u); a[e] = k + e < q.din ? x : 0.f; }
                           return a; },
             [&](int s_) { const unsigned k = (unsigned)(s_ * 16 + lgrp * 8); f32x8_t b;
 #pragma unroll
@@ -166,9 +169,9 @@ __global__ __launch_bounds__(256) void ppo_l1_kernel(const PpoFusedParams q) {
                           return b; }, acc);
     } else {
     pf_mma_chunked<9>(0, (q.kin + 7) / 8,
-        [&](int s_) { const unsigned k = (unsigned)(s_ * 8 + lgrp * 4); f32x4 a;
+        [&](int s_) { const int k = s_ * 8 + lgrp * 4; f32x4 a;
 #pragma unroll
-                      for (int e = 0; e < 4; ++e) a[e] = pf_ld(rsS, (arow + k + e) * 4u);
+                      for (int e = 0; e < 4; ++e) { const float x = pf_ld(rsS, (arow + (unsigned)(k + e)) * 4u); a[e] = k + e < q.din ? x : 0.f; }
                       return a; },
         [&](int s_) { const unsigned k = (unsigned)(s_ * 8 + lgrp * 4); f32x4 b;
 #pragma unroll
@@ -600,6 +603,182 @@ template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kl_kernel
 template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kl_vclip_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, true, true>(q); }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// CLONE (ppo_head_clone_kernel; mi_ppo_clone_step): behaviour cloning, the supervised form of the head / loss kernel.  A body of its own, so that the eight
+// instantiations above stay as they are.  q.actions holds the EXPERT's actions a_E (a table with row_idx), q.clone the kind + 1, q.returns the returns or nullptr.
+// Per sample m and action a, with t = tanh(u), mean = lo + (t + 1) / 2 (hi - lo), sigma = exp(logstd[a]), z = (a_E - mean) / sigma:
+//   kind 0 "nll":  l[m] = sum_a (z^2 / 2 + logstd[a] + log(2 pi) / 2) ;  dl/du = -(z / sigma) (hi - lo) / 2 (1 - t^2) ;  dl/dlogstd[a] = 1 - z^2
+//   kind 1 "mse":  l[m] = sum_a (mean - a_E)^2 ;  dl/du = 2 (mean - a_E) (hi - lo) / 2 (1 - t^2) ;  dl/dlogstd = 0 exactly
+//   value term (only with returns): value_scale (V - R)^2 ,  dV = 2 value_scale (V - R) inv_m          -- the arithmetic of ppo_head_loss_body, operation for operation
+//   clone_loss = inv_m sum_m l[m] ,  loss = clone_loss + value_loss
+// No old policy, no advantage, no ratio, no clip, no entropy term (the call's entropy_scale is 0: ppo_wgrad_kernel's spare wave adds nothing to the logstd
+// gradient).  Partial slots: 0 l[m], 1 (V - R)^2, 2 sum_a (mean - a_E)^2 in BOTH kinds (mean_sq_error), 3 + a dl/dlogstd[a] inv_m, 3 + PF_MAX_ACT + a mean.
+// Without returns (policy only) nothing of the value net is read or written: no h2 row of net 1, no value head, no dv, no dh2 of net 1; slot 1 is 0.
+// As above: 8 lanes per sample, lane `part` owns action `part`, hardware transcendentals, fixed-order block sums, du / dv / dh2 for the chain behind.
+// ---------------------------------------------------------------------------------------------------------------------
+// VAL (returns given) is a template flag, not a test of q.returns: a uniform branch between the two nets' row loads makes the compiler wait for each pair of
+// 16-byte pieces before it requests the next (measured: + 2.6 us on a 39 us step at M = 32), where the straight-line form keeps all of them in flight.
+template <int NA, bool VAL>
+__global__ __launch_bounds__(256) void ppo_head_clone_kernel(const PpoFusedParams q) {
+    __shared__ __attribute__((aligned(16))) float sWm[PF_H2MAX * PF_MAX_ACT], sWv[PF_H2MAX];
+    __shared__ float su[32][NA], sv[32], sdu[32][NA], sdv[32], spart[32][PF_NPART];
+    const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
+    constexpr bool val = VAL;                             // the value net takes part
+    const bool mse = q.clone == 2;
+    const float* __restrict__ Wm = q.theta + q.off[4]; const float* __restrict__ bm = q.theta + q.off[5];
+    const float* __restrict__ Wv = q.theta + q.off[11]; const float* __restrict__ bv = q.theta + q.off[12];
+    const float* __restrict__ h2p = q.h2; const float* __restrict__ h2v = q.h2 + (long long)q.M * H2;
+    const int sm = tid >> 3, part = tid & 7, m = m0 + sm;
+    const bool mok = m < q.M;
+    constexpr int NV = (PF_H2MAX / 4 + 7) / 8;
+    const int nf = H2 >> 2;
+    f32x4 hp[NV], hv[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int f = part + 8 * i;
+        const bool ok = mok && f < nf;
+        hp[i] = ok ? *(const f32x4*)(h2p + (long long)m * H2 + 4 * f) : f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (VAL) hv[i] = ok ? *(const f32x4*)(h2v + (long long)m * H2 + 4 * f) : f32x4{0.f, 0.f, 0.f, 0.f};
+        else hv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    constexpr int NST = (PF_H2MAX * NA + 255) / 256;
+    float stm[NST], stv[(PF_H2MAX + 255) / 256];
+#pragma unroll
+    for (int i = 0; i < NST; ++i) { const int x = tid + 256 * i; stm[i] = x < H2 * A ? Wm[x] : 0.f; }
+#pragma unroll
+    for (int i = 0; i < (PF_H2MAX + 255) / 256; ++i) { const int x = tid + 256 * i; stv[i] = (val && x < H2) ? Wv[x] : 0.f; }
+    const int mr = (q.row_idx && mok) ? min(max(q.row_idx[m], 0), q.n_rows - 1) : m;     // the sample's row in the tables (expert actions / returns)
+    float act = 0.f, ls = 0.f, lo = 0.f, hi = 0.f, p_ret_s = 0.f;                        // lane `part`: its action's scalars
+    if (part < A) { ls = q.theta[q.off[6] + part]; lo = q.low[part]; hi = q.high[part]; if (mok) act = q.actions[(long long)mr * A + part]; }
+    if (val && mok) p_ret_s = q.returns[mr];
+#pragma unroll
+    for (int i = 0; i < NST; ++i) { const int x = tid + 256 * i; if (x < H2 * A) sWm[x] = stm[i]; }
+#pragma unroll
+    for (int i = 0; i < (PF_H2MAX + 255) / 256; ++i) { const int x = tid + 256 * i; if (x < H2) sWv[x] = stv[i]; }
+    __syncthreads();
+    {
+        float au[NA], av = 0.f;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) au[a] = 0.f;
+        if constexpr (NA == 2) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int f = min(part + 8 * i, nf - 1);  // (threads past the row re-read its last piece: their h2 registers are zero)
+                const f32x4 wv = *(const f32x4*)(sWv + 4 * f);
+                const f32x4 wa = *(const f32x4*)(sWm + 8 * f), wb = *(const f32x4*)(sWm + 8 * f + 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    av += hv[i][e] * wv[e];
+                    const float w0 = e < 2 ? wa[2 * e] : wb[2 * e - 4], w1 = e < 2 ? wa[2 * e + 1] : wb[2 * e - 3];
+                    au[0] += hp[i][e] * w0; au[NA > 1 ? 1 : 0] += hp[i][e] * w1;
+                }
+            }
+        } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int f = part + 8 * i;
+            if (f >= nf) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int j = 4 * f + e;
+                av += hv[i][e] * sWv[j];
+                _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) au[a] += hp[i][e] * sWm[j * A + a];
+            }
+        }
+        }
+#pragma unroll
+        for (int o = 4; o > 0; o >>= 1) {
+            av += __shfl_xor(av, o, 64);
+#pragma unroll
+            for (int a = 0; a < NA; ++a) au[a] += __shfl_xor(au[a], o, 64);
+        }
+        if (part == 0) {
+            sv[sm] = val ? av + bv[0] : 0.f;
+            _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) su[sm][a] = au[a] + bm[a];
+        }
+    }
+    __syncthreads();
+    {
+        auto fast_tanh = [](float x) { const float xc = fminf(fmaxf(x, -15.f), 15.f); return 1.0f - 2.0f / (__expf(2.0f * xc) + 1.0f); };
+        float l = 0.f, sq = 0.f, d = 0.f, dls = 0.f, mean = 0.f;
+        const bool aok = part < A && mok;
+        if (aok) {
+            const float t = fast_tanh(su[sm][part < NA ? part : 0]);
+            mean = lo + ((t + 1.0f) * 0.5f) * (hi - lo);
+            const float diff = mean - act, sl = (0.5f * (hi - lo)) * (1.0f - t * t);
+            sq = diff * diff;
+            if (mse) {
+                l = sq;
+                d = (2.0f * diff) * sl * q.inv_m;
+            } else {
+                const float sigma = __expf(ls);
+                const float z = (act - mean) / sigma;
+                l = 0.5f * z * z + (ls + PF_HALF_LOG_2PI);
+                d = -((z / sigma) * sl) * q.inv_m;
+                dls = (1.0f - z * z) * q.inv_m;
+            }
+            if (q.mean_out) q.mean_out[(long long)m * A + part] = mean;
+        }
+#pragma unroll
+        for (int o = 4; o > 0; o >>= 1) { l += __shfl_xor(l, o, 64); sq += __shfl_xor(sq, o, 64); }
+        if (part < NA) sdu[sm][part < NA ? part : 0] = aok ? d : 0.f;
+        if (aok) q.du[(long long)m * A + part] = d;
+        const float dvv = sv[sm] - p_ret_s;
+        const float dvm = (mok && val) ? 2.0f * q.value_scale * dvv * q.inv_m : 0.f;
+        const float lv = dvv * dvv;
+#pragma unroll
+        for (int k = part; k < PF_NPART; k += 8) spart[sm][k] = 0.f;
+        __builtin_amdgcn_wave_barrier();
+        if (part == 0) {
+            sdv[sm] = dvm;
+            if (mok) { if (val) q.dv[m] = dvm; spart[sm][0] = l; spart[sm][1] = val ? lv : 0.f; spart[sm][2] = sq; }
+        }
+        if (aok) { spart[sm][3 + part] = dls; spart[sm][3 + PF_MAX_ACT + part] = mean; }
+    }
+    __syncthreads();
+    if (tid < PF_NPART) {                                 // fixed-order block partial sums
+        float sum = 0.f;
+        for (int i = 0; i < 32; ++i) sum += spart[i][tid];
+        q.partial[(long long)blockIdx.x * PF_NPART + tid] = sum;
+    }
+    // ---- head input gradients of this thread's columns of its sample, masked by relu'(h2): from the rows still held in registers ----
+    if (mok) {
+        float* dh2p = q.dh2 + (long long)m * H2; float* dh2v = q.dh2 + (long long)q.M * H2 + (long long)m * H2;
+        float dus[NA];
+        _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) dus[a] = sdu[sm][a];
+        const float dvs = sdv[sm];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int f = part + 8 * i;
+            if (f >= nf) continue;
+            f32x4 gp, gv;
+            if constexpr (NA == 2) {
+                const f32x4 wv = *(const f32x4*)(sWv + 4 * f);
+                const f32x4 wa = *(const f32x4*)(sWm + 8 * f), wb = *(const f32x4*)(sWm + 8 * f + 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float w0 = e < 2 ? wa[2 * e] : wb[2 * e - 4], w1 = e < 2 ? wa[2 * e + 1] : wb[2 * e - 3];
+                    float sa = dus[0] * w0;
+                    sa += dus[NA > 1 ? 1 : 0] * w1;
+                    gp[e] = hp[i][e] > 0.f ? sa : 0.f;
+                    gv[e] = hv[i][e] > 0.f ? dvs * wv[e] : 0.f;
+                }
+            } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int j = 4 * f + e;
+                float sa = 0.f;
+                _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) sa += dus[a] * sWm[j * A + a];
+                gp[e] = hp[i][e] > 0.f ? sa : 0.f;
+                gv[e] = hv[i][e] > 0.f ? dvs * sWv[j] : 0.f;
+            }
+            }
+            *(f32x4*)(dh2p + 4 * f) = gp;
+            if (val) *(f32x4*)(dh2v + 4 * f) = gv;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // input gradient of layer 2: grid (ceil(H1 / 32), 2 nets, ceil(M / 32)); block = a 32 x 32 tile of
 //   dh1[m, k] = (sum_n dh2[m, n] W2[k, n]) * relu'(h1[m, k])      the four waves split the 300 columns, partial tiles meet in LDS
 // (its own launch: the weight-gradient kernel below updates W2 in place, this one still reads it)
@@ -669,8 +848,9 @@ __global__ __launch_bounds__(256) void ppo_wgrad_kernel(const PpoFusedParams q) 
     const bool split = !FUSE && q.m_chunk > 0;            // large minibatches: blockIdx.y = row chunk
     float* const gb = split ? q.gslab + (long long)blockIdx.y * q.gslab_stride : q.grads;      // where this wave's gradients go: the chunk's slab (every element of a slab
                                                                                                // is written by exactly one wave; an ordered pass adds the slabs) or the buffer
-    if (t == 2 * per_net && blockIdx.y != 0) return;
-    if (t == 2 * per_net) {                               // spare wave: loss scalars + logstd (fixed block order: deterministic)
+    const int spare = q.n_wnets * per_net;                // (n_wnets: 2, or 1 for the policy-only clone step -- net 0's tiles, then the spare wave)
+    if (t == spare && blockIdx.y != 0) return;
+    if (t == spare) {                               // spare wave: loss scalars + logstd (fixed block order: deterministic)
         // lane k sums column k of the per-block partials (one load chain per lane instead of PF_NPART chains on lane 0: this wave's latency was
         // the kernel's duration), lane 0 collects them with shuffles; exp / log through the hardware units (arguments O(1), ~1e-7 relative)
         float col = 0.f;
@@ -688,7 +868,7 @@ __global__ __launch_bounds__(256) void ppo_wgrad_kernel(const PpoFusedParams q) 
         if (lane != 0) return;
         const float pl = sum[0] * q.inv_m, vl = sum[1] * q.inv_m * q.value_scale, el = ent * q.entropy_scale;
         float* L = q.losses;                               // [0..4] policy, value, entropy, total, mean ratio ; [5..5+A) mean action_mean ; [5+A..5+2A) std
-        L[0] = pl; L[1] = vl; L[2] = el; L[3] = -pl + vl - el; L[4] = sum[2] * q.inv_m;
+        L[0] = pl; L[1] = vl; L[2] = el; L[3] = q.clone ? pl + vl : -pl + vl - el; L[4] = sum[2] * q.inv_m;      // (clone step: [clone_loss, value_loss, 0, loss, mean_sq_error])
 #pragma unroll
         for (int a = 0; a < PF_MAX_ACT; ++a) if (a < q.A) { L[5 + a] = sum[3 + PF_MAX_ACT + a] * q.inv_m; L[5 + q.A + a] = sd[a]; }
         if (q.kl_on) {                                    // [5+2A] mean KL(pi_old || pi), [5+2A+1] beta x that, which the total loss also takes
@@ -700,7 +880,7 @@ __global__ __launch_bounds__(256) void ppo_wgrad_kernel(const PpoFusedParams q) 
         for (int a = 0; a < PF_MAX_ACT; ++a) if (a < q.A) pf_emit<FUSE>(q, q.off[6] + a, sum[3 + a] - q.entropy_scale * q.grad_scale, gb);
         return;
     }
-    if (t > 2 * per_net) return;
+    if (t > spare) return;
     const int net = t >= per_net ? 1 : 0;
     t -= net * per_net;
     // ---- which tile ----
@@ -1122,12 +1302,21 @@ int mi_ppo_fused_step(hipStream_t st, PpoFusedParams& q, int fuse_adam, bool x3)
     if (fuse_adam && q.M > 256) return mi_fail(MI_ERR_ARG, "ppo fused step: the in-kernel Adam update needs the whole minibatch in one wave (M <= 256)");
     if (q.kl_on && (!q.kl_partial || (q.logp_old != nullptr) != (q.mean_old != nullptr)))
         return mi_fail(MI_ERR_ARG, "ppo fused step: the KL penalty needs its partial buffer, and logp_old / mean_old both or neither");
+    if (q.n_wnets != 1 && q.n_wnets != 2) return mi_fail(MI_ERR_ARG, "ppo fused step: n_wnets is 2, or 1 for the policy-only clone step");
+    if (q.n_wnets == 1 && !(q.clone && !q.returns)) return mi_fail(MI_ERR_ARG, "ppo fused step: only the clone step without returns leaves the value net out");
     q.n_loss_blocks = (q.M + 31) / 32;
     int rc = mi_ppo_fused_trunks(st, q, x3);
     if (rc != MI_OK) return rc;
     rc = ppo_pad(st, q.losses);
     if (rc != MI_OK) return rc;
-    if (q.kl_on) {                                        // the KL-penalised surrogate (mi_ppo_train_step_kl), with or without the clipped value loss
+    if (q.clone) {                                        // behaviour cloning (mi_ppo_clone_step): its own head / loss kernel, the same chain behind it
+        const dim3 g(q.n_loss_blocks), b(256);
+        if (q.returns) {
+            if (q.A == 2) hipLaunchKernelGGL((ppo_head_clone_kernel<2, true>), g, b, 0, st, q);
+            else hipLaunchKernelGGL((ppo_head_clone_kernel<PF_MAX_ACT, true>), g, b, 0, st, q);
+        } else if (q.A == 2) hipLaunchKernelGGL((ppo_head_clone_kernel<2, false>), g, b, 0, st, q);
+        else hipLaunchKernelGGL((ppo_head_clone_kernel<PF_MAX_ACT, false>), g, b, 0, st, q);
+    } else if (q.kl_on) {                                        // the KL-penalised surrogate (mi_ppo_train_step_kl), with or without the clipped value loss
         const dim3 g(q.n_loss_blocks), b(256);
         if (q.v_old) {
             if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_kl_vclip_kernel<2>, g, b, 0, st, q);
@@ -1139,12 +1328,12 @@ int mi_ppo_fused_step(hipStream_t st, PpoFusedParams& q, int fuse_adam, bool x3)
         else hipLaunchKernelGGL(ppo_head_loss_vclip_kernel<PF_MAX_ACT>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);
     } else if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_kernel<2>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);     // (action loops are compile-time unrolled)
     else hipLaunchKernelGGL(ppo_head_loss_kernel<PF_MAX_ACT>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);
-    if (x3) hipLaunchKernelGGL(ppo_dh1_kernel<true>, dim3((q.H1 + 31) / 32, 2, (q.M + 31) / 32), dim3(256), 0, st, q);
-    else hipLaunchKernelGGL(ppo_dh1_kernel<false>, dim3((q.H1 + 31) / 32, 2, (q.M + 31) / 32), dim3(256), 0, st, q);
+    if (x3) hipLaunchKernelGGL(ppo_dh1_kernel<true>, dim3((q.H1 + 31) / 32, q.n_wnets, (q.M + 31) / 32), dim3(256), 0, st, q);
+    else hipLaunchKernelGGL(ppo_dh1_kernel<false>, dim3((q.H1 + 31) / 32, q.n_wnets, (q.M + 31) / 32), dim3(256), 0, st, q);
     rc = ppo_pad(st, q.losses);
     if (rc != MI_OK) return rc;
     const int nt1 = (q.H1 + 31) / 32, nt2 = (q.H2 + 31) / 32, kt1 = (q.kin + 31) / 32;
-    const int tiles = 2 * (nt1 * nt2 + kt1 * nt1 + nt2) + 1;         // + the wave that finalises the loss scalars
+    const int tiles = q.n_wnets * (nt1 * nt2 + kt1 * nt1 + nt2) + 1;         // + the wave that finalises the loss scalars
     q.m_chunk = 0;
     if (fuse_adam) {
         if (x3) hipLaunchKernelGGL((ppo_wgrad_kernel<true, true>), dim3((tiles + 3) / 4), dim3(256), 0, st, q);
@@ -1160,7 +1349,12 @@ int mi_ppo_fused_step(hipStream_t st, PpoFusedParams& q, int fuse_adam, bool x3)
         const int rc2 = mi_check_launch("ppo_fused_step");
         if (rc2 != MI_OK) return rc2;
         return mi_reduce_slabs(st, q.gslab, q.gslab_stride, chunks, q.n_params, q.grads, 1);
-    } else if (x3) hipLaunchKernelGGL((ppo_wgrad_kernel<false, true>), dim3((tiles + 3) / 4), dim3(256), 0, st, q);
-    else hipLaunchKernelGGL((ppo_wgrad_kernel<false, false>), dim3((tiles + 3) / 4), dim3(256), 0, st, q);
+    } else {
+        // policy only: nobody writes the value net's range of the gradient buffer (variables 7..12 lie behind 0..6): it is cleared, so that it reads exactly 0.0
+        if (q.n_wnets == 1 && hipMemsetAsync(q.grads + q.off[7], 0, (size_t)(q.n_params - q.off[7]) * 4, st) != hipSuccess)
+            return mi_fail(MI_ERR_LAUNCH, "ppo fused step: memset failed");
+        if (x3) hipLaunchKernelGGL((ppo_wgrad_kernel<false, true>), dim3((tiles + 3) / 4), dim3(256), 0, st, q);
+        else hipLaunchKernelGGL((ppo_wgrad_kernel<false, false>), dim3((tiles + 3) / 4), dim3(256), 0, st, q);
+    }
     return mi_check_launch("ppo_fused_step");
 }

@@ -41,8 +41,12 @@ struct PpoFusedParams {
     int kl_on; float kl_coef;
     int max_batch;                                        // the engine's, for the 2 GiB limit of the 32-bit byte offsets (host side only; in the padding behind kl_coef)
     const float* mean_old; float* kl_partial; float* mean_old_out;
+    // behaviour cloning (mi_ppo_clone_step; appended likewise).  clone: 0 = a PPO step, 1 + kind = the clone head / loss kernel runs (1 "nll", 2 "mse") with
+    // `actions` the expert's; returns == nullptr then means policy only.  n_wnets: the nets the backward half covers -- the layer-1 input-gradient grid and the
+    // weight-gradient tiles in front of the spare wave: 2 in every step but the policy-only clone step, which runs net 0 alone (1)
+    int clone, n_wnets;
 };
-static_assert(sizeof(PpoFusedParams) == 448, "PpoFusedParams: a field moved (the kernels' argument offsets are pinned by profiles/r28_ppo_wide_inputs.md)");
+static_assert(sizeof(PpoFusedParams) == 456, "PpoFusedParams: a field moved (the kernels' argument offsets are pinned by profiles/r28_ppo_wide_inputs.md)");
 
 }  // namespace mi
 

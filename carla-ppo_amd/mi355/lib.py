@@ -65,6 +65,19 @@ def kl_target_value(value, who="kl_target"):
     return float(value)
 
 
+CLONE_KINDS = {"nll": 0, "mse": 1}                # `kind` of mi_ppo_clone_step
+
+
+def clone_kind(loss, who="clone_step"):
+    """The loss of a behaviour-cloning step (mi_ppo_clone_step): "nll" or "mse" (or the C entry's 0 / 1) -> 0 / 1; anything else raises ValueError.  No device and
+    no library involved."""
+    if isinstance(loss, str) and loss in CLONE_KINDS:
+        return CLONE_KINDS[loss]
+    if not isinstance(loss, (bool, str)) and isinstance(loss, numbers.Integral) and int(loss) in (0, 1):
+        return int(loss)
+    raise ValueError('%s: the loss is "nll" (the Gaussian negative log-likelihood) or "mse" (the squared error of the action mean), got %r' % (who, loss))
+
+
 _CTYPES = {
     "void*": ctypes.c_void_p, "const void*": ctypes.c_void_p,
     "float*": ctypes.c_void_p, "const float*": ctypes.c_void_p,

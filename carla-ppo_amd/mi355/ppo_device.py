@@ -285,6 +285,24 @@ class PpoDevice:
                                     p(old_values), 0.0 if old_values is None else float(clip_range_vf), p(row_idx), int(states.shape[0]), int(M), float(inv_m),
                                     float(grad_scale), 1 if adam else 0, float(alpha), float(beta1), float(beta2), float(epsilon))
 
+    def clone_step(self, comm_handle, states, expert_actions, returns, kind, row_idx, M, inv_m, grad_scale, alpha,
+                   beta1=0.9, beta2=0.999, epsilon=1e-8, adam=True):
+        """One behaviour-cloning step (mi_ppo_clone_step): the policy is fitted to the expert's actions -- kind "nll" (the Gaussian negative log-likelihood, logstd
+        learns too) or "mse" (the squared error of the action mean, logstd gets a gradient of exactly 0) -- and, with `returns`, the value net to them; returns None
+        is the policy-only form, which neither runs nor touches the value net.  One entry for every form, as train_step_kl: row_idx None or an int32 device tensor
+        [M] naming rows of the tables states / expert_actions / returns; comm_handle None or a communicator; adam False stops with the gradients in the flat buffer.
+        `losses` then holds [clone_loss, value_loss, 0, loss, mean_sq_error] (clone_losses() reads them)."""
+        kind = milib.clone_kind(kind, "PpoDevice.clone_step")
+        self.ensure_batch(M)
+        p = milib.ptr
+        self.L.mi_ppo_clone_step(self.handle, comm_handle, self.stream(), p(states), p(expert_actions), p(returns), kind, p(row_idx), int(states.shape[0]), int(M),
+                                 float(inv_m), float(grad_scale), 1 if adam else 0, float(alpha), float(beta1), float(beta2), float(epsilon))
+
+    def clone_losses(self):
+        """{clone_loss, value_loss, loss, mean_sq_error} of the last clone_step (one readback)."""
+        L = self.losses[:5].cpu().numpy()
+        return {"clone_loss": float(L[0]), "value_loss": float(L[1]), "loss": float(L[3]), "mean_sq_error": float(L[4])}
+
     def kl_stats(self, states, mean_old, row_idx, M, stats, scratch, accumulate=False):
         """The N_KL_STATS sums of the exact KL(pi_old || pi_theta) (mi_ppo_kl_stats_idx; kl_stats_summary turns them into a dict) over rows `row_idx` (int32 device
         tensor [M]) of the tables states / mean_old under the CURRENT parameters, into `stats` (float64 device tensor [N_KL_STATS]; accumulate: added to it).

@@ -454,6 +454,73 @@ class PPO():
             out["kl"], out["kl_penalty"] = float(K[0]), float(K[1])
         return out
 
+    # ------------------------------------------------------------------ behaviour cloning
+    def _clone_kind(self, who, loss):
+        """What a clone step refuses without a device: the loss name, and a policy outside the fused kernels' range (there is no per-layer clone step).  -> kind"""
+        kind = milib.clone_kind(loss, who)
+        kin = (self.input_dim + 7) // 8 * 8
+        if not (1 <= self.num_actions <= 8 and kin <= (1024 if self.wide_inputs else 96)) or os.environ.get("MI355_PPO_FUSED", "1") == "0":
+            raise ValueError("%s: behaviour cloning exists only in the fused kernels (this policy's shape is outside their range (more than 96 inputs: "
+                             "PPO.set_wide_inputs()) or MI355_PPO_FUSED=0)" % who)
+        return kind
+
+    def _clone_dispatch(self, kind, s, a_e, r, rows, m_local, m_global, learning_rate=None):
+        """One clone step on device tensors: contiguous (rows None) or table rows; single rank or the library's communicator.  Adam's powers advance."""
+        dev, world = self.dev, midist.world_size()
+        comm = None if world == 1 else self._dp_comm()
+        if world > 1 and comm is None:
+            raise ValueError("PPO.clone_step: data parallel needs the library's communicator (the clone step is one C call)")
+        lr = self.current_learning_rate() if learning_rate is None else np.float32(learning_rate)
+        alpha = _adam_alpha(lr, self.beta1_power, self.beta2_power)
+        dev.clone_step(None if comm is None else comm.handle, s, a_e, r, kind, rows, m_local, 1.0 / m_global, m_local / float(m_global), alpha,
+                       ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON)
+        self.beta1_power = np.float32(self.beta1_power * np.float32(ADAM_BETA1))
+        self.beta2_power = np.float32(self.beta2_power * np.float32(ADAM_BETA2))
+
+    def clone_step(self, input_states, expert_actions, returns=None, loss="nll", learning_rate=None):
+        """One behaviour-cloning SGD step on a minibatch of demonstrations (include/mi355_carla.h, mi_ppo_clone_step): the policy is fitted to the expert's actions
+        with loss "nll" (the Gaussian negative log-likelihood: action_logstd learns too) or "mse" (the squared error of the action mean: action_logstd keeps its
+        value); with `returns` the value net is fitted to them as in train(), without them it is neither run nor changed.  Like train_step: host arrays in, one
+        step, Adam's powers and train_step_counter advance; data parallel, every rank passes its rows.  learning_rate None: current_learning_rate().
+        -> {clone_loss, value_loss, loss, mean_sq_error}.  Refused before anything touches a device: an unknown loss, mismatched shapes, expert actions that are
+        not finite, and a policy outside the fused kernels' range."""
+        kind = self._clone_kind("PPO.clone_step", loss)
+        s = np.asarray(input_states, np.float32)
+        a_e = np.asarray(expert_actions, np.float32)
+        m = s.shape[0] if s.ndim == 2 else 0
+        if m < 1 or s.shape != (m, self.input_dim):
+            raise ValueError("PPO.clone_step: input_states has shape %s, expected [M, %d] with M >= 1" % (s.shape, self.input_dim))
+        if a_e.shape != (m, self.num_actions):
+            raise ValueError("PPO.clone_step: expert_actions has shape %s, expected %s" % (a_e.shape, (m, self.num_actions)))
+        if not np.isfinite(a_e).all():
+            raise ValueError("PPO.clone_step: expert_actions holds values that are not finite")
+        if returns is not None:
+            returns = np.asarray(returns, np.float32)
+            if returns.reshape(-1).shape != (m,):
+                raise ValueError("PPO.clone_step: returns has shape %s, expected [%d]" % (returns.shape, m))
+        if learning_rate is not None and not (isinstance(learning_rate, (int, float, np.floating)) and not isinstance(learning_rate, bool) and 0 < learning_rate < float("inf")):
+            raise ValueError("PPO.clone_step: learning_rate is None or a finite float > 0, got %r" % (learning_rate,))
+        self._need_dev()
+        self._clone_dispatch(kind, self._to_dev(s, (m, self.input_dim)), self._to_dev(a_e, (m, self.num_actions)),
+                             None if returns is None else self._to_dev(returns, (m,)), None, m, m * midist.world_size(), learning_rate)
+        self.train_step_counter += 1
+        L = self._global_clone_losses()
+        return dict(clone_loss=float(L[0]), value_loss=float(L[1]), loss=float(L[3]), mean_sq_error=float(L[4]))
+
+    def _clone_rows(self, s_all, a_all, r_all, rows, m_local, m_global, loss="nll", learning_rate=None):
+        """One clone step on rows `rows` (int32 device tensor) of device-resident tables states / expert actions / returns (r_all None: policy only): the gather
+        runs inside the step's kernels.  Adam's powers advance; the counters are the caller's."""
+        kind = self._clone_kind("PPO._clone_rows", loss)
+        self._need_dev()
+        self._clone_dispatch(kind, s_all, a_all, r_all, rows, m_local, m_global, learning_rate)
+
+    def _global_clone_losses(self):
+        """The loss scalars of the last clone step; data parallel: the device holds this rank's share of the batch means, summed here (COLLECTIVE)."""
+        L = self.dev.losses[:5].clone()
+        if midist.world_size() > 1:
+            midist.all_reduce_sum(L)
+        return L.cpu().numpy()
+
     def update_old_policy(self):
         self._need_dev().update_old()
 

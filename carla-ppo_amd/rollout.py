@@ -251,6 +251,12 @@ entry, has no stacked form (RolloutStep.stacked raises ValueError: use BatchedRo
 is allocated and every call makes the launches it always made.
 
 Single rank only (ragged rows give ranks different numbers of gradient all-reduces).
+
+DemonstrationBuffer(vae, ppo, capacity, chunk=64) is the warm start in front of all this: behaviour cloning from (camera frame, measurements, expert action[, return])
+rows -- CARLA's autopilot, a human driver.  add() encodes the frames with the batched recording step (greedy, at most `chunk` per call) into a device table of
+state rows, clone() runs epochs of shuffled minibatches through PPO._clone_rows (mi_ppo_clone_step: the fused chain with a supervised head / loss kernel, loss "nll"
+or "mse"; the value net is fitted if and only if returns were added, and is otherwise neither run nor touched), evaluate() scores the policy against the expert in
+float64 on the host.  Single rank; no latent stacking.
 """
 import contextlib
 import os
@@ -1631,3 +1637,175 @@ class ContinuousRolloutBuffer(RolloutBuffer):
             final[truncs] = self.final_values.view(self.num_envs, self.horizon + 1)[:, :self.horizon].cpu().numpy()[truncs]
         out["final_values"] = final
         return out
+
+
+class _DemonstrationStep(BatchedRolloutStep):
+    """The step of a DemonstrationBuffer: the recording step under the buffer's name."""
+
+    _who = "DemonstrationBuffer"
+    _row_ints = 1
+
+
+def clone_losses_of(records):
+    """The loss records of clone steps (the first five floats of the losses buffer each) -> [{clone_loss, value_loss, loss, mean_sq_error}, ...]."""
+    return [{"clone_loss": float(r[0]), "value_loss": float(r[1]), "loss": float(r[3]), "mean_sq_error": float(r[4])} for r in records]
+
+
+class DemonstrationBuffer:
+    """Behaviour cloning from demonstrations (CARLA's autopilot, a human driver): up to `capacity` (camera frame, measurements, expert action[, return]) rows.
+    add() turns the frames into the policy's state rows on the device -- the batched recording step, greedy, in chunks of at most `chunk` frames -- and keeps them in
+    the device table `states` [capacity, input_dim]; the expert's actions and the returns go to the tables `expert_actions` [capacity, A] and `returns` [capacity],
+    the policy's own greedy actions and values at recording time to `policy_actions` / `policy_values`.  clone() trains the policy on shuffled minibatches of the
+    rows (PPO._clone_rows: mi_ppo_clone_step with the in-kernel gather), and the value net if and only if returns were added; evaluate() scores the current policy
+    against the expert in float64.  Afterwards PPO training continues from the warm-started policy through a rollout buffer.  Latent stacking is not supported."""
+
+    def __init__(self, vae, ppo, capacity, chunk=64, seed=None, io=None):
+        import torch
+        for name, v, hi in (("capacity", capacity, 1 << 24), ("chunk", chunk, MAX_ENVS)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
+                raise ValueError("DemonstrationBuffer: %s is an int in [1, %d], got %r" % (name, hi, v))
+        self.capacity, self.chunk = int(capacity), int(chunk)
+        self.vae, self.ppo = vae, ppo
+        self._step = _DemonstrationStep(vae, ppo, self.chunk, seed=seed, io=io)     # (raises before anything touches a device where the sizes do not fit)
+        self.io, self.device, self.L = self._step.io, self._step.device, self._step.L
+        self.A = int(ppo.num_actions)
+        n = self.capacity
+        self.states = torch.zeros(n, int(ppo.input_dim), device=self.device)
+        self.policy_actions = torch.zeros(n, self.A, device=self.device)
+        self.policy_values = torch.zeros(n, device=self.device)
+        self.expert_actions = torch.zeros(n, self.A, device=self.device)
+        self.returns = torch.zeros(n, device=self.device)
+        self.raw_states = None                                                       # the raw rows beside normalised ones (set_observation_normalization)
+        self.reset()
+
+    @classmethod
+    def stacked(cls, vae, ppo, capacity, latent_stack, chunk=64, seed=None, io=None):
+        """The demonstration buffer has no stacked form: ValueError for anything but latent_stack = 1."""
+        if isinstance(latent_stack, (bool, np.bool_)) or not isinstance(latent_stack, (int, np.integer)) or int(latent_stack) != 1:
+            raise ValueError("DemonstrationBuffer: latent stacking is not supported (a stacked policy's demonstrations need their episodes' order): latent_stack must be 1")
+        return cls(vae, ppo, capacity, chunk=chunk, seed=seed, io=io)
+
+    def reset(self):
+        """Empties the buffer; the tables keep their contents and are overwritten by the next rows."""
+        self.size = 0
+        self.has_returns = None                                                      # None until the first add() decides it
+
+    def set_observation_normalization(self, state_dict):
+        """Frozen observation statistics (a rollout buffer's observation_normalization_state(); None: off) are applied at encoding time by every add() from now on:
+        `states` then holds the normalised rows, as the buffer that produced the statistics trains on, and `raw_states` the raw ones."""
+        import torch
+        self._step.set_observation_normalization(state_dict)
+        if state_dict is not None and self.raw_states is None:
+            self.raw_states = torch.zeros(self.capacity, int(self.ppo.input_dim), device=self.device)
+
+    def check_add(self, frames_u8, measurements, expert_actions, returns):
+        """The host-side checks of add() -> (frames, n, measurements, expert actions float32 [n, A], returns float32 [n] or None).  ValueError, before any launch."""
+        who = "DemonstrationBuffer.add"
+        f = np.asarray(frames_u8)
+        fb = self._step.frame_bytes
+        if f.dtype != np.uint8 or f.ndim < 1 or f.shape[0] < 1 or f.size != f.shape[0] * fb:
+            raise ValueError("%s: expected uint8 frames [n, ...] of %d bytes each, n >= 1" % (who, fb))
+        n = int(f.shape[0])
+        if self.size + n > self.capacity:
+            raise ValueError("%s: %d rows on top of %d exceed the capacity of %d" % (who, n, self.size, self.capacity))
+        meas = np.asarray(measurements, np.float64)
+        if meas.shape != (n, self._step.n_meas):
+            raise ValueError("%s: expected measurements [%d, %d]" % (who, n, self._step.n_meas))
+        a = np.asarray(expert_actions)
+        if a.dtype.kind not in "fiu" or a.shape != (n, self.A):
+            raise ValueError("%s: expected expert_actions [%d, %d]" % (who, n, self.A))
+        a = np.ascontiguousarray(a, np.float32)
+        if not np.isfinite(a).all():
+            raise ValueError("%s: expert_actions holds values that are not finite" % who)
+        lo, hi = np.asarray(self.ppo.action_low, np.float32), np.asarray(self.ppo.action_high, np.float32)
+        if (a < lo).any() or (a > hi).any():
+            raise ValueError("%s: expert_actions outside [action_low, action_high] = [%s, %s]: the expert's units are not the policy's" % (who, lo.tolist(), hi.tolist()))
+        if self.has_returns is not None and (returns is not None) != self.has_returns:
+            raise ValueError("%s: returns were %s by the earlier add() calls and are %s now: all rows carry returns or none does (reset() starts over)"
+                             % (who, "given" if self.has_returns else "not given", "given" if returns is not None else "not given"))
+        r = None
+        if returns is not None:
+            r = np.asarray(returns)
+            if r.dtype.kind not in "fiu" or r.reshape(-1).shape != (n,):
+                raise ValueError("%s: expected returns [%d]" % (who, n))
+            r = np.ascontiguousarray(r.reshape(-1), np.float32)
+            if not np.isfinite(r).all():
+                raise ValueError("%s: returns holds values that are not finite" % who)
+        return f.reshape(n, -1), n, meas, a, r
+
+    def add(self, frames_u8, measurements, expert_actions, returns=None):
+        """Appends n demonstration rows: frames_u8 uint8 [n, H, W, 3], measurements [n, k], expert_actions [n, A] inside [action_low, action_high], returns [n] or
+        None (for every add() alike).  -> the table rows, int64 [n]."""
+        import torch
+        f, n, meas, a, r = self.check_add(frames_u8, measurements, expert_actions, returns)
+        step, lo = self._step, self.size
+        for i in range(0, n, self.chunk):
+            c = min(self.chunk, n - i)
+            rows = np.arange(lo + i, lo + i + c, dtype=np.int32)
+            step.record(f[i:i + c], c, meas[i:i + c], None, True, table_rows=rows, states=self.states, actions=self.policy_actions, values=self.policy_values,
+                        raw_states=self.raw_states)
+        self.expert_actions[lo:lo + n].copy_(torch.from_numpy(a))
+        if r is not None:
+            self.returns[lo:lo + n].copy_(torch.from_numpy(r))
+        self.has_returns = r is not None
+        self.size = lo + n
+        return np.arange(lo, lo + n)
+
+    def clone(self, num_epochs=1, batch_size=32, loss="nll"):
+        """Epochs of np.random.shuffle'd minibatches over the rows (the legacy numpy RNG, as the rollout buffers; the last minibatch of an epoch may be partial), each
+        one PPO._clone_rows call.  The value net is fitted if and only if returns were added.  -> {"losses": [{clone_loss, value_loss, loss, mean_sq_error}, ...],
+        "samples"} and, with gradient clipping on, "grad_norms" / "clip_scales"."""
+        import torch
+        from mi355 import dist as midist
+        who = "DemonstrationBuffer"
+        if midist.world_size() > 1:
+            raise ValueError(who + ".clone: single rank only (ragged rows give ranks different numbers of gradient all-reduces)")
+        if isinstance(batch_size, (bool, np.bool_)) or isinstance(num_epochs, (bool, np.bool_)) or int(batch_size) < 1 or int(num_epochs) < 0:
+            raise ValueError(who + ".clone: batch_size >= 1 and num_epochs >= 0")
+        milib.clone_kind(loss, who + ".clone")
+        if self.size < 1:
+            raise ValueError(who + ".clone: the buffer is empty")
+        ppo, pdev, n, batch_size = self.ppo, self.ppo._need_dev(), self.size, int(batch_size)
+        returns = self.returns if self.has_returns else None
+        clip = ppo.max_grad_norm is not None
+        records, clips = [], []
+        for _ in range(int(num_epochs)):
+            indices = np.arange(n)
+            np.random.shuffle(indices)
+            perm = torch.from_numpy(indices.astype(np.int32)).to(self.device)
+            for i in range(0, n, batch_size):
+                mb = perm[i:i + batch_size]
+                m = int(mb.numel())
+                ppo._clone_rows(self.states, self.expert_actions, returns, mb, m, m, loss=loss)
+                ppo.train_step_counter += 1
+                records.append(pdev.losses[:5].clone())
+                if clip:
+                    clips.append(pdev.grad_clip.clone())
+        losses = torch.stack(records).cpu().numpy() if records else np.zeros((0, 5), np.float32)
+        out = {"losses": clone_losses_of(losses), "samples": n}
+        if clip:
+            gc = torch.stack(clips).cpu().numpy() if clips else np.zeros((0, 4), np.float32)
+            out["grad_norms"], out["clip_scales"] = gc[:, 0].astype(np.float32).copy(), gc[:, 1].astype(np.float32).copy()
+        return out
+
+    def evaluate(self):
+        """The current policy against the expert over all rows: PpoDevice.predict (greedy) in chunks -- theta_old and the training state are not touched --, then in
+        float64 on the host: {"samples", "nll": mean_m sum_a (z^2 / 2 + logstd + log(2 pi) / 2), "mean_sq_error": mean_m sum_a (mean - a_E)^2,
+        "max_abs_error": float64 [A], "means": float32 [n, A]}."""
+        import torch
+        if self.size < 1:
+            raise ValueError("DemonstrationBuffer.evaluate: the buffer is empty")
+        pdev, n = self.ppo._need_dev(), self.size
+        mean = torch.empty(n, self.A, device=self.device)
+        value = torch.empty(n, device=self.device)
+        chunk = max(self.chunk, 256)
+        for lo in range(0, n, chunk):
+            hi = min(lo + chunk, n)
+            pdev.predict(self.states[lo:hi], hi - lo, None, True, mean[lo:hi], value[lo:hi])
+        o, cnt = pdev.layout["policy/action_logstd"]
+        logstd = pdev.params[o:o + cnt].cpu().numpy().astype(np.float64)
+        mu, a_e = mean.cpu().numpy(), self.expert_actions[:n].cpu().numpy().astype(np.float64)
+        d = mu.astype(np.float64) - a_e
+        z = d / np.exp(logstd)
+        return {"samples": n, "nll": float((0.5 * z * z + logstd + 0.5 * np.log(2.0 * np.pi)).sum(axis=1).mean()), "mean_sq_error": float((d * d).sum(axis=1).mean()),
+                "max_abs_error": np.abs(d).max(axis=0), "means": mu}

@@ -769,6 +769,24 @@ int mi_ppo_old_policy_cache(void* h, void* stream, const float* states, const fl
 int mi_ppo_train_step_kl(void* h, void* comm, void* stream, const float* states, const float* actions, const float* returns, const float* advantage, const float* logp_old, const float* mean_old, float kl_coef, const float* old_values, float clip_range_vf, const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon);
 long long mi_ppo_kl_stats_scratch_doubles(int M);
 int mi_ppo_kl_stats_idx(void* h, void* stream, const float* states, const float* mean_old, const int* row_idx, int n_rows, int M, int accumulate, double* scratch, double* stats);
+/* behaviour cloning: one supervised step of the policy (and optionally the value net) on (state, expert action[, return]) rows -- the warm start from demonstrations
+ * in front of PPO.  The fused chain of the minibatch step with a head / loss kernel of its own (csrc/ppo_fused.hip, ppo_head_clone_kernel); no old policy, no
+ * advantage, no ratio, no clip, no entropy term.  Per sample m and action a, with t = tanh(u), mean = lo + (t + 1) / 2 (hi - lo), sigma = exp(logstd[a]),
+ * a_E the expert's action, z = (a_E - mean) / sigma:
+ *   kind 0 ("nll"): l[m] = sum_a (z^2 / 2 + logstd[a] + log(2 pi) / 2)      dl/du = -(z / sigma) (hi - lo) / 2 (1 - t^2)      dl/dlogstd[a] = 1 - z^2
+ *   kind 1 ("mse"): l[m] = sum_a (mean - a_E)^2                            dl/du = 2 (mean - a_E) (hi - lo) / 2 (1 - t^2)    dl/dlogstd = 0 exactly
+ *   with returns:   value_loss = value_scale mean_m (V - R)^2 ,  dV = 2 value_scale (V - R) inv_m       (the value side of the PPO step, operation for operation)
+ *   clone_loss = inv_m sum_m l[m] ,  loss = clone_loss + value_loss
+ * returns NULL is the policy-only form: the value net is not run, and its parameters and both of its Adam slots are bitwise unchanged on every route (the in-tile
+ * Adam, the flat buffer + Adam over the policy's prefix of it, clipping, a communicator, M > 256); with adam = 0 the value net's range of the gradient buffer is
+ * exactly 0.0.  One entry for every form, as mi_ppo_train_step_kl: row_idx NULL (contiguous tensors, n_rows ignored) or states / expert_actions / returns are tables
+ * of n_rows rows gathered in-kernel (rows clamped; rows that row_idx does not name are not read); comm NULL or a communicator; adam 0 / 1 on the routes of
+ * mi_ppo_train_step_kl.  Both precision modes; wide inputs as mi_ppo_set_wide_inputs routes them.  The losses buffer (mi_ppo_buffer(h, 0)) holds
+ *   [0] clone_loss   [1] value_loss (0 without returns)   [2] 0   [3] loss   [4] mean_sq_error = mean_m sum_a (mean - a_E)^2 (in both kinds)
+ * and behind them the mean action_mean [A] and std [A] as after every step.  MI_ERR_STATE: null handle, missing gradient / optimiser buffers; MI_ERR_ARG: M outside
+ * [1, max_batch], row_idx set with n_rows < 1, states or expert_actions NULL, kind not 0 / 1, adam not 0 / 1; MI_ERR_SHAPE: mi_ppo_fused_shape_ok(h) is 0 (there is
+ * no per-layer form).  A refused call writes nothing. */
+int mi_ppo_clone_step(void* h, void* comm, void* stream, const float* states, const float* expert_actions, const float* returns, int kind, const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon);
 /* advantages normalised PER MINIBATCH, inside the SGD loop — SB3's normalize_advantage, CleanRL's norm_adv; no reference counterpart in train.py, which normalises per
  * trajectory (train.py:176-177): one pass per epoch between the finish calls (mi_rollout_finish*, which leave the raw advantages in fp64) and the epoch's SGD steps, which
  * gather their advantage from an fp32 table by row index.  No engine handle.  adv_raw: fp64 [num_envs, T], the raw advantages (entries beyond a lane's length may hold
