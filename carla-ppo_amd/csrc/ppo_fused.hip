@@ -11,6 +11,15 @@
 // Behaviour cloning (mi_ppo_clone_step) is the same chain with ppo_head_clone_kernel in the third place -- a supervised loss on the expert's actions -- and, without
 // returns, with net 0 alone in every launch (PpoFusedParams::n_wnets).
 //
+// The head-level kernels are built from the helpers of ppo_head.hpp, each shared piece written once:
+//   ppo_head_loss_body (ppo_head_loss[_kl][_vclip]_kernel) and ppo_head_clone_kernel:  pf_head_rows, pf_stage_request / pf_stage_commit, pf_head_sums,
+//       pf_fast_tanh, pf_block_partials, pf_head_dh2; between them each kernel keeps only its own gathers and its per-sample loss terms.  The loss body's
+//       old-policy block also calls pf_mean_libm / pf_logp_term_libm
+//   ppo_predict_head_kernel, ppo_update_stats_head_kernel, ppo_kl_stats_head_kernel:  pf_head_sums_strided, pf_mean_libm, pf_logp_term_libm -- the one spelling the
+//       bit-for-bit contracts between these kernels and the loss body rest on (stated at those functions); the two statistics kernels end in pf_ordered_block_sum,
+//       and ppo_stats_reduce_kernel<N> runs behind either
+// On the host pf_step_head_kernel picks the step's head kernel from a table and pf_na_pick the NA of the other launches; the two rules differ on purpose (A = 1).
+//
 // All arithmetic is exact fp32 (v_mfma_f32_32x32x2_f32 = fmaf chains; 1e-4 parity with the oracle).  The split-bf16 mode (X3 = true: MI_BF16X3 through
 // mi_ppo_set_precision) instantiates the four GEMM kernels with three v_mfma_f32_32x32x16_bf16 per k-block of 16 instead; everything else is shared.  The step is latency bound (78 MFLOP,
 // 1.5 MB of weights): what matters is the number of dependent launches and that none of them serialises on one CU.  With FUSE_ADAM the
@@ -23,12 +32,9 @@
 #include "mi_internal.hpp"
 #include "mi355_carla.h"
 #include "ppo_fused.hpp"
+#include "ppo_head.hpp"
 
 namespace mi {
-
-constexpr float PF_HALF_LOG_2PI = 0.918938533204672741780329736406f;
-constexpr int PF_MAX_ACT = 8;
-constexpr int PF_NPART = 3 + 2 * PF_MAX_ACT;             // per loss block: policy sum, value sq sum, ratio sum, dlogstd[A], action-mean sums [A]
 
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
@@ -350,30 +356,19 @@ __global__ __launch_bounds__(256) void ppo_l2_kernel(const PpoFusedParams q) {
 // (tanhf, the cache kernel's spelling: both sources give the same mu_o).  lso comes from theta_old in both.  The block's sum of KL[m] (samples in order, one
 // thread) goes to q.kl_partial[block]; ppo_wgrad_kernel's spare wave adds those in block order.  beta = 0 measures: every added term is 0.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int PF_H2MAX = 320;                             // head kernels staged in LDS: H2 <= 320 (the reference: 300)
 template <int NA, bool VCLIP, bool KLP>
 __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
     __shared__ __attribute__((aligned(16))) float sWm[PF_H2MAX * PF_MAX_ACT], sWo[PF_H2MAX * PF_MAX_ACT], sWv[PF_H2MAX];
     __shared__ float su[32][NA], sv[32], sdu[32][NA], sdv[32], spart[32][PF_NPART];
     __shared__ float skl[KLP ? 32 : 1];                   // KLP: KL[m] of the block's samples
     const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
-    const float* __restrict__ Wm = q.theta + q.off[4]; const float* __restrict__ bm = q.theta + q.off[5];
-    const float* __restrict__ Wmo = q.theta_old + q.off[4]; const float* __restrict__ bmo = q.theta_old + q.off[5];
-    const float* __restrict__ Wv = q.theta + q.off[11]; const float* __restrict__ bv = q.theta + q.off[12];
-    const float* __restrict__ h2p = q.h2; const float* __restrict__ h2v = q.h2 + (long long)q.M * H2; const float* __restrict__ h2o = q.h2 + 2ll * q.M * H2;
+    const float* __restrict__ bm = q.theta + q.off[5]; const float* __restrict__ bmo = q.theta_old + q.off[5]; const float* __restrict__ bv = q.theta + q.off[12];
+    const float* __restrict__ h2o = q.h2 + 2ll * q.M * H2;
     const bool old_net = q.logp_old == nullptr;
     const int sm = tid >> 3, part = tid & 7, m = m0 + sm;
     const bool mok = m < q.M;
-    constexpr int NV = (PF_H2MAX / 4 + 7) / 8;            // float4 pieces per thread and row (10)
-    const int nf = H2 >> 2;                               // float4 per row (H2 % 4 == 0)
-    f32x4 hp[NV], hv[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int f = part + 8 * i;
-        const bool ok = mok && f < nf;
-        hp[i] = ok ? *(const f32x4*)(h2p + (long long)m * H2 + 4 * f) : f32x4{0.f, 0.f, 0.f, 0.f};
-        hv[i] = ok ? *(const f32x4*)(h2v + (long long)m * H2 + 4 * f) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+    f32x4 hp[PF_NV], hv[PF_NV];
+    pf_head_rows<PF_NV, true>(q, m, mok, part, hp, hv);
     // the old policy's row (only without a cached log pi_old), requested with the others: this thread's columns are j = part, part + 8, .. as in the kernel that
     // fills the cache (see the head sums below), so single floats instead of 16-byte pieces
     constexpr int NH = PF_H2MAX / 8;                      // columns per thread (40)
@@ -386,12 +381,8 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
         for (int k = 0; k < NH; ++k) ho[k] = 0.f;
     }
     // head kernels -> LDS through registers (all requests in flight together), and the per-sample scalars the loss thread will need
-    constexpr int NST = (PF_H2MAX * NA + 255) / 256;
-    float stm[NST], sto[NST], stv[(PF_H2MAX + 255) / 256];
-#pragma unroll
-    for (int i = 0; i < NST; ++i) { const int x = tid + 256 * i; stm[i] = x < H2 * A ? Wm[x] : 0.f; sto[i] = (old_net && x < H2 * A) ? Wmo[x] : 0.f; }
-#pragma unroll
-    for (int i = 0; i < (PF_H2MAX + 255) / 256; ++i) { const int x = tid + 256 * i; stv[i] = x < H2 ? Wv[x] : 0.f; }
+    PfHeadStage<NA> st;
+    pf_stage_request<NA, true, true>(q, tid, old_net, st);
     float p_act[NA], p_adv_s = 0.f, p_ret_s = 0.f, p_lpo_s = 0.f, p_vold_s = 0.f, p_muo_s = 0.f, p_ls[NA], p_lso[NA], p_lo[NA], p_hi[NA];
     const int mr = (q.row_idx && mok) ? min(max(q.row_idx[m], 0), q.n_rows - 1) : m;     // the sample's row in the horizon-batch tables (actions / returns / advantages / cached log pi_old)
 #pragma unroll
@@ -404,47 +395,18 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
     if (mok) { p_adv_s = q.adv[mr]; p_ret_s = q.returns[mr]; if (!old_net) p_lpo_s = q.logp_old[mr]; }
     if constexpr (VCLIP) { if (mok) p_vold_s = q.v_old[mr]; }
     if constexpr (KLP) { if (mok && !old_net && part < A) p_muo_s = q.mean_old[(long long)mr * A + part]; }
-#pragma unroll
-    for (int i = 0; i < NST; ++i) { const int x = tid + 256 * i; if (x < H2 * A) { sWm[x] = stm[i]; sWo[x] = sto[i]; } }
-#pragma unroll
-    for (int i = 0; i < (PF_H2MAX + 255) / 256; ++i) { const int x = tid + 256 * i; if (x < H2) sWv[x] = stv[i]; }
+    pf_stage_commit<NA, true>(q, tid, st, sWm, sWo, sWv);
     __syncthreads();
     float lp_old_s = 0.f;
     {
-        float au[NA], ao[NA], av = 0.f;
+        float au[NA], ao[NA], av;
 #pragma unroll
-        for (int a = 0; a < NA; ++a) { au[a] = 0.f; ao[a] = 0.f; }
-        if constexpr (NA == 2) {                          // exactly two actions (the reference; the host picks this instantiation only then): head-kernel rows of 4 consecutive j are two 16-byte LDS reads
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int f = min(part + 8 * i, nf - 1);  // (threads past the row re-read its last piece: their h2 registers are zero)
-                const f32x4 wv = *(const f32x4*)(sWv + 4 * f);
-                const f32x4 wa = *(const f32x4*)(sWm + 8 * f), wb = *(const f32x4*)(sWm + 8 * f + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    av += hv[i][e] * wv[e];
-                    const float w0 = e < 2 ? wa[2 * e] : wb[2 * e - 4], w1 = e < 2 ? wa[2 * e + 1] : wb[2 * e - 3];
-                    au[0] += hp[i][e] * w0; au[NA > 1 ? 1 : 0] += hp[i][e] * w1;
-                }
-            }
-        } else {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int f = part + 8 * i;
-            if (f >= nf) continue;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int j = 4 * f + e;
-                av += hv[i][e] * sWv[j];
-                _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) au[a] += hp[i][e] * sWm[j * A + a];
-            }
-        }
-        }
-        // the old policy's log pi_old is spelled as ppo_predict_head_kernel<NA, 3> spells the cache of it (mi_ppo_logp_old): columns j = part, part + 8, .. of the
-        // row in ascending order against the old head kernel (here from LDS: the same values), the same shuffles, then libm tanhf / expf / logf and a serial sum
-        // over the actions -- so that the step gives the same parameters whether log pi_old comes from the cache or from here (in another order the two differ by
-        // an ulp of log pi_old, and Adam's first step multiplies what that does to a gradient near zero by lr / 3.2e-7).  The price is paid only without a cache:
-        // up to A libm chains per thread where the new policy's terms go through the hardware units (see below)
+        for (int a = 0; a < NA; ++a) ao[a] = 0.f;
+        pf_head_sums<NA, PF_NV, false>((pf_lds_cf*)sWm, (pf_lds_cf*)sWv, hp, hv, part, H2 >> 2, A, au, av);
+        // the old policy's log pi_old and means, in the strided form that fills the caches of them (the contracts: ppo_head.hpp): columns j = part, part + 8, ..
+        // of the row in ascending order against the old head kernel (here from LDS: the same values), pf_head_sums_strided's shuffles, then the libm spellings
+        // and a serial sum over the actions.  The price is paid only without a cache: up to A libm chains per thread where the new policy's terms go through
+        // the hardware units (see below)
         if (old_net && mok) {
 #pragma unroll
             for (int k = 0; k < NH; ++k) {
@@ -454,7 +416,7 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
             }
         }
 #pragma unroll
-        for (int o = 4; o > 0; o >>= 1) {
+        for (int o = 4; o > 0; o >>= 1) {                 // (pf_head_sums' rounds, MEET = false, with ao in them: see there)
             av += __shfl_xor(av, o, 64);
 #pragma unroll
             for (int a = 0; a < NA; ++a) { au[a] += __shfl_xor(au[a], o, 64); ao[a] += __shfl_xor(ao[a], o, 64); }
@@ -462,11 +424,8 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
         if (old_net) {                                    // (all 8 threads of a sample hold the same sums and form the same value)
             float lp = 0.f;
             _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) {
-                const float lo = p_lo[a], hi = p_hi[a];
-                const float mean = lo + ((tanhf(ao[a] + bmo[a]) + 1.0f) * 0.5f) * (hi - lo);
-                const float sigma = expf(p_lso[a]);
-                const float z = (p_act[a] - mean) / sigma;
-                lp += -0.5f * z * z - (PF_HALF_LOG_2PI + logf(sigma));
+                const float mean = pf_mean_libm(ao[a], bmo[a], p_lo[a], p_hi[a]);
+                lp += pf_logp_term_libm(p_act[a], mean, p_lso[a]);
                 if constexpr (KLP) { if (a == part) p_muo_s = mean; }
             }
             lp_old_s = lp;
@@ -481,7 +440,6 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
     //      exp / log / tanh through the hardware transcendental units (v_exp_f32 / v_log_f32: ~1 ulp; tanh(u) = 1 - 2 / (e^2u + 1)): the
     //      libm sequences are ~100-instruction dependent chains, which at one wave per block was most of this kernel ----
     {
-        auto fast_tanh = [](float x) { const float xc = fminf(fmaxf(x, -15.f), 15.f); return 1.0f - 2.0f / (__expf(2.0f * xc) + 1.0f); };
         float lp_n = 0.f, dl = 0.f, zsq = 0.f, mean = 0.f;
         float act = 0.f, ls = 0.f, lo = 0.f, hi = 0.f;
         float lso = 0.f, kl = 0.f, kdu = 0.f, kdls = 0.f;  // KLP: this lane's old logstd, KL[m,part] and the penalty's du / dlogstd terms (without beta inv_m)
@@ -489,7 +447,7 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
         for (int a = 0; a < NA; ++a) if (a == part) { act = p_act[a]; ls = p_ls[a]; lo = p_lo[a]; hi = p_hi[a]; if constexpr (KLP) lso = p_lso[a]; }
         const bool aok = part < A && mok;
         if (aok) {
-            const float t = fast_tanh(su[sm][part < NA ? part : 0]);
+            const float t = pf_fast_tanh(su[sm][part < NA ? part : 0]);
             mean = lo + ((t + 1.0f) * 0.5f) * (hi - lo);
             const float sigma = __expf(ls);
             const float z = (act - mean) / sigma;
@@ -548,11 +506,7 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
         }
     }
     __syncthreads();
-    if (tid < PF_NPART) {                                 // fixed-order block partial sums
-        float sum = 0.f;
-        for (int i = 0; i < 32; ++i) sum += spart[i][tid];
-        q.partial[(long long)blockIdx.x * PF_NPART + tid] = sum;
-    }
+    pf_block_partials(q, spart, tid);
     if constexpr (KLP) {
         if (tid == 32) {                                  // the block's KL sum, samples in order
             float sum = 0.f;
@@ -560,42 +514,7 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
             q.kl_partial[blockIdx.x] = sum;
         }
     }
-    // ---- head input gradients of this thread's columns of its sample, masked by relu'(h2): from the rows still held in registers ----
-    if (mok) {
-        float* dh2p = q.dh2 + (long long)m * H2; float* dh2v = q.dh2 + (long long)q.M * H2 + (long long)m * H2;
-        float dus[NA];
-        _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) dus[a] = sdu[sm][a];
-        const float dvs = sdv[sm];
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int f = part + 8 * i;
-            if (f >= nf) continue;
-            f32x4 gp, gv;
-            if constexpr (NA == 2) {
-                const f32x4 wv = *(const f32x4*)(sWv + 4 * f);
-                const f32x4 wa = *(const f32x4*)(sWm + 8 * f), wb = *(const f32x4*)(sWm + 8 * f + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float w0 = e < 2 ? wa[2 * e] : wb[2 * e - 4], w1 = e < 2 ? wa[2 * e + 1] : wb[2 * e - 3];
-                    float sa = dus[0] * w0;
-                    sa += dus[NA > 1 ? 1 : 0] * w1;
-                    gp[e] = hp[i][e] > 0.f ? sa : 0.f;
-                    gv[e] = hv[i][e] > 0.f ? dvs * wv[e] : 0.f;
-                }
-            } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int j = 4 * f + e;
-                float sa = 0.f;
-                _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) sa += dus[a] * sWm[j * A + a];
-                gp[e] = hp[i][e] > 0.f ? sa : 0.f;
-                gv[e] = hv[i][e] > 0.f ? dvs * sWv[j] : 0.f;
-            }
-            }
-            *(f32x4*)(dh2p + 4 * f) = gp;
-            *(f32x4*)(dh2v + 4 * f) = gv;
-        }
-    }
+    pf_head_dh2<NA, PF_NV, true>(q, sWm, sWv, sdu, sdv, hp, hv, m, mok, sm, part);
 }
 template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, false, false>(q); }
 template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_vclip_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, true, false>(q); }
@@ -603,8 +522,8 @@ template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kl_kernel
 template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kl_vclip_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, true, true>(q); }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// CLONE (ppo_head_clone_kernel; mi_ppo_clone_step): behaviour cloning, the supervised form of the head / loss kernel.  A body of its own, so that the eight
-// instantiations above stay as they are.  q.actions holds the EXPERT's actions a_E (a table with row_idx), q.clone the kind + 1, q.returns the returns or nullptr.
+// CLONE (ppo_head_clone_kernel; mi_ppo_clone_step): behaviour cloning, the supervised form of the head / loss kernel.  A kernel of its own, built from the same
+// helpers (ppo_head.hpp): it keeps no sWo and no old-policy row, and the eight instantiations above stay as they are.  q.actions holds the EXPERT's actions a_E (a table with row_idx), q.clone the kind + 1, q.returns the returns or nullptr.
 // Per sample m and action a, with t = tanh(u), mean = lo + (t + 1) / 2 (hi - lo), sigma = exp(logstd[a]), z = (a_E - mean) / sigma:
 //   kind 0 "nll":  l[m] = sum_a (z^2 / 2 + logstd[a] + log(2 pi) / 2) ;  dl/du = -(z / sigma) (hi - lo) / 2 (1 - t^2) ;  dl/dlogstd[a] = 1 - z^2
 //   kind 1 "mse":  l[m] = sum_a (mean - a_E)^2 ;  dl/du = 2 (mean - a_E) (hi - lo) / 2 (1 - t^2) ;  dl/dlogstd = 0 exactly
@@ -615,94 +534,40 @@ template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kl_vclip_
 // Without returns (policy only) nothing of the value net is read or written: no h2 row of net 1, no value head, no dv, no dh2 of net 1; slot 1 is 0.
 // As above: 8 lanes per sample, lane `part` owns action `part`, hardware transcendentals, fixed-order block sums, du / dv / dh2 for the chain behind.
 // ---------------------------------------------------------------------------------------------------------------------
-// VAL (returns given) is a template flag, not a test of q.returns: a uniform branch between the two nets' row loads makes the compiler wait for each pair of
-// 16-byte pieces before it requests the next (measured: + 2.6 us on a 39 us step at M = 32), where the straight-line form keeps all of them in flight.
+// VAL (returns given) is a template flag, not a test of q.returns: see pf_head_rows.
 template <int NA, bool VAL>
 __global__ __launch_bounds__(256) void ppo_head_clone_kernel(const PpoFusedParams q) {
     __shared__ __attribute__((aligned(16))) float sWm[PF_H2MAX * PF_MAX_ACT], sWv[PF_H2MAX];
     __shared__ float su[32][NA], sv[32], sdu[32][NA], sdv[32], spart[32][PF_NPART];
     const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
-    constexpr bool val = VAL;                             // the value net takes part
     const bool mse = q.clone == 2;
-    const float* __restrict__ Wm = q.theta + q.off[4]; const float* __restrict__ bm = q.theta + q.off[5];
-    const float* __restrict__ Wv = q.theta + q.off[11]; const float* __restrict__ bv = q.theta + q.off[12];
-    const float* __restrict__ h2p = q.h2; const float* __restrict__ h2v = q.h2 + (long long)q.M * H2;
+    const float* __restrict__ bm = q.theta + q.off[5]; const float* __restrict__ bv = q.theta + q.off[12];
     const int sm = tid >> 3, part = tid & 7, m = m0 + sm;
     const bool mok = m < q.M;
-    constexpr int NV = (PF_H2MAX / 4 + 7) / 8;
-    const int nf = H2 >> 2;
-    f32x4 hp[NV], hv[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int f = part + 8 * i;
-        const bool ok = mok && f < nf;
-        hp[i] = ok ? *(const f32x4*)(h2p + (long long)m * H2 + 4 * f) : f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (VAL) hv[i] = ok ? *(const f32x4*)(h2v + (long long)m * H2 + 4 * f) : f32x4{0.f, 0.f, 0.f, 0.f};
-        else hv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    constexpr int NST = (PF_H2MAX * NA + 255) / 256;
-    float stm[NST], stv[(PF_H2MAX + 255) / 256];
-#pragma unroll
-    for (int i = 0; i < NST; ++i) { const int x = tid + 256 * i; stm[i] = x < H2 * A ? Wm[x] : 0.f; }
-#pragma unroll
-    for (int i = 0; i < (PF_H2MAX + 255) / 256; ++i) { const int x = tid + 256 * i; stv[i] = (val && x < H2) ? Wv[x] : 0.f; }
+    f32x4 hp[PF_NV], hv[PF_NV];
+    pf_head_rows<PF_NV, VAL>(q, m, mok, part, hp, hv);
+    PfHeadStage<NA> st;
+    pf_stage_request<NA, false, VAL>(q, tid, false, st);
     const int mr = (q.row_idx && mok) ? min(max(q.row_idx[m], 0), q.n_rows - 1) : m;     // the sample's row in the tables (expert actions / returns)
     float act = 0.f, ls = 0.f, lo = 0.f, hi = 0.f, p_ret_s = 0.f;                        // lane `part`: its action's scalars
     if (part < A) { ls = q.theta[q.off[6] + part]; lo = q.low[part]; hi = q.high[part]; if (mok) act = q.actions[(long long)mr * A + part]; }
-    if (val && mok) p_ret_s = q.returns[mr];
-#pragma unroll
-    for (int i = 0; i < NST; ++i) { const int x = tid + 256 * i; if (x < H2 * A) sWm[x] = stm[i]; }
-#pragma unroll
-    for (int i = 0; i < (PF_H2MAX + 255) / 256; ++i) { const int x = tid + 256 * i; if (x < H2) sWv[x] = stv[i]; }
+    if (VAL && mok) p_ret_s = q.returns[mr];
+    pf_stage_commit<NA, false>(q, tid, st, sWm, nullptr, sWv);
     __syncthreads();
     {
-        float au[NA], av = 0.f;
-#pragma unroll
-        for (int a = 0; a < NA; ++a) au[a] = 0.f;
-        if constexpr (NA == 2) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const int f = min(part + 8 * i, nf - 1);  // (threads past the row re-read its last piece: their h2 registers are zero)
-                const f32x4 wv = *(const f32x4*)(sWv + 4 * f);
-                const f32x4 wa = *(const f32x4*)(sWm + 8 * f), wb = *(const f32x4*)(sWm + 8 * f + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    av += hv[i][e] * wv[e];
-                    const float w0 = e < 2 ? wa[2 * e] : wb[2 * e - 4], w1 = e < 2 ? wa[2 * e + 1] : wb[2 * e - 3];
-                    au[0] += hp[i][e] * w0; au[NA > 1 ? 1 : 0] += hp[i][e] * w1;
-                }
-            }
-        } else {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int f = part + 8 * i;
-            if (f >= nf) continue;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int j = 4 * f + e;
-                av += hv[i][e] * sWv[j];
-                _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) au[a] += hp[i][e] * sWm[j * A + a];
-            }
-        }
-        }
-#pragma unroll
-        for (int o = 4; o > 0; o >>= 1) {
-            av += __shfl_xor(av, o, 64);
-#pragma unroll
-            for (int a = 0; a < NA; ++a) au[a] += __shfl_xor(au[a], o, 64);
-        }
+        float au[NA], av;
+        pf_head_sums<NA, PF_NV>((pf_lds_cf*)sWm, (pf_lds_cf*)sWv, hp, hv, part, H2 >> 2, A, au, av);
         if (part == 0) {
-            sv[sm] = val ? av + bv[0] : 0.f;
+            sv[sm] = VAL ? av + bv[0] : 0.f;
             _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) su[sm][a] = au[a] + bm[a];
         }
     }
     __syncthreads();
     {
-        auto fast_tanh = [](float x) { const float xc = fminf(fmaxf(x, -15.f), 15.f); return 1.0f - 2.0f / (__expf(2.0f * xc) + 1.0f); };
         float l = 0.f, sq = 0.f, d = 0.f, dls = 0.f, mean = 0.f;
         const bool aok = part < A && mok;
         if (aok) {
-            const float t = fast_tanh(su[sm][part < NA ? part : 0]);
+            const float t = pf_fast_tanh(su[sm][part < NA ? part : 0]);
             mean = lo + ((t + 1.0f) * 0.5f) * (hi - lo);
             const float diff = mean - act, sl = (0.5f * (hi - lo)) * (1.0f - t * t);
             sq = diff * diff;
@@ -723,59 +588,20 @@ __global__ __launch_bounds__(256) void ppo_head_clone_kernel(const PpoFusedParam
         if (part < NA) sdu[sm][part < NA ? part : 0] = aok ? d : 0.f;
         if (aok) q.du[(long long)m * A + part] = d;
         const float dvv = sv[sm] - p_ret_s;
-        const float dvm = (mok && val) ? 2.0f * q.value_scale * dvv * q.inv_m : 0.f;
+        const float dvm = (mok && VAL) ? 2.0f * q.value_scale * dvv * q.inv_m : 0.f;
         const float lv = dvv * dvv;
 #pragma unroll
         for (int k = part; k < PF_NPART; k += 8) spart[sm][k] = 0.f;
         __builtin_amdgcn_wave_barrier();
         if (part == 0) {
             sdv[sm] = dvm;
-            if (mok) { if (val) q.dv[m] = dvm; spart[sm][0] = l; spart[sm][1] = val ? lv : 0.f; spart[sm][2] = sq; }
+            if (mok) { if (VAL) q.dv[m] = dvm; spart[sm][0] = l; spart[sm][1] = VAL ? lv : 0.f; spart[sm][2] = sq; }
         }
         if (aok) { spart[sm][3 + part] = dls; spart[sm][3 + PF_MAX_ACT + part] = mean; }
     }
     __syncthreads();
-    if (tid < PF_NPART) {                                 // fixed-order block partial sums
-        float sum = 0.f;
-        for (int i = 0; i < 32; ++i) sum += spart[i][tid];
-        q.partial[(long long)blockIdx.x * PF_NPART + tid] = sum;
-    }
-    // ---- head input gradients of this thread's columns of its sample, masked by relu'(h2): from the rows still held in registers ----
-    if (mok) {
-        float* dh2p = q.dh2 + (long long)m * H2; float* dh2v = q.dh2 + (long long)q.M * H2 + (long long)m * H2;
-        float dus[NA];
-        _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) dus[a] = sdu[sm][a];
-        const float dvs = sdv[sm];
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int f = part + 8 * i;
-            if (f >= nf) continue;
-            f32x4 gp, gv;
-            if constexpr (NA == 2) {
-                const f32x4 wv = *(const f32x4*)(sWv + 4 * f);
-                const f32x4 wa = *(const f32x4*)(sWm + 8 * f), wb = *(const f32x4*)(sWm + 8 * f + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float w0 = e < 2 ? wa[2 * e] : wb[2 * e - 4], w1 = e < 2 ? wa[2 * e + 1] : wb[2 * e - 3];
-                    float sa = dus[0] * w0;
-                    sa += dus[NA > 1 ? 1 : 0] * w1;
-                    gp[e] = hp[i][e] > 0.f ? sa : 0.f;
-                    gv[e] = hv[i][e] > 0.f ? dvs * wv[e] : 0.f;
-                }
-            } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int j = 4 * f + e;
-                float sa = 0.f;
-                _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) sa += dus[a] * sWm[j * A + a];
-                gp[e] = hp[i][e] > 0.f ? sa : 0.f;
-                gv[e] = hv[i][e] > 0.f ? dvs * sWv[j] : 0.f;
-            }
-            }
-            *(f32x4*)(dh2p + 4 * f) = gp;
-            if (val) *(f32x4*)(dh2v + 4 * f) = gv;
-        }
-    }
+    pf_block_partials(q, spart, tid);
+    pf_head_dh2<NA, PF_NV, VAL>(q, sWm, sWv, sdu, sdv, hp, hv, m, mok, sm, part);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -997,31 +823,15 @@ __global__ __launch_bounds__(256) void ppo_predict_head_kernel(const PpoFusedPar
     const float* Wm = th + q.off[4]; const float* bm = th + q.off[5]; const float* logstd = th + q.off[6];
     const float* Wv = q.theta + q.off[11]; const float* bv = q.theta + q.off[12];
     const float* h2p = q.h2 + (long long)(logp_out ? (lp_net == 2 ? 2 : 0) : 0) * q.M * H2; const float* h2v = q.h2 + (long long)q.M * H2;
-    float au[NA], av = 0.f;
-#pragma unroll
-    for (int a = 0; a < NA; ++a) au[a] = 0.f;
-    if (m < q.M) {
-        for (int j = part; j < H2; j += TPS) {
-            const float hp = h2p[(long long)m * H2 + j];
-            if (!logp_out) av += h2v[(long long)m * H2 + j] * Wv[j];
-            _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) au[a] += hp * Wm[(long long)j * A + a];
-        }
-    }
-#pragma unroll
-    for (int o = TPS / 2; o > 0; o >>= 1) {
-        av += __shfl_xor(av, o, 64);
-#pragma unroll
-        for (int a = 0; a < NA; ++a) au[a] += __shfl_xor(au[a], o, 64);
-    }
+    float au[NA], av;
+    pf_head_sums_strided<NA, TPS>(h2p + (long long)m * H2, h2v + (long long)m * H2, Wm, Wv, m < q.M, !logp_out, part, H2, A, au, av);
     if (part != 0 || m >= q.M) return;
     float lp = 0.f;
     _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) {
         const float lo = q.low[a], hi = q.high[a];
-        const float mean = lo + ((tanhf(au[a] + bm[a]) + 1.0f) * 0.5f) * (hi - lo);
+        const float mean = pf_mean_libm(au[a], bm[a], lo, hi);
         if (logp_out) {
-            const float sigma = expf(logstd[a]);
-            const float z = (q.actions[(long long)m * A + a] - mean) / sigma;
-            lp += -0.5f * z * z - (PF_HALF_LOG_2PI + logf(sigma));
+            lp += pf_logp_term_libm(q.actions[(long long)m * A + a], mean, logstd[a]);
             if (q.mean_old_out) q.mean_old_out[(long long)m * A + a] = mean;      // (mi_ppo_old_policy_cache: the means the KL penalty reads)
         } else {
             if (q.mean_out) q.mean_out[(long long)m * A + a] = mean;
@@ -1036,37 +846,22 @@ __global__ __launch_bounds__(256) void ppo_predict_head_kernel(const PpoFusedPar
 // ---------------------------------------------------------------------------------------------------------------------
 // update diagnostics (mi_ppo_update_stats_idx): heads of the CURRENT policy and value net on the trunks of nets 0 / 1, and the per-sample terms of the
 // MI_PPO_N_STATS running sums in double precision.  grid ceil(M / 32) blocks; 8 threads per sample, sample m = table row row_idx[m] (clamped).
-//   lp = log pi(a | s) under theta: the loop, the shuffles and the libm calls of ppo_predict_head_kernel<NA, 3>'s log-probability path, so that with
+//   lp = log pi(a | s) under theta in the strided form of ppo_predict_head_kernel<NA, 3>'s log-probability path (the contracts: ppo_head.hpp), so that with
 //        theta == theta_old it is the cached logp_old bit for bit;  v = h2_v Wv + bv in that kernel's order
 //   d = lp - logp_old, r = exp(d), ret = returns: terms 1, d, r - 1 - d (k3), |r - 1| > clip_eps, r, ret, ret^2, ret - v, (ret - v)^2
-// Ordered reduction, no atomics: the 8 samples of a wave meet by an xor tree of shuffles (every lane forms the same sums), the four waves' sums in LDS are added
-// in wave order and stored as this block's row of `scratch`; ppo_update_stats_reduce_kernel adds the rows in block order.
+// Ordered reduction, no atomics: pf_ordered_block_sum stores this block's row of `scratch`; ppo_stats_reduce_kernel adds the rows in block order.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int PF_NSTATS = MI_PPO_N_STATS;
 template <int NA>
 __global__ __launch_bounds__(256) void ppo_update_stats_head_kernel(const PpoFusedParams q, double* __restrict__ scratch, float* __restrict__ logp_new_out, float* __restrict__ value_out) {
     __shared__ double swave[4][PF_NSTATS];
     const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
-    const int sm = tid >> 3, part = tid & 7, m = m0 + sm, wave = tid >> 6;
+    const int sm = tid >> 3, part = tid & 7, m = m0 + sm;
     const float* Wm = q.theta + q.off[4]; const float* bm = q.theta + q.off[5]; const float* logstd = q.theta + q.off[6];
     const float* Wv = q.theta + q.off[11]; const float* bv = q.theta + q.off[12];
     const float* h2p = q.h2; const float* h2v = q.h2 + (long long)q.M * H2;
-    float au[NA], av = 0.f;
-#pragma unroll
-    for (int a = 0; a < NA; ++a) au[a] = 0.f;
-    if (m < q.M) {
-        for (int j = part; j < H2; j += 8) {
-            const float hp = h2p[(long long)m * H2 + j];
-            av += h2v[(long long)m * H2 + j] * Wv[j];
-            _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) au[a] += hp * Wm[(long long)j * A + a];
-        }
-    }
-#pragma unroll
-    for (int o = 4; o > 0; o >>= 1) {
-        av += __shfl_xor(av, o, 64);
-#pragma unroll
-        for (int a = 0; a < NA; ++a) au[a] += __shfl_xor(au[a], o, 64);
-    }
+    float au[NA], av;
+    pf_head_sums_strided<NA, 8>(h2p + (long long)m * H2, h2v + (long long)m * H2, Wm, Wv, m < q.M, true, part, H2, A, au, av);
     double term[PF_NSTATS];
 #pragma unroll
     for (int k = 0; k < PF_NSTATS; ++k) term[k] = 0.0;
@@ -1074,11 +869,7 @@ __global__ __launch_bounds__(256) void ppo_update_stats_head_kernel(const PpoFus
         const long long mr = min(max(q.row_idx[m], 0), q.n_rows - 1);
         float lp = 0.f;
         _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) {
-            const float lo = q.low[a], hi = q.high[a];
-            const float mean = lo + ((tanhf(au[a] + bm[a]) + 1.0f) * 0.5f) * (hi - lo);
-            const float sigma = expf(logstd[a]);
-            const float z = (q.actions[mr * A + a] - mean) / sigma;
-            lp += -0.5f * z * z - (PF_HALF_LOG_2PI + logf(sigma));
+            lp += pf_logp_term_libm(q.actions[mr * A + a], pf_mean_libm(au[a], bm[a], q.low[a], q.high[a]), logstd[a]);
         }
         const float v = av + bv[0];
         if (logp_new_out) logp_new_out[mr] = lp;
@@ -1089,58 +880,27 @@ __global__ __launch_bounds__(256) void ppo_update_stats_head_kernel(const PpoFus
         term[0] = 1.0; term[1] = d; term[2] = (r - 1.0) - d; term[3] = fabs(r - 1.0) > (double)q.clip_eps ? 1.0 : 0.0; term[4] = r;
         term[5] = ret; term[6] = ret * ret; term[7] = e; term[8] = e * e;
     }
-#pragma unroll
-    for (int k = 0; k < PF_NSTATS; ++k) {
-#pragma unroll
-        for (int o = 8; o < 64; o <<= 1) term[k] += __shfl_xor(term[k], o, 64);
-    }
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < PF_NSTATS; ++k) swave[wave][k] = term[k];
-    }
-    __syncthreads();
-    if (tid < PF_NSTATS) scratch[(long long)blockIdx.x * PF_NSTATS + tid] = ((swave[0][tid] + swave[1][tid]) + swave[2][tid]) + swave[3][tid];
-}
-
-// one wave: lane k adds column k of the block rows in block order, then stores (accumulate 0) or adds to (1) stats[k]
-__global__ __launch_bounds__(64) void ppo_update_stats_reduce_kernel(const double* __restrict__ scratch, int n_blocks, int accumulate, double* __restrict__ stats) {
-    const int k = threadIdx.x;
-    if (k >= PF_NSTATS) return;
-    double sum = 0.0;
-    for (int b = 0; b < n_blocks; ++b) sum += scratch[(long long)b * PF_NSTATS + k];
-    stats[k] = accumulate ? stats[k] + sum : sum;
+    pf_ordered_block_sum<PF_NSTATS>(term, swave, scratch, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // exact-KL statistics (mi_ppo_kl_stats_idx): the head of the CURRENT policy on the trunk of net 0, and per sample the closed-form KL(pi_old || pi_theta) of the
-// diagonal Gaussians in double precision from the fp32 means (this pass: the loop, the shuffles and the libm tanhf of ppo_predict_head_kernel<NA, 3>, so that with
+// diagonal Gaussians in double precision from the fp32 means (this pass: the strided form of ppo_predict_head_kernel<NA, 3>, ppo_head.hpp, so that with
 // theta == theta_old the mean is the cached one bit for bit and the KL is 0; old: q.mean_old[row]) and the two log-stds:
 //   KL[m] = sum_a d + expm1(-2 d) / 2 + D^2 / (2 sigma^2) ,  d = ls - lso, D = mu - mu_o, sigma = exp(ls)
 // terms 1, KL, KL^2, sum_a D^2 / (2 sigma^2) (the mean part).  grid ceil(M / 32) blocks; 8 threads per sample, sample m = table row row_idx[m] (clamped).  The
-// reduction is that of ppo_update_stats_head_kernel: xor tree over the wave's 8 samples, the four waves in order, one scratch row per block.
+// reduction is that of ppo_update_stats_head_kernel.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int PF_NKLSTATS = MI_PPO_N_KL_STATS;
 template <int NA>
 __global__ __launch_bounds__(256) void ppo_kl_stats_head_kernel(const PpoFusedParams q, double* __restrict__ scratch) {
     __shared__ double swave[4][PF_NKLSTATS];
     const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
-    const int sm = tid >> 3, part = tid & 7, m = m0 + sm, wave = tid >> 6;
+    const int sm = tid >> 3, part = tid & 7, m = m0 + sm;
     const float* Wm = q.theta + q.off[4]; const float* bm = q.theta + q.off[5]; const float* logstd = q.theta + q.off[6]; const float* logstd_o = q.theta_old + q.off[6];
     const float* h2p = q.h2;
-    float au[NA];
-#pragma unroll
-    for (int a = 0; a < NA; ++a) au[a] = 0.f;
-    if (m < q.M) {
-        for (int j = part; j < H2; j += 8) {
-            const float hp = h2p[(long long)m * H2 + j];
-            _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) au[a] += hp * Wm[(long long)j * A + a];
-        }
-    }
-#pragma unroll
-    for (int o = 4; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < NA; ++a) au[a] += __shfl_xor(au[a], o, 64);
-    }
+    float au[NA], av;                                     // (av: no value net here)
+    pf_head_sums_strided<NA, 8>(h2p + (long long)m * H2, nullptr, Wm, nullptr, m < q.M, false, part, H2, A, au, av);
     double term[PF_NKLSTATS];
 #pragma unroll
     for (int k = 0; k < PF_NKLSTATS; ++k) term[k] = 0.0;
@@ -1148,8 +908,7 @@ __global__ __launch_bounds__(256) void ppo_kl_stats_head_kernel(const PpoFusedPa
         const long long mr = min(max(q.row_idx[m], 0), q.n_rows - 1);
         double kl = 0.0, mp = 0.0;
         _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) {
-            const float lo = q.low[a], hi = q.high[a];
-            const float mean = lo + ((tanhf(au[a] + bm[a]) + 1.0f) * 0.5f) * (hi - lo);
+            const float mean = pf_mean_libm(au[a], bm[a], q.low[a], q.high[a]);
             const double ls = (double)logstd[a], d = ls - (double)logstd_o[a], dm = (double)mean - (double)q.mean_old[mr * A + a];
             const double qh = 0.5 * dm * dm * exp(-2.0 * ls);      // D^2 / (2 sigma^2)
             kl += d + 0.5 * expm1(-2.0 * d) + qh;
@@ -1157,26 +916,7 @@ __global__ __launch_bounds__(256) void ppo_kl_stats_head_kernel(const PpoFusedPa
         }
         term[0] = 1.0; term[1] = kl; term[2] = kl * kl; term[3] = mp;
     }
-#pragma unroll
-    for (int k = 0; k < PF_NKLSTATS; ++k) {
-#pragma unroll
-        for (int o = 8; o < 64; o <<= 1) term[k] += __shfl_xor(term[k], o, 64);
-    }
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < PF_NKLSTATS; ++k) swave[wave][k] = term[k];
-    }
-    __syncthreads();
-    if (tid < PF_NKLSTATS) scratch[(long long)blockIdx.x * PF_NKLSTATS + tid] = ((swave[0][tid] + swave[1][tid]) + swave[2][tid]) + swave[3][tid];
-}
-
-// one wave: lane k adds column k of the block rows in block order, then stores (accumulate 0) or adds to (1) stats[k]
-__global__ __launch_bounds__(64) void ppo_kl_stats_reduce_kernel(const double* __restrict__ scratch, int n_blocks, int accumulate, double* __restrict__ stats) {
-    const int k = threadIdx.x;
-    if (k >= PF_NKLSTATS) return;
-    double sum = 0.0;
-    for (int b = 0; b < n_blocks; ++b) sum += scratch[(long long)b * PF_NKLSTATS + k];
-    stats[k] = accumulate ? stats[k] + sum : sum;
+    pf_ordered_block_sum<PF_NKLSTATS>(term, swave, scratch, tid);
 }
 
 }  // namespace mi
@@ -1205,16 +945,19 @@ static int pf_check_shape(const PpoFusedParams& q, const char* who) {
     return MI_OK;
 }
 
+// the predict / logp_old / statistics heads take their NA = 2 instantiation up to two actions, A = 1 included -- unlike the loss and clone kernels of the step
+// (pf_step_head_kernel), which take theirs for A == 2 only
+template <class K> static K pf_na_pick(int A, K k2, K k8) { return A <= 2 ? k2 : k8; }
+
 int mi_ppo_fused_predict(hipStream_t st, PpoFusedParams& q, const float* noise, int greedy, float* action, float* value) {
     { const int rc0 = pf_check_shape(q, "ppo fused predict"); if (rc0 != MI_OK) return rc0; }
     q.n_nets = 2;
     int rc = mi_ppo_fused_trunks(st, q, false);            // (PPO.predict stays exact fp32 in every precision mode)
     if (rc != MI_OK) return rc;
-    if (q.M <= 8) {                                       // a wave per sample
-        if (q.A <= 2) hipLaunchKernelGGL((ppo_predict_head_kernel<2, 6>), dim3((q.M + 3) / 4), dim3(256), 0, st, q, noise, greedy, action, value, (float*)nullptr, 0);
-        else hipLaunchKernelGGL((ppo_predict_head_kernel<PF_MAX_ACT, 6>), dim3((q.M + 3) / 4), dim3(256), 0, st, q, noise, greedy, action, value, (float*)nullptr, 0);
-    } else if (q.A <= 2) hipLaunchKernelGGL((ppo_predict_head_kernel<2, 3>), dim3((q.M + 31) / 32), dim3(256), 0, st, q, noise, greedy, action, value, (float*)nullptr, 0);
-    else hipLaunchKernelGGL((ppo_predict_head_kernel<PF_MAX_ACT, 3>), dim3((q.M + 31) / 32), dim3(256), 0, st, q, noise, greedy, action, value, (float*)nullptr, 0);
+    if (q.M <= 8)                                         // a wave per sample
+        hipLaunchKernelGGL(pf_na_pick(q.A, ppo_predict_head_kernel<2, 6>, ppo_predict_head_kernel<PF_MAX_ACT, 6>), dim3((q.M + 3) / 4), dim3(256), 0, st, q, noise, greedy, action, value, (float*)nullptr, 0);
+    else
+        hipLaunchKernelGGL(pf_na_pick(q.A, ppo_predict_head_kernel<2, 3>, ppo_predict_head_kernel<PF_MAX_ACT, 3>), dim3((q.M + 31) / 32), dim3(256), 0, st, q, noise, greedy, action, value, (float*)nullptr, 0);
     return mi_check_launch("ppo_predict_head");
 }
 
@@ -1226,8 +969,7 @@ int mi_ppo_fused_logp_old(hipStream_t st, PpoFusedParams& q, float* out, bool x3
     q.n_nets = 3;
     int rc = mi_ppo_fused_trunks(st, q, x3);
     if (rc != MI_OK) return rc;
-    if (q.A <= 2) hipLaunchKernelGGL((ppo_predict_head_kernel<2, 3>), dim3((q.M + 31) / 32), dim3(256), 0, st, q, (const float*)nullptr, 1, (float*)nullptr, (float*)nullptr, out, 2);
-    else hipLaunchKernelGGL((ppo_predict_head_kernel<PF_MAX_ACT, 3>), dim3((q.M + 31) / 32), dim3(256), 0, st, q, (const float*)nullptr, 1, (float*)nullptr, (float*)nullptr, out, 2);
+    hipLaunchKernelGGL(pf_na_pick(q.A, ppo_predict_head_kernel<2, 3>, ppo_predict_head_kernel<PF_MAX_ACT, 3>), dim3((q.M + 31) / 32), dim3(256), 0, st, q, (const float*)nullptr, 1, (float*)nullptr, (float*)nullptr, out, 2);
     return mi_check_launch("ppo_logp_old");
 }
 
@@ -1240,9 +982,8 @@ int mi_ppo_fused_update_stats(hipStream_t st, PpoFusedParams& q, int accumulate,
     int rc = mi_ppo_fused_trunks(st, q, x3);
     if (rc != MI_OK) return rc;
     const int nb = (q.M + 31) / 32;
-    if (q.A <= 2) hipLaunchKernelGGL(ppo_update_stats_head_kernel<2>, dim3(nb), dim3(256), 0, st, q, scratch, logp_new_out, value_out);
-    else hipLaunchKernelGGL(ppo_update_stats_head_kernel<PF_MAX_ACT>, dim3(nb), dim3(256), 0, st, q, scratch, logp_new_out, value_out);
-    hipLaunchKernelGGL(ppo_update_stats_reduce_kernel, dim3(1), dim3(64), 0, st, (const double*)scratch, nb, accumulate, stats);
+    hipLaunchKernelGGL(pf_na_pick(q.A, ppo_update_stats_head_kernel<2>, ppo_update_stats_head_kernel<PF_MAX_ACT>), dim3(nb), dim3(256), 0, st, q, scratch, logp_new_out, value_out);
+    hipLaunchKernelGGL(ppo_stats_reduce_kernel<PF_NSTATS>, dim3(1), dim3(64), 0, st, (const double*)scratch, nb, accumulate, stats);
     return mi_check_launch("ppo_update_stats");
 }
 
@@ -1255,9 +996,8 @@ int mi_ppo_fused_kl_stats(hipStream_t st, PpoFusedParams& q, int accumulate, dou
     int rc = mi_ppo_fused_trunks(st, q, x3);
     if (rc != MI_OK) return rc;
     const int nb = (q.M + 31) / 32;
-    if (q.A <= 2) hipLaunchKernelGGL(ppo_kl_stats_head_kernel<2>, dim3(nb), dim3(256), 0, st, q, scratch);
-    else hipLaunchKernelGGL(ppo_kl_stats_head_kernel<PF_MAX_ACT>, dim3(nb), dim3(256), 0, st, q, scratch);
-    hipLaunchKernelGGL(ppo_kl_stats_reduce_kernel, dim3(1), dim3(64), 0, st, (const double*)scratch, nb, accumulate, stats);
+    hipLaunchKernelGGL(pf_na_pick(q.A, ppo_kl_stats_head_kernel<2>, ppo_kl_stats_head_kernel<PF_MAX_ACT>), dim3(nb), dim3(256), 0, st, q, scratch);
+    hipLaunchKernelGGL(ppo_stats_reduce_kernel<PF_NKLSTATS>, dim3(1), dim3(64), 0, st, (const double*)scratch, nb, accumulate, stats);
     return mi_check_launch("ppo_kl_stats");
 }
 
@@ -1295,6 +1035,19 @@ static int ppo_pad(hipStream_t st, float* sink) {
 static inline int ppo_pad(hipStream_t, float*) { return MI_OK; }
 #endif
 
+// the head / loss kernel of a step.  NA = 2 only for A == 2 (the 16-byte LDS reads of pf_head_sums need exactly two actions; A = 1 runs the general form).
+//   behaviour cloning (mi_ppo_clone_step): by returns given (VAL)
+//   PPO: by the KL-penalised surrogate (KLP: mi_ppo_train_step_kl) and the clipped value loss (VCLIP: v_old given; mi_ppo_train_step_vclip)
+typedef void (*pf_head_kernel_t)(const PpoFusedParams);
+static pf_head_kernel_t pf_step_head_kernel(const PpoFusedParams& q) {
+    static const pf_head_kernel_t table[12] = {           // [clone ? 8 + 2 VAL : 4 KLP + 2 VCLIP] + (A == 2)
+        ppo_head_loss_kernel<PF_MAX_ACT>, ppo_head_loss_kernel<2>, ppo_head_loss_vclip_kernel<PF_MAX_ACT>, ppo_head_loss_vclip_kernel<2>,
+        ppo_head_loss_kl_kernel<PF_MAX_ACT>, ppo_head_loss_kl_kernel<2>, ppo_head_loss_kl_vclip_kernel<PF_MAX_ACT>, ppo_head_loss_kl_vclip_kernel<2>,
+        ppo_head_clone_kernel<PF_MAX_ACT, false>, ppo_head_clone_kernel<2, false>, ppo_head_clone_kernel<PF_MAX_ACT, true>, ppo_head_clone_kernel<2, true>};
+    const int variant = q.clone ? 8 + 2 * (q.returns != nullptr) : 4 * (q.kl_on != 0) + 2 * (q.v_old != nullptr);
+    return table[variant + (q.A == 2)];
+}
+
 // the whole minibatch step; fuse_adam = 0: gradients to q.grads instead of the in-place optimiser update.  x3: the GEMM stages (layers 1-2, the layer-1 input
 // gradient, the weight gradients) in their split-bf16 instantiations; the head / loss kernel, the flat Adam and the slab sums are the same launches in both modes
 int mi_ppo_fused_step(hipStream_t st, PpoFusedParams& q, int fuse_adam, bool x3) {
@@ -1309,25 +1062,7 @@ int mi_ppo_fused_step(hipStream_t st, PpoFusedParams& q, int fuse_adam, bool x3)
     if (rc != MI_OK) return rc;
     rc = ppo_pad(st, q.losses);
     if (rc != MI_OK) return rc;
-    if (q.clone) {                                        // behaviour cloning (mi_ppo_clone_step): its own head / loss kernel, the same chain behind it
-        const dim3 g(q.n_loss_blocks), b(256);
-        if (q.returns) {
-            if (q.A == 2) hipLaunchKernelGGL((ppo_head_clone_kernel<2, true>), g, b, 0, st, q);
-            else hipLaunchKernelGGL((ppo_head_clone_kernel<PF_MAX_ACT, true>), g, b, 0, st, q);
-        } else if (q.A == 2) hipLaunchKernelGGL((ppo_head_clone_kernel<2, false>), g, b, 0, st, q);
-        else hipLaunchKernelGGL((ppo_head_clone_kernel<PF_MAX_ACT, false>), g, b, 0, st, q);
-    } else if (q.kl_on) {                                        // the KL-penalised surrogate (mi_ppo_train_step_kl), with or without the clipped value loss
-        const dim3 g(q.n_loss_blocks), b(256);
-        if (q.v_old) {
-            if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_kl_vclip_kernel<2>, g, b, 0, st, q);
-            else hipLaunchKernelGGL(ppo_head_loss_kl_vclip_kernel<PF_MAX_ACT>, g, b, 0, st, q);
-        } else if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_kl_kernel<2>, g, b, 0, st, q);
-        else hipLaunchKernelGGL(ppo_head_loss_kl_kernel<PF_MAX_ACT>, g, b, 0, st, q);
-    } else if (q.v_old) {                                 // the clipped value loss (mi_ppo_train_step_vclip): the same kernel body with one more gather per sample
-        if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_vclip_kernel<2>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);
-        else hipLaunchKernelGGL(ppo_head_loss_vclip_kernel<PF_MAX_ACT>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);
-    } else if (q.A == 2) hipLaunchKernelGGL(ppo_head_loss_kernel<2>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);     // (action loops are compile-time unrolled)
-    else hipLaunchKernelGGL(ppo_head_loss_kernel<PF_MAX_ACT>, dim3(q.n_loss_blocks), dim3(256), 0, st, q);
+    hipLaunchKernelGGL(pf_step_head_kernel(q), dim3(q.n_loss_blocks), dim3(256), 0, st, q);
     if (x3) hipLaunchKernelGGL(ppo_dh1_kernel<true>, dim3((q.H1 + 31) / 32, q.n_wnets, (q.M + 31) / 32), dim3(256), 0, st, q);
     else hipLaunchKernelGGL(ppo_dh1_kernel<false>, dim3((q.H1 + 31) / 32, q.n_wnets, (q.M + 31) / 32), dim3(256), 0, st, q);
     rc = ppo_pad(st, q.losses);

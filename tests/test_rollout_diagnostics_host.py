@@ -202,7 +202,7 @@ def test_signatures_and_documents():
 
 
 NEW_HEAD = [r"_ZN2mi28ppo_update_stats_head_kernelILi2EE", r"_ZN2mi28ppo_update_stats_head_kernelILi8EE"]
-NEW_REDUCE = r"_ZN2mi30ppo_update_stats_reduce_kernelE"
+NEW_REDUCE = r"_ZN2mi23ppo_stats_reduce_kernelILi9EE"                            # (one template behind both statistics kernels, here at MI_PPO_N_STATS: csrc/ppo_head.hpp)
 OLD_FUSED = [r"_ZN2mi23ppo_predict_head_kernelILi2ELi3EE", r"_ZN2mi23ppo_predict_head_kernelILi8ELi3EE", r"_ZN2mi23ppo_predict_head_kernelILi2ELi6EE",
              r"_ZN2mi20ppo_head_loss_kernelILi2EE", r"_ZN2mi20ppo_head_loss_kernelILi8EE", r"_ZN2mi13ppo_l1_kernelILb0EE", r"_ZN2mi13ppo_l1_kernelILb1EE",
              r"_ZN2mi13ppo_l2_kernelILb0EE", r"_ZN2mi13ppo_l2_kernelILb1EE", r"_ZN2mi14ppo_dh1_kernelILb0EE", r"_ZN2mi16ppo_wgrad_kernelILb1ELb0EE"]

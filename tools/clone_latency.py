@@ -1,13 +1,15 @@
-"""What a behaviour-cloning step costs (profiles/r34_behaviour_cloning.md): interleaved windows of mi_ppo_clone_step with returns and policy-only against the plain
-one-call PPO step (mi_ppo_train_step with a cached log pi_old) at M = 32 and M = 2048 (fp32, 67 inputs, 2 actions) -- one process, device events, a warm-up, nine
-rounds per variant; median / min / max of the rounds in us per call.  Two windows of the plain step per round give its own run-to-run spread.  With
---parent-lib PATH the plain step also runs from ANOTHER build of the library (the parent commit's libmi355_carla.so) in the same process and the same rounds, on an
-engine of its own with the same parameters: the plain step's entry points have the same prototypes in both.
+"""What the calls through the head-level kernels of csrc/ppo_fused.hip cost (profiles/r34_behaviour_cloning.md, profiles/r35_ppo_head_helpers.md): interleaved windows
+of the plain one-call PPO step (mi_ppo_train_step with a cached log pi_old, two windows: its own run-to-run spread), mi_ppo_clone_step with returns and policy-only
+in both kinds, and mi_ppo_train_step_kl with value clipping, at M = 32 and M = 2048 (fp32, 67 inputs, 2 actions); at M = 2048 also one window each of
+mi_ppo_update_stats_idx, mi_ppo_kl_stats_idx and mi_ppo_logp_old.  One process, device events, a warm-up of 100 calls, nine rounds per variant; median / min / max
+of the rounds in us per call.  With --parent-lib PATH every variant also runs from ANOTHER build of the library (the parent commit's libmi355_carla.so) in the same
+process and the same rounds, on an engine of its own with the same parameters, and each variant of this build is compared with the SAME variant of that one: the
+entry points have the same prototypes in both.
 
     python tools/clone_latency.py [--parent-lib PATH] [OUT_DIR]      # default out/: writes clone_latency.json there and prints the table
 
-Expectations (recorded, not enforced): the step with returns is the same chain with fewer gathers and should not exceed the plain step by more than the larger of
-2 % and the plain step's own spread; policy-only should be below the plain step."""
+Expectations (recorded, not enforced): no variant exceeds its twin from the other build by more than the allowance, the larger of 2 % and the plain step's own
+spread; the clone step with returns stays within the allowance of the plain step, and policy-only below it."""
 import ctypes
 import json
 import os
@@ -21,7 +23,7 @@ for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
     sys.path.insert(0, p)
 from mi355 import lib as milib  # noqa: E402
 from mi355.init import init_ppo  # noqa: E402
-from mi355.ppo_device import PpoDevice  # noqa: E402
+from mi355.ppo_device import N_KL_STATS, N_STATS, PpoDevice  # noqa: E402
 
 argv = sys.argv[1:]
 PARENT = None
@@ -39,33 +41,67 @@ d = PpoDevice(DIN, A, low, high, 0.2, 1.0, 0.01, max_batch=MAXB)
 th = init_ppo(1, DIN, A, 0.4)
 d.load_params(th, {k.replace("policy/", "policy_old/", 1): (v + 0.01 * rng.standard_normal(v.shape)).astype(np.float32) for k, v in th.items()})
 up = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)      # noqa: E731
+p = milib.ptr
+ADAM = (1e-6, 0.9, 0.999, 1e-8)
 
 
-class OtherBuild:
-    """The plain step of another build of the library: an engine of its own (buffers, workspace) holding d's parameters."""
+class Build:
+    """The measured entries of one build of the library on one engine, called through the raw C prototypes (the same Python work per call for both builds)."""
 
-    NAMES = ("mi_ppo_workspace_bytes", "mi_ppo_create", "mi_ppo_destroy", "mi_ppo_train_step")
+    NAMES = ("mi_ppo_workspace_bytes", "mi_ppo_create", "mi_ppo_destroy", "mi_ppo_train_step", "mi_ppo_clone_step", "mi_ppo_train_step_kl",
+             "mi_ppo_update_stats_idx", "mi_ppo_kl_stats_idx", "mi_ppo_logp_old")
 
-    def __init__(self, path):
-        self.cdll = ctypes.CDLL(path)
-        protos = milib.parse_header()
-        for name in self.NAMES:                              # (prototypes of this tree's header: these four are the same in both builds)
-            fn = getattr(self.cdll, name)
-            fn.restype, fn.argtypes = milib._CTYPES[protos[name][0]], [milib._CTYPES[t] for t, _ in protos[name][1]]
-        desc = d._desc(MAXB)
-        nbytes = int(self.cdll.mi_ppo_workspace_bytes(ctypes.byref(desc)))
-        self.bufs = [x.clone() for x in (d.params, d.params_old, d.grads, d.adam_m, d.adam_v)]
-        self.ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        p = milib.ptr
-        self.handle = self.cdll.mi_ppo_create(ctypes.byref(desc), *[p(x) for x in self.bufs], p(self.ws), nbytes, low.ctypes.data, high.ctypes.data)
-        if not self.handle:
-            raise RuntimeError("mi_ppo_create failed in " + path)
+    def __init__(self, path=None):
+        """path None: this tree's library on d's engine; else another build, on an engine of its own (buffers, workspace) holding d's parameters."""
+        self.path = path
+        if path is None:
+            self.cdll, self.handle, self.bufs = d.L.cdll, d.handle, [d.params, d.params_old, d.grads, d.adam_m, d.adam_v]
+        else:
+            self.cdll = ctypes.CDLL(path)
+            protos = milib.parse_header()
+            for name in self.NAMES:                          # (prototypes of this tree's header: the same in both builds)
+                fn = getattr(self.cdll, name)
+                fn.restype, fn.argtypes = milib._CTYPES[protos[name][0]], [milib._CTYPES[t] for t, _ in protos[name][1]]
+            desc = d._desc(MAXB)
+            nbytes = int(self.cdll.mi_ppo_workspace_bytes(ctypes.byref(desc)))
+            self.bufs = [x.clone() for x in (d.params, d.params_old, d.grads, d.adam_m, d.adam_v)]
+            self.ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            self.handle = self.cdll.mi_ppo_create(ctypes.byref(desc), *[p(x) for x in self.bufs], p(self.ws), nbytes, low.ctypes.data, high.ctypes.data)
+            if not self.handle:
+                raise RuntimeError("mi_ppo_create failed in " + path)
+        self.state = [x.clone() for x in self.bufs]
 
-    def train_step(self, s, a, R, adv, lp, M, inv_m, gs, alpha):
-        p = milib.ptr
-        rc = self.cdll.mi_ppo_train_step(self.handle, d.stream(), p(s), p(a), p(R), p(adv), p(lp), M, inv_m, gs, alpha, 0.9, 0.999, 1e-8)
+    def restore(self):
+        for x, y in zip(self.bufs, self.state):
+            x.copy_(y)
+
+    def call(self, name, *args):
+        rc = getattr(self.cdll, name)(self.handle, *args)
         if rc != 0:
-            raise RuntimeError("mi_ppo_train_step failed in the other build (%d)" % rc)
+            raise RuntimeError("%s failed (%d) in %s" % (name, rc, self.path or "this build"))
+
+    def close(self):
+        if self.path is not None:
+            self.cdll.mi_ppo_destroy(self.handle)
+
+    def variants(self, t, M, with_stats):
+        """name -> call, on the tensors t."""
+        st, a = d.stream(), (M, 1.0 / M, 1.0)
+        kinds = {k: milib.clone_kind(k, "clone_latency") for k in ("nll", "mse")}
+        plain = lambda: self.call("mi_ppo_train_step", st, p(t["s"]), p(t["a"]), p(t["R"]), p(t["adv"]), p(t["lp"]), *a, *ADAM)      # noqa: E731
+        clone = lambda R, kind: lambda: self.call("mi_ppo_clone_step", None, st, p(t["s"]), p(t["a"]), p(R), kinds[kind], None, M, *a, 1, *ADAM)      # noqa: E731
+        v = {"plain_a": plain,
+             "clone_returns_nll": clone(t["R"], "nll"), "clone_policy_only_nll": clone(None, "nll"),
+             "kl_vclip": lambda: self.call("mi_ppo_train_step_kl", None, st, p(t["s"]), p(t["a"]), p(t["R"]), p(t["adv"]), p(t["lp"]), p(t["mo"]), 0.7, p(t["vo"]), 0.2,
+                                           None, M, *a, 1, *ADAM),
+             "plain_b": plain,
+             "clone_returns_mse": clone(t["R"], "mse"), "clone_policy_only_mse": clone(None, "mse")}
+        if with_stats:
+            v["update_stats"] = lambda: self.call("mi_ppo_update_stats_idx", st, p(t["s"]), p(t["a"]), p(t["R"]), p(t["lp"]), p(t["rows"]), M, M, 0, p(t["scratch"]),
+                                                  p(t["stats"]), None, None)
+            v["kl_stats"] = lambda: self.call("mi_ppo_kl_stats_idx", st, p(t["s"]), p(t["mo"]), p(t["rows"]), M, M, 0, p(t["kl_scratch"]), p(t["kl_stats"]))
+            v["logp_old"] = lambda: self.call("mi_ppo_logp_old", st, p(t["s"]), p(t["a"]), M, p(t["lp_out"]))
+        return v
 
 
 def window(fn, iters):
@@ -90,38 +126,37 @@ def ab(variants, iters, rounds=9, warm=100):
     return {k: dict(median=float(np.median(v)), min=float(np.min(v)), max=float(np.max(v))) for k, v in t.items()}
 
 
-other = OtherBuild(PARENT) if PARENT else None
+this = Build()
+other = Build(PARENT) if PARENT else None
 out = {"parent_lib": bool(PARENT)}
-state = [x.clone() for x in (d.params, d.adam_m, d.adam_v)]
 for M, iters in ((32, 2000), (2048, 300)):
-    s, a = up(0.5 * rng.standard_normal((M, DIN))), up(rng.uniform(0, 1, (M, A)))
-    R, adv = up(rng.standard_normal(M)), up(rng.standard_normal(M))
-    lp = torch.empty(M, device=dev)
-    d.logp_old(s, a, M, lp)
-    args = (M, 1.0 / M, 1.0, 1e-6)
-    variants = {
-        "plain_a": lambda: d.train_step(s, a, R, adv, *args, logp_old=lp),
-        "clone_returns_nll": lambda: d.clone_step(None, s, a, R, "nll", None, *args),
-        "clone_policy_only_nll": lambda: d.clone_step(None, s, a, None, "nll", None, *args),
-        "plain_b": lambda: d.train_step(s, a, R, adv, *args, logp_old=lp),
-        "clone_returns_mse": lambda: d.clone_step(None, s, a, R, "mse", None, *args),
-        "clone_policy_only_mse": lambda: d.clone_step(None, s, a, None, "mse", None, *args),
-    }
-    if other is not None:
-        variants["plain_parent"] = lambda: other.train_step(s, a, R, adv, lp, *args)
+    t = {"s": up(0.5 * rng.standard_normal((M, DIN))), "a": up(rng.uniform(0, 1, (M, A))), "R": up(rng.standard_normal(M)), "adv": up(rng.standard_normal(M)),
+         "vo": up(rng.standard_normal(M)), "lp": torch.empty(M, device=dev), "mo": torch.empty(M, A, device=dev), "lp_out": torch.empty(M, device=dev),
+         "rows": torch.arange(M, device=dev, dtype=torch.int32), "stats": torch.zeros(N_STATS, device=dev, dtype=torch.float64),
+         "scratch": torch.zeros(d.stats_scratch_doubles(M), device=dev, dtype=torch.float64), "kl_stats": torch.zeros(N_KL_STATS, device=dev, dtype=torch.float64),
+         "kl_scratch": torch.zeros(d.kl_stats_scratch_doubles(M), device=dev, dtype=torch.float64)}
+    d.old_policy_cache(t["s"], t["a"], M, t["lp"], t["mo"])
+    variants = dict(this.variants(t, M, M == 2048))
+    if other is not None:                                    # the twins, interleaved with this build's windows (no second window of the plain step)
+        variants.update({k + "_parent": fn for k, fn in other.variants(t, M, M == 2048).items() if k != "plain_b"})
     res = ab(variants, iters)
-    base = res["plain_parent" if other is not None else "plain_a"]["median"]
+    base = res["plain_a_parent" if other is not None else "plain_a"]["median"]
     spread = abs(res["plain_a"]["median"] - res["plain_b"]["median"]) / base
     spread = max(spread, max((res[k]["max"] - res[k]["min"]) / res[k]["median"] for k in ("plain_a", "plain_b")))
     allow = max(0.02, spread)
-    res["summary"] = {"baseline": "plain_parent" if other is not None else "plain_a", "baseline_us": base, "plain_spread": spread, "allowance": allow,
+    res["summary"] = {"baseline": "plain_a_parent" if other is not None else "plain_a", "baseline_us": base, "plain_spread": spread, "allowance": allow,
                       "with_returns_over_plain": {k: res["clone_returns_" + k]["median"] / base - 1.0 for k in ("nll", "mse")},
                       "policy_only_over_plain": {k: res["clone_policy_only_" + k]["median"] / base - 1.0 for k in ("nll", "mse")}}
     res["summary"]["with_returns_within_allowance"] = all(v <= allow for v in res["summary"]["with_returns_over_plain"].values())
     res["summary"]["policy_only_below_plain"] = all(v < 0 for v in res["summary"]["policy_only_over_plain"].values())
+    if other is not None:
+        over = {k: res[k]["median"] / res[("plain_a" if k == "plain_b" else k) + "_parent"]["median"] - 1.0 for k in variants if not k.endswith("_parent")}
+        res["summary"]["over_parent_twin"] = over
+        res["summary"]["all_within_allowance_of_parent"] = all(v <= allow for v in over.values())
     out["step_M%d" % M] = res
-    for x, y in zip((d.params, d.adam_m, d.adam_v), state):
-        x.copy_(y)
+    this.restore()
+    if other is not None:
+        other.restore()
 
 os.makedirs(OUT, exist_ok=True)
 json.dump(out, open(os.path.join(OUT, "clone_latency.json"), "w"), indent=1)
@@ -130,7 +165,7 @@ for k, v in out.items():
         continue
     print(k)
     for kk, vv in v.items():
-        print("   %-24s %s" % (kk, "median %9.2f us  min %9.2f  max %9.2f" % (vv["median"], vv["min"], vv["max"]) if "median" in vv else json.dumps(vv)))
+        print("   %-28s %s" % (kk, "median %9.2f us  min %9.2f  max %9.2f" % (vv["median"], vv["min"], vv["max"]) if "median" in vv else json.dumps(vv)))
 if other is not None:
-    other.cdll.mi_ppo_destroy(other.handle)
+    other.close()
 d.close()

@@ -1,9 +1,17 @@
-"""Bit-for-bit digest of the PPO minibatch-step entries (profiles/r25_ppo_step_routes.md): every entry x {contiguous tensors, table rows} x M in (5, 33, 256, 257)
-x gradient-norm limit in (None, 0.5, inf) x {fp32, bf16x3} on the reference shape (67 -> 500 / 300, 2 actions) with seeded inputs.  A cell starts from the same
-parameters, zero optimiser state and a gradient buffer of 4.25, runs three consecutive steps and prints one JSON line: the CRC-32C (mi_crc32c over the host copy) of
-params, m, v, the gradient buffer, losses, kl_losses, grad_clip and value_head_grad[:M].  Two builds compute the same steps iff their outputs are the same text.
+"""Bit-for-bit digest of the PPO entries that run the kernels of csrc/ppo_fused.hip (profiles/r25_ppo_step_routes.md, profiles/r35_ppo_head_helpers.md), with seeded
+inputs, on two shapes: the reference's (67 -> 500 / 300, 2 actions: the NA = 2 instantiations) and the small one of the cloning tests (5 -> 36 / 20, 3 actions: the
+NA = 8 instantiations).  Two builds compute the same thing iff their outputs are the same text.
 
-    python tools/ppo_step_digest.py [--time-limit 300] > digest.jsonl      # one process, no retries; the alarm ends a run that takes longer"""
+Step cells: every minibatch-step entry x {contiguous tensors, table rows} x M in (5, 33, 256, 257) x gradient-norm limit in (None, 0.5, inf) x {fp32, bf16x3}; at
+M = 5 and 33 also clone_step over {nll, mse} x {with returns, policy only} x {adam 1, adam 0}.  A cell starts from the same parameters, zero optimiser state and a
+gradient buffer of 4.25, runs three consecutive steps and prints one JSON line: the CRC-32C (mi_crc32c over the host copy) of params, m, v, the gradient buffer,
+losses, kl_losses, grad_clip and value_head_grad[:M].
+
+Head cells, at M = 5 (the wave-per-sample predict kernel) and 33, per precision: old_policy_cache (both outputs), logp_old, update_stats (the sums and the two
+optional tables), kl_stats, predict sampled with given noise and greedy; one JSON line each with the CRC-32C of every output.
+
+    python tools/ppo_step_digest.py [--time-limit 600] > digest.jsonl      # one process, no retries; the alarm ends a run that takes longer
+    MI355_LIB=<another build's library> python tools/ppo_step_digest.py    # the same cells from that build (the C ABI has to be this tree's)"""
 import argparse
 import ctypes
 import json
@@ -19,19 +27,19 @@ for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
     sys.path.insert(0, p)
 from mi355 import lib as milib  # noqa: E402
 from mi355.init import init_ppo  # noqa: E402
-from mi355.ppo_device import PpoDevice  # noqa: E402
+from mi355.ppo_device import N_KL_STATS, N_STATS, PpoDevice  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--time-limit", type=int, default=300, help="seconds; the process is ended by SIGALRM behind it")
+ap.add_argument("--time-limit", type=int, default=600, help="seconds; the process is ended by SIGALRM behind it")
 args = ap.parse_args()
 signal.alarm(args.time_limit)
 
-DIN, A, MAXB, STEPS = 67, 2, 320, 3
-MS, LIMITS = (5, 33, 256, 257), (None, 0.5, float("inf"))
+MAXB, STEPS = 320, 3
+SHAPES = (("A2", 67, 2, (500, 300)), ("A3", 5, 3, (36, 20)))
+MS, HEAD_MS, LIMITS = (5, 33, 256, 257), (5, 33), (None, 0.5, float("inf"))
 ALPHA, EPS_V, BETA, FILL = 1e-3, 0.2, 0.7, 4.25
 L = milib.get()
 dev = torch.device("cuda", 0)
-low, high = np.array([-1.0, 0.0], np.float32), np.array([1.0, 1.0], np.float32)
 hcomm, comm_log = ctypes.c_void_p(), np.zeros((64, 4), np.int64)
 L.mi_comm_init_recording(ctypes.addressof(hcomm), 0, 1, comm_log.ctypes.data, 64)
 
@@ -41,54 +49,98 @@ def crc(t):
     return int(L.mi_crc32c(0, b, len(b))) & 0xffffffff
 
 
-for precision in ("fp32", "bf16x3"):
-    rng = np.random.RandomState(25)
-    d = PpoDevice(DIN, A, low, high, 0.2, 1.0, 0.01, max_batch=MAXB, precision=precision)
-    th = init_ppo(1, DIN, A, 0.4)
-    d.load_params(th, {k.replace("policy/", "policy_old/", 1): (v + 0.02 * rng.standard_normal(v.shape)).astype(np.float32) for k, v in th.items()})
-    d.kl_losses.zero_()                                  # (workspace no step but train_step_kl writes)
-    start = [x.clone() for x in (d.params, d.adam_m, d.adam_v)]
-    up = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)      # noqa: E731
-    for M in MS:
-        flat = {"s": up(0.5 * rng.standard_normal((M, DIN))), "a": up(rng.uniform(0, 1, (M, A))), "R": up(rng.standard_normal(M)), "adv": up(rng.standard_normal(M)),
-                "vo": up(rng.standard_normal(M)), "lp": torch.empty(M, device=dev), "mo": torch.empty(M, A, device=dev)}
-        d.old_policy_cache(flat["s"], flat["a"], M, flat["lp"], flat["mo"])
-        n = 2 * M + 3
-        rows = torch.from_numpy(rng.permutation(n)[:M].astype(np.int32)).to(dev)
-        tab = {}
-        for k, x in flat.items():
-            tab[k] = up(0.5 * rng.standard_normal((n,) + tuple(x.shape[1:])))
-            tab[k][rows.long()] = x
-        a = (M, 1.0 / M, 1.0, ALPHA)
-        adam = lambda: d.apply_adam(ALPHA)      # noqa: E731
-        for form, t, r in (("contiguous", flat, None), ("rows", tab, rows)):
-            data = (t["s"], t["a"], t["R"], t["adv"])
-            vclip = lambda comm, **kw: d.train_step_vclip(comm, *data, t["lp"], t["vo"], EPS_V, r, *a, **kw)      # noqa: E731
-            kl = lambda comm, **kw: d.train_step_kl(comm, *data, t["lp"], t["mo"], BETA, r, *a, old_values=t["vo"], clip_range_vf=EPS_V, **kw)      # noqa: E731
-            entries = [("dp", lambda: d.train_step_dp(hcomm, *data, t["lp"], r, *a)), ("dp_no_cache", lambda: d.train_step_dp(hcomm, *data, None, r, *a)),
-                       ("vclip", lambda: vclip(None)), ("vclip_comm", lambda: vclip(hcomm)), ("vclip_adam0", lambda: (vclip(None, adam=False), adam())),
-                       ("vclip_comm_adam0", lambda: (vclip(hcomm, adam=False), adam())),
-                       ("kl", lambda: kl(None)), ("kl_comm", lambda: kl(hcomm)), ("kl_adam0", lambda: (kl(None, adam=False), adam())),
-                       ("kl_no_cache", lambda: d.train_step_kl(None, *data, None, None, BETA, r, *a))]
-            entries += [("vclip_gradients", lambda: vclip(None, adam=False)), ("kl_gradients", lambda: kl(None, adam=False))]      # the buffer before Adam zeroes it
-            if r is None:
-                fb = lambda: d.forward_backward(*data, M, 1.0 / M, 1.0)      # noqa: E731
-                entries += [("forward_backward_gradients", fb), ("forward_backward", lambda: (fb(), adam())),
-                            ("train_step", lambda: d.train_step(*data, *a, logp_old=t["lp"])), ("train_step_no_cache", lambda: d.train_step(*data, *a))]
-            else:
-                entries += [("train_step_idx", lambda: d.train_step_idx(*data, t["lp"], r, *a)), ("train_step_idx_no_cache", lambda: d.train_step_idx(*data, None, r, *a))]
-            for limit in LIMITS:
-                d.set_max_grad_norm(limit)
-                for name, step in entries:
-                    for x, y in zip((d.params, d.adam_m, d.adam_v), start):
-                        x.copy_(y)
-                    d.grads.fill_(FILL)
-                    for _ in range(STEPS):
-                        step()
-                    out = {"cell": "%s %s M=%d limit=%s %s" % (precision, form, M, limit, name)}
-                    for key, x in (("params", d.params), ("m", d.adam_m), ("v", d.adam_v), ("grads", d.grads), ("losses", d.losses), ("kl_losses", d.kl_losses),
-                                   ("grad_clip", d.grad_clip), ("value_head_grad", d.value_head_grad[:M])):
-                        out[key] = "%08x" % crc(x)
-                    print(json.dumps(out), flush=True)
-    d.close()
+def emit(cell, named):
+    out = {"cell": cell}
+    for key, x in named:
+        out[key] = "%08x" % crc(x)
+    print(json.dumps(out), flush=True)
+
+
+def head_cells(d, tag, M, A, flat, tab, rows):
+    """The forward-only entries under the start parameters: every output starts from a fill, so that an entry left unwritten shows."""
+    f32 = lambda *shape: torch.full(shape, FILL, device=dev)      # noqa: E731
+    f64 = lambda n: torch.full((n,), FILL, device=dev, dtype=torch.float64)      # noqa: E731
+    n = tab["s"].shape[0]
+    lp, mo = f32(M), f32(M, A)
+    d.old_policy_cache(flat["s"], flat["a"], M, lp, mo)
+    emit("%s M=%d old_policy_cache" % (tag, M), (("logp", lp), ("mean", mo)))
+    lp2 = f32(M)
+    d.logp_old(flat["s"], flat["a"], M, lp2)
+    emit("%s M=%d logp_old" % (tag, M), (("logp", lp2),))
+    for acc in (False, True):
+        stats, scratch, lpn, val = f64(N_STATS), f64(d.stats_scratch_doubles(M)), f32(n), f32(n)
+        d.update_stats(tab["s"], tab["a"], tab["R"], tab["lp"], rows, M, stats, scratch, accumulate=acc, logp_new_out=lpn, value_out=val)
+        emit("%s M=%d update_stats accumulate=%d" % (tag, M, acc), (("stats", stats), ("logp_new", lpn), ("value", val)))
+        stats, scratch = f64(N_KL_STATS), f64(d.kl_stats_scratch_doubles(M))
+        d.kl_stats(tab["s"], tab["mo"], rows, M, stats, scratch, accumulate=acc)
+        emit("%s M=%d kl_stats accumulate=%d" % (tag, M, acc), (("stats", stats),))
+    for greedy in (0, 1):
+        act, val = f32(M, A), f32(M)
+        d.predict(flat["s"], M, flat["noise"], greedy, act, val)
+        emit("%s M=%d predict greedy=%d" % (tag, M, greedy), (("action", act), ("value", val)))
+
+
+for shape, DIN, A, HIDDEN in SHAPES:
+    low = np.array([-1.0, 0.0, -0.5][:A], np.float32)
+    high = np.array([1.0, 1.0, 0.75][:A], np.float32)
+    for precision in ("fp32", "bf16x3"):
+        rng = np.random.RandomState(25)
+        d = PpoDevice(DIN, A, low, high, 0.2, 1.0, 0.01, hidden=HIDDEN, max_batch=MAXB, precision=precision)
+        th = init_ppo(1, DIN, A, 0.4, hidden=HIDDEN)
+        d.load_params(th, {k.replace("policy/", "policy_old/", 1): (v + 0.02 * rng.standard_normal(v.shape)).astype(np.float32) for k, v in th.items()})
+        d.kl_losses.zero_()                                  # (workspace no step but train_step_kl writes)
+        start = [x.clone() for x in (d.params, d.adam_m, d.adam_v)]
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)      # noqa: E731
+        tag = "%s %s" % (shape, precision)
+        for M in MS:
+            flat = {"s": up(0.5 * rng.standard_normal((M, DIN))), "a": up(rng.uniform(0, 1, (M, A))), "R": up(rng.standard_normal(M)), "adv": up(rng.standard_normal(M)),
+                    "vo": up(rng.standard_normal(M)), "lp": torch.empty(M, device=dev), "mo": torch.empty(M, A, device=dev)}
+            d.old_policy_cache(flat["s"], flat["a"], M, flat["lp"], flat["mo"])
+            n = 2 * M + 3
+            rows = torch.from_numpy(rng.permutation(n)[:M].astype(np.int32)).to(dev)
+            tab = {}
+            for k, x in flat.items():
+                tab[k] = up(0.5 * rng.standard_normal((n,) + tuple(x.shape[1:])))
+                tab[k][rows.long()] = x
+            if M in HEAD_MS:
+                flat["noise"] = up(rng.standard_normal((M, A)))
+                d.params.copy_(start[0])
+                head_cells(d, tag, M, A, flat, tab, rows)
+            a = (M, 1.0 / M, 1.0, ALPHA)
+            adam = lambda: d.apply_adam(ALPHA)      # noqa: E731
+            for form, t, r in (("contiguous", flat, None), ("rows", tab, rows)):
+                data = (t["s"], t["a"], t["R"], t["adv"])
+                vclip = lambda comm, **kw: d.train_step_vclip(comm, *data, t["lp"], t["vo"], EPS_V, r, *a, **kw)      # noqa: E731
+                kl = lambda comm, **kw: d.train_step_kl(comm, *data, t["lp"], t["mo"], BETA, r, *a, old_values=t["vo"], clip_range_vf=EPS_V, **kw)      # noqa: E731
+                entries = [("dp", lambda: d.train_step_dp(hcomm, *data, t["lp"], r, *a)), ("dp_no_cache", lambda: d.train_step_dp(hcomm, *data, None, r, *a)),
+                           ("vclip", lambda: vclip(None)), ("vclip_comm", lambda: vclip(hcomm)), ("vclip_adam0", lambda: (vclip(None, adam=False), adam())),
+                           ("vclip_comm_adam0", lambda: (vclip(hcomm, adam=False), adam())),
+                           ("kl", lambda: kl(None)), ("kl_comm", lambda: kl(hcomm)), ("kl_adam0", lambda: (kl(None, adam=False), adam())),
+                           ("kl_no_cache", lambda: d.train_step_kl(None, *data, None, None, BETA, r, *a))]
+                entries += [("vclip_gradients", lambda: vclip(None, adam=False)), ("kl_gradients", lambda: kl(None, adam=False))]      # the buffer before Adam zeroes it
+                if r is None:
+                    fb = lambda: d.forward_backward(*data, M, 1.0 / M, 1.0)      # noqa: E731
+                    entries += [("forward_backward_gradients", fb), ("forward_backward", lambda: (fb(), adam())),
+                                ("train_step", lambda: d.train_step(*data, *a, logp_old=t["lp"])), ("train_step_no_cache", lambda: d.train_step(*data, *a))]
+                else:
+                    entries += [("train_step_idx", lambda: d.train_step_idx(*data, t["lp"], r, *a)), ("train_step_idx_no_cache", lambda: d.train_step_idx(*data, None, r, *a))]
+                if M in HEAD_MS:
+                    for kind in ("nll", "mse"):
+                        for what, R in (("returns", t["R"]), ("policy_only", None)):
+                            for on in (True, False):
+                                entries.append(("clone_%s_%s_adam%d" % (kind, what, on),
+                                                lambda kind=kind, R=R, on=on: d.clone_step(None, t["s"], t["a"], R, kind, r, *a, adam=on)))
+                for limit in LIMITS:
+                    d.set_max_grad_norm(limit)
+                    for name, step in entries:
+                        for x, y in zip((d.params, d.adam_m, d.adam_v), start):
+                            x.copy_(y)
+                        d.grads.fill_(FILL)
+                        for _ in range(STEPS):
+                            step()
+                        emit("%s %s M=%d limit=%s %s" % (tag, form, M, limit, name),
+                             (("params", d.params), ("m", d.adam_m), ("v", d.adam_v), ("grads", d.grads), ("losses", d.losses), ("kl_losses", d.kl_losses),
+                              ("grad_clip", d.grad_clip), ("value_head_grad", d.value_head_grad[:M])))
+                d.set_max_grad_norm(None)
+        d.close()
 L.mi_comm_destroy(hcomm)
