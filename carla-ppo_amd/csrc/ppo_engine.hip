@@ -30,6 +30,7 @@ struct PpoEngine {
     long long gn_part, clip;                      // global-norm clipping: the block partials of the sum of squares (doubles), and {norm, scale, c, 0} of the last norm (mi_ppo_buffer(h, 2))
     float max_grad_norm;                          // 0 (calloc: the default): no clipping; > 0 or +inf: mi_ppo_apply_adam clips by the global norm (mi_ppo_set_max_grad_norm)
     long long f_klpart;                           // KL penalty (mi_ppo_train_step_kl): one float per loss block
+    long long f_demopart, f_demo;                 // demonstration term (mi_ppo_train_step_demo): two floats per loss block, and [demo_loss, c_d demo_loss, mean_sq_error] (mi_ppo_buffer(h, 4))
     long long wg_scr[2], wg_bytes;                // per-layer path: row-split slabs of its filter and bias gradients (mi_gemm_wgrad_bias_ws), one piece per stream of the backward pass
     long long f_h1, f_h2, f_dh1, f_dh2, f_part;   // fused step (ppo_fused.hip): [3][M][H1], [3][M][H2], [2][M][H1], [2][M][H2], loss-block partials
     int last_M;
@@ -67,6 +68,7 @@ void layout(PpoEngine& e) {
     e.f_gslab = wa(M > 256 ? ((M + 255) / 256) * e.total * 4 : 0);
     e.gn_part = wa(MI_GRAD_NORM_BLOCKS * 8); e.clip = wa(16);
     e.f_klpart = wa(((M + 31) / 32) * 4);
+    e.f_demopart = wa(((M + 31) / 32) * 8); e.f_demo = wa(16);
     // the per-layer path's filter gradients, with the bias gradient as one more row of the same product (mi_gemm_wgrad_bias_ws: no column-sum launches), sum their
     // row splits through slabs in a fixed order, not through fp32 atomics: two runs are bitwise equal, as on the fused path.  One piece per stream, sized for the
     // largest layer of a side at the row count with the most splits (the launches of a side are ordered on its stream)
@@ -271,10 +273,11 @@ void mi_ppo_destroy(void* h) {
 
 // 0 losses[5] (policy, value, entropy, total, mean ratio)   1 action_mean [M,A] of the last predict   2 {norm, scale, c, 0} of the last gradient norm
 // 3 dv [M] of the last step: d loss / d value-head output per sample (workspace of the step; what value clipping zeroes)
+// 4 [demo_loss, c_d demo_loss, mean_sq_error] of the last mi_ppo_train_step_demo
 void* mi_ppo_buffer(void* h, int which) {
     PpoEngine* e = (PpoEngine*)h;
     if (!e) return nullptr;
-    return which == 0 ? e->at(e->losses) : which == 1 ? e->at(e->mean) : which == 2 ? e->at(e->clip) : which == 3 ? e->at(e->dv) : nullptr;
+    return which == 0 ? e->at(e->losses) : which == 1 ? e->at(e->mean) : which == 2 ? e->at(e->clip) : which == 3 ? e->at(e->dv) : which == 4 ? e->at(e->f_demo) : nullptr;
 }
 
 // PPO.update_old_policy (ppo.py:275-276): theta_old <- theta, one device copy of the flat buffer
@@ -491,6 +494,42 @@ int mi_ppo_clone_step(void* h, void* comm, void* stream, const float* states, co
     // no old policy (net 2 is not run), no advantage, no entropy term; policy only: net 0 alone through the whole chain
     q.clone = 1 + kind; q.entropy_scale = 0.f;
     q.n_nets = q.n_wnets = returns ? 2 : 1;
+    return route_step(e, stream, q, comm, adam, alpha, beta1, beta2, epsilon);
+}
+
+// The PPO step with a demonstration term (include/mi355_carla.h; the definition is in ppo_fused.hip's head / loss kernel, DEMO): M PPO rows and M_demo demonstration
+// rows in ONE fused chain over M + M_demo rows -- a staging launch gathers the state rows of the two tables, the trunks, ppo_head_demo*_kernel (per sample the PPO or the
+// clone arithmetic), the layer-1 input gradient, the weight gradients -- one gradient, one Adam update.  ONE entry for every form, as mi_ppo_train_step_kl is, on
+// route_step's routes with M + M_demo in the place of M.  Every refusal stands in front of the first launch.  Fused kernels only.
+int mi_ppo_train_step_demo(void* h, void* comm, void* stream, const float* states, const float* actions, const float* returns, const float* advantage,
+                           const float* logp_old, const float* mean_old, int kl_on, float kl_coef, const float* old_values, float clip_range_vf,
+                           const int* row_idx, int n_rows, int M, const float* demo_states, const float* demo_actions, const int* demo_row_idx, int n_demo_rows, int M_demo,
+                           int demo_kind, float demo_coef, float inv_m_demo, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step_demo: null handle");
+    // (what needs no engine is checked before the handle is looked at)
+    if (M < 1 || (row_idx && n_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: batch outside [1, max_batch] or empty tables");
+    if (M_demo < 1 || (demo_row_idx && n_demo_rows < 1)) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: M_demo is at least 1 and the demonstration tables are not empty");
+    if (!states || !actions || !returns || !advantage) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: missing buffers (states, actions, returns, advantage)");
+    if (!demo_states || !demo_actions) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: missing buffers (demo_states, demo_actions)");
+    if (demo_kind != 0 && demo_kind != 1) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: demo_kind is 0 (the Gaussian negative log-likelihood) or 1 (the squared error of the mean)");
+    if (!(demo_coef >= 0.f) || !(demo_coef <= 3.402823466e+38f)) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: demo_coef is a finite float >= 0");
+    if (!(inv_m_demo > 0.f)) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: inv_m_demo is 1 / M_demo(global), a positive float");
+    if (kl_on != 0 && kl_on != 1) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: kl_on is 0 (no KL penalty) or 1");
+    if (kl_on && (logp_old != nullptr) != (mean_old != nullptr))
+        return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: with kl_on, logp_old and mean_old come together (mi_ppo_old_policy_cache) or are both NULL (the step evaluates the old policy)");
+    if (kl_on && (!(kl_coef >= 0.f) || !(kl_coef <= 3.402823466e+38f))) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: kl_coef is a finite float >= 0 (0: measure the KL, add nothing)");
+    if (old_values && !(clip_range_vf > 0.f)) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: with old_values, clip_range_vf is a positive float or +inf");
+    if (adam != 0 && adam != 1) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: adam is 0 (stop with the gradients in the flat buffer) or 1 (apply the optimiser)");
+    if ((long long)M + M_demo > e->d.max_batch) return mi_fail(MI_ERR_ARG, "mi_ppo_train_step_demo: M + M_demo exceeds max_batch");
+    if (!e->grads || (adam && (!e->m || !e->v))) return mi_fail(MI_ERR_STATE, "mi_ppo_train_step_demo: engine created without gradient / optimiser buffers");
+    if (!fused_enabled(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_train_step_demo: needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0): there is no per-layer form of the demonstration term");
+    PpoFusedParams q; fill_step(e, q, states, actions, returns, advantage, logp_old, row_idx, n_rows, M + M_demo, inv_m, grad_scale, old_values, clip_range_vf,
+                                kl_on != 0, kl_coef, kl_on ? mean_old : nullptr);
+    q.m_ppo = M; q.demo_kind = demo_kind; q.demo_coef = demo_coef; q.inv_m_demo = inv_m_demo;
+    q.demo_states = demo_states; q.demo_actions = demo_actions; q.demo_row_idx = demo_row_idx; q.n_demo_rows = n_demo_rows;
+    q.demo_partial = (float*)e->at(e->f_demopart); q.demo_out = (float*)e->at(e->f_demo);
+    q.s_gath = (float*)e->at(e->s_pad);                    // the staged rows of both tables (with and without row lists)
     return route_step(e, stream, q, comm, adam, alpha, beta1, beta2, epsilon);
 }
 

@@ -10,9 +10,12 @@
 //                         one spare wave finalises the loss scalars and logstd
 // Behaviour cloning (mi_ppo_clone_step) is the same chain with ppo_head_clone_kernel in the third place -- a supervised loss on the expert's actions -- and, without
 // returns, with net 0 alone in every launch (PpoFusedParams::n_wnets).
+// The step with a demonstration term (mi_ppo_train_step_demo) is the same chain over M PPO rows + M_demo demonstration rows with ppo_head_demo*_kernel in the third
+// place -- the loss body with DEMO = true, which takes the PPO or the clone arithmetic per sample -- and ONE staging launch in front (ppo_demo_stage_kernel gathers
+// the state rows of the two tables into [M + M_demo, din]; the layer-1 kernels then read a contiguous minibatch, unchanged).
 //
 // The head-level kernels are built from the helpers of ppo_head.hpp, each shared piece written once:
-//   ppo_head_loss_body (ppo_head_loss[_kl][_vclip]_kernel) and ppo_head_clone_kernel:  pf_head_rows, pf_stage_request / pf_stage_commit, pf_head_sums,
+//   ppo_head_loss_body (ppo_head_loss[_kl][_vclip]_kernel, ppo_head_demo[_kl][_vclip]_kernel) and ppo_head_clone_kernel:  pf_head_rows, pf_stage_request / pf_stage_commit, pf_head_sums,
 //       pf_fast_tanh, pf_block_partials, pf_head_dh2; between them each kernel keeps only its own gathers and its per-sample loss terms.  The loss body's
 //       old-policy block also calls pf_mean_libm / pf_logp_term_libm
 //   ppo_predict_head_kernel, ppo_update_stats_head_kernel, ppo_kl_stats_head_kernel:  pf_head_sums_strided, pf_mean_libm, pf_logp_term_libm -- the one spelling the
@@ -356,17 +359,27 @@ __global__ __launch_bounds__(256) void ppo_l2_kernel(const PpoFusedParams q) {
 // (tanhf, the cache kernel's spelling: both sources give the same mu_o).  lso comes from theta_old in both.  The block's sum of KL[m] (samples in order, one
 // thread) goes to q.kl_partial[block]; ppo_wgrad_kernel's spare wave adds those in block order.  beta = 0 measures: every added term is 0.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NA, bool VCLIP, bool KLP>
+//
+// DEMO (ppo_head_demo[_kl][_vclip]_kernel; mi_ppo_train_step_demo): the step over M = m_ppo + M_demo rows of which rows m >= q.m_ppo are DEMONSTRATION rows.  A
+// demonstration row takes the arithmetic of ppo_head_clone_kernel (policy only), operation for operation, with inv_m_demo in the place of inv_m, and then the
+// weight c_d = q.demo_coef on du and on the logstd term: it gathers its expert action from q.demo_actions at row demo_row_idx[m - m_ppo] (clamped; nullptr:
+// row m - m_ppo), reads no return, advantage, old policy or value target, leaves dv = 0.0 exactly, slots 0 - 2 and the action-mean slots of the block partials 0
+// (the PPO scalars are over PPO rows), KL[m] = 0, and its l[m] and squared error in sdemo -> q.demo_partial[block][2], added in block order by ppo_wgrad_kernel's
+// spare wave.  The 8 lanes of a sample take one path; the one wave that holds row m_ppo diverges.  With DEMO = false nothing of this is compiled: the eight
+// kernels of the other entries are the code they were.
+template <int NA, bool VCLIP, bool KLP, bool DEMO = false>
 __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
     __shared__ __attribute__((aligned(16))) float sWm[PF_H2MAX * PF_MAX_ACT], sWo[PF_H2MAX * PF_MAX_ACT], sWv[PF_H2MAX];
     __shared__ float su[32][NA], sv[32], sdu[32][NA], sdv[32], spart[32][PF_NPART];
     __shared__ float skl[KLP ? 32 : 1];                   // KLP: KL[m] of the block's samples
+    __shared__ float sdemo[DEMO ? 32 : 1][2];             // DEMO: l[m] and the squared error of the block's demonstration rows (0 at PPO rows)
     const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
     const float* __restrict__ bm = q.theta + q.off[5]; const float* __restrict__ bmo = q.theta_old + q.off[5]; const float* __restrict__ bv = q.theta + q.off[12];
     const float* __restrict__ h2o = q.h2 + 2ll * q.M * H2;
     const bool old_net = q.logp_old == nullptr;
     const int sm = tid >> 3, part = tid & 7, m = m0 + sm;
     const bool mok = m < q.M;
+    const bool demo = DEMO && mok && m >= q.m_ppo;        // a demonstration row (all 8 lanes of the sample agree)
     f32x4 hp[PF_NV], hv[PF_NV];
     pf_head_rows<PF_NV, true>(q, m, mok, part, hp, hv);
     // the old policy's row (only without a cached log pi_old), requested with the others: this thread's columns are j = part, part + 8, .. as in the kernel that
@@ -384,17 +397,21 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
     PfHeadStage<NA> st;
     pf_stage_request<NA, true, true>(q, tid, old_net, st);
     float p_act[NA], p_adv_s = 0.f, p_ret_s = 0.f, p_lpo_s = 0.f, p_vold_s = 0.f, p_muo_s = 0.f, p_ls[NA], p_lso[NA], p_lo[NA], p_hi[NA];
-    const int mr = (q.row_idx && mok) ? min(max(q.row_idx[m], 0), q.n_rows - 1) : m;     // the sample's row in the horizon-batch tables (actions / returns / advantages / cached log pi_old)
+    int mr = (q.row_idx && mok) ? min(max(q.row_idx[m], 0), q.n_rows - 1) : m;     // the sample's row in the horizon-batch tables (actions / returns / advantages / cached log pi_old)
+    const float* __restrict__ acts = q.actions;
+    if constexpr (DEMO) {                                 // ... or in the demonstration tables
+        if (demo) { mr = q.demo_row_idx ? min(max(q.demo_row_idx[m - q.m_ppo], 0), q.n_demo_rows - 1) : m - q.m_ppo; acts = q.demo_actions; }
+    }
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
         const bool aok = a < A;
-        p_act[a] = (mok && aok) ? q.actions[(long long)mr * A + a] : 0.f;
+        p_act[a] = (mok && aok) ? acts[(long long)mr * A + a] : 0.f;
         p_ls[a] = aok ? q.theta[q.off[6] + a] : 0.f; p_lso[a] = (aok && (old_net || KLP)) ? q.theta_old[q.off[6] + a] : 0.f;
         p_lo[a] = aok ? q.low[a] : 0.f; p_hi[a] = aok ? q.high[a] : 0.f;
     }
-    if (mok) { p_adv_s = q.adv[mr]; p_ret_s = q.returns[mr]; if (!old_net) p_lpo_s = q.logp_old[mr]; }
-    if constexpr (VCLIP) { if (mok) p_vold_s = q.v_old[mr]; }
-    if constexpr (KLP) { if (mok && !old_net && part < A) p_muo_s = q.mean_old[(long long)mr * A + part]; }
+    if (mok && !demo) { p_adv_s = q.adv[mr]; p_ret_s = q.returns[mr]; if (!old_net) p_lpo_s = q.logp_old[mr]; }
+    if constexpr (VCLIP) { if (mok && !demo) p_vold_s = q.v_old[mr]; }
+    if constexpr (KLP) { if (mok && !demo && !old_net && part < A) p_muo_s = q.mean_old[(long long)mr * A + part]; }
     pf_stage_commit<NA, true>(q, tid, st, sWm, sWo, sWv);
     __syncthreads();
     float lp_old_s = 0.f;
@@ -439,7 +456,46 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
     // ---- per-sample loss terms: lane `part` of a sample's 8 threads owns action `part` of the new policy, the terms meet by shuffles (log pi_old: lp_old_s above, or the cache).
     //      exp / log / tanh through the hardware transcendental units (v_exp_f32 / v_log_f32: ~1 ulp; tanh(u) = 1 - 2 / (e^2u + 1)): the
     //      libm sequences are ~100-instruction dependent chains, which at one wave per block was most of this kernel ----
-    {
+    if (DEMO && demo) {
+        // a demonstration row: ppo_head_clone_kernel's terms (policy only), then the weight c_d
+        float act = 0.f, ls = 0.f, lo = 0.f, hi = 0.f;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) if (a == part) { act = p_act[a]; ls = p_ls[a]; lo = p_lo[a]; hi = p_hi[a]; }
+        float l = 0.f, sq = 0.f, d = 0.f, dls = 0.f, mean = 0.f;
+        const bool aok = part < A;
+        if (aok) {
+            const float t = pf_fast_tanh(su[sm][part < NA ? part : 0]);
+            mean = lo + ((t + 1.0f) * 0.5f) * (hi - lo);
+            const float diff = mean - act, sl = (0.5f * (hi - lo)) * (1.0f - t * t);
+            sq = diff * diff;
+            if (q.demo_kind == 1) {
+                l = sq;
+                d = (2.0f * diff) * sl * q.inv_m_demo;
+            } else {
+                const float sigma = __expf(ls);
+                const float z = (act - mean) / sigma;
+                l = 0.5f * z * z + (ls + PF_HALF_LOG_2PI);
+                d = -((z / sigma) * sl) * q.inv_m_demo;
+                dls = (1.0f - z * z) * q.inv_m_demo;
+            }
+            d *= q.demo_coef; dls *= q.demo_coef;
+            if (q.mean_out) q.mean_out[(long long)m * A + part] = mean;
+        }
+#pragma unroll
+        for (int o = 4; o > 0; o >>= 1) { l += __shfl_xor(l, o, 64); sq += __shfl_xor(sq, o, 64); }
+        if (part < NA) sdu[sm][part < NA ? part : 0] = aok ? d : 0.f;
+        if (aok) q.du[(long long)m * A + part] = d;
+#pragma unroll
+        for (int k = part; k < PF_NPART; k += 8) spart[sm][k] = 0.f;
+        __builtin_amdgcn_wave_barrier();
+        if (part == 0) {
+            sdv[sm] = 0.f; q.dv[m] = 0.f;
+            if constexpr (KLP) skl[sm] = 0.f;
+            if (q.logp_out) q.logp_out[m] = 0.f;
+            sdemo[sm][0] = l; sdemo[sm][1] = sq;
+        }
+        if (aok) spart[sm][3 + part] = dls;
+    } else {
         float lp_n = 0.f, dl = 0.f, zsq = 0.f, mean = 0.f;
         float act = 0.f, ls = 0.f, lo = 0.f, hi = 0.f;
         float lso = 0.f, kl = 0.f, kdu = 0.f, kdls = 0.f;  // KLP: this lane's old logstd, KL[m,part] and the penalty's du / dlogstd terms (without beta inv_m)
@@ -497,6 +553,7 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
         if (part == 0) {
             sdv[sm] = dvm;
             if constexpr (KLP) skl[sm] = mok ? kl : 0.f;
+            if constexpr (DEMO) { sdemo[sm][0] = 0.f; sdemo[sm][1] = 0.f; }
             if (mok) { q.dv[m] = dvm; if (q.logp_out) q.logp_out[m] = lp_n; spart[sm][0] = fminf(s1, s2); spart[sm][1] = lv; spart[sm][2] = r; }
         }
         if (aok) {
@@ -514,12 +571,37 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
             q.kl_partial[blockIdx.x] = sum;
         }
     }
+    if constexpr (DEMO) {
+        if (tid == 33 || tid == 34) {                     // the block's demonstration sums, samples in order
+            float sum = 0.f;
+            for (int i = 0; i < 32; ++i) sum += sdemo[i][tid - 33];
+            q.demo_partial[(long long)blockIdx.x * 2 + (tid - 33)] = sum;
+        }
+    }
     pf_head_dh2<NA, PF_NV, true>(q, sWm, sWv, sdu, sdv, hp, hv, m, mok, sm, part);
 }
 template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, false, false>(q); }
 template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_vclip_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, true, false>(q); }
 template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kl_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, false, true>(q); }
 template <int NA> __global__ __launch_bounds__(256) void ppo_head_loss_kl_vclip_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, true, true>(q); }
+template <int NA> __global__ __launch_bounds__(256) void ppo_head_demo_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, false, false, true>(q); }
+template <int NA> __global__ __launch_bounds__(256) void ppo_head_demo_vclip_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, true, false, true>(q); }
+template <int NA> __global__ __launch_bounds__(256) void ppo_head_demo_kl_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, false, true, true>(q); }
+template <int NA> __global__ __launch_bounds__(256) void ppo_head_demo_kl_vclip_kernel(const PpoFusedParams q) { ppo_head_loss_body<NA, true, true, true>(q); }
+
+// the rows the demonstration step's chain reads: out [M, din], row m < m_ppo = PPO state row row_idx[m] (clamped; nullptr: m), row m >= m_ppo = demonstration
+// state row demo_row_idx[m - m_ppo] (likewise).  One thread per element, 64-bit offsets into the tables; a row no index names is never read
+__global__ __launch_bounds__(256) void ppo_demo_stage_kernel(const float* __restrict__ states, const int* __restrict__ row_idx, int n_rows, int m_ppo,
+                                                             const float* __restrict__ demo_states, const int* __restrict__ demo_row_idx, int n_demo_rows, int M, int din,
+                                                             float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)M * din) return;
+    const int m = (int)(i / din), k = (int)(i - (long long)m * din);
+    float v;
+    if (m < m_ppo) { const long long r = row_idx ? min(max(row_idx[m], 0), n_rows - 1) : m; v = states[r * din + k]; }
+    else { const int md = m - m_ppo; const long long r = demo_row_idx ? min(max(demo_row_idx[md], 0), n_demo_rows - 1) : md; v = demo_states[r * din + k]; }
+    out[i] = v;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // CLONE (ppo_head_clone_kernel; mi_ppo_clone_step): behaviour cloning, the supervised form of the head / loss kernel.  A kernel of its own, built from the same
@@ -682,7 +764,9 @@ __global__ __launch_bounds__(256) void ppo_wgrad_kernel(const PpoFusedParams q) 
         float col = 0.f;
         if (lane < PF_NPART) for (int b = 0; b < q.n_loss_blocks; ++b) col += q.partial[(long long)b * PF_NPART + lane];
         else if (lane == PF_NPART && q.kl_on) for (int b = 0; b < q.n_loss_blocks; ++b) col += q.kl_partial[b];      // the KL penalty's block sums, on a lane of their own
+        else if (lane > PF_NPART && lane <= PF_NPART + 2 && q.m_ppo) for (int b = 0; b < q.n_loss_blocks; ++b) col += q.demo_partial[(long long)b * 2 + (lane - PF_NPART - 1)];      // the demonstration term's two
         const float kl_sum = __shfl(col, PF_NPART, 64);
+        const float demo_l = __shfl(col, PF_NPART + 1, 64), demo_sq = __shfl(col, PF_NPART + 2, 64);
         float sum[PF_NPART];
 #pragma unroll
         for (int k = 0; k < PF_NPART; ++k) sum[k] = __shfl(col, k, 64);
@@ -694,12 +778,18 @@ __global__ __launch_bounds__(256) void ppo_wgrad_kernel(const PpoFusedParams q) 
         if (lane != 0) return;
         const float pl = sum[0] * q.inv_m, vl = sum[1] * q.inv_m * q.value_scale, el = ent * q.entropy_scale;
         float* L = q.losses;                               // [0..4] policy, value, entropy, total, mean ratio ; [5..5+A) mean action_mean ; [5+A..5+2A) std
-        L[0] = pl; L[1] = vl; L[2] = el; L[3] = q.clone ? pl + vl : -pl + vl - el; L[4] = sum[2] * q.inv_m;      // (clone step: [clone_loss, value_loss, 0, loss, mean_sq_error])
+        float tot = q.clone ? pl + vl : -pl + vl - el;
+        L[0] = pl; L[1] = vl; L[2] = el; L[3] = tot; L[4] = sum[2] * q.inv_m;      // (clone step: [clone_loss, value_loss, 0, loss, mean_sq_error])
 #pragma unroll
         for (int a = 0; a < PF_MAX_ACT; ++a) if (a < q.A) { L[5 + a] = sum[3 + PF_MAX_ACT + a] * q.inv_m; L[5 + q.A + a] = sd[a]; }
         if (q.kl_on) {                                    // [5+2A] mean KL(pi_old || pi), [5+2A+1] beta x that, which the total loss also takes
             const float klm = kl_sum * q.inv_m, pen = q.kl_coef * klm;
-            L[5 + 2 * q.A] = klm; L[5 + 2 * q.A + 1] = pen; L[3] = (-pl + vl - el) + pen;
+            tot = (-pl + vl - el) + pen;
+            L[5 + 2 * q.A] = klm; L[5 + 2 * q.A + 1] = pen; L[3] = tot;
+        }
+        if (q.m_ppo) {                                    // the demonstration term: [demo_loss, c_d demo_loss, mean_sq_error] to a buffer of its own; the total takes the weighted term
+            const float dlm = demo_l * q.inv_m_demo, dw = q.demo_coef * dlm;
+            q.demo_out[0] = dlm; q.demo_out[1] = dw; q.demo_out[2] = demo_sq * q.inv_m_demo; L[3] = tot + dw;
         }
         // the entropy term is state independent: under data parallelism grad_scale = local_M / global_M shares it across the ranks
 #pragma unroll
@@ -1040,6 +1130,10 @@ static inline int ppo_pad(hipStream_t, float*) { return MI_OK; }
 //   PPO: by the KL-penalised surrogate (KLP: mi_ppo_train_step_kl) and the clipped value loss (VCLIP: v_old given; mi_ppo_train_step_vclip)
 typedef void (*pf_head_kernel_t)(const PpoFusedParams);
 static pf_head_kernel_t pf_step_head_kernel(const PpoFusedParams& q) {
+    static const pf_head_kernel_t demo_table[8] = {       // the demonstration step (m_ppo > 0): [4 KLP + 2 VCLIP] + (A == 2)
+        ppo_head_demo_kernel<PF_MAX_ACT>, ppo_head_demo_kernel<2>, ppo_head_demo_vclip_kernel<PF_MAX_ACT>, ppo_head_demo_vclip_kernel<2>,
+        ppo_head_demo_kl_kernel<PF_MAX_ACT>, ppo_head_demo_kl_kernel<2>, ppo_head_demo_kl_vclip_kernel<PF_MAX_ACT>, ppo_head_demo_kl_vclip_kernel<2>};
+    if (q.m_ppo) return demo_table[4 * (q.kl_on != 0) + 2 * (q.v_old != nullptr) + (q.A == 2)];
     static const pf_head_kernel_t table[12] = {           // [clone ? 8 + 2 VAL : 4 KLP + 2 VCLIP] + (A == 2)
         ppo_head_loss_kernel<PF_MAX_ACT>, ppo_head_loss_kernel<2>, ppo_head_loss_vclip_kernel<PF_MAX_ACT>, ppo_head_loss_vclip_kernel<2>,
         ppo_head_loss_kl_kernel<PF_MAX_ACT>, ppo_head_loss_kl_kernel<2>, ppo_head_loss_kl_vclip_kernel<PF_MAX_ACT>, ppo_head_loss_kl_vclip_kernel<2>,
@@ -1057,12 +1151,24 @@ int mi_ppo_fused_step(hipStream_t st, PpoFusedParams& q, int fuse_adam, bool x3)
         return mi_fail(MI_ERR_ARG, "ppo fused step: the KL penalty needs its partial buffer, and logp_old / mean_old both or neither");
     if (q.n_wnets != 1 && q.n_wnets != 2) return mi_fail(MI_ERR_ARG, "ppo fused step: n_wnets is 2, or 1 for the policy-only clone step");
     if (q.n_wnets == 1 && !(q.clone && !q.returns)) return mi_fail(MI_ERR_ARG, "ppo fused step: only the clone step without returns leaves the value net out");
+    if (q.m_ppo && (q.clone || q.m_ppo < 1 || q.m_ppo >= q.M || !q.demo_states || !q.demo_actions || !q.demo_partial || !q.demo_out || !q.s_gath ||
+                    (q.demo_row_idx && q.n_demo_rows < 1) || (q.demo_kind != 0 && q.demo_kind != 1)))
+        return mi_fail(MI_ERR_ARG, "ppo fused step: the demonstration term needs PPO rows and demonstration rows, both demonstration tables, its buffers and a kind of 0 / 1");
     q.n_loss_blocks = (q.M + 31) / 32;
+    // the demonstration step: one staging launch gathers the M = m_ppo + M_demo state rows of the two tables; every launch but the head kernel then reads them as a
+    // contiguous minibatch (the layer-1 kernels are the code and the launches of the other entries), the head kernel keeps both row lists for its scalar gathers
+    PpoFusedParams qh = q;
+    if (q.m_ppo) {
+        const long long n = (long long)q.M * q.din;
+        hipLaunchKernelGGL(ppo_demo_stage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q.states, q.row_idx, q.n_rows, q.m_ppo,
+                           q.demo_states, q.demo_row_idx, q.n_demo_rows, q.M, q.din, q.s_gath);
+        q.states = q.s_gath; q.row_idx = nullptr;
+    }
     int rc = mi_ppo_fused_trunks(st, q, x3);
     if (rc != MI_OK) return rc;
     rc = ppo_pad(st, q.losses);
     if (rc != MI_OK) return rc;
-    hipLaunchKernelGGL(pf_step_head_kernel(q), dim3(q.n_loss_blocks), dim3(256), 0, st, q);
+    hipLaunchKernelGGL(pf_step_head_kernel(qh), dim3(q.n_loss_blocks), dim3(256), 0, st, qh);
     if (x3) hipLaunchKernelGGL(ppo_dh1_kernel<true>, dim3((q.H1 + 31) / 32, q.n_wnets, (q.M + 31) / 32), dim3(256), 0, st, q);
     else hipLaunchKernelGGL(ppo_dh1_kernel<false>, dim3((q.H1 + 31) / 32, q.n_wnets, (q.M + 31) / 32), dim3(256), 0, st, q);
     rc = ppo_pad(st, q.losses);

@@ -45,8 +45,18 @@ struct PpoFusedParams {
     // `actions` the expert's; returns == nullptr then means policy only.  n_wnets: the nets the backward half covers -- the layer-1 input-gradient grid and the
     // weight-gradient tiles in front of the spare wave: 2 in every step but the policy-only clone step, which runs net 0 alone (1)
     int clone, n_wnets;
+    // demonstration term (mi_ppo_train_step_demo; appended likewise).  m_ppo: 0 = no demonstration rows; > 0: rows [0, m_ppo) of the M = m_ppo + M_demo rows of
+    // the chain are PPO rows, the rest demonstration rows, and the ppo_head_demo kernels run.  The chain reads the staged rows (ppo_demo_stage_kernel: `states` of the
+    // launches other than the head is the engine's [M, din] staging buffer, their row_idx is nullptr); the head kernel alone keeps row_idx / n_rows (the PPO tables)
+    // and demo_row_idx / n_demo_rows (the demonstration tables demo_states / demo_actions; nullptr: contiguous).  demo_kind: 0 "nll", 1 "mse"; demo_coef = c_d;
+    // inv_m_demo = 1 / M_demo(global).  demo_partial: two floats per loss block (the sums of l[m] and of the squared error over its demonstration rows);
+    // demo_out: [demo_loss, c_d demo_loss, mean_sq_error] (mi_ppo_buffer(h, 4))
+    int m_ppo, demo_kind, n_demo_rows; float demo_coef, inv_m_demo;
+    const float *demo_states, *demo_actions; const int* demo_row_idx; float *demo_partial, *demo_out;
 };
-static_assert(sizeof(PpoFusedParams) == 456, "PpoFusedParams: a field moved (the kernels' argument offsets are pinned by profiles/r28_ppo_wide_inputs.md)");
+static_assert(sizeof(PpoFusedParams) == 520, "PpoFusedParams: a field moved (the offsets of its fields are pinned by profiles/r28_ppo_wide_inputs.md)");
+// (fields are appended only.  A kernel's arguments BEHIND the struct -- the predict and statistics heads -- move with its size, 456 -> 520 with the demonstration
+// term; they are passed by value with every launch, so nothing else depends on where they sit: profiles/r36_demonstration_term.md)
 
 }  // namespace mi
 

@@ -4,7 +4,7 @@
 //
 //   the 16-byte form (32 samples per block, 8 lanes per sample, h2 rows in registers from the first request to the dh2 stores):
 //     pf_head_rows, pf_stage_request / pf_stage_commit, pf_head_sums, pf_fast_tanh, pf_block_partials, pf_head_dh2
-//         -> ppo_head_loss_body (8 instantiations), ppo_head_clone_kernel (4)
+//         -> ppo_head_loss_body (8 instantiations, and 8 with DEMO: the step with a demonstration term), ppo_head_clone_kernel (4)
 //   the strided form (columns j = part, part + TPS, .. straight from memory; libm):
 //     pf_head_sums_strided, pf_mean_libm, pf_logp_term_libm
 //         -> ppo_predict_head_kernel (4), ppo_update_stats_head_kernel (2), ppo_kl_stats_head_kernel (2); the two libm spellings also in the loss body's

@@ -149,6 +149,10 @@ class PpoDevice:
         o = addr - self.workspace.data_ptr()
         # d loss / d value-head output per sample of the last step (the step's workspace; exactly 0 where value clipping stops the gradient)
         self.value_head_grad = self.workspace[o:o + 4 * int(max_batch)].view(torch.float32)
+        addr = self.L.mi_ppo_buffer(self.handle, 4)
+        o = addr - self.workspace.data_ptr()
+        # [demo_loss, demo_coef x demo_loss, mean_sq_error] of the last train_step_demo (no other step writes them)
+        self.demo_losses = self.workspace[o:o + 12].view(torch.float32)
         # like the precision, the clipping limit is applied to every engine this object creates
         self.L.mi_ppo_set_max_grad_norm(self.handle, 0.0 if self.max_grad_norm is None else self.max_grad_norm)
 
@@ -297,6 +301,23 @@ class PpoDevice:
         p = milib.ptr
         self.L.mi_ppo_clone_step(self.handle, comm_handle, self.stream(), p(states), p(expert_actions), p(returns), kind, p(row_idx), int(states.shape[0]), int(M),
                                  float(inv_m), float(grad_scale), 1 if adam else 0, float(alpha), float(beta1), float(beta2), float(epsilon))
+
+    def train_step_demo(self, comm_handle, states, actions, returns, advantage, logp_old, mean_old, kl_coef, row_idx, M, demo_states, demo_actions, demo_row_idx,
+                        M_demo, demo_kind, demo_coef, inv_m_demo, inv_m, grad_scale, alpha, beta1=0.9, beta2=0.999, epsilon=1e-8, adam=True,
+                        old_values=None, clip_range_vf=None):
+        """The PPO step with a demonstration term (mi_ppo_train_step_demo): M PPO rows and M_demo demonstration rows in one fused chain, one gradient, one Adam
+        update; loss = L_ppo + demo_coef x clone_loss(demonstration rows), demo_kind "nll" / "mse", policy only.  The PPO side as train_step_kl -- kl_coef None: no
+        KL penalty (mean_old is not read); old_values / clip_range_vf: the clipped value loss; row_idx None or an int32 device tensor [M] naming rows of the PPO
+        tables -- and the demonstration side likewise: demo_row_idx None (demo_states / demo_actions contiguous) or rows of the demonstration tables.  comm_handle
+        None or a communicator; adam False stops with the gradients in the flat buffer.  `demo_losses` holds [demo_loss, demo_coef x demo_loss, mean_sq_error]."""
+        demo_kind = milib.clone_kind(demo_kind, "PpoDevice.train_step_demo")
+        self.ensure_batch(int(M) + int(M_demo))
+        p = milib.ptr
+        self.L.mi_ppo_train_step_demo(self.handle, comm_handle, self.stream(), p(states), p(actions), p(returns), p(advantage), p(logp_old), p(mean_old),
+                                      0 if kl_coef is None else 1, 0.0 if kl_coef is None else float(kl_coef), p(old_values),
+                                      0.0 if old_values is None else float(clip_range_vf), p(row_idx), int(states.shape[0]), int(M), p(demo_states), p(demo_actions),
+                                      p(demo_row_idx), int(demo_states.shape[0]), int(M_demo), demo_kind, float(demo_coef), float(inv_m_demo), float(inv_m),
+                                      float(grad_scale), 1 if adam else 0, float(alpha), float(beta1), float(beta2), float(epsilon))
 
     def clone_losses(self):
         """{clone_loss, value_loss, loss, mean_sq_error} of the last clone_step (one readback)."""

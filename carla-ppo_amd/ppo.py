@@ -94,6 +94,9 @@ class PPO():
         # kl_penalty_state() / load_kl_penalty_state() carry it.
         self.kl_penalty = _kl_coef_from_env()
         self.kl_target = None
+        # demonstration term (set_demonstration_loss): c_d x clone_loss of a minibatch of demonstration rows added to the PPO objective inside the same step
+        # (_demo_rows); None = off.  demo_kind: "nll" / "mse".  Not part of a checkpoint.
+        self.demo_coef, self.demo_kind = None, "nll"
         # wide inputs (set_wide_inputs): the fused kernels for a policy of more than 96 inputs (a VAE of more than 93 latents).  MI355_PPO_WIDE_INPUTS=1 supplies it
         # when set_wide_inputs is not called (the reference's train.py builds this object itself).  Routing only; not part of a checkpoint.
         self.wide_inputs = _wide_inputs_from_env()
@@ -506,6 +509,51 @@ class PPO():
         self.train_step_counter += 1
         L = self._global_clone_losses()
         return dict(clone_loss=float(L[0]), value_loss=float(L[1]), loss=float(L[3]), mean_sq_error=float(L[4]))
+
+    # ------------------------------------------------------------------ the demonstration term
+    def set_demonstration_loss(self, coef, loss="nll"):
+        """Keep a supervised term in the PPO objective (DAPG's remedy for a warm start that the first PPO updates undo): loss = L_ppo + coef x clone_loss of a
+        minibatch of demonstration rows, formed in the same fused step (include/mi355_carla.h, mi_ppo_train_step_demo; _demo_rows).  coef None switches it off (the
+        default), a finite float >= 0 switches it on; loss "nll" or "mse" as in clone_step.  Usable before or after init_session(); bool, str, NaN, inf or a
+        negative coefficient and an unknown loss raise ValueError before anything touches a device.  It is no part of a checkpoint."""
+        if coef is not None and (isinstance(coef, bool) or not isinstance(coef, (int, float, np.integer, np.floating)) or not (coef >= 0 and coef < float("inf"))):
+            raise ValueError("PPO.set_demonstration_loss: the value is None or a finite float >= 0, got %r" % (coef,))
+        kind = milib.clone_kind(loss, "PPO.set_demonstration_loss")
+        self.demo_coef, self.demo_kind = None if coef is None else float(coef), ("nll", "mse")[kind]
+
+    def _demo_rows(self, s_all, a_all, r_all, adv_all, logp_old_all, mean_old_all, rows, m_local, m_global, demo_s_all, demo_a_all, demo_rows, md_local, md_global,
+                   old_values_all=None, coef=None, loss=None):
+        """One SGD step with the demonstration term on table rows, next to _step_rows / _kl_step: rows `rows` (int32 device tensor) of the horizon-batch tables and
+        rows `demo_rows` of the demonstration tables demo_s_all / demo_a_all, in one fused chain with one Adam update (mi_ppo_train_step_demo).  The KL penalty
+        (set_kl_penalty; mean_old_all None: the step evaluates the old policy itself) and value clipping (old_values_all with set_value_clip) apply to the PPO rows.
+        There is no per-layer form and no gathered fall-back: a policy outside the fused kernels' range and data parallel without the library's communicator are
+        refused by name.  coef / loss: this step's coefficient and loss (the rollout buffers pass their own, decaying coefficient; this object's setting is not
+        touched), None: what set_demonstration_loss set.  Adam's powers advance; the counters are the caller's."""
+        if coef is None:
+            if self.demo_coef is None:
+                raise ValueError("PPO._demo_rows: the demonstration term is off (set_demonstration_loss)")
+            coef = self.demo_coef
+        elif isinstance(coef, bool) or not isinstance(coef, (int, float, np.integer, np.floating)) or not (coef >= 0 and coef < float("inf")):
+            raise ValueError("PPO._demo_rows: coef is None or a finite float >= 0, got %r" % (coef,))
+        loss = self.demo_kind if loss is None else loss
+        if old_values_all is not None and self.value_clip is None:
+            raise ValueError("PPO._demo_rows: old values were passed but value clipping is off (set_value_clip)")
+        self._clone_kind("PPO._demo_rows", loss)               # (the loss name and the fused range: the same refusal as a clone step's)
+        dev, world = self._need_dev(), midist.world_size()
+        comm = None if world == 1 else self._dp_comm()
+        if world > 1 and comm is None:
+            raise ValueError("PPO._demo_rows: data parallel needs the library's communicator (the demonstration step is one C call)")
+        if not dev.fused_ok():
+            raise ValueError("PPO._demo_rows: the demonstration term exists only in the fused kernels (this policy's shape is outside their range)")
+        kl = self.kl_penalty
+        if kl is not None and mean_old_all is None:            # no table of old means: the step evaluates the old policy itself -- correct, slower
+            logp_old_all = None
+        alpha = _adam_alpha(self.current_learning_rate(), self.beta1_power, self.beta2_power)
+        dev.train_step_demo(None if comm is None else comm.handle, s_all, a_all, r_all, adv_all, logp_old_all, mean_old_all if kl is not None else None, kl, rows, m_local,
+                            demo_s_all, demo_a_all, demo_rows, md_local, loss, coef, 1.0 / md_global, 1.0 / m_global, m_local / float(m_global), alpha,
+                            ADAM_BETA1, ADAM_BETA2, ADAM_EPSILON, old_values=old_values_all, clip_range_vf=None if old_values_all is None else self.value_clip)
+        self.beta1_power = np.float32(self.beta1_power * np.float32(ADAM_BETA1))
+        self.beta2_power = np.float32(self.beta2_power * np.float32(ADAM_BETA2))
 
     def _clone_rows(self, s_all, a_all, r_all, rows, m_local, m_global, loss="nll", learning_rate=None):
         """One clone step on rows `rows` (int32 device tensor) of device-resident tables states / expert actions / returns (r_all None: policy only): the gather

@@ -257,6 +257,18 @@ rows -- CARLA's autopilot, a human driver.  add() encodes the frames with the ba
 state rows, clone() runs epochs of shuffled minibatches through PPO._clone_rows (mi_ppo_clone_step: the fused chain with a supervised head / loss kernel, loss "nll"
 or "mse"; the value net is fitted if and only if returns were added, and is otherwise neither run nor touched), evaluate() scores the policy against the expert in
 float64 on the host.  Single rank; no latent stacking.
+
+RolloutBuffer.set_demonstrations(demo_buffer, coef, loss="nll", batch_size=32, decay=1.0, seed=0) keeps the demonstrations in the PPO update behind the warm start
+(DAPG; a warm-started policy beside a value net that has seen no on-policy data is where the first PPO updates undo the warm start): with it on, every SGD step of
+update() / update_with_diagnostics() is ONE PPO._demo_rows call (mi_ppo_train_step_demo) on the PPO minibatch plus min(batch_size, demo_buffer.size) demonstration
+rows -- loss = L_ppo + coef x clone_loss(those rows), one fused chain over all rows, one gradient, one Adam update; value clipping and the KL penalty apply to the PPO
+rows, the demonstration rows carry no value target.  The demonstration rows come from a np.random.RandomState(seed) the setting owns (a permutation of the rows and a
+cursor; when fewer rows than a minibatch remain a fresh permutation is drawn: demonstration_rows_drawn), so the legacy numpy stream that shuffles the PPO minibatches is
+consumed exactly as with the setting off.  After every update coef *= decay; demonstration_state() / load_demonstration_state() carry the coefficient, the
+RandomState, the permutation and the cursor.  The result gains `demo_losses` (one {demo_loss, mean_sq_error} per step), `demo_rows`, `demo_coef` and `demo_coef_next`;
+with the setting off no key appears and the update makes the launches it always made.  Refused before anything is launched: an empty demonstration buffer, another
+input_dim / action count / ppo object, a stacked rollout buffer, observation normalisation that is not off in both buffers or frozen here and equal by value to the
+state the demonstration buffer was given, and a policy outside the fused kernels' range.
 """
 import contextlib
 import os
@@ -1053,6 +1065,7 @@ class RolloutBuffer:
         self._obs_norm = None                                                        # running observation normalisation (set_observation_normalization): None = off
         self.raw_states = None                                                       # its fp32 table of the raw rows, allocated when the setting is turned on
         self.mean_old = None                                                         # the old policy's action means per table row, allocated by the first update with the KL penalty on (PPO.set_kl_penalty)
+        self._demo = None                                                            # the demonstration term (set_demonstrations): None = off
 
     def set_observation_normalization(self, clip=10.0, epsilon=1e-8, frozen=False, normalize_latents=True):
         """Turns running observation normalisation on (see the module docstring): step(), bootstrap() and truncate() feed the trunks clamp((s - mean) * inv_std, +-clip)
@@ -1206,6 +1219,104 @@ class RolloutBuffer:
             return
         self._minibatch_norm = {"ddof": minibatch_normalization_ddof(ddof)}
 
+    def set_demonstrations(self, demo_buffer, coef=None, loss="nll", batch_size=32, decay=1.0, seed=0):
+        """Turns the demonstration term on (see the module docstring): every SGD step of update() / update_with_diagnostics() is one PPO._demo_rows call on the PPO
+        minibatch plus min(batch_size, demo_buffer.size) rows of `demo_buffer` (a DemonstrationBuffer of the same policy), loss = L_ppo + coef x clone_loss(those
+        rows) with loss "nll" or "mse"; after every update coef *= decay.  The rows come from a np.random.RandomState(seed) of this setting's own
+        (demonstration_rows_drawn: a permutation and a cursor); the legacy numpy stream is consumed as with the setting off.  set_demonstrations(None) turns it off.  ValueError before
+        anything touches a device: coef not a finite float >= 0, an unknown loss, batch_size < 1, decay not a finite float >= 0, and every refusal of
+        _check_demonstrations."""
+        if demo_buffer is None:
+            self._demo = None
+            return
+        who = type(self).__name__ + ".set_demonstrations"
+        if not isinstance(demo_buffer, DemonstrationBuffer):
+            raise ValueError("%s: demo_buffer is a DemonstrationBuffer or None, got %r" % (who, type(demo_buffer).__name__))
+        for name, v in (("coef", coef), ("decay", decay)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not (v >= 0 and v < float("inf")):
+                raise ValueError("%s: %s is a finite float >= 0, got %r" % (who, name, v))
+        kind = milib.clone_kind(loss, who)
+        for name, v in (("batch_size", batch_size), ("seed", seed)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not (1 if name == "batch_size" else 0) <= int(v) < 1 << 32:
+                raise ValueError("%s: %s is an int >= %d, got %r" % (who, name, 1 if name == "batch_size" else 0, v))
+        dm = {"buffer": demo_buffer, "coef": float(coef), "loss": ("nll", "mse")[kind], "batch_size": int(batch_size), "decay": float(decay),
+              "rng": np.random.RandomState(int(seed)), "perm": None, "cursor": 0}
+        self._check_demonstrations(dm, who)
+        self._demo = dm
+
+    def _check_demonstrations(self, dm, who):
+        """What the demonstration term refuses, when it is set and again in front of every update: an empty demonstration buffer, another input_dim / action count /
+        ppo object, a stacked rollout buffer, observation normalisation that does not match (off in both buffers, or frozen here and equal by value to the state
+        the demonstration buffer was given) and a policy outside the fused kernels' range."""
+        import torch
+        db = dm["buffer"]
+        if self._stacked():
+            raise ValueError(who + ": latent stacking is on and DemonstrationBuffer has no stacked form")
+        if db.size < 1:
+            raise ValueError(who + ": the demonstration buffer is empty")
+        if db.ppo is not self.ppo:
+            raise ValueError(who + ": the demonstration buffer belongs to another ppo object")
+        if int(db.states.shape[1]) != int(self.states.shape[1]) or int(db.A) != int(self.actions.shape[1]):
+            raise ValueError("%s: the demonstration buffer's rows are [%d inputs, %d actions], this buffer's [%d, %d]"
+                             % (who, db.states.shape[1], db.A, self.states.shape[1], self.actions.shape[1]))
+        mine, theirs = self._obs_norm, db._step._obs_norm
+        if (mine is None) != (theirs is None):
+            raise ValueError(who + ": observation normalisation is on in one buffer and off in the other: the demonstration rows and the rollout rows are not the same kind of state")
+        if mine is not None:
+            same = all(mine[k] == theirs[k] for k in ("clip", "epsilon", "normalize_latents")) and torch.equal(mine["state"], theirs["state"])
+            if not (mine["frozen"] and same):
+                raise ValueError(who + ": with observation normalisation on, this buffer's statistics must be frozen and equal to the state the demonstration buffer was given "
+                                 "(DemonstrationBuffer.set_observation_normalization(observation_normalization_state()))")
+        self.ppo._clone_kind(who, dm["loss"])                                        # (the fused range, without a device)
+        if self.ppo.dev is not None and not self.ppo.dev.fused_ok():
+            raise ValueError(who + ": the demonstration term exists only in the fused kernels (this policy's shape is outside their range (more than 96 inputs: "
+                             "PPO.set_wide_inputs()) or MI355_PPO_FUSED=0)")
+
+    def _need_demonstrations(self, what):
+        if getattr(self, "_demo", None) is None:
+            raise ValueError("%s.%s: the demonstration term is off (set_demonstrations)" % (type(self).__name__, what))
+        return self._demo
+
+    @staticmethod
+    def demonstration_rows_drawn(dm, n, steps):
+        """The draw rule: `steps` minibatches of m = min(batch_size, n) rows of a demonstration buffer of n rows -> int32 [steps, m].  The setting keeps a permutation of
+        the n rows and a cursor; a minibatch is the next m rows of the permutation, and when fewer than m remain (or there is no permutation of n rows yet) a fresh
+        rng.permutation(n) is drawn first and the cursor returns to 0."""
+        m = min(dm["batch_size"], n)
+        out = np.zeros((steps, m), np.int32)
+        for i in range(steps):
+            if dm["perm"] is None or dm["perm"].shape[0] != n or n - dm["cursor"] < m:
+                dm["perm"], dm["cursor"] = dm["rng"].permutation(n), 0
+            out[i] = dm["perm"][dm["cursor"]:dm["cursor"] + m]
+            dm["cursor"] += m
+        return out
+
+    def demonstration_state(self):
+        """What a training script writes to its checkpoint: {"coef", "rng" (RandomState.get_state()), "perm" (int64 [n] or None), "cursor"}."""
+        dm = self._need_demonstrations("demonstration_state")
+        return {"coef": dm["coef"], "rng": dm["rng"].get_state(), "perm": None if dm["perm"] is None else np.array(dm["perm"], np.int64), "cursor": int(dm["cursor"])}
+
+    def load_demonstration_state(self, d):
+        """Takes demonstration_state()'s dict back (the setting must be on); the whole dict is checked before anything changes (ValueError)."""
+        dm = self._need_demonstrations("load_demonstration_state")
+        who = type(self).__name__ + ".load_demonstration_state"
+        if not isinstance(d, dict) or set(d) != {"coef", "rng", "perm", "cursor"}:
+            raise ValueError(who + ": expected the keys coef, rng, perm and cursor")
+        coef, cursor = d["coef"], d["cursor"]
+        if isinstance(coef, (bool, np.bool_)) or not isinstance(coef, (int, float, np.integer, np.floating)) or not (coef >= 0 and coef < float("inf")):
+            raise ValueError("%s: coef is a finite float >= 0, got %r" % (who, coef))
+        perm = None if d["perm"] is None else np.array(d["perm"], np.int64).reshape(-1)
+        if perm is not None and not np.array_equal(np.sort(perm), np.arange(perm.shape[0])):
+            raise ValueError(who + ": perm is not a permutation")
+        if isinstance(cursor, (bool, np.bool_)) or not isinstance(cursor, (int, np.integer)) or not 0 <= int(cursor) <= (0 if perm is None else perm.shape[0]):
+            raise ValueError("%s: cursor is an int inside the permutation, got %r" % (who, cursor))
+        rng = np.random.RandomState(0)
+        try:
+            rng.set_state(d["rng"])
+        except Exception as e:                                                       # (numpy raises TypeError, ValueError or IndexError by what is wrong with it)
+            raise ValueError("%s: rng is not a RandomState state (%s)" % (who, e))
+        dm["coef"], dm["rng"], dm["perm"], dm["cursor"] = float(coef), rng, perm, int(cursor)
+
     @property
     def lengths(self):
         return self.rows.lengths
@@ -1325,10 +1436,11 @@ class RolloutBuffer:
         rs = self._reward_scaling                                                    # running-return reward scaling (set_reward_scaling): None = off
         mbn = getattr(self, "_minibatch_norm", None)                                 # per-minibatch advantage normalisation (set_minibatch_normalization): None = off
         on = getattr(self, "_obs_norm", None)                                        # running observation normalisation (set_observation_normalization): None = off
+        demo = getattr(self, "_demo", None)                                          # the demonstration term (set_demonstrations): None = off
         E, T, device = self.num_envs, self.horizon, self.device
         valid = self.rows.valid_rows()
         # this update: what its stages share, and what they leave for the result
-        u = types.SimpleNamespace(batch_size=int(batch_size), num_epochs=int(num_epochs), vclip=vclip, klp=klp, diag=diag, mbn=mbn, valid=valid, n_valid=int(valid.shape[0]),
+        u = types.SimpleNamespace(batch_size=int(batch_size), num_epochs=int(num_epochs), vclip=vclip, klp=klp, diag=diag, mbn=mbn, demo=demo, valid=valid, n_valid=int(valid.shape[0]),
                                   lengths=self.rows.lengths.copy(), recorded=recorded, clock=_StageClock(stage_times, device),
                                   st=torch.cuda.current_stream(device).cuda_stream)
         r = torch.from_numpy(self.rows.rewards).to(device)
@@ -1348,6 +1460,8 @@ class RolloutBuffer:
             self._kl_penalty_result(u, out)
         if mbn is not None:
             self._minibatch_norm_result(u, out)
+        if demo is not None:
+            self._demonstration_result(u, out)
         if rs is not None:
             self._reward_scaling_result(u, rs, scaled, out)
         if on is not None:                                                           # the update's last launch: nothing above can raise behind it
@@ -1371,6 +1485,8 @@ class RolloutBuffer:
         if diag is not None and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update_with_diagnostics: the statistics pass reads the cached log pi_old, which only the fused kernels fill "
                              "(this policy's shape is outside their range (more than 96 inputs: PPO.set_wide_inputs()) or MI355_PPO_FUSED=0)")
+        if getattr(self, "_demo", None) is not None:
+            self._check_demonstrations(self._demo, who + ".update")
         self.rows.check_update()
         recorded = np.arange(self.horizon)[None, :] < self.rows.lengths[:, None]
         if self._reward_scaling is not None and not np.isfinite(self.rows.rewards[recorded]).all():
@@ -1429,6 +1545,10 @@ class RolloutBuffer:
         clip = ppo.max_grad_norm is not None                                         # global-norm clipping on: every step's {norm, scale, c, 0} is kept as well
         records, clips = [], []
         u.records, u.clips, u.epoch_first, u.epochs, u.stopped, u.mb_epochs = records, clips, [0], [], False, 0
+        if u.demo is not None:                                                       # the demonstration term: this update's coefficient and loss go to every step; the policy's own setting is not touched
+            db = u.demo["buffer"]
+            u.demo_coef, u.demo_records, u.demo_rows = u.demo["coef"], [], []
+            steps_per_epoch, md = -(-n_valid // batch_size), min(u.demo["batch_size"], db.size)
         observe = self._stats_pass(u) if u.diag is not None else None
         adv_table = self.advantages                                                  # the table the steps gather their advantage from
         if u.mbn is not None:
@@ -1445,10 +1565,18 @@ class RolloutBuffer:
                     self.L.mi_ppo_minibatch_advantages(u.st, u.f64[0].data_ptr(), perm.data_ptr(), n_valid, batch_size, self.num_envs, self.horizon, u.mbn["ddof"],
                                                        adv_table.data_ptr(), u.mb_stats[u.mb_epochs].data_ptr())
                     u.mb_epochs += 1
+            if u.demo is not None:                                                   # this epoch's demonstration rows, from the setting's own stream: one upload
+                drawn = self.demonstration_rows_drawn(u.demo, db.size, steps_per_epoch)
+                u.demo_rows.extend(drawn)
+                drawn_dev = torch.from_numpy(drawn).to(device)
             for i in range(0, n_valid, batch_size):
                 mb = perm[i:i + batch_size]                                          # the last one may be partial (train.py:199-201)
                 m = int(mb.numel())
-                if u.klp is not None:                                                # (the penalised step reads the old policy's means next to its log-probabilities)
+                if u.demo is not None:                                               # one step on the PPO minibatch and the demonstration rows together
+                    ppo._demo_rows(self.states, self.actions, self.returns, adv_table, logp_old, self.mean_old if u.klp is not None else None, mb, m, m,
+                                   db.states, db.expert_actions, drawn_dev[i // batch_size], md, md, old_values_all=step_kw.get("old_values_all"), coef=u.demo_coef, loss=u.demo["loss"])
+                    u.demo_records.append(pdev.demo_losses.clone())
+                elif u.klp is not None:                                                # (the penalised step reads the old policy's means next to its log-probabilities)
                     ppo._kl_step(self.states, self.actions, self.returns, adv_table, logp_old, self.mean_old, mb, m, m, old_values=step_kw.get("old_values_all"))
                 else:
                     ppo._step_rows(self.states, self.actions, self.returns, adv_table, logp_old, mb, m, m, **step_kw)
@@ -1488,6 +1616,16 @@ class RolloutBuffer:
         adapt = self.ppo.kl_target is not None and bool(np.isfinite(kl["kl"])) and kl["kl"] >= 0
         out["kl_coef_next"] = float(self.ppo.adapt_kl_penalty(kl["kl"])) if adapt else float(self.ppo.kl_penalty)
         out["kl_adapted"] = bool(adapt)
+
+    def _demonstration_result(self, u, out):
+        """Behind the last epoch: every step's demonstration scalars and rows (one readback), then the coefficient's decay."""
+        import torch
+        dl = torch.stack(u.demo_records).cpu().numpy() if u.demo_records else np.zeros((0, 3), np.float32)
+        out["demo_losses"] = [{"demo_loss": float(r[0]), "mean_sq_error": float(r[2])} for r in dl]
+        out["demo_rows"] = [np.array(r, np.int32) for r in u.demo_rows]
+        out["demo_coef"] = float(u.demo_coef)
+        u.demo["coef"] = float(u.demo_coef * u.demo["decay"])
+        out["demo_coef_next"] = u.demo["coef"]
 
     def _minibatch_norm_result(self, u, out):
         E, T = self.num_envs, self.horizon                                           # one readback behind the last epoch; only the epochs that ran

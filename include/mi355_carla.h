@@ -787,6 +787,24 @@ int mi_ppo_kl_stats_idx(void* h, void* stream, const float* states, const float*
  * [1, max_batch], row_idx set with n_rows < 1, states or expert_actions NULL, kind not 0 / 1, adam not 0 / 1; MI_ERR_SHAPE: mi_ppo_fused_shape_ok(h) is 0 (there is
  * no per-layer form).  A refused call writes nothing. */
 int mi_ppo_clone_step(void* h, void* comm, void* stream, const float* states, const float* expert_actions, const float* returns, int kind, const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon);
+/* the PPO step with a demonstration term: M PPO rows and M_demo demonstration rows in ONE step -- one fused chain over M + M_demo rows (a staging launch that gathers
+ * the state rows of the two tables, the trunks, a head / loss kernel that takes the PPO or the clone arithmetic per sample, the layer-1 input gradient, the weight
+ * gradients), one gradient, one Adam update -- where mi_ppo_train_step_kl followed by mi_ppo_clone_step is two chains and two optimiser steps.
+ *   loss = L_ppo(PPO rows) + demo_coef L_demo(demonstration rows)
+ * L_ppo: the objective of mi_ppo_train_step[_idx] on the PPO rows with inv_m = 1 / M(global); old_values given: the clipped value loss of mi_ppo_train_step_vclip;
+ * kl_on = 1: the KL penalty of mi_ppo_train_step_kl (kl_coef a finite float >= 0) and logp_old / mean_old both given or both NULL; kl_on = 0: mean_old is not read.
+ * L_demo: clone_loss of mi_ppo_clone_step, demo_kind 0 ("nll") or 1 ("mse"), policy only, the same per-sample formulas with inv_m_demo = 1 / M_demo(global).
+ * Demonstration rows carry no return, advantage, old policy or value target: their dv (mi_ppo_buffer(h, 3), rows M .. M + M_demo - 1) is exactly 0.0, and they add
+ * nothing to the entropy and KL terms nor to the scalars of the losses buffer, mean action_mean among them (those stay means over the PPO rows; grad_scale is the PPO
+ * rows').  Global-norm clipping sees the whole gradient.  row_idx NULL: contiguous PPO tensors, else the PPO tables of n_rows rows gathered in-kernel; demo_row_idx
+ * NULL: demo_states [M_demo, input_dim] / demo_actions [M_demo, A] contiguous, else tables of n_demo_rows rows; the two sides gather from different tables, rows are
+ * clamped and a row no list names is never read.  comm NULL or a communicator; adam 0 / 1 on the routes of mi_ppo_train_step_kl with M + M_demo in the place of M (the
+ * in-tile Adam only when M + M_demo <= 256 with clipping off and no communicator).  Both precision modes; wide inputs as mi_ppo_set_wide_inputs routes them.
+ * mi_ppo_buffer(h, 4): three floats [demo_loss, demo_coef x demo_loss, mean_sq_error] of the demonstration rows; losses[3] includes the weighted term.  All sums in a
+ * fixed order, no atomics: two runs are bitwise equal.  MI_ERR_STATE: null handle, missing gradient / optimiser buffers; MI_ERR_ARG: M or M_demo < 1, M + M_demo >
+ * max_batch, a row list with an empty table, a missing buffer, demo_kind not 0 / 1, demo_coef negative / NaN / infinite, inv_m_demo not > 0, kl_on not 0 / 1 and the
+ * argument checks of mi_ppo_train_step_kl; MI_ERR_SHAPE: mi_ppo_fused_shape_ok(h) is 0 (there is no per-layer form).  A refused call writes nothing. */
+int mi_ppo_train_step_demo(void* h, void* comm, void* stream, const float* states, const float* actions, const float* returns, const float* advantage, const float* logp_old, const float* mean_old, int kl_on, float kl_coef, const float* old_values, float clip_range_vf, const int* row_idx, int n_rows, int M, const float* demo_states, const float* demo_actions, const int* demo_row_idx, int n_demo_rows, int M_demo, int demo_kind, float demo_coef, float inv_m_demo, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon);
 /* advantages normalised PER MINIBATCH, inside the SGD loop — SB3's normalize_advantage, CleanRL's norm_adv; no reference counterpart in train.py, which normalises per
  * trajectory (train.py:176-177): one pass per epoch between the finish calls (mi_rollout_finish*, which leave the raw advantages in fp64) and the epoch's SGD steps, which
  * gather their advantage from an fp32 table by row index.  No engine handle.  adv_raw: fp64 [num_envs, T], the raw advantages (entries beyond a lane's length may hold

@@ -1,7 +1,9 @@
 """What the calls through the head-level kernels of csrc/ppo_fused.hip cost (profiles/r34_behaviour_cloning.md, profiles/r35_ppo_head_helpers.md): interleaved windows
 of the plain one-call PPO step (mi_ppo_train_step with a cached log pi_old, two windows: its own run-to-run spread), mi_ppo_clone_step with returns and policy-only
 in both kinds, and mi_ppo_train_step_kl with value clipping, at M = 32 and M = 2048 (fp32, 67 inputs, 2 actions); at M = 2048 also one window each of
-mi_ppo_update_stats_idx, mi_ppo_kl_stats_idx and mi_ppo_logp_old.  One process, device events, a warm-up of 100 calls, nine rounds per variant; median / min / max
+mi_ppo_update_stats_idx, mi_ppo_kl_stats_idx and mi_ppo_logp_old.  In the same rounds: the step with a demonstration term (mi_ppo_train_step_demo, this build
+only: the parent has no such entry) at (M_p, M_d) = (32, 32) and (2048, 256), and the plain step followed by the policy-only clone step on the same M_d rows -- the
+two calls, two chains and two optimiser steps the one-chain step replaces (profiles/r36_demonstration_term.md).  One process, device events, a warm-up of 100 calls, nine rounds per variant; median / min / max
 of the rounds in us per call.  With --parent-lib PATH every variant also runs from ANOTHER build of the library (the parent commit's libmi355_carla.so) in the same
 process and the same rounds, on an engine of its own with the same parameters, and each variant of this build is compared with the SAME variant of that one: the
 entry points have the same prototypes in both.
@@ -9,7 +11,8 @@ entry points have the same prototypes in both.
     python tools/clone_latency.py [--parent-lib PATH] [OUT_DIR]      # default out/: writes clone_latency.json there and prints the table
 
 Expectations (recorded, not enforced): no variant exceeds its twin from the other build by more than the allowance, the larger of 2 % and the plain step's own
-spread; the clone step with returns stays within the allowance of the plain step, and policy-only below it."""
+spread; the clone step with returns stays within the allowance of the plain step, and policy-only below it; the demonstration step is faster than the two calls by
+more than the allowance (summary: one_chain_pays)."""
 import ctypes
 import json
 import os
@@ -35,7 +38,8 @@ OUT = argv[0] if argv else os.path.join(ROOT, "out")
 
 dev = torch.device("cuda", 0)
 rng = np.random.RandomState(0)
-A, DIN, MAXB = 2, 67, 2048
+A, DIN, MAXB = 2, 67, 2048 + 256                        # (the largest demonstration step: 2048 + 256 rows)
+M_DEMO = {32: 32, 2048: 256}
 low, high = np.array([-1.0, 0.0], np.float32), np.array([1.0, 1.0], np.float32)
 d = PpoDevice(DIN, A, low, high, 0.2, 1.0, 0.01, max_batch=MAXB)
 th = init_ppo(1, DIN, A, 0.4)
@@ -96,6 +100,12 @@ class Build:
                                            None, M, *a, 1, *ADAM),
              "plain_b": plain,
              "clone_returns_mse": clone(t["R"], "mse"), "clone_policy_only_mse": clone(None, "mse")}
+        Md = M_DEMO[M]
+        clone_demo = lambda: self.call("mi_ppo_clone_step", None, st, p(t["ds"]), p(t["da"]), None, kinds["nll"], None, Md, Md, 1.0 / Md, 1.0, 1, *ADAM)      # noqa: E731
+        v["plain_then_clone"] = lambda: (plain(), clone_demo())
+        if self.path is None:                                # (the new entry: this build only)
+            v["demo"] = lambda: self.call("mi_ppo_train_step_demo", None, st, p(t["s"]), p(t["a"]), p(t["R"]), p(t["adv"]), p(t["lp"]), None, 0, 0.0, None, 0.0, None, M, M,
+                                          p(t["ds"]), p(t["da"]), None, Md, Md, 0, 0.5, 1.0 / Md, 1.0 / M, 1.0, 1, *ADAM)
         if with_stats:
             v["update_stats"] = lambda: self.call("mi_ppo_update_stats_idx", st, p(t["s"]), p(t["a"]), p(t["R"]), p(t["lp"]), p(t["rows"]), M, M, 0, p(t["scratch"]),
                                                   p(t["stats"]), None, None)
@@ -134,7 +144,8 @@ for M, iters in ((32, 2000), (2048, 300)):
          "vo": up(rng.standard_normal(M)), "lp": torch.empty(M, device=dev), "mo": torch.empty(M, A, device=dev), "lp_out": torch.empty(M, device=dev),
          "rows": torch.arange(M, device=dev, dtype=torch.int32), "stats": torch.zeros(N_STATS, device=dev, dtype=torch.float64),
          "scratch": torch.zeros(d.stats_scratch_doubles(M), device=dev, dtype=torch.float64), "kl_stats": torch.zeros(N_KL_STATS, device=dev, dtype=torch.float64),
-         "kl_scratch": torch.zeros(d.kl_stats_scratch_doubles(M), device=dev, dtype=torch.float64)}
+         "kl_scratch": torch.zeros(d.kl_stats_scratch_doubles(M), device=dev, dtype=torch.float64),
+         "ds": up(0.5 * rng.standard_normal((M_DEMO[M], DIN))), "da": up(rng.uniform(0, 1, (M_DEMO[M], A)))}
     d.old_policy_cache(t["s"], t["a"], M, t["lp"], t["mo"])
     variants = dict(this.variants(t, M, M == 2048))
     if other is not None:                                    # the twins, interleaved with this build's windows (no second window of the plain step)
@@ -149,8 +160,13 @@ for M, iters in ((32, 2000), (2048, 300)):
                       "policy_only_over_plain": {k: res["clone_policy_only_" + k]["median"] / base - 1.0 for k in ("nll", "mse")}}
     res["summary"]["with_returns_within_allowance"] = all(v <= allow for v in res["summary"]["with_returns_over_plain"].values())
     res["summary"]["policy_only_below_plain"] = all(v < 0 for v in res["summary"]["policy_only_over_plain"].values())
+    two = res["plain_then_clone"]["median"]
+    res["summary"]["demo_rows"] = M_DEMO[M]
+    res["summary"]["demo_over_plain"] = res["demo"]["median"] / res["plain_a"]["median"] - 1.0
+    res["summary"]["demo_over_two_calls"] = res["demo"]["median"] / two - 1.0
+    res["summary"]["one_chain_pays"] = bool(res["demo"]["median"] < two * (1.0 - allow))
     if other is not None:
-        over = {k: res[k]["median"] / res[("plain_a" if k == "plain_b" else k) + "_parent"]["median"] - 1.0 for k in variants if not k.endswith("_parent")}
+        over = {k: res[k]["median"] / res[("plain_a" if k == "plain_b" else k) + "_parent"]["median"] - 1.0 for k in variants if not k.endswith("_parent") and k != "demo"}
         res["summary"]["over_parent_twin"] = over
         res["summary"]["all_within_allowance_of_parent"] = all(v <= allow for v in over.values())
     out["step_M%d" % M] = res

@@ -5,7 +5,9 @@ NA = 8 instantiations).  Two builds compute the same thing iff their outputs are
 Step cells: every minibatch-step entry x {contiguous tensors, table rows} x M in (5, 33, 256, 257) x gradient-norm limit in (None, 0.5, inf) x {fp32, bf16x3}; at
 M = 5 and 33 also clone_step over {nll, mse} x {with returns, policy only} x {adam 1, adam 0}.  A cell starts from the same parameters, zero optimiser state and a
 gradient buffer of 4.25, runs three consecutive steps and prints one JSON line: the CRC-32C (mi_crc32c over the host copy) of params, m, v, the gradient buffer,
-losses, kl_losses, grad_clip and value_head_grad[:M].
+losses, kl_losses, grad_clip and value_head_grad[:M].  At M = 5, 33 and 257 also the step with a demonstration term (train_step_demo) with M_DEMO = 7 demonstration
+rows drawn from a stream of their own (the inputs of every other cell are those they were): plain "nll", KL + value clip "mse", on the recording communicator, and
+adam 0; those cells also print demo_losses and value_head_grad[:M + M_DEMO].
 
 Head cells, at M = 5 (the wave-per-sample predict kernel) and 33, per precision: old_policy_cache (both outputs), logp_old, update_stats (the sums and the two
 optional tables), kl_stats, predict sampled with given noise and greedy; one JSON line each with the CRC-32C of every output.
@@ -37,6 +39,7 @@ signal.alarm(args.time_limit)
 MAXB, STEPS = 320, 3
 SHAPES = (("A2", 67, 2, (500, 300)), ("A3", 5, 3, (36, 20)))
 MS, HEAD_MS, LIMITS = (5, 33, 256, 257), (5, 33), (None, 0.5, float("inf"))
+DEMO_MS, M_DEMO = (5, 33, 257), 7
 ALPHA, EPS_V, BETA, FILL = 1e-3, 0.2, 0.7, 4.25
 L = milib.get()
 dev = torch.device("cuda", 0)
@@ -85,6 +88,7 @@ for shape, DIN, A, HIDDEN in SHAPES:
     high = np.array([1.0, 1.0, 0.75][:A], np.float32)
     for precision in ("fp32", "bf16x3"):
         rng = np.random.RandomState(25)
+        drng = np.random.RandomState(36)                     # the demonstration rows: a stream of their own
         d = PpoDevice(DIN, A, low, high, 0.2, 1.0, 0.01, hidden=HIDDEN, max_batch=MAXB, precision=precision)
         th = init_ppo(1, DIN, A, 0.4, hidden=HIDDEN)
         d.load_params(th, {k.replace("policy/", "policy_old/", 1): (v + 0.02 * rng.standard_normal(v.shape)).astype(np.float32) for k, v in th.items()})
@@ -106,6 +110,12 @@ for shape, DIN, A, HIDDEN in SHAPES:
                 flat["noise"] = up(rng.standard_normal((M, A)))
                 d.params.copy_(start[0])
                 head_cells(d, tag, M, A, flat, tab, rows)
+            dflat = {"ds": up(0.5 * drng.standard_normal((M_DEMO, DIN))), "da": up(drng.uniform(0, 1, (M_DEMO, A)))}
+            drows = torch.from_numpy(drng.permutation(2 * M_DEMO + 3)[:M_DEMO].astype(np.int32)).to(dev)
+            dtab = {}
+            for k, x in dflat.items():
+                dtab[k] = up(0.5 * drng.standard_normal((2 * M_DEMO + 3,) + tuple(x.shape[1:])))
+                dtab[k][drows.long()] = x
             a = (M, 1.0 / M, 1.0, ALPHA)
             adam = lambda: d.apply_adam(ALPHA)      # noqa: E731
             for form, t, r in (("contiguous", flat, None), ("rows", tab, rows)):
@@ -130,17 +140,33 @@ for shape, DIN, A, HIDDEN in SHAPES:
                             for on in (True, False):
                                 entries.append(("clone_%s_%s_adam%d" % (kind, what, on),
                                                 lambda kind=kind, R=R, on=on: d.clone_step(None, t["s"], t["a"], R, kind, r, *a, adam=on)))
-                for limit in LIMITS:
-                    d.set_max_grad_norm(limit)
-                    for name, step in entries:
-                        for x, y in zip((d.params, d.adam_m, d.adam_v), start):
-                            x.copy_(y)
-                        d.grads.fill_(FILL)
-                        for _ in range(STEPS):
-                            step()
-                        emit("%s %s M=%d limit=%s %s" % (tag, form, M, limit, name),
-                             (("params", d.params), ("m", d.adam_m), ("v", d.adam_v), ("grads", d.grads), ("losses", d.losses), ("kl_losses", d.kl_losses),
-                              ("grad_clip", d.grad_clip), ("value_head_grad", d.value_head_grad[:M])))
+                demo_entries = []
+                if M in DEMO_MS:
+                    dt, dr = (dflat, None) if r is None else (dtab, drows)
+                    demo = lambda comm, kind, klc, vo, **kw: d.train_step_demo(comm, *data, t["lp"], t["mo"] if klc is not None else None, klc, r, M, dt["ds"], dt["da"], dr,      # noqa: E731
+                                                                               M_DEMO, kind, 0.5, 1.0 / M_DEMO, 1.0 / M, 1.0, ALPHA, old_values=vo, clip_range_vf=EPS_V, **kw)
+                    demo_entries = [("demo_nll", lambda: demo(None, "nll", None, None)), ("demo_kl_vclip_mse", lambda: demo(None, "mse", BETA, t["vo"])),
+                                    ("demo_comm", lambda: demo(hcomm, "nll", None, None)), ("demo_gradients", lambda: demo(None, "nll", BETA, t["vo"], adam=False))]
+
+                def run(cells, named):
+                    for limit in LIMITS:
+                        d.set_max_grad_norm(limit)
+                        for name, step in cells:
+                            for x, y in zip((d.params, d.adam_m, d.adam_v), start):
+                                x.copy_(y)
+                            d.grads.fill_(FILL)
+                            for _ in range(STEPS):
+                                step()
+                            emit("%s %s M=%d limit=%s %s" % (tag, form, M, limit, name), named())
+                common = lambda: (("params", d.params), ("m", d.adam_m), ("v", d.adam_v), ("grads", d.grads), ("losses", d.losses), ("kl_losses", d.kl_losses),      # noqa: E731
+                                  ("grad_clip", d.grad_clip))
+                run(entries, lambda: common() + (("value_head_grad", d.value_head_grad[:M]),))
+                # the demonstration cells behind the others, and the workspace a later cell may show unwritten (the last norm, the KL floats, dv) put back behind them: the
+                # text of every other cell is what it is without them
+                carried = [x.clone() for x in (d.grad_clip, d.kl_losses, d.losses, d.value_head_grad)]
+                run(demo_entries, lambda: common() + (("demo_losses", d.demo_losses), ("value_head_grad", d.value_head_grad[:M + M_DEMO])))
+                for x, y in zip((d.grad_clip, d.kl_losses, d.losses, d.value_head_grad), carried):
+                    x.copy_(y)
                 d.set_max_grad_norm(None)
         d.close()
 L.mi_comm_destroy(hcomm)
