@@ -175,11 +175,9 @@ int try_tapconv(hipStream_t st, int dtype, int mode, const void* a, const void* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Deferred split reductions.  The reduce that follows a tapwgrad launch is a small, bandwidth-trivial kernel, but on the filter-gradient
-// stream of the engine it shares the chip with a big input-gradient kernel and takes 15-30 us instead of 7.  In deferred mode the launch
-// is recorded instead (parameters by value; every layer then needs its OWN scratch region until the flush) and mi_tapwgrad_flush issues
-// all of them back to back.  Per host THREAD (thread_local): a backward pass is issued by one thread from defer(1) to flush, so two engines driven by two
-// threads keep separate lists (round 3; the tuning knobs stay process-global configuration).  Used by the VAE engine only.
+// Deferred split reductions (MiTiledReduces, mi_internal.hpp: the rules).  The reduce that follows a tapwgrad launch is a small, bandwidth-trivial kernel, but on the
+// filter-gradient stream of the engine it shares the chip with a big input-gradient kernel and takes 15-30 us instead of 7.  A pass that brings a list has the launch
+// recorded instead (parameters by value) and mi_tiled_reduces_flush issues all of them back to back.  Used by the VAE engine only.
 // one more job of a fused ordered slab sum (kernel: tapwgrad_tile.hpp, sr_job_body); the lane count depends on the job's shape only
 static int sr_kl(long long n, int nslab) {                // slab lanes per element group: a power of two, >= ~96 blocks per job where the slabs allow
     const long long quads = (n + 3) / 4;
@@ -202,8 +200,11 @@ struct PendingReduce { TapWgradParams q; int splits, ngroups, kind; const float*
 // element c), the kernel produces dW'[t][2R][2Q] in a temporary, and the fold  dW[t][r][q] += dW'[t][2r][2q] + dW'[t][2r][2q+1] + dW'[t][2r+1][2q] + dW'[t][2r+1][2q+1]
 // (all four partial products of the two-term expansion) follows the slab reduce -- deferred with it when the reduces are deferred.
 struct PendingFold { const float* tmp; float* out; const float* tmp_bias; float* dbias; int T, R, Q, NB; };
-static thread_local PendingFold g_folds[16];
-static thread_local int g_nfolds = 0;
+struct TiledStore { PendingReduce reduce[16]; PendingFold fold[16]; FusedReduceParams fused; };      // MiTiledReduces::store (the 3.5 KB argument block of the fused launch with it: off the flush's stack)
+static_assert(sizeof(TiledStore) <= sizeof(MiTiledReduces::store) && alignof(TiledStore) <= 16 && MI_SMALL_SUMS_MAX == SR_MAX, "mi_internal.hpp: the lists' sizes");
+static inline TiledStore& tiled_store(MiTiledReduces* l) { return *reinterpret_cast<TiledStore*>(l->store); }
+static inline MiTiledReduces* tiled_on(const MiWgradCtx* c, hipStream_t st) { return c && c->tiled && c->tiled->stream == st ? c->tiled : nullptr; }      // the list that records what a call on st issues, or NULL
+static inline MiSmallSums* small_of(const MiWgradCtx* c) { return c ? c->small : nullptr; }
 __global__ __launch_bounds__(256) void fold_split_kernel(const PendingFold f) {
     const long long n = (long long)f.T * f.R * f.Q;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -221,76 +222,29 @@ static int launch_fold(hipStream_t st, const PendingFold& f) {
     MI_LAUNCH(fold_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f);
     return mi_check_launch("fold_split_kernel");
 }
-static thread_local PendingReduce g_pending[16];
-static thread_local int g_npending = 0, g_defer_reduces = 0, g_defer_pause = 0;
 static unsigned reduce_ry(const PendingReduce& r) {       // slab chains per element (a power of two <= 64, from the shape only): about 512 blocks in flight, at most ~16 slabs per thread
     unsigned ry = 1;                                        // (MI355_REDUCE_RY_CAP: A/B knob -- fewer chains = longer contiguous pieces per slab and block, fewer blocks)
     while (((unsigned)(r.ngroups / 512 + 1) * ry < 512 || r.splits / (int)ry > 16) && (int)(ry * 2) <= r.splits / 4 && ry < (unsigned)knob(K_REDUCE_RY_CAP)) ry *= 2;
     return ry;
 }
 static unsigned reduce_blocks(const PendingReduce& r, unsigned ry) { const unsigned upb = 256 / ry, nunits = (unsigned)r.ngroups / 2; return (nunits + upb - 1) / upb; }      // units = pairs of 16-byte groups
-static void launch_tiled_reduce(hipStream_t st, const PendingReduce& r) {
+static void launch_tiled_reduce(hipStream_t st, const PendingReduce& r, MiSmallSums* small) {
     const unsigned ry = reduce_ry(r);
     const dim3 rg(reduce_blocks(r, ry), 1, 1);
     if (r.kind == 0) MI_LAUNCH((reduce_tiled_kernel<TC_CONV, 2, 4, 2>), rg, dim3(256), 0, st, r.q, r.splits, r.ngroups, (int)ry);
     else if (r.kind == 1) MI_LAUNCH((reduce_tiled_kernel<TC_GATHER, 2, 4, 2>), rg, dim3(256), 0, st, r.q, r.splits, r.ngroups, (int)ry);
     else MI_LAUNCH((reduce_tiled_kernel<TC_GATHER, 3, 2, 4>), rg, dim3(256), 0, st, r.q, r.splits, r.ngroups, (int)ry);
-    if (r.bpart) mi_reduce_slabs(st, r.bpart, (long long)r.bN, r.bnslab, (long long)r.bN, r.bout);
+    if (r.bpart) mi_reduce_slabs(st, r.bpart, (long long)r.bN, r.bnslab, (long long)r.bN, r.bout, 0, small);
 }
-extern "C" int mi_tapwgrad_defer(int on) {               // switching the mode drops whatever an aborted pass may have left in the list
-    const int prev = g_defer_reduces;
-    g_defer_reduces = on ? 1 : 0;
-    g_npending = 0; g_nfolds = 0; g_defer_pause = 0;
-    return prev;
-}
-// pause != 0: the next filter gradients reduce their slabs right behind their own launch although the pass defers (a layer issued on ANOTHER stream than the
-// one the deferred list will be flushed on); returns the previous setting
-extern "C" int mi_tapwgrad_defer_pause(int pause) { const int prev = g_defer_pause; g_defer_pause = pause ? 1 : 0; return prev; }
-static thread_local int t_slab_bf16 = -1;                  // this thread's override for the pass it is issuing (-1: the process default, K_SLAB_BF16_DEFAULT)
-static inline int slab_bf16_now() { return t_slab_bf16 >= 0 ? t_slab_bf16 : knob(K_SLAB_BF16_DEFAULT); }
-static thread_local int t_bias_rows = 0;                   // this thread's pass wants the bias sums of a one-split launch ordered as well (see try_tapwgrad)
+static thread_local int t_bias_rows = 0;                   // what a call WITHOUT a context (a layer-op call from outside) does about the bias sums of a one-split launch (see try_tapwgrad)
 extern "C" int mi_tapwgrad_bias_rows(int on) { const int prev = t_bias_rows; t_bias_rows = on ? 1 : 0; return prev; }
-extern "C" int mi_tapwgrad_slab_bf16(int on) { const int prev = t_slab_bf16; t_slab_bf16 = on < 0 ? -1 : (on ? 1 : 0); return prev; }
-static int tapwgrad_flush_reduces(void* stream);
-extern "C" int mi_tapwgrad_flush(void* stream) {
-    int rc = tapwgrad_flush_reduces(stream);
-    const int nf = g_nfolds;
-    g_nfolds = 0;
-    // A fold reads its layer's bias sums (tmp_bias).  A LONE deferred filter gradient reduces them through mi_reduce_slabs, and inside a backward PART (mi_vae_backward,
-    // part != 0) that call only records a job in the pass's small-reduce list, which is bound to this very stream and flushed behind this function: the fold then read the
-    // zeros of the memset and the split-storage engine lost conv2's bias gradient in every data-parallel step.  The list runs first.
-    if (nf > 0 && rc == MI_OK) rc = mi_small_reduce_flush_bound(stream);
-    for (int i = 0; i < nf && rc == MI_OK; ++i) rc = launch_fold((hipStream_t)stream, g_folds[i]);
-    return rc;
-}
-static int tapwgrad_flush_reduces(void* stream) {
-    const int n = g_npending;
-    g_npending = 0;
-    if (n == 0) return MI_OK;
-    if (n == 1 || n > TW_MAX_FUSED) {
-        for (int i = 0; i < n; ++i) launch_tiled_reduce((hipStream_t)stream, g_pending[i]);
-        return mi_check_launch("reduce_tiled_kernel");
-    }
-    static thread_local FusedReduceParams f;              // (4 KB: kept off the stack; the launch copies it into the kernel-argument buffer)
-    f.n = n; f.first[0] = 0; f.bias.njobs = 0; f.bias.first[0] = 0; f.bias.ovw = 0;
-    for (int i = 0; i < n; ++i) {
-        const PendingReduce& r = g_pending[i];
-        f.q[i] = r.q; f.splits[i] = r.splits; f.ngroups[i] = r.ngroups; f.kind[i] = r.kind; f.ry[i] = (int)reduce_ry(r);
-        f.first[i + 1] = f.first[i] + (int)reduce_blocks(r, (unsigned)f.ry[i]);
-        if (r.bpart && f.bias.njobs < SR_MAX) sr_add(f.bias, r.bpart, (long long)r.bN, r.bnslab, (long long)r.bN, r.bout);
-    }
-    for (int i = n; i < TW_MAX_FUSED; ++i) f.first[i + 1] = f.first[n];
-    for (int i = f.bias.njobs; i < SR_MAX; ++i) f.bias.first[i + 1] = f.bias.first[f.bias.njobs];
-    MI_LAUNCH(reduce_fused_kernel, dim3((unsigned)(f.first[n] + f.bias.first[f.bias.njobs])), dim3(256), 0, (hipStream_t)stream, f);
-    return mi_check_launch("reduce_fused_kernel");
-}
 
 // tapwgrad (tapwgrad_tile.hpp): bf16 weight gradients of the wide stride-2 layers on raw-staged slot tiles.
 // mi_set_tuning key 3 / MI355_TAPWGRAD=0 disables it.
 // ---------------------------------------------------------------------------------------------------------------
 // a: slot-side tensor [B,IH,IW,C]; d: gradient tensor [B,OH,OW,N]; out: dW (conv form HWIO [kh,kw,C,N]; gather form [kh,kw,N,C])
 int try_tapwgrad(hipStream_t st, int dtype, int mode, const void* a, const void* d, int B, int IH, int IW, int C, int OH, int OW, int N,
-                 int KH, int KW, float* out, void* scratch, long long scratch_bytes, float* dbias) {
+                 int KH, int KW, float* out, void* scratch, long long scratch_bytes, float* dbias, const MiWgradCtx* ctx) {
     if (!knob(K_TAPWGRAD) || dtype != MI_BF16) return 0;
     if (KH != KW || KH < 3 || KH > 6) return 0;
     if ((((uintptr_t)a) & 15) || (((uintptr_t)d) & 15) || C % 8 != 0 || N % 8 != 0) return 0;
@@ -353,7 +307,7 @@ int try_tapwgrad(hipStream_t st, int dtype, int mode, const void* a, const void*
     // when it is large enough; otherwise fp32 atomics straight into dW (~1 element per clock per CU: 35-45 % of the kernel at 256 splits)
     const int kt_tiles = taps == 2 ? 4 : 2;
     const long long slab_floats = (long long)gy * q.npairs * kt_tiles * 1024;
-    q.slabs = nullptr; q.slab_stride = slab_floats; q.slab_bf16 = slab_bf16_now() ? 1 : 0;
+    q.slabs = nullptr; q.slab_stride = slab_floats; q.slab_bf16 = ((ctx && ctx->slab_bf16) || knob(K_SLAB_BF16_DEFAULT)) ? 1 : 0;
     const bool split = knob(K_TAPWGRAD_SPLIT) && taps == 2 && q.npairs == 8;   // wave = (tap, position half): fewer LDS reads per MFMA
     // behind the slabs: the bias-gradient partial sums of every position split (x 2 position halves in the split layout), summed in a fixed order with the slabs
     const long long slab_bytes = ((long long)splits * slab_floats * (q.slab_bf16 ? 2 : 4) + 255) / 256 * 256;
@@ -362,10 +316,10 @@ int try_tapwgrad(hipStream_t st, int dtype, int mode, const void* a, const void*
     if (scratch && splits > 1 && (((uintptr_t)scratch) & 15) == 0 && scratch_bytes >= slab_bytes + bias_bytes && slab_floats < (1ll << 29) && (!dbias || N <= 256)) {
         q.slabs = (float*)scratch;
         if (dbias) q.bias_part = (float*)((char*)scratch + slab_bytes);
-    } else if (t_bias_rows && scratch && splits == 1 && dbias && (((uintptr_t)scratch) & 15) == 0 && scratch_bytes >= bias_bytes && N <= 256) {
+    } else if ((ctx ? ctx->bias_rows : t_bias_rows) && scratch && splits == 1 && dbias && (((uintptr_t)scratch) & 15) == 0 && scratch_bytes >= bias_bytes && N <= 256) {
         // ONE position split (a few frames of a small layer): dW needs no slabs, but every bias element is still the sum of bias_nh x NE / N partial sums (position halves, parity
         // classes).  Through atomics they met in any order: two runs of a small-batch step differed in the last bit of a bias gradient.  Where the caller asked for it
-        // (mi_tapwgrad_bias_rows: the VAE engine) the partial sums take the FIRST bias_bytes of the scratch -- there are no slabs in front of them -- and the ordered pass below.
+        // (MiWgradCtx::bias_rows: the VAE engine; mi_tapwgrad_bias_rows from outside) the partial sums take the FIRST bias_bytes of the scratch -- there are no slabs in front of them -- and the ordered pass below.
         // Off (the layer-op entry points' default): a scratch that holds no slabs stays untouched, as before.
         q.bias_part = (float*)scratch;
     }
@@ -398,17 +352,18 @@ int try_tapwgrad(hipStream_t st, int dtype, int mode, const void* a, const void*
         PendingReduce r;
         r.q = q; r.splits = splits; r.ngroups = (int)(slab_floats / 4); r.kind = mode == TC_CONV ? 0 : (taps == 2 ? 1 : 2);
         r.bpart = q.bias_part; r.bout = dbias; r.bnslab = splits * q.bias_nh * (q.NE / N); r.bN = N;
-        if (g_defer_reduces && !g_defer_pause && g_npending < 16) g_pending[g_npending++] = r;
-        else { launch_tiled_reduce(st, r); rc = mi_check_launch("reduce_tiled_kernel"); }
+        MiTiledReduces* const l = tiled_on(ctx, st);
+        if (l && l->nreduce < 16) tiled_store(l).reduce[l->nreduce++] = r;
+        else { launch_tiled_reduce(st, r, small_of(ctx)); rc = mi_check_launch("reduce_tiled_kernel"); }
     } else if (rc == MI_OK && q.bias_part) {
-        rc = mi_reduce_slabs(st, q.bias_part, (long long)N, splits * q.bias_nh * (q.NE / N), (long long)N, dbias);
+        rc = mi_reduce_slabs(st, q.bias_part, (long long)N, splits * q.bias_nh * (q.NE / N), (long long)N, dbias, 0, small_of(ctx));
     }
     return rc == MI_OK ? 1 : rc;
 }
 
 // MI_BF16X3 filter gradients on the bf16 kernel (see PendingFold): scratch = [dW' (4 x the filter, fp32) | bias' (2 N) | slabs ...]
 int try_tapwgrad_split(hipStream_t st, int mode, const void* a, const void* d, int B, int IH, int IW, int C, int OH, int OW, int N,
-                       int KH, int KW, float* out, void* scratch, long long scratch_bytes, float* dbias) {
+                       int KH, int KW, float* out, void* scratch, long long scratch_bytes, float* dbias, const MiWgradCtx* ctx) {
     const int on = knob(K_X3_TAPWGRAD);
     if (!on || !scratch || (((uintptr_t)scratch) & 255)) return 0;
     const long long nw = (long long)KH * KW * C * N;
@@ -422,11 +377,11 @@ int try_tapwgrad_split(hipStream_t st, int mode, const void* a, const void* d, i
     if (on != 2 && (mode != TC_CONV || (long long)C * N > 64 * 128)) return 0;
     float* tmp = (float*)scratch; float* tb = tmp + 4 * nw;
     if (hipMemsetAsync(tmp, 0, (size_t)((4 * nw + 2 * N) * 4), st) != hipSuccess) return mi_fail(MI_ERR_LAUNCH, "try_tapwgrad_split: memset failed");
-    const int r = try_tapwgrad(st, MI_BF16, mode, a, d, B, IH, IW, 2 * C, OH, OW, 2 * N, KH, KW, tmp, (char*)scratch + tmp_bytes, scratch_bytes - tmp_bytes, dbias ? tb : nullptr);
+    const int r = try_tapwgrad(st, MI_BF16, mode, a, d, B, IH, IW, 2 * C, OH, OW, 2 * N, KH, KW, tmp, (char*)scratch + tmp_bytes, scratch_bytes - tmp_bytes, dbias ? tb : nullptr, ctx);
     if (r <= 0) return r;
     PendingFold f = {tmp, out, tb, dbias, KH * KW, mode == TC_CONV ? C : N, mode == TC_CONV ? N : C, N};
-    if (g_defer_reduces && !g_defer_pause && g_nfolds < 16) { g_folds[g_nfolds++] = f; return 1; }
-    { const int rcf = mi_small_reduce_flush_bound(st); if (rcf != MI_OK) return rcf; }      // (the fold reads the bias sums: a deferring pass on this stream may only have recorded them)
+    if (MiTiledReduces* const l = tiled_on(ctx, st); l && l->nfold < 16) { tiled_store(l).fold[l->nfold++] = f; return 1; }
+    if (MiSmallSums* const sm = small_of(ctx); sm && sm->stream == st) { const int rcf = mi_small_sums_flush(sm); if (rcf != MI_OK) return rcf; }      // (the fold reads the bias sums: a pass with a list on this stream may only have recorded them)
     const int rc = launch_fold(st, f);
     return rc == MI_OK ? 1 : rc;
 }
@@ -490,7 +445,7 @@ int try_gather_narrow(hipStream_t st, int dtype, const void* a, const void* w, i
 // narrow: [*,IH,IW,Cs] (fp32 frames, optionally gathered, or bf16); wide: [B,OH,OW,32]; out [KH*KW*Cs][32] fp32 (+=)
 int try_narrow_wgrad(hipStream_t st, int dtype, const void* narrow, int narrow_f32, const int* frame_idx, const void* wide,
                      int B, int IH, int IW, int Cs, int OH, int OW, int Nwide, int KH, int KW, float* out, float* dbias,
-                     void* scratch, long long scratch_bytes) {
+                     void* scratch, long long scratch_bytes, const MiWgradCtx* ctx) {
     if (!knob(K_NARROW) || dtype != MI_BF16) return 0;
     const int run = KW * Cs;
     if (Nwide != 32 || KH > 4 || run > 12 || run % 4 != 0 || KH * run > 64 || (((uintptr_t)wide) & 15)) return 0;
@@ -532,8 +487,8 @@ int try_narrow_wgrad(hipStream_t st, int dtype, const void* narrow, int narrow_f
     int rc = mi_check_launch("narrow_wgrad_kernel");
     if (rc == MI_OK && q.slabs) {
         const long long n_out = (long long)KH * run * 32;
-        rc = mi_reduce_slabs(st, q.slabs, (long long)NW_SLAB, blocks, n_out, out);
-        if (rc == MI_OK && dbias) rc = mi_reduce_slabs(st, q.slabs + 64 * 32, (long long)NW_SLAB, blocks, 32ll, dbias);
+        rc = mi_reduce_slabs(st, q.slabs, (long long)NW_SLAB, blocks, n_out, out, 0, small_of(ctx));
+        if (rc == MI_OK && dbias) rc = mi_reduce_slabs(st, q.slabs + 64 * 32, (long long)NW_SLAB, blocks, 32ll, dbias, 0, small_of(ctx));
     }
     return rc == MI_OK ? 1 : rc;
 }
@@ -773,7 +728,7 @@ static int prepare_wgrad(int dtype, WgradParams& p, int target_blocks, void* scr
     return MI_OK;
 }
 
-int launch_wgrad(hipStream_t st, int dtype, int in_f32, WgradParams& p, int target_blocks, void* scratch = nullptr, long long scratch_bytes = 0, int overwrite = 0) {
+int launch_wgrad(hipStream_t st, int dtype, int in_f32, WgradParams& p, int target_blocks, void* scratch = nullptr, long long scratch_bytes = 0, int overwrite = 0, const MiWgradCtx* ctx = nullptr) {
     dim3 g; bool wide = false;
     { const int rc0 = prepare_wgrad(dtype, p, target_blocks, scratch, scratch_bytes, overwrite, &g, &wide); if (rc0 != MI_OK) return rc0; }
     const int splits = (int)g.z;
@@ -808,8 +763,8 @@ int launch_wgrad(hipStream_t st, int dtype, int in_f32, WgradParams& p, int targ
 #undef WG_LAUNCH
     int rc = mi_check_launch("wgrad_kernel");
     if (rc == MI_OK && p.slabs) {
-        rc = mi_reduce_slabs(st, p.slabs, p.slab_stride, splits, (long long)p.Kc * p.N, p.out, overwrite);
-        if (rc == MI_OK && p.ones_row) rc = mi_reduce_slabs(st, p.slabs + (long long)p.Kc * p.N, p.slab_stride, splits, (long long)p.N, p.dbias, overwrite);
+        rc = mi_reduce_slabs(st, p.slabs, p.slab_stride, splits, (long long)p.Kc * p.N, p.out, overwrite, small_of(ctx));
+        if (rc == MI_OK && p.ones_row) rc = mi_reduce_slabs(st, p.slabs + (long long)p.Kc * p.N, p.slab_stride, splits, (long long)p.N, p.dbias, overwrite, small_of(ctx));
     }
     return rc;
 }
@@ -831,61 +786,54 @@ inline bool needs_merge(int C, int dtype, int in_f32) {
 }  // namespace
 
 // internal entry points for the other translation units (mi_internal.hpp)
-// Ordered slab sums: out[0 .. n) += sum_k slabs[k * stride + i], fixed order.  Deferred mode (per host thread; the VAE engine around the end of a full backward pass):
-// the jobs are recorded and mi_small_reduce_flush issues all of them as ONE launch -- every job's slabs must stay untouched until then and be complete on the
-// flush stream (the engine gives each its own piece of scratch and flushes on the stream that produced them).
-static thread_local SmallReduceParams t_sr;
-static thread_local int t_sr_defer = 0;
-// The recorded list belongs to ONE stream (round 5): the stream of its first job, or the one the engine named with mi_small_reduce_bind.  A job that
-// arrives from another stream while the pass defers (e.g. conv1's narrow filter gradient on the caller's stream in a backward part whose list is bound to the
-// filter-gradient stream) is launched at once on ITS stream instead of being flushed later on a stream that never waited for its slabs.
-static thread_local hipStream_t t_sr_stream = nullptr;
-static thread_local bool t_sr_bound = false;
-static int sr_launch_params(hipStream_t st, SmallReduceParams& f) {
-    if (f.njobs == 0) return MI_OK;
+// Ordered slab sums (MiSmallSums, mi_internal.hpp: the rules): out[0 .. n) += sum_k slabs[k * stride + i], fixed order.  The VAE engine around the end of a full backward pass and in
+// the parts of a data-parallel step, and the MlpVAE engine, record seven to eleven latency-bound launches in a row and issue them as ONE; the engine gives each job its own piece of
+// scratch and flushes on the stream that produced the slabs.
+static int sr_launch(hipStream_t st, const MiSlabSum* job, int njobs) {
+    if (njobs == 0) return MI_OK;
+    SmallReduceParams f = {};
+    for (int j = 0; j < njobs; ++j) sr_add(f, job[j].slabs, job[j].stride, job[j].nslab, job[j].n, job[j].out, job[j].overwrite);
     for (int i = f.njobs; i < SR_MAX; ++i) f.first[i + 1] = f.first[f.njobs];
     MI_LAUNCH(reduce_small_fused_kernel, dim3((unsigned)f.first[f.njobs]), dim3(256), 0, st, f);
-    f.njobs = 0;
     return mi_check_launch("reduce_small_fused_kernel");
 }
-int mi_reduce_slabs(hipStream_t st, const float* slabs, long long stride, int nslab, long long n, float* out, int overwrite) {
+int mi_small_sums_flush(MiSmallSums* l) { const int n = l->njobs; l->njobs = 0; return sr_launch(l->stream, l->job, n); }
+int mi_reduce_slabs(hipStream_t st, const float* slabs, long long stride, int nslab, long long n, float* out, int overwrite, MiSmallSums* list) {
     if (nslab < 1 || n < 1) return MI_OK;
-    SmallReduceParams& f = t_sr;
-    if (!t_sr_defer || ((f.njobs > 0 || t_sr_bound) && st != t_sr_stream)) {      // not deferring, or not the list's stream: one launch of its own, right here
-        SmallReduceParams one = {};
-        sr_add(one, slabs, stride, nslab, n, out, overwrite);
-        return sr_launch_params(st, one);
-    }
-    if (f.njobs == SR_MAX) { const int rc = sr_launch_params(t_sr_stream, f); if (rc != MI_OK) return rc; }      // (a full list is issued as it is, on its own stream: still one fixed order per job)
-    if (f.njobs == 0 && !t_sr_bound) t_sr_stream = st;
-    sr_add(f, slabs, stride, nslab, n, out, overwrite);
+    const MiSlabSum job = {slabs, out, stride, n, nslab, overwrite};
+    if (!list || st != list->stream) return sr_launch(st, &job, 1);      // no list, or not the list's stream: one launch of its own, right here
+    if (list->njobs == MI_SMALL_SUMS_MAX) { const int rc = mi_small_sums_flush(list); if (rc != MI_OK) return rc; }      // (a full list is issued as it is: still one fixed order per job)
+    list->job[list->njobs++] = job;
     return MI_OK;
 }
-extern "C" int mi_small_reduce_defer(int on) {              // returns the previous mode; switching drops what an aborted pass may have left in the list
-    const int prev = t_sr_defer;
-    t_sr_defer = on ? 1 : 0;
-    t_sr.njobs = 0; t_sr.first[0] = 0;
-    t_sr_bound = false; t_sr_stream = nullptr;
-    return prev;
-}
-extern "C" int mi_small_reduce_bind(void* stream) {         // the deferring pass names the stream its list will be flushed on (jobs from any other stream launch at once)
-    if (t_sr.njobs > 0 && (hipStream_t)stream != t_sr_stream) return mi_fail(MI_ERR_STATE, "mi_small_reduce_bind: jobs of another stream are pending");
-    t_sr_stream = (hipStream_t)stream; t_sr_bound = true;
-    return MI_OK;
-}
-extern "C" int mi_small_reduce_flush(void* stream) {
-    if (t_sr.njobs == 0) return MI_OK;
-    if ((hipStream_t)stream != t_sr_stream) {               // a programming error in the calling engine: nothing is lost (the list runs where its slabs are complete), but say so
-        const int rc = sr_launch_params(t_sr_stream, t_sr);
-        return rc != MI_OK ? rc : mi_fail(MI_ERR_STATE, "mi_small_reduce_flush: the recorded jobs belong to another stream (issued there)");
+int mi_tiled_reduces_flush(MiTiledReduces* l, MiSmallSums* small) {
+    TiledStore& t = tiled_store(l);
+    const int n = l->nreduce, nf = l->nfold;
+    l->nreduce = 0; l->nfold = 0;
+    int rc = MI_OK;
+    if (n == 1 || n > TW_MAX_FUSED) {
+        for (int i = 0; i < n; ++i) launch_tiled_reduce(l->stream, t.reduce[i], small);
+        rc = mi_check_launch("reduce_tiled_kernel");
+    } else if (n > 0) {
+        FusedReduceParams& f = t.fused;                     // (the launch copies it into the kernel-argument buffer)
+        f.n = n; f.first[0] = 0; f.bias.njobs = 0; f.bias.first[0] = 0; f.bias.ovw = 0;
+        for (int i = 0; i < n; ++i) {
+            const PendingReduce& r = t.reduce[i];
+            f.q[i] = r.q; f.splits[i] = r.splits; f.ngroups[i] = r.ngroups; f.kind[i] = r.kind; f.ry[i] = (int)reduce_ry(r);
+            f.first[i + 1] = f.first[i] + (int)reduce_blocks(r, (unsigned)f.ry[i]);
+            if (r.bpart && f.bias.njobs < SR_MAX) sr_add(f.bias, r.bpart, (long long)r.bN, r.bnslab, (long long)r.bN, r.bout);
+        }
+        for (int i = n; i < TW_MAX_FUSED; ++i) f.first[i + 1] = f.first[n];
+        for (int i = f.bias.njobs; i < SR_MAX; ++i) f.bias.first[i + 1] = f.bias.first[f.bias.njobs];
+        MI_LAUNCH(reduce_fused_kernel, dim3((unsigned)(f.first[n] + f.bias.first[f.bias.njobs])), dim3(256), 0, l->stream, f);
+        rc = mi_check_launch("reduce_fused_kernel");
     }
-    return sr_launch_params(t_sr_stream, t_sr);
-}
-extern "C" int mi_small_reduce_deferring(void) { return t_sr_defer; }
-// the recorded jobs now, if the list belongs to `stream` (anything else: nothing happens, nothing is an error)
-extern "C" int mi_small_reduce_flush_bound(void* stream) {
-    if (t_sr.njobs == 0 || (hipStream_t)stream != t_sr_stream) return MI_OK;
-    return sr_launch_params(t_sr_stream, t_sr);
+    // A fold reads its layer's bias sums (tmp_bias).  A LONE recorded filter gradient reduces them through mi_reduce_slabs, and inside a backward PART (mi_vae_backward,
+    // part != 0) that call only records a job in the part's small list, which lives on this very stream and is flushed behind this function: the fold then read the
+    // zeros of the memset and the split-storage engine lost conv2's bias gradient in every data-parallel step.  The list runs first.
+    if (nf > 0 && rc == MI_OK && small && small->stream == l->stream) rc = mi_small_sums_flush(small);
+    for (int i = 0; i < nf && rc == MI_OK; ++i) rc = launch_fold(l->stream, t.fold[i]);
+    return rc;
 }
 
 void mi_get_trace(long long** buf, int* cap) { *buf = g_trace; *cap = g_trace_cap; }
@@ -894,6 +842,15 @@ extern "C" {
 
 // debug: device buffer of int64 stamps, 32 per wave of every tapconv block (see tools/trace_tapconv.py); nullptr switches it off
 int mi_debug_set_trace(void* dev_ptr, int capacity_entries) { g_trace = (long long*)dev_ptr; g_trace_cap = dev_ptr ? capacity_entries : 0; return MI_OK; }
+
+// debug (tools/wgrad_ablate.py; in no header): a raw-staged filter gradient WITHOUT its slab reduce, i.e. the product kernel alone -- the reduce is recorded in a list of this
+// call's own that goes out of scope unflushed.  deconv == 0: mi_conv2d_nhwc_wgrad_ws(t0 = x [B,H,W,C0], t1 = dy, C1 = Cout); else mi_deconv2d_nhwc_wgrad_ws(t0 = dy [B,H,W,C0], t1 = x, C1 = Cin)
+int mi_debug_wgrad_unreduced(void* stream, int deconv, int dtype, const void* t0, int B, int H, int W, int C0, const void* t1, int K, int C1, float* dw, void* scratch, long long scratch_bytes, float* dbias) {
+    MiTiledReduces dropped(stream);
+    const MiWgradCtx cx = {&dropped, nullptr, 0, 0};
+    return deconv ? mi_deconv2d_nhwc_wgrad_ctx(stream, dtype, t0, B, H, W, C0, t1, K, K, C1, dw, scratch, scratch_bytes, dbias, &cx)
+                  : mi_conv2d_nhwc_wgrad_ctx(stream, dtype, t0, nullptr, 0, B, H, W, C0, t1, K, K, C1, dw, scratch, scratch_bytes, dbias, &cx);
+}
 
 // conv2d NHWC stride-2 VALID forward: out[B,OH,OW,Cout] = relu?(im2col(x) * W[kh,kw,ci,co] + bias)
 // replaces tf.layers.conv2d in ConvVAE.build_encoder (reference vae/models.py:250-253)
@@ -952,28 +909,32 @@ int mi_conv2d_nhwc_dgrad_bits(void* stream, int dtype, const void* dy, int B, in
 // conv2d filter gradient: dw[kh,kw,ci,co] += im2col(x)^T * dy      (TF Conv2DBackpropFilter), fp32 accumulate
 int mi_conv2d_nhwc_wgrad(void* stream, int dtype, const void* x, const int* frame_idx, int x_is_f32,
                          int B, int IH, int IW, int Cin, const void* dy, int KH, int KW, int Cout, float* dw) {
-    return mi_conv2d_nhwc_wgrad_ws(stream, dtype, x, frame_idx, x_is_f32, B, IH, IW, Cin, dy, KH, KW, Cout, dw, nullptr, 0, nullptr);
+    return mi_conv2d_nhwc_wgrad_ctx(stream, dtype, x, frame_idx, x_is_f32, B, IH, IW, Cin, dy, KH, KW, Cout, dw, nullptr, 0, nullptr, nullptr);
 }
 
 // same with caller-provided scratch (bytes): lets the bf16 kernel reduce its position splits without atomics (deterministic)
 int mi_conv2d_nhwc_wgrad_ws(void* stream, int dtype, const void* x, const int* frame_idx, int x_is_f32,
                             int B, int IH, int IW, int Cin, const void* dy, int KH, int KW, int Cout, float* dw, void* scratch, long long scratch_bytes,
                             float* dbias) {
+    return mi_conv2d_nhwc_wgrad_ctx(stream, dtype, x, frame_idx, x_is_f32, B, IH, IW, Cin, dy, KH, KW, Cout, dw, scratch, scratch_bytes, dbias, nullptr);
+}
+int mi_conv2d_nhwc_wgrad_ctx(void* stream, int dtype, const void* x, const int* frame_idx, int x_is_f32, int B, int IH, int IW, int Cin, const void* dy, int KH, int KW, int Cout,
+                             float* dw, void* scratch, long long scratch_bytes, float* dbias, const MiWgradCtx* ctx) {
     const int OH = (IH - KH) / 2 + 1, OW = (IW - KW) / 2 + 1;
     {
-        const int r4 = try_narrow_wgrad((hipStream_t)stream, dtype, x, x_is_f32 == 2 ? 2 : ((x_is_f32 || dtype == MI_F32) ? 1 : 0), frame_idx, dy, B, IH, IW, Cin, OH, OW, Cout, KH, KW, dw, dbias, scratch, scratch_bytes);   // per-block slabs + ordered reduce when the caller brings scratch (deterministic; atomics measured 92 vs 119 us -- the engines' default path is the fused encoder-head kernel anyway)
+        const int r4 = try_narrow_wgrad((hipStream_t)stream, dtype, x, x_is_f32 == 2 ? 2 : ((x_is_f32 || dtype == MI_F32) ? 1 : 0), frame_idx, dy, B, IH, IW, Cin, OH, OW, Cout, KH, KW, dw, dbias, scratch, scratch_bytes, ctx);   // per-block slabs + ordered reduce when the caller brings scratch (deterministic; atomics measured 92 vs 119 us -- the engines' default path is the fused encoder-head kernel anyway)
         if (r4 != 0) return r4 > 0 ? MI_OK : r4;
     }
     if (x_is_f32 == 2) return mi_fail(MI_ERR_ARG, "mi_conv2d_nhwc_wgrad: uint8 frames are only read by the narrow-layer kernel (bf16 mode)");
     if (!frame_idx && !x_is_f32) {
-        const int r3 = dtype == MI_BF16X3 ? try_tapwgrad_split((hipStream_t)stream, TC_CONV, x, dy, B, IH, IW, Cin, OH, OW, Cout, KH, KW, dw, scratch, scratch_bytes, dbias)
-                                          : try_tapwgrad((hipStream_t)stream, dtype, TC_CONV, x, dy, B, IH, IW, Cin, OH, OW, Cout, KH, KW, dw, scratch, scratch_bytes, dbias);
+        const int r3 = dtype == MI_BF16X3 ? try_tapwgrad_split((hipStream_t)stream, TC_CONV, x, dy, B, IH, IW, Cin, OH, OW, Cout, KH, KW, dw, scratch, scratch_bytes, dbias, ctx)
+                                          : try_tapwgrad((hipStream_t)stream, dtype, TC_CONV, x, dy, B, IH, IW, Cin, OH, OW, Cout, KH, KW, dw, scratch, scratch_bytes, dbias, ctx);
         if (r3 != 0) return r3 > 0 ? MI_OK : r3;
     }
-    if (dbias) {                                          // not fused on this path: BiasAddGrad as its own pass, with the first piece of the scratch (its reduce may be deferred: the filter gradient below must not reuse it)
+    if (dbias) {                                          // not fused on this path: BiasAddGrad as its own pass, with the first piece of the scratch (its reduce may only be recorded: the filter gradient below must not reuse it)
         long long cb = (mi_colsum_scratch_bytes(dtype, (long long)B * OH * OW, Cout) + 255) / 256 * 256;
         if (!scratch || cb > scratch_bytes) cb = 0;
-        const int rcb = mi_colsum_ws(stream, dtype, dy, (long long)B * OH * OW, Cout, dbias, cb ? scratch : nullptr, cb);
+        const int rcb = mi_colsum_ctx(stream, dtype, dy, (long long)B * OH * OW, Cout, dbias, cb ? scratch : nullptr, cb, ctx);
         if (rcb != MI_OK) return rcb;
         if (cb) { scratch = (char*)scratch + cb; scratch_bytes -= cb; }
     }
@@ -981,7 +942,7 @@ int mi_conv2d_nhwc_wgrad_ws(void* stream, int dtype, const void* x, const int* f
     p.big = x; p.frame_idx = frame_idx;
     fill_wgrad_geom(p, B, IH, IW, Cin, OH, OW, KH, KW, 2, needs_merge(Cin, dtype, x_is_f32));
     p.N = Cout; p.small = dy; p.s_vec = vec_ok(dy, Cout, dtype); p.out = dw;
-    return launch_wgrad((hipStream_t)stream, dtype, x_is_f32, p, 1024, scratch, scratch_bytes);
+    return launch_wgrad((hipStream_t)stream, dtype, x_is_f32, p, 1024, scratch, scratch_bytes, 0, ctx);
 }
 
 // conv2d_transpose NHWC stride-2 VALID forward, kernel [kh,kw,co,ci] (reference vae/models.py:261-264)
@@ -1086,16 +1047,17 @@ int mi_deconv2d_tail_fused(void* stream, int dtype, const void* x, int B, int IH
     else MI_LAUNCH(dectail_kernel<false>, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, q);
     int rc = mi_check_launch("dectail_kernel");
     if (rc != MI_OK) return rc;
-    if (reduce_now) rc = mi_deconv2d_tail_reduce(stream, scratch, nblocks, dw);
+    if (reduce_now) rc = mi_deconv2d_tail_reduce_ctx(stream, scratch, nblocks, dw, nullptr);
     if (rc == MI_OK) *n_partial = nblocks;
     return rc;
 }
 
 // dw[1536] += the per-block partial filter gradients mi_deconv2d_tail_fused(reduce_now = 0) left in scratch (n_partial of them): any stream position
 // behind that launch and in front of the optimiser step (the VAE engine runs it where its stream would otherwise wait for the other one)
-int mi_deconv2d_tail_reduce(void* stream, const void* scratch, int n_partial, float* dw) {
+int mi_deconv2d_tail_reduce(void* stream, const void* scratch, int n_partial, float* dw) { return mi_deconv2d_tail_reduce_ctx(stream, scratch, n_partial, dw, nullptr); }
+int mi_deconv2d_tail_reduce_ctx(void* stream, const void* scratch, int n_partial, float* dw, const MiWgradCtx* ctx) {
     if (!scratch || !dw || n_partial < 1) return mi_fail(MI_ERR_ARG, "mi_deconv2d_tail_reduce: missing buffers");
-    if (t_sr_defer) return mi_reduce_slabs((hipStream_t)stream, (const float*)scratch, (long long)DT_SLAB, n_partial, (long long)DT_SLAB, dw);      // one of the jobs of the pass's fused small reduce
+    if (small_of(ctx)) return mi_reduce_slabs((hipStream_t)stream, (const float*)scratch, (long long)DT_SLAB, n_partial, (long long)DT_SLAB, dw, 0, ctx->small);      // one of the jobs of the pass's fused small reduce (a list of another stream: that kernel as well, at once)
     MI_LAUNCH(dectail_reduce_kernel, dim3(DT_SLAB / 32), dim3(1024), 0, (hipStream_t)stream, (const float*)scratch, n_partial, dw);
     return mi_check_launch("dectail_reduce_kernel");
 }
@@ -1127,25 +1089,29 @@ int mi_deconv2d_nhwc_dgrad_bits(void* stream, int dtype, const void* dy, int B, 
 // conv2d_transpose filter gradient: dw[kh,kw,co,ci] += im2col(dy)^T * x
 int mi_deconv2d_nhwc_wgrad(void* stream, int dtype, const void* dy, int B, int OH, int OW, int Cout,
                            const void* x, int KH, int KW, int Cin, float* dw) {
-    return mi_deconv2d_nhwc_wgrad_ws(stream, dtype, dy, B, OH, OW, Cout, x, KH, KW, Cin, dw, nullptr, 0, nullptr);
+    return mi_deconv2d_nhwc_wgrad_ctx(stream, dtype, dy, B, OH, OW, Cout, x, KH, KW, Cin, dw, nullptr, 0, nullptr, nullptr);
 }
 
 int mi_deconv2d_nhwc_wgrad_ws(void* stream, int dtype, const void* dy, int B, int OH, int OW, int Cout,
                               const void* x, int KH, int KW, int Cin, float* dw, void* scratch, long long scratch_bytes, float* dbias) {
+    return mi_deconv2d_nhwc_wgrad_ctx(stream, dtype, dy, B, OH, OW, Cout, x, KH, KW, Cin, dw, scratch, scratch_bytes, dbias, nullptr);
+}
+int mi_deconv2d_nhwc_wgrad_ctx(void* stream, int dtype, const void* dy, int B, int OH, int OW, int Cout, const void* x, int KH, int KW, int Cin,
+                               float* dw, void* scratch, long long scratch_bytes, float* dbias, const MiWgradCtx* ctx) {
     const int IH = (OH - KH) / 2 + 1, IW = (OW - KW) / 2 + 1;
     {   // deconv with a narrow OUTPUT: dW[kh,kw,co,ci] = sum patches(dy)[.,(kh,kw,co)] x[.,ci]; its bias gradient is not a by-product here
-        const int r4 = dbias ? 0 : try_narrow_wgrad((hipStream_t)stream, dtype, dy, 0, nullptr, x, B, OH, OW, Cout, IH, IW, Cin, KH, KW, dw, nullptr, scratch, scratch_bytes);
+        const int r4 = dbias ? 0 : try_narrow_wgrad((hipStream_t)stream, dtype, dy, 0, nullptr, x, B, OH, OW, Cout, IH, IW, Cin, KH, KW, dw, nullptr, scratch, scratch_bytes, ctx);
         if (r4 != 0) return r4 > 0 ? MI_OK : r4;
     }
     {
-        const int r3 = dtype == MI_BF16X3 ? try_tapwgrad_split((hipStream_t)stream, TC_GATHER, x, dy, B, IH, IW, Cin, OH, OW, Cout, KH, KW, dw, scratch, scratch_bytes, dbias)
-                                          : try_tapwgrad((hipStream_t)stream, dtype, TC_GATHER, x, dy, B, IH, IW, Cin, OH, OW, Cout, KH, KW, dw, scratch, scratch_bytes, dbias);
+        const int r3 = dtype == MI_BF16X3 ? try_tapwgrad_split((hipStream_t)stream, TC_GATHER, x, dy, B, IH, IW, Cin, OH, OW, Cout, KH, KW, dw, scratch, scratch_bytes, dbias, ctx)
+                                          : try_tapwgrad((hipStream_t)stream, dtype, TC_GATHER, x, dy, B, IH, IW, Cin, OH, OW, Cout, KH, KW, dw, scratch, scratch_bytes, dbias, ctx);
         if (r3 != 0) return r3 > 0 ? MI_OK : r3;
     }
     if (dbias) {
         long long cb = (mi_colsum_scratch_bytes(dtype, (long long)B * OH * OW, Cout) + 255) / 256 * 256;
         if (!scratch || cb > scratch_bytes) cb = 0;
-        const int rcb = mi_colsum_ws(stream, dtype, dy, (long long)B * OH * OW, Cout, dbias, cb ? scratch : nullptr, cb);
+        const int rcb = mi_colsum_ctx(stream, dtype, dy, (long long)B * OH * OW, Cout, dbias, cb ? scratch : nullptr, cb, ctx);
         if (rcb != MI_OK) return rcb;
         if (cb) { scratch = (char*)scratch + cb; scratch_bytes -= cb; }
     }
@@ -1153,7 +1119,7 @@ int mi_deconv2d_nhwc_wgrad_ws(void* stream, int dtype, const void* dy, int B, in
     p.big = dy; p.frame_idx = nullptr;
     fill_wgrad_geom(p, B, OH, OW, Cout, IH, IW, KH, KW, 2, needs_merge(Cout, dtype, 0));
     p.N = Cin; p.small = x; p.s_vec = vec_ok(x, Cin, dtype); p.out = dw;
-    return launch_wgrad((hipStream_t)stream, dtype, 0, p, 1024, scratch, scratch_bytes);
+    return launch_wgrad((hipStream_t)stream, dtype, 0, p, 1024, scratch, scratch_bytes, 0, ctx);
 }
 
 // Dense: out[M,N] = act(a[M,K] * W + bias).  w_layout 0: W[K,N] (tf dense kernel), 1: W[N,K] (used for x * W^T).
@@ -1235,12 +1201,15 @@ int mi_gemm_wgrad_ws(void* stream, int dtype, const void* a, const void* dy, int
 // same; dbias != NULL: dbias[n] += sum_m dy[m, n] as well -- the layer's BiasAddGrad as one more row of the same product (a column of ones appended to `a` inside
 // the kernel's loader): no separate column-sum launch
 int mi_gemm_wgrad_bias_ws(void* stream, int dtype, const void* a, const void* dy, int M, int K, int N, float* dw, float* dbias, void* scratch, long long scratch_bytes) {
-    return mi_gemm_wgrad_bias_set(stream, dtype, a, dy, M, K, N, dw, dbias, scratch, scratch_bytes, 0);
+    return mi_gemm_wgrad_bias_ctx(stream, dtype, a, dy, M, K, N, dw, dbias, scratch, scratch_bytes, 0, nullptr);
 }
 
 // same; overwrite != 0: dw (and dbias) = the gradient instead of += : plain stores (one row split) or the storing form of the ordered slab sum -- the gradient buffer
 // need not be zeroed between steps and no element is touched by an atomic (the MlpVAE engine: 39.5 M weights, the zeroing alone was 158 MB per step)
 int mi_gemm_wgrad_bias_set(void* stream, int dtype, const void* a, const void* dy, int M, int K, int N, float* dw, float* dbias, void* scratch, long long scratch_bytes, int overwrite) {
+    return mi_gemm_wgrad_bias_ctx(stream, dtype, a, dy, M, K, N, dw, dbias, scratch, scratch_bytes, overwrite, nullptr);
+}
+int mi_gemm_wgrad_bias_ctx(void* stream, int dtype, const void* a, const void* dy, int M, int K, int N, float* dw, float* dbias, void* scratch, long long scratch_bytes, int overwrite, const MiWgradCtx* ctx) {
     // large result, short reduction, storing form: whole 128 x 128 tiles of dW per block over all rows (dwg_tile.hpp)
     if (overwrite && knob(K_DWG) && dtype == MI_BF16 && M >= 1 && K % 128 == 0 && N % 128 == 0 && (long long)(K / 128) * (N / 128) >= 256 &&
         ((((uintptr_t)a) | ((uintptr_t)dy) | ((uintptr_t)dw)) & 15) == 0 && fits_desc((long long)M * K * 2) && fits_desc((long long)M * N * 2)) {
@@ -1266,7 +1235,7 @@ int mi_gemm_wgrad_bias_set(void* stream, int dtype, const void* a, const void* d
     const int vb = dtype == MI_BF16 ? 8 : 4;
     if (K % vb != 0) return mi_fail(MI_ERR_SHAPE, "mi_gemm_wgrad: K must be a multiple of the 16-byte vector (pad K)");
     p.N = N; p.small = dy; p.s_vec = vec_ok(dy, N, dtype); p.out = dw;
-    return launch_wgrad((hipStream_t)stream, dtype, 0, p, knob(K_DENSE_WGRAD_BLOCKS), scratch, scratch_bytes, overwrite);
+    return launch_wgrad((hipStream_t)stream, dtype, 0, p, knob(K_DENSE_WGRAD_BLOCKS), scratch, scratch_bytes, overwrite, ctx);
 }
 
 // TWO dense filter gradients (+ bias rows) as ONE launch: what mi_gemm_wgrad_bias_ws(problem 0) followed by mi_gemm_wgrad_bias_ws(problem 1) computes, bit for bit, when both take the
@@ -1274,6 +1243,10 @@ int mi_gemm_wgrad_bias_set(void* stream, int dtype, const void* a, const void* d
 // shapes: the two single calls.  Round 6: the two ~190-block grids sat back to back at the very end of the backward pass.
 int mi_gemm_wgrad_bias_pair_ws(void* stream, int dtype, const void* a0, const void* dy0, int M0, int K0, int N0, float* dw0, float* db0, void* scratch0, long long scratch_bytes0,
                                const void* a1, const void* dy1, int M1, int K1, int N1, float* dw1, float* db1, void* scratch1, long long scratch_bytes1) {
+    return mi_gemm_wgrad_bias_pair_ctx(stream, dtype, a0, dy0, M0, K0, N0, dw0, db0, scratch0, scratch_bytes0, a1, dy1, M1, K1, N1, dw1, db1, scratch1, scratch_bytes1, nullptr);
+}
+int mi_gemm_wgrad_bias_pair_ctx(void* stream, int dtype, const void* a0, const void* dy0, int M0, int K0, int N0, float* dw0, float* db0, void* scratch0, long long scratch_bytes0,
+                                const void* a1, const void* dy1, int M1, int K1, int N1, float* dw1, float* db1, void* scratch1, long long scratch_bytes1, const MiWgradCtx* ctx) {
     const void* A[2] = {a0, a1}; const void* DY[2] = {dy0, dy1}; const int M[2] = {M0, M1}, K[2] = {K0, K1}, N[2] = {N0, N1};
     float* DW[2] = {dw0, dw1}; float* DB[2] = {db0, db1}; void* WS[2] = {scratch0, scratch1}; const long long NB[2] = {scratch_bytes0, scratch_bytes1};
     bool ok = dtype == MI_BF16;
@@ -1290,8 +1263,8 @@ int mi_gemm_wgrad_bias_pair_ws(void* stream, int dtype, const void* a0, const vo
         if (prepare_wgrad(dtype, p, knob(K_DENSE_WGRAD_BLOCKS), WS[i], NB[i], 0, &g[i], &wide) != MI_OK || !wide || p.C % 8 != 0) ok = false;
     }
     if (!ok) {
-        const int rc = mi_gemm_wgrad_bias_ws(stream, dtype, a0, dy0, M0, K0, N0, dw0, db0, scratch0, scratch_bytes0);
-        return rc != MI_OK ? rc : mi_gemm_wgrad_bias_ws(stream, dtype, a1, dy1, M1, K1, N1, dw1, db1, scratch1, scratch_bytes1);
+        const int rc = mi_gemm_wgrad_bias_ctx(stream, dtype, a0, dy0, M0, K0, N0, dw0, db0, scratch0, scratch_bytes0, 0, ctx);
+        return rc != MI_OK ? rc : mi_gemm_wgrad_bias_ctx(stream, dtype, a1, dy1, M1, K1, N1, dw1, db1, scratch1, scratch_bytes1, 0, ctx);
     }
     q.n0 = (int)(g[0].x * g[0].y * g[0].z);
     for (int i = 0; i < 2; ++i) { q.gx[i] = (int)g[i].x; q.gy[i] = (int)g[i].y; }
@@ -1301,8 +1274,8 @@ int mi_gemm_wgrad_bias_pair_ws(void* stream, int dtype, const void* a0, const vo
     for (int i = 0; i < 2 && rc == MI_OK; ++i) {
         const WgradParams& p = q.p[i];
         if (!p.slabs) continue;
-        rc = mi_reduce_slabs((hipStream_t)stream, p.slabs, p.slab_stride, (int)g[i].z, (long long)p.Kc * p.N, p.out, 0);
-        if (rc == MI_OK && p.ones_row) rc = mi_reduce_slabs((hipStream_t)stream, p.slabs + (long long)p.Kc * p.N, p.slab_stride, (int)g[i].z, (long long)p.N, p.dbias, 0);
+        rc = mi_reduce_slabs((hipStream_t)stream, p.slabs, p.slab_stride, (int)g[i].z, (long long)p.Kc * p.N, p.out, 0, small_of(ctx));
+        if (rc == MI_OK && p.ones_row) rc = mi_reduce_slabs((hipStream_t)stream, p.slabs + (long long)p.Kc * p.N, p.slab_stride, (int)g[i].z, (long long)p.N, p.dbias, 0, small_of(ctx));
     }
     return rc;
 }

@@ -1176,6 +1176,9 @@ long long mi_colsum_scratch_bytes(int dtype, long long M, int N) {
 // out[n] += sum_m x[m, n].  With scratch (>= mi_colsum_scratch_bytes) every row block stores its column sums and one ordered pass adds them to out:
 // two runs are bitwise equal (round 4).  Without it the row blocks meet in fp32 atomics on out.
 int mi_colsum_ws(void* stream, int dtype, const void* x, long long M, int N, float* out, void* scratch, long long scratch_bytes) {
+    return mi_colsum_ctx(stream, dtype, x, M, N, out, scratch, scratch_bytes, nullptr);
+}
+int mi_colsum_ctx(void* stream, int dtype, const void* x, long long M, int N, float* out, void* scratch, long long scratch_bytes, const MiWgradCtx* ctx) {      // (the pass's small list takes the ordered pass)
     if (M <= 0 || N <= 0) return MI_OK;
     const int pstride = (N + 3) / 4 * 4;
     int kind; long long rows;
@@ -1190,7 +1193,7 @@ int mi_colsum_ws(void* stream, int dtype, const void* x, long long M, int N, flo
         BY_DTYPE(dtype, hipLaunchKernelGGL(colsum_wide_kernel<TT>, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, (const TT*)x, M, N, (int)rows, out, part, pstride));
     }
     int rc = mi_check_launch("colsum");
-    if (rc == MI_OK && part) rc = mi_reduce_slabs((hipStream_t)stream, part, pstride, gx, N, out);
+    if (rc == MI_OK && part) rc = mi_reduce_slabs((hipStream_t)stream, part, pstride, gx, N, out, 0, ctx ? ctx->small : nullptr);
     return rc;
 }
 

@@ -55,6 +55,10 @@ extern "C" int mi_conv2d_head_bwd_blocks(void) { const int a = enchead_grid(0), 
 // not the ones the kernel takes (nothing was launched: use mi_conv2d_nhwc_dgrad_bits + mi_conv2d_nhwc_wgrad_ws).  scratch >= mi_conv2d_head_bwd_blocks() * 8320 bytes.
 extern "C" int mi_conv2d_head_bwd_fused(void* stream, int dtype, const void* frames, int frames_fmt, const int* frame_idx, int B, int FH, int FW,
                                         const void* dy2, const void* w2, const void* bits_act1, float* dw1, float* db1, void* scratch, long long scratch_bytes, int* n_blocks) {
+    return mi_conv2d_head_bwd_fused_ctx(stream, dtype, frames, frames_fmt, frame_idx, B, FH, FW, dy2, w2, bits_act1, dw1, db1, scratch, scratch_bytes, n_blocks, nullptr);
+}
+extern "C" int mi_conv2d_head_bwd_fused_ctx(void* stream, int dtype, const void* frames, int frames_fmt, const int* frame_idx, int B, int FH, int FW, const void* dy2, const void* w2,
+                                            const void* bits_act1, float* dw1, float* db1, void* scratch, long long scratch_bytes, int* n_blocks, const MiWgradCtx* ctx) {
     if (!n_blocks || !frames || !dy2 || !w2 || !dw1 || !db1) return mi_fail(MI_ERR_ARG, "mi_conv2d_head_bwd_fused: missing buffers");
     *n_blocks = 0;
     if (!knob(K_ENCHEAD) || !knob(K_NARROW) || dtype != MI_BF16 || !bits_act1 || !scratch || B < 1) return MI_OK;
@@ -88,9 +92,9 @@ extern "C" int mi_conv2d_head_bwd_fused(void* stream, int dtype, const void* fra
     else MI_LAUNCH(enchead_bwd_kernel<float>, dim3(nblocks), dim3(256), 0, st, q);
     int rc = mi_check_launch("enchead_bwd_kernel");
     if (rc != MI_OK) return rc;
-    if (mi_small_reduce_deferring()) {                       // two jobs of the pass's fused small reduce: the 48 x 32 filter-gradient sums and the 32 bias sums at slab offset 2048
-        rc = mi_reduce_slabs(st, q.slabs, (long long)EH_SLAB, nblocks, 48ll * 32, dw1);
-        if (rc == MI_OK) rc = mi_reduce_slabs(st, q.slabs + 64 * 32, (long long)EH_SLAB, nblocks, 32ll, db1);
+    if (ctx && ctx->small) {                                 // two jobs of the pass's fused small reduce: the 48 x 32 filter-gradient sums and the 32 bias sums at slab offset 2048 (a list of another stream: that kernel as well, at once)
+        rc = mi_reduce_slabs(st, q.slabs, (long long)EH_SLAB, nblocks, 48ll * 32, dw1, 0, ctx->small);
+        if (rc == MI_OK) rc = mi_reduce_slabs(st, q.slabs + 64 * 32, (long long)EH_SLAB, nblocks, 32ll, db1, 0, ctx->small);
     } else {
         MI_LAUNCH(enchead_reduce_kernel, dim3(49), dim3(1024), 0, st, (const float*)q.slabs, nblocks, dw1, db1);
         rc = mi_check_launch("enchead_reduce_kernel");

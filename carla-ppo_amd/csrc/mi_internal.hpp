@@ -22,12 +22,55 @@ bool mi_enc12_eligible(int dtype, int B, int FH, int FW);   // enc12.hip: mi_con
 int mi_fail(int code, const char* msg);          // records msg (thread-local) and returns code
 int mi_check_launch(const char* what);           // hipGetLastError() -> MI_OK / MI_ERR_LAUNCH
 
-// deferred split reductions of the raw-staged filter-gradient kernel (conv_ops.hip; used by the VAE engine)
-extern "C" int mi_tapwgrad_defer(int on);        // returns the previous mode
-extern "C" int mi_tapwgrad_flush(void* stream);  // launches the recorded reduces on `stream`
-extern "C" int mi_tapwgrad_defer_pause(int pause);   // != 0: reduce right behind the launch although the pass defers (a layer issued on another stream); returns the previous setting
-extern "C" int mi_tapwgrad_bias_rows(int on);    // != 0: a filter gradient with ONE position split sums its bias partial rows through the scratch in a fixed order instead of atomics (public: mi355_carla.h); returns the previous setting
-extern "C" int mi_tapwgrad_slab_bf16(int on);    // partial-sum slabs rounded to bf16 (the engine's bf16 backward); returns the previous setting
+// ---- Slab sums that a backward pass issues LATER than the kernel that wrote the slabs (conv_ops.hip).  The pass owns the two lists below for its own length (on its
+// stack) and hands them down the filter-gradient calls in a MiWgradCtx; nothing of this is per-thread or per-process state.  Each list is created with the ONE stream it
+// will be flushed on; a list that goes out of scope with jobs in it launches nothing.
+//
+// The small ordered slab sums (reduce_small_fused_kernel): out[0 .. n) += (overwrite: =) sum_k slabs[k * stride + i] in a fixed order.
+//   * add (mi_reduce_slabs with the list): a job of the list's stream is recorded -- its slabs must stay untouched until the flush; a job of ANY OTHER stream is launched
+//     at once on its own stream (one launch of the same kernel), never flushed later on a stream that did not wait for its slabs.
+//   * a full list (MI_SMALL_SUMS_MAX jobs) is issued as it is and recording goes on.
+//   * mi_small_sums_flush: ONE launch on the list's stream; the list is empty afterwards and may go on recording.
+struct MiSlabSum { const float* slabs; float* out; long long stride, n; int nslab, overwrite; };
+constexpr int MI_SMALL_SUMS_MAX = 12;            // the jobs of one launch (= SR_MAX of tapwgrad_tile.hpp)
+struct MiSmallSums {
+    hipStream_t stream; int njobs; MiSlabSum job[MI_SMALL_SUMS_MAX];
+    explicit MiSmallSums(void* st) : stream((hipStream_t)st), njobs(0) {}
+};
+int mi_small_sums_flush(MiSmallSums* l);
+// The tiled reduces of the raw-staged filter-gradient kernel (try_tapwgrad) and the folds of its split-storage form (try_tapwgrad_split).
+//   * a reduce (a fold) of a call on the list's stream is recorded, up to 16 of each -- every layer then needs its OWN scratch region until the flush; past 16, or from
+//     any other stream, it is launched right behind its kernel.
+//   * mi_tiled_reduces_flush: the recorded reduces (one launch each for 1 or more than TW_MAX_FUSED of them, else one reduce_fused_kernel), then -- only where folds are
+//     recorded -- the jobs of `small` if that list is on the same stream (the folds read its sums), then the folds.  Recording may go on afterwards.
+struct MiTiledReduces {
+    hipStream_t stream; int nreduce, nfold;
+    alignas(16) unsigned char store[11 << 10];   // 16 reduces, 16 folds, the fused launch's argument block: types of the kernel headers, which this header does not pull in (conv_ops.hip)
+    explicit MiTiledReduces(void* st) : stream((hipStream_t)st), nreduce(0), nfold(0) {}
+};
+int mi_tiled_reduces_flush(MiTiledReduces* l, MiSmallSums* small);
+// What a filter-gradient call takes from the pass that issues it.  NULL, or NULL lists: what a layer-op call from outside gets -- every reduce right behind its kernel.
+// (mi_tl_stop_event above and mi_rwconv_next_weights_fragment_ordered are hidden arguments of the same kind; they reach every launcher and were left as they are on purpose.)
+struct MiWgradCtx {
+    MiTiledReduces* tiled;                       // or NULL
+    MiSmallSums* small;                          // or NULL.  The encoder-head and decoder-tail sums take reduce_small_fused_kernel whenever a list is given, also one of another stream
+    int slab_bf16;                               // != 0: the raw-staged kernels round their partial-sum slabs to bf16 (the engine's bf16 backward); 0: K_SLAB_BF16_DEFAULT
+    int bias_rows;                               // != 0: a raw-staged filter gradient with ONE position split sums its bias partial rows through the scratch in a fixed order
+};                                               //       instead of atomics.  A NULL context follows mi_tapwgrad_bias_rows, this thread's public switch (mi355_carla.h)
+// the entries of mi355_carla.h that issue slab sums, with the context (the public ones pass NULL; C linkage as theirs, defined next to them)
+extern "C" {
+int mi_conv2d_nhwc_wgrad_ctx(void* stream, int dtype, const void* x, const int* frame_idx, int x_is_f32, int B, int IH, int IW, int Cin, const void* dy, int KH, int KW, int Cout,
+                             float* dw, void* scratch, long long scratch_bytes, float* dbias, const MiWgradCtx* ctx);
+int mi_deconv2d_nhwc_wgrad_ctx(void* stream, int dtype, const void* dy, int B, int OH, int OW, int Cout, const void* x, int KH, int KW, int Cin,
+                               float* dw, void* scratch, long long scratch_bytes, float* dbias, const MiWgradCtx* ctx);
+int mi_gemm_wgrad_bias_ctx(void* stream, int dtype, const void* a, const void* dy, int M, int K, int N, float* dw, float* dbias, void* scratch, long long scratch_bytes, int overwrite, const MiWgradCtx* ctx);      // mi_gemm_wgrad_bias_set (and through it _ws, _bias_ws)
+int mi_gemm_wgrad_bias_pair_ctx(void* stream, int dtype, const void* a0, const void* dy0, int M0, int K0, int N0, float* dw0, float* db0, void* scratch0, long long scratch_bytes0,
+                                const void* a1, const void* dy1, int M1, int K1, int N1, float* dw1, float* db1, void* scratch1, long long scratch_bytes1, const MiWgradCtx* ctx);
+int mi_colsum_ctx(void* stream, int dtype, const void* x, long long M, int N, float* out, void* scratch, long long scratch_bytes, const MiWgradCtx* ctx);      // elementwise.hip
+int mi_deconv2d_tail_reduce_ctx(void* stream, const void* scratch, int n_partial, float* dw, const MiWgradCtx* ctx);
+int mi_conv2d_head_bwd_fused_ctx(void* stream, int dtype, const void* frames, int frames_fmt, const int* frame_idx, int B, int FH, int FW, const void* dy2, const void* w2,
+                                 const void* bits_act1, float* dw1, float* db1, void* scratch, long long scratch_bytes, int* n_blocks, const MiWgradCtx* ctx);      // enchead.hip
+}
 
 // register-weight kernel of the thin gather-form layers (rwconv.hip): 1 launched, 0 not eligible, < 0 error
 // wfrag: the layer's weights in fragment order (mi_rwconv_take_wfrag), or NULL
@@ -38,13 +81,8 @@ int mi_try_rwconv_conv(hipStream_t st, int dtype, const void* a, const void* w, 
 void mi_get_trace(long long** buf, int* cap);     // the debug stamp buffer of mi_debug_set_trace
 
 // out[0 .. n) += sum over nslab slabs of slabs[k * stride + i] (reduce_small_fused_kernel, tapwgrad_tile.hpp; fixed summation order, no atomics) -- conv_ops.hip
-int mi_reduce_slabs(hipStream_t st, const float* slabs, long long stride, int nslab, long long n, float* out, int overwrite = 0);   // overwrite: out = sum
-// deferred mode of mi_reduce_slabs (per host thread): jobs are recorded and mi_small_reduce_flush(stream) issues all of them as ONE launch -- conv_ops.hip
-extern "C" int mi_small_reduce_defer(int on);
-extern "C" int mi_small_reduce_flush(void* stream);
-extern "C" int mi_small_reduce_bind(void* stream);      // the list of the deferring pass belongs to `stream`; mi_reduce_slabs calls from other streams launch immediately (round 5)
-extern "C" int mi_small_reduce_deferring(void);
-extern "C" int mi_small_reduce_flush_bound(void* stream);      // issues the recorded jobs if the list belongs to `stream`; otherwise nothing (mi_tapwgrad_flush, in front of its folds)
+// overwrite: out = sum.  list: NULL = one launch right here; else MiSmallSums' add rule above
+int mi_reduce_slabs(hipStream_t st, const float* slabs, long long stride, int nslab, long long n, float* out, int overwrite = 0, MiSmallSums* list = nullptr);
 
 // global-norm gradient clipping in front of TF ApplyAdam (elementwise.hip; the PPO engine).  mi_grad_sumsq: sum of (double)g * (double)g over `count` tensors of a
 // flat fp32 buffer (offsets in floats, multiples of 4; what lies between the tensors is not read) as MI_GRAD_NORM_BLOCKS ordered block partials.  mi_grad_norm_finish:

@@ -360,8 +360,7 @@ int mi_mlpvae_backward(void* h, void* stream, const float* eps, float inv_batch,
     const MiMlpVaeDesc& d = e->d;
     const int B = e->last_B, Z = d.z_dim, dt = d.dtype;
     // the ordered slab sums of the layers whose filter gradient is split over rows (the small ones) are recorded and issued as ONE launch at the end of the part
-    // (eight 4.5 us launches per step otherwise); every layer owns a piece of the scratch until then
-    struct SrGuard { int prev; SrGuard() : prev(mi_small_reduce_defer(1)) {} ~SrGuard() { mi_small_reduce_defer(prev); } } sr_guard;
+    // (eight 4.5 us launches per step otherwise); every layer owns a piece of the scratch until then.  One list per stream the pass issues on (mi_internal.hpp).
     // A full pass (part 0) runs on two streams: the input-gradient chain is a row of dependent kernels, eight of them a few microseconds of work on an empty GPU, and no
     // filter gradient is on it.  The output layer's filter gradient (needs only the loss gradient) runs UNDER the chain on the second stream; behind the chain the small
     // layers' filter gradients run there next to the first layer's on the caller's stream.  Two events on the caller's stream, one join.  MI355_MLP_STREAMS=0: one stream.
@@ -373,13 +372,15 @@ int mi_mlpvae_backward(void* h, void* stream, const float* eps, float inv_batch,
     }
     const bool fork = part == 0 && streams_on && e->side_ok == 1;
     hipStream_t sm = (hipStream_t)stream;
+    MiSmallSums sums_main(stream), sums_side(fork ? (void*)e->side : nullptr);
     long long scr_used = 0;
     auto wgrad_on = [&](void* s_, const Dense& l, const void* a, const void* gy) {
         const long long need = al256(mi_gemm_wgrad_scratch_bytes(dt, 1 << 20, l.K, l.N));
         if (scr_used + need > e->scratch_bytes) return mi_fail(MI_ERR_STATE, "mi_mlpvae_backward: scratch exhausted");
         void* scr = e->at(e->o_scratch + scr_used);
         scr_used += need;
-        return mi_gemm_wgrad_bias_set(s_, dt, a, gy, B, l.K, l.N, e->grads + l.wo, e->grads + l.bo, scr, need, 1);
+        const MiWgradCtx cx = {nullptr, s_ == stream ? &sums_main : &sums_side, 0, 0};
+        return mi_gemm_wgrad_bias_ctx(s_, dt, a, gy, B, l.K, l.N, e->grads + l.wo, e->grads + l.bo, scr, need, 1, &cx);
     };
     struct Later { const Dense* l; const void* a; const void* gy; } later[2 * ML_MAX + 2];
     int nlater = 0;
@@ -431,13 +432,13 @@ int mi_mlpvae_backward(void* h, void* stream, const float* eps, float inv_batch,
         // slab sums as one launch there; the first encoder layer's on the caller's stream next to them (its own slab sum, if it has one, by the flush below)
         if (hipEventRecord(e->ev_chain, sm) != hipSuccess || hipStreamWaitEvent(e->side, e->ev_chain, 0) != hipSuccess) return mi_fail(MI_ERR_LAUNCH, "mi_mlpvae_backward: stream hand-over failed");
         for (int j = 0; j + 1 < nlater; ++j) CK(wgrad_on((void*)e->side, *later[j].l, later[j].a, later[j].gy));
-        CK(mi_small_reduce_flush((void*)e->side));
+        CK(mi_small_sums_flush(&sums_side));
         if (nlater > 0) CK(wgrad_on(stream, *later[nlater - 1].l, later[nlater - 1].a, later[nlater - 1].gy));
-        const int rc = mi_small_reduce_flush(stream);
+        const int rc = mi_small_sums_flush(&sums_main);
         const int rcj = join_guard.join();
         return rc != MI_OK ? rc : rcj;
     }
-    return mi_small_reduce_flush(stream);
+    return mi_small_sums_flush(&sums_main);
 }
 
 long long mi_mlpvae_decoder_offset(void* h) {

@@ -49,7 +49,7 @@ constexpr Row rows[K_COUNT] = {
     {K_RWCONV_BLOCKS, "MI355_RWCONV_BLOCKS", 16, 0, P_INT, S_CLAMP, 0, MAXI},      // register-weight kernels: persistent blocks per XCD, 0 = as many as stay resident (one, k = 4 gather: three, per CU)
     {K_GEMM2_TILE, "MI355_GEMM2_TILE", 17, 2, P_INT, S_RAW},                       // wide-output gemm2 layers: 0 auto (64 x 64 tiles on small grids), 1 always 64 x 64, 2 never, 3 always 128 x 128 (64 x 64 wave tiles: 1 KB of LDS reads per MFMA instead of 1.5)
     {K_SLAB_BF16_DEFAULT, nullptr, 18, 0, P_NONE, S_BOOL},                         // tapwgrad partial-sum slabs rounded to bf16 (half the slab traffic): the PROCESS DEFAULT of the layer-op entry points (off: exact fp32 partial sums),
-                                                                                   // under the thread's override mi_tapwgrad_slab_bf16 -- not MI355_SLAB_BF16 (K_SLAB_BF16 below), the engine's switch that sets that override
+                                                                                   // which a pass may override for its own calls (MiWgradCtx::slab_bf16) -- not MI355_SLAB_BF16 (K_SLAB_BF16 below), the engine's switch that sets that override
     {K_NW_DEPTH, "MI355_NW_DEPTH", 19, 3, P_INT, S_RAW},                           // narrow_wgrad (uint8 conv1 shape): steps in flight per wave (3 | 5 | 6)
     {K_GEMM2_STAGES, "MI355_GEMM2_STAGES", 20, 2, P_INT, S_RAW},                   // gemm2 128 x 64 tiles: LDS stages of the K pipeline (2 | 3 | 4)
     {K_X3_TAPWGRAD, "MI355_X3_TAPWGRAD", 21, 1, P_INT, S_RAW},                     // split-storage filter gradients on the doubled-channel bf16 kernel: 0 off, 1 conv2 / conv3 (default since round 5: 2.637 -> 2.595 ms per bf16x3 step, two interleaved pairs on one box;

@@ -628,8 +628,10 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
     auto arm = [&]() { produced = false; if (fork) mi_tl_stop_event = e->ev_ready; };
     auto armed_ok = [&]() { if (fork) { produced = mi_tl_stop_event == nullptr; mi_tl_stop_event = nullptr; } };
     // In two-stream mode the split reductions of the filter gradients are deferred to the end of the side stream's work (they are tiny, but
-    // next to a big input-gradient kernel each takes 15-30 us instead of ~7): every layer writes its slabs into its own scratch region.
+    // next to a big input-gradient kernel each takes 15-30 us instead of ~7): every layer writes its slabs into its own scratch region.  The list lives on the
+    // filter-gradient stream: a filter gradient issued on the caller's stream next to it reduces right behind its own kernel.
     const bool defer = fork && W.scratch_bytes > 0;
+    MiTiledReduces tiled(sw);
     const long long region = W.scratch_bytes / SCRATCH_REGIONS;
     int next_region = 0;
     auto scratch_of = [&]() -> void* {
@@ -641,26 +643,28 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
     // latent-layer filter / bias gradients (dense1, heads): slabs of their row splits in the region that belongs to the stream they are issued on
     // (reused in stream order: each call's ordered reduce is issued right behind its kernel)
     // End of a full two-stream pass (round 4): the slab sums of the encoder head, the decoder tail and the latent layers' filter / bias gradients -- seven to eleven
-    // latency-bound launches in a row on the caller's stream -- are recorded and issued as ONE launch (mi_small_reduce_flush); every job then keeps its own piece of the
-    // tail scratch until that launch.
-    bool tail_defer = false;
+    // latency-bound launches in a row on the caller's stream -- are recorded and issued as ONE launch (tail_sums, switched on behind conv2's filter gradient); every job then
+    // keeps its own piece of the tail scratch until that launch.
+    MiSmallSums tail_sums(st);
     long long tail_bump = 0;
     // A backward PART on two streams (the data-parallel step; round 6): the small slab sums of the part's filter-gradient stream -- the latent layer's filter + bias gradient, the bias
     // rows of a lone raw-staged filter gradient -- are recorded the same way and issued as ONE launch in front of the part's join (they were two or three ~5 us launches per part on the
-    // stream that ends the data-parallel step).  (tail_defer belongs to the full pass, part 0: the two never meet.)
-    bool side_defer = false;
-    if (fork && part != 0 && W.scratch_tail_bytes > 0 && e->tm.mode != 1) { mi_small_reduce_defer(1); mi_small_reduce_bind(sw); side_defer = true; }
-    struct SrGuard { bool* on; bool* on2; ~SrGuard() { if (*on || *on2) mi_small_reduce_defer(0); } } sr_guard{&tail_defer, &side_defer};
+    // stream that ends the data-parallel step).  (tail_sums belongs to the full pass, part 0: the two never meet, and cx.small is the one that is live, if any.)
+    MiSmallSums side_sums(sw);
+    // What every filter-gradient call of this pass is handed (mi_internal.hpp): the lists, bf16 slabs (below), and ordered bias rows -- a small layer at a small batch has
+    // ONE position split: no slabs, and the 8 partial sums of each bias element met in fp32 atomics (conv_ops.hip).  Calls on either stream take the same context: a list
+    // records only what is issued on its own stream.
+    MiWgradCtx cx = {defer ? &tiled : nullptr, (fork && part != 0 && W.scratch_tail_bytes > 0 && e->tm.mode != 1) ? &side_sums : nullptr, 0, 1};
     auto small_ws = [&](void* s_, long long need, long long* bytes) -> void* {
-        if ((tail_defer && s_ == st) || (side_defer && s_ == sw)) {
+        if (cx.small && s_ == (void*)cx.small->stream) {
             need = (need + 255) / 256 * 256;
             if (need <= W.scratch_tail_bytes) {
-                if (tail_bump + need > W.scratch_tail_bytes) { mi_small_reduce_flush(s_); tail_bump = 0; }      // (the jobs recorded so far read their slabs before anything below overwrites them: same stream)
+                if (tail_bump + need > W.scratch_tail_bytes) { mi_small_sums_flush(cx.small); tail_bump = 0; }      // (the jobs recorded so far read their slabs before anything below overwrites them: same stream)
                 void* ptr = (char*)e->at(W.scratch_tail) + tail_bump;
                 tail_bump += need; *bytes = need;
                 return ptr;
             }
-            mi_small_reduce_flush(s_);
+            mi_small_sums_flush(cx.small);
         }
         if (fork && s_ == (void*)e->side) { *bytes = W.scratch_side_bytes; return e->at(W.scratch_side); }
         *bytes = W.scratch_main_bytes; return e->at(W.scratch_main);
@@ -669,14 +673,13 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
     // loader) -- two launches less at the end of the pass
     auto dense_wgrad = [&](void* s_, const void* a, const void* dy, int M, int K, int N, float* dw, float* db) -> int {
         long long nb = 0; void* ws_ = small_ws(s_, mi_gemm_wgrad_scratch_bytes(d.dtype, M, K, N), &nb);
-        return mi_gemm_wgrad_bias_ws(s_, d.dtype, a, dy, M, K, N, dw, db, ws_, nb);
+        return mi_gemm_wgrad_bias_ctx(s_, d.dtype, a, dy, M, K, N, dw, db, ws_, nb, 0, &cx);
     };
-    if (defer) mi_tapwgrad_defer(1);
     auto join = [&]() {
-        // (with a split-storage fold pending mi_tapwgrad_flush issues the part's recorded small reduces itself, in front of the folds that read their sums: everything in that
+        // (with a split-storage fold pending mi_tiled_reduces_flush issues the part's recorded small sums itself, in front of the folds that read their sums: everything in that
         // list was recorded on sw and is complete there in stream order, so running it early is the same sums; the flush below then finds the list empty)
-        if (defer) mi_tapwgrad_flush(sw);
-        if (side_defer) { mi_small_reduce_flush(sw); mi_small_reduce_defer(0); side_defer = false; }
+        if (defer) mi_tiled_reduces_flush(&tiled, cx.small);
+        if (cx.small == &side_sums) { mi_small_sums_flush(&side_sums); cx.small = nullptr; }
         if (fork && e->dp_open_join) {                      // (one-call data-parallel step, parts 1 and 3) everything of this part that ran on the caller's stream is complete on the other one
             hipEventRecord(e->ev_done, (hipStream_t)st); hipStreamWaitEvent(e->side, e->ev_done, 0);
             e->dp_side_ready = 1;
@@ -684,7 +687,6 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
         }
         if (fork) { hipEventRecord(e->ev_done, e->side); hipStreamWaitEvent((hipStream_t)st, e->ev_done, 0); }
     };
-    struct DeferGuard { bool on; ~DeferGuard() { if (on) mi_tapwgrad_defer(0); } } guard{defer};
     // The position-split partial sums of the six raw-staged filter gradients are stored ROUNDED TO BF16 (round 3): 211 MB written + 214 MB read per step
     // become half of that.  ~250 slabs per element, each within 2^-9 of ITS OWN value (RMS 2^-9 / sqrt 3) with independent rounding errors: the error of the
     // total is that fraction of sqrt(sum s_i^2), i.e. ~1e-3 of the RMS element of dW when the partial sums have independent signs (the usual case for a
@@ -692,10 +694,7 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
     // and inside the 1.25 e_emul + 2e-3 gradient criterion of the bf16 engine with bench.py's parity.bf16.grad_worst = 0.79 (the operands were bf16 to begin
     // with: their own rounding contributes 3e-3 ... 6e-2 of the tensor max).  The layer-op entry points keep exact fp32 slabs.
     // Measured, three interleaved pairs on one box: 0.966 -> 0.943 ms per step.  MI355_SLAB_BF16=0: fp32 slabs.
-    struct SlabGuard { int prev; bool on; ~SlabGuard() { if (on) mi_tapwgrad_slab_bf16(prev); } } slab_guard{-1, false};
-    if (knob(K_SLAB_BF16) && d.dtype == MI_BF16) { slab_guard.prev = mi_tapwgrad_slab_bf16(1); slab_guard.on = true; }
-    // a small layer at a small batch has ONE position split: no slabs, and the 8 partial sums of each bias element met in fp32 atomics -- ordered rows for this pass (conv_ops.hip)
-    struct BiasRowsGuard { int prev; ~BiasRowsGuard() { mi_tapwgrad_bias_rows(prev); } } bias_rows_guard{mi_tapwgrad_bias_rows(1)};
+    cx.slab_bf16 = (knob(K_SLAB_BF16) && d.dtype == MI_BF16) ? 1 : 0;
     // Full two-stream backward (round 3): the latent-side filter / bias gradients (dense1, heads: ~60 us of the filter-gradient stream, which is the longer one) are
     // issued on the caller's stream at the very END of the pass, where that stream would otherwise wait ~100 us for the other one; their operands (gdec0, z, dheads,
     // act4) stay intact until then and no event is needed for them.  The parts and the one-stream pass issue them in place on the filter-gradient stream.
@@ -706,7 +705,7 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
             const void* gy = e->at(W.gdec[i + 1]);
             release();                                       // gy is complete on st (loss pass / previous input gradient)
             // BiasAddGrad is fused into the filter-gradient call
-            TOP(e, sw, OP_DECONV_WGRAD + i, mi_deconv2d_nhwc_wgrad_ws(sw, d.dtype, gy, B, g.dh[i + 1], g.dw[i + 1], g.dc[i + 1], e->at(W.dec[i]), DEC_K[i], DEC_K[i], g.dc[i], e->gptr(12 + 2 * i), scratch_of(), scratch_sz, (i == 3 && e->b4_fused) ? nullptr : e->gptr(13 + 2 * i)));
+            TOP(e, sw, OP_DECONV_WGRAD + i, mi_deconv2d_nhwc_wgrad_ctx(sw, d.dtype, gy, B, g.dh[i + 1], g.dw[i + 1], g.dc[i + 1], e->at(W.dec[i]), DEC_K[i], DEC_K[i], g.dc[i], e->gptr(12 + 2 * i), scratch_of(), scratch_sz, (i == 3 && e->b4_fused) ? nullptr : e->gptr(13 + 2 * i), &cx));
             if (i == 0 && e->ares_ok) {                      // deconv1's input gradient: conv form on the activation-resident kernel (no mask: dense1 has no ReLU)
                 int launched = 0;
                 TOP(e, st, OP_DECONV_DGRAD + i, mi_ares_conv(st, d.dtype, 0, gy, B, e->at(W.wfrag[3]), nullptr, 0, nullptr, e->at(W.gdec[0]), &launched));
@@ -724,9 +723,9 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
         // the filter-gradient stream idles ~20 us at this point (conv4's filter gradient waits for the latent chain dense1.dgrad -> reparam.bwd -> heads.dgrad on the
         // caller's stream, six small launches that leave the chip nearly empty), and the reduce at the end of the pass -- which ends the longer of the two queues --
         // shrinks from six layers to three.
-        if (defer && part == 0) CK(mi_tapwgrad_flush(sw));
+        if (defer && part == 0) CK(mi_tiled_reduces_flush(&tiled, cx.small));
         if (e->tail_nblk > 0 && !late_dense) {               // deconv4's filter gradient: the fused tail's per-block sums -> the gradient buffer
-            CK(mi_deconv2d_tail_reduce(st, e->at(W.tail_slabs), e->tail_nblk, e->gptr(18)));      // (full two-stream backward: at the tail of the caller's stream, below)
+            CK(mi_deconv2d_tail_reduce_ctx(st, e->at(W.tail_slabs), e->tail_nblk, e->gptr(18), &cx));      // (full two-stream backward: at the tail of the caller's stream, below)
             e->tail_nblk = 0;
         }
         // dense1: h = z W1 + b1
@@ -768,22 +767,16 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
             if (i == 0 && enc_fused) continue;               // conv1's filter / bias gradient came out of the fused encoder-head kernel below
             if (!on_main) release();
             // on the caller's stream next to a live filter-gradient stream: its own scratch region, and its slab reduce is issued right behind it on THIS stream
-            // (the deferred list is flushed on the other one)
+            // (the list of the tiled reduces lives on the other one)
             const bool own = on_main && fork;
-            if (own) mi_tapwgrad_defer_pause(1);
-            const int rcw = [&]() -> int {
-                TOP(e, sg, OP_CONV_WGRAD + i, mi_conv2d_nhwc_wgrad_ws(sg, d.dtype, x, i == 0 ? idx : nullptr, i == 0 ? (e->last_u8 ? 2 : 1) : 0, B, g.ih[i], g.iw[i], g.c[i], gy, 4, 4, g.c[i + 1], e->gptr(2 * i),
-                                                                       own ? e->at(W.scratch_main) : scratch_of(), own ? W.scratch_main_bytes : scratch_sz, e->gptr(2 * i + 1)));
-                return MI_OK;
-            }();
-            if (own) mi_tapwgrad_defer_pause(0);
-            CK(rcw);
-            if (i == 1 && late_dense) { mi_small_reduce_defer(1); mi_small_reduce_bind(st); tail_defer = true; }      // from here to the end of the pass every small slab sum on st is one job of the fused launch
+            TOP(e, sg, OP_CONV_WGRAD + i, mi_conv2d_nhwc_wgrad_ctx(sg, d.dtype, x, i == 0 ? idx : nullptr, i == 0 ? (e->last_u8 ? 2 : 1) : 0, B, g.ih[i], g.iw[i], g.c[i], gy, 4, 4, g.c[i + 1], e->gptr(2 * i),
+                                                                    own ? e->at(W.scratch_main) : scratch_of(), own ? W.scratch_main_bytes : scratch_sz, e->gptr(2 * i + 1), &cx));
+            if (i == 1 && late_dense) cx.small = &tail_sums;      // from here to the end of the pass every small slab sum on st is one job of the fused launch
             if (i == 1 && d.dtype == MI_BF16 && e->bits1_ok && e->W.enc_slab_bytes > 0 && g.c[0] == 3 && g.c[1] == 32 && g.c[2] == 64) {
                 // conv2's input gradient feeds nothing but conv1's filter gradient: both in one launch, the 99 MB tensor between them never exists (enchead_tile.hpp)
                 int nblk = 0;
-                TOP(e, st, OP_CONV_DGRAD + 1, mi_conv2d_head_bwd_fused(st, d.dtype, src, e->last_u8 ? 2 : 1, idx, B, d.ih, d.iw, gy, e->wptr(2), e->at(W.bits_act1),
-                                                                      e->gptr(0), e->gptr(1), e->at(W.enc_slabs), W.enc_slab_bytes, &nblk));
+                TOP(e, st, OP_CONV_DGRAD + 1, mi_conv2d_head_bwd_fused_ctx(st, d.dtype, src, e->last_u8 ? 2 : 1, idx, B, d.ih, d.iw, gy, e->wptr(2), e->at(W.bits_act1),
+                                                                      e->gptr(0), e->gptr(1), e->at(W.enc_slabs), W.enc_slab_bytes, &nblk, &cx));
                 if (nblk > 0) { enc_fused = true; continue; }
             }
             if (i > 1) arm();
@@ -818,21 +811,21 @@ int mi_vae_backward(void* h, void* stream, const void* src, const int* idx, cons
             void* ws1 = pair ? small_ws(st, mi_gemm_wgrad_scratch_bytes(d.dtype, B, g.flat, 2 * d.z_dim), &nb1) : nullptr;
             // (both launches' slabs are live at once: two DISJOINT pieces of the tail scratch, which its bump allocator hands out while the slab sums are deferred)
             if (pair && ws0 && ws1 && ((char*)ws0 + nb0 <= (char*)ws1 || (char*)ws1 + nb1 <= (char*)ws0)) {
-                TOP(e, st, OP_DENSE1_WGRAD, mi_gemm_wgrad_bias_pair_ws(st, d.dtype, e->at(W.z), e->at(W.gdec[0]), B, d.z_dim, g.flat, e->gptr(10), e->gptr(11), ws0, nb0,
-                                                                       e->at(W.act[4]), e->at(W.dheads), B, g.flat, 2 * d.z_dim, e->gptr(8), e->gptr(9), ws1, nb1));
+                TOP(e, st, OP_DENSE1_WGRAD, mi_gemm_wgrad_bias_pair_ctx(st, d.dtype, e->at(W.z), e->at(W.gdec[0]), B, d.z_dim, g.flat, e->gptr(10), e->gptr(11), ws0, nb0,
+                                                                       e->at(W.act[4]), e->at(W.dheads), B, g.flat, 2 * d.z_dim, e->gptr(8), e->gptr(9), ws1, nb1, &cx));
                 pair_used = true;
             } else {
                 TOP(e, st, OP_DENSE1_WGRAD, dense_wgrad(st, e->at(W.z), e->at(W.gdec[0]), B, d.z_dim, g.flat, e->gptr(10), e->gptr(11)));
             }
-            if (e->tail_nblk > 0) { CK(mi_deconv2d_tail_reduce(st, e->at(W.tail_slabs), e->tail_nblk, e->gptr(18))); e->tail_nblk = 0; }
-            if (defer) { mi_tapwgrad_flush(sw); }            // (the deferred slab reductions first: they end the other stream's real work; join() then finds the list empty)
+            if (e->tail_nblk > 0) { CK(mi_deconv2d_tail_reduce_ctx(st, e->at(W.tail_slabs), e->tail_nblk, e->gptr(18), &cx)); e->tail_nblk = 0; }
+            if (defer) { mi_tiled_reduces_flush(&tiled, cx.small); }            // (the deferred slab reductions first: they end the other stream's real work; join() then finds the list empty)
             if (!pair_used) {
                 // the heads' gradients: behind a fused encoder head the caller's stream is the one that ends early (conv1's filter gradient is no longer a launch of its own)
                 void* sh = enc_fused ? st : sw;
-                if (tail_defer && sh != st) { CK(mi_small_reduce_flush(st)); mi_small_reduce_defer(0); tail_defer = false; }      // (what follows is issued on the other stream: nothing of it may land in st's list)
+                if (cx.small && sh != st) { CK(mi_small_sums_flush(&tail_sums)); cx.small = nullptr; }      // (what follows is issued on the other stream: nothing of it may land in st's list)
                 TOP(e, sh, OP_HEADS_WGRAD, dense_wgrad(sh, e->at(W.act[4]), e->at(W.dheads), B, g.flat, 2 * d.z_dim, e->gptr(8), e->gptr(9)));
             }
-            if (tail_defer) { CK(mi_small_reduce_flush(st)); mi_small_reduce_defer(0); tail_defer = false; }
+            if (cx.small) { CK(mi_small_sums_flush(&tail_sums)); cx.small = nullptr; }
         }
         if (e->fin.pending && (part == 0 || part == 2 || part == 4)) {      // the deferred loss scalars, where the pair launch did not take them
             e->fin.pending = 0;

@@ -118,7 +118,7 @@ int mi_device_probe(void* stream, void* scratch, long long scratch_bytes, int mi
 int mi_set_tuning(int key, int value);
 /* Per calling thread, default 0 (returns the previous setting).  != 0: a raw-staged filter gradient (mi_conv2d_nhwc_wgrad_ws / mi_deconv2d_nhwc_wgrad_ws on bf16 tensors) whose
  * positions fit ONE split sums the partial rows of its bias gradient through the first bytes of the caller's scratch in a fixed order instead of fp32 atomics: two runs are
- * bitwise equal.  The ConvVAE engine's backward pass switches it on for itself; 0 leaves a scratch that holds no slabs untouched. */
+ * bitwise equal.  The switch of layer-op calls from outside: the ConvVAE engine's backward pass asks for the same in its own calls and leaves it alone; 0 leaves a scratch that holds no slabs untouched. */
 int mi_tapwgrad_bias_rows(int on);
 /* debug only: s_memtime stamps of the tapconv kernel (32 int64 per wave per block) into a caller-provided device buffer; NULL = off */
 int mi_debug_set_trace(void* dev_ptr, int capacity_entries);

@@ -57,7 +57,7 @@ def header_constants():
     grab("rwconv.hip", {"RW_MAXHALO": r"static constexpr int MAXHALO = TAPS == 2 \? (\d+) : (\d+);",
                         "RC_MAXHALO": r"static constexpr int MAXHALO = TAPS == 2 \? \(CK == 1 \? (\d+) : (\d+)\) : (\d+);"})
     grab("conv_ops.hip", {"NW_CUS": r"long long nwave = (\d+)ll \* knob\(K_NW_WAVES\);", "SMALL_TILE": r"launch_tapconv_v<T, MODE, TAPS, (\d+), (\d+)>\(st, q\) : launch_tapconv_v<T, MODE, TAPS, TC_BMT, TC_MAXHALO>",
-                          "GEN1_WGRAD_TARGET": r"return launch_wgrad\(\(hipStream_t\)stream, dtype, x_is_f32, p, (\d+), scratch, scratch_bytes\);"})
+                          "GEN1_WGRAD_TARGET": r"return launch_wgrad\(\(hipStream_t\)stream, dtype, x_is_f32, p, (\d+), scratch, scratch_bytes, 0, ctx\);"})
     text = open(os.path.join(CSRC, "tuning.hip")).read()
     out["NW_WAVES"] = int(re.search(r"\{K_NW_WAVES, \"MI355_NW_WAVES\", NOKEY, (\d+),", text).group(1))
     out["DEFAULTS"] = {int(m.group(1)): int(m.group(2)) for m in re.finditer(r"^\s*\{K_\w+, (?:nullptr|\"\w+\"), (\d+), (-?\d+), P_", text, flags=re.M)}

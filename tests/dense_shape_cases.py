@@ -70,7 +70,7 @@ def source_constants():
         "DWGS_PRED": r"M >= (\d+) && M % (\d+) == 0 && K % (\d+) == 0 && N % (\d+) == 0 && \(long long\)K \* N <= (\d+)",
         "DWGS_WSPLIT": r"const int steps = M / (\d+);\s*if \(steps % 4 == 0 && steps / 4 >= (\d+)\) return 4;\s*if \(steps % 2 == 0 && steps / 2 >= (\d+)\) return 2;",
         "WIDE_ROWS": r"const bool wide = Kce > (\d+);"})
-    assert "launch_wgrad((hipStream_t)stream, dtype, 0, p, knob(K_DENSE_WGRAD_BLOCKS), scratch, scratch_bytes, overwrite)" in open(os.path.join(CSRC, "conv_ops.hip")).read()
+    assert "launch_wgrad((hipStream_t)stream, dtype, 0, p, knob(K_DENSE_WGRAD_BLOCKS), scratch, scratch_bytes, overwrite, ctx)" in open(os.path.join(CSRC, "conv_ops.hip")).read()
     text = open(os.path.join(CSRC, "tuning.hip")).read()
     out["DEFAULTS"] = {int(m.group(1)): int(m.group(2)) for m in re.finditer(r"^\s*\{K_\w+, (?:nullptr|\"\w+\"), (\d+), (-?\d+), P_", text, flags=re.M)}
     out["ENV_DEFAULTS"] = {m.group(1): int(m.group(2)) for m in re.finditer(r"^\s*\{K_\w+, \"(MI355_\w+)\", NOKEY, (-?\d+), P_", text, flags=re.M)}

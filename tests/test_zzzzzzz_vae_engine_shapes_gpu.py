@@ -506,7 +506,8 @@ def test_inference_form_of_the_fused_encoder_head_against_float64(zoo):
 
 @pytest.mark.parametrize("case_no", [79, 97, 105])
 def test_one_split_filter_gradient_sums_its_bias_rows_in_order(case_no):
-    """What mi_vae_backward switches on for itself (mi_tapwgrad_bias_rows): a raw-staged filter gradient whose positions fit ONE split -- a small layer at a small
+    """What mi_vae_backward asks for in its own calls (the bias_rows field of the context it hands them) and a caller from outside switches on per thread
+    (mi_tapwgrad_bias_rows, used here): a raw-staged filter gradient whose positions fit ONE split -- a small layer at a small
     batch; one case per kernel family of tests/conv_shape_cases.py -- has no slabs, but each bias element is still the sum of 2 - 8 partial sums (position halves, parity
     classes), which met in fp32 atomics: two runs of a small-batch step differed in the last bit.  Switched on: the partial rows go through the scratch and one ordered
     sum -- the bias gradient of three runs bitwise equal, dW and dbias inside the layer ops' bounds against float64 (1e-4 rel + 1e-4 of max; 1e-4 of max), the

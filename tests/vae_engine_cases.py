@@ -292,7 +292,7 @@ def sum_slabs(slabs_flat, ns, middle, B, width):
 # Part B: the bf16 engine layer by layer, each op in float64 on the tensors the engine ITSELF stored
 # ---------------------------------------------------------------------------------------------------------------------------------------
 FWD_TOL = (4e-3, 4e-3)                       # hip_helpers.tols("bf16"): rel, abs as a fraction of the reference's max
-WGRAD_RMS, WGRAD_MAX = 2e-3, 1e-2            # filter gradients, of the tensor's max: the engine's position-split slabs are bf16 (vae_engine.hip, SlabGuard)
+WGRAD_RMS, WGRAD_MAX = 2e-3, 1e-2            # filter gradients, of the tensor's max: the engine's position-split slabs are bf16 (vae_engine.hip, MiWgradCtx::slab_bf16)
 BIAS_BASE = 1e-4                             # bias gradients: this + the same slab allowance
 
 
