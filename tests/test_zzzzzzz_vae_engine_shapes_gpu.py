@@ -170,7 +170,8 @@ def infer(m, c):
     return mean.cpu().numpy(), rec.cpu().numpy(), gen.cpu().numpy()
 
 
-def check_step(m, c, precision, loss_fn="bce", kl_tolerance=0.0):
+def check_step(m, c, precision, loss_fn="bce", kl_tolerance=0.0, env=None):
+    """env: the tuning knobs this process runs under, off their defaults (vae_engine_cases.route; tests/knob_route_worker.py)."""
     ref = vc.reference(c, loss_fn=loss_fn, kl_tolerance=kl_tolerance)
     got = run_step(m, c)
     rows, bad = vc.step_report(ref, float(got["losses"][0]), float(got["losses"][1]), got["mean"], got["grads"], precision)
@@ -180,7 +181,7 @@ def check_step(m, c, precision, loss_fn="bce", kl_tolerance=0.0):
     worst = max((r for r in rows if r[0].startswith("grad ")), key=lambda r: r[1])
     measure(c, tag, "worst gradient: " + worst[0][5:], float(worst[1]), worst[2])
     # the route the host gates chose is the one the case's row states
-    want = vc.route(c, precision, max_batch=m.dev.max_batch)
+    want = vc.route(c, precision, max_batch=m.dev.max_batch, env=env)
     measure(c, tag, "route (tail, head backward)", "%s, %s" % got["route"], "%s, %s" % (want["tail"], want["head_bwd"]))
     assert got["route"] == (want["tail"], want["head_bwd"]), (got["route"], want)
     assert not bad, bad
@@ -243,18 +244,13 @@ def _route_none(st, rt):
     return st
 
 
-@pytest.mark.parametrize("cid", vc.PART_B_CASES)
-def test_bf16_engine_layer_by_layer_on_its_own_stored_tensors(zoo, cid):
-    """Part B.  Forward against the oracle's bf16-storage emulation: reconstruction loss 2e-3, posterior mean 3e-2 of max, KL within 1.25 x |emulation - float64| +
-    5e-3 |float64|.  (The bf16 engine's GRADIENTS are not compared with the oracle at these batch sizes: the emulation itself is 19 % - 67 % of deconv1's kernel
-    gradient away from float64 -- ReLU flips behind the bottleneck with few samples to average them.)  Instead, after one forward + backward, every layer is held
-    against the float64 statement of that ONE op on the engine's own stored inputs (vae_engine_cases.layer_report): forward outputs and input gradients 4e-3 rel +
-    4e-3 of max, filter gradients 2e-3 rms / 1e-2 max of the tensor's max, bias gradients 1e-4 of max more.  Cases 1 and 7: uint8 frame tables give bitwise the
-    float tables' losses, stored tensors and gradients (as test_uint8_frame_tables_in_the_bf16_engine asserts at the model's shape)."""
+def bf16_layer_by_layer(zoo, cid, env=None, slab="bf16", u8=None):
+    """The body of test_bf16_engine_layer_by_layer_on_its_own_stored_tensors.  env, slab: the tuning knobs the process runs under and the slab kind they give the
+    backward pass (tests/knob_route_worker.py; the defaults are a process without knobs); u8: also run the step on uint8 frame tables (None: cases 1 and 7)."""
     c = vc.by_id(cid)
     m = zoo.get(c, "bf16")
     got = run_step(m, c, grab=True)
-    rt = vc.route(c, "bf16", max_batch=m.dev.max_batch)
+    rt = vc.route(c, "bf16", max_batch=m.dev.max_batch, env=env)
     measure(c, "bf16", "route (tail, head backward)", "%s, %s" % got["route"], "%s, %s" % (rt["tail"], rt["head_bwd"]))
     assert got["route"] == (rt["tail"], rt["head_bwd"]), (got["route"], rt)
     emul, exact = vc.reference(c, dtype="f32", storage="bf16"), vc.reference(c)
@@ -264,18 +260,30 @@ def test_bf16_engine_layer_by_layer_on_its_own_stored_tensors(zoo, cid):
     measure(c, "bf16", "posterior mean / max vs emulation", d_mean, 3e-2)
     measure(c, "bf16", "|kl - float64|", float(abs(got["losses"][1] - exact.kl)), float(kl_bound))
     assert d_recon < 2e-3 and d_mean < 3e-2 and abs(got["losses"][1] - exact.kl) <= kl_bound, (d_recon, d_mean, got["losses"][1], exact.kl, emul.kl)
-    R = vc.layer_report(c, _route_none(got["stored"], rt), got["grads"], vc.params(c), vc.inputs(c), rt)
+    R = vc.layer_report(c, _route_none(got["stored"], rt), got["grads"], vc.params(c), vc.inputs(c), rt, slab=slab)
     for name, how, val, bound in R.rows:
         measure(c, "bf16", "%s (%s)" % (name, how), val, bound)
     assert not R.bad, R.bad
     assert len(R.rows) >= 41
-    if cid in vc.PART_B_U8_CASES:
+    if cid in vc.PART_B_U8_CASES if u8 is None else u8:
         assert m.dev.accepts_u8
         u8 = run_step(m, c, u8=True, grab=True)
         assert np.array_equal(u8["losses"], got["losses"]) and np.array_equal(u8["flat"], got["flat"]) and np.array_equal(u8["params_flat"], got["params_flat"])
         for k, v in _route_none(got["stored"], rt).items():
             if v is not None:
                 assert np.array_equal(u8["stored"][k], v), k
+    return got
+
+
+@pytest.mark.parametrize("cid", vc.PART_B_CASES)
+def test_bf16_engine_layer_by_layer_on_its_own_stored_tensors(zoo, cid):
+    """Part B.  Forward against the oracle's bf16-storage emulation: reconstruction loss 2e-3, posterior mean 3e-2 of max, KL within 1.25 x |emulation - float64| +
+    5e-3 |float64|.  (The bf16 engine's GRADIENTS are not compared with the oracle at these batch sizes: the emulation itself is 19 % - 67 % of deconv1's kernel
+    gradient away from float64 -- ReLU flips behind the bottleneck with few samples to average them.)  Instead, after one forward + backward, every layer is held
+    against the float64 statement of that ONE op on the engine's own stored inputs (vae_engine_cases.layer_report): forward outputs and input gradients 4e-3 rel +
+    4e-3 of max, filter gradients 2e-3 rms / 1e-2 max of the tensor's max, bias gradients 1e-4 of max more.  Cases 1 and 7: uint8 frame tables give bitwise the
+    float tables' losses, stored tensors and gradients (as test_uint8_frame_tables_in_the_bf16_engine asserts at the model's shape)."""
+    bf16_layer_by_layer(zoo, cid)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------

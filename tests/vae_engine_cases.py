@@ -10,7 +10,7 @@ References: the oracle (oracle/vae_oracle.py, which takes the encoded shape from
 per-layer float64 statements of Part B (layer_report) run each op on the tensors the engine itself stored.
 
 route() restates the HOST gates of csrc/vae_engine.hip that choose the kernels of a step and nothing else (fresh torch allocations are 256-byte aligned, the tuning knobs
-at their defaults); test_vae_engine_cases_host.py asserts that every case takes the route its row states."""
+at their defaults unless `env` names them: tests/knob_route_cases.py); test_vae_engine_cases_host.py asserts that every case takes the route its row states."""
 import collections
 
 import numpy as np
@@ -114,10 +114,10 @@ BCE_CHUNK = 256 * 24                       # elementwise.hip
 GN_BMT = 128                               # narrow_tile.hpp: positions per block of the loss epilogue
 
 
-def pick_split(M, N, K, bk):
-    """vae_engine.hip pick_split: K slabs of the latent layers' split-K sums."""
+def pick_split(M, N, K, bk, cap=LATENT_SPLIT):
+    """vae_engine.hip pick_split: K slabs of the latent layers' split-K sums.  cap: MI355_LATENT_SPLIT (a value outside 1 .. 32 is the default, tuning.hip P_RANGE)."""
     tiles = -(-M // 128) * (1 if N <= 64 else -(-N // 128))
-    ns = min(max(256 // max(tiles, 1), 1), LATENT_SPLIT)
+    ns = min(max(256 // max(tiles, 1), 1), cap)
     while ns > 1:
         ln = -(-K // ns)
         ln = -(-ln // bk) * bk
@@ -132,30 +132,55 @@ def z_dim_multiple(precision):
     return 8 if precision == "bf16" else 4
 
 
-def route(c, precision, training=True, max_batch=128):
+# the knobs route() knows (tests/knob_route_cases.py runs the engine under each): name without the MI355_ prefix -> default.  All but LATENT_SPLIT are on / off switches
+# read as tuning.hip's P_ON rows read them (off only for a value that starts with '0'); LATENT_SPLIT is a P_RANGE row, 1 .. 32, anything else the default.
+ROUTE_KNOBS = {"ENC12": 1, "NARROW": 1, "RELU_BITS": 1, "ENCHEAD": 1, "ARES": 1, "ARES_MID": 1, "DECTAIL": 1, "LATENT_SPLIT": LATENT_SPLIT}
+
+
+def route_knobs(env=None):
+    """{knob: value} of ROUTE_KNOBS under env, a dict of knob name (with or without the MI355_ prefix) -> value as the environment would hold it (int or str).
+    Knobs route() does not depend on are ignored: a step of knob_route_cases.py passes its whole environment."""
+    kn = dict(ROUTE_KNOBS)
+    for name, v in (env or {}).items():
+        name = name[6:] if name.startswith("MI355_") else name
+        if name not in kn:
+            continue
+        if name == "LATENT_SPLIT":
+            kn[name] = int(v) if 1 <= int(v) <= 32 else LATENT_SPLIT
+        else:
+            kn[name] = 0 if str(v).startswith("0") else 1
+    return kn
+
+
+def route(c, precision, training=True, max_batch=128, env=None):
+    """env: knobs off their defaults (route_knobs); None = every knob at its default, today's behaviour."""
     g = geom(c)
+    kn = route_knobs(env)
     bf16 = precision == "bf16"
     r = {}
-    # mi_enc12_eligible (enc12.hip) behind enc12_model(): bf16, 3-channel frames, 80 x 160
-    r["enc_head"] = "fused" if bf16 and c.cin == 3 and (c.H, c.W) == (80, 160) else "two launches"
+    # mi_enc12_eligible (enc12.hip: MI355_ENC12 and the narrow kernels) behind enc12_model(): bf16, 3-channel frames, 80 x 160
+    r["enc_head"] = "fused" if bf16 and c.cin == 3 and (c.H, c.W) == (80, 160) and kn["ENC12"] and kn["NARROW"] else "two launches"
     # try_narrow_conv (conv_ops.hip): 1..3 channels into 32 (K = 16 cin <= 48), rows of whole 2-element groups, >= 32 output pixels
     oh1, ow1, _ = g["enc"][1]
-    r["conv1"] = "narrow" if (16 * c.cin <= 48 and (c.W * c.cin) % 2 == 0 and oh1 * ow1 >= 32) else "general"
-    # the ReLU bit words of conv1's output exist: training pass of the bf16 engine through the fused head or the narrow kernel
-    bits1 = bf16 and training and (r["enc_head"] == "fused" or r["conv1"] == "narrow")
-    # vae_engine.hip:747 (no geometry term) + mi_conv2d_head_bwd_fused (enchead.hip): 3-channel frames of at least 10 x 10
-    r["head_bwd"] = "fused" if bits1 and c.cin == 3 and c.H >= 10 and c.W >= 10 else "layer ops"
-    # ares_eligible: bf16, conv4 8 x 18 x 128 -> 3 x 8 x 256; the mid-layer forms depend on channel counts alone, which this model family never changes
-    r["ares"] = "on+mid" if bf16 and g["enc"][3][:2] == (8, 18) and g["enc"][4][:2] == (3, 8) else "off"
-    # decoder tail: mi_deconv2d_tail_fused (bf16, 32 -> 3 channels, rows of 3 OW labels in 4-value items), else the loss epilogue of try_gather_narrow (1 or 3 channels,
-    # even OW, blocks within the partial-sum capacity), else deconv4 + mi_bce_logits_fwd_bwd_bias + the chunked mi_vae_finalize_losses
+    r["conv1"] = "narrow" if (kn["NARROW"] and 16 * c.cin <= 48 and (c.W * c.cin) % 2 == 0 and oh1 * ow1 >= 32) else "general"
+    # the ReLU bit words of conv1's output exist (MI355_RELU_BITS): training pass of the bf16 engine through the fused head or the narrow kernel
+    bits1 = bf16 and training and kn["RELU_BITS"] and (r["enc_head"] == "fused" or r["conv1"] == "narrow")
+    r["bits1"] = bool(bits1)
+    # vae_engine.hip (no geometry term) + mi_conv2d_head_bwd_fused (enchead.hip: MI355_ENCHEAD, the narrow kernels, the bit words): 3-channel frames of at least 10 x 10
+    r["head_bwd"] = "fused" if bits1 and kn["ENCHEAD"] and kn["NARROW"] and c.cin == 3 and c.H >= 10 and c.W >= 10 else "layer ops"
+    # ares_eligible (MI355_ARES): bf16, conv4 8 x 18 x 128 -> 3 x 8 x 256; the mid-layer forms depend on channel counts alone, which this model family never changes,
+    # and on MI355_ARES_MID (mi_ares_conv refuses form 2 without it: the engine then runs the layer op)
+    r["ares"] = ("on+mid" if kn["ARES_MID"] else "on") if bf16 and kn["ARES"] and g["enc"][3][:2] == (8, 18) and g["enc"][4][:2] == (3, 8) else "off"
+    # decoder tail: mi_deconv2d_tail_fused (MI355_DECTAIL and the narrow kernels; bf16, 32 -> 3 channels, rows of 3 OW labels in 4-value items), else the loss epilogue of
+    # try_gather_narrow (the narrow kernels; 1 or 3 channels, even OW, blocks within the partial-sum capacity), else deconv4 + mi_bce_logits_fwd_bwd_bias + the chunked
+    # mi_vae_finalize_losses
     h3, w3, _ = g["dec"][3]
     P = c.H * c.W * c.ct
     cap_per_frame = max(64, -(-P // BCE_CHUNK))
     epi_blocks_per_frame = -(-(((c.H + 1) // 2 + 1) * ((c.W + 1) // 2 + 1)) // GN_BMT) + 1      # ceil(B GH GW / 128) <= B x (this)
-    if bf16 and training and c.ct == 3 and (3 * (2 * w3 + 2)) % 4 == 0 and P % 4 == 0:
+    if bf16 and training and kn["DECTAIL"] and kn["NARROW"] and c.ct == 3 and (3 * (2 * w3 + 2)) % 4 == 0 and P % 4 == 0:
         r["tail"] = "fused"
-    elif c.ct in (1, 3) and c.W % 2 == 0 and epi_blocks_per_frame <= cap_per_frame:
+    elif kn["NARROW"] and c.ct in (1, 3) and c.W % 2 == 0 and epi_blocks_per_frame <= cap_per_frame:
         r["tail"] = "epilogue"
     else:
         r["tail"] = "plain"
@@ -163,8 +188,8 @@ def route(c, precision, training=True, max_batch=128):
     r["stream_mask"] = 1 if r["tail"] == "fused" else 5
     r["pair_launch"] = r["head_bwd"] == "fused"           # dense1's and the heads' filter gradients as one launch, the loss finalisation in front of it (enc_fused)
     bk = 32 if bf16 else 16
-    r["ns_heads"] = pick_split(max_batch, 2 * c.z, g["flat"], bk)
-    r["ns_dz"] = pick_split(max_batch, c.z, g["flat"], bk)
+    r["ns_heads"] = pick_split(max_batch, 2 * c.z, g["flat"], bk, kn["LATENT_SPLIT"])
+    r["ns_dz"] = pick_split(max_batch, c.z, g["flat"], bk, kn["LATENT_SPLIT"])
     return r
 
 
@@ -362,9 +387,13 @@ def loss_grad(logits, tgt, inv_batch, loss_fn):
     return rows.detach(), x.grad
 
 
+WGRAD_F32_SLABS = (1e-4, 1e-4)              # filter gradients summed through fp32 slabs (MI355_SLAB_BF16=0): the layer ops' bf16 bound, rel + of the tensor's max (README, conv row)
+
+
 class LayerReport:
-    def __init__(self):
-        self.rows, self.bad = [], []
+    def __init__(self, slab="bf16"):
+        assert slab in ("bf16", "fp32"), slab
+        self.rows, self.bad, self.slab = [], [], slab
 
     def close(self, name, got, ref, tol=FWD_TOL):
         got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
@@ -378,6 +407,8 @@ class LayerReport:
 
     def wgrad(self, name, got, ref):
         got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64).reshape(np.shape(got))
+        if self.slab == "fp32":
+            return self.close(name, got, ref, WGRAD_F32_SLABS)
         scale = max(np.abs(ref).max(), 1e-30)
         rms, mx = float(np.sqrt(np.mean((got - ref) ** 2)) / scale), float(np.abs(got - ref).max() / scale)
         self.rows.append((name, "rms / max of tensor max", (rms, mx), (WGRAD_RMS, WGRAD_MAX)))
@@ -388,19 +419,26 @@ class LayerReport:
         got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
         scale = max(np.abs(ref).max(), 1e-30)
         rms, mx = float(np.sqrt(np.mean((got - ref) ** 2)) / scale), float(np.abs(got - ref).max() / scale)
+        if self.slab == "fp32":                              # no slab allowance: the layer ops' bias bound, 1e-4 of the tensor's max
+            self.rows.append((name, "max of tensor max", mx, BIAS_BASE))
+            if not mx <= BIAS_BASE:
+                self.bad.append((name, rms, mx))
+            return
         self.rows.append((name, "rms / max of tensor max", (rms, mx), (BIAS_BASE + WGRAD_RMS, BIAS_BASE + WGRAD_MAX)))
         if not (rms <= BIAS_BASE + WGRAD_RMS and mx <= BIAS_BASE + WGRAD_MAX):
             self.bad.append((name, rms, mx))
 
 
-def layer_report(c, st, grads, p, d, rt, loss_fn="bce", kl_tolerance=0.0, drop_tap_row=None):
+def layer_report(c, st, grads, p, d, rt, loss_fn="bce", kl_tolerance=0.0, drop_tap_row=None, slab="bf16"):
     """Every layer of one forward + backward of the bf16 engine against the float64 statement of that ONE op on the engine's own stored inputs.
     st: {'act1'..'act4', 'dec0'..'dec4', 'gact1'..'gact4', 'gdec0'..'gdec4', 'dheads', 'z', 'mean', 'logvar'} float64 numpy (None: the route never stores it);
     grads: the 22 gradient tensors (TF names); p: fp32 parameters; d: inputs(); rt: route().  The weights are rounded to bf16 (the shadow copy the kernels multiply),
     the ReLU masks are the engine's own stored activations.  Where a fused route never stores an intermediate the statement runs both stages from the last stored
     tensor, with the intermediate rounded to bf16 where the kernel's own comment says it is (dectail_tile.hpp: "logits as STORED, dlogits as STORED";
-    enchead_tile.hpp: "g1 is rounded to bf16 exactly where the unfused path stores it"), under the looser of the two stages' bounds."""
-    R = LayerReport()
+    enchead_tile.hpp: "g1 is rounded to bf16 exactly where the unfused path stores it"), under the looser of the two stages' bounds.
+    slab: how the engine stored the partial sums of its filter / bias gradients -- 'bf16' (the engine's default) or 'fp32' (MI355_SLAB_BF16=0: those rows then take
+    the layer ops' bound, 1e-4 rel + 1e-4 of max and 1e-4 of max, with no slab allowance)."""
+    R = LayerReport(slab)
     B, z = c.B, c.z
     inv_b = 1.0 / B
     W = {k: bf16r(v) for k, v in p.items() if k.endswith("kernel")}
