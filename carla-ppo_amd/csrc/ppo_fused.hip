@@ -21,6 +21,8 @@
 //   ppo_predict_head_kernel, ppo_update_stats_head_kernel, ppo_kl_stats_head_kernel:  pf_head_sums_strided, pf_mean_libm, pf_logp_term_libm -- the one spelling the
 //       bit-for-bit contracts between these kernels and the loss body rest on (stated at those functions); the two statistics kernels end in pf_ordered_block_sum,
 //       and ppo_stats_reduce_kernel<N> runs behind either
+//   ppo_values_head_kernel (mi_ppo_values_idx: the value net alone, forward only):  pf_head_sums_strided's value half, so that its value is the statistics kernel's
+//       value_out bit for bit
 // On the host pf_step_head_kernel picks the step's head kernel from a table and pf_na_pick the NA of the other launches; the two rules differ on purpose (A = 1).
 //
 // All arithmetic is exact fp32 (v_mfma_f32_32x32x2_f32 = fmaf chains; 1e-4 parity with the oracle).  The split-bf16 mode (X3 = true: MI_BF16X3 through
@@ -1009,6 +1011,26 @@ __global__ __launch_bounds__(256) void ppo_kl_stats_head_kernel(const PpoFusedPa
     pf_ordered_block_sum<PF_NKLSTATS>(term, swave, scratch, tid);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// values of table rows (mi_ppo_values_idx): the value head of the CURRENT value net alone, on a trunk that ran the value net as net 0 -- the caller's parameter
+// block has off[0..3] = off[7..10] and n_nets = 1, so h2 slot 0 holds the value net's activations; Wv / bv stay at off[11] / off[12].  grid ceil(M / 32) blocks; 8
+// threads per sample, ppo_update_stats_head_kernel's part / row split and, through pf_head_sums_strided, its order of operations: the stored value is that
+// kernel's value_out bit for bit (the contracts: ppo_head.hpp).  Sample m is table row row_idx[m] (nullptr: m) and its value goes to values_out[that row]; a row
+// outside [0, n_rows) stores NOTHING (the statistics head clamps the store; layer 1 clamped the loads).  No LDS, no atomics, no reduction behind it.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ppo_values_head_kernel(const PpoFusedParams q, float* __restrict__ values_out) {
+    const int tid = threadIdx.x, m0 = blockIdx.x * 32, H2 = q.H2;
+    const int sm = tid >> 3, part = tid & 7, m = m0 + sm;
+    const float* Wv = q.theta + q.off[11]; const float* bv = q.theta + q.off[12];
+    const float* h2v = q.h2 + (long long)m * H2;          // (slot 0: see above)
+    float au[1], av;                                      // (A = 0: no policy sums are formed)
+    pf_head_sums_strided<1, 8>(h2v, h2v, Wv, Wv, m < q.M, true, part, H2, 0, au, av);
+    if (part != 0 || m >= q.M) return;
+    const int row = q.row_idx ? q.row_idx[m] : m;
+    if (row < 0 || row >= q.n_rows) return;
+    values_out[row] = av + bv[0];
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -1089,6 +1111,35 @@ int mi_ppo_fused_kl_stats(hipStream_t st, PpoFusedParams& q, int accumulate, dou
     hipLaunchKernelGGL(pf_na_pick(q.A, ppo_kl_stats_head_kernel<2>, ppo_kl_stats_head_kernel<PF_MAX_ACT>), dim3(nb), dim3(256), 0, st, q, scratch);
     hipLaunchKernelGGL(ppo_stats_reduce_kernel<PF_NKLSTATS>, dim3(1), dim3(64), 0, st, (const double*)scratch, nb, accumulate, stats);
     return mi_check_launch("ppo_kl_stats");
+}
+
+// V(s) of M table rows under the current theta (mi_ppo_values_idx): the value net ALONE.  The trunk kernels number nets by blockIdx.y from 0, so a copy of the
+// parameter block with the value net's layer-1 / layer-2 tensors in net 0's places (off[0..3] = off[7..10]) and n_nets = 1 runs it in slot 0 of h1 / h2 without a
+// kernel change; the head reads Wv / bv at the untouched off[11] / off[12].  M may exceed the engine's max_batch: chunks of max_batch rows, three launches each
+// (row_idx given: the chunk's part of the list against the whole table; else the chunk's rows of states / values_out).  Every chunk is checked before the first
+// launch.  Nothing but the activation workspace and values_out is written.
+int mi_ppo_fused_values(hipStream_t st, const PpoFusedParams& q0, const int* row_idx, long long n_rows, long long M, float* values_out, bool x3) {
+    PpoFusedParams q = q0;
+    for (int i = 0; i < 4; ++i) q.off[i] = q0.off[7 + i];
+    q.n_nets = 1;
+    q.s_gath = nullptr;                                   // (no filter gradient behind this pass)
+    const long long mb = q.max_batch;
+    // (a table the 32-bit offsets cannot address is refused by pf_check_shape whatever its row count: the int field saturates)
+    const int n_rows_i = n_rows > 0x7fffffffll ? 0x7fffffff : (int)n_rows;
+    for (long long lo = 0; lo < M; lo += mb) {
+        const int m = (int)(M - lo < mb ? M - lo : mb);
+        q.M = m;
+        if (row_idx) { q.states = q0.states; q.row_idx = row_idx + lo; q.n_rows = n_rows_i; }
+        else { q.states = q0.states + lo * q.din; q.row_idx = nullptr; q.n_rows = m; }
+        // the first chunk is the largest and every chunk addresses the same table: its check, before the first launch, is the call's
+        if (lo == 0) { const int rc0 = pf_check_shape(q, "ppo fused values"); if (rc0 != MI_OK) return rc0; }
+        const int rc = mi_ppo_fused_trunks(st, q, x3);
+        if (rc != MI_OK) return rc;
+        hipLaunchKernelGGL(ppo_values_head_kernel, dim3((m + 31) / 32), dim3(256), 0, st, q, row_idx ? values_out : values_out + lo);
+        const int rc2 = mi_check_launch("ppo_values_head");
+        if (rc2 != MI_OK) return rc2;
+    }
+    return MI_OK;
 }
 
 int mi_ppo_fused_partial_floats(int M) { return ((M + 31) / 32) * PF_NPART; }

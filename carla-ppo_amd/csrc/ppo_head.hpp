@@ -7,7 +7,8 @@
 //         -> ppo_head_loss_body (8 instantiations, and 8 with DEMO: the step with a demonstration term), ppo_head_clone_kernel (4)
 //   the strided form (columns j = part, part + TPS, .. straight from memory; libm):
 //     pf_head_sums_strided, pf_mean_libm, pf_logp_term_libm
-//         -> ppo_predict_head_kernel (4), ppo_update_stats_head_kernel (2), ppo_kl_stats_head_kernel (2); the two libm spellings also in the loss body's
+//         -> ppo_predict_head_kernel (4), ppo_update_stats_head_kernel (2), ppo_kl_stats_head_kernel (2), ppo_values_head_kernel (1: the value half of the sums
+//            alone); the two libm spellings also in the loss body's
 //            old-policy block, whose sums stay there (from LDS, in the strided order)
 //     pf_ordered_block_sum, ppo_stats_reduce_kernel
 //         -> the two statistics kernels and the launch behind each
@@ -181,6 +182,10 @@ __device__ __forceinline__ void pf_head_dh2(const PpoFusedParams& q, const float
 //                                                by lr / 3.2e-7)
 //   ppo_update_stats_head_kernel                 with theta == theta_old its log-probabilities are the cached ones, so d = 0 and r = 1 exactly
 //   ppo_kl_stats_head_kernel                     with theta == theta_old its means are the cached ones, so the KL of a policy with itself is 0
+// A fourth contract is on the VALUE: ppo_values_head_kernel (mi_ppo_values_idx, the value net run alone) stores for a row what ppo_update_stats_head_kernel's
+// value_out stores for it under the same parameters, so a table refreshed by the one can stand where the other's stood.  Both call pf_head_sums_strided<., 8> with
+// val = true on the value net's h2 row -- the same columns in the same order, the same three shuffles -- and add bv[0] last; the h2 row is the same bits whichever
+// net slot the trunk kernels wrote it to.
 // They do because all four go through the three functions below and sum the actions' terms serially, a = 0, 1, ..: the columns j = part, part + 8, .. of the row
 // in ascending order (the loss body spells that loop itself, from LDS: the same values in the same order), the same shuffles, then libm tanhf / expf / logf. ----
 

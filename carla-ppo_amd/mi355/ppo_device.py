@@ -389,6 +389,16 @@ class PpoDevice:
         self.L.mi_ppo_update_stats_idx(self.handle, self.stream(), p(states), p(actions), p(returns), p(logp_old), p(row_idx), int(states.shape[0]), int(M),
                                        1 if accumulate else 0, p(scratch), p(stats), p(logp_new_out), p(value_out))
 
+    def values_idx(self, states, row_idx, M, out):
+        """V(s) under the CURRENT parameters of M rows of the table `states` [n_rows, input_dim] (mi_ppo_values_idx): the value net alone, forward only.  row_idx: an
+        int32 device tensor [M] naming table rows, or None (rows 0 .. M-1).  The value of a row goes to the entry of `out` (float32 device tensor, n_rows entries) with
+        that row's number; a row outside [0, n_rows) stores nothing, and entries no row names keep their contents.  M may exceed max_batch: the entry walks the chunks
+        itself and the engine is NOT grown.  Bit for bit the value_out table of update_stats.  Nothing of the training state is written."""
+        if int(out.shape[0]) < int(states.shape[0]):
+            raise ValueError("PpoDevice.values_idx: `out` has %d entries for a table of %d rows" % (int(out.shape[0]), int(states.shape[0])))
+        p = milib.ptr
+        self.L.mi_ppo_values_idx(self.handle, self.stream(), p(states), p(row_idx), int(states.shape[0]), int(M), p(out))
+
     def stats_scratch_doubles(self, M):
         return int(self.L.mi_ppo_update_stats_scratch_doubles(int(M)))
 

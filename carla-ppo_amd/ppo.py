@@ -612,6 +612,27 @@ class PPO():
             return sampled_action[0], value[0]
         return sampled_action, value
 
+    def values(self, input_states):
+        """V(s) under the current parameters -> float32 [n], without sampling an action.  input_states: host array or device tensor [n, input_dim] (one state
+        [input_dim] counts as n = 1; the result is still [1]).  With the fused kernels (PpoDevice.fused_ok()) one forward-only pass of the value net alone
+        (mi_ppo_values_idx, in the engine's precision mode, any n); otherwise the value half of predict(greedy=True), whose values it then equals bit for bit."""
+        import torch
+        dev = self._need_dev()
+        if isinstance(input_states, torch.Tensor):
+            s = input_states.to(device=dev.device, dtype=torch.float32).reshape(-1, self.input_dim).contiguous()
+        else:
+            a = np.asarray(input_states)
+            s = self._to_dev(a, (1 if a.ndim == 1 else len(a), self.input_dim))
+        n = int(s.shape[0])
+        if n < 1:
+            raise ValueError("PPO.values: no states")
+        value = torch.empty(n, device=dev.device)
+        if dev.fused_ok():
+            dev.values_idx(s, None, n, value)
+        else:
+            dev.predict(s, n, None, True, torch.empty(n, self.num_actions, device=dev.device), value)
+        return value.cpu().numpy()
+
     def get_episode_idx(self):
         return int(self.episode_counter)
 

@@ -269,6 +269,19 @@ RandomState, the permutation and the cursor.  The result gains `demo_losses` (on
 with the setting off no key appears and the update makes the launches it always made.  Refused before anything is launched: an empty demonstration buffer, another
 input_dim / action count / ppo object, a stacked rollout buffer, observation normalisation that is not off in both buffers or frozen here and equal by value to the
 state the demonstration buffer was given, and a policy outside the fused kernels' range.
+
+RolloutBuffer.set_advantage_recomputation(on=True) RECOMPUTES VALUES AND ADVANTAGES before every epoch of an update but the first (Andrychowicz et al. 2021, "What
+Matters in On-Policy RL": by epoch 2 the value net has moved, and returns and advantages formed from the values of collection time are stale).  Epoch 1 is the epoch
+it always was -- the finish call reads the recorded `values` -- so num_epochs = 1 is bitwise the setting off.  Before every later epoch that runs (a KL stop ends the
+refreshes with the epochs) the stage "recompute" makes ONE mi_ppo_values_idx call (the value net alone, forward only, chunked inside the entry) over the recorded rows
+and the bootstrap slots of `states` into a second table `values_now`, and repeats the update's finish call with `values_now` in the place of `values` and everything
+else as it was; `returns` and `advantages`, which the steps gather from, are rewritten, and per-minibatch normalisation reads the refreshed raw advantages.  `values`
+stays the collection-time table: value clipping reads it as V_old (PPO2's meaning) and `out["values"]` returns it; `returns` / `advantages` / `raw_advantages` of the
+result are the first finish call's.  New keys: `recomputed_epochs`, and when a refresh ran `refreshed_values` (fp32) and `refreshed_returns` /
+`refreshed_advantages` / `refreshed_raw_advantages` (fp64), [num_envs, T] of the LAST refresh, NaN beyond a lane's length.  ContinuousRolloutBuffer.truncate() becomes
+a greedy recording call that keeps the final observation's state row in `final_states`; every refresh values those rows into `final_values_now`, from which the
+truncated segments then bootstrap; `final_values` stays the recorded table and the result gains `refreshed_final_values`.  Needs the fused kernels; switched only
+with no step recorded.  With the setting off no table is allocated and every call makes the launches it always made.
 """
 import contextlib
 import os
@@ -1066,6 +1079,8 @@ class RolloutBuffer:
         self.raw_states = None                                                       # its fp32 table of the raw rows, allocated when the setting is turned on
         self.mean_old = None                                                         # the old policy's action means per table row, allocated by the first update with the KL penalty on (PPO.set_kl_penalty)
         self._demo = None                                                            # the demonstration term (set_demonstrations): None = off
+        self._adv_recompute = False                                                  # advantage recomputation before every later epoch (set_advantage_recomputation)
+        self.values_now = None                                                       # its fp32 table: V per table row under the current parameters, allocated by the first update that needs it
 
     def set_observation_normalization(self, clip=10.0, epsilon=1e-8, frozen=False, normalize_latents=True):
         """Turns running observation normalisation on (see the module docstring): step(), bootstrap() and truncate() feed the trunks clamp((s - mean) * inv_std, +-clip)
@@ -1208,6 +1223,20 @@ class RolloutBuffer:
             ids = np.asarray(env_ids)
             ids = self.rows.env_ids(ids, ids.shape[0] if ids.ndim == 1 else 0)
             rs["carry"][torch.from_numpy(ids).to(self.device)] = 0.0
+
+    def set_advantage_recomputation(self, on=True):
+        """Turns advantage recomputation on (True) or off (False / None): with it on, update() refreshes the values and with them the returns and advantages before
+        every epoch but the first (see `_recompute_stage`; Andrychowicz et al. 2021).  Epoch 1 reads the values recorded at collection time, so num_epochs = 1 is bitwise the
+        setting off.  `values` stays the collection-time table: value clipping reads it as V_old and the result returns it.  Needs the fused kernels (update() refuses
+        otherwise).  Only with no step recorded (after reset()): with the setting on ContinuousRolloutBuffer.truncate() records the final observation's state row,
+        which a collection must do for all of its truncations or for none.  ValueError before anything changes."""
+        if on is not None and not isinstance(on, (bool, np.bool_)):
+            raise ValueError("%s.set_advantage_recomputation: the value is True, False or None (off), got %r" % (type(self).__name__, on))
+        if (self.rows.lengths > 0).any() or self.rows.awaiting.any():
+            raise ValueError("%s.set_advantage_recomputation: steps are recorded; call it after reset() -- a collection records its truncations in one way" % type(self).__name__)
+        self._adv_recompute = bool(on)
+        if not self._adv_recompute:
+            self.values_now = None
 
     def set_minibatch_normalization(self, ddof=0):
         """Turns per-minibatch advantage normalisation on (see the module docstring): in front of every epoch one mi_ppo_minibatch_advantages call normalises the raw
@@ -1394,7 +1423,12 @@ class RolloutBuffer:
         (NaN beyond a row's length, all NaN for num_epochs = 0); `stage_times` gains "minibatch_norm", which is also part of "sgd".  With observation normalisation on
         (set_observation_normalization) the last launch is mi_rollout_obs_stats over `raw_states` at rows.valid_rows() (merging unless frozen), and the result gains
         `observation_rms` = {"count", "mean" [input_dim], "var" [input_dim]} and `observation_clip_fraction`, float64 [input_dim]; `stage_times` gains
-        "observation_stats".  A recorded observation that is not finite is not merged: ValueError behind that last launch, the statistics as they were."""
+        "observation_stats".  A recorded observation that is not finite is not merged: ValueError behind that last launch, the statistics as they were.
+        With advantage recomputation on (set_advantage_recomputation) every epoch but the first starts with a refresh (_recompute_stage: one mi_ppo_values_idx call
+        into `values_now`, then the finish call again on it): the steps of that epoch gather the refreshed returns and advantages, the result gains
+        `recomputed_epochs` and, when a refresh ran, `refreshed_values` / `refreshed_returns` / `refreshed_advantages` / `refreshed_raw_advantages` of the last one;
+        `returns` / `advantages` / `raw_advantages` / `values` stay the first finish call's and the recorded ones; `stage_times` gains "recompute", which is also
+        part of "sgd"."""
         return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, None)
 
     def update_with_diagnostics(self, gamma=0.99, lam=0.95, num_epochs=3, batch_size=32, stage_times=None, target_kl=None):
@@ -1413,20 +1447,23 @@ class RolloutBuffer:
         (mi355.ppo_device.value_clip_summary): the statistics pass also writes V per table row, mi_ppo_value_clip_stats runs over the same chunks, and both sets of
         sums come back in the epoch's one readback.
         With reward scaling on (set_reward_scaling) the returns table holds returns of the SCALED rewards: value_mse and explained_variance are measured on those.
+        With advantage recomputation on (set_advantage_recomputation) the returns table holds, from epoch 2 on, the REFRESHED returns of that epoch: value_mse and
+        explained_variance are measured against those.
         Needs the cached log pi_old, i.e. the fused kernels (PpoDevice.fused_ok()): ValueError otherwise, before anything is launched or changed."""
         return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, _diagnostics(type(self).__name__, target_kl))
 
     def _run_update(self, gamma, lam, num_epochs, batch_size, stage_times, diag):
-        def finish(st, r, d, lengths, f64):
+        def finish(st, r, d, lengths, f64, now=False):
             import torch
             ln = torch.from_numpy(lengths).to(self.device)
-            self.L.mi_rollout_finish(st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), ln.data_ptr(), self.num_envs, self.horizon, float(gamma), float(lam),
+            self.L.mi_rollout_finish(st, (self.values_now if now else self.values).data_ptr(), r.data_ptr(), d.data_ptr(), ln.data_ptr(), self.num_envs, self.horizon, float(gamma), float(lam),
                                      self.returns.data_ptr(), self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
         return self._update(finish, num_epochs, batch_size, stage_times, diag, gamma)
 
     def _update(self, finish, num_epochs, batch_size, stage_times, diag=None, gamma=None, truncs=None):
-        """What every buffer's update does around its finish call `finish(stream, rewards, dones, lengths, f64)` (device rewards / dones, fp64 [3, E, T] of NaN for the raw
-        advantages, returns and normalised advantages): check, upload, scale the rewards, finish, cache log pi_old, the epochs, the result, the observation statistics.
+        """What every buffer's update does around its finish call `finish(stream, rewards, dones, lengths, f64, now=False)` (device rewards / dones, fp64 [3, E, T] of NaN for
+        the raw advantages, returns and normalised advantages; now=True: the call reads the refreshed value tables instead of the recorded ones): check, upload,
+        scale the rewards, finish, cache log pi_old, the epochs, the result, the observation statistics.
         A stage of an optional setting runs only with that setting on.  diag: None, or update_with_diagnostics' {"target_kl": None or float}.  gamma, truncs (host bool
         [E, T] or None): what the reward scaling pass in front of the finish call takes, read only with the setting on."""
         import torch
@@ -1446,16 +1483,20 @@ class RolloutBuffer:
         r = torch.from_numpy(self.rows.rewards).to(device)
         d = torch.from_numpy(self.rows.dones).to(device)
         u.f64 = torch.full((3, E, T), float("nan"), dtype=torch.float64, device=device)    # raw advantages, returns, normalised advantages (inspection)
+        u.f64_cur = u.f64                                                            # the triple of the epoch that runs: a refresh puts its own in its place
         if rs is not None:
             scaled = self._scale_rewards(u, rs, r, d, gamma, truncs)
             r = scaled[1]                                                            # what the finish call reads
         finish(u.st, r, d, u.lengths, u.f64)
         u.clock.lap("finish")
+        u.recompute = self._recompute_stage(u, finish, r, d) if getattr(self, "_adv_recompute", False) else None
         self.ppo.update_old_policy()
         logp_old = self._cache_logp_old(valid, klp is not None)
         u.clock.lap("logp_old")
         self._run_epochs(u, logp_old)
         out = self._result(u)
+        if u.recompute is not None:
+            self._recompute_result(u, out)
         if klp is not None:
             self._kl_penalty_result(u, out)
         if mbn is not None:
@@ -1482,6 +1523,9 @@ class RolloutBuffer:
         if klp is not None and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update: the KL penalty (PPO.set_kl_penalty) exists only in the fused kernels (this policy's shape is outside their range (more than 96 inputs: PPO.set_wide_inputs()) or "
                              "MI355_PPO_FUSED=0)")
+        if getattr(self, "_adv_recompute", False) and not self.ppo._need_dev().fused_ok():
+            raise ValueError(who + ".update: advantage recomputation (set_advantage_recomputation) exists only in the fused kernels (this policy's shape is outside the fused range (more than 96 inputs: PPO.set_wide_inputs()) or "
+                             "MI355_PPO_FUSED=0)")
         if diag is not None and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update_with_diagnostics: the statistics pass reads the cached log pi_old, which only the fused kernels fill "
                              "(this policy's shape is outside their range (more than 96 inputs: PPO.set_wide_inputs()) or MI355_PPO_FUSED=0)")
@@ -1492,6 +1536,47 @@ class RolloutBuffer:
         if self._reward_scaling is not None and not np.isfinite(self.rows.rewards[recorded]).all():
             raise ValueError(who + ".update: a recorded reward is not finite; it would poison the statistics of reward scaling for good")
         return recorded
+
+    def _recompute_rows(self, u):
+        """The table rows a refresh values: every recorded step and the bootstrap slot lengths[e] of every non-empty lane (int32, host)."""
+        lanes = np.nonzero(u.lengths > 0)[0]
+        return np.concatenate([u.valid, (self.rows._base[lanes] + u.lengths[lanes]).astype(np.int32)]).astype(np.int32)
+
+    def _recompute_extra(self, u):
+        """What a refresh does between its value pass and its finish call (ContinuousRolloutBuffer: the final observations of the truncated steps)."""
+
+    def _recompute_stage(self, u, finish, r, d):
+        """Advantage recomputation (set_advantage_recomputation) -> refresh(), which _run_epochs calls before every epoch but the first (stage "recompute", also part
+        of "sgd"; a KL stop ends the refreshes with the epochs).  A refresh is ONE mi_ppo_values_idx call -- the value net alone under the current parameters -- over
+        _recompute_rows() of `states` into `values_now`, and the update's finish call again with `values_now` in the place of `values`: the same rewards (scaled, with
+        reward scaling on), dones, lengths or segments, gamma, lam and normalisation.  It rewrites `returns` and `advantages`, which the steps gather from, and a second
+        fp64 triple, which per-minibatch normalisation then reads.  `values_now` starts every update as a copy of `values`; `values` is never written."""
+        import torch
+        pdev, device = self.ppo._need_dev(), self.device
+        if getattr(self, "values_now", None) is None:
+            self.values_now = torch.zeros(self.n_table_rows, device=device)
+        self.values_now.copy_(self.values)
+        rows = torch.from_numpy(self._recompute_rows(u)).to(device)
+        u.f64_now = torch.full((3, self.num_envs, self.horizon), float("nan"), dtype=torch.float64, device=device)
+        u.recomputed = 0
+
+        def refresh():
+            with u.clock.stage("recompute"):
+                pdev.values_idx(self.states, rows, int(rows.numel()), self.values_now)
+                self._recompute_extra(u)
+                finish(u.st, r, d, u.lengths, u.f64_now, now=True)
+                u.f64_cur = u.f64_now
+                u.recomputed += 1
+        return refresh
+
+    def _recompute_result(self, u, out):
+        out["recomputed_epochs"] = int(u.recomputed)
+        if not u.recomputed:
+            return
+        E, T = self.num_envs, self.horizon
+        f64 = u.f64_now.cpu().numpy()
+        out["refreshed_raw_advantages"], out["refreshed_returns"], out["refreshed_advantages"] = f64[0], f64[1], f64[2]
+        out["refreshed_values"] = np.where(u.recorded, self.values_now.view(E, T + 1)[:, :T].cpu().numpy(), np.float32(np.nan)).astype(np.float32)
 
     def _scale_rewards(self, u, rs, r, d, gamma, truncs):
         """The reward-scaling pass in front of the finish call (mi_rollout_scale_rewards) -> fp64 [2, E, T] on the device: discounted returns G, scaled rewards."""
@@ -1556,13 +1641,15 @@ class RolloutBuffer:
                 self._minibatch_advantages = torch.zeros(self.n_table_rows, device=device)
             adv_table = self._minibatch_advantages
             u.mb_stats = torch.zeros(u.num_epochs, -(-n_valid // batch_size), 3, dtype=torch.float64, device=device)
-        for _ in range(u.num_epochs):
+        for epoch in range(u.num_epochs):
+            if u.recompute is not None and epoch > 0:                                # every later epoch that runs: values, returns and advantages under the current parameters
+                u.recompute()
             indices = np.arange(n_valid)
             np.random.shuffle(indices)                                               # legacy numpy RNG, as train.py:194-195
             perm = torch.from_numpy(u.valid[indices]).to(device)                     # shuffled positions -> table rows
             if u.mbn is not None:                                                    # this epoch's minibatches, each normalised alone, from the raw advantages
                 with u.clock.stage("minibatch_norm"):
-                    self.L.mi_ppo_minibatch_advantages(u.st, u.f64[0].data_ptr(), perm.data_ptr(), n_valid, batch_size, self.num_envs, self.horizon, u.mbn["ddof"],
+                    self.L.mi_ppo_minibatch_advantages(u.st, u.f64_cur[0].data_ptr(), perm.data_ptr(), n_valid, batch_size, self.num_envs, self.horizon, u.mbn["ddof"],
                                                        adv_table.data_ptr(), u.mb_stats[u.mb_epochs].data_ptr())
                     u.mb_epochs += 1
             if u.demo is not None:                                                   # this epoch's demonstration rows, from the setting's own stream: one upload
@@ -1709,6 +1796,24 @@ class ContinuousRolloutBuffer(RolloutBuffer):
         import torch
         super()._init(vae, ppo, num_envs, horizon, seed, io, latent_stack)
         self.final_values = torch.zeros(self.n_table_rows, device=self.device)
+        # advantage recomputation (set_advantage_recomputation): the state rows of the final observations, the scratch tables the recording call fills beside them, and
+        # the refreshed final values -- allocated when the setting is turned on / by the first update that needs it
+        self.final_states = self._final_actions = self._final_raw_states = self.final_values_now = None
+
+    def set_advantage_recomputation(self, on=True):
+        """RolloutBuffer.set_advantage_recomputation.  With the setting on truncate() is a greedy recording call that keeps the final observation's state row in
+        `final_states` (at the truncated step's row, like `final_values`), and every refresh also values those rows into `final_values_now`, which its finish call
+        bootstraps the truncated segments from.  `final_values` stays the recorded table."""
+        import torch
+        super().set_advantage_recomputation(on)
+        if not self._adv_recompute:
+            self.final_states = self._final_actions = self._final_raw_states = self.final_values_now = None
+            return
+        if self.final_states is None:
+            n = self.n_table_rows
+            self.final_states = torch.zeros(n, int(self.ppo.input_dim), device=self.device)
+            self._final_actions = torch.zeros(n, int(self.ppo.num_actions), device=self.device)
+            self.final_values_now = torch.zeros(n, device=self.device)
 
     def bootstrap(self, frames_u8, measurements, env_ids=None):
         """RolloutBuffer.bootstrap; env_ids None: rows.needs_bootstrap() -- a lane whose last step reported done or was truncated needs none (given one, it is recorded and
@@ -1722,9 +1827,22 @@ class ContinuousRolloutBuffer(RolloutBuffer):
     def truncate(self, final_frames_u8, final_measurements, env_ids=None):
         """The episodes of these environments (None: 0 .. n-1) stopped at their last counted step WITHOUT being terminal, and their lanes go on with a reset observation:
         call it after outcome() (done False) and before these lanes' next step, with the final observation of the stopped episodes.  One value-only device call
-        (mi_rollout_value_batch_rec; with observation normalisation on, mi_rollout_value_batch_norm) leaves V(final observation) in final_values at the row of that step; update() bootstraps the segment from it.  -> float32 [n]."""
+        (mi_rollout_value_batch_rec; with observation normalisation on, mi_rollout_value_batch_norm) leaves V(final observation) in final_values at the row of that step; update() bootstraps the segment from it.  -> float32 [n].
+        With advantage recomputation on (set_advantage_recomputation) it is a greedy recording call instead (mi_rollout_step_batch_rec and its forms, as bootstrap():
+        the history is read and not advanced) that also keeps the state row, in `final_states` at the same row; the value it returns is the same quantity."""
         f, n, meas, _ = self._step.check(final_frames_u8, final_measurements, True, None)
         rows = self.rows.truncate_rows(env_ids, n)
+        if getattr(self, "_adv_recompute", False):
+            # advantage recomputation: a greedy recording call, as bootstrap() is -- the state row stays on the device (final_states) for the refreshes to value; the
+            # action it writes is never read, the history is read and not advanced
+            if self._obs_norm is not None and self._final_raw_states is None:
+                import torch
+                self._final_raw_states = torch.zeros(self.n_table_rows, int(self.ppo.input_dim), device=self.device)
+            values = self._step.record(f, n, meas, None, True, rows, self.final_states, self._final_actions, self.final_values, self._final_raw_states,
+                                       lanes=self._lanes(env_ids, n), advance=False)[1].astype(np.float32)
+            if self._stacked():
+                self._step.fresh[self.rows.env_ids(env_ids, n)] = True
+            return values
         if not self._stacked():
             return self._step.record_value(f, n, meas, rows, self.final_values)
         lanes = self.rows.env_ids(env_ids, n)                                        # latent stacking: the final observation is valued on the episode's history, the lane's next step starts afresh
@@ -1751,7 +1869,7 @@ class ContinuousRolloutBuffer(RolloutBuffer):
         truncs = self.rows.truncs.copy()
         seg_trunc = self.rows._truncated(segs)                                      # = segment_truncated(), from the one segments() walk
 
-        def finish(st, r, d, lengths, f64):
+        def finish(st, r, d, lengths, f64, now=False):
             import torch
             n_seg, T = int(segs.shape[0]), self.horizon
             desc = [segs[:, 0] * (T + 1) + segs[:, 1], segs[:, 2]]                   # table row of the first slot | length
@@ -1760,10 +1878,10 @@ class ContinuousRolloutBuffer(RolloutBuffer):
             desc = torch.from_numpy(np.stack(desc).astype(np.int32)).to(self.device)
             batch = normalize == "batch"
             scratch = torch.empty(int(self.L.mi_rollout_finish_segments_scratch_doubles(n_seg)), dtype=torch.float64, device=self.device) if batch else None
-            args = (st, self.values.data_ptr(), r.data_ptr(), d.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), n_seg, self.num_envs, T, float(gamma), float(lam),
+            args = (st, (self.values_now if now else self.values).data_ptr(), r.data_ptr(), d.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), n_seg, self.num_envs, T, float(gamma), float(lam),
                     1 if batch else 0, milib.ptr(scratch), self.returns.data_ptr(), self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
             if truncs.any():
-                self.L.mi_rollout_finish_segments_boot(*args, self.final_values.data_ptr(), desc[2].data_ptr())
+                self.L.mi_rollout_finish_segments_boot(*args, (self.final_values_now if now else self.final_values).data_ptr(), desc[2].data_ptr())
             else:
                 self.L.mi_rollout_finish_segments(*args)
         last_done = self.rows._last_done()
@@ -1774,7 +1892,28 @@ class ContinuousRolloutBuffer(RolloutBuffer):
         if truncs.any():
             final[truncs] = self.final_values.view(self.num_envs, self.horizon + 1)[:, :self.horizon].cpu().numpy()[truncs]
         out["final_values"] = final
+        if out.get("recomputed_epochs"):                                             # advantage recomputation: what the last refresh's truncated segments bootstrapped from
+            now = np.full(truncs.shape, np.nan, np.float32)
+            if truncs.any():
+                now[truncs] = self.final_values_now.view(self.num_envs, self.horizon + 1)[:, :self.horizon].cpu().numpy()[truncs]
+            out["refreshed_final_values"] = now
         return out
+
+    def _recompute_rows(self, u):
+        """RolloutBuffer._recompute_rows without the bootstrap slot of a lane whose last step reported done or was truncated: nothing behind it is read, and no
+        bootstrap() need have recorded a state there."""
+        lanes = np.nonzero((u.lengths > 0) & ~self.rows._last_done())[0]
+        return np.concatenate([u.valid, (self.rows._base[lanes] + u.lengths[lanes]).astype(np.int32)]).astype(np.int32)
+
+    def _recompute_extra(self, u):
+        """The truncated steps' final observations: one more mi_ppo_values_idx call, over `final_states` at the truncated rows into `final_values_now`."""
+        import torch
+        if getattr(u, "trunc_rows", None) is None:
+            e, t = np.nonzero(self.rows.truncs)
+            u.trunc_rows = torch.from_numpy((e * (self.horizon + 1) + t).astype(np.int32)).to(self.device)
+            self.final_values_now.copy_(self.final_values)
+        if int(u.trunc_rows.numel()):
+            self.ppo._need_dev().values_idx(self.final_states, u.trunc_rows, int(u.trunc_rows.numel()), self.final_values_now)
 
 
 class _DemonstrationStep(BatchedRolloutStep):

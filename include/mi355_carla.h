@@ -642,7 +642,7 @@ int mi_ppo_precision(void* h);
 /* wide inputs: which padded input widths kin = ceil(input_dim / 8) * 8 the fused kernels take -- ppo.py:16-66 with a VAE of more than 93 latents (train_vae.py
  * --z_dim 128: 131 inputs; ConvVAE's own default z_dim = 512: 515).
  *   mode 0 (the default of a new engine): kin <= 96, every launch as it always was; a wider policy runs the per-layer path, on which mi_ppo_train_step_idx,
- *          _vclip, _kl, mi_ppo_old_policy_cache, mi_ppo_logp_old, mi_ppo_update_stats_idx, mi_ppo_kl_stats_idx and MI_BF16X3 return MI_ERR_SHAPE;
+ *          _vclip, _kl, mi_ppo_old_policy_cache, mi_ppo_logp_old, mi_ppo_update_stats_idx, mi_ppo_kl_stats_idx, mi_ppo_values_idx and MI_BF16X3 return MI_ERR_SHAPE;
  *   mode 1: kin <= 1024; layer 1 of an engine with kin > 96 runs as ppo_l1_wide_kernel (the four waves of a block split K and meet in LDS in a fixed order: no
  *          atomics, two runs bitwise equal; a state entry at or past input_dim counts as 0.0 whatever the table holds there), every launch behind it is the one
  *          the narrow range takes; an engine with kin <= 96 takes the launches of mode 0 bit for bit;
@@ -769,6 +769,21 @@ int mi_ppo_old_policy_cache(void* h, void* stream, const float* states, const fl
 int mi_ppo_train_step_kl(void* h, void* comm, void* stream, const float* states, const float* actions, const float* returns, const float* advantage, const float* logp_old, const float* mean_old, float kl_coef, const float* old_values, float clip_range_vf, const int* row_idx, int n_rows, int M, float inv_m, float grad_scale, int adam, float alpha, float beta1, float beta2, float epsilon);
 long long mi_ppo_kl_stats_scratch_doubles(int M);
 int mi_ppo_kl_stats_idx(void* h, void* stream, const float* states, const float* mean_old, const int* row_idx, int n_rows, int M, int accumulate, double* scratch, double* stats);
+/* values of table rows: V(s) under the CURRENT theta for M rows of a state table of n_rows rows -- the forward-only value pass the rollout buffers recompute their
+ * advantages from before every later epoch of an update (Andrychowicz et al. 2021, "What Matters in On-Policy RL").  Only the value net runs: layers 1 - 2 of it
+ * (the narrow or the wide layer-1 form, as mi_ppo_set_wide_inputs selects; the engine's precision mode, as mi_ppo_update_stats_idx) and one value head kernel --
+ * three launches per chunk, no policy trunk, no reduction, no scratch, no atomics; two runs give bitwise equal tables.
+ * Sample m is row row_idx[m] (int32, device) of `states`, or row m with row_idx == NULL (then M <= n_rows).  Its value goes to values_out[row_idx[m]] (values_out[m]
+ * without a list): values_out is a table of n_rows floats laid out like the rollout buffers' other tables, and an entry no sample names is left alone.  A row that
+ * is negative or >= n_rows stores NOTHING (its loads are clamped into the table as in mi_ppo_train_step_idx; unlike mi_ppo_update_stats_idx, which clamps the store
+ * as well).  The stored value is bit for bit what value_out of mi_ppo_update_stats_idx holds for the same row and parameters.
+ * M may exceed the engine's max_batch: the entry walks chunks of max_batch rows itself (the last one partial), so a caller makes one call per table.
+ * NOT modified: parameters, theta_old, the optimiser state, the gradient buffer, the losses and action_mean buffers -- only the engine's activation workspace and
+ * values_out are written.  Like the other gathering entries layer 1 reads the first few state entries behind a named row against zero weights (narrow form): those
+ * must be finite.  Every refusal comes before the first launch and writes nothing; those that need no engine come first: MI_ERR_ARG: M < 1, n_rows < 1, states or
+ * values_out NULL, row_idx == NULL with M > n_rows; then MI_ERR_STATE: null handle; MI_ERR_SHAPE: mi_ppo_fused_shape_ok(h) is 0 (there is no per-layer form), or the
+ * 2 GiB limit stated at mi_ppo_set_wide_inputs. */
+int mi_ppo_values_idx(void* h, void* stream, const float* states, const int* row_idx, long long n_rows, long long M, float* values_out);
 /* behaviour cloning: one supervised step of the policy (and optionally the value net) on (state, expert action[, return]) rows -- the warm start from demonstrations
  * in front of PPO.  The fused chain of the minibatch step with a head / loss kernel of its own (csrc/ppo_fused.hip, ppo_head_clone_kernel); no old policy, no
  * advantage, no ratio, no clip, no entropy term.  Per sample m and action a, with t = tanh(u), mean = lo + (t + 1) / 2 (hi - lo), sigma = exp(logstd[a]),

@@ -24,7 +24,14 @@ mi_ppo_train_step_vclip calls.
     python tools/rollout_buffer_bench.py --minibatch-norm [--ddof 0] [--envs 1024] [--steps 128] [--batch 32,2048] [--epochs 3] ...
 
 runs the same update with RolloutBuffer.set_minibatch_normalization off and on in interleaved rounds, without the replay paths: the "minibatch_norm" stage (part of
-"sgd") is the cost of the one mi_ppo_minibatch_advantages call per epoch, and the line ends with the on / off ratio of the medians."""
+"sgd") is the cost of the one mi_ppo_minibatch_advantages call per epoch, and the line ends with the on / off ratio of the medians.
+
+    python tools/rollout_buffer_bench.py --recompute [--envs 64] [--steps 128] [--batch 32,2048] [--epochs 3] ...
+
+runs the same update (three epochs unless --epochs says otherwise) with RolloutBuffer.set_advantage_recomputation off and on in interleaved rounds, without the
+replay paths: the "recompute" stage (part of "sgd") is the cost of the refreshes -- one mi_ppo_values_idx call and one finish call before every epoch but the first
+-- printed per refresh beside the "sgd" stage per epoch.  Then the bare value pass over 1024 x 128 table rows (one mi_ppo_values_idx call) against
+mi_ppo_update_stats_idx with value_out and mi_ppo_kl_stats_idx over the same rows in chunks of 4096: one process, device events, three interleaved rounds."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
@@ -47,10 +54,13 @@ ap.add_argument("--no-box", action="store_true")
 ap.add_argument("--continuous", action="store_true", help="RolloutBuffer against ContinuousRolloutBuffer on one scripted set of simulators (no replay paths)")
 ap.add_argument("--diagnostics", action="store_true", help="RolloutBuffer.update against update_with_diagnostics in interleaved rounds (no replay paths)")
 ap.add_argument("--minibatch-norm", action="store_true", help="RolloutBuffer.update with per-minibatch advantage normalisation off and on in interleaved rounds (no replay paths)")
+ap.add_argument("--recompute", action="store_true", help="RolloutBuffer.update with advantage recomputation off and on in interleaved rounds, then the bare value pass (no replay paths)")
 ap.add_argument("--ddof", type=int, default=0, help="ddof of the normalised path of --minibatch-norm")
 ap.add_argument("--value-clip", type=float, default=0.2, help="eps_v of the value-clipped path of --diagnostics")
 ap.add_argument("--mean-episode", type=float, default=None, help="mean of the geometric episode lengths of --continuous (default: steps / 3)")
 args = ap.parse_args()
+if args.recompute and args.epochs == 1:
+    args.epochs = 3                                                                   # (the first epoch never refreshes)
 
 
 class Box:
@@ -134,13 +144,13 @@ if args.continuous:
 idx = rng.randint(0, args.pool, (E, T + 1))
 meas = np.stack([rng.uniform(-1, 1, (E, T + 1)), rng.uniform(0, 1, (E, T + 1)), rng.uniform(0, 30, (E, T + 1))], axis=-1).astype(np.float32)
 rewards, dones = rng.uniform(0, 1, (E, T)), np.zeros((E, T))
-frames_d = None if args.diagnostics or args.minibatch_norm else torch.from_numpy(pool).to("cuda")[torch.from_numpy(idx).to("cuda")]           # [E, T + 1, 80, 160, 3] uint8 in HBM
-frames_h = None if args.no_host_frames or args.diagnostics or args.minibatch_norm else pool[idx]
+frames_d = None if args.diagnostics or args.minibatch_norm or args.recompute else torch.from_numpy(pool).to("cuda")[torch.from_numpy(idx).to("cuda")]           # [E, T + 1, 80, 160, 3] uint8 in HBM
+frames_h = None if args.no_host_frames or args.diagnostics or args.minibatch_norm or args.recompute else pool[idx]
 
 buf = RolloutBuffer(vae, agent, E, T)
 
 
-def collect():
+def collect(buf=buf):
     buf.reset()
     acts = np.zeros((E, T, 2), np.float32)
     t0 = time.perf_counter()
@@ -156,6 +166,56 @@ actions, t_collect = collect()
 print("collection of %d x %d steps through the recording step: %.3f s (%.1f us per call incl. the host's frame gather)" % (E, T, t_collect, 1e6 * t_collect / (T + 1)), flush=True)
 
 
+buf_on = None
+if args.recompute:                                                                    # the setting is switched with no step recorded: a buffer of its own, the same collection
+    buf_on = RolloutBuffer(vae, agent, E, T)
+    buf_on.set_advantage_recomputation(True)
+    collect(buf_on)
+
+
+def value_pass_bench(rows_total=1024 * 128, rounds=3, passes=10, chunk=4096):
+    """The bare value pass against the two existing forward-only passes on the same table rows, interleaved: microseconds per pass over all rows (device events)."""
+    from mi355.ppo_device import N_KL_STATS, N_STATS
+    d, dev = agent.dev, agent.dev.device
+    g = torch.Generator(device="cpu").manual_seed(0)
+    S = (0.5 * torch.randn(rows_total, 67, generator=g)).to(dev)
+    Act, Ret, LP, MO = torch.zeros(rows_total, 2, device=dev), torch.zeros(rows_total, device=dev), torch.zeros(rows_total, device=dev), torch.zeros(rows_total, 2, device=dev)
+    rows = torch.randperm(rows_total, generator=g).to(torch.int32).to(dev)
+    V, V2 = torch.zeros(rows_total, device=dev), torch.zeros(rows_total, device=dev)
+    d.ensure_batch(chunk)
+    us, uscr = torch.zeros(N_STATS, dtype=torch.float64, device=dev), torch.zeros(d.stats_scratch_doubles(chunk), dtype=torch.float64, device=dev)
+    ks, kscr = torch.zeros(N_KL_STATS, dtype=torch.float64, device=dev), torch.zeros(d.kl_stats_scratch_doubles(chunk), dtype=torch.float64, device=dev)
+
+    def values():
+        d.values_idx(S, rows, rows_total, V)
+
+    def stats():
+        for lo in range(0, rows_total, chunk):
+            d.update_stats(S, Act, Ret, LP, rows[lo:lo + chunk], chunk, us, uscr, accumulate=lo > 0, value_out=V2)
+
+    def kl():
+        for lo in range(0, rows_total, chunk):
+            d.kl_stats(S, MO, rows[lo:lo + chunk], chunk, ks, kscr, accumulate=lo > 0)
+    fns = {"values_idx": values, "update_stats + value_out": stats, "kl_stats": kl}
+    for f in fns.values():
+        f()
+    torch.cuda.synchronize()
+    res = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, f in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(passes):
+                f()
+            b.record()
+            torch.cuda.synchronize()
+            res[k].append(1e3 * a.elapsed_time(b) / passes)
+    assert torch.equal(V.view(torch.int32), V2.view(torch.int32))                     # the two value tables hold the same bits
+    print("value pass over %d table rows (max_batch %d, %d passes per window, %d interleaved rounds), us per pass:" % (rows_total, d.max_batch, passes, rounds), flush=True)
+    for k, v in res.items():
+        print("  %-26s median %.1f  (rounds %s)" % (k, sorted(v)[len(v) // 2], "  ".join("%.1f" % x for x in v)), flush=True)
+
+
 def run(path, batch):
     st = {}
     torch.cuda.synchronize()
@@ -164,6 +224,8 @@ def run(path, batch):
         buf.update(num_epochs=args.epochs, batch_size=batch, stage_times=st)
     elif path == "buffer + diagnostics":
         buf.update_with_diagnostics(num_epochs=args.epochs, batch_size=batch, stage_times=st)
+    elif path == "+ recompute":
+        buf_on.update(num_epochs=args.epochs, batch_size=batch, stage_times=st)
     elif path == "+ minibatch norm":
         buf.set_minibatch_normalization(args.ddof)
         try:
@@ -187,6 +249,8 @@ if args.diagnostics:
     paths = ["buffer", "buffer + diagnostics", "+ value clip"]
 if args.minibatch_norm:
     paths = ["buffer", "+ minibatch norm"]
+if args.recompute:
+    paths = ["buffer", "+ recompute"]
 for batch in [int(x) for x in args.batch.split(",") if x]:
     for p in paths:
         run(p, batch)                                                                     # warm-up (engine growth, allocator)
@@ -199,13 +263,20 @@ for batch in [int(x) for x in args.batch.split(",") if x]:
         tot = sorted(r[0] for r in res[p])
         med = tot[len(tot) // 2]
         stages = next(r[1] for r in res[p] if r[0] == med)
-        front = sum(v for k, v in stages.items() if k not in ("sgd", "stats", "minibatch_norm"))
+        front = sum(v for k, v in stages.items() if k not in ("sgd", "stats", "minibatch_norm", "recompute"))
         print("  %-22s %.4f s (rounds %.4f - %.4f)  in front of the SGD loop %.4f s  | %s" % (p, med, tot[0], tot[-1], front, "  ".join("%s %.4f" % kv for kv in stages.items())), flush=True)
         if args.minibatch_norm:
             off = sorted(r[0] for r in res["buffer"])[args.rounds // 2]
             print("    every round: %s" % "  ".join("%.4f" % r[0] for r in res[p]) + ("" if "minibatch_norm" not in stages else
                   "   minibatch_norm stage %.6f s = %.1f us per epoch, %.3f %% of the update;  on / off %.4f" % (stages["minibatch_norm"], 1e6 * stages["minibatch_norm"] / max(args.epochs, 1),
                                                                                                                    100.0 * stages["minibatch_norm"] / med, med / off)), flush=True)
+        if args.recompute:
+            off = sorted(r[0] for r in res["buffer"])[args.rounds // 2]
+            print("    every round: %s   sgd stage %.4f s per epoch" % ("  ".join("%.4f" % r[0] for r in res[p]), stages["sgd"] / max(args.epochs, 1)) + ("" if "recompute" not in stages else
+                  "   recompute stage %.6f s = %.1f us per refresh (%d refreshes), %.3f %% of the update;  on / off %.4f"
+                  % (stages["recompute"], 1e6 * stages["recompute"] / max(args.epochs - 1, 1), max(args.epochs - 1, 0), 100.0 * stages["recompute"] / med, med / off)), flush=True)
         if args.diagnostics:
             print("    every round: %s" % "  ".join("%.4f" % r[0] for r in res[p]) + ("" if "stats" not in stages else
                   "   stats stage %.4f s = %.4f s per epoch, %.1f %% of the update" % (stages["stats"], stages["stats"] / max(args.epochs, 1), 100.0 * stages["stats"] / med)), flush=True)
+if args.recompute:
+    value_pass_bench()
