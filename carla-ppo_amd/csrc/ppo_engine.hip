@@ -615,6 +615,22 @@ int mi_ppo_values_idx(void* h, void* stream, const float* states, const int* row
     return mi_ppo_fused_values((hipStream_t)stream, q, row_idx, n_rows, M, values_out, x3(e));
 }
 
+// log pi_theta(a | s) of table rows under the CURRENT theta (include/mi355_carla.h): the policy net alone, forward only -- the twin of mi_ppo_values_idx, what the
+// rollout buffers form their V-trace importance weights from.  M may exceed max_batch (the chunk loop is mi_ppo_fused_logp's).  Nothing of the training state is written.
+int mi_ppo_logp_idx(void* h, void* stream, const float* states, const float* actions, const int* row_idx, long long n_rows, long long M, float* logp_out) {
+    // (what needs no engine is checked before the handle is looked at)
+    if (M < 1 || n_rows < 1) return mi_fail(MI_ERR_ARG, "mi_ppo_logp_idx: no rows (M < 1) or an empty table (n_rows < 1)");
+    if (!states) return mi_fail(MI_ERR_ARG, "mi_ppo_logp_idx: missing buffers (states)");
+    if (!actions) return mi_fail(MI_ERR_ARG, "mi_ppo_logp_idx: missing buffers (actions)");
+    if (!logp_out) return mi_fail(MI_ERR_ARG, "mi_ppo_logp_idx: missing buffers (logp_out)");
+    if (!row_idx && M > n_rows) return mi_fail(MI_ERR_ARG, "mi_ppo_logp_idx: without a row list the rows are 0 .. M - 1 of the table: M exceeds n_rows");
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_logp_idx: null handle");
+    if (!fused_enabled(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_logp_idx: needs the fused kernels (shape outside their range or MI355_PPO_FUSED=0)");
+    PpoFusedParams q; fill_fused(e, q, states, 1);
+    return mi_ppo_fused_logp((hipStream_t)stream, q, actions, row_idx, n_rows, M, logp_out, x3(e));
+}
+
 // precision of the engine's training forms (mi_ppo_train_step[_idx|_dp], the fused mi_ppo_forward_backward, mi_ppo_logp_old): MI_F32 (exact fp32, the default) or
 // MI_BF16X3 (split-bf16 GEMM stages, ppo_fused.hip).  MI_BF16 has no PPO form; the split form exists only as fused kernels, so an engine that runs the per-layer
 // path refuses it instead of training in fp32.  mi_ppo_predict and the rollout step stay exact fp32 in both modes.

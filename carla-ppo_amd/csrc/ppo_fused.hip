@@ -1031,6 +1031,32 @@ __global__ __launch_bounds__(256) void ppo_values_head_kernel(const PpoFusedPara
     values_out[row] = av + bv[0];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// log pi_theta(a | s) of table rows (mi_ppo_logp_idx): the policy head of the CURRENT parameters alone, on the trunk of net 0 -- the twin of ppo_values_head_kernel
+// for the policy side, and the log-probability path of ppo_update_stats_head_kernel without the value net, the double-precision terms and the reduction.  grid
+// ceil(M / 32) blocks; 8 threads per sample, that kernel's part / row split and, through pf_head_sums_strided / pf_mean_libm / pf_logp_term_libm and the serial sum
+// over a = 0, 1, .., its order of operations: the stored float is that kernel's logp_new_out bit for bit, and with theta == theta_old the cache of mi_ppo_logp_old
+// (the fifth contract: ppo_head.hpp).  Sample m is table row row_idx[m] (nullptr: m); q.actions is gathered by that row and the result goes to logp_out[that
+// row]; a row outside [0, n_rows) stores NOTHING (its loads are clamped, as layer 1 clamped the state's).  No LDS, no atomics, no reduction behind it.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int NA>
+__global__ __launch_bounds__(256) void ppo_logp_head_kernel(const PpoFusedParams q, float* __restrict__ logp_out) {
+    const int tid = threadIdx.x, m0 = blockIdx.x * 32, A = q.A, H2 = q.H2;
+    const int sm = tid >> 3, part = tid & 7, m = m0 + sm;
+    const float* Wm = q.theta + q.off[4]; const float* bm = q.theta + q.off[5]; const float* logstd = q.theta + q.off[6];
+    float au[NA], av;                                     // (av: no value net here)
+    pf_head_sums_strided<NA, 8>(q.h2 + (long long)m * H2, nullptr, Wm, nullptr, m < q.M, false, part, H2, A, au, av);
+    if (part != 0 || m >= q.M) return;
+    const int row = q.row_idx ? q.row_idx[m] : m;
+    const long long mr = min(max(row, 0), q.n_rows - 1);
+    float lp = 0.f;
+    _Pragma("unroll") for (int a = 0; a < NA; ++a) if (a < A) {
+        lp += pf_logp_term_libm(q.actions[mr * A + a], pf_mean_libm(au[a], bm[a], q.low[a], q.high[a]), logstd[a]);
+    }
+    if (row < 0 || row >= q.n_rows) return;
+    logp_out[row] = lp;
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -1137,6 +1163,31 @@ int mi_ppo_fused_values(hipStream_t st, const PpoFusedParams& q0, const int* row
         if (rc != MI_OK) return rc;
         hipLaunchKernelGGL(ppo_values_head_kernel, dim3((m + 31) / 32), dim3(256), 0, st, q, row_idx ? values_out : values_out + lo);
         const int rc2 = mi_check_launch("ppo_values_head");
+        if (rc2 != MI_OK) return rc2;
+    }
+    return MI_OK;
+}
+
+// log pi_theta(a | s) of M table rows under the current theta (mi_ppo_logp_idx): the policy net ALONE -- net 0 already, so the parameter block goes in as it is
+// with n_nets = 1.  mi_ppo_fused_values' chunk loop and row rules: chunks of max_batch rows, three launches each (row_idx given: the chunk's part of the list
+// against the whole tables; else the chunk's rows of states / actions / logp_out); the first chunk's check, before the first launch, is the call's.  Nothing but
+// the activation workspace and logp_out is written.
+int mi_ppo_fused_logp(hipStream_t st, const PpoFusedParams& q0, const float* actions, const int* row_idx, long long n_rows, long long M, float* logp_out, bool x3) {
+    PpoFusedParams q = q0;
+    q.n_nets = 1;                                         // (net 0: the policy)
+    q.s_gath = nullptr;                                   // (no filter gradient behind this pass)
+    const long long mb = q.max_batch;
+    const int n_rows_i = n_rows > 0x7fffffffll ? 0x7fffffff : (int)n_rows;
+    for (long long lo = 0; lo < M; lo += mb) {
+        const int m = (int)(M - lo < mb ? M - lo : mb);
+        q.M = m;
+        if (row_idx) { q.states = q0.states; q.actions = actions; q.row_idx = row_idx + lo; q.n_rows = n_rows_i; }
+        else { q.states = q0.states + lo * q.din; q.actions = actions + lo * q.A; q.row_idx = nullptr; q.n_rows = m; }
+        if (lo == 0) { const int rc0 = pf_check_shape(q, "ppo fused logp"); if (rc0 != MI_OK) return rc0; }
+        const int rc = mi_ppo_fused_trunks(st, q, x3);
+        if (rc != MI_OK) return rc;
+        hipLaunchKernelGGL(pf_na_pick(q.A, ppo_logp_head_kernel<2>, ppo_logp_head_kernel<PF_MAX_ACT>), dim3((m + 31) / 32), dim3(256), 0, st, q, row_idx ? logp_out : logp_out + lo);
+        const int rc2 = mi_check_launch("ppo_logp_head");
         if (rc2 != MI_OK) return rc2;
     }
     return MI_OK;

@@ -70,6 +70,8 @@ int mi_ppo_fused_logp_old(hipStream_t st, mi::PpoFusedParams& q, float* out, boo
 int mi_ppo_fused_kl_stats(hipStream_t st, mi::PpoFusedParams& q, int accumulate, double* scratch, double* stats, bool x3);
 // V(s) of M rows under the current theta, the value net alone; M may exceed q.max_batch (chunks).  q: fill_fused's block for the engine (states set, M ignored)
 int mi_ppo_fused_values(hipStream_t st, const mi::PpoFusedParams& q, const int* row_idx, long long n_rows, long long M, float* values_out, bool x3);
+// log pi_theta(a | s) of M rows under the current theta, the policy net alone; the same chunk loop and the same q
+int mi_ppo_fused_logp(hipStream_t st, const mi::PpoFusedParams& q, const float* actions, const int* row_idx, long long n_rows, long long M, float* logp_out, bool x3);
 int mi_ppo_fused_update_stats(hipStream_t st, mi::PpoFusedParams& q, int accumulate, double* scratch, double* stats, float* logp_new_out, float* value_out, bool x3);
 // internal accessors of the two engines for the rollout step (rollout path only)
 int mi_ppo_internal_fill(void* ppo_handle, mi::PpoFusedParams* q, const float* states, int M);

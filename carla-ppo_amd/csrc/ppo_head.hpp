@@ -8,7 +8,7 @@
 //   the strided form (columns j = part, part + TPS, .. straight from memory; libm):
 //     pf_head_sums_strided, pf_mean_libm, pf_logp_term_libm
 //         -> ppo_predict_head_kernel (4), ppo_update_stats_head_kernel (2), ppo_kl_stats_head_kernel (2), ppo_values_head_kernel (1: the value half of the sums
-//            alone); the two libm spellings also in the loss body's
+//            alone), ppo_logp_head_kernel (2: the policy half alone); the two libm spellings also in the loss body's
 //            old-policy block, whose sums stay there (from LDS, in the strided order)
 //     pf_ordered_block_sum, ppo_stats_reduce_kernel
 //         -> the two statistics kernels and the launch behind each
@@ -186,7 +186,11 @@ __device__ __forceinline__ void pf_head_dh2(const PpoFusedParams& q, const float
 // value_out stores for it under the same parameters, so a table refreshed by the one can stand where the other's stood.  Both call pf_head_sums_strided<., 8> with
 // val = true on the value net's h2 row -- the same columns in the same order, the same three shuffles -- and add bv[0] last; the h2 row is the same bits whichever
 // net slot the trunk kernels wrote it to.
-// They do because all four go through the three functions below and sum the actions' terms serially, a = 0, 1, ..: the columns j = part, part + 8, .. of the row
+// A fifth contract is on the LOG-PROBABILITY of the policy net run alone: ppo_logp_head_kernel (mi_ppo_logp_idx) stores for a row what
+// ppo_update_stats_head_kernel's logp_new_out stores for it under the same parameters, and with theta == theta_old what mi_ppo_logp_old cached -- so the V-trace
+// weight exp(lp_now - lp_old) of a policy that has not moved is exactly 1.  It calls pf_head_sums_strided<NA, 8> with val = false on net 0's h2 row (the policy
+// sums do not depend on val), then pf_mean_libm and pf_logp_term_libm, and sums the terms serially.
+// They do because all of them go through the three functions below and sum the actions' terms serially, a = 0, 1, ..: the columns j = part, part + 8, .. of the row
 // in ascending order (the loss body spells that loop itself, from LDS: the same values in the same order), the same shuffles, then libm tanhf / expf / logf. ----
 
 // au[a] = sum over this lane's columns j = part, part + TPS, .. of h2p[j] Wm[j, a] (with val: av likewise from h2v and Wv, else 0), then the xor shuffles over the

@@ -141,14 +141,16 @@ __device__ __forceinline__ double gae_step(double& carry, double delta, double g
 // SKIP_BEHIND_DONE: behind a terminal LAST step the bootstrap value is 0.0 and slot L is not read; without it slot L is read and the terminal flag masks it (the two
 // differ in the sign of a zero and in what a NaN in slot L does).  FINAL with v_final != NULL (a TRUNCATED segment: the episode stopped without being terminal): the
 // value behind the last step is *v_final and slot L is not read; the terminal flag of the last step masks it as it masks slot L.
+// (the successor-value rule is gae_vnext, written once: the V-trace finish kernel forms its deltas by it too)
+template <bool SKIP_BEHIND_DONE, bool FINAL>
+__device__ __forceinline__ double gae_vnext(const float* v, const double* d, int t, int L, const float* v_final) {
+    if (FINAL && v_final && t == L - 1) return (double)v_final[0];
+    if (!SKIP_BEHIND_DONE || t < L - 1 || d[t] == 0.0) return (double)v[t + 1];
+    return 0.0;
+}
 template <bool SKIP_BEHIND_DONE, bool FINAL = false>
 __device__ __forceinline__ void finish_gae(double* a, const float* v, const double* r, const double* d, int L, double gamma, double gl, int lane, const float* v_final = nullptr) {
-    for (int t = lane; t < L; t += WAVE) {
-        double vnext = 0.0;
-        if (FINAL && v_final && t == L - 1) vnext = (double)v_final[0];
-        else if (!SKIP_BEHIND_DONE || t < L - 1 || d[t] == 0.0) vnext = (double)v[t + 1];
-        a[t] = gae_delta(r[t], d[t], vnext, (double)v[t], gamma);
-    }
+    for (int t = lane; t < L; t += WAVE) a[t] = gae_delta(r[t], d[t], gae_vnext<SKIP_BEHIND_DONE, FINAL>(v, d, t, L, v_final), (double)v[t], gamma);
     __syncthreads();
     if (lane == 0) {
         double carry = 0.0;
@@ -159,13 +161,15 @@ __device__ __forceinline__ void finish_gae(double* a, const float* v, const doub
 
 // returns = A + V into the fp32 table (f64 -> f32 at the feed, ppo.py:108-109, round to nearest even) and the optional fp64 outputs; -> the wave's sum of A.
 // tab / flat: the first step's position in the [num_envs (T + 1)] tables and in the [num_envs, T] arrays.  RAW_ALWAYS: adv_raw is not optional.
+// dret: what the value is added to for the return -- the advantages themselves (nullptr: GAE), or the V-trace kernel's vs - V.
 template <bool RAW_ALWAYS>
 __device__ __forceinline__ double finish_returns(const double* a, const float* v, int L, int lane, long long tab, long long flat, float* tab_returns, double* returns,
-                                                 double* adv_raw) {
+                                                 double* adv_raw, const double* dret = nullptr) {
+    if (!dret) dret = a;
     double s = 0.0;
     for (int t = lane; t < L; t += WAVE) {
         s += a[t];
-        const double ret = a[t] + (double)v[t];
+        const double ret = dret[t] + (double)v[t];
         tab_returns[tab + t] = (float)ret;
         if (returns) returns[flat + t] = ret;
         if (RAW_ALWAYS || adv_raw) adv_raw[flat + t] = a[t];
@@ -359,6 +363,69 @@ __global__ __launch_bounds__(64) void rollout_seg_norm_kernel(const double* __re
     } else {
         store_normalized(a, mean, stat[1], L, lane, tab, flat, tab_adv, adv_norm);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// mi_rollout_finish_vtrace: the finish of rollout_finish_seg_kernel / rollout_finish_seg_boot_kernel with V-trace's truncated importance weights (Espeholt et al.
+// 2018) on the recurrence.  One wave (= one block) per segment; the dynamic LDS holds two arrays of T doubles.  All lanes form, for t < L, the delta of step t --
+// gae_delta on the successor value of gae_vnext: READ_BEHIND = true is mi_rollout_finish's rule (the slot behind a terminal last step is read and masked), false the
+// segment kernels' (0.0 there, the slot is not read); a truncated segment (seg_boot) takes final_values under either -- and the weight
+// w_t = exp((double)lp_now[t] - (double)lp_old[t]).  Lane 0 walks t = L - 1 .. 0 with Dn = 0.0, explicit roundings, no fma:
+//     cw = min(c_bar, w_t), rw = min(rho_bar, w_t)          (as w > bar ? bar : w: a NaN weight is not masked)
+//     A_t = gl Dn + delta_t                                  the policy advantage delta_t + gamma lam (vs_{t+1} - V_{t+1})
+//     D_t = (gl cw) Dn + rw delta_t                          vs_t - V_t;  Dn = D_t
+// and the returns are D_t + V_t, the V-trace value target.  The weight of step t does not multiply A_t: PPO's surrogate applies the ratio itself.  As in the GAE
+// kernels the recurrence is not cut at a terminal inside a segment: segments end at their terminal.
+// THE GAE IDENTITY: with w_t = 1 and both bars >= 1, cw = rw = 1.0 and every product with them is exact, so D_t = A_t = gl A_{t+1} + delta_t in gae_step's
+// roundings: the kernel stores what the GAE kernel of the same successor rule stores, bit for bit.  The sums, the returns and the normalisation are the helpers'.
+// ---------------------------------------------------------------------------------------------------
+template <int NORM, bool READ_BEHIND>
+__global__ __launch_bounds__(64) void rollout_finish_vtrace_kernel(const float* __restrict__ values, const float* __restrict__ lp_now, const float* __restrict__ lp_old,
+                                                                   const float* __restrict__ final_values, const double* __restrict__ rewards,
+                                                                   const double* __restrict__ terminals, const int* __restrict__ seg_row, const int* __restrict__ seg_len,
+                                                                   const int* __restrict__ seg_boot, int num_envs, int T, double gamma, double gl, double rho_bar, double c_bar,
+                                                                   float* __restrict__ tab_returns, float* __restrict__ tab_adv, double* __restrict__ adv_raw,
+                                                                   double* __restrict__ returns, double* __restrict__ adv_norm, double* __restrict__ weights_out,
+                                                                   double* __restrict__ part) {
+    extern __shared__ double seg_vt[];                     // 2 T doubles: delta -> A | w -> D
+    double* a = seg_vt;
+    double* w = seg_vt + T;
+    const int seg = blockIdx.x, lane = threadIdx.x;
+    const int L = seg_len[seg];
+    const long long tab = seg_row[seg];
+    long long flat;
+    if (!rollout_seg_decode((int)tab, L, num_envs, T, flat)) {
+        if (NORM && lane == 0) part[seg] = 0.0;            // adds nothing to the batch sum
+        return;
+    }
+    const float* v = values + tab;
+    const double* r = rewards + flat; const double* d = terminals + flat;
+    const float* v_final = (seg_boot && seg_boot[seg] != 0) ? final_values + tab + (L - 1) : nullptr;
+    for (int t = lane; t < L; t += WAVE) {
+        a[t] = gae_delta(r[t], d[t], gae_vnext<!READ_BEHIND, true>(v, d, t, L, v_final), (double)v[t], gamma);
+        const double wt = exp((double)lp_now[tab + t] - (double)lp_old[tab + t]);
+        w[t] = wt;
+        if (weights_out) weights_out[flat + t] = wt;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        double Dn = 0.0;
+        for (int t = L - 1; t >= 0; --t) {
+            const double wt = w[t], delta = a[t];
+            const double cw = wt > c_bar ? c_bar : wt;
+            const double rw = wt > rho_bar ? rho_bar : wt;
+            a[t] = __dadd_rn(__dmul_rn(gl, Dn), delta);
+            Dn = __dadd_rn(__dmul_rn(__dmul_rn(gl, cw), Dn), __dmul_rn(rw, delta));
+            w[t] = Dn;
+        }
+    }
+    __syncthreads();
+    const double s = finish_returns<NORM != 0>(a, v, L, lane, tab, flat, tab_returns, returns, adv_raw, w);
+    if (NORM) {
+        if (lane == 0) part[seg] = s;
+        return;
+    }
+    finish_normalize(a, s, L, lane, tab, flat, tab_adv, adv_norm);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -845,6 +912,44 @@ int mi_rollout_finish_segments_boot(void* stream, const float* tab_values, const
     return finish_segments(true, stream, tab_values, rewards, terminals, seg_row, seg_len, n_seg, num_envs, T, gamma, lam, normalize, scratch, tab_returns, tab_advantages,
                            adv_raw, returns, adv_norm, tab_final_values, seg_boot);
 }
+
+// The V-trace finish (include/mi355_carla.h): rollout_finish_vtrace_kernel, and with normalize = 1 the four launches of the batch normalisation behind it.
+// tab_logp_now / tab_logp_old fp32 [num_envs (T + 1)]; tab_final_values / seg_boot both or neither; weights_out fp64 [num_envs, T] or NULL.  Every check runs
+// before the first launch.
+#define VT_FAIL(text) return mi_fail(MI_ERR_ARG, "mi_rollout_finish_vtrace: " text)
+int mi_rollout_finish_vtrace(void* stream, const float* tab_values, const float* tab_logp_now, const float* tab_logp_old, const double* rewards, const double* terminals,
+                             const int* seg_row, const int* seg_len, int n_seg, int num_envs, int T, double gamma, double lam, double rho_bar, double c_bar,
+                             int read_behind_done, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw, double* returns,
+                             double* adv_norm, double* weights_out, const float* tab_final_values, const int* seg_boot) {
+    if (!tab_values || !tab_logp_now || !tab_logp_old || !rewards || !terminals || !seg_row || !seg_len || !tab_returns || !tab_advantages) VT_FAIL("missing buffers");
+    if ((tab_final_values != nullptr) != (seg_boot != nullptr)) VT_FAIL("tab_final_values and seg_boot come together or are both NULL");
+    if (n_seg < 1 || num_envs < 1 || T < 1) VT_FAIL("empty input (n_seg >= 1, num_envs >= 1, T >= 1)");
+    if (T > MI_ROLLOUT_MAX_HORIZON) VT_FAIL("the horizon exceeds MI_ROLLOUT_MAX_HORIZON");
+    if (!(rho_bar > 0.0)) VT_FAIL("rho_bar is a positive value (+inf: never truncates)");
+    if (!(c_bar >= 0.0)) VT_FAIL("c_bar is a value >= 0 (+inf: never truncates)");
+    if (read_behind_done != 0 && read_behind_done != 1) VT_FAIL("read_behind_done is 0 (the segment kernels' successor rule) or 1 (mi_rollout_finish's)");
+    if (normalize != 0 && normalize != 1) VT_FAIL("normalize is 0 (per segment) or 1 (per batch)");
+    if (normalize == 1 && (!scratch || !adv_raw)) VT_FAIL("normalize = 1 needs scratch and adv_raw (missing buffers)");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = 2 * (size_t)T * sizeof(double);
+    const double gl = gamma * lam;
+    double* part = normalize ? scratch : nullptr;
+#define VT_LAUNCH(NORM, RB) hipLaunchKernelGGL((rollout_finish_vtrace_kernel<NORM, RB>), dim3(n_seg), dim3(64), lds, st, tab_values, tab_logp_now, tab_logp_old, \
+        tab_final_values, rewards, terminals, seg_row, seg_len, seg_boot, num_envs, T, gamma, gl, rho_bar, c_bar, tab_returns, tab_advantages, adv_raw, returns, adv_norm, \
+        weights_out, part)
+    if (normalize == 0) { if (read_behind_done) VT_LAUNCH(0, true); else VT_LAUNCH(0, false); }
+    else { if (read_behind_done) VT_LAUNCH(1, true); else VT_LAUNCH(1, false); }
+#undef VT_LAUNCH
+    if (normalize == 0) return mi_check_launch("rollout_finish_vtrace");
+    double* part2 = scratch + n_seg;
+    double* stat = scratch + 2LL * n_seg;
+    hipLaunchKernelGGL(rollout_seg_reduce_kernel<0>, dim3(1), dim3(64), 0, st, part, seg_row, seg_len, n_seg, num_envs, T, stat);
+    hipLaunchKernelGGL(rollout_seg_norm_kernel<0>, dim3(n_seg), dim3(64), 0, st, adv_raw, seg_row, seg_len, num_envs, T, stat, part2, tab_advantages, adv_norm);
+    hipLaunchKernelGGL(rollout_seg_reduce_kernel<1>, dim3(1), dim3(64), 0, st, part2, seg_row, seg_len, n_seg, num_envs, T, stat);
+    hipLaunchKernelGGL(rollout_seg_norm_kernel<1>, dim3(n_seg), dim3(64), 0, st, adv_raw, seg_row, seg_len, num_envs, T, stat, part2, tab_advantages, adv_norm);
+    return mi_check_launch("rollout_finish_vtrace (batch normalisation)");
+}
+#undef VT_FAIL
 
 // scratch: per-lane sums of G | per-lane sums of squared deviations | n_b, m_b
 long long mi_rollout_scale_rewards_scratch_doubles(int num_envs) { return num_envs < 1 ? -1 : 2LL * num_envs + 2; }

@@ -399,6 +399,19 @@ class PpoDevice:
         p = milib.ptr
         self.L.mi_ppo_values_idx(self.handle, self.stream(), p(states), p(row_idx), int(states.shape[0]), int(M), p(out))
 
+    def logp_idx(self, states, actions, row_idx, M, out):
+        """log pi_theta(a | s) under the CURRENT parameters of M rows of the tables `states` [n_rows, input_dim] / `actions` [n_rows, num_actions]
+        (mi_ppo_logp_idx): the policy net alone, forward only -- the twin of values_idx.  row_idx: an int32 device tensor [M] naming table rows, or None (rows
+        0 .. M-1).  The result of a row goes to the entry of `out` (float32 device tensor, n_rows entries) with that row's number; a row outside [0, n_rows) stores
+        nothing, and entries no row names keep their contents.  M may exceed max_batch: the entry walks the chunks itself and the engine is NOT grown.  Bit for
+        bit the logp_new_out table of update_stats, and right behind update_old_policy() the cache of logp_old.  Nothing of the training state is written."""
+        if int(out.shape[0]) < int(states.shape[0]):
+            raise ValueError("PpoDevice.logp_idx: `out` has %d entries for a table of %d rows" % (int(out.shape[0]), int(states.shape[0])))
+        if int(actions.shape[0]) < int(states.shape[0]):
+            raise ValueError("PpoDevice.logp_idx: `actions` has %d rows for a table of %d rows" % (int(actions.shape[0]), int(states.shape[0])))
+        p = milib.ptr
+        self.L.mi_ppo_logp_idx(self.handle, self.stream(), p(states), p(actions), p(row_idx), int(states.shape[0]), int(M), p(out))
+
     def stats_scratch_doubles(self, M):
         return int(self.L.mi_ppo_update_stats_scratch_doubles(int(M)))
 

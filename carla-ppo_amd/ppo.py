@@ -633,6 +633,29 @@ class PPO():
             dev.predict(s, n, None, True, torch.empty(n, self.num_actions, device=dev.device), value)
         return value.cpu().numpy()
 
+    def log_probs(self, input_states, taken_actions):
+        """log pi_theta(a | s) under the current parameters -> float32 [n].  input_states: host array or device tensor [n, input_dim], taken_actions likewise
+        [n, num_actions] (one state / action counts as n = 1; the result is still [1]).  One forward-only pass of the policy net alone (mi_ppo_logp_idx, in the
+        engine's precision mode, any n); it needs the fused kernels (PpoDevice.fused_ok()): there is no per-layer form, and without them the call raises."""
+        import torch
+        dev = self._need_dev()
+
+        def dev_rows(x, width):
+            if isinstance(x, torch.Tensor):
+                return x.to(device=dev.device, dtype=torch.float32).reshape(-1, width).contiguous()
+            a = np.asarray(x)
+            return self._to_dev(a, (1 if a.ndim == 1 else len(a), width))
+        s = dev_rows(input_states, self.input_dim)
+        a = dev_rows(taken_actions, self.num_actions)
+        n = int(s.shape[0])
+        if n < 1:
+            raise ValueError("PPO.log_probs: no states")
+        if int(a.shape[0]) != n:
+            raise ValueError("PPO.log_probs: %d states and %d actions" % (n, int(a.shape[0])))
+        logp = torch.empty(n, device=dev.device)
+        dev.logp_idx(s, a, None, n, logp)
+        return logp.cpu().numpy()
+
     def get_episode_idx(self):
         return int(self.episode_counter)
 

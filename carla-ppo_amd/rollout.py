@@ -282,8 +282,20 @@ result are the first finish call's.  New keys: `recomputed_epochs`, and when a r
 a greedy recording call that keeps the final observation's state row in `final_states`; every refresh values those rows into `final_values_now`, from which the
 truncated segments then bootstrap; `final_values` stays the recorded table and the result gains `refreshed_final_values`.  Needs the fused kernels; switched only
 with no step recorded.  With the setting off no table is allocated and every call makes the launches it always made.
+
+RolloutBuffer.set_vtrace(rho_bar=1.0, c_bar=1.0) puts V-TRACE OFF-POLICY CORRECTION on those refreshes (Espeholt et al. 2018, IMPALA): by epoch 2 the policy has moved
+away from the one that drew the recorded actions, and plain GAE on the refreshed values estimates the wrong quantity.  With it on a refresh is the values_idx call, ONE
+mi_ppo_logp_idx call (the policy net alone, forward only) over the recorded rows of `states` / `actions` into a table `logp_now`, and mi_rollout_finish_vtrace on
+`values_now`, `logp_now` and the update's cache of log pi_old in the place of the GAE finish call: w = exp(logp_now - logp_old) per step, min(rho_bar, w) on the TD errors
+and lam min(c_bar, w) on the trace; the returns are the V-trace value targets and the advantages delta_t + gamma lam (vs_{t+1} - V_{t+1}), normalised as the update
+normalises.  Same rewards, dones, segments, gamma, lam and truncation source as the GAE refresh; RolloutBuffer keeps mi_rollout_finish's successor-value rule,
+ContinuousRolloutBuffer the segment kernels'.  The first finish call stays the GAE call (theta == theta_old there and V-trace equals it bit for bit), the SGD steps still
+read the collection-time cache of log pi_old.  New keys, from the last refresh that ran: `refreshed_importance_weights` (fp64 [num_envs, T], NaN beyond a lane's length),
+`vtrace_rho_clip_fraction` and `vtrace_c_clip_fraction` (the share of recorded steps whose weight exceeds the bar).  update() refuses V-trace without advantage
+recomputation or without the fused kernels; set_vtrace(None) turns it off, bitwise a buffer that never had it.
 """
 import contextlib
+import numbers
 import os
 import time
 import types
@@ -914,6 +926,18 @@ def minibatch_normalization_ddof(ddof=0, who="RolloutBuffer.set_minibatch_normal
     return int(ddof)
 
 
+def vtrace_settings(rho_bar=1.0, c_bar=1.0, who="RolloutBuffer.set_vtrace"):
+    """The checked bars of V-trace (mi_rollout_finish_vtrace) -> {"rho_bar": float, "c_bar": float}.  rho_bar: a float > 0, c_bar: a float >= 0; +inf is a valid
+    bar (it never truncates).  bool, str, NaN and every other value raise ValueError.  numpy only: no device and no library involved."""
+    def real(x):
+        return not isinstance(x, (bool, np.bool_, str)) and isinstance(x, (numbers.Real, np.floating, np.integer))
+    if not real(rho_bar) or not float(rho_bar) > 0.0:
+        raise ValueError("%s: rho_bar is a float > 0 (inf: the TD errors' weights are never truncated), got %r" % (who, rho_bar))
+    if not real(c_bar) or not float(c_bar) >= 0.0:
+        raise ValueError("%s: c_bar is a float >= 0 (inf: the trace's weights are never truncated), got %r" % (who, c_bar))
+    return {"rho_bar": float(rho_bar), "c_bar": float(c_bar)}
+
+
 def observation_normalization_settings(clip=10.0, epsilon=1e-8, frozen=False, normalize_latents=True, who="RolloutBuffer.set_observation_normalization"):
     """The checked settings of running observation normalisation (mi_rollout_step_batch_norm / mi_rollout_obs_stats) -> {"clip": float, "epsilon": float, "frozen":
     bool, "normalize_latents": bool}.  clip: a positive float (inf: never clamp); epsilon: a finite float >= 0; frozen, normalize_latents: bools.  Anything else raises
@@ -1081,6 +1105,8 @@ class RolloutBuffer:
         self._demo = None                                                            # the demonstration term (set_demonstrations): None = off
         self._adv_recompute = False                                                  # advantage recomputation before every later epoch (set_advantage_recomputation)
         self.values_now = None                                                       # its fp32 table: V per table row under the current parameters, allocated by the first update that needs it
+        self._vtrace = None                                                          # V-trace correction of the refreshes (set_vtrace): None = off
+        self.logp_now = None                                                         # its fp32 table: log pi_theta per table row under the current parameters, allocated likewise
 
     def set_observation_normalization(self, clip=10.0, epsilon=1e-8, frozen=False, normalize_latents=True):
         """Turns running observation normalisation on (see the module docstring): step(), bootstrap() and truncate() feed the trunks clamp((s - mean) * inv_std, +-clip)
@@ -1237,6 +1263,18 @@ class RolloutBuffer:
         self._adv_recompute = bool(on)
         if not self._adv_recompute:
             self.values_now = None
+
+    def set_vtrace(self, rho_bar=1.0, c_bar=1.0):
+        """Turns V-trace off-policy correction of the refreshes on (Espeholt et al. 2018): with advantage recomputation on, every refresh also runs ONE
+        mi_ppo_logp_idx call -- log pi_theta of the recorded rows under the current parameters -- and its finish call is mi_rollout_finish_vtrace on the refreshed
+        values, that table and the update's cache of log pi_old: truncated importance weights min(rho_bar, pi_theta / pi_old) on the TD errors and
+        lam min(c_bar, pi_theta / pi_old) on the trace.  The first finish call stays the GAE call (theta == theta_old there: V-trace equals it), so one epoch is bitwise
+        the setting off; the SGD steps still take log pi_old from the cache.  rho_bar: a float > 0, c_bar: a float >= 0 (inf: that bar never truncates).
+        set_vtrace(None) turns it off and drops the table.  update() refuses V-trace without advantage recomputation.  ValueError before anything changes."""
+        if rho_bar is None:
+            self._vtrace = self.logp_now = None
+            return
+        self._vtrace = vtrace_settings(rho_bar, c_bar, type(self).__name__ + ".set_vtrace")
 
     def set_minibatch_normalization(self, ddof=0):
         """Turns per-minibatch advantage normalisation on (see the module docstring): in front of every epoch one mi_ppo_minibatch_advantages call normalises the raw
@@ -1453,8 +1491,16 @@ class RolloutBuffer:
         return self._run_update(gamma, lam, num_epochs, batch_size, stage_times, _diagnostics(type(self).__name__, target_kl))
 
     def _run_update(self, gamma, lam, num_epochs, batch_size, stage_times, diag):
-        def finish(st, r, d, lengths, f64, now=False):
+        def finish(st, r, d, lengths, f64, now=False, vt=None):
             import torch
+            if vt is not None:                                                       # a V-trace refresh: one segment per non-empty lane (slot 0, its length), mi_rollout_finish's successor rule
+                lanes = np.nonzero(lengths > 0)[0]
+                desc = torch.from_numpy(np.stack([lanes * (self.horizon + 1), np.minimum(lengths[lanes], self.horizon)]).astype(np.int32)).to(self.device)
+                self.L.mi_rollout_finish_vtrace(st, self.values_now.data_ptr(), vt["logp_now"].data_ptr(), vt["logp_old"].data_ptr(), r.data_ptr(), d.data_ptr(), desc[0].data_ptr(),
+                                                desc[1].data_ptr(), int(lanes.shape[0]), self.num_envs, self.horizon, float(gamma), float(lam), vt["rho_bar"], vt["c_bar"], 1, 0,
+                                                None, self.returns.data_ptr(), self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr(),
+                                                vt["weights"].data_ptr(), None, None)
+                return
             ln = torch.from_numpy(lengths).to(self.device)
             self.L.mi_rollout_finish(st, (self.values_now if now else self.values).data_ptr(), r.data_ptr(), d.data_ptr(), ln.data_ptr(), self.num_envs, self.horizon, float(gamma), float(lam),
                                      self.returns.data_ptr(), self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
@@ -1492,6 +1538,7 @@ class RolloutBuffer:
         u.recompute = self._recompute_stage(u, finish, r, d) if getattr(self, "_adv_recompute", False) else None
         self.ppo.update_old_policy()
         logp_old = self._cache_logp_old(valid, klp is not None)
+        u.logp_old = logp_old                                                        # (a V-trace refresh reads the cache as well: its closure was made in front of this stage)
         u.clock.lap("logp_old")
         self._run_epochs(u, logp_old)
         out = self._result(u)
@@ -1526,6 +1573,12 @@ class RolloutBuffer:
         if getattr(self, "_adv_recompute", False) and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update: advantage recomputation (set_advantage_recomputation) exists only in the fused kernels (this policy's shape is outside the fused range (more than 96 inputs: PPO.set_wide_inputs()) or "
                              "MI355_PPO_FUSED=0)")
+        if getattr(self, "_vtrace", None) is not None:
+            if not getattr(self, "_adv_recompute", False):
+                raise ValueError(who + ".update: V-trace (set_vtrace) corrects the refreshes of advantage recomputation, which is off (set_advantage_recomputation)")
+            if not self.ppo._need_dev().fused_ok():
+                raise ValueError(who + ".update: V-trace (set_vtrace) exists only in the fused kernels (this policy's shape is outside the fused range (more than 96 inputs: PPO.set_wide_inputs()) or "
+                                 "MI355_PPO_FUSED=0)")
         if diag is not None and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update_with_diagnostics: the statistics pass reads the cached log pi_old, which only the fused kernels fill "
                              "(this policy's shape is outside their range (more than 96 inputs: PPO.set_wide_inputs()) or MI355_PPO_FUSED=0)")
@@ -1560,11 +1613,26 @@ class RolloutBuffer:
         u.f64_now = torch.full((3, self.num_envs, self.horizon), float("nan"), dtype=torch.float64, device=device)
         u.recomputed = 0
 
+        vtrace = getattr(self, "_vtrace", None)                                      # V-trace off-policy correction of the refreshes (set_vtrace): None = off
+        if vtrace is not None:
+            # log pi_theta of the recorded rows under the current parameters, and the weights exp(log pi_theta - log pi_old) the last refresh formed.  The cache
+            # of log pi_old is filled behind this stage: refresh() takes it from u.logp_old
+            valid_dev = torch.from_numpy(u.valid).to(device)
+            if getattr(self, "logp_now", None) is None:
+                self.logp_now = torch.zeros(self.n_table_rows, device=device)
+            u.vt_weights = torch.full((self.num_envs, self.horizon), float("nan"), dtype=torch.float64, device=device)
+
         def refresh():
             with u.clock.stage("recompute"):
                 pdev.values_idx(self.states, rows, int(rows.numel()), self.values_now)
-                self._recompute_extra(u)
-                finish(u.st, r, d, u.lengths, u.f64_now, now=True)
+                if vtrace is None:
+                    self._recompute_extra(u)
+                    finish(u.st, r, d, u.lengths, u.f64_now, now=True)
+                else:
+                    pdev.logp_idx(self.states, self.actions, valid_dev, int(valid_dev.numel()), self.logp_now)
+                    self._recompute_extra(u)
+                    finish(u.st, r, d, u.lengths, u.f64_now, now=True, vt={"rho_bar": vtrace["rho_bar"], "c_bar": vtrace["c_bar"], "logp_now": self.logp_now,
+                                                                           "logp_old": u.logp_old, "weights": u.vt_weights})
                 u.f64_cur = u.f64_now
                 u.recomputed += 1
         return refresh
@@ -1577,6 +1645,12 @@ class RolloutBuffer:
         f64 = u.f64_now.cpu().numpy()
         out["refreshed_raw_advantages"], out["refreshed_returns"], out["refreshed_advantages"] = f64[0], f64[1], f64[2]
         out["refreshed_values"] = np.where(u.recorded, self.values_now.view(E, T + 1)[:, :T].cpu().numpy(), np.float32(np.nan)).astype(np.float32)
+        vtrace = getattr(self, "_vtrace", None)
+        if vtrace is not None:                                                       # the last refresh's importance weights, and how many of them each bar truncated
+            w = u.vt_weights.cpu().numpy()
+            out["refreshed_importance_weights"] = w
+            out["vtrace_rho_clip_fraction"] = float((w[u.recorded] > vtrace["rho_bar"]).mean())
+            out["vtrace_c_clip_fraction"] = float((w[u.recorded] > vtrace["c_bar"]).mean())
 
     def _scale_rewards(self, u, rs, r, d, gamma, truncs):
         """The reward-scaling pass in front of the finish call (mi_rollout_scale_rewards) -> fp64 [2, E, T] on the device: discounted returns G, scaled rewards."""
@@ -1869,7 +1943,7 @@ class ContinuousRolloutBuffer(RolloutBuffer):
         truncs = self.rows.truncs.copy()
         seg_trunc = self.rows._truncated(segs)                                      # = segment_truncated(), from the one segments() walk
 
-        def finish(st, r, d, lengths, f64, now=False):
+        def finish(st, r, d, lengths, f64, now=False, vt=None):
             import torch
             n_seg, T = int(segs.shape[0]), self.horizon
             desc = [segs[:, 0] * (T + 1) + segs[:, 1], segs[:, 2]]                   # table row of the first slot | length
@@ -1880,7 +1954,11 @@ class ContinuousRolloutBuffer(RolloutBuffer):
             scratch = torch.empty(int(self.L.mi_rollout_finish_segments_scratch_doubles(n_seg)), dtype=torch.float64, device=self.device) if batch else None
             args = (st, (self.values_now if now else self.values).data_ptr(), r.data_ptr(), d.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), n_seg, self.num_envs, T, float(gamma), float(lam),
                     1 if batch else 0, milib.ptr(scratch), self.returns.data_ptr(), self.advantages.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr())
-            if truncs.any():
+            if vt is not None:                                                       # a V-trace refresh: the same segments, the segment kernels' successor rule
+                boot = truncs.any()
+                self.L.mi_rollout_finish_vtrace(st, self.values_now.data_ptr(), vt["logp_now"].data_ptr(), vt["logp_old"].data_ptr(), *args[2:11], vt["rho_bar"], vt["c_bar"], 0,
+                                                *args[11:], vt["weights"].data_ptr(), self.final_values_now.data_ptr() if boot else None, desc[2].data_ptr() if boot else None)
+            elif truncs.any():
                 self.L.mi_rollout_finish_segments_boot(*args, (self.final_values_now if now else self.final_values).data_ptr(), desc[2].data_ptr())
             else:
                 self.L.mi_rollout_finish_segments(*args)

@@ -448,6 +448,26 @@ int mi_rollout_finish_segments(void* stream, const float* tab_values, const doub
  * that step) and the slot behind the segment in tab_values is NOT read (it holds the next episode's first value, or a stale one); the segment comes out bit for bit as
  * mi_gae_scan + mi_adv_normalize give it on [v_0 .. v_{n-1}, v_final].  normalize, scratch and every other argument as in mi_rollout_finish_segments, and the same checks. */
 int mi_rollout_finish_segments_boot(void* stream, const float* tab_values, const double* rewards, const double* terminals, const int* seg_row, const int* seg_len, int n_seg, int num_envs, int T, double gamma, double lam, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw, double* returns, double* adv_norm, const float* tab_final_values, const int* seg_boot);
+/* the finish with V-TRACE off-policy correction (Espeholt et al. 2018, IMPALA; no reference counterpart in train.py) -- for the refreshes of a multi-epoch update,
+ * where the recorded actions came from pi_old and the values are those of the moved parameters.  Segment form: seg_row / seg_len (and, both or neither,
+ * tab_final_values / seg_boot) as in mi_rollout_finish_segments[_boot].  tab_logp_now / tab_logp_old: fp32 [num_envs (T + 1)] in the table layout (row
+ * e (T + 1) + t): log pi_theta(a_t | s_t) (mi_ppo_logp_idx) and the cache of log pi_old.  Per step w_t = exp((double)lp_now - (double)lp_old), delta_t as in the GAE
+ * entries, and from the segment's last step to its first, in fp64 with each product and sum rounded once, in this order (gl = gamma * lam, D_L = 0):
+ *     A_t = gl D_{t+1} + delta_t                                            the policy advantage delta_t + gamma lam (vs_{t+1} - V_{t+1})
+ *     D_t = ((gl min(c_bar, w_t)) D_{t+1}) + (min(rho_bar, w_t) delta_t)    vs_t - V_t
+ * tab_returns / returns = D_t + V_t (the V-trace value target), adv_raw = A_t, tab_advantages / adv_norm = A normalised per segment (normalize = 0) or over the
+ * batch (normalize = 1: scratch and adv_raw as in mi_rollout_finish_segments, the same kernels behind it, fixed order, no atomics); weights_out (fp64
+ * [num_envs, T], or NULL) receives w_t.  The weight of step t does NOT multiply A_t: PPO's surrogate applies the ratio itself.  A NaN weight is not masked by
+ * a bar: it reaches the segment's outputs.  read_behind_done = 1: the successor value by mi_rollout_finish's rule (the slot behind a terminal last step is read
+ * and masked by the flag); 0: by the segment entries' rule (0.0, the slot is not read).  A truncated segment (seg_boot[i] != 0) takes tab_final_values under either.
+ * TERMINALS: as in the GAE entries the recurrence is not cut at a terminal inside a segment -- segments end at their terminal.
+ * THE GAE IDENTITY: with w_t = 1 (tab_logp_now bitwise tab_logp_old), rho_bar >= 1 and c_bar >= 1 every product with a weight is exact and D = A = the GAE
+ * recurrence: all outputs are bit for bit those of mi_rollout_finish (read_behind_done = 1, one segment per lane) or mi_rollout_finish_segments[_boot] (0).
+ * A descriptor that does not lie inside one lane's step slots is not executed and adds nothing to the batch sums; slots of no executed segment are not written.
+ * MI_ERR_ARG, before any launch and with nothing written: T outside [1, MI_ROLLOUT_MAX_HORIZON]; n_seg or num_envs < 1; rho_bar NaN or <= 0; c_bar NaN or < 0
+ * (+inf is a valid bar: never truncates); read_behind_done or normalize outside {0, 1}; missing buffers; exactly one of tab_final_values / seg_boot; scratch or
+ * adv_raw NULL with normalize = 1.  Dynamic LDS: 2 T doubles (64 KB at T = 4096). */
+int mi_rollout_finish_vtrace(void* stream, const float* tab_values, const float* tab_logp_now, const float* tab_logp_old, const double* rewards, const double* terminals, const int* seg_row, const int* seg_len, int n_seg, int num_envs, int T, double gamma, double lam, double rho_bar, double c_bar, int read_behind_done, int normalize, double* scratch, float* tab_returns, float* tab_advantages, double* adv_raw, double* returns, double* adv_norm, double* weights_out, const float* tab_final_values, const int* seg_boot);
 /* running-return reward scaling in front of the finish calls above — baselines' VecNormalize (ret = ret * gamma + rew; ret_rms.update(ret); rew / sqrt(ret_rms.var + epsilon),
  * clipped), no reference counterpart in train.py: the rewards of one collection divided by the running standard deviation of the discounted return.  No engine handle.
  * rewards / terminals: fp64 [num_envs, T]; truncs: uint8 [num_envs, T] or NULL (none); len: int32 [num_envs], the recorded steps per lane (0: an unused lane; a value
@@ -784,6 +804,22 @@ int mi_ppo_kl_stats_idx(void* h, void* stream, const float* states, const float*
  * values_out NULL, row_idx == NULL with M > n_rows; then MI_ERR_STATE: null handle; MI_ERR_SHAPE: mi_ppo_fused_shape_ok(h) is 0 (there is no per-layer form), or the
  * 2 GiB limit stated at mi_ppo_set_wide_inputs. */
 int mi_ppo_values_idx(void* h, void* stream, const float* states, const int* row_idx, long long n_rows, long long M, float* values_out);
+/* log-probabilities of table rows: log pi_theta(a | s) under the CURRENT theta for M rows of the tables `states` / `actions` of n_rows rows -- the twin of
+ * mi_ppo_values_idx for the policy side, the forward-only pass the rollout buffers form their V-trace importance weights from (mi_rollout_finish_vtrace).  Only
+ * the policy net runs: layers 1 - 2 of it (the narrow or the wide layer-1 form, as mi_ppo_set_wide_inputs selects; the engine's precision mode, as
+ * mi_ppo_update_stats_idx) and one head kernel -- three launches per chunk, no value trunk, no statistics, no reduction, no scratch, no LDS, no atomics; two runs
+ * give bitwise equal tables.
+ * Sample m is row row_idx[m] (int32, device) of `states` and of `actions` [n_rows, num_actions], or row m with row_idx == NULL (then M <= n_rows).  Its result goes
+ * to logp_out[that row]: logp_out is a table of n_rows floats, and an entry no sample names is left alone.  A row that is negative or >= n_rows stores NOTHING (its
+ * loads are clamped into the tables).  The stored float is bit for bit logp_new_out of mi_ppo_update_stats_idx for the same row and parameters, and with
+ * theta == theta_old the cache mi_ppo_logp_old fills (csrc/ppo_head.hpp, the fifth contract).
+ * M may exceed the engine's max_batch: the entry walks chunks of max_batch rows itself.
+ * NOT modified: parameters, theta_old, the optimiser state, the gradient buffer, the losses and action_mean buffers -- only the engine's activation workspace and
+ * logp_out are written.  The finiteness rule of mi_ppo_values_idx for the state entries behind a named row holds here too.  Every refusal comes before the first
+ * launch and writes nothing; those that need no engine come first: MI_ERR_ARG: M < 1, n_rows < 1, states, actions or logp_out NULL, row_idx == NULL with
+ * M > n_rows; then MI_ERR_STATE: null handle; MI_ERR_SHAPE: mi_ppo_fused_shape_ok(h) is 0 (there is no per-layer form), or the 2 GiB limit stated at
+ * mi_ppo_set_wide_inputs. */
+int mi_ppo_logp_idx(void* h, void* stream, const float* states, const float* actions, const int* row_idx, long long n_rows, long long M, float* logp_out);
 /* behaviour cloning: one supervised step of the policy (and optionally the value net) on (state, expert action[, return]) rows -- the warm start from demonstrations
  * in front of PPO.  The fused chain of the minibatch step with a head / loss kernel of its own (csrc/ppo_fused.hip, ppo_head_clone_kernel); no old policy, no
  * advantage, no ratio, no clip, no entropy term.  Per sample m and action a, with t = tanh(u), mean = lo + (t + 1) / 2 (hi - lo), sigma = exp(logstd[a]),

@@ -10,7 +10,8 @@ rows drawn from a stream of their own (the inputs of every other cell are those 
 adam 0; those cells also print demo_losses and value_head_grad[:M + M_DEMO].
 
 Head cells, at M = 5 (the wave-per-sample predict kernel) and 33, per precision: old_policy_cache (both outputs), logp_old, update_stats (the sums and the two
-optional tables), kl_stats, predict sampled with given noise and greedy; one JSON line each with the CRC-32C of every output.
+optional tables), kl_stats, predict sampled with given noise and greedy, logp_idx (the policy net alone: contiguous, and through the row list into a table); one
+JSON line each with the CRC-32C of every output.  (The two logp_idx cells come last and draw nothing from the input streams: every other cell is the line it was.)
 
     python tools/ppo_step_digest.py [--time-limit 600] > digest.jsonl      # one process, no retries; the alarm ends a run that takes longer
     MI355_LIB=<another build's library> python tools/ppo_step_digest.py    # the same cells from that build (the C ABI has to be this tree's)"""
@@ -81,6 +82,11 @@ def head_cells(d, tag, M, A, flat, tab, rows):
         act, val = f32(M, A), f32(M)
         d.predict(flat["s"], M, flat["noise"], greedy, act, val)
         emit("%s M=%d predict greedy=%d" % (tag, M, greedy), (("action", act), ("value", val)))
+    lpc, lpt = f32(M), f32(n)
+    d.logp_idx(flat["s"], flat["a"], None, M, lpc)
+    emit("%s M=%d logp_idx contiguous" % (tag, M), (("logp", lpc),))
+    d.logp_idx(tab["s"], tab["a"], rows, M, lpt)
+    emit("%s M=%d logp_idx rows" % (tag, M), (("logp", lpt),))
 
 
 for shape, DIN, A, HIDDEN in SHAPES:

@@ -31,7 +31,14 @@ runs the same update with RolloutBuffer.set_minibatch_normalization off and on i
 runs the same update (three epochs unless --epochs says otherwise) with RolloutBuffer.set_advantage_recomputation off and on in interleaved rounds, without the
 replay paths: the "recompute" stage (part of "sgd") is the cost of the refreshes -- one mi_ppo_values_idx call and one finish call before every epoch but the first
 -- printed per refresh beside the "sgd" stage per epoch.  Then the bare value pass over 1024 x 128 table rows (one mi_ppo_values_idx call) against
-mi_ppo_update_stats_idx with value_out and mi_ppo_kl_stats_idx over the same rows in chunks of 4096: one process, device events, three interleaved rounds."""
+mi_ppo_update_stats_idx with value_out and mi_ppo_kl_stats_idx over the same rows in chunks of 4096: one process, device events, three interleaved rounds.
+
+    python tools/rollout_buffer_bench.py --vtrace [--envs 1024] [--steps 128] [--batch 2048] [--epochs 3] ...
+
+runs the same update with advantage recomputation alone and with RolloutBuffer.set_vtrace on top of it in interleaved rounds (the refresh of the first is the code
+--recompute measures): the "recompute" stage per refresh of both, and their ratio.  Then the bare log-probability pass over 1024 x 128 table rows (one
+mi_ppo_logp_idx call) against one mi_ppo_values_idx call over the same rows, and mi_rollout_finish_vtrace alone against mi_rollout_finish on the collection's E x T
+steps (one segment per lane), interleaved likewise."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "carla-ppo_amd"), ROOT):
@@ -55,11 +62,12 @@ ap.add_argument("--continuous", action="store_true", help="RolloutBuffer against
 ap.add_argument("--diagnostics", action="store_true", help="RolloutBuffer.update against update_with_diagnostics in interleaved rounds (no replay paths)")
 ap.add_argument("--minibatch-norm", action="store_true", help="RolloutBuffer.update with per-minibatch advantage normalisation off and on in interleaved rounds (no replay paths)")
 ap.add_argument("--recompute", action="store_true", help="RolloutBuffer.update with advantage recomputation off and on in interleaved rounds, then the bare value pass (no replay paths)")
+ap.add_argument("--vtrace", action="store_true", help="RolloutBuffer.update with advantage recomputation alone and with V-trace on top in interleaved rounds, then the bare log-probability pass and the bare finish call (no replay paths)")
 ap.add_argument("--ddof", type=int, default=0, help="ddof of the normalised path of --minibatch-norm")
 ap.add_argument("--value-clip", type=float, default=0.2, help="eps_v of the value-clipped path of --diagnostics")
 ap.add_argument("--mean-episode", type=float, default=None, help="mean of the geometric episode lengths of --continuous (default: steps / 3)")
 args = ap.parse_args()
-if args.recompute and args.epochs == 1:
+if (args.recompute or args.vtrace) and args.epochs == 1:
     args.epochs = 3                                                                   # (the first epoch never refreshes)
 
 
@@ -144,8 +152,8 @@ if args.continuous:
 idx = rng.randint(0, args.pool, (E, T + 1))
 meas = np.stack([rng.uniform(-1, 1, (E, T + 1)), rng.uniform(0, 1, (E, T + 1)), rng.uniform(0, 30, (E, T + 1))], axis=-1).astype(np.float32)
 rewards, dones = rng.uniform(0, 1, (E, T)), np.zeros((E, T))
-frames_d = None if args.diagnostics or args.minibatch_norm or args.recompute else torch.from_numpy(pool).to("cuda")[torch.from_numpy(idx).to("cuda")]           # [E, T + 1, 80, 160, 3] uint8 in HBM
-frames_h = None if args.no_host_frames or args.diagnostics or args.minibatch_norm or args.recompute else pool[idx]
+frames_d = None if args.diagnostics or args.minibatch_norm or args.recompute or args.vtrace else torch.from_numpy(pool).to("cuda")[torch.from_numpy(idx).to("cuda")]           # [E, T + 1, 80, 160, 3] uint8 in HBM
+frames_h = None if args.no_host_frames or args.diagnostics or args.minibatch_norm or args.recompute or args.vtrace else pool[idx]
 
 buf = RolloutBuffer(vae, agent, E, T)
 
@@ -166,8 +174,13 @@ actions, t_collect = collect()
 print("collection of %d x %d steps through the recording step: %.3f s (%.1f us per call incl. the host's frame gather)" % (E, T, t_collect, 1e6 * t_collect / (T + 1)), flush=True)
 
 
-buf_on = None
-if args.recompute:                                                                    # the setting is switched with no step recorded: a buffer of its own, the same collection
+buf_on = buf_vt = None
+if args.vtrace:                                                                       # recomputation with V-trace on top: a third buffer, the same collection
+    buf_vt = RolloutBuffer(vae, agent, E, T)
+    buf_vt.set_advantage_recomputation(True)
+    buf_vt.set_vtrace(1.0, 1.0)
+    collect(buf_vt)
+if args.recompute or args.vtrace:                                                                    # the setting is switched with no step recorded: a buffer of its own, the same collection
     buf_on = RolloutBuffer(vae, agent, E, T)
     buf_on.set_advantage_recomputation(True)
     collect(buf_on)
@@ -216,6 +229,59 @@ def value_pass_bench(rows_total=1024 * 128, rounds=3, passes=10, chunk=4096):
         print("  %-26s median %.1f  (rounds %s)" % (k, sorted(v)[len(v) // 2], "  ".join("%.1f" % x for x in v)), flush=True)
 
 
+def timed_rounds(fns, rounds, passes):
+    """-> {name: [us per pass of every round]}: the functions interleaved in every round, device events around `passes` calls."""
+    for f in fns.values():
+        f()
+    torch.cuda.synchronize()
+    res = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, f in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(passes):
+                f()
+            b.record()
+            torch.cuda.synchronize()
+            res[k].append(1e3 * a.elapsed_time(b) / passes)
+    return res
+
+
+def vtrace_pass_bench(rows_total=1024 * 128, rounds=3, passes=10):
+    """The bare log-probability pass against the bare value pass on the same table rows, then mi_rollout_finish_vtrace against mi_rollout_finish on E x T steps."""
+    d, dev = agent.dev, agent.dev.device
+    g = torch.Generator(device="cpu").manual_seed(0)
+    S = (0.5 * torch.randn(rows_total, 67, generator=g)).to(dev)
+    Act = torch.rand(rows_total, 2, generator=g).to(dev)
+    rows = torch.randperm(rows_total, generator=g).to(torch.int32).to(dev)
+    V, LPN = torch.zeros(rows_total, device=dev), torch.zeros(rows_total, device=dev)
+    res = timed_rounds({"values_idx": lambda: d.values_idx(S, rows, rows_total, V), "logp_idx": lambda: d.logp_idx(S, Act, rows, rows_total, LPN)}, rounds, passes)
+    print("log-probability pass over %d table rows (max_batch %d, %d passes per window, %d interleaved rounds), us per pass:" % (rows_total, d.max_batch, passes, rounds), flush=True)
+    for k, v in res.items():
+        print("  %-26s median %.1f  (rounds %s)" % (k, sorted(v)[len(v) // 2], "  ".join("%.1f" % x for x in v)), flush=True)
+    L, st = buf.L, torch.cuda.current_stream(dev).cuda_stream
+    n = E * (T + 1)
+    vals, lpo = torch.randn(n, generator=g).to(dev), (-1.5 + torch.randn(n, generator=g)).to(dev)
+    lpn = lpo + (0.2 * torch.randn(n, generator=g)).to(dev)
+    r, dn = torch.rand(E, T, generator=g, dtype=torch.float64).to(dev), torch.zeros(E, T, dtype=torch.float64, device=dev)
+    ln = torch.full((E,), T, dtype=torch.int32, device=dev)
+    row0 = (torch.arange(E, dtype=torch.int32) * (T + 1)).to(dev)
+    ret, adv = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    f64, w = torch.zeros(3, E, T, dtype=torch.float64, device=dev), torch.zeros(E, T, dtype=torch.float64, device=dev)
+
+    def gae():
+        L.mi_rollout_finish(st, vals.data_ptr(), r.data_ptr(), dn.data_ptr(), ln.data_ptr(), E, T, 0.99, 0.95, ret.data_ptr(), adv.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(),
+                            f64[2].data_ptr())
+
+    def vtrace():
+        L.mi_rollout_finish_vtrace(st, vals.data_ptr(), lpn.data_ptr(), lpo.data_ptr(), r.data_ptr(), dn.data_ptr(), row0.data_ptr(), ln.data_ptr(), E, E, T, 0.99, 0.95, 1.0, 1.0, 1, 0,
+                                   None, ret.data_ptr(), adv.data_ptr(), f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr(), w.data_ptr(), None, None)
+    res = timed_rounds({"mi_rollout_finish": gae, "mi_rollout_finish_vtrace": vtrace}, rounds, passes)
+    print("finish call on %d x %d steps, one segment per lane (%d passes per window, %d interleaved rounds), us per call:" % (E, T, passes, rounds), flush=True)
+    for k, v in res.items():
+        print("  %-26s median %.1f  (rounds %s)" % (k, sorted(v)[len(v) // 2], "  ".join("%.1f" % x for x in v)), flush=True)
+
+
 def run(path, batch):
     st = {}
     torch.cuda.synchronize()
@@ -226,6 +292,8 @@ def run(path, batch):
         buf.update_with_diagnostics(num_epochs=args.epochs, batch_size=batch, stage_times=st)
     elif path == "+ recompute":
         buf_on.update(num_epochs=args.epochs, batch_size=batch, stage_times=st)
+    elif path == "+ recompute + vtrace":
+        buf_vt.update(num_epochs=args.epochs, batch_size=batch, stage_times=st)
     elif path == "+ minibatch norm":
         buf.set_minibatch_normalization(args.ddof)
         try:
@@ -251,6 +319,8 @@ if args.minibatch_norm:
     paths = ["buffer", "+ minibatch norm"]
 if args.recompute:
     paths = ["buffer", "+ recompute"]
+if args.vtrace:
+    paths = ["+ recompute", "+ recompute + vtrace"]
 for batch in [int(x) for x in args.batch.split(",") if x]:
     for p in paths:
         run(p, batch)                                                                     # warm-up (engine growth, allocator)
@@ -270,8 +340,8 @@ for batch in [int(x) for x in args.batch.split(",") if x]:
             print("    every round: %s" % "  ".join("%.4f" % r[0] for r in res[p]) + ("" if "minibatch_norm" not in stages else
                   "   minibatch_norm stage %.6f s = %.1f us per epoch, %.3f %% of the update;  on / off %.4f" % (stages["minibatch_norm"], 1e6 * stages["minibatch_norm"] / max(args.epochs, 1),
                                                                                                                    100.0 * stages["minibatch_norm"] / med, med / off)), flush=True)
-        if args.recompute:
-            off = sorted(r[0] for r in res["buffer"])[args.rounds // 2]
+        if args.recompute or args.vtrace:
+            off = sorted(r[0] for r in res[paths[0]])[args.rounds // 2]
             print("    every round: %s   sgd stage %.4f s per epoch" % ("  ".join("%.4f" % r[0] for r in res[p]), stages["sgd"] / max(args.epochs, 1)) + ("" if "recompute" not in stages else
                   "   recompute stage %.6f s = %.1f us per refresh (%d refreshes), %.3f %% of the update;  on / off %.4f"
                   % (stages["recompute"], 1e6 * stages["recompute"] / max(args.epochs - 1, 1), max(args.epochs - 1, 0), 100.0 * stages["recompute"] / med, med / off)), flush=True)
@@ -280,3 +350,5 @@ for batch in [int(x) for x in args.batch.split(",") if x]:
                   "   stats stage %.4f s = %.4f s per epoch, %.1f %% of the update" % (stages["stats"], stages["stats"] / max(args.epochs, 1), 100.0 * stages["stats"] / med)), flush=True)
 if args.recompute:
     value_pass_bench()
+if args.vtrace:
+    vtrace_pass_bench()
