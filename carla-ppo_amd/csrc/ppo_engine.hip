@@ -35,6 +35,7 @@ struct PpoEngine {
     long long f_h1, f_h2, f_dh1, f_dh2, f_part;   // fused step (ppo_fused.hip): [3][M][H1], [3][M][H2], [2][M][H1], [2][M][H2], loss-block partials
     int last_M;
     int precision;                                // MI_F32 (calloc: the default) or MI_BF16X3 (mi_ppo_set_precision): which instantiation of the fused GEMM stages runs
+    float dual_clip;                              // 0 (calloc: the default): the plain surrogate; > 1 or +inf: dual-clip PPO in every fused step (mi_ppo_set_dual_clip)
     int wide;                                     // 0 (calloc: the default): the fused range ends at kin = 96; 1 / 2: at kin = 1024 (mi_ppo_set_wide_inputs).  Routing only
     hipStream_t side; hipEvent_t ev_fork, ev_join; int side_ok;     // second stream of the forked minibatch step (0 = not tried, 1 = ok, -1 = unavailable)
     float* P(int t) const { return params + off[t]; }
@@ -122,6 +123,8 @@ bool x3(const PpoEngine* e) { return e->precision == MI_BF16X3; }
 
 bool clipping(const PpoEngine* e) { return e->max_grad_norm > 0.f; }
 
+bool dual_clipping(const PpoEngine* e) { return e->dual_clip > 0.f; }
+
 // the ordered sum of squares over the 13 variables of the gradient buffer (not the alignment gaps behind the odd-sized ones) -> MI_GRAD_NORM_BLOCKS partials
 int grad_sumsq(PpoEngine* e, void* stream, int tensors = PPO_TENSORS) {
     return mi_grad_sumsq((hipStream_t)stream, e->grads, e->off, e->size, tensors, (double*)e->at(e->gn_part));
@@ -153,7 +156,8 @@ void fill_fused(const PpoEngine* e, PpoFusedParams& q, const float* states, int 
     q.mean_out = (float*)e->at(e->mean); q.kl_partial = (float*)e->at(e->f_klpart);
     q.gslab = d.max_batch > 256 ? (float*)e->at(e->f_gslab) : nullptr; q.gslab_stride = e->total;      // (total is a multiple of 8 floats: pad8 per tensor)
     q.n_nets = 3; q.n_wnets = 2;
-    q.clip_eps = d.clip_eps; q.value_scale = d.value_scale; q.entropy_scale = d.entropy_scale;
+    q.clip_eps = d.clip_eps; q.value_scale = d.value_scale; q.entropy_scale = d.entropy_scale;      // (the live values: mi_ppo_set_loss_coefs writes e->d)
+    q.dual_clip = dual_clipping(e) ? e->dual_clip : __builtin_inff();      // off: c = +inf, the branch of the head / loss kernel is never taken
     q.wide = e->wide; q.max_batch = d.max_batch;
 }
 
@@ -274,10 +278,11 @@ void mi_ppo_destroy(void* h) {
 // 0 losses[5] (policy, value, entropy, total, mean ratio)   1 action_mean [M,A] of the last predict   2 {norm, scale, c, 0} of the last gradient norm
 // 3 dv [M] of the last step: d loss / d value-head output per sample (workspace of the step; what value clipping zeroes)
 // 4 [demo_loss, c_d demo_loss, mean_sq_error] of the last mi_ppo_train_step_demo
+// 5 du [M, A] of the last step: d loss / d action-mean head output per sample (workspace of the step; what dual clip zeroes)
 void* mi_ppo_buffer(void* h, int which) {
     PpoEngine* e = (PpoEngine*)h;
     if (!e) return nullptr;
-    return which == 0 ? e->at(e->losses) : which == 1 ? e->at(e->mean) : which == 2 ? e->at(e->clip) : which == 3 ? e->at(e->dv) : which == 4 ? e->at(e->f_demo) : nullptr;
+    return which == 0 ? e->at(e->losses) : which == 1 ? e->at(e->mean) : which == 2 ? e->at(e->clip) : which == 3 ? e->at(e->dv) : which == 4 ? e->at(e->f_demo) : which == 5 ? e->at(e->du) : nullptr;
 }
 
 // PPO.update_old_policy (ppo.py:275-276): theta_old <- theta, one device copy of the flat buffer
@@ -318,6 +323,7 @@ int mi_ppo_forward_backward(void* h, void* stream, const float* states, const fl
         return route_step(e, stream, q, nullptr, 0, 0.f, 0.f, 0.f, 0.f);
     }
     if (x3(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_forward_backward: the split-bf16 mode needs the fused kernels (no per-layer form of it)");
+    if (dual_clipping(e)) return mi_fail(MI_ERR_SHAPE, "mi_ppo_forward_backward: dual clip is on (mi_ppo_set_dual_clip) and needs the fused kernels (no per-layer form of it)");
     const MiPpoDesc& d = e->d;
     void* st = stream;
     const int A = d.num_actions;
@@ -683,6 +689,41 @@ int mi_ppo_set_max_grad_norm(void* h, float max_norm) {
     // (what needs no engine is checked before the handle is looked at)
     if (!(max_norm >= 0.f)) return mi_fail(MI_ERR_ARG, "mi_ppo_set_max_grad_norm: max_norm is 0 (off), a positive float or +inf");
     e->max_grad_norm = max_norm;
+    return MI_OK;
+}
+
+// Dual-clip PPO (include/mi355_carla.h; the definition is in ppo_fused.hip's head / loss kernel).  0: off, the default of a new engine.
+int mi_ppo_set_dual_clip(void* h, float c) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_set_dual_clip: null handle");
+    if (!(c == 0.f || c > 1.f)) return mi_fail(MI_ERR_ARG, "mi_ppo_set_dual_clip: c is 0 (off), a float > 1 or +inf");
+    e->dual_clip = c == 0.f ? 0.f : c;                    // (-0.0 is stored as 0.0)
+    return MI_OK;
+}
+
+float mi_ppo_dual_clip(void* h) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) { mi_fail(MI_ERR_STATE, "mi_ppo_dual_clip: null handle"); return -1.0f; }
+    return e->dual_clip;
+}
+
+// The three loss coefficients of the descriptor, replaced on a live engine (include/mi355_carla.h): every later call reads e->d, so nothing else is to be done.
+int mi_ppo_set_loss_coefs(void* h, float clip_eps, float value_scale, float entropy_scale) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_set_loss_coefs: null handle");
+    const float fmax = 3.402823466e+38f;
+    if (!(clip_eps > 0.f) || !(clip_eps <= fmax)) return mi_fail(MI_ERR_ARG, "mi_ppo_set_loss_coefs: clip_eps is a finite float > 0");
+    if (!(value_scale >= 0.f) || !(value_scale <= fmax)) return mi_fail(MI_ERR_ARG, "mi_ppo_set_loss_coefs: value_scale is a finite float >= 0");
+    if (!(entropy_scale >= 0.f) || !(entropy_scale <= fmax)) return mi_fail(MI_ERR_ARG, "mi_ppo_set_loss_coefs: entropy_scale is a finite float >= 0");
+    e->d.clip_eps = clip_eps; e->d.value_scale = value_scale; e->d.entropy_scale = entropy_scale;
+    return MI_OK;
+}
+
+int mi_ppo_loss_coefs(void* h, float* clip_eps, float* value_scale, float* entropy_scale) {
+    PpoEngine* e = (PpoEngine*)h;
+    if (!e) return mi_fail(MI_ERR_STATE, "mi_ppo_loss_coefs: null handle");
+    if (!clip_eps || !value_scale || !entropy_scale) return mi_fail(MI_ERR_ARG, "mi_ppo_loss_coefs: missing outputs (clip_eps, value_scale, entropy_scale)");
+    *clip_eps = e->d.clip_eps; *value_scale = e->d.value_scale; *entropy_scale = e->d.entropy_scale;
     return MI_OK;
 }
 

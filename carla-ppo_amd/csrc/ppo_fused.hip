@@ -362,6 +362,11 @@ __global__ __launch_bounds__(256) void ppo_l2_kernel(const PpoFusedParams q) {
 // thread) goes to q.kl_partial[block]; ppo_wgrad_kernel's spare wave adds those in block order.  beta = 0 measures: every added term is 0.
 // ---------------------------------------------------------------------------------------------------------------------
 //
+// DUAL CLIP (mi_ppo_set_dual_clip; every instantiation, a run-time value): q.dual_clip = c > 1, or +inf with the setting off.  Behind s = min(s1, s2) a PPO row with
+// A < 0 and c A > s takes the constant c A: its policy partial is c A and dr = 0, so the surrogate adds exactly 0.0 to du and to dlogstd; the KL penalty's own terms,
+// the value side and demonstration rows are as they were.  One multiply, two compares, two selects per lane; with c = +inf no comparison holds and every stored
+// bit is the plain step's (profiles/r42_dual_clip.md: why this is a field of PpoFusedParams and not a template flag).
+//
 // DEMO (ppo_head_demo[_kl][_vclip]_kernel; mi_ppo_train_step_demo): the step over M = m_ppo + M_demo rows of which rows m >= q.m_ppo are DEMONSTRATION rows.  A
 // demonstration row takes the arithmetic of ppo_head_clone_kernel (policy only), operation for operation, with inv_m_demo in the place of inv_m, and then the
 // weight c_d = q.demo_coef on du and on the logstd term: it gathers its expert action from q.demo_actions at row demo_row_idx[m - m_ppo] (clamped; nullptr:
@@ -532,7 +537,12 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
         const float ad = p_adv_s;
         const float rc = fminf(fmaxf(r, 1.0f - q.clip_eps), 1.0f + q.clip_eps);
         const float s1 = r * ad, s2 = rc * ad;
-        const float dr = (s1 <= s2) ? ad : 0.f;           // tf.minimum: gradient to the first argument on ties; the clipped branch has zero slope
+        // dual clip (mi_ppo_set_dual_clip; q.dual_clip = c > 1, +inf with the setting off): a sample with A < 0 whose c A lies above min(s1, s2) takes c A, a
+        // constant of theta, so dr = 0 as on the clipped branch.  tf.maximum's tie rule: on a tie s keeps the gradient.  A >= 0 (-0.0 included) never takes it;
+        // with c = +inf c A is -inf (NaN at A = 0, where A < 0 fails first) and no comparison holds: every stored bit is the plain step's
+        const float sm12 = fminf(s1, s2), ca = q.dual_clip * ad;
+        const bool dual = ad < 0.f && ca > sm12;
+        const float dr = (s1 <= s2 && !dual) ? ad : 0.f;  // tf.minimum: gradient to the first argument on ties; the clipped branches have zero slope
         const float coef = -dr * r * q.inv_m;
         float d = coef * dl;
         const float kb = KLP ? q.kl_coef * q.inv_m : 0.f;
@@ -556,7 +566,7 @@ __device__ __forceinline__ void ppo_head_loss_body(const PpoFusedParams& q) {
             sdv[sm] = dvm;
             if constexpr (KLP) skl[sm] = mok ? kl : 0.f;
             if constexpr (DEMO) { sdemo[sm][0] = 0.f; sdemo[sm][1] = 0.f; }
-            if (mok) { q.dv[m] = dvm; if (q.logp_out) q.logp_out[m] = lp_n; spart[sm][0] = fminf(s1, s2); spart[sm][1] = lv; spart[sm][2] = r; }
+            if (mok) { q.dv[m] = dvm; if (q.logp_out) q.logp_out[m] = lp_n; spart[sm][0] = dual ? ca : sm12; spart[sm][1] = lv; spart[sm][2] = r; }
         }
         if (aok) {
             float dls = coef * (zsq - 1.0f);
@@ -1057,6 +1067,43 @@ __global__ __launch_bounds__(256) void ppo_logp_head_kernel(const PpoFusedParams
     logp_out[row] = lp;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// dual-clip diagnostics (mi_ppo_dual_clip_stats): what the dual-clipped surrogate of ppo_head_loss_body did to M rows row_idx[m] (clamped) of three fp32 tables --
+// lp = log pi_theta(a | s) (the logp_new_out table of mi_ppo_update_stats_idx), lpo = the cached log pi_old, A = the advantage the steps gathered.  No engine, no
+// network: one thread per sample, 256 samples per block.  The CLASS of a sample is formed in fp32 as the step forms it, operation for operation --
+//   r = __expf(lp - lpo), s1 = r A, s2 = clamp(r, 1 - eps, 1 + eps) A, s = min(s1, s2), dual-clipped iff A < 0 and c A > s
+// -- so the counts say what the step did; the two SUMS are taken in double from the fp32 inputs (r = exp((double)lp - (double)lpo)), like the other statistics
+// passes' terms.  terms 1, A < 0, dual-clipped, s' (c A on a dual-clipped sample, else s), s.  Ordered reduction, no atomics: the xor rounds 1, 2, 4 here and
+// pf_ordered_block_sum's 8, 16, 32 are a wave's whole tree; ppo_stats_reduce_kernel adds the block rows in block order.  Rows that row_idx does not name are not read.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int PF_NDCSTATS = MI_PPO_N_DUAL_CLIP_STATS;
+__global__ __launch_bounds__(256) void ppo_dual_clip_stats_kernel(const float* __restrict__ logp_new, const float* __restrict__ logp_old, const float* __restrict__ advantage,
+                                                                  const int* __restrict__ row_idx, int n_rows, int M, float clip_eps, float dual_clip, double* __restrict__ scratch) {
+    __shared__ double swave[4][PF_NDCSTATS];
+    const int tid = threadIdx.x, m = blockIdx.x * 256 + tid;
+    double term[PF_NDCSTATS];
+#pragma unroll
+    for (int k = 0; k < PF_NDCSTATS; ++k) term[k] = 0.0;
+    if (m < M) {
+        const long long mr = min(max(row_idx[m], 0), n_rows - 1);
+        const float lp = logp_new[mr], lpo = logp_old[mr], ad = advantage[mr];
+        const float r = __expf(lp - lpo);
+        const float rc = fminf(fmaxf(r, 1.0f - clip_eps), 1.0f + clip_eps);
+        const float s1 = r * ad, s2 = rc * ad;
+        const bool dual = ad < 0.f && dual_clip * ad > fminf(s1, s2);
+        const double rd = exp((double)lp - (double)lpo), add = (double)ad;
+        const double rcd = fmin(fmax(rd, 1.0 - (double)clip_eps), 1.0 + (double)clip_eps);
+        const double sd = fmin(rd * add, rcd * add);
+        term[0] = 1.0; term[1] = ad < 0.f ? 1.0 : 0.0; term[2] = dual ? 1.0 : 0.0; term[3] = dual ? (double)dual_clip * add : sd; term[4] = sd;
+    }
+#pragma unroll
+    for (int k = 0; k < PF_NDCSTATS; ++k) {
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) term[k] += __shfl_xor(term[k], o, 64);
+    }
+    pf_ordered_block_sum<PF_NDCSTATS>(term, swave, scratch, tid);
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -1137,6 +1184,22 @@ int mi_ppo_fused_kl_stats(hipStream_t st, PpoFusedParams& q, int accumulate, dou
     hipLaunchKernelGGL(pf_na_pick(q.A, ppo_kl_stats_head_kernel<2>, ppo_kl_stats_head_kernel<PF_MAX_ACT>), dim3(nb), dim3(256), 0, st, q, scratch);
     hipLaunchKernelGGL(ppo_stats_reduce_kernel<PF_NKLSTATS>, dim3(1), dim3(64), 0, st, (const double*)scratch, nb, accumulate, stats);
     return mi_check_launch("ppo_kl_stats");
+}
+
+// the dual-clip diagnostics (include/mi355_carla.h): no engine, two launches, nothing but scratch and stats is written
+extern "C" long long mi_ppo_dual_clip_stats_scratch_doubles(int M) { return (long long)MI_PPO_N_DUAL_CLIP_STATS * (M < 1 ? 1 : (M + 255) / 256); }
+
+extern "C" int mi_ppo_dual_clip_stats(void* stream, const float* logp_new, const float* logp_old, const float* advantage, const int* row_idx, int n_rows, int M,
+                                      float clip_eps, float dual_clip, int accumulate, double* scratch, double* stats) {
+    if (M < 1 || n_rows < 1) return mi_fail(MI_ERR_ARG, "mi_ppo_dual_clip_stats: empty input (M >= 1, n_rows >= 1)");
+    if (!logp_new || !logp_old || !advantage || !row_idx || !scratch || !stats) return mi_fail(MI_ERR_ARG, "mi_ppo_dual_clip_stats: missing buffers");
+    if (!(clip_eps > 0.f) || !(clip_eps <= 3.402823466e+38f)) return mi_fail(MI_ERR_ARG, "mi_ppo_dual_clip_stats: clip_eps is a finite float > 0");
+    if (!(dual_clip > 1.f)) return mi_fail(MI_ERR_ARG, "mi_ppo_dual_clip_stats: dual_clip is a float > 1 or +inf");
+    if (accumulate != 0 && accumulate != 1) return mi_fail(MI_ERR_ARG, "mi_ppo_dual_clip_stats: accumulate is 0 (store the sums) or 1 (add them to stats)");
+    const int nb = (M + 255) / 256;
+    hipLaunchKernelGGL(ppo_dual_clip_stats_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, logp_new, logp_old, advantage, row_idx, n_rows, M, clip_eps, dual_clip, scratch);
+    hipLaunchKernelGGL(ppo_stats_reduce_kernel<PF_NDCSTATS>, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)scratch, nb, accumulate, stats);
+    return mi_check_launch("ppo_dual_clip_stats");
 }
 
 // V(s) of M table rows under the current theta (mi_ppo_values_idx): the value net ALONE.  The trunk kernels number nets by blockIdx.y from 0, so a copy of the

@@ -52,6 +52,9 @@ struct PpoFusedParams {
     // inv_m_demo = 1 / M_demo(global).  demo_partial: two floats per loss block (the sums of l[m] and of the squared error over its demonstration rows);
     // demo_out: [demo_loss, c_d demo_loss, mean_sq_error] (mi_ppo_buffer(h, 4))
     int m_ppo, demo_kind, n_demo_rows; float demo_coef, inv_m_demo;
+    // dual-clip PPO (mi_ppo_set_dual_clip), in the 4 bytes of padding behind inv_m_demo, so that no field moves: the constant c > 1 of the head / loss kernel's
+    // surrogate, +inf with the setting off (fill_fused: never 0)
+    float dual_clip;
     const float *demo_states, *demo_actions; const int* demo_row_idx; float *demo_partial, *demo_out;
 };
 static_assert(sizeof(PpoFusedParams) == 520, "PpoFusedParams: a field moved (the offsets of its fields are pinned by profiles/r28_ppo_wide_inputs.md)");

@@ -46,6 +46,28 @@ def value_clip_value(value, who="value_clip"):
     return float(value)
 
 
+def dual_clip_value(value, who="dual_clip"):
+    """The constant c of dual-clip PPO (mi_ppo_set_dual_clip): None (off) or a float > 1 (inf: the setting is on and no sample is ever dual-clipped) -> None or
+    float; bool, str, NaN or a value <= 1 raise ValueError.  No device and no library involved."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not value > 1:
+        raise ValueError("%s: the value is None or a float > 1 (inf: no sample is ever dual-clipped), got %r" % (who, value))
+    return float(value)
+
+
+def loss_coef_values(clip_eps, value_scale, entropy_scale, who="loss_coefs"):
+    """The three loss coefficients of the PPO step (mi_ppo_set_loss_coefs): clip_eps finite and > 0, value_scale and entropy_scale finite and >= 0 -> three floats;
+    bool, str, NaN, inf or a value outside its range raise ValueError.  No device and no library involved."""
+    out = []
+    for name, value, positive in (("clip_eps", clip_eps, True), ("value_scale", value_scale, False), ("entropy_scale", entropy_scale, False)):
+        ok = not isinstance(value, bool) and isinstance(value, numbers.Real) and value < float("inf") and (value > 0 if positive else value >= 0)
+        if not ok:
+            raise ValueError("%s: %s is a finite float %s 0, got %r" % (who, name, ">" if positive else ">=", value))
+        out.append(float(value))
+    return tuple(out)
+
+
 def kl_penalty_value(value, who="kl_penalty"):
     """The coefficient beta of the KL penalty (mi_ppo_train_step_kl): None (off) or a finite float >= 0 (0: the penalised step, nothing added: it measures the KL)
     -> None or float; bool, str, a negative value, inf or NaN raise ValueError.  No device and no library involved."""

@@ -46,6 +46,23 @@ def value_clip_summary(sums):
     return {"value_clip_fraction": float(s[1] / n), "value_loss_clipped": float(s[2] / n), "value_grad_zero_fraction": float(s[3] / n)}
 
 
+N_DUAL_CLIP_STATS = 5                             # MI_PPO_N_DUAL_CLIP_STATS of include/mi355_carla.h
+
+
+def dual_clip_summary(sums):
+    """The MI_PPO_N_DUAL_CLIP_STATS running sums of mi_ppo_dual_clip_stats (count, count of A < 0, count of dual-clipped samples, sum of the dual-clipped surrogate
+    s', sum of the plain surrogate s) -> dual_clip_fraction, negative_advantage_fraction, surrogate_mean (the mean of s': minus the policy loss of a step over these
+    rows) and surrogate_mean_unclipped (the mean of s).  Host arithmetic in float64; no GPU involved."""
+    s = np.asarray(sums, np.float64).reshape(-1)
+    if s.shape[0] != N_DUAL_CLIP_STATS:
+        raise ValueError("dual_clip_summary: expected %d sums, got %d" % (N_DUAL_CLIP_STATS, s.shape[0]))
+    n = float(s[0])
+    if not n > 0:
+        raise ValueError("dual_clip_summary: the sums hold no sample")
+    return {"dual_clip_fraction": float(s[2] / n), "negative_advantage_fraction": float(s[1] / n), "surrogate_mean": float(s[3] / n),
+            "surrogate_mean_unclipped": float(s[4] / n)}
+
+
 N_KL_STATS = 4                                    # MI_PPO_N_KL_STATS of include/mi355_carla.h
 
 
@@ -100,6 +117,7 @@ class PpoDevice:
         self.handle = None
         self.max_batch = 0
         self.max_grad_norm = None                     # global-norm gradient clipping (set_max_grad_norm); None: off
+        self.dual_clip = None                         # dual-clip PPO (set_dual_clip); None: off
         self._create(max_batch)
 
     def _desc(self, max_batch):
@@ -153,8 +171,14 @@ class PpoDevice:
         o = addr - self.workspace.data_ptr()
         # [demo_loss, demo_coef x demo_loss, mean_sq_error] of the last train_step_demo (no other step writes them)
         self.demo_losses = self.workspace[o:o + 12].view(torch.float32)
+        addr = self.L.mi_ppo_buffer(self.handle, 5)
+        o = addr - self.workspace.data_ptr()
+        # d loss / d action-mean head output per sample of the last step (the step's workspace; exactly 0 on a dual-clipped sample with the KL penalty off)
+        self.policy_head_grad = self.workspace[o:o + 4 * int(max_batch) * self.num_actions].view(torch.float32).view(int(max_batch), self.num_actions)
         # like the precision, the clipping limit is applied to every engine this object creates
         self.L.mi_ppo_set_max_grad_norm(self.handle, 0.0 if self.max_grad_norm is None else self.max_grad_norm)
+        # ... and the dual-clip constant (the loss coefficients travel in the descriptor, which _desc fills from the live attributes)
+        self.L.mi_ppo_set_dual_clip(self.handle, 0.0 if self.dual_clip is None else self.dual_clip)
 
     def ensure_batch(self, m):
         if m > self.max_batch:
@@ -420,6 +444,42 @@ class PpoDevice:
         apply_adam and every train_step form.  Kept across ensure_batch."""
         self.max_grad_norm = milib.max_grad_norm_value(max_norm, "PpoDevice.set_max_grad_norm")
         self.L.mi_ppo_set_max_grad_norm(self.handle, 0.0 if self.max_grad_norm is None else self.max_grad_norm)
+
+    def set_dual_clip(self, c):
+        """Dual-clip PPO (mi_ppo_set_dual_clip): None switches it off, a float > 1 (inf: on, and no sample is ever dual-clipped) switches it on for every fused
+        step form -- a sample with A < 0 whose c A lies above the clipped surrogate takes c A and gives the policy no gradient.  Kept across ensure_batch."""
+        self.dual_clip = milib.dual_clip_value(c, "PpoDevice.set_dual_clip")
+        self.L.mi_ppo_set_dual_clip(self.handle, 0.0 if self.dual_clip is None else self.dual_clip)
+
+    def engine_dual_clip(self):
+        """The engine's own record of the constant (mi_ppo_dual_clip): 0.0 = off."""
+        return float(self.L.mi_ppo_dual_clip(self.handle))
+
+    def set_loss_coefs(self, clip_eps, value_scale, entropy_scale):
+        """Replace the three loss coefficients on the live engine (mi_ppo_set_loss_coefs): clip_eps finite and > 0, value_scale and entropy_scale finite and >= 0;
+        ValueError otherwise, nothing changed.  Every later call reads them: the steps, update_stats' clipped fraction, the per-layer path.  Parameters and optimiser
+        state stay.  Kept across ensure_batch (the next engine's descriptor is filled from them)."""
+        ce, vs, es = milib.loss_coef_values(clip_eps, value_scale, entropy_scale, "PpoDevice.set_loss_coefs")
+        self.L.mi_ppo_set_loss_coefs(self.handle, ce, vs, es)
+        self.clip_eps, self.value_scale, self.entropy_scale = ce, vs, es
+
+    def engine_loss_coefs(self):
+        """The engine's own record of (clip_eps, value_scale, entropy_scale) (mi_ppo_loss_coefs)."""
+        out = (ctypes.c_float * 3)()
+        base = ctypes.addressof(out)
+        self.L.mi_ppo_loss_coefs(self.handle, base, base + 4, base + 8)
+        return float(out[0]), float(out[1]), float(out[2])
+
+    def dual_clip_stats(self, logp_new, logp_old, advantage, row_idx, M, clip_eps, dual_clip, stats, scratch, accumulate=False):
+        """The N_DUAL_CLIP_STATS sums of the dual-clip diagnostics (mi_ppo_dual_clip_stats; dual_clip_summary turns them into a dict) over rows `row_idx` (int32
+        device tensor [M]) of the tables logp_new (the logp_new_out table update_stats fills) / logp_old / advantage, into `stats` (float64 device tensor
+        [N_DUAL_CLIP_STATS]; accumulate: added to it).  scratch: float64 device tensor of dual_clip_scratch_doubles(M) entries.  Needs no engine."""
+        p = milib.ptr
+        self.L.mi_ppo_dual_clip_stats(self.stream(), p(logp_new), p(logp_old), p(advantage), p(row_idx), int(logp_new.shape[0]), int(M), float(clip_eps),
+                                      float(dual_clip), 1 if accumulate else 0, p(scratch), p(stats))
+
+    def dual_clip_scratch_doubles(self, M):
+        return int(self.L.mi_ppo_dual_clip_stats_scratch_doubles(int(M)))
 
     def engine_max_grad_norm(self):
         """The engine's own record of the limit (mi_ppo_max_grad_norm): 0.0 = off."""

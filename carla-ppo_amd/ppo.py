@@ -32,6 +32,17 @@ def _max_grad_norm_from_env():
         raise ValueError("MI355_PPO_MAX_GRAD_NORM=%r: expected a positive float or inf" % text) from None
 
 
+def _dual_clip_from_env():
+    """MI355_PPO_DUAL_CLIP (unset or empty: off) -> None or a float > 1 (inf included); anything else raises ValueError."""
+    text = os.environ.get("MI355_PPO_DUAL_CLIP", "").strip()
+    if not text:
+        return None
+    try:
+        return milib.dual_clip_value(float(text), "MI355_PPO_DUAL_CLIP=%r" % text)
+    except ValueError:
+        raise ValueError("MI355_PPO_DUAL_CLIP=%r: expected a float > 1 or inf" % text) from None
+
+
 def _wide_inputs_from_env():
     """MI355_PPO_WIDE_INPUTS (unset or empty: off) -> False for "0", True for "1"; anything else raises ValueError."""
     text = os.environ.get("MI355_PPO_WIDE_INPUTS", "").strip()
@@ -86,6 +97,9 @@ class PPO():
         # global-norm gradient clipping in front of Adam (set_max_grad_norm): None = off.  MI355_PPO_MAX_GRAD_NORM supplies it when set_max_grad_norm is not called
         # (the reference's train.py builds this object itself).  Not part of a checkpoint.
         self.max_grad_norm = _max_grad_norm_from_env()
+        # dual-clip PPO (set_dual_clip): the constant c > 1 that bounds the surrogate of a sample with a negative advantage and a large ratio; None = off.
+        # MI355_PPO_DUAL_CLIP supplies it when set_dual_clip is not called.  Not part of a checkpoint.
+        self.dual_clip = _dual_clip_from_env()
         # PPO2-style value-function clipping (set_value_clip): None = off.  No environment knob: only the rollout buffers record the old values a clipped step needs.
         # Not part of a checkpoint.
         self.value_clip = None
@@ -140,6 +154,7 @@ class PPO():
         self.dev = PpoDevice(self.input_dim, self.num_actions, self.action_low, self.action_high,
                              self.epsilon, self.value_scale, self.entropy_scale, precision=self.precision, wide_inputs=int(self.wide_inputs))
         self.dev.set_max_grad_norm(self.max_grad_norm)
+        self.dev.set_dual_clip(self.dual_clip)
         values = self._init_values or init_ppo(self.seed, self.input_dim, self.num_actions, self.initial_std)
         # policy_old is a separately initialised copy in the reference; the trainer overwrites it with
         # update_old_policy() before the first train() (train.py:192), so it starts as a copy of policy.
@@ -164,6 +179,28 @@ class PPO():
         self.max_grad_norm = milib.max_grad_norm_value(value, "PPO.set_max_grad_norm")
         if self.dev is not None:
             self.dev.set_max_grad_norm(self.max_grad_norm)
+
+    def set_dual_clip(self, c):
+        """Dual-clip PPO (Ye et al. 2020, eq. 5; include/mi355_carla.h, mi_ppo_set_dual_clip): with a constant c > 1 the surrogate of a sample with A < 0 is
+        max(min(r A, clip(r) A), c A) -- once the ratio of such a sample has grown past c its term is the constant c A and gives the policy no gradient, where the
+        clipped surrogate alone grows with r without bound.  None switches it off (the default), a float > 1 switches it on, inf runs the setting and never
+        dual-clips a sample.  Usable before or after init_session(); bool, str, NaN or a value <= 1 raise ValueError before anything touches a device.  train(),
+        train_step() and the rollout buffers' update() honour it without further inputs: the setting lives on the engine.  Fused kernels only: a step that would
+        take the per-layer path refuses while it is on.  Not part of a checkpoint."""
+        self.dual_clip = milib.dual_clip_value(c, "PPO.set_dual_clip")
+        if self.dev is not None:
+            self.dev.set_dual_clip(self.dual_clip)
+
+    def set_loss_coefficients(self, epsilon=None, value_scale=None, entropy_scale=None):
+        """Change the clip range, the value-loss scale and the entropy coefficient of a live model (mi_ppo_set_loss_coefs): a clip-range or entropy schedule that
+        keeps parameters, Adam state and tables.  None keeps a value; epsilon is a finite float > 0, value_scale and entropy_scale finite floats >= 0 -- bool, str,
+        NaN, inf or a value outside its range raise ValueError before anything changes or touches a device.  Updates the attributes epsilon, value_scale and
+        entropy_scale, and the device if there is one; every later step and statistics pass reads the new values."""
+        ce, vs, es = milib.loss_coef_values(self.epsilon if epsilon is None else epsilon, self.value_scale if value_scale is None else value_scale,
+                                            self.entropy_scale if entropy_scale is None else entropy_scale, "PPO.set_loss_coefficients")
+        if self.dev is not None:
+            self.dev.set_loss_coefs(ce, vs, es)
+        self.epsilon, self.value_scale, self.entropy_scale = ce, vs, es
 
     def set_wide_inputs(self, on=True):
         """Let the fused kernels take a policy of up to 1024 (padded) inputs instead of 96 -- a VAE of more than 93 latents: train_vae.py --z_dim 128, ConvVAE's own
@@ -305,6 +342,9 @@ class PPO():
         comm = None if world == 1 else self._dp_comm()
         handle = None if comm is None else comm.handle
         fused, kl = os.environ.get("MI355_PPO_FUSED", "1") != "0", self.kl_penalty is not None
+        if self.dual_clip is not None and not (fused and dev.fused_ok()):          # (asked only with the setting on: the per-layer path has no dual clip)
+            raise ValueError("PPO: dual clip (PPO.set_dual_clip) exists only in the fused kernels (this policy's shape is outside their range (more than 96 inputs: "
+                             "PPO.set_wide_inputs()) or MI355_PPO_FUSED=0)")
         if rows is not None or kl or old_values is not None:
             # (MI355_PPO_IDX is the in-kernel gather's switch; the value-clipped step without the penalty asks it with or without rows, as it always has)
             if not (fused and ((kl and rows is None) or os.environ.get("MI355_PPO_IDX", "1") != "0") and (world == 1 or comm is not None) and dev.fused_ok()):

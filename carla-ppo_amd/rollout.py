@@ -121,6 +121,22 @@ no atomics) and are read back with the epoch's other sums.  There is no environm
 with the setting on, and the policy must be on the fused kernels (ValueError otherwise, before anything is launched).  With the setting off the keys, launches and numbers
 are what they were.
 
+Both buffers honour dual-clip PPO (Ye et al. 2020; PPO.set_dual_clip(c), or MI355_PPO_DUAL_CLIP under the unchanged reference scripts).  Many epochs per collection,
+refreshed advantages and demonstration rows let the ratio r stray from 1, and the clipped surrogate of a sample with A < 0 and r > 1 + eps is r A, which grows with r
+without bound; with a constant c > 1 that sample's term becomes the constant c A once r has passed c, and it gives the policy no gradient.  The setting lives on
+the engine, so update() needs nothing new; update_with_diagnostics() also reports what it did:
+
+    ppo.set_dual_clip(3.0)                                         # float("inf"): the setting on, never a dual-clipped sample;  None: off
+    ppo.set_loss_coefficients(epsilon=0.1, entropy_scale=0.005)    # a clip-range / entropy schedule on the live engine: Adam state and tables stay
+    out = buf.update_with_diagnostics(num_epochs=10, batch_size=32)
+    for e in out["epochs"]:
+        print(e["dual_clip_fraction"], e["negative_advantage_fraction"], e["surrogate_mean"], e["surrogate_mean_unclipped"])
+
+The four keys come from one more small launch pair per statistics chunk (mi_ppo_dual_clip_stats over the log pi_theta table the statistics pass writes, the cached
+log pi_old and the advantage table the epoch's steps gathered from -- the minibatch table with per-minibatch normalisation; ordered double sums, no atomics) and are
+read back with the epoch's other sums.  The policy must be on the fused kernels (ValueError otherwise, before anything is launched).  With the setting off the keys,
+launches and numbers are what they were.
+
 Both buffers can scale the rewards by the running standard deviation of the discounted return, as every code base does that eps_v = 0.2 and max_grad_norm = 0.5 come
 from (baselines VecNormalize and its descendants).  eps_v, value_scale and the gradient norm are in units of the return, and CARLA's reward functions differ by orders of
 magnitude; the advantages are normalised already, the rewards -- and with them the returns, the value targets and the value net's gradients -- are not.  With
@@ -1484,6 +1500,9 @@ class RolloutBuffer:
         With ppo.value_clip set (PPO.set_value_clip), every dict of `epochs` also holds `value_clip_fraction`, `value_loss_clipped` and `value_grad_zero_fraction`
         (mi355.ppo_device.value_clip_summary): the statistics pass also writes V per table row, mi_ppo_value_clip_stats runs over the same chunks, and both sets of
         sums come back in the epoch's one readback.
+        With ppo.dual_clip set (PPO.set_dual_clip), every dict of `epochs` also holds `dual_clip_fraction`, `negative_advantage_fraction`, `surrogate_mean` and
+        `surrogate_mean_unclipped` (mi355.ppo_device.dual_clip_summary): the statistics pass also writes log pi_theta per table row, mi_ppo_dual_clip_stats runs over
+        the same chunks on it, the cached log pi_old and the advantage table the epoch's steps gathered from, and its sums come back in the same readback.
         With reward scaling on (set_reward_scaling) the returns table holds returns of the SCALED rewards: value_mse and explained_variance are measured on those.
         With advantage recomputation on (set_advantage_recomputation) the returns table holds, from epoch 2 on, the REFRESHED returns of that epoch: value_mse and
         explained_variance are measured against those.
@@ -1569,6 +1588,9 @@ class RolloutBuffer:
                              "MI355_PPO_FUSED=0)")
         if klp is not None and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update: the KL penalty (PPO.set_kl_penalty) exists only in the fused kernels (this policy's shape is outside their range (more than 96 inputs: PPO.set_wide_inputs()) or "
+                             "MI355_PPO_FUSED=0)")
+        if getattr(self.ppo, "dual_clip", None) is not None and not self.ppo._need_dev().fused_ok():
+            raise ValueError(who + ".update: dual clip (PPO.set_dual_clip) exists only in the fused kernels (this policy's shape is outside the fused range (more than 96 inputs: PPO.set_wide_inputs()) or "
                              "MI355_PPO_FUSED=0)")
         if getattr(self, "_adv_recompute", False) and not self.ppo._need_dev().fused_ok():
             raise ValueError(who + ".update: advantage recomputation (set_advantage_recomputation) exists only in the fused kernels (this policy's shape is outside the fused range (more than 96 inputs: PPO.set_wide_inputs()) or "
@@ -1708,13 +1730,14 @@ class RolloutBuffer:
             db = u.demo["buffer"]
             u.demo_coef, u.demo_records, u.demo_rows = u.demo["coef"], [], []
             steps_per_epoch, md = -(-n_valid // batch_size), min(u.demo["batch_size"], db.size)
-        observe = self._stats_pass(u) if u.diag is not None else None
         adv_table = self.advantages                                                  # the table the steps gather their advantage from
         if u.mbn is not None:
             if getattr(self, "_minibatch_advantages", None) is None:
                 self._minibatch_advantages = torch.zeros(self.n_table_rows, device=device)
             adv_table = self._minibatch_advantages
             u.mb_stats = torch.zeros(u.num_epochs, -(-n_valid // batch_size), 3, dtype=torch.float64, device=device)
+        u.adv_table = adv_table                                                      # (the dual-clip diagnostics read the advantages the steps read)
+        observe = self._stats_pass(u) if u.diag is not None else None
         for epoch in range(u.num_epochs):
             if u.recompute is not None and epoch > 0:                                # every later epoch that runs: values, returns and advantages under the current parameters
                 u.recompute()
@@ -1796,13 +1819,23 @@ class RolloutBuffer:
 
     def _stats_pass(self, u):
         """The statistics pass of update_with_diagnostics -> observe(): the pass over all valid rows in chunks of 4096 and the epoch's one readback -> the epoch's dict.
-        With value clipping on the pass also writes V per table row (_values_new), mi_ppo_value_clip_stats runs over the same chunks, and its sums sit behind the others."""
+        With value clipping on the pass also writes V per table row (_values_new), mi_ppo_value_clip_stats runs over the same chunks, and its sums sit behind the others.
+        With dual clip on (PPO.set_dual_clip) it also writes log pi_theta per table row (_logp_new), mi_ppo_dual_clip_stats runs over the same chunks on that table, the
+        cache of log pi_old and the advantage table the epoch's steps gathered from (the minibatch table with per-minibatch normalisation), and its sums come last."""
         import torch
-        from mi355.ppo_device import N_STATS, N_VCLIP_STATS, update_stats_summary, value_clip_summary
+        from mi355.ppo_device import N_DUAL_CLIP_STATS, N_STATS, N_VCLIP_STATS, dual_clip_summary, update_stats_summary, value_clip_summary
         pdev, device, vclip, chunk = self.ppo._need_dev(), self.device, u.vclip, 4096
+        dual = getattr(self.ppo, "dual_clip", None)
         valid_dev = torch.from_numpy(u.valid).to(device)
-        sums = torch.zeros(N_STATS + (0 if vclip is None else N_VCLIP_STATS), dtype=torch.float64, device=device)
-        stats, vstats, value_out = sums[:N_STATS], sums[N_STATS:], None
+        n_v = 0 if vclip is None else N_VCLIP_STATS
+        sums = torch.zeros(N_STATS + n_v + (0 if dual is None else N_DUAL_CLIP_STATS), dtype=torch.float64, device=device)
+        stats, vstats, dstats, value_out = sums[:N_STATS], sums[N_STATS:N_STATS + n_v], sums[N_STATS + n_v:], None
+        stats_kw = {}
+        if dual is not None:
+            dscratch = torch.empty(pdev.dual_clip_scratch_doubles(min(u.n_valid, chunk)), dtype=torch.float64, device=device)
+            if getattr(self, "_logp_new", None) is None:
+                self._logp_new = torch.zeros(self.n_table_rows, device=device)
+            stats_kw["logp_new_out"] = self._logp_new
         if vclip is not None:
             vscratch = torch.empty(pdev.value_clip_scratch_doubles(min(u.n_valid, chunk)), dtype=torch.float64, device=device)
             if getattr(self, "_values_new", None) is None:
@@ -1814,13 +1847,17 @@ class RolloutBuffer:
             for lo in range(0, u.n_valid, chunk):
                 rows = valid_dev[lo:lo + chunk]
                 pdev.update_stats(self.states, self.actions, self.returns, self.logp_old, rows, int(rows.numel()), stats, stats_scratch, accumulate=lo > 0,
-                                  value_out=value_out)
+                                  value_out=value_out, **stats_kw)
                 if vclip is not None:
                     pdev.value_clip_stats(value_out, self.values, self.returns, rows, int(rows.numel()), vclip, vstats, vscratch, accumulate=lo > 0)
+                if dual is not None:
+                    pdev.dual_clip_stats(self._logp_new, self.logp_old, u.adv_table, rows, int(rows.numel()), self.ppo.epsilon, dual, dstats, dscratch, accumulate=lo > 0)
             both = sums.cpu().numpy()                                                # the epoch's one readback
             epoch = update_stats_summary(both[:N_STATS])
             if vclip is not None:
-                epoch.update(value_clip_summary(both[N_STATS:]))
+                epoch.update(value_clip_summary(both[N_STATS:N_STATS + n_v]))
+            if dual is not None:
+                epoch.update(dual_clip_summary(both[N_STATS + n_v:]))
             return epoch
         return observe
 

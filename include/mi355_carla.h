@@ -625,7 +625,8 @@ void* mi_ppo_buffer(void* h, int which);
 int mi_ppo_update_old(void* h, void* stream);
 /* PPO.predict — ppo.py:231-251.  mi_ppo_buffer(h, 0): losses of the last step: [policy, value, entropy, total, mean ratio, mean action_mean[A], std[A]] (the
  * scalars of ppo.py:150-163); mi_ppo_buffer(h, 1): action_mean [M,A] of the last predict / train step; mi_ppo_buffer(h, 3): the step's workspace dv [M], the
- * gradient of the loss with respect to each sample's value-head output as the last step formed it (exactly 0 where value clipping stops it) */
+ * gradient of the loss with respect to each sample's value-head output as the last step formed it (exactly 0 where value clipping stops it); mi_ppo_buffer(h, 5): likewise du [M, A], the gradient with respect to each sample's
+ * action-mean head outputs (exactly 0 on a dual-clipped sample with the KL penalty off: mi_ppo_set_dual_clip) */
 int mi_ppo_predict(void* h, void* stream, const float* states, int M, const float* noise, int greedy, float* action, float* value);
 /* gradient half + optimiser half of PPO.train (= north_star "learn") — ppo.py:218-229.  Both paths of mi_ppo_forward_backward are bitwise reproducible: the
  * per-layer one (shapes outside the fused range, MI355_PPO_FUSED=0) adds the row splits of its filter and bias gradients in a fixed order (mi_gemm_wgrad_bias_ws on
@@ -722,6 +723,40 @@ int mi_ppo_update_stats_idx(void* h, void* stream, const float* states, const fl
 int mi_ppo_set_max_grad_norm(void* h, float max_norm);
 float mi_ppo_max_grad_norm(void* h);
 int mi_ppo_grad_norm(void* h, void* stream, float max_norm);
+/* Dual-clip PPO (Ye et al. 2020, "Mastering Complex Control in MOBA Games with Deep Reinforcement Learning", eq. 5): a bound on the one side the clipped
+ * surrogate leaves open.  With r = pi_theta / pi_old, A the advantage, eps = clip_eps, s = min(r A, clamp(r, 1 - eps, 1 + eps) A) the surrogate of ppo.py:112-132
+ * and a constant c > 1, the per-sample surrogate of the fused head / loss kernel becomes
+ *   s' = (A < 0 && c A > s) ? c A : s                      tf.maximum(s, c A) on the samples with A < 0: on a tie s keeps the gradient
+ * A sample in the first branch is "dual-clipped": c A does not depend on theta, so its surrogate contributes exactly 0.0 to du and to dlogstd (dr = 0, as on the
+ * clipped branch), and the policy-loss partial takes c A.  A sample with A >= 0, -0.0 included, never takes the branch.  The KL penalty's own gradient terms, the
+ * value side, the entropy term and demonstration rows are not touched.  c = +inf never takes the branch: every stored bit equals the plain step's.
+ * mi_ppo_set_dual_clip: c = 0 switches the setting off (the default of a new engine), c > 1 -- finite or +inf -- switches it on; anything else (NaN, a negative
+ * value, a value in (0, 1]) is MI_ERR_ARG and leaves the setting as it was; MI_ERR_STATE for a null handle.  Handle state, like mi_ppo_set_max_grad_norm.  On,
+ * every fused step entry uses it -- mi_ppo_train_step / _idx / _dp / _vclip / _kl / _demo and mi_ppo_forward_backward where it runs the fused chain -- with the
+ * launches, routes and reproducibility of the plain step, in both precision modes; mi_ppo_clone_step has no ratio and ignores it.  The per-layer path has no dual
+ * clip: with the setting on, an engine for which mi_ppo_fused_shape_ok(h) is 0 refuses mi_ppo_forward_backward (and mi_ppo_train_step / _dp, which run it) with
+ * MI_ERR_SHAPE in front of the first launch, nothing written -- the way it refuses MI_BF16X3.  (mi_ppo_loss_fwd_bwd, the per-layer loss kernel, takes no handle and
+ * has no dual-clip argument.)
+ * mi_ppo_dual_clip: the current setting (0 = off); -1 for a null handle.
+ * mi_ppo_set_loss_coefs: replaces the descriptor's clip_eps, value_scale and entropy_scale on a live engine -- a clip-range or entropy-coefficient schedule without
+ * giving up the optimiser state.  Every later call reads the new values: the steps, mi_ppo_update_stats_idx's clipped fraction, the per-layer path.  clip_eps finite
+ * and > 0, value_scale and entropy_scale finite and >= 0; anything else is MI_ERR_ARG and changes nothing.  mi_ppo_loss_coefs fills the three current values.
+ * mi_ppo_dual_clip_stats: the diagnostics, without an engine, in the mould of mi_ppo_value_clip_stats: over the M rows row_idx[m] (int32, device; clamped into
+ * [0, n_rows)) of three fp32 tables -- logp_new (log pi_theta(a | s): the logp_new_out table mi_ppo_update_stats_idx writes), logp_old (the cached log pi_old),
+ * advantage (the table the steps gathered from) -- the sums
+ *   [0] 1 (the count)   [1] 1 where A < 0   [2] 1 where the sample is dual-clipped   [3] s'   [4] s
+ * into stats [MI_PPO_N_DUAL_CLIP_STATS] (double, device).  A sample's class is formed in fp32 exactly as the step forms it (r = __expf(lp - lp_old), then the
+ * step's operations), so the counts say what a step on these tables does; the sums [3] and [4] are formed in double from the fp32 inputs.  dual_clip > 1 or +inf,
+ * clip_eps finite and > 0.  Ordered: every block of 256 samples stores its sums to scratch (mi_ppo_dual_clip_stats_scratch_doubles(M) doubles, device), one wave
+ * adds them in block order; no atomics, two runs are bitwise equal.  accumulate 0: stats is overwritten, 1: added to.  Rows not named are not read; nothing but
+ * scratch and stats is written.  MI_ERR_ARG: M < 1, n_rows < 1, a missing buffer, clip_eps or dual_clip outside their ranges, accumulate not 0 / 1. */
+#define MI_PPO_N_DUAL_CLIP_STATS 5
+int mi_ppo_set_dual_clip(void* h, float c);
+float mi_ppo_dual_clip(void* h);
+int mi_ppo_set_loss_coefs(void* h, float clip_eps, float value_scale, float entropy_scale);
+int mi_ppo_loss_coefs(void* h, float* clip_eps, float* value_scale, float* entropy_scale);
+long long mi_ppo_dual_clip_stats_scratch_doubles(int M);
+int mi_ppo_dual_clip_stats(void* stream, const float* logp_new, const float* logp_old, const float* advantage, const int* row_idx, int n_rows, int M, float clip_eps, float dual_clip, int accumulate, double* scratch, double* stats);
 /* PPO2-style value-function clipping (the clipped value loss of baselines ppo2; clip_vloss / clip_range_vf of other PPO implementations) -- the value term of
  * ppo.py:112-132.  Per sample, with V the value head's output under theta, V_old = old_values[row] the value recorded when the data was collected, R the return and
  * eps_v = clip_range_vf > 0:

@@ -12,7 +12,12 @@ entry points have the same prototypes in both.
 
 Expectations (recorded, not enforced): no variant exceeds its twin from the other build by more than the allowance, the larger of 2 % and the plain step's own
 spread; the clone step with returns stays within the allowance of the plain step, and policy-only below it; the demonstration step is faster than the two calls by
-more than the allowance (summary: one_chain_pays)."""
+more than the allowance (summary: one_chain_pays).
+
+Dual clip (profiles/r42_dual_clip.md): this build's plain step also runs on a second engine of this build with mi_ppo_set_dual_clip(3) on -- the column
+`plain_dual_clip`, the same rows, so no sample is dual-clipped and the kernel's extra compare and multiply are all that differs -- and with a parent library
+the parent's plain step gets its second window too: summary.plain_vs_parent holds this build's plain step (setting off) minus the parent's, the parent's own
+difference between its two windows, and whether the first stays within twice the second."""
 import ctypes
 import json
 import os
@@ -55,15 +60,17 @@ class Build:
     NAMES = ("mi_ppo_workspace_bytes", "mi_ppo_create", "mi_ppo_destroy", "mi_ppo_train_step", "mi_ppo_clone_step", "mi_ppo_train_step_kl",
              "mi_ppo_update_stats_idx", "mi_ppo_kl_stats_idx", "mi_ppo_logp_old")
 
-    def __init__(self, path=None):
-        """path None: this tree's library on d's engine; else another build, on an engine of its own (buffers, workspace) holding d's parameters."""
+    def __init__(self, path=None, dual_clip=None):
+        """path None: this tree's library on d's engine; else another build, on an engine of its own (buffers, workspace) holding d's parameters.  dual_clip: this
+        tree's library on an engine of its own with mi_ppo_set_dual_clip(dual_clip) on."""
         self.path = path
-        if path is None:
+        self.own = path is not None or dual_clip is not None
+        if not self.own:
             self.cdll, self.handle, self.bufs = d.L.cdll, d.handle, [d.params, d.params_old, d.grads, d.adam_m, d.adam_v]
         else:
-            self.cdll = ctypes.CDLL(path)
+            self.cdll = ctypes.CDLL(path) if path is not None else d.L.cdll
             protos = milib.parse_header()
-            for name in self.NAMES:                          # (prototypes of this tree's header: the same in both builds)
+            for name in self.NAMES if path is not None else ():      # (prototypes of this tree's header: the same in both builds)
                 fn = getattr(self.cdll, name)
                 fn.restype, fn.argtypes = milib._CTYPES[protos[name][0]], [milib._CTYPES[t] for t, _ in protos[name][1]]
             desc = d._desc(MAXB)
@@ -72,7 +79,9 @@ class Build:
             self.ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
             self.handle = self.cdll.mi_ppo_create(ctypes.byref(desc), *[p(x) for x in self.bufs], p(self.ws), nbytes, low.ctypes.data, high.ctypes.data)
             if not self.handle:
-                raise RuntimeError("mi_ppo_create failed in " + path)
+                raise RuntimeError("mi_ppo_create failed in " + (path or "this build"))
+            if dual_clip is not None and self.cdll.mi_ppo_set_dual_clip(self.handle, ctypes.c_float(dual_clip)) != 0:
+                raise RuntimeError("mi_ppo_set_dual_clip failed")
         self.state = [x.clone() for x in self.bufs]
 
     def restore(self):
@@ -85,8 +94,12 @@ class Build:
             raise RuntimeError("%s failed (%d) in %s" % (name, rc, self.path or "this build"))
 
     def close(self):
-        if self.path is not None:
+        if self.own:
             self.cdll.mi_ppo_destroy(self.handle)
+
+    def plain(self, t, M):
+        st = d.stream()
+        return lambda: self.call("mi_ppo_train_step", st, p(t["s"]), p(t["a"]), p(t["R"]), p(t["adv"]), p(t["lp"]), M, 1.0 / M, 1.0, *ADAM)
 
     def variants(self, t, M, with_stats):
         """name -> call, on the tensors t."""
@@ -137,6 +150,7 @@ def ab(variants, iters, rounds=9, warm=100):
 
 
 this = Build()
+dual = Build(dual_clip=3.0)
 other = Build(PARENT) if PARENT else None
 out = {"parent_lib": bool(PARENT)}
 for M, iters in ((32, 2000), (2048, 300)):
@@ -148,8 +162,9 @@ for M, iters in ((32, 2000), (2048, 300)):
          "ds": up(0.5 * rng.standard_normal((M_DEMO[M], DIN))), "da": up(rng.uniform(0, 1, (M_DEMO[M], A)))}
     d.old_policy_cache(t["s"], t["a"], M, t["lp"], t["mo"])
     variants = dict(this.variants(t, M, M == 2048))
-    if other is not None:                                    # the twins, interleaved with this build's windows (no second window of the plain step)
-        variants.update({k + "_parent": fn for k, fn in other.variants(t, M, M == 2048).items() if k != "plain_b"})
+    variants["plain_dual_clip"] = dual.plain(t, M)
+    if other is not None:                                    # the twins, interleaved with this build's windows
+        variants.update({k + "_parent": fn for k, fn in other.variants(t, M, M == 2048).items()})
     res = ab(variants, iters)
     base = res["plain_a_parent" if other is not None else "plain_a"]["median"]
     spread = abs(res["plain_a"]["median"] - res["plain_b"]["median"]) / base
@@ -166,11 +181,18 @@ for M, iters in ((32, 2000), (2048, 300)):
     res["summary"]["demo_over_two_calls"] = res["demo"]["median"] / two - 1.0
     res["summary"]["one_chain_pays"] = bool(res["demo"]["median"] < two * (1.0 - allow))
     if other is not None:
-        over = {k: res[k]["median"] / res[("plain_a" if k == "plain_b" else k) + "_parent"]["median"] - 1.0 for k in variants if not k.endswith("_parent") and k != "demo"}
+        over = {k: res[k]["median"] / res[k + "_parent"]["median"] - 1.0 for k in variants if not k.endswith("_parent") and k not in ("demo", "plain_dual_clip")}
         res["summary"]["over_parent_twin"] = over
         res["summary"]["all_within_allowance_of_parent"] = all(v <= allow for v in over.values())
+        # the timing condition of profiles/r42_dual_clip.md: both windows of each build together (the mean of the two medians), in us
+        mine, theirs = (0.5 * (res["plain_a" + x]["median"] + res["plain_b" + x]["median"]) for x in ("", "_parent"))
+        parent_diff = abs(res["plain_a_parent"]["median"] - res["plain_b_parent"]["median"])
+        res["summary"]["plain_vs_parent"] = {"this_minus_parent_us": mine - theirs, "parent_two_runs_differ_us": parent_diff,
+                                             "within_twice_the_parents_difference": bool(mine - theirs <= 2.0 * parent_diff)}
+    res["summary"]["dual_clip_over_plain"] = res["plain_dual_clip"]["median"] / (0.5 * (res["plain_a"]["median"] + res["plain_b"]["median"])) - 1.0
     out["step_M%d" % M] = res
     this.restore()
+    dual.restore()
     if other is not None:
         other.restore()
 
@@ -184,4 +206,5 @@ for k, v in out.items():
         print("   %-28s %s" % (kk, "median %9.2f us  min %9.2f  max %9.2f" % (vv["median"], vv["min"], vv["max"]) if "median" in vv else json.dumps(vv)))
 if other is not None:
     other.close()
+dual.close()
 d.close()
